@@ -267,6 +267,35 @@ def hdf5_loop_leg(ra, synth, rows, files=6, per_file=262144):
         shutil.rmtree(tmp, ignore_errors=True)
 
 
+DUMP_BUDGET_BYTES = 60 << 20      # parameters; the loss files and the .npy headers stay well inside the remaining 4 MB of the 64 MB cap
+DUMP_SEED = 0x5EED
+
+
+def dump_outputs(model, losses, weight_sums, out_dir):
+    """--dump-outputs: what the timed step leaves its caller after the last step of the replay in main(), one .npy per array -- the four
+    losses and their weight sums (float64), every trainable parameter after the clip + AdamW update (float32; the frozen metadata table
+    is an input).
+    A tensor larger than its share of the budget is written as a fixed sample: its flattened elements at sorted indices drawn from a seed
+    and the tensor's name, the same in every run, so that two builds run with the same arguments can be compared array for array."""
+    import zlib
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "losses.npy"), np.asarray(losses, np.float64))
+    np.save(os.path.join(out_dir, "loss_weight_sums.npy"), np.asarray(weight_sums, np.float64))
+    params = [(n, shape) for n, shape, trainable in model.named_parameters() if trainable]
+    cap = DUMP_BUDGET_BYTES // (4 * len(params))
+    n_bytes, n_sampled = 0, 0
+    for n, _ in params:
+        w = model.get_parameter(n)
+        if w.size > cap:
+            idx = np.random.default_rng([DUMP_SEED, zlib.crc32(n.encode())]).choice(w.size, cap, replace=False)
+            w = w.reshape(-1)[np.sort(idx)]
+            n_sampled += 1
+        np.save(os.path.join(out_dir, n + ".npy"), w)
+        n_bytes += w.nbytes
+    return {"dir": out_dir, "arrays": len(params) + 2, "MB": round(n_bytes / 1e6, 2), "sampled_tensors": n_sampled,
+            "sample": f"tensors over {cap} elements: {cap} flat elements at sorted seeded indices"}
+
+
 def _lib_switches():
     """RSYS_* environment switches in effect that differ from the library's defaults (csrc/switches.hpp)"""
     from recommendersystem_amd import _lib
@@ -411,7 +440,13 @@ def main():
                          "under the trunk backward, the batch's token rows as gathered lists in the tail (DESIGN 7)")
     ap.add_argument("--rehearse-comm", action="store_true",
                     help="1 GPU only: issue the RCCL gradient all-reduce at world size 1 (what the data-parallel step enqueues)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the measurements, replay the run's steps from the same initial state (all but the last in the fixed-order "
+                         "arithmetic) and write the last step's losses and updated parameters (rank 0's) as DIR/<name>.npy, at most 64 MB: "
+                         "large tensors as a fixed seeded sample")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # plain `python bench.py --gpus N`: this process has made no GPU call (it has not even loaded the library); it starts
@@ -643,6 +678,33 @@ def main():
     elif comm is not None:
         comm_info = {"kind": type(comm).__name__, "ranks": world}
 
+    dumped = None
+    if args.dump_outputs:
+        # The default step sums with float atomics, so the state the last timed step started from depends on the order in which the
+        # earlier steps' atomics landed, and AdamW compounds those last-bit differences step after step.  The dump therefore replays this
+        # run's steps on the re-initialised model, outside every measurement: all but the last in the fixed-order arithmetic
+        # (rsys_model_set_deterministic), so that the last step starts from the same bits in every run, and the last one as it was timed.
+        model.init_weights(0x1217)
+        model.random_pretrained_embeddings(0x3E7A)
+        opt.close()
+        opt = ra.create_optimizer(model, cfg)
+        if zero1:
+            opt.enable_zero1(comm)
+        sched = LambdaLR(WSDScheduler(warmup_steps=2000, total_steps=250000, decay_ratio=0.1, final_ratio=0.1))
+        for _ in range(2000):
+            sched.step()
+        model._step = 0                        # the step index seeds the token masks: the same masks as the timed run, step for step
+        model.upload(d)
+        model.set_deterministic(True)
+        for _ in range(args.warmup + args.steps - 1):
+            step()
+        model.set_deterministic(bool(args.deterministic))
+        step()
+        ra.synchronize()
+        if rank == 0:
+            dumped = dump_outputs(model, model.losses(False), model.last_weight_sums, args.dump_outputs)
+            dumped["replay"] = f"{args.warmup + args.steps - 1} fixed-order steps, then the last step on the timed path"
+
     if rank == 0:
         inter = world * rows * S * args.steps
         value = inter / elapsed
@@ -734,6 +796,8 @@ def main():
             "roofline": roofline,
             "losses": [round(float(x), 4) for x in losses],
         }
+        if dumped is not None:
+            out["dump_outputs"] = dumped
         if args.dtype in ("fp8", "float8"):
             out["dtype_note"] = ("bf16 arithmetic with the transformer blocks' linears (forward, dx, dW) on tensor-wise dynamically scaled e4m3 / e5m2 "
                                  "operands: the reference's pretraining arithmetic (transformer.py:671-676, torchao 'tensorwise'), restated -- parity "

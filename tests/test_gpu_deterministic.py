@@ -318,3 +318,25 @@ def test_benchmark_size_attention_backward_is_bitwise_reproducible():
     finally:
         for p in held:
             lib.rsys_dev_free(p)
+
+
+def test_bench_dump_outputs_agree_between_two_runs(tmp_path):
+    """bench.py --dump-outputs, run twice with the same arguments: the replayed steps before the last are bitwise reproducible, so the
+    last one (on the timed path, float atomics included) starts from the same bits and its outputs agree to float-atomic noise -- where
+    the last timed step itself, after the atomics of every earlier step had compounded through AdamW, moved some weights by percents."""
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    runs = []
+    for k in range(2):
+        out = tmp_path / str(k)
+        subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--config", "cfg2", "--steps", "4", "--warmup", "2", "--no-cpu-baseline",
+                        "--no-kernel-timing", "--no-train-loop", "--no-extra-legs", "--dump-outputs", str(out)],
+                       check=True, cwd=root, timeout=600, stdout=subprocess.DEVNULL)
+        runs.append({f.name: np.load(f) for f in out.iterdir()})
+    assert runs[0].keys() == runs[1].keys() and len(runs[0]) > 80
+    np.testing.assert_allclose(runs[0]["losses.npy"], runs[1]["losses.npy"], rtol=1e-5)
+    for name, a in runs[0].items():
+        b = runs[1][name]
+        assert np.isfinite(a).all() and np.abs(a - b).max() <= 1e-4 * np.abs(a).max(), (name, float(np.abs(a - b).max()), float(np.abs(a).max()))

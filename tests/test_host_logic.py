@@ -264,6 +264,46 @@ def test_prefetch_keeps_order_propagates_errors_and_stops_early():
     assert overlapped < 0.8 * serial, (overlapped, serial)
 
 
+def test_bench_dump_outputs_is_bounded_and_reproducible(tmp_path):
+    """bench.py --dump-outputs on cfg-3's parameter list: only float32 / float64 .npy files, at most 64 MB in all, whole small tensors,
+    the same seeded sample of every large one (flat indices in order) in two runs, frozen tensors left out."""
+    import bench
+    from oracle import synth
+    from recommendersystem_amd import workload
+
+    shapes = synth.param_shapes(workload.make_config("cfg3"))
+
+    class StandIn:      # the two calls dump_outputs makes on a RecommenderModel; a parameter's values are its flat indices
+        def named_parameters(self):
+            return [(n, s, "metadata_embedding" not in n) for n, s in shapes.items()]
+
+        def get_parameter(self, n):
+            return np.arange(int(np.prod(shapes[n])), dtype=np.float32).reshape(shapes[n])
+
+    runs = []
+    for k in range(2):
+        info = bench.dump_outputs(StandIn(), [1.5, 2.5, 3.5, 4.5], [6.0, 7.0, 8.0, 9.0], str(tmp_path / str(k)))
+        files = sorted((tmp_path / str(k)).iterdir())
+        assert len(files) == info["arrays"] == 2 + sum(1 for n in shapes if "metadata_embedding" not in n)
+        assert sum(f.stat().st_size for f in files) <= 64 << 20
+        runs.append({f.name: np.load(f) for f in files})
+    assert info["sampled_tensors"] > 0
+    assert runs[0].keys() == runs[1].keys()
+    for name, a in runs[0].items():
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, runs[1][name]), name
+    np.testing.assert_array_equal(runs[0]["losses.npy"], [1.5, 2.5, 3.5, 4.5])
+    for n, s in shapes.items():
+        if "metadata_embedding" in n:
+            assert n + ".npy" not in runs[0]
+            continue
+        a = runs[0][n + ".npy"]
+        if a.shape == tuple(s):
+            assert np.array_equal(a.reshape(-1), np.arange(a.size, dtype=np.float32)), n
+        else:
+            # (indices beyond 2**24 round in float32: in order, not necessarily distinct, as values)
+            assert a.ndim == 1 and a.size < np.prod(s) and (np.diff(a) >= 0).all() and 0 <= a[0] and a[-1] <= np.prod(s), n
+
+
 def test_bench_attention_density_counts_same_user_pairs():
     import os
     import sys
