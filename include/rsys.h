@@ -131,6 +131,23 @@ int32_t rsys_head_rows_get(rsys_model* m, int32_t out[4]);
 /* ItemEmbedding.forward over all items (model.py:139-145), the table Finetune/register.py:27-33 exports as the watch-head
  * weights of the serving registry: out [V][embed_dim] f32, V = vocab_0 + vocab_1 (manga rows first) */
 int32_t rsys_item_table(rsys_model* m, float* out, int64_t n);
+/* Retrieval candidates for a batch of query embeddings (Finetune/embed.jl:86-90 + the scoring, masking and sort of
+ * Inference/render.jl:240-333), on the model's fused item table of `medium` (the tied watch head, model.py:148-170).
+ * Ids are medium-local, in [0, V_m) (V_m = vocab_0 or vocab_1).  z_q[i] = F_m[i] . u_q accumulated in fp32 on operands of the model's
+ * compute dtype (bf16 mode: the query rounded to bf16, the bf16 table copy); lse_q = log sum_{i < V_m} exp z_q[i] over every item;
+ * score_g[i] = prior_g[i] + sum over the queries q of group g, in query order, of (z_q[i] - lse_q).  Excluded from group g: the ids of
+ * its exclusion list (duplicates allowed) and ids whose score is -inf or NaN; -0.0 ranks as +0.0.  Output per group: the min(k,
+ * admissible) best ids by descending score, ties by ascending id (render.jl's stable sortperm(p, rev=true) without the -Inf entries),
+ * counts_out[g] = that number, the slots after it id -1 and score -inf.  1 <= n_queries <= 4096, 1 <= k <= min(V_m, 8192), every group
+ * needs a query, replicated table only.  Works without an uploaded batch (rebuilds the fused table when stale) and changes no model
+ * state; synchronous, bitwise reproducible; the device workspace grows on demand and is freed with the model. */
+int32_t rsys_retrieve_topk(rsys_model* m, int32_t medium,
+                           const float* queries, int64_t n_queries,          /* [n_queries][embed_dim] f32, host */
+                           const int32_t* group, int32_t n_groups,           /* [n_queries] in [0, n_groups), or NULL: group = query */
+                           const float* prior,                               /* [n_groups][V_m] f32 added to the score, or NULL */
+                           const int64_t* excl_offsets, const int32_t* excl_ids, /* CSR over groups of medium-local ids, or both NULL */
+                           int32_t k, int32_t* ids_out, float* scores_out,   /* [n_groups][k] each */
+                           int32_t* counts_out);                             /* [n_groups] */
 /* on != 0: every float sum of the training step gets a fixed order (split-K partial tiles summed in split order, reductions through
  * per-workgroup partials instead of float atomics), so a step -- losses, gradients, updated parameters -- is bitwise reproducible
  * from run to run; costs a few percent of the step.  Replicated or row-sharded table, full or sampled soft-max.  (The reference's CUDA path is not reproducible:

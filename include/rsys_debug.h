@@ -59,6 +59,11 @@ int32_t rsys_op_gemm_klimit(int32_t dtype, const void* A, const void* B, void* C
 int32_t rsys_op_attention(int32_t dtype, int32_t B, int32_t T, int32_t H, int32_t KV, int32_t hd, const void* qkv,
                           const int32_t* uid, const int32_t* tm, void* O, float* lse, const void* dO, void* dqkv,
                           const float* rope_cos, const float* rope_sin);
+/* the selection of rsys_retrieve_topk alone, on caller-provided device buffers: per row r of scores [rows][ld >= V] the min(k, admissible)
+ * best columns by descending value, ties by ascending column, -inf / NaN excluded, -0.0 == +0.0; ids / vals [rows][k] (padding -1 / -inf),
+ * counts [rows]; 1 <= k <= min(V, 8192) */
+int32_t rsys_op_topk(const float* scores, int64_t ld, int32_t rows, int32_t V, int32_t k,
+                     int32_t* ids, float* vals, int32_t* counts);
 /* embedding-gradient scatter of the backward (nn.Embedding backward, model.py:21) on caller-provided device buffers:
  * gE[id'] += sum over tokens n of gx0[n*ldx .. +D) with id' = m_matchedid[n] (-1 -> row V); matchedid = the raw ids the
  * token index is built from (m_matchedid differs from it only where it is -1).  One writer per table row, fixed summation

@@ -195,6 +195,22 @@ function item_table(m::Model, V::Integer, D::Integer)  # register.py:27-33: (D, 
     out = Matrix{Float32}(undef, D, V)
     GC.@preserve out check(ccall((:rsys_item_table, LIB), Int32, (Ptr{Cvoid}, Ptr{Float32}, Int64), m.h, out, length(out))); out
 end
+# retrieval candidates on the device (Finetune/embed.jl:86-90 + Inference/render.jl:240-333's scoring, masking and sortperm): Q is
+# (D, n_queries) column-major = (n_queries, D) row-major; `group` (0-based, one per query) or nothing (each query its own group); `prior`
+# (V_m, n_groups) or nothing; `excl` one Vector{Int32} of 0-based medium-local ids per group, or nothing.  Returns (ids, scores, counts):
+# (k, n_groups) 0-based medium-local ids (-1 past counts[g]), their scores (-Inf past counts[g]), admissible count per group.
+function retrieve_topk(m::Model, medium::Integer, Q::Matrix{Float32}, k::Integer; group = nothing, n_groups::Integer = size(Q, 2),
+                       prior = nothing, excl = nothing)
+    g = group === nothing ? Ptr{Int32}(C_NULL) : Vector{Int32}(group)
+    p = prior === nothing ? Ptr{Float32}(C_NULL) : Matrix{Float32}(prior)
+    off = excl === nothing ? Ptr{Int64}(C_NULL) : Int64[0; cumsum(Int64[length(e) for e in excl])]
+    xid = excl === nothing ? Ptr{Int32}(C_NULL) : Int32[reduce(vcat, excl; init = Int32[])...]
+    ids = Matrix{Int32}(undef, k, n_groups); scores = Matrix{Float32}(undef, k, n_groups); counts = Vector{Int32}(undef, n_groups)
+    GC.@preserve Q g p off xid ids scores counts check(ccall((:rsys_retrieve_topk, LIB), Int32,
+        (Ptr{Cvoid}, Int32, Ptr{Float32}, Int64, Ptr{Int32}, Int32, Ptr{Float32}, Ptr{Int64}, Ptr{Int32}, Int32, Ptr{Int32}, Ptr{Float32}, Ptr{Int32}),
+        m.h, medium, Q, size(Q, 2), g, n_groups, p, off, xid, k, ids, scores, counts))
+    ids, scores, counts
+end
 function infer(m::Model, task::Integer, rows::Integer, S::Integer, D::Integer)   # model.py:531-538 over every token of the resident batch
     out = task == 0 ? Array{Float32}(undef, D, 2S, rows) : Array{Float32}(undef, 2S, rows)
     GC.@preserve out check(ccall((:rsys_infer, LIB), Int32, (Ptr{Cvoid}, Int32, Ptr{Float32}, Int64), m.h, task, out, length(out))); out

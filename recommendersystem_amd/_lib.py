@@ -73,6 +73,7 @@ _SIGS = [
     ("rsys_losses_drain", C.c_int32, [_P, _P, _P, C.c_int32, C.POINTER(C.c_int32)]),
     ("rsys_head_rows_get", C.c_int32, [_P, C.POINTER(C.c_int32 * 4)]),
     ("rsys_item_table", C.c_int32, [_P, _P, C.c_int64]),
+    ("rsys_retrieve_topk", C.c_int32, [_P, C.c_int32, _P, C.c_int64, _P, C.c_int32, _P, _P, _P, C.c_int32, _P, _P, _P]),
     ("rsys_model_set_deterministic", C.c_int32, [_P, C.c_int32]),
     ("rsys_infer", C.c_int32, [_P, C.c_int32, _P, C.c_int64]),
     ("rsys_infer_select", C.c_int32, [_P, C.c_int32, _P, C.c_int64, _P, C.c_int64]),
@@ -123,6 +124,7 @@ _SIGS = [
                                       C.c_int32, C.c_int32, _P]),
     ("rsys_op_gemm_klimit", C.c_int32, [C.c_int32, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int32, _P]),
     ("rsys_op_attention", C.c_int32, [C.c_int32] + [C.c_int32] * 5 + [_P] * 9),
+    ("rsys_op_topk", C.c_int32, [_P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P]),
     ("rsys_op_embedding_scatter", C.c_int32, [_P, C.c_int64, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32]),
     ("rsys_step_mark", C.c_int32, [_P]),
     ("rsys_step_marks_get", C.c_int32, [_P, _P, C.c_int32, C.POINTER(C.c_int32)]),

@@ -152,6 +152,13 @@ int32_t rsys_head_rows_get(rsys_model* h, int32_t out[4]) {
 }
 
 int32_t rsys_item_table(rsys_model* h, float* out, int64_t n) { CHECK_HANDLE(h); ARG_CHECK(out, "null"); return model_item_table(h->m, out, n); }
+int32_t rsys_retrieve_topk(rsys_model* h, int32_t medium, const float* queries, int64_t n_queries, const int32_t* group, int32_t n_groups,
+                           const float* prior, const int64_t* excl_offsets, const int32_t* excl_ids, int32_t k, int32_t* ids_out,
+                           float* scores_out, int32_t* counts_out) {
+  CHECK_HANDLE(h);
+  return model_retrieve_topk(h->m, medium, queries, n_queries, group, n_groups, prior, excl_offsets, excl_ids, k, ids_out, scores_out,
+                             counts_out);
+}
 int32_t rsys_model_set_deterministic(rsys_model* h, int32_t on) { CHECK_HANDLE(h); return model_set_deterministic(h->m, on); }
 int32_t rsys_infer(rsys_model* h, int32_t task, float* out, int64_t n) { CHECK_HANDLE(h); ARG_CHECK(out, "null"); return model_infer(h->m, task, nullptr, 0, out, n); }
 int32_t rsys_infer_select(rsys_model* h, int32_t task, const int32_t* token_index, int64_t n_tokens, float* out, int64_t n) {
@@ -779,6 +786,10 @@ int32_t rsys_op_attention(int32_t dtype, int32_t B, int32_t T, int32_t H, int32_
 // the backward's embedding scatter on caller-provided device buffers: gE[id'] += sum_n gx0[n * ldx ..+D) over the tokens whose
 // masked id (m_matchedid, -1 -> row V) is id'; the token index is built from the raw ids (matchedid) as at batch upload.
 // atomic != 0 runs the float-atomic form instead (A/B reference).
+int32_t rsys_op_topk(const float* scores, int64_t ld, int32_t rows, int32_t V, int32_t k, int32_t* ids, float* vals, int32_t* counts) {
+  switches_parse();
+  return op_topk(scores, ld, rows, V, k, ids, vals, counts);
+}
 int32_t rsys_op_embedding_scatter(const float* gx0, int64_t ldx, const int32_t* matchedid, const int32_t* m_matchedid, int32_t N,
                                   int32_t V, int32_t D, float* gE, int32_t atomic) {
   switches_parse();

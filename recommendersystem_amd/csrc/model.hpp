@@ -44,6 +44,8 @@ struct PhaseTimer {
   std::vector<char> open;   // per open tic: 1 = recorded, 0 = filtered out (its toc records nothing)
 };
 
+struct RetrieveWs;   // retrieve.hip
+
 struct Model {
   rsys_config cfg;
   int device = 0;
@@ -261,6 +263,7 @@ struct Model {
   bool last_evaluate = false;
   PhaseTimer timer;
   std::vector<hipEvent_t> step_marks;   // rsys_step_mark: one event per optimizer-step boundary (per-step time distribution)
+  RetrieveWs* rws = nullptr;            // rsys_retrieve_topk's workspace (allocated on first use)
 };
 
 struct Optimizer {
@@ -302,6 +305,11 @@ int model_split_table_tail(Model* m, struct rsys_comm* c, hipStream_t cs, int64_
 int model_finalize_stage(Model* m, int stage /*1: prepare, 2: dWp GEMM*/, int64_t* wp_off, int64_t* wp_n);
 int model_clip(Model* m, float max_norm, float* norm_out);
 int model_set_deterministic(Model* m, int on);
+// retrieve.hip: retrieval top-k over the fused item table of a medium (rsys_retrieve_topk) and the selection alone (rsys_op_topk)
+int model_retrieve_topk(Model* m, int medium, const float* queries, int64_t nq, const int32_t* group, int32_t ng, const float* prior,
+                        const int64_t* excl_off, const int32_t* excl_ids, int32_t k, int32_t* ids_out, float* scores_out, int32_t* counts_out);
+void retrieve_free(Model* m);
+int op_topk(const float* scores, int64_t ld, int32_t rows, int32_t V, int32_t k, int32_t* ids, float* vals, int32_t* counts);
 int optimizer_step(Optimizer* o, float lr_factor, float clip, float grad_div);
 
 }  // namespace rsys

@@ -1,0 +1,552 @@
+// Retrieval top-k on the device (Finetune/embed.jl:86-90 + the scoring, masking and sort of Inference/render.jl:240-333): a request's
+// query embeddings against the fused item table of one medium (the tied watch head, model.py:148-170), log soft-max per query, summed
+// per group of queries on top of a prior, exclusions, and the best k items per group.  Only k ids and k scores per group leave the
+// device.  The pipeline (DESIGN.md "Retrieval top-k"):
+//   scores     gemm<T> "gemm_retrieve": z = Q F_m^T in fp32, at most 256 query rows per launch (one pass over the table per chunk)
+//   lse        per row: RT_LSE_SPLIT workgroups each fold a slice into (max, sum of exp) partials, one ordered combine per row
+//   combine    score_g[i] = prior_g[i] + sum over the group's queries, in query order, of (z_q[i] - lse_q); on the last chunk the
+//              same pass maps each score to an order-preserving uint32 key (0 = excluded / -inf / NaN) and counts the first 8-bit
+//              digit of the keys into a per-group histogram (wave-aggregated LDS counts, then one global add per bin)
+//   select     radix select, at most four digit passes: a small kernel per pass picks each group's digit and the remaining rank
+//   compact    keys above the threshold go to the group's candidate list, keys equal to it in ascending id order; every slot is an
+//              exclusive prefix of per-workgroup counts over workgroup order (no atomics: independent of scheduling)
+//   sort       bitonic sort of <= 8192 (key, id) pairs per group in LDS: descending key, then ascending id; -1 / -inf padding
+// Every launch covers all groups (grid = blocks x groups); the host waits once, after the copy out.
+#include "model_internal.hpp"
+
+namespace rsys {
+
+namespace {
+
+constexpr int RT_THREADS = 256;
+constexpr int RT_ITEMS = 1024;        // items per workgroup of the per-item passes (4 per thread)
+constexpr int RT_CHUNK = 256;         // query rows per score GEMM
+constexpr int RT_LSE_SPLIT = 64;      // workgroups per row of the log-sum-exp
+constexpr int RT_MAXK = 8192;         // candidates per group: the sort's LDS holds 8192 x 8 B = 64 KiB
+constexpr int RT_MAXQ = 4096;
+
+// selection state of one group: keys with (key & rmask) > prefix are taken, keys with (key & rmask) == prefix are ties of which the
+// first `need` in ascending id order are taken; total = min(k, admissible) = the group's output count
+struct SelState {
+  unsigned prefix, rmask;
+  int need, total, done, pad0, pad1, pad2;
+};
+
+// order-preserving key: larger score -> larger key; -0.0 is +0.0; -inf and NaN map to 0, which no admissible score produces
+// (the smallest, -FLT_MAX, maps to 0x00800000)
+__device__ __forceinline__ unsigned score_key(float s) {
+  if (!(s > -INFINITY)) return 0u;
+  const unsigned u = __float_as_uint(s == 0.f ? 0.f : s);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float key_score(unsigned k) {
+  return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
+}
+
+// h[digit] += 1 for every lane with `valid`, one LDS atomic per distinct digit of the wave (equal scores all land in one bin: the
+// wave's leader counts its run of equal digits with a ballot instead of 64 atomics on one address).  Called by all 64 lanes.
+__device__ __forceinline__ void hist_add_wave(unsigned* h, unsigned digit, bool valid) {
+  unsigned long long act = __ballot(valid);
+  while (act) {
+    const int leader = __builtin_ctzll(act);
+    const unsigned d = __shfl(digit, leader, 64);
+    const unsigned long long same = __ballot(valid && digit == d);
+    if (lane_id() == leader) atomicAdd(&h[d], (unsigned)__popcll(same));
+    act &= ~same;
+  }
+}
+
+__device__ __forceinline__ void lse_fold(float& m, float& s, float m2, float s2) {
+  const float mx = fmaxf(m, m2);
+  if (mx == -INFINITY) return;
+  s = (m == -INFINITY ? 0.f : s * expf(m - mx)) + (m2 == -INFINITY ? 0.f : s2 * expf(m2 - mx));
+  m = mx;
+}
+
+// (max, sum exp(z - max)) of slice blockIdx.x of row blockIdx.y; one online pass, then a fixed-order fold (lanes, then waves)
+__global__ void __launch_bounds__(RT_THREADS) lse_partial_kernel(const float* z, long long ldz, int V, float2* part) {
+  const int row = blockIdx.y, p = blockIdx.x, P = gridDim.x;
+  const long long lo = (long long)V * p / P, hi = (long long)V * (p + 1) / P;
+  const float* zr = z + row * ldz;
+  float m = -INFINITY, s = 0.f;
+  for (long long i = lo + threadIdx.x; i < hi; i += RT_THREADS) {
+    const float x = zr[i];
+    if (x > m) { s = (m == -INFINITY ? 0.f : s * expf(m - x)) + 1.f; m = x; }
+    else s += expf(x - m);
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float m2 = __shfl_xor(m, o, 64), s2 = __shfl_xor(s, o, 64);
+    lse_fold(m, s, m2, s2);
+  }
+  __shared__ float sm[2][RT_THREADS / 64];
+  const int w = threadIdx.x >> 6;
+  if (lane_id() == 0) { sm[0][w] = m; sm[1][w] = s; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float M = sm[0][0], S = sm[1][0];
+    for (int i = 1; i < RT_THREADS / 64; ++i) lse_fold(M, S, sm[0][i], sm[1][i]);
+    part[(long long)row * P + p] = make_float2(M, S);
+  }
+}
+// lse[q0 + row] = log sum exp of row `row`, its partials folded in slice order
+__global__ void lse_final_kernel(const float2* part, int P, int rows, int q0, float* lse) {
+  const int row = blockIdx.x * blockDim.x + threadIdx.x;
+  if (row >= rows) return;
+  float m = -INFINITY, s = 0.f;
+  for (int p = 0; p < P; ++p) { const float2 v = part[(long long)row * P + p]; lse_fold(m, s, v.x, v.y); }
+  lse[q0 + row] = m + logf(s);
+}
+
+__global__ void scatter_nan_kernel(float* sc, const long long* pos, long long n) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) sc[pos[i]] = __int_as_float(0x7fc00000);
+}
+
+// score_g[i] = src_g[i] + sum over the group's queries of this chunk (members[range.x .. range.y), ascending query index) of
+// (z_q[i] - lse_q).  LAST: write the key instead of the score and count the keys' first digit (bits 31..24) into hist[g][256].
+// ranges == nullptr: no queries (the op hook: keys of given scores).
+template <bool LAST>
+__global__ void __launch_bounds__(RT_THREADS) combine_kernel(const float* src, long long lds, float* dst, long long ldd, const float* z,
+                                                             long long ldz, const float* lse, const int* members, const int2* ranges,
+                                                             int q0, int V, unsigned* hist) {
+  const int g = blockIdx.y;
+  const int2 r = ranges ? ranges[g] : make_int2(0, 0);
+  if (!LAST && r.x == r.y) return;   // (in place, nothing to add)
+  __shared__ unsigned h[256];
+  if (LAST) { h[threadIdx.x] = 0; __syncthreads(); }
+  const long long base = (long long)blockIdx.x * RT_ITEMS;
+  const float* sg = src + g * lds;
+  float* dg = dst + g * ldd;
+  for (int j = 0; j < RT_ITEMS / RT_THREADS; ++j) {
+    const long long i = base + j * RT_THREADS + threadIdx.x;
+    const bool valid = i < V;
+    float s = valid ? sg[i] : 0.f;
+    if (valid)
+      for (int t = r.x; t < r.y; ++t) {
+        const int q = members[t];
+        s += z[(long long)(q - q0) * ldz + i] - lse[q];
+      }
+    if (!LAST) {
+      if (valid) dg[i] = s;
+    } else {
+      const unsigned key = valid ? score_key(s) : 0u;
+      if (valid) ((unsigned*)dg)[i] = key;
+      hist_add_wave(h, key >> 24, key != 0u);
+    }
+  }
+  if (LAST) {
+    __syncthreads();
+    if (h[threadIdx.x]) atomicAdd(&hist[g * 256 + threadIdx.x], h[threadIdx.x]);
+  }
+}
+
+// digit pass `pass` (digit = bits [24 - 8 pass, 32 - 8 pass)) of every group still open: pick the bin that holds the need-th largest
+// candidate, narrow the prefix to it, clear the histogram for the next pass.  Pass 0 also sets the group's output count.
+__global__ void __launch_bounds__(RT_THREADS) select_step_kernel(unsigned* hist, SelState* st, int k, int pass) {
+  const int g = blockIdx.x;
+  SelState* S = st + g;
+  if (pass > 0 && S->done) return;
+  __shared__ unsigned c[256];
+  c[threadIdx.x] = hist[g * 256 + threadIdx.x];
+  hist[g * 256 + threadIdx.x] = 0;
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  SelState t = *S;
+  if (pass == 0) {
+    unsigned adm = 0;
+    for (int b = 0; b < 256; ++b) adm += c[b];
+    t.prefix = 0; t.rmask = 0; t.done = 0;
+    if ((int)adm <= k) {   // every admissible item is in: no digit to resolve
+      t.need = (int)adm; t.total = (int)adm; t.done = 1;
+      *S = t;
+      return;
+    }
+    t.need = k; t.total = k;
+  }
+  const int shift = 24 - 8 * pass;
+  unsigned cum = 0;
+  int b = 255;
+  for (; b > 0; --b) {
+    if (cum + c[b] >= (unsigned)t.need) break;
+    cum += c[b];
+  }
+  t.prefix |= (unsigned)b << shift;
+  t.rmask |= 0xffu << shift;
+  t.need -= (int)cum;
+  if (c[b] == (unsigned)t.need || shift == 0) t.done = 1;   // (every key of the bin is taken, or the key is resolved)
+  *S = t;
+}
+
+// histogram of digit (key >> shift) & 255 over the keys matching an open group's prefix
+__global__ void __launch_bounds__(RT_THREADS) hist_pass_kernel(const unsigned* keys, long long ldk, int V, const SelState* st, int shift,
+                                                               unsigned* hist) {
+  const int g = blockIdx.y;
+  const SelState S = st[g];
+  if (S.done) return;
+  __shared__ unsigned h[256];
+  h[threadIdx.x] = 0;
+  __syncthreads();
+  const unsigned* kg = keys + g * ldk;
+  const long long base = (long long)blockIdx.x * RT_ITEMS;
+  for (int j = 0; j < RT_ITEMS / RT_THREADS; ++j) {
+    const long long i = base + j * RT_THREADS + threadIdx.x;
+    const unsigned key = i < V ? kg[i] : 0u;
+    hist_add_wave(h, (key >> shift) & 0xffu, key != 0u && (key & S.rmask) == S.prefix);
+  }
+  __syncthreads();
+  if (h[threadIdx.x]) atomicAdd(&hist[g * 256 + threadIdx.x], h[threadIdx.x]);
+}
+
+__device__ __forceinline__ bool is_tie(unsigned key, const SelState& S) { return key != 0u && (key & S.rmask) == S.prefix; }
+__device__ __forceinline__ bool is_above(unsigned key, const SelState& S) { return key != 0u && (key & S.rmask) > S.prefix; }
+
+__device__ __forceinline__ unsigned long long cand_pack(unsigned key, long long id) {
+  return ((unsigned long long)key << 32) | (unsigned long long)(0xffffffffu - (unsigned)id);
+}
+
+// exact integer sum over the workgroup (every thread gets it)
+__device__ __forceinline__ int block_sum_int(int v, int* smem /* >= 4 */) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  __syncthreads();
+  if (lane_id() == 0) smem[threadIdx.x >> 6] = v;
+  __syncthreads();
+  int r = 0;
+  for (int i = 0; i < RT_THREADS / 64; ++i) r += smem[i];
+  return r;
+}
+
+// cnt[g][blockIdx.x] = {keys above the threshold, keys equal to it} among this workgroup's items
+__global__ void __launch_bounds__(RT_THREADS) count_kernel(const unsigned* keys, long long ldk, int V, const SelState* st, int2* cnt) {
+  const int g = blockIdx.y;
+  const SelState S = st[g];
+  const unsigned* kg = keys + g * ldk;
+  const long long base = (long long)blockIdx.x * RT_ITEMS;
+  int na = 0, nt = 0;
+  for (int j = 0; j < RT_ITEMS / RT_THREADS; ++j) {
+    const long long i = base + j * RT_THREADS + threadIdx.x;
+    const unsigned key = i < V ? kg[i] : 0u;
+    na += is_above(key, S) ? 1 : 0;
+    nt += is_tie(key, S) ? 1 : 0;
+  }
+  __shared__ int sm[RT_THREADS / 64];
+  const int a = block_sum_int(na, sm);
+  const int t = block_sum_int(nt, sm);
+  if (threadIdx.x == 0) cnt[(long long)g * gridDim.x + blockIdx.x] = make_int2(a, t);
+}
+
+// candidate list of group g: [0, total - need) the keys above the threshold, [total - need, total) the first `need` threshold-equal
+// keys by ascending id.  Every item's slot is an exclusive prefix over workgroup order (the counts of count_kernel), then over the
+// waves and lanes of the workgroup: no atomics, the list does not depend on scheduling.
+__global__ void __launch_bounds__(RT_THREADS) compact_kernel(const unsigned* keys, long long ldk, int V, const SelState* st, const int2* cnt,
+                                                             unsigned long long* cand, int ldc) {
+  const int g = blockIdx.y, nb = gridDim.x;
+  const SelState S = st[g];
+  const unsigned* kg = keys + g * ldk;
+  unsigned long long* cg = cand + (long long)g * ldc;
+  const int above0 = S.total - S.need;
+  __shared__ int sm[RT_THREADS / 64];
+  __shared__ int wa[RT_THREADS / 64], wt[RT_THREADS / 64];
+  int a0 = 0, t0 = 0;
+  for (int b = threadIdx.x; b < blockIdx.x; b += RT_THREADS) { const int2 c = cnt[(long long)g * nb + b]; a0 += c.x; t0 += c.y; }
+  int abase = block_sum_int(a0, sm);
+  int tbase = block_sum_int(t0, sm);
+  const int w = threadIdx.x >> 6, lane = lane_id();
+  const unsigned long long lt = (1ull << lane) - 1ull;
+  const long long base = (long long)blockIdx.x * RT_ITEMS;
+  for (int j = 0; j < RT_ITEMS / RT_THREADS; ++j) {
+    const long long i = base + j * RT_THREADS + threadIdx.x;
+    const unsigned key = i < V ? kg[i] : 0u;
+    const bool above = is_above(key, S), tie = is_tie(key, S);
+    const unsigned long long ba = __ballot(above), bt = __ballot(tie);
+    if (lane == 0) { wa[w] = __popcll(ba); wt[w] = __popcll(bt); }
+    __syncthreads();
+    int oa = abase, ot = tbase, ta = 0, tt = 0;
+    for (int v = 0; v < RT_THREADS / 64; ++v) {
+      if (v < w) { oa += wa[v]; ot += wt[v]; }
+      ta += wa[v]; tt += wt[v];
+    }
+    __syncthreads();
+    if (above) {
+      const int slot = oa + __popcll(ba & lt);
+      if (slot < above0) cg[slot] = cand_pack(key, i);   // (always: the select passes counted exactly above0 of them)
+    }
+    if (tie) {
+      const int rank = ot + __popcll(bt & lt);
+      if (rank < S.need) cg[above0 + rank] = cand_pack(key, i);
+    }
+    abase += ta; tbase += tt;
+  }
+}
+
+// sort group g's candidates (descending key, ascending id) and write ids / scores / count, padding with -1 / -inf
+__global__ void __launch_bounds__(1024) sort_out_kernel(const unsigned long long* cand, int ldc, const SelState* st, int k, int* ids,
+                                                        float* vals, int* counts) {
+  const int g = blockIdx.x;
+  const int n = st[g].total;
+  __shared__ unsigned long long s[RT_MAXK];
+  int N2 = 1;
+  while (N2 < n) N2 <<= 1;
+  const unsigned long long* cg = cand + (long long)g * ldc;
+  for (int i = threadIdx.x; i < N2; i += 1024) s[i] = i < n ? cg[i] : 0ull;
+  __syncthreads();
+  for (int size = 2; size <= N2; size <<= 1) {
+    for (int stride = size >> 1; stride > 0; stride >>= 1) {
+      for (int i = threadIdx.x; i < N2 / 2; i += 1024) {
+        const int lo = 2 * stride * (i / stride) + (i % stride), hi = lo + stride;
+        const bool desc = (lo & size) == 0;
+        const unsigned long long a = s[lo], b = s[hi];
+        if ((a < b) == desc) { s[lo] = b; s[hi] = a; }
+      }
+      __syncthreads();
+    }
+  }
+  int* ig = ids + (long long)g * k;
+  float* vg = vals + (long long)g * k;
+  for (int i = threadIdx.x; i < k; i += 1024) {
+    if (i < n) {
+      const unsigned long long v = s[i];
+      ig[i] = (int)(0xffffffffu - (unsigned)v);
+      vg[i] = key_score((unsigned)(v >> 32));
+    } else {
+      ig[i] = -1;
+      vg[i] = -INFINITY;
+    }
+  }
+  if (threadIdx.x == 0) counts[g] = n;
+}
+
+#define RT_LAUNCH_CHECK() HIP_CHECK(hipGetLastError())
+
+// device buffers of the selection stage
+struct SelBufs {
+  unsigned* hist;          // [rows][256], zero on entry (pass 0 filled by combine_kernel<true>)
+  SelState* st;            // [rows]
+  int2* cnt;               // [rows][nb]
+  unsigned long long* cand; int ldc;   // [rows][ldc >= k]
+};
+
+// radix select + compaction + sort on keys [rows][ldk] whose first-digit histogram is in b.hist
+int topk_select(const unsigned* keys, long long ldk, int rows, int V, int k, const SelBufs& b, int* ids, float* vals, int* counts,
+                hipStream_t s) {
+  const int nb = (V + RT_ITEMS - 1) / RT_ITEMS;
+  const dim3 grid(nb, rows);
+  select_step_kernel<<<rows, RT_THREADS, 0, s>>>(b.hist, b.st, k, 0);
+  RT_LAUNCH_CHECK();
+  for (int pass = 1; pass < 4; ++pass) {
+    hist_pass_kernel<<<grid, RT_THREADS, 0, s>>>(keys, ldk, V, b.st, 24 - 8 * pass, b.hist);
+    RT_LAUNCH_CHECK();
+    select_step_kernel<<<rows, RT_THREADS, 0, s>>>(b.hist, b.st, k, pass);
+    RT_LAUNCH_CHECK();
+  }
+  count_kernel<<<grid, RT_THREADS, 0, s>>>(keys, ldk, V, b.st, b.cnt);
+  RT_LAUNCH_CHECK();
+  compact_kernel<<<grid, RT_THREADS, 0, s>>>(keys, ldk, V, b.st, b.cnt, b.cand, b.ldc);
+  RT_LAUNCH_CHECK();
+  sort_out_kernel<<<rows, 1024, 0, s>>>(b.cand, b.ldc, b.st, k, ids, vals, counts);
+  RT_LAUNCH_CHECK();
+  return RSYS_OK;
+}
+
+// bump allocation inside one device buffer (256-byte aligned pieces)
+struct Carve {
+  char* p; size_t off = 0;
+  template <typename X> X* take(size_t count) {
+    X* r = (X*)(p ? p + off : nullptr);
+    off += (count * sizeof(X) + 255) / 256 * 256;
+    return r;
+  }
+};
+
+}  // namespace
+
+// the retrieval workspace of a model: one device buffer, grown on demand, freed with the model
+struct RetrieveWs {
+  void* buf = nullptr;
+  size_t bytes = 0;
+};
+
+void retrieve_free(Model* m) {
+  if (!m->rws) return;
+  if (m->rws->buf) hipFree(m->rws->buf);
+  delete m->rws;
+  m->rws = nullptr;
+}
+
+template <typename T>
+static int retrieve_t(Model* m, int medium, const float* queries, int64_t nq, const int32_t* group, int ng, const float* prior,
+                      const int64_t* excl_off, const int32_t* excl_ids, int k, int32_t* ids_out, float* scores_out, int32_t* counts_out) {
+  const int D = m->D, Vm = medium == 0 ? m->V0 : m->V1, vs = medium == 0 ? 0 : m->V0;
+  hipStream_t s = m->stream;
+  // host-side index arrays: the queries of each group in query order, per chunk the range of them it holds, exclusion positions
+  std::vector<int> gcount(ng, 0);
+  for (int64_t q = 0; q < nq; ++q) {
+    const int g = group ? group[q] : (int)q;
+    ARG_CHECK(g >= 0 && g < ng, "retrieve_topk: group ids must be in [0, n_groups)");
+    ++gcount[g];
+  }
+  for (int g = 0; g < ng; ++g) ARG_CHECK(gcount[g] > 0, "retrieve_topk: every group needs at least one query");
+  std::vector<int> goff(ng + 1, 0);
+  for (int g = 0; g < ng; ++g) goff[g + 1] = goff[g] + gcount[g];
+  std::vector<int> members(nq), fill(goff.begin(), goff.end() - 1);
+  for (int64_t q = 0; q < nq; ++q) members[fill[group ? group[q] : (int)q]++] = (int)q;
+  const int nchunks = (int)((nq + RT_CHUNK - 1) / RT_CHUNK);
+  std::vector<int2> ranges((size_t)nchunks * ng);
+  for (int g = 0; g < ng; ++g) {
+    int t = goff[g];
+    for (int c = 0; c < nchunks; ++c) {
+      const int lo = t;
+      while (t < goff[g + 1] && members[t] < (c + 1) * RT_CHUNK) ++t;
+      ranges[(size_t)c * ng + g] = make_int2(lo, t);
+    }
+  }
+  std::vector<long long> xpos;
+  if (excl_off) {
+    ARG_CHECK(excl_off[0] == 0, "retrieve_topk: excl_offsets[0] must be 0");
+    for (int g = 0; g < ng; ++g) {
+      ARG_CHECK(excl_off[g + 1] >= excl_off[g], "retrieve_topk: excl_offsets must be non-decreasing");
+      for (int64_t j = excl_off[g]; j < excl_off[g + 1]; ++j) {
+        ARG_CHECK(excl_ids[j] >= 0 && excl_ids[j] < Vm, "retrieve_topk: exclusion ids must be medium-local, in [0, V_m)");
+        xpos.push_back((long long)g * Vm + excl_ids[j]);
+      }
+    }
+  }
+  HIP_CHECK(hipSetDevice(m->device));
+  if (m->table_dirty) { RC(table_forward<T>(m)); m->table_dirty = false; }
+  // workspace: queries (f32 + compute type), lse, partials, the per-chunk score slab (the candidate lists reuse it after the last
+  // chunk), the group scores / keys, the selection state, the outputs, the index arrays
+  const int Vmax = std::max(m->V0, m->V1);
+  const long long ldz = pad8(Vmax);
+  const int nb = (Vm + RT_ITEMS - 1) / RT_ITEMS;
+  const size_t slab = std::max<size_t>((size_t)RT_CHUNK * (size_t)ldz * 4, (size_t)ng * (size_t)k * 8);
+  auto layout = [&](Carve& c, float** qf, T** qt, float** lse, float2** part, float** z, float** sc, SelBufs* sb, int** d_ids,
+                    float** d_vals, int** d_counts, int** d_members, int2** d_ranges, long long** d_xpos) {
+    *qf = c.take<float>((size_t)nq * D);
+    *qt = is_bf16<T>::value ? c.take<T>((size_t)nq * D) : (T*)*qf;
+    *lse = c.take<float>(nq);
+    *part = c.take<float2>((size_t)RT_CHUNK * RT_LSE_SPLIT);
+    *z = (float*)c.take<char>(slab);
+    *sc = c.take<float>((size_t)ng * Vm);
+    sb->hist = c.take<unsigned>((size_t)ng * 256);
+    sb->st = c.take<SelState>(ng);
+    sb->cnt = c.take<int2>((size_t)ng * nb);
+    *d_ids = c.take<int>((size_t)ng * k);
+    *d_vals = c.take<float>((size_t)ng * k);
+    *d_counts = c.take<int>(ng);
+    *d_members = c.take<int>(nq);
+    *d_ranges = c.take<int2>(ranges.size());
+    *d_xpos = c.take<long long>(std::max<size_t>(1, xpos.size()));
+  };
+  float *qf, *lse, *z, *sc, *d_vals; T* qt; float2* part; SelBufs sb; int *d_ids, *d_counts, *d_members; int2* d_ranges; long long* d_xpos;
+  Carve probe{nullptr};
+  layout(probe, &qf, &qt, &lse, &part, &z, &sc, &sb, &d_ids, &d_vals, &d_counts, &d_members, &d_ranges, &d_xpos);
+  if (!m->rws) m->rws = new RetrieveWs();
+  RetrieveWs* ws = m->rws;
+  if (ws->bytes < probe.off) {
+    HIP_CHECK(hipStreamSynchronize(s));
+    if (ws->buf) HIP_CHECK(hipFree(ws->buf));
+    ws->buf = nullptr; ws->bytes = 0;
+    HIP_CHECK(hipMalloc(&ws->buf, probe.off));
+    ws->bytes = probe.off;
+  }
+  Carve c{(char*)ws->buf};
+  layout(c, &qf, &qt, &lse, &part, &z, &sc, &sb, &d_ids, &d_vals, &d_counts, &d_members, &d_ranges, &d_xpos);
+  sb.cand = (unsigned long long*)z; sb.ldc = k;
+
+  tic(m, "retrieve_prep");
+  HIP_CHECK(hipMemcpyAsync(qf, queries, (size_t)nq * D * 4, hipMemcpyHostToDevice, s));
+  if constexpr (is_bf16<T>::value) RC(launch_cast<T>(qf, qt, (long long)nq * D, s));
+  HIP_CHECK(hipMemcpyAsync(d_members, members.data(), members.size() * 4, hipMemcpyHostToDevice, s));
+  HIP_CHECK(hipMemcpyAsync(d_ranges, ranges.data(), ranges.size() * sizeof(int2), hipMemcpyHostToDevice, s));
+  if (prior) HIP_CHECK(hipMemcpyAsync(sc, prior, (size_t)ng * Vm * 4, hipMemcpyHostToDevice, s));
+  else HIP_CHECK(hipMemsetAsync(sc, 0, (size_t)ng * Vm * 4, s));
+  if (!xpos.empty()) {
+    HIP_CHECK(hipMemcpyAsync(d_xpos, xpos.data(), xpos.size() * 8, hipMemcpyHostToDevice, s));
+    scatter_nan_kernel<<<(unsigned)((xpos.size() + 255) / 256), 256, 0, s>>>(sc, d_xpos, (long long)xpos.size());
+    RT_LAUNCH_CHECK();
+  }
+  HIP_CHECK(hipMemsetAsync(sb.hist, 0, (size_t)ng * 256 * 4, s));
+  toc(m);
+  const T* Fm = AT<T>(m->FT) + (int64_t)vs * D;
+  for (int ch = 0; ch < nchunks; ++ch) {
+    const int q0 = ch * RT_CHUNK, nc = (int)std::min<int64_t>(RT_CHUNK, nq - q0);
+    GemmParams p{};
+    p.A = qt + (size_t)q0 * D; p.lda = D; p.B = Fm; p.ldb = D; p.C = z; p.ldc = ldz; p.c_f32 = 1;
+    p.M = nc; p.N = Vm; p.K = D; p.epi = EPI_STORE;
+    RC(gemm<T>(m, "gemm_retrieve", p, false, false, false));
+    tic(m, "retrieve_lse");
+    lse_partial_kernel<<<dim3(RT_LSE_SPLIT, nc), RT_THREADS, 0, s>>>(z, ldz, Vm, part);
+    RT_LAUNCH_CHECK();
+    lse_final_kernel<<<(nc + 255) / 256, 256, 0, s>>>(part, RT_LSE_SPLIT, nc, q0, lse);
+    RT_LAUNCH_CHECK();
+    toc(m);
+    tic(m, "retrieve_combine");
+    const dim3 grid(nb, ng);
+    if (ch + 1 < nchunks)
+      combine_kernel<false><<<grid, RT_THREADS, 0, s>>>(sc, Vm, sc, Vm, z, ldz, lse, d_members, d_ranges + (size_t)ch * ng, q0, Vm, sb.hist);
+    else
+      combine_kernel<true><<<grid, RT_THREADS, 0, s>>>(sc, Vm, sc, Vm, z, ldz, lse, d_members, d_ranges + (size_t)ch * ng, q0, Vm, sb.hist);
+    RT_LAUNCH_CHECK();
+    toc(m);
+  }
+  tic(m, "retrieve_select");
+  RC(topk_select((const unsigned*)sc, Vm, ng, Vm, k, sb, d_ids, d_vals, d_counts, s));
+  toc(m);
+  HIP_CHECK(hipMemcpyAsync(ids_out, d_ids, (size_t)ng * k * 4, hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipMemcpyAsync(scores_out, d_vals, (size_t)ng * k * 4, hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipMemcpyAsync(counts_out, d_counts, (size_t)ng * 4, hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipStreamSynchronize(s));
+  return RSYS_OK;
+}
+
+int model_retrieve_topk(Model* m, int medium, const float* queries, int64_t nq, const int32_t* group, int32_t ng, const float* prior,
+                        const int64_t* excl_off, const int32_t* excl_ids, int32_t k, int32_t* ids_out, float* scores_out,
+                        int32_t* counts_out) {
+  ARG_CHECK(medium == 0 || medium == 1, "retrieve_topk: medium must be 0 or 1");
+  ARG_CHECK(!m->sharded, "retrieve_topk: the row-sharded item table is not supported (replicated table only)");
+  ARG_CHECK(queries && ids_out && scores_out && counts_out, "retrieve_topk: null buffer");
+  ARG_CHECK(nq >= 1 && nq <= RT_MAXQ, "retrieve_topk: 1 <= n_queries <= 4096");
+  ARG_CHECK(ng >= 1 && ng <= nq, "retrieve_topk: 1 <= n_groups <= n_queries (every group needs a query)");
+  ARG_CHECK(group != nullptr || ng == nq, "retrieve_topk: without `group`, n_groups must equal n_queries");
+  ARG_CHECK((excl_off == nullptr) == (excl_ids == nullptr), "retrieve_topk: excl_offsets and excl_ids are both given or both NULL");
+  const int Vm = medium == 0 ? m->V0 : m->V1;
+  ARG_CHECK(k >= 1 && k <= std::min(Vm, RT_MAXK), "retrieve_topk: 1 <= k <= min(V_m, 8192)");
+  return m->bf16_mode ? retrieve_t<bf16>(m, medium, queries, nq, group, ng, prior, excl_off, excl_ids, k, ids_out, scores_out, counts_out)
+                      : retrieve_t<float>(m, medium, queries, nq, group, ng, prior, excl_off, excl_ids, k, ids_out, scores_out, counts_out);
+}
+
+int op_topk(const float* scores, int64_t ld, int32_t rows, int32_t V, int32_t k, int32_t* ids, float* vals, int32_t* counts) {
+  ARG_CHECK(scores && ids && vals && counts, "rsys_op_topk: null buffer");
+  ARG_CHECK(rows >= 1 && V >= 1 && ld >= V, "rsys_op_topk: rows >= 1, V >= 1, ld >= V");
+  ARG_CHECK(k >= 1 && k <= std::min(V, RT_MAXK), "rsys_op_topk: 1 <= k <= min(V, 8192)");
+  const int nb = (V + RT_ITEMS - 1) / RT_ITEMS;
+  Carve probe{nullptr};
+  auto layout = [&](Carve& c, unsigned** keys, SelBufs* sb) {
+    *keys = c.take<unsigned>((size_t)rows * V);
+    sb->hist = c.take<unsigned>((size_t)rows * 256);
+    sb->st = c.take<SelState>(rows);
+    sb->cnt = c.take<int2>((size_t)rows * nb);
+    sb->cand = c.take<unsigned long long>((size_t)rows * k);
+    sb->ldc = k;
+  };
+  unsigned* keys; SelBufs sb;
+  layout(probe, &keys, &sb);
+  void* buf = nullptr;
+  HIP_CHECK(hipMalloc(&buf, probe.off));
+  Carve c{(char*)buf};
+  layout(c, &keys, &sb);
+  int rc = RSYS_OK;
+  if (hipMemset(sb.hist, 0, (size_t)rows * 256 * 4) != hipSuccess) rc = RSYS_ERR_HIP;
+  if (rc == RSYS_OK) {
+    combine_kernel<true><<<dim3(nb, rows), RT_THREADS>>>(scores, ld, (float*)keys, V, nullptr, 0, nullptr, nullptr, nullptr, 0, V, sb.hist);
+    if (hipGetLastError() != hipSuccess) { set_error("rsys_op_topk: launch failed"); rc = RSYS_ERR_HIP; }
+  }
+  if (rc == RSYS_OK) rc = topk_select(keys, V, rows, V, k, sb, ids, vals, counts, nullptr);
+  const hipError_t e = hipDeviceSynchronize();
+  hipFree(buf);
+  if (rc == RSYS_OK && e != hipSuccess) { set_error(std::string("rsys_op_topk: ") + hipGetErrorString(e)); rc = RSYS_ERR_HIP; }
+  return rc;
+}
+
+}  // namespace rsys

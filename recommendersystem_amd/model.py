@@ -360,6 +360,38 @@ class RecommenderModel:
         check(lib().rsys_item_table(self._h, out.ctypes.data, out.size))
         return out
 
+    def retrieve_topk(self, queries, medium, k, group=None, prior=None, exclude=None):
+        """Retrieval candidates on the device (rsys_retrieve_topk: Finetune/embed.jl:86-90 + Inference/render.jl:240-333's scoring,
+        masking and sort): `queries` (n, D) retrieval embeddings; `group` (n,) group ids in [0, n_groups) or None (one group per
+        query); `prior` (n_groups, V_m) added to the scores or None; `exclude` a list of n_groups arrays of medium-local ids or None.
+        Per group the best k medium-local ids by the summed log soft-max (+ prior), exclusions and -inf / NaN scores left out, ties
+        by ascending id.  Returns (ids (n_groups, k) int32, scores (n_groups, k) float32, counts (n_groups,) int32); slots past
+        counts[g] hold -1 / -inf."""
+        q = np.ascontiguousarray(queries, np.float32)
+        if q.ndim == 1:
+            q = q[None, :]
+        n = q.shape[0]
+        gp = None if group is None else np.ascontiguousarray(group, np.int32).reshape(-1)
+        if gp is not None and gp.size != n:
+            raise ValueError(f"group has {gp.size} entries for {n} queries")
+        ng = n if gp is None else (int(gp.max()) + 1 if gp.size else 0)
+        Vm = self.config["vocab_sizes"][f"{int(medium)}_matchedid"] if medium in (0, 1) else 0
+        pr = None
+        if prior is not None:
+            pr = np.ascontiguousarray(prior, np.float32)
+            if pr.shape != (ng, Vm):
+                raise ValueError(f"prior has shape {pr.shape}, expected {(ng, Vm)}")
+        off = ids_x = None
+        if exclude is not None:
+            off, ids_x = exclusion_csr(exclude, ng)
+        ids = np.empty((ng, int(k)), np.int32)
+        scores = np.empty((ng, int(k)), np.float32)
+        counts = np.empty(ng, np.int32)
+        ptr = lambda a: None if a is None else a.ctypes.data
+        check(lib().rsys_retrieve_topk(self._h, int(medium), q.ctypes.data, n, ptr(gp), ng, ptr(pr), ptr(off), ptr(ids_x), int(k),
+                                       ids.ctypes.data, scores.ctypes.data, counts.ctypes.data))
+        return ids, scores, counts
+
     def trunk_output(self, rows):
         S = self.config["max_sequence_length"]; D = self.config["embed_dim"]
         out = np.empty((rows, 2 * S, D), np.float32)
@@ -460,6 +492,17 @@ class RecommenderModel:
             name, ms, cnt, fl = line.split()
             rep[name] = {"ms": float(ms), "count": int(cnt), "flops": float(fl)}
         return rep
+
+
+def exclusion_csr(exclude, n_groups):
+    """(offsets int64 [n_groups + 1], ids int32) of a list of per-group id arrays (ragged; duplicates allowed)."""
+    if len(exclude) != n_groups:
+        raise ValueError(f"exclude has {len(exclude)} lists for {n_groups} groups")
+    parts = [np.asarray(e, np.int64).reshape(-1) for e in exclude]
+    off = np.zeros(n_groups + 1, np.int64)
+    off[1:] = np.cumsum([p.size for p in parts])
+    ids = np.concatenate(parts).astype(np.int32) if parts and off[-1] else np.zeros(1, np.int32)
+    return off, np.ascontiguousarray(ids)
 
 
 def gather_rows(host_group, rows):

@@ -161,3 +161,68 @@ def compute_ranking(registry, medium, user):
         return r_masked.astype(np.float32)
     c = np.asarray(coefs, np.float64).reshape(-1)
     return (c[0] * float(np.asarray(registry[f"{medium}.rating_mean"])) + c[1] * r_masked).astype(np.float32)
+
+
+# Inference/render.jl:13-23
+STATUS_DELETED, STATUS_PLANNED = 3, 5
+
+
+def watched_exclusions(items, medium):
+    """The first two masks of Inference/render.jl:255-266 as medium-local ids (sorted, int32): item 0 (`p[1] = -Inf`, the default
+    id of long-tail items) and every item of `medium` whose status -- the last event's, as render.jl's per-user status dict keeps
+    it -- is neither deleted (3) nor planned (5).  Relation masks and item similarity stay with the host (exclusions / `prior`)."""
+    status = {}
+    for e in items:
+        if int(e["medium"]) == int(medium):
+            status[int(e["matchedid"])] = int(e["status"])
+    out = {0} | {i for i, s in status.items() if s not in (STATUS_DELETED, STATUS_PLANNED)}
+    return np.array(sorted(out), np.int32)
+
+
+def retrieve(model, embeds, medium, k, groups=None, exclude=None, prior=None, coefs=None):
+    """Retrieval candidates on the device (Inference/render.jl:240-333 without its relation masks, which arrive as `exclude` or a
+    -inf `prior`): `embeds` are the "{medium}.retrieval" vectors `predict` returns (dicts) or an (n, D) array; `groups` one group id
+    per embedding (a request's users share one, render.jl sums their log-probabilities) or None (one group each); `exclude` a list
+    of per-group medium-local id arrays (ragged); `prior` (n_groups, V_m) added to the scores; `coefs` the registry's retrieval
+    coefficient (`compute_retrieval`'s factor: adds log(coef) per user, the order does not change).  Returns one (ids, scores)
+    pair per group, best first, at most k items (fewer when fewer are admissible)."""
+    if medium not in (0, 1):
+        raise ValueError("retrieve: medium must be 0 or 1")
+    key = f"{medium}.retrieval"
+    rows = [e[key] if isinstance(e, dict) else e for e in embeds]
+    q = np.asarray(rows, np.float32)
+    if q.ndim != 2 or q.shape[0] == 0:
+        raise ValueError("retrieve: embeds must be a non-empty list of vectors")
+    if q.shape[1] != model.config["embed_dim"]:
+        raise ValueError(f"retrieve: embeddings have {q.shape[1]} values, the model {model.config['embed_dim']}")
+    Vm = model.config["vocab_sizes"][f"{medium}_matchedid"]
+    if not 1 <= int(k) <= min(Vm, 8192):
+        raise ValueError(f"retrieve: k must be in [1, {min(Vm, 8192)}]")
+    g = np.arange(q.shape[0], dtype=np.int32) if groups is None else np.asarray(groups, np.int64).reshape(-1)
+    if g.size != q.shape[0]:
+        raise ValueError(f"retrieve: {g.size} group ids for {q.shape[0]} embeddings")
+    if g.min() < 0:
+        raise ValueError("retrieve: group ids must be >= 0")
+    ng = int(g.max()) + 1
+    members = np.bincount(g, minlength=ng)
+    if (members == 0).any():
+        raise ValueError(f"retrieve: groups without an embedding: {np.flatnonzero(members == 0).tolist()}")
+    if exclude is not None:
+        if len(exclude) != ng:
+            raise ValueError(f"retrieve: exclude has {len(exclude)} lists for {ng} groups")
+        for e in exclude:
+            e = np.asarray(e).reshape(-1)
+            if e.size and (e.min() < 0 or e.max() >= Vm):
+                raise ValueError(f"retrieve: exclusion ids must be in [0, {Vm})")
+    if prior is not None and np.shape(prior) != (ng, Vm):
+        raise ValueError(f"retrieve: prior has shape {np.shape(prior)}, expected {(ng, Vm)}")
+    ids, scores, counts = model.retrieve_topk(q, medium, int(k), group=None if groups is None else g.astype(np.int32),
+                                              prior=prior, exclude=exclude)
+    out = []
+    for j in range(ng):
+        n = int(counts[j])
+        s = scores[j, :n]
+        if coefs is not None:
+            s = (s.astype(np.float64) + members[j] * np.log(float(np.asarray(coefs).reshape(-1)[0]))).astype(np.float32)
+        out.append((ids[j, :n].copy(), s))
+    return out
