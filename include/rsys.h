@@ -148,6 +148,39 @@ int32_t rsys_retrieve_topk(rsys_model* m, int32_t medium,
                            const int64_t* excl_offsets, const int32_t* excl_ids, /* CSR over groups of medium-local ids, or both NULL */
                            int32_t k, int32_t* ids_out, float* scores_out,   /* [n_groups][k] each */
                            int32_t* counts_out);                             /* [n_groups] */
+/* The serving tables of rsys_retrieve_request (Inference/render.jl:240-331, `retrieval(state)`), held on the device by the model, freed with
+ * it, not part of checkpoints; loading them changes nothing else (the fused item table stays valid).  Every setter replaces the table;
+ * a NULL array clears it.
+ * Relations of medium m: kind 0 = "{m}.dependencies" (V_m x V_m), 1 = "{m}.recaps" (V_m x V_m), 2 = "{m}.adaptations" (V_m x V_{1-m}),
+ * as 0-based CSC in Julia's column order (colptr[n_cols + 1] with colptr[0] = 0, non-decreasing; rowval in [0, n_rows)).  Stored
+ * values must be finite and >= 0 (else an ARG error); explicitly stored zeros are dropped, so "product != 0" is reachability along the
+ * stored pattern. */
+int32_t rsys_retrieve_relations_set(rsys_model* m, int32_t medium, int32_t kind, int64_t n_rows, int64_t n_cols,
+                                    const int64_t* colptr, const int32_t* rowval, const float* nzval);
+/* item similarity of medium m: emb = "embeddings.{m}" ([V_m][dim] f32: Julia's dim x V_m), crossproject = "crossproject.{m}" (dim x dim,
+ * column-major as Julia holds it, maps medium m into medium 1 - m; NULL: not loaded).  dim a multiple of 4 in [4, 2048].
+ * emb == NULL clears both. */
+int32_t rsys_retrieve_similarity_set(rsys_model* m, int32_t medium, int64_t dim, const float* emb, const float* crossproject);
+/* released items of medium m: mask[V_m], nonzero = released (render.jl's `keys(get_media_info(m))`); NULL: every item released */
+int32_t rsys_retrieve_released_set(rsys_model* m, int32_t medium, const uint8_t* mask);
+/* A whole render.jl `retrieval(state)` per group of queries, on the tables above: score_g = p_g + the rsys_retrieve_topk score, where
+ * p_g = E_m^T s_g, s_g = sum over the group's selected items in list order of E_m[id] (same medium) or crossproject.{am} E_am[id] (fp32
+ * throughout; 0 without selected items).  Masked for group g (render.jl:255-331): item 0; the group's selected items of medium m; items
+ * not released; and for any user of the group, with its list reduced to the last status per (medium, id): W_m = ids of medium m whose
+ * status is not 3 / 5, W_o = the same of medium 1 - m, C_m = status >= 7, K_m = status 6 / 2 / 1 -- item i if i in W_m, or
+ * (Adapt W_o)[i] != 0 and (Dep W_m)[i] == 0, or (Recap W_m)[i] != 0, or Dep row i is non-empty and (Dep C_m)[i] == 0, or (Dep K_m)[i] != 0.
+ * Output, limits and guarantees as rsys_retrieve_topk.  The three relation tables of `medium` must be loaded; selected items need the
+ * similarity table of their medium (and its crossproject when it is not `medium`) and that of `medium`.  ARG errors: missing tables,
+ * ids out of range for their medium, malformed offsets. */
+int32_t rsys_retrieve_request(rsys_model* m, int32_t medium,
+                              const float* queries, int64_t n_queries,        /* [n_queries][embed_dim] f32 */
+                              const int32_t* group, int32_t n_groups,         /* [n_queries] in [0, n_groups), or NULL: group = query */
+                              const int64_t* hist_offsets,                    /* [n_queries + 1] CSR over queries, or NULL (no lists) */
+                              const int32_t* hist_medium, const int32_t* hist_ids, const int32_t* hist_status, /* list items in list order */
+                              const int64_t* sel_offsets,                     /* [n_groups + 1] CSR over groups, or NULL (none selected) */
+                              const int32_t* sel_medium, const int32_t* sel_ids,
+                              int32_t k, int32_t* ids_out, float* scores_out, /* [n_groups][k] each */
+                              int32_t* counts_out);                           /* [n_groups] */
 /* on != 0: every float sum of the training step gets a fixed order (split-K partial tiles summed in split order, reductions through
  * per-workgroup partials instead of float atomics), so a step -- losses, gradients, updated parameters -- is bitwise reproducible
  * from run to run; costs a few percent of the step.  Replicated or row-sharded table, full or sampled soft-max.  (The reference's CUDA path is not reproducible:

@@ -211,6 +211,54 @@ function retrieve_topk(m::Model, medium::Integer, Q::Matrix{Float32}, k::Integer
         m.h, medium, Q, size(Q, 2), g, n_groups, p, off, xid, k, ids, scores, counts))
     ids, scores, counts
 end
+# whole retrieval requests (Inference/render.jl:240-331, `retrieval(state)`): the serving tables are loaded onto the device once, then
+# retrieve_request needs only the users' embeddings, their list items and the selected items.  kind: 0 = "{m}.dependencies",
+# 1 = "{m}.recaps", 2 = "{m}.adaptations"; 0-based CSC arrays, or colptr = nothing to clear the table.
+function retrieve_relations_set(m::Model, medium::Integer, kind::Integer, n_rows::Integer, n_cols::Integer, colptr, rowval, nzval)
+    cp = colptr === nothing ? Ptr{Int64}(C_NULL) : Vector{Int64}(colptr)
+    rv = colptr === nothing ? Ptr{Int32}(C_NULL) : Vector{Int32}(rowval)
+    nz = colptr === nothing ? Ptr{Float32}(C_NULL) : Vector{Float32}(nzval)
+    colptr === nothing || (length(cp) == n_cols + 1 && length(rv) >= cp[end] && length(nz) >= cp[end]) ||
+        error("retrieve_relations_set: CSC arrays do not match n_cols / colptr")
+    GC.@preserve cp rv nz check(ccall((:rsys_retrieve_relations_set, LIB), Int32,
+        (Ptr{Cvoid}, Int32, Int32, Int64, Int64, Ptr{Int64}, Ptr{Int32}, Ptr{Float32}), m.h, medium, kind, n_rows, n_cols, cp, rv, nz))
+end
+# a SparseMatrixCSC as it is (relations["$m.dependencies"] etc.), or nothing to clear: colptr .- 1, rowval .- 1
+set_relations!(m::Model, medium::Integer, kind::Integer, A) = A === nothing ?
+    retrieve_relations_set(m, medium, kind, 0, 0, nothing, nothing, nothing) :
+    retrieve_relations_set(m, medium, kind, size(A, 1), size(A, 2), A.colptr .- 1, A.rowval .- 1, A.nzval)
+# item_similarity["embeddings.$m"] (dim, V_m) and item_similarity["crossproject.$m"] (dim, dim) or nothing, in their own memory layout
+function retrieve_similarity_set(m::Model, medium::Integer, emb, crossproject = nothing)
+    e = emb === nothing ? Ptr{Float32}(C_NULL) : Matrix{Float32}(emb)
+    c = (emb === nothing || crossproject === nothing) ? Ptr{Float32}(C_NULL) : Matrix{Float32}(crossproject)
+    dim = emb === nothing ? 0 : size(e, 1)
+    GC.@preserve e c check(ccall((:rsys_retrieve_similarity_set, LIB), Int32, (Ptr{Cvoid}, Int32, Int64, Ptr{Float32}, Ptr{Float32}),
+        m.h, medium, dim, e, c))
+end
+# released items of the medium as a Bool / UInt8 mask over the 0-based ids (length V_m), or nothing: every item released
+function retrieve_released_set(m::Model, medium::Integer, mask = nothing)
+    x = mask === nothing ? Ptr{UInt8}(C_NULL) : Vector{UInt8}(mask)
+    GC.@preserve x check(ccall((:rsys_retrieve_released_set, LIB), Int32, (Ptr{Cvoid}, Int32, Ptr{UInt8}), m.h, medium, x))
+end
+# Q (D, n_queries); group 0-based per query or nothing; hist: one vector of (medium, matchedid, status) tuples per query in list order;
+# sel: one vector of (medium, matchedid) tuples per group.  Returns (ids, scores, counts) as retrieve_topk does.
+function retrieve_request(m::Model, medium::Integer, Q::Matrix{Float32}, k::Integer; group = nothing, n_groups::Integer = size(Q, 2),
+                          hist = nothing, sel = nothing)
+    g = group === nothing ? Ptr{Int32}(C_NULL) : Vector{Int32}(group)
+    hoff = hist === nothing ? Ptr{Int64}(C_NULL) : Int64[0; cumsum(Int64[length(h) for h in hist])]
+    hmed = hist === nothing ? Ptr{Int32}(C_NULL) : Int32[x[1] for h in hist for x in h]
+    hid = hist === nothing ? Ptr{Int32}(C_NULL) : Int32[x[2] for h in hist for x in h]
+    hst = hist === nothing ? Ptr{Int32}(C_NULL) : Int32[x[3] for h in hist for x in h]
+    soff = sel === nothing ? Ptr{Int64}(C_NULL) : Int64[0; cumsum(Int64[length(a) for a in sel])]
+    smed = sel === nothing ? Ptr{Int32}(C_NULL) : Int32[x[1] for a in sel for x in a]
+    sid = sel === nothing ? Ptr{Int32}(C_NULL) : Int32[x[2] for a in sel for x in a]
+    ids = Matrix{Int32}(undef, k, n_groups); scores = Matrix{Float32}(undef, k, n_groups); counts = Vector{Int32}(undef, n_groups)
+    GC.@preserve Q g hoff hmed hid hst soff smed sid ids scores counts check(ccall((:rsys_retrieve_request, LIB), Int32,
+        (Ptr{Cvoid}, Int32, Ptr{Float32}, Int64, Ptr{Int32}, Int32, Ptr{Int64}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Int64}, Ptr{Int32},
+         Ptr{Int32}, Int32, Ptr{Int32}, Ptr{Float32}, Ptr{Int32}),
+        m.h, medium, Q, size(Q, 2), g, n_groups, hoff, hmed, hid, hst, soff, smed, sid, k, ids, scores, counts))
+    ids, scores, counts
+end
 function infer(m::Model, task::Integer, rows::Integer, S::Integer, D::Integer)   # model.py:531-538 over every token of the resident batch
     out = task == 0 ? Array{Float32}(undef, D, 2S, rows) : Array{Float32}(undef, 2S, rows)
     GC.@preserve out check(ccall((:rsys_infer, LIB), Int32, (Ptr{Cvoid}, Int32, Ptr{Float32}, Int64), m.h, task, out, length(out))); out

@@ -74,6 +74,10 @@ _SIGS = [
     ("rsys_head_rows_get", C.c_int32, [_P, C.POINTER(C.c_int32 * 4)]),
     ("rsys_item_table", C.c_int32, [_P, _P, C.c_int64]),
     ("rsys_retrieve_topk", C.c_int32, [_P, C.c_int32, _P, C.c_int64, _P, C.c_int32, _P, _P, _P, C.c_int32, _P, _P, _P]),
+    ("rsys_retrieve_relations_set", C.c_int32, [_P, C.c_int32, C.c_int32, C.c_int64, C.c_int64, _P, _P, _P]),
+    ("rsys_retrieve_similarity_set", C.c_int32, [_P, C.c_int32, C.c_int64, _P, _P]),
+    ("rsys_retrieve_released_set", C.c_int32, [_P, C.c_int32, _P]),
+    ("rsys_retrieve_request", C.c_int32, [_P, C.c_int32, _P, C.c_int64, _P, C.c_int32, _P, _P, _P, _P, _P, _P, _P, C.c_int32, _P, _P, _P]),
     ("rsys_model_set_deterministic", C.c_int32, [_P, C.c_int32]),
     ("rsys_infer", C.c_int32, [_P, C.c_int32, _P, C.c_int64]),
     ("rsys_infer_select", C.c_int32, [_P, C.c_int32, _P, C.c_int64, _P, C.c_int64]),

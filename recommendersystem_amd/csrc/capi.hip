@@ -159,6 +159,27 @@ int32_t rsys_retrieve_topk(rsys_model* h, int32_t medium, const float* queries, 
   return model_retrieve_topk(h->m, medium, queries, n_queries, group, n_groups, prior, excl_offsets, excl_ids, k, ids_out, scores_out,
                              counts_out);
 }
+int32_t rsys_retrieve_relations_set(rsys_model* h, int32_t medium, int32_t kind, int64_t n_rows, int64_t n_cols, const int64_t* colptr,
+                                    const int32_t* rowval, const float* nzval) {
+  CHECK_HANDLE(h);
+  return model_retrieve_relations_set(h->m, medium, kind, n_rows, n_cols, colptr, rowval, nzval);
+}
+int32_t rsys_retrieve_similarity_set(rsys_model* h, int32_t medium, int64_t dim, const float* emb, const float* crossproject) {
+  CHECK_HANDLE(h);
+  return model_retrieve_similarity_set(h->m, medium, dim, emb, crossproject);
+}
+int32_t rsys_retrieve_released_set(rsys_model* h, int32_t medium, const uint8_t* mask) {
+  CHECK_HANDLE(h);
+  return model_retrieve_released_set(h->m, medium, mask);
+}
+int32_t rsys_retrieve_request(rsys_model* h, int32_t medium, const float* queries, int64_t n_queries, const int32_t* group, int32_t n_groups,
+                              const int64_t* hist_offsets, const int32_t* hist_medium, const int32_t* hist_ids, const int32_t* hist_status,
+                              const int64_t* sel_offsets, const int32_t* sel_medium, const int32_t* sel_ids, int32_t k, int32_t* ids_out,
+                              float* scores_out, int32_t* counts_out) {
+  CHECK_HANDLE(h);
+  return model_retrieve_request(h->m, medium, queries, n_queries, group, n_groups, hist_offsets, hist_medium, hist_ids, hist_status,
+                                sel_offsets, sel_medium, sel_ids, k, ids_out, scores_out, counts_out);
+}
 int32_t rsys_model_set_deterministic(rsys_model* h, int32_t on) { CHECK_HANDLE(h); return model_set_deterministic(h->m, on); }
 int32_t rsys_infer(rsys_model* h, int32_t task, float* out, int64_t n) { CHECK_HANDLE(h); ARG_CHECK(out, "null"); return model_infer(h->m, task, nullptr, 0, out, n); }
 int32_t rsys_infer_select(rsys_model* h, int32_t task, const int32_t* token_index, int64_t n_tokens, float* out, int64_t n) {

@@ -44,7 +44,8 @@ struct PhaseTimer {
   std::vector<char> open;   // per open tic: 1 = recorded, 0 = filtered out (its toc records nothing)
 };
 
-struct RetrieveWs;   // retrieve.hip
+struct RetrieveWs;       // retrieve.hip
+struct RetrievalTables;  // retrieve_request.hip
 
 struct Model {
   rsys_config cfg;
@@ -264,6 +265,7 @@ struct Model {
   PhaseTimer timer;
   std::vector<hipEvent_t> step_marks;   // rsys_step_mark: one event per optimizer-step boundary (per-step time distribution)
   RetrieveWs* rws = nullptr;            // rsys_retrieve_topk's workspace (allocated on first use)
+  RetrievalTables* rtab = nullptr;      // rsys_retrieve_request's serving tables and workspace (not part of checkpoints)
 };
 
 struct Optimizer {
@@ -309,6 +311,20 @@ int model_set_deterministic(Model* m, int on);
 int model_retrieve_topk(Model* m, int medium, const float* queries, int64_t nq, const int32_t* group, int32_t ng, const float* prior,
                         const int64_t* excl_off, const int32_t* excl_ids, int32_t k, int32_t* ids_out, float* scores_out, int32_t* counts_out);
 void retrieve_free(Model* m);
+// the same pipeline with a device-side initialiser of the group score rows sc [n_groups][V_m] (prior and NaN masks)
+using RetrieveInit = std::function<int(float* sc, hipStream_t s)>;
+int model_retrieve_run(Model* m, int medium, const float* queries, int64_t nq, const int32_t* group, int32_t ng, const RetrieveInit& init,
+                       int32_t k, int32_t* ids_out, float* scores_out, int32_t* counts_out);
+// retrieve_request.hip: the serving tables of rsys_retrieve_request (relations, item similarity, released set) and the request
+int model_retrieve_relations_set(Model* m, int medium, int kind, int64_t n_rows, int64_t n_cols, const int64_t* colptr, const int32_t* rowval,
+                                 const float* nzval);
+int model_retrieve_similarity_set(Model* m, int medium, int64_t dim, const float* emb, const float* crossproject);
+int model_retrieve_released_set(Model* m, int medium, const uint8_t* mask);
+int model_retrieve_request(Model* m, int medium, const float* queries, int64_t nq, const int32_t* group, int32_t ng, const int64_t* hist_off,
+                           const int32_t* hist_medium, const int32_t* hist_ids, const int32_t* hist_status, const int64_t* sel_off,
+                           const int32_t* sel_medium, const int32_t* sel_ids, int32_t k, int32_t* ids_out, float* scores_out,
+                           int32_t* counts_out);
+void retrieve_tables_free(Model* m);
 int op_topk(const float* scores, int64_t ld, int32_t rows, int32_t V, int32_t k, int32_t* ids, float* vals, int32_t* counts);
 int optimizer_step(Optimizer* o, float lr_factor, float clip, float grad_div);
 

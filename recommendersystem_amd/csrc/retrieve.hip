@@ -376,7 +376,8 @@ void retrieve_free(Model* m) {
 
 template <typename T>
 static int retrieve_t(Model* m, int medium, const float* queries, int64_t nq, const int32_t* group, int ng, const float* prior,
-                      const int64_t* excl_off, const int32_t* excl_ids, int k, int32_t* ids_out, float* scores_out, int32_t* counts_out) {
+                      const int64_t* excl_off, const int32_t* excl_ids, const RetrieveInit* init, int k, int32_t* ids_out, float* scores_out,
+                      int32_t* counts_out) {
   const int D = m->D, Vm = medium == 0 ? m->V0 : m->V1, vs = medium == 0 ? 0 : m->V0;
   hipStream_t s = m->stream;
   // host-side index arrays: the queries of each group in query order, per chunk the range of them it holds, exclusion positions
@@ -459,7 +460,8 @@ static int retrieve_t(Model* m, int medium, const float* queries, int64_t nq, co
   if constexpr (is_bf16<T>::value) RC(launch_cast<T>(qf, qt, (long long)nq * D, s));
   HIP_CHECK(hipMemcpyAsync(d_members, members.data(), members.size() * 4, hipMemcpyHostToDevice, s));
   HIP_CHECK(hipMemcpyAsync(d_ranges, ranges.data(), ranges.size() * sizeof(int2), hipMemcpyHostToDevice, s));
-  if (prior) HIP_CHECK(hipMemcpyAsync(sc, prior, (size_t)ng * Vm * 4, hipMemcpyHostToDevice, s));
+  if (init) RC((*init)(sc, s));   // the device-side initialiser of the group score rows (rsys_retrieve_request)
+  else if (prior) HIP_CHECK(hipMemcpyAsync(sc, prior, (size_t)ng * Vm * 4, hipMemcpyHostToDevice, s));
   else HIP_CHECK(hipMemsetAsync(sc, 0, (size_t)ng * Vm * 4, s));
   if (!xpos.empty()) {
     HIP_CHECK(hipMemcpyAsync(d_xpos, xpos.data(), xpos.size() * 8, hipMemcpyHostToDevice, s));
@@ -512,8 +514,17 @@ int model_retrieve_topk(Model* m, int medium, const float* queries, int64_t nq, 
   ARG_CHECK((excl_off == nullptr) == (excl_ids == nullptr), "retrieve_topk: excl_offsets and excl_ids are both given or both NULL");
   const int Vm = medium == 0 ? m->V0 : m->V1;
   ARG_CHECK(k >= 1 && k <= std::min(Vm, RT_MAXK), "retrieve_topk: 1 <= k <= min(V_m, 8192)");
-  return m->bf16_mode ? retrieve_t<bf16>(m, medium, queries, nq, group, ng, prior, excl_off, excl_ids, k, ids_out, scores_out, counts_out)
-                      : retrieve_t<float>(m, medium, queries, nq, group, ng, prior, excl_off, excl_ids, k, ids_out, scores_out, counts_out);
+  return m->bf16_mode ? retrieve_t<bf16>(m, medium, queries, nq, group, ng, prior, excl_off, excl_ids, nullptr, k, ids_out, scores_out, counts_out)
+                      : retrieve_t<float>(m, medium, queries, nq, group, ng, prior, excl_off, excl_ids, nullptr, k, ids_out, scores_out, counts_out);
+}
+
+// the pipeline of model_retrieve_topk with the group score rows [n_groups][V_m] filled on the device by `init` (called on the model's
+// stream after the workspace is in place): the prior and the NaN masks of rsys_retrieve_request.  The caller has checked the arguments
+// model_retrieve_topk checks.
+int model_retrieve_run(Model* m, int medium, const float* queries, int64_t nq, const int32_t* group, int32_t ng, const RetrieveInit& init,
+                       int32_t k, int32_t* ids_out, float* scores_out, int32_t* counts_out) {
+  return m->bf16_mode ? retrieve_t<bf16>(m, medium, queries, nq, group, ng, nullptr, nullptr, nullptr, &init, k, ids_out, scores_out, counts_out)
+                      : retrieve_t<float>(m, medium, queries, nq, group, ng, nullptr, nullptr, nullptr, &init, k, ids_out, scores_out, counts_out);
 }
 
 int op_topk(const float* scores, int64_t ld, int32_t rows, int32_t V, int32_t k, int32_t* ids, float* vals, int32_t* counts) {

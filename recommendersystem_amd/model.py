@@ -17,6 +17,7 @@ and calls loss.backward() (train.py:264-272); here the task weights and the
 All arrays are numpy; device memory is owned by the library.
 """
 import ctypes as C
+import itertools
 import os
 
 import numpy as np
@@ -392,6 +393,95 @@ class RecommenderModel:
                                        ids.ctypes.data, scores.ctypes.data, counts.ctypes.data))
         return ids, scores, counts
 
+    # ---- whole retrieval requests (rsys_retrieve_request): serving tables loaded once, then one call per batch of requests
+    def _vocab(self, medium):
+        if medium not in (0, 1):
+            raise ValueError("medium must be 0 or 1")
+        return self.config["vocab_sizes"][f"{int(medium)}_matchedid"]
+
+    def set_retrieval_relations(self, medium, dependencies=None, recaps=None, adaptations=None):
+        """Loads the relation matrices of `medium` ("{m}.dependencies", "{m}.recaps": V_m x V_m; "{m}.adaptations": V_m x V_{1-m}) onto
+        the device for `retrieve_request`.  Each is a 0-based CSC `(indptr, indices, data, shape)` tuple or any object with those
+        attributes (a scipy CSC matrix); None clears that table.  Stored values must be finite and >= 0; stored zeros are dropped."""
+        for kind, a in enumerate((dependencies, recaps, adaptations)):
+            if a is None:
+                check(lib().rsys_retrieve_relations_set(self._h, int(medium), kind, 0, 0, None, None, None))
+                continue
+            indptr, indices, data, shape = csc_parts(a)
+            check(lib().rsys_retrieve_relations_set(self._h, int(medium), kind, int(shape[0]), int(shape[1]), indptr.ctypes.data,
+                                                    indices.ctypes.data, data.ctypes.data))
+
+    def set_item_similarity(self, medium, embeddings=None, crossproject=None):
+        """Loads the item-similarity table of `medium` for `retrieve_request`'s prior: `embeddings` (V_m, dim), row i = item i's vector
+        (Julia's "embeddings.{m}" is its transpose, dim x V_m), `crossproject` (dim, dim) the matrix that maps a vector of `medium` into
+        the other medium (x -> crossproject @ x, Julia's "crossproject.{m}") or None.  embeddings None clears both."""
+        if embeddings is None:
+            check(lib().rsys_retrieve_similarity_set(self._h, int(medium), 0, None, None))
+            return
+        e = np.ascontiguousarray(embeddings, np.float32)
+        if e.ndim != 2 or e.shape[0] != self._vocab(medium):
+            raise ValueError(f"embeddings have shape {e.shape}, expected ({self._vocab(medium)}, dim)")
+        c = None
+        if crossproject is not None:
+            c = np.asfortranarray(crossproject, np.float32)                  # column-major, as Julia holds it
+            if c.shape != (e.shape[1], e.shape[1]):
+                raise ValueError(f"crossproject has shape {c.shape}, expected {(e.shape[1], e.shape[1])}")
+        check(lib().rsys_retrieve_similarity_set(self._h, int(medium), e.shape[1], e.ctypes.data, None if c is None else c.ctypes.data))
+
+    def set_released(self, medium, ids_or_mask=None):
+        """The released items of `medium` (render.jl keeps only `keys(get_media_info(m))`): a boolean mask over [0, V_m) or an array
+        of medium-local ids; None: every item is released."""
+        if ids_or_mask is None:
+            check(lib().rsys_retrieve_released_set(self._h, int(medium), None))
+            return
+        Vm = self._vocab(medium)
+        a = np.asarray(ids_or_mask)
+        if a.dtype == np.bool_:
+            if a.shape != (Vm,):
+                raise ValueError(f"released mask has shape {a.shape}, expected ({Vm},)")
+            mask = a.astype(np.uint8)
+        else:
+            ids = a.astype(np.int64).reshape(-1)
+            if ids.size and (ids.min() < 0 or ids.max() >= Vm):
+                raise ValueError(f"released ids must be in [0, {Vm})")
+            mask = np.zeros(Vm, np.uint8)
+            mask[ids] = 1
+        check(lib().rsys_retrieve_released_set(self._h, int(medium), np.ascontiguousarray(mask).ctypes.data))
+
+    def retrieve_request(self, queries, medium, k, group=None, histories=None, selected=None):
+        """A whole render.jl `retrieval(state)` per group on the device (rsys_retrieve_request): the scores of `retrieve_topk` plus the
+        item-similarity prior of the group's selected items, with the relation masks, item 0, the selected items and unreleased items
+        masked, from the tables loaded by set_retrieval_relations / set_item_similarity / set_released.  `histories`: one list per query
+        of (medium, id, status) list items in list order (None: no lists); `selected`: one list per group of (medium, id) items in
+        the request's order (None: none).  Returns (ids (n_groups, k) int32, scores (n_groups, k) float32, counts (n_groups,) int32)."""
+        q = np.ascontiguousarray(queries, np.float32)
+        if q.ndim == 1:
+            q = q[None, :]
+        n = q.shape[0]
+        gp = None if group is None else np.ascontiguousarray(group, np.int32).reshape(-1)
+        if gp is not None and gp.size != n:
+            raise ValueError(f"group has {gp.size} entries for {n} queries")
+        ng = n if gp is None else (int(gp.max()) + 1 if gp.size else 0)
+        h = None
+        if histories is not None:
+            if len(histories) != n:
+                raise ValueError(f"histories has {len(histories)} lists for {n} queries")
+            h = triples_csr(histories, 3)
+        sl = None
+        if selected is not None:
+            if len(selected) != ng:
+                raise ValueError(f"selected has {len(selected)} lists for {ng} groups")
+            sl = triples_csr(selected, 2)
+        ids = np.empty((ng, int(k)), np.int32)
+        scores = np.empty((ng, int(k)), np.float32)
+        counts = np.empty(ng, np.int32)
+        ptr = lambda a: None if a is None else a.ctypes.data
+        hp = (None,) * 4 if h is None else tuple(ptr(a) for a in h)
+        sp = (None,) * 3 if sl is None else tuple(ptr(a) for a in sl)
+        check(lib().rsys_retrieve_request(self._h, int(medium), q.ctypes.data, n, ptr(gp), ng, *hp, *sp, int(k), ids.ctypes.data,
+                                          scores.ctypes.data, counts.ctypes.data))
+        return ids, scores, counts
+
     def trunk_output(self, rows):
         S = self.config["max_sequence_length"]; D = self.config["embed_dim"]
         out = np.empty((rows, 2 * S, D), np.float32)
@@ -503,6 +593,39 @@ def exclusion_csr(exclude, n_groups):
     off[1:] = np.cumsum([p.size for p in parts])
     ids = np.concatenate(parts).astype(np.int32) if parts and off[-1] else np.zeros(1, np.int32)
     return off, np.ascontiguousarray(ids)
+
+
+def csc_parts(a):
+    """(indptr int64, indices int32, data float32, shape) of a 0-based CSC matrix given as an (indptr, indices, data, shape) tuple or
+    an object with those attributes (a scipy CSC matrix; scipy itself is not needed)."""
+    if isinstance(a, (tuple, list)):
+        indptr, indices, data, shape = a
+    else:
+        indptr, indices, data, shape = a.indptr, a.indices, a.data, a.shape
+    indptr = np.ascontiguousarray(indptr, np.int64).reshape(-1)
+    indices = np.ascontiguousarray(indices, np.int32).reshape(-1)
+    data = np.ascontiguousarray(data, np.float32).reshape(-1)
+    shape = tuple(int(x) for x in shape)
+    if len(shape) != 2 or indptr.size != shape[1] + 1:
+        raise ValueError(f"CSC indptr has {indptr.size} entries for shape {shape}")
+    if indices.size != data.size or indptr[-1] > indices.size:
+        raise ValueError("CSC indices and data must hold indptr[-1] entries")
+    return indptr, np.ascontiguousarray(indices[:max(int(indptr[-1]), 0)]), np.ascontiguousarray(data[:max(int(indptr[-1]), 0)]), shape
+
+
+def triples_csr(lists, width):
+    """(offsets int64 [n + 1], then `width` int32 columns) of a list of per-row sequences of `width`-tuples (ragged; order kept)."""
+    lens = [len(x) for x in lists]
+    off = np.zeros(len(lists) + 1, np.int64)
+    off[1:] = np.cumsum(lens)
+    n = int(off[-1])
+    if n == 0:
+        flat = np.zeros((1, width), np.int64)
+    elif all(isinstance(x, np.ndarray) for x in lists):
+        flat = np.concatenate([np.asarray(x, np.int64).reshape(-1, width) for x in lists])
+    else:   # (one pass over the Python tuples: a request's lists hold tens of thousands of them)
+        flat = np.fromiter(itertools.chain.from_iterable(itertools.chain.from_iterable(lists)), np.int64, count=n * width).reshape(n, width)
+    return (off,) + tuple(np.ascontiguousarray(flat[:, j], np.int32) for j in range(width))
 
 
 def gather_rows(host_group, rows):

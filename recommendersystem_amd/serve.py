@@ -226,3 +226,84 @@ def retrieve(model, embeds, medium, k, groups=None, exclude=None, prior=None, co
             s = (s.astype(np.float64) + members[j] * np.log(float(np.asarray(coefs).reshape(-1)[0]))).astype(np.float32)
         out.append((ids[j, :n].copy(), s))
     return out
+
+
+# ---------------------------------------------------------------- whole retrieval requests (render.jl `retrieval(state)`)
+RELATION_KINDS = ("dependencies", "recaps", "adaptations")
+
+
+def julia_csc(a):
+    """A relation matrix as `RecommenderModel.set_retrieval_relations` takes it: a Julia-shaped SparseMatrixCSC (a dict or object
+    with 1-based `colptr` / `rowval`, `nzval` and `m` / `n`, as JLD2 stores it) becomes a 0-based (indptr, indices, data, shape);
+    a (indptr, indices, data, shape) tuple or an object with those attributes (scipy CSC) is 0-based already and passes through."""
+    get = (lambda k: a[k]) if isinstance(a, dict) else (lambda k: getattr(a, k))
+    has = (lambda k: k in a) if isinstance(a, dict) else (lambda k: hasattr(a, k))
+    if has("colptr"):
+        shape = (int(np.asarray(get("m"))), int(np.asarray(get("n"))))
+        return (np.asarray(get("colptr"), np.int64) - 1, np.asarray(get("rowval"), np.int64) - 1, np.asarray(get("nzval"), np.float32),
+                shape)
+    return a
+
+
+def load_retrieval_tables(model, relations, item_similarity, released=None):
+    """Loads render.jl's serving tables onto the device once (`relations`, `item_similarity`: its own dicts, keyed "{m}.dependencies",
+    "{m}.recaps", "{m}.adaptations", "embeddings.{m}", "crossproject.{m}").  Relation matrices are Julia-shaped SparseMatrixCSC dicts
+    or 0-based CSC tuples / objects (`julia_csc`); "embeddings.{m}" is Julia's dim x V_m matrix (an array of shape (V_m, dim) is taken
+    as its transpose); "crossproject.{m}" the dim x dim matrix as Julia indexes it.  `released`: {m: mask or ids} (render.jl's
+    `keys(get_media_info(m))`, 0-based) or None.  A medium whose keys are absent is left as it is."""
+    for m in (0, 1):
+        if all(f"{m}.{kind}" in relations for kind in RELATION_KINDS):
+            model.set_retrieval_relations(m, *(julia_csc(relations[f"{m}.{kind}"]) for kind in RELATION_KINDS))
+        if f"embeddings.{m}" in item_similarity:
+            e = np.asarray(item_similarity[f"embeddings.{m}"], np.float32)
+            Vm = model.config["vocab_sizes"][f"{m}_matchedid"]
+            if e.ndim == 2 and e.shape[1] == Vm:
+                e = e.T
+            model.set_item_similarity(m, e, item_similarity.get(f"crossproject.{m}"))
+        if released is not None and m in released:
+            model.set_released(m, released[m])
+
+
+def request_arrays(states, medium):
+    """The arguments of `RecommenderModel.retrieve_request` for render.jl request states of one medium, one group per state: the
+    users' "{medium}.retrieval" embeddings (n, D), their group ids, each user's list items as (medium, matchedid, status) in list
+    order, and each state's selected items as (medium, matchedid) in order."""
+    key = f"{medium}.retrieval"
+    q, group, hist, sel = [], [], [], []
+    for g, st in enumerate(states):
+        if not st["users"]:
+            raise ValueError("retrieval: every state needs at least one user")
+        for u in st["users"]:
+            q.append(np.asarray(u["embeds"][key], np.float32).reshape(-1))
+            group.append(g)
+            hist.append([(int(x["medium"]), int(x["matchedid"]), int(x["status"])) for x in u["user"]["items"]])
+        sel.append([(int(a["medium"]), int(a["matchedid"])) for a in st["items"]])
+    return np.stack(q), np.asarray(group, np.int32), hist, sel
+
+
+def retrieval(model, states, k=1024, coefs=None):
+    """render.jl `retrieval(state)` on the device for a list of request states (`medium`, `items`, `users[*].embeds`,
+    `users[*].user.items`), one group per state, on the tables of `load_retrieval_tables`: prior of the selected items, summed log
+    soft-max of the users, relation / watched / selected / item-0 / unreleased masks, best first.  `coefs`: the registry's retrieval
+    coefficient (adds n_users * log(coef), the order does not change).  Returns one (ids, scores) pair per state, ids 0-based
+    medium-local, at most min(k, V_m, 8192) of them."""
+    out = [None] * len(states)
+    by_medium = {}
+    for j, st in enumerate(states):
+        m = int(st["medium"])
+        if m not in (0, 1):
+            raise ValueError("retrieval: medium must be 0 or 1")
+        by_medium.setdefault(m, []).append(j)
+    for m, idx in sorted(by_medium.items()):
+        q, group, hist, sel = request_arrays([states[j] for j in idx], m)
+        Vm = model.config["vocab_sizes"][f"{m}_matchedid"]
+        kk = min(int(k), Vm, 8192)
+        ids, scores, counts = model.retrieve_request(q, m, kk, group=group, histories=hist, selected=sel)
+        members = np.bincount(group, minlength=len(idx))
+        for g, j in enumerate(idx):
+            n = int(counts[g])
+            s = scores[g, :n]
+            if coefs is not None:
+                s = (s.astype(np.float64) + members[g] * np.log(float(np.asarray(coefs).reshape(-1)[0]))).astype(np.float32)
+            out[j] = (ids[g, :n].copy(), s)
+    return out
