@@ -53,6 +53,13 @@ int32_t rsys_op_gemm_rows(int32_t dtype, const void* A, const void* B, void* C, 
  * (model.py:153-170 backward); rows >= *k_dev may hold anything */
 int32_t rsys_op_gemm_klimit(int32_t dtype, const void* A, const void* B, void* C, int32_t M, int32_t N, int32_t K,
                             int64_t lda, int64_t ldb, int64_t ldc, int32_t accumulate, const int32_t* k_dev);
+/* the kernel launch_gemm would run for this problem, decided on the host without launching anything: `tag` gets its timing tag
+ * ("nt", "nn", "tn", "8p", "8c", "4p", "8t", "4k", "8ts", "8s", "8m"), `splits` the K-split count it runs with.  Fields as in
+ * GemmParams (csrc/gemm.hpp); `set` says which pointer fields the problem has: bit 0 m_dev, 1 k_dev, 2 slab, 3 rope_cs, 4 rope_pos,
+ * 5 C2.  `cus`: the CU count the route assumes.  Reads the RSYS_GEMM* switches as parsed last (rsys_switches_reload). */
+int32_t rsys_debug_gemm_route(int32_t dtype, int32_t M, int32_t N, int32_t K, int64_t lda, int64_t ldb, int64_t ldc, int32_t a_km,
+                              int32_t b_km, int32_t a_f32, int32_t c_f32, int32_t epi, int32_t splitk, int32_t flags, float alpha,
+                              int32_t accum, int32_t set, int32_t m_expect, int32_t cus, char* tag, int32_t tag_bytes, int32_t* splits);
 /* attention fwd+bwd on caller-provided device buffers (T-typed): qkv [B*T][(H+2KV)*hd] post-RoPE, dO [B*T][H*hd],
  * uid/tm [B*T] int32 with 0 <= uid < 2^19 and 0 <= tm < 4096, rope tables [T][hd/2] f32; outputs O [B*T][H*hd], lse [B][H][T] f32,
  * dqkv [B*T][(H+2KV)*hd] (gradients w.r.t. the un-rotated q, k and v) */

@@ -353,7 +353,7 @@ int32_t rsys_adamw_step_zero1(rsys_optimizer* o, rsys_comm* c, float lr_factor, 
   CHECK_HANDLE(o); CHECK_HANDLE(c);
   Model* m = o->o.m;
   m->grad_bucket_hook = nullptr; m->reduced.clear(); m->early_reduced = 0;   // (no early buckets in this mode: the step reduces the whole gradient)
-  m->gemm_flags &= ~2;
+  m->gemm_flags &= ~GEMM_ONE_WG_PER_TILE;
   return optimizer_step_zero1(&o->o, c, lr_factor, clip, grad_div);
 }
 
@@ -485,7 +485,7 @@ int32_t rsys_set_grad_sync(rsys_model* h, rsys_comm* c) {
   m->bucket_log.clear(); m->bucket_phase = 0;
   m->grad_bucket_hook = nullptr;
   m->table_head_hook = nullptr;
-  m->gemm_flags &= ~2;
+  m->gemm_flags &= ~GEMM_ONE_WG_PER_TILE;
   if (!comm_active(c) || m->cfg.finetune) return RSYS_OK;
   if (m->split_table && m->bf16_mode && !m->sharded) {
     // the head part of the item table's gradient, complete when heads() returns: summed over the ranks into tbl_R while the trunk
@@ -553,7 +553,7 @@ int32_t rsys_allreduce_grads(rsys_model* h, rsys_comm* c) {
   const bool split = m->split_head_reduced && comm_active(c) && model_finalize_splittable(m);   // (else: G[E] holds the whole local gradient, the dense path is right)
   m->split_head_reduced = false;
   m->split_head_event = nullptr;   // (everything below is ordered behind the head reduce on the communicator's stream itself)
-  m->gemm_flags &= ~2;             // the optimizer waits for the reduction: nothing after this call overlaps with it
+  m->gemm_flags &= ~GEMM_ONE_WG_PER_TILE;   // the optimizer waits for the reduction: nothing after this call overlaps with it
   m->early_reduced = 0;
   for (auto& r : m->reduced) m->early_reduced += r.second - r.first;
   if (!comm_active(c)) { m->reduced.clear(); return model_finalize_grads(m); }
@@ -712,6 +712,28 @@ int32_t rsys_op_gemm_klimit(int32_t dtype, const void* A, const void* B, void* C
                                     : launch_gemm<float>(p, false, false, true, true, nullptr);
   if (rc) return rc;
   HIP_CHECK(hipDeviceSynchronize());
+  return RSYS_OK;
+}
+
+// the routing of launch_gemm, on the host only: a GemmParams from the fields the route reads (pointer fields only as set / unset)
+int32_t rsys_debug_gemm_route(int32_t dtype, int32_t M, int32_t N, int32_t K, int64_t lda, int64_t ldb, int64_t ldc, int32_t a_km,
+                              int32_t b_km, int32_t a_f32, int32_t c_f32, int32_t epi, int32_t splitk, int32_t flags, float alpha,
+                              int32_t accum, int32_t set, int32_t m_expect, int32_t cus, char* tag, int32_t tag_bytes, int32_t* splits) {
+  ARG_CHECK(tag != nullptr && tag_bytes >= 4 && splits != nullptr, "rsys_debug_gemm_route: null output");
+  static int dummy[4];   // (never dereferenced: the route only tests these for null)
+  GemmParams p{};
+  p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldb = ldb; p.ldc = ldc; p.ldc2 = ldc; p.ldr = ldc;
+  p.c_f32 = c_f32; p.epi = epi; p.splitk = splitk; p.flags = flags; p.alpha = alpha; p.accum = accum; p.m_expect = m_expect;
+  if (set & 1) p.m_dev = dummy;
+  if (set & 2) p.k_dev = dummy;
+  if (set & 4) p.slab = (float*)dummy;
+  if (set & 8) p.rope_cs = (const float*)dummy;
+  if (set & 16) p.rope_pos = dummy;
+  if (set & 32) p.C2 = dummy;
+  const GemmRoute r = dtype == RSYS_DTYPE_BF16 ? gemm_route<bf16>(p, a_f32 != 0, false, a_km != 0, b_km != 0, cus)
+                                                : gemm_route<float>(p, false, false, a_km != 0, b_km != 0, cus);
+  snprintf(tag, tag_bytes, "%s", gemm_kernel_tags[r.kernel]);
+  *splits = r.splitk;
   return RSYS_OK;
 }
 

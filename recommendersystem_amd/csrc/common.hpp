@@ -45,6 +45,12 @@ void set_error(const std::string& msg);
     }                                                                                     \
   } while (0)
 
+// CUs of the current device, queried once per process (256 if the query fails): the grids of the persistent kernels
+inline int cu_count() {
+  static const int n = [] { int dev = 0, v = 0; return hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0 ? v : 256; }();
+  return n;
+}
+
 // ---- type helpers
 template <typename T> struct is_bf16 { static constexpr bool value = false; };
 template <> struct is_bf16<bf16> { static constexpr bool value = true; };

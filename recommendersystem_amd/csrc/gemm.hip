@@ -486,6 +486,18 @@ static int pick_rowmajor_kernel(const GemmParams& p) {
   return 0;
 }
 
+// the one-stream form of the 256x256 pipeline (gemm8c.hip) takes the epilogue classes it has kernels for; RSYS_GEMM8C=0: A/B switch
+// (gemm8p.hip for all of them); RSYS_DEBUG_8P (timing flags of gemm8p's kernel) keeps gemm8p
+static bool use_8c(const GemmParams& p) { return sw().gemm8c && sw().debug_8p == 0 && gemm8c_eligible(p); }
+
+// gemm8c's plain bf16 stores on the long-K four-wave loop (gemm4p.hip): RSYS_GEMM4P: 1 = the rule below, 0 = never, 2 = wherever eligible
+static bool use_4p(const GemmParams& p) {
+  const int mode = sw().gemm4p;
+  if (mode == 0 || !gemm4p_eligible(p)) return false;
+  if (mode == 2) return true;
+  return p.K >= 8192 && p.N >= 1024 && (long long)(p.M / 256) * (p.N / 256) >= 256;   // (see gemm4p.hip's header: where the product is MFMA-bound)
+}
+
 // K-major bf16 operands with the atomic epilogue (weight gradients): the LDS-DMA pipeline unless RSYS_GEMM_KERNEL_TN=1
 static bool use_8p_tn(const GemmParams& p) {
   const int e = sw().gemm_kernel_tn;
@@ -511,7 +523,7 @@ static bool use_8p_tn_store(const GemmParams& p) {
 // row-major bf16 operands with the atomic epilogue: the LDS-DMA split-K form when the output is large enough for it
 static bool use_8p_nt_splitk(const GemmParams& p) {
   if (p.epi != EPI_ATOMIC || !gemm8p_nt_splitk_eligible(p)) return false;
-  if (sw().gemm_kernel_nt_splitk == 2 || (p.flags & 128)) return true;   // 2: force; flags bit 7: the caller wants the 256x256 split-K form for a few tiles (table_forward's tail)
+  if (sw().gemm_kernel_nt_splitk == 2 || (p.flags & GEMM_SPLITK_256)) return true;   // 2: force; the flag: the caller wants the 256x256 split-K form for a few tiles (table_forward's tail)
   // (RSYS_GEMM_KERNEL_NT_SPLITK=2: tools/ab_dw_rowmajor.py: the trunk's weight-gradient shapes on K-contiguous copies)
   // from 32 output tiles on; from 8 when K is long enough that the K splits fill the chip by themselves (cfg-2's metadata-projection
   // gradient: 256 x 6148 outputs = 25 tiles, K = 100 K: 0.59 -> 0.33 ms against the 128x128 kernel, profiles/r6b_*)
@@ -531,28 +543,45 @@ static bool use_8p_mix(const GemmParams& p) {
   return mode == 2 || (p.K >= 8192 && p.N >= 512);
 }
 
-const char* gemm_kernel_name(const GemmParams& p0, bool bf16_mode, bool a_f32, bool b_f32, bool a_km, bool b_km) {
+const char* const gemm_kernel_tags[GK_COUNT] = {"nt", "nn", "tn", "8p", "8c", "4p", "8t", "4k", "8ts", "8s", "8m"};
+
+// The rules above, in launch_gemm's order; what none claims runs on this file's kernel (nt / nn / tn by operand layout) with the caller's
+// K splits rounded up to whole XCDs (see the kernel's work mapping).  The thresholds are measured on 256 CUs: none scales with `cus` yet.
+template <typename CT>
+GemmRoute gemm_route(const GemmParams& p0, bool a_f32, bool b_f32, bool a_km, bool b_km, int cus) {
   GemmParams p = p0;
   if (p.splitk < 1) p.splitk = 1;
-  if (bf16_mode && !a_km && !b_km && !a_f32 && !b_f32) {
-    const int k = pick_rowmajor_kernel(p);
-    if (k == 2) return gemm8p_forwards_to_8c(p) ? (gemm4p_takes(p) ? "4p" : "8c") : "8p";
+  if (p.splitk > 1) p.splitk = (p.splitk + 7) / 8 * 8;
+  const GemmRoute fallback{a_km ? GK_TN : (b_km ? GK_NN : GK_NT), p.splitk};
+  if (!is_bf16<CT>::value || a_f32 || b_f32) return fallback;
+  if (!a_km && !b_km) {
+    if (use_8p_nt_splitk(p)) return {GK_8S, gemm8p_splits(p, false)};
+    if (pick_rowmajor_kernel(p) == 2) {
+      if (!use_8c(p)) return {GK_8P, p.splitk};
+      // gemm4p runs its persistent grid whatever GEMM_ONE_WG_PER_TILE and GEMM_REVERSE_ROWS say (gemm8c handed over
+      // before it read them)
+      return {use_4p(p) ? GK_4P : GK_8C, p.splitk};
+    }
+  } else if (!a_km && b_km) {
+    if (use_8p_mix(p)) return {GK_8M, p.splitk};
+  } else if (a_km && b_km) {
+    if (use_8p_tn(p)) return {gemm4k_eligible(p) ? GK_4K : GK_8T, gemm8p_splits(p, true)};   // (gemm4k: no slab, gemm8p's grid and work mapping)
+    if (use_8p_tn_store(p)) return {GK_8TS, p.splitk};
   }
-  if (bf16_mode && a_km && b_km && !a_f32 && !b_f32 && use_8p_tn(p)) { GemmParams q = p; q.splitk = 8; return gemm4k_eligible(q) ? "4k" : "8t"; }
-  if (bf16_mode && a_km && b_km && !a_f32 && !b_f32 && use_8p_tn_store(p)) return "8ts";
-  if (bf16_mode && !a_km && !b_km && !a_f32 && !b_f32 && use_8p_nt_splitk(p)) return "8s";
-  if (bf16_mode && !a_km && b_km && !a_f32 && !b_f32 && use_8p_mix(p)) return "8m";
-  return a_km ? "tn" : (b_km ? "nn" : "nt");
+  return fallback;
+}
+
+const char* gemm_kernel_name(const GemmParams& p, bool bf16_mode, bool a_f32, bool b_f32, bool a_km, bool b_km) {
+  const GemmRoute r = bf16_mode ? gemm_route<bf16>(p, a_f32, b_f32, a_km, b_km, cu_count()) : gemm_route<float>(p, a_f32, b_f32, a_km, b_km, cu_count());
+  return gemm_kernel_tags[r.kernel];
 }
 
 template <typename CT>
 int launch_gemm(const GemmParams& p0, bool a_f32, bool b_f32, bool a_km, bool b_km, hipStream_t s) {
   GemmParams p = p0;
   constexpr int EPC = MmaT<CT>::EPC;
-  if (p.splitk < 1) p.splitk = 1;
-  if (p.splitk > 1) p.splitk = (p.splitk + 7) / 8 * 8;   // one K split never straddles XCDs (see the kernel's work mapping)
   ARG_CHECK(p.M > 0 && p.N > 0 && p.K > 0, "gemm: empty problem");
-  ARG_CHECK(p.splitk == 1 || p.epi == EPI_ATOMIC, "gemm: split-K needs the atomic epilogue");
+  ARG_CHECK(p.splitk <= 1 || p.epi == EPI_ATOMIC, "gemm: split-K needs the atomic epilogue");
   const int ea = (is_bf16<CT>::value && a_f32) ? 4 : EPC;
   const int eb = (is_bf16<CT>::value && b_f32) ? 4 : EPC;
   ARG_CHECK(p.lda % ea == 0 && p.ldb % eb == 0, "gemm: leading dimensions must keep 16-byte row alignment");
@@ -570,13 +599,17 @@ int launch_gemm(const GemmParams& p0, bool a_f32, bool b_f32, bool a_km, bool b_
     ARG_CHECK(p.ldc % 8 == 0 && (p.C2 == nullptr || (p.ldc2 % 8 == 0 && ((uintptr_t)p.C2 % 16) == 0)), "gemm: bf16 outputs need ldc % 8 == 0");
   if (p.epi == EPI_QKV_ROPE) ARG_CHECK((p.hd & (p.hd - 1)) == 0, "gemm: head_dim must be a power of two");
   if constexpr (!is_bf16<CT>::value) { a_f32 = false; b_f32 = false; }
-  if constexpr (is_bf16<CT>::value) {
-    if (!a_km && !b_km && !a_f32 && !b_f32 && use_8p_nt_splitk(p)) return launch_gemm8p_nt_splitk(p, s);
-    if (!a_km && !b_km && !a_f32 && !b_f32) {
-      const int k = pick_rowmajor_kernel(p);
-      if (k == 2) return launch_gemm8p(p, s);
-    }
-    if (!a_km && b_km && !a_f32 && !b_f32 && use_8p_mix(p)) {
+  const GemmRoute r = gemm_route<CT>(p, a_f32, b_f32, a_km, b_km, cu_count());
+  p.splitk = r.splitk;
+  switch (r.kernel) {
+    case GK_8S: return launch_gemm8p_nt_splitk(p, s);
+    case GK_8P: return launch_gemm8p(p, s);
+    case GK_8C: return launch_gemm8c(p, s);
+    case GK_4P: return launch_gemm4p(p, s);
+    case GK_8T: return launch_gemm8p_tn(p, s);
+    case GK_4K: return launch_gemm4k(p, s);
+    case GK_8TS: return launch_gemm8p_tn_store(p, s);
+    case GK_8M: {
       GemmParams q = p; q.K = p.K & ~63;
       { const int rc_ = launch_gemm8p_mix(q, s); if (rc_ != RSYS_OK) return rc_; }
       if ((p.K & 63) == 0) return RSYS_OK;
@@ -584,35 +617,23 @@ int launch_gemm(const GemmParams& p0, bool a_f32, bool b_f32, bool a_km, bool b_
       t.A = (const char*)p.A + (size_t)q.K * 2; t.B = (const char*)p.B + (size_t)q.K * p.ldb * 2; t.K = p.K & 63; t.splitk = 1;
       return launch_one<CT, false, false, false, true>(t, s);
     }
-    if (a_km && b_km && !a_f32 && !b_f32 && use_8p_tn(p)) return launch_gemm8p_tn(p, s);
-    if (a_km && b_km && !a_f32 && !b_f32 && use_8p_tn_store(p)) return launch_gemm8p_tn_store(p, s);
-  }
-  if (!a_km && !b_km) {
-    if (!a_f32 && !b_f32) return launch_one<CT, false, false, false, false>(p, s);
-    if (a_f32 && !b_f32) return launch_one<CT, true, false, false, false>(p, s);
-  } else if (!a_km && b_km) {
-    if (!a_f32 && !b_f32) return launch_one<CT, false, false, false, true>(p, s);
-    if (a_f32 && !b_f32) return launch_one<CT, true, false, false, true>(p, s);
-  } else if (a_km && b_km) {
-    if (!a_f32 && !b_f32) return launch_one<CT, false, false, true, true>(p, s);
-    if (a_f32 && !b_f32) return launch_one<CT, true, false, true, true>(p, s);
+    case GK_NT: if (!b_f32) return a_f32 ? launch_one<CT, true, false, false, false>(p, s) : launch_one<CT, false, false, false, false>(p, s); break;
+    case GK_NN: if (!b_f32) return a_f32 ? launch_one<CT, true, false, false, true>(p, s) : launch_one<CT, false, false, false, true>(p, s); break;
+    case GK_TN: if (!b_f32 && b_km) return a_f32 ? launch_one<CT, true, false, true, true>(p, s) : launch_one<CT, false, false, true, true>(p, s); break;
+    default: break;
   }
   set_error("gemm: operand layout/type combination not instantiated");
   return RSYS_ERR_ARG;
 }
 
 template <typename CT>
-long long gemm_slab_need(const GemmParams& p0, bool a_f32, bool b_f32, bool a_km, bool b_km) {
-  GemmParams p = p0;
+long long gemm_slab_need(const GemmParams& p, bool a_f32, bool b_f32, bool a_km, bool b_km) {
   if (p.epi != EPI_ATOMIC) return 0;
-  if (p.splitk < 1) p.splitk = 1;
-  if (p.splitk > 1) p.splitk = (p.splitk + 7) / 8 * 8;
-  if constexpr (is_bf16<CT>::value) {
-    if (!a_km && !b_km && !a_f32 && !b_f32 && use_8p_nt_splitk(p)) return (long long)gemm8p_splits(p, false) * p.M * p.N;
-    if (a_km && b_km && !a_f32 && !b_f32 && use_8p_tn(p)) return (long long)gemm8p_splits(p, true) * p.M * p.N;
-  }
-  return p.splitk > 1 ? (long long)p.splitk * p.M * p.N : 0;
+  const GemmRoute r = gemm_route<CT>(p, a_f32, b_f32, a_km, b_km, cu_count());
+  return r.splitk > 1 ? (long long)r.splitk * p.M * p.N : 0;
 }
+template GemmRoute gemm_route<bf16>(const GemmParams&, bool, bool, bool, bool, int);
+template GemmRoute gemm_route<float>(const GemmParams&, bool, bool, bool, bool, int);
 template long long gemm_slab_need<bf16>(const GemmParams&, bool, bool, bool, bool);
 template long long gemm_slab_need<float>(const GemmParams&, bool, bool, bool, bool);
 

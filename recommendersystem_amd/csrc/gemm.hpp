@@ -22,6 +22,17 @@ enum GemmEpi : int {
   EPI_SWIGLU_BWD = 9    // acc = dg: C2 = saved [a|b] (interleaved), C = [da|db] same layout (model.py:205-213 backward)
 };
 
+// GemmParams::flags
+enum GemmFlag : int {
+  GEMM_NO_STORE_ALLOWANCE = 1 << 0,   // timing experiment: no allowance for pending stores
+  GEMM_ONE_WG_PER_TILE = 1 << 1,      // 256x256 kernel with one workgroup per tile instead of its persistent grid (used while RCCL kernels share the CUs, see model.hip)
+  GEMM_START_STAGGER = 1 << 2,        // start-stagger experiment
+  GEMM_BAND_SHIFT = 3,                // bits 3-6: gemm8c / gemm4p walk the tiles in bands of that many tile rows (set by their launchers)
+  GEMM_BAND_MASK = 15 << GEMM_BAND_SHIFT,
+  GEMM_SPLITK_256 = 1 << 7,           // EPI_ATOMIC row-major product on the 256x256 split-K kernel whatever its tile count
+  GEMM_REVERSE_ROWS = 1 << 8          // gemm8c walks its tile rows from the last to the first (the caller's A was written just before, front to back)
+};
+
 struct GemmParams {
   const void* A; const void* B; void* C;
   int M, N, K;
@@ -52,9 +63,7 @@ struct GemmParams {
   // deterministic split-K (Model::deterministic): instead of float atomics into C every K split stores its partial tile into
   // slab[split][M][N] (slab_floats = capacity); the launcher clears the slab, and sums the splits in index order into C afterwards
   float* slab; long long slab_floats;
-  int flags;        // bit 0: timing experiment (no allowance for pending stores); bit 1: 256x256 kernel with one workgroup
-                    // per tile instead of its persistent grid (used while RCCL kernels share the CUs, see model.hip);
-                    // bit 2: start-stagger experiment; bits 3-6: gemm8c walks the tiles in bands of that many tile rows (set by its launcher); bit 7: EPI_ATOMIC row-major product on the 256x256 split-K kernel whatever its tile count; bit 8: gemm8c walks its tile rows from the last to the first (the caller's A was written just before, front to back)
+  int flags;        // GemmFlag bits
   // fp8 operands (launch_gemm8p_f8, the fp8 trunk of f8.hip): f8 = 1: A is e4m3, 2: A is e5m2; B is always e4m3.  lda / ldb / K
   // count 1-byte elements.  The fp32 accumulators are multiplied by a descale 1 / (scale_A scale_B) before the epilogue:
   int f8;
@@ -76,7 +85,16 @@ struct GemmParams {
 template <typename CT>
 int launch_gemm(const GemmParams& p, bool a_f32, bool b_f32, bool a_km, bool b_km, hipStream_t s);
 
-// floats of slab the split-K launch of this problem needs (0: no split-K / nothing to do); mirrors launch_gemm's dispatch
+// The kernel launch_gemm runs for a problem, one value per timing tag (gemm_kernel_tags), and the K splits it runs with.  gemm_route
+// is the only place that chooses: launch_gemm, gemm_slab_need and gemm_kernel_name all read it.
+enum GemmKernel : int { GK_NT, GK_NN, GK_TN, GK_8P, GK_8C, GK_4P, GK_8T, GK_4K, GK_8TS, GK_8S, GK_8M, GK_COUNT };
+extern const char* const gemm_kernel_tags[GK_COUNT];
+struct GemmRoute { GemmKernel kernel; int splitk; };
+// cus: the device's CU count (cu_count(); the test hook fixes it)
+template <typename CT>
+GemmRoute gemm_route(const GemmParams& p, bool a_f32, bool b_f32, bool a_km, bool b_km, int cus);
+
+// floats of slab the split-K launch of this problem needs (0: no split-K / nothing to do)
 template <typename CT>
 long long gemm_slab_need(const GemmParams& p, bool a_f32, bool b_f32, bool a_km, bool b_km);
 
@@ -102,7 +120,7 @@ int launch_gemm8p_f8(const GemmParams& p, hipStream_t s);
 bool gemm8p_f8_splitk_eligible(const GemmParams& p);
 int launch_gemm8p_f8_splitk(const GemmParams& p, hipStream_t s);
 
-// short name of the kernel launch_gemm picks for this problem ("8c", "8p", "8t", "8s", "nt", "nn", "tn"): timing tags
+// timing tag of the kernel launch_gemm runs for this problem (gemm_kernel_tags)
 const char* gemm_kernel_name(const GemmParams& p, bool bf16_mode, bool a_f32, bool b_f32, bool a_km, bool b_km);
 
 }  // namespace rsys

@@ -95,12 +95,12 @@ __global__ __launch_bounds__(512) void gemm8c_kernel(GemmParams p) {
     tile_step = (nblk + 7 - xcd) >> 3;
   }
   if (tile_first >= tile_end) return;
-  // flags bits 3-6 = R > 0 (the launcher sets 4): the tile sequence runs band by band of R tile rows, down the band's columns (4 x 1 pieces) instead of row by row, so
+  // GEMM_BAND_MASK bits = R > 0 (the launcher sets 4): the tile sequence runs band by band of R tile rows, down the band's columns (4 x 1 pieces) instead of row by row, so
   // the 32 workgroups an XCD runs side by side cover 4 row blocks x 8 column blocks and share 12 operand blocks per K step through the
   // XCD's L2 where a row-major run of a wide output shares 1 + 32 (launcher: outputs more than eight tiles wide)
-  const int band_rows = (p.flags >> 3) & 15;
+  const int band_rows = (p.flags & GEMM_BAND_MASK) >> GEMM_BAND_SHIFT;
   const bool patch = band_rows != 0;
-  const bool rev = (p.flags & 256) != 0 && !patch;   // flags bit 8: the run walks the tile ROWS from the last to the first (row-major order otherwise unchanged)
+  const bool rev = (p.flags & GEMM_REVERSE_ROWS) != 0 && !patch;   // the run walks the tile ROWS from the last to the first (row-major order otherwise unchanged)
   const int tiles_m_all = ntiles / tiles_n;
   auto tile_pos = [&](C8Tile& x) __attribute__((always_inline)) {
     if (x.t >= ntiles) return;   // (past the end: never dereferenced)
@@ -374,23 +374,23 @@ bool gemm8c_uses_half(const GemmParams& p, int cus) {
   return t256 < cus || (p.epi == EPI_SWIGLU_BWD && p.K <= 256);
 }
 
+// band order of the output tiles (the kernel's tile_pos): bands of 4 tile rows.  RSYS_GEMM_PATCH=0: row-major tile order everywhere (A/B),
+// 2: band order everywhere (the GEMM tests compare the orders); 1: wide AND tall outputs only: 4096 x 120000 (16 tile rows: every XCD
+// already holds all of A) measured 6 % slower in band order
+int gemm8c_band_flags(int tiles, int tiles_n) {
+  const int mode = sw().gemm_patch;
+  return mode == 2 || (mode == 1 && tiles_n > 8 && tiles >= 32 * tiles_n) ? 4 << GEMM_BAND_SHIFT : 0;
+}
+
 int launch_gemm8c(const GemmParams& p0, hipStream_t s) {
-  if (gemm4p_takes(p0)) return launch_gemm4p(p0, s);
   GemmParams p = p0;
-  { const int mode = sw().gemm_reverse; if (mode == 2) p.flags |= 256; else if (mode == 0) p.flags &= ~256; }   // (bit 8: tile rows walked from the last to the first)
-  int cus = 256;
-  { static int n = 0; if (n == 0) { int dev = 0, v = 0; n = (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) ? v : 256; } cus = n; }
+  { const int mode = sw().gemm_reverse; if (mode == 2) p.flags |= GEMM_REVERSE_ROWS; else if (mode == 0) p.flags &= ~GEMM_REVERSE_ROWS; }
+  const int cus = cu_count();
   const bool half = gemm8c_uses_half(p, cus);
   const int bmt = half ? 128 : C8_BM;
   const int tiles = ((p.M + bmt - 1) / bmt) * ((p.N + C8_BN - 1) / C8_BN);
-  const dim3 grid((p.flags & 2) && p.m_dev == nullptr ? tiles : std::min(tiles, cus)), blk(512);
-  {
-    // RSYS_GEMM_PATCH=0: row-major tile order everywhere (A/B), 2: band order everywhere (the GEMM tests compare the orders)
-    const int mode = sw().gemm_patch, rows = 4;
-    const int tiles_n = (p.N + C8_BN - 1) / C8_BN;
-    // wide AND tall outputs only: 4096 x 120000 (16 tile rows: every XCD already holds all of A) measured 6 % slower in band order
-    if (mode == 2 || (mode == 1 && tiles_n > 8 && tiles >= 32 * tiles_n)) p.flags |= rows << 3;
-  }
+  const dim3 grid((p.flags & GEMM_ONE_WG_PER_TILE) && p.m_dev == nullptr ? tiles : std::min(tiles, cus)), blk(512);
+  p.flags |= gemm8c_band_flags(tiles, (p.N + C8_BN - 1) / C8_BN);
   switch (p.epi) {
     case EPI_STORE:
       if (p.c_f32) hipLaunchKernelGGL((gemm8c_kernel<EPI_STORE, true>), grid, blk, 0, s, p);

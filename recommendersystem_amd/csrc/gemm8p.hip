@@ -439,7 +439,7 @@ __device__ __forceinline__ void gemm8p_body(const GemmParams& p, const int bid, 
   }
   pend = 0;
   if constexpr (PERSIST) {
-    if (p.flags & 4) {   // timing experiment: every other workgroup of an XCD starts p.T microsecond-ish naps late
+    if (p.flags & GEMM_START_STAGGER) {   // timing experiment: every other workgroup of an XCD starts p.T microsecond-ish naps late
       if ((bid >> 3) & 1) for (int k = 0; k < p.T; ++k) __builtin_amdgcn_s_sleep(32);
     }
   }
@@ -494,7 +494,7 @@ __device__ __forceinline__ void gemm8p_body(const GemmParams& p, const int bid, 
     // smaller number only makes the next tile wait for more of the stores than it must.
     pend = 0;
     if constexpr (WANT) {
-      if (more && !(p.flags & 1)) {
+      if (more && !(p.flags & GEMM_NO_STORE_ALLOWANCE)) {
         switch (p.epi) {
           case EPI_STORE: pend = p.c_f32 ? 32 : 16; break;
           case EPI_SWIGLU: pend = 24; break;
@@ -667,9 +667,7 @@ bool gemm8p_group_eligible(const GemmParams& p) { return (p.f8 ? gemm8p_f8_split
 // holds device pointers of the operands: it stays valid while those buffers do.  Synchronous (one small H2D copy).
 int gemm8p_group_plan_create(const GemmParams* probs, int n, GemmGroupPlan** out, bool ordered) {
   ARG_CHECK(n >= 1 && n <= 128, "grouped GEMM: 1..128 products");
-  int cus = 256;
-  { int dev = 0, v = 0; if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v; }
-  const int per_xcd = std::max(1, cus / 8);
+  const int per_xcd = std::max(1, cu_count() / 8);
   std::vector<int> tiles(n), ktiles(n);
   int ktmax = 0;
   const bool f8 = probs[0].f8 != 0;
@@ -764,13 +762,13 @@ int gemm8p_group_plan_create(const GemmParams* probs, int n, GemmGroupPlan** out
 }
 void gemm8p_group_plan_destroy(GemmGroupPlan* pl) { if (pl) { if (pl->dev) hipFree(pl->dev); if (pl->slab_all) hipFree(pl->slab_all); delete pl; } }
 double gemm8p_group_flops(const GemmGroupPlan* pl) { return pl->flops; }
-bool gemm8p_group_on_4k(const GemmGroupPlan* pl) { return pl->asm4k && !pl->f8 && sw().gemm4k != 0; }   // (the launch goes to gemm4k.hip: its tag says so)
+bool gemm8p_group_on_4k(const GemmGroupPlan* pl) { return pl->asm4k && !pl->f8 && sw().gemm4k != 0; }   // launch_gemm8p_group's choice (and its timing tag)
 int gemm8p_group_splitk(const GemmGroupPlan* pl) { return pl->splitk; }
 int launch_gemm8p_group(const GemmGroupPlan* pl, hipStream_t s) {
   if (pl->grid <= 0) return RSYS_OK;
   if (pl->slab_all) HIP_CHECK(hipMemsetAsync(pl->slab_all, 0, pl->slab_bytes, s));   // (K splits without work leave their part untouched)
   if (pl->f8) hipLaunchKernelGGL(gemm8p_group_f8_kernel, dim3(pl->grid), dim3(512), 0, s, pl->d_probs, pl->d_off, pl->d_work);
-  else if (pl->asm4k && sw().gemm4k != 0) return launch_gemm4k_group(pl->d_probs, pl->d_off, pl->d_work, pl->grid, s);
+  else if (gemm8p_group_on_4k(pl)) return launch_gemm4k_group(pl->d_probs, pl->d_off, pl->d_work, pl->grid, s);
   else hipLaunchKernelGGL(gemm8p_group_kernel, dim3(pl->grid), dim3(512), 0, s, pl->d_probs, pl->d_off, pl->d_work);
   HIP_CHECK(hipGetLastError());
   if (pl->slab_all) {
@@ -805,11 +803,9 @@ bool gemm8p_tn_eligible(const GemmParams& p) {
   return true;
 }
 
-// K splits of the two split-K forms (a multiple of 8: one split never straddles XCDs): fill whole rounds of the 256 CUs while
+// K splits of the split-K forms (a multiple of 8: one split never straddles XCDs): fill whole rounds of the 256 CUs while
 // keeping the K range of a workgroup long against its fixed cost (first tiles from HBM + 256 KB of atomics ~ 16 K tiles)
-int gemm8p_splits(const GemmParams& p, bool k_major) {
-  const int tiles = ((p.M + T8_BM - 1) / T8_BM) * ((p.N + T8_BN - 1) / T8_BN);
-  const int ktiles = (p.K + T8_BK - 1) / T8_BK;
+static int splitk_for(int tiles, int ktiles) {
   int best = 8; double best_score = -1.0;
   for (int sk = 8; sk <= 256; sk += 8) {
     const int per = (ktiles + sk - 1) / sk;
@@ -819,8 +815,12 @@ int gemm8p_splits(const GemmParams& p, bool k_major) {
     const double score = eff * per / (per + 16.0);   // (tools/scan_splitk_8t.py: 24 splits 694 TFLOP/s, 40 splits 660 on the dWp shape)
     if (score > best_score) { best_score = score; best = sk; }
   }
+  return best;
+}
+int gemm8p_splits(const GemmParams& p, bool k_major) {
   const int force = sw().debug_8t_splitk;   // scans (tools/)
-  return (k_major && force > 0) ? (force + 7) / 8 * 8 : best;
+  if (k_major && force > 0) return (force + 7) / 8 * 8;
+  return splitk_for(((p.M + T8_BM - 1) / T8_BM) * ((p.N + T8_BN - 1) / T8_BN), (p.K + T8_BK - 1) / T8_BK);
 }
 
 // K-major operands, ONE K split, fp32 output stored or accumulated with plain memory operations (the tied head's table gradient
@@ -842,11 +842,8 @@ int launch_gemm8p_tn_store(const GemmParams& p0, hipStream_t s) {
   return RSYS_OK;
 }
 
-int launch_gemm8p_tn(const GemmParams& p0, hipStream_t s) {
-  GemmParams p = p0;
+int launch_gemm8p_tn(const GemmParams& p, hipStream_t s) {
   const int tiles = ((p.M + T8_BM - 1) / T8_BM) * ((p.N + T8_BN - 1) / T8_BN);
-  p.splitk = gemm8p_splits(p, true);
-  if (gemm4k_eligible(p)) return launch_gemm4k(p, tiles * p.splitk, s);   // (no slab: the four-wave register-named loop, same grid and work mapping)
   { const int rc_ = gemm_slab_begin(p, s); if (rc_ != RSYS_OK) return rc_; }
   hipLaunchKernelGGL(gemm8p_kernel<true>, dim3(tiles * p.splitk), dim3(512), 0, s, p);
   HIP_CHECK(hipGetLastError());
@@ -861,10 +858,8 @@ bool gemm8p_nt_splitk_eligible(const GemmParams& p) {
   return true;
 }
 
-int launch_gemm8p_nt_splitk(const GemmParams& p0, hipStream_t s) {
-  GemmParams p = p0;
+int launch_gemm8p_nt_splitk(const GemmParams& p, hipStream_t s) {
   const int tiles = ((p.M + T8_BM - 1) / T8_BM) * ((p.N + T8_BN - 1) / T8_BN);
-  p.splitk = gemm8p_splits(p, false);
   { const int rc_ = gemm_slab_begin(p, s); if (rc_ != RSYS_OK) return rc_; }
   hipLaunchKernelGGL((gemm8p_kernel<false, true>), dim3(tiles * p.splitk), dim3(512), 0, s, p);
   HIP_CHECK(hipGetLastError());
@@ -881,24 +876,12 @@ bool gemm8p_mix_eligible(const GemmParams& p) {
   if ((unsigned long long)p.K * p.ldb * 2 >= (1ull << 40)) return false;
   return true;
 }
-static int cu_count();
 int launch_gemm8p_mix(const GemmParams& p0, hipStream_t s) {
   GemmParams p = p0;
   ARG_CHECK(p.K % T8_BK == 0, "gemm8p_mix: K must be a multiple of 64 (the caller splits the tail off)");
   hipLaunchKernelGGL(gemm8p_mix_kernel, dim3(8 * std::max(1, cu_count() / 8)), dim3(512), 0, s, p);
   HIP_CHECK(hipGetLastError());
   return RSYS_OK;
-}
-
-// at most one workgroup per CU (128 KB of LDS each): the kernel walks the remaining tiles itself
-static int cu_count() {
-  static int n = 0;
-  if (n == 0) {
-    int dev = 0, v = 0;
-    if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) n = v;
-    else n = 256;
-  }
-  return n;
 }
 
 // fp8 operands: the same eligibility in bytes (K tiles of 128 elements)
@@ -929,7 +912,7 @@ int launch_gemm8p_f8(const GemmParams& p0, hipStream_t s) {
   ARG_CHECK(gemm8p_f8_eligible(p), "fp8 GEMM: shape / operand layout not supported by the 256x256 fp8 pipeline (K % 128, K >= 256, strides % 16)");
   if (p.alpha == 0.f) p.alpha = 1.f;
   const int tiles = ((p.M + T8_BM - 1) / T8_BM) * ((p.N + T8_BN - 1) / T8_BN);
-  const dim3 grid((p.flags & 2) && p.m_dev == nullptr ? tiles : std::min(tiles, cu_count()));
+  const dim3 grid((p.flags & GEMM_ONE_WG_PER_TILE) && p.m_dev == nullptr ? tiles : std::min(tiles, cu_count()));
   if (p.f8 == 1) hipLaunchKernelGGL(gemm8p_f8_kernel<1>, grid, dim3(512), 0, s, p);
   else hipLaunchKernelGGL(gemm8p_f8_kernel<2>, grid, dim3(512), 0, s, p);
   HIP_CHECK(hipGetLastError());
@@ -952,39 +935,18 @@ int launch_gemm8p_f8_splitk(const GemmParams& p0, hipStream_t s) {
   ARG_CHECK(gemm8p_f8_splitk_eligible(p), "fp8 split-K GEMM: shape / operand layout not supported");
   if (p.alpha == 0.f) p.alpha = 1.f;
   const int tiles = ((p.M + T8_BM - 1) / T8_BM) * ((p.N + T8_BN - 1) / T8_BN);
-  {   // K splits as for the bf16 row-major split-K form, in K tiles of 128
-    const int ktiles = p.K / 128;
-    int best = 8; double best_score = -1.0;
-    for (int sk = 8; sk <= 256; sk += 8) {
-      const int per = (ktiles + sk - 1) / sk;
-      if (per < 2 && sk > 8) break;
-      const long long wgs = (long long)tiles * sk;
-      const double eff = (double)wgs / (double)(((wgs + 255) / 256) * 256);
-      const double score = eff * per / (per + 16.0);
-      if (score > best_score) { best_score = score; best = sk; }
-    }
-    p.splitk = best;
-  }
+  p.splitk = splitk_for(tiles, p.K / 128);   // as for the bf16 row-major split-K form, in K tiles of 128
   { const int rc_ = gemm_slab_begin(p, s); if (rc_ != RSYS_OK) return rc_; }
   hipLaunchKernelGGL(gemm8p_f8sk_kernel, dim3(tiles * p.splitk), dim3(512), 0, s, p);
   HIP_CHECK(hipGetLastError());
   return gemm_slab_end(p, s);
 }
 
-// the one-stream form of this pipeline (gemm8c.hip) takes the epilogue classes it has kernels for; RSYS_GEMM8C=0: A/B switch
-bool gemm8p_forwards_to_8c(const GemmParams& p) {
-  const int dbg = sw().debug_8p;
-  const int use_8c = sw().gemm8c;
-  return use_8c && dbg == 0 && p.epi != 99 && gemm8c_eligible(p);
-}
-
 int launch_gemm8p(const GemmParams& p0, hipStream_t s) {
   GemmParams p = p0;
-  const int dbg = sw().debug_8p;
-  p.flags |= dbg;
-  if (gemm8p_forwards_to_8c(p0)) return launch_gemm8c(p0, s);
+  p.flags |= sw().debug_8p;   // (timing experiments)
   const int tiles = ((p.M + T8_BM - 1) / T8_BM) * ((p.N + T8_BN - 1) / T8_BN);
-  hipLaunchKernelGGL(gemm8p_kernel<false>, dim3((p.flags & 2) && p.m_dev == nullptr ? tiles : std::min(tiles, cu_count())), dim3(512), 0, s, p);
+  hipLaunchKernelGGL(gemm8p_kernel<false>, dim3((p.flags & GEMM_ONE_WG_PER_TILE) && p.m_dev == nullptr ? tiles : std::min(tiles, cu_count())), dim3(512), 0, s, p);
   HIP_CHECK(hipGetLastError());
   return RSYS_OK;
 }

@@ -136,24 +136,24 @@ __device__ __forceinline__ void epi_item(const GemmParams& p, long long row, int
   }
 }
 
+// The kernels of the 256x256 family; gemm_route (gemm.hip) decides which one a problem runs on, each launcher runs its own kernel.
 // row-major bf16 operands, one 256x256x64 LDS-DMA pipeline (gemm8p.hip); returns RSYS_OK or an error.
 // gemm8p_eligible: the problem satisfies that kernel's layout / size preconditions.
 bool gemm8p_eligible(const GemmParams& p);
 int launch_gemm8p(const GemmParams& p, hipStream_t s);
 // the same pipeline with one operand stream across the workgroup's output tiles and the epilogue overlapped with the next
-// tile's first K tile (gemm8c.hip): the epilogue classes of the training step; launch_gemm8p forwards eligible problems
+// tile's first K tile (gemm8c.hip): the epilogue classes of the training step
 bool gemm8c_eligible(const GemmParams& p);
 int launch_gemm8c(const GemmParams& p, hipStream_t s);
-// gemm4p.hip: the long-K member of the family (plain bf16 store, whole tiles); launch_gemm8c forwards what gemm4p_takes()
+int gemm8c_band_flags(int tiles, int tiles_n);   // the band order of gemm8c / gemm4p: GemmParams::flags bits to set
+// gemm4p.hip: the long-K member of the family (plain bf16 store, whole tiles)
 bool gemm4p_eligible(const GemmParams& p);
-bool gemm4p_takes(const GemmParams& p);
 int launch_gemm4p(const GemmParams& p, hipStream_t s);
 // gemm4k.hip: the K-major split-K member of the four-wave loops (weight gradients); grids and work lists are gemm8p's
 bool gemm4k_eligible(const GemmParams& p);
-int launch_gemm4k(const GemmParams& p, int grid, hipStream_t s);
+int launch_gemm4k(const GemmParams& p, hipStream_t s);
 int launch_gemm4k_group(const GemmParams* d_probs, const int* d_off, const unsigned int* d_work, int grid, hipStream_t s);
-bool gemm8p_forwards_to_8c(const GemmParams& p);   // what launch_gemm8p will do with p (timing tags)
-// the same pipeline for K-major bf16 operands with split-K fp32 atomics (weight gradients); picks its own K split
+// the same pipeline for K-major bf16 operands with split-K fp32 atomics (weight gradients)
 bool gemm8p_tn_eligible(const GemmParams& p);
 int launch_gemm8p_tn(const GemmParams& p, hipStream_t s);
 bool gemm8p_tn_store_eligible(const GemmParams& p);   // K-major operands, one K split, fp32 C stored / accumulated (device-side K limit allowed)
@@ -161,7 +161,8 @@ int launch_gemm8p_tn_store(const GemmParams& p, hipStream_t s);
 // the row-major pipeline with the same split-K mapping and atomic epilogue (long K, few output tiles, K-contiguous operands)
 bool gemm8p_nt_splitk_eligible(const GemmParams& p);
 int launch_gemm8p_nt_splitk(const GemmParams& p, hipStream_t s);
-int gemm8p_splits(const GemmParams& p, bool k_major);            // K splits the two split-K forms choose (gemm8p.hip)
+// K splits of the two split-K forms and of gemm4k (gemm8p.hip); their launchers run p.splitk splits, which gemm_route sets to this
+int gemm8p_splits(const GemmParams& p, bool k_major);
 int gemm_slab_begin(const GemmParams& p, hipStream_t s);         // deterministic split-K: clear the slab / sum it into C (gemm.hip)
 int gemm_slab_end(const GemmParams& p, hipStream_t s);
 

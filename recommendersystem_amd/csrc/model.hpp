@@ -87,7 +87,7 @@ struct Model {
   float* h_umax = nullptr; float* d_umax = nullptr; hipEvent_t ev_umax = nullptr; bool umax_pending = false;
   int64_t tok_all_rows = 0;          // rows per rank tok_Tall / tok_Uall are sized for
   int tok_all_world = 0;             // ranks tok_Tall / tok_Uall / tok_Pall are sized for
-  int gemm_flags = 0;          // OR-ed into GemmParams.flags: 2 while all-reduce kernels may share the CUs with the backward
+  int gemm_flags = 0;          // OR-ed into GemmParams.flags: GEMM_ONE_WG_PER_TILE while all-reduce kernels may share the CUs with the backward
   int64_t early_reduced = 0;   // elements the last rsys_allreduce_grads found already reduced (tests)
   // what the last optimizer step's gradient reduction enqueued, in order: {first element, one past the last, phase}; phase 0 = early bucket
   // (from inside the backward), 1 = tail beside the dWp GEMM, 2 = dWp itself, 3 = split table reduce: head part out of place (under the

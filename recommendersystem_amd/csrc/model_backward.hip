@@ -341,7 +341,7 @@ int backward_trunk(Model* m) {
         // From here on all-reduce kernels share the CUs with the backward.  A persistent grid (one workgroup pinned per
         // CU, a fixed share of the tiles each) would stall on every CU a communication kernel holds, so the 256x256
         // GEMMs go back to one workgroup per tile until the reduction is over: the tiles flow to whatever CUs are free.
-        m->gemm_flags |= 2;
+        m->gemm_flags |= GEMM_ONE_WG_PER_TILE;
       }
     }
   }

@@ -19,8 +19,7 @@ int table_forward(Model* m) {
   p.C2 = m->FT; p.ldc2 = m->D;
   int rows_main = m->TR;
   if constexpr (is_bf16<T>::value) {
-    static int cus = 0;
-    if (cus == 0) { int dev = 0, v = 0; cus = (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) ? v : 256; }
+    const int cus = cu_count();
     const int tiles_n = (m->D + 255) / 256, tiles = ((m->TR + 255) / 256) * tiles_n;
     const int rounds = tiles / cus, rem = tiles % cus;
     if (sw().table_tail != 0 && !m->deterministic && rounds >= 3 && rem > 0 && rem * 4 <= cus && (rounds * cus) % tiles_n == 0 && m->D % 256 == 0 &&
@@ -37,7 +36,7 @@ int table_forward(Model* m) {
     toc(m);
     GemmParams q{};
     q.A = (const T*)m->Meta + r0 * m->Mp; q.lda = m->Mp; q.B = W<T>(m, m->o_Wp); q.ldb = m->Mp; q.C = Ft; q.ldc = m->D; q.c_f32 = 1;
-    q.M = (int)nr; q.N = m->D; q.K = m->Mp; q.epi = EPI_ATOMIC; q.flags = 128;
+    q.M = (int)nr; q.N = m->D; q.K = m->Mp; q.epi = EPI_ATOMIC; q.flags = GEMM_SPLITK_256;
     RC(gemm<T>(m, "gemm_table_fwd_tail", q, false, false, false));
     tic(m, "table_tail_rows");
     RC(launch_cast<T>(Ft, (T*)m->FT + r0 * m->D, nr * m->D, m->stream));

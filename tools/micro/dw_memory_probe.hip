@@ -15,7 +15,6 @@ void set_error(const std::string& msg) { fprintf(stderr, "error: %s\n", msg.c_st
 int gemm_slab_begin(const GemmParams&, hipStream_t) { return 0; }
 int gemm_slab_end(const GemmParams&, hipStream_t) { return 0; }
 bool gemm8c_eligible(const GemmParams&) { return false; }   // (gemm8c.hip is not part of this build)
-int launch_gemm8c(const GemmParams&, hipStream_t) { return RSYS_ERR_ARG; }
 }
 
 static void run(const char* name, int M, int N, int K, long long lda, long long ldb, const void* A, const void* B, float* C) {
@@ -23,6 +22,7 @@ static void run(const char* name, int M, int N, int K, long long lda, long long 
   GemmParams p{};
   p.A = A; p.B = B; p.C = C; p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldb = ldb; p.ldc = N; p.epi = EPI_ATOMIC; p.c_f32 = 1; p.alpha = 1.f;
   if (!gemm8p_tn_eligible(p)) { printf("%s: not eligible\n", name); return; }
+  p.splitk = gemm8p_splits(p, true);   // (what gemm_route gives launch_gemm8p_tn)
   hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
   for (int i = 0; i < 3; ++i) launch_gemm8p_tn(p, nullptr);
   hipEventRecord(e0);
@@ -31,7 +31,7 @@ static void run(const char* name, int M, int N, int K, long long lda, long long 
   hipEventRecord(e1); hipEventSynchronize(e1);
   float ms = 0; hipEventElapsedTime(&ms, e0, e1);
   const double us = ms * 1e3 / reps, tf = 2.0 * M * N * (double)K / (us * 1e-6) / 1e12;
-  printf("  %-9s M=%5d N=%5d K=%6d splits=%3d : %8.1f us  %7.1f TFLOP/s  fill %5.2f TB/s\n", name, M, N, K, gemm8p_splits(p, true), us, tf,
+  printf("  %-9s M=%5d N=%5d K=%6d splits=%3d : %8.1f us  %7.1f TFLOP/s  fill %5.2f TB/s\n", name, M, N, K, p.splitk, us, tf,
          ((M + 255) / 256) * ((N + 255) / 256) * 512.0 * K * 2 / (us * 1e-6) / 1e12);
 }
 

@@ -82,7 +82,6 @@ static void run(int M, int N, int K, int reps) {
 int main(int argc, char** argv) {
   const int reps = argc > 1 ? atoi(argv[1]) : 5;
   setenv("RSYS_GEMM8C", "1", 1);
-  setenv("RSYS_GEMM4P", "0", 1);   // (launch_gemm8c would forward the long-K shapes to gemm4p: the left column is gemm8c itself)
   if (argc > 4) { run(atoi(argv[2]), atoi(argv[3]), atoi(argv[4]), reps); return 0; }
   run(2048, 2048, 1024, 2);          // 64 tiles: one per workgroup
   run(4096, 4096, 1024, 2);          // 256 tiles
