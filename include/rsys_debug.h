@@ -96,6 +96,46 @@ int32_t rsys_op_f8_weights(const float* src, int64_t ld, int32_t rows, int32_t c
 int32_t rsys_op_gemm_f8(const void* A8, const void* B8, void* C, int32_t M, int32_t N, int32_t K, int64_t lda, int64_t ldb, int64_t ldc,
                         int32_t a_fmt, int32_t c_f32, const float* desc_dev, int32_t seg_cols, int32_t alt, int32_t kb0, int32_t kb1,
                         int32_t kb2);
+/* row kernels between the products and the optimiser (csrc/elementwise.hip, csrc/optim.hip), unit-test access on caller-provided
+ * device buffers; each calls the training step's launcher unchanged and synchronises.  dtype RSYS_DTYPE_FP32 / BF16 = the T of the
+ * launcher (the storage type of y, g, dx_t, logits, z, hact; the shadow copy of AdamW).  deterministic != 0: the call runs with
+ * deterministic-mode scratch of its own (per-workgroup partial sums added in a fixed order) and fails if the launch did not take that
+ * branch.  Optional pointers may be null.
+ * rsys_op_rmsnorm_fwd: y = x rstd scale, rstd = 1 / sqrt(mean x^2 + 1e-5) (model.py:193-202); x, scale, rstd f32 [rows][D] / [D] /
+ *   [rows].  rows_dev (device int): rows [0, *rows_dev) live, rows up to the next multiple of 256 (and below `rows`) written as
+ *   zeros, the rest untouched; in_rows (device int [rows]): output row r from input row in_rows[r]; amax (64 shards of 32 floats,
+ *   zeroed by the caller): max |y| after the storage rounding, in element 0 of the shards.
+ * rsys_op_rmsnorm_bwd: dx = resid + r g scale - x r^3 sum(g scale x) / D, dx_t its dtype copy (+ amax as above), dscale += sum over
+ *   rows of g x r; g is dtype-typed, or f32 with g_f32 != 0 (the final norm; resid_slot, io_rows null).  resid_slot (device int
+ *   [rows]): the residual is row resid_slot[r] of resid, none where -1; io_rows (device int [rows]): x read at, dx / dx_t written to,
+ *   row io_rows[r]; rows_dev as in the forward (not together with io_rows).
+ * rsys_op_ce: per row r < n of logits [n][ldl >= V] with i = idx[r]: loss[0] += (lse - logit[position[i]]) label[i] weight[i], and the
+ *   row is overwritten with task_w label[i] weight[i] / max(stats[0], 1e-8) (softmax - onehot), zero in columns >= V and in rows whose
+ *   label weight is zero; rows from round_up(*npos, 128) on are untouched.  Requires 0 <= position[i] < V where label weight != 0.
+ * rsys_op_rating_tail: pred = hact[r].w2 + b2, e = pred - (label[i] - rating_mean); loss[0..2] += weight[i] (e^2, t^2, (-pred - t)^2);
+ *   unless evaluate: dpred = 2 task_w e weight[i] / max(stats[0], 1e-8), z[r] overwritten with dpred w2 gelu'(z[r]), dw2 += dpred
+ *   hact[r], db0 += that dz, db2 += dpred; rows from round_up(*npos, 128) on are skipped.
+ * rsys_op_sumsq: *out = sum of g[0, n)^2 in a fixed order (g 16-byte aligned).
+ * rsys_op_clip_adamw: *sumsq = |g|^2; then fused != 0: AdamW with the clip coefficient min(1, max_norm / (|g| / grad_div + 1e-6)) /
+ *   grad_div applied inside (no clip where max_norm <= 0), or fused == 0: g *= that coefficient first, then AdamW without a clip.
+ *   Decay on [0, n_decay); the bf16 shadow (dtype BF16) gets every element outside [sh_skip_lo, sh_skip_hi); zero_grad clears g.
+ *   n_decay, n_total and the skip bounds are multiples of 4; RSYS_DEBUG_ADAMW is read at the call. */
+int32_t rsys_op_rmsnorm_fwd(int32_t dtype, const float* x, const float* scale, void* y, float* rstd, int64_t rows, int32_t D,
+                            const int32_t* rows_dev, const int32_t* in_rows, float* amax);
+int32_t rsys_op_rmsnorm_bwd(int32_t dtype, int32_t g_f32, const void* g, const float* x, const float* scale, const float* rstd,
+                            const float* resid, const int32_t* resid_slot, const int32_t* io_rows, const int32_t* rows_dev,
+                            float* dx, void* dx_t, float* dscale, int64_t rows, int32_t D, float* amax, int32_t deterministic);
+int32_t rsys_op_ce(int32_t dtype, void* logits, int64_t ldl, int32_t n, int32_t V, const int32_t* idx, const float* label,
+                   const float* weight, const int32_t* position, const float* stats, const int32_t* npos, float task_w, float* loss,
+                   int32_t deterministic);
+int32_t rsys_op_rating_tail(int32_t dtype, void* z, const void* hact, int32_t n, int32_t D, const float* w2, const float* b2,
+                            const int32_t* idx, const float* label, const float* weight, const float* stats, float rating_mean,
+                            float task_w, int32_t evaluate, float* loss, float* dw2, float* db2, float* db0, const int32_t* npos,
+                            int32_t deterministic);
+int32_t rsys_op_sumsq(const float* g, int64_t n, float* out);
+int32_t rsys_op_clip_adamw(int32_t dtype, float* p, float* g, float* m, float* v, void* shadow, int64_t n_decay, int64_t n_total,
+                           float lr, float b1, float b2, float eps, float wd, int32_t step, float max_norm, float grad_div,
+                           int32_t zero_grad, int64_t sh_skip_lo, int64_t sh_skip_hi, int32_t fused, float* sumsq);
 
 #ifdef __cplusplus
 }

@@ -132,6 +132,14 @@ _SIGS = [
     ("rsys_op_attention", C.c_int32, [C.c_int32] + [C.c_int32] * 5 + [_P] * 9),
     ("rsys_op_topk", C.c_int32, [_P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P]),
     ("rsys_op_embedding_scatter", C.c_int32, [_P, C.c_int64, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32]),
+    ("rsys_op_rmsnorm_fwd", C.c_int32, [C.c_int32, _P, _P, _P, _P, C.c_int64, C.c_int32, _P, _P, _P]),
+    ("rsys_op_rmsnorm_bwd", C.c_int32, [C.c_int32, C.c_int32] + [_P] * 11 + [C.c_int64, C.c_int32, _P, C.c_int32]),
+    ("rsys_op_ce", C.c_int32, [C.c_int32, _P, C.c_int64, C.c_int32, C.c_int32] + [_P] * 6 + [C.c_float, _P, C.c_int32]),
+    ("rsys_op_rating_tail", C.c_int32, [C.c_int32, _P, _P, C.c_int32, C.c_int32] + [_P] * 6 + [C.c_float, C.c_float, C.c_int32]
+                                        + [_P] * 5 + [C.c_int32]),
+    ("rsys_op_sumsq", C.c_int32, [_P, C.c_int64, _P]),
+    ("rsys_op_clip_adamw", C.c_int32, [C.c_int32] + [_P] * 5 + [C.c_int64, C.c_int64] + [C.c_float] * 5
+                                       + [C.c_int32, C.c_float, C.c_float, C.c_int32, C.c_int64, C.c_int64, C.c_int32, _P]),
     ("rsys_step_mark", C.c_int32, [_P]),
     ("rsys_step_marks_get", C.c_int32, [_P, _P, C.c_int32, C.POINTER(C.c_int32)]),
     ("rsys_op_timing", C.c_int32, [_P, C.c_int32]),

@@ -859,6 +859,138 @@ int32_t rsys_op_embedding_scatter(const float* gx0, int64_t ldx, const int32_t* 
   return RSYS_OK;
 }
 
+// ---------------------------------------------------------------- row kernels and the optimiser on caller-provided buffers (tests)
+// Deterministic-mode scratch of one hook call: installed in g_det for that call only (as DetScope does for a model), freed afterwards.
+// check() fails unless the launch took the partial-sum branch with no launch falling back to atomics for want of scratch.
+struct HookDet {
+  DetScratch saved;
+  float *part = nullptr, *tmp = nullptr;
+  bool on;
+  explicit HookDet(bool on_) : saved(g_det), on(on_) { g_det = DetScratch(); }
+  ~HookDet() { hipDeviceSynchronize(); g_det = saved; if (part) hipFree(part); if (tmp) hipFree(tmp); }
+  // part_floats for the launch's partial rows; the two-stage reduction needs ceil(partial rows / 32) * row length floats
+  int alloc(long long part_floats, long long tmp_floats) {
+    if (!on) return RSYS_OK;
+    part_floats = std::max(part_floats, 1LL); tmp_floats = std::max(tmp_floats, 1LL);
+    HIP_CHECK(hipMalloc((void**)&part, (size_t)part_floats * 4));
+    HIP_CHECK(hipMalloc((void**)&tmp, (size_t)tmp_floats * 4));
+    g_det.part = part; g_det.cap = part_floats; g_det.tmp = tmp; g_det.tmp_cap = tmp_floats;
+    return RSYS_OK;
+  }
+  int check(const char* who) {
+    if (!on) return RSYS_OK;
+    if (g_det.part_used < 1 || g_det.part_short != 0) {
+      set_error(std::string(who) + ": the deterministic partial-sum branch did not run");
+      return RSYS_ERR_STATE;
+    }
+    return RSYS_OK;
+  }
+};
+static long long ceil32(long long n) { return (n + 31) / 32; }
+
+int32_t rsys_op_rmsnorm_fwd(int32_t dtype, const float* x, const float* scale, void* y, float* rstd, int64_t rows, int32_t D,
+                            const int32_t* rows_dev, const int32_t* in_rows, float* amax) {
+  switches_parse();
+  ARG_CHECK(x && scale && y && rows >= 1, "rsys_op_rmsnorm_fwd: arguments");
+  int rc = dtype == RSYS_DTYPE_BF16 ? launch_rmsnorm_fwd<bf16>(x, scale, (bf16*)y, rstd, rows, D, nullptr, rows_dev, in_rows, amax)
+                                    : launch_rmsnorm_fwd<float>(x, scale, (float*)y, rstd, rows, D, nullptr, rows_dev, in_rows, amax);
+  if (rc) return rc;
+  HIP_CHECK(hipDeviceSynchronize());
+  return RSYS_OK;
+}
+
+int32_t rsys_op_rmsnorm_bwd(int32_t dtype, int32_t g_f32, const void* g, const float* x, const float* scale, const float* rstd,
+                            const float* resid, const int32_t* resid_slot, const int32_t* io_rows, const int32_t* rows_dev,
+                            float* dx, void* dx_t, float* dscale, int64_t rows, int32_t D, float* amax, int32_t deterministic) {
+  switches_parse();
+  ARG_CHECK(g && x && scale && rstd && dx && dscale && rows >= 0, "rsys_op_rmsnorm_bwd: arguments");
+  ARG_CHECK(!g_f32 || (resid_slot == nullptr && io_rows == nullptr), "rsys_op_rmsnorm_bwd: the f32-gradient form takes no resid_slot / io_rows");
+  HookDet det(deterministic != 0);
+  const long long wgs = std::max<long long>(1, std::min<long long>(rows, 4LL * std::max(1, sw().debug_norm_bwd_grid)));   // >= the launch's grid
+  RC(det.alloc(wgs * D, ceil32(wgs) * D));
+  const bool bf = dtype == RSYS_DTYPE_BF16;
+  int rc;
+  if (g_f32) rc = bf ? launch_rmsnorm_bwd_f32<bf16>((const float*)g, x, scale, rstd, resid, dx, (bf16*)dx_t, dscale, rows, D, nullptr, rows_dev, amax)
+                     : launch_rmsnorm_bwd_f32<float>((const float*)g, x, scale, rstd, resid, dx, (float*)dx_t, dscale, rows, D, nullptr, rows_dev, amax);
+  else rc = bf ? launch_rmsnorm_bwd<bf16>((const bf16*)g, x, scale, rstd, resid, dx, (bf16*)dx_t, dscale, rows, D, nullptr, rows_dev, resid_slot, io_rows, amax)
+               : launch_rmsnorm_bwd<float>((const float*)g, x, scale, rstd, resid, dx, (float*)dx_t, dscale, rows, D, nullptr, rows_dev, resid_slot, io_rows, amax);
+  if (rc) return rc;
+  HIP_CHECK(hipDeviceSynchronize());
+  return det.check("rsys_op_rmsnorm_bwd");
+}
+
+int32_t rsys_op_ce(int32_t dtype, void* logits, int64_t ldl, int32_t n, int32_t V, const int32_t* idx, const float* label,
+                   const float* weight, const int32_t* position, const float* stats, const int32_t* npos, float task_w, float* loss,
+                   int32_t deterministic) {
+  switches_parse();
+  ARG_CHECK(logits && idx && label && weight && position && stats && loss && n >= 0 && V >= 1, "rsys_op_ce: arguments");
+  HookDet det(deterministic != 0 && n > 0);
+  RC(det.alloc(n, ceil32(n)));
+  int rc = dtype == RSYS_DTYPE_BF16 ? launch_ce_fwd_bwd<bf16>((bf16*)logits, ldl, n, V, idx, label, weight, position, stats, npos, task_w, loss, nullptr)
+                                    : launch_ce_fwd_bwd<float>((float*)logits, ldl, n, V, idx, label, weight, position, stats, npos, task_w, loss, nullptr);
+  if (rc) return rc;
+  HIP_CHECK(hipDeviceSynchronize());
+  return det.check("rsys_op_ce");
+}
+
+int32_t rsys_op_rating_tail(int32_t dtype, void* z, const void* hact, int32_t n, int32_t D, const float* w2, const float* b2,
+                            const int32_t* idx, const float* label, const float* weight, const float* stats, float rating_mean,
+                            float task_w, int32_t evaluate, float* loss, float* dw2, float* db2, float* db0, const int32_t* npos,
+                            int32_t deterministic) {
+  switches_parse();
+  ARG_CHECK(z && hact && w2 && b2 && idx && label && weight && stats && loss && dw2 && db2 && db0 && n >= 0, "rsys_op_rating_tail: arguments");
+  HookDet det(deterministic != 0 && n > 0);
+  const long long grid = std::min<long long>((n + 3) / 4, 512);   // the launcher's grid
+  RC(det.alloc(grid * (2LL * D + 4), ceil32(grid) * D));
+  int rc = dtype == RSYS_DTYPE_BF16
+               ? launch_rating_tail<bf16>((bf16*)z, (const bf16*)hact, n, D, w2, b2, idx, label, weight, stats, rating_mean, task_w, evaluate, loss,
+                                          dw2, db2, db0, nullptr, npos)
+               : launch_rating_tail<float>((float*)z, (const float*)hact, n, D, w2, b2, idx, label, weight, stats, rating_mean, task_w, evaluate, loss,
+                                           dw2, db2, db0, nullptr, npos);
+  if (rc) return rc;
+  HIP_CHECK(hipDeviceSynchronize());
+  return det.check("rsys_op_rating_tail");
+}
+
+int32_t rsys_op_sumsq(const float* g, int64_t n, float* out) {
+  ARG_CHECK(g && out, "rsys_op_sumsq: arguments");
+  float* part = nullptr;
+  HIP_CHECK(hipMalloc((void**)&part, (size_t)sumsq_parts() * 4));
+  int rc = launch_sumsq(g, n, out, part, nullptr, true);
+  hipError_t e = hipDeviceSynchronize();
+  hipFree(part);
+  if (rc) return rc;
+  HIP_CHECK(e);
+  return RSYS_OK;
+}
+
+int32_t rsys_op_clip_adamw(int32_t dtype, float* p, float* g, float* m, float* v, void* shadow, int64_t n_decay, int64_t n_total,
+                           float lr, float b1, float b2, float eps, float wd, int32_t step, float max_norm, float grad_div,
+                           int32_t zero_grad, int64_t sh_skip_lo, int64_t sh_skip_hi, int32_t fused, float* sumsq) {
+  switches_parse();
+  ARG_CHECK(p && g && m && v && sumsq && n_total >= 4 && step >= 1, "rsys_op_clip_adamw: arguments");
+  float* part = nullptr;
+  HIP_CHECK(hipMalloc((void**)&part, (size_t)sumsq_parts() * 4));
+  const bool bf = dtype == RSYS_DTYPE_BF16;
+  int rc = launch_sumsq(g, n_total, sumsq, part, nullptr, true);
+  if (fused) {   // optimizer_step: the clip coefficient and the 1 / grad_div inside AdamW
+    const float* ss = max_norm > 0.f ? sumsq : nullptr;
+    if (!rc) rc = bf ? launch_adamw<bf16>(p, g, m, v, (bf16*)shadow, n_decay, n_total, lr, b1, b2, eps, wd, step, ss, grad_div, max_norm, zero_grad, nullptr,
+                                          sh_skip_lo, sh_skip_hi)
+                     : launch_adamw<float>(p, g, m, v, nullptr, n_decay, n_total, lr, b1, b2, eps, wd, step, ss, grad_div, max_norm, zero_grad, nullptr);
+  } else {       // clip_grad_norm_ (model_clip: a scale pass over the gradients), then AdamW with no clip
+    if (!rc) rc = launch_scale(g, n_total, sumsq, grad_div, max_norm, nullptr);
+    if (!rc) rc = bf ? launch_adamw<bf16>(p, g, m, v, (bf16*)shadow, n_decay, n_total, lr, b1, b2, eps, wd, step, nullptr, 1.f, 0.f, zero_grad, nullptr,
+                                          sh_skip_lo, sh_skip_hi)
+                     : launch_adamw<float>(p, g, m, v, nullptr, n_decay, n_total, lr, b1, b2, eps, wd, step, nullptr, 1.f, 0.f, zero_grad, nullptr);
+  }
+  hipError_t e = hipDeviceSynchronize();
+  hipFree(part);
+  if (rc) return rc;
+  HIP_CHECK(e);
+  return RSYS_OK;
+}
+
 // step boundaries on the model's stream: rsys_step_mark records an event, rsys_step_marks_get returns the elapsed time
 // between consecutive marks (ms) and clears them -- the per-step time distribution without a host sync per step
 int32_t rsys_step_mark(rsys_model* h) {

@@ -42,7 +42,9 @@ int launch_reduce_parts(const float* part, int nparts, long long stride, int n, 
 // scratch of the deterministic mode for `floats` partial sums, or nullptr (atomics) when the mode is off
 static inline float* det_part(long long floats) {
   if (g_det.part == nullptr) return nullptr;
-  return floats <= g_det.cap ? g_det.part : nullptr;
+  if (floats > g_det.cap) { ++g_det.part_short; return nullptr; }
+  ++g_det.part_used;
+  return g_det.part;
 }
 
 static inline int div_up(long long a, long long b) { return (int)((a + b - 1) / b); }
@@ -367,6 +369,7 @@ static int rmsnorm_bwd_any(const TG* g, const float* x, const float* scale, cons
                            const int* resid_slot, const int* io_rows = nullptr, float* f8_amax = nullptr) {
   float* const amax = f8_amax;
   ARG_CHECK(D % 4 == 0 && D <= 64 * 4 * NORM_MAXJ, "rmsnorm_bwd: D must be a multiple of 4 and <= 2048");
+  ARG_CHECK(rows_dev == nullptr || io_rows == nullptr, "rmsnorm_bwd: io_rows with rows_dev (the zero rows would be written at the unmapped rows)");
   // (every workgroup ends with D atomics onto the same D scale gradients: with 4 waves per workgroup, 512-1024 workgroups 1.39-1.45 ms per step
   // at cfg-3, 2048: 1.49, 4096: 1.97, 8192: 3.37.)  RSYS_DEBUG_NORM_BWD_GRID caps the number of WAVES / 4 (the unit of those scans).
   const int grid_cap = sw().debug_norm_bwd_grid;
@@ -660,6 +663,7 @@ template <typename T>
 int launch_ce_fwd_bwd(T* logits, long long ldl, int n, int V, const int* idx, const float* label, const float* weight,
                       const int* position, const float* stats, const int* npos, float task_w, float* loss_out, hipStream_t s) {
   ARG_CHECK((ldl * sizeof(T)) % 16 == 0 && ldl >= V, "ce: ldl");
+  if (n <= 0) return RSYS_OK;
   float* part = det_part(n);
   if (part != nullptr) HIP_CHECK(hipMemsetAsync(part, 0, (size_t)n * 4, s));   // (rows without a term write nothing)
   hipLaunchKernelGGL((ce_kernel<T>), dim3(n), dim3(256), 0, s, logits, ldl, V, idx, label, weight, position, stats, npos, task_w, loss_out, part);
@@ -741,6 +745,7 @@ template <typename T>
 int launch_rating_tail(T* z, const T* hact, int n, int D, const float* w2, const float* b2, const int* idx,
                        const float* label, const float* weight, const float* stats, float rating_mean, float task_w,
                        int evaluate, float* loss_out, float* dw2, float* db2, float* db0, hipStream_t s, const int* npos) {
+  if (n <= 0) return RSYS_OK;
   int grid = std::min(div_up(n, 4), 512);
   const long long prow = 2LL * D + 4;
   float* part = det_part(grid * prow);

@@ -26,7 +26,12 @@ struct BatchDev {
 // into it instead of issuing float atomics, and their launchers add the partials to the destination in workgroup order
 // (launch_reduce_parts).  Thread-local: set by the model around its launches (one host thread drives one model), all on the
 // model's stream, so consecutive launches may reuse the scratch from offset 0.
-struct DetScratch { float* part = nullptr; long long cap = 0; float* tmp = nullptr; long long tmp_cap = 0; };   // tmp: second stage of long reductions
+// part_used / part_short count the launches that took the partial-sum branch / fell back to atomics for want of scratch (the per-kernel
+// test hooks check them: a deterministic-mode test cannot pass on the atomic path).
+struct DetScratch {
+  float* part = nullptr; long long cap = 0; float* tmp = nullptr; long long tmp_cap = 0;   // tmp: second stage of long reductions
+  int part_used = 0, part_short = 0;
+};
 extern thread_local DetScratch g_det;
 // dst[c] += sum_b part[b * stride + c] for c < n, b = 0 .. nparts-1 in that order
 int launch_reduce_parts(const float* part, int nparts, long long stride, int n, float* dst, hipStream_t s);
@@ -61,7 +66,8 @@ template <typename T>
 int launch_rmsnorm_bwd(const T* g, const float* x, const float* scale, const float* rstd, const float* resid_grad,
                        float* dx_out, T* dx_out_t, float* dscale, long long rows, int D, hipStream_t s, const int* rows_dev = nullptr,
                        const int* resid_slot = nullptr /* resid_grad is compact: row resid_slot[row] of it, zero where -1 */,
-                       const int* io_rows = nullptr /* x is read at, and dx_out / dx_out_t written to, row io_rows[row] (g, rstd, resid_slot: row) */,
+                       const int* io_rows = nullptr /* x is read at, and dx_out / dx_out_t written to, row io_rows[row] (g, rstd, resid_slot: row);
+                                                       not together with rows_dev (its zero rows are written at `row`) */,
                        float* f8_amax = nullptr /* fp8 trunk: sharded amax slot of dx_out_t */);
 // same with an f32 incoming gradient (final norm: gy is f32)
 template <typename T>
@@ -90,12 +96,13 @@ int launch_scatter_rows_add(const float* src, const int* idx, int parity, float*
                             const int* npos = nullptr /* device: only rows r < *npos are added */);
 
 // cross entropy over logits[n][ldl] (valid cols < V): accumulates loss_out[0] += sum ce*label*w ;
-// overwrites logits with dlogits = coef*(softmax - onehot), coef = tw*label*w/max(wsum,1e-8); pad cols zeroed
+// overwrites logits with dlogits = coef*(softmax - onehot), coef = tw*label*w/max(wsum,1e-8); pad cols zeroed.
+// Precondition: 0 <= position[idx[r]] < V for every row with label*w != 0 (the target logit is read without a check); n = 0 launches nothing
 template <typename T>
 int launch_ce_fwd_bwd(T* logits, long long ldl, int n, int V, const int* idx, const float* label, const float* weight,
                       const int* position, const float* stats, const int* npos, float task_w, float* loss_out, hipStream_t s);
 
-// rating head tail: pred = hact.w2 + b2 ; losses ; dz = dpred*w2*gelu'(z) (in place over z) ; dw2,db2,db0 accumulated
+// rating head tail: pred = hact.w2 + b2 ; losses ; dz = dpred*w2*gelu'(z) (in place over z) ; dw2,db2,db0 accumulated; n = 0 launches nothing
 template <typename T>
 int launch_rating_tail(T* z, const T* hact, int n, int D, const float* w2, const float* b2, const int* idx,
                        const float* label, const float* weight, const float* stats, float rating_mean, float task_w,

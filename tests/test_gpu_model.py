@@ -42,9 +42,23 @@ CASES = [
 ]
 
 
+FWD_BWD_TOLS = [("fp32", 1e-4, 1e-4, 5e-4), ("bf16", 4e-2, 6e-2, 1.5e-1)]
+
+
 @pytest.mark.parametrize("name,over,rows,seed", CASES)
-@pytest.mark.parametrize("dtype,tol_loss,tol_act,tol_grad", [("fp32", 1e-4, 1e-4, 5e-4), ("bf16", 4e-2, 6e-2, 1.5e-1)])
+@pytest.mark.parametrize("dtype,tol_loss,tol_act,tol_grad", FWD_BWD_TOLS)
 def test_forward_backward_vs_oracle(name, over, rows, seed, dtype, tol_loss, tol_act, tol_grad):
+    _forward_backward_vs_oracle(name, over, rows, seed, dtype, tol_loss, tol_act, tol_grad, False)
+
+
+@pytest.mark.parametrize("name,over,rows,seed", CASES)
+@pytest.mark.parametrize("dtype,tol_loss,tol_act,tol_grad", FWD_BWD_TOLS)
+def test_forward_backward_vs_oracle_deterministic(name, over, rows, seed, dtype, tol_loss, tol_act, tol_grad):
+    """the same checks in deterministic mode (partial-sum reductions instead of float atomics), with the same bounds"""
+    _forward_backward_vs_oracle(name, over, rows, seed, dtype, tol_loss, tol_act, tol_grad, True)
+
+
+def _forward_backward_vs_oracle(name, over, rows, seed, dtype, tol_loss, tol_act, tol_grad, deterministic):
     import recommendersystem_amd as ra
     from oracle import synth
     cfg, P, d = _setup(name, over, rows, seed)
@@ -52,7 +66,7 @@ def test_forward_backward_vs_oracle(name, over, rows, seed, dtype, tol_loss, tol
     u = z["meta/u"]; r = np.float32(cfg["mask_rate"])
     wm = u < r; rm = (u >= r) & (u < 2 * r)
     y_ref, l_ref, G_ref, ev_ref = _oracle(cfg, P, d, wm, rm)
-    model = ra.RecommenderModel(cfg, dtype=dtype, max_rows=rows)
+    model = ra.RecommenderModel(dict(cfg, deterministic=deterministic), dtype=dtype, max_rows=rows)
     model.load_state_dict(P)
     model.set_loss_weights(TASK_W, 1)
     losses = model(d, False, masks=(wm, rm))
