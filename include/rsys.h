@@ -181,6 +181,42 @@ int32_t rsys_retrieve_request(rsys_model* m, int32_t medium,
                               const int32_t* sel_medium, const int32_t* sel_ids,
                               int32_t k, int32_t* ids_out, float* scores_out, /* [n_groups][k] each */
                               int32_t* counts_out);                           /* [n_groups] */
+/* "{m}.related" of Inference/render.jl's reranking (the franchise relation, V_m x V_m) for rsys_rank_request: 0-based CSC in Julia's column
+ * order, with the contract and validation of rsys_retrieve_relations_set (colptr[n + 1], colptr[0] = 0, non-decreasing; rowval in [0, n);
+ * stored values finite and >= 0, else an ARG error; explicitly stored zeros are dropped).  n must be V_m.  NULL colptr clears the table.
+ * Held on the device, freed with the model, not part of checkpoints. */
+int32_t rsys_rank_related_set(rsys_model* m, int32_t medium, int64_t n, const int64_t* colptr, const int32_t* rowval, const float* nzval);
+/* render.jl `ranking(state, idxs)` + `reranking!(state, idxs, r, partialk)` for n_groups requests of one medium.
+ * Group g: candidates ids[cand_offsets[g] .. cand_offsets[g + 1]) (medium-local, distinct, 1 <= n_g <= 1024), partialk[g] >= 1 (min(partialk,
+ * n_g) rounds), penalties[g][4] = (decay, mmr_penalty, same_series_penalty, related_penalty).  User u: queries[u] (its "{m}.retrieval"
+ * embedding), group[u], r_masked (n_g values of its group's candidates, ragged in user order; n_r_masked = their sum), list items in
+ * list order (CSR as rsys_retrieve_request; NULL: no lists).
+ * Ranking score of candidate i, summed in user order as score = score + (lp_u + r_u): lp_u = z - lse_u + log(coef) with z, lse_u the fp32
+ * scores of rsys_retrieve_topk (-inf where coef * exp(z - lse_u) is 0 in fp32, log(0) in the reference); coef = *retrieval_coef or 1;
+ * r_u = c0 * rating_mean + c1 * r_masked with (c0, c1) = rating_coefs, or r_masked when rating_coefs is NULL.  r_in (n_total floats in
+ * candidate order) replaces the score (queries and r_masked are then not read).
+ * Reranking (every operation rounded in fp32, no contraction): per round score = ((r - mmr) - ss) - rel, best = the first position of the
+ * maximum under Julia's isless (-inf < ... < -0.0 < +0.0 < ... < inf < NaN), r[best] = -inf (a position is picked again once fewer finite
+ * scores than rounds remain); then ss = ss * decay, + same_series_penalty for every candidate that is a stored row of column ids[best] of
+ * "{m}.related"; rel = rel * decay, + flag * related_penalty if flag[best]; mmr = max(mmr * decay, G[:, best] * mmr_penalty) with Julia's
+ * max (NaN propagates, +0.0 over -0.0).  flag[i]: candidate i is a stored row of the column of any list entry of medium m, of any user of
+ * the group, whose status is not 3 or 5 (every entry, not the last status per item).  G = E_c^T E_c over the candidates' rows of the
+ * item-similarity table of m (rsys_retrieve_similarity_set), fp32 with a fixed summation order.
+ * Output: ids_out[cand_offsets[g] + t] = the id picked in round t (slots t >= min(partialk, n_g): -1), or NULL (ranking only: no Gram, no
+ * loop); r_out = the ranking scores before reranking (n_total floats in candidate order), or NULL.  ids_out needs the related and
+ * similarity tables of `medium`.  1 <= n_users <= 4096, every group needs a user.  Synchronous, bitwise reproducible, changes no model
+ * state; the device workspace grows on demand and is freed with the model. */
+int32_t rsys_rank_request(rsys_model* m, int32_t medium, int32_t n_groups,
+                          const int64_t* cand_offsets, const int32_t* cand_ids,   /* [n_groups + 1] CSR over groups, [n_total] */
+                          const int32_t* partialk, const float* penalties,        /* [n_groups], [n_groups][4] */
+                          const float* queries, int64_t n_users,                  /* [n_users][embed_dim] f32 */
+                          const int32_t* group,                                   /* [n_users] in [0, n_groups), or NULL: group = user */
+                          const float* r_masked, int64_t n_r_masked,              /* ragged over users */
+                          const int64_t* hist_offsets,                            /* [n_users + 1] CSR over users, or NULL (no lists) */
+                          const int32_t* hist_medium, const int32_t* hist_ids, const int32_t* hist_status,
+                          const float* retrieval_coef, const float* rating_coefs, float rating_mean, /* [1] or NULL, [2] or NULL */
+                          const float* r_in,                                      /* [n_total] or NULL */
+                          int32_t* ids_out, float* r_out);                        /* [n_total] each, or NULL */
 /* on != 0: every float sum of the training step gets a fixed order (split-K partial tiles summed in split order, reductions through
  * per-workgroup partials instead of float atomics), so a step -- losses, gradients, updated parameters -- is bitwise reproducible
  * from run to run; costs a few percent of the step.  Replicated or row-sharded table, full or sampled soft-max.  (The reference's CUDA path is not reproducible:

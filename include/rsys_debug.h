@@ -71,6 +71,15 @@ int32_t rsys_op_attention(int32_t dtype, int32_t B, int32_t T, int32_t H, int32_
  * counts [rows]; 1 <= k <= min(V, 8192) */
 int32_t rsys_op_topk(const float* scores, int64_t ld, int32_t rows, int32_t V, int32_t k,
                      int32_t* ids, float* vals, int32_t* counts);
+/* rsys_rank_request's Gram matrices alone, as its loop reads them: out = per group in order, G_g [n_g][n_g] row-major (sum of n_g^2 floats),
+ * computed by the same kernel from the model's item-similarity table of `medium`; host arrays */
+int32_t rsys_rank_gram_get(rsys_model* m, int32_t medium, int32_t n_groups, const int64_t* cand_offsets, const int32_t* cand_ids,
+                           float* out, int64_t n_out);
+/* rsys_rank_request's greedy loop alone for one group, on caller-provided device buffers: r [n], gram [n][n] (row b is read as column b),
+ * ss_bits [n][ceil(n / 32)] (bit i of row j: candidate i is a stored row of related's column ids[j]), related_bits [ceil(n / 32)] (the
+ * flags); pen[4] (host) = (decay, mmr, same_series, related); picks [min(partialk, n)] = the position chosen per round; 1 <= n <= 1024 */
+int32_t rsys_op_rerank(int32_t n, int32_t partialk, const float* pen, const float* r, const float* gram, const int32_t* ss_bits,
+                       const int32_t* related_bits, int32_t* picks);
 /* embedding-gradient scatter of the backward (nn.Embedding backward, model.py:21) on caller-provided device buffers:
  * gE[id'] += sum over tokens n of gx0[n*ldx .. +D) with id' = m_matchedid[n] (-1 -> row V); matchedid = the raw ids the
  * token index is built from (m_matchedid differs from it only where it is -1).  One writer per table row, fixed summation

@@ -259,6 +259,45 @@ function retrieve_request(m::Model, medium::Integer, Q::Matrix{Float32}, k::Inte
         m.h, medium, Q, size(Q, 2), g, n_groups, hoff, hmed, hid, hst, soff, smed, sid, k, ids, scores, counts))
     ids, scores, counts
 end
+# ranking and reranking of retrieved candidates (Inference/render.jl:335-435): "{m}.related" as a SparseMatrixCSC (V_m x V_m) or nothing
+# to clear; it is held on the device beside the retrieval tables
+function rank_related_set(m::Model, medium::Integer, A)
+    A === nothing && return check(ccall((:rsys_rank_related_set, LIB), Int32, (Ptr{Cvoid}, Int32, Int64, Ptr{Int64}, Ptr{Int32}, Ptr{Float32}),
+                                        m.h, medium, 0, C_NULL, C_NULL, C_NULL))
+    cp = Vector{Int64}(A.colptr .- 1); rv = Vector{Int32}(A.rowval .- 1); nz = Vector{Float32}(A.nzval)
+    GC.@preserve cp rv nz check(ccall((:rsys_rank_related_set, LIB), Int32, (Ptr{Cvoid}, Int32, Int64, Ptr{Int64}, Ptr{Int32}, Ptr{Float32}),
+        m.h, medium, size(A, 2), cp, rv, nz))
+end
+# idxs: one Vector of 0-based candidate ids per group; partialk and penalties (decay, mmr, same_series, related) per group; Q (D, n_users)
+# the users' "{m}.retrieval" embeddings, group 0-based per user, r_masked one Vector{Float32} per user (its group's candidates), hist as
+# retrieve_request.  retrieval_coef / rating_coefs (c0, c1) / rating_mean: the registry's, or nothing.  r: given ranking scores (one Vector
+# per group) instead of computing them.  Returns (ids per group in pick order, ranking score per group).
+function rank_request(m::Model, medium::Integer, idxs, partialk, penalties, Q::Matrix{Float32}, group, r_masked; hist = nothing,
+                      retrieval_coef = nothing, rating_coefs = nothing, rating_mean = 0f0, r = nothing, want_ids::Bool = true)
+    ng = length(idxs)
+    off = Int64[0; cumsum(Int64[length(c) for c in idxs])]
+    cid = Int32[reduce(vcat, idxs; init = Int32[])...]
+    pk = Vector{Int32}(partialk)
+    pen = Float32[x for p in penalties for x in p]
+    g = Vector{Int32}(group)
+    rm = r_masked === nothing ? Ptr{Float32}(C_NULL) : Float32[reduce(vcat, r_masked; init = Float32[])...]
+    nrm = r_masked === nothing ? 0 : length(rm)
+    hoff = hist === nothing ? Ptr{Int64}(C_NULL) : Int64[0; cumsum(Int64[length(h) for h in hist])]
+    hmed = hist === nothing ? Ptr{Int32}(C_NULL) : Int32[x[1] for h in hist for x in h]
+    hid = hist === nothing ? Ptr{Int32}(C_NULL) : Int32[x[2] for h in hist for x in h]
+    hst = hist === nothing ? Ptr{Int32}(C_NULL) : Int32[x[3] for h in hist for x in h]
+    rc = retrieval_coef === nothing ? Ptr{Float32}(C_NULL) : Float32[retrieval_coef]
+    kc = rating_coefs === nothing ? Ptr{Float32}(C_NULL) : Vector{Float32}(rating_coefs)
+    rin = r === nothing ? Ptr{Float32}(C_NULL) : Float32[reduce(vcat, r; init = Float32[])...]
+    ids = want_ids ? Vector{Int32}(undef, off[end]) : Ptr{Int32}(C_NULL)
+    rout = Vector{Float32}(undef, off[end])
+    GC.@preserve off cid pk pen Q g rm hoff hmed hid hst rc kc rin ids rout check(ccall((:rsys_rank_request, LIB), Int32,
+        (Ptr{Cvoid}, Int32, Int32, Ptr{Int64}, Ptr{Int32}, Ptr{Int32}, Ptr{Float32}, Ptr{Float32}, Int64, Ptr{Int32}, Ptr{Float32}, Int64,
+         Ptr{Int64}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Float32}, Ptr{Float32}, Float32, Ptr{Float32}, Ptr{Int32}, Ptr{Float32}),
+        m.h, medium, ng, off, cid, pk, pen, Q, size(Q, 2), g, rm, nrm, hoff, hmed, hid, hst, rc, kc, rating_mean, rin, ids, rout))
+    picked = want_ids ? [ids[off[j]+1:off[j]+min(pk[j], length(idxs[j]))] for j in 1:ng] : nothing
+    picked, [rout[off[j]+1:off[j+1]] for j in 1:ng]
+end
 function infer(m::Model, task::Integer, rows::Integer, S::Integer, D::Integer)   # model.py:531-538 over every token of the resident batch
     out = task == 0 ? Array{Float32}(undef, D, 2S, rows) : Array{Float32}(undef, 2S, rows)
     GC.@preserve out check(ccall((:rsys_infer, LIB), Int32, (Ptr{Cvoid}, Int32, Ptr{Float32}, Int64), m.h, task, out, length(out))); out

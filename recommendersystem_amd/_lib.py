@@ -78,6 +78,9 @@ _SIGS = [
     ("rsys_retrieve_similarity_set", C.c_int32, [_P, C.c_int32, C.c_int64, _P, _P]),
     ("rsys_retrieve_released_set", C.c_int32, [_P, C.c_int32, _P]),
     ("rsys_retrieve_request", C.c_int32, [_P, C.c_int32, _P, C.c_int64, _P, C.c_int32, _P, _P, _P, _P, _P, _P, _P, C.c_int32, _P, _P, _P]),
+    ("rsys_rank_related_set", C.c_int32, [_P, C.c_int32, C.c_int64, _P, _P, _P]),
+    ("rsys_rank_request", C.c_int32, [_P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, C.c_int64, _P, _P, C.c_int64, _P, _P, _P, _P, _P, _P,
+                                      C.c_float, _P, _P, _P]),
     ("rsys_model_set_deterministic", C.c_int32, [_P, C.c_int32]),
     ("rsys_infer", C.c_int32, [_P, C.c_int32, _P, C.c_int64]),
     ("rsys_infer_select", C.c_int32, [_P, C.c_int32, _P, C.c_int64, _P, C.c_int64]),
@@ -131,6 +134,8 @@ _SIGS = [
                                           + [C.c_char_p, C.c_int32, C.POINTER(C.c_int32)]),
     ("rsys_op_attention", C.c_int32, [C.c_int32] + [C.c_int32] * 5 + [_P] * 9),
     ("rsys_op_topk", C.c_int32, [_P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P]),
+    ("rsys_rank_gram_get", C.c_int32, [_P, C.c_int32, C.c_int32, _P, _P, _P, C.c_int64]),
+    ("rsys_op_rerank", C.c_int32, [C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P]),
     ("rsys_op_embedding_scatter", C.c_int32, [_P, C.c_int64, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32]),
     ("rsys_op_rmsnorm_fwd", C.c_int32, [C.c_int32, _P, _P, _P, _P, C.c_int64, C.c_int32, _P, _P, _P]),
     ("rsys_op_rmsnorm_bwd", C.c_int32, [C.c_int32, C.c_int32] + [_P] * 11 + [C.c_int64, C.c_int32, _P, C.c_int32]),

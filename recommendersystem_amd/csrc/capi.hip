@@ -180,6 +180,24 @@ int32_t rsys_retrieve_request(rsys_model* h, int32_t medium, const float* querie
   return model_retrieve_request(h->m, medium, queries, n_queries, group, n_groups, hist_offsets, hist_medium, hist_ids, hist_status,
                                 sel_offsets, sel_medium, sel_ids, k, ids_out, scores_out, counts_out);
 }
+int32_t rsys_rank_related_set(rsys_model* h, int32_t medium, int64_t n, const int64_t* colptr, const int32_t* rowval, const float* nzval) {
+  CHECK_HANDLE(h);
+  return model_rank_related_set(h->m, medium, n, colptr, rowval, nzval);
+}
+int32_t rsys_rank_request(rsys_model* h, int32_t medium, int32_t n_groups, const int64_t* cand_offsets, const int32_t* cand_ids,
+                          const int32_t* partialk, const float* penalties, const float* queries, int64_t n_users, const int32_t* group,
+                          const float* r_masked, int64_t n_r_masked, const int64_t* hist_offsets, const int32_t* hist_medium,
+                          const int32_t* hist_ids, const int32_t* hist_status, const float* retrieval_coef, const float* rating_coefs,
+                          float rating_mean, const float* r_in, int32_t* ids_out, float* r_out) {
+  CHECK_HANDLE(h);
+  return model_rank_request(h->m, medium, n_groups, cand_offsets, cand_ids, partialk, penalties, queries, n_users, group, r_masked, n_r_masked,
+                            hist_offsets, hist_medium, hist_ids, hist_status, retrieval_coef, rating_coefs, rating_mean, r_in, ids_out, r_out);
+}
+int32_t rsys_rank_gram_get(rsys_model* h, int32_t medium, int32_t n_groups, const int64_t* cand_offsets, const int32_t* cand_ids, float* out,
+                           int64_t n_out) {
+  CHECK_HANDLE(h);
+  return model_rank_gram(h->m, medium, n_groups, cand_offsets, cand_ids, out, n_out);
+}
 int32_t rsys_model_set_deterministic(rsys_model* h, int32_t on) { CHECK_HANDLE(h); return model_set_deterministic(h->m, on); }
 int32_t rsys_infer(rsys_model* h, int32_t task, float* out, int64_t n) { CHECK_HANDLE(h); ARG_CHECK(out, "null"); return model_infer(h->m, task, nullptr, 0, out, n); }
 int32_t rsys_infer_select(rsys_model* h, int32_t task, const int32_t* token_index, int64_t n_tokens, float* out, int64_t n) {
@@ -832,6 +850,11 @@ int32_t rsys_op_attention(int32_t dtype, int32_t B, int32_t T, int32_t H, int32_
 int32_t rsys_op_topk(const float* scores, int64_t ld, int32_t rows, int32_t V, int32_t k, int32_t* ids, float* vals, int32_t* counts) {
   switches_parse();
   return op_topk(scores, ld, rows, V, k, ids, vals, counts);
+}
+int32_t rsys_op_rerank(int32_t n, int32_t partialk, const float* pen, const float* r, const float* gram, const int32_t* ss_bits,
+                       const int32_t* related_bits, int32_t* picks) {
+  switches_parse();
+  return op_rerank(n, partialk, pen, r, gram, ss_bits, related_bits, picks);
 }
 int32_t rsys_op_embedding_scatter(const float* gx0, int64_t ldx, const int32_t* matchedid, const int32_t* m_matchedid, int32_t N,
                                   int32_t V, int32_t D, float* gE, int32_t atomic) {

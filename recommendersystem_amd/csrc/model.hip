@@ -393,6 +393,7 @@ int model_destroy(Model* m) {
   for (void* p : m->allocs) hipFree(p);
   retrieve_free(m);
   retrieve_tables_free(m);
+  rank_free(m);
   if (m->copy_stream) { hipStreamSynchronize(m->copy_stream); hipStreamDestroy(m->copy_stream); }
   if (m->h_stage) hipHostFree(m->h_stage);
   if (m->slot_stage[1]) hipHostFree(m->slot_stage[1]);

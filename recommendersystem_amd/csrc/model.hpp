@@ -46,6 +46,7 @@ struct PhaseTimer {
 
 struct RetrieveWs;       // retrieve.hip
 struct RetrievalTables;  // retrieve_request.hip
+struct RankTables;       // rank_request.hip
 
 struct Model {
   rsys_config cfg;
@@ -266,6 +267,7 @@ struct Model {
   std::vector<hipEvent_t> step_marks;   // rsys_step_mark: one event per optimizer-step boundary (per-step time distribution)
   RetrieveWs* rws = nullptr;            // rsys_retrieve_topk's workspace (allocated on first use)
   RetrievalTables* rtab = nullptr;      // rsys_retrieve_request's serving tables and workspace (not part of checkpoints)
+  RankTables* rank = nullptr;           // rsys_rank_request's "{m}.related" tables and workspace (not part of checkpoints)
 };
 
 struct Optimizer {
@@ -315,6 +317,10 @@ void retrieve_free(Model* m);
 using RetrieveInit = std::function<int(float* sc, hipStream_t s)>;
 int model_retrieve_run(Model* m, int medium, const float* queries, int64_t nq, const int32_t* group, int32_t ng, const RetrieveInit& init,
                        int32_t k, int32_t* ids_out, float* scores_out, int32_t* counts_out);
+// z = Q F_m^T and lse of one chunk of <= RETRIEVE_CHUNK query rows (part: nc * RETRIEVE_LSE_SPLIT float2), as rsys_retrieve_topk scores
+constexpr int RETRIEVE_CHUNK = 256, RETRIEVE_LSE_SPLIT = 64;
+template <typename T>
+int retrieve_chunk_scores(Model* m, const T* qt, int nc, int q0, const T* Fm, int Vm, float* z, long long ldz, float2* part, float* lse);
 // retrieve_request.hip: the serving tables of rsys_retrieve_request (relations, item similarity, released set) and the request
 int model_retrieve_relations_set(Model* m, int medium, int kind, int64_t n_rows, int64_t n_cols, const int64_t* colptr, const int32_t* rowval,
                                  const float* nzval);
@@ -325,6 +331,18 @@ int model_retrieve_request(Model* m, int medium, const float* queries, int64_t n
                            const int32_t* sel_medium, const int32_t* sel_ids, int32_t k, int32_t* ids_out, float* scores_out,
                            int32_t* counts_out);
 void retrieve_tables_free(Model* m);
+const float* retrieve_similarity_table(Model* m, int medium, int64_t* dim);   // "embeddings.{m}" [V_m][dim] on the device, or null
+// rank_request.hip: ranking and diversity reranking of retrieved candidates (rsys_rank_related_set, rsys_rank_request, test hooks)
+int model_rank_related_set(Model* m, int medium, int64_t n, const int64_t* colptr, const int32_t* rowval, const float* nzval);
+int model_rank_request(Model* m, int medium, int32_t ng, const int64_t* cand_off, const int32_t* cand_ids, const int32_t* partialk,
+                       const float* penalties, const float* queries, int64_t nu, const int32_t* group, const float* r_masked, int64_t n_rm,
+                       const int64_t* hist_off, const int32_t* hist_medium, const int32_t* hist_ids, const int32_t* hist_status,
+                       const float* retrieval_coef, const float* rating_coefs, float rating_mean, const float* r_in, int32_t* ids_out,
+                       float* r_out);
+int model_rank_gram(Model* m, int medium, int32_t ng, const int64_t* cand_off, const int32_t* cand_ids, float* out, int64_t n_out);
+void rank_free(Model* m);
+int op_rerank(int32_t n, int32_t partialk, const float* pen, const float* r, const float* gram, const int32_t* ss_bits,
+              const int32_t* related_bits, int32_t* picks);
 int op_topk(const float* scores, int64_t ld, int32_t rows, int32_t V, int32_t k, int32_t* ids, float* vals, int32_t* counts);
 int optimizer_step(Optimizer* o, float lr_factor, float clip, float grad_div);
 

@@ -361,6 +361,28 @@ struct Carve {
 
 }  // namespace
 
+static_assert(RT_CHUNK == RETRIEVE_CHUNK && RT_LSE_SPLIT == RETRIEVE_LSE_SPLIT, "retrieval chunk constants");
+
+// z[r][0, V_m) = q_{q0 + r} . F_m[i] (gemm_retrieve, fp32 accumulation) and lse[q0 + r] for the nc <= RETRIEVE_CHUNK query rows of one
+// chunk; part holds nc * RETRIEVE_LSE_SPLIT partials.  The scoring of rsys_retrieve_topk, shared with rsys_rank_request.
+template <typename T>
+int retrieve_chunk_scores(Model* m, const T* qt, int nc, int q0, const T* Fm, int Vm, float* z, long long ldz, float2* part, float* lse) {
+  hipStream_t s = m->stream;
+  GemmParams p{};
+  p.A = qt; p.lda = m->D; p.B = Fm; p.ldb = m->D; p.C = z; p.ldc = ldz; p.c_f32 = 1;
+  p.M = nc; p.N = Vm; p.K = m->D; p.epi = EPI_STORE;
+  RC(gemm<T>(m, "gemm_retrieve", p, false, false, false));
+  tic(m, "retrieve_lse");
+  lse_partial_kernel<<<dim3(RT_LSE_SPLIT, nc), RT_THREADS, 0, s>>>(z, ldz, Vm, part);
+  RT_LAUNCH_CHECK();
+  lse_final_kernel<<<(nc + 255) / 256, 256, 0, s>>>(part, RT_LSE_SPLIT, nc, q0, lse);
+  RT_LAUNCH_CHECK();
+  toc(m);
+  return RSYS_OK;
+}
+template int retrieve_chunk_scores<float>(Model*, const float*, int, int, const float*, int, float*, long long, float2*, float*);
+template int retrieve_chunk_scores<bf16>(Model*, const bf16*, int, int, const bf16*, int, float*, long long, float2*, float*);
+
 // the retrieval workspace of a model: one device buffer, grown on demand, freed with the model
 struct RetrieveWs {
   void* buf = nullptr;
@@ -473,16 +495,7 @@ static int retrieve_t(Model* m, int medium, const float* queries, int64_t nq, co
   const T* Fm = AT<T>(m->FT) + (int64_t)vs * D;
   for (int ch = 0; ch < nchunks; ++ch) {
     const int q0 = ch * RT_CHUNK, nc = (int)std::min<int64_t>(RT_CHUNK, nq - q0);
-    GemmParams p{};
-    p.A = qt + (size_t)q0 * D; p.lda = D; p.B = Fm; p.ldb = D; p.C = z; p.ldc = ldz; p.c_f32 = 1;
-    p.M = nc; p.N = Vm; p.K = D; p.epi = EPI_STORE;
-    RC(gemm<T>(m, "gemm_retrieve", p, false, false, false));
-    tic(m, "retrieve_lse");
-    lse_partial_kernel<<<dim3(RT_LSE_SPLIT, nc), RT_THREADS, 0, s>>>(z, ldz, Vm, part);
-    RT_LAUNCH_CHECK();
-    lse_final_kernel<<<(nc + 255) / 256, 256, 0, s>>>(part, RT_LSE_SPLIT, nc, q0, lse);
-    RT_LAUNCH_CHECK();
-    toc(m);
+    RC(retrieve_chunk_scores<T>(m, qt + (size_t)q0 * D, nc, q0, Fm, Vm, z, ldz, part, lse));
     tic(m, "retrieve_combine");
     const dim3 grid(nb, ng);
     if (ch + 1 < nchunks)

@@ -290,6 +290,12 @@ int model_retrieve_relations_set(Model* m, int medium, int kind, int64_t n_rows,
   return RSYS_OK;
 }
 
+const float* retrieve_similarity_table(Model* m, int medium, int64_t* dim) {
+  const MediumTables& t = tables(m)->t[medium];
+  *dim = t.dim;
+  return t.emb;
+}
+
 int model_retrieve_similarity_set(Model* m, int medium, int64_t dim, const float* emb, const float* crossproject) {
   ARG_CHECK(medium == 0 || medium == 1, "retrieve_similarity_set: medium must be 0 or 1");
   if (emb) ARG_CHECK(dim >= 4 && dim <= RR_MAXDIM && dim % 4 == 0, "retrieve_similarity_set: dim must be a multiple of 4 in [4, 2048]");

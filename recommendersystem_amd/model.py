@@ -482,6 +482,93 @@ class RecommenderModel:
                                           scores.ctypes.data, counts.ctypes.data))
         return ids, scores, counts
 
+    # ---- ranking and reranking of retrieved candidates (rsys_rank_request: Inference/render.jl:335-435)
+    def set_related(self, medium, related=None):
+        """Loads "{m}.related" (V_m x V_m, a 0-based CSC `(indptr, indices, data, shape)` tuple or an object with those attributes) onto
+        the device for `rank_request`'s same-series and related penalties; None clears it.  Values as `set_retrieval_relations`."""
+        if related is None:
+            check(lib().rsys_rank_related_set(self._h, int(medium), 0, None, None, None))
+            return
+        indptr, indices, data, shape = csc_parts(related)
+        if shape[0] != shape[1]:
+            raise ValueError(f"related has shape {shape}, expected a square V_m x V_m matrix")
+        check(lib().rsys_rank_related_set(self._h, int(medium), int(shape[1]), indptr.ctypes.data, indices.ctypes.data, data.ctypes.data))
+
+    def rank_request(self, queries, medium, candidates, group=None, r_masked=None, partialk=None, penalties=None, histories=None,
+                     retrieval_coef=None, rating_coefs=None, rating_mean=0.0, scores=None, rerank=True):
+        """render.jl `ranking` + `reranking!` per group on the device (rsys_rank_request).  `candidates`: one array of distinct medium-local
+        ids per group (1..1024 each); `queries` (n_users, D) the users' "{m}.retrieval" embeddings; `group` (n_users,) group ids or None
+        (one group per user); `r_masked`: one array per user of its group's candidates' rating-head values; `partialk`: rounds per group;
+        `penalties`: per group (decay, mmr_penalty, same_series_penalty, related_penalty); `histories`: per user (medium, id, status) list
+        items or None; `retrieval_coef`, `rating_coefs` (c0, c1), `rating_mean`: the registry's (None: p = softmax, r = r_masked);
+        `scores`: one given ranking-score array per group instead of computing them (queries and r_masked are then not needed);
+        rerank=False: ranking only.  Returns (ids per group in pick order, min(partialk, n) each, or None; ranking scores per group)."""
+        ng = len(candidates)
+        cand = [np.asarray(c, np.int64).reshape(-1) for c in candidates]
+        off = np.zeros(ng + 1, np.int64)
+        off[1:] = np.cumsum([c.size for c in cand])
+        ids_in = np.ascontiguousarray(np.concatenate(cand) if ng else np.zeros(0), np.int32)
+        N = int(off[-1])
+        q = None
+        if queries is not None:
+            q = np.ascontiguousarray(queries, np.float32)
+            if q.ndim == 1:
+                q = q[None, :]
+        nu = q.shape[0] if q is not None else (len(np.asarray(group).reshape(-1)) if group is not None else ng)
+        gp = None if group is None else np.ascontiguousarray(group, np.int32).reshape(-1)
+        if gp is not None and gp.size != nu:
+            raise ValueError(f"group has {gp.size} entries for {nu} users")
+        rm = None
+        if r_masked is not None:
+            if len(r_masked) != nu:
+                raise ValueError(f"r_masked has {len(r_masked)} rows for {nu} users")
+            rm = np.ascontiguousarray(np.concatenate([np.asarray(x, np.float32).reshape(-1) for x in r_masked]) if nu else np.zeros(0),
+                                      np.float32)
+        pk = pen = None
+        if rerank:
+            pk = np.ascontiguousarray(partialk, np.int32).reshape(-1)
+            pen = np.ascontiguousarray(penalties, np.float32).reshape(-1)
+            if pk.size != ng or pen.size != 4 * ng:
+                raise ValueError(f"partialk and penalties need {ng} entries and {ng} x 4 values")
+        h = None
+        if histories is not None:
+            if len(histories) != nu:
+                raise ValueError(f"histories has {len(histories)} lists for {nu} users")
+            h = triples_csr(histories, 3)
+        rin = None
+        if scores is not None:
+            rin = np.ascontiguousarray(np.concatenate([np.asarray(x, np.float32).reshape(-1) for x in scores]), np.float32)
+            if rin.size != N:
+                raise ValueError(f"scores hold {rin.size} values for {N} candidates")
+        rc = None if retrieval_coef is None else np.array([float(np.asarray(retrieval_coef).reshape(-1)[0])], np.float32)
+        kc = None if rating_coefs is None else np.ascontiguousarray(np.asarray(rating_coefs, np.float32).reshape(-1)[:2])
+        ids = np.empty(max(N, 1), np.int32) if rerank else None
+        rout = np.empty(max(N, 1), np.float32)
+        ptr = lambda a: None if a is None else a.ctypes.data
+        hp = (None,) * 4 if h is None else tuple(ptr(a) for a in h)
+        check(lib().rsys_rank_request(self._h, int(medium), ng, off.ctypes.data, ids_in.ctypes.data, ptr(pk), ptr(pen), ptr(q), nu, ptr(gp),
+                                      ptr(rm), 0 if rm is None else rm.size, *hp, ptr(rc), ptr(kc), float(rating_mean), ptr(rin), ptr(ids),
+                                      rout.ctypes.data))
+        picked = None
+        if rerank:
+            picked = [ids[off[j]:off[j] + min(int(pk[j]), int(off[j + 1] - off[j]))].copy() for j in range(ng)]
+        return picked, [rout[off[j]:off[j + 1]].copy() for j in range(ng)]
+
+    def rank_gram(self, medium, candidates):
+        """rsys_rank_gram_get (test hook): per group the fp32 Gram matrix (n, n) of the candidates' item-similarity rows, as the
+        reranking loop reads it."""
+        cand = [np.asarray(c, np.int64).reshape(-1) for c in candidates]
+        off = np.zeros(len(cand) + 1, np.int64)
+        off[1:] = np.cumsum([c.size for c in cand])
+        ids_in = np.ascontiguousarray(np.concatenate(cand), np.int32)
+        n2 = int(sum(c.size * c.size for c in cand))
+        out = np.empty(max(n2, 1), np.float32)
+        check(lib().rsys_rank_gram_get(self._h, int(medium), len(cand), off.ctypes.data, ids_in.ctypes.data, out.ctypes.data, n2))
+        res, at = [], 0
+        for c in cand:
+            res.append(out[at:at + c.size * c.size].reshape(c.size, c.size).copy()); at += c.size * c.size
+        return res
+
     def trunk_output(self, rows):
         S = self.config["max_sequence_length"]; D = self.config["embed_dim"]
         out = np.empty((rows, 2 * S, D), np.float32)

@@ -307,3 +307,159 @@ def retrieval(model, states, k=1024, coefs=None):
                 s = (s.astype(np.float64) + members[g] * np.log(float(np.asarray(coefs).reshape(-1)[0]))).astype(np.float32)
             out[j] = (ids[g, :n].copy(), s)
     return out
+
+
+# ---------------------------------------------------------------- ranking and reranking (render.jl `ranking`, `reranking!`, `render`)
+MAX_ITEMS_TO_RANK = 1024          # render.jl:449
+RETRIEVAL_CAP = 8192              # candidates rsys_retrieve_request returns at most
+
+
+def load_ranking_tables(model, relations):
+    """Loads render.jl's "{m}.related" (a Julia-shaped SparseMatrixCSC dict or a 0-based CSC tuple / object, `julia_csc`) onto the
+    device for `reranking`; a medium whose key is absent is left as it is.  The item-similarity embeddings come from
+    `load_retrieval_tables`."""
+    for m in (0, 1):
+        if f"{m}.related" in relations:
+            model.set_related(m, julia_csc(relations[f"{m}.related"]))
+
+
+def _registry_coefs(registry, m):
+    """(retrieval coefficient or None, rating coefficients or None, rating mean) as compute_retrieval / compute_ranking read them"""
+    if registry is None:
+        return None, None, 0.0
+    rc = registry.get(f"{m}.retrieval.coefs")
+    kc = registry.get(f"{m}.rating.coefs")
+    rc = None if rc is None else float(np.asarray(rc).reshape(-1)[0])
+    kc = None if kc is None else np.asarray(kc, np.float32).reshape(-1)[:2]
+    mean = float(np.asarray(registry[f"{m}.rating_mean"])) if kc is not None else 0.0
+    return rc, kc, mean
+
+
+def rank_arrays(states, idxs, with_embeds=True):
+    """The per-user arguments of `RecommenderModel.rank_request` for render.jl states of one medium (one group per state, `idxs[g]` its
+    candidates): queries (n, D) or None, group ids, r_masked (one row per user: its "{m}.ranking" values), list items (medium,
+    matchedid, status) in list order -- every entry, duplicates and all statuses included -- and per group the penalties
+    (decay, mmr_penalty, same_series_penalty, related_penalty) of `state["penalties"]`."""
+    q, group, rm, hist, pen = [], [], [], [], []
+    for g, st in enumerate(states):
+        m = int(st["medium"])
+        if not st["users"]:
+            raise ValueError("ranking: every state needs at least one user")
+        p = st.get("penalties", {})
+        pen.append([float(p.get(k, 0.0)) for k in ("decay", "mmr_penalty", "same_series_penalty", "related_penalty")])
+        for u in st["users"]:
+            group.append(g)
+            hist.append([(int(x["medium"]), int(x["matchedid"]), int(x["status"])) for x in u["user"]["items"]])
+            if with_embeds:
+                q.append(np.asarray(u["embeds"][f"{m}.retrieval"], np.float32).reshape(-1))
+                r = np.asarray(u["embeds"][f"{m}.ranking"], np.float32).reshape(-1)
+                if r.size != len(idxs[g]):
+                    raise ValueError(f"ranking: a user has {r.size} \"{m}.ranking\" values for {len(idxs[g])} candidates")
+                rm.append(r)
+    return (np.stack(q) if with_embeds else None), np.asarray(group, np.int32), (rm if with_embeds else None), hist, \
+        np.asarray(pen, np.float32).reshape(-1, 4)
+
+
+def _by_medium(states):
+    out = {}
+    for j, st in enumerate(states):
+        m = int(st["medium"])
+        if m not in (0, 1):
+            raise ValueError("medium must be 0 or 1")
+        out.setdefault(m, []).append(j)
+    return sorted(out.items())
+
+
+def ranking(model, states, idxs, registry=None):
+    """render.jl `ranking(state, idxs)` on the device for a list of states (one candidate array `idxs[j]` of 0-based medium-local ids
+    per state): score = sum over the state's users, in order, of log(p_u[idxs]) + r_u, with p_u = coef * softmax(table_m . u) and
+    r_u = c0 * rating_mean + c1 * "{m}.ranking" (compute_retrieval / compute_ranking; without registry coefficients p_u = softmax and
+    r_u = "{m}.ranking").  Every user needs "{m}.retrieval" and "{m}.ranking" (the rating head at the candidates, `predict(...,
+    "ranking")`) in its embeds.  Returns one float32 score array per state."""
+    out = [None] * len(states)
+    for m, js in _by_medium(states):
+        sub, cand = [states[j] for j in js], [np.asarray(idxs[j]) for j in js]
+        q, group, rm, hist, _ = rank_arrays(sub, cand)
+        rc, kc, mean = _registry_coefs(registry, m)
+        _, r = model.rank_request(q, m, cand, group=group, r_masked=rm, retrieval_coef=rc, rating_coefs=kc, rating_mean=mean, rerank=False)
+        for g, j in enumerate(js):
+            out[j] = r[g]
+    return out
+
+
+def reranking(model, states, idxs, r, partialk):
+    """render.jl `reranking!(state, idxs, r, partialk)` on the device: per state the greedy min(partialk, n) picks under the MMR,
+    same-series and related penalties of `state["penalties"]` (keys decay, mmr_penalty, same_series_penalty, related_penalty) from the
+    tables of `load_retrieval_tables` (item similarity) and `load_ranking_tables` ("{m}.related").  `r`: one score array per state;
+    `partialk`: an int or one per state.  Returns one array of picked ids (0-based medium-local, in pick order) per state."""
+    pks = [int(partialk)] * len(states) if np.ndim(partialk) == 0 else [int(x) for x in partialk]
+    out = [None] * len(states)
+    for m, js in _by_medium(states):
+        sub, cand = [states[j] for j in js], [np.asarray(idxs[j]) for j in js]
+        _, group, _, hist, pen = rank_arrays(sub, cand, with_embeds=False)
+        ids, _ = model.rank_request(None, m, cand, group=group, partialk=[pks[j] for j in js], penalties=pen, histories=hist,
+                                    scores=[r[j] for j in js])
+        for g, j in enumerate(js):
+            out[j] = ids[g]
+    return out
+
+
+def page_window(n_retrieved, pagination):
+    """render.jl:447-465 for one state: (start, stop) of the ranked slice of the retrieved list, (sidx, eidx) 1-based within it, or None
+    when the page starts past the list.  max_items_to_rank = 1024 - 1024 % limit.  Deviation: render.jl throws a BoundsError when the
+    ranked slice runs past the retrieved list; here it is clamped to it."""
+    limit, offset = int(pagination["limit"]), int(pagination["offset"])
+    if limit < 1 or offset < 0:
+        raise ValueError("pagination: limit >= 1 and offset >= 0")
+    mitr = MAX_ITEMS_TO_RANK - MAX_ITEMS_TO_RANK % limit
+    sidx, eidx = offset + 1, offset + limit
+    if sidx > n_retrieved:
+        return None
+    eidx = min(eidx, n_retrieved)
+    page = (sidx - 1) // mitr
+    start, stop = page * mitr, min((page + 1) * mitr, n_retrieved)
+    return start, stop, sidx - start, eidx - start
+
+
+def render(model, states, pagination, registry=None, max_ranking_items=None):
+    """render.jl `render(state, pagination)` (lines 437-474) without the card rendering, for a list of states: `retrieval`, the page's
+    slice of at most 1024 candidates, the ranking forward (`predict(..., "ranking")` in chunks of at most `max_ranking_items` candidates,
+    default the model's S - S // 2; candidates are masked from each other, so chunking does not change the result), then `ranking` +
+    `reranking` in one device call with partialk = the page's last index.  `pagination`: {"offset", "limit"} or one per state.  Returns
+    one (ids of the page, total) pair per state.  Deviations: the ranked slice is clamped to the retrieved list (render.jl throws a
+    BoundsError), and total = min(admissible items, 8192), the retrieval cap."""
+    pags = [pagination] * len(states) if isinstance(pagination, dict) else list(pagination)
+    S = model.config["max_sequence_length"]
+    max_user_len = S // 2
+    chunk = S - max_user_len if max_ranking_items is None else min(int(max_ranking_items), S - max_user_len)
+    if chunk < 1:
+        raise ValueError("render: max_ranking_items must be >= 1")
+    retrieved = retrieval(model, states, k=RETRIEVAL_CAP, coefs=None)
+    out = [None] * len(states)
+    work = []
+    for j, st in enumerate(states):
+        ids = retrieved[j][0]
+        win = page_window(ids.size, pags[j])
+        if win is None:
+            out[j] = (np.zeros(0, np.int32), int(ids.size))
+            continue
+        work.append((j, ids[win[0]:win[1]], win[2], win[3], int(ids.size)))
+    for m, js in _by_medium([states[w[0]] for w in work]) if work else []:
+        items = [work[i] for i in js]
+        sub = [states[w[0]] for w in items]
+        for st, w in zip(sub, items):         # the ranking forward: "{m}.ranking" at the page's candidates, per user
+            cand = w[1]
+            for u in st["users"]:
+                vals = []
+                for c0 in range(0, cand.size, chunk):
+                    req = dict(u["user"], ranking_items=[int(x) for x in cand[c0:c0 + chunk]])
+                    vals += predict(model, [req], "ranking", m, max_user_len, S - max_user_len)[0][f"{m}.ranking"]
+                u.setdefault("embeds", {})[f"{m}.ranking"] = np.asarray(vals, np.float32)
+        cand = [w[1] for w in items]
+        q, group, rm, hist, pen = rank_arrays(sub, cand)
+        rc, kc, mean = _registry_coefs(registry, m)
+        ids, _ = model.rank_request(q, m, cand, group=group, r_masked=rm, partialk=[w[3] for w in items], penalties=pen, histories=hist,
+                                    retrieval_coef=rc, rating_coefs=kc, rating_mean=mean)
+        for g, w in enumerate(items):
+            out[w[0]] = (ids[g][w[2] - 1:w[3]], w[4])
+    return out
