@@ -148,6 +148,20 @@ int32_t rsys_retrieve_topk(rsys_model* m, int32_t medium,
                            const int64_t* excl_offsets, const int32_t* excl_ids, /* CSR over groups of medium-local ids, or both NULL */
                            int32_t k, int32_t* ids_out, float* scores_out,   /* [n_groups][k] each */
                            int32_t* counts_out);                             /* [n_groups] */
+/* Finetune evaluation (Finetune/regress.jl:193-266): per query q the rank and log-probability of one target item t_q, on the scores of
+ * rsys_retrieve_topk.  s_i = z_q[i] - lse_q in fp32, bit for bit the score rsys_retrieve_topk gives item i for a one-query group
+ * without prior (lse_q over every item of the medium, exclusions included).  logp_out[q] = s_{t_q}, read before any exclusion.
+ * Admissible: not in q's exclusion list (duplicates allowed) and s_i neither NaN nor -inf; -0.0 equals +0.0.
+ * rank_out[q] = 1 + #{i admissible : s_i > s_t} + #{i admissible, i < t : s_i == s_t}, the 1-based position of t in Julia's
+ * partialsortperm(logp, rev=true) (ties by ascending id) and in rsys_retrieve_topk's order; 0 when t itself is not admissible.
+ * 1 <= n_queries <= 4096, replicated table only.  Works without an uploaded batch (rebuilds the fused table when stale) and changes no
+ * model state; synchronous, bitwise reproducible; the device workspace grows on demand and is freed with the model.  ARG errors: a
+ * target or exclusion id outside [0, V_m), malformed offsets, a bad medium. */
+int32_t rsys_retrieve_target_rank(rsys_model* m, int32_t medium,
+                                  const float* queries, int64_t n_queries,          /* [n_queries][embed_dim] f32, host */
+                                  const int32_t* targets,                           /* [n_queries] medium-local, in [0, V_m) */
+                                  const int64_t* excl_offsets, const int32_t* excl_ids, /* CSR over queries of medium-local ids, or both NULL */
+                                  int32_t* rank_out, float* logp_out);              /* [n_queries] each */
 /* The serving tables of rsys_retrieve_request (Inference/render.jl:240-331, `retrieval(state)`), held on the device by the model, freed with
  * it, not part of checkpoints; loading them changes nothing else (the fused item table stays valid).  Every setter replaces the table;
  * a NULL array clears it.

@@ -71,6 +71,10 @@ int32_t rsys_op_attention(int32_t dtype, int32_t B, int32_t T, int32_t H, int32_
  * counts [rows]; 1 <= k <= min(V, 8192) */
 int32_t rsys_op_topk(const float* scores, int64_t ld, int32_t rows, int32_t V, int32_t k,
                      int32_t* ids, float* vals, int32_t* counts);
+/* the count of rsys_retrieve_target_rank alone, on caller-provided device buffers: per row r of scores [rows][ld >= V] (NaN or -inf marks
+ * an inadmissible entry, -0.0 == +0.0) rank_out[r] = 1 + #{admissible i : s_i > s_t} + #{admissible i < t : s_i == s_t} with
+ * t = targets[r] in [0, V), or 0 when s_t is NaN or -inf; 1 <= rows <= 65535 */
+int32_t rsys_op_target_rank(const float* scores, int64_t ld, int32_t rows, int32_t V, const int32_t* targets, int32_t* rank_out);
 /* rsys_rank_request's Gram matrices alone, as its loop reads them: out = per group in order, G_g [n_g][n_g] row-major (sum of n_g^2 floats),
  * computed by the same kernel from the model's item-similarity table of `medium`; host arrays */
 int32_t rsys_rank_gram_get(rsys_model* m, int32_t medium, int32_t n_groups, const int64_t* cand_offsets, const int32_t* cand_ids,

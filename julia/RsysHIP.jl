@@ -211,6 +211,18 @@ function retrieve_topk(m::Model, medium::Integer, Q::Matrix{Float32}, k::Integer
         m.h, medium, Q, size(Q, 2), g, n_groups, p, off, xid, k, ids, scores, counts))
     ids, scores, counts
 end
+# finetune evaluation (Finetune/regress.jl:193-266): per query (column of Q) the rank of its target among the admissible items (0 when
+# the target is excluded) and the target's log-probability; targets and exclusion ids are 0-based medium-local, excl one vector per query
+function retrieve_target_rank(m::Model, medium::Integer, Q::Matrix{Float32}, targets; excl = nothing)
+    t = Vector{Int32}(targets)
+    off = excl === nothing ? Ptr{Int64}(C_NULL) : Int64[0; cumsum(Int64[length(e) for e in excl])]
+    xid = excl === nothing ? Ptr{Int32}(C_NULL) : Int32[reduce(vcat, excl; init = Int32[])...]
+    rank = Vector{Int32}(undef, size(Q, 2)); logp = Vector{Float32}(undef, size(Q, 2))
+    GC.@preserve Q t off xid rank logp check(ccall((:rsys_retrieve_target_rank, LIB), Int32,
+        (Ptr{Cvoid}, Int32, Ptr{Float32}, Int64, Ptr{Int32}, Ptr{Int64}, Ptr{Int32}, Ptr{Int32}, Ptr{Float32}),
+        m.h, medium, Q, size(Q, 2), t, off, xid, rank, logp))
+    rank, logp
+end
 # whole retrieval requests (Inference/render.jl:240-331, `retrieval(state)`): the serving tables are loaded onto the device once, then
 # retrieve_request needs only the users' embeddings, their list items and the selected items.  kind: 0 = "{m}.dependencies",
 # 1 = "{m}.recaps", 2 = "{m}.adaptations"; 0-based CSC arrays, or colptr = nothing to clear the table.

@@ -74,6 +74,7 @@ _SIGS = [
     ("rsys_head_rows_get", C.c_int32, [_P, C.POINTER(C.c_int32 * 4)]),
     ("rsys_item_table", C.c_int32, [_P, _P, C.c_int64]),
     ("rsys_retrieve_topk", C.c_int32, [_P, C.c_int32, _P, C.c_int64, _P, C.c_int32, _P, _P, _P, C.c_int32, _P, _P, _P]),
+    ("rsys_retrieve_target_rank", C.c_int32, [_P, C.c_int32, _P, C.c_int64, _P, _P, _P, _P, _P]),
     ("rsys_retrieve_relations_set", C.c_int32, [_P, C.c_int32, C.c_int32, C.c_int64, C.c_int64, _P, _P, _P]),
     ("rsys_retrieve_similarity_set", C.c_int32, [_P, C.c_int32, C.c_int64, _P, _P]),
     ("rsys_retrieve_released_set", C.c_int32, [_P, C.c_int32, _P]),
@@ -134,6 +135,7 @@ _SIGS = [
                                           + [C.c_char_p, C.c_int32, C.POINTER(C.c_int32)]),
     ("rsys_op_attention", C.c_int32, [C.c_int32] + [C.c_int32] * 5 + [_P] * 9),
     ("rsys_op_topk", C.c_int32, [_P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P]),
+    ("rsys_op_target_rank", C.c_int32, [_P, C.c_int64, C.c_int32, C.c_int32, _P, _P]),
     ("rsys_rank_gram_get", C.c_int32, [_P, C.c_int32, C.c_int32, _P, _P, _P, C.c_int64]),
     ("rsys_op_rerank", C.c_int32, [C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P]),
     ("rsys_op_embedding_scatter", C.c_int32, [_P, C.c_int64, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32]),

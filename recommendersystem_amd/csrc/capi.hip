@@ -159,6 +159,11 @@ int32_t rsys_retrieve_topk(rsys_model* h, int32_t medium, const float* queries, 
   return model_retrieve_topk(h->m, medium, queries, n_queries, group, n_groups, prior, excl_offsets, excl_ids, k, ids_out, scores_out,
                              counts_out);
 }
+int32_t rsys_retrieve_target_rank(rsys_model* h, int32_t medium, const float* queries, int64_t n_queries, const int32_t* targets,
+                                  const int64_t* excl_offsets, const int32_t* excl_ids, int32_t* rank_out, float* logp_out) {
+  CHECK_HANDLE(h);
+  return model_retrieve_target_rank(h->m, medium, queries, n_queries, targets, excl_offsets, excl_ids, rank_out, logp_out);
+}
 int32_t rsys_retrieve_relations_set(rsys_model* h, int32_t medium, int32_t kind, int64_t n_rows, int64_t n_cols, const int64_t* colptr,
                                     const int32_t* rowval, const float* nzval) {
   CHECK_HANDLE(h);
@@ -850,6 +855,10 @@ int32_t rsys_op_attention(int32_t dtype, int32_t B, int32_t T, int32_t H, int32_
 int32_t rsys_op_topk(const float* scores, int64_t ld, int32_t rows, int32_t V, int32_t k, int32_t* ids, float* vals, int32_t* counts) {
   switches_parse();
   return op_topk(scores, ld, rows, V, k, ids, vals, counts);
+}
+int32_t rsys_op_target_rank(const float* scores, int64_t ld, int32_t rows, int32_t V, const int32_t* targets, int32_t* rank_out) {
+  switches_parse();
+  return op_target_rank(scores, ld, rows, V, targets, rank_out);
 }
 int32_t rsys_op_rerank(int32_t n, int32_t partialk, const float* pen, const float* r, const float* gram, const int32_t* ss_bits,
                        const int32_t* related_bits, int32_t* picks) {

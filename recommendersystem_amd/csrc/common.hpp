@@ -63,6 +63,14 @@ template <> __device__ __forceinline__ bf16 from_f32<bf16>(float x) { return (bf
 
 __device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }
 
+// order-preserving key of a retrieval score (retrieve.hip, retrieve_eval.hip): larger score -> larger key; -0.0 is +0.0; -inf and NaN
+// map to 0, which no admissible score produces (the smallest, -FLT_MAX, maps to 0x00800000)
+__device__ __forceinline__ unsigned score_key(float s) {
+  if (!(s > -INFINITY)) return 0u;
+  const unsigned u = __float_as_uint(s == 0.f ? 0.f : s);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

@@ -394,6 +394,7 @@ int model_destroy(Model* m) {
   retrieve_free(m);
   retrieve_tables_free(m);
   rank_free(m);
+  retrieve_eval_free(m);
   if (m->copy_stream) { hipStreamSynchronize(m->copy_stream); hipStreamDestroy(m->copy_stream); }
   if (m->h_stage) hipHostFree(m->h_stage);
   if (m->slot_stage[1]) hipHostFree(m->slot_stage[1]);

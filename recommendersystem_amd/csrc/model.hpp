@@ -47,6 +47,7 @@ struct PhaseTimer {
 struct RetrieveWs;       // retrieve.hip
 struct RetrievalTables;  // retrieve_request.hip
 struct RankTables;       // rank_request.hip
+struct EvalWs;           // retrieve_eval.hip
 
 struct Model {
   rsys_config cfg;
@@ -268,6 +269,7 @@ struct Model {
   RetrieveWs* rws = nullptr;            // rsys_retrieve_topk's workspace (allocated on first use)
   RetrievalTables* rtab = nullptr;      // rsys_retrieve_request's serving tables and workspace (not part of checkpoints)
   RankTables* rank = nullptr;           // rsys_rank_request's "{m}.related" tables and workspace (not part of checkpoints)
+  EvalWs* ews = nullptr;                // rsys_retrieve_target_rank's workspace (allocated on first use)
 };
 
 struct Optimizer {
@@ -344,6 +346,11 @@ void rank_free(Model* m);
 int op_rerank(int32_t n, int32_t partialk, const float* pen, const float* r, const float* gram, const int32_t* ss_bits,
               const int32_t* related_bits, int32_t* picks);
 int op_topk(const float* scores, int64_t ld, int32_t rows, int32_t V, int32_t k, int32_t* ids, float* vals, int32_t* counts);
+// retrieve_eval.hip: the rank and log-probability of one target item per query (rsys_retrieve_target_rank) and the count alone
+int model_retrieve_target_rank(Model* m, int medium, const float* queries, int64_t nq, const int32_t* targets, const int64_t* excl_off,
+                               const int32_t* excl_ids, int32_t* rank_out, float* logp_out);
+void retrieve_eval_free(Model* m);
+int op_target_rank(const float* scores, int64_t ld, int32_t rows, int32_t V, const int32_t* targets, int32_t* rank_out);
 int optimizer_step(Optimizer* o, float lr_factor, float clip, float grad_div);
 
 }  // namespace rsys

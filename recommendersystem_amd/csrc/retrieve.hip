@@ -32,13 +32,7 @@ struct SelState {
   int need, total, done, pad0, pad1, pad2;
 };
 
-// order-preserving key: larger score -> larger key; -0.0 is +0.0; -inf and NaN map to 0, which no admissible score produces
-// (the smallest, -FLT_MAX, maps to 0x00800000)
-__device__ __forceinline__ unsigned score_key(float s) {
-  if (!(s > -INFINITY)) return 0u;
-  const unsigned u = __float_as_uint(s == 0.f ? 0.f : s);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
+// score_key (common.hpp) is the order-preserving key; key_score maps a key back to its score
 __device__ __forceinline__ float key_score(unsigned k) {
   return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
 }

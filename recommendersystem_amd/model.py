@@ -393,6 +393,38 @@ class RecommenderModel:
                                        ids.ctypes.data, scores.ctypes.data, counts.ctypes.data))
         return ids, scores, counts
 
+    TARGET_RANK_MAXQ = 4096           # queries per rsys_retrieve_target_rank call
+
+    def retrieve_target_rank(self, queries, medium, targets, exclude=None):
+        """Finetune evaluation on the device (rsys_retrieve_target_rank, Finetune/regress.jl:193-266): per query of `queries` (n, D) the
+        1-based rank of its target (`targets` (n,) medium-local ids) among the admissible items by the log soft-max score of
+        `retrieve_topk` (descending, ties by ascending id; 0 when the target itself is excluded, -inf or NaN) and the target's
+        log-probability, read before the exclusions.  `exclude`: one array of medium-local ids per query, or None.  Calls of more than
+        4096 queries are split.  Returns (rank (n,) int32, logp (n,) float32)."""
+        q = np.ascontiguousarray(queries, np.float32)
+        if q.ndim == 1:
+            q = q[None, :]
+        n = q.shape[0]
+        t = np.ascontiguousarray(targets, np.int32).reshape(-1)
+        if t.size != n:
+            raise ValueError(f"targets has {t.size} entries for {n} queries")
+        if exclude is not None and len(exclude) != n:
+            raise ValueError(f"exclude has {len(exclude)} lists for {n} queries")
+        rank = np.empty(n, np.int32)
+        logp = np.empty(n, np.float32)
+        ptr = lambda a: None if a is None else a.ctypes.data
+        for a in range(0, max(n, 1), self.TARGET_RANK_MAXQ):
+            b = min(n, a + self.TARGET_RANK_MAXQ)
+            off = ids_x = None
+            if exclude is not None:
+                off, ids_x = exclusion_csr(exclude[a:b], b - a)
+            qa, ta = np.ascontiguousarray(q[a:b]), np.ascontiguousarray(t[a:b])
+            ra_, la = np.empty(b - a, np.int32), np.empty(b - a, np.float32)
+            check(lib().rsys_retrieve_target_rank(self._h, int(medium), qa.ctypes.data, b - a, ta.ctypes.data, ptr(off), ptr(ids_x),
+                                                  ra_.ctypes.data, la.ctypes.data))
+            rank[a:b], logp[a:b] = ra_, la
+        return rank, logp
+
     # ---- whole retrieval requests (rsys_retrieve_request): serving tables loaded once, then one call per batch of requests
     def _vocab(self, medium):
         if medium not in (0, 1):
