@@ -2,11 +2,16 @@
 forward + backward + gradient all-reduce + clip + AdamW on synthetic histories.
 
   python bench.py --gpus 1 --steps 10 --warmup 3
+  python bench.py --gpus 1 --steps 10 --warmup 3 --full
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
       bench.py --gpus N --steps K --warmup W
 
 Workload = cfg-3 of SURVEY.md section 8 (retrieval d=512 seq=512, 200K items, L=8, 64 rows per GPU per
 step): data-parallel, weak scaling (per-GPU rows fixed).  Prints ONE JSON line on rank 0.
+
+A plain run does only what that line's headline needs: set-up, warm-up, the timed steps, --dump-outputs if asked, the line.  --full
+adds every other measurement and check: the CPU baseline, the two child rocprofv3 --pmc passes behind roofline.traffic, the
+train_epoch loop, the legs at other configurations and, with a communicator, the replica checksums and the step without all-reduce.
 """
 import argparse
 import json
@@ -418,6 +423,10 @@ def main():
     ap.add_argument("--rows", type=int, default=64)
     ap.add_argument("--dtype", default="bf16")
     ap.add_argument("--layers", type=int, default=None)
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: cpu_baseline, the live PMC passes of roofline.traffic (else read from the "
+                         "committed summary), train_loop_*, other_configs and, with a communicator, replicas_consistent and "
+                         "allreduce_exposed_ms_per_step; --no-cpu-baseline, --no-live-pmc, --no-train-loop and --no-extra-legs leave single parts of it out")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-kernel-timing", action="store_true")
     ap.add_argument("--no-live-pmc", action="store_true", help="do not run the two child rocprofv3 --pmc passes (roofline.traffic then comes from the committed summary)")
@@ -506,7 +515,7 @@ def main():
         model.set_shard_comm(comm)             # row exchange + vocabulary-parallel head run on this communicator
     # DDP broadcasts rank 0's parameters when it wraps the model (transformer.py:678-682); here every rank initialised from the same seed
     # and the ranks compare device-side checksums of their parameter buffers: now, and again behind the timed steps
-    replicas = {"after_init": rdist.assert_replicas_equal(model, comm, "after init") is not None} if (comm is not None and world > 1) else None
+    replicas = {"after_init": rdist.assert_replicas_equal(model, comm, "after init") is not None} if (args.full and comm is not None and world > 1) else None
     sched = LambdaLR(WSDScheduler(warmup_steps=2000, total_steps=250000, decay_ratio=0.1, final_ratio=0.1))
     for _ in range(2000):
         sched.step()                           # bench at the stable learning rate
@@ -609,7 +618,7 @@ def main():
     # the reference's real loop (train.py:238-283) beside the resident-batch number: every step uploads its batch from an
     # in-memory shard (to_device) and reads its losses back (the host sync train_epoch does), through train.train_epoch
     loop_ms = None
-    if not args.no_train_loop:
+    if args.full and not args.no_train_loop:
         # (the resident batch itself, uploaded again every step: a step's time depends on its batch, so the loop is held against the
         # resident-batch step on the same data)
         loader = [d for i in range(max(4, args.steps))]
@@ -622,7 +631,7 @@ def main():
     # exposed (non-overlapped) all-reduce time: the same resident-batch step with the gradient all-reduce left
     # out.  Measured LAST: from here on the ranks' parameters drift apart, and nothing that is reported runs afterwards.
     nocomm_ms = None
-    if comm is not None and not sharded:
+    if args.full and comm is not None and not sharded:
         model.upload(d)
 
         def step_nc():
@@ -735,7 +744,7 @@ def main():
         # profiles/ and only describes that workload
         pmc_applies = args.config == "cfg3" and rows == 64 and args.layers is None and args.dtype == "bf16" and not sharded and not args.deterministic
         traffic_note = None
-        live_ok = (pmc_applies and world == 1 and rows == 64 and not args.no_live_pmc and not args.detail and not args.no_kernel_timing
+        live_ok = (args.full and pmc_applies and world == 1 and rows == 64 and not args.no_live_pmc and not args.detail and not args.no_kernel_timing
                    and not zero1 and not split_table and comm is None)
         if live_ok:
             traffic_db, traffic_note = live_pmc_traffic()
@@ -775,7 +784,7 @@ def main():
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms, 3),
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
             "comm": comm_info,
-            "replicas_consistent": replicas,   # per-rank parameter checksums equal on every rank (None: one rank, nothing to compare)
+            "replicas_consistent": replicas,   # per-rank parameter checksums equal on every rank (None: one rank, nothing to compare, or no --full)
             "switches": _lib_switches(),     # RSYS_* switches that differ from the library's defaults ({} = the shipped path)
             "library": os.environ.get("RSYS_LIB_PATH") or "recommendersystem_amd/librsys_hip.so",
             "config": {"workload": f"{args.config}: train step fwd+bwd+{'allreduce+' if comm is not None else ''}clip+AdamW, D={cfg['embed_dim']} L={cfg['num_layers']} "
@@ -837,13 +846,13 @@ def main():
             for k, v in sorted(rep.items(), key=lambda kv: -kv[1]["ms"]):
                 tf = v["flops"] / (v["ms"] * 1e-3) / 1e12 if v["flops"] else 0.0
                 print(f"  {k:22s} {v['ms'] / n_rep:8.3f} ms/step  {v['count'] // n_rep:4d} launches/step  {tf:7.1f} TFLOP/s", file=sys.stderr)
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(cfg, 1, args.cpu_rows)
         # the numbers README / DESIGN quote for other configurations, under the same clock as `value`: short
         # resident-batch legs after the cfg-3 measurement; `value`, `config` and everything above describe cfg-3 in bf16 only
         default_run = (world == 1 and args.config == "cfg3" and args.dtype == "bf16" and rows == 64 and args.layers is None and not sharded
                        and not args.deterministic and not args.detail and not args.no_kernel_timing)
-        if default_run and not args.no_extra_legs:
+        if args.full and default_run and not args.no_extra_legs:
             model.close(); model = None
             legs = {}
             for key, cname, dt, warm, k, shard in (("cfg2_bf16", "cfg2", "bf16", 5, 20, None), ("cfg3_fp8", "cfg3", "fp8", 5, 20, None),

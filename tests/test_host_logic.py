@@ -157,7 +157,7 @@ def test_train_loop_checkpoints_and_stops(tmp_path):
 
 
 def test_committed_bench_line_follows_the_contract():
-    """The newest bench line under profiles/ (written by `python bench.py` on an MI355X) carries every field the driver's
+    """The newest bench line under profiles/ (written by `python bench.py --full` on an MI355X) carries every field the driver's
     contract names, and its numbers are consistent with each other."""
     import glob
     import json

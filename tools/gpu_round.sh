@@ -3,7 +3,7 @@
 # script stops at the first failing one (a GPU step that was killed must not be followed by another one).
 #
 #   tests[=<-k expression>]      pytest -m gpu (whole suite, or the tests the expression selects), ONE process
-#   bench[=<config>[,<dtype>]]   the driver's line (default flags) for cfg3, or `--config <config>` with 20 steps / 5 warm-up
+#   bench[=<config>[,<dtype>]]   the full line (bench.py --full) for cfg3, or `--config <config>` with 20 steps / 5 warm-up
 #   detail[=<config>[,<dtype>]]  per call-site table (bench.py --detail), 20 steps
 #   prof[=<config>]              rocprofv3 --kernel-trace --stats of the bench + the steady-state per-step table (tools/trace_steady.py)
 #   pmc[=<config>]               HBM bytes per launch: separate FETCH_SIZE / WRITE_SIZE passes + tools/pmc_traffic.py
@@ -39,7 +39,7 @@ for step in "$@"; do
       echo "pytest rc=$rc" >> $O/${T}_tests.log; tail -6 $O/${T}_tests.log | cut -c1-220 ;;
     bench)
       if [ -z "$arg" ]; then
-        timeout -k 10 900 python3 $R/bench.py > $O/${T}_bench_cfg3.json 2> $O/${T}_bench_cfg3.err; rc=$?
+        timeout -k 10 900 python3 $R/bench.py --full > $O/${T}_bench_cfg3.json 2> $O/${T}_bench_cfg3.err; rc=$?
       else
         timeout -k 10 600 python3 $R/bench.py $(cfgflags "$arg") --steps 20 --warmup 5 --no-cpu-baseline --no-train-loop > $O/${T}_bench_${c}.json 2> $O/${T}_bench_${c}.err; rc=$?
       fi
