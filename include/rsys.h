@@ -231,6 +231,67 @@ int32_t rsys_rank_request(rsys_model* m, int32_t medium, int32_t n_groups,
                           const float* retrieval_coef, const float* rating_coefs, float rating_mean, /* [1] or NULL, [2] or NULL */
                           const float* r_in,                                      /* [n_total] or NULL */
                           int32_t* ids_out, float* r_out);                        /* [n_total] each, or NULL */
+/* ---- Item-similarity LambdaRank model (Training/item_similarity/pairwise_ltr.py, --features transformer / content).
+ * A handle of its own, independent of rsys_model: an rsys_simmodel, passed as an opaque void*.  Trainable parameters by the reference's
+ * state-dict names: "encoder.1.weight" [E][F] (weight decay 0.1) and "logit_scale" (scalar, log(1/0.07) at creation, no decay); the frozen
+ * table f [V][F] ("transformer_embeddings.weight", F = 2048, or [transformer | content], F = 5120) goes through rsys_sim_features_set.
+ * embed(ids) = normalize(W dropout_p(f[ids])), normalize(y) = y / max(|y|, 1e-12); score x = <embed(source), embed(target)> exp(logit_scale).
+ * dtype RSYS_DTYPE_BF16 follows bf16 autocast: gathered features and W rounded to bf16, fp32 accumulation, the encoder output rounded to
+ * bf16, normalisation, dot and scale in fp32; the weight gradient takes dY rounded to bf16 and is accumulated in fp32.  Every call is
+ * bitwise reproducible (no float atomics in any sum a result depends on).  Calls on one handle are serialised by the caller. */
+/* LTRModel(config) (pairwise_ltr.py:124-141): V items, F feature width (a multiple of 64), E = embed_dim (a multiple of 64), dtype
+ * RSYS_DTYPE_FP32 or _BF16; 1 <= max_queries <= 4096 lists of 1 <= items_per_query <= 2048 slots per call; dropout in [0, 1) */
+int32_t rsys_sim_create(int64_t V, int32_t F, int32_t E, int32_t dtype, int32_t max_queries, int32_t items_per_query, float dropout,
+                        int32_t device, void** out);
+int32_t rsys_sim_destroy(void* h);
+/* state_dict access (load_pretrained_embeddings / load_state_dict): n must be the tensor's element count; unknown names are ARG errors */
+int32_t rsys_sim_param_get(void* h, const char* name, float* out, int64_t n);
+int32_t rsys_sim_param_set(void* h, const char* name, const float* in, int64_t n);
+int32_t rsys_sim_grad_get(void* h, const char* name, float* out, int64_t n);
+int32_t rsys_sim_zero_grad(void* h);   /* optimizer.zero_grad (train_epoch, pairwise_ltr.py:246) */
+/* the frozen feature table [V][F] f32 (pairwise_ltr.py:146-155); V and F must be the handle's (a wrong F is an ARG error) */
+int32_t rsys_sim_features_set(void* h, const float* features, int64_t V, int64_t F);
+/* the same from a transformer model on the same device, without a host round trip: the rows of medium `medium` of its fp32 item table
+ * (ItemEmbedding over all items, the table rsys_item_table returns; rebuilt first when stale).  The handle's V must be V_m and its F the
+ * model's embed_dim ("transformer_embeddings.weight" of pairwise_ltr.py:146-155); replicated table only.  Synchronous. */
+int32_t rsys_sim_features_from_model(void* h, rsys_model* m, int32_t medium);
+/* model(batch) + loss.backward() (process_batch + lambdarank_loss, pairwise_ltr.py:175-190, 244-252): n_q lists of n slots, source[n_q],
+ * target[n_q][n], relevance[n_q][n] and weight[n_q] (= sqrt(popularity)) as f32 (the reference holds them in fp64: relevances that differ
+ * only beyond fp32 precision compare equal here).  order = 1-based rank of x descending, ties by slot; the loss is
+ * sum_q w_q sum_{i,j: y_i > y_j} -logsigmoid(x_i - x_j) |(D_i - D_j)(y_i - y_j)| / sum_q w_q with D = 1 / log2(1 + order); the ranks
+ * carry no gradient.  Training (evaluate == 0): every slot embeds its own copy of the source, each gathered row with its own dropout
+ * mask (Philox keyed on (seed, step, row, column), launch_dropout's stream), and the gradient is ACCUMULATED.  evaluate != 0: no
+ * dropout, no gradient.  *loss_out (may be NULL) = the batch loss.  Synchronous.  ARG errors: ids outside [0, V), n_q or n out of
+ * range, non-finite or negative weights, a zero weight sum, features not set. */
+int32_t rsys_sim_forward_backward(void* h, int32_t n_q, int32_t n, const int32_t* source, const int32_t* target, const float* relevance,
+                                  const float* weight, int32_t evaluate, uint64_t seed, uint64_t step, float* loss_out);
+/* LTRModel.ndcg in eval mode (pairwise_ltr.py:192-208): per list DCG = sum_r y_(r) / log2(r + 1) over the slots sorted by x descending
+ * (ties by slot), IDCG the same over y sorted descending; out[0] = sum_q w_q nDCG_q, out[1] = sum_q w_q (fp64, query order) */
+int32_t rsys_sim_ndcg(void* h, int32_t n_q, int32_t n, const int32_t* source, const int32_t* target, const float* relevance,
+                      const float* weight, double out[2]);
+/* clip_grad_norm_(clip) + GradScaler.step(AdamW) + zero_grad (pairwise_ltr.py:253-256, 263-275): AdamW beta 0.9 / 0.999, eps 1e-8, weight
+ * decay 0.1 on encoder.1.weight and 0 on logit_scale, lr as given, the global-norm clip fused (clip <= 0: none).  A non-finite gradient
+ * norm skips the update: parameters, moments and the step count stay as they were.  *norm_out = the norm before clipping, *skipped_out =
+ * 1 when skipped (either may be NULL).  The gradient is cleared in both cases. */
+int32_t rsys_sim_adamw_step(void* h, float lr, float clip, float* norm_out, int32_t* skipped_out);
+int32_t rsys_sim_adamw_state_get(void* h, const char* name, float* exp_avg, float* exp_avg_sq, int64_t n, int32_t* step);
+/* generate_embeddings (pairwise_ltr.py:450-472): embed every id in fp32 in both dtypes; out [V][E] (may be NULL).  train_mode != 0
+ * applies dropout (the export train() takes right after train_epoch, the model still in train mode): row = id, RNG stream 0xffffffff.
+ * The result is held on the device as the export rsys_sim_hard_negatives scores against. */
+int32_t rsys_sim_embed_all(void* h, int32_t train_mode, uint64_t seed, float* out);
+/* sets the held export [V][E] f32 directly (the reference's output.embeddings file) */
+int32_t rsys_sim_export_set(void* h, const float* emb);
+/* pairs.{m}.h5 "testmask" as bit rows: bits[V][ceil(V / 32)], bit (j & 31) of word j >> 5 of row i = testmask[i, j]; NULL clears */
+int32_t rsys_sim_testmask_set(void* h, const int32_t* bits);
+/* load_hard_negatives (pairwise_ltr.py:56-82) for n_src sources: w = bf16(bf16(E[i]) . bf16(E)^T) over the held export (fp32
+ * accumulation, the output rounded to bf16); -inf for the source itself, for testmask[i, :] (split 0, training) or ~testmask[i, :]
+ * (split 1, test), and for the source's positives pos_ids[pos_offsets[s] .. pos_offsets[s + 1]) (CSR over sources, or both NULL).
+ * ids_out[s][n] = np.argsort(w, kind="stable")[-n:]: the n best ids in ascending (score, id) order, so a tie keeps the larger id and
+ * lists tied ids ascending; when fewer than n ids are admissible, the admissible ones come last, preceded by the largest inadmissible
+ * ids in ascending order.  1 <= n <= min(items_per_query, V).  ARG errors: ids out of range, malformed offsets, no testmask or export. */
+int32_t rsys_sim_hard_negatives(void* h, int32_t split, int32_t n_src, const int32_t* sources, const int64_t* pos_offsets,
+                                const int32_t* pos_ids, int32_t n, int32_t* ids_out);
+
 /* on != 0: every float sum of the training step gets a fixed order (split-K partial tiles summed in split order, reductions through
  * per-workgroup partials instead of float atomics), so a step -- losses, gradients, updated parameters -- is bitwise reproducible
  * from run to run; costs a few percent of the step.  Replicated or row-sharded table, full or sampled soft-max.  (The reference's CUDA path is not reproducible:

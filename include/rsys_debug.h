@@ -84,6 +84,10 @@ int32_t rsys_rank_gram_get(rsys_model* m, int32_t medium, int32_t n_groups, cons
  * flags); pen[4] (host) = (decay, mmr, same_series, related); picks [min(partialk, n)] = the position chosen per round; 1 <= n <= 1024 */
 int32_t rsys_op_rerank(int32_t n, int32_t partialk, const float* pen, const float* r, const float* gram, const int32_t* ss_bits,
                        const int32_t* related_bits, int32_t* picks);
+/* the last rsys_sim_forward_backward / rsys_sim_ndcg call of an item-similarity handle (host arrays): "ranks" int32 [n_q][n] (1-based
+ * order of each slot), "scores" f32 [n_q][n] (x), "dldx" f32 [n_q][n] (d batch loss / dx), "dropout_mask" uint8 [rows][F] (1 = kept, the
+ * mask of every gathered row: rows = 2 n_q n in training, [source copies | targets], slot-major; all ones without dropout) */
+int32_t rsys_sim_debug_get(void* h, const char* name, void* out, int64_t n);
 /* embedding-gradient scatter of the backward (nn.Embedding backward, model.py:21) on caller-provided device buffers:
  * gE[id'] += sum over tokens n of gx0[n*ldx .. +D) with id' = m_matchedid[n] (-1 -> row V); matchedid = the raw ids the
  * token index is built from (m_matchedid differs from it only where it is -1).  One writer per table row, fixed summation

@@ -382,6 +382,74 @@ function timing_report(m::Model)
     unsafe_string(pointer(buf))
 end
 
+# Item-similarity LambdaRank model (Training/item_similarity/pairwise_ltr.py; DESIGN.md §4p): its own handle.  Arrays are 0-based ids,
+# Julia column-major: features F x V, targets / relevance n x n_q, the export E x V.
+mutable struct SimModel
+    h::Ptr{Cvoid}
+end
+function SimModel(V::Integer, F::Integer, E::Integer; dtype = DTYPE_BF16, max_queries = 128, items_per_query = 2048, dropout = 0.1f0,
+                  device = 0)
+    r = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:rsys_sim_create, LIB), Int32, (Int64, Int32, Int32, Int32, Int32, Int32, Float32, Int32, Ref{Ptr{Cvoid}}),
+                V, F, E, dtype, max_queries, items_per_query, dropout, device, r))
+    s = SimModel(r[])
+    finalizer(x -> ccall((:rsys_sim_destroy, LIB), Int32, (Ptr{Cvoid},), x.h), s)
+    s
+end
+sim_param_get(s::SimModel, name::AbstractString, out::Array{Float32}) =
+    check(ccall((:rsys_sim_param_get, LIB), Int32, (Ptr{Cvoid}, Cstring, Ptr{Float32}, Int64), s.h, name, out, length(out)))
+sim_param_set!(s::SimModel, name::AbstractString, x::Array{Float32}) =
+    check(ccall((:rsys_sim_param_set, LIB), Int32, (Ptr{Cvoid}, Cstring, Ptr{Float32}, Int64), s.h, name, x, length(x)))
+sim_grad_get(s::SimModel, name::AbstractString, out::Array{Float32}) =
+    check(ccall((:rsys_sim_grad_get, LIB), Int32, (Ptr{Cvoid}, Cstring, Ptr{Float32}, Int64), s.h, name, out, length(out)))
+sim_zero_grad!(s::SimModel) = check(ccall((:rsys_sim_zero_grad, LIB), Int32, (Ptr{Cvoid},), s.h))
+sim_features_set!(s::SimModel, f::Matrix{Float32}) =
+    check(ccall((:rsys_sim_features_set, LIB), Int32, (Ptr{Cvoid}, Ptr{Float32}, Int64, Int64), s.h, f, size(f, 2), size(f, 1)))
+# the rows of `medium` of a transformer model's item table, copied on the device (same device as the handle)
+sim_features_from_model!(s::SimModel, m::Model, medium::Integer) =
+    check(ccall((:rsys_sim_features_from_model, LIB), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Int32), s.h, m.h, medium))
+function sim_forward_backward!(s::SimModel, source, target::Matrix{Int32}, relevance::Matrix{Float32}, weight; evaluate = false,
+                               seed = 0, step = 0)
+    src = Vector{Int32}(source); w = Vector{Float32}(weight); loss = Ref{Float32}(0)
+    GC.@preserve src target relevance w check(ccall((:rsys_sim_forward_backward, LIB), Int32,
+        (Ptr{Cvoid}, Int32, Int32, Ptr{Int32}, Ptr{Int32}, Ptr{Float32}, Ptr{Float32}, Int32, UInt64, UInt64, Ref{Float32}),
+        s.h, length(src), size(target, 1), src, target, relevance, w, evaluate, seed, step, loss))
+    loss[]
+end
+function sim_ndcg(s::SimModel, source, target::Matrix{Int32}, relevance::Matrix{Float32}, weight)
+    src = Vector{Int32}(source); w = Vector{Float32}(weight); out = zeros(Float64, 2)
+    GC.@preserve src target relevance w out check(ccall((:rsys_sim_ndcg, LIB), Int32,
+        (Ptr{Cvoid}, Int32, Int32, Ptr{Int32}, Ptr{Int32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float64}),
+        s.h, length(src), size(target, 1), src, target, relevance, w, out))
+    out[1], out[2]
+end
+function sim_adamw_step!(s::SimModel; lr = 3f-4, clip = 1f0)
+    norm = Ref{Float32}(0); skipped = Ref{Int32}(0)
+    check(ccall((:rsys_sim_adamw_step, LIB), Int32, (Ptr{Cvoid}, Float32, Float32, Ref{Float32}, Ref{Int32}), s.h, lr, clip, norm, skipped))
+    norm[], skipped[] != 0
+end
+function sim_adamw_state_get(s::SimModel, name::AbstractString, n::Integer)
+    m = zeros(Float32, n); v = zeros(Float32, n); step = Ref{Int32}(0)
+    check(ccall((:rsys_sim_adamw_state_get, LIB), Int32, (Ptr{Cvoid}, Cstring, Ptr{Float32}, Ptr{Float32}, Int64, Ref{Int32}),
+                s.h, name, m, v, n, step))
+    m, v, step[]
+end
+sim_embed_all!(s::SimModel, out::Matrix{Float32}; train_mode = false, seed = 0) =
+    check(ccall((:rsys_sim_embed_all, LIB), Int32, (Ptr{Cvoid}, Int32, UInt64, Ptr{Float32}), s.h, train_mode, seed, out))
+sim_export_set!(s::SimModel, emb::Matrix{Float32}) = check(ccall((:rsys_sim_export_set, LIB), Int32, (Ptr{Cvoid}, Ptr{Float32}), s.h, emb))
+# bits: ceil(V / 32) x V Int32 words (column i = row i of the testmask)
+sim_testmask_set!(s::SimModel, bits::Matrix{Int32}) = check(ccall((:rsys_sim_testmask_set, LIB), Int32, (Ptr{Cvoid}, Ptr{Int32}), s.h, bits))
+# positives: one Vector{Int32} of 0-based ids per source; returns n x n_src ids in ascending score order
+function sim_hard_negatives(s::SimModel, split::Integer, sources, positives, n::Integer)
+    src = Vector{Int32}(sources)
+    off = Int64[0; cumsum(Int64[length(p) for p in positives])]
+    pid = Int32[reduce(vcat, positives; init = Int32[])...]
+    out = Matrix{Int32}(undef, n, length(src))
+    GC.@preserve src off pid out check(ccall((:rsys_sim_hard_negatives, LIB), Int32,
+        (Ptr{Cvoid}, Int32, Int32, Ptr{Int32}, Ptr{Int64}, Ptr{Int32}, Int32, Ptr{Int32}), s.h, split, length(src), src, off, pid, n, out))
+    out
+end
+
 # One optimizer step of train_epoch (transformer.py:256-276) with grad_accum = 1
 function train_step!(m::Model, o::Optimizer, c::Union{Comm,Nothing}, task_w, lr_factor, seed, step)
     c === nothing || begin_grad_sync!(m, c)

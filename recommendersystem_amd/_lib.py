@@ -82,6 +82,24 @@ _SIGS = [
     ("rsys_rank_related_set", C.c_int32, [_P, C.c_int32, C.c_int64, _P, _P, _P]),
     ("rsys_rank_request", C.c_int32, [_P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, C.c_int64, _P, _P, C.c_int64, _P, _P, _P, _P, _P, _P,
                                       C.c_float, _P, _P, _P]),
+    ("rsys_sim_create", C.c_int32, [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.POINTER(_P)]),
+    ("rsys_sim_destroy", C.c_int32, [_P]),
+    ("rsys_sim_param_get", C.c_int32, [_P, C.c_char_p, _P, C.c_int64]),
+    ("rsys_sim_param_set", C.c_int32, [_P, C.c_char_p, _P, C.c_int64]),
+    ("rsys_sim_grad_get", C.c_int32, [_P, C.c_char_p, _P, C.c_int64]),
+    ("rsys_sim_zero_grad", C.c_int32, [_P]),
+    ("rsys_sim_features_set", C.c_int32, [_P, _P, C.c_int64, C.c_int64]),
+    ("rsys_sim_features_from_model", C.c_int32, [_P, _P, C.c_int32]),
+    ("rsys_sim_forward_backward", C.c_int32, [_P, C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_int32, C.c_uint64, C.c_uint64,
+                                              C.POINTER(C.c_float)]),
+    ("rsys_sim_ndcg", C.c_int32, [_P, C.c_int32, C.c_int32, _P, _P, _P, _P, C.POINTER(C.c_double * 2)]),
+    ("rsys_sim_adamw_step", C.c_int32, [_P, C.c_float, C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_int32)]),
+    ("rsys_sim_adamw_state_get", C.c_int32, [_P, C.c_char_p, _P, _P, C.c_int64, C.POINTER(C.c_int32)]),
+    ("rsys_sim_embed_all", C.c_int32, [_P, C.c_int32, C.c_uint64, _P]),
+    ("rsys_sim_export_set", C.c_int32, [_P, _P]),
+    ("rsys_sim_testmask_set", C.c_int32, [_P, _P]),
+    ("rsys_sim_hard_negatives", C.c_int32, [_P, C.c_int32, C.c_int32, _P, _P, _P, C.c_int32, _P]),
+    ("rsys_sim_debug_get", C.c_int32, [_P, C.c_char_p, _P, C.c_int64]),
     ("rsys_model_set_deterministic", C.c_int32, [_P, C.c_int32]),
     ("rsys_infer", C.c_int32, [_P, C.c_int32, _P, C.c_int64]),
     ("rsys_infer_select", C.c_int32, [_P, C.c_int32, _P, C.c_int64, _P, C.c_int64]),

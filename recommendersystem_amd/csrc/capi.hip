@@ -159,6 +159,13 @@ int32_t rsys_retrieve_topk(rsys_model* h, int32_t medium, const float* queries, 
   return model_retrieve_topk(h->m, medium, queries, n_queries, group, n_groups, prior, excl_offsets, excl_ids, k, ids_out, scores_out,
                              counts_out);
 }
+int32_t rsys_sim_features_from_model(void* sim, rsys_model* h, int32_t medium) {
+  CHECK_HANDLE(h);
+  if (sim == nullptr) { set_error("null handle"); return RSYS_ERR_ARG; }
+  const float* rows = nullptr; int64_t Vm = 0; int D = 0;
+  RC(model_item_table_device(h->m, medium, &rows, &Vm, &D));
+  return sim_features_from_device(sim, rows, Vm, D, h->m->device);
+}
 int32_t rsys_retrieve_target_rank(rsys_model* h, int32_t medium, const float* queries, int64_t n_queries, const int32_t* targets,
                                   const int64_t* excl_offsets, const int32_t* excl_ids, int32_t* rank_out, float* logp_out) {
   CHECK_HANDLE(h);

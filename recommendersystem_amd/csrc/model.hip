@@ -907,6 +907,24 @@ static int item_table_t(Model* m, float* out, int64_t n) {
   HIP_CHECK(hipMemcpy(out, m->F32, (size_t)n * 4, hipMemcpyDeviceToHost));
   return RSYS_OK;
 }
+// the device-resident fp32 item table rows of `medium` (rebuilt first when stale), valid until the model's parameters change
+template <typename T>
+static int item_table_dev_t(Model* m) {
+  if (m->table_dirty) { RC(table_forward<T>(m)); m->table_dirty = false; }
+  HIP_CHECK(hipStreamSynchronize(m->stream));
+  return RSYS_OK;
+}
+int model_item_table_device(Model* m, int medium, const float** rows, int64_t* Vm, int* D) {
+  ARG_CHECK(!m->sharded, "item table: a model with a replicated table");
+  ARG_CHECK(medium == 0 || medium == 1, "item table: medium must be 0 or 1");
+  HIP_CHECK(hipSetDevice(m->device));
+  RC(m->bf16_mode ? item_table_dev_t<bf16>(m) : item_table_dev_t<float>(m));
+  *rows = m->F32 + (int64_t)(medium == 0 ? 0 : m->V0) * m->D;
+  *Vm = medium == 0 ? m->V0 : m->V1;
+  *D = m->D;
+  return RSYS_OK;
+}
+
 int model_item_table(Model* m, float* out, int64_t n) {
   HIP_CHECK(hipSetDevice(m->device));
   return m->bf16_mode ? item_table_t<bf16>(m, out, n) : item_table_t<float>(m, out, n);

@@ -300,6 +300,10 @@ int model_batch_upload(Model* m, const rsys_batch* b);
 int model_forward_backward(Model* m, int evaluate, const float task_w[4], float grad_scale, uint64_t seed, uint64_t step);
 int model_infer(Model* m, int task, const int32_t* token_index, int64_t n_tokens, float* out, int64_t n);   // token_index == nullptr: every token
 int model_item_table(Model* m, float* out, int64_t n);
+// the fp32 item table rows [V_m][D] of `medium` on the model's device (rsys_sim_features_from_model); the model's stream is idle on return
+int model_item_table_device(Model* m, int medium, const float** rows, int64_t* Vm, int* D);
+// similarity.hip: frozen features of an item-similarity handle from device rows [V][F] on `device`
+int sim_features_from_device(void* h, const float* rows, int64_t V, int64_t F, int device);
 int model_materialise_trunk_output(Model* m);   // dense trunk output of the resident forward in m->out (a training pass computes it at the selected tokens only)
 int model_finalize_grads(Model* m);
 bool model_finalize_splittable(const Model* m);
@@ -346,6 +350,10 @@ void rank_free(Model* m);
 int op_rerank(int32_t n, int32_t partialk, const float* pen, const float* r, const float* gram, const int32_t* ss_bits,
               const int32_t* related_bits, int32_t* picks);
 int op_topk(const float* scores, int64_t ld, int32_t rows, int32_t V, int32_t k, int32_t* ids, float* vals, int32_t* counts);
+// the selection of rsys_op_topk on device scores [rows][ld], stream-ordered, in a caller's device workspace of topk_rows_ws_bytes bytes
+// (1 <= k <= min(V, 8192)); ids / vals / counts are device arrays
+size_t topk_rows_ws_bytes(int rows, int V, int k);
+int topk_rows(const float* scores, long long ld, int rows, int V, int k, void* ws, int* ids, float* vals, int* counts, hipStream_t s);
 // retrieve_eval.hip: the rank and log-probability of one target item per query (rsys_retrieve_target_rank) and the count alone
 int model_retrieve_target_rank(Model* m, int medium, const float* queries, int64_t nq, const int32_t* targets, const int64_t* excl_off,
                                const int32_t* excl_ids, int32_t* rank_out, float* logp_out);

@@ -534,33 +534,41 @@ int model_retrieve_run(Model* m, int medium, const float* queries, int64_t nq, c
                       : retrieve_t<float>(m, medium, queries, nq, group, ng, nullptr, nullptr, nullptr, &init, k, ids_out, scores_out, counts_out);
 }
 
+static void topk_rows_layout(Carve& c, int rows, int V, int k, unsigned** keys, SelBufs* sb) {
+  const int nb = (V + RT_ITEMS - 1) / RT_ITEMS;
+  *keys = c.take<unsigned>((size_t)rows * V);
+  sb->hist = c.take<unsigned>((size_t)rows * 256);
+  sb->st = c.take<SelState>(rows);
+  sb->cnt = c.take<int2>((size_t)rows * nb);
+  sb->cand = c.take<unsigned long long>((size_t)rows * k);
+  sb->ldc = k;
+}
+
+size_t topk_rows_ws_bytes(int rows, int V, int k) {
+  Carve probe{nullptr};
+  unsigned* keys; SelBufs sb;
+  topk_rows_layout(probe, rows, V, k, &keys, &sb);
+  return probe.off;
+}
+
+int topk_rows(const float* scores, long long ld, int rows, int V, int k, void* ws, int* ids, float* vals, int* counts, hipStream_t s) {
+  const int nb = (V + RT_ITEMS - 1) / RT_ITEMS;
+  Carve c{(char*)ws};
+  unsigned* keys; SelBufs sb;
+  topk_rows_layout(c, rows, V, k, &keys, &sb);
+  HIP_CHECK(hipMemsetAsync(sb.hist, 0, (size_t)rows * 256 * 4, s));
+  combine_kernel<true><<<dim3(nb, rows), RT_THREADS, 0, s>>>(scores, ld, (float*)keys, V, nullptr, 0, nullptr, nullptr, nullptr, 0, V, sb.hist);
+  RT_LAUNCH_CHECK();
+  return topk_select(keys, V, rows, V, k, sb, ids, vals, counts, s);
+}
+
 int op_topk(const float* scores, int64_t ld, int32_t rows, int32_t V, int32_t k, int32_t* ids, float* vals, int32_t* counts) {
   ARG_CHECK(scores && ids && vals && counts, "rsys_op_topk: null buffer");
   ARG_CHECK(rows >= 1 && V >= 1 && ld >= V, "rsys_op_topk: rows >= 1, V >= 1, ld >= V");
   ARG_CHECK(k >= 1 && k <= std::min(V, RT_MAXK), "rsys_op_topk: 1 <= k <= min(V, 8192)");
-  const int nb = (V + RT_ITEMS - 1) / RT_ITEMS;
-  Carve probe{nullptr};
-  auto layout = [&](Carve& c, unsigned** keys, SelBufs* sb) {
-    *keys = c.take<unsigned>((size_t)rows * V);
-    sb->hist = c.take<unsigned>((size_t)rows * 256);
-    sb->st = c.take<SelState>(rows);
-    sb->cnt = c.take<int2>((size_t)rows * nb);
-    sb->cand = c.take<unsigned long long>((size_t)rows * k);
-    sb->ldc = k;
-  };
-  unsigned* keys; SelBufs sb;
-  layout(probe, &keys, &sb);
   void* buf = nullptr;
-  HIP_CHECK(hipMalloc(&buf, probe.off));
-  Carve c{(char*)buf};
-  layout(c, &keys, &sb);
-  int rc = RSYS_OK;
-  if (hipMemset(sb.hist, 0, (size_t)rows * 256 * 4) != hipSuccess) rc = RSYS_ERR_HIP;
-  if (rc == RSYS_OK) {
-    combine_kernel<true><<<dim3(nb, rows), RT_THREADS>>>(scores, ld, (float*)keys, V, nullptr, 0, nullptr, nullptr, nullptr, 0, V, sb.hist);
-    if (hipGetLastError() != hipSuccess) { set_error("rsys_op_topk: launch failed"); rc = RSYS_ERR_HIP; }
-  }
-  if (rc == RSYS_OK) rc = topk_select(keys, V, rows, V, k, sb, ids, vals, counts, nullptr);
+  HIP_CHECK(hipMalloc(&buf, topk_rows_ws_bytes(rows, V, k)));
+  int rc = topk_rows(scores, ld, rows, V, k, buf, ids, vals, counts, nullptr);
   const hipError_t e = hipDeviceSynchronize();
   hipFree(buf);
   if (rc == RSYS_OK && e != hipSuccess) { set_error(std::string("rsys_op_topk: ") + hipGetErrorString(e)); rc = RSYS_ERR_HIP; }
