@@ -292,6 +292,31 @@ int32_t rsys_sim_testmask_set(void* h, const int32_t* bits);
 int32_t rsys_sim_hard_negatives(void* h, int32_t split, int32_t n_src, const int32_t* sources, const int64_t* pos_offsets,
                                 const int32_t* pos_ids, int32_t n, int32_t* ids_out);
 
+/* ---- Watch-order counts (Training/media_relations.jl get_watch_order, :174-197).  A handle of its own, passed as an opaque
+ * void*: one row band [row0, row1) of the V x V int32 matrix W, W[a][b] = the number of users whose projected history has a before b
+ * (the reference's watch_order[a+1, b+1]).  Counts are exact integer adds, so every result is bitwise reproducible and independent of
+ * how the users are split into add calls.  A full band (0, V) is the normal case; a narrower one caps device memory. */
+/* zeros(Int32, V, V) (:175) restricted to rows [row0, row1): 0 <= row0 <= row1 <= V.  RSYS_ERR_STATE when the band does not fit in free
+ * device memory (the message names the bytes asked for) */
+int32_t rsys_watch_order_create(int64_t V, int64_t row0, int64_t row1, int32_t device, void** out);
+int32_t rsys_watch_order_destroy(void* h);
+/* the loop of :184-193 over n_users projected histories (project_earliest, :156-172): items[offsets[u] .. offsets[u + 1]) in watch order,
+ * distinct per user, in [0, V); adds 1 to W[h_i][h_j] for every i < j with h_i in the band.  offsets [n_users + 1] start at 0 and do not
+ * decrease.  ARG errors (nothing is added): malformed offsets, an item outside [0, V), a user count past 2^31 - 1.  Synchronous. */
+int32_t rsys_watch_order_add(void* h, int64_t n_users, const int64_t* offsets, const int32_t* items);
+/* users with >= 1 item added so far (get_watch_order's num_users, :186-188) */
+int32_t rsys_watch_order_users(void* h, int64_t* out);
+/* dense rows [row0, row0 + n_rows) of W, within the band: out[n_rows][V] */
+int32_t rsys_watch_order_rows_get(void* h, int64_t row0, int64_t n_rows, int32_t* out);
+/* out[k] = W[a[k]][b[k]] (is_watched_before, :199-202; pairwise_dataset.jl:126-135); a[k] in the band, b[k] in [0, V), else ARG */
+int32_t rsys_watch_order_gather(void* h, int64_t n, const int32_t* a, const int32_t* b, int32_t* out);
+/* the band's non-zeros as CSR (rows band-local, columns ascending): indptr [row1 - row0 + 1] int64, indices / values [nnz].  *nnz is
+ * always written; the arrays only when none is NULL and cap >= nnz (call once with NULL to size them).  The same matrix gives the same
+ * bytes on every call. */
+int32_t rsys_watch_order_csr(void* h, int64_t* indptr, int32_t* indices, int32_t* values, int64_t cap, int64_t* nnz);
+/* zeros the band and the user count */
+int32_t rsys_watch_order_clear(void* h);
+
 /* on != 0: every float sum of the training step gets a fixed order (split-K partial tiles summed in split order, reductions through
  * per-workgroup partials instead of float atomics), so a step -- losses, gradients, updated parameters -- is bitwise reproducible
  * from run to run; costs a few percent of the step.  Replicated or row-sharded table, full or sampled soft-max.  (The reference's CUDA path is not reproducible:

@@ -450,6 +450,55 @@ function sim_hard_negatives(s::SimModel, split::Integer, sources, positives, n::
     out
 end
 
+# Watch-order counts (Training/media_relations.jl get_watch_order; DESIGN.md §4q): its own handle over the row band [row0, row1) of W.
+# Ids are 0-based; W[a][b] = users who watched a before b.
+mutable struct WatchOrder
+    h::Ptr{Cvoid}
+end
+function WatchOrder(V::Integer; row0 = 0, row1 = V, device = 0)
+    r = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:rsys_watch_order_create, LIB), Int32, (Int64, Int64, Int64, Int32, Ref{Ptr{Cvoid}}), V, row0, row1, device, r))
+    w = WatchOrder(r[])
+    finalizer(x -> ccall((:rsys_watch_order_destroy, LIB), Int32, (Ptr{Cvoid},), x.h), w)
+    w
+end
+# histories: one Vector{Int32} of 0-based ids per user (project_earliest's output)
+function watch_order_add!(w::WatchOrder, histories)
+    off = Int64[0; cumsum(Int64[length(h) for h in histories])]
+    items = Int32[reduce(vcat, histories; init = Int32[])...]
+    GC.@preserve off items check(ccall((:rsys_watch_order_add, LIB), Int32, (Ptr{Cvoid}, Int64, Ptr{Int64}, Ptr{Int32}),
+                                       w.h, length(histories), off, items))
+end
+function watch_order_users(w::WatchOrder)
+    n = Ref{Int64}(0)
+    check(ccall((:rsys_watch_order_users, LIB), Int32, (Ptr{Cvoid}, Ref{Int64}), w.h, n))
+    n[]
+end
+# rows [row0, row0 + n_rows) as a V x n_rows matrix (column k = row row0 + k)
+function watch_order_rows(w::WatchOrder, V::Integer, row0::Integer, n_rows::Integer)
+    out = Matrix{Int32}(undef, V, n_rows)
+    check(ccall((:rsys_watch_order_rows_get, LIB), Int32, (Ptr{Cvoid}, Int64, Int64, Ptr{Int32}), w.h, row0, n_rows, out))
+    out
+end
+function watch_order_gather(w::WatchOrder, a::Vector{Int32}, b::Vector{Int32})
+    out = Vector{Int32}(undef, length(a))
+    check(ccall((:rsys_watch_order_gather, LIB), Int32, (Ptr{Cvoid}, Int64, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}), w.h, length(a), a, b, out))
+    out
+end
+# (indptr, indices, values) of the band, 0-based CSR
+function watch_order_csr(w::WatchOrder, n_rows::Integer)
+    nnz = Ref{Int64}(0)
+    check(ccall((:rsys_watch_order_csr, LIB), Int32, (Ptr{Cvoid}, Ptr{Int64}, Ptr{Int32}, Ptr{Int32}, Int64, Ref{Int64}),
+                w.h, C_NULL, C_NULL, C_NULL, 0, nnz))
+    indptr = Vector{Int64}(undef, n_rows + 1)
+    indices = Vector{Int32}(undef, nnz[])
+    values = Vector{Int32}(undef, nnz[])
+    check(ccall((:rsys_watch_order_csr, LIB), Int32, (Ptr{Cvoid}, Ptr{Int64}, Ptr{Int32}, Ptr{Int32}, Int64, Ref{Int64}),
+                w.h, indptr, indices, values, nnz[], nnz))
+    indptr, indices, values
+end
+watch_order_clear!(w::WatchOrder) = check(ccall((:rsys_watch_order_clear, LIB), Int32, (Ptr{Cvoid},), w.h))
+
 # One optimizer step of train_epoch (transformer.py:256-276) with grad_accum = 1
 function train_step!(m::Model, o::Optimizer, c::Union{Comm,Nothing}, task_w, lr_factor, seed, step)
     c === nothing || begin_grad_sync!(m, c)

@@ -100,6 +100,14 @@ _SIGS = [
     ("rsys_sim_testmask_set", C.c_int32, [_P, _P]),
     ("rsys_sim_hard_negatives", C.c_int32, [_P, C.c_int32, C.c_int32, _P, _P, _P, C.c_int32, _P]),
     ("rsys_sim_debug_get", C.c_int32, [_P, C.c_char_p, _P, C.c_int64]),
+    ("rsys_watch_order_create", C.c_int32, [C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.POINTER(_P)]),
+    ("rsys_watch_order_destroy", C.c_int32, [_P]),
+    ("rsys_watch_order_add", C.c_int32, [_P, C.c_int64, _P, _P]),
+    ("rsys_watch_order_users", C.c_int32, [_P, C.POINTER(C.c_int64)]),
+    ("rsys_watch_order_rows_get", C.c_int32, [_P, C.c_int64, C.c_int64, _P]),
+    ("rsys_watch_order_gather", C.c_int32, [_P, C.c_int64, _P, _P, _P]),
+    ("rsys_watch_order_csr", C.c_int32, [_P, _P, _P, _P, C.c_int64, C.POINTER(C.c_int64)]),
+    ("rsys_watch_order_clear", C.c_int32, [_P]),
     ("rsys_model_set_deterministic", C.c_int32, [_P, C.c_int32]),
     ("rsys_infer", C.c_int32, [_P, C.c_int32, _P, C.c_int64]),
     ("rsys_infer_select", C.c_int32, [_P, C.c_int32, _P, C.c_int64, _P, C.c_int64]),
