@@ -291,6 +291,21 @@ int32_t rsys_sim_testmask_set(void* h, const int32_t* bits);
  * ids in ascending order.  1 <= n <= min(items_per_query, V).  ARG errors: ids out of range, malformed offsets, no testmask or export. */
 int32_t rsys_sim_hard_negatives(void* h, int32_t split, int32_t n_src, const int32_t* sources, const int64_t* pos_offsets,
                                 const int32_t* pos_ids, int32_t n, int32_t* ids_out);
+/* The ranks pairwise_metrics.jl sorts the whole catalogue for (ndcg_at_k / recall_at_k, :72-123, over M = E' * E .* testmask, :172-174):
+ * for n_src sources and their targets tgt_ids[tgt_offsets[s] .. tgt_offsets[s + 1]) (CSR over sources, tgt_offsets[0] == 0), ranks_out[j]
+ * = the 1-based position of target j among ALL items i != source of the medium.  Over the held fp32 export (rsys_sim_embed_all /
+ * rsys_sim_export_set) and the held test mask (rsys_sim_testmask_set):
+ *   g[s][i] = the fp32 dot product of export rows s and i, fp32 accumulation in a fixed order (no bf16 anywhere);
+ *   v[s][i] = g[s][i] where testmask[s][i] is set, else g[s][i] * 0.0f as an IEEE product (a masked zero keeps the sign of g, a
+ *             non-finite g becomes NaN);
+ *   order   = sortperm(v, rev = true): descending under isless (-inf < ... < -0.0 < +0.0 < ... < +inf < NaN, all NaNs equal), equal
+ *             values by ascending id;
+ *   rank(t) = 1 + #{i != s : v_i sorts above v_t} + #{i != s, i < t : v_i equal to v_t} for t != s, and 0 for t == s (not a candidate).
+ * Sources may repeat, and so may the targets of a source (each gets its rank).  Any n_src >= 1 (chunks of 256 sources; the workspace
+ * grows on demand and is freed with the handle).  Synchronous, bitwise reproducible, changes no model state.  ARG errors (nothing is
+ * written): no export, no test mask, ids outside [0, V), malformed offsets, more than 2^31 - 1 targets. */
+int32_t rsys_sim_pair_ranks(void* h, int32_t n_src, const int32_t* sources, const int64_t* tgt_offsets, const int32_t* tgt_ids,
+                            int32_t* ranks_out);
 
 /* ---- Watch-order counts (Training/media_relations.jl get_watch_order, :174-197).  A handle of its own, passed as an opaque
  * void*: one row band [row0, row1) of the V x V int32 matrix W, W[a][b] = the number of users whose projected history has a before b

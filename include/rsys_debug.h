@@ -75,6 +75,15 @@ int32_t rsys_op_topk(const float* scores, int64_t ld, int32_t rows, int32_t V, i
  * an inadmissible entry, -0.0 == +0.0) rank_out[r] = 1 + #{admissible i : s_i > s_t} + #{admissible i < t : s_i == s_t} with
  * t = targets[r] in [0, V), or 0 when s_t is NaN or -inf; 1 <= rows <= 65535 */
 int32_t rsys_op_target_rank(const float* scores, int64_t ld, int32_t rows, int32_t V, const int32_t* targets, int32_t* rank_out);
+/* the count of rsys_sim_pair_ranks alone: scores [rows][ld >= V] is a DEVICE array of final (already masked) score rows; self [rows],
+ * tgt_offsets [rows + 1], tgt_ids and ranks_out [tgt_offsets[rows]] are host arrays.  Per row r with s = self[r] and every target t of its
+ * CSR slice: ranks_out = 1 + #{i != s : v_i sorts above v_t} + #{i != s, i < t : v_i equal to v_t} under isless (-inf < ... < -0.0 < +0.0
+ * < ... < +inf < NaN, all NaNs equal), 0 where t == s.  Columns >= V are never read.  1 <= rows <= 65535 */
+int32_t rsys_op_pair_ranks(const float* scores, int64_t ld, int32_t rows, int32_t V, const int32_t* self, const int64_t* tgt_offsets,
+                           const int32_t* tgt_ids, int32_t* ranks_out);
+/* the masked score rows rsys_sim_pair_ranks ranks: out[n_src][V] (host) = v[sources[s]][:], from the same row gather, GEMM and mask
+ * arithmetic (the mask is applied by a kernel of its own here, on load in the ranking) */
+int32_t rsys_sim_pair_scores(void* h, int32_t n_src, const int32_t* sources, float* out);
 /* rsys_rank_request's Gram matrices alone, as its loop reads them: out = per group in order, G_g [n_g][n_g] row-major (sum of n_g^2 floats),
  * computed by the same kernel from the model's item-similarity table of `medium`; host arrays */
 int32_t rsys_rank_gram_get(rsys_model* m, int32_t medium, int32_t n_groups, const int64_t* cand_offsets, const int32_t* cand_ids,

@@ -449,6 +449,17 @@ function sim_hard_negatives(s::SimModel, split::Integer, sources, positives, n::
         (Ptr{Cvoid}, Int32, Int32, Ptr{Int32}, Ptr{Int64}, Ptr{Int32}, Int32, Ptr{Int32}), s.h, split, length(src), src, off, pid, n, out))
     out
 end
+# pairwise_metrics.jl's ranking over the held export and testmask (DESIGN.md §4r): targets = one Vector of 0-based ids per source;
+# returns the concatenated 1-based ranks among all items != source in sortperm(rev = true) order (0: target == source) and the offsets
+function sim_pair_ranks(s::SimModel, sources, targets)
+    src = Vector{Int32}(sources)
+    off = Int64[0; cumsum(Int64[length(t) for t in targets])]
+    tid = Int32[reduce(vcat, targets; init = Int32[])...]
+    out = zeros(Int32, max(off[end], 1))
+    GC.@preserve src off tid out check(ccall((:rsys_sim_pair_ranks, LIB), Int32,
+        (Ptr{Cvoid}, Int32, Ptr{Int32}, Ptr{Int64}, Ptr{Int32}, Ptr{Int32}), s.h, length(src), src, off, tid, out))
+    out[1:off[end]], off
+end
 
 # Watch-order counts (Training/media_relations.jl get_watch_order; DESIGN.md §4q): its own handle over the row band [row0, row1) of W.
 # Ids are 0-based; W[a][b] = users who watched a before b.

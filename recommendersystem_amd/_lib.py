@@ -99,6 +99,8 @@ _SIGS = [
     ("rsys_sim_export_set", C.c_int32, [_P, _P]),
     ("rsys_sim_testmask_set", C.c_int32, [_P, _P]),
     ("rsys_sim_hard_negatives", C.c_int32, [_P, C.c_int32, C.c_int32, _P, _P, _P, C.c_int32, _P]),
+    ("rsys_sim_pair_ranks", C.c_int32, [_P, C.c_int32, _P, _P, _P, _P]),
+    ("rsys_sim_pair_scores", C.c_int32, [_P, C.c_int32, _P, _P]),
     ("rsys_sim_debug_get", C.c_int32, [_P, C.c_char_p, _P, C.c_int64]),
     ("rsys_watch_order_create", C.c_int32, [C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.POINTER(_P)]),
     ("rsys_watch_order_destroy", C.c_int32, [_P]),
@@ -162,6 +164,7 @@ _SIGS = [
     ("rsys_op_attention", C.c_int32, [C.c_int32] + [C.c_int32] * 5 + [_P] * 9),
     ("rsys_op_topk", C.c_int32, [_P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P]),
     ("rsys_op_target_rank", C.c_int32, [_P, C.c_int64, C.c_int32, C.c_int32, _P, _P]),
+    ("rsys_op_pair_ranks", C.c_int32, [_P, C.c_int64, C.c_int32, C.c_int32, _P, _P, _P, _P]),
     ("rsys_rank_gram_get", C.c_int32, [_P, C.c_int32, C.c_int32, _P, _P, _P, C.c_int64]),
     ("rsys_op_rerank", C.c_int32, [C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P]),
     ("rsys_op_embedding_scatter", C.c_int32, [_P, C.c_int64, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32]),

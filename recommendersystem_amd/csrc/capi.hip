@@ -867,6 +867,11 @@ int32_t rsys_op_target_rank(const float* scores, int64_t ld, int32_t rows, int32
   switches_parse();
   return op_target_rank(scores, ld, rows, V, targets, rank_out);
 }
+int32_t rsys_op_pair_ranks(const float* scores, int64_t ld, int32_t rows, int32_t V, const int32_t* self, const int64_t* tgt_offsets,
+                           const int32_t* tgt_ids, int32_t* ranks_out) {
+  switches_parse();
+  return op_pair_ranks(scores, ld, rows, V, self, tgt_offsets, tgt_ids, ranks_out);
+}
 int32_t rsys_op_rerank(int32_t n, int32_t partialk, const float* pen, const float* r, const float* gram, const int32_t* ss_bits,
                        const int32_t* related_bits, int32_t* picks) {
   switches_parse();

@@ -71,6 +71,15 @@ __device__ __forceinline__ unsigned score_key(float s) {
   return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 
+// total-order key of a float under Julia's `isless` (similarity_metrics.hip; the order rsys_rank_request documents for its argmax):
+// -inf < ... < -0.0 < +0.0 < ... < +inf < NaN, every NaN (either sign, any payload) the same largest key.  Unlike score_key nothing is
+// merged or dropped: the two zeros differ, -inf and NaN are ordinary values.  The smallest key, -inf's, is 0x007fffff, so 0 is free.
+__device__ __forceinline__ unsigned isless_key(float s) {
+  if (s != s) return 0xffffffffu;
+  const unsigned u = __float_as_uint(s);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

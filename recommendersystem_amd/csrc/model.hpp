@@ -359,6 +359,17 @@ int model_retrieve_target_rank(Model* m, int medium, const float* queries, int64
                                const int32_t* excl_ids, int32_t* rank_out, float* logp_out);
 void retrieve_eval_free(Model* m);
 int op_target_rank(const float* scores, int64_t ld, int32_t rows, int32_t V, const int32_t* targets, int32_t* rank_out);
+// similarity_metrics.hip: catalogue ranks of the targets of item-similarity test sources (rsys_sim_pair_ranks) over a handle's fp32
+// export [V][E] and test-mask bit rows, the masked score rows alone (rsys_sim_pair_scores) and the count alone (rsys_op_pair_ranks).
+// PairWs: one device buffer, grown on demand, owned by the caller
+struct PairWs { void* buf = nullptr; size_t bytes = 0; };
+void pair_ws_free(PairWs* ws);
+int pair_ranks_run(const float* exp32, int V, int E, const unsigned* tmask, long long tmw, int32_t n_src, const int32_t* sources,
+                   const int64_t* off, const int32_t* tids, int32_t* ranks_out, PairWs* ws, hipStream_t s);
+int pair_scores_run(const float* exp32, int V, int E, const unsigned* tmask, long long tmw, int32_t n_src, const int32_t* sources,
+                    float* out, PairWs* ws, hipStream_t s);
+int op_pair_ranks(const float* scores, int64_t ld, int32_t rows, int32_t V, const int32_t* self, const int64_t* off, const int32_t* tids,
+                  int32_t* ranks_out);
 int optimizer_step(Optimizer* o, float lr_factor, float clip, float grad_div);
 
 }  // namespace rsys

@@ -360,6 +360,7 @@ struct SimModel {
   float* exp32 = nullptr; bf16* exp16 = nullptr; bool has_export = false;
   unsigned* tmask = nullptr; long long tmw = 0;
   void* hws = nullptr; size_t hws_bytes = 0;        // hard-negative workspace, grown on demand
+  PairWs pws;                                       // catalogue-rank workspace (similarity_metrics.hip), grown on demand
   int last_nq = 0, last_n = 0, last_drop = 0; long long last_rows = 0;
   uint64_t last_seed = 0, last_step = 0;
   std::vector<int> h_rowid; std::vector<float> h_wscale;   // host sources of a call's uploads, alive until its closing wait
@@ -383,6 +384,7 @@ static void sim_free(SimModel* h) {
   for (void* p : h->allocs) hipFree(p);
   if (h->slab) hipFree(h->slab);
   if (h->hws) hipFree(h->hws);
+  pair_ws_free(&h->pws);
   if (h->exp32) hipFree(h->exp32);
   if (h->exp16) hipFree(h->exp16);
   if (h->tmask) hipFree(h->tmask);
@@ -780,6 +782,21 @@ static int sim_hard_negatives(SimModel* h, int split, int n_src, const int32_t* 
   return RSYS_OK;
 }
 
+// the ranks / masked score rows of similarity_metrics.hip over the held export and test mask; no model state changes
+static int sim_pair_ranks(SimModel* h, int32_t n_src, const int32_t* sources, const int64_t* off, const int32_t* tids, int32_t* ranks_out) {
+  ARG_CHECK(h->tmask, "rsys_sim_pair_ranks: no testmask (rsys_sim_testmask_set)");
+  ARG_CHECK(h->has_export, "rsys_sim_pair_ranks: no export (rsys_sim_embed_all or rsys_sim_export_set)");
+  HIP_CHECK(hipSetDevice(h->device));
+  return pair_ranks_run(h->exp32, h->V, h->E, h->tmask, h->tmw, n_src, sources, off, tids, ranks_out, &h->pws, h->stream);
+}
+
+static int sim_pair_scores(SimModel* h, int32_t n_src, const int32_t* sources, float* out) {
+  ARG_CHECK(h->tmask, "rsys_sim_pair_scores: no testmask (rsys_sim_testmask_set)");
+  ARG_CHECK(h->has_export, "rsys_sim_pair_scores: no export (rsys_sim_embed_all or rsys_sim_export_set)");
+  HIP_CHECK(hipSetDevice(h->device));
+  return pair_scores_run(h->exp32, h->V, h->E, h->tmask, h->tmw, n_src, sources, out, &h->pws, h->stream);
+}
+
 static int sim_debug_get(SimModel* h, const char* name, void* out, int64_t n) {
   ARG_CHECK(name && out, "rsys_sim_debug_get: null argument");
   ARG_CHECK(h->last_nq > 0, "rsys_sim_debug_get: no forward yet");
@@ -901,6 +918,12 @@ int32_t rsys_sim_hard_negatives(void* hv, int32_t split, int32_t n_src, const in
   SIM_HANDLE(hv);
   return sim_hard_negatives(h, split, n_src, sources, pos_offsets, pos_ids, n, ids_out);
 }
+int32_t rsys_sim_pair_ranks(void* hv, int32_t n_src, const int32_t* sources, const int64_t* tgt_offsets, const int32_t* tgt_ids,
+                            int32_t* ranks_out) {
+  SIM_HANDLE(hv);
+  return sim_pair_ranks(h, n_src, sources, tgt_offsets, tgt_ids, ranks_out);
+}
+int32_t rsys_sim_pair_scores(void* hv, int32_t n_src, const int32_t* sources, float* out) { SIM_HANDLE(hv); return sim_pair_scores(h, n_src, sources, out); }
 int32_t rsys_sim_debug_get(void* hv, const char* name, void* out, int64_t n) { SIM_HANDLE(hv); return sim_debug_get(h, name, out, n); }
 
 }  // extern "C"

@@ -3,7 +3,10 @@ on the device, under the reference's names, and the cross-medium map of Finetune
 
 The device work goes through the rsys_sim_* entry points of include/rsys.h: forward, LambdaRank loss and backward, nDCG, AdamW, the
 embedding export and the hard-negative mining.  This module holds the dataset assembly, the training loop, early stopping, checkpoints
-and the tables `serve.load_retrieval_tables` reads.  Inputs are plain arrays: the columns of pairs.{m}.csv and the boolean testmask."""
+and the tables `serve.load_retrieval_tables` reads.  Inputs are plain arrays: the columns of pairs.{m}.csv and the boolean testmask.
+
+The acceptance metrics of Training/item_similarity/pairwise_metrics.jl (nDCG@k and Recall@k of every test target ranked against the whole
+catalogue) are at the end of the file: the ranks come from rsys_sim_pair_ranks, the fp64 arithmetic is done here."""
 import csv
 import ctypes as C
 import math
@@ -203,6 +206,32 @@ class LTRModel:
         out = np.zeros((len(src), n), np.int32)
         check(lib().rsys_sim_hard_negatives(self.h, 0 if split == "training" else 1, len(src), _ptr(src), _ptr(off),
                                             _ptr(pid) if pid.size else _ptr(np.zeros(1, np.int32)), n, _ptr(out)))
+        return out
+
+    @staticmethod
+    def _csr(sources, targets):
+        src = np.ascontiguousarray(sources, np.int32)
+        assert len(targets) == len(src), "one target list per source"
+        off = np.zeros(len(src) + 1, np.int64)
+        off[1:] = np.cumsum([len(t) for t in targets])
+        tid = np.ascontiguousarray(np.concatenate([np.asarray(t, np.int32).reshape(-1) for t in targets]) if len(targets) else
+                                   np.zeros(0, np.int32), np.int32)
+        return src, off, tid
+
+    def pair_ranks(self, sources, targets):
+        """pairwise_metrics.jl's ranking (rsys_sim_pair_ranks): per source s the 1-based rank of each of its targets among all items
+        i != s, by the held export's fp32 Gram row times the held testmask row, in sortperm(rev = true) order; 0 for a target equal to
+        its source.  targets: one id sequence per source.  Returns one int32 array per source."""
+        src, off, tid = self._csr(sources, targets)
+        out = np.zeros(max(int(off[-1]), 1), np.int32)
+        check(lib().rsys_sim_pair_ranks(self.h, len(src), _ptr(src), _ptr(off), _ptr(tid if tid.size else np.zeros(1, np.int32)), _ptr(out)))
+        return [out[off[i]:off[i + 1]] for i in range(len(src))]
+
+    def pair_scores(self, sources):
+        """test hook: the masked score rows pair_ranks ranks, f32 [len(sources)][V] (rsys_sim_pair_scores)"""
+        src = np.ascontiguousarray(sources, np.int32)
+        out = np.zeros((len(src), self.V), np.float32)
+        check(lib().rsys_sim_pair_scores(self.h, len(src), _ptr(src), _ptr(out)))
         return out
 
     def debug(self, name, shape, dtype):
@@ -425,3 +454,138 @@ def item_similarity_tables(embeddings, adaptations):
         metrics[f"{m}.project.test"] = avg_norm(M @ A[np.asarray(s2)].T - B[np.asarray(t2)].T) if len(s2) else float("nan")
         d[f"crossproject.{m}"] = M.astype(np.float32)
     return d, metrics
+
+
+# ---- pairwise_metrics.jl: the catalogue metrics the model is accepted by, from the device's ranks
+METRIC_KS = (8, 128, 1024)
+
+
+def dcg_at_k(relevances, k):
+    """pairwise_metrics.jl:60-70"""
+    score = 0.0
+    for i in range(min(k, len(relevances))):
+        score += float(relevances[i]) / math.log2(i + 2)
+    return score
+
+
+def _metric_groups(df, ranks):
+    """per source in order of first appearance: (weight of its first row, {target: (relevance, rank)} with the LAST row of a repeated
+    target, the sum of the relevance column over all of its rows)"""
+    groups = {}
+    for s, t, r, w, rk in zip(df["source"], df["target"], df["relevance"], df["weight"], ranks):
+        g = groups.get(int(s))
+        if g is None:
+            g = groups[int(s)] = [float(w), {}, []]
+        g[1][int(t)] = (float(r), int(rk))
+        g[2].append(float(r))
+    return groups
+
+
+def ndcg_at_k(df, ranks, k):
+    """ndcg_at_k (pairwise_metrics.jl:72-97) with the sort replaced by its result: ranks[i] = the 1-based position of df's row i's target
+    among its source's candidates (LTRModel.pair_ranks; 0: not a candidate).  df: columns source, target, relevance, weight."""
+    num = den = 0.0
+    for weight, rel, _ in _metric_groups(df, ranks).values():
+        dcg = 0.0
+        for r, rk in sorted(rel.values(), key=lambda x: x[1]):
+            if 1 <= rk <= k:
+                dcg += r / math.log2(rk + 1)
+        idcg = dcg_at_k(sorted((r for r, _ in rel.values()), reverse=True), k)
+        num += (dcg / idcg if idcg > 0 else 0.0) * weight
+        den += weight
+    return num / den
+
+
+def recall_at_k(df, ranks, k):
+    """recall_at_k (pairwise_metrics.jl:99-123): the relevance found in the top k over the relevance column's sum (repeated rows included)"""
+    num = den = 0.0
+    for weight, rel, column in _metric_groups(df, ranks).values():
+        found = 0.0
+        for r, rk in sorted(rel.values(), key=lambda x: x[1]):
+            if 1 <= rk <= k:
+                found += r
+        total = 0.0
+        for r in column:
+            total += r
+        num += found / total * weight
+        den += weight
+    return num / den
+
+
+def _natural_sort_key(s):
+    import re
+    return [int(m.group(2)) if m.group(1) is None else m.group(1) for m in re.finditer(r"([^\d]+)|(\d+)", s)]
+
+
+def make_metric_dataframe(d):
+    """make_metric_dataframe (pairwise_metrics.jl:125-155) without a data-frame library: {"{medium}.{metric}": value} -> (columns, rows),
+    `medium` first and the other columns in natural sort order, one row per medium in ascending order"""
+    result = {}
+    for key, v in d.items():
+        task, metric = key.split(".", 1)
+        result.setdefault(int(task), {})[metric] = v
+    cols = sorted({c for v in result.values() for c in v}, key=_natural_sort_key)
+    return ["medium"] + cols, [[m] + [result[m].get(c) for c in cols] for m in sorted(result)]
+
+
+def metric_frame(pairs, testmask, medium):
+    """the data frame of save_metrics (pairwise_metrics.jl:164-172), 0-based ids: rows with cliptype == "medium{m}", score != 0 and
+    testmask[source, target] != 0; weight = sqrt(source_popularity)"""
+    clip = np.asarray([str(c) for c in pairs["cliptype"]])
+    src = np.asarray(pairs["source_matchedid"], np.int64)
+    tgt = np.asarray(pairs["target_matchedid"], np.int64)
+    score = np.asarray(pairs["score"], np.float64)
+    keep = (clip == f"medium{medium}") & (score != 0)
+    keep[keep] = np.asarray(testmask)[src[keep], tgt[keep]] != 0
+    return {"source": src[keep], "target": tgt[keep], "relevance": score[keep],
+            "weight": np.sqrt(np.asarray(pairs["source_popularity"], np.float64)[keep])}
+
+
+def frame_ranks(model, df):
+    """the rank of every row of a metric frame (LTRModel.pair_ranks over its sources in order of first appearance)"""
+    rows = {}
+    for i, s in enumerate(df["source"]):
+        rows.setdefault(int(s), []).append(i)
+    ranks = np.zeros(len(df["source"]), np.int32)
+    if rows:
+        out = model.pair_ranks(list(rows), [df["target"][idx] for idx in rows.values()])
+        for idx, r in zip(rows.values(), out):
+            ranks[idx] = r
+    return ranks
+
+
+def save_metrics(models_or_exports, pairs, testmasks, datadir, device=0):
+    """save_metrics (pairwise_metrics.jl:157-184).  models_or_exports[m]: an LTRModel (its eval-mode export is taken, and held) or the
+    export [V_m][E] itself; pairs[m]: the columns of pairs.{m}.csv; testmasks[m]: bool [V_m][V_m].  Writes pairwise.embeddings.csv and
+    pairwise.embeddings.npz ("embeddings.{m}": E x V_m, Julia's layout) into datadir; returns (tables, metrics) with metrics =
+    {"{m}.nDCG@{k}", "{m}.Recall@{k}"} for k in (8, 128, 1024)."""
+    tables, ret = {}, {}
+    for medium in sorted(models_or_exports):
+        entry = models_or_exports[medium]
+        own = not isinstance(entry, LTRModel)
+        if own:
+            emb = np.ascontiguousarray(entry, np.float32)
+            cfg = training_config({medium: emb.shape[0]}, embed_dim=emb.shape[1], batch_size=1, items_per_query=1)
+            model = LTRModel(cfg, medium, np.zeros((emb.shape[0], 64), np.float32), dtype="fp32", dropout=0.0, device=device)
+            model.set_export(emb)
+        else:
+            model = entry
+            emb = model.embed_all(train_mode=False)
+        try:
+            model.set_testmask(testmasks[medium])
+            df = metric_frame(pairs[medium], testmasks[medium], medium)
+            ranks = frame_ranks(model, df)
+        finally:
+            if own:
+                model.close()
+        for k in METRIC_KS:
+            ret[f"{medium}.nDCG@{k}"] = ndcg_at_k(df, ranks, k)
+            ret[f"{medium}.Recall@{k}"] = recall_at_k(df, ranks, k)
+        tables[f"embeddings.{medium}"] = np.ascontiguousarray(emb.T)
+    np.savez(os.path.join(datadir, "pairwise.embeddings.npz"), **tables)
+    cols, rows = make_metric_dataframe(ret)
+    with open(os.path.join(datadir, "pairwise.embeddings.csv"), "w", newline="") as f:
+        w = csv.writer(f)
+        w.writerow(cols)
+        w.writerows(rows)
+    return tables, ret
