@@ -343,6 +343,26 @@ int32_t rsys_infer(rsys_model* m, int32_t task, float* out, int64_t n);
  * retrieval and the candidates' action tokens for ranking): token_index[n_tokens] = flat token indices in [0, rows*2S);
  * out = n_tokens*D floats (retrieval: the trunk output rows) or n_tokens floats (ranking: the rating head on those rows only) */
 int32_t rsys_infer_select(rsys_model* m, int32_t task, const int32_t* token_index, int64_t n_tokens, float* out, int64_t n);
+/* Adapter bank of a base model (finetune = 0; fp32 or bf16): up to RSYS_ADAPTER_SLOTS rank-8 LoRA adapter sets on q_proj / v_proj
+ * (model.py:235-271; alpha 16, scaling 2) held on the device beside the frozen trunk -- what Finetune/embed.py:180-255 serves as four
+ * models that share one trunk.  Tensors go in and out by their state-dict names "transformers.layers.{l}.attn.{q,v}_proj_lora_{A,B}.weight"
+ * (A: 8 x embed_dim; q B: num_heads*head_dim x 8; v B: num_kv_heads*head_dim x 8, row-major).  A slot is complete once all 4 * num_layers
+ * tensors have been set since its last clear; get returns the float32 values that were set, bit for bit.  Setting or clearing a slot
+ * changes no parameter of the model: the fused item table, the serving tables and a following training step are unaffected.
+ * Errors (RSYS_ERR_ARG, nothing written): slot outside [0, RSYS_ADAPTER_SLOTS), unknown name, wrong element count, get of a tensor that
+ * is not set, a finetune = 1 or fp8 model. */
+#define RSYS_ADAPTER_SLOTS 8
+int32_t rsys_adapter_set(rsys_model* m, int32_t slot, const char* name, const float* in, int64_t n);
+int32_t rsys_adapter_get(rsys_model* m, int32_t slot, const char* name, float* out, int64_t n);
+int32_t rsys_adapter_clear(rsys_model* m, int32_t slot);
+/* bit s of *mask_out: slot s is complete */
+int32_t rsys_adapter_slots(rsys_model* m, int32_t* mask_out);
+/* rsys_infer_select with one adapter slot per batch row: row_adapter[rows] in [-1, RSYS_ADAPTER_SLOTS); the tokens of row r run with
+ * q += 2 (xn A_q^T) B_q^T, v += 2 (xn A_v^T) B_v^T of slot row_adapter[r] in every layer, -1 = the base model.  One forward for the
+ * whole batch, whatever the number of distinct slots; a row's result does not depend on the other rows' slots.  Output and limits as
+ * rsys_infer_select.  RSYS_ERR_ARG (out untouched): row_adapter NULL, an entry out of range or naming an incomplete slot, no batch. */
+int32_t rsys_infer_select_adapters(rsys_model* m, int32_t task, const int32_t* row_adapter, const int32_t* token_index, int64_t n_tokens,
+                                   float* out, int64_t n);
 /* debug/parity: trunk output of the last forward (rows*2S*D floats).  A training pass computes it only at the positions the heads
  * select; this call then runs the dense tail of the last layer first (results as model.py:335-343 over every token). */
 int32_t rsys_trunk_output_get(rsys_model* m, float* out, int64_t n);

@@ -105,6 +105,30 @@ function infer_select(m::Model, task::Integer, tokens::Vector{Int32}, D::Integer
     out
 end
 
+# adapter bank of a base model (Finetune/embed.py:180-255: four LoRA adapters on one trunk): tensors by state-dict name into slot
+# 0 .. 7 (0-based, as the C ABI counts them), then one forward with a slot (or -1 = base model) per batch row
+const ADAPTER_SLOTS = 8
+function set_adapter!(m::Model, slot::Integer, name::String, x::Array{Float32})
+    GC.@preserve x check(ccall((:rsys_adapter_set, LIB), Int32, (Ptr{Cvoid}, Int32, Cstring, Ptr{Float32}, Int64), m.h, slot, name, x, length(x)))
+end
+function get_adapter!(m::Model, slot::Integer, name::String, out::Array{Float32})
+    GC.@preserve out check(ccall((:rsys_adapter_get, LIB), Int32, (Ptr{Cvoid}, Int32, Cstring, Ptr{Float32}, Int64), m.h, slot, name, out, length(out)))
+    out
+end
+clear_adapter!(m::Model, slot::Integer) = check(ccall((:rsys_adapter_clear, LIB), Int32, (Ptr{Cvoid}, Int32), m.h, slot))
+function adapter_slots(m::Model)
+    mask = Ref{Int32}(0)
+    check(ccall((:rsys_adapter_slots, LIB), Int32, (Ptr{Cvoid}, Ref{Int32}), m.h, mask))
+    [s for s in 0:ADAPTER_SLOTS-1 if (mask[] >> s) & 1 == 1]
+end
+function infer_select_adapters(m::Model, task::Integer, row_adapter::Vector{Int32}, tokens::Vector{Int32}, D::Integer)
+    out = task == 0 ? Matrix{Float32}(undef, D, length(tokens)) : Vector{Float32}(undef, length(tokens))
+    GC.@preserve row_adapter tokens out check(ccall((:rsys_infer_select_adapters, LIB), Int32,
+                                                    (Ptr{Cvoid}, Int32, Ptr{Int32}, Ptr{Int32}, Int64, Ptr{Float32}, Int64),
+                                                    m.h, task, row_adapter, tokens, length(tokens), out, length(out)))
+    out
+end
+
 function create_optimizer(m::Model; lr = 1f-4, betas = (0.9f0, 0.95f0), eps = 1f-8, weight_decay = 0.1f0)
     h = Ref{Ptr{Cvoid}}(C_NULL)
     check(ccall((:rsys_adamw_create, LIB), Int32, (Ptr{Cvoid}, Float32, Float32, Float32, Float32, Float32, Ref{Ptr{Cvoid}}),

@@ -113,6 +113,11 @@ _SIGS = [
     ("rsys_model_set_deterministic", C.c_int32, [_P, C.c_int32]),
     ("rsys_infer", C.c_int32, [_P, C.c_int32, _P, C.c_int64]),
     ("rsys_infer_select", C.c_int32, [_P, C.c_int32, _P, C.c_int64, _P, C.c_int64]),
+    ("rsys_adapter_set", C.c_int32, [_P, C.c_int32, C.c_char_p, _P, C.c_int64]),
+    ("rsys_adapter_get", C.c_int32, [_P, C.c_int32, C.c_char_p, _P, C.c_int64]),
+    ("rsys_adapter_clear", C.c_int32, [_P, C.c_int32]),
+    ("rsys_adapter_slots", C.c_int32, [_P, C.POINTER(C.c_int32)]),
+    ("rsys_infer_select_adapters", C.c_int32, [_P, C.c_int32, _P, _P, C.c_int64, _P, C.c_int64]),
     ("rsys_trunk_output_get", C.c_int32, [_P, _P, C.c_int64]),
     ("rsys_debug_get", C.c_int32, [_P, C.c_char_p, _P, C.c_int64]),
     ("rsys_clip_grad_norm", C.c_int32, [_P, C.c_float, C.POINTER(C.c_float)]),

@@ -10,6 +10,9 @@ reference's state-dict names under "model/", AdamW moments by parameter NAME, th
     python -m recommendersystem_amd.checkpoint pt2npz transformer.masked.pt transformer.masked.npz
     python -m recommendersystem_amd.checkpoint npz2pt transformer.masked.npz transformer.masked.pt [DATADIR | media_embeddings.h5]
 (the optional last argument supplies the frozen metadata table the reference's strict load expects)
+    python -m recommendersystem_amd.checkpoint dedup OUTDIR 0.watch.npz 0.rating.npz 1.watch.npz 1.rating.npz
+(Finetune/register.py:38-63: the four finetuned checkpoints' shared trunk once, as OUTDIR/base.npz, and each checkpoint's LoRA
+tensors as OUTDIR/{medium}.{metric}.lora.npz -- what `serve.get_models` loads)
 
 The conversion needs torch only to read / write the pickle (host side; nothing here touches the GPU path).
 Optimizer state is keyed by parameter INDEX in the reference: `create_optimizer` (transformer.py:285-298) puts the
@@ -194,7 +197,33 @@ def dedup_finetune_models(blobs):
     return base, out
 
 
+DEDUP_NAMES = ("0.watch", "0.rating", "1.watch", "1.rating")     # Finetune/run.jl:9-13
+
+
+def dedup_files(outdir, paths):
+    """the `dedup` command: four finetune checkpoints (`.npz`) -> outdir/base.npz + outdir/{medium}.{metric}.lora.npz; returns the paths"""
+    import os
+    if len(paths) != len(DEDUP_NAMES):
+        raise ValueError(f"dedup: {len(paths)} checkpoints, expected {len(DEDUP_NAMES)} ({', '.join(DEDUP_NAMES)})")
+    blobs = []
+    for p in paths:
+        z = np.load(p)
+        blobs.append({k: z[k] for k in z.files})
+    base, loras = dedup_finetune_models(blobs)
+    os.makedirs(outdir, exist_ok=True)
+    out = [os.path.join(outdir, "base.npz")]
+    np.savez(out[0], **base)
+    for name, blob in zip(DEDUP_NAMES, loras):
+        out.append(os.path.join(outdir, f"{name}.lora.npz"))
+        np.savez(out[-1], **blob)
+    return out
+
+
 def main(argv):
+    if len(argv) == 7 and argv[1] == "dedup":
+        for p in dedup_files(argv[2], argv[3:]):
+            print(p)
+        return 0
     if len(argv) not in (4, 5) or argv[1] not in ("pt2npz", "npz2pt"):
         print(__doc__)
         return 2

@@ -216,6 +216,22 @@ int32_t rsys_infer_select(rsys_model* h, int32_t task, const int32_t* token_inde
   CHECK_HANDLE(h); ARG_CHECK(out && token_index && n_tokens >= 1, "null or empty selection");
   return model_infer(h->m, task, token_index, n_tokens, out, n);
 }
+int32_t rsys_adapter_set(rsys_model* h, int32_t slot, const char* name, const float* in, int64_t n) {
+  CHECK_HANDLE(h); ARG_CHECK(name && in, "null");
+  return adapter_io(h->m, slot, name, nullptr, in, n);
+}
+int32_t rsys_adapter_get(rsys_model* h, int32_t slot, const char* name, float* out, int64_t n) {
+  CHECK_HANDLE(h); ARG_CHECK(name && out, "null");
+  return adapter_io(h->m, slot, name, out, nullptr, n);
+}
+int32_t rsys_adapter_clear(rsys_model* h, int32_t slot) { CHECK_HANDLE(h); return adapter_clear(h->m, slot); }
+int32_t rsys_adapter_slots(rsys_model* h, int32_t* mask_out) { CHECK_HANDLE(h); return adapter_slots(h->m, mask_out); }
+int32_t rsys_infer_select_adapters(rsys_model* h, int32_t task, const int32_t* row_adapter, const int32_t* token_index, int64_t n_tokens, float* out,
+                                   int64_t n) {
+  CHECK_HANDLE(h); ARG_CHECK(out && token_index && n_tokens >= 1, "null or empty selection");
+  ARG_CHECK(row_adapter, "row_adapter is null (rsys_infer_select runs the base model)");
+  return model_infer_adapters(h->m, task, row_adapter, token_index, n_tokens, out, n);
+}
 
 int32_t rsys_trunk_output_get(rsys_model* h, float* out, int64_t n) {
   CHECK_HANDLE(h);

@@ -395,6 +395,7 @@ int model_destroy(Model* m) {
   retrieve_tables_free(m);
   rank_free(m);
   retrieve_eval_free(m);
+  adapter_bank_free(m);
   if (m->copy_stream) { hipStreamSynchronize(m->copy_stream); hipStreamDestroy(m->copy_stream); }
   if (m->h_stage) hipHostFree(m->h_stage);
   if (m->slot_stage[1]) hipHostFree(m->slot_stage[1]);
@@ -935,6 +936,16 @@ int model_infer(Model* m, int task, const int32_t* token_index, int64_t n_tokens
   ARG_CHECK(task == 0 || task == 1, "task: 0 retrieval, 1 ranking");
   HIP_CHECK(hipSetDevice(m->device));
   return m->bf16_mode ? infer_t<bf16>(m, task, token_index, n_tokens, out, n) : infer_t<float>(m, task, token_index, n_tokens, out, n);
+}
+
+// the same forward with a LoRA adapter slot per batch row (adapter_bank.hip); row_adapter[r] = -1: the base model for that row
+int model_infer_adapters(Model* m, int task, const int32_t* row_adapter, const int32_t* token_index, int64_t n_tokens, float* out, int64_t n) {
+  ARG_CHECK(m->cur_rows > 0, "no batch uploaded");
+  ARG_CHECK(task == 0 || task == 1, "task: 0 retrieval, 1 ranking");
+  RC(adapter_bind_rows(m, row_adapter));
+  const int rc = m->bf16_mode ? infer_t<bf16>(m, task, token_index, n_tokens, out, n) : infer_t<float>(m, task, token_index, n_tokens, out, n);
+  adapter_unbind_rows(m);
+  return rc;
 }
 
 }  // namespace rsys

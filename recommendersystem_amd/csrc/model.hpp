@@ -48,6 +48,7 @@ struct RetrieveWs;       // retrieve.hip
 struct RetrievalTables;  // retrieve_request.hip
 struct RankTables;       // rank_request.hip
 struct EvalWs;           // retrieve_eval.hip
+struct AdapterBank;      // adapter_bank.hip
 
 struct Model {
   rsys_config cfg;
@@ -270,6 +271,11 @@ struct Model {
   RetrievalTables* rtab = nullptr;      // rsys_retrieve_request's serving tables and workspace (not part of checkpoints)
   RankTables* rank = nullptr;           // rsys_rank_request's "{m}.related" tables and workspace (not part of checkpoints)
   EvalWs* ews = nullptr;                // rsys_retrieve_target_rank's workspace (allocated on first use)
+  // adapter bank of a base model (adapter_bank.hip, allocated by the first rsys_adapter_set): LoRA adapter sets in slots beside the frozen
+  // trunk.  bank_rows (device, one slot or -1 per batch row) is non-null only inside rsys_infer_select_adapters: forward_trunk then adds
+  // every row's own update to q and v; every other pass leaves it null and launches what it always has
+  AdapterBank* bank = nullptr;
+  const int* bank_rows = nullptr;
 };
 
 struct Optimizer {
@@ -299,6 +305,16 @@ int model_refresh_shadow(Model* m);
 int model_batch_upload(Model* m, const rsys_batch* b);
 int model_forward_backward(Model* m, int evaluate, const float task_w[4], float grad_scale, uint64_t seed, uint64_t step);
 int model_infer(Model* m, int task, const int32_t* token_index, int64_t n_tokens, float* out, int64_t n);   // token_index == nullptr: every token
+// adapter bank (adapter_bank.hip): slot storage by state-dict name, and the inference forward with one slot per batch row
+int adapter_io(Model* m, int slot, const char* name, float* out, const float* in, int64_t n);   // exactly one of out / in
+int adapter_clear(Model* m, int slot);
+int adapter_slots(Model* m, int32_t* mask_out);
+int adapter_bind_rows(Model* m, const int32_t* row_adapter);
+void adapter_unbind_rows(Model* m);
+void adapter_bank_free(Model* m);
+template <typename T> int adapter_bank_stage_a(Model* m, int l, const T* xn);                      // La = xn . [A_q; A_v][slot]^T
+template <typename T> int adapter_bank_stage_b(Model* m, int l, T* qkv, const int* rope_pos);      // q, v += 2 La . B[slot]^T (q rotated)
+int model_infer_adapters(Model* m, int task, const int32_t* row_adapter, const int32_t* token_index, int64_t n_tokens, float* out, int64_t n);
 int model_item_table(Model* m, float* out, int64_t n);
 // the fp32 item table rows [V_m][D] of `medium` on the model's device (rsys_sim_features_from_model); the model's stream is idle on return
 int model_item_table_device(Model* m, int medium, const float** rows, int64_t* Vm, int* D);

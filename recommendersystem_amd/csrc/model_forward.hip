@@ -209,6 +209,7 @@ int forward_trunk(Model* m) {
       p.M = NT; p.N = 16; p.K = D; p.epi = EPI_STORE;
       RC(gemm<T>(m, "gemm_lora_a_fwd", p, false, false, false));
     }
+    if (m->bank_rows) RC(adapter_bank_stage_a<T>(m, l, AT<T>(a.xn)));   // rsys_infer_select_adapters: every row's own adapter (or none)
     {
       GemmParams p{};
       p.A = a.xn; p.lda = D; p.B = W<T>(m, m->lo[l].wqkv); p.ldb = D; p.C = a.qkv; p.ldc = m->Nqkv;
@@ -228,6 +229,7 @@ int forward_trunk(Model* m) {
       p.n_q = m->H * hd; p.n_k = m->KV * hd;
       RC(gemm<T>(m, "gemm_lora_b_fwd", p, false, false, false));
     }
+    if (m->bank_rows) RC(adapter_bank_stage_b<T>(m, l, AT<T>(a.qkv), rpos_l));
     AttnParams& apl = top ? ap_top : ap;
     apl.q = a.qkv; apl.k = AT<T>(a.qkv) + m->H * hd; apl.v = AT<T>(a.qkv) + (m->H + m->KV) * hd; apl.ld = m->Nqkv;
     apl.o = a.O; apl.ldo = D; apl.lse = a.lse;

@@ -343,16 +343,73 @@ class RecommenderModel:
             return out
         raise AssertionError(task)
 
-    def inference_select(self, d, task, token_index):
+    def inference_select(self, d, task, token_index, adapters=None):
         """The inference forward reporting only the tokens a server reads (embed.py:147-161): `token_index` = flat token indices
-        in [0, rows * 2S).  "retrieval" -> (n, D) trunk outputs, "ranking" -> (n,) rating-head values (computed on those rows only)."""
+        in [0, rows * 2S).  "retrieval" -> (n, D) trunk outputs, "ranking" -> (n,) rating-head values (computed on those rows only).
+        `adapters`: one adapter-bank slot per batch row (-1 = the base model) or one slot for every row; None = the model as it is."""
         self.upload(d)
         idx = np.ascontiguousarray(np.asarray(token_index).reshape(-1), np.int32)
         D = self.config["embed_dim"]
         t = {"retrieval": 0, "ranking": 1}[task]
         out = np.empty((idx.size, D) if t == 0 else (idx.size,), np.float32)
-        check(lib().rsys_infer_select(self._h, t, idx.ctypes.data, idx.size, out.ctypes.data, out.size))
+        if adapters is None:
+            check(lib().rsys_infer_select(self._h, t, idx.ctypes.data, idx.size, out.ctypes.data, out.size))
+            return out
+        rows = int(np.asarray(d["userid"]).size) // self.config["max_sequence_length"]
+        slots = np.full(rows, int(adapters), np.int32) if np.ndim(adapters) == 0 else np.ascontiguousarray(np.asarray(adapters).reshape(-1), np.int32)
+        if slots.size != rows:
+            raise ValueError(f"inference_select: {slots.size} adapter slots for {rows} batch rows")
+        check(lib().rsys_infer_select_adapters(self._h, t, slots.ctypes.data, idx.ctypes.data, idx.size, out.ctypes.data, out.size))
         return out
+
+    # ---- adapter bank (base model: several LoRA adapter sets beside one frozen trunk, Finetune/embed.py:180-255)
+    ADAPTER_SLOTS = 8
+
+    def adapter_names(self):
+        """[(name, shape)] of the 4 * num_layers LoRA tensors of one adapter, in the reference's state-dict order (model.py:235-254)"""
+        c = self.config
+        D = c["embed_dim"]; hd = D // c["num_heads"]
+        out = []
+        for l in range(c["num_layers"]):
+            p = f"transformers.layers.{l}.attn."
+            out += [(p + "q_proj_lora_A.weight", (8, D)), (p + "q_proj_lora_B.weight", (c["num_heads"] * hd, 8)),
+                    (p + "v_proj_lora_A.weight", (8, D)), (p + "v_proj_lora_B.weight", (c["num_kv_heads"] * hd, 8))]
+        return out
+
+    def load_adapter(self, slot, state_dict):
+        """Loads the `lora_` tensors of `state_dict` (a finetuned model's full state dict or its LoRA-only part, as
+        `load_state_dict(..., strict=False)` takes them in embed.py:196) into bank slot `slot`; every LoRA tensor must be there.
+        Nothing of the model itself changes: the item table, serving tables and a later training step are unaffected."""
+        names = self.adapter_names()
+        missing = [n for n, _ in names if n not in state_dict]
+        if missing:
+            raise KeyError(f"load_adapter: missing LoRA keys {missing[:4]}{' ...' if len(missing) > 4 else ''}")
+        vals = []
+        for n, shape in names:
+            v = np.ascontiguousarray(state_dict[n], np.float32)
+            if v.shape != shape:
+                raise ValueError(f"load_adapter: {n} has shape {v.shape}, expected {shape}")
+            vals.append(v)
+        for (n, _), v in zip(names, vals):
+            check(lib().rsys_adapter_set(self._h, int(slot), n.encode(), v.ctypes.data, v.size))
+
+    def adapter_state_dict(self, slot):
+        """the LoRA tensors held in `slot`, as float32 arrays under their state-dict names (bit for bit what was loaded)"""
+        sd = {}
+        for n, shape in self.adapter_names():
+            out = np.empty(shape, np.float32)
+            check(lib().rsys_adapter_get(self._h, int(slot), n.encode(), out.ctypes.data, out.size))
+            sd[n] = out
+        return sd
+
+    def clear_adapter(self, slot):
+        check(lib().rsys_adapter_clear(self._h, int(slot)))
+
+    def adapters_loaded(self):
+        """the complete slots, ascending"""
+        mask = C.c_int32()
+        check(lib().rsys_adapter_slots(self._h, C.byref(mask)))
+        return [s for s in range(self.ADAPTER_SLOTS) if (mask.value >> s) & 1]
 
     def item_embeddings(self):
         """`model.item_embedding(torch.arange(0, n_0 + n_1))` (register.py:27-29): the (V, D) table E + Wp.Meta + bp."""

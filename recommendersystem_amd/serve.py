@@ -98,9 +98,9 @@ def extract(embs, users, task, medium, max_user_len=1024):
     return out
 
 
-def predict(model, users, task, medium, max_user_len=None, max_ranking_items=None):
-    """embed.py:74-161 on the HIP model (`model.config["forward"]` semantics = inference): sequence length of the request =
-    the model's `max_sequence_length` (retrieval: all of it is history + query; ranking: split between history and candidates)."""
+def _request_lengths(model, task, max_user_len, max_ranking_items):
+    """(max_user_len, max_ranking_items) of a request: the model's `max_sequence_length` is all history + query for retrieval and is
+    split between history and candidates for ranking"""
     S = model.config["max_sequence_length"]
     if task == "retrieval":
         max_user_len = S if max_user_len is None else max_user_len
@@ -110,24 +110,113 @@ def predict(model, users, task, medium, max_user_len=None, max_ranking_items=Non
         max_user_len = S // 2 if max_user_len is None else max_user_len
         max_ranking_items = S - max_user_len if max_ranking_items is None else max_ranking_items
         assert max_user_len + max_ranking_items == S
-    d = build_batch(users, task, medium, model.config["vocab_sizes"]["0_matchedid"], max_user_len, max_ranking_items)
-    if not hasattr(model, "inference_select"):           # (a model that only has the reference's call: the full tensor, then extract)
-        return extract(model.inference_forward(d, task), users, task, medium, max_user_len)
-    # only the tokens `extract` would read leave the device (one row per user for retrieval, the candidates' action tokens for
-    # ranking) instead of the (rows, 2S, D) tensor
+    return max_user_len, max_ranking_items
+
+
+def _selected_tokens(users, task, S, max_user_len):
+    """flat token indices `extract` would read (one per user for retrieval, the candidates' action tokens for ranking) and their
+    number per user"""
     index, counts = [], []
     for row, u in enumerate(users):
         n = len(_history(u, max_user_len))
         toks = [2 * n] if task == "retrieval" else list(2 * (n + np.arange(len(u["ranking_items"]))) + 1)
         index += [row * 2 * S + int(t) for t in toks]; counts.append(len(toks))
+    return index, counts
+
+
+def predict(model, users, task, medium, max_user_len=None, max_ranking_items=None):
+    """embed.py:74-161 on the HIP model (`model.config["forward"]` semantics = inference): sequence length of the request =
+    the model's `max_sequence_length` (retrieval: all of it is history + query; ranking: split between history and candidates).
+    A model built by `get_models` (it has an `adapter_slots` map) runs every row with the adapter of "{medium}.{task}"."""
+    S = model.config["max_sequence_length"]
+    max_user_len, max_ranking_items = _request_lengths(model, task, max_user_len, max_ranking_items)
+    d = build_batch(users, task, medium, model.config["vocab_sizes"]["0_matchedid"], max_user_len, max_ranking_items)
+    if not hasattr(model, "inference_select"):           # (a model that only has the reference's call: the full tensor, then extract)
+        return extract(model.inference_forward(d, task), users, task, medium, max_user_len)
+    # only the tokens `extract` would read leave the device (one row per user for retrieval, the candidates' action tokens for
+    # ranking) instead of the (rows, 2S, D) tensor
+    index, counts = _selected_tokens(users, task, S, max_user_len)
     key = f"{medium}.{task}"
     if not index:
         return [{key: []} for _ in users]
-    vals = model.inference_select(d, task, index)
+    slots = getattr(model, "adapter_slots", None)
+    if slots:
+        vals = model.inference_select(d, task, index, adapters=[slots[key]] * len(users))
+    else:
+        vals = model.inference_select(d, task, index)
     out, at = [], 0
     for c in counts:
         out.append({key: (vals[at].tolist() if task == "retrieval" else vals[at:at + c].tolist())}); at += c
     return out
+
+
+def predict_mixed(model, requests, task, max_user_len=None, max_ranking_items=None):
+    """`predict` for users of both media in ONE forward: `requests` = [(user, medium), ...]; row i of the batch is the row
+    `build_batch([user_i], task, medium_i, ...)` builds and runs with the adapter slot `model.adapter_slots[f"{medium_i}.{task}"]`
+    (embed.jl:5-84 keeps one queue per (medium, task) on one GPU; single-user inference is launch-bound, so sharing a forward
+    is what the shared trunk buys).  Result i is keyed "{medium_i}.{task}" like `predict`'s."""
+    slots = getattr(model, "adapter_slots", None)
+    if not slots:
+        raise ValueError("predict_mixed: the model has no adapter_slots map (build it with get_models)")
+    if not requests:
+        return []
+    S = model.config["max_sequence_length"]
+    max_user_len, max_ranking_items = _request_lengths(model, task, max_user_len, max_ranking_items)
+    n0 = model.config["vocab_sizes"]["0_matchedid"]
+    parts = [build_batch([u], task, int(m), n0, max_user_len, max_ranking_items) for u, m in requests]
+    d = {k: np.concatenate([p[k] for p in parts], axis=0) for k in parts[0]}    # (every row keeps userid 1: attention never crosses batch rows)
+    users = [u for u, _ in requests]
+    index, counts = _selected_tokens(users, task, S, max_user_len)
+    keys = [f"{int(m)}.{task}" for _, m in requests]
+    if not index:
+        return [{k: []} for k in keys]
+    vals = model.inference_select(d, task, index, adapters=[slots[k] for k in keys])
+    out, at = [], 0
+    for k, c in zip(keys, counts):
+        out.append({k: (vals[at].tolist() if task == "retrieval" else vals[at:at + c].tolist())}); at += c
+    return out
+
+
+ADAPTER_TASKS = {"watch": "retrieval", "rating": "ranking"}      # embed.py:182
+
+
+def get_models(base, loras, config, device=0, dtype="bf16", max_rows=4, model_cls=None):
+    """Finetune/embed.py:180-255 (`load_model` + `get_models`) on one base model: the consumer of
+    `checkpoint.dedup_finetune_models`.  `base`: the shared trunk (`.npz`-layout dict, keys "model/..."); `loras`: the LoRA-only
+    blobs, either {"{medium}.{metric}": blob} (metric watch / rating) or a list in the reference's order (0.watch, 0.rating, 1.watch,
+    1.rating, Finetune/run.jl:9-13).  Builds ONE model (finetune off, forward = inference), loads the trunk once, puts every adapter
+    into a bank slot and records `model.adapter_slots = {"0.retrieval": s, "0.ranking": s, "1.retrieval": s, "1.ranking": s}`."""
+    order = [(m, metric) for m in (0, 1) for metric in ("watch", "rating")]
+    if not isinstance(loras, dict):
+        loras = list(loras)
+        if len(loras) != len(order):
+            raise ValueError(f"get_models: {len(loras)} adapters, expected {len(order)} (0.watch, 0.rating, 1.watch, 1.rating)")
+        loras = {f"{m}.{metric}": blob for (m, metric), blob in zip(order, loras)}
+    strip = lambda blob: {k[len("model/"):]: v for k, v in blob.items() if k.startswith("model/")}
+    adapters = {}
+    for m, metric in order:
+        key = f"{m}.{metric}"
+        if key not in loras:
+            raise KeyError(f"get_models: no adapter for {key}")
+        sd = {k: v for k, v in strip(loras[key]).items() if "lora_" in k}
+        if not sd:
+            raise KeyError(f"get_models: adapter {key} has no lora keys")
+        adapters[key] = sd
+    trunk = {k: v for k, v in strip(base).items() if "lora_" not in k}
+    if not trunk:
+        raise KeyError("get_models: the base has no trunk keys")
+    cfg = dict(config)
+    cfg["finetune"] = False
+    cfg["forward"] = "inference"
+    if model_cls is None:
+        from .model import RecommenderModel as model_cls
+    model = model_cls(cfg, device=device, dtype=dtype, max_rows=max_rows)
+    model.load_state_dict(trunk, strict=False)
+    model.adapter_slots = {}
+    for slot, (m, metric) in enumerate(order):
+        model.load_adapter(slot, adapters[f"{m}.{metric}"])
+        model.adapter_slots[f"{m}.{ADAPTER_TASKS[metric]}"] = slot
+    return model
 
 
 def register_transformer(model, path):
