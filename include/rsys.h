@@ -307,6 +307,56 @@ int32_t rsys_sim_hard_negatives(void* h, int32_t split, int32_t n_src, const int
 int32_t rsys_sim_pair_ranks(void* h, int32_t n_src, const int32_t* sources, const int64_t* tgt_offsets, const int32_t* tgt_ids,
                             int32_t* ranks_out);
 
+/* ---- Search model (Training/search/train.py:76-130): text-query embeddings against the transformer's item table.  A handle
+ * of its own per medium, independent of rsys_model: an rsys_searchmodel, passed as an opaque void*.  Trainable parameters by the
+ * reference's state-dict names: "encoder.weight" Wenc [Q][D] (nn.Linear(D, Q, bias = False); weight decay) and "logit_scale" (scalar, 1.0
+ * at creation, no decay); the frozen table E_m [V_m][D] (the rows of medium m of "retrieval_embeddings.weight") goes through
+ * rsys_search_features_set.  The reference forms W = E Wenc^T and soft-maxes x W^T exp(logit_scale) over the columns of each medium; all
+ * labels of a batch lie in the handle's medium, so the other medium's columns carry neither loss nor gradient, and the device computes
+ * the factored form: P = x Wenc, logits = P E_m^T exp(logit_scale), loss = sum_i w_i (logsumexp_i - logit_i[y_i]) / sum w.
+ * dtype RSYS_DTYPE_FP32: everything fp32.  RSYS_DTYPE_BF16: x, Wenc, E_m, P, G = w (softmax - onehot) and dP rounded to bf16 as MFMA
+ * operands with fp32 accumulation; the scores, soft-max statistics, loss, d logit_scale, dWenc and the optimizer stay fp32.  These are
+ * NOT bf16 autocast's rounding points (autocast rounds W and the logits, which the factored form never holds).  Every call is bitwise
+ * reproducible (no float atomics in any sum a result depends on).  Calls on one handle are serialised by the caller. */
+/* SearchModel(config, medium): V_m items (any count), D = the item table's width and Q = the query embedding's width (multiples of 64;
+ * 2048 and 3072 in the reference), 1 <= max_batch <= 4096 rows per call */
+int32_t rsys_search_create(int64_t V_m, int32_t D, int32_t Q, int32_t dtype, int32_t max_batch, int32_t device, void** out);
+int32_t rsys_search_destroy(void* h);
+/* state_dict access: n must be the tensor's element count; unknown names are ARG errors */
+int32_t rsys_search_param_get(void* h, const char* name, float* out, int64_t n);
+int32_t rsys_search_param_set(void* h, const char* name, const float* in, int64_t n);
+int32_t rsys_search_grad_get(void* h, const char* name, float* out, int64_t n);
+int32_t rsys_search_zero_grad(void* h);
+/* the frozen table E_m [V_m][D] f32 from the host; V_m and D must be the handle's */
+int32_t rsys_search_features_set(void* h, const float* features, int64_t V_m, int64_t D);
+/* the same from a transformer model on the same device without a host round trip: the rows of medium `medium` of its fp32 item table
+ * (as rsys_sim_features_from_model).  Synchronous. */
+int32_t rsys_search_features_from_model(void* h, rsys_model* m, int32_t medium);
+/* model(batch) + loss.backward() (train.py:113-130): x [B][Q] f32 query embeddings, labels [B] medium-local ids, weights [B] (=
+ * sqrt(counts)).  *loss_out = sum_i w_i (lse_i - logit_i[y_i]) / sum w, *weight_sum_out = sum w (either may be NULL).  evaluate == 0:
+ * the gradient is ACCUMULATED into .grad; evaluate != 0: forward only.  Synchronous.  ARG errors (the reference would return NaN or
+ * fault): B outside [1, max_batch], a label outside [0, V_m), a negative or non-finite weight, a zero weight sum, features not set. */
+int32_t rsys_search_forward_backward(void* h, const float* x, const int32_t* labels, const float* weights, int32_t B, int32_t evaluate,
+                                     float* loss_out, float* weight_sum_out);
+/* AdamW over the two parameters (train.py:181-192): betas and eps as given (torch's defaults 0.9, 0.999, 1e-8 in the reference),
+ * weight_decay on encoder.weight and 0 on logit_scale; clears the moments and the step count */
+int32_t rsys_search_adamw_create(void* h, float beta1, float beta2, float eps, float weight_decay);
+/* clip_grad_norm_(clip) + GradScaler.step(AdamW) + zero_grad (train.py:170-174): the global-norm clip fused (clip <= 0: none).  A
+ * non-finite gradient norm skips the update: parameters, moments and the step count stay as they were.  *norm_out = the norm before
+ * clipping, *skipped_out = 1 when skipped (either may be NULL).  The gradient is cleared in both cases.  RSYS_ERR_STATE before
+ * rsys_search_adamw_create. */
+int32_t rsys_search_adamw_step(void* h, float lr, float clip, float* norm_out, int32_t* skipped_out);
+int32_t rsys_search_adamw_state_get(void* h, const char* name, float* exp_avg, float* exp_avg_sq, int64_t n, int32_t* step);
+int32_t rsys_search_adamw_state_set(void* h, const char* name, const float* exp_avg, const float* exp_avg_sq, int64_t n, int32_t step);
+/* generate_embeddings (train.py:346-371): out [V_m][Q] = E_m Wenc^T ("search.{m}"), fp32 arithmetic in both dtypes.  "temperature" is
+ * the raw logit_scale parameter (rsys_search_param_get), not its exponential. */
+int32_t rsys_search_export(void* h, float* out);
+/* Serving (beyond the reference, which has no serving code for this model; parity is against the numpy restatement only): for n_queries
+ * query embeddings x [n_queries][Q], log_softmax over the medium's items of the factored logits (W is not needed), and per query the k
+ * best items by descending log-probability, ties by ascending id: ids_out / logp_out [n_queries][k].  1 <= n_queries <= max_batch,
+ * 1 <= k <= min(V_m, 8192); a non-finite x is an ARG error (checked on the host).  Changes no model state. */
+int32_t rsys_search_topk(void* h, const float* x, int32_t n_queries, int32_t k, int32_t* ids_out, float* logp_out);
+
 /* ---- Watch-order counts (Training/media_relations.jl get_watch_order, :174-197).  A handle of its own, passed as an opaque
  * void*: one row band [row0, row1) of the V x V int32 matrix W, W[a][b] = the number of users whose projected history has a before b
  * (the reference's watch_order[a+1, b+1]).  Counts are exact integer adds, so every result is bitwise reproducible and independent of

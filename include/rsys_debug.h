@@ -97,6 +97,9 @@ int32_t rsys_op_rerank(int32_t n, int32_t partialk, const float* pen, const floa
  * order of each slot), "scores" f32 [n_q][n] (x), "dldx" f32 [n_q][n] (d batch loss / dx), "dropout_mask" uint8 [rows][F] (1 = kept, the
  * mask of every gathered row: rows = 2 n_q n in training, [source copies | targets], slot-major; all ones without dropout) */
 int32_t rsys_sim_debug_get(void* h, const char* name, void* out, int64_t n);
+/* the last rsys_search_forward_backward / rsys_search_topk call of a search handle (host arrays, f32): "lse" [B] (the per-row logsumexp of
+ * the logits), "dP" [B][D] (d loss / d (x Wenc) in fp32, before the bf16 mode rounds it for dWenc; training calls only) */
+int32_t rsys_search_debug_get(void* h, const char* name, float* out, int64_t n);
 /* embedding-gradient scatter of the backward (nn.Embedding backward, model.py:21) on caller-provided device buffers:
  * gE[id'] += sum over tokens n of gx0[n*ldx .. +D) with id' = m_matchedid[n] (-1 -> row V); matchedid = the raw ids the
  * token index is built from (m_matchedid differs from it only where it is -1).  One writer per table row, fixed summation

@@ -485,6 +485,65 @@ function sim_pair_ranks(s::SimModel, sources, targets)
     out[1:off[end]], off
 end
 
+# Search model (Training/search/train.py; DESIGN.md §4t): its own handle per medium.  Labels are 0-based medium-local ids; Julia
+# column-major: features D x V_m, queries Q x B, "encoder.weight" D x Q, the export Q x V_m.
+mutable struct SearchModel
+    h::Ptr{Cvoid}
+end
+function SearchModel(V::Integer, D::Integer, Q::Integer; dtype = DTYPE_BF16, max_batch = 1024, device = 0)
+    r = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:rsys_search_create, LIB), Int32, (Int64, Int32, Int32, Int32, Int32, Int32, Ref{Ptr{Cvoid}}),
+                V, D, Q, dtype, max_batch, device, r))
+    s = SearchModel(r[])
+    finalizer(x -> ccall((:rsys_search_destroy, LIB), Int32, (Ptr{Cvoid},), x.h), s)
+    s
+end
+search_param_get(s::SearchModel, name::AbstractString, out::Array{Float32}) =
+    check(ccall((:rsys_search_param_get, LIB), Int32, (Ptr{Cvoid}, Cstring, Ptr{Float32}, Int64), s.h, name, out, length(out)))
+search_param_set!(s::SearchModel, name::AbstractString, x::Array{Float32}) =
+    check(ccall((:rsys_search_param_set, LIB), Int32, (Ptr{Cvoid}, Cstring, Ptr{Float32}, Int64), s.h, name, x, length(x)))
+search_grad_get(s::SearchModel, name::AbstractString, out::Array{Float32}) =
+    check(ccall((:rsys_search_grad_get, LIB), Int32, (Ptr{Cvoid}, Cstring, Ptr{Float32}, Int64), s.h, name, out, length(out)))
+search_zero_grad!(s::SearchModel) = check(ccall((:rsys_search_zero_grad, LIB), Int32, (Ptr{Cvoid},), s.h))
+search_features_set!(s::SearchModel, f::Matrix{Float32}) =
+    check(ccall((:rsys_search_features_set, LIB), Int32, (Ptr{Cvoid}, Ptr{Float32}, Int64, Int64), s.h, f, size(f, 2), size(f, 1)))
+search_features_from_model!(s::SearchModel, m::Model, medium::Integer) =
+    check(ccall((:rsys_search_features_from_model, LIB), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Int32), s.h, m.h, medium))
+# returns (loss, sum of the weights)
+function search_forward_backward!(s::SearchModel, queries::Matrix{Float32}, labels, weight; evaluate = false)
+    y = Vector{Int32}(labels); w = Vector{Float32}(weight); loss = Ref{Float32}(0); wsum = Ref{Float32}(0)
+    GC.@preserve queries y w check(ccall((:rsys_search_forward_backward, LIB), Int32,
+        (Ptr{Cvoid}, Ptr{Float32}, Ptr{Int32}, Ptr{Float32}, Int32, Int32, Ref{Float32}, Ref{Float32}),
+        s.h, queries, y, w, length(y), evaluate, loss, wsum))
+    loss[], wsum[]
+end
+search_adamw_create!(s::SearchModel; beta1 = 0.9f0, beta2 = 0.999f0, eps = 1f-8, weight_decay = 0.1f0) =
+    check(ccall((:rsys_search_adamw_create, LIB), Int32, (Ptr{Cvoid}, Float32, Float32, Float32, Float32), s.h, beta1, beta2, eps, weight_decay))
+function search_adamw_step!(s::SearchModel; lr = 3f-4, clip = 1f0)
+    norm = Ref{Float32}(0); skipped = Ref{Int32}(0)
+    check(ccall((:rsys_search_adamw_step, LIB), Int32, (Ptr{Cvoid}, Float32, Float32, Ref{Float32}, Ref{Int32}), s.h, lr, clip, norm, skipped))
+    norm[], skipped[] != 0
+end
+function search_adamw_state_get(s::SearchModel, name::AbstractString, n::Integer)
+    m = zeros(Float32, n); v = zeros(Float32, n); step = Ref{Int32}(0)
+    check(ccall((:rsys_search_adamw_state_get, LIB), Int32, (Ptr{Cvoid}, Cstring, Ptr{Float32}, Ptr{Float32}, Int64, Ref{Int32}),
+                s.h, name, m, v, n, step))
+    m, v, step[]
+end
+search_adamw_state_set!(s::SearchModel, name::AbstractString, m::Array{Float32}, v::Array{Float32}, step::Integer) =
+    check(ccall((:rsys_search_adamw_state_set, LIB), Int32, (Ptr{Cvoid}, Cstring, Ptr{Float32}, Ptr{Float32}, Int64, Int32),
+                s.h, name, m, v, length(m), step))
+# "search.{m}": out is Q x V_m
+search_export!(s::SearchModel, out::Matrix{Float32}) = check(ccall((:rsys_search_export, LIB), Int32, (Ptr{Cvoid}, Ptr{Float32}), s.h, out))
+# queries Q x n; returns (0-based ids, log-probabilities), each k x n, best first, ties by ascending id
+function search_topk(s::SearchModel, queries::Matrix{Float32}, k::Integer)
+    n = size(queries, 2)
+    ids = Matrix{Int32}(undef, k, n); lp = Matrix{Float32}(undef, k, n)
+    GC.@preserve queries ids lp check(ccall((:rsys_search_topk, LIB), Int32, (Ptr{Cvoid}, Ptr{Float32}, Int32, Int32, Ptr{Int32}, Ptr{Float32}),
+        s.h, queries, n, k, ids, lp))
+    ids, lp
+end
+
 # Watch-order counts (Training/media_relations.jl get_watch_order; DESIGN.md §4q): its own handle over the row band [row0, row1) of W.
 # Ids are 0-based; W[a][b] = users who watched a before b.
 mutable struct WatchOrder

@@ -102,6 +102,22 @@ _SIGS = [
     ("rsys_sim_pair_ranks", C.c_int32, [_P, C.c_int32, _P, _P, _P, _P]),
     ("rsys_sim_pair_scores", C.c_int32, [_P, C.c_int32, _P, _P]),
     ("rsys_sim_debug_get", C.c_int32, [_P, C.c_char_p, _P, C.c_int64]),
+    ("rsys_search_create", C.c_int32, [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(_P)]),
+    ("rsys_search_destroy", C.c_int32, [_P]),
+    ("rsys_search_param_get", C.c_int32, [_P, C.c_char_p, _P, C.c_int64]),
+    ("rsys_search_param_set", C.c_int32, [_P, C.c_char_p, _P, C.c_int64]),
+    ("rsys_search_grad_get", C.c_int32, [_P, C.c_char_p, _P, C.c_int64]),
+    ("rsys_search_zero_grad", C.c_int32, [_P]),
+    ("rsys_search_features_set", C.c_int32, [_P, _P, C.c_int64, C.c_int64]),
+    ("rsys_search_features_from_model", C.c_int32, [_P, _P, C.c_int32]),
+    ("rsys_search_forward_backward", C.c_int32, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    ("rsys_search_adamw_create", C.c_int32, [_P, C.c_float, C.c_float, C.c_float, C.c_float]),
+    ("rsys_search_adamw_step", C.c_int32, [_P, C.c_float, C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_int32)]),
+    ("rsys_search_adamw_state_get", C.c_int32, [_P, C.c_char_p, _P, _P, C.c_int64, C.POINTER(C.c_int32)]),
+    ("rsys_search_adamw_state_set", C.c_int32, [_P, C.c_char_p, _P, _P, C.c_int64, C.c_int32]),
+    ("rsys_search_export", C.c_int32, [_P, _P]),
+    ("rsys_search_topk", C.c_int32, [_P, _P, C.c_int32, C.c_int32, _P, _P]),
+    ("rsys_search_debug_get", C.c_int32, [_P, C.c_char_p, _P, C.c_int64]),
     ("rsys_watch_order_create", C.c_int32, [C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.POINTER(_P)]),
     ("rsys_watch_order_destroy", C.c_int32, [_P]),
     ("rsys_watch_order_add", C.c_int32, [_P, C.c_int64, _P, _P]),

@@ -320,6 +320,8 @@ int model_item_table(Model* m, float* out, int64_t n);
 int model_item_table_device(Model* m, int medium, const float** rows, int64_t* Vm, int* D);
 // similarity.hip: frozen features of an item-similarity handle from device rows [V][F] on `device`
 int sim_features_from_device(void* h, const float* rows, int64_t V, int64_t F, int device);
+// search.hip: the same for a search-model handle (rows [V_m][D])
+int search_features_from_device(void* h, const float* rows, int64_t V, int64_t D, int device);
 int model_materialise_trunk_output(Model* m);   // dense trunk output of the resident forward in m->out (a training pass computes it at the selected tokens only)
 int model_finalize_grads(Model* m);
 bool model_finalize_splittable(const Model* m);
