@@ -8,6 +8,7 @@
 #include <sstream>
 
 #include "comm.hpp"
+#include "encoder_handle.hpp"
 #include "model.hpp"
 
 namespace rsys {
@@ -159,18 +160,16 @@ int32_t rsys_retrieve_topk(rsys_model* h, int32_t medium, const float* queries, 
   return model_retrieve_topk(h->m, medium, queries, n_queries, group, n_groups, prior, excl_offsets, excl_ids, k, ids_out, scores_out,
                              counts_out);
 }
-// the fp32 item-table rows of `medium` handed to a feature sink on the model's device (the item-similarity and the search handles)
-static int32_t features_from_model(void* sink, rsys_model* h, int32_t medium, int (*take)(void*, const float*, int64_t, int64_t, int)) {
+// the fp32 item-table rows of `medium` become the frozen features of an item-similarity or search handle on the model's device
+static int32_t features_from_model(void* sink, rsys_model* h, int32_t medium) {
   CHECK_HANDLE(h);
   if (sink == nullptr) { set_error("null handle"); return RSYS_ERR_ARG; }
   const float* rows = nullptr; int64_t Vm = 0; int D = 0;
   RC(model_item_table_device(h->m, medium, &rows, &Vm, &D));
-  return take(sink, rows, Vm, D, h->m->device);
+  return enc_features_from_device((EncoderCore*)sink, rows, Vm, D, h->m->device);
 }
-int32_t rsys_sim_features_from_model(void* sim, rsys_model* h, int32_t medium) { return features_from_model(sim, h, medium, sim_features_from_device); }
-int32_t rsys_search_features_from_model(void* search, rsys_model* h, int32_t medium) {
-  return features_from_model(search, h, medium, search_features_from_device);
-}
+int32_t rsys_sim_features_from_model(void* sim, rsys_model* h, int32_t medium) { return features_from_model(sim, h, medium); }
+int32_t rsys_search_features_from_model(void* search, rsys_model* h, int32_t medium) { return features_from_model(search, h, medium); }
 int32_t rsys_retrieve_target_rank(rsys_model* h, int32_t medium, const float* queries, int64_t n_queries, const int32_t* targets,
                                   const int64_t* excl_offsets, const int32_t* excl_ids, int32_t* rank_out, float* logp_out) {
   CHECK_HANDLE(h);

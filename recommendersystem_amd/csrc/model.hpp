@@ -318,10 +318,6 @@ int model_infer_adapters(Model* m, int task, const int32_t* row_adapter, const i
 int model_item_table(Model* m, float* out, int64_t n);
 // the fp32 item table rows [V_m][D] of `medium` on the model's device (rsys_sim_features_from_model); the model's stream is idle on return
 int model_item_table_device(Model* m, int medium, const float** rows, int64_t* Vm, int* D);
-// similarity.hip: frozen features of an item-similarity handle from device rows [V][F] on `device`
-int sim_features_from_device(void* h, const float* rows, int64_t V, int64_t F, int device);
-// search.hip: the same for a search-model handle (rows [V_m][D])
-int search_features_from_device(void* h, const float* rows, int64_t V, int64_t D, int device);
 int model_materialise_trunk_output(Model* m);   // dense trunk output of the resident forward in m->out (a training pass computes it at the selected tokens only)
 int model_finalize_grads(Model* m);
 bool model_finalize_splittable(const Model* m);
@@ -379,13 +375,12 @@ void retrieve_eval_free(Model* m);
 int op_target_rank(const float* scores, int64_t ld, int32_t rows, int32_t V, const int32_t* targets, int32_t* rank_out);
 // similarity_metrics.hip: catalogue ranks of the targets of item-similarity test sources (rsys_sim_pair_ranks) over a handle's fp32
 // export [V][E] and test-mask bit rows, the masked score rows alone (rsys_sim_pair_scores) and the count alone (rsys_op_pair_ranks).
-// PairWs: one device buffer, grown on demand, owned by the caller
-struct PairWs { void* buf = nullptr; size_t bytes = 0; };
-void pair_ws_free(PairWs* ws);
+// ws: the caller's workspace (encoder_handle.hpp), grown on demand
+struct DevScratch;
 int pair_ranks_run(const float* exp32, int V, int E, const unsigned* tmask, long long tmw, int32_t n_src, const int32_t* sources,
-                   const int64_t* off, const int32_t* tids, int32_t* ranks_out, PairWs* ws, hipStream_t s);
+                   const int64_t* off, const int32_t* tids, int32_t* ranks_out, DevScratch* ws, hipStream_t s);
 int pair_scores_run(const float* exp32, int V, int E, const unsigned* tmask, long long tmw, int32_t n_src, const int32_t* sources,
-                    float* out, PairWs* ws, hipStream_t s);
+                    float* out, DevScratch* ws, hipStream_t s);
 int op_pair_ranks(const float* scores, int64_t ld, int32_t rows, int32_t V, const int32_t* self, const int64_t* off, const int32_t* tids,
                   int32_t* ranks_out);
 int optimizer_step(Optimizer* o, float lr_factor, float clip, float grad_div);

@@ -13,6 +13,7 @@
 // NaN becomes key 0 in the combine pass, so the rest of the pipeline is retrieve.hip's, unchanged.
 #include <cmath>
 
+#include "encoder_handle.hpp"
 #include "model_internal.hpp"
 
 namespace rsys {
@@ -201,21 +202,11 @@ __global__ void __launch_bounds__(RR_THREADS) relation_mask_kernel(float* sc, in
 
 #define RR_LAUNCH_CHECK() HIP_CHECK(hipGetLastError())
 
-struct Carve {
-  char* p; size_t off = 0;
-  template <typename X> X* take(size_t count) {
-    X* r = (X*)(p ? p + off : nullptr);
-    off += (count * sizeof(X) + 255) / 256 * 256;
-    return r;
-  }
-};
-
 }  // namespace
 
 struct RetrievalTables {
   MediumTables t[2];
-  void* ws = nullptr;   // the request's device workspace, grown on demand
-  size_t ws_bytes = 0;
+  DevScratch ws;        // the request's device workspace
   std::vector<uint32_t> mark;    // host: last-status rule over [0, V0 + V1) (stamps; status)
   std::vector<int32_t> status;
   uint32_t tick = 0;
@@ -233,7 +224,7 @@ void retrieve_tables_free(Model* m) {
     for (Csc& c : t.rel) { dfree(c.colptr); dfree(c.rowval); }
     dfree(t.dep_rows); dfree(t.emb); dfree(t.cross); dfree(t.released);
   }
-  if (R->ws) hipFree(R->ws);
+  R->ws.release();
   delete R;
   m->rtab = nullptr;
 }
@@ -440,14 +431,8 @@ int model_retrieve_request(Model* m, int medium, const float* queries, int64_t n
   float *S, *X; int64_t* d_soff; int32_t *d_smed, *d_sids, *d_eq, *d_eid, *d_ef, *d_qg; unsigned* planes;
   Carve probe{nullptr};
   layout(probe, &S, &X, &d_soff, &d_smed, &d_sids, &d_eq, &d_eid, &d_ef, &d_qg, &planes);
-  if (R->ws_bytes < probe.off) {
-    HIP_CHECK(hipStreamSynchronize(s));
-    if (R->ws) HIP_CHECK(hipFree(R->ws));
-    R->ws = nullptr; R->ws_bytes = 0;
-    HIP_CHECK(hipMalloc(&R->ws, probe.off));
-    R->ws_bytes = probe.off;
-  }
-  Carve c{(char*)R->ws};
+  if (int rc = R->ws.reserve(probe.off, s)) return rc;
+  Carve c{(char*)R->ws.p};
   layout(c, &S, &X, &d_soff, &d_smed, &d_sids, &d_eq, &d_eid, &d_ef, &d_qg, &planes);
   std::vector<int64_t> soff(sel_off ? sel_off : nullptr, sel_off ? sel_off + ng + 1 : nullptr);
   if (!sel_off) soff.assign((size_t)ng + 1, 0);

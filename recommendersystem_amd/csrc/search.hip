@@ -1,5 +1,6 @@
 // Search model on the device (Training/search/train.py:76-130: `SearchModel.forward`, the AdamW step of `train_epoch` and
-// `generate_embeddings`), one handle per medium (rsys_search_*), independent of rsys_model.  The reference forms W = E Wenc^T [V][Q] every
+// `generate_embeddings`), one handle per medium (rsys_search_*), independent of rsys_model, on the core of encoder_handle.hpp (parameters,
+// AdamW, the feature table, the ordered split-K product).  The reference forms W = E Wenc^T [V][Q] every
 // step and soft-maxes x W^T over both media; every label of a batch lies in the handle's medium, so the other medium's columns carry
 // neither loss nor gradient, and x W^T = (x Wenc) E_m^T.  The pipeline:
 //   project    P = x Wenc [B][D] through launch_gemm (bf16 mode: bf16 operands, fp32 accumulation, bf16 output)
@@ -20,13 +21,11 @@
 #include <string>
 #include <vector>
 
-#include "model.hpp"
+#include "encoder_handle.hpp"
 
 namespace rsys {
 
 namespace {
-
-#define SEARCH_RC(expr) do { int _rc = (expr); if (_rc != RSYS_OK) return _rc; } while (0)
 
 constexpr int SEARCH_MAXB = 4096;
 constexpr int SEARCH_MAXSPLIT = 64;        // column splits of a row in the statistics kernel
@@ -180,25 +179,12 @@ __global__ void __launch_bounds__(256) search_logp_kernel(float* __restrict__ z,
   *p = *p * expf(*ls) - lse[row];
 }
 
-inline unsigned search_grid(long long work, int per_block = 256, long long cap = 8192) {
-  return (unsigned)std::max<long long>(1, std::min<long long>((work + per_block - 1) / per_block, cap));
-}
-
 }  // namespace
 
 // ------------------------------------------------------------------ the handle
-struct SearchModel {
-  int device = 0, V = 0, Vpad = 0, D = 0, Q = 0, dtype = 0, maxb = 0, bcap = 0;
-  hipStream_t stream = nullptr;
-  long long nflat = 0;                              // [Wenc (Q x D) | logit_scale | 3 pad]
-  float *feat = nullptr;                            // E_m [Vpad][D] fp32, rows >= V zero
-  bf16* feat16 = nullptr;                           // bf16 copy (bf16 mode)
-  float *P = nullptr, *G = nullptr, *M1 = nullptr, *M2 = nullptr;
-  bf16* Wsh = nullptr;                              // bf16 copy of Wenc (bf16 mode)
-  bool has_features = false, has_adam = false;
-  float b1 = 0.9f, b2 = 0.999f, eps = 1e-8f, wd = 0.1f;
-  int adam_step = 0;
-  float *sumsq = nullptr, *sq_part = nullptr;
+struct SearchModel : EncoderCore {
+  int V = 0, Vpad = 0, D = 0, Q = 0, maxb = 0, bcap = 0;   // E_m [Vpad][D] (rows >= V zero), Wenc [Q][D]
+  bf16* feat16 = nullptr;                           // bf16 copy of E_m (bf16 mode)
   float* X32 = nullptr; void* Xt = nullptr;         // queries [bcap][Q]: the fp32 upload and the operand (the same buffer in fp32 mode)
   void* Pt = nullptr;                               // x Wenc [bcap][D] in the operand dtype
   float* z = nullptr;                               // scores [bcap][Vpad] fp32
@@ -206,107 +192,51 @@ struct SearchModel {
   float* dP = nullptr; void* dPt = nullptr;         // [bcap][D]: fp32 sum, operand copy (bf16 mode)
   float4* part = nullptr;
   int* labels = nullptr; float *wn = nullptr, *lse = nullptr, *loss = nullptr;
-  float* slab = nullptr; long long slab_floats = 0;
   float* exp32 = nullptr;                           // export [V][Q], allocated by the first export
-  void* tws = nullptr; size_t tws_bytes = 0;        // top-k workspace, grown on demand
+  DevScratch tws;                                   // top-k workspace
   int last_B = 0; bool last_grads = false;
   int g_rows = 0;                                   // rows of Gs an earlier call wrote (the rest is zero)
   std::vector<float> h_wn;                          // host source of a call's upload, alive until its closing wait
-  std::vector<void*> allocs;
-  bool bf16_mode() const { return dtype == RSYS_DTYPE_BF16; }
-  float* ls() const { return P + (long long)Q * D; }
+  void free_own() override {
+    tws.release();
+    if (exp32) hipFree(exp32);
+  }
+  int features_ready() override {                   // the bf16 operand copy of the table
+    if (bf16_mode()) ENC_RC(launch_cast<bf16>(feat, feat16, (long long)Vpad * D, stream));
+    return EncoderCore::features_ready();
+  }
 };
 
-static int search_alloc(SearchModel* h, void** p, size_t bytes) {
-  bytes = std::max<size_t>(256, (bytes + 255) / 256 * 256);
-  HIP_CHECK(hipMalloc(p, bytes));
-  HIP_CHECK(hipMemset(*p, 0, bytes));
-  h->allocs.push_back(*p);
-  return RSYS_OK;
-}
-#define SEARCH_ALLOC(ptr, bytes) SEARCH_RC(search_alloc(h, (void**)&(ptr), (size_t)(bytes)))
-
-static void search_free(SearchModel* h) {
-  if (!h) return;
-  hipSetDevice(h->device);
-  if (h->stream) hipStreamSynchronize(h->stream);
-  for (void* p : h->allocs) hipFree(p);
-  if (h->slab) hipFree(h->slab);
-  if (h->exp32) hipFree(h->exp32);
-  if (h->tws) hipFree(h->tws);
-  if (h->stream) hipStreamDestroy(h->stream);
-  delete h;
-}
-
-static int search_create(int64_t V, int32_t D, int32_t Q, int32_t dtype, int32_t maxb, int32_t device, SearchModel** out) {
+static int search_create(int64_t V, int32_t D, int32_t Q, int32_t dtype, int32_t maxb, int32_t device, void** out) {
   ARG_CHECK(out, "rsys_search_create: null output");
   ARG_CHECK(V >= 1 && V <= (1 << 24), "rsys_search_create: 1 <= V_m <= 2^24");
   ARG_CHECK(D >= 64 && D % 64 == 0 && D <= 8192, "rsys_search_create: D must be a multiple of 64 in [64, 8192] (2048: the transformer's embed_dim)");
   ARG_CHECK(Q >= 64 && Q % 64 == 0 && Q <= 16384, "rsys_search_create: Q must be a multiple of 64 in [64, 16384] (3072: the query embeddings)");
-  ARG_CHECK(dtype == RSYS_DTYPE_FP32 || dtype == RSYS_DTYPE_BF16, "rsys_search_create: dtype must be RSYS_DTYPE_FP32 or RSYS_DTYPE_BF16");
   ARG_CHECK(maxb >= 1 && maxb <= SEARCH_MAXB, "rsys_search_create: 1 <= max_batch <= 4096");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { set_error("rsys_search_create: no HIP device visible"); return RSYS_ERR_HIP; }
-  ARG_CHECK(device >= 0 && device < ndev, "rsys_search_create: device index out of range");
-  HIP_CHECK(hipSetDevice(device));
+  ENC_RC(enc_check_device("rsys_search", dtype, device));
   SearchModel* h = new SearchModel();
-  h->device = device; h->V = (int)V; h->Vpad = (int)((V + 255) / 256 * 256); h->D = D; h->Q = Q; h->dtype = dtype; h->maxb = maxb;
+  h->V = (int)V; h->Vpad = (int)((V + 255) / 256 * 256); h->D = D; h->Q = Q; h->maxb = maxb;
   h->bcap = (maxb + 255) / 256 * 256;
-  h->nflat = (long long)Q * D + 4;
+  h->api = "rsys_search"; h->wname = "encoder.weight"; h->device = device; h->dtype = dtype;
+  h->frows = V; h->fpad = h->Vpad; h->fcols = h->wcols = D; h->wrows = Q;
   const size_t tsz = h->bf16_mode() ? 2 : 4;
   const int rc = [&]() -> int {
-    HIP_CHECK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-    SEARCH_ALLOC(h->feat, (size_t)h->Vpad * D * 4);
-    if (h->bf16_mode()) SEARCH_ALLOC(h->feat16, (size_t)h->Vpad * D * 2);
-    SEARCH_ALLOC(h->P, h->nflat * 4); SEARCH_ALLOC(h->G, h->nflat * 4); SEARCH_ALLOC(h->M1, h->nflat * 4); SEARCH_ALLOC(h->M2, h->nflat * 4);
-    if (h->bf16_mode()) SEARCH_ALLOC(h->Wsh, h->nflat * 2);
-    SEARCH_ALLOC(h->sumsq, 16); SEARCH_ALLOC(h->sq_part, (size_t)sumsq_parts() * 4);
-    SEARCH_ALLOC(h->X32, (size_t)h->bcap * Q * 4);
-    if (h->bf16_mode()) SEARCH_ALLOC(h->Xt, (size_t)h->bcap * Q * 2); else h->Xt = h->X32;
-    SEARCH_ALLOC(h->Pt, (size_t)h->bcap * D * tsz);
-    SEARCH_ALLOC(h->z, (size_t)h->bcap * h->Vpad * 4);
-    SEARCH_ALLOC(h->Gs, (size_t)h->bcap * h->Vpad * tsz);
-    SEARCH_ALLOC(h->dP, (size_t)h->bcap * D * 4);
-    if (h->bf16_mode()) SEARCH_ALLOC(h->dPt, (size_t)h->bcap * D * 2); else h->dPt = h->dP;
-    SEARCH_ALLOC(h->part, (size_t)h->bcap * SEARCH_MAXSPLIT * sizeof(float4));
-    SEARCH_ALLOC(h->labels, h->bcap * 4); SEARCH_ALLOC(h->wn, h->bcap * 4); SEARCH_ALLOC(h->lse, h->bcap * 4); SEARCH_ALLOC(h->loss, 16);
-    const float ls = 1.f;   // logit_scale = 1.0 (train.py:85); Wenc stays zero until set
-    HIP_CHECK(hipMemcpy(h->ls(), &ls, 4, hipMemcpyHostToDevice));
+    ENC_RC(enc_init(h, 1.f));   // logit_scale = 1.0 (train.py:85)
+    if (h->bf16_mode()) ENC_ALLOC(h->feat16, (size_t)h->Vpad * D * 2);
+    ENC_ALLOC(h->X32, (size_t)h->bcap * Q * 4);
+    if (h->bf16_mode()) ENC_ALLOC(h->Xt, (size_t)h->bcap * Q * 2); else h->Xt = h->X32;
+    ENC_ALLOC(h->Pt, (size_t)h->bcap * D * tsz);
+    ENC_ALLOC(h->z, (size_t)h->bcap * h->Vpad * 4);
+    ENC_ALLOC(h->Gs, (size_t)h->bcap * h->Vpad * tsz);
+    ENC_ALLOC(h->dP, (size_t)h->bcap * D * 4);
+    if (h->bf16_mode()) ENC_ALLOC(h->dPt, (size_t)h->bcap * D * 2); else h->dPt = h->dP;
+    ENC_ALLOC(h->part, (size_t)h->bcap * SEARCH_MAXSPLIT * sizeof(float4));
+    ENC_ALLOC(h->labels, h->bcap * 4); ENC_ALLOC(h->wn, h->bcap * 4); ENC_ALLOC(h->lse, h->bcap * 4); ENC_ALLOC(h->loss, 16);
     return RSYS_OK;
   }();
-  if (rc != RSYS_OK) { search_free(h); return rc; }
-  *out = h;
+  if (rc != RSYS_OK) { enc_free(h); return rc; }
+  *out = (EncoderCore*)h;
   return RSYS_OK;
-}
-
-// the bf16 operand copy of the feature table after feat changed; the stream is idle on return
-static int search_features_ready(SearchModel* h) {
-  if (h->bf16_mode()) SEARCH_RC(launch_cast<bf16>(h->feat, h->feat16, (long long)h->Vpad * h->D, h->stream));
-  HIP_CHECK(hipStreamSynchronize(h->stream));
-  h->has_features = true;
-  return RSYS_OK;
-}
-
-static int search_slab(SearchModel* h, long long need) {
-  if (need <= h->slab_floats) return RSYS_OK;
-  HIP_CHECK(hipStreamSynchronize(h->stream));
-  if (h->slab) HIP_CHECK(hipFree(h->slab));
-  h->slab = nullptr; h->slab_floats = 0;
-  HIP_CHECK(hipMalloc((void**)&h->slab, (size_t)need * 4));
-  h->slab_floats = need;
-  return RSYS_OK;
-}
-
-// A product whose sum must have a fixed order (EPI_ATOMIC into fp32 C): with a slab in its parameters launch_gemm stays off the
-// split-K forms that add partial tiles with float atomics (gemm8p's mixed-layout form, gemm4k), and every K split stores its partial
-// tile into the slab, summed in split order afterwards.  The slab is grown to what the routed kernel needs.
-template <typename T>
-static int search_ordered_gemm(SearchModel* h, GemmParams p, bool a_km, bool b_km) {
-  SEARCH_RC(search_slab(h, 256));
-  p.slab = h->slab; p.slab_floats = h->slab_floats;
-  SEARCH_RC(search_slab(h, std::max<long long>(256, gemm_slab_need<T>(p, false, false, a_km, b_km))));
-  p.slab = h->slab; p.slab_floats = h->slab_floats;
-  return launch_gemm<T>(p, false, false, a_km, b_km, h->stream);
 }
 
 // rows [0, B) of x uploaded, the operand copy made, rows [B, Bpad) of the operand zero
@@ -315,7 +245,7 @@ static int search_upload_x(SearchModel* h, const float* x, int B, int Bpad) {
   hipStream_t s = h->stream;
   const long long n = (long long)B * h->Q;
   HIP_CHECK(hipMemcpyAsync(h->X32, x, (size_t)n * 4, hipMemcpyHostToDevice, s));
-  if (h->bf16_mode()) SEARCH_RC(launch_cast<bf16>(h->X32, (bf16*)h->Xt, n, s));
+  if (h->bf16_mode()) ENC_RC(launch_cast<bf16>(h->X32, (bf16*)h->Xt, n, s));
   if (Bpad > B) HIP_CHECK(hipMemsetAsync((T*)h->Xt + n, 0, (size_t)(Bpad - B) * h->Q * sizeof(T), s));
   return RSYS_OK;
 }
@@ -331,7 +261,7 @@ static int search_scores(SearchModel* h, int B, int Bpad, bool with_loss, bool g
     p.B = bf ? (const void*)h->Wsh : (const void*)h->P; p.ldb = h->D;
     p.C = h->Pt; p.ldc = h->D; p.c_f32 = bf ? 0 : 1;
     p.M = Bpad; p.N = h->D; p.K = h->Q; p.epi = EPI_STORE; p.alpha = 1.f; p.splitk = 1;
-    SEARCH_RC(launch_gemm<T>(p, false, false, false, true, s));
+    ENC_RC(launch_gemm<T>(p, false, false, false, true, s));
   }
   {
     GemmParams p{};   // z[m][n] = sum_k P[m][k] E[n][k]
@@ -339,7 +269,7 @@ static int search_scores(SearchModel* h, int B, int Bpad, bool with_loss, bool g
     p.B = bf ? (const void*)h->feat16 : (const void*)h->feat; p.ldb = h->D;
     p.C = h->z; p.ldc = h->Vpad; p.c_f32 = 1;
     p.M = Bpad; p.N = h->Vpad; p.K = h->D; p.epi = EPI_STORE; p.alpha = 1.f; p.splitk = 1;
-    SEARCH_RC(launch_gemm<T>(p, false, false, false, false, s));
+    ENC_RC(launch_gemm<T>(p, false, false, false, false, s));
   }
   // enough workgroups to fill the chip at small B, at least 1024 columns each
   int nsplit = std::max(1, std::min(SEARCH_MAXSPLIT, std::min((2048 + B - 1) / B, h->V / 1024)));
@@ -348,7 +278,7 @@ static int search_scores(SearchModel* h, int B, int Bpad, bool with_loss, bool g
   search_stats_kernel<<<dim3(nsplit, B), 256, 0, s>>>(h->z, h->Vpad, h->V, cps, h->ls(), h->part);
   HIP_CHECK(hipGetLastError());
   search_finish_kernel<<<1, 1024, 0, s>>>(h->part, nsplit, B, h->z, h->Vpad, with_loss ? h->labels : nullptr, h->wn, h->ls(), h->lse, h->loss,
-                                          h->G + (long long)h->Q * h->D, grads ? 1 : 0);
+                                          h->G + h->nw(), grads ? 1 : 0);
   HIP_CHECK(hipGetLastError());
   if (nsplit_out) *nsplit_out = nsplit;
   return RSYS_OK;
@@ -375,9 +305,9 @@ static int search_backward(SearchModel* h, int B, int Bpad) {
     const long long tiles = (long long)((Bpad + 127) / 128) * ((h->D + 127) / 128);
     const long long sk = std::min<long long>(64, std::min<long long>(h->Vpad / 2048, std::max<long long>(1, 2048 / tiles)));
     p.splitk = sk >= 8 ? (int)(sk / 8 * 8) : 1;
-    SEARCH_RC(search_ordered_gemm<T>(h, p, false, true));
+    ENC_RC(enc_ordered_gemm<T>(h, p, false, true));
   }
-  search_scale_kernel<T><<<search_grid((long long)Bpad * h->D / 4), 256, 0, s>>>(h->dP, bf ? (T*)h->dPt : (T*)nullptr, (long long)Bpad * h->D / 4,
+  search_scale_kernel<T><<<grid_for((long long)Bpad * h->D / 4), 256, 0, s>>>(h->dP, bf ? (T*)h->dPt : (T*)nullptr, (long long)Bpad * h->D / 4,
                                                                                 h->ls());
   HIP_CHECK(hipGetLastError());
   {
@@ -386,7 +316,7 @@ static int search_backward(SearchModel* h, int B, int Bpad) {
     p.B = h->dPt; p.ldb = h->D;
     p.C = h->G; p.ldc = h->D; p.c_f32 = 1;
     p.M = h->Q; p.N = h->D; p.K = Bpad; p.epi = EPI_ATOMIC; p.alpha = 1.f; p.splitk = 1;
-    SEARCH_RC(search_ordered_gemm<T>(h, p, true, true));
+    ENC_RC(enc_ordered_gemm<T>(h, p, true, true));
   }
   return RSYS_OK;
 }
@@ -412,13 +342,13 @@ static int search_forward_backward(SearchModel* h, const float* x, const int32_t
   HIP_CHECK(hipMemcpyAsync(h->labels, labels, (size_t)B * 4, hipMemcpyHostToDevice, s));
   HIP_CHECK(hipMemcpyAsync(h->wn, h->h_wn.data(), (size_t)B * 4, hipMemcpyHostToDevice, s));
   if (h->bf16_mode()) {
-    SEARCH_RC(search_upload_x<bf16>(h, x, B, Bpad));
-    SEARCH_RC(search_scores<bf16>(h, B, Bpad, true, grads, nullptr));
-    if (grads) SEARCH_RC(search_backward<bf16>(h, B, Bpad));
+    ENC_RC(search_upload_x<bf16>(h, x, B, Bpad));
+    ENC_RC(search_scores<bf16>(h, B, Bpad, true, grads, nullptr));
+    if (grads) ENC_RC(search_backward<bf16>(h, B, Bpad));
   } else {
-    SEARCH_RC(search_upload_x<float>(h, x, B, Bpad));
-    SEARCH_RC(search_scores<float>(h, B, Bpad, true, grads, nullptr));
-    if (grads) SEARCH_RC(search_backward<float>(h, B, Bpad));
+    ENC_RC(search_upload_x<float>(h, x, B, Bpad));
+    ENC_RC(search_scores<float>(h, B, Bpad, true, grads, nullptr));
+    if (grads) ENC_RC(search_backward<float>(h, B, Bpad));
   }
   float l = 0.f;
   HIP_CHECK(hipMemcpyAsync(&l, h->loss, 4, hipMemcpyDeviceToHost, s));
@@ -426,75 +356,6 @@ static int search_forward_backward(SearchModel* h, const float* x, const int32_t
   h->last_B = B; h->last_grads = grads;
   if (loss_out) *loss_out = l;
   if (wsum_out) *wsum_out = (float)W;
-  return RSYS_OK;
-}
-
-// name -> (offset, size) in the flat buffers
-static int search_tensor(SearchModel* h, const char* name, long long* off, long long* size) {
-  ARG_CHECK(name, "rsys_search: null name");
-  if (strcmp(name, "encoder.weight") == 0) { *off = 0; *size = (long long)h->Q * h->D; return RSYS_OK; }
-  if (strcmp(name, "logit_scale") == 0) { *off = (long long)h->Q * h->D; *size = 1; return RSYS_OK; }
-  set_error(std::string("rsys_search: unknown parameter '") + name + "' (trainable: encoder.weight, logit_scale; the frozen table goes "
-            "through rsys_search_features_set)");
-  return RSYS_ERR_ARG;
-}
-
-static int search_param_io(SearchModel* h, const char* name, float* out, const float* in, int64_t n, int grad) {
-  long long off, size;
-  SEARCH_RC(search_tensor(h, name, &off, &size));
-  ARG_CHECK(n == size, "rsys_search: element count does not match the parameter's");
-  HIP_CHECK(hipSetDevice(h->device));
-  HIP_CHECK(hipStreamSynchronize(h->stream));
-  float* base = grad ? h->G : h->P;
-  if (out) HIP_CHECK(hipMemcpy(out, base + off, (size_t)n * 4, hipMemcpyDeviceToHost));
-  if (in) {
-    HIP_CHECK(hipMemcpy(base + off, in, (size_t)n * 4, hipMemcpyHostToDevice));
-    if (h->bf16_mode()) SEARCH_RC(launch_cast<bf16>(h->P, h->Wsh, (long long)h->Q * h->D, h->stream));
-    HIP_CHECK(hipStreamSynchronize(h->stream));
-  }
-  return RSYS_OK;
-}
-
-static int search_adamw_step(SearchModel* h, float lr, float clip, float* norm_out, int32_t* skipped_out) {
-  if (!h->has_adam) { set_error("rsys_search_adamw_step: no optimizer (rsys_search_adamw_create)"); return RSYS_ERR_STATE; }
-  HIP_CHECK(hipSetDevice(h->device));
-  hipStream_t s = h->stream;
-  SEARCH_RC(launch_sumsq(h->G, h->nflat, h->sumsq, h->sq_part, s, true));
-  float ss = 0.f;
-  HIP_CHECK(hipMemcpyAsync(&ss, h->sumsq, 4, hipMemcpyDeviceToHost, s));
-  HIP_CHECK(hipStreamSynchronize(s));
-  const float norm = sqrtf(ss);
-  const bool skip = !std::isfinite(norm);
-  if (norm_out) *norm_out = norm;
-  if (skipped_out) *skipped_out = skip ? 1 : 0;
-  if (skip) {   // GradScaler: no update and no step count; the gradient is cleared as the next zero_grad would
-    HIP_CHECK(hipMemsetAsync(h->G, 0, (size_t)h->nflat * 4, s));
-    HIP_CHECK(hipStreamSynchronize(s));
-    return RSYS_OK;
-  }
-  ++h->adam_step;
-  const long long nd = (long long)h->Q * h->D;
-  if (h->bf16_mode())
-    SEARCH_RC(launch_adamw<bf16>(h->P, h->G, h->M1, h->M2, h->Wsh, nd, h->nflat, lr, h->b1, h->b2, h->eps, h->wd, h->adam_step, h->sumsq, 1.f,
-                                 clip, 1, s));
-  else
-    SEARCH_RC(launch_adamw<float>(h->P, h->G, h->M1, h->M2, (float*)nullptr, nd, h->nflat, lr, h->b1, h->b2, h->eps, h->wd, h->adam_step,
-                                  h->sumsq, 1.f, clip, 1, s));
-  HIP_CHECK(hipStreamSynchronize(s));
-  return RSYS_OK;
-}
-
-static int search_adamw_state_io(SearchModel* h, const char* name, float* m_out, float* v_out, const float* m_in, const float* v_in, int64_t n) {
-  if (!h->has_adam) { set_error("rsys_search_adamw_state: no optimizer (rsys_search_adamw_create)"); return RSYS_ERR_STATE; }
-  long long off, size;
-  SEARCH_RC(search_tensor(h, name, &off, &size));
-  ARG_CHECK(n == size, "rsys_search_adamw_state: element count does not match the parameter's");
-  HIP_CHECK(hipSetDevice(h->device));
-  HIP_CHECK(hipStreamSynchronize(h->stream));
-  if (m_out) HIP_CHECK(hipMemcpy(m_out, h->M1 + off, (size_t)n * 4, hipMemcpyDeviceToHost));
-  if (v_out) HIP_CHECK(hipMemcpy(v_out, h->M2 + off, (size_t)n * 4, hipMemcpyDeviceToHost));
-  if (m_in) HIP_CHECK(hipMemcpy(h->M1 + off, m_in, (size_t)n * 4, hipMemcpyHostToDevice));
-  if (v_in) HIP_CHECK(hipMemcpy(h->M2 + off, v_in, (size_t)n * 4, hipMemcpyHostToDevice));
   return RSYS_OK;
 }
 
@@ -509,7 +370,7 @@ static int search_export(SearchModel* h, float* out) {
     GemmParams p{};   // out[m][n] = sum_k E[m][k] Wenc[n][k], fp32 in both modes
     p.A = h->feat + r0 * h->D; p.lda = h->D; p.B = h->P; p.ldb = h->D; p.C = h->exp32 + r0 * h->Q; p.ldc = h->Q; p.c_f32 = 1;
     p.M = rows; p.N = h->Q; p.K = h->D; p.epi = EPI_STORE; p.alpha = 1.f; p.splitk = 1;
-    SEARCH_RC(launch_gemm<float>(p, false, false, false, false, s));
+    ENC_RC(launch_gemm<float>(p, false, false, false, false, s));
   }
   HIP_CHECK(hipMemcpyAsync(out, h->exp32, (size_t)h->V * h->Q * 4, hipMemcpyDeviceToHost, s));
   HIP_CHECK(hipStreamSynchronize(s));
@@ -525,28 +386,28 @@ static int search_topk(SearchModel* h, const float* x, int nq, int k, int32_t* i
   HIP_CHECK(hipSetDevice(h->device));
   hipStream_t s = h->stream;
   const int Bpad = (nq + 255) / 256 * 256;
-  auto align = [](size_t b) { return (b + 255) / 256 * 256; };
-  const size_t ws_b = align(topk_rows_ws_bytes(nq, h->V, k)), ids_b = align((size_t)nq * k * 4), vals_b = ids_b, cnt_b = align((size_t)nq * 4);
-  const size_t need = ws_b + ids_b + vals_b + cnt_b;
-  if (h->tws_bytes < need) {
-    HIP_CHECK(hipStreamSynchronize(s));
-    if (h->tws) HIP_CHECK(hipFree(h->tws));
-    h->tws = nullptr; h->tws_bytes = 0;
-    HIP_CHECK(hipMalloc(&h->tws, need));
-    h->tws_bytes = need;
-  }
-  char* base = (char*)h->tws;
-  int* ids = (int*)(base + ws_b); float* vals = (float*)(base + ws_b + ids_b); int* cnt = (int*)(base + ws_b + ids_b + vals_b);
+  auto layout = [&](Carve& c, void** ws, int** ids, float** vals, int** cnt) {
+    *ws = c.take<char>(topk_rows_ws_bytes(nq, h->V, k));
+    *ids = c.take<int>((size_t)nq * k);
+    *vals = c.take<float>((size_t)nq * k);
+    *cnt = c.take<int>(nq);
+  };
+  void* ws; int *ids, *cnt; float* vals;
+  Carve probe{nullptr};
+  layout(probe, &ws, &ids, &vals, &cnt);
+  ENC_RC(h->tws.reserve(probe.off, s));
+  Carve cv{(char*)h->tws.p};
+  layout(cv, &ws, &ids, &vals, &cnt);
   if (h->bf16_mode()) {
-    SEARCH_RC(search_upload_x<bf16>(h, x, nq, Bpad));
-    SEARCH_RC(search_scores<bf16>(h, nq, Bpad, false, false, nullptr));
+    ENC_RC(search_upload_x<bf16>(h, x, nq, Bpad));
+    ENC_RC(search_scores<bf16>(h, nq, Bpad, false, false, nullptr));
   } else {
-    SEARCH_RC(search_upload_x<float>(h, x, nq, Bpad));
-    SEARCH_RC(search_scores<float>(h, nq, Bpad, false, false, nullptr));
+    ENC_RC(search_upload_x<float>(h, x, nq, Bpad));
+    ENC_RC(search_scores<float>(h, nq, Bpad, false, false, nullptr));
   }
   search_logp_kernel<<<dim3((h->V + 255) / 256, nq), 256, 0, s>>>(h->z, h->Vpad, h->V, h->lse, h->ls());
   HIP_CHECK(hipGetLastError());
-  SEARCH_RC(topk_rows(h->z, h->Vpad, nq, h->V, k, base, ids, vals, cnt, s));
+  ENC_RC(topk_rows(h->z, h->Vpad, nq, h->V, k, ws, ids, vals, cnt, s));
   HIP_CHECK(hipMemcpyAsync(ids_out, ids, (size_t)nq * k * 4, hipMemcpyDeviceToHost, s));
   HIP_CHECK(hipMemcpyAsync(logp_out, vals, (size_t)nq * k * 4, hipMemcpyDeviceToHost, s));
   HIP_CHECK(hipStreamSynchronize(s));
@@ -574,66 +435,37 @@ static int search_debug_get(SearchModel* h, const char* name, float* out, int64_
   return RSYS_ERR_ARG;
 }
 
-int search_features_from_device(void* hv, const float* rows, int64_t V, int64_t D, int device) {
-  ARG_CHECK(hv, "null handle");
-  SearchModel* h = (SearchModel*)hv;
-  ARG_CHECK(V == h->V, "rsys_search_features_from_model: the medium's item count must be the handle's V_m");
-  ARG_CHECK(D == h->D, "rsys_search_features_from_model: the model's embed_dim must be the handle's D");
-  ARG_CHECK(device == h->device, "rsys_search_features_from_model: the model and the handle must be on one device");
-  HIP_CHECK(hipSetDevice(h->device));
-  HIP_CHECK(hipStreamSynchronize(h->stream));
-  HIP_CHECK(hipMemcpyAsync(h->feat, rows, (size_t)V * D * 4, hipMemcpyDeviceToDevice, h->stream));
-  return search_features_ready(h);
-}
-
 }  // namespace rsys
 
 using namespace rsys;
 
-#define SEARCH_HANDLE(hv)                                                       \
-  SearchModel* h = (SearchModel*)(hv);                                          \
-  do {                                                                          \
-    if (h == nullptr) { set_error("null handle"); return RSYS_ERR_ARG; }        \
-  } while (0)
-
 extern "C" {
 
 int32_t rsys_search_create(int64_t V, int32_t D, int32_t Q, int32_t dtype, int32_t max_batch, int32_t device, void** out) {
-  return search_create(V, D, Q, dtype, max_batch, device, (SearchModel**)out);
+  return search_create(V, D, Q, dtype, max_batch, device, out);
 }
-int32_t rsys_search_destroy(void* hv) { search_free((SearchModel*)hv); return RSYS_OK; }
+int32_t rsys_search_destroy(void* hv) { enc_free((EncoderCore*)hv); return RSYS_OK; }
 int32_t rsys_search_param_get(void* hv, const char* name, float* out, int64_t n) {
-  SEARCH_HANDLE(hv); ARG_CHECK(out, "rsys_search_param_get: null output"); return search_param_io(h, name, out, nullptr, n, 0);
+  ENC_HANDLE(SearchModel, hv); ARG_CHECK(out, "rsys_search_param_get: null output"); return enc_param_io(h, name, out, nullptr, n, 0);
 }
 int32_t rsys_search_param_set(void* hv, const char* name, const float* in, int64_t n) {
-  SEARCH_HANDLE(hv); ARG_CHECK(in, "rsys_search_param_set: null input"); return search_param_io(h, name, nullptr, in, n, 0);
+  ENC_HANDLE(SearchModel, hv); ARG_CHECK(in, "rsys_search_param_set: null input"); return enc_param_io(h, name, nullptr, in, n, 0);
 }
 int32_t rsys_search_grad_get(void* hv, const char* name, float* out, int64_t n) {
-  SEARCH_HANDLE(hv); ARG_CHECK(out, "rsys_search_grad_get: null output"); return search_param_io(h, name, out, nullptr, n, 1);
+  ENC_HANDLE(SearchModel, hv); ARG_CHECK(out, "rsys_search_grad_get: null output"); return enc_param_io(h, name, out, nullptr, n, 1);
 }
-int32_t rsys_search_zero_grad(void* hv) {
-  SEARCH_HANDLE(hv);
-  HIP_CHECK(hipSetDevice(h->device));
-  HIP_CHECK(hipMemsetAsync(h->G, 0, (size_t)h->nflat * 4, h->stream));
-  return RSYS_OK;
-}
+int32_t rsys_search_zero_grad(void* hv) { ENC_HANDLE(SearchModel, hv); return enc_zero_grad(h); }
 int32_t rsys_search_features_set(void* hv, const float* features, int64_t V, int64_t D) {
-  SEARCH_HANDLE(hv);
-  ARG_CHECK(features, "rsys_search_features_set: null table");
-  ARG_CHECK(V == h->V, "rsys_search_features_set: V must be the handle's V_m");
-  ARG_CHECK(D == h->D, "rsys_search_features_set: D must be the handle's D");
-  HIP_CHECK(hipSetDevice(h->device));
-  HIP_CHECK(hipStreamSynchronize(h->stream));
-  HIP_CHECK(hipMemcpy(h->feat, features, (size_t)V * D * 4, hipMemcpyHostToDevice));
-  return search_features_ready(h);
+  ENC_HANDLE(SearchModel, hv);
+  return enc_features_set(h, features, V, D);
 }
 int32_t rsys_search_forward_backward(void* hv, const float* x, const int32_t* labels, const float* weights, int32_t B, int32_t evaluate,
                                      float* loss_out, float* weight_sum_out) {
-  SEARCH_HANDLE(hv);
+  ENC_HANDLE(SearchModel, hv);
   return search_forward_backward(h, x, labels, weights, B, evaluate, loss_out, weight_sum_out);
 }
 int32_t rsys_search_adamw_create(void* hv, float beta1, float beta2, float eps, float weight_decay) {
-  SEARCH_HANDLE(hv);
+  ENC_HANDLE(SearchModel, hv);
   ARG_CHECK(beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f, "rsys_search_adamw_create: betas must be in [0, 1)");
   ARG_CHECK(eps > 0.f && weight_decay >= 0.f, "rsys_search_adamw_create: eps > 0 and weight_decay >= 0");
   HIP_CHECK(hipSetDevice(h->device));
@@ -644,28 +476,28 @@ int32_t rsys_search_adamw_create(void* hv, float beta1, float beta2, float eps, 
   return RSYS_OK;
 }
 int32_t rsys_search_adamw_step(void* hv, float lr, float clip, float* norm_out, int32_t* skipped_out) {
-  SEARCH_HANDLE(hv);
-  return search_adamw_step(h, lr, clip, norm_out, skipped_out);
+  ENC_HANDLE(SearchModel, hv);
+  return enc_adamw_step(h, lr, clip, norm_out, skipped_out);
 }
 int32_t rsys_search_adamw_state_get(void* hv, const char* name, float* exp_avg, float* exp_avg_sq, int64_t n, int32_t* step) {
-  SEARCH_HANDLE(hv);
-  SEARCH_RC(search_adamw_state_io(h, name, exp_avg, exp_avg_sq, nullptr, nullptr, n));
+  ENC_HANDLE(SearchModel, hv);
+  ENC_RC(enc_adamw_state_io(h, name, exp_avg, exp_avg_sq, nullptr, nullptr, n));
   if (step) *step = h->adam_step;
   return RSYS_OK;
 }
 int32_t rsys_search_adamw_state_set(void* hv, const char* name, const float* exp_avg, const float* exp_avg_sq, int64_t n, int32_t step) {
-  SEARCH_HANDLE(hv);
+  ENC_HANDLE(SearchModel, hv);
   ARG_CHECK(exp_avg && exp_avg_sq, "rsys_search_adamw_state_set: null input");
   ARG_CHECK(step >= 0, "rsys_search_adamw_state_set: step >= 0");
-  SEARCH_RC(search_adamw_state_io(h, name, nullptr, nullptr, exp_avg, exp_avg_sq, n));
+  ENC_RC(enc_adamw_state_io(h, name, nullptr, nullptr, exp_avg, exp_avg_sq, n));
   h->adam_step = step;
   return RSYS_OK;
 }
-int32_t rsys_search_export(void* hv, float* out) { SEARCH_HANDLE(hv); return search_export(h, out); }
+int32_t rsys_search_export(void* hv, float* out) { ENC_HANDLE(SearchModel, hv); return search_export(h, out); }
 int32_t rsys_search_topk(void* hv, const float* x, int32_t n_queries, int32_t k, int32_t* ids_out, float* logp_out) {
-  SEARCH_HANDLE(hv);
+  ENC_HANDLE(SearchModel, hv);
   return search_topk(h, x, n_queries, k, ids_out, logp_out);
 }
-int32_t rsys_search_debug_get(void* hv, const char* name, float* out, int64_t n) { SEARCH_HANDLE(hv); return search_debug_get(h, name, out, n); }
+int32_t rsys_search_debug_get(void* hv, const char* name, float* out, int64_t n) { ENC_HANDLE(SearchModel, hv); return search_debug_get(h, name, out, n); }
 
 }  // extern "C"

@@ -1,6 +1,7 @@
 // Item-similarity LambdaRank model on the device (Training/item_similarity/pairwise_ltr.py with --features transformer / content:
 // `LTRModel.embed`, `process_batch`, `lambdarank_loss`, `ndcg`, the AdamW step of `train_epoch`, `generate_embeddings` and the scoring
-// and selection of `load_hard_negatives`).  A handle of its own (rsys_sim_*), independent of rsys_model.  The pipeline:
+// and selection of `load_hard_negatives`).  A handle of its own (rsys_sim_*), independent of rsys_model, on the core of encoder_handle.hpp
+// (parameters, AdamW, the feature table, the ordered split-K product).  The pipeline:
 //   gather     X[r] = T(dropout(f[id_r])): in training one row per (query, slot) for the source copy and one for the target, every row
 //              with its own mask (launch_dropout's counter RNG keyed on (seed, step, row, column)); in evaluation one row per source
 //   encoder    Y = X W^T through launch_gemm (gemm_route picks the kernel); bf16 mode: bf16 operands, fp32 accumulation, bf16 output
@@ -21,13 +22,11 @@
 #include <string>
 #include <vector>
 
-#include "model.hpp"
+#include "encoder_handle.hpp"
 
 namespace rsys {
 
 namespace {
-
-#define SIM_RC(expr) do { int _rc = (expr); if (_rc != RSYS_OK) return _rc; } while (0)
 
 constexpr int SIM_MAXN = 2048;            // slots per list: the rank sort holds 2048 (key, slot) pairs in LDS
 constexpr int SIM_MAXQ = 4096;
@@ -323,113 +322,64 @@ __global__ void __launch_bounds__(256) sim_hn_finish_kernel(const float* __restr
   }
 }
 
-inline unsigned grid_for(long long work, int per_block = 256, long long cap = 8192) {
-  return (unsigned)std::max<long long>(1, std::min<long long>((work + per_block - 1) / per_block, cap));
-}
-
-struct HnCarve {
-  char* p; size_t off = 0;
-  template <typename X> X* take(size_t count) {
-    X* r = (X*)(p ? p + off : nullptr);
-    off += (std::max<size_t>(count, 1) * sizeof(X) + 255) / 256 * 256;
-    return r;
-  }
-};
-
 }  // namespace
 
 // ------------------------------------------------------------------ the handle
-struct SimModel {
-  int device = 0, V = 0, F = 0, E = 0, dtype = 0, maxq = 0, nmax = 0;
+struct SimModel : EncoderCore {
+  int V = 0, F = 0, E = 0, maxq = 0, nmax = 0;      // features [V][F], W [E][F]
   float p = 0.f;
-  hipStream_t stream = nullptr;
-  long long nflat = 0;                              // [W (E x F) | logit_scale | 3 pad]
-  float *feat = nullptr, *P = nullptr, *G = nullptr, *M1 = nullptr, *M2 = nullptr;
-  bf16* Wsh = nullptr;                              // bf16 copy of W (bf16 mode)
-  bool has_features = false;
-  int adam_step = 0;
-  float *sumsq = nullptr, *sq_part = nullptr;
   long long rcap = 0;                               // rows of the per-call operands
   void *X = nullptr, *Y = nullptr, *dY = nullptr;
   int* rowid = nullptr;
   float *x = nullptr, *rel = nullptr, *dldx = nullptr, *gx = nullptr, *w = nullptr, *wscale = nullptr, *lpart = nullptr, *loss = nullptr;
   float* qout = nullptr;
   int *order = nullptr, *perm = nullptr, *order_y = nullptr, *perm_y = nullptr;
-  float* slab = nullptr; long long slab_floats = 0;
   float *Xe = nullptr, *Ye = nullptr;               // export chunk
   float* exp32 = nullptr; bf16* exp16 = nullptr; bool has_export = false;
   unsigned* tmask = nullptr; long long tmw = 0;
-  void* hws = nullptr; size_t hws_bytes = 0;        // hard-negative workspace, grown on demand
-  PairWs pws;                                       // catalogue-rank workspace (similarity_metrics.hip), grown on demand
+  DevScratch hws;                                   // hard-negative workspace
+  DevScratch pws;                                   // catalogue-rank workspace (similarity_metrics.hip)
   int last_nq = 0, last_n = 0, last_drop = 0; long long last_rows = 0;
   uint64_t last_seed = 0, last_step = 0;
   std::vector<int> h_rowid; std::vector<float> h_wscale;   // host sources of a call's uploads, alive until its closing wait
-  std::vector<void*> allocs;
-  bool bf16_mode() const { return dtype == RSYS_DTYPE_BF16; }
+  void free_own() override {
+    hws.release(); pws.release();
+    if (exp32) hipFree(exp32);
+    if (exp16) hipFree(exp16);
+    if (tmask) hipFree(tmask);
+  }
 };
 
-static int sim_alloc(SimModel* h, void** p, size_t bytes) {
-  bytes = std::max<size_t>(256, (bytes + 255) / 256 * 256);
-  HIP_CHECK(hipMalloc(p, bytes));
-  HIP_CHECK(hipMemset(*p, 0, bytes));
-  h->allocs.push_back(*p);
-  return RSYS_OK;
-}
-#define SIM_ALLOC(ptr, bytes) SIM_RC(sim_alloc(h, (void**)&(ptr), (size_t)(bytes)))
-
-static void sim_free(SimModel* h) {
-  if (!h) return;
-  hipSetDevice(h->device);
-  if (h->stream) hipStreamSynchronize(h->stream);
-  for (void* p : h->allocs) hipFree(p);
-  if (h->slab) hipFree(h->slab);
-  if (h->hws) hipFree(h->hws);
-  pair_ws_free(&h->pws);
-  if (h->exp32) hipFree(h->exp32);
-  if (h->exp16) hipFree(h->exp16);
-  if (h->tmask) hipFree(h->tmask);
-  if (h->stream) hipStreamDestroy(h->stream);
-  delete h;
-}
-
-static int sim_create(int64_t V, int32_t F, int32_t E, int32_t dtype, int32_t maxq, int32_t nmax, float dropout, int32_t device, SimModel** out) {
+static int sim_create(int64_t V, int32_t F, int32_t E, int32_t dtype, int32_t maxq, int32_t nmax, float dropout, int32_t device, void** out) {
   ARG_CHECK(out, "rsys_sim_create: null output");
   ARG_CHECK(V >= 1 && V <= (1 << 30), "rsys_sim_create: 1 <= V <= 2^30");
   ARG_CHECK(F >= 64 && F % 64 == 0 && F <= 16384, "rsys_sim_create: F must be a multiple of 64 in [64, 16384] (2048: transformer, 5120: content)");
   ARG_CHECK(E >= 64 && E % 64 == 0 && E <= 8192, "rsys_sim_create: E must be a multiple of 64 in [64, 8192]");
-  ARG_CHECK(dtype == RSYS_DTYPE_FP32 || dtype == RSYS_DTYPE_BF16, "rsys_sim_create: dtype must be RSYS_DTYPE_FP32 or RSYS_DTYPE_BF16");
   ARG_CHECK(maxq >= 1 && maxq <= SIM_MAXQ, "rsys_sim_create: 1 <= max_queries <= 4096");
   ARG_CHECK(nmax >= 1 && nmax <= SIM_MAXN, "rsys_sim_create: 1 <= items_per_query <= 2048");
   ARG_CHECK(dropout >= 0.f && dropout < 1.f, "rsys_sim_create: 0 <= dropout < 1");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { set_error("rsys_sim_create: no HIP device visible"); return RSYS_ERR_HIP; }
-  ARG_CHECK(device >= 0 && device < ndev, "rsys_sim_create: device index out of range");
-  HIP_CHECK(hipSetDevice(device));
+  ENC_RC(enc_check_device("rsys_sim", dtype, device));
   SimModel* h = new SimModel();
-  h->device = device; h->V = (int)V; h->F = F; h->E = E; h->dtype = dtype; h->maxq = maxq; h->nmax = nmax; h->p = dropout;
+  h->api = "rsys_sim"; h->wname = "encoder.1.weight"; h->device = device; h->dtype = dtype;
+  h->frows = h->fpad = V; h->fcols = h->wcols = F; h->wrows = E;   // (the table is not padded)
+  h->has_adam = true;   // the optimizer exists from creation: AdamW(betas 0.9 / 0.999, eps 1e-8, weight decay 0.1), the core's defaults
+  h->V = (int)V; h->F = F; h->E = E; h->maxq = maxq; h->nmax = nmax; h->p = dropout;
   const size_t tsz = h->bf16_mode() ? 2 : 4;
-  h->nflat = (long long)E * F + 4;
   h->rcap = ((2LL * maxq * nmax) + 255) / 256 * 256;
   const long long pairs = (long long)maxq * nmax;
   const int rc = [&]() -> int {
-    HIP_CHECK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-    SIM_ALLOC(h->feat, (size_t)V * F * 4);
-    SIM_ALLOC(h->P, h->nflat * 4); SIM_ALLOC(h->G, h->nflat * 4); SIM_ALLOC(h->M1, h->nflat * 4); SIM_ALLOC(h->M2, h->nflat * 4);
-    if (h->bf16_mode()) SIM_ALLOC(h->Wsh, h->nflat * 2);
-    SIM_ALLOC(h->sumsq, 16); SIM_ALLOC(h->sq_part, (size_t)sumsq_parts() * 4);
-    SIM_ALLOC(h->X, (size_t)h->rcap * F * tsz); SIM_ALLOC(h->Y, (size_t)h->rcap * E * tsz); SIM_ALLOC(h->dY, (size_t)h->rcap * E * tsz);
-    SIM_ALLOC(h->rowid, h->rcap * 4);
-    SIM_ALLOC(h->x, pairs * 4); SIM_ALLOC(h->rel, pairs * 4); SIM_ALLOC(h->dldx, pairs * 4); SIM_ALLOC(h->gx, pairs * 4);
-    SIM_ALLOC(h->w, maxq * 4); SIM_ALLOC(h->wscale, maxq * 4); SIM_ALLOC(h->qout, maxq * 4);
-    SIM_ALLOC(h->lpart, (size_t)maxq * ((SIM_MAXN + SIM_LT - 1) / SIM_LT) * 4); SIM_ALLOC(h->loss, 16);
-    SIM_ALLOC(h->order, pairs * 4); SIM_ALLOC(h->perm, pairs * 4); SIM_ALLOC(h->order_y, pairs * 4); SIM_ALLOC(h->perm_y, pairs * 4);
-    SIM_ALLOC(h->Xe, (size_t)SIM_EXPORT_ROWS * F * 4); SIM_ALLOC(h->Ye, (size_t)SIM_EXPORT_ROWS * E * 4);
-    const float ls = logf(1.f / 0.07f);   // logit_scale = log(1 / 0.07) (pairwise_ltr.py:134); W stays zero until set
-    HIP_CHECK(hipMemcpy(h->P + (long long)E * F, &ls, 4, hipMemcpyHostToDevice));
+    ENC_RC(enc_init(h, logf(1.f / 0.07f)));   // logit_scale = log(1 / 0.07) (pairwise_ltr.py:134)
+    ENC_ALLOC(h->X, (size_t)h->rcap * F * tsz); ENC_ALLOC(h->Y, (size_t)h->rcap * E * tsz); ENC_ALLOC(h->dY, (size_t)h->rcap * E * tsz);
+    ENC_ALLOC(h->rowid, h->rcap * 4);
+    ENC_ALLOC(h->x, pairs * 4); ENC_ALLOC(h->rel, pairs * 4); ENC_ALLOC(h->dldx, pairs * 4); ENC_ALLOC(h->gx, pairs * 4);
+    ENC_ALLOC(h->w, maxq * 4); ENC_ALLOC(h->wscale, maxq * 4); ENC_ALLOC(h->qout, maxq * 4);
+    ENC_ALLOC(h->lpart, (size_t)maxq * ((SIM_MAXN + SIM_LT - 1) / SIM_LT) * 4); ENC_ALLOC(h->loss, 16);
+    ENC_ALLOC(h->order, pairs * 4); ENC_ALLOC(h->perm, pairs * 4); ENC_ALLOC(h->order_y, pairs * 4); ENC_ALLOC(h->perm_y, pairs * 4);
+    ENC_ALLOC(h->Xe, (size_t)SIM_EXPORT_ROWS * F * 4); ENC_ALLOC(h->Ye, (size_t)SIM_EXPORT_ROWS * E * 4);
     return RSYS_OK;
   }();
-  if (rc != RSYS_OK) { sim_free(h); return rc; }
-  *out = h;
+  if (rc != RSYS_OK) { enc_free(h); return rc; }
+  *out = (EncoderCore*)h;
   return RSYS_OK;
 }
 
@@ -444,8 +394,7 @@ static int sim_encode(SimModel* h, long long Rpad) {
   return launch_gemm<T>(p, false, false, false, false, h->stream);
 }
 
-// G[W] += dY^T X over K = Rpad rows: K-major operands; the split-K partial tiles go to a slab and are summed in split order (a slab is
-// always passed, which also keeps the product off gemm4k, whose split-K has no ordered form)
+// G[W] += dY^T X over K = Rpad rows: K-major operands, the split-K partial tiles summed in split order
 template <typename T>
 static int sim_weight_grad(SimModel* h, long long Rpad) {
   GemmParams p{};
@@ -454,16 +403,7 @@ static int sim_weight_grad(SimModel* h, long long Rpad) {
   p.C = h->G; p.ldc = h->F; p.c_f32 = 1;
   p.M = h->E; p.N = h->F; p.K = (int)Rpad; p.epi = EPI_ATOMIC; p.alpha = 1.f;
   p.splitk = (int)std::max<long long>(1, std::min<long long>(64, Rpad / 4096));
-  const long long need = std::max<long long>(256, gemm_slab_need<T>(p, false, false, true, true));
-  if (need > h->slab_floats) {
-    HIP_CHECK(hipStreamSynchronize(h->stream));
-    if (h->slab) HIP_CHECK(hipFree(h->slab));
-    h->slab = nullptr; h->slab_floats = 0;
-    HIP_CHECK(hipMalloc((void**)&h->slab, (size_t)need * 4));
-    h->slab_floats = need;
-  }
-  p.slab = h->slab; p.slab_floats = h->slab_floats;
-  return launch_gemm<T>(p, false, false, true, true, h->stream);
+  return enc_ordered_gemm<T>(h, p, true, true);
 }
 
 static int sim_check_lists(SimModel* h, int nq, int n, const int32_t* src, const int32_t* tgt, const float* rel, const float* w) {
@@ -516,8 +456,8 @@ static int sim_run(SimModel* h, int nq, int n, const int32_t* src, const int32_t
   sim_gather_kernel<T><<<grid_for(Rpad * h->F / 4), 256, 0, s>>>(h->feat, h->F, h->rowid, R, Rpad, 0, h->p, seed, (unsigned)step, drop,
                                                                   (T*)h->X);
   HIP_CHECK(hipGetLastError());
-  SIM_RC(sim_encode<T>(h, Rpad));
-  const float* ls = h->P + (long long)h->E * h->F;
+  ENC_RC(sim_encode<T>(h, Rpad));
+  const float* ls = h->ls();
   const unsigned pgrid = (unsigned)((P2 + SIM_PAIR_WAVES - 1) / SIM_PAIR_WAVES);
   sim_pair_fwd_kernel<T><<<pgrid, 64 * SIM_PAIR_WAVES, 0, s>>>((const T*)h->Y, h->E, nq, n, train ? 1 : 0, ls, h->x);
   HIP_CHECK(hipGetLastError());
@@ -536,8 +476,8 @@ static int sim_run(SimModel* h, int nq, int n, const int32_t* src, const int32_t
     if (Rpad > R) HIP_CHECK(hipMemsetAsync(dY + R * h->E, 0, (size_t)(Rpad - R) * h->E * sizeof(T), s));
     sim_pair_bwd_kernel<T><<<pgrid, 64 * SIM_PAIR_WAVES, 0, s>>>((const T*)h->Y, h->E, nq, n, ls, h->dldx, h->x, dY, h->gx);
     HIP_CHECK(hipGetLastError());
-    SIM_RC(sim_weight_grad<T>(h, Rpad));
-    sim_sum_kernel<<<1, 1024, 0, s>>>(h->gx, P2, h->G + (long long)h->E * h->F);
+    ENC_RC(sim_weight_grad<T>(h, Rpad));
+    sim_sum_kernel<<<1, 1024, 0, s>>>(h->gx, P2, h->G + h->nw());
     HIP_CHECK(hipGetLastError());
   }
   return RSYS_OK;
@@ -545,10 +485,10 @@ static int sim_run(SimModel* h, int nq, int n, const int32_t* src, const int32_t
 
 static int sim_forward_backward(SimModel* h, int nq, int n, const int32_t* src, const int32_t* tgt, const float* rel, const float* w,
                                 int evaluate, uint64_t seed, uint64_t step, float* loss_out) {
-  SIM_RC(sim_check_lists(h, nq, n, src, tgt, rel, w));
+  ENC_RC(sim_check_lists(h, nq, n, src, tgt, rel, w));
   HIP_CHECK(hipSetDevice(h->device));
   const bool train = evaluate == 0;
-  SIM_RC(h->bf16_mode() ? sim_run<bf16>(h, nq, n, src, tgt, rel, w, train, seed, step, true, train)
+  ENC_RC(h->bf16_mode() ? sim_run<bf16>(h, nq, n, src, tgt, rel, w, train, seed, step, true, train)
                         : sim_run<float>(h, nq, n, src, tgt, rel, w, train, seed, step, true, train));
   float l = 0.f;
   HIP_CHECK(hipMemcpyAsync(&l, h->loss, 4, hipMemcpyDeviceToHost, h->stream));
@@ -559,9 +499,9 @@ static int sim_forward_backward(SimModel* h, int nq, int n, const int32_t* src, 
 
 static int sim_ndcg(SimModel* h, int nq, int n, const int32_t* src, const int32_t* tgt, const float* rel, const float* w, double* out) {
   ARG_CHECK(out, "rsys_sim_ndcg: null output");
-  SIM_RC(sim_check_lists(h, nq, n, src, tgt, rel, w));
+  ENC_RC(sim_check_lists(h, nq, n, src, tgt, rel, w));
   HIP_CHECK(hipSetDevice(h->device));
-  SIM_RC(h->bf16_mode() ? sim_run<bf16>(h, nq, n, src, tgt, rel, w, false, 0, 0, false, false)
+  ENC_RC(h->bf16_mode() ? sim_run<bf16>(h, nq, n, src, tgt, rel, w, false, 0, 0, false, false)
                         : sim_run<float>(h, nq, n, src, tgt, rel, w, false, 0, 0, false, false));
   hipStream_t s = h->stream;
   sim_rank_kernel<<<nq, 1024, 0, s>>>(h->rel, n, h->order_y, h->perm_y);
@@ -577,72 +517,6 @@ static int sim_ndcg(SimModel* h, int nq, int n, const int32_t* src, const int32_
   return RSYS_OK;
 }
 
-// name -> (offset, size) in the flat buffers
-static int sim_tensor(SimModel* h, const char* name, long long* off, long long* size) {
-  ARG_CHECK(name, "rsys_sim: null name");
-  if (strcmp(name, "encoder.1.weight") == 0) { *off = 0; *size = (long long)h->E * h->F; return RSYS_OK; }
-  if (strcmp(name, "logit_scale") == 0) { *off = (long long)h->E * h->F; *size = 1; return RSYS_OK; }
-  set_error(std::string("rsys_sim: unknown parameter '") + name + "' (trainable: encoder.1.weight, logit_scale; the frozen tables go "
-            "through rsys_sim_features_set)");
-  return RSYS_ERR_ARG;
-}
-
-static int sim_param_io(SimModel* h, const char* name, float* out, const float* in, int64_t n, int grad) {
-  long long off, size;
-  SIM_RC(sim_tensor(h, name, &off, &size));
-  ARG_CHECK(n == size, "rsys_sim: element count does not match the parameter's");
-  HIP_CHECK(hipSetDevice(h->device));
-  HIP_CHECK(hipStreamSynchronize(h->stream));
-  float* base = grad ? h->G : h->P;
-  if (out) HIP_CHECK(hipMemcpy(out, base + off, (size_t)n * 4, hipMemcpyDeviceToHost));
-  if (in) {
-    HIP_CHECK(hipMemcpy(base + off, in, (size_t)n * 4, hipMemcpyHostToDevice));
-    if (h->bf16_mode()) SIM_RC(launch_cast<bf16>(h->P, h->Wsh, (long long)h->E * h->F, h->stream));
-    HIP_CHECK(hipStreamSynchronize(h->stream));
-  }
-  return RSYS_OK;
-}
-
-static int sim_adamw_step(SimModel* h, float lr, float clip, float* norm_out, int32_t* skipped_out) {
-  HIP_CHECK(hipSetDevice(h->device));
-  hipStream_t s = h->stream;
-  SIM_RC(launch_sumsq(h->G, h->nflat, h->sumsq, h->sq_part, s, true));
-  float ss = 0.f;
-  HIP_CHECK(hipMemcpyAsync(&ss, h->sumsq, 4, hipMemcpyDeviceToHost, s));
-  HIP_CHECK(hipStreamSynchronize(s));
-  const float norm = sqrtf(ss);
-  const bool skip = !std::isfinite(norm);
-  if (norm_out) *norm_out = norm;
-  if (skipped_out) *skipped_out = skip ? 1 : 0;
-  if (skip) {   // GradScaler: no update and no step count; the gradient is cleared as the next zero_grad would
-    HIP_CHECK(hipMemsetAsync(h->G, 0, (size_t)h->nflat * 4, s));
-    HIP_CHECK(hipStreamSynchronize(s));
-    return RSYS_OK;
-  }
-  ++h->adam_step;
-  const long long nd = (long long)h->E * h->F;
-  if (h->bf16_mode())
-    SIM_RC(launch_adamw<bf16>(h->P, h->G, h->M1, h->M2, h->Wsh, nd, h->nflat, lr, 0.9f, 0.999f, 1e-8f, 0.1f, h->adam_step, h->sumsq, 1.f,
-                              clip, 1, s));
-  else
-    SIM_RC(launch_adamw<float>(h->P, h->G, h->M1, h->M2, (float*)nullptr, nd, h->nflat, lr, 0.9f, 0.999f, 1e-8f, 0.1f, h->adam_step,
-                               h->sumsq, 1.f, clip, 1, s));
-  HIP_CHECK(hipStreamSynchronize(s));
-  return RSYS_OK;
-}
-
-static int sim_features_copy(SimModel* h, const float* rows, int64_t V, int64_t F, int device) {
-  ARG_CHECK(V == h->V, "rsys_sim_features_from_model: the medium's item count must be the handle's V");
-  ARG_CHECK(F == h->F, "rsys_sim_features_from_model: the model's embed_dim must be the handle's F");
-  ARG_CHECK(device == h->device, "rsys_sim_features_from_model: the model and the handle must be on one device");
-  HIP_CHECK(hipSetDevice(h->device));
-  HIP_CHECK(hipStreamSynchronize(h->stream));
-  HIP_CHECK(hipMemcpyAsync(h->feat, rows, (size_t)V * F * 4, hipMemcpyDeviceToDevice, h->stream));
-  HIP_CHECK(hipStreamSynchronize(h->stream));
-  h->has_features = true;
-  return RSYS_OK;
-}
-
 static int sim_export_alloc(SimModel* h) {
   if (h->exp32) return RSYS_OK;
   HIP_CHECK(hipMalloc((void**)&h->exp32, (size_t)h->V * h->E * 4));
@@ -654,7 +528,7 @@ static int sim_embed_all(SimModel* h, int train_mode, uint64_t seed, float* out)
   ARG_CHECK(h->has_features, "rsys_sim_embed_all: features are not set (rsys_sim_features_set)");
   HIP_CHECK(hipSetDevice(h->device));
   hipStream_t s = h->stream;
-  SIM_RC(sim_export_alloc(h));
+  ENC_RC(sim_export_alloc(h));
   const int drop = train_mode && h->p > 0.f ? 1 : 0;
   for (long long r0 = 0; r0 < h->V; r0 += SIM_EXPORT_ROWS) {
     const int rows = (int)std::min<long long>(SIM_EXPORT_ROWS, h->V - r0);
@@ -664,11 +538,11 @@ static int sim_embed_all(SimModel* h, int train_mode, uint64_t seed, float* out)
     GemmParams p{};
     p.A = h->Xe; p.lda = h->F; p.B = h->P; p.ldb = h->F; p.C = h->Ye; p.ldc = h->E; p.c_f32 = 1;
     p.M = rows; p.N = h->E; p.K = h->F; p.epi = EPI_STORE; p.alpha = 1.f; p.splitk = 1;
-    SIM_RC(launch_gemm<float>(p, false, false, false, false, s));
+    ENC_RC(launch_gemm<float>(p, false, false, false, false, s));
     sim_normalize_kernel<<<(unsigned)((rows + 3) / 4), 256, 0, s>>>(h->Ye, h->E, rows, h->exp32 + r0 * h->E);
     HIP_CHECK(hipGetLastError());
   }
-  SIM_RC(launch_cast<bf16>(h->exp32, h->exp16, (long long)h->V * h->E, s));
+  ENC_RC(launch_cast<bf16>(h->exp32, h->exp16, (long long)h->V * h->E, s));
   h->has_export = true;
   if (out) HIP_CHECK(hipMemcpyAsync(out, h->exp32, (size_t)h->V * h->E * 4, hipMemcpyDeviceToHost, s));
   HIP_CHECK(hipStreamSynchronize(s));
@@ -678,10 +552,10 @@ static int sim_embed_all(SimModel* h, int train_mode, uint64_t seed, float* out)
 static int sim_export_set(SimModel* h, const float* emb) {
   ARG_CHECK(emb, "rsys_sim_export_set: null table");
   HIP_CHECK(hipSetDevice(h->device));
-  SIM_RC(sim_export_alloc(h));
+  ENC_RC(sim_export_alloc(h));
   HIP_CHECK(hipStreamSynchronize(h->stream));
   HIP_CHECK(hipMemcpy(h->exp32, emb, (size_t)h->V * h->E * 4, hipMemcpyHostToDevice));
-  SIM_RC(launch_cast<bf16>(h->exp32, h->exp16, (long long)h->V * h->E, h->stream));
+  ENC_RC(launch_cast<bf16>(h->exp32, h->exp16, (long long)h->V * h->E, h->stream));
   HIP_CHECK(hipStreamSynchronize(h->stream));
   h->has_export = true;
   return RSYS_OK;
@@ -727,7 +601,7 @@ static int sim_hard_negatives(SimModel* h, int split, int n_src, const int32_t* 
   if (pos_off)
     for (int c0 = 0; c0 < n_src; c0 += SIM_HN_CHUNK)
       max_pos = std::max<long long>(max_pos, pos_off[std::min(n_src, c0 + SIM_HN_CHUNK)] - pos_off[c0]);
-  auto layout = [&](HnCarve& c, bf16** A, float** z, float** sc, void** tws, int** tids, float** tvals, int** cnt, int** out, int** src,
+  auto layout = [&](Carve& c, bf16** A, float** z, float** sc, void** tws, int** tids, float** tvals, int** cnt, int** out, int** src,
                     long long** pos) {
     *A = c.take<bf16>((size_t)C * E);
     *z = c.take<float>((size_t)C * ldz);
@@ -741,16 +615,10 @@ static int sim_hard_negatives(SimModel* h, int split, int n_src, const int32_t* 
     *pos = c.take<long long>(max_pos);
   };
   bf16* A; float *z, *sc, *tvals; void* tws; int *tids, *cnt, *out, *dsrc; long long* dpos;
-  HnCarve probe{nullptr};
+  Carve probe{nullptr};
   layout(probe, &A, &z, &sc, &tws, &tids, &tvals, &cnt, &out, &dsrc, &dpos);
-  if (h->hws_bytes < probe.off) {
-    HIP_CHECK(hipStreamSynchronize(s));
-    if (h->hws) HIP_CHECK(hipFree(h->hws));
-    h->hws = nullptr; h->hws_bytes = 0;
-    HIP_CHECK(hipMalloc(&h->hws, probe.off));
-    h->hws_bytes = probe.off;
-  }
-  HnCarve cv{(char*)h->hws};
+  ENC_RC(h->hws.reserve(probe.off, s));
+  Carve cv{(char*)h->hws.p};
   layout(cv, &A, &z, &sc, &tws, &tids, &tvals, &cnt, &out, &dsrc, &dpos);
   std::vector<long long> hpos;
   for (int c0 = 0; c0 < n_src; c0 += SIM_HN_CHUNK) {
@@ -761,7 +629,7 @@ static int sim_hard_negatives(SimModel* h, int split, int n_src, const int32_t* 
     GemmParams p{};
     p.A = A; p.lda = E; p.B = h->exp16; p.ldb = E; p.C = z; p.ldc = ldz; p.c_f32 = 1;
     p.M = nc; p.N = V; p.K = E; p.epi = EPI_STORE; p.alpha = 1.f; p.splitk = 1;
-    SIM_RC(launch_gemm<bf16>(p, false, false, false, false, s));
+    ENC_RC(launch_gemm<bf16>(p, false, false, false, false, s));
     sim_hn_mask_kernel<<<dim3((V + 255) / 256, nc), 256, 0, s>>>(z, ldz, V, dsrc, h->tmask, h->tmw, split, sc);
     HIP_CHECK(hipGetLastError());
     hpos.clear();
@@ -773,7 +641,7 @@ static int sim_hard_negatives(SimModel* h, int split, int n_src, const int32_t* 
       sim_hn_pos_kernel<<<grid_for((long long)hpos.size(), 256, 1LL << 30), 256, 0, s>>>(dpos, (long long)hpos.size(), sc);
       HIP_CHECK(hipGetLastError());
     }
-    SIM_RC(topk_rows(sc, V, nc, V, n, tws, tids, tvals, cnt, s));
+    ENC_RC(topk_rows(sc, V, nc, V, n, tws, tids, tvals, cnt, s));
     sim_hn_finish_kernel<<<nc, 256, 0, s>>>(sc, V, tids, cnt, n, out);
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipMemcpyAsync(ids_out + (long long)c0 * n, out, (size_t)nc * n * 4, hipMemcpyDeviceToHost, s));
@@ -833,97 +701,62 @@ static int sim_debug_get(SimModel* h, const char* name, void* out, int64_t n) {
   return RSYS_ERR_ARG;
 }
 
-int sim_features_from_device(void* hv, const float* rows, int64_t V, int64_t F, int device) {
-  ARG_CHECK(hv, "null handle");
-  return sim_features_copy((SimModel*)hv, rows, V, F, device);
-}
-
 }  // namespace rsys
 
 using namespace rsys;
-
-#define SIM_HANDLE(hv)                                                          \
-  SimModel* h = (SimModel*)(hv);                                                \
-  do {                                                                          \
-    if (h == nullptr) { set_error("null handle"); return RSYS_ERR_ARG; }        \
-  } while (0)
 
 extern "C" {
 
 int32_t rsys_sim_create(int64_t V, int32_t F, int32_t E, int32_t dtype, int32_t max_queries, int32_t items_per_query, float dropout,
                         int32_t device, void** out) {
-  SimModel* h = nullptr;
-  const int rc = sim_create(V, F, E, dtype, max_queries, items_per_query, dropout, device, &h);
-  if (rc == RSYS_OK) *out = h;
-  return rc;
+  return sim_create(V, F, E, dtype, max_queries, items_per_query, dropout, device, out);
 }
-int32_t rsys_sim_destroy(void* hv) { sim_free((SimModel*)hv); return RSYS_OK; }
+int32_t rsys_sim_destroy(void* hv) { enc_free((EncoderCore*)hv); return RSYS_OK; }
 int32_t rsys_sim_param_get(void* hv, const char* name, float* out, int64_t n) {
-  SIM_HANDLE(hv); ARG_CHECK(out, "rsys_sim_param_get: null output"); return sim_param_io(h, name, out, nullptr, n, 0);
+  ENC_HANDLE(SimModel, hv); ARG_CHECK(out, "rsys_sim_param_get: null output"); return enc_param_io(h, name, out, nullptr, n, 0);
 }
 int32_t rsys_sim_param_set(void* hv, const char* name, const float* in, int64_t n) {
-  SIM_HANDLE(hv); ARG_CHECK(in, "rsys_sim_param_set: null input"); return sim_param_io(h, name, nullptr, in, n, 0);
+  ENC_HANDLE(SimModel, hv); ARG_CHECK(in, "rsys_sim_param_set: null input"); return enc_param_io(h, name, nullptr, in, n, 0);
 }
 int32_t rsys_sim_grad_get(void* hv, const char* name, float* out, int64_t n) {
-  SIM_HANDLE(hv); ARG_CHECK(out, "rsys_sim_grad_get: null output"); return sim_param_io(h, name, out, nullptr, n, 1);
+  ENC_HANDLE(SimModel, hv); ARG_CHECK(out, "rsys_sim_grad_get: null output"); return enc_param_io(h, name, out, nullptr, n, 1);
 }
-int32_t rsys_sim_zero_grad(void* hv) {
-  SIM_HANDLE(hv);
-  HIP_CHECK(hipSetDevice(h->device));
-  HIP_CHECK(hipMemsetAsync(h->G, 0, (size_t)h->nflat * 4, h->stream));
-  return RSYS_OK;
-}
-int32_t rsys_sim_features_set(void* hv, const float* features, int64_t V, int64_t F) {
-  SIM_HANDLE(hv);
-  ARG_CHECK(features, "rsys_sim_features_set: null table");
-  ARG_CHECK(V == h->V, "rsys_sim_features_set: V must be the handle's V");
-  ARG_CHECK(F == h->F, "rsys_sim_features_set: F must be the handle's F (2048: transformer; 5120: [transformer | content])");
-  HIP_CHECK(hipSetDevice(h->device));
-  HIP_CHECK(hipStreamSynchronize(h->stream));
-  HIP_CHECK(hipMemcpy(h->feat, features, (size_t)V * F * 4, hipMemcpyHostToDevice));
-  h->has_features = true;
-  return RSYS_OK;
-}
+int32_t rsys_sim_zero_grad(void* hv) { ENC_HANDLE(SimModel, hv); return enc_zero_grad(h); }
+int32_t rsys_sim_features_set(void* hv, const float* features, int64_t V, int64_t F) { ENC_HANDLE(SimModel, hv); return enc_features_set(h, features, V, F); }
 int32_t rsys_sim_forward_backward(void* hv, int32_t n_q, int32_t n, const int32_t* source, const int32_t* target, const float* relevance,
                                   const float* weight, int32_t evaluate, uint64_t seed, uint64_t step, float* loss_out) {
-  SIM_HANDLE(hv);
+  ENC_HANDLE(SimModel, hv);
   return sim_forward_backward(h, n_q, n, source, target, relevance, weight, evaluate, seed, step, loss_out);
 }
 int32_t rsys_sim_ndcg(void* hv, int32_t n_q, int32_t n, const int32_t* source, const int32_t* target, const float* relevance,
                       const float* weight, double out[2]) {
-  SIM_HANDLE(hv);
+  ENC_HANDLE(SimModel, hv);
   return sim_ndcg(h, n_q, n, source, target, relevance, weight, out);
 }
 int32_t rsys_sim_adamw_step(void* hv, float lr, float clip, float* norm_out, int32_t* skipped_out) {
-  SIM_HANDLE(hv);
-  return sim_adamw_step(h, lr, clip, norm_out, skipped_out);
+  ENC_HANDLE(SimModel, hv);
+  return enc_adamw_step(h, lr, clip, norm_out, skipped_out);
 }
 int32_t rsys_sim_adamw_state_get(void* hv, const char* name, float* exp_avg, float* exp_avg_sq, int64_t n, int32_t* step) {
-  SIM_HANDLE(hv);
-  long long off, size;
-  SIM_RC(sim_tensor(h, name, &off, &size));
-  ARG_CHECK(n == size, "rsys_sim_adamw_state_get: element count does not match the parameter's");
-  HIP_CHECK(hipSetDevice(h->device));
-  HIP_CHECK(hipStreamSynchronize(h->stream));
-  if (exp_avg) HIP_CHECK(hipMemcpy(exp_avg, h->M1 + off, (size_t)n * 4, hipMemcpyDeviceToHost));
-  if (exp_avg_sq) HIP_CHECK(hipMemcpy(exp_avg_sq, h->M2 + off, (size_t)n * 4, hipMemcpyDeviceToHost));
+  ENC_HANDLE(SimModel, hv);
+  ENC_RC(enc_adamw_state_io(h, name, exp_avg, exp_avg_sq, nullptr, nullptr, n));
   if (step) *step = h->adam_step;
   return RSYS_OK;
 }
-int32_t rsys_sim_embed_all(void* hv, int32_t train_mode, uint64_t seed, float* out) { SIM_HANDLE(hv); return sim_embed_all(h, train_mode, seed, out); }
-int32_t rsys_sim_export_set(void* hv, const float* emb) { SIM_HANDLE(hv); return sim_export_set(h, emb); }
-int32_t rsys_sim_testmask_set(void* hv, const int32_t* bits) { SIM_HANDLE(hv); return sim_testmask_set(h, bits); }
+int32_t rsys_sim_embed_all(void* hv, int32_t train_mode, uint64_t seed, float* out) { ENC_HANDLE(SimModel, hv); return sim_embed_all(h, train_mode, seed, out); }
+int32_t rsys_sim_export_set(void* hv, const float* emb) { ENC_HANDLE(SimModel, hv); return sim_export_set(h, emb); }
+int32_t rsys_sim_testmask_set(void* hv, const int32_t* bits) { ENC_HANDLE(SimModel, hv); return sim_testmask_set(h, bits); }
 int32_t rsys_sim_hard_negatives(void* hv, int32_t split, int32_t n_src, const int32_t* sources, const int64_t* pos_offsets,
                                 const int32_t* pos_ids, int32_t n, int32_t* ids_out) {
-  SIM_HANDLE(hv);
+  ENC_HANDLE(SimModel, hv);
   return sim_hard_negatives(h, split, n_src, sources, pos_offsets, pos_ids, n, ids_out);
 }
 int32_t rsys_sim_pair_ranks(void* hv, int32_t n_src, const int32_t* sources, const int64_t* tgt_offsets, const int32_t* tgt_ids,
                             int32_t* ranks_out) {
-  SIM_HANDLE(hv);
+  ENC_HANDLE(SimModel, hv);
   return sim_pair_ranks(h, n_src, sources, tgt_offsets, tgt_ids, ranks_out);
 }
-int32_t rsys_sim_pair_scores(void* hv, int32_t n_src, const int32_t* sources, float* out) { SIM_HANDLE(hv); return sim_pair_scores(h, n_src, sources, out); }
-int32_t rsys_sim_debug_get(void* hv, const char* name, void* out, int64_t n) { SIM_HANDLE(hv); return sim_debug_get(h, name, out, n); }
+int32_t rsys_sim_pair_scores(void* hv, int32_t n_src, const int32_t* sources, float* out) { ENC_HANDLE(SimModel, hv); return sim_pair_scores(h, n_src, sources, out); }
+int32_t rsys_sim_debug_get(void* hv, const char* name, void* out, int64_t n) { ENC_HANDLE(SimModel, hv); return sim_debug_get(h, name, out, n); }
 
 }  // extern "C"

@@ -18,7 +18,7 @@
 #include <algorithm>
 #include <vector>
 
-#include "model.hpp"
+#include "encoder_handle.hpp"
 
 namespace rsys {
 
@@ -201,19 +201,6 @@ __global__ void __launch_bounds__(PR_THREADS) pair_count_kernel(const float* __r
   }
 }
 
-inline unsigned grid_for(long long work, int per_block = 256, long long cap = 8192) {
-  return (unsigned)std::max<long long>(1, std::min<long long>((work + per_block - 1) / per_block, cap));
-}
-
-struct Carve {
-  char* p; size_t off = 0;
-  template <typename X> X* take(size_t count) {
-    X* r = (X*)(p ? p + off : nullptr);
-    off += (std::max<size_t>(count, 1) * sizeof(X) + 255) / 256 * 256;
-    return r;
-  }
-};
-
 // the device arrays of one call
 struct PairBufs {
   float *A, *z;
@@ -262,16 +249,6 @@ int pair_count_rows(const float* z, long long ldz, int V, int r0, int nc, const 
   return RSYS_OK;
 }
 
-int pair_ws_grow(PairWs* ws, size_t bytes, hipStream_t s) {
-  if (ws->bytes >= bytes) return RSYS_OK;
-  HIP_CHECK(hipStreamSynchronize(s));
-  if (ws->buf) HIP_CHECK(hipFree(ws->buf));
-  ws->buf = nullptr; ws->bytes = 0;
-  HIP_CHECK(hipMalloc(&ws->buf, bytes));
-  ws->bytes = bytes;
-  return RSYS_OK;
-}
-
 // g = rows(sources[c0 .. c0 + nc)) . export^T into b.z
 int pair_chunk_scores(const float* exp32, int V, int E, int c0, int nc, long long ldz, const PairBufs& b, hipStream_t s) {
   pair_rows_kernel<<<grid_for((long long)nc * E / 4), 256, 0, s>>>(exp32, E, b.src + c0, nc, b.A);
@@ -284,13 +261,8 @@ int pair_chunk_scores(const float* exp32, int V, int E, int c0, int nc, long lon
 
 }  // namespace
 
-void pair_ws_free(PairWs* ws) {
-  if (ws->buf) hipFree(ws->buf);
-  ws->buf = nullptr; ws->bytes = 0;
-}
-
 int pair_ranks_run(const float* exp32, int V, int E, const unsigned* tmask, long long tmw, int32_t n_src, const int32_t* sources,
-                   const int64_t* off, const int32_t* tids, int32_t* ranks_out, PairWs* ws, hipStream_t s) {
+                   const int64_t* off, const int32_t* tids, int32_t* ranks_out, DevScratch* ws, hipStream_t s) {
   ARG_CHECK(ranks_out, "rsys_sim_pair_ranks: null output");
   if (int rc = pair_check_csr("rsys_sim_pair_ranks", V, n_src, sources, off, tids)) return rc;
   const long long total = off[n_src];
@@ -300,8 +272,8 @@ int pair_ranks_run(const float* exp32, int V, int E, const unsigned* tmask, long
   PairBufs b;
   Carve probe{nullptr};
   pair_layout(probe, n_src, total, C, E, ldz, true, &b);
-  if (int rc = pair_ws_grow(ws, probe.off, s)) return rc;
-  Carve cv{(char*)ws->buf};
+  if (int rc = ws->reserve(probe.off, s)) return rc;
+  Carve cv{(char*)ws->p};
   pair_layout(cv, n_src, total, C, E, ldz, true, &b);
   HIP_CHECK(hipMemcpyAsync(b.src, sources, (size_t)n_src * 4, hipMemcpyHostToDevice, s));
   HIP_CHECK(hipMemcpyAsync(b.off, off, ((size_t)n_src + 1) * 8, hipMemcpyHostToDevice, s));
@@ -318,7 +290,7 @@ int pair_ranks_run(const float* exp32, int V, int E, const unsigned* tmask, long
 }
 
 int pair_scores_run(const float* exp32, int V, int E, const unsigned* tmask, long long tmw, int32_t n_src, const int32_t* sources,
-                    float* out, PairWs* ws, hipStream_t s) {
+                    float* out, DevScratch* ws, hipStream_t s) {
   ARG_CHECK(sources && out && n_src >= 1, "rsys_sim_pair_scores: null buffer or no source");
   for (int i = 0; i < n_src; ++i) ARG_CHECK(sources[i] >= 0 && sources[i] < V, "rsys_sim_pair_scores: source ids must be in [0, V)");
   const int C = std::min<int>(n_src, PR_CHUNK);
@@ -326,8 +298,8 @@ int pair_scores_run(const float* exp32, int V, int E, const unsigned* tmask, lon
   PairBufs b;
   Carve probe{nullptr};
   pair_layout(probe, n_src, 0, C, E, ldz, true, &b);
-  if (int rc = pair_ws_grow(ws, probe.off, s)) return rc;
-  Carve cv{(char*)ws->buf};
+  if (int rc = ws->reserve(probe.off, s)) return rc;
+  Carve cv{(char*)ws->p};
   pair_layout(cv, n_src, 0, C, E, ldz, true, &b);
   HIP_CHECK(hipMemcpyAsync(b.src, sources, (size_t)n_src * 4, hipMemcpyHostToDevice, s));
   for (int c0 = 0; c0 < n_src; c0 += PR_CHUNK) {
@@ -348,12 +320,12 @@ int op_pair_ranks(const float* scores, int64_t ld, int32_t rows, int32_t V, cons
   if (int rc = pair_check_csr("rsys_op_pair_ranks", V, rows, self, off, tids)) return rc;
   const long long total = off[rows];
   if (total == 0) return RSYS_OK;
-  PairWs ws;
+  DevScratch ws;
   PairBufs b;
   Carve probe{nullptr};
   pair_layout(probe, rows, total, 0, 0, 0, false, &b);
-  if (int rc = pair_ws_grow(&ws, probe.off, nullptr)) return rc;
-  Carve cv{(char*)ws.buf};
+  if (int rc = ws.reserve(probe.off, nullptr)) return rc;
+  Carve cv{(char*)ws.p};
   pair_layout(cv, rows, total, 0, 0, 0, false, &b);
   const int rc = [&]() -> int {
     HIP_CHECK(hipMemcpy(b.src, self, (size_t)rows * 4, hipMemcpyHostToDevice));
@@ -364,7 +336,7 @@ int op_pair_ranks(const float* scores, int64_t ld, int32_t rows, int32_t V, cons
     HIP_CHECK(hipMemcpy(ranks_out, b.rank, (size_t)total * 4, hipMemcpyDeviceToHost));
     return RSYS_OK;
   }();
-  pair_ws_free(&ws);
+  ws.release();
   return rc;
 }
 

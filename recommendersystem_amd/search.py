@@ -12,6 +12,7 @@ import os
 
 import numpy as np
 
+from ._encoder_handle import EarlyStopper, EncoderHandle, _ptr, load_checkpoint, write_checkpoint  # noqa: F401 (re-exported)
 from ._lib import check, lib
 
 DTYPES = {"fp32": 0, "bf16": 1}
@@ -22,10 +23,6 @@ def training_config(vocab_sizes, learning_rate=3e-4, batch_size=1024, embed_dim=
     """train.py:282-288; embed_dim / query_dim are the widths the reference hard-codes (train.py:81,86)"""
     return {"vocab_sizes": dict(vocab_sizes), "learning_rate": learning_rate, "batch_size": batch_size, "embed_dim": embed_dim,
             "query_dim": query_dim}
-
-
-def _ptr(a):
-    return a.ctypes.data_as(C.c_void_p) if a is not None else None
 
 
 def read_chunk(fn):
@@ -88,10 +85,12 @@ class SearchDataset:
                 yield {k: v[idx, ...] for k, v in d.items()}
 
 
-class SearchModel:
+class SearchModel(EncoderHandle):
     """SearchModel (train.py:76-130) of one medium over an rsys_search handle.  features: the frozen table E_m [V_m][D] (the medium's
     rows of `retrieval_embeddings.weight`), or a RecommenderModel whose item table of `medium` is copied on the device
     (rsys_search_features_from_model: no host round trip)."""
+
+    _PREFIX = "rsys_search"
 
     def __init__(self, config, medium, features, dtype="bf16", max_batch=None, device=0):
         if dtype not in DTYPES:
@@ -125,38 +124,10 @@ class SearchModel:
         self.training = True
         self.has_optimizer = False
 
-    def close(self):
-        if getattr(self, "h", None):
-            lib().rsys_search_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def train(self, mode=True):
-        self.training = mode
-        return self
-
-    def eval(self):
-        return self.train(False)
-
     def _tensor(self, name):
         if name not in ("encoder.weight", "logit_scale"):
             raise KeyError(f"SearchModel: unknown parameter {name!r} (encoder.weight, logit_scale)")
         return (self.Q, self.D) if name == "encoder.weight" else ()
-
-    def param_get(self, name, grad=False):
-        out = np.zeros(self._tensor(name), np.float32)
-        fn = lib().rsys_search_grad_get if grad else lib().rsys_search_param_get
-        check(fn(self.h, name.encode(), _ptr(out), out.size))
-        return out
-
-    def param_set(self, name, value):
-        v = np.ascontiguousarray(np.asarray(value, np.float32).reshape(self._tensor(name)))
-        check(lib().rsys_search_param_set(self.h, name.encode(), _ptr(v), v.size))
 
     def init_weights(self, seed=0):
         """nn.Linear's default init of the encoder: U(-1 / sqrt(D), 1 / sqrt(D)); logit_scale = 1"""
@@ -164,19 +135,12 @@ class SearchModel:
         self.param_set("encoder.weight", np.random.default_rng(seed).uniform(-b, b, (self.Q, self.D)))
         self.param_set("logit_scale", 1.0)
 
-    def get_temperature(self):
-        """train.py:88-89: the raw parameter, not its exponential"""
-        return float(self.param_get("logit_scale"))
-
     def state_dict(self):
         return {"logit_scale": self.param_get("logit_scale"), "encoder.weight": self.param_get("encoder.weight")}
 
     def load_state_dict(self, d):
         for name in ("logit_scale", "encoder.weight"):
             self.param_set(name, d[name])
-
-    def zero_grad(self):
-        check(lib().rsys_search_zero_grad(self.h))
 
     def _batch(self, batch):
         x = np.ascontiguousarray(batch["queries"], np.float32)
@@ -203,18 +167,6 @@ class SearchModel:
     def create_optimizer(self, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.1):
         check(lib().rsys_search_adamw_create(self.h, betas[0], betas[1], eps, weight_decay))
         self.has_optimizer = True
-
-    def adamw_step(self, lr, clip=1.0):
-        """clip_grad_norm_ + GradScaler.step(AdamW) + zero_grad; returns (norm, skipped)"""
-        norm, skipped = C.c_float(0), C.c_int32(0)
-        check(lib().rsys_search_adamw_step(self.h, lr, clip, C.byref(norm), C.byref(skipped)))
-        return norm.value, bool(skipped.value)
-
-    def adamw_state(self, name):
-        m, v = np.zeros(self._tensor(name), np.float32), np.zeros(self._tensor(name), np.float32)
-        step = C.c_int32(0)
-        check(lib().rsys_search_adamw_state_get(self.h, name.encode(), _ptr(m), _ptr(v), m.size, C.byref(step)))
-        return m, v, step.value
 
     def adamw_state_set(self, name, exp_avg, exp_avg_sq, step):
         m = np.ascontiguousarray(np.asarray(exp_avg, np.float32).reshape(self._tensor(name)))
@@ -264,34 +216,6 @@ class ConstantScheduler:
         return 1
 
 
-class EarlyStopper:
-    """train.py:208-232: stops if the loss does not decrease by rtol in `patience` epochs"""
-
-    def __init__(self, patience, rtol):
-        self.patience = patience
-        self.rtol = rtol
-        self.counter = 0
-        self.stop_score = float("inf")
-        self.stop = False
-        self.saved_score = float("inf")
-        self.save_model = False
-
-    def __call__(self, score):
-        assert not self.stop
-        if score < self.stop_score * (1 - self.rtol):
-            self.counter = 0
-            self.stop_score = score
-        else:
-            self.counter += 1
-            if self.counter >= self.patience:
-                self.stop = True
-        if score < self.saved_score:
-            self.saved_score = score
-            self.save_model = True
-        else:
-            self.save_model = False
-
-
 def evaluate_metrics(model, dataset):
     """train.py:133-149: sum loss * (raw sum w) / sum (raw sum w) over the split, forward only"""
     losses = weights = 0.0
@@ -321,22 +245,7 @@ def train_epoch(model, dataset, scheduler=None, lr=None):
 def checkpoint_model(model, epoch, training_loss, test_loss, save, datadir, medium=None):
     """train.py:248-272: search.model.{m}.npz under the reference's state-dict names (+ epoch and losses) when `save`, and a row of
     search.model.{m}.csv (header written at epoch -1)"""
-    medium = model.medium if medium is None else medium
-    if save:
-        d = dict(model.state_dict())
-        d.update(epoch=np.array(epoch), training_loss=np.array(training_loss), test_loss=np.array(test_loss))
-        np.savez(os.path.join(datadir, f"search.model.{medium}.npz"), **d)
-    csv_fn = os.path.join(datadir, f"search.model.{medium}.csv")
-    if epoch < 0:
-        with open(csv_fn, "w") as f:
-            f.write(",".join(["epoch", "training_loss", "test_loss", "saved"]) + "\n")
-    with open(csv_fn, "a") as f:
-        f.write(",".join(str(x) for x in [epoch, training_loss, test_loss, 1 if save else 0]) + "\n")
-
-
-def load_checkpoint(path):
-    with np.load(path) as z:
-        return {k: z[k] for k in z.files}
+    write_checkpoint("search.model", model, epoch, training_loss, test_loss, save, datadir, model.medium if medium is None else medium)
 
 
 def train(model, training, test, datadir, num_epochs=1024, log=print):

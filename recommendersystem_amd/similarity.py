@@ -14,6 +14,7 @@ import os
 
 import numpy as np
 
+from ._encoder_handle import EarlyStopper, EncoderHandle, _ptr, load_checkpoint, write_checkpoint  # noqa: F401 (re-exported)
 from ._lib import check, lib
 
 DTYPES = {"fp32": 0, "bf16": 1}
@@ -52,14 +53,12 @@ def pack_testmask(testmask):
     return np.ascontiguousarray(pad).view("<u4").astype(np.uint32).view(np.int32).reshape(V, W)
 
 
-def _ptr(a):
-    return a.ctypes.data_as(C.c_void_p) if a is not None else None
-
-
-class LTRModel:
+class LTRModel(EncoderHandle):
     """LTRModel (pairwise_ltr.py:124-213) over an rsys_sim handle: `embed`, `process_batch`, `lambdarank_loss`, `ndcg` run on the
     device.  features: the frozen [V][F] table (F = 2048: transformer; 5120: [transformer | content]), or a RecommenderModel whose
     item table of `medium` is copied on the device (rsys_sim_features_from_model: no host round trip)."""
+
+    _PREFIX = "rsys_sim"
 
     def __init__(self, config, medium, features, dtype="bf16", max_queries=None, dropout=0.1, device=0, content=None):
         self.config = config
@@ -95,39 +94,8 @@ class LTRModel:
         self.seed = 0
         self.step = 0
 
-    def close(self):
-        if self.h:
-            lib().rsys_sim_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def train(self, mode=True):
-        self.training = mode
-        return self
-
-    def eval(self):
-        return self.train(False)
-
     def _tensor(self, name):
         return (self.E, self.F) if name == "encoder.1.weight" else ()
-
-    def param_get(self, name, grad=False):
-        out = np.zeros(self._tensor(name), np.float32)
-        fn = lib().rsys_sim_grad_get if grad else lib().rsys_sim_param_get
-        check(fn(self.h, name.encode(), _ptr(out), out.size))
-        return out
-
-    def param_set(self, name, value):
-        v = np.ascontiguousarray(np.asarray(value, np.float32).reshape(self._tensor(name)))
-        check(lib().rsys_sim_param_set(self.h, name.encode(), _ptr(v), v.size))
-
-    def get_temperature(self):
-        return float(self.param_get("logit_scale"))
 
     def state_dict(self):
         d = {"logit_scale": self.param_get("logit_scale"), "encoder.1.weight": self.param_get("encoder.1.weight")}
@@ -140,9 +108,6 @@ class LTRModel:
     def load_state_dict(self, d):
         for name in ("logit_scale", "encoder.1.weight"):
             self.param_set(name, d[name])
-
-    def zero_grad(self):
-        check(lib().rsys_sim_zero_grad(self.h))
 
     @staticmethod
     def _batch(batch):
@@ -167,18 +132,6 @@ class LTRModel:
         out = (C.c_double * 2)()
         check(lib().rsys_sim_ndcg(self.h, len(src), tgt.shape[1], _ptr(src), _ptr(tgt), _ptr(rel), _ptr(w), C.byref(out)))
         return out[0], out[1]
-
-    def adamw_step(self, lr, clip=1.0):
-        """clip_grad_norm_ + GradScaler.step(AdamW) + zero_grad; returns (norm, skipped)"""
-        norm, skipped = C.c_float(0), C.c_int32(0)
-        check(lib().rsys_sim_adamw_step(self.h, lr, clip, C.byref(norm), C.byref(skipped)))
-        return norm.value, bool(skipped.value)
-
-    def adamw_state(self, name):
-        m, v = np.zeros(self._tensor(name), np.float32), np.zeros(self._tensor(name), np.float32)
-        step = C.c_int32(0)
-        check(lib().rsys_sim_adamw_state_get(self.h, name.encode(), _ptr(m), _ptr(v), m.size, C.byref(step)))
-        return m, v, step.value
 
     def embed_all(self, train_mode=None, seed=None):
         """every id embedded in fp32 [V][E]; held on the device for hard_negatives"""
@@ -330,52 +283,10 @@ def train_epoch(model, dataset, rng=None, lr=None):
     return losses / weights
 
 
-class EarlyStopper:
-    """pairwise_ltr.py:290-315"""
-
-    def __init__(self, patience, rtol):
-        self.patience = patience
-        self.rtol = rtol
-        self.counter = 0
-        self.stop_score = float("inf")
-        self.stop = False
-        self.saved_score = float("inf")
-        self.save_model = False
-
-    def __call__(self, score):
-        assert not self.stop
-        if score < self.stop_score * (1 - self.rtol):
-            self.counter = 0
-            self.stop_score = score
-        else:
-            self.counter += 1
-            if self.counter >= self.patience:
-                self.stop = True
-        if score < self.saved_score:
-            self.saved_score = score
-            self.save_model = True
-        else:
-            self.save_model = False
-
-
 def checkpoint_model(model, epoch, training_loss, test_loss, save, datadir, medium):
     """pairwise_ltr.py:330-355: pairwise.model.{m}.npz under the reference's state-dict names (+ epoch and losses) when `save`, and a row
     of pairwise.model.{m}.csv (header written at epoch -1)"""
-    if save:
-        d = dict(model.state_dict())
-        d.update(epoch=np.array(epoch), training_loss=np.array(training_loss), test_loss=np.array(test_loss))
-        np.savez(os.path.join(datadir, f"pairwise.model.{medium}.npz"), **d)
-    csv_fn = os.path.join(datadir, f"pairwise.model.{medium}.csv")
-    if epoch < 0:
-        with open(csv_fn, "w") as f:
-            f.write(",".join(["epoch", "training_loss", "test_loss", "saved"]) + "\n")
-    with open(csv_fn, "a") as f:
-        f.write(",".join(str(x) for x in [epoch, training_loss, test_loss, 1 if save else 0]) + "\n")
-
-
-def load_checkpoint(path):
-    with np.load(path) as z:
-        return {k: z[k] for k in z.files}
+    write_checkpoint("pairwise.model", model, epoch, training_loss, test_loss, save, datadir, medium)
 
 
 def generate_embeddings(model):
