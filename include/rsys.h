@@ -231,6 +231,41 @@ int32_t rsys_rank_request(rsys_model* m, int32_t medium, int32_t n_groups,
                           const float* retrieval_coef, const float* rating_coefs, float rating_mean, /* [1] or NULL, [2] or NULL */
                           const float* r_in,                                      /* [n_total] or NULL */
                           int32_t* ids_out, float* r_out);                        /* [n_total] each, or NULL */
+/* A page from raw histories in one device pipeline (Inference/compute.jl:512-531 + render.jl:437-474): for n_groups request
+ * states of either medium -- the retrieval forward of their users, rsys_retrieve_request, the page window (render.jl:447-465, the ranked
+ * slice clamped to the retrieved list), the ranking forward at the page's candidates, rsys_rank_request with partialk = the page's last
+ * index.  User embeddings, retrieved ids and rating-head values stay on the device; only the per-group counts are read back in between.
+ * Group g: group_medium[g], pagination (offset[g] >= 0, 1 <= limit[g] <= 1024), penalties[g][4] as rsys_rank_request.  User u (1 <= n_users
+ * <= 4096, every group needs one): group[u]; row u of retrieval_rows, an inference batch of n_users rows of max_sequence_length
+ * interactions laid out as rsys_batch_upload takes it (the ten inference arrays incl. rope_input_pos; targets and masks are not read),
+ * whose query token is token retrieval_token[u] in [0, 2 S) of the row; row u of ranking_prefix, the same ten arrays with prefix_stride
+ * columns per row, of which the first nh = user_desc[u][0] (<= S / 2) are the history part of the user's ranking rows; user_desc[u] =
+ * (nh, userid, gender, source) and user_ts[u] = `time` of the candidate tokens.  The library assembles one ranking row per user and chunk of
+ * at most S - S / 2 candidates on the device: prefix, then per candidate j matchedid = id (+ vocab_0 for medium 1), time = user_ts, status
+ * -1, rating = progress = 0, rope_input_pos = nh, token_mask_ids = nh + j, and reads the rating head at its action token.  Both forwards
+ * run in waves of at most max_rows rows, media mixed.  adapter_slots[4] = the bank slots of (0.retrieval, 0.ranking, 1.retrieval, 1.ranking),
+ * each -1 for the base model, or NULL: every row runs the base model.  List items and selected items once, as CSR over users / groups in
+ * the shapes of rsys_retrieve_request (either may be NULL).  coef_have[m] (NULL: 0): bit 0 = coefs[m][0] is medium m's retrieval
+ * coefficient, bit 1 = coefs[m][1..2] are its rating coefficients and coefs[m][3] its rating mean (rsys_rank_request's).
+ * Output: ids_out[ids_offsets[g] .. ids_offsets[g + 1]) = the page of group g (empty when it starts past the list), ids_offsets[n_groups
+ * + 1]; total_out[g] = min(admissible items, 8192); ids_cap >= the sum of the limits.  fp32 and bf16 models with a replicated table; needs
+ * the serving tables of both request calls.  Synchronous, bitwise reproducible.  Replaces the resident batch; reads and changes no
+ * parameter, gradient or optimizer state.  RSYS_ERR_ARG (outputs untouched): a bad medium, a group without users, limit < 1, malformed
+ * offsets, an incomplete adapter slot, an fp8 model, ids or index-path values out of range, missing tables. */
+int32_t rsys_render_request(rsys_model* m, int32_t n_groups,
+                            const int32_t* group_medium, const int64_t* offset, const int32_t* limit,  /* [n_groups] each */
+                            const float* penalties,                                  /* [n_groups][4] */
+                            int64_t n_users, const int32_t* group,                   /* [n_users] in [0, n_groups) */
+                            const rsys_batch* retrieval_rows, const int32_t* retrieval_token,   /* rows = n_users; [n_users] */
+                            const rsys_batch* ranking_prefix, int32_t prefix_stride, /* rows = n_users, prefix_stride columns per row */
+                            const int32_t* user_desc, const double* user_ts,         /* [n_users][4], [n_users] */
+                            const int32_t* adapter_slots,                            /* [4] or NULL */
+                            const int64_t* hist_offsets,                             /* [n_users + 1] CSR over users, or NULL (no lists) */
+                            const int32_t* hist_medium, const int32_t* hist_ids, const int32_t* hist_status,
+                            const int64_t* sel_offsets,                              /* [n_groups + 1] CSR over groups, or NULL (none selected) */
+                            const int32_t* sel_medium, const int32_t* sel_ids,
+                            const int32_t* coef_have, const float* coefs,            /* [2] or NULL, [2][4] or NULL */
+                            int32_t* ids_out, int64_t ids_cap, int64_t* ids_offsets, int32_t* total_out);
 /* ---- Item-similarity LambdaRank model (Training/item_similarity/pairwise_ltr.py, --features transformer / content).
  * A handle of its own, independent of rsys_model: an rsys_simmodel, passed as an opaque void*.  Trainable parameters by the reference's
  * state-dict names: "encoder.1.weight" [E][F] (weight decay 0.1) and "logit_scale" (scalar, log(1/0.07) at creation, no decay); the frozen

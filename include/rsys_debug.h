@@ -93,6 +93,18 @@ int32_t rsys_rank_gram_get(rsys_model* m, int32_t medium, int32_t n_groups, cons
  * flags); pen[4] (host) = (decay, mmr, same_series, related); picks [min(partialk, n)] = the position chosen per round; 1 <= n <= 1024 */
 int32_t rsys_op_rerank(int32_t n, int32_t partialk, const float* pen, const float* r, const float* gram, const int32_t* ss_bits,
                        const int32_t* related_bits, int32_t* picks);
+/* rsys_render_request's intermediates.  rsys_render_debug_keep(m, 1): every following request copies its intermediates to host memory as
+ * it goes (off again with 0, which also drops them).  rsys_render_debug_get: *bytes = the size of the array kept under `key` by the last
+ * request; it is copied to out when out != NULL and cap >= *bytes.  Keys: "forwards" int32 [2] (forwards of the last request: retrieval,
+ * ranking; kept always); "queries" f32 [n_users][D] (the query buffer, user order); "ret.counts" int32 [n_groups]; "ret.ids" int32 (the
+ * groups' retrieved ids, counts[g] each, group order); "rows" int32 [n_rows][6] = (user, group, first candidate slot, candidates, row in
+ * its wave, wave) per ranking row in run order; "batch.<array>" (userid, token_mask_ids, gender, source, matchedid, status, rope_input_pos
+ * int32; rating, progress f32; time f64) [n_rows][S], the assembled ranking rows; "token_index" int32 (the rows' action tokens, flat within
+ * their wave); "groups" int32 [n_active][6] = (group, medium, first slot in "r" / "picks", candidates, sidx, eidx) per group with a page;
+ * "rm_users" int32 [n][3] = (user, first value in "r_masked", values); "r_masked" f32; "r" f32 (ranking scores) and "picks" int32 (picked
+ * positions; the slots after a group's eidx rounds hold -1). */
+int32_t rsys_render_debug_keep(rsys_model* m, int32_t on);
+int32_t rsys_render_debug_get(rsys_model* m, const char* key, void* out, int64_t cap, int64_t* bytes);
 /* the last rsys_sim_forward_backward / rsys_sim_ndcg call of an item-similarity handle (host arrays): "ranks" int32 [n_q][n] (1-based
  * order of each slot), "scores" f32 [n_q][n] (x), "dldx" f32 [n_q][n] (d batch loss / dx), "dropout_mask" uint8 [rows][F] (1 = kept, the
  * mask of every gathered row: rows = 2 n_q n in training, [source copies | targets], slot-major; all ones without dropout) */

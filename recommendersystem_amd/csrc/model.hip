@@ -396,6 +396,7 @@ int model_destroy(Model* m) {
   rank_free(m);
   retrieve_eval_free(m);
   adapter_bank_free(m);
+  render_free(m);
   if (m->copy_stream) { hipStreamSynchronize(m->copy_stream); hipStreamDestroy(m->copy_stream); }
   if (m->h_stage) hipHostFree(m->h_stage);
   if (m->slot_stage[1]) hipHostFree(m->slot_stage[1]);
@@ -641,6 +642,37 @@ static int build_exchange_plan(Model* m, int N) {
   return RSYS_OK;
 }
 
+// Where the arrays of a batch of N interactions sit in a slot's blob, back to back at 64-byte steps: the one layout of uploaded
+// (batch_stage) and device-assembled (model_batch_device_begin) batches.
+struct BlobLayout {
+  size_t time, userid, tmid, gender, source, matchedid, status, rating, progress, label[6], weight[6], position[6], wm, rm, rope, bytes;
+};
+static BlobLayout blob_layout(size_t N) {
+  BlobLayout L{};
+  size_t off = 0;
+  auto place = [&](size_t bytes) { const size_t at = off; off += (bytes + 63) / 64 * 64; return at; };
+  L.time = place(N * 8);
+  L.userid = place(N * 4); L.tmid = place(N * 4); L.gender = place(N * 4); L.source = place(N * 4);
+  L.matchedid = place(N * 4); L.status = place(N * 4); L.rating = place(N * 4); L.progress = place(N * 4);
+  for (int k = 0; k < 6; ++k) { L.label[k] = place(N * 4); L.weight[k] = place(N * 4); L.position[k] = place(N * 4); }
+  L.wm = place(N); L.rm = place(N);
+  L.rope = place(2 * N * 4);
+  L.bytes = off;
+  return L;
+}
+// the device addresses of a layout's arrays in `blob` (the mask_tokens outputs and the sizes stay the model's own)
+static void blob_point(Model* m, unsigned char* blob, const BlobLayout& L, BatchDev& d, unsigned char** wm, unsigned char** rm, int** rope) {
+  d.time = (const double*)(blob + L.time);
+  d.userid = (const int*)(blob + L.userid); d.tmid = (const int*)(blob + L.tmid);
+  d.gender = (const int*)(blob + L.gender); d.source = (const int*)(blob + L.source);
+  d.matchedid = (const int*)(blob + L.matchedid); d.status = (const int*)(blob + L.status);
+  d.rating = (const float*)(blob + L.rating); d.progress = (const float*)(blob + L.progress);
+  for (int k = 0; k < 6; ++k) {
+    d.label[k] = (const float*)(blob + L.label[k]); d.weight[k] = (const float*)(blob + L.weight[k]); d.position[k] = (const int*)(blob + L.position[k]);
+  }
+  *wm = blob + L.wm; *rm = blob + L.rm; *rope = (int*)(blob + L.rope);
+}
+
 // Checks a host batch and packs it into staging buffer `slot` (pinned); `d` and the flag outputs receive the device addresses the
 // arrays will have in that slot's blob.  Index paths are checked on the host BEFORE anything is written.
 struct StagedBatch { BatchDev bd; bool has_masks = false, has_rope_pos = false; unsigned char *d_wm = nullptr, *d_rm = nullptr; int* d_rope_pos = nullptr; size_t bytes = 0;
@@ -691,28 +723,22 @@ static int batch_stage(Model* m, const rsys_batch* b, int slot, StagedBatch& out
   }
   // pack (pinned staging) -> one H2D -> the device arrays sit back to back in the slot's blob
   unsigned char* blob = m->slot_blob[slot]; unsigned char* stage = m->slot_stage[slot];
-  BatchDev d = m->bd;    // (the mask_tokens outputs and the sizes are the model's own; only the input arrays move)
-  size_t off = 0;
-  auto place = [&](const void* src, size_t bytes) -> void* {
-    void* dev = blob + off;
-    if (src != nullptr) memcpy(stage + off, src, bytes);
-    off += (bytes + 63) / 64 * 64;
-    return dev;
-  };
-  d.time = (const double*)place(b->time, N * 8);
-  d.userid = (const int*)place(b->userid, N * 4); d.tmid = (const int*)place(b->token_mask_ids, N * 4);
-  d.gender = (const int*)place(b->gender, N * 4); d.source = (const int*)place(b->source, N * 4);
-  d.matchedid = (const int*)place(b->matchedid, N * 4); d.status = (const int*)place(b->status, N * 4);
-  d.rating = (const float*)place(b->rating, N * 4); d.progress = (const float*)place(b->progress, N * 4);
+  const BlobLayout L = blob_layout(N);
+  if (L.bytes > m->raw_bytes) { set_error("batch upload: staging buffer too small"); return RSYS_ERR_STATE; }
+  auto put = [&](size_t at, const void* src, size_t bytes) { if (src != nullptr) memcpy(stage + at, src, bytes); };
+  put(L.time, b->time, N * 8);
+  put(L.userid, b->userid, N * 4); put(L.tmid, b->token_mask_ids, N * 4); put(L.gender, b->gender, N * 4); put(L.source, b->source, N * 4);
+  put(L.matchedid, b->matchedid, N * 4); put(L.status, b->status, N * 4); put(L.rating, b->rating, N * 4); put(L.progress, b->progress, N * 4);
   for (int k = 0; k < 6; ++k) {   // (status targets may be absent: their slots stay unwritten, nothing reads them)
-    d.label[k] = (const float*)place(b->label[k], N * 4); d.weight[k] = (const float*)place(b->weight[k], N * 4);
-    d.position[k] = (const int*)place(b->position[k], N * 4);
+    put(L.label[k], b->label[k], N * 4); put(L.weight[k], b->weight[k], N * 4); put(L.position[k], b->position[k], N * 4);
   }
+  put(L.wm, b->watch_mask, N); put(L.rm, b->rating_mask, N);
   out.has_masks = b->watch_mask != nullptr;
-  out.d_wm = (unsigned char*)place(b->watch_mask, N); out.d_rm = (unsigned char*)place(b->rating_mask, N);
   out.has_rope_pos = b->rope_input_pos != nullptr;
-  out.d_rope_pos = (int*)place(out.has_rope_pos ? pos.data() : nullptr, 2 * N * 4);
-  if (off > m->raw_bytes) { set_error("batch upload: staging buffer too small"); return RSYS_ERR_STATE; }
+  put(L.rope, out.has_rope_pos ? pos.data() : nullptr, 2 * N * 4);
+  BatchDev d = m->bd;    // (the mask_tokens outputs and the sizes are the model's own; only the input arrays move)
+  blob_point(m, blob, L, d, &out.d_wm, &out.d_rm, &out.d_rope_pos);
+  const size_t off = L.bytes;
   out.bd = d; out.bytes = off;
   return RSYS_OK;
 }
@@ -746,6 +772,29 @@ int model_batch_upload(Model* m, const rsys_batch* b) {
   HIP_CHECK(hipStreamSynchronize(s));
   if (m->sharded) RC(build_exchange_plan(m, (int)N));
   m->cur_rows = b->rows;
+  return RSYS_OK;
+}
+
+// The resident batch as device arrays for a kernel to fill (rsys_render_request's ranking rows): the layout of batch_stage for `rows`
+// rows in the current slot's blob, nothing copied.  Everything enqueued so far that reads the blob runs before the kernel that fills it
+// (same stream); the slot's staging buffer is not touched.
+int model_batch_device_begin(Model* m, int rows, BatchDevRows* out) {
+  ARG_CHECK(rows >= 1 && rows <= m->rows_max, "batch rows must be in [1, max_rows]");
+  ARG_CHECK(!m->sharded, "device-assembled batch: replicated table only");
+  HIP_CHECK(hipSetDevice(m->device));
+  if (m->pending.valid) HIP_CHECK(hipEventSynchronize(m->ev_copy_done));
+  m->pending.valid = false;
+  const BlobLayout L = blob_layout((size_t)rows * m->S);
+  if (L.bytes > m->raw_bytes) { set_error("device-assembled batch: blob too small"); return RSYS_ERR_STATE; }
+  BatchDev d = m->bd;
+  blob_point(m, m->slot_blob[m->cur_slot], L, d, &m->d_wm, &m->d_rm, &out->rope_pos);
+  out->time = (double*)d.time; out->userid = (int*)d.userid; out->tmid = (int*)d.tmid; out->gender = (int*)d.gender;
+  out->source = (int*)d.source; out->matchedid = (int*)d.matchedid; out->status = (int*)d.status; out->rating = (float*)d.rating;
+  out->progress = (float*)d.progress;
+  m->bd = d;
+  m->has_masks = false; m->has_rope_pos = true; m->d_rope_pos = out->rope_pos;
+  m->tok_index_valid = false; m->split_plan_valid = false; m->u_bound_host = 0;
+  m->cur_rows = rows;
   return RSYS_OK;
 }
 
@@ -846,17 +895,42 @@ int model_forward_backward(Model* m, int evaluate, const float task_w[4], float 
 // token indices, host) restricts the output to those tokens: the rows are gathered on the device, the rating head runs on them
 // only, and what crosses PCIe is n_sel rows instead of rows * 2S.
 template <typename T>
+static int infer_rows_t(Model* m, int task, const int* d_sel, int64_t ntok, float* dst, const float** rows_f32);
+
+template <typename T>
 static int infer_t(Model* m, int task, const int32_t* sel, int64_t n_sel, float* out, int64_t n) {
   const int rows = m->cur_rows, N = rows * m->S, NT = 2 * N, D = m->D;
   hipStream_t s = m->stream;
-  BatchDev b = m->bd;
-  const int KB = m->K * m->rows_max;
   if (sel != nullptr) {
     ARG_CHECK(n_sel <= NT, "selection: more tokens than the batch holds");
     for (int64_t i = 0; i < n_sel; ++i) ARG_CHECK(sel[i] >= 0 && sel[i] < NT, "selection: token index out of range");
   }
   const int64_t ntok = sel != nullptr ? n_sel : NT;
   ARG_CHECK(n == (task == 0 ? ntok * D : ntok), task == 0 ? "retrieval output has tokens*D floats" : "ranking output has one float per token");
+  int* d_sel = nullptr;
+  if (sel != nullptr) {
+    d_sel = (int*)m->gf;                       // N * 32 floats: room for NT indices (a backward workspace: the forward does not touch it)
+    HIP_CHECK(hipMemcpyAsync(d_sel, sel, (size_t)n_sel * 4, hipMemcpyHostToDevice, s));
+  }
+  // predictions gather in a device vector (rows_max * H * T floats >= NT; only the attention backward uses it otherwise)
+  const float* f = nullptr;
+  RC(infer_rows_t<T>(m, task, d_sel, ntok, task == 1 ? m->delta : nullptr, &f));
+  HIP_CHECK(hipMemcpyAsync(out, task == 0 ? f : m->delta, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipStreamSynchronize(s));
+  return RSYS_OK;
+}
+
+// The one body of the inference forward over the resident batch (rsys_infer, rsys_infer_select[_adapters], rsys_render_request): the batch
+// is used as given, the trunk runs, and the rows to report -- all of m->out, or the ntok tokens d_sel (device) names, gathered into the
+// (free) dx buffer of the backward -- become: task 0, fp32 trunk rows [ntok][D] on the device, in dst when given, else where they already
+// are (*rows_f32 says where); task 1, the rating head (model.py:355-359) on those rows only, in chunks of the head workspace, into dst.
+// Stream-ordered, no host wait.
+template <typename T>
+static int infer_rows_t(Model* m, int task, const int* d_sel, int64_t ntok, float* dst, const float** rows_f32) {
+  const int rows = m->cur_rows, N = rows * m->S, D = m->D;
+  hipStream_t s = m->stream;
+  BatchDev b = m->bd;
+  const int KB = m->K * m->rows_max;
   m->f8_tcopies = false;
   HIP_CHECK(hipMemcpyAsync(b.m_tmid, b.tmid, N * 4, hipMemcpyDeviceToDevice, s));
   HIP_CHECK(hipMemcpyAsync(b.m_matchedid, b.matchedid, N * 4, hipMemcpyDeviceToDevice, s));
@@ -866,35 +940,47 @@ static int infer_t(Model* m, int task, const int32_t* sel, int64_t n_sel, float*
   m->drop_active = false;
   m->top_is_sparse = false;
   RC(forward_trunk<T>(m));
-  // the rows to report: all of m->out, or the selected ones gathered into the (free) dx buffer of the backward
   const T* src = AT<T>(m->out);
-  if (sel != nullptr) {
-    int* d_sel = (int*)m->gf;                       // N * 32 floats: room for NT indices
-    HIP_CHECK(hipMemcpyAsync(d_sel, sel, (size_t)n_sel * 4, hipMemcpyHostToDevice, s));
-    RC(launch_gather_rows_plain<T>(AT<T>(m->out), D, d_sel, 0, AT<T>(m->dhn), (int)n_sel, D, s));
+  if (d_sel != nullptr) {
+    RC(launch_gather_rows_plain<T>(AT<T>(m->out), D, d_sel, 0, AT<T>(m->dhn), (int)ntok, D, s));
     src = AT<T>(m->dhn);
   }
   if (task == 0) {
-    // float32 on the device (the head-gradient buffer is free in an inference pass), one copy out
-    const float* f = (const float*)src;
-    if (m->bf16_mode) { RC(launch_widen<T>(src, m->gy, ntok * D, s)); f = m->gy; }
-    HIP_CHECK(hipMemcpyAsync(out, f, (size_t)ntok * D * 4, hipMemcpyDeviceToHost, s));
-    HIP_CHECK(hipStreamSynchronize(s));
+    // float32 on the device (the head-gradient buffer is free in an inference pass)
+    if (m->bf16_mode) {
+      float* w = dst ? dst : m->gy;
+      RC(launch_widen<T>(src, w, ntok * D, s));
+      *rows_f32 = w;
+    } else if (dst) {
+      HIP_CHECK(hipMemcpyAsync(dst, src, (size_t)ntok * D * 4, hipMemcpyDeviceToDevice, s));
+      *rows_f32 = dst;
+    } else {
+      *rows_f32 = (const float*)src;
+    }
     return RSYS_OK;
   }
-  // rating_head (model.py:355-359) in chunks of the head workspace; predictions gather in a device vector
-  float* pred = m->delta;   // (rows_max * H * T floats >= NT; only the attention backward uses it otherwise)
   for (int64_t r0 = 0; r0 < ntok; r0 += KB) {
     const int nr = (int)std::min<int64_t>(KB, ntok - r0);
     GemmParams p{};
     p.A = (const unsigned char*)src + (size_t)r0 * D * m->esz; p.lda = D; p.B = W<T>(m, m->o_r0w); p.ldb = D; p.C = m->z; p.ldc = D;
     p.M = nr; p.N = D; p.K = D; p.epi = EPI_GELU; p.bias = m->P + m->o_r0b; p.C2 = m->hact; p.ldc2 = D;
     RC(gemm<T>(m, "gemm_rating_fwd", p, false, false, false));
-    RC(launch_rowdot<T>(AT<T>(m->hact), m->P + m->o_r2w, m->P + m->o_r2b, pred + r0, nr, D, s));
+    RC(launch_rowdot<T>(AT<T>(m->hact), m->P + m->o_r2w, m->P + m->o_r2b, dst + r0, nr, D, s));
   }
-  HIP_CHECK(hipMemcpyAsync(out, pred, (size_t)ntok * 4, hipMemcpyDeviceToHost, s));
-  HIP_CHECK(hipStreamSynchronize(s));
   return RSYS_OK;
+}
+
+int model_infer_device(Model* m, int task, const int32_t* row_adapter, const int* d_sel, int n_sel, float* d_out) {
+  ARG_CHECK(m->cur_rows > 0, "no batch uploaded");
+  ARG_CHECK(task == 0 || task == 1, "task: 0 retrieval, 1 ranking");
+  ARG_CHECK(!m->fp8, "device-resident inference: fp32 and bf16 models only");
+  ARG_CHECK(d_sel && d_out && n_sel >= 1 && n_sel <= 2 * m->cur_rows * m->S, "selection: 1 <= tokens <= the batch's");
+  HIP_CHECK(hipSetDevice(m->device));
+  if (row_adapter) RC(adapter_bind_rows(m, row_adapter));
+  const float* f = nullptr;
+  const int rc = m->bf16_mode ? infer_rows_t<bf16>(m, task, d_sel, n_sel, d_out, &f) : infer_rows_t<float>(m, task, d_sel, n_sel, d_out, &f);
+  adapter_unbind_rows(m);
+  return rc;
 }
 
 // ItemEmbedding.forward over every item id (model.py:139-145; what register.py:27-29 stores as the watch-head weights):

@@ -49,6 +49,7 @@ struct RetrievalTables;  // retrieve_request.hip
 struct RankTables;       // rank_request.hip
 struct EvalWs;           // retrieve_eval.hip
 struct AdapterBank;      // adapter_bank.hip
+struct RenderState;      // render_request.hip
 
 struct Model {
   rsys_config cfg;
@@ -276,6 +277,7 @@ struct Model {
   // every row's own update to q and v; every other pass leaves it null and launches what it always has
   AdapterBank* bank = nullptr;
   const int* bank_rows = nullptr;
+  RenderState* render = nullptr;        // rsys_render_request's workspace, forward counters and kept intermediates (allocated on first use)
 };
 
 struct Optimizer {
@@ -315,6 +317,15 @@ void adapter_bank_free(Model* m);
 template <typename T> int adapter_bank_stage_a(Model* m, int l, const T* xn);                      // La = xn . [A_q; A_v][slot]^T
 template <typename T> int adapter_bank_stage_b(Model* m, int l, T* qkv, const int* rope_pos);      // q, v += 2 La . B[slot]^T (q rotated)
 int model_infer_adapters(Model* m, int task, const int32_t* row_adapter, const int32_t* token_index, int64_t n_tokens, float* out, int64_t n);
+// A batch whose arrays a kernel fills on the device (render_request.hip): makes `rows` rows the resident batch without a host copy and
+// returns where its arrays live in the current slot's blob (target arrays stay as they are: an inference forward never reads them).
+// rope_pos holds the per-token positions (2 p, 2 p + 1 for interaction position p), as rsys_batch_upload derives them.
+struct BatchDevRows { double* time; int *userid, *tmid, *gender, *source, *matchedid, *status; float *rating, *progress; int* rope_pos; };
+int model_batch_device_begin(Model* m, int rows, BatchDevRows* out);
+// the forward of rsys_infer_select_adapters over the resident batch with the selection (n_sel flat token indices) and the result
+// (task 0: n_sel x D trunk rows, task 1: n_sel rating-head values, fp32) both on the device; row_adapter (host) may be null (base model);
+// stream-ordered, no host wait
+int model_infer_device(Model* m, int task, const int32_t* row_adapter, const int* d_sel, int n_sel, float* d_out);
 int model_item_table(Model* m, float* out, int64_t n);
 // the fp32 item table rows [V_m][D] of `medium` on the model's device (rsys_sim_features_from_model); the model's stream is idle on return
 int model_item_table_device(Model* m, int medium, const float** rows, int64_t* Vm, int* D);
@@ -335,8 +346,9 @@ int model_retrieve_topk(Model* m, int medium, const float* queries, int64_t nq, 
 void retrieve_free(Model* m);
 // the same pipeline with a device-side initialiser of the group score rows sc [n_groups][V_m] (prior and NaN masks)
 using RetrieveInit = std::function<int(float* sc, hipStream_t s)>;
+struct RetrieveDev;
 int model_retrieve_run(Model* m, int medium, const float* queries, int64_t nq, const int32_t* group, int32_t ng, const RetrieveInit& init,
-                       int32_t k, int32_t* ids_out, float* scores_out, int32_t* counts_out);
+                       int32_t k, int32_t* ids_out, float* scores_out, int32_t* counts_out, RetrieveDev* dev = nullptr);
 // z = Q F_m^T and lse of one chunk of <= RETRIEVE_CHUNK query rows (part: nc * RETRIEVE_LSE_SPLIT float2), as rsys_retrieve_topk scores
 constexpr int RETRIEVE_CHUNK = 256, RETRIEVE_LSE_SPLIT = 64;
 template <typename T>
@@ -351,6 +363,13 @@ int model_retrieve_request(Model* m, int medium, const float* queries, int64_t n
                            const int32_t* sel_medium, const int32_t* sel_ids, int32_t k, int32_t* ids_out, float* scores_out,
                            int32_t* counts_out);
 void retrieve_tables_free(Model* m);
+// the same request with its queries read from, and its result left in, device memory (rsys_render_request): d_queries [nq][D] fp32;
+// after the call *d_ids / *d_vals point at the [ng][k] result rows in the retrieval workspace (valid until the next retrieval call on the
+// model) and only counts_out has crossed to the host
+struct RetrieveDev { const float* d_queries = nullptr; int32_t* d_ids = nullptr; float* d_vals = nullptr; };
+int model_retrieve_request_dev(Model* m, int medium, RetrieveDev* dev, int64_t nq, const int32_t* group, int32_t ng, const int64_t* hist_off,
+                               const int32_t* hist_medium, const int32_t* hist_ids, const int32_t* hist_status, const int64_t* sel_off,
+                               const int32_t* sel_medium, const int32_t* sel_ids, int32_t k, int32_t* counts_out);
 const float* retrieve_similarity_table(Model* m, int medium, int64_t* dim);   // "embeddings.{m}" [V_m][dim] on the device, or null
 // rank_request.hip: ranking and diversity reranking of retrieved candidates (rsys_rank_related_set, rsys_rank_request, test hooks)
 int model_rank_related_set(Model* m, int medium, int64_t n, const int64_t* colptr, const int32_t* rowval, const float* nzval);
@@ -360,7 +379,28 @@ int model_rank_request(Model* m, int medium, int32_t ng, const int64_t* cand_off
                        const float* retrieval_coef, const float* rating_coefs, float rating_mean, const float* r_in, int32_t* ids_out,
                        float* r_out);
 int model_rank_gram(Model* m, int medium, int32_t ng, const int64_t* cand_off, const int32_t* cand_ids, float* out, int64_t n_out);
+// the same request with candidates, queries and r_masked read from device memory (rsys_render_request): d_cand [n_total] distinct ids in
+// [0, V_m) per group (a retrieval result), d_queries [nu][D], d_rm ragged over users.  Group g's page = picks [page_lo[g], page_hi[g]) of
+// its pick order, written to page_out (host) at page_off[g]; keep_r / keep_picks (host, n_total each, may be null) receive the ranking
+// scores and the picked positions.  Only those cross to the host.
+struct RankDev { const int32_t* d_cand; const float* d_queries; const float* d_rm; const int32_t *page_lo, *page_hi; const int64_t* page_off;
+                 int32_t* page_out; float* keep_r; int32_t* keep_picks; };
+int model_rank_request_dev(Model* m, int medium, int32_t ng, const int64_t* cand_off, const RankDev* dev, const int32_t* partialk,
+                           const float* penalties, int64_t nu, const int32_t* group, int64_t n_rm, const int64_t* hist_off,
+                           const int32_t* hist_medium, const int32_t* hist_ids, const int32_t* hist_status, const float* retrieval_coef,
+                           const float* rating_coefs, float rating_mean);
 void rank_free(Model* m);
+// render_request.hip: a page from raw histories in one device pipeline (rsys_render_request) and its test hooks
+int model_render_request(Model* m, int32_t ng, const int32_t* group_medium, const int64_t* offset, const int32_t* limit, const float* penalties,
+                         int64_t nu, const int32_t* group, const rsys_batch* retrieval_rows, const int32_t* retrieval_token,
+                         const rsys_batch* ranking_prefix, int32_t prefix_stride, const int32_t* user_desc, const double* user_ts,
+                         const int32_t* adapter_slots, const int64_t* hist_off, const int32_t* hist_medium, const int32_t* hist_ids,
+                         const int32_t* hist_status, const int64_t* sel_off, const int32_t* sel_medium, const int32_t* sel_ids,
+                         const int32_t* coef_have, const float* coefs, int32_t* ids_out, int64_t ids_cap, int64_t* ids_offsets,
+                         int32_t* total_out);
+int render_debug_keep(Model* m, int on);
+int render_debug_get(Model* m, const char* key, void* out, int64_t cap, int64_t* bytes);
+void render_free(Model* m);
 int op_rerank(int32_t n, int32_t partialk, const float* pen, const float* r, const float* gram, const int32_t* ss_bits,
               const int32_t* related_bits, int32_t* picks);
 int op_topk(const float* scores, int64_t ld, int32_t rows, int32_t V, int32_t k, int32_t* ids, float* vals, int32_t* counts);

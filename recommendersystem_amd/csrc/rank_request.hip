@@ -229,6 +229,39 @@ __global__ void __launch_bounds__(RK_MAXN) rerank_kernel(const RankGroup* grp, c
   }
 }
 
+// sorted copy of group blockIdx.x's candidate ids with their positions (what make_groups sorts on the host when the ids are there): a
+// bitonic sort of (id, position) keys in LDS, one candidate per lane; the ids of a group are distinct, so the order is total
+__global__ void __launch_bounds__(RK_MAXN) sort_cand_kernel(const RankGroup* grp, const int32_t* cand, int32_t* sorted_ids, int32_t* sorted_pos) {
+  const RankGroup gd = grp[blockIdx.x];
+  const int n = gd.n, i = threadIdx.x;
+  __shared__ unsigned long long key[RK_MAXN];
+  key[i] = i < n ? ((unsigned long long)(unsigned)cand[gd.c0 + i] << 32) | (unsigned)i : ~0ull;
+  __syncthreads();
+  for (int size = 2; size <= RK_MAXN; size <<= 1) {
+    for (int stride = size >> 1; stride > 0; stride >>= 1) {
+      if (i < RK_MAXN / 2) {
+        const int lo = 2 * stride * (i / stride) + (i % stride), hi = lo + stride;
+        const bool asc = (lo & size) == 0;
+        const unsigned long long a = key[lo], b = key[hi];
+        if ((a > b) == asc) { key[lo] = b; key[hi] = a; }
+      }
+      __syncthreads();
+    }
+  }
+  if (i < n) {
+    sorted_ids[gd.c0 + i] = (int32_t)(key[i] >> 32);
+    sorted_pos[gd.c0 + i] = (int32_t)(key[i] & 0xffffffffu);
+  }
+}
+
+// the page of group blockIdx.x: the ids picked in rounds [lo[g], hi[g]) to page[off[g] ..]
+__global__ void __launch_bounds__(RK_THREADS) page_gather_kernel(const RankGroup* grp, const int32_t* cand, const int* picks, const int32_t* lo,
+                                                                 const int32_t* hi, const int64_t* off, int32_t* page) {
+  const int g = blockIdx.x;
+  const RankGroup gd = grp[g];
+  for (int t = lo[g] + threadIdx.x; t < hi[g]; t += RK_THREADS) page[off[g] + t - lo[g]] = cand[gd.c0 + picks[gd.c0 + t]];
+}
+
 #define RK_LAUNCH_CHECK() HIP_CHECK(hipGetLastError())
 
 struct Carve {
@@ -247,9 +280,10 @@ struct Groups {
   long long N = 0, gram = 0, bits = 0, flags = 0;
 };
 
+// ids_on_device: the ids are a retrieval result in device memory (distinct and in range by construction); sort_cand_kernel sorts them there
 int make_groups(const char* who, int ng, const int64_t* cand_off, const int32_t* cand_ids, const int32_t* partialk, const float* pen, int Vm,
-                Groups& G) {
-  ARG_CHECK(cand_off && cand_ids, std::string(who) + ": candidate offsets and ids are required");
+                Groups& G, bool ids_on_device = false) {
+  ARG_CHECK(cand_off && (cand_ids || ids_on_device), std::string(who) + ": candidate offsets and ids are required");
   ARG_CHECK(cand_off[0] == 0, std::string(who) + ": cand_offsets[0] must be 0");
   G.g.resize(ng);
   for (int j = 0; j < ng; ++j) {
@@ -267,6 +301,7 @@ int make_groups(const char* who, int ng, const int64_t* cand_off, const int32_t*
     if (pen) { d.decay = pen[4 * j]; d.mmr = pen[4 * j + 1]; d.ss = pen[4 * j + 2]; d.rel = pen[4 * j + 3]; }
   }
   G.N = cand_off[ng];
+  if (ids_on_device) return RSYS_OK;
   G.sorted_ids.resize((size_t)G.N); G.sorted_pos.resize((size_t)G.N);
   std::vector<int32_t> idx;
   for (int j = 0; j < ng; ++j) {
@@ -373,10 +408,13 @@ template <typename T>
 static int rank_t(Model* m, int medium, int ng, const Groups& gs, const int32_t* cand_ids, const float* queries, int64_t nu,
                   const std::vector<int32_t>& ugroup, const float* r_masked, int64_t n_rm, const std::vector<int64_t>& rm_off,
                   const std::vector<int32_t>& ent_g, const std::vector<int32_t>& ent_id, const float* retrieval_coef,
-                  const float* rating_coefs, float rating_mean, const float* r_in, const float* E, int dim, int32_t* ids_out, float* r_out) {
+                  const float* rating_coefs, float rating_mean, const float* r_in, const float* E, int dim, int32_t* ids_out, float* r_out,
+                  const RankDev* dev = nullptr) {
   const int D = m->D, Vm = medium == 0 ? m->V0 : m->V1, vs = medium == 0 ? 0 : m->V0;
   hipStream_t s = m->stream;
-  const bool score = r_in == nullptr, rerank = ids_out != nullptr;
+  const bool score = r_in == nullptr, rerank = ids_out != nullptr || dev != nullptr;
+  int64_t npage = 0;
+  if (dev) for (int g = 0; g < ng; ++g) npage = std::max<int64_t>(npage, dev->page_off[g] + dev->page_hi[g] - dev->page_lo[g]);
   // users of each group in user order; per chunk of RETRIEVE_CHUNK users the range of them it holds
   const int nchunks = score ? (int)((nu + RETRIEVE_CHUNK - 1) / RETRIEVE_CHUNK) : 0;
   std::vector<int> goff(ng + 1, 0), members((size_t)nu);
@@ -399,7 +437,8 @@ static int rank_t(Model* m, int medium, int ng, const Groups& gs, const int32_t*
   const int64_t nent = (int64_t)ent_g.size();
   auto layout = [&](Carve& c, float** qf, T** qt, float** lse, float2** part, float** z, int** d_members, int2** d_ranges, float** d_rm,
                     int64_t** d_rmoff, RankGroup** d_grp, int32_t** d_cand, int32_t** d_sid, int32_t** d_spos, float** sc, float** G,
-                    unsigned** bits, unsigned** flags, int32_t** d_eg, int32_t** d_eid, int** picks) {
+                    unsigned** bits, unsigned** flags, int32_t** d_eg, int32_t** d_eid, int** picks, int32_t** d_plo, int32_t** d_phi,
+                    int64_t** d_poff, int32_t** d_page) {
     *qf = c.take<float>(score ? (size_t)nu * D : 0);
     *qt = is_bf16<T>::value ? c.take<T>(score ? (size_t)nu * D : 0) : (T*)*qf;
     *lse = c.take<float>(score ? nu : 0);
@@ -420,39 +459,55 @@ static int rank_t(Model* m, int medium, int ng, const Groups& gs, const int32_t*
     *d_eg = c.take<int32_t>(nent);
     *d_eid = c.take<int32_t>(nent);
     *picks = c.take<int>(rerank ? gs.N : 0);
+    *d_plo = c.take<int32_t>(dev ? ng : 0);
+    *d_phi = c.take<int32_t>(dev ? ng : 0);
+    *d_poff = c.take<int64_t>(dev ? ng : 0);
+    *d_page = c.take<int32_t>(npage);
   };
   float *qf, *lse, *z, *d_rm, *sc, *G; T* qt; float2* part; int *d_members, *picks; int2* d_ranges; int64_t* d_rmoff; RankGroup* d_grp;
-  int32_t *d_cand, *d_sid, *d_spos, *d_eg, *d_eid; unsigned *bits, *flags;
+  int32_t *d_cand, *d_sid, *d_spos, *d_eg, *d_eid, *d_plo, *d_phi, *d_page; int64_t* d_poff; unsigned *bits, *flags;
   Carve probe{nullptr};
   layout(probe, &qf, &qt, &lse, &part, &z, &d_members, &d_ranges, &d_rm, &d_rmoff, &d_grp, &d_cand, &d_sid, &d_spos, &sc, &G, &bits, &flags,
-         &d_eg, &d_eid, &picks);
+         &d_eg, &d_eid, &picks, &d_plo, &d_phi, &d_poff, &d_page);
   RC(ensure_ws(m, probe.off));
   Carve c{(char*)m->rank->ws};
   layout(c, &qf, &qt, &lse, &part, &z, &d_members, &d_ranges, &d_rm, &d_rmoff, &d_grp, &d_cand, &d_sid, &d_spos, &sc, &G, &bits, &flags,
-         &d_eg, &d_eid, &picks);
+         &d_eg, &d_eid, &picks, &d_plo, &d_phi, &d_poff, &d_page);
+  // (dev: candidates, queries and r_masked are device arrays; same kernels on the same values)
+  const hipMemcpyKind in_kind = dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+  if (dev) { cand_ids = dev->d_cand; queries = dev->d_queries; r_masked = dev->d_rm; }
 
   tic(m, "rank_prep");
   HIP_CHECK(hipMemcpyAsync(d_grp, gs.g.data(), (size_t)ng * sizeof(RankGroup), hipMemcpyHostToDevice, s));
-  HIP_CHECK(hipMemcpyAsync(d_cand, cand_ids, (size_t)gs.N * 4, hipMemcpyHostToDevice, s));
+  HIP_CHECK(hipMemcpyAsync(d_cand, cand_ids, (size_t)gs.N * 4, in_kind, s));
   if (score) {
-    HIP_CHECK(hipMemcpyAsync(qf, queries, (size_t)nu * D * 4, hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(qf, queries, (size_t)nu * D * 4, in_kind, s));
     if constexpr (is_bf16<T>::value) RC(launch_cast<T>(qf, qt, (long long)nu * D, s));
     HIP_CHECK(hipMemcpyAsync(d_members, members.data(), members.size() * 4, hipMemcpyHostToDevice, s));
     HIP_CHECK(hipMemcpyAsync(d_ranges, ranges.data(), ranges.size() * sizeof(int2), hipMemcpyHostToDevice, s));
-    HIP_CHECK(hipMemcpyAsync(d_rm, r_masked, (size_t)n_rm * 4, hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(d_rm, r_masked, (size_t)n_rm * 4, in_kind, s));
     HIP_CHECK(hipMemcpyAsync(d_rmoff, rm_off.data(), (size_t)nu * 8, hipMemcpyHostToDevice, s));
   } else {
     HIP_CHECK(hipMemcpyAsync(sc, r_in, (size_t)gs.N * 4, hipMemcpyHostToDevice, s));
   }
   if (rerank) {
-    HIP_CHECK(hipMemcpyAsync(d_sid, gs.sorted_ids.data(), (size_t)gs.N * 4, hipMemcpyHostToDevice, s));
-    HIP_CHECK(hipMemcpyAsync(d_spos, gs.sorted_pos.data(), (size_t)gs.N * 4, hipMemcpyHostToDevice, s));
+    if (dev) {
+      sort_cand_kernel<<<ng, RK_MAXN, 0, s>>>(d_grp, d_cand, d_sid, d_spos);
+      RK_LAUNCH_CHECK();
+      HIP_CHECK(hipMemcpyAsync(d_plo, dev->page_lo, (size_t)ng * 4, hipMemcpyHostToDevice, s));
+      HIP_CHECK(hipMemcpyAsync(d_phi, dev->page_hi, (size_t)ng * 4, hipMemcpyHostToDevice, s));
+      HIP_CHECK(hipMemcpyAsync(d_poff, dev->page_off, (size_t)ng * 8, hipMemcpyHostToDevice, s));
+    } else {
+      HIP_CHECK(hipMemcpyAsync(d_sid, gs.sorted_ids.data(), (size_t)gs.N * 4, hipMemcpyHostToDevice, s));
+      HIP_CHECK(hipMemcpyAsync(d_spos, gs.sorted_pos.data(), (size_t)gs.N * 4, hipMemcpyHostToDevice, s));
+    }
     if (nent) {
       HIP_CHECK(hipMemcpyAsync(d_eg, ent_g.data(), (size_t)nent * 4, hipMemcpyHostToDevice, s));
       HIP_CHECK(hipMemcpyAsync(d_eid, ent_id.data(), (size_t)nent * 4, hipMemcpyHostToDevice, s));
     }
     HIP_CHECK(hipMemsetAsync(bits, 0, (size_t)gs.bits * 4, s));
     HIP_CHECK(hipMemsetAsync(flags, 0, (size_t)gs.flags * 4, s));
+    if (dev && dev->keep_picks) HIP_CHECK(hipMemsetAsync(picks, 0xff, (size_t)gs.N * 4, s));   // (test hook: the rounds not run read -1)
   }
   toc(m);
   if (score) {
@@ -489,6 +544,15 @@ static int rank_t(Model* m, int medium, int ng, const Groups& gs, const int32_t*
     RK_LAUNCH_CHECK();
     toc(m);
   }
+  if (dev) {   // only the pages leave the device (and, for the test hooks, the scores and the pick order)
+    page_gather_kernel<<<ng, RK_THREADS, 0, s>>>(d_grp, d_cand, picks, d_plo, d_phi, d_poff, d_page);
+    RK_LAUNCH_CHECK();
+    if (npage) HIP_CHECK(hipMemcpyAsync(dev->page_out, d_page, (size_t)npage * 4, hipMemcpyDeviceToHost, s));
+    if (dev->keep_r) HIP_CHECK(hipMemcpyAsync(dev->keep_r, sc, (size_t)gs.N * 4, hipMemcpyDeviceToHost, s));
+    if (dev->keep_picks) HIP_CHECK(hipMemcpyAsync(dev->keep_picks, picks, (size_t)gs.N * 4, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    return RSYS_OK;
+  }
   std::vector<int32_t> pos(rerank ? (size_t)gs.N : 0);
   if (rerank) HIP_CHECK(hipMemcpyAsync(pos.data(), picks, (size_t)gs.N * 4, hipMemcpyDeviceToHost, s));
   if (r_out) HIP_CHECK(hipMemcpyAsync(r_out, sc, (size_t)gs.N * 4, hipMemcpyDeviceToHost, s));
@@ -499,26 +563,28 @@ static int rank_t(Model* m, int medium, int ng, const Groups& gs, const int32_t*
   return RSYS_OK;
 }
 
-int model_rank_request(Model* m, int medium, int32_t ng, const int64_t* cand_off, const int32_t* cand_ids, const int32_t* partialk,
-                       const float* penalties, const float* queries, int64_t nu, const int32_t* group, const float* r_masked, int64_t n_rm,
-                       const int64_t* hist_off, const int32_t* hist_medium, const int32_t* hist_ids, const int32_t* hist_status,
-                       const float* retrieval_coef, const float* rating_coefs, float rating_mean, const float* r_in, int32_t* ids_out,
-                       float* r_out) {
+// the one body of rsys_rank_request and of rsys_render_request's last stage (dev != nullptr: candidates, queries and r_masked on the device)
+static int rank_request_body(Model* m, int medium, int32_t ng, const int64_t* cand_off, const int32_t* cand_ids, const int32_t* partialk,
+                             const float* penalties, const float* queries, int64_t nu, const int32_t* group, const float* r_masked, int64_t n_rm,
+                             const int64_t* hist_off, const int32_t* hist_medium, const int32_t* hist_ids, const int32_t* hist_status,
+                             const float* retrieval_coef, const float* rating_coefs, float rating_mean, const float* r_in, int32_t* ids_out,
+                             float* r_out, const RankDev* dev) {
   ARG_CHECK(medium == 0 || medium == 1, "rank_request: medium must be 0 or 1");
-  ARG_CHECK(ids_out || r_out, "rank_request: no output (ids_out and r_out are both NULL)");
+  ARG_CHECK(ids_out || r_out || dev, "rank_request: no output (ids_out and r_out are both NULL)");
   ARG_CHECK(nu >= 1 && nu <= RK_MAXQ, "rank_request: 1 <= n_users <= 4096");
   ARG_CHECK(ng >= 1 && ng <= nu, "rank_request: 1 <= n_groups <= n_users (every group needs a user)");
   ARG_CHECK(group != nullptr || ng == nu, "rank_request: without `group`, n_groups must equal n_users");
   const bool score = r_in == nullptr;
   if (score) {
     ARG_CHECK(!m->sharded, "rank_request: the row-sharded item table is not supported (replicated table only)");
-    ARG_CHECK(queries && r_masked, "rank_request: queries and r_masked are required unless r_in is given");
+    ARG_CHECK(dev ? (dev->d_queries && dev->d_rm) : (queries && r_masked), "rank_request: queries and r_masked are required unless r_in is given");
   }
-  if (ids_out) ARG_CHECK(partialk && penalties, "rank_request: partialk and penalties are required with ids_out");
+  const bool rerank = ids_out != nullptr || dev != nullptr;
+  if (rerank) ARG_CHECK(partialk && penalties, "rank_request: partialk and penalties are required with ids_out");
   const int V[2] = {m->V0, m->V1};
   const int Vm = V[medium];
   Groups gs;
-  RC(make_groups("rank_request", ng, cand_off, cand_ids, ids_out ? partialk : nullptr, ids_out ? penalties : nullptr, Vm, gs));
+  RC(make_groups("rank_request", ng, cand_off, cand_ids, rerank ? partialk : nullptr, rerank ? penalties : nullptr, Vm, gs, dev != nullptr));
   std::vector<int32_t> ugroup((size_t)nu);
   std::vector<int> members(ng, 0);
   std::vector<int64_t> rm_off((size_t)nu);
@@ -554,7 +620,7 @@ int model_rank_request(Model* m, int medium, int32_t ng, const int64_t* cand_off
   }
   const float* E = nullptr;
   int64_t dim = 0;
-  if (ids_out) {
+  if (rerank) {
     E = retrieve_similarity_table(m, medium, &dim);
     ARG_CHECK(E != nullptr, "rank_request: the item-similarity embeddings of the medium are not loaded (rsys_retrieve_similarity_set)");
     const RankTables* R = rank_tables(m);
@@ -562,9 +628,27 @@ int model_rank_request(Model* m, int medium, int32_t ng, const int64_t* cand_off
   }
   HIP_CHECK(hipSetDevice(m->device));
   return m->bf16_mode ? rank_t<bf16>(m, medium, ng, gs, cand_ids, queries, nu, ugroup, r_masked, n_rm, rm_off, ent_g, ent_id, retrieval_coef,
-                                     rating_coefs, rating_mean, r_in, E, (int)dim, ids_out, r_out)
+                                     rating_coefs, rating_mean, r_in, E, (int)dim, ids_out, r_out, dev)
                       : rank_t<float>(m, medium, ng, gs, cand_ids, queries, nu, ugroup, r_masked, n_rm, rm_off, ent_g, ent_id, retrieval_coef,
-                                      rating_coefs, rating_mean, r_in, E, (int)dim, ids_out, r_out);
+                                      rating_coefs, rating_mean, r_in, E, (int)dim, ids_out, r_out, dev);
+}
+
+int model_rank_request(Model* m, int medium, int32_t ng, const int64_t* cand_off, const int32_t* cand_ids, const int32_t* partialk,
+                       const float* penalties, const float* queries, int64_t nu, const int32_t* group, const float* r_masked, int64_t n_rm,
+                       const int64_t* hist_off, const int32_t* hist_medium, const int32_t* hist_ids, const int32_t* hist_status,
+                       const float* retrieval_coef, const float* rating_coefs, float rating_mean, const float* r_in, int32_t* ids_out,
+                       float* r_out) {
+  return rank_request_body(m, medium, ng, cand_off, cand_ids, partialk, penalties, queries, nu, group, r_masked, n_rm, hist_off, hist_medium,
+                           hist_ids, hist_status, retrieval_coef, rating_coefs, rating_mean, r_in, ids_out, r_out, nullptr);
+}
+
+int model_rank_request_dev(Model* m, int medium, int32_t ng, const int64_t* cand_off, const RankDev* dev, const int32_t* partialk,
+                           const float* penalties, int64_t nu, const int32_t* group, int64_t n_rm, const int64_t* hist_off,
+                           const int32_t* hist_medium, const int32_t* hist_ids, const int32_t* hist_status, const float* retrieval_coef,
+                           const float* rating_coefs, float rating_mean) {
+  ARG_CHECK(dev && dev->d_cand && dev->page_lo && dev->page_hi && dev->page_off && dev->page_out, "rank_request: null device buffers");
+  return rank_request_body(m, medium, ng, cand_off, nullptr, partialk, penalties, nullptr, nu, group, nullptr, n_rm, hist_off, hist_medium,
+                           hist_ids, hist_status, retrieval_coef, rating_coefs, rating_mean, nullptr, nullptr, nullptr, dev);
 }
 
 int model_rank_gram(Model* m, int medium, int32_t ng, const int64_t* cand_off, const int32_t* cand_ids, float* out, int64_t n_out) {

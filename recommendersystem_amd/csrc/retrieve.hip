@@ -393,7 +393,7 @@ void retrieve_free(Model* m) {
 template <typename T>
 static int retrieve_t(Model* m, int medium, const float* queries, int64_t nq, const int32_t* group, int ng, const float* prior,
                       const int64_t* excl_off, const int32_t* excl_ids, const RetrieveInit* init, int k, int32_t* ids_out, float* scores_out,
-                      int32_t* counts_out) {
+                      int32_t* counts_out, RetrieveDev* dev = nullptr) {
   const int D = m->D, Vm = medium == 0 ? m->V0 : m->V1, vs = medium == 0 ? 0 : m->V0;
   hipStream_t s = m->stream;
   // host-side index arrays: the queries of each group in query order, per chunk the range of them it holds, exclusion positions
@@ -472,7 +472,9 @@ static int retrieve_t(Model* m, int medium, const float* queries, int64_t nq, co
   sb.cand = (unsigned long long*)z; sb.ldc = k;
 
   tic(m, "retrieve_prep");
-  HIP_CHECK(hipMemcpyAsync(qf, queries, (size_t)nq * D * 4, hipMemcpyHostToDevice, s));
+  // (dev: the queries are on the device already and the result stays there; the arithmetic below is the same)
+  if (dev) HIP_CHECK(hipMemcpyAsync(qf, dev->d_queries, (size_t)nq * D * 4, hipMemcpyDeviceToDevice, s));
+  else HIP_CHECK(hipMemcpyAsync(qf, queries, (size_t)nq * D * 4, hipMemcpyHostToDevice, s));
   if constexpr (is_bf16<T>::value) RC(launch_cast<T>(qf, qt, (long long)nq * D, s));
   HIP_CHECK(hipMemcpyAsync(d_members, members.data(), members.size() * 4, hipMemcpyHostToDevice, s));
   HIP_CHECK(hipMemcpyAsync(d_ranges, ranges.data(), ranges.size() * sizeof(int2), hipMemcpyHostToDevice, s));
@@ -502,8 +504,11 @@ static int retrieve_t(Model* m, int medium, const float* queries, int64_t nq, co
   tic(m, "retrieve_select");
   RC(topk_select((const unsigned*)sc, Vm, ng, Vm, k, sb, d_ids, d_vals, d_counts, s));
   toc(m);
-  HIP_CHECK(hipMemcpyAsync(ids_out, d_ids, (size_t)ng * k * 4, hipMemcpyDeviceToHost, s));
-  HIP_CHECK(hipMemcpyAsync(scores_out, d_vals, (size_t)ng * k * 4, hipMemcpyDeviceToHost, s));
+  if (dev) { dev->d_ids = d_ids; dev->d_vals = d_vals; }
+  else {
+    HIP_CHECK(hipMemcpyAsync(ids_out, d_ids, (size_t)ng * k * 4, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(scores_out, d_vals, (size_t)ng * k * 4, hipMemcpyDeviceToHost, s));
+  }
   HIP_CHECK(hipMemcpyAsync(counts_out, d_counts, (size_t)ng * 4, hipMemcpyDeviceToHost, s));
   HIP_CHECK(hipStreamSynchronize(s));
   return RSYS_OK;
@@ -529,9 +534,9 @@ int model_retrieve_topk(Model* m, int medium, const float* queries, int64_t nq, 
 // stream after the workspace is in place): the prior and the NaN masks of rsys_retrieve_request.  The caller has checked the arguments
 // model_retrieve_topk checks.
 int model_retrieve_run(Model* m, int medium, const float* queries, int64_t nq, const int32_t* group, int32_t ng, const RetrieveInit& init,
-                       int32_t k, int32_t* ids_out, float* scores_out, int32_t* counts_out) {
-  return m->bf16_mode ? retrieve_t<bf16>(m, medium, queries, nq, group, ng, nullptr, nullptr, nullptr, &init, k, ids_out, scores_out, counts_out)
-                      : retrieve_t<float>(m, medium, queries, nq, group, ng, nullptr, nullptr, nullptr, &init, k, ids_out, scores_out, counts_out);
+                       int32_t k, int32_t* ids_out, float* scores_out, int32_t* counts_out, RetrieveDev* dev) {
+  return m->bf16_mode ? retrieve_t<bf16>(m, medium, queries, nq, group, ng, nullptr, nullptr, nullptr, &init, k, ids_out, scores_out, counts_out, dev)
+                      : retrieve_t<float>(m, medium, queries, nq, group, ng, nullptr, nullptr, nullptr, &init, k, ids_out, scores_out, counts_out, dev);
 }
 
 static void topk_rows_layout(Carve& c, int rows, int V, int k, unsigned** keys, SelBufs* sb) {

@@ -317,14 +317,16 @@ int model_retrieve_released_set(Model* m, int medium, const uint8_t* mask) {
   return upload((void**)&t.released, b.data(), b.size() * 4);
 }
 
-int model_retrieve_request(Model* m, int medium, const float* queries, int64_t nq, const int32_t* group, int32_t ng, const int64_t* hist_off,
-                           const int32_t* hist_medium, const int32_t* hist_ids, const int32_t* hist_status, const int64_t* sel_off,
-                           const int32_t* sel_medium, const int32_t* sel_ids, int32_t k, int32_t* ids_out, float* scores_out,
-                           int32_t* counts_out) {
+// the one body of rsys_retrieve_request and of rsys_render_request's retrieval stage: dev == nullptr takes the queries from, and returns
+// the result to, the host; else both stay on the device (RetrieveDev) and only the counts come back
+static int retrieve_request_body(Model* m, int medium, const float* queries, RetrieveDev* dev, int64_t nq, const int32_t* group, int32_t ng,
+                                 const int64_t* hist_off, const int32_t* hist_medium, const int32_t* hist_ids, const int32_t* hist_status,
+                                 const int64_t* sel_off, const int32_t* sel_medium, const int32_t* sel_ids, int32_t k, int32_t* ids_out,
+                                 float* scores_out, int32_t* counts_out) {
   // the limits of rsys_retrieve_topk (model_retrieve_topk)
   ARG_CHECK(medium == 0 || medium == 1, "retrieve_request: medium must be 0 or 1");
   ARG_CHECK(!m->sharded, "retrieve_request: the row-sharded item table is not supported (replicated table only)");
-  ARG_CHECK(queries && ids_out && scores_out && counts_out, "retrieve_request: null buffer");
+  ARG_CHECK(dev ? (dev->d_queries && counts_out) : (queries && ids_out && scores_out && counts_out), "retrieve_request: null buffer");
   ARG_CHECK(nq >= 1 && nq <= 4096, "retrieve_request: 1 <= n_queries <= 4096");
   ARG_CHECK(ng >= 1 && ng <= nq, "retrieve_request: 1 <= n_groups <= n_queries (every group needs a query)");
   ARG_CHECK(group != nullptr || ng == nq, "retrieve_request: without `group`, n_groups must equal n_queries");
@@ -496,7 +498,23 @@ int model_retrieve_request(Model* m, int medium, const float* queries, int64_t n
     toc(m);
     return RSYS_OK;
   };
-  return model_retrieve_run(m, medium, queries, nq, group, ng, init, k, ids_out, scores_out, counts_out);
+  return model_retrieve_run(m, medium, queries, nq, group, ng, init, k, ids_out, scores_out, counts_out, dev);
+}
+
+int model_retrieve_request(Model* m, int medium, const float* queries, int64_t nq, const int32_t* group, int32_t ng, const int64_t* hist_off,
+                           const int32_t* hist_medium, const int32_t* hist_ids, const int32_t* hist_status, const int64_t* sel_off,
+                           const int32_t* sel_medium, const int32_t* sel_ids, int32_t k, int32_t* ids_out, float* scores_out,
+                           int32_t* counts_out) {
+  return retrieve_request_body(m, medium, queries, nullptr, nq, group, ng, hist_off, hist_medium, hist_ids, hist_status, sel_off, sel_medium,
+                               sel_ids, k, ids_out, scores_out, counts_out);
+}
+
+int model_retrieve_request_dev(Model* m, int medium, RetrieveDev* dev, int64_t nq, const int32_t* group, int32_t ng, const int64_t* hist_off,
+                               const int32_t* hist_medium, const int32_t* hist_ids, const int32_t* hist_status, const int64_t* sel_off,
+                               const int32_t* sel_medium, const int32_t* sel_ids, int32_t k, int32_t* counts_out) {
+  ARG_CHECK(dev != nullptr, "retrieve_request: null device buffers");
+  return retrieve_request_body(m, medium, nullptr, dev, nq, group, ng, hist_off, hist_medium, hist_ids, hist_status, sel_off, sel_medium,
+                               sel_ids, k, nullptr, nullptr, counts_out);
 }
 
 }  // namespace rsys

@@ -643,6 +643,97 @@ class RecommenderModel:
             picked = [ids[off[j]:off[j] + min(int(pk[j]), int(off[j + 1] - off[j]))].copy() for j in range(ng)]
         return picked, [rout[off[j]:off[j + 1]].copy() for j in range(ng)]
 
+    # ---- a page from raw histories in one device pipeline (rsys_render_request: compute.jl:512-531 + render.jl:437-474)
+    @staticmethod
+    def _c_rows(d, rows, width):
+        """an rsys_batch of `rows` rows of `width` columns holding the ten inference arrays only (+ the arrays it points into)"""
+        b = _lib.rsys_batch()
+        b.rows = rows
+        keep = []
+
+        def arr(x, dt):
+            a = np.ascontiguousarray(np.asarray(x).reshape(-1), dt)
+            if a.size != rows * width:
+                raise ValueError(f"render_request: an array holds {a.size} values, expected {rows} x {width}")
+            keep.append(a)
+            return a.ctypes.data if a.size else None
+
+        b.userid = arr(d["userid"], np.int32); b.token_mask_ids = arr(d["token_mask_ids"], np.int32)
+        b.gender = arr(d["gender"], np.int32); b.source = arr(d["source"], np.int32)
+        b.matchedid = arr(d["matchedid"], np.int32); b.status = arr(d["status"], np.int32)
+        b.time = arr(d["time"], np.float64); b.rating = arr(d["rating"], np.float32); b.progress = arr(d["progress"], np.float32)
+        b.rope_input_pos = arr(d["rope_input_pos"], np.int32)
+        return b, keep
+
+    def render_request(self, group_medium, offsets, limits, penalties, group, retrieval_rows, retrieval_token, ranking_prefix, prefix_stride,
+                       user_desc, user_ts, adapter_slots=None, histories=None, selected=None, coef_have=None, coefs=None):
+        """rsys_render_request: per group (medium, offset, limit, penalties (4)); per user its group, its row of `retrieval_rows` (the
+        dict `serve.build_batch(..., "retrieval")` builds, n_users rows) with its query token `retrieval_token`, its row of
+        `ranking_prefix` (the same ten arrays, `prefix_stride` columns per row), `user_desc` (nh, userid, gender, source) and `user_ts`;
+        `adapter_slots` the bank slots of (0.retrieval, 0.ranking, 1.retrieval, 1.ranking) or None (base model); `histories` per user
+        and `selected` per group as `retrieve_request` takes them; `coef_have` (2,) / `coefs` (2, 4) the registry's coefficients.
+        Returns (one int32 page array per group, totals (n_groups,) int32)."""
+        gm = np.ascontiguousarray(group_medium, np.int32).reshape(-1)
+        ng = gm.size
+        off = np.ascontiguousarray(offsets, np.int64).reshape(-1)
+        lim = np.ascontiguousarray(limits, np.int32).reshape(-1)
+        pen = np.ascontiguousarray(penalties, np.float32).reshape(-1)
+        gp = np.ascontiguousarray(group, np.int32).reshape(-1)
+        nu = gp.size
+        if off.size != ng or lim.size != ng or pen.size != 4 * ng:
+            raise ValueError(f"render_request: offsets, limits and penalties need {ng} entries and {ng} x 4 values")
+        S = self.config["max_sequence_length"]
+        rb, keep_r = self._c_rows(retrieval_rows, nu, S)
+        pb, keep_p = self._c_rows(ranking_prefix, nu, int(prefix_stride))
+        tok = np.ascontiguousarray(retrieval_token, np.int32).reshape(-1)
+        desc = np.ascontiguousarray(user_desc, np.int32).reshape(-1)
+        ts = np.ascontiguousarray(user_ts, np.float64).reshape(-1)
+        if tok.size != nu or desc.size != 4 * nu or ts.size != nu:
+            raise ValueError(f"render_request: retrieval_token, user_desc and user_ts need {nu} entries ({nu} x 4 for user_desc)")
+        sl = None if adapter_slots is None else np.ascontiguousarray(adapter_slots, np.int32).reshape(-1)
+        if sl is not None and sl.size != 4:
+            raise ValueError("render_request: adapter_slots holds the slots of 0.retrieval, 0.ranking, 1.retrieval, 1.ranking")
+        h = None
+        if histories is not None:
+            if len(histories) != nu:
+                raise ValueError(f"histories has {len(histories)} lists for {nu} users")
+            h = triples_csr(histories, 3)
+        sel = None
+        if selected is not None:
+            if len(selected) != ng:
+                raise ValueError(f"selected has {len(selected)} lists for {ng} groups")
+            sel = triples_csr(selected, 2)
+        ch = None if coef_have is None else np.ascontiguousarray(coef_have, np.int32).reshape(-1)
+        cf = None if coefs is None else np.ascontiguousarray(coefs, np.float32).reshape(-1)
+        if (ch is not None and ch.size != 2) or (cf is not None and cf.size != 8):
+            raise ValueError("render_request: coef_have holds 2 flags and coefs 2 x 4 values")
+        cap = int(np.clip(lim, 0, None).sum())
+        ids = np.empty(max(cap, 1), np.int32)
+        ioff = np.empty(ng + 1, np.int64)
+        total = np.empty(max(ng, 1), np.int32)
+        ptr = lambda a: None if a is None else a.ctypes.data
+        hp = (None,) * 4 if h is None else tuple(ptr(a) for a in h)
+        sp = (None,) * 3 if sel is None else tuple(ptr(a) for a in sel)
+        check(lib().rsys_render_request(self._h, ng, ptr(gm), ptr(off), ptr(lim), ptr(pen), nu, ptr(gp), C.byref(rb), ptr(tok), C.byref(pb),
+                                        int(prefix_stride), ptr(desc), ptr(ts), ptr(sl), *hp, *sp, ptr(ch), ptr(cf), ptr(ids), cap, ptr(ioff),
+                                        ptr(total)))
+        return [ids[ioff[g]:ioff[g + 1]].copy() for g in range(ng)], total[:ng].copy()
+
+    _RENDER_KEPT = {"time": np.float64, "rating": np.float32, "progress": np.float32, "queries": np.float32, "r_masked": np.float32,
+                    "r": np.float32}
+
+    def render_keep(self, on=True):
+        """rsys_render_debug_keep (test hook): the following render_request calls keep their intermediates for render_kept"""
+        check(lib().rsys_render_debug_keep(self._h, 1 if on else 0))
+
+    def render_kept(self, key):
+        """rsys_render_debug_get (test hook): the array the last render_request kept under `key` (flat; float32 / float64 / int32 by key)"""
+        n = C.c_int64()
+        check(lib().rsys_render_debug_get(self._h, key.encode(), None, 0, C.byref(n)))
+        out = np.empty(n.value, np.uint8)
+        check(lib().rsys_render_debug_get(self._h, key.encode(), out.ctypes.data, n.value, C.byref(n)))
+        return out.view(self._RENDER_KEPT.get(key.split(".")[-1], np.int32))
+
     def rank_gram(self, medium, candidates):
         """rsys_rank_gram_get (test hook): per group the fp32 Gram matrix (n, n) of the candidates' item-similarity rows, as the
         reranking loop reads it."""

@@ -552,3 +552,114 @@ def render(model, states, pagination, registry=None, max_ranking_items=None):
         for g, w in enumerate(items):
             out[w[0]] = (ids[g][w[2] - 1:w[3]], w[4])
     return out
+
+
+# ---------------------------------------------------------------- a page from raw histories in one device call (rsys_render_request)
+_ROW_COLS = _INT_COLS + ("time", "rating", "progress")
+
+
+def _fill_row(d, row, seq, nh, who, num_items_0, ranking):
+    """row `row` of the ten arrays from the token sequence `seq` (nh history tokens first), exactly as `build_batch` fills the row of a
+    one-user request: userid 1, history positions 0..nh-1 and mask id 0, appended tokens at position nh with their own mask id"""
+    L = len(seq)
+    d["userid"][row, :L] = 1
+    d["gender"][row, :L] = 0 if who["gender"] is None else who["gender"] + 1
+    d["source"][row, :L] = who["source"]
+    d["time"][row, :L] = [e["history_max_ts"] for e in seq]
+    d["rope_input_pos"][row, :L] = np.minimum(np.arange(L), nh)
+    if ranking:
+        d["token_mask_ids"][row, nh:L] = np.arange(nh, L)
+    d["matchedid"][row, :L] = [e["matchedid"] + (num_items_0 if e["medium"] == 1 else 0) for e in seq]
+    d["status"][row, :L] = [e["status"] for e in seq]
+    d["rating"][row, :L] = [e["rating"] for e in seq]
+    d["progress"][row, :L] = [e["progress"] for e in seq]
+
+
+def _empty_rows(n, width):
+    d = {k: np.zeros((n, width), np.int32) for k in _INT_COLS}
+    d["time"] = np.zeros((n, width), np.float64)
+    d["rating"] = np.zeros((n, width), np.float32)
+    d["progress"] = np.zeros((n, width), np.float32)
+    return d
+
+
+def render_row_plan(n_candidates, nh, S):
+    """Reference statement (tests and documentation; the library plans its rows itself): the ranking rows rsys_render_request runs for one user of a group whose page window holds `n_candidates` candidates: one
+    (first candidate, candidates, action tokens within the row) triple per chunk of at most S - S // 2 candidates; none for an
+    empty window.  The action token of candidate j of a chunk is 2 (nh + j) + 1 (`_selected_tokens`)."""
+    chunk = S - S // 2
+    return [(c0, min(chunk, n_candidates - c0), 2 * (nh + np.arange(min(chunk, n_candidates - c0))) + 1)
+            for c0 in range(0, int(n_candidates), chunk)]
+
+
+def render_pack(states, pagination, S, num_items_0, registry=None, adapter_slots=None):
+    """The arguments of `RecommenderModel.render_request` for render.jl request states (the states `render` takes; users need no
+    "embeds"): every history is tokenised and projected once; from it come the user's retrieval row (`build_batch([user], "retrieval")`:
+    the newest S - 1 tokens + the query token), the history part of its ranking rows (the first nh columns of `build_batch([user],
+    "ranking")`: the newest S // 2 - 1 tokens) with the descriptor (nh, userid, gender, source) and timestamp the device completes them
+    from, its list items, and per state the selected items, penalties, pagination and medium."""
+    pags = [pagination] * len(states) if isinstance(pagination, dict) else list(pagination)
+    if len(pags) != len(states):
+        raise ValueError(f"render_users: {len(pags)} paginations for {len(states)} states")
+    users, group = [], []
+    gm, off, lim, pen, sel = [], [], [], [], []
+    for g, st in enumerate(states):
+        m = int(st["medium"])
+        if m not in (0, 1):
+            raise ValueError("medium must be 0 or 1")
+        if not st["users"]:
+            raise ValueError("render_users: every state needs at least one user")
+        limit, offset = int(pags[g]["limit"]), int(pags[g]["offset"])
+        if limit < 1 or offset < 0:
+            raise ValueError("pagination: limit >= 1 and offset >= 0")
+        gm.append(m); off.append(offset); lim.append(limit)
+        p = st.get("penalties", {})
+        pen.append([float(p.get(k, 0.0)) for k in ("decay", "mmr_penalty", "same_series_penalty", "related_penalty")])
+        sel.append([(int(a["medium"]), int(a["matchedid"])) for a in st["items"]])
+        for u in st["users"]:
+            users.append(u["user"]); group.append(g)
+    n = len(users)
+    P = max(S // 2 - 1, 0)
+    rows, prefix = _empty_rows(n, S), _empty_rows(n, P)
+    tok = np.zeros(n, np.int32)
+    desc = np.zeros((n, 4), np.int32)
+    ts = np.zeros(n, np.float64)
+    hist = []
+    for i, user in enumerate(users):
+        h = project(tokenize(user["items"]))                      # once per user
+        hr = h[-(S - 1):] if len(h) > S - 1 else h
+        hk = (h[-P:] if len(h) > P else h) if P else []
+        who = user["user"]
+        _fill_row(rows, i, hr + [make_item(user["timestamp"])], len(hr), who, num_items_0, False)
+        _fill_row(prefix, i, hk, len(hk), who, num_items_0, True)
+        tok[i] = 2 * len(hr)
+        desc[i] = (len(hk), 1, 0 if who["gender"] is None else who["gender"] + 1, who["source"])
+        ts[i] = user["timestamp"]
+        hist.append([(int(x["medium"]), int(x["matchedid"]), int(x["status"])) for x in user["items"]])
+    have, coefs = np.zeros(2, np.int32), np.zeros((2, 4), np.float32)
+    for m in (0, 1):
+        rc, kc, mean = _registry_coefs(registry, m)
+        if rc is not None:
+            have[m] |= 1; coefs[m, 0] = rc
+        if kc is not None:
+            have[m] |= 2; coefs[m, 1:3] = kc; coefs[m, 3] = mean
+    slots = None
+    if adapter_slots:
+        slots = [adapter_slots[f"{m}.{task}"] for m in (0, 1) for task in ("retrieval", "ranking")]
+    return dict(group_medium=gm, offsets=off, limits=lim, penalties=np.asarray(pen, np.float32).reshape(-1, 4), group=group,
+                retrieval_rows=rows, retrieval_token=tok, ranking_prefix=prefix, prefix_stride=P, user_desc=desc, user_ts=ts,
+                adapter_slots=slots, histories=hist, selected=sel, coef_have=have, coefs=coefs)
+
+
+def render_users(model, states, pagination, registry=None):
+    """`render` from raw histories in ONE device call (rsys_render_request): the same states, but users need no "embeds" -- the
+    retrieval forward, `retrieval`, the page window, the ranking forward (every chunk row of every user, both media, in waves of the
+    model's max_rows) and `ranking` + `reranking` run back to back on the device; only the pages and the totals come back.  A model built
+    by `get_models` runs every row with the adapter of its "{medium}.{task}"; a plain model runs the base.  Returns one (ids of the
+    page, total) pair per state, as `render`."""
+    if not states:
+        return []
+    args = render_pack(states, pagination, model.config["max_sequence_length"], model.config["vocab_sizes"]["0_matchedid"], registry,
+                       getattr(model, "adapter_slots", None))
+    pages, totals = model.render_request(**args)
+    return [(pages[g], int(totals[g])) for g in range(len(states))]
