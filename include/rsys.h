@@ -448,6 +448,32 @@ int32_t rsys_adapter_slots(rsys_model* m, int32_t* mask_out);
  * rsys_infer_select.  RSYS_ERR_ARG (out untouched): row_adapter NULL, an entry out of range or naming an incomplete slot, no batch. */
 int32_t rsys_infer_select_adapters(rsys_model* m, int32_t task, const int32_t* row_adapter, const int32_t* token_index, int64_t n_tokens,
                                    float* out, int64_t n);
+/* Ranking forward over full-length histories through a per-user K/V cache (Finetune/embed.py:74-161).  The reference ranks a user in one
+ * row of max_user_len + max_ranking_items interactions: up to max_user_len - 1 history events (token_mask_ids 0) followed by the candidates
+ * (token_mask_ids n_hist + j, all at rope_input_pos n_hist).  Under the mask a history token never sees a candidate and a candidate sees the
+ * whole history plus its own two tokens, so the history's K and V of every layer do not depend on the candidates: they are computed once,
+ * in a row of at most S events, kept post-RoPE per layer, and the candidates run as query-only rows against them -- the reference's function
+ * without a 4 S-token row, for histories of up to S - 1 events, and without recomputing the history per chunk of candidates.
+ * rsys_rank_cache_reserve: n_slots >= 1 cache slots of [num_layers][2 S][2 num_kv_heads head_dim] values in the compute dtype (0 frees them;
+ *   a new size drops what was stored).  RSYS_ERR_STATE when they do not fit in free device memory: the model stays usable, and when the
+ *   size is refused before anything was freed the slots stored so far stay; when the allocation itself fails it has no cache.
+ * rsys_rank_cache_store: the inference trunk forward of the resident batch, whose row r holds a history alone (events 0 .. n_hist[r] - 1
+ *   with token_mask_ids 0 and rope_input_pos 0 .. n_hist[r] - 1; what follows in the row is padding the history never sees), with the
+ *   adapter slot row_adapter[r] as in rsys_infer_select_adapters (NULL: the base model); K and V of tokens [0, 2 n_hist[r]) of every layer,
+ *   after RoPE and the adapters' updates, go to slot slot[r].  0 <= n_hist[r] <= S; the slots of one call are distinct.
+ * rsys_rank_cache_candidates: the same trunk over the resident batch of CANDIDATE rows: row r holds n_cand[r] in [1, S] candidates at
+ *   events 0 .. n_cand[r] - 1 (item, status, rating, ... as the reference's candidate events) and reads slot slot[r]; several rows may read
+ *   one slot.  Every event of row r runs at RoPE position n_hist of its slot (the call sets it; the batch's rope_input_pos,
+ *   token_mask_ids and userid are not read), so the slot must hold at most S - 1 events.  A token of candidate j attends to the slot's
+ *   2 n_hist cached tokens and to tokens 2 j, 2 j + 1 of its own row.  out[sum n_cand], row order = the rating head at action tokens
+ *   2 j + 1.  n_hist = 0: a candidate sees only itself.  (Deviation: the reference gives candidate 0 of an EMPTY history
+ *   token_mask_ids 0, which makes it visible to the other candidates; here it is not.  Hosts that need that row use rsys_infer_select.)
+ * Both calls are synchronous, replace the resident batch's derived arrays as every inference call does, and touch no parameter, gradient
+ * or optimizer state.  RSYS_ERR_ARG (out and the cache untouched): no batch uploaded, nothing reserved, a slot outside the reserve, a slot
+ * never stored, duplicate slots in one store, a count out of range, an adapter slot that is not complete, an fp8 or row-sharded model. */
+int32_t rsys_rank_cache_reserve(rsys_model* m, int32_t n_slots);
+int32_t rsys_rank_cache_store(rsys_model* m, const int32_t* row_adapter, const int32_t* n_hist, const int32_t* slot);
+int32_t rsys_rank_cache_candidates(rsys_model* m, const int32_t* row_adapter, const int32_t* slot, const int32_t* n_cand, float* out);
 /* debug/parity: trunk output of the last forward (rows*2S*D floats).  A training pass computes it only at the positions the heads
  * select; this call then runs the dense tail of the last layer first (results as model.py:335-343 over every token). */
 int32_t rsys_trunk_output_get(rsys_model* m, float* out, int64_t n);

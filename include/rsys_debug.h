@@ -66,6 +66,14 @@ int32_t rsys_debug_gemm_route(int32_t dtype, int32_t M, int32_t N, int32_t K, in
 int32_t rsys_op_attention(int32_t dtype, int32_t B, int32_t T, int32_t H, int32_t KV, int32_t hd, const void* qkv,
                           const int32_t* uid, const int32_t* tm, void* O, float* lse, const void* dO, void* dqkv,
                           const float* rope_cos, const float* rope_sin);
+/* the candidate attention of rsys_rank_cache_candidates alone, on caller-provided device buffers (T-typed): qkv [rows*T][(H+2KV)*hd] the
+ * candidate rows' post-RoPE q | k | v, cache [n_slots][T][2*KV*hd] (K | V per cached token), slot / n_hist / n_cand int32 [rows] (device;
+ * 0 <= n_hist[r] <= T/2, 0 <= n_cand[r] <= T/2); O [rows*T][H*hd]: rows of tokens >= 2 n_cand[r] are zeros up to the end of the last
+ * 64-token tile that holds a candidate and left as they were behind it */
+int32_t rsys_op_attention_cached(int32_t dtype, int32_t rows, int32_t T, int32_t H, int32_t KV, int32_t hd, const void* qkv, const void* cache,
+                                 int32_t n_slots, const int32_t* slot, const int32_t* n_hist, const int32_t* n_cand, void* O);
+/* K | V rows a ranking-cache slot holds for one layer: out (host) [2 n_hist][2*KV*hd] in the compute dtype; bytes must be exact */
+int32_t rsys_rank_cache_get(rsys_model* m, int32_t layer, int32_t slot, void* out, int64_t bytes);
 /* the selection of rsys_retrieve_topk alone, on caller-provided device buffers: per row r of scores [rows][ld >= V] the min(k, admissible)
  * best columns by descending value, ties by ascending column, -inf / NaN excluded, -0.0 == +0.0; ids / vals [rows][k] (padding -1 / -inf),
  * counts [rows]; 1 <= k <= min(V, 8192) */

@@ -129,6 +129,21 @@ function infer_select_adapters(m::Model, task::Integer, row_adapter::Vector{Int3
     out
 end
 
+# Full-length ranking through a per-user K/V cache of the history (rsys.h: rsys_rank_cache_*).  row_adapter may be `nothing` (base model).
+rank_cache_reserve(m::Model, n_slots::Integer) = check(ccall((:rsys_rank_cache_reserve, LIB), Int32, (Ptr{Cvoid}, Int32), m.h, n_slots))
+function rank_cache_store(m::Model, row_adapter::Union{Nothing, Vector{Int32}}, n_hist::Vector{Int32}, slot::Vector{Int32})
+    ra = row_adapter === nothing ? Ptr{Int32}(C_NULL) : pointer(row_adapter)
+    GC.@preserve row_adapter n_hist slot check(ccall((:rsys_rank_cache_store, LIB), Int32, (Ptr{Cvoid}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}),
+                                                     m.h, ra, n_hist, slot))
+end
+function rank_cache_candidates(m::Model, row_adapter::Union{Nothing, Vector{Int32}}, slot::Vector{Int32}, n_cand::Vector{Int32})
+    out = Vector{Float32}(undef, sum(n_cand))
+    ra = row_adapter === nothing ? Ptr{Int32}(C_NULL) : pointer(row_adapter)
+    GC.@preserve row_adapter slot n_cand out check(ccall((:rsys_rank_cache_candidates, LIB), Int32,
+                                                         (Ptr{Cvoid}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Float32}), m.h, ra, slot, n_cand, out))
+    out
+end
+
 function create_optimizer(m::Model; lr = 1f-4, betas = (0.9f0, 0.95f0), eps = 1f-8, weight_decay = 0.1f0)
     h = Ref{Ptr{Cvoid}}(C_NULL)
     check(ccall((:rsys_adamw_create, LIB), Int32, (Ptr{Cvoid}, Float32, Float32, Float32, Float32, Float32, Ref{Ptr{Cvoid}}),

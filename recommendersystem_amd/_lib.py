@@ -138,6 +138,11 @@ _SIGS = [
     ("rsys_adapter_clear", C.c_int32, [_P, C.c_int32]),
     ("rsys_adapter_slots", C.c_int32, [_P, C.POINTER(C.c_int32)]),
     ("rsys_infer_select_adapters", C.c_int32, [_P, C.c_int32, _P, _P, C.c_int64, _P, C.c_int64]),
+    ("rsys_rank_cache_reserve", C.c_int32, [_P, C.c_int32]),
+    ("rsys_rank_cache_store", C.c_int32, [_P, _P, _P, _P]),
+    ("rsys_rank_cache_candidates", C.c_int32, [_P, _P, _P, _P, _P]),
+    ("rsys_rank_cache_get", C.c_int32, [_P, C.c_int32, C.c_int32, _P, C.c_int64]),
+    ("rsys_op_attention_cached", C.c_int32, [C.c_int32] * 6 + [_P, _P, C.c_int32, _P, _P, _P, _P]),
     ("rsys_trunk_output_get", C.c_int32, [_P, _P, C.c_int64]),
     ("rsys_debug_get", C.c_int32, [_P, C.c_char_p, _P, C.c_int64]),
     ("rsys_clip_grad_norm", C.c_int32, [_P, C.c_float, C.POINTER(C.c_float)]),

@@ -1933,6 +1933,216 @@ int launch_attn_bwd(const AttnParams& p, hipStream_t s) {
 template int launch_attn_bwd<bf16>(const AttnParams&, hipStream_t);
 template int launch_attn_bwd<float>(const AttnParams&, hipStream_t);
 
+// ------------------------------------------------------------------------ candidate attention against a cached history
+// rsys_rank_cache_candidates (Finetune/embed.py:74-131 without the history half of the row).  A row holds candidates only: candidate j at
+// tokens 2 j, 2 j + 1.  The key set of a query token is dense -- the 2 n_hist cached tokens of the row's slot -- plus its own pair, so
+// there are no tile maps: the workgroup of a query tile walks the ceil(2 n_hist / 64) cached K / V tiles (only the last one is masked,
+// where it is ragged) and then ONE "self" tile, its own 64 tokens' fresh K / V under the constant block-diagonal 2 x 2 pair mask, all
+// in one online soft-max.  Fragments, staging (register-staged, double-buffered, one barrier per tile), the rounding points (P in the
+// operand type, fp32 accumulation, O in the operand type) and the head grouping are attn_fwd_kernel's.  The cached tiles are read
+// through a descriptor that ends at the slot's last stored row: rows past it come back as zeros, never as what an earlier user left.
+// No atomics; query tiles past the row's candidates return at once and write nothing; inside the last live tile the rows of tokens
+// >= 2 n_cand are written as zeros.
+template <typename T, int HD, int R>
+__global__ __launch_bounds__(256, (is_bf16<T>::value && HD <= 64) ? (R == 1 ? 3 : 2) : 1) void attn_cand_kernel(CandAttnParams p) {
+  using C = ACfg<T, HD>;
+  using M = AMma<T>;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  T* Ks = (T*)smem_raw;                       // [2][64][LDD]
+  T* Vs = Ks + 2 * C::TILE;                   // [2][64][LDD]
+  const int nt = (p.T + 63) / 64, n_inner = (p.H / p.KV / R) * nt;
+  const int grp = blockIdx.x / n_inner, inner = blockIdx.x % n_inner;
+  const int b = grp / p.KV, kvh = grp % p.KV, h0 = kvh * (p.H / p.KV) + (inner / nt) * R, qt = inner % nt;
+  const int nq = 2 * min(max(p.n_cand[b], 0), p.T / 2);     // candidate tokens of the row
+  if (qt * 64 >= nq) return;                                 // (uniform: whole workgroup)
+  const int nh2 = 2 * min(max(p.n_hist[b], 0), p.T / 2);     // cached tokens of the row's slot
+  const int slot = min(max(p.slot[b], 0), p.n_slots - 1);
+  const int nht = (nh2 + 63) / 64;
+  const int t = threadIdx.x, l = t & 63, w = t >> 6, g = l >> 4, fr = l & 15;
+  const long long tok0 = (long long)b * p.T;
+  const int ldc = 2 * p.KV * HD;                             // a cached token: K of every kv head, then V
+  const float c2 = rsqrtf((float)HD) * LOG2E;
+  const int q = qt * 64 + w * 16 + fr;
+  typename M::Frag qf[R][C::NDS];
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    const T* qrow = (const T*)p.qkv + (tok0 + min(q, p.T - 1)) * p.ld + (h0 + r) * HD;
+#pragma unroll
+    for (int s = 0; s < C::NDS; ++s) qf[r][s] = frag_global<T>(qrow, s * C::KS, HD, l);
+  }
+  float m_run[R], l_run[R];
+  f32x4 oacc[R][HD / 16];
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    m_run[r] = -1e30f; l_run[r] = 0.f;
+#pragma unroll
+    for (int j = 0; j < HD / 16; ++j) oacc[r][j] = f32x4{0, 0, 0, 0};
+  }
+  zero_pad_cols<T, HD>(Ks, t); zero_pad_cols<T, HD>(Ks + C::TILE, t);
+  // the slot's cached rows [0, nh2) of this kv head (nh2 = 0: never loaded from), and the row's own fresh K / V
+  const T* cbase = (const T*)p.cache + (long long)slot * p.T * ldc + kvh * HD;
+  const long long cbytes = nh2 > 0 ? ((long long)(nh2 - 1) * ldc + HD) * sizeof(T) : 0;
+  const at_i32x4 ck_rs = at_rsrc(cbase, cbytes), cv_rs = at_rsrc(cbase + p.KV * HD, cbytes);
+  const long long sbytes = ((long long)(p.T - 1) * p.ld + HD) * sizeof(T);
+  const at_i32x4 sk_rs = at_rsrc((const T*)p.qkv + tok0 * p.ld + (p.H + kvh) * HD, sbytes);
+  const at_i32x4 sv_rs = at_rsrc((const T*)p.qkv + tok0 * p.ld + (p.H + p.KV + kvh) * HD, sbytes);
+  TileOffs<T, HD> c_of, s_of;
+  tile_offsets<T, HD>(c_of, ldc, t);
+  tile_offsets<T, HD>(s_of, p.ld, t);
+  TileRegs<T, HD> rk, rv;
+  auto gload = [&](int kt) {   // tile kt < nht: cached; kt == nht: the self tile
+    if (kt < nht) {
+      const int so = (int)(kt * 64 * ldc * sizeof(T));
+      tile_load_buf<T, HD>(rk, ck_rs, c_of, so);
+      tile_load_buf<T, HD>(rv, cv_rs, c_of, so);
+    } else {
+      const int so = (int)(qt * 64 * p.ld * sizeof(T));
+      tile_load_buf<T, HD>(rk, sk_rs, s_of, so);
+      tile_load_buf<T, HD>(rv, sv_rs, s_of, so);
+    }
+  };
+  auto lstore = [&](int buf) {
+    tile_store<T, HD>(rk, Ks + buf * C::TILE, t);
+    tile_store<T, HD>(rv, Vs + buf * C::TILE, t);
+  };
+  int cur = 0;
+  gload(0); lstore(0);
+  __syncthreads();
+  for (int kt = 0; kt <= nht; ++kt) {
+    if (kt < nht) gload(kt + 1);
+    const T* Kc = Ks + cur * C::TILE;
+    const T* Vc = Vs + cur * C::TILE;
+    f32x4 S[R][4];
+    const bool self = kt == nht;
+    if (self || kt * 64 + 64 > nh2) {
+      // the mask enters the score chains as their starting value (0 / -1e30, as in attn_fwd_kernel): the lane's query 16 w + fr against
+      // keys 16 i + 4 g + rr of the tile -- its own pair in the self tile, the stored rows in the ragged last cached tile
+      f32x4 bias[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int rr = 0; rr < 4; ++rr) {
+          const int key = 16 * i + 4 * g + rr;
+          const bool ok = self ? (key >> 1) == ((16 * w + fr) >> 1) : kt * 64 + key < nh2;
+          bias[i][rr] = ok ? 0.f : -1e30f;
+        }
+      first_stage_r<T, HD, R>(S, Kc, qf, l, bias);
+    } else {
+      first_stage_r<T, HD, R>(S, Kc, qf, l);
+    }
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      float tmax = -1e30f;
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int rr = 0; rr < 4; ++rr) tmax = fmaxf(tmax, S[r][i][rr]);
+      tmax = quad_rows_max(tmax);
+      const float m_new = fmaxf(m_run[r], tmax * c2);
+      const float mu_old = fmaxf(m_run[r], -1e20f), mu_new = fmaxf(m_new, -1e20f);
+      const float alpha = fexp2(mu_old - mu_new);
+      float psum = 0.f;
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int rr = 0; rr < 4; ++rr) {
+          const float pv = fexp2(fmaf(S[r][i][rr], c2, -mu_new));
+          S[r][i][rr] = pv;
+          psum += pv;
+        }
+      psum = quad_rows_sum(psum);
+      l_run[r] = l_run[r] * alpha + psum;
+      m_run[r] = m_new;
+#pragma unroll
+      for (int j = 0; j < HD / 16; ++j) oacc[r][j] *= alpha;
+    }
+    acc_second_stage_r<T, HD, R>(oacc, S, Vc, l);
+    if (kt < nht) lstore(cur ^ 1);
+    __syncthreads();
+    cur ^= 1;
+  }
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    T* Os = Ks + r * C::TILE;
+    const float inv = l_run[r] > 0.f ? 1.f / l_run[r] : 0.f;
+#pragma unroll
+    for (int j = 0; j < HD / 16; ++j) {
+      T* dst = Os + (w * 16 + fr) * C::LDD + 16 * j + 4 * g;
+#pragma unroll
+      for (int rr = 0; rr < 4; ++rr) dst[rr] = from_f32<T>(q < nq ? oacc[r][j][rr] * inv : 0.f);
+    }
+  }
+  __syncthreads();
+  // the whole tile is written: the padding tokens behind the row's last candidate get ZEROS, not what an earlier forward left in O.  Their
+  // K / V of the next layer sit in this tile's self tile, where live queries meet them with P = 0 -- exact only while they are finite.
+#pragma unroll
+  for (int r = 0; r < R; ++r)
+    copy_out_tile<T, HD>(Ks + r * C::TILE, (T*)p.o + (tok0 + qt * 64) * p.ldo + (h0 + r) * HD, p.ldo, qt * 64, p.T, t);
+}
+
+template <typename T, int HD>
+static int attn_cand_hd(const CandAttnParams& p, hipStream_t s) {
+  using C = ACfg<T, HD>;
+  const size_t sm = sizeof(T) * 4 * C::TILE;
+  static bool set = false;
+  if (!set) {
+    HIP_CHECK(hipFuncSetAttribute((const void*)attn_cand_kernel<T, HD, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm));
+    HIP_CHECK(hipFuncSetAttribute((const void*)attn_cand_kernel<T, HD, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm));
+    set = true;
+  }
+  const int nt = (p.T + 63) / 64;
+  if (p.H / p.KV == 2 && HD <= 64) hipLaunchKernelGGL((attn_cand_kernel<T, HD, 2>), dim3(nt * (p.H / 2) * p.rows), dim3(256), sm, s, p);   // (heads per workgroup: as attn_heads_per_wg)
+  else hipLaunchKernelGGL((attn_cand_kernel<T, HD, 1>), dim3(nt * p.H * p.rows), dim3(256), sm, s, p);
+  HIP_CHECK(hipGetLastError());
+  return RSYS_OK;
+}
+template <typename T>
+int launch_attn_cand(const CandAttnParams& p, hipStream_t s) {
+  ARG_CHECK(p.rows >= 1 && p.n_slots >= 1, "candidate attention: rows and slots");
+  ARG_CHECK(p.T % 8 == 0 && (p.T + 63) / 64 <= 32, "candidate attention: T must be a multiple of 8 and <= 2048");
+  ARG_CHECK(p.H % p.KV == 0, "candidate attention: H % KV");
+  ARG_CHECK((p.ld * sizeof(T)) % 16 == 0 && (p.ldo * sizeof(T)) % 16 == 0 && (p.hd * sizeof(T)) % 16 == 0, "candidate attention: 16-byte row alignment");
+  ARG_CHECK((long long)p.T * p.ld * sizeof(T) < (1ll << 31), "candidate attention: a row of qkv must stay below 2 GiB");
+  switch (p.hd) {
+    case 16: return attn_cand_hd<T, 16>(p, s);
+    case 32: return attn_cand_hd<T, 32>(p, s);
+    case 64: return attn_cand_hd<T, 64>(p, s);
+    case 128: return attn_cand_hd<T, 128>(p, s);
+  }
+  set_error("candidate attention: head_dim must be 16, 32, 64 or 128");
+  return RSYS_ERR_ARG;
+}
+template int launch_attn_cand<bf16>(const CandAttnParams&, hipStream_t);
+template int launch_attn_cand<float>(const CandAttnParams&, hipStream_t);
+
+// K | V of the leading 2 n_hist[r] tokens of every row -> the row's cache slot, in 16-byte chunks (rsys_rank_cache_store, once per layer)
+template <typename T>
+__global__ __launch_bounds__(256) void rank_cache_copy_kernel(const T* __restrict__ qkv, long long ld, int kv_off, int kvw, int T_len, const int* __restrict__ slot,
+                                                              const int* __restrict__ n_hist, int n_slots, T* __restrict__ cache) {
+  const int r = blockIdx.y, sl = slot[r];
+  if (sl < 0 || sl >= n_slots) return;
+  const int ntok = 2 * min(max(n_hist[r], 0), T_len / 2);
+  const int cpr = kvw * (int)sizeof(T) / 16;
+  const long long n = (long long)ntok * cpr;
+  for (long long c = (long long)blockIdx.x * 256 + threadIdx.x; c < n; c += (long long)gridDim.x * 256) {
+    const long long tok = c / cpr; const int ch = (int)(c % cpr);
+    const uint4 v = *(const uint4*)((const unsigned char*)(qkv + ((long long)r * T_len + tok) * ld + kv_off) + 16 * ch);
+    *(uint4*)((unsigned char*)(cache + ((long long)sl * T_len + tok) * kvw) + 16 * ch) = v;
+  }
+}
+template <typename T>
+int launch_rank_cache_copy(const T* qkv, long long ld, int kv_off, int kvw, int T_len, int rows, const int* slot, const int* n_hist, int n_slots, T* cache,
+                           hipStream_t s) {
+  ARG_CHECK((kvw * sizeof(T)) % 16 == 0 && (kv_off * sizeof(T)) % 16 == 0 && (ld * sizeof(T)) % 16 == 0, "ranking cache: 16-byte row alignment");
+  const int cpr = kvw * (int)sizeof(T) / 16;
+  const int gx = (int)std::min<long long>(((long long)T_len * cpr + 255) / 256, 64);
+  hipLaunchKernelGGL((rank_cache_copy_kernel<T>), dim3(gx, rows), dim3(256), 0, s, qkv, ld, kv_off, kvw, T_len, slot, n_hist, n_slots, cache);
+  HIP_CHECK(hipGetLastError());
+  return RSYS_OK;
+}
+template int launch_rank_cache_copy<bf16>(const bf16*, long long, int, int, int, int, const int*, const int*, int, bf16*, hipStream_t);
+template int launch_rank_cache_copy<float>(const float*, long long, int, int, int, int, const int*, const int*, int, float*, hipStream_t);
+
 }  // namespace rsys
 
 #ifdef ATTN_KV_TRACE

@@ -254,6 +254,20 @@ int32_t rsys_infer_select_adapters(rsys_model* h, int32_t task, const int32_t* r
   return model_infer_adapters(h->m, task, row_adapter, token_index, n_tokens, out, n);
 }
 
+int32_t rsys_rank_cache_reserve(rsys_model* h, int32_t n_slots) { CHECK_HANDLE(h); return model_rank_cache_reserve(h->m, n_slots); }
+int32_t rsys_rank_cache_store(rsys_model* h, const int32_t* row_adapter, const int32_t* n_hist, const int32_t* slot) {
+  CHECK_HANDLE(h);
+  return model_rank_cache_store(h->m, row_adapter, n_hist, slot);
+}
+int32_t rsys_rank_cache_candidates(rsys_model* h, const int32_t* row_adapter, const int32_t* slot, const int32_t* n_cand, float* out) {
+  CHECK_HANDLE(h);
+  return model_rank_cache_candidates(h->m, row_adapter, slot, n_cand, out);
+}
+int32_t rsys_rank_cache_get(rsys_model* h, int32_t layer, int32_t slot, void* out, int64_t bytes) {
+  CHECK_HANDLE(h);
+  return model_rank_cache_get(h->m, layer, slot, out, bytes);
+}
+
 int32_t rsys_trunk_output_get(rsys_model* h, float* out, int64_t n) {
   CHECK_HANDLE(h);
   Model* m = h->m;
@@ -890,6 +904,21 @@ int32_t rsys_op_attention(int32_t dtype, int32_t B, int32_t T, int32_t H, int32_
   hipFree(maps); hipFree(delta); hipFree(pairbits);
   if (rc) return rc;
   HIP_CHECK(e2);
+  return RSYS_OK;
+}
+
+int32_t rsys_op_attention_cached(int32_t dtype, int32_t rows, int32_t T, int32_t H, int32_t KV, int32_t hd, const void* qkv, const void* cache,
+                                 int32_t n_slots, const int32_t* slot, const int32_t* n_hist, const int32_t* n_cand, void* O) {
+  switches_parse();
+  ARG_CHECK(dtype == RSYS_DTYPE_BF16 || dtype == RSYS_DTYPE_FP32, "dtype: fp32 or bf16");
+  ARG_CHECK(qkv && cache && slot && n_hist && n_cand && O && KV >= 1 && H >= 1, "null or empty");
+  CandAttnParams p{};
+  p.rows = rows; p.T = T; p.H = H; p.KV = KV; p.hd = hd;
+  p.qkv = qkv; p.ld = (long long)(H + 2 * KV) * hd; p.cache = cache; p.n_slots = n_slots;
+  p.slot = slot; p.n_hist = n_hist; p.n_cand = n_cand; p.o = O; p.ldo = (long long)H * hd;
+  const int rc = dtype == RSYS_DTYPE_BF16 ? launch_attn_cand<bf16>(p, nullptr) : launch_attn_cand<float>(p, nullptr);
+  if (rc) return rc;
+  HIP_CHECK(hipDeviceSynchronize());
   return RSYS_OK;
 }
 

@@ -231,6 +231,23 @@ struct AttnParams {
   unsigned long long *qbits, *kbits;
 };
 int launch_attn_tilemap(const AttnParams& p, hipStream_t s);
+// Candidate attention against a cached history (rank_cache.hip; Finetune/embed.py:74-131's ranking row without its history half).  Row r of
+// qkv [rows * T][ld] holds n_cand[r] candidates, candidate j at tokens 2 j (item) and 2 j + 1 (action).  A query token of candidate j
+// sees the 2 n_hist[r] cached tokens of slot[r] -- cache [n_slots][T][2 KV hd], K | V per token, post-RoPE -- and the row's own
+// tokens 2 j, 2 j + 1, in one soft-max.  O of tokens from 2 n_cand[r] on: zeros up to the end of the last 64-token tile that holds a
+// candidate, untouched behind it (those tiles do no work).  n_hist[r] = 0: only the pair.
+struct CandAttnParams {
+  int rows, T, H, KV, hd;
+  const void* qkv; long long ld;        // q | k | v of the fresh rows, as AttnParams
+  const void* cache; int n_slots;       // one layer's slots
+  const int *slot, *n_hist, *n_cand;    // [rows], device
+  void* o; long long ldo;               // [rows * T][H * hd]
+};
+template <typename T> int launch_attn_cand(const CandAttnParams& p, hipStream_t s);
+// K | V of tokens [0, 2 n_hist[r]) of row r of qkv -> cache slot slot[r] (one layer)
+// (kv_off: first K column of a qkv row; kvw = 2 KV hd)
+template <typename T> int launch_rank_cache_copy(const T* qkv, long long ld, int kv_off, int kvw, int T_len, int rows, const int* slot, const int* n_hist,
+                                                 int n_slots, T* cache, hipStream_t s);
 template <typename T> int launch_attn_fwd(const AttnParams& p, hipStream_t s);
 template <typename T> int launch_attn_bwd(const AttnParams& p, hipStream_t s);
 

@@ -397,6 +397,7 @@ int model_destroy(Model* m) {
   retrieve_eval_free(m);
   adapter_bank_free(m);
   render_free(m);
+  rank_cache_free(m);
   if (m->copy_stream) { hipStreamSynchronize(m->copy_stream); hipStreamDestroy(m->copy_stream); }
   if (m->h_stage) hipHostFree(m->h_stage);
   if (m->slot_stage[1]) hipHostFree(m->slot_stage[1]);
@@ -926,11 +927,10 @@ static int infer_t(Model* m, int task, const int32_t* sel, int64_t n_sel, float*
 // are (*rows_f32 says where); task 1, the rating head (model.py:355-359) on those rows only, in chunks of the head workspace, into dst.
 // Stream-ordered, no host wait.
 template <typename T>
-static int infer_rows_t(Model* m, int task, const int* d_sel, int64_t ntok, float* dst, const float** rows_f32) {
-  const int rows = m->cur_rows, N = rows * m->S, D = m->D;
+int infer_trunk(Model* m) {
+  const int N = m->cur_rows * m->S;
   hipStream_t s = m->stream;
   BatchDev b = m->bd;
-  const int KB = m->K * m->rows_max;
   m->f8_tcopies = false;
   HIP_CHECK(hipMemcpyAsync(b.m_tmid, b.tmid, N * 4, hipMemcpyDeviceToDevice, s));
   HIP_CHECK(hipMemcpyAsync(b.m_matchedid, b.matchedid, N * 4, hipMemcpyDeviceToDevice, s));
@@ -939,7 +939,16 @@ static int infer_rows_t(Model* m, int task, const int* d_sel, int64_t ntok, floa
   HIP_CHECK(hipMemcpyAsync(b.m_progress, b.progress, N * 4, hipMemcpyDeviceToDevice, s));
   m->drop_active = false;
   m->top_is_sparse = false;
-  RC(forward_trunk<T>(m));
+  return forward_trunk<T>(m);
+}
+template int infer_trunk<float>(Model*);
+template int infer_trunk<bf16>(Model*);
+template <typename T>
+static int infer_rows_t(Model* m, int task, const int* d_sel, int64_t ntok, float* dst, const float** rows_f32) {
+  const int D = m->D;
+  hipStream_t s = m->stream;
+  const int KB = m->K * m->rows_max;
+  RC(infer_trunk<T>(m));
   const T* src = AT<T>(m->out);
   if (d_sel != nullptr) {
     RC(launch_gather_rows_plain<T>(AT<T>(m->out), D, d_sel, 0, AT<T>(m->dhn), (int)ntok, D, s));
@@ -969,6 +978,11 @@ static int infer_rows_t(Model* m, int task, const int* d_sel, int64_t ntok, floa
   }
   return RSYS_OK;
 }
+
+template <typename T>
+int infer_rows_device(Model* m, int task, const int* d_sel, int64_t ntok, float* dst, const float** rows_f32) { return infer_rows_t<T>(m, task, d_sel, ntok, dst, rows_f32); }
+template int infer_rows_device<float>(Model*, int, const int*, int64_t, float*, const float**);
+template int infer_rows_device<bf16>(Model*, int, const int*, int64_t, float*, const float**);
 
 int model_infer_device(Model* m, int task, const int32_t* row_adapter, const int* d_sel, int n_sel, float* d_out) {
   ARG_CHECK(m->cur_rows > 0, "no batch uploaded");

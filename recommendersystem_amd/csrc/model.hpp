@@ -278,6 +278,14 @@ struct Model {
   AdapterBank* bank = nullptr;
   const int* bank_rows = nullptr;
   RenderState* render = nullptr;        // rsys_render_request's workspace, forward counters and kept intermediates (allocated on first use)
+  // ranking cache (rank_cache.hip, rsys_rank_cache_*): the post-RoPE K | V of users' history tokens per layer, [L][rc_slots][T][2 KV hd] in
+  // the compute dtype, and the events held per slot (-1: never stored).  rc_mode is non-zero only inside the two cache calls: 1 = store
+  // (forward_trunk copies every layer's K | V of the resident history rows into their slots), 2 = candidates (the resident rows are
+  // candidate rows: no tile maps, attention through launch_attn_cand); rc_rows = the rows' {slot, n_hist, n_cand} on the device.  Every
+  // other pass finds rc_mode == 0 and launches what it always has.  Not part of checkpoints.
+  void* rcache = nullptr; int rc_slots = 0; std::vector<int> rc_nhist;
+  int* rc_rows = nullptr;               // [3][rows_max]
+  int rc_mode = 0;
 };
 
 struct Optimizer {
@@ -326,6 +334,17 @@ int model_batch_device_begin(Model* m, int rows, BatchDevRows* out);
 // (task 0: n_sel x D trunk rows, task 1: n_sel rating-head values, fp32) both on the device; row_adapter (host) may be null (base model);
 // stream-ordered, no host wait
 int model_infer_device(Model* m, int task, const int32_t* row_adapter, const int* d_sel, int n_sel, float* d_out);
+// rank_cache.hip: full-length ranking through a per-user K/V cache of the history (rsys_rank_cache_*)
+int model_rank_cache_reserve(Model* m, int n_slots);
+int model_rank_cache_store(Model* m, const int32_t* row_adapter, const int32_t* n_hist, const int32_t* slot);
+int model_rank_cache_candidates(Model* m, const int32_t* row_adapter, const int32_t* slot, const int32_t* n_cand, float* out);
+int model_rank_cache_get(Model* m, int layer, int slot, void* out, int64_t bytes);   // a slot's K | V rows of one layer, [2 n_hist][2 KV hd], compute dtype
+void rank_cache_free(Model* m);
+template <typename T> int rank_cache_store_layer(Model* m, int l, const T* qkv);      // forward_trunk, rc_mode == 1
+template <typename T> int rank_cache_attention(Model* m, int l, const T* qkv, T* O);  // forward_trunk, rc_mode == 2
+// the inference forward over the resident batch with the tokens to report (n_sel flat indices) and the rating head's values on the device
+template <typename T> int infer_rows_device(Model* m, int task, const int* d_sel, int64_t ntok, float* dst, const float** rows_f32);
+template <typename T> int infer_trunk(Model* m);   // its first part alone: the batch as given (no masking) through forward_trunk
 int model_item_table(Model* m, float* out, int64_t n);
 // the fp32 item table rows [V_m][D] of `medium` on the model's device (rsys_sim_features_from_model); the model's stream is idle on return
 int model_item_table_device(Model* m, int medium, const float** rows, int64_t* Vm, int* D);

@@ -173,7 +173,7 @@ int forward_trunk(Model* m) {
   ap.uid = m->uid_t; ap.tm = m->tm_t; ap.qmap = m->qmap; ap.kmap = m->kmap; ap.qmap_full = m->qmap_full; ap.kmap_full = m->kmap_full; ap.qmap16 = m->qmap16; ap.kmap16 = m->kmap16;
   ap.maps_zero_base = m->kmap; ap.maps_zero_bytes = m->maps_zero_bytes;
   ap.order_q = m->attn_order_q; ap.order_q2 = m->attn_order_q + (int64_t)m->rows_max * m->H * ((m->T + 63) / 64); ap.order_k = m->attn_order_k; ap.qbits = m->attn_qbits; ap.kbits = m->attn_kbits;
-  RC(launch_attn_tilemap(ap, s));
+  if (m->rc_mode != 2) RC(launch_attn_tilemap(ap, s));   // (rc_mode 2, rsys_rank_cache_candidates: candidate rows have no tile maps)
   toc(m);
   AttnParams ap_top = ap;   // the last layer under the compact top: selected-first token order, its own tile maps, leading query tiles only
   if (m->top_is_sparse) {
@@ -230,6 +230,12 @@ int forward_trunk(Model* m) {
       RC(gemm<T>(m, "gemm_lora_b_fwd", p, false, false, false));
     }
     if (m->bank_rows) RC(adapter_bank_stage_b<T>(m, l, AT<T>(a.qkv), rpos_l));
+    if (m->rc_mode == 1) RC(rank_cache_store_layer<T>(m, l, AT<T>(a.qkv)));   // rsys_rank_cache_store: the forward as it is + this layer's K | V of the history rows into their slots
+    if (m->rc_mode == 2) {   // rsys_rank_cache_candidates: the rows' candidates against their slots' cached history
+      RC(rank_cache_attention<T>(m, l, AT<T>(a.qkv), AT<T>(a.O)));
+      RC(layer_tail_dense<T>(m, l));
+      continue;
+    }
     AttnParams& apl = top ? ap_top : ap;
     apl.q = a.qkv; apl.k = AT<T>(a.qkv) + m->H * hd; apl.v = AT<T>(a.qkv) + (m->H + m->KV) * hd; apl.ld = m->Nqkv;
     apl.o = a.O; apl.ldo = D; apl.lse = a.lse;

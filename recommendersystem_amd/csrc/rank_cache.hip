@@ -1,0 +1,186 @@
+// Full-length ranking through a per-user K/V cache of the history (rsys_rank_cache_*; Finetune/embed.py:74-161).  The reference ranks a
+// user in ONE row of max_user_len + max_ranking_items interactions: the history (token_mask_ids 0) and then the candidates (token_mask_ids
+// n_hist + j, all at rope_input_pos n_hist).  Under allowed(q, kv) = same user AND (tm[kv] == 0 OR tm[q] == tm[kv]) a history token never
+// sees a candidate, and a candidate sees the whole history plus its own two tokens: the history's K and V of every layer do not depend on
+// the candidates.  So the history runs once, alone, in a row of the trunk's ordinary length (store: the unchanged forward_trunk, which copies K | V behind
+// every layer's QKV stage -- RoPE, LoRA and adapter-bank updates included -- into the user's slot), and the candidates run as query-only
+// rows against the slot (candidates: the same trunk, no tile maps, attention through attn_cand_kernel).  Everything that is not attention
+// is token-local, so nothing else of the trunk changes.
+#include "model_internal.hpp"
+
+namespace rsys {
+
+static int rc_check_model(Model* m) {
+  ARG_CHECK(!m->fp8, "ranking cache: fp32 and bf16 models only");
+  ARG_CHECK(!m->sharded, "ranking cache: a model with a replicated table");
+  return RSYS_OK;
+}
+static inline size_t rc_kvw(const Model* m) { return (size_t)2 * m->KV * m->hd; }                    // values of a cached token: K | V
+static inline size_t rc_layer_elems(const Model* m) { return (size_t)m->rc_slots * m->T * rc_kvw(m); }
+
+void rank_cache_free(Model* m) {
+  if (m->rcache) (void)hipFree(m->rcache);
+  if (m->rc_rows) (void)hipFree(m->rc_rows);
+  m->rcache = nullptr; m->rc_rows = nullptr; m->rc_slots = 0; m->rc_nhist.clear(); m->rc_mode = 0;
+}
+
+int model_rank_cache_reserve(Model* m, int n_slots) {
+  RC(rc_check_model(m));
+  ARG_CHECK(n_slots >= 0 && n_slots <= (1 << 20), "ranking cache: 0 <= n_slots <= 2^20");
+  HIP_CHECK(hipSetDevice(m->device));
+  HIP_CHECK(hipStreamSynchronize(m->stream));
+  if (n_slots == 0) { rank_cache_free(m); return RSYS_OK; }
+  const size_t bytes = (size_t)m->L * n_slots * m->T * rc_kvw(m) * m->esz;
+  const size_t held = (size_t)m->L * m->rc_slots * m->T * rc_kvw(m) * m->esz;
+  size_t free_b = 0, total_b = 0;
+  HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
+  // (checked before the old cache goes: a size that cannot fit leaves the slots that are stored where they are)
+  if (bytes > free_b + held) {
+    set_error("ranking cache: " + std::to_string(n_slots) + " slots need " + std::to_string(bytes) + " bytes, " + std::to_string(free_b + held) + " are free");
+    return RSYS_ERR_STATE;
+  }
+  rank_cache_free(m);
+  void* p = nullptr;
+  if (hipMalloc(&p, bytes) != hipSuccess) {
+    (void)hipGetLastError();
+    set_error("ranking cache: " + std::to_string(n_slots) + " slots need " + std::to_string(bytes) + " bytes, " + std::to_string(free_b) + " are free");
+    return RSYS_ERR_STATE;
+  }
+  // rows' {slot, n_hist, n_cand} and the candidates' RoPE positions (one per token of a full batch)
+  int* rows = nullptr;
+  if (hipMalloc((void**)&rows, ((size_t)3 * m->rows_max + (size_t)m->rows_max * m->T) * 4) != hipSuccess) {
+    (void)hipGetLastError(); (void)hipFree(p);
+    set_error("ranking cache: no memory for the row descriptors");
+    return RSYS_ERR_STATE;
+  }
+  m->rcache = p; m->rc_rows = rows; m->rc_slots = n_slots;
+  m->rc_nhist.assign((size_t)n_slots, -1);
+  return RSYS_OK;
+}
+
+template <typename T>
+int rank_cache_store_layer(Model* m, int l, const T* qkv) {
+  tic(m, "hbm_rank_cache_store", 2.0 * sizeof(T) * m->cur_rows * m->T * (double)rc_kvw(m));
+  const int rc = launch_rank_cache_copy<T>(qkv, m->Nqkv, m->H * m->hd, (int)rc_kvw(m), m->T, m->cur_rows, m->rc_rows, m->rc_rows + m->rows_max, m->rc_slots,
+                                           (T*)m->rcache + (size_t)l * rc_layer_elems(m), m->stream);
+  toc(m);
+  return rc;
+}
+template <typename T>
+int rank_cache_attention(Model* m, int l, const T* qkv, T* O) {
+  CandAttnParams p{};
+  p.rows = m->cur_rows; p.T = m->T; p.H = m->H; p.KV = m->KV; p.hd = m->hd;
+  p.qkv = qkv; p.ld = m->Nqkv;
+  p.cache = (const T*)m->rcache + (size_t)l * rc_layer_elems(m); p.n_slots = m->rc_slots;
+  p.slot = m->rc_rows; p.n_hist = m->rc_rows + m->rows_max; p.n_cand = m->rc_rows + 2 * m->rows_max;
+  p.o = O; p.ldo = m->D;
+  tic(m, "attn_cand");
+  const int rc = launch_attn_cand<T>(p, m->stream);
+  toc(m);
+  return rc;
+}
+template int rank_cache_store_layer<float>(Model*, int, const float*);
+template int rank_cache_store_layer<bf16>(Model*, int, const bf16*);
+template int rank_cache_attention<float>(Model*, int, const float*, float*);
+template int rank_cache_attention<bf16>(Model*, int, const bf16*, bf16*);
+
+static int rc_check_call(Model* m, const int32_t* a, const int32_t* b) {
+  RC(rc_check_model(m));
+  ARG_CHECK(m->rcache != nullptr, "ranking cache: nothing reserved (rsys_rank_cache_reserve)");
+  ARG_CHECK(m->cur_rows > 0, "no batch uploaded");
+  ARG_CHECK(a != nullptr && b != nullptr, "ranking cache: null row arrays");
+  return RSYS_OK;
+}
+
+int model_rank_cache_store(Model* m, const int32_t* row_adapter, const int32_t* n_hist, const int32_t* slot) {
+  RC(rc_check_call(m, n_hist, slot));
+  const int rows = m->cur_rows;
+  std::vector<char> seen((size_t)m->rc_slots, 0);
+  for (int r = 0; r < rows; ++r) {
+    ARG_CHECK(n_hist[r] >= 0 && n_hist[r] <= m->S, "ranking cache: n_hist must be in [0, max_sequence_length]");
+    ARG_CHECK(slot[r] >= 0 && slot[r] < m->rc_slots, "ranking cache: slot outside the reserve");
+    ARG_CHECK(!seen[slot[r]], "ranking cache: the slots of one store call must be distinct");
+    seen[slot[r]] = 1;
+  }
+  HIP_CHECK(hipSetDevice(m->device));
+  if (row_adapter) RC(adapter_bind_rows(m, row_adapter));
+  std::vector<int> h((size_t)3 * m->rows_max, 0);
+  for (int r = 0; r < rows; ++r) { h[r] = slot[r]; h[m->rows_max + r] = n_hist[r]; }
+  int rc = RSYS_OK;
+  auto run = [&]() -> int {
+    HIP_CHECK(hipMemcpyAsync(m->rc_rows, h.data(), h.size() * 4, hipMemcpyHostToDevice, m->stream));
+    m->rc_mode = 1;
+    RC(m->bf16_mode ? infer_trunk<bf16>(m) : infer_trunk<float>(m));
+    HIP_CHECK(hipStreamSynchronize(m->stream));
+    return RSYS_OK;
+  };
+  rc = run();
+  m->rc_mode = 0;
+  adapter_unbind_rows(m);
+  if (rc != RSYS_OK) (void)hipStreamSynchronize(m->stream);   // (the copies above read this call's host vectors)
+  // (a failed pass may have written some layers of the slots: they no longer hold a history)
+  for (int r = 0; r < rows; ++r) m->rc_nhist[slot[r]] = rc == RSYS_OK ? n_hist[r] : -1;
+  return rc;
+}
+
+int model_rank_cache_candidates(Model* m, const int32_t* row_adapter, const int32_t* slot, const int32_t* n_cand, float* out) {
+  RC(rc_check_call(m, slot, n_cand));
+  ARG_CHECK(out != nullptr, "ranking cache: null output");
+  const int rows = m->cur_rows, T = m->T;
+  int64_t ntok = 0;
+  for (int r = 0; r < rows; ++r) {
+    ARG_CHECK(slot[r] >= 0 && slot[r] < m->rc_slots, "ranking cache: slot outside the reserve");
+    ARG_CHECK(m->rc_nhist[slot[r]] >= 0, "ranking cache: slot never stored");
+    ARG_CHECK(m->rc_nhist[slot[r]] <= m->S - 1, "ranking cache: candidates run at position n_hist, which must stay below max_sequence_length");
+    ARG_CHECK(n_cand[r] >= 1 && n_cand[r] <= m->S, "ranking cache: n_cand must be in [1, max_sequence_length]");
+    ntok += n_cand[r];
+  }
+  HIP_CHECK(hipSetDevice(m->device));
+  if (row_adapter) RC(adapter_bind_rows(m, row_adapter));
+  std::vector<int> h((size_t)3 * m->rows_max, 0), pos((size_t)rows * T), sel((size_t)ntok);
+  int64_t k = 0;
+  for (int r = 0; r < rows; ++r) {
+    const int nh = m->rc_nhist[slot[r]];
+    h[r] = slot[r]; h[m->rows_max + r] = nh; h[2 * m->rows_max + r] = n_cand[r];
+    for (int i = 0; i < m->S; ++i) { pos[(size_t)r * T + 2 * i] = 2 * nh; pos[(size_t)r * T + 2 * i + 1] = 2 * nh + 1; }   // model.py:470-476 at rope_input_pos = n_hist
+    for (int j = 0; j < n_cand[r]; ++j) sel[k++] = r * T + 2 * j + 1;
+  }
+  // the rows' positions live in the cache's own buffer for the length of this call: the resident batch's rope_input_pos stays what it is
+  int* const d_pos = m->rc_rows + 3 * m->rows_max;
+  int* const saved_pos = m->d_rope_pos; const bool saved_has = m->has_rope_pos;
+  auto run = [&]() -> int {
+    hipStream_t s = m->stream;
+    HIP_CHECK(hipMemcpyAsync(m->rc_rows, h.data(), h.size() * 4, hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(d_pos, pos.data(), pos.size() * 4, hipMemcpyHostToDevice, s));
+    int* d_sel = (int*)m->gf;   // (as rsys_infer_select: room for every token of the batch)
+    HIP_CHECK(hipMemcpyAsync(d_sel, sel.data(), sel.size() * 4, hipMemcpyHostToDevice, s));
+    m->d_rope_pos = d_pos; m->has_rope_pos = true;
+    m->rc_mode = 2;
+    const float* f = nullptr;
+    RC(m->bf16_mode ? infer_rows_device<bf16>(m, 1, d_sel, ntok, m->delta, &f) : infer_rows_device<float>(m, 1, d_sel, ntok, m->delta, &f));
+    HIP_CHECK(hipStreamSynchronize(s));
+    return RSYS_OK;
+  };
+  int rc = run();
+  m->rc_mode = 0;
+  m->d_rope_pos = saved_pos; m->has_rope_pos = saved_has;
+  adapter_unbind_rows(m);
+  if (rc != RSYS_OK) { (void)hipStreamSynchronize(m->stream); return rc; }
+  HIP_CHECK(hipMemcpy(out, m->delta, (size_t)ntok * 4, hipMemcpyDeviceToHost));   // (out is written only by a call that succeeded)
+  return RSYS_OK;
+}
+
+int model_rank_cache_get(Model* m, int layer, int slot, void* out, int64_t bytes) {
+  ARG_CHECK(m->rcache != nullptr, "ranking cache: nothing reserved");
+  ARG_CHECK(layer >= 0 && layer < m->L && slot >= 0 && slot < m->rc_slots && out != nullptr, "ranking cache: layer or slot out of range");
+  ARG_CHECK(m->rc_nhist[slot] >= 0, "ranking cache: slot never stored");
+  const size_t want = (size_t)2 * m->rc_nhist[slot] * rc_kvw(m) * m->esz;
+  ARG_CHECK(bytes == (int64_t)want, "ranking cache: out holds [2 n_hist][2 KV hd] values of the compute dtype");
+  HIP_CHECK(hipSetDevice(m->device));
+  HIP_CHECK(hipStreamSynchronize(m->stream));
+  const unsigned char* src = (const unsigned char*)m->rcache + ((size_t)layer * rc_layer_elems(m) + (size_t)slot * m->T * rc_kvw(m)) * m->esz;
+  if (want) HIP_CHECK(hipMemcpy(out, src, want, hipMemcpyDeviceToHost));
+  return RSYS_OK;
+}
+
+}  // namespace rsys

@@ -362,6 +362,53 @@ class RecommenderModel:
         check(lib().rsys_infer_select_adapters(self._h, t, slots.ctypes.data, idx.ctypes.data, idx.size, out.ctypes.data, out.size))
         return out
 
+    # ---- ranking cache (full-length histories: the history's K / V per layer once, the candidates against it; embed.py:74-161)
+    def _row_slots(self, d, adapters):
+        rows = int(np.asarray(d["userid"]).size) // self.config["max_sequence_length"]
+        if adapters is None:
+            return rows, None
+        slots = np.full(rows, int(adapters), np.int32) if np.ndim(adapters) == 0 else np.ascontiguousarray(np.asarray(adapters).reshape(-1), np.int32)
+        if slots.size != rows:
+            raise ValueError(f"rank cache: {slots.size} adapter slots for {rows} batch rows")
+        return rows, slots
+
+    def rank_cache_reserve(self, n_slots):
+        """n_slots cache slots of [num_layers][2S][2 num_kv_heads head_dim] values in the compute dtype (0 frees them; a new size drops
+        what was stored)"""
+        check(lib().rsys_rank_cache_reserve(self._h, int(n_slots)))
+        self.rank_cache_slots = int(n_slots)
+
+    def rank_cache_store(self, d, n_hist, slots, adapters=None):
+        """The trunk forward of the history-only rows `d` (row r: n_hist[r] events, token_mask_ids 0, rope_input_pos 0 .. n_hist[r] - 1);
+        every layer's K / V of row r's history tokens goes to cache slot slots[r].  `adapters` as in `inference_select`."""
+        self.upload(d)
+        rows, ad = self._row_slots(d, adapters)
+        nh = np.ascontiguousarray(np.asarray(n_hist).reshape(-1), np.int32); sl = np.ascontiguousarray(np.asarray(slots).reshape(-1), np.int32)
+        if nh.size != rows or sl.size != rows:
+            raise ValueError(f"rank_cache_store: {nh.size} history lengths and {sl.size} slots for {rows} batch rows")
+        check(lib().rsys_rank_cache_store(self._h, None if ad is None else ad.ctypes.data, nh.ctypes.data, sl.ctypes.data))
+
+    def rank_cache_candidates(self, d, slots, n_cand, adapters=None):
+        """The trunk forward of the candidate rows `d` (row r: n_cand[r] candidates at events 0 .. n_cand[r] - 1) against the histories
+        cached in slots[r]; returns the rating head at the candidates' action tokens, (sum n_cand,) float32 in row order."""
+        self.upload(d)
+        rows, ad = self._row_slots(d, adapters)
+        sl = np.ascontiguousarray(np.asarray(slots).reshape(-1), np.int32); nc = np.ascontiguousarray(np.asarray(n_cand).reshape(-1), np.int32)
+        if nc.size != rows or sl.size != rows:
+            raise ValueError(f"rank_cache_candidates: {sl.size} slots and {nc.size} candidate counts for {rows} batch rows")
+        out = np.empty(int(np.clip(nc, 0, None).sum()), np.float32)
+        check(lib().rsys_rank_cache_candidates(self._h, None if ad is None else ad.ctypes.data, sl.ctypes.data, nc.ctypes.data, out.ctypes.data))
+        return out
+
+    def rank_cache_get(self, layer, slot, n_hist):
+        """test hook (rsys_debug.h): the K | V rows slot `slot` holds for `layer`, (2 n_hist, 2 num_kv_heads head_dim), float32 for an
+        fp32 model, raw bf16 bit patterns (uint16) for a bf16 model; n_hist must be what was stored"""
+        c = self.config
+        kvw = 2 * c["num_kv_heads"] * (c["embed_dim"] // c["num_heads"])
+        out = np.empty((2 * int(n_hist), kvw), np.float32 if self.dtype == "fp32" else np.uint16)
+        check(lib().rsys_rank_cache_get(self._h, int(layer), int(slot), out.ctypes.data, out.nbytes))
+        return out
+
     # ---- adapter bank (base model: several LoRA adapter sets beside one frozen trunk, Finetune/embed.py:180-255)
     ADAPTER_SLOTS = 8
 

@@ -150,6 +150,77 @@ def predict(model, users, task, medium, max_user_len=None, max_ranking_items=Non
     return out
 
 
+def rank_cache_plan(n_hist, n_cand, S, max_rows):
+    """The calls `predict_ranking_full` makes for users with `n_hist[i]` >= 1 history events and `n_cand[i]` candidates, as data: a list of
+    waves of at most `max_rows` users; a wave is (store, batches) with store = [(user, slot, n_hist)] (slot = the user's place in the
+    wave, one history row each) and batches = lists of at most `max_rows` candidate rows (user, slot, first candidate, candidates <= S,
+    rope_input_pos = n_hist), users in order and a user's rows in candidate order -- so the concatenated outputs of a wave's batches are
+    the users' values in order."""
+    waves = []
+    for u0 in range(0, len(n_hist), max_rows):
+        users = range(u0, min(u0 + max_rows, len(n_hist)))
+        store = [(u, u - u0, int(n_hist[u])) for u in users]
+        rows = [(u, u - u0, c0, min(S, int(n_cand[u]) - c0), int(n_hist[u])) for u in users for c0 in range(0, int(n_cand[u]), S)]
+        waves.append((store, [rows[r0:r0 + max_rows] for r0 in range(0, len(rows), max_rows)]))
+    return waves
+
+
+def predict_ranking_full(model, users, medium):
+    """`predict(model, users, "ranking", medium)` on the reference's row (embed.py:74-161 with max_user_len = S): every user is ranked
+    on its newest S - 1 history events, whatever the number of candidates, instead of the newest S // 2 - 1 that share a row with the
+    candidates.  Each history is tokenised and projected once and runs once (one `rank_cache_store` per wave of `max_rows` users);
+    the candidates run against the cached K / V in rows of up to S (a user's candidates may span rows, several users' rows share a
+    forward).  Users with an empty history go through `predict`, one row per chunk of S - S // 2 candidates as `render` cuts them, so
+    their values are what `render` gives today.  Returns what `predict` returns, for any number of candidates."""
+    S = model.config["max_sequence_length"]
+    n0 = model.config["vocab_sizes"]["0_matchedid"]
+    key = f"{medium}.ranking"
+    out = [None] * len(users)
+    hists = [_history(u, S) for u in users]
+    chunk = S - S // 2
+    for i in (i for i, h in enumerate(hists) if not h):
+        # as `render` runs them: one `predict` row per chunk of S - S // 2 candidates, so the values are the ones that path gives
+        # (with an empty history they depend on where the chunks are cut: candidate 0 of a row carries mask id 0)
+        items, vals = users[i]["ranking_items"], []
+        for c0 in range(0, len(items), chunk):
+            vals += predict(model, [dict(users[i], ranking_items=items[c0:c0 + chunk])], "ranking", medium)[0][key]
+        out[i] = {key: vals}
+    full = [i for i, h in enumerate(hists) if h]
+    for i in full:
+        if not users[i]["ranking_items"]:
+            out[i] = {key: []}
+    full = [i for i in full if users[i]["ranking_items"]]
+    if not full:
+        return out
+    slots = getattr(model, "adapter_slots", None)
+    adapter = slots[key] if slots else None
+    max_rows = model.max_rows
+    if getattr(model, "rank_cache_slots", 0) < min(max_rows, len(full)):
+        model.rank_cache_reserve(max_rows)
+    plan = rank_cache_plan([len(hists[i]) for i in full], [len(users[i]["ranking_items"]) for i in full], S, max_rows)
+    for store, batches in plan:
+        d = _empty_rows(len(store), S)
+        for row, (k, _, nh) in enumerate(store):
+            _fill_row(d, row, hists[full[k]], nh, users[full[k]]["user"], n0, False)
+        model.rank_cache_store(d, [s[2] for s in store], [s[1] for s in store], adapters=adapter)
+        vals = {k: [] for k, _, _ in store}
+        for rows in batches:
+            d = _empty_rows(len(rows), S)
+            for row, (k, _, c0, n, nh) in enumerate(rows):
+                u = users[full[k]]
+                seq = [make_item(u["timestamp"], medium, c) for c in u["ranking_items"][c0:c0 + n]]
+                _fill_row(d, row, seq, 0, u["user"], n0, False)
+                d["rope_input_pos"][row, :] = nh     # (the reference's value for every candidate; the call sets the positions itself from the
+                                                     #  slot, so this only keeps the uploaded row equal to the reference's candidate events)
+            v = model.rank_cache_candidates(d, [r[1] for r in rows], [r[3] for r in rows], adapters=adapter)
+            at = 0
+            for k, _, _, n, _ in rows:
+                vals[k] += v[at:at + n].tolist(); at += n
+        for k, _, _ in store:
+            out[full[k]] = {key: vals[k]}
+    return out
+
+
 def predict_mixed(model, requests, task, max_user_len=None, max_ranking_items=None):
     """`predict` for users of both media in ONE forward: `requests` = [(user, medium), ...]; row i of the batch is the row
     `build_batch([user_i], task, medium_i, ...)` builds and runs with the adapter slot `model.adapter_slots[f"{medium_i}.{task}"]`
@@ -510,13 +581,16 @@ def page_window(n_retrieved, pagination):
     return start, stop, sidx - start, eidx - start
 
 
-def render(model, states, pagination, registry=None, max_ranking_items=None):
+def render(model, states, pagination, registry=None, max_ranking_items=None, full_history=False):
     """render.jl `render(state, pagination)` (lines 437-474) without the card rendering, for a list of states: `retrieval`, the page's
     slice of at most 1024 candidates, the ranking forward (`predict(..., "ranking")` in chunks of at most `max_ranking_items` candidates,
-    default the model's S - S // 2; candidates are masked from each other, so chunking does not change the result), then `ranking` +
-    `reranking` in one device call with partialk = the page's last index.  `pagination`: {"offset", "limit"} or one per state.  Returns
-    one (ids of the page, total) pair per state.  Deviations: the ranked slice is clamped to the retrieved list (render.jl throws a
-    BoundsError), and total = min(admissible items, 8192), the retrieval cap."""
+    default the model's S - S // 2; candidates are masked from each other, so chunking does not change the result of a user with a
+    history -- with an EMPTY history the first candidate of every chunk carries mask id 0 and is seen by the chunk's others, so there
+    the values depend on where the chunks are cut), then `ranking` + `reranking` in one device call with partialk = the page's last
+    index.  `full_history=True`: the ranking forward is `predict_ranking_full` instead -- every user ranked on its newest S - 1 events
+    (the reference's row) rather than the S // 2 - 1 that fit beside a chunk; `max_ranking_items` is then not used.  `pagination`:
+    {"offset", "limit"} or one per state.  Returns one (ids of the page, total) pair per state.  Deviations: the ranked slice is
+    clamped to the retrieved list (render.jl throws a BoundsError), and total = min(admissible items, 8192), the retrieval cap."""
     pags = [pagination] * len(states) if isinstance(pagination, dict) else list(pagination)
     S = model.config["max_sequence_length"]
     max_user_len = S // 2
@@ -538,6 +612,11 @@ def render(model, states, pagination, registry=None, max_ranking_items=None):
         sub = [states[w[0]] for w in items]
         for st, w in zip(sub, items):         # the ranking forward: "{m}.ranking" at the page's candidates, per user
             cand = w[1]
+            if full_history:
+                reqs = [dict(u["user"], ranking_items=[int(x) for x in cand]) for u in st["users"]]
+                for u, r in zip(st["users"], predict_ranking_full(model, reqs, m)):
+                    u.setdefault("embeds", {})[f"{m}.ranking"] = np.asarray(r[f"{m}.ranking"], np.float32)
+                continue
             for u in st["users"]:
                 vals = []
                 for c0 in range(0, cand.size, chunk):
