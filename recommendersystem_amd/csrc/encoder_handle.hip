@@ -9,21 +9,6 @@
 
 namespace rsys {
 
-int DevScratch::reserve(size_t need, hipStream_t s) {
-  if (need <= bytes) return RSYS_OK;
-  HIP_CHECK(hipStreamSynchronize(s));
-  if (p) HIP_CHECK(hipFree(p));
-  p = nullptr; bytes = 0;
-  HIP_CHECK(hipMalloc(&p, need));
-  bytes = need;
-  return RSYS_OK;
-}
-
-void DevScratch::release() {
-  if (p) hipFree(p);
-  p = nullptr; bytes = 0;
-}
-
 int enc_alloc(EncoderCore* h, void** p, size_t bytes) {
   bytes = std::max<size_t>(256, (bytes + 255) / 256 * 256);
   HIP_CHECK(hipMalloc(p, bytes));

@@ -2,7 +2,7 @@
 // own, a frozen fp32 feature table, one trainable matrix W and a scalar logit_scale in a flat buffer [W | logit_scale | 3 pad] with
 // matching gradient and AdamW moment buffers, a bf16 shadow of W, and an fp32 slab for split-K sums in a fixed order.  A model embeds
 // the core by inheriting from it and keeps what is its own: kernels, per-call buffers, forward / backward, export and serving calls.
-// Also here: the grow-on-demand device buffer and the workspace carver the request paths use.
+// The grow-on-demand device buffer and the workspace carver come from workspace.hpp (through model.hpp).
 #pragma once
 #include <algorithm>
 #include <vector>
@@ -23,25 +23,6 @@ namespace rsys {
 inline unsigned grid_for(long long work, int per_block = 256, long long cap = 8192) {
   return (unsigned)std::max<long long>(1, std::min<long long>((work + per_block - 1) / per_block, cap));
 }
-
-// One device buffer that only grows.  reserve() waits for `s` before it replaces the buffer (work in flight may still read the old
-// one); the contents are not kept.
-struct DevScratch {
-  void* p = nullptr; size_t bytes = 0;
-  int reserve(size_t need, hipStream_t s);
-  void release();
-};
-
-// Sub-buffers of one workspace at 256-byte steps.  Run the same sequence of take() twice: over a null base to learn the size (off),
-// then over the buffer.
-struct Carve {
-  char* p; size_t off = 0;
-  template <typename X> X* take(size_t count) {
-    X* r = (X*)(p ? p + off : nullptr);
-    off += (std::max<size_t>(count, 1) * sizeof(X) + 255) / 256 * 256;
-    return r;
-  }
-};
 
 struct EncoderCore {
   const char* api = "";                             // "rsys_sim" / "rsys_search": which model's call failed

@@ -318,5 +318,7 @@ struct F8WeightJob {
   unsigned char* dst_t; long long ld_t;             // e4m3 [cols][ld_t]: column = row (SWIGLU: de-interleaved to [all w1 | all w3])
 };
 int launch_f8_weights(const F8WeightJob* jobs_dev, const int* tile_job_dev, const int* tile_first_dev, int ntiles, hipStream_t s);
+// sc[pos[i]] = quiet NaN for i < n (retrieve.hip: the exclusions of the retrieval and evaluation score rows)
+int launch_scatter_nan(float* sc, const long long* pos, long long n, hipStream_t s);
 
 }  // namespace rsys

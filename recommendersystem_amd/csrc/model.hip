@@ -391,10 +391,10 @@ int model_destroy(Model* m) {
   hipStreamSynchronize(m->stream);
   hipStreamSynchronize(m->side);
   for (void* p : m->allocs) hipFree(p);
-  retrieve_free(m);
+  m->rws.release();
   retrieve_tables_free(m);
   rank_free(m);
-  retrieve_eval_free(m);
+  m->ews.release();
   adapter_bank_free(m);
   render_free(m);
   rank_cache_free(m);

@@ -10,6 +10,7 @@
 #include "comm.hpp"
 #include "gemm.hpp"
 #include "kernels.hpp"
+#include "workspace.hpp"
 
 namespace rsys {
 
@@ -44,10 +45,8 @@ struct PhaseTimer {
   std::vector<char> open;   // per open tic: 1 = recorded, 0 = filtered out (its toc records nothing)
 };
 
-struct RetrieveWs;       // retrieve.hip
 struct RetrievalTables;  // retrieve_request.hip
 struct RankTables;       // rank_request.hip
-struct EvalWs;           // retrieve_eval.hip
 struct AdapterBank;      // adapter_bank.hip
 struct RenderState;      // render_request.hip
 
@@ -268,10 +267,10 @@ struct Model {
   bool last_evaluate = false;
   PhaseTimer timer;
   std::vector<hipEvent_t> step_marks;   // rsys_step_mark: one event per optimizer-step boundary (per-step time distribution)
-  RetrieveWs* rws = nullptr;            // rsys_retrieve_topk's workspace (allocated on first use)
+  DevScratch rws;                       // rsys_retrieve_topk's workspace; a RetrieveDev result lives in it until the next retrieval call
   RetrievalTables* rtab = nullptr;      // rsys_retrieve_request's serving tables and workspace (not part of checkpoints)
   RankTables* rank = nullptr;           // rsys_rank_request's "{m}.related" tables and workspace (not part of checkpoints)
-  EvalWs* ews = nullptr;                // rsys_retrieve_target_rank's workspace (allocated on first use)
+  DevScratch ews;                       // rsys_retrieve_target_rank's workspace
   // adapter bank of a base model (adapter_bank.hip, allocated by the first rsys_adapter_set): LoRA adapter sets in slots beside the frozen
   // trunk.  bank_rows (device, one slot or -1 per batch row) is non-null only inside rsys_infer_select_adapters: forward_trunk then adds
   // every row's own update to q and v; every other pass leaves it null and launches what it always has
@@ -362,7 +361,6 @@ int model_set_deterministic(Model* m, int on);
 // retrieve.hip: retrieval top-k over the fused item table of a medium (rsys_retrieve_topk) and the selection alone (rsys_op_topk)
 int model_retrieve_topk(Model* m, int medium, const float* queries, int64_t nq, const int32_t* group, int32_t ng, const float* prior,
                         const int64_t* excl_off, const int32_t* excl_ids, int32_t k, int32_t* ids_out, float* scores_out, int32_t* counts_out);
-void retrieve_free(Model* m);
 // the same pipeline with a device-side initialiser of the group score rows sc [n_groups][V_m] (prior and NaN masks)
 using RetrieveInit = std::function<int(float* sc, hipStream_t s)>;
 struct RetrieveDev;
@@ -430,12 +428,10 @@ int topk_rows(const float* scores, long long ld, int rows, int V, int k, void* w
 // retrieve_eval.hip: the rank and log-probability of one target item per query (rsys_retrieve_target_rank) and the count alone
 int model_retrieve_target_rank(Model* m, int medium, const float* queries, int64_t nq, const int32_t* targets, const int64_t* excl_off,
                                const int32_t* excl_ids, int32_t* rank_out, float* logp_out);
-void retrieve_eval_free(Model* m);
 int op_target_rank(const float* scores, int64_t ld, int32_t rows, int32_t V, const int32_t* targets, int32_t* rank_out);
 // similarity_metrics.hip: catalogue ranks of the targets of item-similarity test sources (rsys_sim_pair_ranks) over a handle's fp32
 // export [V][E] and test-mask bit rows, the masked score rows alone (rsys_sim_pair_scores) and the count alone (rsys_op_pair_ranks).
-// ws: the caller's workspace (encoder_handle.hpp), grown on demand
-struct DevScratch;
+// ws: the caller's workspace, grown on demand
 int pair_ranks_run(const float* exp32, int V, int E, const unsigned* tmask, long long tmw, int32_t n_src, const int32_t* sources,
                    const int64_t* off, const int32_t* tids, int32_t* ranks_out, DevScratch* ws, hipStream_t s);
 int pair_scores_run(const float* exp32, int V, int E, const unsigned* tmask, long long tmw, int32_t n_src, const int32_t* sources,

@@ -7,6 +7,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <initializer_list>
 
 #include "model.hpp"
 
@@ -310,5 +311,50 @@ int select_positions_all(Model* m);
 int select_join(Model* m);   // (position selection may run on the side stream)
 // ---- defined in model_backward.hip
 template <typename T> int backward_trunk(Model* m);
+
+// ---- defined in retrieve.hip: what the request paths share (rsys_retrieve_topk / _request, rsys_rank_request, rsys_retrieve_target_rank,
+// rsys_render_request)
+// The device arrays of query scoring: the queries in fp32 and in the compute type (the same array in fp32 mode), one log-sum-exp per query,
+// the partials and the score slab z [rows][ldz] of one chunk of RETRIEVE_CHUNK queries.
+static inline long long score_ldz(const Model* m) { return pad8(std::max(m->V0, m->V1)); }   // row stride of the score slab, either medium
+template <typename T> struct ScoreBufs {
+  float* qf = nullptr; T* qt = nullptr; float* lse = nullptr; float2* part = nullptr; float* z = nullptr;
+  long long ldz; int D;
+  explicit ScoreBufs(const Model* m) : ldz(score_ldz(m)), D(m->D) {}
+  // nq == 0: nothing is scored (an empty piece each); z_bytes == 0: the rows of one chunk
+  void take(Carve& c, int64_t nq, size_t z_bytes = 0) {
+    qf = c.take<float>((size_t)nq * D);
+    qt = is_bf16<T>::value ? c.take<T>((size_t)nq * D) : (T*)qf;
+    lse = c.take<float>(nq);
+    part = c.take<float2>(nq ? (size_t)RETRIEVE_CHUNK * RETRIEVE_LSE_SPLIT : 0);
+    z = (float*)c.take<char>(z_bytes ? z_bytes : (size_t)std::min<int64_t>(nq, RETRIEVE_CHUNK) * ldz * 4);
+  }
+};
+// The prologue of the chunk loop around retrieve_chunk_scores, in two calls because its callers enqueue them in different orders:
+// the queries [nq][D] fp32 into b.qf (and cast into b.qt in bf16 mode), and the fused item table brought up to date, *Fm = the medium's rows.
+template <typename T> int score_upload_queries(const ScoreBufs<T>& b, const float* queries, int64_t nq, hipMemcpyKind kind, hipStream_t s);
+template <typename T> int score_table_ready(Model* m, int medium, const T** Fm);
+// The queries of each group in query order (members[goff[g] .. goff[g + 1])) and, per chunk c of `chunk` queries, the part of them it
+// holds (ranges[c * ng + g]); group == nullptr: query q is group q.  Fails on a group id outside [0, ng) and on an empty group.
+struct GroupPlan { std::vector<int> goff, members; std::vector<int2> ranges; int nchunks = 0; };
+int group_plan(const char* who, const int32_t* group, int64_t nq, int ng, int chunk, GroupPlan& gp);
+// Ragged lists of a request (offsets [n + 1] and parallel arrays): the words their error texts are built from
+struct ListKind { const char *given, *offsets, *media, *ids; };
+constexpr ListKind LIST_HISTORY{"the history arrays are all given or all NULL", "hist_offsets", "list items' media must be 0 or 1",
+                                "list ids must be in [0, V) of their medium"};
+constexpr ListKind LIST_SELECTED{"the selected-item arrays are all given or all NULL", "sel_offsets", "selected items' media must be 0 or 1",
+                                 "selected ids must be in [0, V) of their medium"};
+// (exclusion lists carry no media: check_list_items takes them with medium == nullptr and V = {V_m, unused})
+constexpr ListKind LIST_EXCLUDED{"excl_offsets and excl_ids are both given or both NULL", "excl_offsets", "",
+                                 "exclusion ids must be medium-local, in [0, V_m)"};
+// off and `arrays` all given or all NULL; if given, off[0] == 0 and off non-decreasing over n rows
+int check_ragged(const char* who, const ListKind& what, const int64_t* off, int64_t n, std::initializer_list<const void*> arrays);
+// every item's medium in {0, 1} and id in [0, V[medium]); medium == nullptr: ids in [0, V[0]).  off == nullptr: nothing to check
+int check_list_items(const char* who, const ListKind& what, const int64_t* off, int64_t n, const int32_t* medium, const int32_t* ids,
+                     const int V[2]);
+// A host CSC matrix checked (colptr, row indices in [0, n_rows) -- `rows` is that range in the caller's words --, values finite and >= 0)
+// and reduced to the pattern of its non-zero entries: cp [n_cols + 1], rv
+int csc_nonzero_pattern(const char* who, const char* rows, int64_t n_rows, int64_t n_cols, const int64_t* colptr, const int32_t* rowval,
+                        const float* nzval, std::vector<int64_t>& cp, std::vector<int32_t>& rv);
 
 }  // namespace rsys

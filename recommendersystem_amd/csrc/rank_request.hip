@@ -51,11 +51,6 @@ struct RelCsc {
   int64_t n = 0, nnz = 0;
 };
 
-template <typename X> void dfree(X*& p) {
-  if (p) hipFree(p);
-  p = nullptr;
-}
-
 __device__ __forceinline__ bool bit(const unsigned* b, long long i) { return (b[i >> 5] >> (i & 31)) & 1u; }
 
 // Julia's isless as an unsigned order: -inf < ... < -0.0 < +0.0 < ... < inf < every NaN (all NaNs equal)
@@ -264,15 +259,6 @@ __global__ void __launch_bounds__(RK_THREADS) page_gather_kernel(const RankGroup
 
 #define RK_LAUNCH_CHECK() HIP_CHECK(hipGetLastError())
 
-struct Carve {
-  char* p; size_t off = 0;
-  template <typename X> X* take(size_t count) {
-    X* r = (X*)(p ? p + off : nullptr);
-    off += (std::max<size_t>(count, 1) * sizeof(X) + 255) / 256 * 256;
-    return r;
-  }
-};
-
 // host side of a request's candidates: the groups' device descriptors and sorted copies of the ids
 struct Groups {
   std::vector<RankGroup> g;
@@ -324,8 +310,7 @@ int make_groups(const char* who, int ng, const int64_t* cand_off, const int32_t*
 
 struct RankTables {
   RelCsc related[2];
-  void* ws = nullptr;   // the request's device workspace, grown on demand
-  size_t ws_bytes = 0;
+  DevScratch ws;        // the request's device workspace
 };
 
 static RankTables* rank_tables(Model* m) {
@@ -337,26 +322,9 @@ void rank_free(Model* m) {
   RankTables* R = m->rank;
   if (!R) return;
   for (RelCsc& c : R->related) { dfree(c.colptr); dfree(c.rowval); }
-  if (R->ws) hipFree(R->ws);
+  R->ws.release();
   delete R;
   m->rank = nullptr;
-}
-
-static int upload(void** dst, const void* src, size_t bytes) {
-  HIP_CHECK(hipMalloc(dst, std::max<size_t>(bytes, 4)));
-  if (bytes) HIP_CHECK(hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice));
-  return RSYS_OK;
-}
-
-static int ensure_ws(Model* m, size_t bytes) {
-  RankTables* R = rank_tables(m);
-  if (R->ws_bytes >= bytes) return RSYS_OK;
-  HIP_CHECK(hipStreamSynchronize(m->stream));
-  if (R->ws) HIP_CHECK(hipFree(R->ws));
-  R->ws = nullptr; R->ws_bytes = 0;
-  HIP_CHECK(hipMalloc(&R->ws, bytes));
-  R->ws_bytes = bytes;
-  return RSYS_OK;
 }
 
 int model_rank_related_set(Model* m, int medium, int64_t n, const int64_t* colptr, const int32_t* rowval, const float* nzval) {
@@ -367,18 +335,7 @@ int model_rank_related_set(Model* m, int medium, int64_t n, const int64_t* colpt
   if (colptr) {
     ARG_CHECK(rowval && nzval, "rank_related_set: rowval and nzval are required with colptr");
     ARG_CHECK(n == Vm, "rank_related_set: the matrix must be V_m x V_m");
-    ARG_CHECK(colptr[0] == 0, "rank_related_set: colptr[0] must be 0");
-    for (int64_t c = 0; c < n; ++c) ARG_CHECK(colptr[c + 1] >= colptr[c], "rank_related_set: colptr must be non-decreasing");
-    cp.assign((size_t)n + 1, 0);
-    rv.reserve((size_t)colptr[n]);
-    for (int64_t c = 0; c < n; ++c) {
-      for (int64_t j = colptr[c]; j < colptr[c + 1]; ++j) {
-        ARG_CHECK(rowval[j] >= 0 && rowval[j] < n, "rank_related_set: row indices must be in [0, V_m)");
-        ARG_CHECK(std::isfinite(nzval[j]) && nzval[j] >= 0.f, "rank_related_set: stored values must be finite and >= 0");
-        if (nzval[j] != 0.f) rv.push_back(rowval[j]);   // (render.jl tests related_vals[k] != 0)
-      }
-      cp[(size_t)c + 1] = (int64_t)rv.size();
-    }
+    RC(csc_nonzero_pattern("rank_related_set", "[0, V_m)", n, n, colptr, rowval, nzval, cp, rv));
   }
   HIP_CHECK(hipSetDevice(m->device));
   HIP_CHECK(hipStreamSynchronize(m->stream));
@@ -410,69 +367,42 @@ static int rank_t(Model* m, int medium, int ng, const Groups& gs, const int32_t*
                   const std::vector<int32_t>& ent_g, const std::vector<int32_t>& ent_id, const float* retrieval_coef,
                   const float* rating_coefs, float rating_mean, const float* r_in, const float* E, int dim, int32_t* ids_out, float* r_out,
                   const RankDev* dev = nullptr) {
-  const int D = m->D, Vm = medium == 0 ? m->V0 : m->V1, vs = medium == 0 ? 0 : m->V0;
+  const int Vm = medium == 0 ? m->V0 : m->V1;
   hipStream_t s = m->stream;
   const bool score = r_in == nullptr, rerank = ids_out != nullptr || dev != nullptr;
   int64_t npage = 0;
   if (dev) for (int g = 0; g < ng; ++g) npage = std::max<int64_t>(npage, dev->page_off[g] + dev->page_hi[g] - dev->page_lo[g]);
-  // users of each group in user order; per chunk of RETRIEVE_CHUNK users the range of them it holds
-  const int nchunks = score ? (int)((nu + RETRIEVE_CHUNK - 1) / RETRIEVE_CHUNK) : 0;
-  std::vector<int> goff(ng + 1, 0), members((size_t)nu);
-  for (int64_t u = 0; u < nu; ++u) ++goff[ugroup[u] + 1];
-  for (int g = 0; g < ng; ++g) goff[g + 1] += goff[g];
-  {
-    std::vector<int> fill(goff.begin(), goff.end() - 1);
-    for (int64_t u = 0; u < nu; ++u) members[fill[ugroup[u]]++] = (int)u;
-  }
-  std::vector<int2> ranges((size_t)std::max(nchunks, 1) * ng);
-  for (int g = 0; g < ng; ++g) {
-    int t = goff[g];
-    for (int c = 0; c < nchunks; ++c) {
-      const int lo = t;
-      while (t < goff[g + 1] && members[t] < (c + 1) * RETRIEVE_CHUNK) ++t;
-      ranges[(size_t)c * ng + g] = make_int2(lo, t);
-    }
-  }
-  const long long ldz = pad8(std::max(m->V0, m->V1));
+  // users of each group in user order; per chunk of RETRIEVE_CHUNK users the range of them it holds.  Only scoring reads the plan;
+  // rank_request_body has checked the group ids and that no group is empty, in its own words, so group_plan's two checks cannot fail here.
+  GroupPlan gp;
+  if (score) RC(group_plan("rank_request", ugroup.data(), nu, ng, RETRIEVE_CHUNK, gp));
+  const int nchunks = gp.nchunks;
   const int64_t nent = (int64_t)ent_g.size();
-  auto layout = [&](Carve& c, float** qf, T** qt, float** lse, float2** part, float** z, int** d_members, int2** d_ranges, float** d_rm,
-                    int64_t** d_rmoff, RankGroup** d_grp, int32_t** d_cand, int32_t** d_sid, int32_t** d_spos, float** sc, float** G,
-                    unsigned** bits, unsigned** flags, int32_t** d_eg, int32_t** d_eid, int** picks, int32_t** d_plo, int32_t** d_phi,
-                    int64_t** d_poff, int32_t** d_page) {
-    *qf = c.take<float>(score ? (size_t)nu * D : 0);
-    *qt = is_bf16<T>::value ? c.take<T>(score ? (size_t)nu * D : 0) : (T*)*qf;
-    *lse = c.take<float>(score ? nu : 0);
-    *part = c.take<float2>(score ? (size_t)RETRIEVE_CHUNK * RETRIEVE_LSE_SPLIT : 0);
-    *z = c.take<float>(score ? (size_t)std::min<int64_t>(nu, RETRIEVE_CHUNK) * ldz : 0);
-    *d_members = c.take<int>(nu);
-    *d_ranges = c.take<int2>(ranges.size());
-    *d_rm = c.take<float>(score ? n_rm : 0);
-    *d_rmoff = c.take<int64_t>(nu);
-    *d_grp = c.take<RankGroup>(ng);
-    *d_cand = c.take<int32_t>(gs.N);
-    *d_sid = c.take<int32_t>(rerank ? gs.N : 0);
-    *d_spos = c.take<int32_t>(rerank ? gs.N : 0);
-    *sc = c.take<float>(gs.N);
-    *G = c.take<float>(rerank ? gs.gram : 0);
-    *bits = c.take<unsigned>(rerank ? gs.bits : 0);
-    *flags = c.take<unsigned>(rerank ? gs.flags : 0);
-    *d_eg = c.take<int32_t>(nent);
-    *d_eid = c.take<int32_t>(nent);
-    *picks = c.take<int>(rerank ? gs.N : 0);
-    *d_plo = c.take<int32_t>(dev ? ng : 0);
-    *d_phi = c.take<int32_t>(dev ? ng : 0);
-    *d_poff = c.take<int64_t>(dev ? ng : 0);
-    *d_page = c.take<int32_t>(npage);
-  };
-  float *qf, *lse, *z, *d_rm, *sc, *G; T* qt; float2* part; int *d_members, *picks; int2* d_ranges; int64_t* d_rmoff; RankGroup* d_grp;
+  ScoreBufs<T> b(m);
+  float *d_rm, *sc, *G; int *d_members, *picks; int2* d_ranges; int64_t* d_rmoff; RankGroup* d_grp;
   int32_t *d_cand, *d_sid, *d_spos, *d_eg, *d_eid, *d_plo, *d_phi, *d_page; int64_t* d_poff; unsigned *bits, *flags;
-  Carve probe{nullptr};
-  layout(probe, &qf, &qt, &lse, &part, &z, &d_members, &d_ranges, &d_rm, &d_rmoff, &d_grp, &d_cand, &d_sid, &d_spos, &sc, &G, &bits, &flags,
-         &d_eg, &d_eid, &picks, &d_plo, &d_phi, &d_poff, &d_page);
-  RC(ensure_ws(m, probe.off));
-  Carve c{(char*)m->rank->ws};
-  layout(c, &qf, &qt, &lse, &part, &z, &d_members, &d_ranges, &d_rm, &d_rmoff, &d_grp, &d_cand, &d_sid, &d_spos, &sc, &G, &bits, &flags,
-         &d_eg, &d_eid, &picks, &d_plo, &d_phi, &d_poff, &d_page);
+  RC(carve_into(rank_tables(m)->ws, s, [&](Carve& c) {
+    b.take(c, score ? nu : 0);
+    d_members = c.take<int>(nu);
+    d_ranges = c.take<int2>((size_t)std::max(nchunks, 1) * ng);
+    d_rm = c.take<float>(score ? n_rm : 0);
+    d_rmoff = c.take<int64_t>(nu);
+    d_grp = c.take<RankGroup>(ng);
+    d_cand = c.take<int32_t>(gs.N);
+    d_sid = c.take<int32_t>(rerank ? gs.N : 0);
+    d_spos = c.take<int32_t>(rerank ? gs.N : 0);
+    sc = c.take<float>(gs.N);
+    G = c.take<float>(rerank ? gs.gram : 0);
+    bits = c.take<unsigned>(rerank ? gs.bits : 0);
+    flags = c.take<unsigned>(rerank ? gs.flags : 0);
+    d_eg = c.take<int32_t>(nent);
+    d_eid = c.take<int32_t>(nent);
+    picks = c.take<int>(rerank ? gs.N : 0);
+    d_plo = c.take<int32_t>(dev ? ng : 0);
+    d_phi = c.take<int32_t>(dev ? ng : 0);
+    d_poff = c.take<int64_t>(dev ? ng : 0);
+    d_page = c.take<int32_t>(npage);
+  }));
   // (dev: candidates, queries and r_masked are device arrays; same kernels on the same values)
   const hipMemcpyKind in_kind = dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
   if (dev) { cand_ids = dev->d_cand; queries = dev->d_queries; r_masked = dev->d_rm; }
@@ -481,10 +411,9 @@ static int rank_t(Model* m, int medium, int ng, const Groups& gs, const int32_t*
   HIP_CHECK(hipMemcpyAsync(d_grp, gs.g.data(), (size_t)ng * sizeof(RankGroup), hipMemcpyHostToDevice, s));
   HIP_CHECK(hipMemcpyAsync(d_cand, cand_ids, (size_t)gs.N * 4, in_kind, s));
   if (score) {
-    HIP_CHECK(hipMemcpyAsync(qf, queries, (size_t)nu * D * 4, in_kind, s));
-    if constexpr (is_bf16<T>::value) RC(launch_cast<T>(qf, qt, (long long)nu * D, s));
-    HIP_CHECK(hipMemcpyAsync(d_members, members.data(), members.size() * 4, hipMemcpyHostToDevice, s));
-    HIP_CHECK(hipMemcpyAsync(d_ranges, ranges.data(), ranges.size() * sizeof(int2), hipMemcpyHostToDevice, s));
+    RC(score_upload_queries(b, queries, nu, in_kind, s));
+    HIP_CHECK(hipMemcpyAsync(d_members, gp.members.data(), gp.members.size() * 4, hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(d_ranges, gp.ranges.data(), gp.ranges.size() * sizeof(int2), hipMemcpyHostToDevice, s));
     HIP_CHECK(hipMemcpyAsync(d_rm, r_masked, (size_t)n_rm * 4, in_kind, s));
     HIP_CHECK(hipMemcpyAsync(d_rmoff, rm_off.data(), (size_t)nu * 8, hipMemcpyHostToDevice, s));
   } else {
@@ -511,17 +440,17 @@ static int rank_t(Model* m, int medium, int ng, const Groups& gs, const int32_t*
   }
   toc(m);
   if (score) {
-    if (m->table_dirty) { RC(table_forward<T>(m)); m->table_dirty = false; }
-    const T* Fm = AT<T>(m->FT) + (int64_t)vs * D;
+    const T* Fm;
+    RC(score_table_ready<T>(m, medium, &Fm));
     const float coef = retrieval_coef ? *retrieval_coef : 1.f;
     const float logc = logf(coef);
     const int have_rc = rating_coefs != nullptr;
     const float c0m = have_rc ? rating_coefs[0] * rating_mean : 0.f, c1 = have_rc ? rating_coefs[1] : 0.f;
     for (int ch = 0; ch < nchunks; ++ch) {
       const int q0 = ch * RETRIEVE_CHUNK, nc = (int)std::min<int64_t>(RETRIEVE_CHUNK, nu - q0);
-      RC(retrieve_chunk_scores<T>(m, qt + (size_t)q0 * D, nc, q0, Fm, Vm, z, ldz, part, lse));
+      RC(retrieve_chunk_scores<T>(m, b.qt + (size_t)q0 * b.D, nc, q0, Fm, Vm, b.z, b.ldz, b.part, b.lse));
       tic(m, "rank_score");
-      rank_score_kernel<<<dim3(RK_MAXN / RK_THREADS, ng), RK_THREADS, 0, s>>>(d_grp, d_cand, z, ldz, lse, d_members, d_ranges + (size_t)ch * ng,
+      rank_score_kernel<<<dim3(RK_MAXN / RK_THREADS, ng), RK_THREADS, 0, s>>>(d_grp, d_cand, b.z, b.ldz, b.lse, d_members, d_ranges + (size_t)ch * ng,
                                                                              q0, d_rm, d_rmoff, coef, logc, have_rc, c0m, c1, ch == 0, sc);
       RK_LAUNCH_CHECK();
       toc(m);
@@ -598,22 +527,16 @@ static int rank_request_body(Model* m, int medium, int32_t ng, const int64_t* ca
   }
   for (int g = 0; g < ng; ++g) ARG_CHECK(members[g] > 0, "rank_request: every group needs at least one user");
   if (score) ARG_CHECK(n_rm == need, "rank_request: r_masked must hold n_g values per user of group g (n_r_masked = their sum)");
-  ARG_CHECK((hist_off == nullptr) == (hist_medium == nullptr) && (hist_off == nullptr) == (hist_ids == nullptr) &&
-                (hist_off == nullptr) == (hist_status == nullptr),
-            "rank_request: the history arrays are all given or all NULL");
+  RC(check_ragged("rank_request", LIST_HISTORY, hist_off, nu, {hist_medium, hist_ids, hist_status}));
+  RC(check_list_items("rank_request", LIST_HISTORY, hist_off, nu, hist_medium, hist_ids, V));
   // related flags: every list entry of medium m whose status is not deleted / planned (render.jl:395-408 walks the whole list, not the
   // last status per item), one entry per distinct (group, id)
   std::vector<int32_t> ent_g, ent_id;
   if (hist_off) {
-    ARG_CHECK(hist_off[0] == 0, "rank_request: hist_offsets[0] must be 0");
-    for (int64_t u = 0; u < nu; ++u) ARG_CHECK(hist_off[u + 1] >= hist_off[u], "rank_request: hist_offsets must be non-decreasing");
     std::vector<std::pair<int32_t, int32_t>> ent;
     for (int64_t u = 0; u < nu; ++u)
-      for (int64_t j = hist_off[u]; j < hist_off[u + 1]; ++j) {
-        ARG_CHECK(hist_medium[j] == 0 || hist_medium[j] == 1, "rank_request: list items' media must be 0 or 1");
-        ARG_CHECK(hist_ids[j] >= 0 && hist_ids[j] < V[hist_medium[j]], "rank_request: list ids must be in [0, V) of their medium");
+      for (int64_t j = hist_off[u]; j < hist_off[u + 1]; ++j)
         if (hist_medium[j] == medium && hist_status[j] != ST_DELETED && hist_status[j] != ST_PLANNED) ent.emplace_back(ugroup[u], hist_ids[j]);
-      }
     std::sort(ent.begin(), ent.end());
     ent.erase(std::unique(ent.begin(), ent.end()), ent.end());
     for (const auto& e : ent) { ent_g.push_back(e.first); ent_id.push_back(e.second); }
@@ -661,18 +584,13 @@ int model_rank_gram(Model* m, int medium, int32_t ng, const int64_t* cand_off, c
   const float* E = retrieve_similarity_table(m, medium, &dim);
   ARG_CHECK(E != nullptr, "rank_gram: the item-similarity embeddings of the medium are not loaded");
   HIP_CHECK(hipSetDevice(m->device));
-  Carve probe{nullptr};
-  auto layout = [&](Carve& c, RankGroup** d_grp, int32_t** d_cand, float** G) {
-    *d_grp = c.take<RankGroup>(ng);
-    *d_cand = c.take<int32_t>(gs.N);
-    *G = c.take<float>(gs.gram);
-  };
-  RankGroup* d_grp; int32_t* d_cand; float* G;
-  layout(probe, &d_grp, &d_cand, &G);
-  RC(ensure_ws(m, probe.off));
-  Carve c{(char*)m->rank->ws};
-  layout(c, &d_grp, &d_cand, &G);
   hipStream_t s = m->stream;
+  RankGroup* d_grp; int32_t* d_cand; float* G;
+  RC(carve_into(rank_tables(m)->ws, s, [&](Carve& c) {
+    d_grp = c.take<RankGroup>(ng);
+    d_cand = c.take<int32_t>(gs.N);
+    G = c.take<float>(gs.gram);
+  }));
   HIP_CHECK(hipMemcpyAsync(d_grp, gs.g.data(), (size_t)ng * sizeof(RankGroup), hipMemcpyHostToDevice, s));
   HIP_CHECK(hipMemcpyAsync(d_cand, cand_ids, (size_t)gs.N * 4, hipMemcpyHostToDevice, s));
   RC(launch_gram(m, gs, d_grp, d_cand, E, (int)dim, G));

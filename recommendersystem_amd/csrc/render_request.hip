@@ -17,7 +17,6 @@
 #include <cstring>
 #include <map>
 
-#include "encoder_handle.hpp"
 #include "model_internal.hpp"
 
 namespace rsys {
@@ -189,11 +188,8 @@ int model_render_request(Model* m, int32_t ng, const int32_t* group_medium, cons
   ARG_CHECK(group_medium && offset && limit && penalties && group && rb && retrieval_token && pb && user_desc && user_ts && ids_out &&
                 ids_offsets && total_out,
             "render_request: null argument");
-  ARG_CHECK((hist_off == nullptr) == (hist_medium == nullptr) && (hist_off == nullptr) == (hist_ids == nullptr) &&
-                (hist_off == nullptr) == (hist_status == nullptr),
-            "render_request: the history arrays are all given or all NULL");
-  ARG_CHECK((sel_off == nullptr) == (sel_medium == nullptr) && (sel_off == nullptr) == (sel_ids == nullptr),
-            "render_request: the selected-item arrays are all given or all NULL");
+  RC(check_ragged("render_request", LIST_HISTORY, hist_off, nu, {hist_medium, hist_ids, hist_status}));
+  RC(check_ragged("render_request", LIST_SELECTED, sel_off, ng, {sel_medium, sel_ids}));
   ARG_CHECK(coef_have == nullptr || coefs != nullptr, "render_request: coef_have needs coefs");
   int64_t need_ids = 0;
   for (int g = 0; g < ng; ++g) {
@@ -209,14 +205,6 @@ int model_render_request(Model* m, int32_t ng, const int32_t* group_medium, cons
     ++members[group[u]];
   }
   for (int g = 0; g < ng; ++g) ARG_CHECK(members[g] > 0, "render_request: every group needs at least one user");
-  if (hist_off) {
-    ARG_CHECK(hist_off[0] == 0, "render_request: hist_offsets[0] must be 0");
-    for (int64_t u = 0; u < nu; ++u) ARG_CHECK(hist_off[u + 1] >= hist_off[u], "render_request: hist_offsets must be non-decreasing");
-  }
-  if (sel_off) {
-    ARG_CHECK(sel_off[0] == 0, "render_request: sel_offsets[0] must be 0");
-    for (int g = 0; g < ng; ++g) ARG_CHECK(sel_off[g + 1] >= sel_off[g], "render_request: sel_offsets must be non-decreasing");
-  }
   if (slots) {
     int32_t mask = 0;
     RC(adapter_slots(m, &mask));
@@ -268,7 +256,7 @@ int model_render_request(Model* m, int32_t ng, const int32_t* group_medium, cons
   hipStream_t s = m->stream;
   float *Q, *Qs, *pred, *rm; int *d_sel, *d_order; int32_t* cand; RowDesc* d_rows; Win* d_win; Prefix pf; double* pf_time;
   int *pf_i[7]; float *pf_f[2];
-  auto layout = [&](Carve& c) {
+  RC(carve_into(R->ws, s, [&](Carve& c) {
     Q = c.take<float>((size_t)nu * D); Qs = c.take<float>((size_t)nu * D);
     pred = c.take<float>(sel_cap); rm = c.take<float>((size_t)nu * RN_MAX_RANK);
     d_sel = c.take<int>(sel_cap); d_order = c.take<int>(nu);
@@ -277,12 +265,7 @@ int model_render_request(Model* m, int32_t ng, const int32_t* group_medium, cons
     pf_time = c.take<double>(n_prefix);
     for (int k = 0; k < 7; ++k) pf_i[k] = c.take<int>(n_prefix);
     for (int k = 0; k < 2; ++k) pf_f[k] = c.take<float>(n_prefix);
-  };
-  Carve probe{nullptr};
-  layout(probe);
-  if (int rc = R->ws.reserve(probe.off, s)) return rc;
-  Carve cv{(char*)R->ws.p};
-  layout(cv);
+  }));
   pf.time = pf_time; pf.userid = pf_i[0]; pf.tmid = pf_i[1]; pf.gender = pf_i[2]; pf.source = pf_i[3]; pf.matchedid = pf_i[4];
   pf.status = pf_i[5]; pf.rope = pf_i[6]; pf.rating = pf_f[0]; pf.progress = pf_f[1];
 

@@ -12,6 +12,8 @@
 //              exclusive prefix of per-workgroup counts over workgroup order (no atomics: independent of scheduling)
 //   sort       bitonic sort of <= 8192 (key, id) pairs per group in LDS: descending key, then ascending id; -1 / -inf padding
 // Every launch covers all groups (grid = blocks x groups); the host waits once, after the copy out.
+#include <cmath>
+
 #include "model_internal.hpp"
 
 namespace rsys {
@@ -343,17 +345,13 @@ int topk_select(const unsigned* keys, long long ldk, int rows, int V, int k, con
   return RSYS_OK;
 }
 
-// bump allocation inside one device buffer (256-byte aligned pieces)
-struct Carve {
-  char* p; size_t off = 0;
-  template <typename X> X* take(size_t count) {
-    X* r = (X*)(p ? p + off : nullptr);
-    off += (count * sizeof(X) + 255) / 256 * 256;
-    return r;
-  }
-};
-
 }  // namespace
+
+int launch_scatter_nan(float* sc, const long long* pos, long long n, hipStream_t s) {
+  scatter_nan_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(sc, pos, n);
+  RT_LAUNCH_CHECK();
+  return RSYS_OK;
+}
 
 static_assert(RT_CHUNK == RETRIEVE_CHUNK && RT_LSE_SPLIT == RETRIEVE_LSE_SPLIT, "retrieval chunk constants");
 
@@ -377,127 +375,149 @@ int retrieve_chunk_scores(Model* m, const T* qt, int nc, int q0, const T* Fm, in
 template int retrieve_chunk_scores<float>(Model*, const float*, int, int, const float*, int, float*, long long, float2*, float*);
 template int retrieve_chunk_scores<bf16>(Model*, const bf16*, int, int, const bf16*, int, float*, long long, float2*, float*);
 
-// the retrieval workspace of a model: one device buffer, grown on demand, freed with the model
-struct RetrieveWs {
-  void* buf = nullptr;
-  size_t bytes = 0;
-};
+template <typename T>
+int score_upload_queries(const ScoreBufs<T>& b, const float* queries, int64_t nq, hipMemcpyKind kind, hipStream_t s) {
+  HIP_CHECK(hipMemcpyAsync(b.qf, queries, (size_t)nq * b.D * 4, kind, s));
+  if constexpr (is_bf16<T>::value) RC(launch_cast<T>(b.qf, b.qt, (long long)nq * b.D, s));
+  return RSYS_OK;
+}
+template int score_upload_queries<float>(const ScoreBufs<float>&, const float*, int64_t, hipMemcpyKind, hipStream_t);
+template int score_upload_queries<bf16>(const ScoreBufs<bf16>&, const float*, int64_t, hipMemcpyKind, hipStream_t);
 
-void retrieve_free(Model* m) {
-  if (!m->rws) return;
-  if (m->rws->buf) hipFree(m->rws->buf);
-  delete m->rws;
-  m->rws = nullptr;
+template <typename T>
+int score_table_ready(Model* m, int medium, const T** Fm) {
+  if (m->table_dirty) { RC(table_forward<T>(m)); m->table_dirty = false; }
+  *Fm = AT<T>(m->FT) + (int64_t)(medium == 0 ? 0 : m->V0) * m->D;
+  return RSYS_OK;
+}
+template int score_table_ready<float>(Model*, int, const float**);
+template int score_table_ready<bf16>(Model*, int, const bf16**);
+
+int group_plan(const char* who, const int32_t* group, int64_t nq, int ng, int chunk, GroupPlan& gp) {
+  gp.goff.assign((size_t)ng + 1, 0);
+  for (int64_t q = 0; q < nq; ++q) {
+    const int g = group ? group[q] : (int)q;
+    ARG_CHECK(g >= 0 && g < ng, std::string(who) + ": group ids must be in [0, n_groups)");
+    ++gp.goff[g + 1];
+  }
+  for (int g = 0; g < ng; ++g) {
+    ARG_CHECK(gp.goff[g + 1] > 0, std::string(who) + ": every group needs at least one query");
+    gp.goff[g + 1] += gp.goff[g];
+  }
+  gp.members.resize((size_t)nq);
+  std::vector<int> fill(gp.goff.begin(), gp.goff.end() - 1);
+  for (int64_t q = 0; q < nq; ++q) gp.members[fill[group ? group[q] : (int)q]++] = (int)q;
+  gp.nchunks = (int)((nq + chunk - 1) / chunk);
+  gp.ranges.resize((size_t)gp.nchunks * ng);
+  for (int g = 0; g < ng; ++g) {
+    int t = gp.goff[g];
+    for (int c = 0; c < gp.nchunks; ++c) {
+      const int lo = t;
+      while (t < gp.goff[g + 1] && gp.members[t] < (c + 1) * chunk) ++t;
+      gp.ranges[(size_t)c * ng + g] = make_int2(lo, t);
+    }
+  }
+  return RSYS_OK;
+}
+
+int check_ragged(const char* who, const ListKind& what, const int64_t* off, int64_t n, std::initializer_list<const void*> arrays) {
+  for (const void* a : arrays) ARG_CHECK((off == nullptr) == (a == nullptr), std::string(who) + ": " + what.given);
+  if (!off) return RSYS_OK;
+  ARG_CHECK(off[0] == 0, std::string(who) + ": " + what.offsets + "[0] must be 0");
+  for (int64_t i = 0; i < n; ++i) ARG_CHECK(off[i + 1] >= off[i], std::string(who) + ": " + what.offsets + " must be non-decreasing");
+  return RSYS_OK;
+}
+
+int check_list_items(const char* who, const ListKind& what, const int64_t* off, int64_t n, const int32_t* medium, const int32_t* ids,
+                     const int V[2]) {
+  if (!off) return RSYS_OK;
+  for (int64_t j = 0; j < off[n]; ++j) {
+    if (medium) ARG_CHECK(medium[j] == 0 || medium[j] == 1, std::string(who) + ": " + what.media);
+    ARG_CHECK(ids[j] >= 0 && ids[j] < V[medium ? medium[j] : 0], std::string(who) + ": " + what.ids);
+  }
+  return RSYS_OK;
+}
+
+int csc_nonzero_pattern(const char* who, const char* rows, int64_t n_rows, int64_t n_cols, const int64_t* colptr, const int32_t* rowval,
+                        const float* nzval, std::vector<int64_t>& cp, std::vector<int32_t>& rv) {
+  const std::string w = std::string(who) + ": ";
+  ARG_CHECK(colptr[0] == 0, w + "colptr[0] must be 0");
+  for (int64_t c = 0; c < n_cols; ++c) ARG_CHECK(colptr[c + 1] >= colptr[c], w + "colptr must be non-decreasing");
+  cp.assign((size_t)n_cols + 1, 0);
+  rv.reserve((size_t)colptr[n_cols]);
+  for (int64_t c = 0; c < n_cols; ++c) {
+    for (int64_t j = colptr[c]; j < colptr[c + 1]; ++j) {
+      ARG_CHECK(rowval[j] >= 0 && rowval[j] < n_rows, w + "row indices must be in " + rows);
+      ARG_CHECK(std::isfinite(nzval[j]) && nzval[j] >= 0.f, w + "stored values must be finite and >= 0");
+      if (nzval[j] != 0.f) rv.push_back(rowval[j]);   // (explicitly stored zeros reach nothing: render.jl tests related_vals[k] != 0)
+    }
+    cp[(size_t)c + 1] = (int64_t)rv.size();
+  }
+  return RSYS_OK;
 }
 
 template <typename T>
 static int retrieve_t(Model* m, int medium, const float* queries, int64_t nq, const int32_t* group, int ng, const float* prior,
                       const int64_t* excl_off, const int32_t* excl_ids, const RetrieveInit* init, int k, int32_t* ids_out, float* scores_out,
                       int32_t* counts_out, RetrieveDev* dev = nullptr) {
-  const int D = m->D, Vm = medium == 0 ? m->V0 : m->V1, vs = medium == 0 ? 0 : m->V0;
+  const int Vm = medium == 0 ? m->V0 : m->V1;
   hipStream_t s = m->stream;
   // host-side index arrays: the queries of each group in query order, per chunk the range of them it holds, exclusion positions
-  std::vector<int> gcount(ng, 0);
-  for (int64_t q = 0; q < nq; ++q) {
-    const int g = group ? group[q] : (int)q;
-    ARG_CHECK(g >= 0 && g < ng, "retrieve_topk: group ids must be in [0, n_groups)");
-    ++gcount[g];
-  }
-  for (int g = 0; g < ng; ++g) ARG_CHECK(gcount[g] > 0, "retrieve_topk: every group needs at least one query");
-  std::vector<int> goff(ng + 1, 0);
-  for (int g = 0; g < ng; ++g) goff[g + 1] = goff[g] + gcount[g];
-  std::vector<int> members(nq), fill(goff.begin(), goff.end() - 1);
-  for (int64_t q = 0; q < nq; ++q) members[fill[group ? group[q] : (int)q]++] = (int)q;
-  const int nchunks = (int)((nq + RT_CHUNK - 1) / RT_CHUNK);
-  std::vector<int2> ranges((size_t)nchunks * ng);
-  for (int g = 0; g < ng; ++g) {
-    int t = goff[g];
-    for (int c = 0; c < nchunks; ++c) {
-      const int lo = t;
-      while (t < goff[g + 1] && members[t] < (c + 1) * RT_CHUNK) ++t;
-      ranges[(size_t)c * ng + g] = make_int2(lo, t);
-    }
-  }
+  GroupPlan gp;
+  RC(group_plan("retrieve_topk", group, nq, ng, RT_CHUNK, gp));
+  RC(check_ragged("retrieve_topk", LIST_EXCLUDED, excl_off, ng, {excl_ids}));
+  RC(check_list_items("retrieve_topk", LIST_EXCLUDED, excl_off, ng, nullptr, excl_ids, &Vm));
   std::vector<long long> xpos;
-  if (excl_off) {
-    ARG_CHECK(excl_off[0] == 0, "retrieve_topk: excl_offsets[0] must be 0");
-    for (int g = 0; g < ng; ++g) {
-      ARG_CHECK(excl_off[g + 1] >= excl_off[g], "retrieve_topk: excl_offsets must be non-decreasing");
-      for (int64_t j = excl_off[g]; j < excl_off[g + 1]; ++j) {
-        ARG_CHECK(excl_ids[j] >= 0 && excl_ids[j] < Vm, "retrieve_topk: exclusion ids must be medium-local, in [0, V_m)");
-        xpos.push_back((long long)g * Vm + excl_ids[j]);
-      }
-    }
-  }
+  if (excl_off)
+    for (int g = 0; g < ng; ++g)
+      for (int64_t j = excl_off[g]; j < excl_off[g + 1]; ++j) xpos.push_back((long long)g * Vm + excl_ids[j]);
   HIP_CHECK(hipSetDevice(m->device));
-  if (m->table_dirty) { RC(table_forward<T>(m)); m->table_dirty = false; }
+  const T* Fm;
+  RC(score_table_ready<T>(m, medium, &Fm));
   // workspace: queries (f32 + compute type), lse, partials, the per-chunk score slab (the candidate lists reuse it after the last
   // chunk), the group scores / keys, the selection state, the outputs, the index arrays
-  const int Vmax = std::max(m->V0, m->V1);
-  const long long ldz = pad8(Vmax);
   const int nb = (Vm + RT_ITEMS - 1) / RT_ITEMS;
-  const size_t slab = std::max<size_t>((size_t)RT_CHUNK * (size_t)ldz * 4, (size_t)ng * (size_t)k * 8);
-  auto layout = [&](Carve& c, float** qf, T** qt, float** lse, float2** part, float** z, float** sc, SelBufs* sb, int** d_ids,
-                    float** d_vals, int** d_counts, int** d_members, int2** d_ranges, long long** d_xpos) {
-    *qf = c.take<float>((size_t)nq * D);
-    *qt = is_bf16<T>::value ? c.take<T>((size_t)nq * D) : (T*)*qf;
-    *lse = c.take<float>(nq);
-    *part = c.take<float2>((size_t)RT_CHUNK * RT_LSE_SPLIT);
-    *z = (float*)c.take<char>(slab);
-    *sc = c.take<float>((size_t)ng * Vm);
-    sb->hist = c.take<unsigned>((size_t)ng * 256);
-    sb->st = c.take<SelState>(ng);
-    sb->cnt = c.take<int2>((size_t)ng * nb);
-    *d_ids = c.take<int>((size_t)ng * k);
-    *d_vals = c.take<float>((size_t)ng * k);
-    *d_counts = c.take<int>(ng);
-    *d_members = c.take<int>(nq);
-    *d_ranges = c.take<int2>(ranges.size());
-    *d_xpos = c.take<long long>(std::max<size_t>(1, xpos.size()));
-  };
-  float *qf, *lse, *z, *sc, *d_vals; T* qt; float2* part; SelBufs sb; int *d_ids, *d_counts, *d_members; int2* d_ranges; long long* d_xpos;
-  Carve probe{nullptr};
-  layout(probe, &qf, &qt, &lse, &part, &z, &sc, &sb, &d_ids, &d_vals, &d_counts, &d_members, &d_ranges, &d_xpos);
-  if (!m->rws) m->rws = new RetrieveWs();
-  RetrieveWs* ws = m->rws;
-  if (ws->bytes < probe.off) {
-    HIP_CHECK(hipStreamSynchronize(s));
-    if (ws->buf) HIP_CHECK(hipFree(ws->buf));
-    ws->buf = nullptr; ws->bytes = 0;
-    HIP_CHECK(hipMalloc(&ws->buf, probe.off));
-    ws->bytes = probe.off;
-  }
-  Carve c{(char*)ws->buf};
-  layout(c, &qf, &qt, &lse, &part, &z, &sc, &sb, &d_ids, &d_vals, &d_counts, &d_members, &d_ranges, &d_xpos);
-  sb.cand = (unsigned long long*)z; sb.ldc = k;
+  ScoreBufs<T> b(m);
+  const size_t slab = std::max<size_t>((size_t)RT_CHUNK * (size_t)b.ldz * 4, (size_t)ng * (size_t)k * 8);
+  float *sc, *d_vals; SelBufs sb; int *d_ids, *d_counts, *d_members; int2* d_ranges; long long* d_xpos;
+  RC(carve_into(m->rws, s, [&](Carve& c) {
+    b.take(c, nq, slab);
+    sc = c.take<float>((size_t)ng * Vm);
+    sb.hist = c.take<unsigned>((size_t)ng * 256);
+    sb.st = c.take<SelState>(ng);
+    sb.cnt = c.take<int2>((size_t)ng * nb);
+    d_ids = c.take<int>((size_t)ng * k);
+    d_vals = c.take<float>((size_t)ng * k);
+    d_counts = c.take<int>(ng);
+    d_members = c.take<int>(nq);
+    d_ranges = c.take<int2>(gp.ranges.size());
+    d_xpos = c.take<long long>(xpos.size());
+  }));
+  sb.cand = (unsigned long long*)b.z; sb.ldc = k;
 
   tic(m, "retrieve_prep");
   // (dev: the queries are on the device already and the result stays there; the arithmetic below is the same)
-  if (dev) HIP_CHECK(hipMemcpyAsync(qf, dev->d_queries, (size_t)nq * D * 4, hipMemcpyDeviceToDevice, s));
-  else HIP_CHECK(hipMemcpyAsync(qf, queries, (size_t)nq * D * 4, hipMemcpyHostToDevice, s));
-  if constexpr (is_bf16<T>::value) RC(launch_cast<T>(qf, qt, (long long)nq * D, s));
-  HIP_CHECK(hipMemcpyAsync(d_members, members.data(), members.size() * 4, hipMemcpyHostToDevice, s));
-  HIP_CHECK(hipMemcpyAsync(d_ranges, ranges.data(), ranges.size() * sizeof(int2), hipMemcpyHostToDevice, s));
+  RC(score_upload_queries(b, dev ? dev->d_queries : queries, nq, dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
+  HIP_CHECK(hipMemcpyAsync(d_members, gp.members.data(), gp.members.size() * 4, hipMemcpyHostToDevice, s));
+  HIP_CHECK(hipMemcpyAsync(d_ranges, gp.ranges.data(), gp.ranges.size() * sizeof(int2), hipMemcpyHostToDevice, s));
   if (init) RC((*init)(sc, s));   // the device-side initialiser of the group score rows (rsys_retrieve_request)
   else if (prior) HIP_CHECK(hipMemcpyAsync(sc, prior, (size_t)ng * Vm * 4, hipMemcpyHostToDevice, s));
   else HIP_CHECK(hipMemsetAsync(sc, 0, (size_t)ng * Vm * 4, s));
   if (!xpos.empty()) {
     HIP_CHECK(hipMemcpyAsync(d_xpos, xpos.data(), xpos.size() * 8, hipMemcpyHostToDevice, s));
-    scatter_nan_kernel<<<(unsigned)((xpos.size() + 255) / 256), 256, 0, s>>>(sc, d_xpos, (long long)xpos.size());
-    RT_LAUNCH_CHECK();
+    RC(launch_scatter_nan(sc, d_xpos, (long long)xpos.size(), s));
   }
   HIP_CHECK(hipMemsetAsync(sb.hist, 0, (size_t)ng * 256 * 4, s));
   toc(m);
-  const T* Fm = AT<T>(m->FT) + (int64_t)vs * D;
-  for (int ch = 0; ch < nchunks; ++ch) {
+  for (int ch = 0; ch < gp.nchunks; ++ch) {
     const int q0 = ch * RT_CHUNK, nc = (int)std::min<int64_t>(RT_CHUNK, nq - q0);
-    RC(retrieve_chunk_scores<T>(m, qt + (size_t)q0 * D, nc, q0, Fm, Vm, z, ldz, part, lse));
+    RC(retrieve_chunk_scores<T>(m, b.qt + (size_t)q0 * b.D, nc, q0, Fm, Vm, b.z, b.ldz, b.part, b.lse));
     tic(m, "retrieve_combine");
     const dim3 grid(nb, ng);
-    if (ch + 1 < nchunks)
-      combine_kernel<false><<<grid, RT_THREADS, 0, s>>>(sc, Vm, sc, Vm, z, ldz, lse, d_members, d_ranges + (size_t)ch * ng, q0, Vm, sb.hist);
+    if (ch + 1 < gp.nchunks)
+      combine_kernel<false><<<grid, RT_THREADS, 0, s>>>(sc, Vm, sc, Vm, b.z, b.ldz, b.lse, d_members, d_ranges + (size_t)ch * ng, q0, Vm, sb.hist);
     else
-      combine_kernel<true><<<grid, RT_THREADS, 0, s>>>(sc, Vm, sc, Vm, z, ldz, lse, d_members, d_ranges + (size_t)ch * ng, q0, Vm, sb.hist);
+      combine_kernel<true><<<grid, RT_THREADS, 0, s>>>(sc, Vm, sc, Vm, b.z, b.ldz, b.lse, d_members, d_ranges + (size_t)ch * ng, q0, Vm, sb.hist);
     RT_LAUNCH_CHECK();
     toc(m);
   }
@@ -523,7 +543,6 @@ int model_retrieve_topk(Model* m, int medium, const float* queries, int64_t nq, 
   ARG_CHECK(nq >= 1 && nq <= RT_MAXQ, "retrieve_topk: 1 <= n_queries <= 4096");
   ARG_CHECK(ng >= 1 && ng <= nq, "retrieve_topk: 1 <= n_groups <= n_queries (every group needs a query)");
   ARG_CHECK(group != nullptr || ng == nq, "retrieve_topk: without `group`, n_groups must equal n_queries");
-  ARG_CHECK((excl_off == nullptr) == (excl_ids == nullptr), "retrieve_topk: excl_offsets and excl_ids are both given or both NULL");
   const int Vm = medium == 0 ? m->V0 : m->V1;
   ARG_CHECK(k >= 1 && k <= std::min(Vm, RT_MAXK), "retrieve_topk: 1 <= k <= min(V_m, 8192)");
   return m->bf16_mode ? retrieve_t<bf16>(m, medium, queries, nq, group, ng, prior, excl_off, excl_ids, nullptr, k, ids_out, scores_out, counts_out)

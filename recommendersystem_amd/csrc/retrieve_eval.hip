@@ -72,94 +72,45 @@ __global__ void target_logp_kernel(const float* z, long long ldz, int nc, const 
   logp[q] = z[row * ldz + targets[q]] - lse[q];
 }
 
-__global__ void eval_scatter_nan_kernel(float* z, const long long* pos, long long n) {
-  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) z[pos[i]] = __int_as_float(0x7fc00000);
-}
-
-struct Carve {
-  char* p; size_t off = 0;
-  template <typename X> X* take(size_t count) {
-    X* r = (X*)(p ? p + off : nullptr);
-    off += (std::max<size_t>(count, 1) * sizeof(X) + 255) / 256 * 256;
-    return r;
-  }
-};
-
 }  // namespace
-
-// rsys_retrieve_target_rank's workspace: one device buffer, grown on demand, freed with the model
-struct EvalWs {
-  void* buf = nullptr;
-  size_t bytes = 0;
-};
-
-void retrieve_eval_free(Model* m) {
-  if (!m->ews) return;
-  if (m->ews->buf) hipFree(m->ews->buf);
-  delete m->ews;
-  m->ews = nullptr;
-}
 
 template <typename T>
 static int target_rank_t(Model* m, int medium, const float* queries, int64_t nq, const int32_t* targets, const std::vector<long long>& xpos,
                          const std::vector<long long>& xcoff, int32_t* rank_out, float* logp_out) {
-  const int D = m->D, Vm = medium == 0 ? m->V0 : m->V1, vs = medium == 0 ? 0 : m->V0;
+  const int Vm = medium == 0 ? m->V0 : m->V1;
   hipStream_t s = m->stream;
-  const long long ldz = pad8(std::max(m->V0, m->V1));   // (the slab stride of rsys_retrieve_topk: the same GEMM launch)
   const int nchunks = (int)((nq + RETRIEVE_CHUNK - 1) / RETRIEVE_CHUNK);
-  auto layout = [&](Carve& c, float** qf, T** qt, float** lse, float2** part, float** z, int** d_tgt, int** d_rank, float** d_logp,
-                    long long** d_xpos) {
-    *qf = c.take<float>((size_t)nq * D);
-    *qt = is_bf16<T>::value ? c.take<T>((size_t)nq * D) : (T*)*qf;
-    *lse = c.take<float>(nq);
-    *part = c.take<float2>((size_t)RETRIEVE_CHUNK * RETRIEVE_LSE_SPLIT);
-    *z = c.take<float>((size_t)std::min<int64_t>(nq, RETRIEVE_CHUNK) * ldz);
-    *d_tgt = c.take<int>(nq);
-    *d_rank = c.take<int>(nq);
-    *d_logp = c.take<float>(nq);
-    *d_xpos = c.take<long long>(xpos.size());
-  };
-  float *qf, *lse, *z, *d_logp; T* qt; float2* part; int *d_tgt, *d_rank; long long* d_xpos;
-  Carve probe{nullptr};
-  layout(probe, &qf, &qt, &lse, &part, &z, &d_tgt, &d_rank, &d_logp, &d_xpos);
+  ScoreBufs<T> b(m);   // (the slab stride of rsys_retrieve_topk: the same GEMM launch)
+  int *d_tgt, *d_rank; float* d_logp; long long* d_xpos;
   HIP_CHECK(hipSetDevice(m->device));
-  if (!m->ews) m->ews = new EvalWs();
-  EvalWs* ws = m->ews;
-  if (ws->bytes < probe.off) {
-    HIP_CHECK(hipStreamSynchronize(s));
-    if (ws->buf) HIP_CHECK(hipFree(ws->buf));
-    ws->buf = nullptr; ws->bytes = 0;
-    HIP_CHECK(hipMalloc(&ws->buf, probe.off));
-    ws->bytes = probe.off;
-  }
-  Carve c{(char*)ws->buf};
-  layout(c, &qf, &qt, &lse, &part, &z, &d_tgt, &d_rank, &d_logp, &d_xpos);
-  if (m->table_dirty) { RC(table_forward<T>(m)); m->table_dirty = false; }
+  RC(carve_into(m->ews, s, [&](Carve& c) {
+    b.take(c, nq);
+    d_tgt = c.take<int>(nq);
+    d_rank = c.take<int>(nq);
+    d_logp = c.take<float>(nq);
+    d_xpos = c.take<long long>(xpos.size());
+  }));
+  const T* Fm;
+  RC(score_table_ready<T>(m, medium, &Fm));
 
   tic(m, "eval_prep");
-  HIP_CHECK(hipMemcpyAsync(qf, queries, (size_t)nq * D * 4, hipMemcpyHostToDevice, s));
-  if constexpr (is_bf16<T>::value) RC(launch_cast<T>(qf, qt, (long long)nq * D, s));
+  RC(score_upload_queries(b, queries, nq, hipMemcpyHostToDevice, s));
   HIP_CHECK(hipMemcpyAsync(d_tgt, targets, (size_t)nq * 4, hipMemcpyHostToDevice, s));
   if (!xpos.empty()) HIP_CHECK(hipMemcpyAsync(d_xpos, xpos.data(), xpos.size() * 8, hipMemcpyHostToDevice, s));
   HIP_CHECK(hipMemsetAsync(d_rank, 0, (size_t)nq * 4, s));
   toc(m);
-  const T* Fm = AT<T>(m->FT) + (int64_t)vs * D;
   const int nb = (Vm + RE_ITEMS - 1) / RE_ITEMS;
   for (int ch = 0; ch < nchunks; ++ch) {
     const int q0 = ch * RETRIEVE_CHUNK, nc = (int)std::min<int64_t>(RETRIEVE_CHUNK, nq - q0);
-    RC(retrieve_chunk_scores<T>(m, qt + (size_t)q0 * D, nc, q0, Fm, Vm, z, ldz, part, lse));
+    RC(retrieve_chunk_scores<T>(m, b.qt + (size_t)q0 * b.D, nc, q0, Fm, Vm, b.z, b.ldz, b.part, b.lse));
     tic(m, "eval_logp");
-    target_logp_kernel<<<(nc + 255) / 256, 256, 0, s>>>(z, ldz, nc, lse, d_tgt, q0, d_logp);
+    target_logp_kernel<<<(nc + 255) / 256, 256, 0, s>>>(b.z, b.ldz, nc, b.lse, d_tgt, q0, d_logp);
     HIP_CHECK(hipGetLastError());
     const long long nx = xcoff[ch + 1] - xcoff[ch];
-    if (nx) {
-      eval_scatter_nan_kernel<<<(unsigned)((nx + 255) / 256), 256, 0, s>>>(z, d_xpos + xcoff[ch], nx);
-      HIP_CHECK(hipGetLastError());
-    }
+    if (nx) RC(launch_scatter_nan(b.z, d_xpos + xcoff[ch], nx, s));
     toc(m);
     tic(m, "eval_count");
-    target_count_kernel<true, true><<<dim3(nb, nc), RE_THREADS, 0, s>>>(z, ldz, Vm, lse, d_tgt, q0, d_rank);
+    target_count_kernel<true, true><<<dim3(nb, nc), RE_THREADS, 0, s>>>(b.z, b.ldz, Vm, b.lse, d_tgt, q0, d_rank);
     HIP_CHECK(hipGetLastError());
     toc(m);
   }
@@ -175,24 +126,19 @@ int model_retrieve_target_rank(Model* m, int medium, const float* queries, int64
   ARG_CHECK(!m->sharded, "retrieve_target_rank: the row-sharded item table is not supported (replicated table only)");
   ARG_CHECK(queries && targets && rank_out && logp_out, "retrieve_target_rank: null buffer");
   ARG_CHECK(nq >= 1 && nq <= RE_MAXQ, "retrieve_target_rank: 1 <= n_queries <= 4096");
-  ARG_CHECK((excl_off == nullptr) == (excl_ids == nullptr), "retrieve_target_rank: excl_offsets and excl_ids are both given or both NULL");
+  RC(check_ragged("retrieve_target_rank", LIST_EXCLUDED, excl_off, nq, {excl_ids}));
   const int Vm = medium == 0 ? m->V0 : m->V1;
   for (int64_t q = 0; q < nq; ++q) ARG_CHECK(targets[q] >= 0 && targets[q] < Vm, "retrieve_target_rank: targets must be in [0, V_m)");
   // exclusion positions in the score slab of their chunk: (q - q0) * ldz + id, in query order; xcoff[ch] = first of chunk ch
-  const long long ldz = pad8(std::max(m->V0, m->V1));
+  const long long ldz = score_ldz(m);
   const int nchunks = (int)((nq + RETRIEVE_CHUNK - 1) / RETRIEVE_CHUNK);
   std::vector<long long> xpos, xcoff(nchunks + 1, 0);
-  if (excl_off) {
-    ARG_CHECK(excl_off[0] == 0, "retrieve_target_rank: excl_offsets[0] must be 0");
+  RC(check_list_items("retrieve_target_rank", LIST_EXCLUDED, excl_off, nq, nullptr, excl_ids, &Vm));
+  if (excl_off)
     for (int64_t q = 0; q < nq; ++q) {
-      ARG_CHECK(excl_off[q + 1] >= excl_off[q], "retrieve_target_rank: excl_offsets must be non-decreasing");
-      for (int64_t j = excl_off[q]; j < excl_off[q + 1]; ++j) {
-        ARG_CHECK(excl_ids[j] >= 0 && excl_ids[j] < Vm, "retrieve_target_rank: exclusion ids must be medium-local, in [0, V_m)");
-        xpos.push_back((q % RETRIEVE_CHUNK) * ldz + excl_ids[j]);
-      }
+      for (int64_t j = excl_off[q]; j < excl_off[q + 1]; ++j) xpos.push_back((q % RETRIEVE_CHUNK) * ldz + excl_ids[j]);
       if ((q + 1) % RETRIEVE_CHUNK == 0 || q + 1 == nq) xcoff[q / RETRIEVE_CHUNK + 1] = (long long)xpos.size();
     }
-  }
   return m->bf16_mode ? target_rank_t<bf16>(m, medium, queries, nq, targets, xpos, xcoff, rank_out, logp_out)
                       : target_rank_t<float>(m, medium, queries, nq, targets, xpos, xcoff, rank_out, logp_out);
 }

@@ -13,7 +13,6 @@
 // NaN becomes key 0 in the combine pass, so the rest of the pipeline is retrieve.hip's, unchanged.
 #include <cmath>
 
-#include "encoder_handle.hpp"
 #include "model_internal.hpp"
 
 namespace rsys {
@@ -44,11 +43,6 @@ struct MediumTables {
   int64_t dim = 0;
   unsigned* released = nullptr;  // bitset over [0, V_m), or null: every item released
 };
-
-template <typename X> void dfree(X*& p) {
-  if (p) hipFree(p);
-  p = nullptr;
-}
 
 __device__ __forceinline__ bool bit(const unsigned* b, long long i) { return (b[i >> 5] >> (i & 31)) & 1u; }
 __device__ __forceinline__ float qnan() { return __int_as_float(0x7fc00000); }
@@ -229,12 +223,6 @@ void retrieve_tables_free(Model* m) {
   m->rtab = nullptr;
 }
 
-static int upload(void** dst, const void* src, size_t bytes) {
-  HIP_CHECK(hipMalloc(dst, std::max<size_t>(bytes, 4)));
-  if (bytes) HIP_CHECK(hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice));
-  return RSYS_OK;
-}
-
 static std::vector<unsigned> bitset_of(int64_t n) { return std::vector<unsigned>((size_t)((n + 31) / 32), 0u); }
 
 int model_retrieve_relations_set(Model* m, int medium, int kind, int64_t n_rows, int64_t n_cols, const int64_t* colptr, const int32_t* rowval,
@@ -248,19 +236,7 @@ int model_retrieve_relations_set(Model* m, int medium, int kind, int64_t n_rows,
     ARG_CHECK(rowval && nzval, "retrieve_relations_set: rowval and nzval are required with colptr");
     ARG_CHECK(n_rows == Vm, "retrieve_relations_set: n_rows must be V_m");
     ARG_CHECK(n_cols == (kind == 2 ? Vo : Vm), "retrieve_relations_set: n_cols must be V_m (dependencies, recaps) or V_{1-m} (adaptations)");
-    ARG_CHECK(colptr[0] == 0, "retrieve_relations_set: colptr[0] must be 0");
-    for (int64_t c = 0; c < n_cols; ++c) ARG_CHECK(colptr[c + 1] >= colptr[c], "retrieve_relations_set: colptr must be non-decreasing");
-    const int64_t nnz = colptr[n_cols];
-    cp.assign((size_t)n_cols + 1, 0);
-    rv.reserve((size_t)nnz);
-    for (int64_t c = 0; c < n_cols; ++c) {
-      for (int64_t j = colptr[c]; j < colptr[c + 1]; ++j) {
-        ARG_CHECK(rowval[j] >= 0 && rowval[j] < n_rows, "retrieve_relations_set: row indices must be in [0, n_rows)");
-        ARG_CHECK(std::isfinite(nzval[j]) && nzval[j] >= 0.f, "retrieve_relations_set: stored values must be finite and >= 0");
-        if (nzval[j] != 0.f) rv.push_back(rowval[j]);   // explicitly stored zeros reach nothing
-      }
-      cp[(size_t)c + 1] = (int64_t)rv.size();
-    }
+    RC(csc_nonzero_pattern("retrieve_relations_set", "[0, n_rows)", n_rows, n_cols, colptr, rowval, nzval, cp, rv));
   }
   HIP_CHECK(hipSetDevice(m->device));
   HIP_CHECK(hipStreamSynchronize(m->stream));   // (a request in flight may read the old table)
@@ -343,22 +319,16 @@ static int retrieve_request_body(Model* m, int medium, const float* queries, Ret
   const MediumTables& T = R->t[medium];
   for (int kind = 0; kind < 3; ++kind)
     ARG_CHECK(T.rel[kind].colptr != nullptr, "retrieve_request: the dependencies, recaps and adaptations of the medium must be loaded");
-  ARG_CHECK((hist_off == nullptr) == (hist_medium == nullptr) && (hist_off == nullptr) == (hist_ids == nullptr) &&
-                (hist_off == nullptr) == (hist_status == nullptr),
-            "retrieve_request: the history arrays are all given or all NULL");
-  ARG_CHECK((sel_off == nullptr) == (sel_medium == nullptr) && (sel_off == nullptr) == (sel_ids == nullptr),
-            "retrieve_request: the selected-item arrays are all given or all NULL");
+  RC(check_ragged("retrieve_request", LIST_HISTORY, hist_off, nq, {hist_medium, hist_ids, hist_status}));
+  RC(check_ragged("retrieve_request", LIST_SELECTED, sel_off, ng, {sel_medium, sel_ids}));
   // selected items: ranges, ids, the similarity tables they need
   int64_t nsel = 0;
   if (sel_off) {
-    ARG_CHECK(sel_off[0] == 0, "retrieve_request: sel_offsets[0] must be 0");
-    for (int g = 0; g < ng; ++g) ARG_CHECK(sel_off[g + 1] >= sel_off[g], "retrieve_request: sel_offsets must be non-decreasing");
     nsel = sel_off[ng];
     ARG_CHECK(nsel <= 65535, "retrieve_request: at most 65535 selected items per call");
+    RC(check_list_items("retrieve_request", LIST_SELECTED, sel_off, ng, sel_medium, sel_ids, V));
     for (int64_t a = 0; a < nsel; ++a) {
       const int am = sel_medium[a];
-      ARG_CHECK(am == 0 || am == 1, "retrieve_request: selected items' media must be 0 or 1");
-      ARG_CHECK(sel_ids[a] >= 0 && sel_ids[a] < V[am], "retrieve_request: selected ids must be in [0, V) of their medium");
       ARG_CHECK(R->t[am].emb != nullptr, "retrieve_request: the item-similarity embeddings of a selected item's medium are not loaded");
       if (am != medium)
         ARG_CHECK(R->t[am].cross != nullptr, "retrieve_request: the crossproject of a selected item's medium is not loaded");
@@ -373,12 +343,7 @@ static int retrieve_request_body(Model* m, int medium, const float* queries, Ret
   std::vector<int32_t> ent_q, ent_id, ent_f;
   std::vector<int64_t> ent_off((size_t)nq + 1, 0);
   if (hist_off) {
-    ARG_CHECK(hist_off[0] == 0, "retrieve_request: hist_offsets[0] must be 0");
-    for (int64_t q = 0; q < nq; ++q) ARG_CHECK(hist_off[q + 1] >= hist_off[q], "retrieve_request: hist_offsets must be non-decreasing");
-    for (int64_t j = 0; j < hist_off[nq]; ++j) {
-      ARG_CHECK(hist_medium[j] == 0 || hist_medium[j] == 1, "retrieve_request: list items' media must be 0 or 1");
-      ARG_CHECK(hist_ids[j] >= 0 && hist_ids[j] < V[hist_medium[j]], "retrieve_request: list ids must be in [0, V) of their medium");
-    }
+    RC(check_list_items("retrieve_request", LIST_HISTORY, hist_off, nq, hist_medium, hist_ids, V));
     const size_t nkeys = (size_t)m->V0 + m->V1;
     if (R->mark.size() != nkeys || R->tick > 0xfffffff0u) { R->mark.assign(nkeys, 0u); R->status.assign(nkeys, 0); R->tick = 0; }
     for (int64_t q = 0; q < nq; ++q) {
@@ -417,25 +382,19 @@ static int retrieve_request_body(Model* m, int medium, const float* queries, Ret
 
   HIP_CHECK(hipSetDevice(m->device));
   hipStream_t s = m->stream;
-  auto layout = [&](Carve& c, float** S, float** X, int64_t** d_soff, int32_t** d_smed, int32_t** d_sids, int32_t** d_eq, int32_t** d_eid, int32_t** d_ef,
-                    int32_t** d_qg, unsigned** planes) {
-    *S = c.take<float>(nsel ? (size_t)ng * dim : 1);
-    *X = c.take<float>(nsel ? (size_t)nsel * dim : 1);
-    *d_soff = c.take<int64_t>((size_t)ng + 1);
-    *d_smed = c.take<int32_t>(std::max<int64_t>(nsel, 1));
-    *d_sids = c.take<int32_t>(std::max<int64_t>(nsel, 1));
-    *d_eq = c.take<int32_t>(std::max<int64_t>(nent, 1));
-    *d_eid = c.take<int32_t>(std::max<int64_t>(nent, 1));
-    *d_ef = c.take<int32_t>(std::max<int64_t>(nent, 1));
-    *d_qg = c.take<int32_t>((size_t)nq);
-    *planes = c.take<unsigned>((size_t)slice * RR_PLANES * W);
-  };
   float *S, *X; int64_t* d_soff; int32_t *d_smed, *d_sids, *d_eq, *d_eid, *d_ef, *d_qg; unsigned* planes;
-  Carve probe{nullptr};
-  layout(probe, &S, &X, &d_soff, &d_smed, &d_sids, &d_eq, &d_eid, &d_ef, &d_qg, &planes);
-  if (int rc = R->ws.reserve(probe.off, s)) return rc;
-  Carve c{(char*)R->ws.p};
-  layout(c, &S, &X, &d_soff, &d_smed, &d_sids, &d_eq, &d_eid, &d_ef, &d_qg, &planes);
+  RC(carve_into(R->ws, s, [&](Carve& c) {
+    S = c.take<float>(nsel ? (size_t)ng * dim : 0);
+    X = c.take<float>(nsel ? (size_t)nsel * dim : 0);
+    d_soff = c.take<int64_t>((size_t)ng + 1);
+    d_smed = c.take<int32_t>(nsel);
+    d_sids = c.take<int32_t>(nsel);
+    d_eq = c.take<int32_t>(nent);
+    d_eid = c.take<int32_t>(nent);
+    d_ef = c.take<int32_t>(nent);
+    d_qg = c.take<int32_t>((size_t)nq);
+    planes = c.take<unsigned>((size_t)slice * RR_PLANES * W);
+  }));
   std::vector<int64_t> soff(sel_off ? sel_off : nullptr, sel_off ? sel_off + ng + 1 : nullptr);
   if (!sel_off) soff.assign((size_t)ng + 1, 0);
   // (synchronous copies from pageable memory: the host vectors above outlive them)

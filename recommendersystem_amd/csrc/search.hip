@@ -386,18 +386,13 @@ static int search_topk(SearchModel* h, const float* x, int nq, int k, int32_t* i
   HIP_CHECK(hipSetDevice(h->device));
   hipStream_t s = h->stream;
   const int Bpad = (nq + 255) / 256 * 256;
-  auto layout = [&](Carve& c, void** ws, int** ids, float** vals, int** cnt) {
-    *ws = c.take<char>(topk_rows_ws_bytes(nq, h->V, k));
-    *ids = c.take<int>((size_t)nq * k);
-    *vals = c.take<float>((size_t)nq * k);
-    *cnt = c.take<int>(nq);
-  };
   void* ws; int *ids, *cnt; float* vals;
-  Carve probe{nullptr};
-  layout(probe, &ws, &ids, &vals, &cnt);
-  ENC_RC(h->tws.reserve(probe.off, s));
-  Carve cv{(char*)h->tws.p};
-  layout(cv, &ws, &ids, &vals, &cnt);
+  ENC_RC(carve_into(h->tws, s, [&](Carve& c) {
+    ws = c.take<char>(topk_rows_ws_bytes(nq, h->V, k));
+    ids = c.take<int>((size_t)nq * k);
+    vals = c.take<float>((size_t)nq * k);
+    cnt = c.take<int>(nq);
+  }));
   if (h->bf16_mode()) {
     ENC_RC(search_upload_x<bf16>(h, x, nq, Bpad));
     ENC_RC(search_scores<bf16>(h, nq, Bpad, false, false, nullptr));

@@ -601,25 +601,19 @@ static int sim_hard_negatives(SimModel* h, int split, int n_src, const int32_t* 
   if (pos_off)
     for (int c0 = 0; c0 < n_src; c0 += SIM_HN_CHUNK)
       max_pos = std::max<long long>(max_pos, pos_off[std::min(n_src, c0 + SIM_HN_CHUNK)] - pos_off[c0]);
-  auto layout = [&](Carve& c, bf16** A, float** z, float** sc, void** tws, int** tids, float** tvals, int** cnt, int** out, int** src,
-                    long long** pos) {
-    *A = c.take<bf16>((size_t)C * E);
-    *z = c.take<float>((size_t)C * ldz);
-    *sc = c.take<float>((size_t)C * V);
-    *tws = c.take<char>(topk_rows_ws_bytes(C, V, n));
-    *tids = c.take<int>((size_t)C * n);
-    *tvals = c.take<float>((size_t)C * n);
-    *cnt = c.take<int>(C);
-    *out = c.take<int>((size_t)C * n);
-    *src = c.take<int>(C);
-    *pos = c.take<long long>(max_pos);
-  };
   bf16* A; float *z, *sc, *tvals; void* tws; int *tids, *cnt, *out, *dsrc; long long* dpos;
-  Carve probe{nullptr};
-  layout(probe, &A, &z, &sc, &tws, &tids, &tvals, &cnt, &out, &dsrc, &dpos);
-  ENC_RC(h->hws.reserve(probe.off, s));
-  Carve cv{(char*)h->hws.p};
-  layout(cv, &A, &z, &sc, &tws, &tids, &tvals, &cnt, &out, &dsrc, &dpos);
+  ENC_RC(carve_into(h->hws, s, [&](Carve& c) {
+    A = c.take<bf16>((size_t)C * E);
+    z = c.take<float>((size_t)C * ldz);
+    sc = c.take<float>((size_t)C * V);
+    tws = c.take<char>(topk_rows_ws_bytes(C, V, n));
+    tids = c.take<int>((size_t)C * n);
+    tvals = c.take<float>((size_t)C * n);
+    cnt = c.take<int>(C);
+    out = c.take<int>((size_t)C * n);
+    dsrc = c.take<int>(C);
+    dpos = c.take<long long>(max_pos);
+  }));
   std::vector<long long> hpos;
   for (int c0 = 0; c0 < n_src; c0 += SIM_HN_CHUNK) {
     const int nc = std::min(SIM_HN_CHUNK, n_src - c0);

@@ -207,18 +207,17 @@ struct PairBufs {
   int *src, *tid, *rank, *sslot;
   long long* off;
   u64* skeys;
+  void take(Carve& c, int n_src, long long total, int C, int E, long long ldz, bool scores) {
+    A = c.take<float>(scores ? (size_t)C * E : 0);
+    z = c.take<float>(scores ? (size_t)C * ldz : 0);
+    src = c.take<int>(n_src);
+    off = c.take<long long>((size_t)n_src + 1);
+    tid = c.take<int>(total);
+    rank = c.take<int>(total);
+    sslot = c.take<int>(total);
+    skeys = c.take<u64>(total);
+  }
 };
-
-void pair_layout(Carve& c, int n_src, long long total, int C, int E, long long ldz, bool scores, PairBufs* b) {
-  b->A = c.take<float>(scores ? (size_t)C * E : 0);
-  b->z = c.take<float>(scores ? (size_t)C * ldz : 0);
-  b->src = c.take<int>(n_src);
-  b->off = c.take<long long>((size_t)n_src + 1);
-  b->tid = c.take<int>(total);
-  b->rank = c.take<int>(total);
-  b->sslot = c.take<int>(total);
-  b->skeys = c.take<u64>(total);
-}
 
 int pair_check_csr(const char* who, int V, int32_t n_rows, const int32_t* self, const int64_t* off, const int32_t* tids) {
   ARG_CHECK(self && off, std::string(who) + ": null buffer");
@@ -270,11 +269,7 @@ int pair_ranks_run(const float* exp32, int V, int E, const unsigned* tmask, long
   const int C = std::min<int>(n_src, PR_CHUNK);
   const long long ldz = (V + 7) / 8 * 8;
   PairBufs b;
-  Carve probe{nullptr};
-  pair_layout(probe, n_src, total, C, E, ldz, true, &b);
-  if (int rc = ws->reserve(probe.off, s)) return rc;
-  Carve cv{(char*)ws->p};
-  pair_layout(cv, n_src, total, C, E, ldz, true, &b);
+  if (int rc = carve_into(*ws, s, [&](Carve& c) { b.take(c, n_src, total, C, E, ldz, true); })) return rc;
   HIP_CHECK(hipMemcpyAsync(b.src, sources, (size_t)n_src * 4, hipMemcpyHostToDevice, s));
   HIP_CHECK(hipMemcpyAsync(b.off, off, ((size_t)n_src + 1) * 8, hipMemcpyHostToDevice, s));
   HIP_CHECK(hipMemcpyAsync(b.tid, tids, (size_t)total * 4, hipMemcpyHostToDevice, s));
@@ -296,11 +291,7 @@ int pair_scores_run(const float* exp32, int V, int E, const unsigned* tmask, lon
   const int C = std::min<int>(n_src, PR_CHUNK);
   const long long ldz = (V + 7) / 8 * 8;
   PairBufs b;
-  Carve probe{nullptr};
-  pair_layout(probe, n_src, 0, C, E, ldz, true, &b);
-  if (int rc = ws->reserve(probe.off, s)) return rc;
-  Carve cv{(char*)ws->p};
-  pair_layout(cv, n_src, 0, C, E, ldz, true, &b);
+  if (int rc = carve_into(*ws, s, [&](Carve& c) { b.take(c, n_src, 0, C, E, ldz, true); })) return rc;
   HIP_CHECK(hipMemcpyAsync(b.src, sources, (size_t)n_src * 4, hipMemcpyHostToDevice, s));
   for (int c0 = 0; c0 < n_src; c0 += PR_CHUNK) {
     const int nc = std::min(PR_CHUNK, n_src - c0);
@@ -322,11 +313,7 @@ int op_pair_ranks(const float* scores, int64_t ld, int32_t rows, int32_t V, cons
   if (total == 0) return RSYS_OK;
   DevScratch ws;
   PairBufs b;
-  Carve probe{nullptr};
-  pair_layout(probe, rows, total, 0, 0, 0, false, &b);
-  if (int rc = ws.reserve(probe.off, nullptr)) return rc;
-  Carve cv{(char*)ws.p};
-  pair_layout(cv, rows, total, 0, 0, 0, false, &b);
+  if (int rc = carve_into(ws, nullptr, [&](Carve& c) { b.take(c, rows, total, 0, 0, 0, false); })) return rc;
   const int rc = [&]() -> int {
     HIP_CHECK(hipMemcpy(b.src, self, (size_t)rows * 4, hipMemcpyHostToDevice));
     HIP_CHECK(hipMemcpy(b.off, off, ((size_t)rows + 1) * 8, hipMemcpyHostToDevice));

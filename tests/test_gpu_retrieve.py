@@ -331,3 +331,100 @@ def test_retrieve_topk_argument_errors():
     with pytest.raises(ra.RsysError):
         sh.retrieve_topk(q, 0, 5)
     sh.close()
+
+
+# ---------------------------------------------------------------- results do not depend on what the workspace held before
+# A small call, a call sized to replace every buffer of the call family's workspace (257 queries: one row past the 256-query chunk),
+# then the small call again: the second small call returns what the first did, bit for bit.  The three callers of the shared scoring
+# prologue: retrieve_topk, retrieve_target_rank, rank_request.
+def _same_bits(a, b):
+    assert len(a) == len(b)
+    for x, y in zip(a, b):
+        assert x.dtype == y.dtype and x.tobytes() == y.tobytes()
+
+
+@pytest.mark.parametrize("dtype", ["fp32", "bf16"])
+def test_retrieve_topk_small_large_small(dtype):
+    cfg, model = _model("hd64", dtype)
+    tol_rel = 2e-5 if dtype == "fp32" else 2e-3
+    rng = np.random.default_rng(31)
+    D = cfg["embed_dim"]
+    qa = rng.standard_normal((3, D)).astype(np.float32)
+    qb = rng.standard_normal((257, D)).astype(np.float32)
+    for medium in (0, 1):
+        Vm = cfg["vocab_sizes"][f"{medium}_matchedid"]
+        small = dict(queries=qa, medium=medium, k=8, group=[0, 1, 0], exclude=[np.array([0, 5, Vm - 1]), np.array([3])])
+        a1 = model.retrieve_topk(**small)
+        group = (np.arange(257) % 5).astype(np.int32)
+        exclude = [rng.integers(0, Vm, 10) for _ in range(5)]
+        k = min(Vm, 8192)
+        ids, sc, cnt = model.retrieve_topk(qb, medium, k, group=group, exclude=exclude)
+        a2 = model.retrieve_topk(**small)
+        _same_bits(a1, a2)
+        ref, adm, _ = _reference(model, cfg, dtype, qb, medium, group, 5, None, exclude)
+        _check_e2e(ids, sc, cnt, ref, adm, k, tol_rel)
+    model.close()
+
+
+@pytest.mark.parametrize("dtype", ["fp32", "bf16"])
+def test_retrieve_target_rank_small_large_small(dtype):
+    cfg, model = _model("hd64", dtype)
+    tol_rel = 2e-5 if dtype == "fp32" else 2e-3
+    rng = np.random.default_rng(32)
+    D = cfg["embed_dim"]
+    medium = 1
+    Vm = cfg["vocab_sizes"]["1_matchedid"]
+    qa = rng.standard_normal((3, D)).astype(np.float32)
+    qb = rng.standard_normal((257, D)).astype(np.float32)
+    small = dict(queries=qa, medium=medium, targets=[4, 0, Vm - 1], exclude=[np.array([1, 2]), np.array([], np.int64), np.array([Vm - 1])])
+    a1 = model.retrieve_target_rank(**small)
+    targets = rng.integers(0, Vm, 257).astype(np.int32)
+    exclude = [np.setdiff1d(rng.integers(0, Vm, 6), [targets[i]]) for i in range(257)]
+    rank, logp = model.retrieve_target_rank(qb, medium, targets, exclude=exclude)
+    a2 = model.retrieve_target_rank(**small)
+    _same_bits(a1, a2)
+    assert a1[0][2] == 0                                                    # its target is excluded
+    _, _, lp = _reference(model, cfg, dtype, qb, medium, range(257), 257, None, None)
+    for i in range(257):
+        t = lp[i, targets[i]]
+        tol = tol_rel * max(1.0, abs(t))
+        assert abs(logp[i] - t) <= tol, (i, logp[i], t)
+        others = np.ones(Vm, bool)
+        others[exclude[i]] = False
+        others[targets[i]] = False
+        lo = 1 + int((lp[i, others] > t + 2 * tol).sum())
+        hi = 1 + int((lp[i, others] >= t - 2 * tol).sum())
+        assert lo <= rank[i] <= hi, (i, rank[i], lo, hi)
+    model.close()
+
+
+@pytest.mark.parametrize("dtype", ["fp32", "bf16"])
+def test_rank_request_small_large_small(dtype):
+    cfg, model = _model("hd64", dtype)
+    rng = np.random.default_rng(33)
+    D = cfg["embed_dim"]
+    medium = 1
+    Vm = cfg["vocab_sizes"]["1_matchedid"]
+    model.set_item_similarity(medium, (0.3 * rng.standard_normal((Vm, 64))).astype(np.float32))
+    cols = [np.unique(rng.integers(0, Vm, 4)) for _ in range(Vm)]
+    indptr = np.concatenate([[0], np.cumsum([c.size for c in cols])])
+    rows = np.concatenate(cols)
+    model.set_related(medium, (indptr, rows, np.ones(rows.size, np.float32), (Vm, Vm)))
+
+    def request(sizes, group):
+        r = np.random.default_rng(34 + len(sizes))
+        cand = [r.choice(Vm, n, replace=False).astype(np.int32) for n in sizes]
+        q = r.standard_normal((len(group), D)).astype(np.float32)
+        rm = [r.uniform(0, 10, sizes[g]).astype(np.float32) for g in group]
+        hist = [[(medium, int(i), 2) for i in r.integers(0, Vm, 5)] for _ in group]
+        pen = [(0.9, 0.3, 1.5, 0.5)] * len(sizes)
+        ids, sc = model.rank_request(q, medium, cand, group=group, r_masked=rm, partialk=[n for n in sizes], penalties=pen, histories=hist)
+        for g, n in enumerate(sizes):
+            assert ids[g].size == n and set(ids[g].tolist()) <= set(cand[g].tolist())
+        return ids + sc
+
+    a1 = request([4], [0])
+    request([64, 33, min(64, Vm)], [0, 1, 2, 0, 2])
+    a2 = request([4], [0])
+    _same_bits(a1, a2)
+    model.close()
