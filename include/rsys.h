@@ -266,6 +266,31 @@ int32_t rsys_render_request(rsys_model* m, int32_t n_groups,
                             const int32_t* sel_medium, const int32_t* sel_ids,
                             const int32_t* coef_have, const float* coefs,            /* [2] or NULL, [2][4] or NULL */
                             int32_t* ids_out, int64_t ids_cap, int64_t* ids_offsets, int32_t* total_out);
+/* rsys_render_request with the ranking forward on the reference's row (Finetune/embed.py:74-131, max_user_len - 1 = S - 1 events; DESIGN.md
+ * 4w): every user is ranked on ALL the history its retrieval row holds, through the per-user K/V cache of rsys_rank_cache_*, instead of the
+ * newest S / 2 - 1 events that fit beside a chunk of candidates.  The arguments of rsys_render_request without ranking_prefix and
+ * prefix_stride; user_desc[u] = (n_hist, userid, gender, source) with n_hist in [0, S - 1]: columns [0, n_hist) of retrieval row u are the
+ * user's history (positions 0 .. n_hist - 1, token_mask_ids 0; serve.render_pack writes retrieval_token[u] = 2 n_hist).  The rows' history
+ * columns stay on the device while the retrieval waves upload them; no history column crosses the bus twice.  Per wave of at most max_rows
+ * users with n_hist >= 1 one forward stores their histories (slot = the user's place in the wave), then their candidates run against the
+ * slots in rows of at most S candidates (a user's candidates may span rows, rows of several users share a forward of at most max_rows rows):
+ * candidate j of a row at column j with rope_input_pos = n_hist.  Users with n_hist = 0 run the assembled rows of rsys_render_request (nh =
+ * 0, chunks of S - S / 2), in forwards of their own.  The cache is the model's reserve when it holds min(max_rows, users with a history)
+ * slots, else max_rows slots are reserved (RSYS_ERR_STATE, outputs untouched, when they do not fit); the slots a call used hold its last
+ * wave's histories afterwards, other slots are not touched.  Outputs, limits, errors and side effects as rsys_render_request. */
+int32_t rsys_render_request_full(rsys_model* m, int32_t n_groups,
+                                 const int32_t* group_medium, const int64_t* offset, const int32_t* limit,  /* [n_groups] each */
+                                 const float* penalties,                                  /* [n_groups][4] */
+                                 int64_t n_users, const int32_t* group,                   /* [n_users] in [0, n_groups) */
+                                 const rsys_batch* retrieval_rows, const int32_t* retrieval_token,   /* rows = n_users; [n_users] */
+                                 const int32_t* user_desc, const double* user_ts,         /* [n_users][4], [n_users] */
+                                 const int32_t* adapter_slots,                            /* [4] or NULL */
+                                 const int64_t* hist_offsets,                             /* [n_users + 1] CSR over users, or NULL (no lists) */
+                                 const int32_t* hist_medium, const int32_t* hist_ids, const int32_t* hist_status,
+                                 const int64_t* sel_offsets,                              /* [n_groups + 1] CSR over groups, or NULL (none selected) */
+                                 const int32_t* sel_medium, const int32_t* sel_ids,
+                                 const int32_t* coef_have, const float* coefs,            /* [2] or NULL, [2][4] or NULL */
+                                 int32_t* ids_out, int64_t ids_cap, int64_t* ids_offsets, int32_t* total_out);
 /* ---- Item-similarity LambdaRank model (Training/item_similarity/pairwise_ltr.py, --features transformer / content).
  * A handle of its own, independent of rsys_model: an rsys_simmodel, passed as an opaque void*.  Trainable parameters by the reference's
  * state-dict names: "encoder.1.weight" [E][F] (weight decay 0.1) and "logit_scale" (scalar, log(1/0.07) at creation, no decay); the frozen

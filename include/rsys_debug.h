@@ -110,7 +110,13 @@ int32_t rsys_op_rerank(int32_t n, int32_t partialk, const float* pen, const floa
  * int32; rating, progress f32; time f64) [n_rows][S], the assembled ranking rows; "token_index" int32 (the rows' action tokens, flat within
  * their wave); "groups" int32 [n_active][6] = (group, medium, first slot in "r" / "picks", candidates, sidx, eidx) per group with a page;
  * "rm_users" int32 [n][3] = (user, first value in "r_masked", values); "r_masked" f32; "r" f32 (ranking scores) and "picks" int32 (picked
- * positions; the slots after a group's eidx rounds hold -1). */
+ * positions; the slots after a group's eidx rounds hold -1).
+ * After rsys_render_request_full: "forwards" [1] counts every ranking-stage forward; "forwards.full" int32 [3] = (store forwards, candidate
+ * forwards, empty-history chunk forwards; kept always); "store.<array>" the store rows [n_store_rows][S] in run order with "store.rows"
+ * int32 [n][4] = (user, slot, events, wave); "cand.<array>" the candidate rows of the cached path with "cand.token_index"; "rows" int32
+ * [n_rows][7] = (user, group, first candidate slot, candidates, row in its forward, forward, kind): kind 0 = a candidate row of the cached
+ * path (forward = index among the candidate forwards), kind 1 = an assembled row of a user with an empty history (forward = index among
+ * those forwards; its arrays under "batch.<array>" / "token_index" as above); the cached rows come first. */
 int32_t rsys_render_debug_keep(rsys_model* m, int32_t on);
 int32_t rsys_render_debug_get(rsys_model* m, const char* key, void* out, int64_t cap, int64_t* bytes);
 /* the last rsys_sim_forward_backward / rsys_sim_ndcg call of an item-similarity handle (host arrays): "ranks" int32 [n_q][n] (1-based

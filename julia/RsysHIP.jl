@@ -382,6 +382,34 @@ function render_request(m::Model, medium, offset, limit, penalties::Matrix{Float
         ioff, total))
     [ids[ioff[j]+1:ioff[j+1]] for j in 1:ng], total
 end
+# the same page with the ranking forward on full-length histories through the per-user K/V cache (rsys_render_request_full): no prefix;
+# desc[1, u] = n_hist in 0:S-1, the history columns of row u of `rows`
+function render_request_full(m::Model, medium, offset, limit, penalties::Matrix{Float32}, group, rows::RsysBatch, token, desc::Matrix{Int32},
+                             ts; slots = nothing, hist = nothing, sel = nothing, coef_have = nothing, coefs = nothing)
+    gm = Vector{Int32}(medium); ng = length(gm)
+    off = Vector{Int64}(offset); lim = Vector{Int32}(limit)
+    g = Vector{Int32}(group); nu = length(g)
+    tok = Vector{Int32}(token); tsv = Vector{Float64}(ts)
+    sl = slots === nothing ? Ptr{Int32}(C_NULL) : Vector{Int32}(slots)
+    hoff = hist === nothing ? Ptr{Int64}(C_NULL) : Int64[0; cumsum(Int64[length(h) for h in hist])]
+    hmed = hist === nothing ? Ptr{Int32}(C_NULL) : Int32[x[1] for h in hist for x in h]
+    hid = hist === nothing ? Ptr{Int32}(C_NULL) : Int32[x[2] for h in hist for x in h]
+    hst = hist === nothing ? Ptr{Int32}(C_NULL) : Int32[x[3] for h in hist for x in h]
+    soff = sel === nothing ? Ptr{Int64}(C_NULL) : Int64[0; cumsum(Int64[length(s) for s in sel])]
+    smed = sel === nothing ? Ptr{Int32}(C_NULL) : Int32[x[1] for s in sel for x in s]
+    sid = sel === nothing ? Ptr{Int32}(C_NULL) : Int32[x[2] for s in sel for x in s]
+    ch = coef_have === nothing ? Ptr{Int32}(C_NULL) : Vector{Int32}(coef_have)
+    cf = coefs === nothing ? Ptr{Float32}(C_NULL) : Vector{Float32}(vec(coefs))
+    cap = sum(Int64.(lim))
+    ids = Vector{Int32}(undef, max(cap, 1)); ioff = Vector{Int64}(undef, ng + 1); total = Vector{Int32}(undef, ng)
+    GC.@preserve gm off lim penalties g tok desc tsv sl hoff hmed hid hst soff smed sid ch cf ids ioff total check(ccall((:rsys_render_request_full, LIB), Int32,
+        (Ptr{Cvoid}, Int32, Ptr{Int32}, Ptr{Int64}, Ptr{Int32}, Ptr{Float32}, Int64, Ptr{Int32}, Ref{RsysBatch}, Ptr{Int32},
+         Ptr{Int32}, Ptr{Float64}, Ptr{Int32}, Ptr{Int64}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Int64}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32},
+         Ptr{Float32}, Ptr{Int32}, Int64, Ptr{Int64}, Ptr{Int32}),
+        m.h, ng, gm, off, lim, penalties, nu, g, rows, tok, desc, tsv, sl, hoff, hmed, hid, hst, soff, smed, sid, ch, cf, ids, cap,
+        ioff, total))
+    [ids[ioff[j]+1:ioff[j+1]] for j in 1:ng], total
+end
 function infer(m::Model, task::Integer, rows::Integer, S::Integer, D::Integer)   # model.py:531-538 over every token of the resident batch
     out = task == 0 ? Array{Float32}(undef, D, 2S, rows) : Array{Float32}(undef, 2S, rows)
     GC.@preserve out check(ccall((:rsys_infer, LIB), Int32, (Ptr{Cvoid}, Int32, Ptr{Float32}, Int64), m.h, task, out, length(out))); out

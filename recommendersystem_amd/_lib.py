@@ -84,6 +84,8 @@ _SIGS = [
                                       C.c_float, _P, _P, _P]),
     ("rsys_render_request", C.c_int32, [_P, C.c_int32, _P, _P, _P, _P, C.c_int64, _P, C.POINTER(rsys_batch), _P, C.POINTER(rsys_batch),
                                         C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int64, _P, _P]),
+    ("rsys_render_request_full", C.c_int32, [_P, C.c_int32, _P, _P, _P, _P, C.c_int64, _P, C.POINTER(rsys_batch), _P, _P, _P, _P, _P, _P, _P,
+                                             _P, _P, _P, _P, _P, _P, _P, C.c_int64, _P, _P]),
     ("rsys_render_debug_keep", C.c_int32, [_P, C.c_int32]),
     ("rsys_render_debug_get", C.c_int32, [_P, C.c_char_p, _P, C.c_int64, C.POINTER(C.c_int64)]),
     ("rsys_sim_create", C.c_int32, [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.POINTER(_P)]),

@@ -221,6 +221,17 @@ int32_t rsys_render_request(rsys_model* h, int32_t n_groups, const int32_t* grou
                               ranking_prefix, prefix_stride, user_desc, user_ts, adapter_slots, hist_offsets, hist_medium, hist_ids, hist_status,
                               sel_offsets, sel_medium, sel_ids, coef_have, coefs, ids_out, ids_cap, ids_offsets, total_out);
 }
+int32_t rsys_render_request_full(rsys_model* h, int32_t n_groups, const int32_t* group_medium, const int64_t* offset, const int32_t* limit,
+                                 const float* penalties, int64_t n_users, const int32_t* group, const rsys_batch* retrieval_rows,
+                                 const int32_t* retrieval_token, const int32_t* user_desc, const double* user_ts, const int32_t* adapter_slots,
+                                 const int64_t* hist_offsets, const int32_t* hist_medium, const int32_t* hist_ids, const int32_t* hist_status,
+                                 const int64_t* sel_offsets, const int32_t* sel_medium, const int32_t* sel_ids, const int32_t* coef_have,
+                                 const float* coefs, int32_t* ids_out, int64_t ids_cap, int64_t* ids_offsets, int32_t* total_out) {
+  CHECK_HANDLE(h);
+  return model_render_request_full(h->m, n_groups, group_medium, offset, limit, penalties, n_users, group, retrieval_rows, retrieval_token,
+                                   user_desc, user_ts, adapter_slots, hist_offsets, hist_medium, hist_ids, hist_status, sel_offsets, sel_medium,
+                                   sel_ids, coef_have, coefs, ids_out, ids_cap, ids_offsets, total_out);
+}
 int32_t rsys_render_debug_keep(rsys_model* h, int32_t on) { CHECK_HANDLE(h); return render_debug_keep(h->m, on); }
 int32_t rsys_render_debug_get(rsys_model* h, const char* key, void* out, int64_t cap, int64_t* bytes) {
   CHECK_HANDLE(h);

@@ -339,6 +339,12 @@ int model_rank_cache_store(Model* m, const int32_t* row_adapter, const int32_t* 
 int model_rank_cache_candidates(Model* m, const int32_t* row_adapter, const int32_t* slot, const int32_t* n_cand, float* out);
 int model_rank_cache_get(Model* m, int layer, int slot, void* out, int64_t bytes);   // a slot's K | V rows of one layer, [2 n_hist][2 KV hd], compute dtype
 void rank_cache_free(Model* m);
+// the two passes without a host wait, for a caller whose rows (and, for the candidates, RoPE positions d_pos [rows][2S], selection d_sel
+// [ntok] and output d_out [ntok]) are on the device: rsys_render_request_full.  tab: host [3 max_rows], filled here and read by a
+// stream-ordered copy, as row_adapter is -- both stay valid until the stream has passed the call
+int rank_cache_store_rows(Model* m, const int32_t* row_adapter, const int32_t* n_hist, const int32_t* slot, int* tab);
+int rank_cache_candidates_rows(Model* m, const int32_t* row_adapter, const int32_t* slot, const int32_t* n_cand, int* tab, int* d_pos,
+                               const int* d_sel, int64_t ntok, float* d_out);
 template <typename T> int rank_cache_store_layer(Model* m, int l, const T* qkv);      // forward_trunk, rc_mode == 1
 template <typename T> int rank_cache_attention(Model* m, int l, const T* qkv, T* O);  // forward_trunk, rc_mode == 2
 // the inference forward over the resident batch with the tokens to report (n_sel flat indices) and the rating head's values on the device
@@ -415,6 +421,14 @@ int model_render_request(Model* m, int32_t ng, const int32_t* group_medium, cons
                          const int32_t* hist_status, const int64_t* sel_off, const int32_t* sel_medium, const int32_t* sel_ids,
                          const int32_t* coef_have, const float* coefs, int32_t* ids_out, int64_t ids_cap, int64_t* ids_offsets,
                          int32_t* total_out);
+// the same page with the ranking forward on full-length histories through the K/V cache (rsys_render_request_full): no prefix arrays,
+// user_desc[u][0] = the history columns of retrieval row u
+int model_render_request_full(Model* m, int32_t ng, const int32_t* group_medium, const int64_t* offset, const int32_t* limit,
+                              const float* penalties, int64_t nu, const int32_t* group, const rsys_batch* rb, const int32_t* retrieval_token,
+                              const int32_t* user_desc, const double* user_ts, const int32_t* slots, const int64_t* hist_off,
+                              const int32_t* hist_medium, const int32_t* hist_ids, const int32_t* hist_status, const int64_t* sel_off,
+                              const int32_t* sel_medium, const int32_t* sel_ids, const int32_t* coef_have, const float* coefs,
+                              int32_t* ids_out, int64_t ids_cap, int64_t* ids_offsets, int32_t* total_out);
 int render_debug_keep(Model* m, int on);
 int render_debug_get(Model* m, const char* key, void* out, int64_t cap, int64_t* bytes);
 void render_free(Model* m);

@@ -92,7 +92,10 @@ static int rc_check_call(Model* m, const int32_t* a, const int32_t* b) {
   return RSYS_OK;
 }
 
-int model_rank_cache_store(Model* m, const int32_t* row_adapter, const int32_t* n_hist, const int32_t* slot) {
+// The store pass over the resident batch, whose rows were uploaded (rsys_rank_cache_store) or assembled on the device
+// (rsys_render_request_full).  `tab` (host, [3 max_rows]) receives the rows' {slot | n_hist | 0} table and is read by a stream-ordered
+// copy, as row_adapter is: both stay as they are until the stream has passed this call.  No host wait on success.
+int rank_cache_store_rows(Model* m, const int32_t* row_adapter, const int32_t* n_hist, const int32_t* slot, int* tab) {
   RC(rc_check_call(m, n_hist, slot));
   const int rows = m->cur_rows;
   std::vector<char> seen((size_t)m->rc_slots, 0);
@@ -104,68 +107,104 @@ int model_rank_cache_store(Model* m, const int32_t* row_adapter, const int32_t* 
   }
   HIP_CHECK(hipSetDevice(m->device));
   if (row_adapter) RC(adapter_bind_rows(m, row_adapter));
-  std::vector<int> h((size_t)3 * m->rows_max, 0);
-  for (int r = 0; r < rows; ++r) { h[r] = slot[r]; h[m->rows_max + r] = n_hist[r]; }
-  int rc = RSYS_OK;
+  std::fill(tab, tab + (size_t)3 * m->rows_max, 0);
+  for (int r = 0; r < rows; ++r) { tab[r] = slot[r]; tab[m->rows_max + r] = n_hist[r]; }
   auto run = [&]() -> int {
-    HIP_CHECK(hipMemcpyAsync(m->rc_rows, h.data(), h.size() * 4, hipMemcpyHostToDevice, m->stream));
+    HIP_CHECK(hipMemcpyAsync(m->rc_rows, tab, (size_t)3 * m->rows_max * 4, hipMemcpyHostToDevice, m->stream));
     m->rc_mode = 1;
     RC(m->bf16_mode ? infer_trunk<bf16>(m) : infer_trunk<float>(m));
-    HIP_CHECK(hipStreamSynchronize(m->stream));
     return RSYS_OK;
   };
-  rc = run();
+  const int rc = run();
   m->rc_mode = 0;
   adapter_unbind_rows(m);
-  if (rc != RSYS_OK) (void)hipStreamSynchronize(m->stream);   // (the copies above read this call's host vectors)
+  if (rc != RSYS_OK) (void)hipStreamSynchronize(m->stream);   // (the copies above read the caller's host arrays)
   // (a failed pass may have written some layers of the slots: they no longer hold a history)
   for (int r = 0; r < rows; ++r) m->rc_nhist[slot[r]] = rc == RSYS_OK ? n_hist[r] : -1;
   return rc;
 }
 
-int model_rank_cache_candidates(Model* m, const int32_t* row_adapter, const int32_t* slot, const int32_t* n_cand, float* out) {
+int model_rank_cache_store(Model* m, const int32_t* row_adapter, const int32_t* n_hist, const int32_t* slot) {
+  std::vector<int> tab((size_t)3 * m->rows_max);
+  RC(rank_cache_store_rows(m, row_adapter, n_hist, slot, tab.data()));
+  const hipError_t e = hipStreamSynchronize(m->stream);
+  if (e != hipSuccess)
+    for (int r = 0; r < m->cur_rows; ++r) m->rc_nhist[slot[r]] = -1;
+  HIP_CHECK(e);
+  return RSYS_OK;
+}
+
+static int rc_check_candidates(Model* m, const int32_t* slot, const int32_t* n_cand, int64_t* ntok) {
   RC(rc_check_call(m, slot, n_cand));
-  ARG_CHECK(out != nullptr, "ranking cache: null output");
-  const int rows = m->cur_rows, T = m->T;
-  int64_t ntok = 0;
-  for (int r = 0; r < rows; ++r) {
+  *ntok = 0;
+  for (int r = 0; r < m->cur_rows; ++r) {
     ARG_CHECK(slot[r] >= 0 && slot[r] < m->rc_slots, "ranking cache: slot outside the reserve");
     ARG_CHECK(m->rc_nhist[slot[r]] >= 0, "ranking cache: slot never stored");
     ARG_CHECK(m->rc_nhist[slot[r]] <= m->S - 1, "ranking cache: candidates run at position n_hist, which must stay below max_sequence_length");
     ARG_CHECK(n_cand[r] >= 1 && n_cand[r] <= m->S, "ranking cache: n_cand must be in [1, max_sequence_length]");
-    ntok += n_cand[r];
+    *ntok += n_cand[r];
   }
+  return RSYS_OK;
+}
+
+// The candidate pass over the resident batch with everything but the row table on the device: d_pos [rows][2S] the tokens' RoPE positions
+// (2 n_hist, 2 n_hist + 1), d_sel [ntok] the candidates' action tokens (row 2S + 2 j + 1, rows in order), d_out [ntok] the rating-head
+// values.  `tab` (host, [3 max_rows]) receives {slot | n_hist | n_cand} and is read by a stream-ordered copy, as row_adapter is.  No
+// host wait on success.
+int rank_cache_candidates_rows(Model* m, const int32_t* row_adapter, const int32_t* slot, const int32_t* n_cand, int* tab, int* d_pos,
+                               const int* d_sel, int64_t ntok, float* d_out) {
+  int64_t want = 0;
+  RC(rc_check_candidates(m, slot, n_cand, &want));
+  ARG_CHECK(d_pos && d_sel && d_out && ntok == want, "ranking cache: one selected token per candidate");
+  const int rows = m->cur_rows;
   HIP_CHECK(hipSetDevice(m->device));
   if (row_adapter) RC(adapter_bind_rows(m, row_adapter));
-  std::vector<int> h((size_t)3 * m->rows_max, 0), pos((size_t)rows * T), sel((size_t)ntok);
-  int64_t k = 0;
-  for (int r = 0; r < rows; ++r) {
-    const int nh = m->rc_nhist[slot[r]];
-    h[r] = slot[r]; h[m->rows_max + r] = nh; h[2 * m->rows_max + r] = n_cand[r];
-    for (int i = 0; i < m->S; ++i) { pos[(size_t)r * T + 2 * i] = 2 * nh; pos[(size_t)r * T + 2 * i + 1] = 2 * nh + 1; }   // model.py:470-476 at rope_input_pos = n_hist
-    for (int j = 0; j < n_cand[r]; ++j) sel[k++] = r * T + 2 * j + 1;
-  }
-  // the rows' positions live in the cache's own buffer for the length of this call: the resident batch's rope_input_pos stays what it is
-  int* const d_pos = m->rc_rows + 3 * m->rows_max;
+  std::fill(tab, tab + (size_t)3 * m->rows_max, 0);
+  for (int r = 0; r < rows; ++r) { tab[r] = slot[r]; tab[m->rows_max + r] = m->rc_nhist[slot[r]]; tab[2 * m->rows_max + r] = n_cand[r]; }
+  // the rows' positions are the caller's for the length of this call: the resident batch's rope_input_pos stays what it is
   int* const saved_pos = m->d_rope_pos; const bool saved_has = m->has_rope_pos;
   auto run = [&]() -> int {
-    hipStream_t s = m->stream;
-    HIP_CHECK(hipMemcpyAsync(m->rc_rows, h.data(), h.size() * 4, hipMemcpyHostToDevice, s));
-    HIP_CHECK(hipMemcpyAsync(d_pos, pos.data(), pos.size() * 4, hipMemcpyHostToDevice, s));
-    int* d_sel = (int*)m->gf;   // (as rsys_infer_select: room for every token of the batch)
-    HIP_CHECK(hipMemcpyAsync(d_sel, sel.data(), sel.size() * 4, hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(m->rc_rows, tab, (size_t)3 * m->rows_max * 4, hipMemcpyHostToDevice, m->stream));
     m->d_rope_pos = d_pos; m->has_rope_pos = true;
     m->rc_mode = 2;
     const float* f = nullptr;
-    RC(m->bf16_mode ? infer_rows_device<bf16>(m, 1, d_sel, ntok, m->delta, &f) : infer_rows_device<float>(m, 1, d_sel, ntok, m->delta, &f));
-    HIP_CHECK(hipStreamSynchronize(s));
+    RC(m->bf16_mode ? infer_rows_device<bf16>(m, 1, d_sel, ntok, d_out, &f) : infer_rows_device<float>(m, 1, d_sel, ntok, d_out, &f));
     return RSYS_OK;
   };
-  int rc = run();
+  const int rc = run();
   m->rc_mode = 0;
   m->d_rope_pos = saved_pos; m->has_rope_pos = saved_has;
   adapter_unbind_rows(m);
-  if (rc != RSYS_OK) { (void)hipStreamSynchronize(m->stream); return rc; }
+  if (rc != RSYS_OK) (void)hipStreamSynchronize(m->stream);
+  return rc;
+}
+
+int model_rank_cache_candidates(Model* m, const int32_t* row_adapter, const int32_t* slot, const int32_t* n_cand, float* out) {
+  int64_t ntok = 0;
+  RC(rc_check_candidates(m, slot, n_cand, &ntok));
+  ARG_CHECK(out != nullptr, "ranking cache: null output");
+  const int rows = m->cur_rows, T = m->T;
+  HIP_CHECK(hipSetDevice(m->device));
+  std::vector<int> tab((size_t)3 * m->rows_max), pos((size_t)rows * T), sel((size_t)ntok);
+  int64_t k = 0;
+  for (int r = 0; r < rows; ++r) {
+    const int nh = m->rc_nhist[slot[r]];
+    for (int i = 0; i < m->S; ++i) { pos[(size_t)r * T + 2 * i] = 2 * nh; pos[(size_t)r * T + 2 * i + 1] = 2 * nh + 1; }   // model.py:470-476 at rope_input_pos = n_hist
+    for (int j = 0; j < n_cand[r]; ++j) sel[k++] = r * T + 2 * j + 1;
+  }
+  // the rows' positions live in the cache's own buffer for the length of this call
+  int* const d_pos = m->rc_rows + 3 * m->rows_max;
+  int* const d_sel = (int*)m->gf;   // (as rsys_infer_select: room for every token of the batch)
+  hipStream_t s = m->stream;
+  auto run = [&]() -> int {
+    HIP_CHECK(hipMemcpyAsync(d_pos, pos.data(), pos.size() * 4, hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(d_sel, sel.data(), sel.size() * 4, hipMemcpyHostToDevice, s));
+    RC(rank_cache_candidates_rows(m, row_adapter, slot, n_cand, tab.data(), d_pos, d_sel, ntok, m->delta));
+    HIP_CHECK(hipStreamSynchronize(s));
+    return RSYS_OK;
+  };
+  const int rc = run();
+  if (rc != RSYS_OK) { (void)hipStreamSynchronize(s); return rc; }   // (the copies above read this call's host vectors)
   HIP_CHECK(hipMemcpy(out, m->delta, (size_t)ntok * 4, hipMemcpyDeviceToHost));   // (out is written only by a call that succeeded)
   return RSYS_OK;
 }

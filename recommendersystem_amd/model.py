@@ -720,6 +720,24 @@ class RecommenderModel:
         `adapter_slots` the bank slots of (0.retrieval, 0.ranking, 1.retrieval, 1.ranking) or None (base model); `histories` per user
         and `selected` per group as `retrieve_request` takes them; `coef_have` (2,) / `coefs` (2, 4) the registry's coefficients.
         Returns (one int32 page array per group, totals (n_groups,) int32)."""
+        return self._render_call(False, group_medium, offsets, limits, penalties, group, retrieval_rows, retrieval_token, ranking_prefix,
+                                 prefix_stride, user_desc, user_ts, adapter_slots, histories, selected, coef_have, coefs)
+
+    def render_request_full(self, group_medium, offsets, limits, penalties, group, retrieval_rows, retrieval_token, user_desc, user_ts,
+                            adapter_slots=None, histories=None, selected=None, coef_have=None, coefs=None):
+        """rsys_render_request_full: `render_request` with the ranking forward on full-length histories through the per-user K/V cache
+        (DESIGN.md 4w).  The same arguments without `ranking_prefix` / `prefix_stride`; `user_desc` = (n_hist, userid, gender, source)
+        with n_hist in [0, S - 1] = the history columns of the user's retrieval row (`serve.render_pack(..., full_history=True)`).  The
+        library reserves max_rows cache slots when the model's reserve is smaller than a wave's users."""
+        out = self._render_call(True, group_medium, offsets, limits, penalties, group, retrieval_rows, retrieval_token, None, 0, user_desc,
+                                user_ts, adapter_slots, histories, selected, coef_have, coefs)
+        with_hist = int((np.asarray(user_desc, np.int32).reshape(-1, 4)[:, 0] >= 1).sum())
+        if getattr(self, "rank_cache_slots", 0) < min(self.max_rows, with_hist):       # (the library reserved max_rows slots)
+            self.rank_cache_slots = self.max_rows
+        return out
+
+    def _render_call(self, full, group_medium, offsets, limits, penalties, group, retrieval_rows, retrieval_token, ranking_prefix, prefix_stride,
+                     user_desc, user_ts, adapter_slots, histories, selected, coef_have, coefs):
         gm = np.ascontiguousarray(group_medium, np.int32).reshape(-1)
         ng = gm.size
         off = np.ascontiguousarray(offsets, np.int64).reshape(-1)
@@ -731,7 +749,8 @@ class RecommenderModel:
             raise ValueError(f"render_request: offsets, limits and penalties need {ng} entries and {ng} x 4 values")
         S = self.config["max_sequence_length"]
         rb, keep_r = self._c_rows(retrieval_rows, nu, S)
-        pb, keep_p = self._c_rows(ranking_prefix, nu, int(prefix_stride))
+        if not full:
+            pb, keep_p = self._c_rows(ranking_prefix, nu, int(prefix_stride))
         tok = np.ascontiguousarray(retrieval_token, np.int32).reshape(-1)
         desc = np.ascontiguousarray(user_desc, np.int32).reshape(-1)
         ts = np.ascontiguousarray(user_ts, np.float64).reshape(-1)
@@ -761,6 +780,10 @@ class RecommenderModel:
         ptr = lambda a: None if a is None else a.ctypes.data
         hp = (None,) * 4 if h is None else tuple(ptr(a) for a in h)
         sp = (None,) * 3 if sel is None else tuple(ptr(a) for a in sel)
+        if full:
+            check(lib().rsys_render_request_full(self._h, ng, ptr(gm), ptr(off), ptr(lim), ptr(pen), nu, ptr(gp), C.byref(rb), ptr(tok), ptr(desc),
+                                                 ptr(ts), ptr(sl), *hp, *sp, ptr(ch), ptr(cf), ptr(ids), cap, ptr(ioff), ptr(total)))
+            return [ids[ioff[g]:ioff[g + 1]].copy() for g in range(ng)], total[:ng].copy()
         check(lib().rsys_render_request(self._h, ng, ptr(gm), ptr(off), ptr(lim), ptr(pen), nu, ptr(gp), C.byref(rb), ptr(tok), C.byref(pb),
                                         int(prefix_stride), ptr(desc), ptr(ts), ptr(sl), *hp, *sp, ptr(ch), ptr(cf), ptr(ids), cap, ptr(ioff),
                                         ptr(total)))

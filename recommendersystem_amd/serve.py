@@ -671,12 +671,14 @@ def render_row_plan(n_candidates, nh, S):
             for c0 in range(0, int(n_candidates), chunk)]
 
 
-def render_pack(states, pagination, S, num_items_0, registry=None, adapter_slots=None):
+def render_pack(states, pagination, S, num_items_0, registry=None, adapter_slots=None, full_history=False):
     """The arguments of `RecommenderModel.render_request` for render.jl request states (the states `render` takes; users need no
     "embeds"): every history is tokenised and projected once; from it come the user's retrieval row (`build_batch([user], "retrieval")`:
     the newest S - 1 tokens + the query token), the history part of its ranking rows (the first nh columns of `build_batch([user],
     "ranking")`: the newest S // 2 - 1 tokens) with the descriptor (nh, userid, gender, source) and timestamp the device completes them
-    from, its list items, and per state the selected items, penalties, pagination and medium."""
+    from, its list items, and per state the selected items, penalties, pagination and medium.  `full_history=True`: the arguments of
+    `RecommenderModel.render_request_full` instead -- no prefix arrays, and the descriptor's first entry is n_hist = len(hr), the history
+    columns of the retrieval row (the device cuts the cache's store rows from them)."""
     pags = [pagination] * len(states) if isinstance(pagination, dict) else list(pagination)
     if len(pags) != len(states):
         raise ValueError(f"render_users: {len(pags)} paginations for {len(states)} states")
@@ -712,7 +714,7 @@ def render_pack(states, pagination, S, num_items_0, registry=None, adapter_slots
         _fill_row(rows, i, hr + [make_item(user["timestamp"])], len(hr), who, num_items_0, False)
         _fill_row(prefix, i, hk, len(hk), who, num_items_0, True)
         tok[i] = 2 * len(hr)
-        desc[i] = (len(hk), 1, 0 if who["gender"] is None else who["gender"] + 1, who["source"])
+        desc[i] = (len(hr) if full_history else len(hk), 1, 0 if who["gender"] is None else who["gender"] + 1, who["source"])
         ts[i] = user["timestamp"]
         hist.append([(int(x["medium"]), int(x["matchedid"]), int(x["status"])) for x in user["items"]])
     have, coefs = np.zeros(2, np.int32), np.zeros((2, 4), np.float32)
@@ -725,20 +727,45 @@ def render_pack(states, pagination, S, num_items_0, registry=None, adapter_slots
     slots = None
     if adapter_slots:
         slots = [adapter_slots[f"{m}.{task}"] for m in (0, 1) for task in ("retrieval", "ranking")]
-    return dict(group_medium=gm, offsets=off, limits=lim, penalties=np.asarray(pen, np.float32).reshape(-1, 4), group=group,
-                retrieval_rows=rows, retrieval_token=tok, ranking_prefix=prefix, prefix_stride=P, user_desc=desc, user_ts=ts,
-                adapter_slots=slots, histories=hist, selected=sel, coef_have=have, coefs=coefs)
+    out = dict(group_medium=gm, offsets=off, limits=lim, penalties=np.asarray(pen, np.float32).reshape(-1, 4), group=group,
+               retrieval_rows=rows, retrieval_token=tok, ranking_prefix=prefix, prefix_stride=P, user_desc=desc, user_ts=ts,
+               adapter_slots=slots, histories=hist, selected=sel, coef_have=have, coefs=coefs)
+    if full_history:
+        del out["ranking_prefix"], out["prefix_stride"]
+    return out
 
 
-def render_users(model, states, pagination, registry=None):
+def render_full_plan(n_hist, n_cand, S, max_rows):
+    """Reference statement (tests and documentation; the library plans its rows itself): the ranking forwards rsys_render_request_full
+    runs for users -- in r_masked order: the users of medium-0 groups with a page, then those of medium 1 -- with `n_hist[i]` history
+    events and `n_cand[i]` >= 1 candidates.  Returns (waves, empty): `waves` = `rank_cache_plan` over the users with a history (user
+    indices are positions in that sub-list), `empty` = the assembled rows of the others as (user, first candidate, candidates), one per
+    `render_row_plan(n, 0, S)` chunk, users in order, which run in forwards of at most `max_rows` rows after the cached waves."""
+    hist = [i for i, h in enumerate(n_hist) if h >= 1]
+    waves = rank_cache_plan([n_hist[i] for i in hist], [n_cand[i] for i in hist], S, max_rows)
+    waves = [([(hist[u], sl, nh) for u, sl, nh in store], [[(hist[u], sl, c0, n, nh) for u, sl, c0, n, nh in b] for b in batches])
+             for store, batches in waves]
+    empty = [(i, c0, n) for i, h in enumerate(n_hist) if h < 1 for c0, n, _ in render_row_plan(n_cand[i], 0, S)]
+    return waves, empty
+
+
+def render_full_forwards(n_hist, n_cand, S, max_rows):
+    """(store forwards, candidate forwards, empty-history chunk forwards) of `render_full_plan`: what the library reports as "forwards.full" """
+    waves, empty = render_full_plan(n_hist, n_cand, S, max_rows)
+    return len(waves), sum(len(b) for _, b in waves), -(-len(empty) // max_rows)
+
+
+def render_users(model, states, pagination, registry=None, full_history=False):
     """`render` from raw histories in ONE device call (rsys_render_request): the same states, but users need no "embeds" -- the
     retrieval forward, `retrieval`, the page window, the ranking forward (every chunk row of every user, both media, in waves of the
     model's max_rows) and `ranking` + `reranking` run back to back on the device; only the pages and the totals come back.  A model built
     by `get_models` runs every row with the adapter of its "{medium}.{task}"; a plain model runs the base.  Returns one (ids of the
-    page, total) pair per state, as `render`."""
+    page, total) pair per state, as `render`.  `full_history=True` (rsys_render_request_full): the ranking forward of
+    `render(..., full_history=True)` inside the same call -- every user ranked on its newest S - 1 events through the per-user K/V cache,
+    whose store rows the device cuts from the retrieval rows it already holds; no ranking prefix is built or uploaded."""
     if not states:
         return []
     args = render_pack(states, pagination, model.config["max_sequence_length"], model.config["vocab_sizes"]["0_matchedid"], registry,
-                       getattr(model, "adapter_slots", None))
-    pages, totals = model.render_request(**args)
+                       getattr(model, "adapter_slots", None), full_history)
+    pages, totals = (model.render_request_full if full_history else model.render_request)(**args)
     return [(pages[g], int(totals[g])) for g in range(len(states))]

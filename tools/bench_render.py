@@ -16,6 +16,14 @@ medium what the two request bodies upload minus queries / candidates / r_masked,
 [+ adapter rows]; down: counts per medium and the pages).
 
     python tools/bench_render.py --out profiles/render_request_bench.json
+
+--full-history: the same set-up, three paths timed in the same process in alternating blocks -- (i) the staged
+full-history path (one serve.predict per user, then serve.render(..., full_history=True): unchanged code), (ii)
+serve.render_users(full_history=True) (one rsys_render_request_full call), (iii) serve.render_users() -- for users with --events and
+with 1000 events.  Forwards of (i) are counted at the wrapper (inference_select, rank_cache_store, rank_cache_candidates), of (ii) / (iii)
+by the library and compared with serve.render_full_forwards.  "bytes up" of (ii) is (iii)'s accounting minus the prefix arrays.
+
+    python tools/bench_render.py --full-history --out profiles/render_full_bench.json
 """
 import argparse
 import json
@@ -84,6 +92,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--reps", type=int, default=15)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--full-history", action="store_true", help="time the staged full-history path, render_users(full_history=True) and render_users()")
     a = ap.parse_args()
     import recommendersystem_amd as ra
     from recommendersystem_amd import serve, workload
@@ -147,6 +156,9 @@ def main():
         return serve.render(model, states, pag, registry)
 
     results = []
+    if a.full_history:
+        results = full_history_cases(a, model, V, registry, pag, rng)
+        cases = {}
     for name, states in cases.items():
         n_users = sum(len(st["users"]) for st in states)
         model.inference_select, model.retrieve_request, model.rank_request = count_select, count_ret, count_rank
@@ -183,6 +195,76 @@ def main():
     if a.out:
         with open(a.out, "w") as f:
             json.dump(results, f, indent=1)
+
+
+def full_history_cases(a, model, V, registry, pag, rng):
+    from recommendersystem_amd import serve
+    S = a.seq
+    results = []
+    calls = dict(n=0)
+    real = {k: getattr(model, k) for k in ("inference_select", "rank_cache_store", "rank_cache_candidates")}
+
+    def counted(fn):
+        def f(*p, **kw):
+            calls["n"] += 1
+            return fn(*p, **kw)
+        return f
+
+    def staged(states):
+        for st in states:
+            m = int(st["medium"])
+            for u in st["users"]:
+                u["embeds"] = {f"{m}.retrieval": serve.predict(model, [u["user"]], "retrieval", m)[0][f"{m}.retrieval"]}
+        return serve.render(model, states, pag, registry, full_history=True)
+
+    for events in sorted({a.events, 1000}):
+        cases = {"a_1_user": [make_state(rng, V, 0, 1, events)], "b_3_users": [make_state(rng, V, 0, 3, events)],
+                 "c_8_states": [make_state(rng, V, g % 2, 1 + g % 3, events) for g in range(8)]}
+        for name, states in cases.items():
+            n_users = sum(len(st["users"]) for st in states)
+            for k, fn in real.items():
+                setattr(model, k, counted(fn))
+            calls["n"] = 0
+            want = staged(states)
+            staged_forwards = calls["n"]
+            for k, fn in real.items():
+                setattr(model, k, fn)
+            got = serve.render_users(model, states, pag, registry, full_history=True)
+            fw, ff = model.render_kept("forwards").tolist(), model.render_kept("forwards.full").tolist()
+            split = serve.render_users(model, states, pag, registry)
+            fw_split = model.render_kept("forwards").tolist()
+            # the plan's forwards: users in r_masked order (medium 0's states, then medium 1's), every state has a page here
+            order = [u for m in (0, 1) for st, (_, total) in zip(states, got) if int(st["medium"]) == m and total for u in st["users"]]
+            nh = [len(serve._history(u["user"], S)) for u in order]
+            nc = [min(1024 - 1024 % pag["limit"], total) for m in (0, 1) for st, (_, total) in zip(states, got)
+                  if int(st["medium"]) == m and total for _ in st["users"]]
+            plan = list(serve.render_full_forwards(nh, nc, S, model.max_rows))
+            args = serve.render_pack(states, pag, S, V[0], registry, model.adapter_slots)
+            prefix = sum(v.nbytes for v in args["ranking_prefix"].values())
+            up_split = n_users * S * (9 * 4 + 8 + 18 * 4 + 8) + prefix + 2 * sum(12 * len(h) for h in args["histories"]) + n_users * (4 + 16 + 8)
+            t = {"staged_full": [], "render_users_full": [], "render_users": []}
+            fns = {"staged_full": lambda: staged(states), "render_users_full": lambda: serve.render_users(model, states, pag, registry, full_history=True),
+                   "render_users": lambda: serve.render_users(model, states, pag, registry)}
+            blocks = 3
+            for b in range(blocks):
+                for k in t:
+                    t[k] += timed(fns[k], a.warmup if b == 0 else 1, a.reps // blocks)
+            med = {k: float(np.median(v)) for k, v in t.items()}
+            iqr_staged = float(np.subtract(*np.percentile(t["staged_full"], [75, 25])))
+            res = dict(case=name, events=events, shape=a.shape, S=S, states=len(states), users=n_users, totals=[int(x) for _, x in got],
+                       same_pages_as_staged=bool(all(np.array_equal(x[0], y[0]) and x[1] == y[1] for x, y in zip(want, got))),
+                       same_pages_as_split=bool(all(np.array_equal(x[0], y[0]) for x, y in zip(split, got))),
+                       staged_full=dict(stats(t["staged_full"]), forwards=staged_forwards),
+                       render_users_full=dict(stats(t["render_users_full"]), forwards=sum(fw), forwards_retrieval=fw[0], forwards_store=ff[0],
+                                              forwards_candidates=ff[1], forwards_empty=ff[2], plan=plan, forwards_equal_plan=bool(ff == plan),
+                                              bytes_up=int(up_split - prefix)),
+                       render_users=dict(stats(t["render_users"]), forwards=sum(fw_split), bytes_up=int(up_split), prefix_bytes=int(prefix)),
+                       full_below_staged_by_more_than_iqr=bool(med["staged_full"] - med["render_users_full"] > iqr_staged),
+                       ratio_staged_over_full=round(med["staged_full"] / med["render_users_full"], 3),
+                       full_over_split_ms=round((med["render_users_full"] - med["render_users"]) * 1e3, 3))
+            results.append(res)
+            print(json.dumps(res), flush=True)
+    return results
 
 
 if __name__ == "__main__":
