@@ -217,9 +217,14 @@ int32_t rsys_render_request(rsys_model* h, int32_t n_groups, const int32_t* grou
                             const int32_t* sel_ids, const int32_t* coef_have, const float* coefs, int32_t* ids_out, int64_t ids_cap,
                             int64_t* ids_offsets, int32_t* total_out) {
   CHECK_HANDLE(h);
-  return model_render_request(h->m, n_groups, group_medium, offset, limit, penalties, n_users, group, retrieval_rows, retrieval_token,
-                              ranking_prefix, prefix_stride, user_desc, user_ts, adapter_slots, hist_offsets, hist_medium, hist_ids, hist_status,
-                              sel_offsets, sel_medium, sel_ids, coef_have, coefs, ids_out, ids_cap, ids_offsets, total_out);
+  RenderArgs a{};
+  a.full = false; a.ng = n_groups; a.group_medium = group_medium; a.offset = offset; a.limit = limit; a.penalties = penalties;
+  a.nu = n_users; a.group = group; a.rb = retrieval_rows; a.retrieval_token = retrieval_token; a.pb = ranking_prefix; a.P = prefix_stride;
+  a.user_desc = user_desc; a.user_ts = user_ts; a.slots = adapter_slots;
+  a.hist_off = hist_offsets; a.hist_medium = hist_medium; a.hist_ids = hist_ids; a.hist_status = hist_status;
+  a.sel_off = sel_offsets; a.sel_medium = sel_medium; a.sel_ids = sel_ids; a.coef_have = coef_have; a.coefs = coefs;
+  a.ids_out = ids_out; a.ids_cap = ids_cap; a.ids_offsets = ids_offsets; a.total_out = total_out;
+  return model_render(h->m, a);
 }
 int32_t rsys_render_request_full(rsys_model* h, int32_t n_groups, const int32_t* group_medium, const int64_t* offset, const int32_t* limit,
                                  const float* penalties, int64_t n_users, const int32_t* group, const rsys_batch* retrieval_rows,
@@ -228,9 +233,14 @@ int32_t rsys_render_request_full(rsys_model* h, int32_t n_groups, const int32_t*
                                  const int64_t* sel_offsets, const int32_t* sel_medium, const int32_t* sel_ids, const int32_t* coef_have,
                                  const float* coefs, int32_t* ids_out, int64_t ids_cap, int64_t* ids_offsets, int32_t* total_out) {
   CHECK_HANDLE(h);
-  return model_render_request_full(h->m, n_groups, group_medium, offset, limit, penalties, n_users, group, retrieval_rows, retrieval_token,
-                                   user_desc, user_ts, adapter_slots, hist_offsets, hist_medium, hist_ids, hist_status, sel_offsets, sel_medium,
-                                   sel_ids, coef_have, coefs, ids_out, ids_cap, ids_offsets, total_out);
+  RenderArgs a{};
+  a.full = true; a.ng = n_groups; a.group_medium = group_medium; a.offset = offset; a.limit = limit; a.penalties = penalties;
+  a.nu = n_users; a.group = group; a.rb = retrieval_rows; a.retrieval_token = retrieval_token; a.pb = nullptr; a.P = 0;
+  a.user_desc = user_desc; a.user_ts = user_ts; a.slots = adapter_slots;
+  a.hist_off = hist_offsets; a.hist_medium = hist_medium; a.hist_ids = hist_ids; a.hist_status = hist_status;
+  a.sel_off = sel_offsets; a.sel_medium = sel_medium; a.sel_ids = sel_ids; a.coef_have = coef_have; a.coefs = coefs;
+  a.ids_out = ids_out; a.ids_cap = ids_cap; a.ids_offsets = ids_offsets; a.total_out = total_out;
+  return model_render(h->m, a);
 }
 int32_t rsys_render_debug_keep(rsys_model* h, int32_t on) { CHECK_HANDLE(h); return render_debug_keep(h->m, on); }
 int32_t rsys_render_debug_get(rsys_model* h, const char* key, void* out, int64_t cap, int64_t* bytes) {

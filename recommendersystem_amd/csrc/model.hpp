@@ -414,21 +414,20 @@ int model_rank_request_dev(Model* m, int medium, int32_t ng, const int64_t* cand
                            const float* rating_coefs, float rating_mean);
 void rank_free(Model* m);
 // render_request.hip: a page from raw histories in one device pipeline (rsys_render_request) and its test hooks
-int model_render_request(Model* m, int32_t ng, const int32_t* group_medium, const int64_t* offset, const int32_t* limit, const float* penalties,
-                         int64_t nu, const int32_t* group, const rsys_batch* retrieval_rows, const int32_t* retrieval_token,
-                         const rsys_batch* ranking_prefix, int32_t prefix_stride, const int32_t* user_desc, const double* user_ts,
-                         const int32_t* adapter_slots, const int64_t* hist_off, const int32_t* hist_medium, const int32_t* hist_ids,
-                         const int32_t* hist_status, const int64_t* sel_off, const int32_t* sel_medium, const int32_t* sel_ids,
-                         const int32_t* coef_have, const float* coefs, int32_t* ids_out, int64_t ids_cap, int64_t* ids_offsets,
-                         int32_t* total_out);
-// the same page with the ranking forward on full-length histories through the K/V cache (rsys_render_request_full): no prefix arrays,
-// user_desc[u][0] = the history columns of retrieval row u
-int model_render_request_full(Model* m, int32_t ng, const int32_t* group_medium, const int64_t* offset, const int32_t* limit,
-                              const float* penalties, int64_t nu, const int32_t* group, const rsys_batch* rb, const int32_t* retrieval_token,
-                              const int32_t* user_desc, const double* user_ts, const int32_t* slots, const int64_t* hist_off,
-                              const int32_t* hist_medium, const int32_t* hist_ids, const int32_t* hist_status, const int64_t* sel_off,
-                              const int32_t* sel_medium, const int32_t* sel_ids, const int32_t* coef_have, const float* coefs,
-                              int32_t* ids_out, int64_t ids_cap, int64_t* ids_offsets, int32_t* total_out);
+// One request of rsys_render_request (full == false) or rsys_render_request_full (full == true: the ranking forward on full-length
+// histories through the K/V cache; pb == nullptr, P == 0, user_desc[u][0] = the history columns of retrieval row u).  The fields are
+// the C functions' arguments in their order: rb = retrieval_rows, pb / P = ranking_prefix / prefix_stride, slots = adapter_slots.
+struct RenderArgs {
+  bool full;
+  int32_t ng; const int32_t* group_medium; const int64_t* offset; const int32_t* limit; const float* penalties;
+  int64_t nu; const int32_t* group; const rsys_batch* rb; const int32_t* retrieval_token; const rsys_batch* pb; int32_t P;
+  const int32_t* user_desc; const double* user_ts; const int32_t* slots;
+  const int64_t* hist_off; const int32_t *hist_medium, *hist_ids, *hist_status;
+  const int64_t* sel_off; const int32_t *sel_medium, *sel_ids;
+  const int32_t* coef_have; const float* coefs;
+  int32_t* ids_out; int64_t ids_cap; int64_t* ids_offsets; int32_t* total_out;
+};
+int model_render(Model* m, const RenderArgs& a);
 int render_debug_keep(Model* m, int on);
 int render_debug_get(Model* m, const char* key, void* out, int64_t cap, int64_t* bytes);
 void render_free(Model* m);

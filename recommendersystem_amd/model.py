@@ -780,13 +780,10 @@ class RecommenderModel:
         ptr = lambda a: None if a is None else a.ctypes.data
         hp = (None,) * 4 if h is None else tuple(ptr(a) for a in h)
         sp = (None,) * 3 if sel is None else tuple(ptr(a) for a in sel)
-        if full:
-            check(lib().rsys_render_request_full(self._h, ng, ptr(gm), ptr(off), ptr(lim), ptr(pen), nu, ptr(gp), C.byref(rb), ptr(tok), ptr(desc),
-                                                 ptr(ts), ptr(sl), *hp, *sp, ptr(ch), ptr(cf), ptr(ids), cap, ptr(ioff), ptr(total)))
-            return [ids[ioff[g]:ioff[g + 1]].copy() for g in range(ng)], total[:ng].copy()
-        check(lib().rsys_render_request(self._h, ng, ptr(gm), ptr(off), ptr(lim), ptr(pen), nu, ptr(gp), C.byref(rb), ptr(tok), C.byref(pb),
-                                        int(prefix_stride), ptr(desc), ptr(ts), ptr(sl), *hp, *sp, ptr(ch), ptr(cf), ptr(ids), cap, ptr(ioff),
-                                        ptr(total)))
+        prefix = () if full else (C.byref(pb), int(prefix_stride))
+        fn = lib().rsys_render_request_full if full else lib().rsys_render_request
+        check(fn(self._h, ng, ptr(gm), ptr(off), ptr(lim), ptr(pen), nu, ptr(gp), C.byref(rb), ptr(tok), *prefix, ptr(desc), ptr(ts), ptr(sl),
+                 *hp, *sp, ptr(ch), ptr(cf), ptr(ids), cap, ptr(ioff), ptr(total)))
         return [ids[ioff[g]:ioff[g + 1]].copy() for g in range(ng)], total[:ng].copy()
 
     _RENDER_KEPT = {"time": np.float64, "rating": np.float32, "progress": np.float32, "queries": np.float32, "r_masked": np.float32,

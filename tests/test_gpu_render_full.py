@@ -470,7 +470,41 @@ def test_reproducible():
     model.close()
 
 
-# ---------------------------------------------------------------- 9. errors leave the outputs untouched
+# ---------------------------------------------------------------- 9. the assembly's column loop past one workgroup's width
+def test_assembly_past_one_workgroup_of_columns():
+    """S = 320: more columns than the 256 threads of a row's workgroup and no multiple of them, so the assembly kernel's column loop takes
+    a second, partial step.  Past column 256 it copies history columns only in the store rows of rsys_render_request_full (n_hist = 319);
+    a split row's prefix holds at most S // 2 - 1 = 159 columns and the windows here hold fewer than 97 candidates, so in
+    rsys_render_request, and in the candidate rows, the second step writes the zero columns behind the candidates.  One state per
+    medium, each with a user of more than S events (n_hist = S - 1: more than 256 history columns are copied), one of 10 events and one
+    of none; fp32, base model, max_rows 4.  Both entry points: the store, candidate and batch rows and the token indices bit for bit
+    against serve._fill_row / build_batch (`_check_assembly`, test_gpu_render_request._check_request)."""
+    from oracle import synth
+    from recommendersystem_amd import serve
+    cfg = synth.make_config("hd64", mask_rate=0.2, mask_topk=4, max_sequence_length=320)
+    cfg["forward"] = "inference"
+    cfg["vocab_sizes"] = dict(cfg["vocab_sizes"], **{"0_matchedid": 400, "1_matchedid": 600})   # (candidates are left beside 319 events)
+    V = (400, 600)
+    S = cfg["max_sequence_length"]
+    assert S > 256 and S % 256
+    model, _, _ = trc._model(cfg, "base", "fp32", max_rows=4)
+    related = _tables(model, V)
+    rng = np.random.default_rng(91)
+    pen = dict(decay=0.9, mmr_penalty=0.2, same_series_penalty=0.4, related_penalty=-0.3)
+    states = [dict(medium=m, items=[], penalties=pen, users=[_wrap(make_user(rng, n, [], V)) for n in (S + 20, 10, 0)]) for m in (0, 1)]
+    assert [len(serve._history(u["user"], S)) for st in states for u in st["users"]] == [S - 1, 10, 0] * 2
+    pags = [{"offset": 0, "limit": 10}] * 2
+    out, k = _run(model, cfg, states, pags, None)
+    _check_assembly(model, cfg, V, states, pags, out, k)
+    assert k["store_rows"][:, 2].max() == S - 1 > 256                                           # history columns past 256 are copied
+    assert (k["rows"][:, 6] == 0).any() and (k["rows"][:, 6] == 1).any()
+    out = serve.render_users(model, states, pags, None)
+    ks = trr._check_request(model, cfg, V, related, states, pags, None, "fp32", out)
+    assert ks["rows"].shape[0] >= 6 and ks["batch"]["time"].shape == (ks["rows"].shape[0], S)
+    model.close()
+
+
+# ---------------------------------------------------------------- 10. errors leave the outputs untouched
 def _raw(model, args, ids_cap=None):
     """rsys_render_request_full on sentinel-filled outputs: (return code, outputs untouched)"""
     from recommendersystem_amd import _lib

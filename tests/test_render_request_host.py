@@ -99,7 +99,7 @@ def test_render_users_packs_rows_prefixes_and_descriptors():
 @pytest.mark.parametrize("S_", [16, 64, 1024])
 def test_row_plan_chunks(S_):
     """`serve.render_row_plan` is the REFERENCE statement of the row plan, not the code that runs: the library plans the rows itself
-    (model_render_request), and tests/test_gpu_render_request.py checks the rows it actually ran against this plan, at 1024 candidates
+    (model_render), and tests/test_gpu_render_request.py checks the rows it actually ran against this plan, at 1024 candidates
     too.  Here the reference is checked on its own terms -- descriptors and chunk counts for 0, 1, S - S // 2, S - S // 2 + 1 and 1024: every candidate in exactly one row,
     rows of at most S - S // 2 candidates that fit behind the longest history, action tokens as serve._selected_tokens gives them"""
     from recommendersystem_amd import serve
