@@ -53,6 +53,35 @@ int32_t rsys_op_gemm_rows(int32_t dtype, const void* A, const void* B, void* C, 
  * (model.py:153-170 backward); rows >= *k_dev may hold anything */
 int32_t rsys_op_gemm_klimit(int32_t dtype, const void* A, const void* B, void* C, int32_t M, int32_t N, int32_t K,
                             int64_t lda, int64_t ldb, int64_t ldc, int32_t accumulate, const int32_t* k_dev);
+/* one launch_gemm call with any fused epilogue but EPI_ATOMIC (GemmEpi, csrc/gemm.hpp: 0 store, 1 accumulate, 3 bias, 4 residual, 5 QKV +
+ * RoPE, 6 SwiGLU, 7 table, 8 GELU, 9 SwiGLU backward), row-major A, one K split; synchronises.  Fields as in GemmParams; T = the dtype.
+ *   A [M][lda >= K], B [N][ldb >= K] or with b_km [K][ldb >= N], T-typed, 16-byte aligned, rows padded to 16 bytes.
+ *   C [M][ldc]: fp32 when c_f32 != 0 and always for epi 1, 4 and 7, else T-typed; ldc % 4 == 0 (T = bf16 outputs: % 8).  Only columns
+ *     < N of rows < M are written (epi 9: columns < 2 N); with m_dev see below.
+ *   alpha: epi 0 and 5 store alpha * acc (the register epilogues take alpha != 1 for epi 0 only).  accum != 0: epi 0 / 5 with a T-typed
+ *     C add the result to what C holds (the 128x128 kernel only).
+ *   bias [N] f32: epi 3 C = acc + bias; epi 7; epi 8.      resid [M][ldr] f32: epi 4 C = resid + acc.      epi 1: C += acc.
+ *   epi 6: N % 32 == 0, the columns come in blocks [16 a | 16 b]; C = the [a|b] values as they are, C2 [M][ldc2 >= N / 2] (T) =
+ *     silu(a) b, block u of 16 columns from the u-th [a|b] block.
+ *   epi 9: N % 16 == 0 is the width of acc = dg; C2 [M][ldc2] (T, ldc2 == ldc) holds the saved [a|b] blocks (2 N columns), C (T) gets
+ *     [da|db] in the same blocks: da = dg b s (1 + a (1 - s)), db = dg a s, s = sigmoid(a).
+ *   epi 7: f = acc + E + bias with E [M][...] f32 READ WITH STRIDE ldc (it has no stride of its own); C (fp32) = f, C2 [M][ldc2] (T) = f.
+ *   epi 8: z = acc + bias; C (T) = z, C2 [M][ldc2] (T) = z (1 + erf(z / sqrt 2)) / 2.
+ *   epi 5: columns [0, n_q) are q, [n_q, n_q + n_k) k, the rest v; q and k are whole heads of hd columns (hd a power of two >= 16) and
+ *     each interleaved pair (x0, x1) = columns (2 d, 2 d + 1) of a head becomes (x0 c - x1 s, x0 s + x1 c) with c = rope_cos[pos][d],
+ *     s = rope_sin[pos][d] (tables [positions][hd / 2] f32); pos = rope_pos[row] (int32 [M], values inside the tables) or, when null,
+ *     row % T.  rope_cs: the same values as [pos][hd / 2][2] = (cos, sin); the 256x256 family needs it and reads ONLY it (without it
+ *     the product runs on the 128x128 kernel, which reads only the two plain tables).  The register epilogue rotates the v columns
+ *     too, with table row 0: ROW 0 MUST BE (cos 1, sin 0) -- position 0 of a true RoPE table.
+ *   m_dev (device int, may be null): tiles whose first row is >= *m_dev are not computed; rows < min(*m_dev, M) are written, rows up to
+ *     the end of the last started tile (128 rows; 256 in gemm8p and gemm8c's full form) may be, later rows are untouched.
+ * It fills no fp8 field.  `tag` gets the timing tag of the kernel that ran (as rsys_debug_gemm_route) and *half whether that was gemm8c
+ * in its HALF form (128 x 256 tiles), both decided by the code launch_gemm runs, from the RSYS_GEMM* switches as the call parsed them. */
+int32_t rsys_op_gemm_epi(int32_t dtype, const void* A, const void* B, void* C, int32_t M, int32_t N, int32_t K, int64_t lda,
+                         int64_t ldb, int64_t ldc, int32_t b_km, int32_t c_f32, int32_t epi, float alpha, int32_t accum,
+                         const float* bias, const float* resid, int64_t ldr, void* C2, int64_t ldc2, const float* E,
+                         const float* rope_cos, const float* rope_sin, const float* rope_cs, const int32_t* rope_pos, int32_t T,
+                         int32_t hd, int32_t n_q, int32_t n_k, const int32_t* m_dev, char* tag, int32_t tag_bytes, int32_t* half);
 /* the kernel launch_gemm would run for this problem, decided on the host without launching anything: `tag` gets its timing tag
  * ("nt", "nn", "tn", "8p", "8c", "4p", "8t", "4k", "8ts", "8s", "8m"), `splits` the K-split count it runs with.  Fields as in
  * GemmParams (csrc/gemm.hpp); `set` says which pointer fields the problem has: bit 0 m_dev, 1 k_dev, 2 slab, 3 rope_cs, 4 rope_pos,

@@ -191,6 +191,9 @@ _SIGS = [
     ("rsys_op_gemm_rows", C.c_int32, [C.c_int32, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64,
                                       C.c_int32, C.c_int32, _P]),
     ("rsys_op_gemm_klimit", C.c_int32, [C.c_int32, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int32, _P]),
+    ("rsys_op_gemm_epi", C.c_int32, [C.c_int32, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32,
+                                     C.c_int32, C.c_float, C.c_int32, _P, _P, C.c_int64, _P, C.c_int64, _P, _P, _P, _P, _P,
+                                     C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, C.c_char_p, C.c_int32, C.POINTER(C.c_int32)]),
     ("rsys_debug_gemm_route", C.c_int32, [C.c_int32] * 4 + [C.c_int64] * 3 + [C.c_int32] * 7 + [C.c_float] + [C.c_int32] * 4
                                           + [C.c_char_p, C.c_int32, C.POINTER(C.c_int32)]),
     ("rsys_op_attention", C.c_int32, [C.c_int32] + [C.c_int32] * 5 + [_P] * 9),

@@ -817,6 +817,39 @@ int32_t rsys_op_gemm_klimit(int32_t dtype, const void* A, const void* B, void* C
   return RSYS_OK;
 }
 
+int32_t rsys_op_gemm_epi(int32_t dtype, const void* A, const void* B, void* C, int32_t M, int32_t N, int32_t K, int64_t lda,
+                         int64_t ldb, int64_t ldc, int32_t b_km, int32_t c_f32, int32_t epi, float alpha, int32_t accum,
+                         const float* bias, const float* resid, int64_t ldr, void* C2, int64_t ldc2, const float* E,
+                         const float* rope_cos, const float* rope_sin, const float* rope_cs, const int32_t* rope_pos, int32_t T,
+                         int32_t hd, int32_t n_q, int32_t n_k, const int32_t* m_dev, char* tag, int32_t tag_bytes, int32_t* half) {
+  switches_parse();
+  ARG_CHECK(dtype == RSYS_DTYPE_BF16 || dtype == RSYS_DTYPE_FP32, "rsys_op_gemm_epi: dtype is fp32 or bf16");
+  ARG_CHECK(A != nullptr && B != nullptr && C != nullptr, "rsys_op_gemm_epi: null operand");
+  ARG_CHECK(tag != nullptr && tag_bytes >= 4 && half != nullptr, "rsys_op_gemm_epi: null output");
+  ARG_CHECK(epi >= EPI_STORE && epi <= EPI_SWIGLU_BWD && epi != EPI_ATOMIC, "rsys_op_gemm_epi: epilogue is one of GemmEpi without EPI_ATOMIC");
+  // the operands an epilogue dereferences (the launchers take them on trust)
+  if (epi == EPI_BIAS || epi == EPI_TABLE || epi == EPI_GELU) ARG_CHECK(bias != nullptr, "rsys_op_gemm_epi: this epilogue reads bias");
+  if (epi == EPI_RESIDUAL) ARG_CHECK(resid != nullptr, "rsys_op_gemm_epi: EPI_RESIDUAL reads resid");
+  if (epi == EPI_TABLE) ARG_CHECK(E != nullptr, "rsys_op_gemm_epi: EPI_TABLE reads E");
+  if (epi == EPI_SWIGLU || epi == EPI_TABLE || epi == EPI_GELU || epi == EPI_SWIGLU_BWD) ARG_CHECK(C2 != nullptr, "rsys_op_gemm_epi: this epilogue needs C2");
+  if (epi == EPI_QKV_ROPE) ARG_CHECK(rope_cos != nullptr && rope_sin != nullptr, "rsys_op_gemm_epi: EPI_QKV_ROPE reads rope_cos / rope_sin");
+  GemmParams p{};
+  p.A = A; p.B = B; p.C = C; p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldb = ldb; p.ldc = ldc;
+  p.c_f32 = c_f32 != 0; p.splitk = 1; p.epi = epi; p.alpha = alpha; p.accum = accum != 0;
+  p.bias = bias; p.resid = resid; p.ldr = ldr; p.C2 = C2; p.ldc2 = ldc2; p.E = E;
+  p.rope_cos = rope_cos; p.rope_sin = rope_sin; p.rope_cs = rope_cs; p.rope_pos = rope_pos; p.T = T; p.hd = hd; p.n_q = n_q; p.n_k = n_k;
+  p.m_dev = m_dev;
+  const bool bf = dtype == RSYS_DTYPE_BF16;
+  int rc = bf ? launch_gemm<bf16>(p, false, false, false, b_km != 0, nullptr) : launch_gemm<float>(p, false, false, false, b_km != 0, nullptr);
+  if (rc) return rc;
+  HIP_CHECK(hipDeviceSynchronize());
+  // what launch_gemm just decided, from the same parameters and switches
+  const GemmRoute r = bf ? gemm_route<bf16>(p, false, false, false, b_km != 0, cu_count()) : gemm_route<float>(p, false, false, false, b_km != 0, cu_count());
+  snprintf(tag, tag_bytes, "%s", gemm_kernel_tags[r.kernel]);
+  *half = r.kernel == GK_8C && gemm8c_uses_half(p, cu_count()) ? 1 : 0;
+  return RSYS_OK;
+}
+
 // the routing of launch_gemm, on the host only: a GemmParams from the fields the route reads (pointer fields only as set / unset)
 int32_t rsys_debug_gemm_route(int32_t dtype, int32_t M, int32_t N, int32_t K, int64_t lda, int64_t ldb, int64_t ldc, int32_t a_km,
                               int32_t b_km, int32_t a_f32, int32_t c_f32, int32_t epi, int32_t splitk, int32_t flags, float alpha,

@@ -591,7 +591,10 @@ int launch_gemm(const GemmParams& p0, bool a_f32, bool b_f32, bool a_km, bool b_
   if (!b_km) ARG_CHECK(p.ldb >= ((p.K + EPC - 1) / EPC) * EPC, "gemm: row-major B rows must be padded to a whole chunk");
   else ARG_CHECK(p.ldb >= ((p.N + EPC - 1) / EPC) * EPC, "gemm: K-major B rows must be padded to a whole chunk");
   if (p.epi == EPI_QKV_ROPE)
-    ARG_CHECK(p.hd % 16 == 0 && p.N % 4 == 0 && p.n_q % 4 == 0 && p.n_k % 4 == 0, "gemm: rope epilogue needs hd % 16 == 0");
+    // whole heads per region: an epilogue item (4 or 8 consecutive columns) then never straddles the q / k / v boundaries or a head
+    ARG_CHECK(p.hd >= 16 && p.hd % 16 == 0 && p.N % 4 == 0 && p.n_q >= 0 && p.n_k >= 0 && p.n_q % p.hd == 0 && p.n_k % p.hd == 0 &&
+                  p.n_q + p.n_k <= p.N && (p.rope_pos != nullptr || p.T > 0),
+              "gemm: rope epilogue needs hd % 16 == 0, q and k regions of whole heads inside N, and T > 0 or rope_pos");
   if (p.epi == EPI_SWIGLU) ARG_CHECK(p.N % 32 == 0 && p.ldc2 % 4 == 0, "gemm: swiglu epilogue needs N % 32 == 0");
   if (p.epi == EPI_SWIGLU_BWD) ARG_CHECK(p.N % 16 == 0 && p.ldc2 == p.ldc && ((uintptr_t)p.C2 % 16) == 0, "gemm: swiglu-bwd epilogue needs N % 16 == 0");
   ARG_CHECK(p.ldc % 4 == 0 && ((uintptr_t)p.C % 16) == 0, "gemm: C rows must keep 16-byte alignment (ldc % 4 == 0)");

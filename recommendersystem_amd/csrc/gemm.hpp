@@ -122,5 +122,7 @@ int launch_gemm8p_f8_splitk(const GemmParams& p, hipStream_t s);
 
 // timing tag of the kernel launch_gemm runs for this problem (gemm_kernel_tags)
 const char* gemm_kernel_name(const GemmParams& p, bool bf16_mode, bool a_f32, bool b_f32, bool a_km, bool b_km);
+// whether gemm8c (GK_8C) runs this problem in its HALF form, 128 x 256 output tiles (gemm8c.hip; RSYS_GEMM8C_HALF)
+bool gemm8c_uses_half(const GemmParams& p, int cus);
 
 }  // namespace rsys
