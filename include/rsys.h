@@ -195,6 +195,46 @@ int32_t rsys_retrieve_request(rsys_model* m, int32_t medium,
                               const int32_t* sel_medium, const int32_t* sel_ids,
                               int32_t k, int32_t* ids_out, float* scores_out, /* [n_groups][k] each */
                               int32_t* counts_out);                           /* [n_groups] */
+/* rsys_retrieve_request for any rank range: per group the items whose rank in the request's ordering (descending score, ties by ascending
+ * id, -0.0 as +0.0, NaN and -inf inadmissible) lies in [win_start[g], win_start[g] + win_len[g]), 1 <= win_len <= 1024, and the exact
+ * number of admissible items -- what render.jl:450-463 needs for `total` and for a page at any offset.  The arguments of
+ * rsys_retrieve_request with k replaced by the windows.  A group may have no queries, and n_queries may be 0 with queries == NULL: 1 <=
+ * n_groups <= 4096, not bounded by n_queries.  A group without queries (render.jl:243-252, a state without users) is scored by the prior
+ * p_g alone, in the same fp32 arithmetic (+0.0 everywhere without selected items), under the item-0, selected-item and released masks; it
+ * has no relation masks.  Groups with queries get bit for bit the scores of rsys_retrieve_request.
+ * Output: ids_out / scores_out [n_groups][1024], best first, slots past counts_out[g] = clamp(total_g - win_start[g], 0, win_len[g]) hold
+ * -1 / -inf; total_out[g] = the admissible items of group g.  Device candidate storage is n_groups x 1024 whatever win_start is.  Tables:
+ * as rsys_retrieve_request, but the relation tables only when n_queries > 0, and neither the item table nor a forward when n_queries == 0.
+ * Synchronous, bitwise reproducible, no side effects.  RSYS_ERR_ARG (outputs untouched): win_len outside [1, 1024], win_start < 0, and
+ * whatever rsys_retrieve_request rejects. */
+int32_t rsys_retrieve_window(rsys_model* m, int32_t medium,
+                             const float* queries, int64_t n_queries,        /* [n_queries][embed_dim] f32, or NULL with n_queries == 0 */
+                             const int32_t* group, int32_t n_groups,         /* [n_queries] in [0, n_groups), or NULL: group = query */
+                             const int64_t* hist_offsets,                    /* [n_queries + 1] CSR over queries, or NULL (no lists) */
+                             const int32_t* hist_medium, const int32_t* hist_ids, const int32_t* hist_status,
+                             const int64_t* sel_offsets,                     /* [n_groups + 1] CSR over groups, or NULL (none selected) */
+                             const int32_t* sel_medium, const int32_t* sel_ids,
+                             const int64_t* win_start, const int32_t* win_len, /* [n_groups] each */
+                             int32_t* ids_out, float* scores_out,            /* [n_groups][1024] each */
+                             int32_t* counts_out, int32_t* total_out);       /* [n_groups] each */
+/* A page for states without users in one device pipeline (Inference/compute.jl:490-514 `/add_item` + render.jl:437-474):
+ * "pick a title, see similar titles".  Group g, media mixed: group_medium[g], pagination (offset[g] >= 0, 1 <= limit[g] <= 1024),
+ * penalties[g][4] as rsys_rank_request, selected items as CSR over groups in the shape of rsys_retrieve_request (NULL: none).  Per group:
+ * the window of render.jl:448-463 from the exact total (mitr = 1024 - 1024 % limit, start = offset / mitr * mitr, mitr ranks, clamped to
+ * the total), rsys_retrieve_window without queries, then the reranking of rsys_rank_request on r = +0.0 (render.jl:354) without related
+ * flags, partialk = the page's last index.  Candidates stay on the device; counts, pages and totals come back.
+ * Output as rsys_render_request, except that total_out[g] is exact (the admissible items, not capped at 8192) and a page exists for every
+ * offset below it; a page starting at or past the total is empty.  Needs the similarity table of every medium involved (and the
+ * crossproject of the other medium when a selected item crosses media) and the related table; no relation tables, no item table, no
+ * forward.  Any dtype.  Synchronous, bitwise reproducible; the resident batch, parameters, gradients and optimizer state are not touched.
+ * RSYS_ERR_ARG (outputs untouched): a bad medium, limit outside [1, 1024], offset < 0, malformed offsets, ids out of range, missing
+ * tables, ids_cap below the sum of the limits. */
+int32_t rsys_render_items(rsys_model* m, int32_t n_groups,
+                          const int32_t* group_medium, const int64_t* offset, const int32_t* limit,   /* [n_groups] each */
+                          const float* penalties,                                  /* [n_groups][4] */
+                          const int64_t* sel_offsets,                              /* [n_groups + 1] CSR over groups, or NULL (none selected) */
+                          const int32_t* sel_medium, const int32_t* sel_ids,
+                          int32_t* ids_out, int64_t ids_cap, int64_t* ids_offsets, int32_t* total_out);
 /* "{m}.related" of Inference/render.jl's reranking (the franchise relation, V_m x V_m) for rsys_rank_request: 0-based CSC in Julia's column
  * order, with the contract and validation of rsys_retrieve_relations_set (colptr[n + 1], colptr[0] = 0, non-decreasing; rowval in [0, n);
  * stored values finite and >= 0, else an ARG error; explicitly stored zeros are dropped).  n must be V_m.  NULL colptr clears the table.

@@ -310,6 +310,47 @@ function retrieve_request(m::Model, medium::Integer, Q::Matrix{Float32}, k::Inte
         m.h, medium, Q, size(Q, 2), g, n_groups, hoff, hmed, hid, hst, soff, smed, sid, k, ids, scores, counts))
     ids, scores, counts
 end
+# the ranks [start[g], start[g] + len[g]) (0-based, 1 <= len <= 1024) of each group's ordering and its exact admissible count
+# (rsys_retrieve_window).  Q (D, n_queries) or nothing (no queries: states without users); a group may have no queries.  Returns
+# (ids (1024, n_groups), scores (1024, n_groups), counts, totals).
+function retrieve_window(m::Model, medium::Integer, Q, start, len; group = nothing, n_groups::Integer = length(start), hist = nothing,
+                         sel = nothing)
+    q = Q === nothing ? Ptr{Float32}(C_NULL) : Matrix{Float32}(Q)
+    nq = Q === nothing ? 0 : size(q, 2)
+    g = group === nothing ? Ptr{Int32}(C_NULL) : Vector{Int32}(group)
+    hoff = hist === nothing ? Ptr{Int64}(C_NULL) : Int64[0; cumsum(Int64[length(h) for h in hist])]
+    hmed = hist === nothing ? Ptr{Int32}(C_NULL) : Int32[x[1] for h in hist for x in h]
+    hid = hist === nothing ? Ptr{Int32}(C_NULL) : Int32[x[2] for h in hist for x in h]
+    hst = hist === nothing ? Ptr{Int32}(C_NULL) : Int32[x[3] for h in hist for x in h]
+    soff = sel === nothing ? Ptr{Int64}(C_NULL) : Int64[0; cumsum(Int64[length(a) for a in sel])]
+    smed = sel === nothing ? Ptr{Int32}(C_NULL) : Int32[x[1] for a in sel for x in a]
+    sid = sel === nothing ? Ptr{Int32}(C_NULL) : Int32[x[2] for a in sel for x in a]
+    ws = Vector{Int64}(start); wl = Vector{Int32}(len)
+    (length(ws) == n_groups && length(wl) == n_groups) || error("retrieve_window: one start and one length per group")
+    ids = Matrix{Int32}(undef, 1024, n_groups); scores = Matrix{Float32}(undef, 1024, n_groups)
+    counts = Vector{Int32}(undef, n_groups); totals = Vector{Int32}(undef, n_groups)
+    GC.@preserve q g hoff hmed hid hst soff smed sid ws wl ids scores counts totals check(ccall((:rsys_retrieve_window, LIB), Int32,
+        (Ptr{Cvoid}, Int32, Ptr{Float32}, Int64, Ptr{Int32}, Int32, Ptr{Int64}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Int64}, Ptr{Int32},
+         Ptr{Int32}, Ptr{Int64}, Ptr{Int32}, Ptr{Int32}, Ptr{Float32}, Ptr{Int32}, Ptr{Int32}),
+        m.h, medium, q, nq, g, n_groups, hoff, hmed, hid, hst, soff, smed, sid, ws, wl, ids, scores, counts, totals))
+    ids, scores, counts, totals
+end
+# a page per state without users (compute.jl:490-514 `/add_item`; rsys_render_items): per group medium, offset, limit, penalties (4 x ng);
+# sel[g] = [(medium, id), ...] or nothing.  Returns (page ids per group, exact totals).
+function render_items(m::Model, medium, offset, limit, penalties::Matrix{Float32}; sel = nothing)
+    gm = Vector{Int32}(medium); ng = length(gm)
+    off = Vector{Int64}(offset); lim = Vector{Int32}(limit)
+    soff = sel === nothing ? Ptr{Int64}(C_NULL) : Int64[0; cumsum(Int64[length(s) for s in sel])]
+    smed = sel === nothing ? Ptr{Int32}(C_NULL) : Int32[x[1] for s in sel for x in s]
+    sid = sel === nothing ? Ptr{Int32}(C_NULL) : Int32[x[2] for s in sel for x in s]
+    cap = sum(Int64.(lim))
+    ids = Vector{Int32}(undef, max(cap, 1)); ioff = Vector{Int64}(undef, ng + 1); total = Vector{Int32}(undef, ng)
+    GC.@preserve gm off lim penalties soff smed sid ids ioff total check(ccall((:rsys_render_items, LIB), Int32,
+        (Ptr{Cvoid}, Int32, Ptr{Int32}, Ptr{Int64}, Ptr{Int32}, Ptr{Float32}, Ptr{Int64}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Int64, Ptr{Int64},
+         Ptr{Int32}),
+        m.h, ng, gm, off, lim, penalties, soff, smed, sid, ids, cap, ioff, total))
+    [ids[ioff[j]+1:ioff[j+1]] for j in 1:ng], total
+end
 # ranking and reranking of retrieved candidates (Inference/render.jl:335-435): "{m}.related" as a SparseMatrixCSC (V_m x V_m) or nothing
 # to clear; it is held on the device beside the retrieval tables
 function rank_related_set(m::Model, medium::Integer, A)

@@ -79,6 +79,8 @@ _SIGS = [
     ("rsys_retrieve_similarity_set", C.c_int32, [_P, C.c_int32, C.c_int64, _P, _P]),
     ("rsys_retrieve_released_set", C.c_int32, [_P, C.c_int32, _P]),
     ("rsys_retrieve_request", C.c_int32, [_P, C.c_int32, _P, C.c_int64, _P, C.c_int32, _P, _P, _P, _P, _P, _P, _P, C.c_int32, _P, _P, _P]),
+    ("rsys_retrieve_window", C.c_int32, [_P, C.c_int32, _P, C.c_int64, _P, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    ("rsys_render_items", C.c_int32, [_P, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int64, _P, _P]),
     ("rsys_rank_related_set", C.c_int32, [_P, C.c_int32, C.c_int64, _P, _P, _P]),
     ("rsys_rank_request", C.c_int32, [_P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, C.c_int64, _P, _P, C.c_int64, _P, _P, _P, _P, _P, _P,
                                       C.c_float, _P, _P, _P]),

@@ -196,6 +196,22 @@ int32_t rsys_retrieve_request(rsys_model* h, int32_t medium, const float* querie
   return model_retrieve_request(h->m, medium, queries, n_queries, group, n_groups, hist_offsets, hist_medium, hist_ids, hist_status,
                                 sel_offsets, sel_medium, sel_ids, k, ids_out, scores_out, counts_out);
 }
+int32_t rsys_retrieve_window(rsys_model* h, int32_t medium, const float* queries, int64_t n_queries, const int32_t* group, int32_t n_groups,
+                             const int64_t* hist_offsets, const int32_t* hist_medium, const int32_t* hist_ids, const int32_t* hist_status,
+                             const int64_t* sel_offsets, const int32_t* sel_medium, const int32_t* sel_ids, const int64_t* win_start,
+                             const int32_t* win_len, int32_t* ids_out, float* scores_out, int32_t* counts_out, int32_t* total_out) {
+  CHECK_HANDLE(h);
+  const RetrieveWin win{win_start, win_len, total_out};
+  return model_retrieve_window(h->m, medium, queries, n_queries, group, n_groups, hist_offsets, hist_medium, hist_ids, hist_status,
+                               sel_offsets, sel_medium, sel_ids, &win, nullptr, ids_out, scores_out, counts_out);
+}
+int32_t rsys_render_items(rsys_model* h, int32_t n_groups, const int32_t* group_medium, const int64_t* offset, const int32_t* limit,
+                          const float* penalties, const int64_t* sel_offsets, const int32_t* sel_medium, const int32_t* sel_ids,
+                          int32_t* ids_out, int64_t ids_cap, int64_t* ids_offsets, int32_t* total_out) {
+  CHECK_HANDLE(h);
+  return model_render_items(h->m, n_groups, group_medium, offset, limit, penalties, sel_offsets, sel_medium, sel_ids, ids_out, ids_cap,
+                            ids_offsets, total_out);
+}
 int32_t rsys_rank_related_set(rsys_model* h, int32_t medium, int64_t n, const int64_t* colptr, const int32_t* rowval, const float* nzval) {
   CHECK_HANDLE(h);
   return model_rank_related_set(h->m, medium, n, colptr, rowval, nzval);

@@ -370,8 +370,12 @@ int model_retrieve_topk(Model* m, int medium, const float* queries, int64_t nq, 
 // the same pipeline with a device-side initialiser of the group score rows sc [n_groups][V_m] (prior and NaN masks)
 using RetrieveInit = std::function<int(float* sc, hipStream_t s)>;
 struct RetrieveDev;
+// win != nullptr (rsys_retrieve_window): instead of the top k, the ranks [start[g], start[g] + len[g]) of group g's ordering, 1 <= len <=
+// 1024, in rows of 1024 (k is not read); total_out[g] = the group's admissible items; groups may be empty and nq may be 0
+struct RetrieveWin { const int64_t* start; const int32_t* len; int32_t* total_out; };
 int model_retrieve_run(Model* m, int medium, const float* queries, int64_t nq, const int32_t* group, int32_t ng, const RetrieveInit& init,
-                       int32_t k, int32_t* ids_out, float* scores_out, int32_t* counts_out, RetrieveDev* dev = nullptr);
+                       int32_t k, int32_t* ids_out, float* scores_out, int32_t* counts_out, RetrieveDev* dev = nullptr,
+                       const RetrieveWin* win = nullptr);
 // z = Q F_m^T and lse of one chunk of <= RETRIEVE_CHUNK query rows (part: nc * RETRIEVE_LSE_SPLIT float2), as rsys_retrieve_topk scores
 constexpr int RETRIEVE_CHUNK = 256, RETRIEVE_LSE_SPLIT = 64;
 template <typename T>
@@ -393,6 +397,12 @@ struct RetrieveDev { const float* d_queries = nullptr; int32_t* d_ids = nullptr;
 int model_retrieve_request_dev(Model* m, int medium, RetrieveDev* dev, int64_t nq, const int32_t* group, int32_t ng, const int64_t* hist_off,
                                const int32_t* hist_medium, const int32_t* hist_ids, const int32_t* hist_status, const int64_t* sel_off,
                                const int32_t* sel_medium, const int32_t* sel_ids, int32_t k, int32_t* counts_out);
+// rsys_retrieve_window: the request above with a window of each group's ordering instead of its top k (RetrieveWin); dev == nullptr: the
+// rows [ng][1024] go to ids_out / scores_out (host), else they stay on the device as after model_retrieve_request_dev
+int model_retrieve_window(Model* m, int medium, const float* queries, int64_t nq, const int32_t* group, int32_t ng, const int64_t* hist_off,
+                          const int32_t* hist_medium, const int32_t* hist_ids, const int32_t* hist_status, const int64_t* sel_off,
+                          const int32_t* sel_medium, const int32_t* sel_ids, const RetrieveWin* win, RetrieveDev* dev, int32_t* ids_out,
+                          float* scores_out, int32_t* counts_out);
 const float* retrieve_similarity_table(Model* m, int medium, int64_t* dim);   // "embeddings.{m}" [V_m][dim] on the device, or null
 // rank_request.hip: ranking and diversity reranking of retrieved candidates (rsys_rank_related_set, rsys_rank_request, test hooks)
 int model_rank_related_set(Model* m, int medium, int64_t n, const int64_t* colptr, const int32_t* rowval, const float* nzval);
@@ -412,6 +422,9 @@ int model_rank_request_dev(Model* m, int medium, int32_t ng, const int64_t* cand
                            const float* penalties, int64_t nu, const int32_t* group, int64_t n_rm, const int64_t* hist_off,
                            const int32_t* hist_medium, const int32_t* hist_ids, const int32_t* hist_status, const float* retrieval_coef,
                            const float* rating_coefs, float rating_mean);
+// reranking alone on device candidates (rsys_render_items: a state without users): r = +0.0 for every candidate, no related flags
+int model_rank_items_dev(Model* m, int medium, int32_t ng, const int64_t* cand_off, const RankDev* dev, const int32_t* partialk,
+                         const float* penalties);
 void rank_free(Model* m);
 // render_request.hip: a page from raw histories in one device pipeline (rsys_render_request) and its test hooks
 // One request of rsys_render_request (full == false) or rsys_render_request_full (full == true: the ranking forward on full-length
@@ -428,6 +441,10 @@ struct RenderArgs {
   int32_t* ids_out; int64_t ids_cap; int64_t* ids_offsets; int32_t* total_out;
 };
 int model_render(Model* m, const RenderArgs& a);
+// rsys_render_items: a page per user-less state (windowed retrieval on the prior, reranking) in one device pipeline
+int model_render_items(Model* m, int32_t ng, const int32_t* group_medium, const int64_t* offset, const int32_t* limit, const float* penalties,
+                       const int64_t* sel_off, const int32_t* sel_medium, const int32_t* sel_ids, int32_t* ids_out, int64_t ids_cap,
+                       int64_t* ids_offsets, int32_t* total_out);
 int render_debug_keep(Model* m, int on);
 int render_debug_get(Model* m, const char* key, void* out, int64_t cap, int64_t* bytes);
 void render_free(Model* m);

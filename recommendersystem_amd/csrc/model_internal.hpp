@@ -335,9 +335,10 @@ template <typename T> struct ScoreBufs {
 template <typename T> int score_upload_queries(const ScoreBufs<T>& b, const float* queries, int64_t nq, hipMemcpyKind kind, hipStream_t s);
 template <typename T> int score_table_ready(Model* m, int medium, const T** Fm);
 // The queries of each group in query order (members[goff[g] .. goff[g + 1])) and, per chunk c of `chunk` queries, the part of them it
-// holds (ranges[c * ng + g]); group == nullptr: query q is group q.  Fails on a group id outside [0, ng) and on an empty group.
+// holds (ranges[c * ng + g]); group == nullptr: query q is group q.  Fails on a group id outside [0, ng) and, unless allow_empty, on an
+// empty group.
 struct GroupPlan { std::vector<int> goff, members; std::vector<int2> ranges; int nchunks = 0; };
-int group_plan(const char* who, const int32_t* group, int64_t nq, int ng, int chunk, GroupPlan& gp);
+int group_plan(const char* who, const int32_t* group, int64_t nq, int ng, int chunk, GroupPlan& gp, bool allow_empty = false);
 // Ragged lists of a request (offsets [n + 1] and parallel arrays): the words their error texts are built from
 struct ListKind { const char *given, *offsets, *media, *ids; };
 constexpr ListKind LIST_HISTORY{"the history arrays are all given or all NULL", "hist_offsets", "list items' media must be 0 or 1",

@@ -574,6 +574,16 @@ int model_rank_request_dev(Model* m, int medium, int32_t ng, const int64_t* cand
                            hist_ids, hist_status, retrieval_coef, rating_coefs, rating_mean, nullptr, nullptr, nullptr, dev);
 }
 
+int model_rank_items_dev(Model* m, int medium, int32_t ng, const int64_t* cand_off, const RankDev* dev, const int32_t* partialk,
+                         const float* penalties) {
+  ARG_CHECK(dev && dev->d_cand && dev->page_lo && dev->page_hi && dev->page_off && dev->page_out && cand_off, "render_items: null device buffers");
+  ARG_CHECK(ng >= 1 && ng <= RK_MAXQ, "render_items: 1 <= n_groups <= 4096");
+  // render.jl:354 ranks a state without users as zeros; one user without a list per group stands in for its (absent) users
+  const std::vector<float> zeros((size_t)std::max<int64_t>(cand_off[ng], 1), 0.f);
+  return rank_request_body(m, medium, ng, cand_off, nullptr, partialk, penalties, nullptr, ng, nullptr, nullptr, 0, nullptr, nullptr, nullptr,
+                           nullptr, nullptr, nullptr, 0.f, zeros.data(), nullptr, nullptr, dev);
+}
+
 int model_rank_gram(Model* m, int medium, int32_t ng, const int64_t* cand_off, const int32_t* cand_ids, float* out, int64_t n_out) {
   ARG_CHECK(medium == 0 || medium == 1, "rank_gram: medium must be 0 or 1");
   ARG_CHECK(ng >= 1 && out, "rank_gram: n_groups >= 1 and an output buffer");

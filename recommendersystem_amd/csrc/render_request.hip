@@ -19,6 +19,8 @@
 // Every batch a ranking forward reads is filled by rows_kernel from row descriptors (RowDesc), one workgroup per row, one launch per wave;
 // rank_wave is the one forward over such rows: rating head at the candidates' action tokens, rank_scatter_kernel puts the values into the
 // ragged r_masked layout of rsys_rank_request.
+// rsys_render_items (model_render_items) is the same page for states without users: no forward, the windowed
+// retrieval of rsys_retrieve_window on the prior alone, window_kernel, then the reranking of rsys_rank_request on zeros.
 #include <algorithm>
 #include <array>
 #include <cmath>
@@ -681,6 +683,98 @@ int model_render(Model* m, const RenderArgs& a) {
   const int rc = c.run_stages();
   if (rc != RSYS_OK) (void)hipStreamSynchronize(c.s);   // (copies a failed stage has enqueued read the context's host tables)
   return rc;
+}
+
+// rsys_render_items.  Per medium: the window of render.jl:448-463 from each group's offset (the same arithmetic as page_window, before
+// the total is known: the window's first rank does not depend on it), rsys_retrieve_window without queries, the windows gathered into
+// one candidate list, the reranking of rsys_rank_request on zeros.  Outputs are written once both media have succeeded.
+int model_render_items(Model* m, int32_t ng, const int32_t* group_medium, const int64_t* offset, const int32_t* limit, const float* penalties,
+                       const int64_t* sel_off, const int32_t* sel_medium, const int32_t* sel_ids, int32_t* ids_out, int64_t ids_cap,
+                       int64_t* ids_offsets, int32_t* total_out) {
+  ARG_CHECK(ng >= 1 && ng <= RN_MAXQ, "render_items: 1 <= n_groups <= 4096");
+  ARG_CHECK(group_medium && offset && limit && penalties && ids_out && ids_offsets && total_out, "render_items: null argument");
+  RC(check_ragged("render_items", LIST_SELECTED, sel_off, ng, {sel_medium, sel_ids}));
+  int64_t need_ids = 0;
+  std::vector<int> groups_m[2];
+  for (int g = 0; g < ng; ++g) {
+    ARG_CHECK(group_medium[g] == 0 || group_medium[g] == 1, "render_items: medium must be 0 or 1");
+    ARG_CHECK(limit[g] >= 1 && limit[g] <= RN_MAX_RANK, "render_items: 1 <= limit <= 1024");
+    ARG_CHECK(offset[g] >= 0, "render_items: offset >= 0");
+    need_ids += limit[g];
+    groups_m[group_medium[g]].push_back(g);
+  }
+  ARG_CHECK(ids_cap >= need_ids, "render_items: ids_out must hold the sum of the limits");
+  for (int mm = 0; mm < 2; ++mm) {   // the tables of the reranking, before anything runs (the retrieval checks its own)
+    if (groups_m[mm].empty()) continue;
+    int64_t dim = 0;
+    ARG_CHECK(retrieve_similarity_table(m, mm, &dim) != nullptr, "render_items: the item-similarity embeddings of the medium are not loaded");
+  }
+  HIP_CHECK(hipSetDevice(m->device));
+  hipStream_t s = m->stream;
+  RenderState* R = render_state(m);
+  int32_t* cand; Win* d_win;
+  RC(carve_into(R->ws, s, [&](Carve& c) {
+    cand = c.take<int32_t>((size_t)ng * RN_MAX_RANK);
+    d_win = c.take<Win>(ng);
+  }));
+  std::vector<int32_t> total(ng, 0);
+  std::vector<std::vector<int32_t>> pages(ng);
+  for (int mm = 0; mm < 2; ++mm) {
+    const std::vector<int>& gs = groups_m[mm];
+    if (gs.empty()) continue;
+    const int ngm = (int)gs.size();
+    std::vector<int64_t> wstart(ngm);
+    std::vector<int32_t> wlen(ngm), counts(ngm), totals(ngm);
+    for (int j = 0; j < ngm; ++j) {
+      const int mitr = RN_MAX_RANK - RN_MAX_RANK % limit[gs[j]];
+      wstart[j] = offset[gs[j]] / mitr * mitr;
+      wlen[j] = mitr;
+    }
+    SubCsr sl;
+    if (sel_off) sub_csr(gs, sel_off, sel_medium, sel_ids, nullptr, sl);
+    const RetrieveWin win{wstart.data(), wlen.data(), totals.data()};
+    RetrieveDev rd;
+    RC(model_retrieve_window(m, mm, nullptr, 0, nullptr, ngm, nullptr, nullptr, nullptr, nullptr, sel_off ? sl.off.data() : nullptr,
+                             sel_off ? sl.a.data() : nullptr, sel_off ? sl.b.data() : nullptr, &win, &rd, nullptr, nullptr, counts.data()));
+    std::vector<Win> wins;
+    std::vector<int> act;
+    std::vector<int64_t> coff(1, 0), poff;
+    std::vector<int32_t> pk, plo, phi;
+    std::vector<float> pen;
+    int64_t np = 0;
+    for (int j = 0; j < ngm; ++j) {
+      const int g = gs[j];
+      total[g] = totals[j];
+      int start, stop, sidx, eidx;
+      if (!page_window(totals[j], offset[g], limit[g], &start, &stop, &sidx, &eidx)) continue;
+      // (start == wstart[j] and stop - start == counts[j]: the retrieval clamped the same window)
+      wins.push_back({j * RN_MAX_RANK, counts[j], (int)coff.back()});
+      coff.push_back(coff.back() + counts[j]);
+      act.push_back(g);
+      const int last = std::min(eidx, counts[j]);   // (an offset that is no multiple of the limit may end the page past the ranked slice)
+      pk.push_back(eidx); plo.push_back(sidx - 1); phi.push_back(last); poff.push_back(np); np += last - (sidx - 1);
+      pen.insert(pen.end(), penalties + 4 * (size_t)g, penalties + 4 * (size_t)g + 4);
+    }
+    if (act.empty()) continue;
+    const int na = (int)act.size();
+    HIP_CHECK(hipMemcpyAsync(d_win, wins.data(), wins.size() * sizeof(Win), hipMemcpyHostToDevice, s));
+    window_kernel<<<(unsigned)na, RN_THREADS, 0, s>>>(d_win, rd.d_ids, cand);
+    RN_LAUNCH_CHECK();
+    std::vector<int32_t> page((size_t)np);
+    const RankDev rk{cand, nullptr, nullptr, plo.data(), phi.data(), poff.data(), page.data(), nullptr, nullptr};
+    const int rc = model_rank_items_dev(m, mm, na, coff.data(), &rk, pk.data(), pen.data());
+    if (rc != RSYS_OK) { (void)hipStreamSynchronize(s); return rc; }   // (the copy of `wins` may be in flight)
+    for (int a = 0; a < na; ++a) pages[act[a]].assign(page.begin() + poff[a], page.begin() + poff[a] + (phi[a] - plo[a]));
+  }
+  int64_t at = 0;
+  for (int g = 0; g < ng; ++g) {
+    ids_offsets[g] = at;
+    if (!pages[g].empty()) memcpy(ids_out + at, pages[g].data(), pages[g].size() * 4);
+    at += (int64_t)pages[g].size();
+    total_out[g] = total[g];
+  }
+  ids_offsets[ng] = at;
+  return RSYS_OK;
 }
 
 }  // namespace rsys

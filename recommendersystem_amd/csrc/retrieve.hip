@@ -12,6 +12,8 @@
 //              exclusive prefix of per-workgroup counts over workgroup order (no atomics: independent of scheduling)
 //   sort       bitonic sort of <= 8192 (key, id) pairs per group in LDS: descending key, then ascending id; -1 / -inf padding
 // Every launch covers all groups (grid = blocks x groups); the host waits once, after the copy out.
+// rsys_retrieve_window replaces select / compact / sort by their windowed forms (win_*_kernel): two rank bounds
+// per group, the items between them, a sort of <= 1024 pairs -- any 1024 ranks of the ordering in n_groups x 1024 candidate slots.
 #include <cmath>
 
 #include "model_internal.hpp"
@@ -26,6 +28,7 @@ constexpr int RT_CHUNK = 256;         // query rows per score GEMM
 constexpr int RT_LSE_SPLIT = 64;      // workgroups per row of the log-sum-exp
 constexpr int RT_MAXK = 8192;         // candidates per group: the sort's LDS holds 8192 x 8 B = 64 KiB
 constexpr int RT_MAXQ = 4096;
+constexpr int RT_WIN = 1024;          // ranks of one window (rsys_retrieve_window): one per lane of the window sort, 8 KiB of LDS
 
 // selection state of one group: keys with (key & rmask) > prefix are taken, keys with (key & rmask) == prefix are ties of which the
 // first `need` in ascending id order are taken; total = min(k, admissible) = the group's output count
@@ -313,6 +316,203 @@ __global__ void __launch_bounds__(1024) sort_out_kernel(const unsigned long long
   if (threadIdx.x == 0) counts[g] = n;
 }
 
+
+// ---- windowed selection (rsys_retrieve_window): the items of ranks [start, start + len) of the same ordering, len <= RT_WIN, as
+// (top-stop) minus (top-start) with stop = min(start + len, total).  Each of the two rank bounds is resolved by the radix select
+// above to an exact pair (T, need): the top-c set is every key above T plus the first `need` keys equal to T in ascending id order.
+// st[g] is the bound of the window's end (c = stop), st[ng + g] that of its start (c = min(start, total)); prefix holds T, rmask is
+// full once the bound is exact.  c == 0 is T = 0xffffffff (no score has that key), c == total is T = 0 (every admissible key is above).
+// The candidate list of a group holds the window only: [n_groups][RT_WIN] whatever `start` is.
+
+__device__ __forceinline__ int win_count(int adm, long long start, int len) {
+  const long long left = (long long)adm - start;
+  return left <= 0 ? 0 : (int)(left < len ? left : len);
+}
+
+// digit pass `pass` of both bounds of group blockIdx.x (wave 0: the end, wave 1: the start).  hist rows [0, ng) hold the end's
+// histograms and, in pass 0, the first-digit histogram both bounds start from; rows [ng, 2 ng) the start's.  A bound whose bin is
+// taken whole falls between two keys: T = the bin's smallest key - 1, need = 0.
+__global__ void __launch_bounds__(RT_THREADS) win_select_step_kernel(unsigned* hist, SelState* st, const long long* wstart, const int* wlen,
+                                                                     int ng, int pass) {
+  const int g = blockIdx.x;
+  __shared__ unsigned c[2][256];
+  c[0][threadIdx.x] = hist[g * 256 + threadIdx.x];
+  c[1][threadIdx.x] = pass == 0 ? c[0][threadIdx.x] : hist[(ng + g) * 256 + threadIdx.x];
+  hist[g * 256 + threadIdx.x] = 0;
+  hist[(ng + g) * 256 + threadIdx.x] = 0;
+  __syncthreads();
+  if (lane_id() != 0 || threadIdx.x >= 128) return;
+  const int bound = threadIdx.x >> 6;
+  const unsigned* cb = c[bound];
+  SelState* S = st + bound * ng + g;
+  SelState t = *S;
+  if (pass > 0 && t.done) return;
+  if (pass == 0) {
+    unsigned adm = 0;
+    for (int b = 0; b < 256; ++b) adm += cb[b];
+    const long long s0 = wstart[g];
+    const int lo = s0 < (long long)adm ? (int)s0 : (int)adm;
+    const int cnt = bound == 0 ? lo + win_count((int)adm, s0, wlen[g]) : lo;
+    t.total = (int)adm; t.need = 0; t.rmask = 0xffffffffu; t.done = 1;
+    t.pad0 = t.pad1 = t.pad2 = 0;
+    if (cnt <= 0) { t.prefix = 0xffffffffu; *S = t; return; }
+    if (cnt >= (int)adm) { t.prefix = 0u; *S = t; return; }
+    t.prefix = 0; t.rmask = 0; t.done = 0; t.need = cnt;
+  }
+  const int shift = 24 - 8 * pass;
+  unsigned cum = 0;
+  int b = 255;
+  for (; b > 0; --b) {
+    if (cum + cb[b] >= (unsigned)t.need) break;
+    cum += cb[b];
+  }
+  t.prefix |= (unsigned)b << shift;
+  t.rmask |= 0xffu << shift;
+  t.need -= (int)cum;
+  if (shift == 0) {
+    t.done = 1;
+  } else if (cb[b] == (unsigned)t.need) {
+    t.prefix = (t.prefix ? t.prefix : 1u) - 1u; t.rmask = 0xffffffffu; t.need = 0; t.done = 1;
+  }
+  *S = t;
+}
+
+// one read of the keys for both bounds: histogram of digit (key >> shift) & 255 over the keys matching each open bound's prefix
+__global__ void __launch_bounds__(RT_THREADS) win_hist_pass_kernel(const unsigned* keys, long long ldk, int V, const SelState* st, int ng,
+                                                                   int shift, unsigned* hist) {
+  const int g = blockIdx.y;
+  const SelState A = st[g], B = st[ng + g];
+  if (A.done && B.done) return;
+  __shared__ unsigned h[2][256];
+  h[0][threadIdx.x] = 0; h[1][threadIdx.x] = 0;
+  __syncthreads();
+  const unsigned* kg = keys + g * ldk;
+  const long long base = (long long)blockIdx.x * RT_ITEMS;
+  for (int j = 0; j < RT_ITEMS / RT_THREADS; ++j) {
+    const long long i = base + j * RT_THREADS + threadIdx.x;
+    const unsigned key = i < V ? kg[i] : 0u;
+    const unsigned digit = (key >> shift) & 0xffu;
+    if (!A.done) hist_add_wave(h[0], digit, is_tie(key, A));
+    if (!B.done) hist_add_wave(h[1], digit, is_tie(key, B));
+  }
+  __syncthreads();
+  if (h[0][threadIdx.x]) atomicAdd(&hist[g * 256 + threadIdx.x], h[0][threadIdx.x]);
+  if (h[1][threadIdx.x]) atomicAdd(&hist[(ng + g) * 256 + threadIdx.x], h[1][threadIdx.x]);
+}
+
+// the three classes a window's items come from, for a key and the two thresholds TS <= TB (end, start)
+__device__ __forceinline__ bool win_between(unsigned key, unsigned TS, unsigned TB) { return key > TS && key < TB; }
+__device__ __forceinline__ bool win_at(unsigned key, unsigned T) { return key != 0u && key == T; }
+
+// cnt[g][blockIdx.x] = {keys strictly between the thresholds, keys equal to the start's, keys equal to the end's} of this workgroup
+__global__ void __launch_bounds__(RT_THREADS) win_count_kernel(const unsigned* keys, long long ldk, int V, const SelState* st, int ng, int4* cnt) {
+  const int g = blockIdx.y;
+  const unsigned TS = st[g].prefix, TB = st[ng + g].prefix;
+  const unsigned* kg = keys + g * ldk;
+  const long long base = (long long)blockIdx.x * RT_ITEMS;
+  int nw = 0, nb = 0, ns = 0;
+  for (int j = 0; j < RT_ITEMS / RT_THREADS; ++j) {
+    const long long i = base + j * RT_THREADS + threadIdx.x;
+    const unsigned key = i < V ? kg[i] : 0u;
+    nw += win_between(key, TS, TB) ? 1 : 0;
+    nb += win_at(key, TB) ? 1 : 0;
+    ns += win_at(key, TS) ? 1 : 0;
+  }
+  __shared__ int sm[RT_THREADS / 64];
+  const int w = block_sum_int(nw, sm);
+  const int b = block_sum_int(nb, sm);
+  const int s = block_sum_int(ns, sm);
+  if (threadIdx.x == 0) cnt[(long long)g * gridDim.x + blockIdx.x] = make_int4(w, b, s, 0);
+}
+
+// the window's candidate list cand[g][0 .. n): [0, W) the keys strictly between the thresholds (W = their number), then the keys equal
+// to the start's threshold whose tie rank (ascending id) is >= the start's need, then those equal to the end's whose tie rank is < the
+// end's need; one threshold for both: the ties of rank [need_start, need_end).  Every slot is an exclusive prefix over workgroup
+// order, waves and lanes, as in compact_kernel: no atomics.  The sort orders the list, so the order of the classes does not matter.
+__global__ void __launch_bounds__(RT_THREADS) win_compact_kernel(const unsigned* keys, long long ldk, int V, const SelState* st, int ng,
+                                                                 const long long* wstart, const int* wlen, const int4* cnt,
+                                                                 unsigned long long* cand) {
+  const int g = blockIdx.y, nblk = gridDim.x;
+  const SelState SS = st[g], SB = st[ng + g];
+  const unsigned TS = SS.prefix, TB = SB.prefix;
+  const int n = win_count(SS.total, wstart[g], wlen[g]);
+  if (n == 0) return;
+  const bool same = TS == TB;
+  const unsigned* kg = keys + g * ldk;
+  unsigned long long* cg = cand + (long long)g * RT_WIN;
+  __shared__ int sm[RT_THREADS / 64];
+  __shared__ int ww[RT_THREADS / 64], wb[RT_THREADS / 64], ws[RT_THREADS / 64];
+  int pw = 0, pb = 0, ps = 0, aw = 0, ab = 0;   // before this workgroup; over all workgroups
+  for (int b = threadIdx.x; b < nblk; b += RT_THREADS) {
+    const int4 c = cnt[(long long)g * nblk + b];
+    if (b < blockIdx.x) { pw += c.x; pb += c.y; ps += c.z; }
+    aw += c.x; ab += c.y;
+  }
+  int wbase = block_sum_int(pw, sm);
+  int bbase = block_sum_int(pb, sm);
+  int sbase = block_sum_int(ps, sm);
+  const int W = block_sum_int(aw, sm);
+  const int tail_b = W - SB.need;                                  // slot of the start's tie of rank r: tail_b + r
+  const int tail_s = W + block_sum_int(ab, sm) - SB.need;          // slot of the end's tie of rank r: tail_s + r
+  const int w = threadIdx.x >> 6, lane = lane_id();
+  const unsigned long long lt = (1ull << lane) - 1ull;
+  const long long base = (long long)blockIdx.x * RT_ITEMS;
+  for (int j = 0; j < RT_ITEMS / RT_THREADS; ++j) {
+    const long long i = base + j * RT_THREADS + threadIdx.x;
+    const unsigned key = i < V ? kg[i] : 0u;
+    const bool inw = win_between(key, TS, TB), atb = win_at(key, TB), ats = win_at(key, TS);
+    const unsigned long long bw = __ballot(inw), bb = __ballot(atb), bs = __ballot(ats);
+    if (lane == 0) { ww[w] = __popcll(bw); wb[w] = __popcll(bb); ws[w] = __popcll(bs); }
+    __syncthreads();
+    int ow = wbase, ob = bbase, os = sbase, tw = 0, tb = 0, ts = 0;
+    for (int v = 0; v < RT_THREADS / 64; ++v) {
+      if (v < w) { ow += ww[v]; ob += wb[v]; os += ws[v]; }
+      tw += ww[v]; tb += wb[v]; ts += ws[v];
+    }
+    __syncthreads();
+    int slot = -1;
+    if (inw) {
+      slot = ow + __popcll(bw & lt);
+    } else if (atb) {
+      const int r = ob + __popcll(bb & lt);
+      if (r >= SB.need && (!same || r < SS.need)) slot = same ? r - SB.need : tail_b + r;
+    } else if (ats) {
+      const int r = os + __popcll(bs & lt);
+      if (r < SS.need) slot = tail_s + r;
+    }
+    if (slot >= 0 && slot < n) cg[slot] = cand_pack(key, i);   // (slot < n always: the bounds counted exactly n members)
+    wbase += tw; bbase += tb; sbase += ts;
+  }
+}
+
+// sort group g's window (descending key, ascending id), one candidate per lane, and write ids / scores / count / total with -1 / -inf padding
+__global__ void __launch_bounds__(RT_WIN) win_sort_kernel(const unsigned long long* cand, const SelState* st, const long long* wstart,
+                                                          const int* wlen, int* ids, float* vals, int* counts, int* totals) {
+  const int g = blockIdx.x, i = threadIdx.x;
+  const int adm = st[g].total;
+  const int n = win_count(adm, wstart[g], wlen[g]);
+  __shared__ unsigned long long s[RT_WIN];
+  s[i] = i < n ? cand[(long long)g * RT_WIN + i] : 0ull;
+  __syncthreads();
+  int N2 = 1;
+  while (N2 < n) N2 <<= 1;
+  for (int size = 2; size <= N2; size <<= 1) {
+    for (int stride = size >> 1; stride > 0; stride >>= 1) {
+      if (i < N2 / 2) {
+        const int lo = 2 * stride * (i / stride) + (i % stride), hi = lo + stride;
+        const bool desc = (lo & size) == 0;
+        const unsigned long long a = s[lo], b = s[hi];
+        if ((a < b) == desc) { s[lo] = b; s[hi] = a; }
+      }
+      __syncthreads();
+    }
+  }
+  const unsigned long long v = s[i];
+  ids[(long long)g * RT_WIN + i] = i < n ? (int)(0xffffffffu - (unsigned)v) : -1;
+  vals[(long long)g * RT_WIN + i] = i < n ? key_score((unsigned)(v >> 32)) : -INFINITY;
+  if (i == 0) { counts[g] = n; totals[g] = adm; }
+}
+
 #define RT_LAUNCH_CHECK() HIP_CHECK(hipGetLastError())
 
 // device buffers of the selection stage
@@ -341,6 +541,29 @@ int topk_select(const unsigned* keys, long long ldk, int rows, int V, int k, con
   compact_kernel<<<grid, RT_THREADS, 0, s>>>(keys, ldk, V, b.st, b.cnt, b.cand, b.ldc);
   RT_LAUNCH_CHECK();
   sort_out_kernel<<<rows, 1024, 0, s>>>(b.cand, b.ldc, b.st, k, ids, vals, counts);
+  RT_LAUNCH_CHECK();
+  return RSYS_OK;
+}
+
+// the window [wstart[g], wstart[g] + wlen[g]) of every row's ordering on keys [rows][ldk] whose first-digit histogram is in rows
+// [0, rows) of b.hist ([2 rows][256], the rest zero); b.st [2 rows], b.cnt [rows][nb] int4, b.cand [rows][RT_WIN]
+int window_select(const unsigned* keys, long long ldk, int rows, int V, const long long* wstart, const int* wlen, const SelBufs& b, int* ids,
+                  float* vals, int* counts, int* totals, hipStream_t s) {
+  const int nb = (V + RT_ITEMS - 1) / RT_ITEMS;
+  const dim3 grid(nb, rows);
+  win_select_step_kernel<<<rows, RT_THREADS, 0, s>>>(b.hist, b.st, wstart, wlen, rows, 0);
+  RT_LAUNCH_CHECK();
+  for (int pass = 1; pass < 4; ++pass) {
+    win_hist_pass_kernel<<<grid, RT_THREADS, 0, s>>>(keys, ldk, V, b.st, rows, 24 - 8 * pass, b.hist);
+    RT_LAUNCH_CHECK();
+    win_select_step_kernel<<<rows, RT_THREADS, 0, s>>>(b.hist, b.st, wstart, wlen, rows, pass);
+    RT_LAUNCH_CHECK();
+  }
+  win_count_kernel<<<grid, RT_THREADS, 0, s>>>(keys, ldk, V, b.st, rows, (int4*)b.cnt);
+  RT_LAUNCH_CHECK();
+  win_compact_kernel<<<grid, RT_THREADS, 0, s>>>(keys, ldk, V, b.st, rows, wstart, wlen, (const int4*)b.cnt, b.cand);
+  RT_LAUNCH_CHECK();
+  win_sort_kernel<<<rows, RT_WIN, 0, s>>>(b.cand, b.st, wstart, wlen, ids, vals, counts, totals);
   RT_LAUNCH_CHECK();
   return RSYS_OK;
 }
@@ -393,7 +616,7 @@ int score_table_ready(Model* m, int medium, const T** Fm) {
 template int score_table_ready<float>(Model*, int, const float**);
 template int score_table_ready<bf16>(Model*, int, const bf16**);
 
-int group_plan(const char* who, const int32_t* group, int64_t nq, int ng, int chunk, GroupPlan& gp) {
+int group_plan(const char* who, const int32_t* group, int64_t nq, int ng, int chunk, GroupPlan& gp, bool allow_empty) {
   gp.goff.assign((size_t)ng + 1, 0);
   for (int64_t q = 0; q < nq; ++q) {
     const int g = group ? group[q] : (int)q;
@@ -401,7 +624,7 @@ int group_plan(const char* who, const int32_t* group, int64_t nq, int ng, int ch
     ++gp.goff[g + 1];
   }
   for (int g = 0; g < ng; ++g) {
-    ARG_CHECK(gp.goff[g + 1] > 0, std::string(who) + ": every group needs at least one query");
+    ARG_CHECK(allow_empty || gp.goff[g + 1] > 0, std::string(who) + ": every group needs at least one query");
     gp.goff[g + 1] += gp.goff[g];
   }
   gp.members.resize((size_t)nq);
@@ -459,12 +682,15 @@ int csc_nonzero_pattern(const char* who, const char* rows, int64_t n_rows, int64
 template <typename T>
 static int retrieve_t(Model* m, int medium, const float* queries, int64_t nq, const int32_t* group, int ng, const float* prior,
                       const int64_t* excl_off, const int32_t* excl_ids, const RetrieveInit* init, int k, int32_t* ids_out, float* scores_out,
-                      int32_t* counts_out, RetrieveDev* dev = nullptr) {
+                      int32_t* counts_out, RetrieveDev* dev = nullptr, const RetrieveWin* win = nullptr) {
+  // win: the window [start, start + len) of each group's ordering instead of its top k (rsys_retrieve_window): rows of RT_WIN ranks, a
+  // group may have no queries (its score row is what `init` wrote), nq may be 0 (nothing is scored, the item table is not read)
   const int Vm = medium == 0 ? m->V0 : m->V1;
   hipStream_t s = m->stream;
+  if (win) k = RT_WIN;
   // host-side index arrays: the queries of each group in query order, per chunk the range of them it holds, exclusion positions
   GroupPlan gp;
-  RC(group_plan("retrieve_topk", group, nq, ng, RT_CHUNK, gp));
+  RC(group_plan(win ? "retrieve_window" : "retrieve_topk", group, nq, ng, RT_CHUNK, gp, win != nullptr));
   RC(check_ragged("retrieve_topk", LIST_EXCLUDED, excl_off, ng, {excl_ids}));
   RC(check_list_items("retrieve_topk", LIST_EXCLUDED, excl_off, ng, nullptr, excl_ids, &Vm));
   std::vector<long long> xpos;
@@ -472,34 +698,46 @@ static int retrieve_t(Model* m, int medium, const float* queries, int64_t nq, co
     for (int g = 0; g < ng; ++g)
       for (int64_t j = excl_off[g]; j < excl_off[g + 1]; ++j) xpos.push_back((long long)g * Vm + excl_ids[j]);
   HIP_CHECK(hipSetDevice(m->device));
-  const T* Fm;
-  RC(score_table_ready<T>(m, medium, &Fm));
+  const T* Fm = nullptr;
+  if (nq) RC(score_table_ready<T>(m, medium, &Fm));
   // workspace: queries (f32 + compute type), lse, partials, the per-chunk score slab (the candidate lists reuse it after the last
   // chunk), the group scores / keys, the selection state, the outputs, the index arrays
   const int nb = (Vm + RT_ITEMS - 1) / RT_ITEMS;
   ScoreBufs<T> b(m);
-  const size_t slab = std::max<size_t>((size_t)RT_CHUNK * (size_t)b.ldz * 4, (size_t)ng * (size_t)k * 8);
-  float *sc, *d_vals; SelBufs sb; int *d_ids, *d_counts, *d_members; int2* d_ranges; long long* d_xpos;
+  const size_t zrows = win ? (size_t)std::min<int64_t>(nq, RT_CHUNK) : (size_t)RT_CHUNK;
+  const size_t slab = std::max<size_t>(zrows * (size_t)b.ldz * 4, (size_t)ng * (size_t)k * 8);
+  const size_t nbound = win ? 2 : 1;   // (a window selects two rank bounds per group and counts int4 per workgroup)
+  float *sc, *d_vals; SelBufs sb; int *d_ids, *d_counts, *d_members, *d_totals, *d_wlen; int2* d_ranges; long long *d_xpos, *d_wstart;
   RC(carve_into(m->rws, s, [&](Carve& c) {
     b.take(c, nq, slab);
     sc = c.take<float>((size_t)ng * Vm);
-    sb.hist = c.take<unsigned>((size_t)ng * 256);
-    sb.st = c.take<SelState>(ng);
-    sb.cnt = c.take<int2>((size_t)ng * nb);
+    sb.hist = c.take<unsigned>(nbound * ng * 256);
+    sb.st = c.take<SelState>(nbound * ng);
+    sb.cnt = c.take<int2>(nbound * ng * nb);
     d_ids = c.take<int>((size_t)ng * k);
     d_vals = c.take<float>((size_t)ng * k);
     d_counts = c.take<int>(ng);
     d_members = c.take<int>(nq);
     d_ranges = c.take<int2>(gp.ranges.size());
     d_xpos = c.take<long long>(xpos.size());
+    d_totals = c.take<int>(win ? ng : 0);
+    d_wstart = c.take<long long>(win ? ng : 0);
+    d_wlen = c.take<int>(win ? ng : 0);
   }));
   sb.cand = (unsigned long long*)b.z; sb.ldc = k;
 
   tic(m, "retrieve_prep");
   // (dev: the queries are on the device already and the result stays there; the arithmetic below is the same)
-  RC(score_upload_queries(b, dev ? dev->d_queries : queries, nq, dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
-  HIP_CHECK(hipMemcpyAsync(d_members, gp.members.data(), gp.members.size() * 4, hipMemcpyHostToDevice, s));
-  HIP_CHECK(hipMemcpyAsync(d_ranges, gp.ranges.data(), gp.ranges.size() * sizeof(int2), hipMemcpyHostToDevice, s));
+  if (nq) {
+    RC(score_upload_queries(b, dev ? dev->d_queries : queries, nq, dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(d_members, gp.members.data(), gp.members.size() * 4, hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(d_ranges, gp.ranges.data(), gp.ranges.size() * sizeof(int2), hipMemcpyHostToDevice, s));
+  }
+  if (win) {
+    static_assert(sizeof(long long) == sizeof(int64_t), "window starts are copied as they are");
+    HIP_CHECK(hipMemcpyAsync(d_wstart, win->start, (size_t)ng * 8, hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(d_wlen, win->len, (size_t)ng * 4, hipMemcpyHostToDevice, s));
+  }
   if (init) RC((*init)(sc, s));   // the device-side initialiser of the group score rows (rsys_retrieve_request)
   else if (prior) HIP_CHECK(hipMemcpyAsync(sc, prior, (size_t)ng * Vm * 4, hipMemcpyHostToDevice, s));
   else HIP_CHECK(hipMemsetAsync(sc, 0, (size_t)ng * Vm * 4, s));
@@ -507,8 +745,12 @@ static int retrieve_t(Model* m, int medium, const float* queries, int64_t nq, co
     HIP_CHECK(hipMemcpyAsync(d_xpos, xpos.data(), xpos.size() * 8, hipMemcpyHostToDevice, s));
     RC(launch_scatter_nan(sc, d_xpos, (long long)xpos.size(), s));
   }
-  HIP_CHECK(hipMemsetAsync(sb.hist, 0, (size_t)ng * 256 * 4, s));
+  HIP_CHECK(hipMemsetAsync(sb.hist, 0, nbound * ng * 256 * 4, s));
   toc(m);
+  if (gp.nchunks == 0) {   // (a window call without queries: the keys of the initialised rows)
+    combine_kernel<true><<<dim3(nb, ng), RT_THREADS, 0, s>>>(sc, Vm, sc, Vm, nullptr, 0, nullptr, nullptr, nullptr, 0, Vm, sb.hist);
+    RT_LAUNCH_CHECK();
+  }
   for (int ch = 0; ch < gp.nchunks; ++ch) {
     const int q0 = ch * RT_CHUNK, nc = (int)std::min<int64_t>(RT_CHUNK, nq - q0);
     RC(retrieve_chunk_scores<T>(m, b.qt + (size_t)q0 * b.D, nc, q0, Fm, Vm, b.z, b.ldz, b.part, b.lse));
@@ -522,7 +764,8 @@ static int retrieve_t(Model* m, int medium, const float* queries, int64_t nq, co
     toc(m);
   }
   tic(m, "retrieve_select");
-  RC(topk_select((const unsigned*)sc, Vm, ng, Vm, k, sb, d_ids, d_vals, d_counts, s));
+  if (win) RC(window_select((const unsigned*)sc, Vm, ng, Vm, d_wstart, d_wlen, sb, d_ids, d_vals, d_counts, d_totals, s));
+  else RC(topk_select((const unsigned*)sc, Vm, ng, Vm, k, sb, d_ids, d_vals, d_counts, s));
   toc(m);
   if (dev) { dev->d_ids = d_ids; dev->d_vals = d_vals; }
   else {
@@ -530,6 +773,7 @@ static int retrieve_t(Model* m, int medium, const float* queries, int64_t nq, co
     HIP_CHECK(hipMemcpyAsync(scores_out, d_vals, (size_t)ng * k * 4, hipMemcpyDeviceToHost, s));
   }
   HIP_CHECK(hipMemcpyAsync(counts_out, d_counts, (size_t)ng * 4, hipMemcpyDeviceToHost, s));
+  if (win) HIP_CHECK(hipMemcpyAsync(win->total_out, d_totals, (size_t)ng * 4, hipMemcpyDeviceToHost, s));
   HIP_CHECK(hipStreamSynchronize(s));
   return RSYS_OK;
 }
@@ -553,9 +797,9 @@ int model_retrieve_topk(Model* m, int medium, const float* queries, int64_t nq, 
 // stream after the workspace is in place): the prior and the NaN masks of rsys_retrieve_request.  The caller has checked the arguments
 // model_retrieve_topk checks.
 int model_retrieve_run(Model* m, int medium, const float* queries, int64_t nq, const int32_t* group, int32_t ng, const RetrieveInit& init,
-                       int32_t k, int32_t* ids_out, float* scores_out, int32_t* counts_out, RetrieveDev* dev) {
-  return m->bf16_mode ? retrieve_t<bf16>(m, medium, queries, nq, group, ng, nullptr, nullptr, nullptr, &init, k, ids_out, scores_out, counts_out, dev)
-                      : retrieve_t<float>(m, medium, queries, nq, group, ng, nullptr, nullptr, nullptr, &init, k, ids_out, scores_out, counts_out, dev);
+                       int32_t k, int32_t* ids_out, float* scores_out, int32_t* counts_out, RetrieveDev* dev, const RetrieveWin* win) {
+  return m->bf16_mode ? retrieve_t<bf16>(m, medium, queries, nq, group, ng, nullptr, nullptr, nullptr, &init, k, ids_out, scores_out, counts_out, dev, win)
+                      : retrieve_t<float>(m, medium, queries, nq, group, ng, nullptr, nullptr, nullptr, &init, k, ids_out, scores_out, counts_out, dev, win);
 }
 
 static void topk_rows_layout(Carve& c, int rows, int V, int k, unsigned** keys, SelBufs* sb) {

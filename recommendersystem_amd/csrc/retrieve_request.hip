@@ -293,57 +293,72 @@ int model_retrieve_released_set(Model* m, int medium, const uint8_t* mask) {
   return upload((void**)&t.released, b.data(), b.size() * 4);
 }
 
-// the one body of rsys_retrieve_request and of rsys_render_request's retrieval stage: dev == nullptr takes the queries from, and returns
-// the result to, the host; else both stay on the device (RetrieveDev) and only the counts come back
+// the one body of rsys_retrieve_request, rsys_retrieve_window and the retrieval stages of rsys_render_request / rsys_render_items:
+// dev == nullptr takes the queries from, and returns the result to, the host; else both stay on the device (RetrieveDev) and only the
+// counts come back.  win != nullptr: a window of each group's ordering instead of its top k (RetrieveWin); groups may then have no
+// queries -- such a group is scored by its prior alone and has no relation masks -- and nq may be 0, which needs no relation table.
 static int retrieve_request_body(Model* m, int medium, const float* queries, RetrieveDev* dev, int64_t nq, const int32_t* group, int32_t ng,
                                  const int64_t* hist_off, const int32_t* hist_medium, const int32_t* hist_ids, const int32_t* hist_status,
                                  const int64_t* sel_off, const int32_t* sel_medium, const int32_t* sel_ids, int32_t k, int32_t* ids_out,
-                                 float* scores_out, int32_t* counts_out) {
+                                 float* scores_out, int32_t* counts_out, const RetrieveWin* win = nullptr) {
+  const char* who = win ? "retrieve_window" : "retrieve_request";
+  auto msg = [who](const char* text) { return std::string(who) + ": " + text; };
   // the limits of rsys_retrieve_topk (model_retrieve_topk)
-  ARG_CHECK(medium == 0 || medium == 1, "retrieve_request: medium must be 0 or 1");
-  ARG_CHECK(!m->sharded, "retrieve_request: the row-sharded item table is not supported (replicated table only)");
-  ARG_CHECK(dev ? (dev->d_queries && counts_out) : (queries && ids_out && scores_out && counts_out), "retrieve_request: null buffer");
-  ARG_CHECK(nq >= 1 && nq <= 4096, "retrieve_request: 1 <= n_queries <= 4096");
-  ARG_CHECK(ng >= 1 && ng <= nq, "retrieve_request: 1 <= n_groups <= n_queries (every group needs a query)");
-  ARG_CHECK(group != nullptr || ng == nq, "retrieve_request: without `group`, n_groups must equal n_queries");
+  ARG_CHECK(medium == 0 || medium == 1, msg("medium must be 0 or 1"));
+  ARG_CHECK(!m->sharded, msg("the row-sharded item table is not supported (replicated table only)"));
+  ARG_CHECK((nq == 0 || (dev ? dev->d_queries != nullptr : queries != nullptr)) && counts_out && (dev || (ids_out && scores_out)), msg("null buffer"));
   const int Vm = medium == 0 ? m->V0 : m->V1;
   const int V[2] = {m->V0, m->V1};
-  ARG_CHECK(k >= 1 && k <= std::min(Vm, 8192), "retrieve_request: 1 <= k <= min(V_m, 8192)");
-  ARG_CHECK(Vm <= 65535 * 64, "retrieve_request: V_m <= 4194240 (item blocks of the prior)");
+  if (win) {
+    ARG_CHECK(win->start && win->len && win->total_out, msg("null buffer"));
+    ARG_CHECK(nq >= 0 && nq <= 4096, msg("0 <= n_queries <= 4096"));
+    ARG_CHECK(ng >= 1 && ng <= 4096, msg("1 <= n_groups <= 4096"));
+    ARG_CHECK(group != nullptr || ng == nq || nq == 0, msg("without `group`, n_groups must equal n_queries"));
+    for (int g = 0; g < ng; ++g) {
+      ARG_CHECK(win->len[g] >= 1 && win->len[g] <= 1024, msg("1 <= win_len <= 1024"));
+      ARG_CHECK(win->start[g] >= 0, msg("win_start >= 0"));
+    }
+  } else {
+    ARG_CHECK(nq >= 1 && nq <= 4096, msg("1 <= n_queries <= 4096"));
+    ARG_CHECK(ng >= 1 && ng <= nq, msg("1 <= n_groups <= n_queries (every group needs a query)"));
+    ARG_CHECK(group != nullptr || ng == nq, msg("without `group`, n_groups must equal n_queries"));
+    ARG_CHECK(k >= 1 && k <= std::min(Vm, 8192), msg("1 <= k <= min(V_m, 8192)"));
+  }
+  ARG_CHECK(Vm <= 65535 * 64, msg("V_m <= 4194240 (item blocks of the prior)"));
   std::vector<int32_t> qgroup((size_t)nq);
   for (int64_t q = 0; q < nq; ++q) {
     qgroup[q] = group ? group[q] : (int32_t)q;
-    ARG_CHECK(qgroup[q] >= 0 && qgroup[q] < ng, "retrieve_request: group ids must be in [0, n_groups)");
+    ARG_CHECK(qgroup[q] >= 0 && qgroup[q] < ng, msg("group ids must be in [0, n_groups)"));
   }
   RetrievalTables* R = tables(m);
   const MediumTables& T = R->t[medium];
-  for (int kind = 0; kind < 3; ++kind)
-    ARG_CHECK(T.rel[kind].colptr != nullptr, "retrieve_request: the dependencies, recaps and adaptations of the medium must be loaded");
-  RC(check_ragged("retrieve_request", LIST_HISTORY, hist_off, nq, {hist_medium, hist_ids, hist_status}));
-  RC(check_ragged("retrieve_request", LIST_SELECTED, sel_off, ng, {sel_medium, sel_ids}));
+  for (int kind = 0; kind < 3 && nq > 0; ++kind)
+    ARG_CHECK(T.rel[kind].colptr != nullptr, msg("the dependencies, recaps and adaptations of the medium must be loaded"));
+  RC(check_ragged(who, LIST_HISTORY, hist_off, nq, {hist_medium, hist_ids, hist_status}));
+  RC(check_ragged(who, LIST_SELECTED, sel_off, ng, {sel_medium, sel_ids}));
   // selected items: ranges, ids, the similarity tables they need
   int64_t nsel = 0;
   if (sel_off) {
     nsel = sel_off[ng];
-    ARG_CHECK(nsel <= 65535, "retrieve_request: at most 65535 selected items per call");
-    RC(check_list_items("retrieve_request", LIST_SELECTED, sel_off, ng, sel_medium, sel_ids, V));
+    ARG_CHECK(nsel <= 65535, msg("at most 65535 selected items per call"));
+    RC(check_list_items(who, LIST_SELECTED, sel_off, ng, sel_medium, sel_ids, V));
     for (int64_t a = 0; a < nsel; ++a) {
       const int am = sel_medium[a];
-      ARG_CHECK(R->t[am].emb != nullptr, "retrieve_request: the item-similarity embeddings of a selected item's medium are not loaded");
+      ARG_CHECK(R->t[am].emb != nullptr, msg("the item-similarity embeddings of a selected item's medium are not loaded"));
       if (am != medium)
-        ARG_CHECK(R->t[am].cross != nullptr, "retrieve_request: the crossproject of a selected item's medium is not loaded");
+        ARG_CHECK(R->t[am].cross != nullptr, msg("the crossproject of a selected item's medium is not loaded"));
     }
     if (nsel) {
-      ARG_CHECK(T.emb != nullptr, "retrieve_request: the item-similarity embeddings of the request medium are not loaded");
+      ARG_CHECK(T.emb != nullptr, msg("the item-similarity embeddings of the request medium are not loaded"));
       for (int64_t a = 0; a < nsel; ++a)
-        ARG_CHECK(R->t[sel_medium[a]].dim == T.dim, "retrieve_request: the item-similarity tables of the two media differ in width");
+        ARG_CHECK(R->t[sel_medium[a]].dim == T.dim, msg("the item-similarity tables of the two media differ in width"));
     }
   }
   // list items: the last status of each (medium, id) per user (render.jl's `statuses` dict), turned into the sets it is in
   std::vector<int32_t> ent_q, ent_id, ent_f;
   std::vector<int64_t> ent_off((size_t)nq + 1, 0);
   if (hist_off) {
-    RC(check_list_items("retrieve_request", LIST_HISTORY, hist_off, nq, hist_medium, hist_ids, V));
+    RC(check_list_items(who, LIST_HISTORY, hist_off, nq, hist_medium, hist_ids, V));
     const size_t nkeys = (size_t)m->V0 + m->V1;
     if (R->mark.size() != nkeys || R->tick > 0xfffffff0u) { R->mark.assign(nkeys, 0u); R->status.assign(nkeys, 0); R->tick = 0; }
     for (int64_t q = 0; q < nq; ++q) {
@@ -408,7 +423,7 @@ static int retrieve_request_body(Model* m, int medium, const float* queries, Ret
     HIP_CHECK(hipMemcpyAsync(d_eid, ent_id.data(), (size_t)nent * 4, hipMemcpyHostToDevice, s));
     HIP_CHECK(hipMemcpyAsync(d_ef, ent_f.data(), (size_t)nent * 4, hipMemcpyHostToDevice, s));
   }
-  HIP_CHECK(hipMemcpyAsync(d_qg, qgroup.data(), (size_t)nq * 4, hipMemcpyHostToDevice, s));
+  if (nq) HIP_CHECK(hipMemcpyAsync(d_qg, qgroup.data(), (size_t)nq * 4, hipMemcpyHostToDevice, s));
 
   const MediumTables& T0 = R->t[0];
   const MediumTables& T1 = R->t[1];
@@ -457,7 +472,7 @@ static int retrieve_request_body(Model* m, int medium, const float* queries, Ret
     toc(m);
     return RSYS_OK;
   };
-  return model_retrieve_run(m, medium, queries, nq, group, ng, init, k, ids_out, scores_out, counts_out, dev);
+  return model_retrieve_run(m, medium, queries, nq, group, ng, init, k, ids_out, scores_out, counts_out, dev, win);
 }
 
 int model_retrieve_request(Model* m, int medium, const float* queries, int64_t nq, const int32_t* group, int32_t ng, const int64_t* hist_off,
@@ -474,6 +489,15 @@ int model_retrieve_request_dev(Model* m, int medium, RetrieveDev* dev, int64_t n
   ARG_CHECK(dev != nullptr, "retrieve_request: null device buffers");
   return retrieve_request_body(m, medium, nullptr, dev, nq, group, ng, hist_off, hist_medium, hist_ids, hist_status, sel_off, sel_medium,
                                sel_ids, k, nullptr, nullptr, counts_out);
+}
+
+int model_retrieve_window(Model* m, int medium, const float* queries, int64_t nq, const int32_t* group, int32_t ng, const int64_t* hist_off,
+                          const int32_t* hist_medium, const int32_t* hist_ids, const int32_t* hist_status, const int64_t* sel_off,
+                          const int32_t* sel_medium, const int32_t* sel_ids, const RetrieveWin* win, RetrieveDev* dev, int32_t* ids_out,
+                          float* scores_out, int32_t* counts_out) {
+  ARG_CHECK(win != nullptr, "retrieve_window: null window");
+  return retrieve_request_body(m, medium, queries, dev, nq, group, ng, hist_off, hist_medium, hist_ids, hist_status, sel_off, sel_medium,
+                               sel_ids, 0, ids_out, scores_out, counts_out, win);
 }
 
 }  // namespace rsys

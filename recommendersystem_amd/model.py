@@ -618,6 +618,76 @@ class RecommenderModel:
                                           scores.ctypes.data, counts.ctypes.data))
         return ids, scores, counts
 
+    WINDOW_ROWS = 1024                # ranks per window row of rsys_retrieve_window
+
+    def retrieve_window(self, queries, medium, starts, lengths, group=None, n_groups=None, histories=None, selected=None):
+        """`retrieve_request` for any rank range (rsys_retrieve_window): per group the items of ranks [starts[g], starts[g] + lengths[g])
+        of its ordering (0-based, 1 <= length <= 1024) and its exact number of admissible items.  A group may have no queries (a state
+        without users: scored by the prior of its selected items alone, no relation masks); `queries` may be None or empty, `group` then
+        too.  `n_groups` defaults to len(starts).  Returns (ids (n_groups, 1024) int32, scores (n_groups, 1024) float32, counts, totals
+        (n_groups,) int32 each); slots past counts[g] = clamp(totals[g] - starts[g], 0, lengths[g]) hold -1 / -inf."""
+        q = None if queries is None else np.ascontiguousarray(queries, np.float32)
+        if q is not None and q.ndim == 1:
+            q = q[None, :]
+        n = 0 if q is None else q.shape[0]
+        if n == 0:
+            q = None
+        ws = np.ascontiguousarray(starts, np.int64).reshape(-1)
+        wl = np.ascontiguousarray(lengths, np.int32).reshape(-1)
+        ng = ws.size if n_groups is None else int(n_groups)
+        if ws.size != ng or wl.size != ng:
+            raise ValueError(f"retrieve_window: starts and lengths need {ng} entries, one per group")
+        gp = None if group is None or n == 0 else np.ascontiguousarray(group, np.int32).reshape(-1)
+        if gp is not None and gp.size != n:
+            raise ValueError(f"group has {gp.size} entries for {n} queries")
+        if gp is None and n not in (0, ng):
+            raise ValueError(f"retrieve_window: without group, {n} queries need {n} groups, not {ng}")
+        h = None
+        if histories is not None and n:
+            if len(histories) != n:
+                raise ValueError(f"histories has {len(histories)} lists for {n} queries")
+            h = triples_csr(histories, 3)
+        sl = None
+        if selected is not None:
+            if len(selected) != ng:
+                raise ValueError(f"selected has {len(selected)} lists for {ng} groups")
+            sl = triples_csr(selected, 2)
+        ids = np.empty((ng, self.WINDOW_ROWS), np.int32)
+        scores = np.empty((ng, self.WINDOW_ROWS), np.float32)
+        counts = np.empty(max(ng, 1), np.int32)
+        totals = np.empty(max(ng, 1), np.int32)
+        ptr = lambda a: None if a is None else a.ctypes.data
+        hp = (None,) * 4 if h is None else tuple(ptr(a) for a in h)
+        sp = (None,) * 3 if sl is None else tuple(ptr(a) for a in sl)
+        check(lib().rsys_retrieve_window(self._h, int(medium), ptr(q), n, ptr(gp), ng, *hp, *sp, ptr(ws), ptr(wl), ids.ctypes.data,
+                                         scores.ctypes.data, counts.ctypes.data, totals.ctypes.data))
+        return ids, scores, counts[:ng], totals[:ng]
+
+    def render_items(self, group_medium, offsets, limits, penalties, selected=None):
+        """rsys_render_items: a page per state WITHOUT users (compute.jl `/add_item`) in one device call -- per group (medium, offset,
+        limit, penalties (4)) and its selected items [(medium, id), ...]: the windowed retrieval on the item-similarity prior, then the
+        reranking on zero ranking scores.  Returns (one int32 page array per group, exact totals (n_groups,) int32)."""
+        gm = np.ascontiguousarray(group_medium, np.int32).reshape(-1)
+        ng = gm.size
+        off = np.ascontiguousarray(offsets, np.int64).reshape(-1)
+        lim = np.ascontiguousarray(limits, np.int32).reshape(-1)
+        pen = np.ascontiguousarray(penalties, np.float32).reshape(-1)
+        if off.size != ng or lim.size != ng or pen.size != 4 * ng:
+            raise ValueError(f"render_items: offsets, limits and penalties need {ng} entries and {ng} x 4 values")
+        sel = None
+        if selected is not None:
+            if len(selected) != ng:
+                raise ValueError(f"selected has {len(selected)} lists for {ng} groups")
+            sel = triples_csr(selected, 2)
+        cap = int(np.clip(lim, 0, None).sum())
+        ids = np.empty(max(cap, 1), np.int32)
+        ioff = np.empty(ng + 1, np.int64)
+        total = np.empty(max(ng, 1), np.int32)
+        ptr = lambda a: None if a is None else a.ctypes.data
+        sp = (None,) * 3 if sel is None else tuple(ptr(a) for a in sel)
+        check(lib().rsys_render_items(self._h, ng, ptr(gm), ptr(off), ptr(lim), ptr(pen), *sp, ptr(ids), cap, ptr(ioff), ptr(total)))
+        return [ids[ioff[g]:ioff[g + 1]].copy() for g in range(ng)], total[:ng].copy()
+
     # ---- ranking and reranking of retrieved candidates (rsys_rank_request: Inference/render.jl:335-435)
     def set_related(self, medium, related=None):
         """Loads "{m}.related" (V_m x V_m, a 0-based CSC `(indptr, indices, data, shape)` tuple or an object with those attributes) onto

@@ -469,6 +469,43 @@ def retrieval(model, states, k=1024, coefs=None):
     return out
 
 
+def _window_arrays(states, medium):
+    """`request_arrays` for states that may have no users: (queries or None, group ids, list items per user, selected items per state)"""
+    key = f"{medium}.retrieval"
+    q, group, hist, sel = [], [], [], []
+    for g, st in enumerate(states):
+        for u in st["users"]:
+            q.append(np.asarray(u["embeds"][key], np.float32).reshape(-1))
+            group.append(g)
+            hist.append([(int(x["medium"]), int(x["matchedid"]), int(x["status"])) for x in u["user"]["items"]])
+        sel.append([(int(a["medium"]), int(a["matchedid"])) for a in st["items"]])
+    return (np.stack(q) if q else None), np.asarray(group, np.int32), hist, sel
+
+
+def retrieval_window(model, states, windows):
+    """Ranks [start, start + length) of render.jl `retrieval(state)` and its exact length (rsys_retrieve_window), for a list of request
+    states with or without users: `retrieval`'s ordering without its cap of 8192 -- any start, at most 1024 ranks per call.  A state
+    without users (compute.jl `/add_item`) is ordered by the item-similarity prior of its selected items alone.  `windows`: one
+    (start, length) pair, or one per state.  Returns one (ids, scores, total) triple per state: the window's ids (0-based
+    medium-local) and scores, best first -- fewer than `length` when the list ends inside the window, none when it starts past the end
+    -- and the number of admissible items."""
+    wins = [windows] * len(states) if np.ndim(windows) == 1 else list(windows)
+    if len(wins) != len(states):
+        raise ValueError(f"retrieval_window: {len(wins)} windows for {len(states)} states")
+    for start, length in wins:
+        if int(start) < 0 or not 1 <= int(length) <= MAX_ITEMS_TO_RANK:
+            raise ValueError("retrieval_window: start >= 0 and 1 <= length <= 1024")
+    out = [None] * len(states)
+    for m, idx in _by_medium(states):
+        q, group, hist, sel = _window_arrays([states[j] for j in idx], m)
+        ids, scores, counts, totals = model.retrieve_window(q, m, [int(wins[j][0]) for j in idx], [int(wins[j][1]) for j in idx], group=group,
+                                                            n_groups=len(idx), histories=hist, selected=sel)
+        for g, j in enumerate(idx):
+            n = int(counts[g])
+            out[j] = (ids[g, :n].copy(), scores[g, :n].copy(), int(totals[g]))
+    return out
+
+
 # ---------------------------------------------------------------- ranking and reranking (render.jl `ranking`, `reranking!`, `render`)
 MAX_ITEMS_TO_RANK = 1024          # render.jl:449
 RETRIEVAL_CAP = 8192              # candidates rsys_retrieve_request returns at most
@@ -581,7 +618,39 @@ def page_window(n_retrieved, pagination):
     return start, stop, sidx - start, eidx - start
 
 
-def render(model, states, pagination, registry=None, max_ranking_items=None, full_history=False):
+def _penalties(st):
+    p = st.get("penalties", {})
+    return [float(p.get(k, 0.0)) for k in ("decay", "mmr_penalty", "same_series_penalty", "related_penalty")]
+
+
+def render_items(model, states, pagination):
+    """render.jl `render(state, pagination)` for states WITHOUT users (compute.jl:490-514 `/add_item`: pick a title, see similar
+    titles) in one device call (rsys_render_items): `retrieval` is the item-similarity prior of the selected items with item 0, the
+    selected and the unreleased items masked, `ranking` is zeros, `reranking!` runs on them under `state["penalties"]`.  `pagination`:
+    {"offset", "limit"} or one per state.  Returns one (ids of the page, total) pair per state; total is the exact number of admissible
+    items and every offset below it has a page."""
+    pags = [pagination] * len(states) if isinstance(pagination, dict) else list(pagination)
+    if len(pags) != len(states):
+        raise ValueError(f"render_items: {len(pags)} paginations for {len(states)} states")
+    gm, off, lim, pen, sel = [], [], [], [], []
+    for st, pg in zip(states, pags):
+        if st["users"]:
+            raise ValueError("render_items: a state has users (render, render_users)")
+        m, limit, offset = int(st["medium"]), int(pg["limit"]), int(pg["offset"])
+        if m not in (0, 1):
+            raise ValueError("medium must be 0 or 1")
+        if not 1 <= limit <= MAX_ITEMS_TO_RANK or offset < 0:
+            raise ValueError("pagination: 1 <= limit <= 1024 and offset >= 0")
+        gm.append(m); off.append(offset); lim.append(limit)
+        pen.append(_penalties(st))
+        sel.append([(int(a["medium"]), int(a["matchedid"])) for a in st["items"]])
+    if not states:
+        return []
+    pages, totals = model.render_items(gm, off, lim, np.asarray(pen, np.float32).reshape(-1, 4), sel)
+    return [(pages[g], int(totals[g])) for g in range(len(states))]
+
+
+def render(model, states, pagination, registry=None, max_ranking_items=None, full_history=False, exact=False):
     """render.jl `render(state, pagination)` (lines 437-474) without the card rendering, for a list of states: `retrieval`, the page's
     slice of at most 1024 candidates, the ranking forward (`predict(..., "ranking")` in chunks of at most `max_ranking_items` candidates,
     default the model's S - S // 2; candidates are masked from each other, so chunking does not change the result of a user with a
@@ -589,24 +658,57 @@ def render(model, states, pagination, registry=None, max_ranking_items=None, ful
     the values depend on where the chunks are cut), then `ranking` + `reranking` in one device call with partialk = the page's last
     index.  `full_history=True`: the ranking forward is `predict_ranking_full` instead -- every user ranked on its newest S - 1 events
     (the reference's row) rather than the S // 2 - 1 that fit beside a chunk; `max_ranking_items` is then not used.  `pagination`:
-    {"offset", "limit"} or one per state.  Returns one (ids of the page, total) pair per state.  Deviations: the ranked slice is
-    clamped to the retrieved list (render.jl throws a BoundsError), and total = min(admissible items, 8192), the retrieval cap."""
+    {"offset", "limit"} or one per state.  Returns one (ids of the page, total) pair per state.  Deviation: the ranked slice is
+    clamped to the retrieved list (render.jl throws a BoundsError).  By default total = min(admissible items, 8192), the retrieval cap, a
+    page past rank 8192 is empty and every state needs a user; both are closed by `exact=True` / `render_items`: the page's candidates
+    then come from `retrieval_window`, so total is the number of admissible items and every offset below it has a page (ranking and
+    reranking unchanged), and states without users go through `render_items` -- every state render.jl renders."""
     pags = [pagination] * len(states) if isinstance(pagination, dict) else list(pagination)
+    if exact:
+        for pg in pags:
+            if not 1 <= int(pg["limit"]) <= MAX_ITEMS_TO_RANK or int(pg["offset"]) < 0:
+                raise ValueError("pagination: 1 <= limit <= 1024 and offset >= 0")
+        out = [None] * len(states)
+        bare = [j for j, st in enumerate(states) if not st["users"]]
+        for j, res in zip(bare, render_items(model, [states[j] for j in bare], [pags[j] for j in bare])):
+            out[j] = res
+        rest = [j for j, st in enumerate(states) if st["users"]]
+        if rest:
+            for j, res in zip(rest, _render_states(model, [states[j] for j in rest], [pags[j] for j in rest], registry, max_ranking_items,
+                                                  full_history, True)):
+                out[j] = res
+        return out
+    return _render_states(model, states, pags, registry, max_ranking_items, full_history, False)
+
+
+def _render_states(model, states, pags, registry, max_ranking_items, full_history, exact):
+    """`render` for states with users; exact: the page's candidates are the window of `retrieval_window` instead of a slice of the top 8192"""
     S = model.config["max_sequence_length"]
     max_user_len = S // 2
     chunk = S - max_user_len if max_ranking_items is None else min(int(max_ranking_items), S - max_user_len)
     if chunk < 1:
         raise ValueError("render: max_ranking_items must be >= 1")
-    retrieved = retrieval(model, states, k=RETRIEVAL_CAP, coefs=None)
     out = [None] * len(states)
     work = []
+    if exact:   # the ranked slice starts at a multiple of max_items_to_rank that the offset alone fixes: ask for exactly it
+        mitr = [MAX_ITEMS_TO_RANK - MAX_ITEMS_TO_RANK % int(pg["limit"]) for pg in pags]
+        windows = retrieval_window(model, states, [(int(pg["offset"]) // k * k, k) for pg, k in zip(pags, mitr)])
+    else:
+        retrieved = retrieval(model, states, k=RETRIEVAL_CAP, coefs=None)
     for j, st in enumerate(states):
-        ids = retrieved[j][0]
-        win = page_window(ids.size, pags[j])
+        if exact:
+            ids, _, total = windows[j]
+            win = page_window(total, pags[j])
+        else:
+            ids = retrieved[j][0]
+            total = int(ids.size)
+            win = page_window(total, pags[j])
+            if win is not None:
+                ids = ids[win[0]:win[1]]
         if win is None:
-            out[j] = (np.zeros(0, np.int32), int(ids.size))
+            out[j] = (np.zeros(0, np.int32), total)
             continue
-        work.append((j, ids[win[0]:win[1]], win[2], win[3], int(ids.size)))
+        work.append((j, ids, win[2], win[3], total))
     for m, js in _by_medium([states[w[0]] for w in work]) if work else []:
         items = [work[i] for i in js]
         sub = [states[w[0]] for w in items]
