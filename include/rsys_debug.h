@@ -95,6 +95,18 @@ int32_t rsys_debug_gemm_route(int32_t dtype, int32_t M, int32_t N, int32_t K, in
 int32_t rsys_op_attention(int32_t dtype, int32_t B, int32_t T, int32_t H, int32_t KV, int32_t hd, const void* qkv,
                           const int32_t* uid, const int32_t* tm, void* O, float* lse, const void* dO, void* dqkv,
                           const float* rope_cos, const float* rope_sin);
+/* the same launches with the remaining AttnParams fields (csrc/kernels.hpp); rsys_op_attention is this call with all of them null and
+ * rope_rows = T.  rope tables [rope_rows][hd/2] f32.  rope_pos (device int32 [B*T], or null: token t of a row has position t): the
+ * table row each token's gradient is un-rotated with; the host copies it back once and checks 0 <= pos < rope_rows (null: rope_rows
+ * >= T).  q_active (device int32 [B], or null): only the first q_active[b] 64-token query tiles of row b matter -- O / lse of the
+ * others are not written, their dq rows are zeros, and dk / dv leave them out (THEIR dO ROWS MUST BE ZERO); delta of those tiles is
+ * NaN during the call.  amax_fwd / amax_bwd (device, 64 shards of 32 floats each, zeroed by the caller, or null): AttnParams::f8_amax
+ * of the forward / the backward launches -- the maximum over the shards of element 0 of amax_fwd = max |O|, of elements 0 / 1 / 2 of
+ * amax_bwd = max |dq| / |dk| / |dv|, of the stored (rounded) values */
+int32_t rsys_op_attention_ex(int32_t dtype, int32_t B, int32_t T, int32_t H, int32_t KV, int32_t hd, const void* qkv,
+                             const int32_t* uid, const int32_t* tm, void* O, float* lse, const void* dO, void* dqkv,
+                             const float* rope_cos, const float* rope_sin, const int32_t* rope_pos, int32_t rope_rows,
+                             const int32_t* q_active, float* amax_fwd, float* amax_bwd);
 /* the candidate attention of rsys_rank_cache_candidates alone, on caller-provided device buffers (T-typed): qkv [rows*T][(H+2KV)*hd] the
  * candidate rows' post-RoPE q | k | v, cache [n_slots][T][2*KV*hd] (K | V per cached token), slot / n_hist / n_cand int32 [rows] (device;
  * 0 <= n_hist[r] <= T/2, 0 <= n_cand[r] <= T/2); O [rows*T][H*hd]: rows of tokens >= 2 n_cand[r] are zeros up to the end of the last

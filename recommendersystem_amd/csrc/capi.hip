@@ -945,7 +945,24 @@ int32_t rsys_op_gemm_f8(const void* A8, const void* B8, void* C, int32_t M, int3
 int32_t rsys_op_attention(int32_t dtype, int32_t B, int32_t T, int32_t H, int32_t KV, int32_t hd, const void* qkv,
                           const int32_t* uid, const int32_t* tm, void* O, float* lse, const void* dO, void* dqkv,
                           const float* rope_cos, const float* rope_sin) {
+  return rsys_op_attention_ex(dtype, B, T, H, KV, hd, qkv, uid, tm, O, lse, dO, dqkv, rope_cos, rope_sin, nullptr, T, nullptr, nullptr, nullptr);
+}
+
+int32_t rsys_op_attention_ex(int32_t dtype, int32_t B, int32_t T, int32_t H, int32_t KV, int32_t hd, const void* qkv,
+                             const int32_t* uid, const int32_t* tm, void* O, float* lse, const void* dO, void* dqkv,
+                             const float* rope_cos, const float* rope_sin, const int32_t* rope_pos, int32_t rope_rows,
+                             const int32_t* q_active, float* amax_fwd, float* amax_bwd) {
   switches_parse();
+  ARG_CHECK(dtype == RSYS_DTYPE_BF16 || dtype == RSYS_DTYPE_FP32, "rsys_op_attention: dtype fp32 or bf16");
+  ARG_CHECK(B >= 1 && T >= 1 && H >= 1 && KV >= 1 && qkv && uid && tm && O && lse, "rsys_op_attention: null or empty");
+  ARG_CHECK(!dO || (dqkv && rope_cos && rope_sin), "rsys_op_attention: the backward needs dqkv and the rope tables");
+  if (dO && rope_pos) {   // every explicit position inside the tables (one copy back)
+    std::vector<int32_t> pos((size_t)B * T);
+    HIP_CHECK(hipMemcpy(pos.data(), rope_pos, pos.size() * 4, hipMemcpyDeviceToHost));
+    for (int32_t v : pos) ARG_CHECK(v >= 0 && v < rope_rows, "rsys_op_attention: rope_pos outside the tables");
+  } else if (dO) {
+    ARG_CHECK(rope_rows >= T, "rsys_op_attention: rope tables shorter than T");
+  }
   const size_t e = dtype == RSYS_DTYPE_BF16 ? 2 : 4;
   const int nt = (T + 63) / 64;
   AttnParams p{};
@@ -964,9 +981,13 @@ int32_t rsys_op_attention(int32_t dtype, int32_t B, int32_t T, int32_t H, int32_
   p.qbits = pairbits; p.kbits = pairbits + (size_t)B * nt * nt * 64;
   p.dO = dO; p.dq = dqkv; p.dk = (unsigned char*)dqkv + (size_t)H * hd * e;
   p.dv = (unsigned char*)dqkv + (size_t)(H + KV) * hd * e; p.ldg = p.ld;
-  p.rope_cos = rope_cos; p.rope_sin = rope_sin; p.rope_pos = nullptr;
+  p.rope_cos = rope_cos; p.rope_sin = rope_sin; p.rope_pos = rope_pos; p.q_active = q_active;
+  // (delta of the query tiles beyond q_active is never written: NaN there, so that a dK/dV kernel that reads it shows)
+  if (q_active) HIP_CHECK(hipMemsetAsync(delta, 0xFF, sizeof(float) * B * H * T, nullptr));
   int rc = launch_attn_tilemap(p, nullptr);
+  p.f8_amax = amax_fwd;
   if (!rc) rc = dtype == RSYS_DTYPE_BF16 ? launch_attn_fwd<bf16>(p, nullptr) : launch_attn_fwd<float>(p, nullptr);
+  p.f8_amax = amax_bwd;
   if (!rc && dO) {
     rc = dtype == RSYS_DTYPE_BF16 ? launch_attn_bwd<bf16>(p, nullptr) : launch_attn_bwd<float>(p, nullptr);
   }
