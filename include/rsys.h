@@ -106,6 +106,8 @@ int32_t rsys_batch_upload(rsys_model* m, const rsys_batch* b);
  * device (a second staging buffer / device blob); rsys_batch_swap then makes it the resident batch -- enqueue the step's forward /
  * backward / optimizer first, prefetch, read the step's losses, swap.  The host arrays may be freed when prefetch returns.
  * Replicated item table only (the row-sharded table builds its row-exchange plan inside rsys_batch_upload). */
+/* rows of the resident batch (0: none), whichever call made it resident */
+int32_t rsys_batch_rows(rsys_model* m, int32_t* rows_out);
 int32_t rsys_batch_prefetch(rsys_model* m, const rsys_batch* b);
 int32_t rsys_batch_swap(rsys_model* m);
 /* device-side synthetic batch (bench): fills the resident batch from a counter RNG */
@@ -513,6 +515,40 @@ int32_t rsys_adapter_slots(rsys_model* m, int32_t* mask_out);
  * rsys_infer_select.  RSYS_ERR_ARG (out untouched): row_adapter NULL, an entry out of range or naming an incomplete slot, no batch. */
 int32_t rsys_infer_select_adapters(rsys_model* m, int32_t task, const int32_t* row_adapter, const int32_t* token_index, int64_t n_tokens,
                                    float* out, int64_t n);
+/* Training through the adapter bank: the reference's daily finetune -- four rank-8 adapters, one per medium and metric, as
+ * four sequential jobs on the same frozen trunk (Finetune/run.jl:9-13; transformer.py:591-597, 259-276) -- as ONE pass over a batch whose
+ * rows name their slot and task.
+ * rsys_adapter_train_enable (model.py:238, nn.Dropout(lora_dropout) on the LoRA input): allocates, on first use, fp32 gradients and AdamW
+ *   moments in the bank's layout and La per layer; dropout in [0, 1) applies to training passes only.  May be called again to change it.
+ * rsys_adapter_forward_backward (model.py:417-435, 493-529 + loss.backward() of train.py:259-272, per task): row r of the resident batch
+ *   runs with slot row_slot[r] in [-1, RSYS_ADAPTER_SLOTS) and task row_task[r] = medium * 2 + metric in {0,1,2,3} (the order of task_w), or
+ *   -1 / -1: the base model, no loss.  Within one call a task belongs to at most one slot.  A row of task (m, x) is masked by the finetune
+ *   rule with metric x, its masked weights of every other task are zero; loss_i and its weight sum therefore come from the rows of task i
+ *   alone and are read with rsys_losses_get / _push / _drain.  evaluate == 0: the gradient of sum_i loss_i * grad_scale is ACCUMULATED into
+ *   the slots' LoRA gradients (trunk frozen: no other gradient is formed or written); every sum has a fixed order, so a call is bitwise
+ *   reproducible and a slot's gradient does not depend on other slots' rows.  seed / step key the dropout mask (with layer and element).
+ * rsys_adapter_grad_get / rsys_adapter_zero_grad: a slot's gradient by the state-dict name of its tensor; all slots' gradients to zero.
+ * rsys_adapter_adamw_step (clip_grad_norm_ + AdamW.step + zero_grad of train.py:273-275, per slot): per_slot[n_slots][3] = {active (0 / 1),
+ *   lr factor, max_norm (<= 0: no clip)}; an active slot's tensors are scaled by min(1, max_norm / (norm + 1e-6)) of the slot's own global
+ *   norm (norms_out[n_slots], 0 for inactive slots), take one AdamW step at lr0 * factor (decoupled decay wd on every LoRA tensor, all 2-D;
+ *   bias correction by the slot's own step count) and their gradients are zeroed; the compute-type copies the forward reads are refreshed.
+ *   An inactive slot's masters, moments, step count and gradient stay bit for bit.  rsys_adapter_clear also zeroes the slot's gradient,
+ *   moments and step count: an adapter loaded into a used slot starts a fresh optimizer state (rsys_adapter_set of single tensors keeps it).
+ * rsys_adapter_adamw_state_get / _set: a slot's moments by tensor name (name NULL: only the step count), step_in < 0 leaves the count.
+ * RSYS_ERR_ARG, nothing written: an fp8, finetune = 1 or row-sharded model; training not enabled; no batch; a NULL vector; a slot out of
+ * range or incomplete; a task out of range; slot -1 with a task or a slot without one; one task named by two slots; n_slots outside
+ * [1, RSYS_ADAPTER_SLOTS]; dropout outside [0, 1). */
+int32_t rsys_adapter_train_enable(rsys_model* m, float dropout);
+int32_t rsys_adapter_forward_backward(rsys_model* m, int32_t evaluate, const int32_t* row_slot, const int32_t* row_task, float grad_scale,
+                                      uint64_t seed, uint64_t step);
+int32_t rsys_adapter_grad_get(rsys_model* m, int32_t slot, const char* name, float* out, int64_t n);
+int32_t rsys_adapter_zero_grad(rsys_model* m);
+int32_t rsys_adapter_adamw_step(rsys_model* m, float lr0, float beta1, float beta2, float eps, float wd, const float* per_slot,
+                                int32_t n_slots, float* norms_out);
+int32_t rsys_adapter_adamw_state_get(rsys_model* m, int32_t slot, const char* name, float* exp_avg, float* exp_avg_sq, int64_t n,
+                                     int32_t* step_out);
+int32_t rsys_adapter_adamw_state_set(rsys_model* m, int32_t slot, const char* name, const float* exp_avg, const float* exp_avg_sq, int64_t n,
+                                     int32_t step);
 /* Ranking forward over full-length histories through a per-user K/V cache (Finetune/embed.py:74-161).  The reference ranks a user in one
  * row of max_user_len + max_ranking_items interactions: up to max_user_len - 1 history events (token_mask_ids 0) followed by the candidates
  * (token_mask_ids n_hist + j, all at rope_input_pos n_hist).  Under the mask a history token never sees a candidate and a candidate sees the

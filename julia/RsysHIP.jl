@@ -129,6 +129,46 @@ function infer_select_adapters(m::Model, task::Integer, row_adapter::Vector{Int3
     out
 end
 
+# Training through the adapter bank (rsys.h: rsys_adapter_train_enable ...; Finetune/run.jl:9-13 as one pass): row r of the resident
+# batch runs with slot row_slot[r] on task row_task[r] = medium * 2 + metric (-1 / -1: base model, no loss)
+function batch_rows(m::Model)
+    n = Ref{Int32}(0)
+    check(ccall((:rsys_batch_rows, LIB), Int32, (Ptr{Cvoid}, Ref{Int32}), m.h, n))
+    Int(n[])
+end
+adapter_train_enable(m::Model, dropout::Real) = check(ccall((:rsys_adapter_train_enable, LIB), Int32, (Ptr{Cvoid}, Float32), m.h, dropout))
+function adapter_forward_backward(m::Model, evaluate::Bool, row_slot::Vector{Int32}, row_task::Vector{Int32}, grad_scale::Real, seed::Integer, step::Integer)
+    GC.@preserve row_slot row_task check(ccall((:rsys_adapter_forward_backward, LIB), Int32,
+                                               (Ptr{Cvoid}, Int32, Ptr{Int32}, Ptr{Int32}, Float32, UInt64, UInt64),
+                                               m.h, evaluate ? 1 : 0, row_slot, row_task, grad_scale, seed, step))
+end
+function adapter_grad!(m::Model, slot::Integer, name::String, out::Array{Float32})
+    GC.@preserve out check(ccall((:rsys_adapter_grad_get, LIB), Int32, (Ptr{Cvoid}, Int32, Cstring, Ptr{Float32}, Int64), m.h, slot, name, out, length(out)))
+    out
+end
+adapter_zero_grad(m::Model) = check(ccall((:rsys_adapter_zero_grad, LIB), Int32, (Ptr{Cvoid},), m.h))
+# per_slot: 3 x n_slots (active, lr factor, max_norm per column); returns the slots' gradient norms
+function adapter_adamw_step(m::Model, lr0::Real, beta1::Real, beta2::Real, eps::Real, wd::Real, per_slot::Matrix{Float32})
+    n = size(per_slot, 2)
+    norms = Vector{Float32}(undef, n)
+    GC.@preserve per_slot norms check(ccall((:rsys_adapter_adamw_step, LIB), Int32,
+                                            (Ptr{Cvoid}, Float32, Float32, Float32, Float32, Float32, Ptr{Float32}, Int32, Ptr{Float32}),
+                                            m.h, lr0, beta1, beta2, eps, wd, per_slot, n, norms))
+    norms
+end
+function adapter_adamw_state!(m::Model, slot::Integer, name::String, exp_avg::Array{Float32}, exp_avg_sq::Array{Float32})
+    step = Ref{Int32}(0)
+    GC.@preserve exp_avg exp_avg_sq check(ccall((:rsys_adapter_adamw_state_get, LIB), Int32,
+                                                (Ptr{Cvoid}, Int32, Cstring, Ptr{Float32}, Ptr{Float32}, Int64, Ref{Int32}),
+                                                m.h, slot, name, exp_avg, exp_avg_sq, length(exp_avg), step))
+    step[]
+end
+function set_adapter_adamw_state!(m::Model, slot::Integer, name::String, exp_avg::Array{Float32}, exp_avg_sq::Array{Float32}, step::Integer)
+    GC.@preserve exp_avg exp_avg_sq check(ccall((:rsys_adapter_adamw_state_set, LIB), Int32,
+                                                (Ptr{Cvoid}, Int32, Cstring, Ptr{Float32}, Ptr{Float32}, Int64, Int32),
+                                                m.h, slot, name, exp_avg, exp_avg_sq, length(exp_avg), step))
+end
+
 # Full-length ranking through a per-user K/V cache of the history (rsys.h: rsys_rank_cache_*).  row_adapter may be `nothing` (base model).
 rank_cache_reserve(m::Model, n_slots::Integer) = check(ccall((:rsys_rank_cache_reserve, LIB), Int32, (Ptr{Cvoid}, Int32), m.h, n_slots))
 function rank_cache_store(m::Model, row_adapter::Union{Nothing, Vector{Int32}}, n_hist::Vector{Int32}, slot::Vector{Int32})

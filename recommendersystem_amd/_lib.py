@@ -142,6 +142,14 @@ _SIGS = [
     ("rsys_adapter_clear", C.c_int32, [_P, C.c_int32]),
     ("rsys_adapter_slots", C.c_int32, [_P, C.POINTER(C.c_int32)]),
     ("rsys_infer_select_adapters", C.c_int32, [_P, C.c_int32, _P, _P, C.c_int64, _P, C.c_int64]),
+    ("rsys_batch_rows", C.c_int32, [_P, C.POINTER(C.c_int32)]),
+    ("rsys_adapter_train_enable", C.c_int32, [_P, C.c_float]),
+    ("rsys_adapter_forward_backward", C.c_int32, [_P, C.c_int32, _P, _P, C.c_float, C.c_uint64, C.c_uint64]),
+    ("rsys_adapter_grad_get", C.c_int32, [_P, C.c_int32, C.c_char_p, _P, C.c_int64]),
+    ("rsys_adapter_zero_grad", C.c_int32, [_P]),
+    ("rsys_adapter_adamw_step", C.c_int32, [_P, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, _P, C.c_int32, _P]),
+    ("rsys_adapter_adamw_state_get", C.c_int32, [_P, C.c_int32, C.c_char_p, _P, _P, C.c_int64, C.POINTER(C.c_int32)]),
+    ("rsys_adapter_adamw_state_set", C.c_int32, [_P, C.c_int32, C.c_char_p, _P, _P, C.c_int64, C.c_int32]),
     ("rsys_rank_cache_reserve", C.c_int32, [_P, C.c_int32]),
     ("rsys_rank_cache_store", C.c_int32, [_P, _P, _P, _P]),
     ("rsys_rank_cache_candidates", C.c_int32, [_P, _P, _P, _P, _P]),

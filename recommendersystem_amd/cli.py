@@ -90,12 +90,53 @@ def load_checkpoint_blob(path):
     return blob, json.loads(bytes(np.asarray(blob["config"], np.uint8)).decode())
 
 
+def finetune_all(args):
+    """`--finetune CKPT --finetune_all`: the reference's four sequential finetune jobs (Finetune/run.jl:9-13; transformer.py:591-597:
+    16 rows per micro-batch, accumulation 2, constant schedule, two epochs of patience) as one run on one base model.  Every task has
+    its own bank slot, FinetuneDataset (rows of its medium), scheduler, stopper and metrics CSV; one joint pass serves the active
+    slots.  Writes {datadir}/finetune_all/base.npz and {m}.{metric}.lora.npz, the files of `checkpoint dedup` that serve.get_models
+    reads."""
+    from .optim import AdapterAdamW
+    assert args.finetune is not None, "--finetune_all needs --finetune CKPT"
+    log = lambda *a: print(*a, file=sys.stderr, flush=True)
+    blob, config = load_checkpoint_blob(args.finetune)
+    config.update(learning_rate=2e-4, finetune=False, forward="train")
+    run = rtrain.get_run_config(True)
+    local_batch = args.local_batch_size or run["local_batch_size"]
+    global_batch = args.global_batch_size or run["global_batch_size"]
+    assert global_batch % local_batch == 0
+    num_epochs = args.num_epochs or run["num_epochs"]
+    transdir = "transformer_mini" if args.mini else "transformer"
+    tasks = list(enumerate(rtrain.ADAPTER_TASKS))                      # slot s = task s: the order serve.get_models loads them in
+    loaders = {split: {s: rdata.Prefetch(rdata.FinetuneDataset(f"{args.datadir}/{transdir}/{split}", 0, 1, local_batch, split == "training", m))
+                       for s, (m, _) in tasks} for split in ("training", "test")}
+    model = RecommenderModel(config, device=0, dtype=args.dtype, max_rows=local_batch * len(tasks))
+    model.load_pretrained_embeddings(args.datadir)
+    trunk = {k[len("model/"):]: v for k, v in blob.items() if k.startswith("model/") and "lora_" not in k}
+    model.load_state_dict(trunk, strict=False)
+    rng = np.random.default_rng(0x1217)
+    for s, _ in tasks:                                                 # LoRA init (model.py:251-254): A ~ N(0, 0.006^2), B = 0
+        model.load_adapter(s, {n: (rng.standard_normal(shape) * 0.006).astype(np.float32) if "lora_A" in n else np.zeros(shape, np.float32)
+                               for n, shape in model.adapter_names()})
+    model.enable_adapter_training(float(config.get("lora_dropout", 0.1)))
+    optimizer = AdapterAdamW(model, lr=config["learning_rate"], slots=[s for s, _ in tasks])
+    runs = rtrain.make_adapter_runs([(s, s) for s, _ in tasks], config)
+    history = rtrain.train_adapters(model, optimizer, runs, loaders, config, os.path.join(args.datadir, "finetune_all"), num_epochs,
+                                    global_batch // local_batch, log=log,
+                                    base_blob={k: v for k, v in blob.items() if k.startswith("model/") and "lora_" not in k})
+    model.close()
+    return history
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="recommendersystem_amd.cli")
     ap.add_argument("--datadir", type=str, required=True)
     ap.add_argument("--finetune", type=str, default=None)
     ap.add_argument("--finetune_medium", type=int, default=None)
     ap.add_argument("--finetune_metric", type=str, default=None)
+    ap.add_argument("--finetune_all", action="store_true",
+                    help="with --finetune CKPT: train the four (medium, metric) adapters in one run through the adapter bank of one base "
+                         "model (Finetune/run.jl:9-13 as one job) and write base.npz + four {m}.{metric}.lora.npz (DESIGN 4y)")
     ap.add_argument("--mini", action="store_true")
     ap.add_argument("--prod", action="store_true")
     ap.add_argument("--model", default="prod", help="prod (transformer.py:536-558) or a workload.make_config name")
@@ -117,6 +158,8 @@ def main(argv=None):
         raw = list(sys.argv[1:] if argv is None else argv)
         sys.exit(rdist.launch_local(args.nproc_per_node, [sys.executable, "-m", "recommendersystem_amd.cli"] + raw))
 
+    if args.finetune_all:
+        return finetune_all(args)
     rank, world, local_rank = rdist.env_rank()
     local_world = int(os.environ.get("LOCAL_WORLD_SIZE", world))
     log = (lambda *a: print(*a, file=sys.stderr, flush=True)) if local_rank == 0 else (lambda *a: None)

@@ -18,10 +18,23 @@ struct AdapterBank {
   int* d_rows = nullptr;                  // [rows_max] slot per batch row of the current call
   std::vector<unsigned char> have[RSYS_ADAPTER_SLOTS];   // per slot: tensor (4 l + {qA, qB, vA, vB}) has been set since the last clear
   bool any_row = false;                   // the current call names at least one slot
+  // ---- training through the bank (allocated by rsys_adapter_train_enable)
+  bool train = false;
+  float dropout = 0.f;                    // nn.Dropout(p) on the LoRA input, training passes only
+  bool drop_now = false;                  // the current pass draws masks (keyed on m->drop_seed, m->drop_step, layer, element)
+  float *gA = nullptr, *gB = nullptr;     // fp32 gradients in the masters' layouts
+  float *mA = nullptr, *vA = nullptr, *mB = nullptr, *vB = nullptr;   // AdamW moments, same layouts
+  int step[RSYS_ADAPTER_SLOTS] = {0, 0, 0, 0, 0, 0, 0, 0};            // per-slot step count (bias correction)
+  void* La_l = nullptr;                   // [L][rows_max * 2S][16] compute type: La of every layer, kept for the backward
+  void* dLa = nullptr;                    // [rows_max * 2S][16] compute type: of the layer the backward is in
+  float *partA = nullptr, *partB = nullptr;   // per-row partial gradients of that layer: [rows_max][16][D], [rows_max][Nq + Nv][8]
+  int* d_task = nullptr;                  // [rows_max] task per batch row of the current call
+  float* d_norms = nullptr;               // [RSYS_ADAPTER_SLOTS] the optimizer step's per-slot gradient norms
 };
 
 static inline int64_t bank_a_floats(const Model* m) { return (int64_t)16 * m->D; }
 static inline int64_t bank_b_floats(const Model* m) { return (int64_t)(m->H + m->KV) * m->hd * 8; }
+template <typename T> static inline T* bank_la(const Model* m, int l) { return (T*)m->bank->La_l + (int64_t)l * m->rows_max * m->T * 16; }   // layer l's La of a training pass
 
 // ------------------------------------------------------------------ kernels
 template <typename T> __device__ __forceinline__ void load8(const T* p, float (&v)[8]);
@@ -154,6 +167,308 @@ __global__ __launch_bounds__(256) void adapter_bank_b_kernel(const T* __restrict
   }
 }
 
+
+// ------------------------------------------------------------------ training through the bank
+// nn.Dropout of the LoRA input (model.py:238,265,269) drawn where it is used instead of in a pass of its own: element e of the layer's
+// [tokens][D] input is kept iff u01(Philox(seed)(e >> 2, stream)[e & 3]) >= p -- launch_dropout's mask, with stream = step * 64 + layer.
+// The forward (stage A) and the two backward kernels that need drop(xn) or drop' call the same function with the same key.
+struct BankDrop {
+  float p, keep; Philox ph; unsigned int stream;
+  __device__ BankDrop(float p_, unsigned long long seed, unsigned int stream_) : p(p_), keep(1.f / (1.f - p_)), ph(seed), stream(stream_) {}
+  // mask factors (keep or 0) of the 4 elements [4 q, 4 q + 4)
+  __device__ __forceinline__ void quad(long long q, float (&f)[4]) const {
+    uint32_t r[4];
+    ph.gen((unsigned long long)q, stream, r);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) f[k] = u01(r[k]) >= p ? keep : 0.f;
+  }
+  __device__ __forceinline__ float one(long long e) const {
+    uint32_t r[4];
+    ph.gen((unsigned long long)(e >> 2), stream, r);
+    return u01(r[e & 3]) >= p ? keep : 0.f;
+  }
+};
+// drop(x) of one fragment of E consecutive elements starting at element e0 (a multiple of 4), rounded to T as launch_dropout stores it
+__device__ __forceinline__ bf16x8 bank_drop_frag(bf16x8 x, long long e0, const BankDrop& dr) {
+  float f0[4], f1[4];
+  dr.quad(e0 >> 2, f0); dr.quad((e0 >> 2) + 1, f1);
+#pragma unroll
+  for (int k = 0; k < 4; ++k) { x[k] = (bf16)((float)x[k] * f0[k]); x[4 + k] = (bf16)((float)x[4 + k] * f1[k]); }
+  return x;
+}
+__device__ __forceinline__ float4 bank_drop_frag(float4 x, long long e0, const BankDrop& dr) {
+  float f[4];
+  dr.quad(e0 >> 2, f);
+  return make_float4(x.x * f[0], x.y * f[1], x.z * f[2], x.w * f[3]);
+}
+// E elements `stride` apart as one fragment (operands whose contraction index is not the contiguous one)
+__device__ __forceinline__ bf16x8 bank_gather(const bf16* p, long long stride) {
+  bf16x8 x;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) x[k] = p[k * stride];
+  return x;
+}
+__device__ __forceinline__ float4 bank_gather(const float* p, long long stride) { return make_float4(p[0], p[stride], p[2 * stride], p[3 * stride]); }
+__device__ __forceinline__ void bank_frag_mul(bf16x8& x, int k, float f) { x[k] = (bf16)((float)x[k] * f); }
+__device__ __forceinline__ void bank_frag_mul(float4& x, int k, float f) { ((float*)&x)[k] *= f; }
+
+// stage A of a training pass: adapter_bank_a_kernel with the LoRA input under the dropout mask (p == 0: the same sums) and the layer's own La
+template <typename T>
+__global__ __launch_bounds__(256) void adapter_bank_a_train_kernel(const T* __restrict__ xn, const T* __restrict__ bankA, const int* __restrict__ row_slot,
+                                                                   int layer, int L, int D, int Ttok, T* __restrict__ La, float p,
+                                                                   unsigned long long seed, unsigned int stream) {
+  using MM = BankMma<T>;
+  __shared__ float red[4][4][64];
+  const int row = blockIdx.y, slot = row_slot[row];
+  if (slot < 0) return;
+  const BankDrop dr(p, seed, stream);
+  const int t0 = blockIdx.x * BANK_A_TOK;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int r = lane & 15, kq = lane >> 4;
+  const bool tok_ok = t0 + r < Ttok;
+  const long long tok = (long long)row * Ttok + (tok_ok ? t0 + r : 0);
+  const T* xr = xn + tok * D;
+  const T* ar = bankA + (((long long)slot * L + layer) * 16 + r) * D;
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+  for (int k0 = w * MM::KS; k0 < D; k0 += 4 * MM::KS) {
+    const int k = k0 + kq * MM::E;
+    const bool k_ok = k < D;
+    typename MM::Frag xa = (tok_ok && k_ok) ? MM::load(xr + k) : MM::zero();
+    if (p > 0.f && tok_ok && k_ok) xa = bank_drop_frag(xa, tok * D + k, dr);
+    const typename MM::Frag ab = k_ok ? MM::load(ar + k) : MM::zero();
+    acc = MM::mma(xa, ab, acc);
+  }
+#pragma unroll
+  for (int i = 0; i < 4; ++i) red[w][i][lane] = acc[i];
+  __syncthreads();
+  const float sum = ((red[0][w][lane] + red[1][w][lane]) + red[2][w][lane]) + red[3][w][lane];
+  const int tk = t0 + 4 * kq + w;
+  if (tk < Ttok) La[((long long)row * Ttok + tk) * 16 + r] = from_f32<T>(sum);
+}
+
+// dLa[t, 0:8] = 2 dq_t . B_q[slot], dLa[t, 8:16] = 2 dv_t . B_v[slot] (the un-rotated dqkv the finetune model's gemm_lora_dla reads; rounded
+// to the compute type as that GEMM stores it).  grid (ceil(2S / 16), rows), 256 threads: stage A's tile -- tokens on the rows, the 16
+// LoRA columns on the columns -- with K = the q columns, then the v columns; B is [column][8], so its fragment is gathered 8 apart and
+// is zero on the half of the LoRA columns the segment does not feed.  The four waves split the K steps, partial tiles added in wave order.
+template <typename T>
+__global__ __launch_bounds__(256) void adapter_bank_dla_kernel(const T* __restrict__ dqkv, const T* __restrict__ bankB, const int* __restrict__ row_slot,
+                                                               int layer, int L, int Nq, int Nk, int Nv, int Ttok, T* __restrict__ dLa) {
+  using MM = BankMma<T>;
+  __shared__ float red[4][4][64];
+  const int row = blockIdx.y, slot = row_slot[row];
+  if (slot < 0) return;
+  const int t0 = blockIdx.x * BANK_A_TOK;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int r = lane & 15, kq = lane >> 4;
+  const bool tok_ok = t0 + r < Ttok;
+  const int ld = Nq + Nk + Nv;
+  const T* gr = dqkv + ((long long)row * Ttok + (tok_ok ? t0 + r : 0)) * ld;
+  const T* bb = bankB + ((long long)slot * L + layer) * (long long)(Nq + Nv) * 8;
+  const int sq = (Nq + MM::KS - 1) / MM::KS, sv = (Nv + MM::KS - 1) / MM::KS;
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+  for (int st = w; st < sq + sv; st += 4) {
+    const bool isq = st < sq;
+    const int k = (isq ? st : st - sq) * MM::KS + kq * MM::E;   // column inside the segment (8 | Nq, Nv: a fragment is inside or past it)
+    const bool k_ok = k < (isq ? Nq : Nv);
+    const typename MM::Frag ga = (tok_ok && k_ok) ? MM::load(gr + (isq ? k : Nq + Nk + k)) : MM::zero();
+    const bool mine = isq ? r < 8 : r >= 8;                     // this lane's LoRA column is fed by this segment
+    const typename MM::Frag bf = (k_ok && mine) ? bank_gather(bb + (long long)(isq ? k : Nq + k) * 8 + (r & 7), 8) : MM::zero();
+    acc = MM::mma(ga, bf, acc);
+  }
+#pragma unroll
+  for (int i = 0; i < 4; ++i) red[w][i][lane] = acc[i];
+  __syncthreads();
+  const float sum = ((red[0][w][lane] + red[1][w][lane]) + red[2][w][lane]) + red[3][w][lane];
+  const int tk = t0 + 4 * kq + w;
+  if (tk < Ttok) dLa[((long long)row * Ttok + tk) * 16 + r] = from_f32<T>(2.f * sum);   // lora_scaling = 2 on the fp32 sum
+}
+
+// dxn[t, :] += drop'(dLa[t, :] . [A_q; A_v][slot]) (K = 16: no MFMA).  grid (2S / 8, rows), 256 threads, an item = 8 columns of one
+// token.  Rounding as the finetune model's gemm_lora_dx: without dropout the fp32 sum is added to dxn; with it the sum is rounded to the
+// compute type first (that model stores it), masked and scaled, then added.
+template <typename T>
+__global__ __launch_bounds__(256) void adapter_bank_dx_kernel(const T* __restrict__ dLa, const T* __restrict__ bankA, const int* __restrict__ row_slot,
+                                                              int layer, int L, int D, int Ttok, T* __restrict__ dxn, float p,
+                                                              unsigned long long seed, unsigned int stream) {
+  const int row = blockIdx.y, slot = row_slot[row];
+  if (slot < 0) return;
+  const BankDrop dr(p, seed, stream);
+  const int t0 = blockIdx.x * BANK_B_TOK;
+  const int ntok = min(BANK_B_TOK, Ttok - t0);
+  const int G = D >> 3;
+  const T* aa = bankA + ((long long)slot * L + layer) * 16 * (long long)D;
+  for (int i = threadIdx.x; i < ntok * G; i += 256) {
+    const int tl = i / G, c = (i - tl * G) * 8;
+    const long long t = (long long)row * Ttok + t0 + tl;
+    float g0[8], g1[8], u[8], old[8];
+    load8<T>(dLa + t * 16, g0); load8<T>(dLa + t * 16 + 8, g1);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) u[k] = 0.f;
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+      float a[8];
+      load8<T>(aa + (long long)j * D + c, a);
+      const float g = j < 8 ? g0[j] : g1[j - 8];
+#pragma unroll
+      for (int k = 0; k < 8; ++k) u[k] = fmaf(g, a[k], u[k]);
+    }
+    if (p > 0.f) {
+      float f0[4], f1[4];
+      const long long e0 = t * D + c;
+      dr.quad(e0 >> 2, f0); dr.quad((e0 >> 2) + 1, f1);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) { u[k] = to_f32(from_f32<T>(u[k])) * f0[k]; u[4 + k] = to_f32(from_f32<T>(u[4 + k])) * f1[k]; }
+    }
+    T* dst = dxn + t * D + c;
+    load8<T>(dst, old);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) u[k] += old[k];
+    store8<T>(dst, u);
+  }
+}
+
+// Per-row partial of dA: partA[row][j][d] = sum over the row's tokens t, ascending, of dLa[t][j] drop(xn)[t][d].  grid (ceil(D / 64), rows),
+// 256 threads: every wave owns 16 columns d and the whole contraction (K = 2S tokens), so a partial has one fixed order and no
+// cross-wave sum.  MFMA tile: the 16 LoRA rows j on the rows, d on the columns; both operands have the token as their OUTER index, so
+// the fragments are gathered (16 resp. D apart).
+template <typename T>
+__global__ __launch_bounds__(256) void adapter_bank_da_kernel(const T* __restrict__ dLa, const T* __restrict__ xn, const int* __restrict__ row_slot,
+                                                              int D, int Ttok, float* __restrict__ partA, float p, unsigned long long seed,
+                                                              unsigned int stream) {
+  using MM = BankMma<T>;
+  const int row = blockIdx.y;
+  if (row_slot[row] < 0) return;
+  const BankDrop dr(p, seed, stream);
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int d0 = (blockIdx.x * 4 + w) * 16;
+  if (d0 >= D) return;   // (D % 16 == 0; no barrier below)
+  const int r = lane & 15, kq = lane >> 4;
+  const long long tb = (long long)row * Ttok;
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+  for (int k0 = 0; k0 < Ttok; k0 += MM::KS) {
+    const int k = k0 + kq * MM::E;
+    const bool k_ok = k < Ttok;   // (2S % 8 == 0: a fragment's tokens are inside the row or all past it)
+    typename MM::Frag ga = MM::zero(), xb = MM::zero();
+    if (k_ok) {
+      ga = bank_gather(dLa + (tb + k) * 16 + r, 16);
+      xb = bank_gather(xn + (tb + k) * D + d0 + r, D);
+      if (p > 0.f) {
+#pragma unroll
+        for (int i = 0; i < MM::E; ++i) bank_frag_mul(xb, i, dr.one((tb + k + i) * D + d0 + r));
+      }
+    }
+    acc = MM::mma(ga, xb, acc);
+  }
+  float* dst = partA + (long long)row * 16 * D;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) dst[(long long)(4 * kq + i) * D + d0 + r] = acc[i];
+}
+
+// Per-row partial of dB: partB[row][c][j] = sum over the row's tokens, ascending, of dqv[t][c] La[t][j (q columns) | 8 + j (v columns)]
+// (the factor 2 is applied when the rows are added).  grid (ceil((Nq + Nv) / 64), rows), 256 threads; a wave owns 16 columns c of
+// [dq | dv] and the whole contraction; the tile's 16 columns are La's, of which a q (v) row keeps the first (last) 8.
+template <typename T>
+__global__ __launch_bounds__(256) void adapter_bank_db_kernel(const T* __restrict__ dqkv, const T* __restrict__ La, const int* __restrict__ row_slot,
+                                                              int Nq, int Nk, int Nv, int Ttok, float* __restrict__ partB) {
+  using MM = BankMma<T>;
+  const int row = blockIdx.y;
+  if (row_slot[row] < 0) return;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int c0 = (blockIdx.x * 4 + w) * 16;
+  if (c0 >= Nq + Nv) return;
+  const int r = lane & 15, kq = lane >> 4;
+  const int ld = Nq + Nk + Nv;
+  const long long tb = (long long)row * Ttok;
+  const int ca = c0 + r;                              // this lane's row of the tile as the A operand
+  const bool ca_ok = ca < Nq + Nv;
+  const int col = ca < Nq ? ca : ca + Nk;            // its column of dqkv
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+  for (int k0 = 0; k0 < Ttok; k0 += MM::KS) {
+    const int k = k0 + kq * MM::E;
+    const bool k_ok = k < Ttok;
+    const typename MM::Frag ga = (k_ok && ca_ok) ? bank_gather(dqkv + (tb + k) * ld + col, ld) : MM::zero();
+    const typename MM::Frag lb = k_ok ? bank_gather(La + (tb + k) * 16 + r, 16) : MM::zero();
+    acc = MM::mma(ga, lb, acc);
+  }
+  float* dst = partB + (long long)row * (Nq + Nv) * 8;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int c = c0 + 4 * kq + i;
+    if (c >= Nq + Nv) continue;
+    const bool isq = c < Nq;
+    if (isq ? r < 8 : r >= 8) dst[(long long)c * 8 + (r & 7)] = acc[i];
+  }
+}
+
+// g[slot][layer][e] += alpha * (sum of part[row][e] over the rows of `slot`, in row order): one thread per element, the fixed order that
+// makes a call reproducible and a slot's gradient independent of the other slots' rows.  A slot without a row is not touched.
+__global__ __launch_bounds__(256) void adapter_bank_rows_reduce_kernel(const float* __restrict__ part, const int* __restrict__ row_slot, int rows,
+                                                                       long long n, float alpha, float* __restrict__ g, long long slot_stride) {
+  const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (e >= n) return;
+  for (int a = 0; a < RSYS_ADAPTER_SLOTS; ++a) {
+    float acc = 0.f; bool any = false;
+    for (int r = 0; r < rows; ++r)
+      if (row_slot[r] == a) { acc += part[(long long)r * n + e]; any = true; }
+    if (any) g[(long long)a * slot_stride + e] += alpha * acc;
+  }
+}
+
+// The bank's optimizer step (clip_grad_norm_ + AdamW.step + zero_grad of train.py:273-275 per adapter): one workgroup of 1024 threads
+// per slot.  Phase 1: the slot's sum of squared gradients, A tensors then B tensors, every thread its strided share in ascending
+// order, then one fixed tree -- the slot's own global norm.  Phase 2: g * min(1, max_norm / (norm + 1e-6)), the AdamW update of
+// optim.hip's adamw_kernel (decoupled decay on every tensor: all LoRA tensors are 2-D), zeroed gradient, refreshed compute-type copy.
+struct BankStepRec { int active; float lr, max_norm, bc1, bc2_sqrt; };
+struct BankStepArgs { BankStepRec rec[RSYS_ADAPTER_SLOTS]; };
+template <typename T>
+__global__ __launch_bounds__(1024) void adapter_bank_adamw_kernel(float* A32, float* B32, float* gA, float* gB, float* mA, float* vA, float* mB, float* vB,
+                                                                  T* A, T* B, long long nA, long long nB, BankStepArgs args, float b1, float b2,
+                                                                  float eps, float wd, float* __restrict__ norms) {
+  __shared__ float red[16];
+  __shared__ float s_coef;
+  const int slot = blockIdx.x;
+  const BankStepRec rc = args.rec[slot];
+  if (!rc.active) { if (threadIdx.x == 0) norms[slot] = 0.f; return; }   // (uniform per workgroup) nothing of this slot is read or written
+  float acc = 0.f;
+  for (int part = 0; part < 2; ++part) {
+    const float* g = part == 0 ? gA + slot * nA : gB + slot * nB;
+    const long long n = part == 0 ? nA : nB;
+    for (long long i = threadIdx.x; i < n; i += 1024) acc = fmaf(g[i], g[i], acc);
+  }
+  // fixed tree: lanes of a wave by shuffles, the 16 waves through LDS in wave order
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o, 64);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float ss = 0.f;
+    for (int k = 0; k < 16; ++k) ss += red[k];
+    const float norm = sqrtf(ss);
+    norms[slot] = norm;
+    float c = 1.f;
+    if (rc.max_norm > 0.f) { c = rc.max_norm / (norm + 1e-6f); c = c < 1.f ? c : 1.f; }
+    s_coef = c;
+  }
+  __syncthreads();
+  const float coef = s_coef, decay = 1.f - rc.lr * wd;
+  for (int part = 0; part < 2; ++part) {
+    const long long n = part == 0 ? nA : nB, off = slot * n;
+    float* p = (part == 0 ? A32 : B32) + off; float* g = (part == 0 ? gA : gB) + off;
+    float* mm = (part == 0 ? mA : mB) + off; float* vv = (part == 0 ? vA : vB) + off;
+    T* sh = part == 0 ? A : B;
+    for (long long i = threadIdx.x; i < n; i += 1024) {
+      const float gk = g[i] * coef;
+      const float pk = p[i] * decay;
+      const float m1 = b1 * mm[i] + (1.f - b1) * gk;
+      const float v1 = b2 * vv[i] + (1.f - b2) * gk * gk;
+      const float denom = sqrtf(v1) / rc.bc2_sqrt + eps;
+      const float pn = pk - (rc.lr / rc.bc1) * (m1 / denom);
+      p[i] = pn; mm[i] = m1; vv[i] = v1; g[i] = 0.f;
+      if (sh != nullptr) sh[off + i] = from_f32<T>(pn);
+    }
+  }
+}
+
 // ------------------------------------------------------------------ bank storage
 static int bank_check_model(const Model* m) {
   ARG_CHECK(!m->cfg.finetune, "adapter bank: a finetune = 1 model owns one adapter as its trainable parameters; the bank lives on a base model");
@@ -236,6 +551,11 @@ int adapter_clear(Model* m, int slot) {
   HIP_CHECK(hipMemset(b->A32 + slot * na, 0, (size_t)na * 4)); HIP_CHECK(hipMemset(b->B32 + slot * nb, 0, (size_t)nb * 4));
   if (m->bf16_mode) { HIP_CHECK(hipMemset((bf16*)b->A + slot * na, 0, (size_t)na * 2)); HIP_CHECK(hipMemset((bf16*)b->B + slot * nb, 0, (size_t)nb * 2)); }
   std::fill(b->have[slot].begin(), b->have[slot].end(), 0);
+  if (b->train) {   // the slot's optimizer state belongs to the adapter that leaves: the next one starts from zero moments and step 0
+    for (float* p : {b->gA, b->mA, b->vA}) HIP_CHECK(hipMemset(p + slot * na, 0, (size_t)na * 4));
+    for (float* p : {b->gB, b->mB, b->vB}) HIP_CHECK(hipMemset(p + slot * nb, 0, (size_t)nb * 4));
+    b->step[slot] = 0;
+  }
   return RSYS_OK;
 }
 
@@ -276,6 +596,10 @@ int adapter_bank_stage_a(Model* m, int l, const T* xn) {
   const AdapterBank* b = m->bank;
   const int rows = m->cur_rows;
   tic(m, "hbm_adapter_bank_a", (double)sizeof(T) * rows * m->T * (m->D + 16.0));
+  if (m->bank_train)   // the layer's own La (the backward reads it), the LoRA input under this pass's dropout mask
+    hipLaunchKernelGGL((adapter_bank_a_train_kernel<T>), dim3((m->T + BANK_A_TOK - 1) / BANK_A_TOK, rows), dim3(256), 0, m->stream, xn, (const T*)b->A,
+                       m->bank_rows, l, m->L, m->D, m->T, bank_la<T>(m, l), b->drop_now ? b->dropout : 0.f, m->drop_seed, (unsigned int)(m->drop_step * 64 + l));
+  else
   hipLaunchKernelGGL((adapter_bank_a_kernel<T>), dim3((m->T + BANK_A_TOK - 1) / BANK_A_TOK, rows), dim3(256), 0, m->stream, xn, (const T*)b->A,
                      m->bank_rows, l, m->L, m->D, m->T, (T*)b->La);
   HIP_CHECK(hipGetLastError());
@@ -287,7 +611,8 @@ int adapter_bank_stage_b(Model* m, int l, T* qkv, const int* rope_pos) {
   const AdapterBank* b = m->bank;
   const int rows = m->cur_rows, Nq = m->H * m->hd, Nk = m->KV * m->hd;
   tic(m, "hbm_adapter_bank_b", (double)sizeof(T) * rows * m->T * (2.0 * (Nq + Nk) + 16.0));
-  hipLaunchKernelGGL((adapter_bank_b_kernel<T>), dim3((m->T + BANK_B_TOK - 1) / BANK_B_TOK, rows), dim3(256), 0, m->stream, (const T*)b->La,
+  hipLaunchKernelGGL((adapter_bank_b_kernel<T>), dim3((m->T + BANK_B_TOK - 1) / BANK_B_TOK, rows), dim3(256), 0, m->stream,
+                     m->bank_train ? (const T*)bank_la<T>(m, l) : (const T*)b->La,
                      (const T*)b->B, m->bank_rows, l, m->L, Nq, Nk, Nk, m->T, m->hd, m->rope_cos, m->rope_sin, rope_pos, qkv);
   HIP_CHECK(hipGetLastError());
   toc(m);
@@ -297,5 +622,198 @@ template int adapter_bank_stage_a<float>(Model*, int, const float*);
 template int adapter_bank_stage_a<bf16>(Model*, int, const bf16*);
 template int adapter_bank_stage_b<float>(Model*, int, float*, const int*);
 template int adapter_bank_stage_b<bf16>(Model*, int, bf16*, const int*);
+
+// ------------------------------------------------------------------ training through the bank: host side
+static int bank_train_check_model(const Model* m) {
+  RC(bank_check_model(m));
+  ARG_CHECK(!m->sharded, "adapter bank training: a model with a replicated item table");
+  return RSYS_OK;
+}
+
+int adapter_train_enable(Model* m, float dropout) {
+  RC(bank_train_check_model(m));
+  ARG_CHECK(dropout >= 0.f && dropout < 1.f, "adapter bank training: dropout must be in [0, 1)");
+  ARG_CHECK(m->T % 8 == 0 && m->D % 16 == 0 && m->hd % 8 == 0, "adapter bank training: 2 S % 8, embed_dim % 16 and head_dim % 8 must be 0");
+  RC(bank_ensure(m));
+  AdapterBank* b = m->bank;
+  HIP_CHECK(hipSetDevice(m->device));
+  if (!b->train) {
+    const int64_t na = (int64_t)RSYS_ADAPTER_SLOTS * m->L * bank_a_floats(m), nb = (int64_t)RSYS_ADAPTER_SLOTS * m->L * bank_b_floats(m);
+    const int64_t tok = (int64_t)m->rows_max * m->T;
+    // (every buffer once: a call that failed part-way is taken up where it stopped)
+#define BANK_ONCE(ptr, bytes) do { if ((ptr) == nullptr) DALLOC(ptr, bytes); } while (0)
+    BANK_ONCE(b->gA, na * 4); BANK_ONCE(b->gB, nb * 4);
+    BANK_ONCE(b->mA, na * 4); BANK_ONCE(b->vA, na * 4); BANK_ONCE(b->mB, nb * 4); BANK_ONCE(b->vB, nb * 4);
+    BANK_ONCE(b->La_l, (int64_t)m->L * tok * 16 * m->esz); BANK_ONCE(b->dLa, tok * 16 * m->esz);
+    BANK_ONCE(b->partA, (int64_t)m->rows_max * bank_a_floats(m) * 4); BANK_ONCE(b->partB, (int64_t)m->rows_max * bank_b_floats(m) * 4);
+    BANK_ONCE(b->d_task, (int64_t)m->rows_max * 4); BANK_ONCE(b->d_norms, RSYS_ADAPTER_SLOTS * 4);
+    BANK_ONCE(m->bank_sink, (int64_t)std::max(m->D, 64) * 4);
+#undef BANK_ONCE
+    // the pass runs with every sum of the trunk in a fixed order too, whatever the model's own setting: it needs that mode's scratch
+    RC(model_ensure_det_scratch(m));
+    b->train = true;
+  }
+  b->dropout = dropout;
+  return RSYS_OK;
+}
+
+int adapter_forward_backward(Model* m, int evaluate, const int32_t* row_slot, const int32_t* row_task, float grad_scale, uint64_t seed, uint64_t step) {
+  RC(bank_train_check_model(m));
+  ARG_CHECK(m->bank != nullptr && m->bank->train, "adapter bank training is not enabled (rsys_adapter_train_enable)");
+  ARG_CHECK(m->cur_rows > 0, "no batch uploaded");
+  ARG_CHECK(row_slot != nullptr && row_task != nullptr, "row_slot / row_task is null");
+  int owner[4] = {-1, -1, -1, -1};
+  bool any = false;
+  for (int r = 0; r < m->cur_rows; ++r) {
+    const int s = row_slot[r], t = row_task[r];
+    ARG_CHECK(s >= -1 && s < RSYS_ADAPTER_SLOTS, "row_slot entries must be in [-1, RSYS_ADAPTER_SLOTS)");
+    ARG_CHECK(t >= -1 && t < 4, "row_task entries must be in [-1, 4)");
+    ARG_CHECK((s < 0) == (t < 0), "a row names a slot and a task, or neither (-1 / -1)");
+    if (s < 0) continue;
+    ARG_CHECK(bank_complete(m, s), "row_slot names a slot that is not complete (4 tensors per layer since its last clear)");
+    ARG_CHECK(owner[t] < 0 || owner[t] == s, "one task is named by two slots in the same call");
+    owner[t] = s;
+    any = true;
+  }
+  AdapterBank* b = m->bank;
+  HIP_CHECK(hipSetDevice(m->device));
+  HIP_CHECK(hipMemcpyAsync(b->d_rows, row_slot, (size_t)m->cur_rows * 4, hipMemcpyHostToDevice, m->stream));
+  HIP_CHECK(hipMemcpyAsync(b->d_task, row_task, (size_t)m->cur_rows * 4, hipMemcpyHostToDevice, m->stream));
+  const bool det = m->deterministic;
+  m->deterministic = true;
+  m->bank_rows = any ? b->d_rows : nullptr;
+  m->bank_train = true;
+  b->drop_now = !evaluate && b->dropout > 0.f;
+  int rc;
+  {
+    DetScope scope(m);
+    rc = model_forward_backward_rows(m, evaluate, b->d_task, grad_scale, seed, step);
+  }
+  m->bank_train = false;
+  m->bank_rows = nullptr;
+  m->deterministic = det;
+  return rc;
+}
+
+template <typename T>
+int adapter_bank_backward(Model* m, int l, const T* xn, const T* dqkv, T* dxn) {
+  if (!m->bank_rows) return RSYS_OK;   // every row runs the base model: nothing to differentiate
+  AdapterBank* b = m->bank;
+  const int rows = m->cur_rows, Nq = m->H * m->hd, Nk = m->KV * m->hd, Nv = Nk, Ttok = m->T, D = m->D;
+  const float p = b->drop_now ? b->dropout : 0.f;
+  const unsigned int stream = (unsigned int)(m->drop_step * 64 + l);
+  hipStream_t s = m->stream;
+  T* dLa = (T*)b->dLa;
+  const T* La = bank_la<T>(m, l);
+  tic(m, "adapter_bank_bwd");
+  hipLaunchKernelGGL((adapter_bank_dla_kernel<T>), dim3((Ttok + BANK_A_TOK - 1) / BANK_A_TOK, rows), dim3(256), 0, s, dqkv, (const T*)b->B, m->bank_rows, l,
+                     m->L, Nq, Nk, Nv, Ttok, dLa);
+  hipLaunchKernelGGL((adapter_bank_db_kernel<T>), dim3((Nq + Nv + 63) / 64, rows), dim3(256), 0, s, dqkv, La, m->bank_rows, Nq, Nk, Nv, Ttok, b->partB);
+  hipLaunchKernelGGL((adapter_bank_da_kernel<T>), dim3((D + 63) / 64, rows), dim3(256), 0, s, (const T*)dLa, xn, m->bank_rows, D, Ttok, b->partA, p,
+                     m->drop_seed, stream);
+  hipLaunchKernelGGL((adapter_bank_dx_kernel<T>), dim3((Ttok + BANK_B_TOK - 1) / BANK_B_TOK, rows), dim3(256), 0, s, (const T*)dLa, (const T*)b->A, m->bank_rows,
+                     l, m->L, D, Ttok, dxn, p, m->drop_seed, stream);
+  const long long na = bank_a_floats(m), nb = bank_b_floats(m);
+  hipLaunchKernelGGL(adapter_bank_rows_reduce_kernel, dim3((unsigned)((na + 255) / 256)), dim3(256), 0, s, b->partA, m->bank_rows, rows, na, 1.f,
+                     b->gA + (long long)l * na, (long long)m->L * na);
+  hipLaunchKernelGGL(adapter_bank_rows_reduce_kernel, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, s, b->partB, m->bank_rows, rows, nb, 2.f,
+                     b->gB + (long long)l * nb, (long long)m->L * nb);
+  HIP_CHECK(hipGetLastError());
+  toc(m);
+  return RSYS_OK;
+}
+template int adapter_bank_backward<float>(Model*, int, const float*, const float*, float*);
+template int adapter_bank_backward<bf16>(Model*, int, const bf16*, const bf16*, bf16*);
+
+// a slot's tensor in one of the training buffers (which: 0 gradient, 1 exp_avg, 2 exp_avg_sq)
+static int bank_train_locate(Model* m, int slot, const char* name, int64_t n, float** g, float** mo, float** va) {
+  RC(bank_train_check_model(m));
+  ARG_CHECK(m->bank != nullptr && m->bank->train, "adapter bank training is not enabled (rsys_adapter_train_enable)");
+  ARG_CHECK(slot >= 0 && slot < RSYS_ADAPTER_SLOTS, "adapter slot must be in [0, RSYS_ADAPTER_SLOTS)");
+  int layer, which;
+  if (!bank_parse_name(m, name, &layer, &which)) { set_error(std::string("unknown adapter tensor: ") + name); return RSYS_ERR_ARG; }
+  bool in_b; int64_t off, cnt;
+  bank_locate(m, slot, layer, which, &in_b, &off, &cnt);
+  ARG_CHECK(n == cnt, "element count does not match the adapter tensor's shape");
+  AdapterBank* b = m->bank;
+  *g = (in_b ? b->gB : b->gA) + off; *mo = (in_b ? b->mB : b->mA) + off; *va = (in_b ? b->vB : b->vA) + off;
+  return RSYS_OK;
+}
+
+int adapter_grad_get(Model* m, int slot, const char* name, float* out, int64_t n) {
+  ARG_CHECK(name != nullptr && out != nullptr, "null");
+  float *g, *mo, *va;
+  RC(bank_train_locate(m, slot, name, n, &g, &mo, &va));
+  HIP_CHECK(hipSetDevice(m->device));
+  HIP_CHECK(hipStreamSynchronize(m->stream));
+  HIP_CHECK(hipMemcpy(out, g, (size_t)n * 4, hipMemcpyDeviceToHost));
+  return RSYS_OK;
+}
+
+int adapter_zero_grad(Model* m) {
+  RC(bank_train_check_model(m));
+  ARG_CHECK(m->bank != nullptr && m->bank->train, "adapter bank training is not enabled (rsys_adapter_train_enable)");
+  AdapterBank* b = m->bank;
+  HIP_CHECK(hipSetDevice(m->device));
+  HIP_CHECK(hipMemsetAsync(b->gA, 0, (size_t)RSYS_ADAPTER_SLOTS * m->L * bank_a_floats(m) * 4, m->stream));
+  HIP_CHECK(hipMemsetAsync(b->gB, 0, (size_t)RSYS_ADAPTER_SLOTS * m->L * bank_b_floats(m) * 4, m->stream));
+  return RSYS_OK;
+}
+
+int adapter_adamw_step(Model* m, float lr0, float b1, float b2, float eps, float wd, const float* per_slot, int n_slots, float* norms_out) {
+  RC(bank_train_check_model(m));
+  ARG_CHECK(m->bank != nullptr && m->bank->train, "adapter bank training is not enabled (rsys_adapter_train_enable)");
+  ARG_CHECK(per_slot != nullptr && norms_out != nullptr, "per_slot / norms_out is null");
+  ARG_CHECK(n_slots >= 1 && n_slots <= RSYS_ADAPTER_SLOTS, "n_slots must be in [1, RSYS_ADAPTER_SLOTS]");
+  for (int s = 0; s < n_slots; ++s)
+    if (per_slot[3 * s] != 0.f) ARG_CHECK(bank_complete(m, s), "an active slot is not complete (4 tensors per layer since its last clear)");
+  AdapterBank* b = m->bank;
+  BankStepArgs a{};
+  for (int s = 0; s < n_slots; ++s) {
+    BankStepRec& r = a.rec[s];
+    r.active = per_slot[3 * s] != 0.f ? 1 : 0;
+    if (!r.active) continue;
+    const float t = (float)(b->step[s] + 1);   // (the count itself moves once the kernel is enqueued)
+    r.lr = lr0 * per_slot[3 * s + 1]; r.max_norm = per_slot[3 * s + 2];
+    r.bc1 = 1.f - powf(b1, t); r.bc2_sqrt = sqrtf(1.f - powf(b2, t));
+  }
+  HIP_CHECK(hipSetDevice(m->device));
+  const long long na = (long long)m->L * bank_a_floats(m), nb = (long long)m->L * bank_b_floats(m);
+  if (m->bf16_mode)
+    hipLaunchKernelGGL((adapter_bank_adamw_kernel<bf16>), dim3(n_slots), dim3(1024), 0, m->stream, b->A32, b->B32, b->gA, b->gB, b->mA, b->vA, b->mB, b->vB,
+                       (bf16*)b->A, (bf16*)b->B, na, nb, a, b1, b2, eps, wd, b->d_norms);
+  else
+    hipLaunchKernelGGL((adapter_bank_adamw_kernel<float>), dim3(n_slots), dim3(1024), 0, m->stream, b->A32, b->B32, b->gA, b->gB, b->mA, b->vA, b->mB, b->vB,
+                       (float*)nullptr, (float*)nullptr, na, nb, a, b1, b2, eps, wd, b->d_norms);
+  HIP_CHECK(hipGetLastError());
+  for (int s = 0; s < n_slots; ++s) b->step[s] += a.rec[s].active;
+  HIP_CHECK(hipMemcpyAsync(norms_out, b->d_norms, (size_t)n_slots * 4, hipMemcpyDeviceToHost, m->stream));
+  HIP_CHECK(hipStreamSynchronize(m->stream));
+  return RSYS_OK;   // (no parameter of the trunk changed: table_dirty / wt_dirty stay as they are)
+}
+
+int adapter_adamw_state_io(Model* m, int slot, const char* name, float* m_out, float* v_out, const float* m_in, const float* v_in, int64_t n,
+                           int32_t* step_out, int32_t step_in) {
+  RC(bank_train_check_model(m));
+  ARG_CHECK(m->bank != nullptr && m->bank->train, "adapter bank training is not enabled (rsys_adapter_train_enable)");
+  ARG_CHECK(slot >= 0 && slot < RSYS_ADAPTER_SLOTS, "adapter slot must be in [0, RSYS_ADAPTER_SLOTS)");
+  AdapterBank* b = m->bank;
+  if (name != nullptr) {
+    const bool get = m_out != nullptr || v_out != nullptr;
+    ARG_CHECK(get ? (m_out && v_out) : (m_in && v_in), "exp_avg and exp_avg_sq are both given");
+    float *g, *mo, *va;
+    RC(bank_train_locate(m, slot, name, n, &g, &mo, &va));
+    HIP_CHECK(hipSetDevice(m->device));
+    HIP_CHECK(hipStreamSynchronize(m->stream));
+    if (get) {
+      HIP_CHECK(hipMemcpy(m_out, mo, (size_t)n * 4, hipMemcpyDeviceToHost)); HIP_CHECK(hipMemcpy(v_out, va, (size_t)n * 4, hipMemcpyDeviceToHost));
+    } else {
+      HIP_CHECK(hipMemcpy(mo, m_in, (size_t)n * 4, hipMemcpyHostToDevice)); HIP_CHECK(hipMemcpy(va, v_in, (size_t)n * 4, hipMemcpyHostToDevice));
+    }
+  }
+  if (step_out) *step_out = b->step[slot];
+  if (step_in >= 0) b->step[slot] = step_in;
+  return RSYS_OK;
+}
 
 }  // namespace rsys

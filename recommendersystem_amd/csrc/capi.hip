@@ -80,6 +80,7 @@ int32_t rsys_zero_grad(rsys_model* h) {
 }
 
 int32_t rsys_batch_upload(rsys_model* h, const rsys_batch* b) { CHECK_HANDLE(h); return model_batch_upload(h->m, b); }
+int32_t rsys_batch_rows(rsys_model* h, int32_t* rows_out) { CHECK_HANDLE(h); ARG_CHECK(rows_out, "null"); *rows_out = h->m->cur_rows; return RSYS_OK; }
 int32_t rsys_batch_prefetch(rsys_model* h, const rsys_batch* b) { CHECK_HANDLE(h); return model_batch_prefetch(h->m, b); }
 int32_t rsys_batch_swap(rsys_model* h) { CHECK_HANDLE(h); return model_batch_swap(h->m); }
 
@@ -284,6 +285,31 @@ int32_t rsys_adapter_get(rsys_model* h, int32_t slot, const char* name, float* o
 }
 int32_t rsys_adapter_clear(rsys_model* h, int32_t slot) { CHECK_HANDLE(h); return adapter_clear(h->m, slot); }
 int32_t rsys_adapter_slots(rsys_model* h, int32_t* mask_out) { CHECK_HANDLE(h); return adapter_slots(h->m, mask_out); }
+// training through the bank: the reference's four sequential finetune jobs (Finetune/run.jl:9-13; transformer.py:591-597,
+// 259-276) as one pass over a batch whose rows name their slot and task
+int32_t rsys_adapter_train_enable(rsys_model* h, float dropout) { CHECK_HANDLE(h); return adapter_train_enable(h->m, dropout); }   // model.py:238
+int32_t rsys_adapter_forward_backward(rsys_model* h, int32_t evaluate, const int32_t* row_slot, const int32_t* row_task, float grad_scale, uint64_t seed,
+                                      uint64_t step) {   // model.py:417-435, 493-529; train.py:259-272
+  CHECK_HANDLE(h);
+  return adapter_forward_backward(h->m, evaluate, row_slot, row_task, grad_scale, seed, step);
+}
+int32_t rsys_adapter_grad_get(rsys_model* h, int32_t slot, const char* name, float* out, int64_t n) { CHECK_HANDLE(h); return adapter_grad_get(h->m, slot, name, out, n); }
+int32_t rsys_adapter_zero_grad(rsys_model* h) { CHECK_HANDLE(h); return adapter_zero_grad(h->m); }   // train.py:275
+int32_t rsys_adapter_adamw_step(rsys_model* h, float lr0, float beta1, float beta2, float eps, float wd, const float* per_slot, int32_t n_slots,
+                                float* norms_out) {   // train.py:273-275, transformer.py:285-298
+  CHECK_HANDLE(h);
+  return adapter_adamw_step(h->m, lr0, beta1, beta2, eps, wd, per_slot, n_slots, norms_out);
+}
+int32_t rsys_adapter_adamw_state_get(rsys_model* h, int32_t slot, const char* name, float* exp_avg, float* exp_avg_sq, int64_t n, int32_t* step_out) {
+  CHECK_HANDLE(h);
+  ARG_CHECK(name == nullptr || (exp_avg && exp_avg_sq), "null");
+  return adapter_adamw_state_io(h->m, slot, name, exp_avg, exp_avg_sq, nullptr, nullptr, n, step_out, -1);
+}
+int32_t rsys_adapter_adamw_state_set(rsys_model* h, int32_t slot, const char* name, const float* exp_avg, const float* exp_avg_sq, int64_t n, int32_t step) {
+  CHECK_HANDLE(h);
+  ARG_CHECK(name == nullptr || (exp_avg && exp_avg_sq), "null");
+  return adapter_adamw_state_io(h->m, slot, name, nullptr, nullptr, exp_avg, exp_avg_sq, n, nullptr, step);
+}
 int32_t rsys_infer_select_adapters(rsys_model* h, int32_t task, const int32_t* row_adapter, const int32_t* token_index, int64_t n_tokens, float* out,
                                    int64_t n) {
   CHECK_HANDLE(h); ARG_CHECK(out && token_index && n_tokens >= 1, "null or empty selection");

@@ -96,6 +96,44 @@ int launch_mask_tokens(BatchDev b, int finetune, int finetune_metric, float mask
   return RSYS_OK;
 }
 
+// transformer.model.py:417-435 with the metric of the ROW's task (training through the adapter bank): the finetune branch of
+// the kernel above per row, then the masked weights of every task but the row's own are zero, so a task's loss and weight sum come
+// from the rows of its slot alone.  row_task[r] = -1: the row runs the base model as given and carries no weight.
+__global__ void mask_tokens_rows_kernel(BatchDev b, const int* __restrict__ row_task) {
+  int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= b.N) return;
+  const int task = row_task[i / b.S];
+  const int x = task & 1;
+  bool wm = false, rm = false;
+  if (task >= 0) {
+    const bool w = b.weight[0 * 3 + x][i] > 0.f || b.weight[1 * 3 + x][i] > 0.f;
+    wm = (x == 0) && w;
+    rm = (x == 1) && w;
+  }
+  const bool any = wm || rm;
+  b.m_tmid[i] = rm ? b.tmid[i] : 0;
+  b.m_matchedid[i] = wm ? -1 : b.matchedid[i];
+  b.m_status[i] = any ? -1 : b.status[i];
+  b.m_rating[i] = any ? 0.f : b.rating[i];
+  b.m_progress[i] = any ? 0.f : b.progress[i];
+#pragma unroll
+  for (int m = 0; m < 2; ++m) {
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      const bool on = (k == 0 ? wm : rm) && task == m * 2 + k;
+      b.m_label[m * 2 + k][i] = (k == 0 ? wm : rm) ? b.label[m * 3 + k][i] : 0.f;
+      b.m_weight[m * 2 + k][i] = on ? b.weight[m * 3 + k][i] : 0.f;
+      b.m_position[m * 2 + k][i] = (k == 0 ? wm : rm) ? b.position[m * 3 + k][i] : 0;
+    }
+  }
+}
+
+int launch_mask_tokens_rows(BatchDev b, const int* row_task, hipStream_t s) {
+  hipLaunchKernelGGL(mask_tokens_rows_kernel, dim3(div_up(b.N, 256)), dim3(256), 0, s, b, row_task);
+  HIP_CHECK(hipGetLastError());
+  return RSYS_OK;
+}
+
 // --------------------------------------------------------------------- action features
 // transformer.model.py:51-93.  The periodic argument is formed in fp64, cast to
 // fp32, and the learned phase is added IN fp32 (|arg| ~ 1e5): that rounding is

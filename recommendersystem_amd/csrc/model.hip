@@ -842,26 +842,34 @@ int model_batch_swap(Model* m) {
   return RSYS_OK;
 }
 
-int model_set_deterministic(Model* m, int on) {
+// the partial-sum scratch of the fixed-order reductions (DetScope hands it to the kernels' launchers), allocated once
+int model_ensure_det_scratch(Model* m) {
   HIP_CHECK(hipSetDevice(m->device));
-  if (on && m->det_part == nullptr) {
+  if (m->det_part == nullptr) {
     const long long KB = (long long)m->K * m->rows_max;
     m->det_part_floats = std::max<long long>(std::max<long long>(2048LL * m->D, 512LL * (2 * m->D + 4)), std::max<long long>(KB * m->sh_world, 4096)) + 1024;   // (sharded: one loss term per gathered row)
     HIP_CHECK(hipMalloc((void**)&m->det_part, (size_t)m->det_part_floats * 4));
     m->det_tmp_floats = m->det_part_floats / 32 + 4096;
     HIP_CHECK(hipMalloc((void**)&m->det_tmp, (size_t)m->det_tmp_floats * 4));
   }
+  return RSYS_OK;
+}
+
+int model_set_deterministic(Model* m, int on) {
+  if (on) RC(model_ensure_det_scratch(m));
   m->deterministic = on != 0;
   return RSYS_OK;
 }
 
 template <typename T>
-static int forward_backward_t(Model* m, int evaluate, const float task_w[4], float grad_scale, uint64_t seed, uint64_t step) {
+static int forward_backward_t(Model* m, int evaluate, const float task_w[4], float grad_scale, uint64_t seed, uint64_t step,
+                              const int* d_row_task = nullptr /* rsys_adapter_forward_backward: one task per batch row */) {
   const int rows = m->cur_rows, N = rows * m->S;
   BatchDev b = m->bd; b.N = N; b.rows = rows; b.S = m->S;
   if (m->has_masks) { b.watch_mask = m->d_wm; b.rating_mask = m->d_rm; }
   m->cur_seed = seed; m->cur_step = step;
-  RC(launch_mask_tokens(b, m->cfg.finetune, m->cfg.finetune_metric, m->cfg.mask_rate, seed, step, m->stream));
+  if (d_row_task) RC(launch_mask_tokens_rows(b, d_row_task, m->stream));
+  else RC(launch_mask_tokens(b, m->cfg.finetune, m->cfg.finetune_metric, m->cfg.mask_rate, seed, step, m->stream));
   m->drop_active = m->cfg.finetune && !evaluate && m->cfg.lora_dropout > 0.f;   // nn.Dropout is active in train() mode only
   m->drop_seed = seed ^ 0xD409ull; m->drop_step = step;
   m->top_is_sparse = m->sparse_top && !evaluate;
@@ -890,6 +898,15 @@ int model_forward_backward(Model* m, int evaluate, const float task_w[4], float 
   m->last_evaluate = evaluate != 0;
   return m->bf16_mode ? forward_backward_t<bf16>(m, evaluate, task_w, grad_scale, seed, step)
                       : forward_backward_t<float>(m, evaluate, task_w, grad_scale, seed, step);
+}
+
+// The joint pass of the adapter bank (adapter_bank.hip sets bank_rows / bank_train around it): every task at weight 1, the rows' own
+// masks; the frozen-trunk branches of the forward, the heads and the backward are chosen by trunk_frozen(m).
+int model_forward_backward_rows(Model* m, int evaluate, const int* d_row_task, float grad_scale, uint64_t seed, uint64_t step) {
+  const float tw[4] = {1.f, 1.f, 1.f, 1.f};
+  m->last_evaluate = evaluate != 0;
+  return m->bf16_mode ? forward_backward_t<bf16>(m, evaluate, tw, grad_scale, seed, step, d_row_task)
+                      : forward_backward_t<float>(m, evaluate, tw, grad_scale, seed, step, d_row_task);
 }
 
 // inference forward (model.py:531-538): the batch is used as given (no masking), rope positions optional.  `sel` (n_sel flat

@@ -276,6 +276,11 @@ struct Model {
   // every row's own update to q and v; every other pass leaves it null and launches what it always has
   AdapterBank* bank = nullptr;
   const int* bank_rows = nullptr;
+  // training through the bank: true only inside rsys_adapter_forward_backward.  The pass then treats the trunk as frozen
+  // (the `ft` paths of the forward, heads and backward: dx chain only), keeps La per layer, draws the LoRA dropout inside the bank's
+  // kernels and sends the few small gradients those paths still write (norm gains, rating-head biases) to bank_sink, never to G
+  bool bank_train = false;
+  float* bank_sink = nullptr;   // [max(D, 64)] floats nobody reads
   RenderState* render = nullptr;        // rsys_render_request's workspace, forward counters and kept intermediates (allocated on first use)
   // ranking cache (rank_cache.hip, rsys_rank_cache_*): the post-RoPE K | V of users' history tokens per layer, [L][rc_slots][T][2 KV hd] in
   // the compute dtype, and the events held per slot (-1: never stored).  rc_mode is non-zero only inside the two cache calls: 1 = store
@@ -323,6 +328,19 @@ void adapter_unbind_rows(Model* m);
 void adapter_bank_free(Model* m);
 template <typename T> int adapter_bank_stage_a(Model* m, int l, const T* xn);                      // La = xn . [A_q; A_v][slot]^T
 template <typename T> int adapter_bank_stage_b(Model* m, int l, T* qkv, const int* rope_pos);      // q, v += 2 La . B[slot]^T (q rotated)
+// training through the bank (adapter_bank.hip)
+inline bool trunk_frozen(const Model* m) { return m->cfg.finetune != 0 || m->bank_train; }
+inline float* small_grad(Model* m, int64_t off) { return m->bank_train ? m->bank_sink : m->G + off; }   // where a frozen-trunk pass may drop a <= D-float gradient
+int adapter_train_enable(Model* m, float dropout);
+int adapter_forward_backward(Model* m, int evaluate, const int32_t* row_slot, const int32_t* row_task, float grad_scale, uint64_t seed, uint64_t step);
+int adapter_grad_get(Model* m, int slot, const char* name, float* out, int64_t n);
+int adapter_zero_grad(Model* m);
+int adapter_adamw_step(Model* m, float lr0, float b1, float b2, float eps, float wd, const float* per_slot, int n_slots, float* norms_out);
+int adapter_adamw_state_io(Model* m, int slot, const char* name, float* m_out, float* v_out, const float* m_in, const float* v_in, int64_t n, int32_t* step_out, int32_t step_in);
+// per layer of the backward, after the attention backward: dxn (dhn, this layer's token order) += drop'(dLa . [A_q; A_v][slot]) and the slots' dA / dB
+template <typename T> int adapter_bank_backward(Model* m, int l, const T* xn, const T* dqkv, T* dxn);
+// the joint pass's body (model.hip): masks per row task (d_row_task: device, [rows]), forward, heads with every task at grad_scale, backward
+int model_forward_backward_rows(Model* m, int evaluate, const int* d_row_task, float grad_scale, uint64_t seed, uint64_t step);
 int model_infer_adapters(Model* m, int task, const int32_t* row_adapter, const int32_t* token_index, int64_t n_tokens, float* out, int64_t n);
 // A batch whose arrays a kernel fills on the device (render_request.hip): makes `rows` rows the resident batch without a host copy and
 // returns where its arrays live in the current slot's blob (target arrays stay as they are: an inference forward never reads them).
@@ -364,6 +382,7 @@ int model_split_table_tail(Model* m, struct rsys_comm* c, hipStream_t cs, int64_
 int model_finalize_stage(Model* m, int stage /*1: prepare, 2: dWp GEMM*/, int64_t* wp_off, int64_t* wp_n);
 int model_clip(Model* m, float max_norm, float* norm_out);
 int model_set_deterministic(Model* m, int on);
+int model_ensure_det_scratch(Model* m);   // the mode's scratch without switching the mode on (adapter_bank.hip: its passes use it whatever the mode)
 // retrieve.hip: retrieval top-k over the fused item table of a medium (rsys_retrieve_topk) and the selection alone (rsys_op_topk)
 int model_retrieve_topk(Model* m, int medium, const float* queries, int64_t nq, const int32_t* group, int32_t ng, const float* prior,
                         const int64_t* excl_off, const int32_t* excl_ids, int32_t k, int32_t* ids_out, float* scores_out, int32_t* counts_out);

@@ -35,7 +35,7 @@ static int top_tail_compact_bwd(Model* m, bool wt) {
   hipStream_t s = m->stream;
   const int* n = m->c_n;
   const bool cp = m->bf16_mode;
-  const bool ft = m->cfg.finetune != 0;   // finetune: the base weights are frozen, only the dx chain runs here (the LoRA tensors sit before the attention)
+  const bool ft = trunk_frozen(m);   // finetune / adapter bank: the base weights are frozen, only the dx chain runs here (the LoRA tensors sit before the attention)
   tic(m, "phase_top_compact_bwd");
   if (!ft) {
     GemmParams p{};  // dW2 += gx^T . g
@@ -66,7 +66,7 @@ static int top_tail_compact_bwd(Model* m, bool wt) {
     RC(gemm<T>(m, "gemm_top_w13_dx", p, false, false, !wt));
   }
   RC(launch_rmsnorm_bwd<T>(AT<T>(m->c_dhn), m->c_h, m->P + m->lo[l].mlp, m->c_rstd2, m->c_gx, m->c_dh, cp ? AT<T>(m->c_dh_t) : nullptr,
-                           m->G + m->lo[l].mlp, cap, D, s, n));
+                           small_grad(m, m->lo[l].mlp), cap, D, s, n));
   if (!ft) {
     GemmParams p{};  // dWo += dh^T . O
     p.A = m->c_dh_t; p.lda = D; p.B = m->c_O; p.ldb = D; p.C = m->G + m->lo[l].wo; p.ldc = D; p.c_f32 = 1;
@@ -147,7 +147,7 @@ int backward_trunk(Model* m) {
   // deferred weight gradients: the dY operands of layer l live in m->dwb[l] until the grouped launch that consumes them
   // (deterministic mode: the grouped launch in its ordered form -- bf16 products only, and the fp8 weight gradients are off in that mode)
   const bool det_group = sw().det_dw_group != 0;   // A/B: 0 = the per-layer slab path
-  const bool defer = m->defer_dw && (!m->deterministic || (det_group && m->bf16_mode)) && side_mode() == 0;
+  const bool defer = m->defer_dw && (!m->deterministic || (det_group && m->bf16_mode)) && side_mode() == 0 && !m->bank_train;   // (bank pass: no weight gradients at all)
   const bool ctop = m->top_is_sparse;
   if (defer && !ctop) gxt = AT<T>(m->dwb[m->L - 1].gxt);
   RC(ensure_transposes(m));
@@ -156,10 +156,10 @@ int backward_trunk(Model* m) {
   const double nb_bytes = (sizeof(T) + 4.0 + 4.0 + 4.0 + (cp ? 2.0 : 0.0)) * D * NT;   // g, x, residual gradient in; dx (+ its bf16 operand copy) out
   if (ctop) {   // final norm on the compact rows: c_gx = d(last layer's output) at the selected tokens, zero everywhere else
     RC(launch_rmsnorm_bwd_f32<T>(m->c_gy, m->c_xL, m->P + m->o_norm, m->c_rstdf, nullptr, m->c_gx, cp ? AT<T>(m->c_gx_t) : nullptr,
-                                 m->G + m->o_norm, m->ctop_cap, D, s, m->c_n));
+                                 small_grad(m, m->o_norm), m->ctop_cap, D, s, m->c_n));
   } else {
     tic(m, "hbm_rmsnorm_bwd", (4.0 + 4.0 + 4.0 + (cp ? 2.0 : 0.0)) * D * NT);
-    RC(launch_rmsnorm_bwd_f32<T>(m->gy, m->xL, m->P + m->o_norm, m->rstdf, nullptr, gx, cp ? gxt : nullptr, m->G + m->o_norm, NT, D, s, nullptr,
+    RC(launch_rmsnorm_bwd_f32<T>(m->gy, m->xL, m->P + m->o_norm, m->rstdf, nullptr, gx, cp ? gxt : nullptr, small_grad(m, m->o_norm), NT, D, s, nullptr,
                                  m->fp8 ? f8_slot(m, m->L - 1, F8S_DY2) : nullptr));   // (fp8: the top layer's W2 takes this gradient as its dy)
     toc(m);
   }
@@ -171,7 +171,8 @@ int backward_trunk(Model* m) {
   int bucket_top = m->L - 1;
   for (int l = m->L - 1; l >= 0; --l) {
     Model::LayerAct& a = m->la[l];
-    const bool ft = m->cfg.finetune != 0;   // finetune: base weights are frozen, only the dx chain and the LoRA grads run
+    const bool ft = trunk_frozen(m);        // finetune / adapter bank: base weights are frozen, only the dx chain and the LoRA grads run
+    const bool own_lora = m->cfg.finetune != 0;   // the model's own adapter (the bank's gradients: adapter_bank_backward)
     const bool f8dw = use_f8_dw(m);         // fp8 weight gradients: launched behind the cast of their gradient operand (inside the dx product)
     const bool top = ctop && l == m->L - 1;   // this layer's token-local part runs on the compact rows
     void* const dab = (defer && !top) ? m->dwb[l].dab : m->dab;
@@ -215,7 +216,7 @@ int backward_trunk(Model* m) {
     }
     RC(join_dw(m, DW_O));       // the layer above's dWo reads dht
     tic(m, "hbm_rmsnorm_bwd", nb_bytes);
-    RC(launch_rmsnorm_bwd<T>(AT<T>(m->dhn), a.h, m->P + m->lo[l].mlp, a.rstd2, gx, m->dh, cp ? dht : nullptr, m->G + m->lo[l].mlp, NT, D, s, nullptr, nullptr, nullptr,
+    RC(launch_rmsnorm_bwd<T>(AT<T>(m->dhn), a.h, m->P + m->lo[l].mlp, a.rstd2, gx, m->dh, cp ? dht : nullptr, small_grad(m, m->lo[l].mlp), NT, D, s, nullptr, nullptr, nullptr,
                              m->fp8 ? f8_slot(m, l, F8S_DH) : nullptr));
     toc(m);
     if (!ft && !defer && !f8dw) {
@@ -270,7 +271,8 @@ int backward_trunk(Model* m) {
       if (!m->f8_keep.empty()) HIP_CHECK(hipMemcpyAsync(m->f8_keep[l * 3 + 2], m->dhn, (size_t)NT * D * 2, hipMemcpyDeviceToDevice, s));
       RC(join_side(m));
     }
-    if (ft) {
+    if (m->bank_train) RC(adapter_bank_backward<T>(m, l, AT<T>(a.xn), AT<T>(dqkv), AT<T>(m->dhn)));
+    if (own_lora) {
       T* xnd = m->drop_active ? AT<T>(a.xnd) : AT<T>(a.xn);
       const int nq = m->H * hd, nv0 = (m->H + m->KV) * hd, nkv = m->KV * hd;
       {
@@ -316,10 +318,10 @@ int backward_trunk(Model* m) {
     tic(m, "hbm_rmsnorm_bwd", nb_bytes);
     if (top)   // the residual gradient dh exists at the selected tokens only (compact rows, through the token -> row map)
       // ... and this layer's rows are in selected-first order: x is read at, and dx written to, the original token of each place
-      RC(launch_rmsnorm_bwd<T>(AT<T>(m->dhn), a.x, m->P + m->lo[l].sa, a.rstd1, m->c_dh, gx_other, cp ? gxt_other : nullptr, m->G + m->lo[l].sa, NT, D, s,
+      RC(launch_rmsnorm_bwd<T>(AT<T>(m->dhn), a.x, m->P + m->lo[l].sa, a.rstd1, m->c_dh, gx_other, cp ? gxt_other : nullptr, small_grad(m, m->lo[l].sa), NT, D, s,
                                nullptr, m->c_slot_p, m->c_perm));
     else {
-      RC(launch_rmsnorm_bwd<T>(AT<T>(m->dhn), a.x, m->P + m->lo[l].sa, a.rstd1, m->dh, gx_other, cp ? gxt_other : nullptr, m->G + m->lo[l].sa, NT, D, s, nullptr, nullptr, nullptr,
+      RC(launch_rmsnorm_bwd<T>(AT<T>(m->dhn), a.x, m->P + m->lo[l].sa, a.rstd1, m->dh, gx_other, cp ? gxt_other : nullptr, small_grad(m, m->lo[l].sa), NT, D, s, nullptr, nullptr, nullptr,
                                (m->fp8 && l > 0) ? f8_slot(m, l - 1, F8S_DY2) : nullptr));   // (fp8: the layer below takes this gradient as its W2's dy)
     }
     toc(m);
@@ -347,7 +349,7 @@ int backward_trunk(Model* m) {
   }
   RC(join_all(m));   // every weight gradient is final (and the saved activations may be overwritten by the next forward)
   toc(m);
-  if (m->cfg.finetune) return RSYS_OK;   // embeddings are frozen (model.py:361-369)
+  if (trunk_frozen(m)) return RSYS_OK;   // embeddings are frozen (model.py:361-369)
   // gx = gradient w.r.t. the interleaved input embeddings (even rows: items, odd rows: actions)
   tic(m, "phase_embed_bwd");
   BatchDev b = m->bd; b.N = N; b.rows = rows; b.S = m->S;

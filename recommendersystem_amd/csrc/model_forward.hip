@@ -509,14 +509,14 @@ int heads(Model* m, int evaluate, const float tw[4]) {
           RC(gemm<T>(m, "gemm_head_dx", p, false, false, true));
         }
         RC(add_rows(m->dE, ti, 0));
-        if (!m->cfg.finetune) {
+        if (!trunk_frozen(m)) {
           GemmParams p{};  // dF[s:e] += dlogits^T . Ew
           p.A = m->logits; p.lda = m->ldl; p.B = m->Ew; p.ldb = D; p.C = m->G + m->o_E + (int64_t)vs * D; p.ldc = D; p.c_f32 = 1;
           p.M = Vm; p.N = D; p.K = KB; p.epi = m->gE_clean[medium] ? EPI_STORE : EPI_ACCUM; p.k_dev = np;
           m->gE_clean[medium] = false;
           RC(gemm<T>(m, "gemm_head_dw", p, false, true, true));
         }
-        if (!m->cfg.finetune) m->table_grads_pending = true;
+        if (!trunk_frozen(m)) m->table_grads_pending = true;
       }
     } else {
       {
@@ -528,9 +528,9 @@ int heads(Model* m, int evaluate, const float tw[4]) {
       }
       RC(launch_rating_tail<T>(AT<T>(m->z), AT<T>(m->hact), KB, D, m->P + m->o_r2w, m->P + m->o_r2b, m->idx[ti],
                                m->bd.m_label[ti], m->bd.m_weight[ti], st, m->cfg.rating_mean, bwd ? tw[ti] : 0.f,
-                               bwd ? 0 : 1, m->loss_acc + 3 * ti, m->G + m->o_r2w, m->G + m->o_r2b, m->G + m->o_r0b, s, np));
+                               bwd ? 0 : 1, m->loss_acc + 3 * ti, small_grad(m, m->o_r2w), small_grad(m, m->o_r2b), small_grad(m, m->o_r0b), s, np));
       if (bwd) {
-        if (!m->cfg.finetune) {
+        if (!trunk_frozen(m)) {
           GemmParams p{};  // dW0 += dz^T . Er
           p.A = m->z; p.lda = D; p.B = m->Ew; p.ldb = D; p.C = m->G + m->o_r0w; p.ldc = D; p.c_f32 = 1;
           p.M = D; p.N = D; p.K = KB; p.epi = EPI_ATOMIC; p.k_dev = np;   // (dz of the padding rows up to the next tile is zero: rating_tail)

@@ -449,6 +449,47 @@ class RecommenderModel:
             sd[n] = out
         return sd
 
+    # ---- training through the bank: the four finetune adapters in one pass on the frozen trunk (Finetune/run.jl:9-13)
+    def enable_adapter_training(self, dropout=0.1):
+        """gradients, AdamW moments and per-layer activations for the bank's slots; `dropout` on the LoRA input of training passes
+        (model.py:238).  May be called again to change the dropout."""
+        check(lib().rsys_adapter_train_enable(self._h, float(dropout)))
+        self._grad_scale_adapters = 1.0
+
+    def forward_backward_adapters(self, d, row_slot, row_task, evaluate=False, grad_scale=1.0, step=None):
+        """One joint pass: batch row r runs with bank slot row_slot[r] on task row_task[r] = medium * 2 + metric (-1 / -1: the base
+        model, no loss).  d None: the batch already resident.  Training passes accumulate each slot's LoRA gradients (`adapter_grad`).
+        Returns the loss list of `__call__`; `last_weight_sums` holds the tasks' weight sums."""
+        if d is not None:
+            self.upload(d)
+        rs = np.ascontiguousarray(np.asarray(row_slot).reshape(-1), np.int32)
+        rt = np.ascontiguousarray(np.asarray(row_task).reshape(-1), np.int32)
+        n = C.c_int32()
+        check(lib().rsys_batch_rows(self._h, C.byref(n)))       # the resident batch's own count, whichever call made it resident
+        rows = n.value
+        if rs.size != rows or rt.size != rows:
+            raise ValueError(f"forward_backward_adapters: {rs.size} slots / {rt.size} tasks for {rows} batch rows")
+        if step is None:
+            step = self._step
+            self._step += 1
+        check(lib().rsys_adapter_forward_backward(self._h, 1 if evaluate else 0, rs.ctypes.data, rt.ctypes.data, float(grad_scale),
+                                                  self.mask_seed, int(step)))
+        return self.losses(bool(evaluate))
+
+    def adapter_grad(self, slot, name=None):
+        """the fp32 gradient of one LoRA tensor of `slot`, or {name: gradient} of all of them"""
+        def one(n, shape):
+            out = np.empty(shape, np.float32)
+            check(lib().rsys_adapter_grad_get(self._h, int(slot), n.encode(), out.ctypes.data, out.size))
+            return out
+        shapes = dict(self.adapter_names())
+        if name is not None:
+            return one(name, shapes[name])
+        return {n: one(n, shape) for n, shape in shapes.items()}
+
+    def zero_adapter_grads(self):
+        check(lib().rsys_adapter_zero_grad(self._h))
+
     def clear_adapter(self, slot):
         check(lib().rsys_adapter_clear(self._h, int(slot)))
 

@@ -89,6 +89,57 @@ class AdamW:
             pass
 
 
+class AdapterAdamW:
+    """AdamW over the slots of a base model's adapter bank: what `AdamW` is to a finetune = 1 model's LoRA tensors, per
+    slot -- its own step count, learning-rate factor and gradient clip -- in one kernel for all slots that step together
+    (transformer.py:285-298; train.py:273-275)."""
+
+    def __init__(self, model, lr, slots, betas=(0.9, 0.95), eps=1e-8, weight_decay=0.1):
+        self.model, self.lr, self.betas, self.eps, self.weight_decay = model, float(lr), betas, eps, weight_decay
+        self.slots = sorted(int(s) for s in slots)
+        self.last_norms = {}
+
+    def step(self, lr_factors, clip_max_norm=0.0):
+        """One optimizer step (clip by the slot's own norm, AdamW, zeroed gradient) for every slot in `lr_factors` ({slot: factor});
+        the other slots are left bit for bit.  Returns {slot: gradient norm before the clip}."""
+        n = max(self.slots) + 1
+        rec = np.zeros((n, 3), np.float32)
+        for s, f in lr_factors.items():
+            if int(s) not in self.slots:
+                raise ValueError(f"AdapterAdamW: slot {s} is not one of {self.slots}")
+            clip = clip_max_norm[s] if isinstance(clip_max_norm, dict) else clip_max_norm      # ({slot: max_norm} or one for all)
+            rec[int(s)] = (1.0, float(f), float(clip))
+        norms = np.zeros(n, np.float32)
+        check(lib().rsys_adapter_adamw_step(self.model._h, self.lr, self.betas[0], self.betas[1], self.eps, self.weight_decay,
+                                            rec.ctypes.data, n, norms.ctypes.data))
+        self.last_norms = {int(s): float(norms[int(s)]) for s in lr_factors}
+        return self.last_norms
+
+    def zero_grad(self, set_to_none=True):
+        self.model.zero_adapter_grads()
+
+    def state_dict(self):
+        """{slot: {"step", "lr", "state": {name: {"exp_avg", "exp_avg_sq"}}}}: per slot the layout of `AdamW.state_dict`"""
+        out = {}
+        for s in self.slots:
+            st = C.c_int32()
+            check(lib().rsys_adapter_adamw_state_get(self.model._h, s, None, None, None, 0, C.byref(st)))
+            state = {}
+            for name, shape in self.model.adapter_names():
+                m = np.empty(shape, np.float32); v = np.empty(shape, np.float32)
+                check(lib().rsys_adapter_adamw_state_get(self.model._h, s, name.encode(), m.ctypes.data, v.ctypes.data, m.size, None))
+                state[name] = {"exp_avg": m, "exp_avg_sq": v}
+            out[s] = {"step": st.value, "lr": self.lr, "state": state}
+        return out
+
+    def load_state_dict(self, sd):
+        for s, one in sd.items():
+            check(lib().rsys_adapter_adamw_state_set(self.model._h, int(s), None, None, None, 0, int(one["step"])))
+            for name, st in one["state"].items():
+                m = np.ascontiguousarray(st["exp_avg"], np.float32); v = np.ascontiguousarray(st["exp_avg_sq"], np.float32)
+                check(lib().rsys_adapter_adamw_state_set(self.model._h, int(s), name.encode(), m.ctypes.data, v.ctypes.data, m.size, -1))
+
+
 def create_optimizer(model, config):
     return AdamW(model, lr=config["learning_rate"], betas=(0.9, 0.95), weight_decay=0.1)
 

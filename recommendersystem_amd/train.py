@@ -388,3 +388,180 @@ def train(model, optimizer, scheduler, dataloaders, config, datadir, task_weight
         if stopper.early_stop:
             break
     return history
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The four finetune adapters in one run through the adapter bank (DESIGN 4y).  The reference runs four sequential jobs on the
+# same frozen trunk (Finetune/run.jl:9-13, transformer.py:591-597); here every slot keeps the bookkeeping its own `train()` run
+# would have -- micro-step counter, gradient accumulation, scheduler, early stopper, metrics CSV -- and one joint pass per
+# micro-step serves every slot that still has a batch.
+ADAPTER_TASKS = [(m, metric) for m in ALL_MEDIUMS for metric in ALL_METRICS]      # task index = medium * 2 + metric, the order of task_w
+
+
+def pack_adapter_batch(sub_batches, S):
+    """[(slot, task, batch or None)] -> (batch, row_slot, row_task): the sub-batches' rows back to back in the order given, every
+    row naming its slot and task.  A slot whose loader is exhausted or which has stopped passes None and contributes no rows;
+    returns (None, None, None) when nobody has rows.  Each sub-batch comes from its slot's own FinetuneDataset (rows filtered by
+    the slot's medium, transformer.py:137-143) and holds at most one local batch of rows."""
+    parts, row_slot, row_task = [], [], []
+    for slot, task, d in sub_batches:
+        if d is None:
+            continue
+        n = int(np.asarray(d["userid"]).size)
+        if n == 0:
+            continue
+        if n % S:
+            raise ValueError(f"pack_adapter_batch: slot {slot} holds {n} interactions, not whole rows of {S}")
+        if parts and set(d) != set(parts[0]):
+            raise ValueError(f"pack_adapter_batch: slot {slot} has other arrays than the first sub-batch")
+        parts.append(d)
+        row_slot += [int(slot)] * (n // S)
+        row_task += [int(task)] * (n // S)
+    if not parts:
+        return None, None, None
+    batch = {k: np.concatenate([np.asarray(p[k]).reshape(-1) for p in parts]) for k in parts[0]}
+    return batch, np.asarray(row_slot, np.int32), np.asarray(row_task, np.int32)
+
+
+@dataclasses.dataclass
+class AdapterRun:
+    """what one slot's own `train()` run keeps (train.py:697-757): its task, the task weight its loss carries, scheduler, stopper"""
+    slot: int
+    task: int                       # medium * 2 + metric
+    task_weight: float              # make_task_weights(medium, metric)[task]
+    scheduler: object
+    stopper: object
+    micro: int = 0                  # micro-steps of the current epoch
+    opt_steps: int = 0
+    epoch: int = 0
+    done: bool = False              # stopped early or out of epochs: contributes no rows any more
+
+
+def train_epoch_adapters(model, loaders, optimizer, runs, grad_accum_steps, S, max_norm=1.0, log=None):
+    """`train_epoch` (train.py:238-283) for every slot of `runs` that is not done, in joint micro-steps: micro-step j packs the j-th
+    batch of every such slot's loader (`loaders[slot]`), runs one joint pass at grad_scale 1 / grad_accum_steps and, for each slot
+    whose own counter reaches a multiple of grad_accum_steps, one optimizer step with that slot's LR factor, then its scheduler step.
+    The pass differentiates sum_i loss_i; a slot's own run differentiates task_weight * loss, so its clip threshold is max_norm /
+    task_weight here (the same clip coefficient; AdamW is invariant to the remaining scale but for its eps).  Returns {slot:
+    (training loss, weight sum)} of the slot's own task."""
+    active = [r for r in runs if not r.done]
+    iters = {r.slot: iter(loaders[r.slot]) for r in active}
+    sums = {r.slot: [0.0, 0.0] for r in active}
+    optimizer.zero_grad(set_to_none=True)
+    for r in active:
+        r.micro = 0
+    while True:
+        subs = [(r.slot, r.task, next(iters[r.slot], None)) for r in active]
+        batch, row_slot, row_task = pack_adapter_batch(subs, S)
+        if batch is None:
+            break
+        losses = model.forward_backward_adapters(batch, row_slot, row_task, evaluate=False, grad_scale=1.0 / grad_accum_steps)
+        stepping = {}
+        for r, (_, _, d) in zip(active, subs):
+            if d is None:
+                continue
+            w = model.last_weight_sums[r.task]
+            sums[r.slot][0] += losses[r.task] * w
+            sums[r.slot][1] += w
+            r.micro += 1
+            if log is not None:
+                log(("micro", r.slot, r.micro))
+            if r.micro % grad_accum_steps == 0:
+                stepping[r.slot] = r
+        if stepping:
+            factors = {s: r.scheduler.factor() for s, r in stepping.items()}
+            optimizer.step(factors, clip_max_norm={s: max_norm / r.task_weight for s, r in stepping.items()})
+            for s, r in stepping.items():
+                r.scheduler.step()
+                r.opt_steps += 1
+                if log is not None:
+                    log(("step", s, factors[s]))
+    return {s: (a / b if b != 0 else 0, b) for s, (a, b) in sums.items()}
+
+
+def evaluate_adapters(model, loaders, runs, S):
+    """`evaluate_metrics` (train.py:207-235) per slot through joint evaluation passes: {slot: test loss of the slot's own task}"""
+    active = [r for r in runs if not r.done]
+    iters = {r.slot: iter(loaders[r.slot]) for r in active}
+    moments = {r.slot: np.zeros(len(_RATING_SCALES)) for r in active}
+    mass = {r.slot: 0.0 for r in active}
+    while True:
+        subs = [(r.slot, r.task, next(iters[r.slot], None)) for r in active]
+        batch, row_slot, row_task = pack_adapter_batch(subs, S)
+        if batch is None:
+            break
+        out = model.forward_backward_adapters(batch, row_slot, row_task, evaluate=True)
+        for r, (_, _, d) in zip(active, subs):
+            if d is None:
+                continue
+            w = model.last_weight_sums[r.task]
+            vals = out[r.task] if isinstance(out[r.task], list) else [out[r.task]]
+            if w != 0:
+                moments[r.slot][: len(vals)] += w * np.asarray(vals, np.float64)
+            mass[r.slot] += w
+    res = {}
+    for r in active:
+        rating = ADAPTER_TASKS[r.task][1] == "rating"
+        tot = minimize_quadratic(_RATING_SCALES, list(moments[r.slot])) if rating else float(moments[r.slot][0])
+        res[r.slot] = tot / mass[r.slot] if mass[r.slot] != 0 else 0
+    return res
+
+
+def make_adapter_runs(slots_tasks, config):
+    """one AdapterRun per (slot, task) with the finetune schedule, stopper and task weight of `train()` for that medium and metric"""
+    runs = []
+    for slot, task in slots_tasks:
+        m, metric = ADAPTER_TASKS[task]
+        runs.append(AdapterRun(slot, task, make_task_weights(m, metric)[task], create_learning_rate_schedule(0, 1, 1, finetune=True),
+                               make_early_stopper(dict(config, finetune=True))))
+    return runs
+
+
+def train_adapters(model, optimizer, runs, dataloaders, config, outdir, num_epochs, grad_accum_steps, log=print, base_blob=None):
+    """The epoch loop of `train()` (train.py:697-757) for every slot at once: initial evaluation, then per epoch one
+    `train_epoch_adapters`, one `evaluate_adapters`, every slot's own early stopper; a slot whose stopper says its model improved
+    writes `{medium}.{metric}.lora.npz` (its LoRA tensors, epoch and losses) and appends to its own metrics CSV; a slot that runs out
+    of patience is done and contributes no rows from then on.  `base.npz` (the frozen trunk) is written once: together these are the
+    files of `python -m recommendersystem_amd.checkpoint dedup`, which `serve.get_models` loads.  dataloaders = {"training": {slot:
+    loader}, "test": {slot: loader}}.  Returns {slot: [(epoch, training loss, test loss)]}."""
+    import os
+    S = config["max_sequence_length"]
+    os.makedirs(outdir, exist_ok=True)
+    if base_blob is None:
+        base_blob = {"model/" + k: v for k, v in model.state_dict(include_frozen=False).items() if not k.startswith("watch_head.")}
+    np.savez(os.path.join(outdir, "base.npz"), **base_blob)
+    name = lambda r: "%d.%s" % ADAPTER_TASKS[r.task]
+
+    def record(r, epoch, training_loss, test_loss, save):
+        if save:
+            blob = {"model/" + k: v for k, v in model.adapter_state_dict(r.slot).items()}
+            blob.update(epoch=np.array([epoch]), training_loss=np.array([training_loss], np.float64), test_loss=np.array([test_loss], np.float64))
+            np.savez(os.path.join(outdir, name(r) + ".lora.npz"), **blob)
+        csv_fn = os.path.join(outdir, name(r) + ".csv")
+        if epoch < 0:
+            with open(csv_fn, "w") as f:
+                f.write("epoch,training_loss,test_loss," + name(r) + "\n")
+        with open(csv_fn, "a") as f:
+            f.write(",".join(str(x) for x in (epoch, training_loss * r.task_weight, test_loss * r.task_weight, test_loss)) + "\n")
+
+    initial = evaluate_adapters(model, dataloaders["test"], runs, S)
+    for r in runs:
+        r.stopper(initial[r.slot] * r.task_weight)
+        record(r, -1, initial[r.slot], initial[r.slot], True)
+    history = {r.slot: [] for r in runs}
+    for epoch in range(num_epochs):
+        if all(r.done for r in runs):
+            break
+        tr = train_epoch_adapters(model, dataloaders["training"], optimizer, runs, grad_accum_steps, S)
+        te = evaluate_adapters(model, dataloaders["test"], runs, S)
+        for r in runs:
+            if r.done:
+                continue
+            r.stopper(te[r.slot] * r.task_weight)
+            log(f"Epoch: {epoch}, {name(r)}: Training Loss: {tr[r.slot][0]}, Test Loss: {te[r.slot]}, LR factor: {r.scheduler.factor()}")
+            record(r, epoch, tr[r.slot][0], te[r.slot], r.stopper.save_model)
+            history[r.slot].append((epoch, tr[r.slot][0], te[r.slot]))
+            r.epoch = epoch + 1
+            if r.stopper.early_stop or r.epoch >= num_epochs:
+                r.done = True
+    return history
