@@ -35,7 +35,7 @@ enum { RSYS_DTYPE_FP32 = 0, RSYS_DTYPE_BF16 = 1, RSYS_DTYPE_FP8 = 2 };
 /* mirrors the config dict of train.py:535-560 (+ finetune keys of :520-524) */
 typedef struct rsys_config {
   int32_t num_layers, num_heads, num_kv_heads, embed_dim, intermediate_dim;
-  int32_t max_sequence_length;          /* S interactions per row -> 2S tokens */
+  int32_t max_sequence_length;          /* S interactions per row -> 2S tokens; a multiple of 4, S <= 2048 (rows of up to 4096 tokens) */
   int32_t vocab_0, vocab_1;             /* vocab_sizes["0_matchedid"], ["1_matchedid"] */
   int32_t vocab_status, vocab_gender, vocab_source;
   int32_t metadata_dim;                 /* metadata_emb_size */

@@ -91,7 +91,8 @@ int32_t rsys_debug_gemm_route(int32_t dtype, int32_t M, int32_t N, int32_t K, in
                               int32_t accum, int32_t set, int32_t m_expect, int32_t cus, char* tag, int32_t tag_bytes, int32_t* splits);
 /* attention fwd+bwd on caller-provided device buffers (T-typed): qkv [B*T][(H+2KV)*hd] post-RoPE, dO [B*T][H*hd],
  * uid/tm [B*T] int32 with 0 <= uid < 2^19 and 0 <= tm < 4096, rope tables [T][hd/2] f32; outputs O [B*T][H*hd], lse [B][H][T] f32,
- * dqkv [B*T][(H+2KV)*hd] (gradients w.r.t. the un-rotated q, k and v) */
+ * dqkv [B*T][(H+2KV)*hd] (gradients w.r.t. the un-rotated q, k and v).  T a multiple of 8, T <= 4096 (64 tiles of 64 tokens: rows of
+ * more than 2048 tokens run the kernels' 64-bit tile-map instantiations), a row of qkv below 2 GiB */
 int32_t rsys_op_attention(int32_t dtype, int32_t B, int32_t T, int32_t H, int32_t KV, int32_t hd, const void* qkv,
                           const int32_t* uid, const int32_t* tm, void* O, float* lse, const void* dO, void* dqkv,
                           const float* rope_cos, const float* rope_sin);
@@ -109,7 +110,7 @@ int32_t rsys_op_attention_ex(int32_t dtype, int32_t B, int32_t T, int32_t H, int
                              const int32_t* q_active, float* amax_fwd, float* amax_bwd);
 /* the candidate attention of rsys_rank_cache_candidates alone, on caller-provided device buffers (T-typed): qkv [rows*T][(H+2KV)*hd] the
  * candidate rows' post-RoPE q | k | v, cache [n_slots][T][2*KV*hd] (K | V per cached token), slot / n_hist / n_cand int32 [rows] (device;
- * 0 <= n_hist[r] <= T/2, 0 <= n_cand[r] <= T/2); O [rows*T][H*hd]: rows of tokens >= 2 n_cand[r] are zeros up to the end of the last
+ * 0 <= n_hist[r] <= T/2, 0 <= n_cand[r] <= T/2; T a multiple of 8, T <= 4096); O [rows*T][H*hd]: rows of tokens >= 2 n_cand[r] are zeros up to the end of the last
  * 64-token tile that holds a candidate and left as they were behind it */
 int32_t rsys_op_attention_cached(int32_t dtype, int32_t rows, int32_t T, int32_t H, int32_t KV, int32_t hd, const void* qkv, const void* cache,
                                  int32_t n_slots, const int32_t* slot, const int32_t* n_hist, const int32_t* n_cand, void* O);

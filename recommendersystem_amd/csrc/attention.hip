@@ -336,6 +336,31 @@ __device__ __forceinline__ int next_bit(unsigned int bits, int from) {  // lowes
   const unsigned int m = from >= 32 ? 0u : (bits >> from) << from;
   return m ? __ffs(m) - 1 : 32;
 }
+__device__ __forceinline__ int next_bit(unsigned long long bits, int from) {  // the same on a wide map word: ... or 64
+  const unsigned long long m = from >= 64 ? 0ull : (bits >> from) << from;
+  return m ? __ffsll(m) - 1 : 64;
+}
+// Map words.  A row of up to 32 tiles keeps ONE 32-bit word per map entry (LG = 5: every kernel below is then instruction for instruction
+// what it was before rows grew past 2048 tokens); a row of 33 .. 64 tiles keeps one 64-bit word per entry (LG = 6) in the same arrays, which
+// are then twice as long (attn_map_words, kernels.hpp).  The launches pick the instantiation from nt alone, so a kernel never meets a map
+// of the other width.  LG is also the shift of the dK/dV kernels' item numbers (head of the group << LG | q tile).
+template <int LG> struct AMap;
+template <> struct AMap<5> { using W = unsigned int; };
+template <> struct AMap<6> { using W = unsigned long long; };
+template <int LG>
+__device__ __forceinline__ typename AMap<LG>::W* map_ptr(unsigned int* m) { return (typename AMap<LG>::W*)m; }
+template <int LG>
+__device__ __forceinline__ typename AMap<LG>::W map_below(int n) {   // bits 0 .. n - 1
+  using W = typename AMap<LG>::W;
+  return n >= (1 << LG) ? ~(W)0 : (((W)1 << n) - (W)1);
+}
+__device__ __forceinline__ unsigned int map_uniform(unsigned int v) { return (unsigned int)__builtin_amdgcn_readfirstlane((int)v); }
+__device__ __forceinline__ unsigned long long map_uniform(unsigned long long v) {
+  const unsigned int lo = (unsigned int)__builtin_amdgcn_readfirstlane((int)(unsigned int)v), hi = (unsigned int)__builtin_amdgcn_readfirstlane((int)(unsigned int)(v >> 32));
+  return ((unsigned long long)hi << 32) | lo;
+}
+__device__ __forceinline__ int map_popc(unsigned int v) { return __popc(v); }
+__device__ __forceinline__ int map_popc(unsigned long long v) { return __popcll(v); }
 
 // ------------------------------------------------------------------------ tile maps
 // qmap / qmap_full [b][q tile]: bit j = kv tile j has some / only allowed pairs; kmap* is the transposed relation; the
@@ -345,11 +370,15 @@ __device__ __forceinline__ int next_bit(unsigned int bits, int from) {  // lowes
 // 64 keys) step is two compares, an OR and a ballot.  Exact: "some" bits may not miss a pair, "only" bits may not claim one.
 __device__ __forceinline__ int token_key(int uid, int tm);
 extern "C" __device__ int rsys_at_writelane(int value, int lane, int old) __asm("llvm.amdgcn.writelane.i32");   // v_writelane_b32
+template <int LG>
 __global__ __launch_bounds__(256) void attn_tilemap_kernel(AttnParams p) {
-  __shared__ unsigned int any_bits, any16[4], kany[32];   // kany[j]: bit kg = keys 16 kg .. +15 of kv tile j meet a query of this tile
-  __shared__ int cnt[32];
-  __shared__ unsigned short kcols[32][64][4];   // [kv tile][key][query group of 16]: the key's bits against this q tile, written out as words
-  __shared__ int keys[2048];                    // the row's token keys (one round of loads instead of a dependent load per kv tile)
+  using W = typename AMap<LG>::W;
+  constexpr int NTM = 1 << LG;   // tiles a map word holds (LG = 6: kcols 32 KB + keys 16 KB of LDS)
+  __shared__ W any_bits, any16[4];
+  __shared__ unsigned int kany[NTM];            // kany[j]: bit kg = keys 16 kg .. +15 of kv tile j meet a query of this tile
+  __shared__ int cnt[NTM];
+  __shared__ unsigned short kcols[NTM][64][4];  // [kv tile][key][query group of 16]: the key's bits against this q tile, written out as words
+  __shared__ int keys[64 * NTM];                // the row's token keys (one round of loads instead of a dependent load per kv tile)
   __shared__ int qkeys[64];                     // the tile's query keys: read back per query as a lane-uniform VECTOR register (as scalars,
                                                 // 16 keys + their tm-less forms + the loop state spilled scalar registers through v_readlane)
   const int qt = blockIdx.x, b = blockIdx.y, t = threadIdx.x, l = t & 63, w = t >> 6;
@@ -357,7 +386,7 @@ __global__ __launch_bounds__(256) void attn_tilemap_kernel(AttnParams p) {
   const long long base = (long long)b * p.T;
   if (t == 0) any_bits = 0u;
   if (t < 4) any16[t] = 0u;
-  if (t < 32) { cnt[t] = 0; kany[t] = 0u; }
+  if (t < NTM) { cnt[t] = 0; kany[t] = 0u; }
   for (int i = t; i < nt * 64; i += 256) keys[i] = i < p.T ? token_key(p.uid[base + i], p.tm[base + i]) : KEY_NO_K;
   // lane i < 16 of wave w holds the key of query qt*64 + w*16 + i
   int myq = KEY_NO_Q;
@@ -367,7 +396,7 @@ __global__ __launch_bounds__(256) void attn_tilemap_kernel(AttnParams p) {
   int aq[16], aq0[16];
 #pragma unroll
   for (int i = 0; i < 16; ++i) { aq[i] = qkeys[w * 16 + i]; aq0[i] = aq[i] & ~4095; }
-  unsigned int wany = 0u;
+  W wany = 0u;
   for (int j = 0; j < nt; ++j) {
     const int ak = keys[j * 64 + l];
     bool mine = false;     // this key meets one of the wave's queries
@@ -396,7 +425,7 @@ __global__ __launch_bounds__(256) void attn_tilemap_kernel(AttnParams p) {
     if (l < 16) p.qbits[(((long long)b * nt + qt) * nt + j) * 64 + w * 16 + l] = qrow;
     kcols[j][l][w] = (unsigned short)kcol;
     if (n) {
-      wany |= 1u << j;
+      wany |= (W)1 << j;
       const unsigned long long km = __ballot(mine);
       unsigned int kg = 0u;
 #pragma unroll
@@ -410,16 +439,16 @@ __global__ __launch_bounds__(256) void attn_tilemap_kernel(AttnParams p) {
     p.kbits[(((long long)b * nt + (c >> 6)) * nt + qt) * 64 + (c & 63)] = *(const unsigned long long*)kcols[c >> 6][c & 63];
   if (t < nt) {
     const bool any = (any_bits >> t) & 1u, full = cnt[t] == 4096;
-    if (any) atomicOr(&p.kmap[b * nt + t], 1u << qt);
-    if (full) atomicOr(&p.kmap_full[b * nt + t], 1u << qt);
-    if (full) atomicOr(&p.qmap_full[b * nt + qt], 1u << t);
+    if (any) atomicOr(&map_ptr<LG>(p.kmap)[b * nt + t], (W)1 << qt);
+    if (full) atomicOr(&map_ptr<LG>(p.kmap_full)[b * nt + t], (W)1 << qt);
+    if (full) atomicOr(&map_ptr<LG>(p.qmap_full)[b * nt + qt], (W)1 << t);
     const unsigned int kg = kany[t];
 #pragma unroll
     for (int g4 = 0; g4 < 4; ++g4)
-      if ((kg >> g4) & 1u) atomicOr(&p.kmap16[(b * nt + t) * 4 + g4], 1u << qt);
+      if ((kg >> g4) & 1u) atomicOr(&map_ptr<LG>(p.kmap16)[(b * nt + t) * 4 + g4], (W)1 << qt);
   }
-  if (t == 0) p.qmap[b * nt + qt] = any_bits;
-  if (t < 4) p.qmap16[(b * nt + qt) * 4 + t] = any16[t];
+  if (t == 0) map_ptr<LG>(p.qmap)[b * nt + qt] = any_bits;
+  if (t < 4) map_ptr<LG>(p.qmap16)[(b * nt + qt) * 4 + t] = any16[t];
 }
 
 // Heaviest-first launch orders (AttnParams::order_q / order_k).  blockIdx.y = 0: the q-side kernels (work of a slot = kv tiles its
@@ -429,8 +458,15 @@ __global__ __launch_bounds__(256) void attn_tilemap_kernel(AttnParams p) {
 static int attn_heads_per_wg(const AttnParams& p);
 static bool attn_kv_pairs(const AttnParams& p);   // the dK/dV launch of this shape is attn_bwd_kv32_kernel (order_k then lists kv tile PAIRS)
 // kv_pairs: the dK/dV side's slots are PAIRS of kv tiles (attn_bwd_kv32_kernel: 128 keys per workgroup), work = q tiles either tile is visited by
+// Work keys are 0 .. 2^LG tiles and the padding key 2^LG + 1: rows of OS = 2^LG + 2 counters (34 as before for rows of up to 32 tiles: the same
+// stable permutation; 66 for the wide maps, whose chunk cap is halved with it -- attn_order_chunk_cap -- so that the table stays below 64 KB).
+static int attn_order_chunk_cap(int lg) { return lg == 5 ? 400 : 200; }
+template <int LG>
 __global__ __launch_bounds__(256) void attn_order_kernel(AttnParams p, int R, int identity, int kv_pairs) {
-  extern __shared__ int ocnt[];   // [chunks of 64 slots + 1][34]: slots per (chunk, key), then their exclusive prefixes; last row: totals / bases
+  using W = typename AMap<LG>::W;
+  constexpr int NTM = 1 << LG, OS = NTM + 2;
+  const W *qmap = map_ptr<LG>(p.qmap), *kmap = map_ptr<LG>(p.kmap);
+  extern __shared__ int ocnt[];   // [chunks of 64 slots + 1][OS]: slots per (chunk, key), then their exclusive prefixes; last row: totals / bases
   const int side = blockIdx.y, nt = (p.T + 63) / 64, n_groups = p.B * p.KV;   // side 2: the forward kernel's (head, q tile PAIR) slots
   const int n_inner = side == 0 ? (p.H / p.KV / R) * nt : side == 2 ? (p.H / p.KV) * ((nt + 1) / 2) : (kv_pairs ? (nt + 1) / 2 : nt);
   int* out = side == 0 ? p.order_q : side == 2 ? p.order_q2 : p.order_k;
@@ -442,58 +478,59 @@ __global__ __launch_bounds__(256) void attn_order_kernel(AttnParams p, int R, in
   if (identity) { for (int sl = threadIdx.x; sl < ns; sl += 256) out[sl] = sl; return; }
   const int nch = (ns + 63) >> 6, l = threadIdx.x & 63, w = threadIdx.x >> 6;
   auto key_of = [&](int sl) -> int {
-    if (sl >= ns) return 33;   // (padding of the last chunk: a key of its own)
+    if (sl >= ns) return NTM + 1;   // (padding of the last chunk: a key of its own)
     const int group = lists ? (sl / n_inner) * 8 + xcd : sl / n_inner, tile = (sl % n_inner) % nt, b = group / p.KV;
-    const int qa = p.q_active != nullptr ? p.q_active[b] : 32;
-    if (side == 0) return tile < qa ? __popc(p.qmap[b * nt + tile]) : 0;
+    const int qa = p.q_active != nullptr ? p.q_active[b] : NTM;
+    if (side == 0) return tile < qa ? map_popc(qmap[b * nt + tile]) : 0;
     if (side == 2) {
       const int t0 = 2 * ((sl % n_inner) % ((nt + 1) / 2)), lim = min(nt, qa);
-      return __popc((t0 < lim ? p.qmap[b * nt + t0] : 0u) | (t0 + 1 < lim ? p.qmap[b * nt + t0 + 1] : 0u));
+      return map_popc((t0 < lim ? qmap[b * nt + t0] : (W)0) | (t0 + 1 < lim ? qmap[b * nt + t0 + 1] : (W)0));
     }
     if (kv_pairs) {
       const int t0 = 2 * (sl % n_inner);
-      const unsigned int u = p.kmap[b * nt + t0] | (t0 + 1 < nt ? p.kmap[b * nt + t0 + 1] : 0u);
-      return __popc(u & (qa >= 32 ? ~0u : ((1u << qa) - 1u)));
+      const W u = kmap[b * nt + t0] | (t0 + 1 < nt ? kmap[b * nt + t0 + 1] : (W)0);
+      return map_popc(u & map_below<LG>(qa));
     }
-    return __popc(p.kmap[b * nt + tile] & (qa >= 32 ? ~0u : ((1u << qa) - 1u)));
+    return map_popc(kmap[b * nt + tile] & map_below<LG>(qa));
   };
   auto same_key = [&](int k) -> unsigned long long {   // lanes of this wave that hold the same key
     unsigned long long m = ~0ull;
 #pragma unroll
-    for (int bit = 0; bit < 6; ++bit) { const unsigned long long bb = __ballot((k >> bit) & 1); m &= ((k >> bit) & 1) ? bb : ~bb; }
+    for (int bit = 0; bit < LG + 1; ++bit) { const unsigned long long bb = __ballot((k >> bit) & 1); m &= ((k >> bit) & 1) ? bb : ~bb; }
     return m;
   };
-  for (int i = threadIdx.x; i < (nch + 1) * 34; i += 256) ocnt[i] = 0;
+  for (int i = threadIdx.x; i < (nch + 1) * OS; i += 256) ocnt[i] = 0;
   __syncthreads();
   for (int c = w; c < nch; c += 4) {
     const int k = key_of(c * 64 + l);
     const unsigned long long m = same_key(k);
-    if ((m & ((1ull << l) - 1ull)) == 0ull) ocnt[c * 34 + k] = __popcll(m);   // (the first lane of each key of the chunk)
+    if ((m & ((1ull << l) - 1ull)) == 0ull) ocnt[c * OS + k] = __popcll(m);   // (the first lane of each key of the chunk)
   }
   __syncthreads();
-  if (threadIdx.x < 34) {
+  if (threadIdx.x < OS) {
     const int k = threadIdx.x;
     int run = 0;
-    for (int c = 0; c < nch; ++c) { const int n = ocnt[c * 34 + k]; ocnt[c * 34 + k] = run; run += n; }
-    ocnt[nch * 34 + k] = run;
+    for (int c = 0; c < nch; ++c) { const int n = ocnt[c * OS + k]; ocnt[c * OS + k] = run; run += n; }
+    ocnt[nch * OS + k] = run;
   }
   __syncthreads();
   if (threadIdx.x == 0) {   // heaviest first: the base of key k = slots with a larger key
     int acc = 0;
-    for (int k = 32; k >= 0; --k) { const int n = ocnt[nch * 34 + k]; ocnt[nch * 34 + k] = acc; acc += n; }
+    for (int k = NTM; k >= 0; --k) { const int n = ocnt[nch * OS + k]; ocnt[nch * OS + k] = acc; acc += n; }
   }
   __syncthreads();
   for (int c = w; c < nch; c += 4) {
     const int sl = c * 64 + l, k = key_of(sl);
     const unsigned long long m = same_key(k);
-    if (sl < ns) out[ocnt[nch * 34 + k] + ocnt[c * 34 + k] + __popcll(m & ((1ull << l) - 1ull))] = sl;
+    if (sl < ns) out[ocnt[nch * OS + k] + ocnt[c * OS + k] + __popcll(m & ((1ull << l) - 1ull))] = sl;
   }
 }
 
 int launch_attn_tilemap(const AttnParams& p, hipStream_t s) {
-  ARG_CHECK(p.T % 8 == 0 && (p.T + 63) / 64 <= 32, "attention: T must be a multiple of 8 and <= 2048");
+  ARG_CHECK(p.T % 8 == 0 && (p.T + 63) / 64 <= 64, "attention: T must be a multiple of 8 and <= 4096");
   ARG_CHECK(p.qbits != nullptr && p.kbits != nullptr, "attention: the pair-bit buffers (AttnParams::qbits / kbits) are required");
-  const size_t bytes = sizeof(unsigned int) * p.B * ((p.T + 63) / 64);
+  const bool wide = (p.T + 63) / 64 > 32;   // 64-bit map words (AMap<6>)
+  const size_t bytes = sizeof(unsigned int) * attn_map_words(p.T) * p.B * ((p.T + 63) / 64);
   if (p.maps_zero_base != nullptr) {
     HIP_CHECK(hipMemsetAsync(p.maps_zero_base, 0, p.maps_zero_bytes, s));
   } else {
@@ -502,13 +539,16 @@ int launch_attn_tilemap(const AttnParams& p, hipStream_t s) {
     HIP_CHECK(hipMemsetAsync(p.qmap_full, 0, bytes, s));
     HIP_CHECK(hipMemsetAsync(p.kmap16, 0, bytes * 4, s));
   }
-  hipLaunchKernelGGL(attn_tilemap_kernel, dim3((p.T + 63) / 64, p.B), dim3(256), 0, s, p);
+  if (wide) hipLaunchKernelGGL(attn_tilemap_kernel<6>, dim3((p.T + 63) / 64, p.B), dim3(256), 0, s, p);
+  else hipLaunchKernelGGL(attn_tilemap_kernel<5>, dim3((p.T + 63) / 64, p.B), dim3(256), 0, s, p);
   if (p.order_q != nullptr || p.order_k != nullptr || p.order_q2 != nullptr) {
     const int R = attn_heads_per_wg(p), nt = (p.T + 63) / 64, n_groups = p.B * p.KV;
     const int ns_max = ((n_groups & 7) == 0 ? (n_groups >> 3) : n_groups) * (p.H / p.KV) * nt;
     // (a list beyond one workgroup's LDS: keep the plain order -- the kernels read an identity permutation)
-    hipLaunchKernelGGL(attn_order_kernel, dim3((n_groups & 7) == 0 ? 8 : 1, p.order_q2 != nullptr ? 3 : 2), dim3(256), (size_t)(std::min((ns_max + 63) / 64, 400) + 1) * 34 * 4, s, p, R, (ns_max + 63) / 64 > 400 ? 1 : 0,
-                       attn_kv_pairs(p) ? 1 : 0);
+    const int cap = attn_order_chunk_cap(wide ? 6 : 5), nch = (ns_max + 63) / 64;
+    const dim3 og((n_groups & 7) == 0 ? 8 : 1, p.order_q2 != nullptr ? 3 : 2);
+    if (wide) hipLaunchKernelGGL(attn_order_kernel<6>, og, dim3(256), (size_t)(std::min(nch, cap) + 1) * 66 * 4, s, p, R, nch > cap ? 1 : 0, attn_kv_pairs(p) ? 1 : 0);
+    else hipLaunchKernelGGL(attn_order_kernel<5>, og, dim3(256), (size_t)(std::min(nch, cap) + 1) * 34 * 4, s, p, R, nch > cap ? 1 : 0, attn_kv_pairs(p) ? 1 : 0);
   }
   HIP_CHECK(hipGetLastError());
   return RSYS_OK;
@@ -679,9 +719,10 @@ __device__ __forceinline__ bf16x8 pack8f(const f32x16& v, int o) {
 // staged K / V tile, every K and V^T fragment read, the tile maps and -- the mask depends on the tokens only -- the mask
 // predicates; soft-max statistics and the output accumulators are per head.
 // DMA (bf16, head_dim 64): the K / V tiles arrive by LDS-DMA in unpadded XOR-swizzled tiles (frag_rows_sw), as in attn_bwd_kv_dma_kernel.
-template <typename T, int HD, int R, bool DMA = false>
+template <typename T, int HD, int R, bool DMA = false, int LG = 5>
 __global__ __launch_bounds__(256, (is_bf16<T>::value && HD <= 64) ? (R == 1 ? 3 : (DMA ? 3 : 2)) : 1) void attn_fwd_kernel(AttnParams p) {
   using C = ACfg<T, HD>;
+  using W = typename AMap<LG>::W;
   using M = AMma<T>;
   static_assert(!DMA || (is_bf16<T>::value && HD == 64), "LDS-DMA staging: bf16, head_dim 64");
   constexpr int TILE = DMA ? 64 * 64 : C::TILE;   // elements of a staged tile
@@ -716,8 +757,8 @@ __global__ __launch_bounds__(256, (is_bf16<T>::value && HD <= 64) ? (R == 1 ? 3 
   }
   if constexpr (!DMA) { zero_pad_cols<T, HD>(Ks, t); zero_pad_cols<T, HD>(Ks + C::TILE, t); }
   // (scalars through readfirstlane: loaded by vector memory -- the maps are not const -- and otherwise still pending when the item loop begins)
-  const unsigned int bits = (unsigned int)__builtin_amdgcn_readfirstlane((int)p.qmap[b * nt + qt]), fullbits = (unsigned int)__builtin_amdgcn_readfirstlane((int)p.qmap_full[b * nt + qt]);
-  const unsigned int wbits = __builtin_amdgcn_readfirstlane(p.qmap16[(b * nt + qt) * 4 + w]);   // kv tiles this wave's 16 queries take part in
+  const W bits = map_uniform(map_ptr<LG>(p.qmap)[b * nt + qt]), fullbits = map_uniform(map_ptr<LG>(p.qmap_full)[b * nt + qt]);
+  const W wbits = map_uniform(map_ptr<LG>(p.qmap16)[(b * nt + qt) * 4 + w]);   // kv tiles this wave's 16 queries take part in
   // K / V of this kv head, rows of this sequence ([T][HD] windows of the row-major qkv), and the rows' uid / tm (tile_load_buf)
   const at_i32x4 k_rs = at_rsrc((const T*)p.k + tok0 * p.ld + kvh * HD, ((long long)(p.T - 1) * p.ld + HD) * sizeof(T));
   const at_i32x4 v_rs = at_rsrc((const T*)p.v + tok0 * p.ld + kvh * HD, ((long long)(p.T - 1) * p.ld + HD) * sizeof(T));
@@ -862,9 +903,12 @@ __device__ __forceinline__ float pair_rows_sum(float v) {
   auto b = __builtin_amdgcn_permlane32_swap(u, u, false, false);
   return __builtin_bit_cast(float, (unsigned int)b[0]) + __builtin_bit_cast(float, (unsigned int)b[1]);
 }
+template <int LG>
 __global__ __launch_bounds__(256, ATTN_FWD32_WPS) void attn_fwd32_kernel(AttnParams p) {
   constexpr int HD = 64, TB = 64 * 64;   // elements of an unpadded tile
   using T = bf16;
+  using W = typename AMap<LG>::W;
+  const W *qmap = map_ptr<LG>(p.qmap), *qmap_full = map_ptr<LG>(p.qmap_full), *qmap16 = map_ptr<LG>(p.qmap16);
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   unsigned char* const Kb = smem_raw;                 // [2][64 kv][128 B] swizzled (sw32)
   unsigned char* const Vb = smem_raw + 2 * TB * 2;    // [2][64 kv][128 B]
@@ -893,9 +937,9 @@ __global__ __launch_bounds__(256, ATTN_FWD32_WPS) void attn_fwd32_kernel(AttnPar
   for (int i = 0; i < 16; ++i) { O[0][i] = 0.f; O[1][i] = 0.f; }
   float m_run = -1e30f, l_run = 0.f;
   const int t0i = b * nt + 2 * pr, t1i = b * nt + min(2 * pr + 1, nt - 1), qti = b * nt + min(qt, nt - 1);
-  const unsigned int bits = (unsigned int)__builtin_amdgcn_readfirstlane((int)(p.qmap[t0i] | (2 * pr + 1 < qa ? p.qmap[t1i] : 0u)));   // kv tiles the workgroup stages
-  const unsigned int fullbits = tile_ok ? (unsigned int)__builtin_amdgcn_readfirstlane((int)p.qmap_full[qti]) : 0u;
-  const unsigned int wbits = tile_ok ? (unsigned int)__builtin_amdgcn_readfirstlane((int)(p.qmap16[qti * 4 + 2 * (w & 1)] | p.qmap16[qti * 4 + 2 * (w & 1) + 1])) : 0u;
+  const W bits = map_uniform((W)(qmap[t0i] | (2 * pr + 1 < qa ? qmap[t1i] : (W)0)));   // kv tiles the workgroup stages
+  const W fullbits = tile_ok ? map_uniform(qmap_full[qti]) : (W)0;
+  const W wbits = tile_ok ? map_uniform((W)(qmap16[qti * 4 + 2 * (w & 1)] | qmap16[qti * 4 + 2 * (w & 1) + 1])) : (W)0;
   const at_i32x4 k_rs = at_rsrc((const T*)p.k + tok0 * p.ld + kvh * HD, ((long long)(p.T - 1) * p.ld + HD) * sizeof(T));
   const at_i32x4 v_rs = at_rsrc((const T*)p.v + tok0 * p.ld + kvh * HD, ((long long)(p.T - 1) * p.ld + HD) * sizeof(T));
   // the pair bits of this wave's q tile against every kv tile: [nt][64 queries] words (an inactive tile: an empty window, all zero)
@@ -1060,44 +1104,46 @@ static int attn_heads_per_wg(const AttnParams& p) {
   return (p.H / p.KV == 2 && p.hd <= 64) ? 2 : 1;   // (head_dim 128: two heads' accumulators cost a wave per SIMD)
 }
 
-template <typename T, int HD>
+template <typename T, int HD, int LG>
 static int attn_fwd_hd(const AttnParams& p, hipStream_t s) {
   using C = ACfg<T, HD>;
   const size_t sm = sizeof(T) * 4 * C::TILE + 384 * sizeof(int);
   static bool set = false;
   if (!set) {
-    HIP_CHECK(hipFuncSetAttribute((const void*)attn_fwd_kernel<T, HD, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm));
-    HIP_CHECK(hipFuncSetAttribute((const void*)attn_fwd_kernel<T, HD, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm));
+    HIP_CHECK(hipFuncSetAttribute((const void*)attn_fwd_kernel<T, HD, 1, false, LG>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm));
+    HIP_CHECK(hipFuncSetAttribute((const void*)attn_fwd_kernel<T, HD, 2, false, LG>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm));
     set = true;
   }
   if constexpr (is_bf16<T>::value && HD == 64) {
     if (attn_dma_on() && sw().attn_fwd32 != 0) {   // RSYS_ATTN_FWD32=1 (opt-in): 128 queries of one head per workgroup on 32 x 32 x 16 products
       static bool set32 = false;
-      if (!set32) { HIP_CHECK(hipFuncSetAttribute((const void*)attn_fwd32_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 64 * 64 * 2)); set32 = true; }
+      if (!set32) { HIP_CHECK(hipFuncSetAttribute((const void*)attn_fwd32_kernel<LG>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 64 * 64 * 2)); set32 = true; }
       const int nt = (p.T + 63) / 64;
-      hipLaunchKernelGGL(attn_fwd32_kernel, dim3(((nt + 1) / 2) * p.H * p.B), dim3(256), 4 * 64 * 64 * 2, s, p);
+      hipLaunchKernelGGL(attn_fwd32_kernel<LG>, dim3(((nt + 1) / 2) * p.H * p.B), dim3(256), 4 * 64 * 64 * 2, s, p);
       HIP_CHECK(hipGetLastError());
       return RSYS_OK;
     }
     if (attn_dma_on()) {   // LDS-DMA staging (RSYS_ATTN_DMA=0: the register-staged kernels)
       const size_t sm_dma = 4 * 64 * 64 * 2 + 384 * 4;
-      if (attn_heads_per_wg(p) == 2) hipLaunchKernelGGL((attn_fwd_kernel<T, HD, 2, true>), dim3(((p.T + 63) / 64) * (p.H / 2) * p.B), dim3(256), sm_dma, s, p);
-      else hipLaunchKernelGGL((attn_fwd_kernel<T, HD, 1, true>), dim3(((p.T + 63) / 64) * p.H * p.B), dim3(256), sm_dma, s, p);
+      if (attn_heads_per_wg(p) == 2) hipLaunchKernelGGL((attn_fwd_kernel<T, HD, 2, true, LG>), dim3(((p.T + 63) / 64) * (p.H / 2) * p.B), dim3(256), sm_dma, s, p);
+      else hipLaunchKernelGGL((attn_fwd_kernel<T, HD, 1, true, LG>), dim3(((p.T + 63) / 64) * p.H * p.B), dim3(256), sm_dma, s, p);
       HIP_CHECK(hipGetLastError());
       return RSYS_OK;
     }
   }
-  if (attn_heads_per_wg(p) == 2) hipLaunchKernelGGL((attn_fwd_kernel<T, HD, 2>), dim3(((p.T + 63) / 64) * (p.H / 2) * p.B), dim3(256), sm, s, p);
-  else hipLaunchKernelGGL((attn_fwd_kernel<T, HD, 1>), dim3(((p.T + 63) / 64) * p.H * p.B), dim3(256), sm, s, p);
+  if (attn_heads_per_wg(p) == 2) hipLaunchKernelGGL((attn_fwd_kernel<T, HD, 2, false, LG>), dim3(((p.T + 63) / 64) * (p.H / 2) * p.B), dim3(256), sm, s, p);
+  else hipLaunchKernelGGL((attn_fwd_kernel<T, HD, 1, false, LG>), dim3(((p.T + 63) / 64) * p.H * p.B), dim3(256), sm, s, p);
   HIP_CHECK(hipGetLastError());
   return RSYS_OK;
 }
 
 static int check_attn(const AttnParams& p, size_t esz) {
-  ARG_CHECK(p.T % 8 == 0 && (p.T + 63) / 64 <= 32, "attention: T must be a multiple of 8 and <= 2048");
+  ARG_CHECK(p.T % 8 == 0 && (p.T + 63) / 64 <= 64, "attention: T must be a multiple of 8 and <= 4096");
   ARG_CHECK(p.qbits != nullptr && p.kbits != nullptr, "attention: the pair-bit buffers (AttnParams::qbits / kbits) are required");
   ARG_CHECK(p.H % p.KV == 0, "attention: H % KV");
   ARG_CHECK((p.ld * esz) % 16 == 0 && (p.hd * esz) % 16 == 0, "attention: 16-byte row alignment");
+  // (the kernels address a row's tiles through 32-bit buffer offsets: at T = 4096, ld = 4096 in bf16 a row is 32 MiB)
+  ARG_CHECK((long long)p.T * std::max(p.ld, p.ldo) * (long long)esz < (1ll << 31), "attention: a row of qkv must stay below 2 GiB");
   return RSYS_OK;
 }
 
@@ -1105,11 +1151,12 @@ template <typename T>
 int launch_attn_fwd(const AttnParams& p, hipStream_t s) {
   int rc = check_attn(p, sizeof(T));
   if (rc) return rc;
+  const bool wide = (p.T + 63) / 64 > 32;   // 64-bit map words: the AMap<6> instantiations (rows of up to 32 tiles keep the 32-bit ones)
   switch (p.hd) {
-    case 16: return attn_fwd_hd<T, 16>(p, s);
-    case 32: return attn_fwd_hd<T, 32>(p, s);
-    case 64: return attn_fwd_hd<T, 64>(p, s);
-    case 128: return attn_fwd_hd<T, 128>(p, s);
+    case 16: return wide ? attn_fwd_hd<T, 16, 6>(p, s) : attn_fwd_hd<T, 16, 5>(p, s);
+    case 32: return wide ? attn_fwd_hd<T, 32, 6>(p, s) : attn_fwd_hd<T, 32, 5>(p, s);
+    case 64: return wide ? attn_fwd_hd<T, 64, 6>(p, s) : attn_fwd_hd<T, 64, 5>(p, s);
+    case 128: return wide ? attn_fwd_hd<T, 128, 6>(p, s) : attn_fwd_hd<T, 128, 5>(p, s);
   }
   set_error("attention: head_dim must be 16, 32, 64 or 128");
   return RSYS_ERR_ARG;
@@ -1142,10 +1189,12 @@ __device__ __forceinline__ void store_grad_tile(f32x4 (&acc)[HD / 16], bool rota
   }
 }
 // ------------------------------------------------------------------------ backward: dK, dV (one workgroup per kv tile and kv head)
-template <typename T, int HD>
+template <typename T, int HD, int LG = 5>
 __global__ __launch_bounds__(256, (is_bf16<T>::value && HD <= 64) ? 3 : 1) void attn_bwd_kv_kernel(AttnParams p) {
   using C = ACfg<T, HD>;
   using M = AMma<T>;
+  using W = typename AMap<LG>::W;
+  constexpr int NTM = 1 << LG;   // item = head of the group * NTM + q tile
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   T* Qs = (T*)smem_raw;                  // [2][64 q][LDD]
   T* dOs = Qs + 2 * C::TILE;             // [2][64 q][LDD]
@@ -1172,10 +1221,10 @@ __global__ __launch_bounds__(256, (is_bf16<T>::value && HD <= 64) ? 3 : 1) void 
 #pragma unroll
   for (int j = 0; j < HD / 16; ++j) { dK[0][j] = f32x4{0, 0, 0, 0}; dV[0][j] = f32x4{0, 0, 0, 0}; }
   for (int i = 0; i < 2; ++i) { zero_pad_cols<T, HD>(Qs + i * C::TILE, t); zero_pad_cols<T, HD>(dOs + i * C::TILE, t); }
-  const int qa = p.q_active != nullptr ? p.q_active[b] : 32;
-  const unsigned int act = qa >= 32 ? ~0u : ((1u << qa) - 1u);   // query tiles whose dO can be non-zero
-  const unsigned int bits = p.kmap[b * nt + kvt] & act, fullbits = p.kmap_full[b * nt + kvt];
-  const unsigned int wbits = __builtin_amdgcn_readfirstlane(p.kmap16[(b * nt + kvt) * 4 + w]);   // q tiles that may see this wave's 16 keys
+  const int qa = p.q_active != nullptr ? p.q_active[b] : NTM;
+  const W act = map_below<LG>(qa);   // query tiles whose dO can be non-zero
+  const W bits = map_ptr<LG>(p.kmap)[b * nt + kvt] & act, fullbits = map_ptr<LG>(p.kmap_full)[b * nt + kvt];
+  const W wbits = map_uniform(map_ptr<LG>(p.kmap16)[(b * nt + kvt) * 4 + w]);   // q tiles that may see this wave's 16 keys
 
   // Staging runs TWO items ahead of the arithmetic: an item's global loads have a whole iteration (one item of another workgroup's
   // arithmetic would not cover their latency) before they are stored to LDS, and that store is in LDS one barrier before its use.
@@ -1197,8 +1246,8 @@ __global__ __launch_bounds__(256, (is_bf16<T>::value && HD <= 64) ? 3 : 1) void 
   // wave 0 (a wave-uniform branch) stages the 64 rows' scalars.  (One array per wave instead -- log-sum-exp, -delta, keys on waves 0, 1, 2 --
   // was measured 7 % SLOWER: three more uniform branches per item in every wave; profiles/r4_ab_attn_staging.log)
   const bool w0 = __builtin_amdgcn_readfirstlane(w) == 0;
-  auto gload = [&](ItemRegs& r, int it) {   // it = head-in-group * 32 + q tile
-    const int hh = it >> 5, qt = it & 31;
+  auto gload = [&](ItemRegs& r, int it) {   // it = head-in-group * NTM + q tile
+    const int hh = it >> LG, qt = it & (NTM - 1);
     tile_load_buf<T, HD>(r.rq, q_rs, q_of, (int)((qt * 64 * p.ld + hh * HD) * sizeof(T)));
     tile_load_buf<T, HD>(r.rdo, do_rs, do_of, (int)((qt * 64 * p.ldo + hh * HD) * sizeof(T)));
     if (w0) {   // (rows past the sequence: the next head's finite values or zero, all masked, and the key of no query)
@@ -1213,16 +1262,16 @@ __global__ __launch_bounds__(256, (is_bf16<T>::value && HD <= 64) ? 3 : 1) void 
     tile_store<T, HD>(r.rdo, dOs + buf * C::TILE, t);
     if (w0) { ((int*)lse2)[buf * 64 + l] = r.x; ((int*)dls)[buf * 64 + l] = r.y; kbs[buf * 64 + l] = r.kb; }
   };
-  auto next_item = [&](int from) {   // items are (head, q tile) pairs in order; returns rep*32 when exhausted
-    int hh = from >> 5, qt = from & 31;
+  auto next_item = [&](int from) {   // items are (head, q tile) pairs in order; returns rep * NTM when exhausted
+    int hh = from >> LG, qt = from & (NTM - 1);
     while (hh < rep) {
       const int n = next_bit(bits, qt);
-      if (n < nt) return hh * 32 + n;
+      if (n < nt) return hh * NTM + n;
       ++hh; qt = 0;
     }
-    return rep * 32;
+    return rep * NTM;
   };
-  const int end = rep * 32;
+  const int end = rep * NTM;
   int it = next_item(0), cur = 0;
   int nxt = it < end ? next_item(it + 1) : end, nxt2 = nxt < end ? next_item(nxt + 1) : end;   // the items staged one and two ahead
   if (it < end) { gload(R0, it); lstore(R0, 0); }
@@ -1232,8 +1281,8 @@ __global__ __launch_bounds__(256, (is_bf16<T>::value && HD <= 64) ? 3 : 1) void 
     if (nxt2 < end) gload(rload, nxt2);
     const T* Qc = Qs + cur * C::TILE;
     const T* dOc = dOs + cur * C::TILE;
-    if ((wbits >> (it & 31)) & 1u) {   // (nothing to add for a wave whose 16 keys no query of this tile may see)
-    const bool fullt = (fullbits >> (it & 31)) & 1u;
+    if ((wbits >> (it & (NTM - 1))) & 1u) {   // (nothing to add for a wave whose 16 keys no query of this tile may see)
+    const bool fullt = (fullbits >> (it & (NTM - 1))) & 1u;
     const unsigned long long wk = kbs[cur * 64 + w * 16 + fr] >> (4 * g);   // the lane's key against the item's 64 queries (mask_bits_block)
 #pragma unroll
     for (int t2 = 0; t2 < 2; ++t2) {   // 32 queries at a time: both stages, two score blocks alive (no row maximum is needed here)
@@ -1298,11 +1347,14 @@ __device__ unsigned long long rsys_attn_trace[16 * 8192];
 #else
 #define KVT_NOW() 0ull
 #endif
+template <int LG>
 __global__ __launch_bounds__(256, 4) void attn_bwd_kv_dma_kernel(AttnParams p) {
   [[maybe_unused]] unsigned long long tr_[12] = {KVT_NOW(), 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
   constexpr int HD = 64, TB = 64 * 64;   // elements of an unpadded tile
   using T = bf16;
   using C = ACfg<T, HD>;
+  using W = typename AMap<LG>::W;
+  constexpr int NTM = 1 << LG;   // item = head of the group * NTM + q tile
   // (The compiler orders an LDS read behind a pending LDS-DMA unless it can tell the two apart, so each item starts with a wait for the
   // next item's DMA it has just issued; the other three workgroups of the CU run meanwhile.  Telling them apart was tried -- one LDS
   // object per buffer and the item loop unrolled by two: no wait, but 158 registers = three workgroups per CU and 209 against 198 us, or
@@ -1331,10 +1383,10 @@ __global__ __launch_bounds__(256, 4) void attn_bwd_kv_dma_kernel(AttnParams p) {
   f32x4 dK[1][4], dV[1][4];
 #pragma unroll
   for (int j = 0; j < 4; ++j) { dK[0][j] = f32x4{0, 0, 0, 0}; dV[0][j] = f32x4{0, 0, 0, 0}; }
-  const int qa = p.q_active != nullptr ? p.q_active[b] : 32;
-  const unsigned int act = qa >= 32 ? ~0u : ((1u << qa) - 1u);
-  const unsigned int bits = p.kmap[b * nt + kvt] & act, fullbits = p.kmap_full[b * nt + kvt];
-  const unsigned int wbits = __builtin_amdgcn_readfirstlane(p.kmap16[(b * nt + kvt) * 4 + w]);
+  const int qa = p.q_active != nullptr ? p.q_active[b] : NTM;
+  const W act = map_below<LG>(qa);
+  const W bits = map_ptr<LG>(p.kmap)[b * nt + kvt] & act, fullbits = map_ptr<LG>(p.kmap_full)[b * nt + kvt];
+  const W wbits = map_uniform(map_ptr<LG>(p.kmap16)[(b * nt + kvt) * 4 + w]);
   const at_i32x4 q_rs = at_rsrc((const T*)p.q + tok0 * p.ld + kvh * rep * HD, ((long long)(p.T - 1) * p.ld + rep * HD) * sizeof(T));
   const at_i32x4 do_rs = at_rsrc((const T*)p.dO + tok0 * p.ldo + kvh * rep * HD, ((long long)(p.T - 1) * p.ldo + rep * HD) * sizeof(T));
   const at_i32x4 lse_rs = at_rsrc(p.lse + ((long long)b * p.H + kvh * rep) * p.T, (long long)rep * p.T * 4);
@@ -1350,8 +1402,8 @@ __global__ __launch_bounds__(256, 4) void attn_bwd_kv_dma_kernel(AttnParams p) {
     dv_[k] = (int)((row * p.ldo + ch * 8) * sizeof(T));
   }
   int sx = 0, sy = 0; unsigned long long skb = 0ull;   // (wave 0) the next item's row scalars on their way to LDS
-  auto stage = [&](int it, int buf) {   // it = head-in-group * 32 + q tile
-    const int hh = it >> 5, qt = it & 31;
+  auto stage = [&](int it, int buf) {   // it = head-in-group * NTM + q tile
+    const int hh = it >> LG, qt = it & (NTM - 1);
     const int qso = (int)((qt * 64 * p.ld + hh * HD) * sizeof(T)), dso = (int)((qt * 64 * p.ldo + hh * HD) * sizeof(T));
     unsigned char* qd = (unsigned char*)(Qs + buf * TB) + (16 * w) * 128;
     unsigned char* dd = (unsigned char*)(dOs + buf * TB) + (16 * w) * 128;
@@ -1372,15 +1424,15 @@ __global__ __launch_bounds__(256, 4) void attn_bwd_kv_dma_kernel(AttnParams p) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   };
   auto next_item = [&](int from) {
-    int hh = from >> 5, qt = from & 31;
+    int hh = from >> LG, qt = from & (NTM - 1);
     while (hh < rep) {
       const int n = next_bit(bits, qt);
-      if (n < nt) return hh * 32 + n;
+      if (n < nt) return hh * NTM + n;
       ++hh; qt = 0;
     }
-    return rep * 32;
+    return rep * NTM;
   };
-  const int end = rep * 32;
+  const int end = rep * NTM;
   int it = next_item(0), cur = 0;
   if (it < end) { stage(it, 0); publish(0); }
   __syncthreads();
@@ -1392,8 +1444,8 @@ __global__ __launch_bounds__(256, 4) void attn_bwd_kv_dma_kernel(AttnParams p) {
     [[maybe_unused]] const unsigned long long tb = KVT_NOW();
     const T* Qc = Qs + cur * TB;
     const T* dOc = dOs + cur * TB;
-    if ((wbits >> (it & 31)) & 1u) {
-      const bool fullt = (fullbits >> (it & 31)) & 1u;
+    if ((wbits >> (it & (NTM - 1))) & 1u) {
+      const bool fullt = (fullbits >> (it & (NTM - 1))) & 1u;
       const unsigned long long wk = kbs[cur * 64 + w * 16 + fr] >> (4 * g);
 #pragma unroll
       for (int t2 = 0; t2 < 2; ++t2) {
@@ -1435,7 +1487,7 @@ __global__ __launch_bounds__(256, 4) void attn_bwd_kv_dma_kernel(AttnParams p) {
     __syncthreads();
 #ifdef ATTN_KV_TRACE
     const unsigned long long te = KVT_NOW();
-    tr_[4] += tb - ta; tr_[5] += tc - tb; tr_[6] += td - tc; tr_[7] += te - td; tr_[8] += 1; tr_[9] += (wbits >> (it & 31)) & 1u;
+    tr_[4] += tb - ta; tr_[5] += tc - tb; tr_[6] += td - tc; tr_[7] += te - td; tr_[8] += 1; tr_[9] += (wbits >> (it & (NTM - 1))) & 1u;
 #endif
     cur ^= 1;
     it = nxt;
@@ -1473,10 +1525,14 @@ static bool attn_kv_pairs(const AttnParams& p) {   // (bf16 is the caller's busi
 #ifndef ATTN_KV32_WPS
 #define ATTN_KV32_WPS 3   // waves per SIMD the kernel is compiled for: 168 registers, 5 dwords spilled OUTSIDE the item loop; 2 (189 registers) is 9 % slower (profiles/r5_ab_attn_kv32.log)
 #endif
+template <int LG>
 __global__ __launch_bounds__(256, ATTN_KV32_WPS) void attn_bwd_kv32_kernel(AttnParams p) {
   [[maybe_unused]] unsigned long long tr_[12] = {KVT_NOW(), 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};   // (-DATTN_KV_TRACE only: tools/trace_attn_kv.sh)
   constexpr int HD = 64, TB = 64 * 64;   // elements of an unpadded tile
   using T = bf16;
+  using W = typename AMap<LG>::W;
+  constexpr int NTM = 1 << LG;   // item = head of the group * NTM + q tile
+  const W *kmap = map_ptr<LG>(p.kmap), *kmap_full = map_ptr<LG>(p.kmap_full), *kmap16 = map_ptr<LG>(p.kmap16);
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   unsigned char* const Qb = smem_raw;                   // [2][64 q][128 B] swizzled
   unsigned char* const dOb = smem_raw + 2 * TB * 2;     // [2][64 q][128 B]
@@ -1504,13 +1560,13 @@ __global__ __launch_bounds__(256, ATTN_KV32_WPS) void attn_bwd_kv32_kernel(AttnP
   f32x16 dK[2], dV[2];
 #pragma unroll
   for (int i = 0; i < 16; ++i) { dK[0][i] = 0.f; dK[1][i] = 0.f; dV[0][i] = 0.f; dV[1][i] = 0.f; }
-  const int qa = p.q_active != nullptr ? p.q_active[b] : 32;
-  const unsigned int act = qa >= 32 ? ~0u : ((1u << qa) - 1u);
+  const int qa = p.q_active != nullptr ? p.q_active[b] : NTM;
+  const W act = map_below<LG>(qa);
   const int t0i = b * nt + 2 * pr, t1i = min(2 * pr + 1, nt - 1) + b * nt;
-  const unsigned int bits = (unsigned int)__builtin_amdgcn_readfirstlane((int)((p.kmap[t0i] | (2 * pr + 1 < nt ? p.kmap[t1i] : 0u)) & act));   // q tiles the workgroup stages (union of its two kv tiles)
+  const W bits = map_uniform((W)((kmap[t0i] | (2 * pr + 1 < nt ? kmap[t1i] : (W)0)) & act));   // q tiles the workgroup stages (union of its two kv tiles)
   const int kti = b * nt + min(kvt, nt - 1);
-  const unsigned int fullbits = tile_ok ? (unsigned int)__builtin_amdgcn_readfirstlane((int)p.kmap_full[kti]) : 0u;
-  const unsigned int wbits = tile_ok ? (unsigned int)__builtin_amdgcn_readfirstlane((int)(p.kmap16[kti * 4 + 2 * (w & 1)] | p.kmap16[kti * 4 + 2 * (w & 1) + 1])) : 0u;
+  const W fullbits = tile_ok ? map_uniform(kmap_full[kti]) : (W)0;
+  const W wbits = tile_ok ? map_uniform((W)(kmap16[kti * 4 + 2 * (w & 1)] | kmap16[kti * 4 + 2 * (w & 1) + 1])) : (W)0;
   const at_i32x4 q_rs = at_rsrc((const T*)p.q + tok0 * p.ld + kvh * rep * HD, ((long long)(p.T - 1) * p.ld + rep * HD) * sizeof(T));
   const at_i32x4 do_rs = at_rsrc((const T*)p.dO + tok0 * p.ldo + kvh * rep * HD, ((long long)(p.T - 1) * p.ldo + rep * HD) * sizeof(T));
   const at_i32x4 lse_rs = at_rsrc(p.lse + ((long long)b * p.H + kvh * rep) * p.T, (long long)rep * p.T * 4);
@@ -1539,8 +1595,8 @@ __global__ __launch_bounds__(256, ATTN_KV32_WPS) void attn_bwd_kv32_kernel(AttnP
   const bool w0 = w == 0;
   const unsigned int lds0 = (unsigned int)__builtin_amdgcn_readfirstlane((int)(unsigned int)(unsigned long long)(LDS_AS unsigned char*)smem_raw);
   int sx = 0, sy = 0; unsigned long long skb = 0ull;   // the next item's row scalars (wave 0) and this lane's pair-bit word on their way
-  auto stage = [&](int it, int buf) {   // it = head-in-group * 32 + q tile
-    const int hh = it >> 5, qt = it & 31;
+  auto stage = [&](int it, int buf) {   // it = head-in-group * NTM + q tile
+    const int hh = it >> LG, qt = it & (NTM - 1);
     const int qso = (int)((qt * 64 * p.ld + hh * HD) * sizeof(T)), dso = (int)((qt * 64 * p.ldo + hh * HD) * sizeof(T));
     const unsigned int qd = lds0 + buf * (TB * 2) + (16 * w) * 128, dd = qd + 2 * TB * 2;
 #pragma unroll
@@ -1561,12 +1617,12 @@ __global__ __launch_bounds__(256, ATTN_KV32_WPS) void attn_bwd_kv32_kernel(AttnP
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   };
   // items = (head of the group, q tile in `bits`), heads outermost: a scalar iterator, two scalar instructions per step
-  const int end = rep * 32;
+  const int end = rep * NTM;
   auto next_item = [&](int from) {
-    int hh = from >> 5, qt = from & 31;
+    int hh = from >> LG, qt = from & (NTM - 1);
     while (hh < rep) {
       const int n = next_bit(bits, qt);
-      if (n < nt) return hh * 32 + n;
+      if (n < nt) return hh * NTM + n;
       ++hh; qt = 0;
     }
     return end;
@@ -1588,8 +1644,8 @@ __global__ __launch_bounds__(256, ATTN_KV32_WPS) void attn_bwd_kv32_kernel(AttnP
     const int nxt = next_item(it + 1);
     if (nxt < end) stage(nxt, cur ^ 1);   // (the other buffer: every wave left it before the barrier that ended the previous item)
     [[maybe_unused]] const unsigned long long tb = KVT_NOW();
-    if ((wbits >> (it & 31)) & 1u) {
-      const bool fullt = (fullbits >> (it & 31)) & 1u;
+    if ((wbits >> (it & (NTM - 1))) & 1u) {
+      const bool fullt = (fullbits >> (it & (NTM - 1))) & 1u;
       const unsigned char* Qc = Qb + cur * (TB * 2);
       const unsigned char* dOc = dOb + cur * (TB * 2);
 #pragma unroll
@@ -1652,7 +1708,7 @@ __global__ __launch_bounds__(256, ATTN_KV32_WPS) void attn_bwd_kv32_kernel(AttnP
     __syncthreads();
 #ifdef ATTN_KV_TRACE
     const unsigned long long te = KVT_NOW();
-    tr_[4] += tb - ta; tr_[5] += tc - tb; tr_[6] += td - tc; tr_[7] += te - td; tr_[8] += 1; tr_[9] += (wbits >> (it & 31)) & 1u;
+    tr_[4] += tb - ta; tr_[5] += tc - tb; tr_[6] += td - tc; tr_[7] += te - td; tr_[8] += 1; tr_[9] += (wbits >> (it & (NTM - 1))) & 1u;
 #endif
     wk = skb;
     cur ^= 1;
@@ -1709,13 +1765,14 @@ __global__ __launch_bounds__(256, ATTN_KV32_WPS) void attn_bwd_kv32_kernel(AttnP
 }
 
 // ------------------------------------------------------------------------ backward: dQ (one workgroup per q tile and R heads of a kv group)
-template <typename T, int HD, int R, bool DMA = false>
+template <typename T, int HD, int R, bool DMA = false, int LG = 5>
 #ifndef ATTN_DQ_WPS
 #define ATTN_DQ_WPS 3   // waves per SIMD the two-head LDS-DMA form is compiled for (4: 128 registers, 13 spilled dwords; A/B in profiles/r4_ab_attn_dq_four_waves.log)
 #endif
 __global__ __launch_bounds__(256, (is_bf16<T>::value && HD <= 64) ? (R == 1 ? 3 : (DMA ? ATTN_DQ_WPS : 2)) : 1) void attn_bwd_q_kernel(AttnParams p) {
   using C = ACfg<T, HD>;
   using M = AMma<T>;
+  using W = typename AMap<LG>::W;
   static_assert(!DMA || (is_bf16<T>::value && HD == 64), "LDS-DMA staging: bf16, head_dim 64");
   constexpr int TILE = DMA ? 64 * 64 : C::TILE;   // elements of a staged tile (DMA: unpadded, swizzled; attn_fwd_kernel)
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
@@ -1767,8 +1824,8 @@ __global__ __launch_bounds__(256, (is_bf16<T>::value && HD <= 64) ? (R == 1 ? 3 
   }
   if constexpr (!DMA) for (int i = 0; i < 2; ++i) { zero_pad_cols<T, HD>(Ks + i * C::TILE, t); zero_pad_cols<T, HD>(Vs + i * C::TILE, t); }
   // (scalars through readfirstlane: loaded by vector memory -- the maps are not const -- and otherwise still pending when the item loop begins)
-  const unsigned int bits = (unsigned int)__builtin_amdgcn_readfirstlane((int)p.qmap[b * nt + qt]), fullbits = (unsigned int)__builtin_amdgcn_readfirstlane((int)p.qmap_full[b * nt + qt]);
-  const unsigned int wbits = __builtin_amdgcn_readfirstlane(p.qmap16[(b * nt + qt) * 4 + w]);
+  const W bits = map_uniform(map_ptr<LG>(p.qmap)[b * nt + qt]), fullbits = map_uniform(map_ptr<LG>(p.qmap_full)[b * nt + qt]);
+  const W wbits = map_uniform(map_ptr<LG>(p.qmap16)[(b * nt + qt) * 4 + w]);
   // K / V of this kv head, rows of this sequence ([T][HD] windows of the row-major qkv), and the rows' uid / tm (tile_load_buf)
   const at_i32x4 k_rs = at_rsrc((const T*)p.k + tok0 * p.ld + kvh * HD, ((long long)(p.T - 1) * p.ld + HD) * sizeof(T));
   const at_i32x4 v_rs = at_rsrc((const T*)p.v + tok0 * p.ld + kvh * HD, ((long long)(p.T - 1) * p.ld + HD) * sizeof(T));
@@ -1868,16 +1925,16 @@ __global__ __launch_bounds__(256, (is_bf16<T>::value && HD <= 64) ? (R == 1 ? 3 
     copy_out_tile<T, HD>(Ks + r * C::TILE, (T*)p.dq + (tok0 + qt * 64) * p.ldg + (h0 + r) * HD, p.ldg, qt * 64, p.T, t, p.f8_amax);
 }
 
-template <typename T, int HD>
+template <typename T, int HD, int LG>
 static int attn_bwd_hd(const AttnParams& p, hipStream_t s) {
   using C = ACfg<T, HD>;
   const size_t sm_kv = sizeof(T) * 4 * C::TILE + 512 * 4;
   const size_t sm_q = sizeof(T) * 4 * C::TILE + 384 * 4;
   static bool set = false;
   if (!set) {
-    HIP_CHECK(hipFuncSetAttribute((const void*)attn_bwd_kv_kernel<T, HD>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm_kv));
-    HIP_CHECK(hipFuncSetAttribute((const void*)attn_bwd_q_kernel<T, HD, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm_q));
-    HIP_CHECK(hipFuncSetAttribute((const void*)attn_bwd_q_kernel<T, HD, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm_q));
+    HIP_CHECK(hipFuncSetAttribute((const void*)attn_bwd_kv_kernel<T, HD, LG>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm_kv));
+    HIP_CHECK(hipFuncSetAttribute((const void*)attn_bwd_q_kernel<T, HD, 1, false, LG>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm_q));
+    HIP_CHECK(hipFuncSetAttribute((const void*)attn_bwd_q_kernel<T, HD, 2, false, LG>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm_q));
     set = true;
   }
   // the dQ kernel also produces delta = rowsum(dO * O), which the dK/dV kernel reads
@@ -1885,14 +1942,14 @@ static int attn_bwd_hd(const AttnParams& p, hipStream_t s) {
   if constexpr (is_bf16<T>::value && HD == 64) {
     if (attn_dma_on()) {
       const size_t sm_dma = 4 * 64 * 64 * 2 + 384 * 4;
-      if (attn_heads_per_wg(p) == 2) hipLaunchKernelGGL((attn_bwd_q_kernel<T, HD, 2, true>), dim3(((p.T + 63) / 64) * (p.H / 2) * p.B), dim3(256), sm_dma, s, p);
-      else hipLaunchKernelGGL((attn_bwd_q_kernel<T, HD, 1, true>), dim3(((p.T + 63) / 64) * p.H * p.B), dim3(256), sm_dma, s, p);
+      if (attn_heads_per_wg(p) == 2) hipLaunchKernelGGL((attn_bwd_q_kernel<T, HD, 2, true, LG>), dim3(((p.T + 63) / 64) * (p.H / 2) * p.B), dim3(256), sm_dma, s, p);
+      else hipLaunchKernelGGL((attn_bwd_q_kernel<T, HD, 1, true, LG>), dim3(((p.T + 63) / 64) * p.H * p.B), dim3(256), sm_dma, s, p);
       q_done = true;
     }
   }
   if (!q_done) {
-    if (attn_heads_per_wg(p) == 2) hipLaunchKernelGGL((attn_bwd_q_kernel<T, HD, 2>), dim3(((p.T + 63) / 64) * (p.H / 2) * p.B), dim3(256), sm_q, s, p);
-    else hipLaunchKernelGGL((attn_bwd_q_kernel<T, HD, 1>), dim3(((p.T + 63) / 64) * p.H * p.B), dim3(256), sm_q, s, p);
+    if (attn_heads_per_wg(p) == 2) hipLaunchKernelGGL((attn_bwd_q_kernel<T, HD, 2, false, LG>), dim3(((p.T + 63) / 64) * (p.H / 2) * p.B), dim3(256), sm_q, s, p);
+    else hipLaunchKernelGGL((attn_bwd_q_kernel<T, HD, 1, false, LG>), dim3(((p.T + 63) / 64) * p.H * p.B), dim3(256), sm_q, s, p);
   }
   HIP_CHECK(hipGetLastError());
   // (two adjacent kv tiles per workgroup -- Q / dO staging and every fragment read shared by 32 keys per wave -- measured 6 % slower:
@@ -1901,17 +1958,17 @@ static int attn_bwd_hd(const AttnParams& p, hipStream_t s) {
     const bool dma = sw().attn_kv_dma != 0;   // A/B switch of this kernel alone
     if (attn_kv_pairs(p)) {   // 32 keys per wave on 32 x 32 x 16 products, two kv tiles per workgroup (order_k lists the pairs)
       const int npair = ((p.T + 63) / 64 + 1) / 2;
-      hipLaunchKernelGGL(attn_bwd_kv32_kernel, dim3(npair * p.KV * p.B), dim3(256), 4 * 64 * 64 * 2 + 256 * 4, s, p);
+      hipLaunchKernelGGL(attn_bwd_kv32_kernel<LG>, dim3(npair * p.KV * p.B), dim3(256), 4 * 64 * 64 * 2 + 256 * 4, s, p);
       HIP_CHECK(hipGetLastError());
       return RSYS_OK;
     }
     if (dma && attn_dma_on()) {
-      hipLaunchKernelGGL(attn_bwd_kv_dma_kernel, dim3(((p.T + 63) / 64) * p.KV * p.B), dim3(256), 4 * 64 * 64 * 2 + 512 * 4, s, p);
+      hipLaunchKernelGGL(attn_bwd_kv_dma_kernel<LG>, dim3(((p.T + 63) / 64) * p.KV * p.B), dim3(256), 4 * 64 * 64 * 2 + 512 * 4, s, p);
       HIP_CHECK(hipGetLastError());
       return RSYS_OK;
     }
   }
-  hipLaunchKernelGGL((attn_bwd_kv_kernel<T, HD>), dim3(((p.T + 63) / 64) * p.KV * p.B), dim3(256), sm_kv, s, p);
+  hipLaunchKernelGGL((attn_bwd_kv_kernel<T, HD, LG>), dim3(((p.T + 63) / 64) * p.KV * p.B), dim3(256), sm_kv, s, p);
   HIP_CHECK(hipGetLastError());
   return RSYS_OK;
 }
@@ -1921,11 +1978,12 @@ int launch_attn_bwd(const AttnParams& p, hipStream_t s) {
   int rc = check_attn(p, sizeof(T));
   if (rc) return rc;
   ARG_CHECK(p.H / p.KV <= 8, "attention: at most 8 query heads per kv head");
+  const bool wide = (p.T + 63) / 64 > 32;
   switch (p.hd) {
-    case 16: return attn_bwd_hd<T, 16>(p, s);
-    case 32: return attn_bwd_hd<T, 32>(p, s);
-    case 64: return attn_bwd_hd<T, 64>(p, s);
-    case 128: return attn_bwd_hd<T, 128>(p, s);
+    case 16: return wide ? attn_bwd_hd<T, 16, 6>(p, s) : attn_bwd_hd<T, 16, 5>(p, s);
+    case 32: return wide ? attn_bwd_hd<T, 32, 6>(p, s) : attn_bwd_hd<T, 32, 5>(p, s);
+    case 64: return wide ? attn_bwd_hd<T, 64, 6>(p, s) : attn_bwd_hd<T, 64, 5>(p, s);
+    case 128: return wide ? attn_bwd_hd<T, 128, 6>(p, s) : attn_bwd_hd<T, 128, 5>(p, s);
   }
   set_error("attention: head_dim must be 16, 32, 64 or 128");
   return RSYS_ERR_ARG;
@@ -2099,7 +2157,7 @@ static int attn_cand_hd(const CandAttnParams& p, hipStream_t s) {
 template <typename T>
 int launch_attn_cand(const CandAttnParams& p, hipStream_t s) {
   ARG_CHECK(p.rows >= 1 && p.n_slots >= 1, "candidate attention: rows and slots");
-  ARG_CHECK(p.T % 8 == 0 && (p.T + 63) / 64 <= 32, "candidate attention: T must be a multiple of 8 and <= 2048");
+  ARG_CHECK(p.T % 8 == 0 && p.T <= 4096, "candidate attention: T must be a multiple of 8 and <= 4096");
   ARG_CHECK(p.H % p.KV == 0, "candidate attention: H % KV");
   ARG_CHECK((p.ld * sizeof(T)) % 16 == 0 && (p.ldo * sizeof(T)) % 16 == 0 && (p.hd * sizeof(T)) % 16 == 0, "candidate attention: 16-byte row alignment");
   ARG_CHECK((long long)p.T * p.ld * sizeof(T) < (1ll << 31), "candidate attention: a row of qkv must stay below 2 GiB");

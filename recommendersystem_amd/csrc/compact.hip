@@ -62,7 +62,7 @@ __global__ __launch_bounds__(1024) void token_union_kernel(UnionLists ul, int NT
 // Token order of the last layer under the compact top: inside every batch row the selected tokens come first (in their original
 // order), then the others.  Attention does not care about the order of the tokens it is given (positions enter through RoPE,
 // applied per token from pos_p; the mask compares per-token keys), so the last layer runs on this order and its attention
-// kernels only visit the leading query tiles (q_active).  One workgroup per batch row; T <= 2048 tokens.
+// kernels only visit the leading query tiles (q_active, up to 64).  One workgroup per batch row; T <= 4096 tokens.
 //   perm[b T + p]  = original (global) token at permuted place p        uid_p / tm_p / pos_p: that token's ids and position
 //   slot_p[b T + p] = compact row of that token or -1                    sel_p[r] = permuted place (global) of compact row r
 __global__ __launch_bounds__(1024) void selected_first_kernel(const unsigned int* __restrict__ bits, const int* __restrict__ pre, int* __restrict__ slot,
@@ -73,9 +73,9 @@ __global__ __launch_bounds__(1024) void selected_first_kernel(const unsigned int
   __shared__ int wave_tot[16];
   const int b = blockIdx.x, t = threadIdx.x, l = t & 63, wv = t >> 6;
   const long long base = (long long)b * T;
-  const int per = (T + 1023) / 1024;               // 1 or 2 consecutive tokens per thread
+  const int per = (T + 1023) / 1024;               // 1 .. 4 consecutive tokens per thread
   const int j0 = t * per, j1 = min(T, j0 + per);
-  int sl[2] = {-1, -1}, cnt = 0;
+  int sl[4] = {-1, -1, -1, -1}, cnt = 0;
   for (int j = j0; j < j1; ++j) {   // compact row of token base + j: selected tokens before it in its bitmap word + before that word
     const long long tok = base + j;
     const unsigned int b = bits[tok >> 5];
@@ -213,7 +213,7 @@ int launch_token_union(const int* const* idx, const int* const* npos, int ntask,
 
 int launch_selected_first(const unsigned int* bits, const int* pre, int* slot, int* sel, const int* uid, const int* tm, const int* rope_pos, int B, int T,
                           int* perm, int* uid_p, int* tm_p, int* pos_p, int* slot_p, int* sel_p, int* q_active, hipStream_t s) {
-  ARG_CHECK(T >= 1 && T <= 2048, "selected-first order: at most 2048 tokens per row");
+  ARG_CHECK(T >= 1 && T <= 4096, "selected-first order: at most 4096 tokens per row");
   const int identity = sw().top_order == 0 ? 1 : 0;   // RSYS_TOP_ORDER=0: keep the token order
   hipLaunchKernelGGL(selected_first_kernel, dim3(B), dim3(1024), 0, s, bits, pre, slot, sel, uid, tm, rope_pos, T, perm, uid_p, tm_p, pos_p, slot_p, sel_p, q_active, identity);
   HIP_CHECK(hipGetLastError());

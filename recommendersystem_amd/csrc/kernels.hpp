@@ -203,7 +203,8 @@ struct AttnParams {
   float* lse;                  // [B][H][T] natural-log sum-exp of the scaled scores
   const int *uid, *tm;         // [B*T]
   // [B][ceil(T/64)] bitmaps: qmap bit j = kv tile j has an allowed pair with this q tile, qmap_full = every pair allowed;
-  // kmap / kmap_full: the transposed relation (bit j = q tile j)
+  // kmap / kmap_full: the transposed relation (bit j = q tile j).  One 32-bit word per entry for rows of up to 32 tiles; rows of 33 .. 64
+  // tiles (T <= 4096) keep one 64-bit word per entry in the same arrays: attn_map_words(T) words of 32 bits per entry, 8-byte aligned
   unsigned int *qmap, *kmap, *qmap_full, *kmap_full;
   // [B][ceil(T/64)][4]: the same "some allowed pair" bits per group of 16 queries (qmap16: bit j = kv tile j) and per
   // group of 16 keys (kmap16: bit j = q tile j): a wave owns one such group and skips the tiles it has nothing in
@@ -234,6 +235,7 @@ struct AttnParams {
   // kbits [B][nt kv][nt q][64 keys]: bit q = the key is seen by query q of the q tile (the transposed matrix).  Required.
   unsigned long long *qbits, *kbits;
 };
+inline int attn_map_words(int T) { return (T + 63) / 64 > 32 ? 2 : 1; }   // 32-bit words per tile-map entry
 int launch_attn_tilemap(const AttnParams& p, hipStream_t s);
 // Candidate attention against a cached history (rank_cache.hip; Finetune/embed.py:74-131's ranking row without its history half).  Row r of
 // qkv [rows * T][ld] holds n_cand[r] candidates, candidate j at tokens 2 j (item) and 2 j + 1 (action).  A query token of candidate j

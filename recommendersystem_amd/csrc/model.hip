@@ -109,8 +109,8 @@ int model_create(const rsys_config* cfg, int device, Model** out) {
   const int hd = cfg->embed_dim / cfg->num_heads;
   ARG_CHECK(hd == 16 || hd == 32 || hd == 64 || hd == 128, "head_dim must be 16/32/64/128");
   ARG_CHECK(cfg->embed_dim % 16 == 0 && cfg->embed_dim <= 2048, "embed_dim must be a multiple of 16 and <= 2048");
-  ARG_CHECK(cfg->max_sequence_length % 4 == 0 && 2 * cfg->max_sequence_length <= 2048,
-            "max_sequence_length must be a multiple of 4 and <= 1024");
+  ARG_CHECK(cfg->max_sequence_length % 4 == 0 && 2 * cfg->max_sequence_length <= 4096,
+            "max_sequence_length must be a multiple of 4 and <= 2048");
   ARG_CHECK(cfg->max_rows >= 1, "max_rows");
   ARG_CHECK(cfg->mask_topk >= 1 && cfg->mask_topk <= cfg->max_sequence_length, "mask_topk");
   ARG_CHECK(cfg->dtype == RSYS_DTYPE_FP32 || cfg->dtype == RSYS_DTYPE_BF16 || cfg->dtype == RSYS_DTYPE_FP8, "dtype");
@@ -214,7 +214,7 @@ int model_create(const rsys_config* cfg, int device, Model** out) {
   DALLOC(m->feat, N * 32 * e); DALLOC(m->x0, NT * D * 4);
   DALLOC(m->uid_t, NT * 4); DALLOC(m->tm_t, NT * 4);
   {   // attention tile maps: the four the tile-map kernel ORs into sit back to back (one zero-fill per step), then the two it stores
-    const int64_t mb = ((int64_t)m->rows_max * ((m->T + 63) / 64) * 4 + 255) / 256 * 256;
+    const int64_t mb = ((int64_t)m->rows_max * ((m->T + 63) / 64) * 4 * attn_map_words(m->T) + 255) / 256 * 256;   // (64-bit map words above 32 tiles per row)
     unsigned char* base = nullptr;
     DALLOC(base, mb * 7 + mb * 5);
     m->kmap = (unsigned int*)base; m->kmap_full = (unsigned int*)(base + mb); m->qmap_full = (unsigned int*)(base + 2 * mb); m->kmap16 = (unsigned int*)(base + 3 * mb);
@@ -316,7 +316,7 @@ int model_create(const rsys_config* cfg, int device, Model** out) {
       if (m->bf16_mode) { DALLOC(m->c_gx_t, cap * D * 2); DALLOC(m->c_dh_t, cap * D * 2); } else { m->c_gx_t = m->c_gx; m->c_dh_t = m->c_dh; }
       DALLOC(m->c_perm, NT * 4); DALLOC(m->uid_p, NT * 4); DALLOC(m->tm_p, NT * 4); DALLOC(m->pos_p, NT * 4); DALLOC(m->c_slot_p, NT * 4);
       DALLOC(m->c_sel_p, cap * 4); DALLOC(m->c_qact, (int64_t)m->rows_max * 4 + 64);
-      const int64_t mb = ((int64_t)m->rows_max * ((m->T + 63) / 64) * 4 + 255) / 256 * 256;
+      const int64_t mb = ((int64_t)m->rows_max * ((m->T + 63) / 64) * 4 * attn_map_words(m->T) + 255) / 256 * 256;   // (64-bit map words above 32 tiles per row)
       unsigned char* base = nullptr;
       DALLOC(base, mb * 12);
       m->kmap_p = (unsigned int*)base; m->kmap_full_p = (unsigned int*)(base + mb); m->qmap_full_p = (unsigned int*)(base + 2 * mb); m->kmap16_p = (unsigned int*)(base + 3 * mb);

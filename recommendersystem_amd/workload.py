@@ -60,6 +60,9 @@ def make_config(name="tiny", **over):
         "cfg4":  (8, 16, 8, 1024, 2816, 512, 120000, 80000, 6148, 64),
         # the reference's production shape (transformer.py:535-560; vocabulary as in cfg-3, the real one comes from {manga,anime}.csv)
         "prod":  (8, 32, 16, 2048, 5632, 1024, 120000, 80000, 6148, 128),
+        # max_sequence_length 2048 (rows of 4096 tokens = 64 attention tiles): cfg-3 and the production shape, mask_topk > mask_rate * S
+        "cfg3s2k": (8, 8, 4, 512, 1408, 2048, 120000, 80000, 6148, 256),
+        "prod2k":  (8, 32, 16, 2048, 5632, 2048, 120000, 80000, 6148, 256),
     }[name]
     L, H, KV, D, I, S, V0, V1, M, K = shapes
     cfg = dict(base)
