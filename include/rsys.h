@@ -110,6 +110,31 @@ int32_t rsys_batch_upload(rsys_model* m, const rsys_batch* b);
 int32_t rsys_batch_rows(rsys_model* m, int32_t* rows_out);
 int32_t rsys_batch_prefetch(rsys_model* m, const rsys_batch* b);
 int32_t rsys_batch_swap(rsys_model* m);
+/* Inference on trimmed rows (beyond the reference, whose server always runs rows of max_sequence_length).  A serving row
+ * holds one user: its live events are a prefix, everything behind them is padding with userid 0 (Finetune/embed.py:86-123).  The mask's
+ * first predicate is userid[q] == userid[kv] (transformer.model.py:479-480), so no live token attends padding, and every other operator
+ * of the trunk is token-local: dropping the padding columns is exact.
+ * rsys_batch_upload_trimmed is rsys_batch_upload for such rows: the arrays keep the caller's row stride S = max_sequence_length, only
+ *   columns [0, row_len) of each row are read, checked, packed and copied; the resident batch then has rows of row_len interactions
+ *   (2 row_len tokens) and every forward over it launches its kernels for rows * 2 row_len tokens.  row_len % 4 == 0 and
+ *   4 <= row_len <= S; row_len == S is rsys_batch_upload, with everything that call requires.  Every column >= row_len of every row must have userid == 0: checked on the host
+ *   before anything is written, as the index paths are (RSYS_ERR_ARG: the resident batch and its row length stay as they were).  rope_input_pos
+ *   (may be NULL: the column) is a position, bounded by the RoPE tables as in rsys_batch_upload, not by row_len: the candidate rows of the
+ *   ranking cache sit at position n_hist, whatever their length.  The label, weight, position and mask arrays are not read and may be NULL.  fp32 and bf16 models with a replicated table; an fp8 model
+ *   (its tensor-wise amax sees every token) and a row-sharded table return RSYS_ERR_ARG.
+ * On a trimmed batch: rsys_infer returns [rows][2 row_len][D] (n is checked against that); rsys_infer_select[_adapters] keep the caller's
+ *   token geometry r * 2S + t, a t >= 2 row_len is RSYS_ERR_ARG; rsys_rank_cache_store takes n_hist <= row_len and
+ *   rsys_rank_cache_candidates n_cand <= row_len -- the slot layout does not change, so a slot stored from a trimmed row serves candidate
+ *   rows of any length and the reverse; rsys_forward_backward, rsys_adapter_forward_backward and every pass that reads targets return
+ *   RSYS_ERR_STATE ("a trimmed batch is inference-only") and touch nothing.  The next rsys_batch_upload / _swap restores the full rows.
+ * rsys_batch_row_length: interactions per row of the resident batch: S after an ordinary upload, 0 without a batch.
+ * rsys_serving_trim_set (default 0; read by rsys_render_request and rsys_render_request_full only): every forward of those pipelines
+ *   runs at row_len = min(S, 32 ceil(longest live row of that forward / 32)) -- whole 64-token attention tiles.  Waves, chunks, slots
+ *   and outputs are unchanged; with the switch off every launch is what it was. */
+int32_t rsys_batch_upload_trimmed(rsys_model* m, const rsys_batch* b, int32_t row_len);
+int32_t rsys_batch_row_length(rsys_model* m, int32_t* row_len_out);
+int32_t rsys_serving_trim_set(rsys_model* m, int32_t on);
+int32_t rsys_serving_trim_get(rsys_model* m, int32_t* on_out);
 /* device-side synthetic batch (bench): fills the resident batch from a counter RNG */
 
 /* model(d, evaluate) + loss.backward() -- model.py:493-529, train.py:259-272.

@@ -153,6 +153,10 @@ int32_t rsys_op_rerank(int32_t n, int32_t partialk, const float* pen, const floa
  * their wave); "groups" int32 [n_active][6] = (group, medium, first slot in "r" / "picks", candidates, sidx, eidx) per group with a page;
  * "rm_users" int32 [n][3] = (user, first value in "r_masked", values); "r_masked" f32; "r" f32 (ranking scores) and "picks" int32 (picked
  * positions; the slots after a group's eidx rounds hold -1).
+ * "forward_rows" int32 [n_forwards][3] = (stage, rows, row_len) of every trunk forward of the last request in run order (kept always): stage
+ * 0 = retrieval wave, 1 = store wave, 2 = candidate rows against the cache, 3 = assembled rows; row_len < S only under
+ * rsys_serving_trim_set.  The kept batches are what the switch-off call keeps, shapes [n][S] and values: trimmed rows are widened with what
+ * the full rows hold behind them (zeros; rope_input_pos: the row's fill position), token indices are reported as r * 2S + t.
  * After rsys_render_request_full: "forwards" [1] counts every ranking-stage forward; "forwards.full" int32 [3] = (store forwards, candidate
  * forwards, empty-history chunk forwards; kept always); "store.<array>" the store rows [n_store_rows][S] in run order with "store.rows"
  * int32 [n][4] = (user, slot, events, wave); "cand.<array>" the candidate rows of the cached path with "cand.token_index"; "rows" int32

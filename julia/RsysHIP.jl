@@ -136,6 +136,22 @@ function batch_rows(m::Model)
     check(ccall((:rsys_batch_rows, LIB), Int32, (Ptr{Cvoid}, Ref{Int32}), m.h, n))
     Int(n[])
 end
+# Inference on trimmed rows (rsys.h: rsys_batch_upload_trimmed ...): `b` keeps the row stride max_sequence_length, columns [1, row_len] of
+# every row become the resident batch; the rest of each row must be padding (userid 0)
+function batch_upload_trimmed(m::Model, b::RsysBatch, row_len::Integer)
+    check(ccall((:rsys_batch_upload_trimmed, LIB), Int32, (Ptr{Cvoid}, Ref{RsysBatch}, Int32), m.h, b, row_len))
+end
+function batch_row_length(m::Model)
+    n = Ref{Int32}(0)
+    check(ccall((:rsys_batch_row_length, LIB), Int32, (Ptr{Cvoid}, Ref{Int32}), m.h, n))
+    Int(n[])
+end
+serving_trim!(m::Model, on::Bool) = check(ccall((:rsys_serving_trim_set, LIB), Int32, (Ptr{Cvoid}, Int32), m.h, on ? 1 : 0))
+function serving_trim(m::Model)
+    on = Ref{Int32}(0)
+    check(ccall((:rsys_serving_trim_get, LIB), Int32, (Ptr{Cvoid}, Ref{Int32}), m.h, on))
+    on[] != 0
+end
 adapter_train_enable(m::Model, dropout::Real) = check(ccall((:rsys_adapter_train_enable, LIB), Int32, (Ptr{Cvoid}, Float32), m.h, dropout))
 function adapter_forward_backward(m::Model, evaluate::Bool, row_slot::Vector{Int32}, row_task::Vector{Int32}, grad_scale::Real, seed::Integer, step::Integer)
     GC.@preserve row_slot row_task check(ccall((:rsys_adapter_forward_backward, LIB), Int32,

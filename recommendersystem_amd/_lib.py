@@ -143,6 +143,10 @@ _SIGS = [
     ("rsys_adapter_slots", C.c_int32, [_P, C.POINTER(C.c_int32)]),
     ("rsys_infer_select_adapters", C.c_int32, [_P, C.c_int32, _P, _P, C.c_int64, _P, C.c_int64]),
     ("rsys_batch_rows", C.c_int32, [_P, C.POINTER(C.c_int32)]),
+    ("rsys_batch_upload_trimmed", C.c_int32, [_P, C.POINTER(rsys_batch), C.c_int32]),
+    ("rsys_batch_row_length", C.c_int32, [_P, C.POINTER(C.c_int32)]),
+    ("rsys_serving_trim_set", C.c_int32, [_P, C.c_int32]),
+    ("rsys_serving_trim_get", C.c_int32, [_P, C.POINTER(C.c_int32)]),
     ("rsys_adapter_train_enable", C.c_int32, [_P, C.c_float]),
     ("rsys_adapter_forward_backward", C.c_int32, [_P, C.c_int32, _P, _P, C.c_float, C.c_uint64, C.c_uint64]),
     ("rsys_adapter_grad_get", C.c_int32, [_P, C.c_int32, C.c_char_p, _P, C.c_int64]),

@@ -34,7 +34,7 @@ struct AdapterBank {
 
 static inline int64_t bank_a_floats(const Model* m) { return (int64_t)16 * m->D; }
 static inline int64_t bank_b_floats(const Model* m) { return (int64_t)(m->H + m->KV) * m->hd * 8; }
-template <typename T> static inline T* bank_la(const Model* m, int l) { return (T*)m->bank->La_l + (int64_t)l * m->rows_max * m->T * 16; }   // layer l's La of a training pass
+template <typename T> static inline T* bank_la(const Model* m, int l) { return (T*)m->bank->La_l + (int64_t)l * m->rows_max * m->Ta * 16; }   // layer l's La of a training pass
 
 // ------------------------------------------------------------------ kernels
 template <typename T> __device__ __forceinline__ void load8(const T* p, float (&v)[8]);
@@ -584,7 +584,7 @@ int adapter_bind_rows(Model* m, const int32_t* row_adapter) {
   if (!any) return RSYS_OK;   // every row runs the base model: the forward launches what rsys_infer_select launches
   AdapterBank* b = m->bank;
   HIP_CHECK(hipSetDevice(m->device));
-  if (!b->La) DALLOC(b->La, (int64_t)m->rows_max * m->T * 16 * m->esz);
+  if (!b->La) DALLOC(b->La, (int64_t)m->rows_max * m->Ta * 16 * m->esz);
   HIP_CHECK(hipMemcpyAsync(b->d_rows, row_adapter, (size_t)m->cur_rows * 4, hipMemcpyHostToDevice, m->stream));
   m->bank_rows = b->d_rows;
   return RSYS_OK;
@@ -633,13 +633,13 @@ static int bank_train_check_model(const Model* m) {
 int adapter_train_enable(Model* m, float dropout) {
   RC(bank_train_check_model(m));
   ARG_CHECK(dropout >= 0.f && dropout < 1.f, "adapter bank training: dropout must be in [0, 1)");
-  ARG_CHECK(m->T % 8 == 0 && m->D % 16 == 0 && m->hd % 8 == 0, "adapter bank training: 2 S % 8, embed_dim % 16 and head_dim % 8 must be 0");
+  ARG_CHECK(m->Ta % 8 == 0 && m->D % 16 == 0 && m->hd % 8 == 0, "adapter bank training: 2 S % 8, embed_dim % 16 and head_dim % 8 must be 0");
   RC(bank_ensure(m));
   AdapterBank* b = m->bank;
   HIP_CHECK(hipSetDevice(m->device));
   if (!b->train) {
     const int64_t na = (int64_t)RSYS_ADAPTER_SLOTS * m->L * bank_a_floats(m), nb = (int64_t)RSYS_ADAPTER_SLOTS * m->L * bank_b_floats(m);
-    const int64_t tok = (int64_t)m->rows_max * m->T;
+    const int64_t tok = (int64_t)m->rows_max * m->Ta;
     // (every buffer once: a call that failed part-way is taken up where it stopped)
 #define BANK_ONCE(ptr, bytes) do { if ((ptr) == nullptr) DALLOC(ptr, bytes); } while (0)
     BANK_ONCE(b->gA, na * 4); BANK_ONCE(b->gB, nb * 4);
@@ -661,6 +661,7 @@ int adapter_forward_backward(Model* m, int evaluate, const int32_t* row_slot, co
   RC(bank_train_check_model(m));
   ARG_CHECK(m->bank != nullptr && m->bank->train, "adapter bank training is not enabled (rsys_adapter_train_enable)");
   ARG_CHECK(m->cur_rows > 0, "no batch uploaded");
+  RC(check_not_trimmed(m));
   ARG_CHECK(row_slot != nullptr && row_task != nullptr, "row_slot / row_task is null");
   int owner[4] = {-1, -1, -1, -1};
   bool any = false;

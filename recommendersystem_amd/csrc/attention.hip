@@ -2013,7 +2013,7 @@ __global__ __launch_bounds__(256, (is_bf16<T>::value && HD <= 64) ? (R == 1 ? 3 
   const int b = grp / p.KV, kvh = grp % p.KV, h0 = kvh * (p.H / p.KV) + (inner / nt) * R, qt = inner % nt;
   const int nq = 2 * min(max(p.n_cand[b], 0), p.T / 2);     // candidate tokens of the row
   if (qt * 64 >= nq) return;                                 // (uniform: whole workgroup)
-  const int nh2 = 2 * min(max(p.n_hist[b], 0), p.T / 2);     // cached tokens of the row's slot
+  const int nh2 = 2 * min(max(p.n_hist[b], 0), p.Tc / 2);    // cached tokens of the row's slot
   const int slot = min(max(p.slot[b], 0), p.n_slots - 1);
   const int nht = (nh2 + 63) / 64;
   const int t = threadIdx.x, l = t & 63, w = t >> 6, g = l >> 4, fr = l & 15;
@@ -2038,7 +2038,7 @@ __global__ __launch_bounds__(256, (is_bf16<T>::value && HD <= 64) ? (R == 1 ? 3 
   }
   zero_pad_cols<T, HD>(Ks, t); zero_pad_cols<T, HD>(Ks + C::TILE, t);
   // the slot's cached rows [0, nh2) of this kv head (nh2 = 0: never loaded from), and the row's own fresh K / V
-  const T* cbase = (const T*)p.cache + (long long)slot * p.T * ldc + kvh * HD;
+  const T* cbase = (const T*)p.cache + (long long)slot * p.Tc * ldc + kvh * HD;
   const long long cbytes = nh2 > 0 ? ((long long)(nh2 - 1) * ldc + HD) * sizeof(T) : 0;
   const at_i32x4 ck_rs = at_rsrc(cbase, cbytes), cv_rs = at_rsrc(cbase + p.KV * HD, cbytes);
   const long long sbytes = ((long long)(p.T - 1) * p.ld + HD) * sizeof(T);
@@ -2155,8 +2155,11 @@ static int attn_cand_hd(const CandAttnParams& p, hipStream_t s) {
   return RSYS_OK;
 }
 template <typename T>
-int launch_attn_cand(const CandAttnParams& p, hipStream_t s) {
+int launch_attn_cand(const CandAttnParams& p_in, hipStream_t s) {
+  CandAttnParams p = p_in;
+  if (p.Tc == 0) p.Tc = p.T;
   ARG_CHECK(p.rows >= 1 && p.n_slots >= 1, "candidate attention: rows and slots");
+  ARG_CHECK(p.Tc >= p.T && p.Tc % 8 == 0 && p.Tc <= 4096, "candidate attention: the slot stride must be a multiple of 8, >= T and <= 4096");
   ARG_CHECK(p.T % 8 == 0 && p.T <= 4096, "candidate attention: T must be a multiple of 8 and <= 4096");
   ARG_CHECK(p.H % p.KV == 0, "candidate attention: H % KV");
   ARG_CHECK((p.ld * sizeof(T)) % 16 == 0 && (p.ldo * sizeof(T)) % 16 == 0 && (p.hd * sizeof(T)) % 16 == 0, "candidate attention: 16-byte row alignment");
@@ -2175,7 +2178,7 @@ template int launch_attn_cand<float>(const CandAttnParams&, hipStream_t);
 
 // K | V of the leading 2 n_hist[r] tokens of every row -> the row's cache slot, in 16-byte chunks (rsys_rank_cache_store, once per layer)
 template <typename T>
-__global__ __launch_bounds__(256) void rank_cache_copy_kernel(const T* __restrict__ qkv, long long ld, int kv_off, int kvw, int T_len, const int* __restrict__ slot,
+__global__ __launch_bounds__(256) void rank_cache_copy_kernel(const T* __restrict__ qkv, long long ld, int kv_off, int kvw, int T_len, int T_slot, const int* __restrict__ slot,
                                                               const int* __restrict__ n_hist, int n_slots, T* __restrict__ cache) {
   const int r = blockIdx.y, sl = slot[r];
   if (sl < 0 || sl >= n_slots) return;
@@ -2185,21 +2188,22 @@ __global__ __launch_bounds__(256) void rank_cache_copy_kernel(const T* __restric
   for (long long c = (long long)blockIdx.x * 256 + threadIdx.x; c < n; c += (long long)gridDim.x * 256) {
     const long long tok = c / cpr; const int ch = (int)(c % cpr);
     const uint4 v = *(const uint4*)((const unsigned char*)(qkv + ((long long)r * T_len + tok) * ld + kv_off) + 16 * ch);
-    *(uint4*)((unsigned char*)(cache + ((long long)sl * T_len + tok) * kvw) + 16 * ch) = v;
+    *(uint4*)((unsigned char*)(cache + ((long long)sl * T_slot + tok) * kvw) + 16 * ch) = v;
   }
 }
 template <typename T>
-int launch_rank_cache_copy(const T* qkv, long long ld, int kv_off, int kvw, int T_len, int rows, const int* slot, const int* n_hist, int n_slots, T* cache,
+int launch_rank_cache_copy(const T* qkv, long long ld, int kv_off, int kvw, int T_len, int T_slot, int rows, const int* slot, const int* n_hist, int n_slots, T* cache,
                            hipStream_t s) {
+  ARG_CHECK(T_slot >= T_len, "ranking cache: rows longer than a slot");
   ARG_CHECK((kvw * sizeof(T)) % 16 == 0 && (kv_off * sizeof(T)) % 16 == 0 && (ld * sizeof(T)) % 16 == 0, "ranking cache: 16-byte row alignment");
   const int cpr = kvw * (int)sizeof(T) / 16;
   const int gx = (int)std::min<long long>(((long long)T_len * cpr + 255) / 256, 64);
-  hipLaunchKernelGGL((rank_cache_copy_kernel<T>), dim3(gx, rows), dim3(256), 0, s, qkv, ld, kv_off, kvw, T_len, slot, n_hist, n_slots, cache);
+  hipLaunchKernelGGL((rank_cache_copy_kernel<T>), dim3(gx, rows), dim3(256), 0, s, qkv, ld, kv_off, kvw, T_len, T_slot, slot, n_hist, n_slots, cache);
   HIP_CHECK(hipGetLastError());
   return RSYS_OK;
 }
-template int launch_rank_cache_copy<bf16>(const bf16*, long long, int, int, int, int, const int*, const int*, int, bf16*, hipStream_t);
-template int launch_rank_cache_copy<float>(const float*, long long, int, int, int, int, const int*, const int*, int, float*, hipStream_t);
+template int launch_rank_cache_copy<bf16>(const bf16*, long long, int, int, int, int, int, const int*, const int*, int, bf16*, hipStream_t);
+template int launch_rank_cache_copy<float>(const float*, long long, int, int, int, int, int, const int*, const int*, int, float*, hipStream_t);
 
 }  // namespace rsys
 

@@ -81,6 +81,14 @@ int32_t rsys_zero_grad(rsys_model* h) {
 
 int32_t rsys_batch_upload(rsys_model* h, const rsys_batch* b) { CHECK_HANDLE(h); return model_batch_upload(h->m, b); }
 int32_t rsys_batch_rows(rsys_model* h, int32_t* rows_out) { CHECK_HANDLE(h); ARG_CHECK(rows_out, "null"); *rows_out = h->m->cur_rows; return RSYS_OK; }
+int32_t rsys_batch_upload_trimmed(rsys_model* h, const rsys_batch* b, int32_t row_len) { CHECK_HANDLE(h); return model_batch_upload_trimmed(h->m, b, row_len); }
+int32_t rsys_batch_row_length(rsys_model* h, int32_t* row_len_out) {
+  CHECK_HANDLE(h); ARG_CHECK(row_len_out, "null");
+  *row_len_out = h->m->cur_rows > 0 ? h->m->S : 0;
+  return RSYS_OK;
+}
+int32_t rsys_serving_trim_set(rsys_model* h, int32_t on) { CHECK_HANDLE(h); h->m->serving_trim = on != 0; return RSYS_OK; }
+int32_t rsys_serving_trim_get(rsys_model* h, int32_t* on_out) { CHECK_HANDLE(h); ARG_CHECK(on_out, "null"); *on_out = h->m->serving_trim ? 1 : 0; return RSYS_OK; }
 int32_t rsys_batch_prefetch(rsys_model* h, const rsys_batch* b) { CHECK_HANDLE(h); return model_batch_prefetch(h->m, b); }
 int32_t rsys_batch_swap(rsys_model* h) { CHECK_HANDLE(h); return model_batch_swap(h->m); }
 
@@ -356,6 +364,7 @@ int32_t rsys_trunk_output_get(rsys_model* h, float* out, int64_t n) {
 //   "embed.x0"     f32 [rows*2S*D]         interleaved input embeddings (even rows: gathered item rows)
 //   "table.fused"  f32 [(V+1)*D]           the fused item table the gather reads (row V = mask row)
 //   "host_syncs" int32 [2]: blocking host waits inside the last rsys_forward_backward {stream drains, event waits}
+//   "forward.tokens" int64 [1]: tokens the last trunk forward ran over = rows * 2 * row length of the resident batch (S here is that length)
 //   "top.n" int32 [1] | "top.sel" int32 [top.cap] | "top.slot" int32 [rows*2S] | "top.cap" int32 [1]: compact top of the last training
 //                  pass (model.hpp sparse_top): number of selected tokens, the sorted tokens, token -> compact row (-1: not selected)
 int32_t rsys_debug_get(rsys_model* h, const char* key, void* out, int64_t bytes) {
@@ -378,6 +387,7 @@ int32_t rsys_debug_get(rsys_model* h, const char* key, void* out, int64_t bytes)
   else if (k == "tokens.token_mask_ids") { src = m->tm_t; n = 2 * N * 4; }
   else if (k == "embed.x0") { src = m->x0; n = 2 * N * m->D * 4; }
   else if (k == "table.fused") { src = m->F32; n = (int64_t)m->TR * m->D * 4; }
+  else if (k == "forward.tokens") { ARG_CHECK(bytes == 8, "forward.tokens: one int64"); *(int64_t*)out = m->fwd_tokens; return RSYS_OK; }
   else if (k == "host_syncs") {   // blocking host waits inside the last rsys_forward_backward: {stream drains, waits on the early-counts event}
     ARG_CHECK(bytes == 8, "host_syncs: two int32"); ((int32_t*)out)[0] = m->host_stream_syncs; ((int32_t*)out)[1] = m->host_event_waits; return RSYS_OK; }
   else if (k.compare(0, 4, "act.") == 0 && k.size() > 6) {   // act.<layer>.<x|xn|qkv|O|h|hn|ab|g>: a saved activation of the last forward (T-typed ones as stored)

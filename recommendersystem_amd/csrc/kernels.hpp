@@ -246,13 +246,15 @@ struct CandAttnParams {
   int rows, T, H, KV, hd;
   const void* qkv; long long ld;        // q | k | v of the fresh rows, as AttnParams
   const void* cache; int n_slots;       // one layer's slots
+  int Tc;                               // tokens per cache slot (the slot stride); 0: T.  T < Tc: rows shorter than the slots (a trimmed batch)
   const int *slot, *n_hist, *n_cand;    // [rows], device
   void* o; long long ldo;               // [rows * T][H * hd]
 };
 template <typename T> int launch_attn_cand(const CandAttnParams& p, hipStream_t s);
 // K | V of tokens [0, 2 n_hist[r]) of row r of qkv -> cache slot slot[r] (one layer)
 // (kv_off: first K column of a qkv row; kvw = 2 KV hd)
-template <typename T> int launch_rank_cache_copy(const T* qkv, long long ld, int kv_off, int kvw, int T_len, int rows, const int* slot, const int* n_hist,
+// (T_len: tokens per row of qkv; T_slot: tokens per cache slot, >= T_len)
+template <typename T> int launch_rank_cache_copy(const T* qkv, long long ld, int kv_off, int kvw, int T_len, int T_slot, int rows, const int* slot, const int* n_hist,
                                                  int n_slots, T* cache, hipStream_t s);
 template <typename T> int launch_attn_fwd(const AttnParams& p, hipStream_t s);
 template <typename T> int launch_attn_bwd(const AttnParams& p, hipStream_t s);

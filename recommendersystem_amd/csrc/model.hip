@@ -135,7 +135,7 @@ int model_create(const rsys_config* cfg, int device, Model** out) {
   m->esz = m->bf16_mode ? 2 : 4;
   m->L = cfg->num_layers; m->H = cfg->num_heads; m->KV = cfg->num_kv_heads; m->D = cfg->embed_dim;
   m->I = cfg->intermediate_dim; m->Ip = m->fp8 ? (m->I + 127) / 128 * 128 : (m->I + 15) / 16 * 16;   // (fp8: K tiles of 128 elements; padding rows / columns of W13 / W2 are zero)
-  m->S = cfg->max_sequence_length; m->T = 2 * m->S;
+  m->Sa = cfg->max_sequence_length; m->Ta = 2 * m->Sa; set_row_len(m, m->Sa);
   m->V0 = cfg->vocab_0; m->V1 = cfg->vocab_1; m->V = m->V0 + m->V1; m->M = cfg->metadata_dim;
   m->Mp = (m->M + 63) / 64 * 64; m->K = cfg->mask_topk; m->hd = hd;
   m->Nqkv = (m->H + 2 * m->KV) * hd; m->rows_max = cfg->max_rows;
@@ -155,7 +155,7 @@ int model_create(const rsys_config* cfg, int device, Model** out) {
   for (int k = 0; k < 4; ++k) HIP_CHECK(hipEventCreateWithFlags(&m->ev_dw[k], hipEventDisableTiming));
   HIP_CHECK(hipEventCreateWithFlags(&m->ev_sel, hipEventDisableTiming));
   build_layout(m);
-  const int64_t D = m->D, N = (int64_t)m->rows_max * m->S, NT = 2 * N, KB = (int64_t)m->K * m->rows_max;
+  const int64_t D = m->D, N = (int64_t)m->rows_max * m->Sa, NT = 2 * N, KB = (int64_t)m->K * m->rows_max;
   const size_t e = m->esz;
   DALLOC(m->P, m->n_total * 4); DALLOC(m->G, m->n_total * 4);
   if (m->bf16_mode) { DALLOC(m->Sh, m->n_total * 2); DALLOC(m->ShT, m->n_total * 2); } else { m->Sh = m->P; }
@@ -169,10 +169,10 @@ int model_create(const rsys_config* cfg, int device, Model** out) {
   // RoPE tables (model.py:173-179), fp32 like torch; the host may overwrite them (rsys_model_set_rope)
   {
     const int half = hd / 2;
-    std::vector<float> c((size_t)m->T * half), s((size_t)m->T * half);
+    std::vector<float> c((size_t)m->Ta * half), s((size_t)m->Ta * half);
     for (int k = 0; k < half; ++k) {
       float freq = 1.0f / powf(500000.0f, (float)(2 * k) / (float)hd);
-      for (int t = 0; t < m->T; ++t) { float a = (float)t * freq; c[(size_t)t * half + k] = cosf(a); s[(size_t)t * half + k] = sinf(a); }
+      for (int t = 0; t < m->Ta; ++t) { float a = (float)t * freq; c[(size_t)t * half + k] = cosf(a); s[(size_t)t * half + k] = sinf(a); }
     }
     DALLOC(m->rope_cos, c.size() * 4); DALLOC(m->rope_sin, s.size() * 4); DALLOC(m->rope_cs, c.size() * 8);
     HIP_CHECK(hipMemcpy(m->rope_cos, c.data(), c.size() * 4, hipMemcpyHostToDevice));
@@ -180,7 +180,7 @@ int model_create(const rsys_config* cfg, int device, Model** out) {
     std::vector<float> cs(c.size() * 2);
     for (size_t i = 0; i < c.size(); ++i) { cs[2 * i] = c[i]; cs[2 * i + 1] = s[i]; }
     HIP_CHECK(hipMemcpy(m->rope_cs, cs.data(), cs.size() * 4, hipMemcpyHostToDevice));
-    m->rope_npos = m->T;
+    m->rope_npos = m->Ta;
   }
   // batch blob: 27 raw arrays + masked copies
   {
@@ -214,13 +214,13 @@ int model_create(const rsys_config* cfg, int device, Model** out) {
   DALLOC(m->feat, N * 32 * e); DALLOC(m->x0, NT * D * 4);
   DALLOC(m->uid_t, NT * 4); DALLOC(m->tm_t, NT * 4);
   {   // attention tile maps: the four the tile-map kernel ORs into sit back to back (one zero-fill per step), then the two it stores
-    const int64_t mb = ((int64_t)m->rows_max * ((m->T + 63) / 64) * 4 * attn_map_words(m->T) + 255) / 256 * 256;   // (64-bit map words above 32 tiles per row)
+    const int64_t mb = ((int64_t)m->rows_max * ((m->Ta + 63) / 64) * 4 * attn_map_words(m->Ta) + 255) / 256 * 256;   // (64-bit map words above 32 tiles per row)
     unsigned char* base = nullptr;
     DALLOC(base, mb * 7 + mb * 5);
     m->kmap = (unsigned int*)base; m->kmap_full = (unsigned int*)(base + mb); m->qmap_full = (unsigned int*)(base + 2 * mb); m->kmap16 = (unsigned int*)(base + 3 * mb);
     m->qmap = (unsigned int*)(base + 7 * mb); m->qmap16 = (unsigned int*)(base + 8 * mb);
     m->maps_zero_bytes = (size_t)(7 * mb);
-    const int64_t nt = (m->T + 63) / 64;
+    const int64_t nt = (m->Ta + 63) / 64;
     DALLOC(m->attn_order_q, (int64_t)m->rows_max * m->H * nt * 4 * 2);   /* second half: the q-tile-pair list (AttnParams::order_q2) */ DALLOC(m->attn_order_k, (int64_t)m->rows_max * m->KV * nt * 4);
     DALLOC(m->attn_qbits, (int64_t)m->rows_max * nt * nt * 64 * 8); DALLOC(m->attn_kbits, (int64_t)m->rows_max * nt * nt * 64 * 8);
   }
@@ -231,7 +231,7 @@ int model_create(const rsys_config* cfg, int device, Model** out) {
     DALLOC(a.xn, NT * D * e); DALLOC(a.qkv, NT * m->Nqkv * e);
     a.xnd = a.xn; a.La = nullptr;
     if (cfg->finetune) { DALLOC(a.La, NT * 16 * e); if (cfg->lora_dropout > 0.f) DALLOC(a.xnd, NT * D * e); }
-    DALLOC(a.O, NT * D * e); DALLOC(a.lse, (int64_t)m->rows_max * m->H * m->T * 4);
+    DALLOC(a.O, NT * D * e); DALLOC(a.lse, (int64_t)m->rows_max * m->H * m->Ta * 4);
     DALLOC(a.rstd1, NT * 4); DALLOC(a.h, NT * D * 4); DALLOC(a.hn, NT * D * e); DALLOC(a.rstd2, NT * 4);
     DALLOC(a.ab, NT * 2 * m->Ip * e); DALLOC(a.g, NT * m->Ip * e);
   }
@@ -279,7 +279,7 @@ int model_create(const rsys_config* cfg, int device, Model** out) {
   else { m->gxa_t = m->gxa; m->gxb_t = m->gxb; m->dh_t = m->dh; }
   DALLOC(m->dab, NT * 2 * m->Ip * e); DALLOC(m->dhn, NT * D * e);
   DALLOC(m->dO, NT * D * e); DALLOC(m->dqkv, NT * m->Nqkv * e);
-  DALLOC(m->delta, (int64_t)m->rows_max * m->H * m->T * 4); DALLOC(m->gf, N * 32 * 4);
+  DALLOC(m->delta, (int64_t)m->rows_max * m->H * m->Ta * 4); DALLOC(m->gf, N * 32 * 4);
   DALLOC(m->sumsq, 64); DALLOC(m->sumsq_part, (size_t)sumsq_parts() * 4);
   DALLOC(m->sel_scratch, 12 * 32 * 4);
   m->dLa = nullptr; m->dxl = nullptr;
@@ -316,12 +316,12 @@ int model_create(const rsys_config* cfg, int device, Model** out) {
       if (m->bf16_mode) { DALLOC(m->c_gx_t, cap * D * 2); DALLOC(m->c_dh_t, cap * D * 2); } else { m->c_gx_t = m->c_gx; m->c_dh_t = m->c_dh; }
       DALLOC(m->c_perm, NT * 4); DALLOC(m->uid_p, NT * 4); DALLOC(m->tm_p, NT * 4); DALLOC(m->pos_p, NT * 4); DALLOC(m->c_slot_p, NT * 4);
       DALLOC(m->c_sel_p, cap * 4); DALLOC(m->c_qact, (int64_t)m->rows_max * 4 + 64);
-      const int64_t mb = ((int64_t)m->rows_max * ((m->T + 63) / 64) * 4 * attn_map_words(m->T) + 255) / 256 * 256;   // (64-bit map words above 32 tiles per row)
+      const int64_t mb = ((int64_t)m->rows_max * ((m->Ta + 63) / 64) * 4 * attn_map_words(m->Ta) + 255) / 256 * 256;   // (64-bit map words above 32 tiles per row)
       unsigned char* base = nullptr;
       DALLOC(base, mb * 12);
       m->kmap_p = (unsigned int*)base; m->kmap_full_p = (unsigned int*)(base + mb); m->qmap_full_p = (unsigned int*)(base + 2 * mb); m->kmap16_p = (unsigned int*)(base + 3 * mb);
       m->qmap_p = (unsigned int*)(base + 7 * mb); m->qmap16_p = (unsigned int*)(base + 8 * mb);
-      const int64_t nt = (m->T + 63) / 64;
+      const int64_t nt = (m->Ta + 63) / 64;
       DALLOC(m->attn_order_q_p, (int64_t)m->rows_max * m->H * nt * 4 * 2); DALLOC(m->attn_order_k_p, (int64_t)m->rows_max * m->KV * nt * 4);
       DALLOC(m->attn_qbits_p, (int64_t)m->rows_max * nt * nt * 64 * 8); DALLOC(m->attn_kbits_p, (int64_t)m->rows_max * nt * nt * 64 * 8);
     }
@@ -353,7 +353,7 @@ int model_create(const rsys_config* cfg, int device, Model** out) {
     }
     if (!aligned) { set_error("fp8 trunk: weight offsets are not 16-byte aligned in the fp8 copies"); return RSYS_ERR_ARG; }
     const int f8dw = sw().f8_dw;
-    m->f8_dw = f8dw != 0 && (2 * m->S) % 128 == 0;   // (K = tokens in tiles of 128)
+    m->f8_dw = f8dw != 0 && (2 * m->Sa) % 128 == 0;   // (K = tokens in tiles of 128)
     if (m->f8_dw) {
       m->f8_ldt = NT;
       m->f8t.resize(L);
@@ -548,7 +548,7 @@ int model_random_metadata(Model* m, uint64_t seed) {
 }
 
 int model_set_rope(Model* m, const float* c, const float* s, int64_t n_pos) {
-  ARG_CHECK(n_pos == m->T, "rope tables must have 2*max_sequence_length positions");
+  ARG_CHECK(n_pos == m->Ta, "rope tables must have 2*max_sequence_length positions");
   HIP_CHECK(hipSetDevice(m->device));
   size_t bytes = (size_t)n_pos * (m->hd / 2) * 4;
   HIP_CHECK(hipMemcpy(m->rope_cos, c, bytes, hipMemcpyHostToDevice));
@@ -681,7 +681,7 @@ struct StagedBatch { BatchDev bd; bool has_masks = false, has_rope_pos = false; 
 static int batch_stage(Model* m, const rsys_batch* b, int slot, StagedBatch& out) {
   ARG_CHECK(b != nullptr, "null batch");
   ARG_CHECK(b->rows >= 1 && b->rows <= m->rows_max, "batch rows must be in [1, max_rows]");
-  const size_t N = (size_t)b->rows * m->S;
+  const size_t N = (size_t)b->rows * m->Sa;
   ARG_CHECK(b->userid && b->token_mask_ids && b->gender && b->source && b->matchedid && b->status && b->time && b->rating && b->progress,
             "batch arrays must not be null");
   for (int k = 0; k < 6; ++k) {
@@ -720,7 +720,7 @@ static int batch_stage(Model* m, const rsys_batch* b, int slot, StagedBatch& out
     // model.py:470-476: token positions 2p, 2p+1
     pos.resize(2 * N);
     for (size_t i = 0; i < N; ++i) { pos[2 * i] = 2 * b->rope_input_pos[i]; pos[2 * i + 1] = 2 * b->rope_input_pos[i] + 1; }
-    for (size_t i = 0; i < 2 * N; ++i) ARG_CHECK(pos[i] >= 0 && pos[i] < m->T, "rope_input_pos out of range");
+    for (size_t i = 0; i < 2 * N; ++i) ARG_CHECK(pos[i] >= 0 && pos[i] < m->Ta, "rope_input_pos out of range");
   }
   // pack (pinned staging) -> one H2D -> the device arrays sit back to back in the slot's blob
   unsigned char* blob = m->slot_blob[slot]; unsigned char* stage = m->slot_stage[slot];
@@ -756,7 +756,8 @@ int model_batch_upload(Model* m, const rsys_batch* b) {
   // step's optimizer pass.  (A prefetch into this slot's staging is complete too: model_batch_swap waited for its copy.)
   StagedBatch st;
   RC(batch_stage(m, b, m->cur_slot, st));
-  const size_t N = (size_t)b->rows * m->S;
+  const size_t N = (size_t)b->rows * m->Sa;
+  set_row_len(m, m->Sa);
   m->cur_rows = 0;   // (a failing copy below must not leave a half-written batch marked as resident)
   m->bd = st.bd;
   BatchDev& d = m->bd;
@@ -776,17 +777,92 @@ int model_batch_upload(Model* m, const rsys_batch* b) {
   return RSYS_OK;
 }
 
+// A trimmed batch holds no targets and no masks: every pass that reads them refuses it and touches nothing.
+int check_not_trimmed(const Model* m) {
+  if (!batch_trimmed(m)) return RSYS_OK;
+  set_error("a trimmed batch is inference-only (rsys_batch_upload_trimmed): upload the full rows for this call");
+  return RSYS_ERR_STATE;
+}
+
+// rsys_batch_upload_trimmed.  The caller's arrays keep the row stride Sa; columns [0, row_len) of every row are checked,
+// packed at stride row_len and copied, and the resident batch then has rows of row_len interactions: every kernel of the inference
+// forward is launched over rows * 2 row_len tokens.  Exact because the dropped columns are padding (userid 0), which no live token
+// attends (the mask's first predicate is the user id) and every other operator of the trunk is token-local.  Targets and masks are not
+// read; their blob places stay unwritten and nothing of an inference forward reads them.
+int model_batch_upload_trimmed(Model* m, const rsys_batch* b, int row_len) {
+  ARG_CHECK(b != nullptr, "null batch");
+  ARG_CHECK(row_len >= 4 && row_len <= m->Sa && row_len % 4 == 0, "trimmed upload: row_len % 4 == 0 and 4 <= row_len <= max_sequence_length");
+  ARG_CHECK(!m->fp8, "trimmed upload: fp32 and bf16 models only (the fp8 trunk's tensor-wise amax sees every token)");
+  ARG_CHECK(!m->sharded, "trimmed upload: a model with a replicated table");
+  if (row_len == m->Sa) return model_batch_upload(m, b);
+  ARG_CHECK(b->rows >= 1 && b->rows <= m->rows_max, "batch rows must be in [1, max_rows]");
+  ARG_CHECK(b->userid && b->token_mask_ids && b->gender && b->source && b->matchedid && b->status && b->time && b->rating && b->progress,
+            "batch arrays must not be null");
+  const int rows = b->rows, Sa = m->Sa;
+  // index paths and the dead suffix are checked on the host BEFORE anything is written: a rejected batch leaves the resident one untouched
+  for (int r = 0; r < rows; ++r) {
+    const size_t r0 = (size_t)r * Sa;
+    for (int j = 0; j < row_len; ++j) {
+      const size_t i = r0 + j;
+      ARG_CHECK(b->matchedid[i] >= -1 && b->matchedid[i] < m->V, "matchedid out of range");
+      ARG_CHECK(b->userid[i] >= 0 && b->userid[i] < (1 << 19), "userid must be in [0, 2^19)");
+      ARG_CHECK(b->token_mask_ids[i] >= 0 && b->token_mask_ids[i] < 4096, "token_mask_ids must be in [0, 4096)");
+      ARG_CHECK(b->status[i] >= -1 && b->status[i] <= m->cfg.vocab_status, "status out of range");
+      ARG_CHECK(b->gender[i] >= -1 && b->gender[i] <= m->cfg.vocab_gender, "gender out of range");
+      ARG_CHECK(b->source[i] >= -1 && b->source[i] <= m->cfg.vocab_source, "source out of range");
+      if (b->rope_input_pos) ARG_CHECK(b->rope_input_pos[i] >= 0 && 2 * b->rope_input_pos[i] + 1 < m->Ta, "rope_input_pos out of range");   // (a position, not a column: the table's bound, as rsys_batch_upload)
+    }
+    for (int j = row_len; j < Sa; ++j) ARG_CHECK(b->userid[r0 + j] == 0, "trimmed upload: a live event (userid != 0) at or behind column row_len");
+  }
+  HIP_CHECK(hipSetDevice(m->device));
+  hipStream_t s = m->stream;
+  if (m->pending.valid) HIP_CHECK(hipEventSynchronize(m->ev_copy_done));   // (as model_batch_upload: an explicit upload supersedes a prefetched batch)
+  m->pending.valid = false;
+  const size_t N = (size_t)rows * row_len;
+  unsigned char* blob = m->slot_blob[m->cur_slot]; unsigned char* stage = m->slot_stage[m->cur_slot];
+  const BlobLayout L = blob_layout(N);
+  if (L.bytes > m->raw_bytes) { set_error("batch upload: staging buffer too small"); return RSYS_ERR_STATE; }
+  auto put = [&](size_t at, const void* src, size_t esz) {   // columns [0, row_len) of every row, stride Sa -> row_len
+    for (int r = 0; r < rows; ++r) memcpy(stage + at + (size_t)r * row_len * esz, (const unsigned char*)src + (size_t)r * Sa * esz, (size_t)row_len * esz);
+  };
+  put(L.time, b->time, 8);
+  put(L.userid, b->userid, 4); put(L.tmid, b->token_mask_ids, 4); put(L.gender, b->gender, 4); put(L.source, b->source, 4);
+  put(L.matchedid, b->matchedid, 4); put(L.status, b->status, 4); put(L.rating, b->rating, 4); put(L.progress, b->progress, 4);
+  if (b->rope_input_pos) {   // model.py:470-476: token positions 2p, 2p+1
+    int* pos = (int*)(stage + L.rope);
+    for (int r = 0; r < rows; ++r)
+      for (int j = 0; j < row_len; ++j) {
+        const int p = b->rope_input_pos[(size_t)r * Sa + j];
+        pos[2 * ((size_t)r * row_len + j)] = 2 * p; pos[2 * ((size_t)r * row_len + j) + 1] = 2 * p + 1;
+      }
+  }
+  m->cur_rows = 0;   // (a failing copy below must not leave a half-written batch marked as resident)
+  BatchDev d = m->bd;
+  blob_point(m, blob, L, d, &m->d_wm, &m->d_rm, &m->d_rope_pos);
+  m->bd = d;
+  m->has_masks = false; m->has_rope_pos = b->rope_input_pos != nullptr;
+  m->u_bound_host = 0; m->tok_index_valid = false; m->split_plan_valid = false;
+  HIP_CHECK(hipMemcpyAsync(blob, stage, L.bytes, hipMemcpyHostToDevice, s));
+  HIP_CHECK(hipStreamSynchronize(s));
+  set_row_len(m, row_len);
+  m->cur_rows = rows;
+  return RSYS_OK;
+}
+
 // The resident batch as device arrays for a kernel to fill (rsys_render_request's ranking rows): the layout of batch_stage for `rows`
 // rows in the current slot's blob, nothing copied.  Everything enqueued so far that reads the blob runs before the kernel that fills it
 // (same stream); the slot's staging buffer is not touched.
-int model_batch_device_begin(Model* m, int rows, BatchDevRows* out) {
+int model_batch_device_begin(Model* m, int rows, BatchDevRows* out, int row_len) {
   ARG_CHECK(rows >= 1 && rows <= m->rows_max, "batch rows must be in [1, max_rows]");
+  if (row_len == 0) row_len = m->Sa;
+  ARG_CHECK(row_len >= 4 && row_len <= m->Sa && row_len % 4 == 0, "device-assembled batch: row_len % 4 == 0 and 4 <= row_len <= max_sequence_length");
   ARG_CHECK(!m->sharded, "device-assembled batch: replicated table only");
   HIP_CHECK(hipSetDevice(m->device));
   if (m->pending.valid) HIP_CHECK(hipEventSynchronize(m->ev_copy_done));
   m->pending.valid = false;
-  const BlobLayout L = blob_layout((size_t)rows * m->S);
+  const BlobLayout L = blob_layout((size_t)rows * row_len);
   if (L.bytes > m->raw_bytes) { set_error("device-assembled batch: blob too small"); return RSYS_ERR_STATE; }
+  set_row_len(m, row_len);
   BatchDev d = m->bd;
   blob_point(m, m->slot_blob[m->cur_slot], L, d, &m->d_wm, &m->d_rm, &out->rope_pos);
   out->time = (double*)d.time; out->userid = (int*)d.userid; out->tmid = (int*)d.tmid; out->gender = (int*)d.gender;
@@ -835,6 +911,7 @@ int model_batch_swap(Model* m) {
   m->has_masks = m->pending.has_masks; m->d_wm = m->pending.d_wm; m->d_rm = m->pending.d_rm;
   m->has_rope_pos = m->pending.has_rope_pos; m->d_rope_pos = m->pending.d_rope_pos;
   m->cur_rows = m->pending.rows;
+  set_row_len(m, m->Sa);
   m->u_bound_host = m->pending.distinct_ids;
   m->tok_index_valid = false;
   m->split_plan_valid = false;
@@ -892,6 +969,7 @@ static int forward_backward_t(Model* m, int evaluate, const float task_w[4], flo
 
 int model_forward_backward(Model* m, int evaluate, const float task_w[4], float grad_scale, uint64_t seed, uint64_t step) {
   ARG_CHECK(m->cur_rows > 0, "no batch uploaded");
+  RC(check_not_trimmed(m));
   ARG_CHECK(evaluate || task_w != nullptr, "task weights are required for training");
   HIP_CHECK(hipSetDevice(m->device));
   DetScope det(m);
@@ -904,6 +982,7 @@ int model_forward_backward(Model* m, int evaluate, const float task_w[4], float 
 // masks; the frozen-trunk branches of the forward, the heads and the backward are chosen by trunk_frozen(m).
 int model_forward_backward_rows(Model* m, int evaluate, const int* d_row_task, float grad_scale, uint64_t seed, uint64_t step) {
   const float tw[4] = {1.f, 1.f, 1.f, 1.f};
+  RC(check_not_trimmed(m));
   m->last_evaluate = evaluate != 0;
   return m->bf16_mode ? forward_backward_t<bf16>(m, evaluate, tw, grad_scale, seed, step, d_row_task)
                       : forward_backward_t<float>(m, evaluate, tw, grad_scale, seed, step, d_row_task);
@@ -919,8 +998,19 @@ template <typename T>
 static int infer_t(Model* m, int task, const int32_t* sel, int64_t n_sel, float* out, int64_t n) {
   const int rows = m->cur_rows, N = rows * m->S, NT = 2 * N, D = m->D;
   hipStream_t s = m->stream;
+  std::vector<int32_t> moved;   // a trimmed batch: the caller's indices r * 2 Sa + t in the resident rows' geometry r * 2 S + t
   if (sel != nullptr) {
     ARG_CHECK(n_sel <= NT, "selection: more tokens than the batch holds");
+    if (batch_trimmed(m)) {
+      moved.resize((size_t)n_sel);
+      for (int64_t i = 0; i < n_sel; ++i) {
+        ARG_CHECK(sel[i] >= 0 && sel[i] < rows * m->Ta, "selection: token index out of range");
+        const int r = sel[i] / m->Ta, t = sel[i] % m->Ta;
+        ARG_CHECK(t < m->T, "selection: a token at or behind 2 row_len of a trimmed row");
+        moved[(size_t)i] = r * m->T + t;
+      }
+      sel = moved.data();
+    }
     for (int64_t i = 0; i < n_sel; ++i) ARG_CHECK(sel[i] >= 0 && sel[i] < NT, "selection: token index out of range");
   }
   const int64_t ntok = sel != nullptr ? n_sel : NT;

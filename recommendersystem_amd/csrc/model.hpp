@@ -102,6 +102,13 @@ struct Model {
   size_t esz = 4;
   // dims
   int L, H, KV, D, I, Ip, S, T, V0, V1, V, M, Mp, K, hd, Nqkv, rows_max;
+  // S / T above are the RESIDENT BATCH's row length (interactions / tokens): everything that walks the batch reads them.  Sa / Ta are the
+  // allocated geometry (cfg.max_sequence_length, twice that): buffer sizes, the RoPE tables, the offsets inside the launch-order arrays,
+  // the ranking cache's slot stride, the render pipelines' chunking.  S == Sa except under rsys_batch_upload_trimmed and the trimmed
+  // forwards of the render pipelines; every ordinary upload, swap and device-assembled batch sets S = Sa.
+  int Sa = 0, Ta = 0;
+  bool serving_trim = false;      // rsys_serving_trim_set: the two render entry points run every forward at its longest live row
+  int64_t fwd_tokens = 0;         // tokens the last forward_trunk ran over (rsys_debug_get "forward.tokens")
   int64_t n_decay = 0, n_total = 0;
   int64_t n_opt = 0, n_opt_decay = 0;   // range the optimizer / clip / all-reduce cover (finetune: the LoRA segment only)
   std::vector<TensorInfo> tensors;
@@ -317,6 +324,9 @@ int model_set_rope(Model* m, const float* c, const float* s, int64_t n_pos);
 int model_param_io(Model* m, const char* name, float* out, const float* in, int64_t n, int which /*0 P,1 G*/);
 int model_refresh_shadow(Model* m);
 int model_batch_upload(Model* m, const rsys_batch* b);
+// rsys_batch_upload_trimmed: b's arrays keep the row stride Sa, columns [0, row_len) of every row become the resident batch (inference-only)
+int model_batch_upload_trimmed(Model* m, const rsys_batch* b, int row_len);
+int check_not_trimmed(const Model* m);   // RSYS_ERR_STATE on a trimmed resident batch (the passes that read targets)
 int model_forward_backward(Model* m, int evaluate, const float task_w[4], float grad_scale, uint64_t seed, uint64_t step);
 int model_infer(Model* m, int task, const int32_t* token_index, int64_t n_tokens, float* out, int64_t n);   // token_index == nullptr: every token
 // adapter bank (adapter_bank.hip): slot storage by state-dict name, and the inference forward with one slot per batch row
@@ -329,6 +339,8 @@ void adapter_bank_free(Model* m);
 template <typename T> int adapter_bank_stage_a(Model* m, int l, const T* xn);                      // La = xn . [A_q; A_v][slot]^T
 template <typename T> int adapter_bank_stage_b(Model* m, int l, T* qkv, const int* rope_pos);      // q, v += 2 La . B[slot]^T (q rotated)
 // training through the bank (adapter_bank.hip)
+inline void set_row_len(Model* m, int row_len) { m->S = row_len; m->T = 2 * row_len; }
+inline bool batch_trimmed(const Model* m) { return m->S != m->Sa; }
 inline bool trunk_frozen(const Model* m) { return m->cfg.finetune != 0 || m->bank_train; }
 inline float* small_grad(Model* m, int64_t off) { return m->bank_train ? m->bank_sink : m->G + off; }   // where a frozen-trunk pass may drop a <= D-float gradient
 int adapter_train_enable(Model* m, float dropout);
@@ -346,7 +358,7 @@ int model_infer_adapters(Model* m, int task, const int32_t* row_adapter, const i
 // returns where its arrays live in the current slot's blob (target arrays stay as they are: an inference forward never reads them).
 // rope_pos holds the per-token positions (2 p, 2 p + 1 for interaction position p), as rsys_batch_upload derives them.
 struct BatchDevRows { double* time; int *userid, *tmid, *gender, *source, *matchedid, *status; float *rating, *progress; int* rope_pos; };
-int model_batch_device_begin(Model* m, int rows, BatchDevRows* out);
+int model_batch_device_begin(Model* m, int rows, BatchDevRows* out, int row_len = 0 /* 0: the allocated length */);
 // the forward of rsys_infer_select_adapters over the resident batch with the selection (n_sel flat token indices) and the result
 // (task 0: n_sel x D trunk rows, task 1: n_sel rating-head values, fp32) both on the device; row_adapter (host) may be null (base model);
 // stream-ordered, no host wait

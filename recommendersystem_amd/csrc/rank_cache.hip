@@ -16,7 +16,7 @@ static int rc_check_model(Model* m) {
   return RSYS_OK;
 }
 static inline size_t rc_kvw(const Model* m) { return (size_t)2 * m->KV * m->hd; }                    // values of a cached token: K | V
-static inline size_t rc_layer_elems(const Model* m) { return (size_t)m->rc_slots * m->T * rc_kvw(m); }
+static inline size_t rc_layer_elems(const Model* m) { return (size_t)m->rc_slots * m->Ta * rc_kvw(m); }   // (the slot stride is the allocated row: a slot serves rows of any length)
 
 void rank_cache_free(Model* m) {
   if (m->rcache) (void)hipFree(m->rcache);
@@ -30,8 +30,8 @@ int model_rank_cache_reserve(Model* m, int n_slots) {
   HIP_CHECK(hipSetDevice(m->device));
   HIP_CHECK(hipStreamSynchronize(m->stream));
   if (n_slots == 0) { rank_cache_free(m); return RSYS_OK; }
-  const size_t bytes = (size_t)m->L * n_slots * m->T * rc_kvw(m) * m->esz;
-  const size_t held = (size_t)m->L * m->rc_slots * m->T * rc_kvw(m) * m->esz;
+  const size_t bytes = (size_t)m->L * n_slots * m->Ta * rc_kvw(m) * m->esz;
+  const size_t held = (size_t)m->L * m->rc_slots * m->Ta * rc_kvw(m) * m->esz;
   size_t free_b = 0, total_b = 0;
   HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
   // (checked before the old cache goes: a size that cannot fit leaves the slots that are stored where they are)
@@ -48,7 +48,7 @@ int model_rank_cache_reserve(Model* m, int n_slots) {
   }
   // rows' {slot, n_hist, n_cand} and the candidates' RoPE positions (one per token of a full batch)
   int* rows = nullptr;
-  if (hipMalloc((void**)&rows, ((size_t)3 * m->rows_max + (size_t)m->rows_max * m->T) * 4) != hipSuccess) {
+  if (hipMalloc((void**)&rows, ((size_t)3 * m->rows_max + (size_t)m->rows_max * m->Ta) * 4) != hipSuccess) {
     (void)hipGetLastError(); (void)hipFree(p);
     set_error("ranking cache: no memory for the row descriptors");
     return RSYS_ERR_STATE;
@@ -61,7 +61,7 @@ int model_rank_cache_reserve(Model* m, int n_slots) {
 template <typename T>
 int rank_cache_store_layer(Model* m, int l, const T* qkv) {
   tic(m, "hbm_rank_cache_store", 2.0 * sizeof(T) * m->cur_rows * m->T * (double)rc_kvw(m));
-  const int rc = launch_rank_cache_copy<T>(qkv, m->Nqkv, m->H * m->hd, (int)rc_kvw(m), m->T, m->cur_rows, m->rc_rows, m->rc_rows + m->rows_max, m->rc_slots,
+  const int rc = launch_rank_cache_copy<T>(qkv, m->Nqkv, m->H * m->hd, (int)rc_kvw(m), m->T, m->Ta, m->cur_rows, m->rc_rows, m->rc_rows + m->rows_max, m->rc_slots,
                                            (T*)m->rcache + (size_t)l * rc_layer_elems(m), m->stream);
   toc(m);
   return rc;
@@ -69,7 +69,7 @@ int rank_cache_store_layer(Model* m, int l, const T* qkv) {
 template <typename T>
 int rank_cache_attention(Model* m, int l, const T* qkv, T* O) {
   CandAttnParams p{};
-  p.rows = m->cur_rows; p.T = m->T; p.H = m->H; p.KV = m->KV; p.hd = m->hd;
+  p.rows = m->cur_rows; p.T = m->T; p.Tc = m->Ta; p.H = m->H; p.KV = m->KV; p.hd = m->hd;
   p.qkv = qkv; p.ld = m->Nqkv;
   p.cache = (const T*)m->rcache + (size_t)l * rc_layer_elems(m); p.n_slots = m->rc_slots;
   p.slot = m->rc_rows; p.n_hist = m->rc_rows + m->rows_max; p.n_cand = m->rc_rows + 2 * m->rows_max;
@@ -100,7 +100,7 @@ int rank_cache_store_rows(Model* m, const int32_t* row_adapter, const int32_t* n
   const int rows = m->cur_rows;
   std::vector<char> seen((size_t)m->rc_slots, 0);
   for (int r = 0; r < rows; ++r) {
-    ARG_CHECK(n_hist[r] >= 0 && n_hist[r] <= m->S, "ranking cache: n_hist must be in [0, max_sequence_length]");
+    ARG_CHECK(n_hist[r] >= 0 && n_hist[r] <= m->S, "ranking cache: n_hist must be in [0, the resident rows' length]");
     ARG_CHECK(slot[r] >= 0 && slot[r] < m->rc_slots, "ranking cache: slot outside the reserve");
     ARG_CHECK(!seen[slot[r]], "ranking cache: the slots of one store call must be distinct");
     seen[slot[r]] = 1;
@@ -140,8 +140,8 @@ static int rc_check_candidates(Model* m, const int32_t* slot, const int32_t* n_c
   for (int r = 0; r < m->cur_rows; ++r) {
     ARG_CHECK(slot[r] >= 0 && slot[r] < m->rc_slots, "ranking cache: slot outside the reserve");
     ARG_CHECK(m->rc_nhist[slot[r]] >= 0, "ranking cache: slot never stored");
-    ARG_CHECK(m->rc_nhist[slot[r]] <= m->S - 1, "ranking cache: candidates run at position n_hist, which must stay below max_sequence_length");
-    ARG_CHECK(n_cand[r] >= 1 && n_cand[r] <= m->S, "ranking cache: n_cand must be in [1, max_sequence_length]");
+    ARG_CHECK(m->rc_nhist[slot[r]] <= m->Sa - 1, "ranking cache: candidates run at position n_hist, which must stay below max_sequence_length");
+    ARG_CHECK(n_cand[r] >= 1 && n_cand[r] <= m->S, "ranking cache: n_cand must be in [1, the resident rows' length]");
     *ntok += n_cand[r];
   }
   return RSYS_OK;
@@ -217,7 +217,7 @@ int model_rank_cache_get(Model* m, int layer, int slot, void* out, int64_t bytes
   ARG_CHECK(bytes == (int64_t)want, "ranking cache: out holds [2 n_hist][2 KV hd] values of the compute dtype");
   HIP_CHECK(hipSetDevice(m->device));
   HIP_CHECK(hipStreamSynchronize(m->stream));
-  const unsigned char* src = (const unsigned char*)m->rcache + ((size_t)layer * rc_layer_elems(m) + (size_t)slot * m->T * rc_kvw(m)) * m->esz;
+  const unsigned char* src = (const unsigned char*)m->rcache + ((size_t)layer * rc_layer_elems(m) + (size_t)slot * m->Ta * rc_kvw(m)) * m->esz;
   if (want) HIP_CHECK(hipMemcpy(out, src, want, hipMemcpyDeviceToHost));
   return RSYS_OK;
 }

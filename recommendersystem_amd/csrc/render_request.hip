@@ -68,7 +68,7 @@ struct RowDesc {
 struct Win { int src, n, dst; };
 
 // row blockIdx.x of the wave from its descriptor: all ten arrays, the per-token RoPE positions (2 p, 2 p + 1) as rsys_batch_upload derives
-// them, and candidate c's action token r 2S + 2 (ncopy + c) + 1 at sel[sel0 + c]
+// them, and candidate c's action token r 2S + 2 (ncopy + c) + 1 at sel[sel0 + c].  S is the wave's row length (the model's S, or the trimmed one)
 __global__ void __launch_bounds__(RN_THREADS) rows_kernel(const RowDesc* rows, HistSrc h, int S, const int32_t* cand, BatchDevRows out, int* sel) {
   const int r = blockIdx.x;
   const RowDesc d = rows[r];
@@ -139,10 +139,13 @@ struct RenderState {
   bool keep = false;                                   // rsys_render_debug_keep: the next calls keep their intermediates
   int forwards[2] = {0, 0};                            // forwards of the last call: retrieval, ranking
   int forwards_full[3] = {0, 0, 0};                    // rsys_render_request_full's ranking forwards: store, candidates, empty-history chunks
+  std::vector<int32_t> forward_rows;                   // (stage, rows, row_len) of every forward of the last call, run order: stage 0 retrieval, 1 store, 2 cached candidates, 3 assembled
+  void note_forward(int stage, int rows, int row_len) { forward_rows.push_back(stage); forward_rows.push_back(rows); forward_rows.push_back(row_len); }
   std::map<std::string, std::vector<unsigned char>> kept;
   void begin() {   // a call starts
     forwards[0] = forwards[1] = 0;
     forwards_full[0] = forwards_full[1] = forwards_full[2] = 0;
+    forward_rows.clear();
     kept.clear();
   }
   void put_bytes(const std::string& key, const void* p, size_t n) {
@@ -152,15 +155,21 @@ struct RenderState {
     if (n) memcpy(v.data() + at, p, n);
   }
   template <typename X> void put(const char* key, const X* p, size_t n) { put_bytes(key, p, n * sizeof(X)); }
-  // the ten arrays of the nr device-assembled rows of S tokens under "<name>.*"
-  int keep_rows(const std::string& name, const BatchDevRows& bd, int nr, int S) {
-    const size_t N = (size_t)nr * S;
-    std::vector<int64_t> h(N);
+  // the ten arrays of the nr device-assembled rows under "<name>.*", as [nr][S]: rows of rl < S interactions (a trimmed forward) are
+  // widened with what the untrimmed rows hold there: zeros, and the row's fill position fill_pos[r] as rope_input_pos
+  int keep_rows(const std::string& name, const BatchDevRows& bd, int nr, int S, int rl, const std::vector<int>& fill_pos) {
+    const size_t N = (size_t)nr * rl;
+    std::vector<int64_t> h(N), wide((size_t)nr * S);
     for (const KeptCol& c : kept_cols(bd)) {
       HIP_CHECK(hipMemcpy(h.data(), c.src, N * c.size * c.per, hipMemcpyDeviceToHost));
       int32_t* hi = (int32_t*)h.data();
       for (size_t i = 0; i < N && c.per == 2; ++i) hi[i] = hi[2 * i] / 2;   // (the per-token positions 2 p, 2 p + 1 back to rope_input_pos)
-      put_bytes(name + c.suffix, h.data(), N * c.size);
+      if (rl == S) { put_bytes(name + c.suffix, h.data(), N * c.size); continue; }
+      std::fill(wide.begin(), wide.end(), 0);
+      for (int r = 0; r < nr && c.per == 2; ++r) std::fill((int32_t*)wide.data() + (size_t)r * S + rl, (int32_t*)wide.data() + (size_t)(r + 1) * S, fill_pos[r]);
+      for (int r = 0; r < nr; ++r)
+        memcpy((unsigned char*)wide.data() + (size_t)r * S * c.size, (const unsigned char*)h.data() + (size_t)r * rl * c.size, (size_t)rl * c.size);
+      put_bytes(name + c.suffix, wide.data(), (size_t)nr * S * c.size);
     }
     return RSYS_OK;
   }
@@ -198,6 +207,11 @@ int render_debug_get(Model* m, const char* key, void* out, int64_t cap, int64_t*
   if (std::string(key) == "forwards") {
     *bytes = 8;
     if (out && cap >= 8) memcpy(out, R->forwards, 8);
+    return RSYS_OK;
+  }
+  if (std::string(key) == "forward_rows") {
+    *bytes = (int64_t)R->forward_rows.size() * 4;
+    if (out && cap >= *bytes && *bytes) memcpy(out, R->forward_rows.data(), (size_t)*bytes);
     return RSYS_OK;
   }
   if (std::string(key) == "forwards.full") {
@@ -270,7 +284,12 @@ struct Render : RenderArgs {
     std::vector<RowDesc> sd, crows;
   } t;
 
-  Render(Model* model, const RenderArgs& a) : RenderArgs(a), m(model), S(m->S), D(m->D), chunk(S - S / 2), RM(m->rows_max) {}
+  Render(Model* model, const RenderArgs& a) : RenderArgs(a), m(model), S(m->Sa), D(m->D), chunk(S - S / 2), RM(m->rows_max), trim(m->serving_trim) {}
+
+  // rsys_serving_trim_set: a forward whose longest row has `live` live columns runs at this row length -- whole 64-token attention tiles,
+  // clamped to S (serve.trim_length); off: S.  Chunking, waves and slots are planned on S either way.
+  const bool trim;
+  int row_len_for(int live) const { return trim ? std::min(S, (std::max(live, 1) + 31) / 32 * 32) : S; }
 
   // ---- arguments.  Checked here, before anything is enqueued: the request's shape, pagination, groups, offsets' monotonicity, adapter
   // slots, descriptors and prefixes.  Checked later, by the code that owns them: the retrieval rows (rsys_batch_upload's checks, wave by
@@ -334,7 +353,7 @@ struct Render : RenderArgs {
         ARG_CHECK(pb->status[q] >= -1 && pb->status[q] <= m->cfg.vocab_status, "render_request: prefix status out of range");
         ARG_CHECK(pb->gender[q] >= -1 && pb->gender[q] <= m->cfg.vocab_gender, "render_request: prefix gender out of range");
         ARG_CHECK(pb->source[q] >= -1 && pb->source[q] <= m->cfg.vocab_source, "render_request: prefix source out of range");
-        ARG_CHECK(pb->rope_input_pos[q] >= 0 && 2 * pb->rope_input_pos[q] + 1 < m->T, "render_request: prefix rope_input_pos out of range");
+        ARG_CHECK(pb->rope_input_pos[q] >= 0 && 2 * pb->rope_input_pos[q] + 1 < m->Ta, "render_request: prefix rope_input_pos out of range");
       }
     }
     ARG_CHECK(S / 2 + chunk <= 4096, "render_request: max_sequence_length <= 4096 (token_mask_ids of the candidates)");
@@ -381,19 +400,32 @@ struct Render : RenderArgs {
       b.matchedid = rb->matchedid + o; b.status = rb->status + o; b.time = rb->time + o; b.rating = rb->rating + o; b.progress = rb->progress + o;
       b.rope_input_pos = rb->rope_input_pos + o;
       for (int k = 0; k < 6; ++k) { b.label[k] = zf.data(); b.weight[k] = zf.data(); b.position[k] = zi.data(); }
-      RC(model_batch_upload(m, &b));
+      int live = 1;   // the wave's longest live row: the last column with a user, and the query token's column
+      for (int r = 0; r < nr && trim; ++r) {
+        live = std::max(live, retrieval_token[u0 + r] / 2 + 1);
+        if (full) live = std::max(live, user_desc[4 * (u0 + r)] + 1);   // (the store rows read n_hist columns of the kept row: all of them are copied below, whatever the caller's rows hold there)
+        int j = S;
+        while (j > live && b.userid[(size_t)r * S + j - 1] == 0) --j;
+        live = std::max(live, j);
+      }
+      const int rl = row_len_for(live);
+      RC(rl == S ? model_batch_upload(m, &b) : model_batch_upload_trimmed(m, &b, rl));
+      R->note_forward(0, nr, rl);
       if (full) {   // the rows' history columns stay on the device: the store rows are cut from them, nothing of a history is uploaded twice
-        const size_t n = (size_t)nr * S;
-        const BatchDev& bd = m->bd;
-        HIP_CHECK(hipMemcpyAsync(hist.time + o, bd.time, n * 8, hipMemcpyDeviceToDevice, s));
+        const BatchDev& bd = m->bd;   // (rows of rl columns; the kept rows keep the stride S, their columns behind rl are never read: n_hist < rl by the choice of rl above)
+        auto keep_cols = [&](void* dst, const void* src, size_t esz) {
+          if (rl == S) return hipMemcpyAsync(dst, src, (size_t)nr * S * esz, hipMemcpyDeviceToDevice, s);   // (full rows: one contiguous copy)
+          return hipMemcpy2DAsync(dst, (size_t)S * esz, src, (size_t)rl * esz, (size_t)rl * esz, (size_t)nr, hipMemcpyDeviceToDevice, s);
+        };
+        HIP_CHECK(keep_cols(hist.time + o, bd.time, 8));
         const int* src_i[5] = {bd.userid, bd.gender, bd.source, bd.matchedid, bd.status};
         int* dst_i[5] = {hist.userid, hist.gender, hist.source, hist.matchedid, hist.status};
-        for (int k = 0; k < 5; ++k) HIP_CHECK(hipMemcpyAsync(dst_i[k] + o, src_i[k], n * 4, hipMemcpyDeviceToDevice, s));
-        HIP_CHECK(hipMemcpyAsync(hist.rating + o, bd.rating, n * 4, hipMemcpyDeviceToDevice, s));
-        HIP_CHECK(hipMemcpyAsync(hist.progress + o, bd.progress, n * 4, hipMemcpyDeviceToDevice, s));
+        for (int k = 0; k < 5; ++k) HIP_CHECK(keep_cols(dst_i[k] + o, src_i[k], 4));
+        HIP_CHECK(keep_cols(hist.rating + o, bd.rating, 4));
+        HIP_CHECK(keep_cols(hist.progress + o, bd.progress, 4));
       }
       for (int r = 0; r < nr; ++r) {
-        t.tok[r] = r * 2 * S + retrieval_token[u0 + r];
+        t.tok[r] = r * 2 * rl + retrieval_token[u0 + r];
         t.ra[r] = slots ? slots[2 * group_medium[group[u0 + r]]] : -1;
       }
       HIP_CHECK(hipMemcpyAsync(d_sel, t.tok.data(), (size_t)nr * 4, hipMemcpyHostToDevice, s));
@@ -499,11 +531,12 @@ struct Render : RenderArgs {
   }
 
   // the batch of n rows from their descriptors: the resident batch, filled on the device
-  int assemble(const char* label, const RowDesc* host, RowDesc* dev, int n, BatchDevRows* bd) {
-    RC(model_batch_device_begin(m, n, bd));
+  // (rl: the wave's row length, row_len_for its longest row: the rows' stride in the batch and in the token indices of d_sel)
+  int assemble(const char* label, const RowDesc* host, RowDesc* dev, int n, BatchDevRows* bd, int rl) {
+    RC(model_batch_device_begin(m, n, bd, rl));
     HIP_CHECK(hipMemcpyAsync(dev, host, (size_t)n * sizeof(RowDesc), hipMemcpyHostToDevice, s));
     tic(m, label);
-    rows_kernel<<<n, RN_THREADS, 0, s>>>(dev, hist, S, cand, *bd, d_sel);
+    rows_kernel<<<n, RN_THREADS, 0, s>>>(dev, hist, rl, cand, *bd, d_sel);
     RN_LAUNCH_CHECK();
     toc(m);
     return RSYS_OK;
@@ -512,13 +545,16 @@ struct Render : RenderArgs {
   // ---- 5. one ranking forward over the n <= max_rows rows w[0 .. n): the rating head's values at their candidates go to r_masked.
   // WAVE_CACHED: the cache's candidate pass, row r on cache slot slot[r]; WAVE_ASSEMBLED: the plain forward.  `wave` numbers the kept records.
   int rank_wave(WaveKind kind, RowDesc* w, const int32_t* slot, int n, int wave) {
-    int nsel = 0;
+    int nsel = 0, live = 1;
     for (int r = 0; r < n; ++r) {
       w[r].sel0 = nsel; nsel += w[r].ncand;
       t.nc[r] = w[r].ncand; t.ra[r] = slots ? slots[2 * w[r].med + 1] : -1;
+      live = std::max(live, w[r].ncopy + w[r].ncand);
     }
+    const int rl = row_len_for(live);
     BatchDevRows bd;
-    RC(assemble(WAVE_KEYS[kind][0], w, d_rows, n, &bd));
+    RC(assemble(WAVE_KEYS[kind][0], w, d_rows, n, &bd, rl));
+    R->note_forward(kind == WAVE_CACHED ? 2 : 3, n, rl);
     if (kind == WAVE_CACHED) RC(rank_cache_candidates_rows(m, slots ? t.ra.data() : nullptr, slot, t.nc.data(), t.c_tab.data(), bd.rope_pos, d_sel, nsel, pred));
     else RC(model_infer_device(m, 1, slots ? t.ra.data() : nullptr, d_sel, nsel, pred));
     tic(m, "render_rank_scatter");
@@ -529,9 +565,12 @@ struct Render : RenderArgs {
     ++R->forwards[1];
     if (full) ++R->forwards_full[1 + kind];   // (rsys_render_request_full counts its forwards by kind: candidate rows, empty histories)
     if (keep) {
-      RC(R->keep_rows(WAVE_KEYS[kind][1], bd, n, S));
+      std::vector<int> fp(n);
+      for (int r = 0; r < n; ++r) fp[r] = w[r].fill_pos;
+      RC(R->keep_rows(WAVE_KEYS[kind][1], bd, n, S, rl, fp));
       std::vector<int32_t> hi((size_t)std::max(nsel, 1));
       HIP_CHECK(hipMemcpy(hi.data(), d_sel, (size_t)nsel * 4, hipMemcpyDeviceToHost));
+      for (int i = 0; i < nsel && rl != S; ++i) hi[i] = hi[i] / (2 * rl) * 2 * S + hi[i] % (2 * rl);   // (kept in the documented geometry r 2S + t)
       R->put(WAVE_KEYS[kind][2], hi.data(), (size_t)nsel);
       for (int r = 0; r < n; ++r) {
         const int32_t rec[7] = {w[r].user, group[w[r].user], w[r].cand0, w[r].ncand, r, wave, (int32_t)kind};   // user, group, first candidate, count, row in wave, wave (, full: kind)
@@ -562,12 +601,16 @@ struct Render : RenderArgs {
           t.crows.push_back(q); t.crow_slot.push_back(r);
         }
       }
+      int live = 1;
+      for (int r = 0; r < nw; ++r) live = std::max(live, t.sd[r].ncopy);
+      const int rl = row_len_for(live);
       BatchDevRows bd;
-      RC(assemble("render_store_rows", t.sd.data(), d_store, nw, &bd));
+      RC(assemble("render_store_rows", t.sd.data(), d_store, nw, &bd, rl));
+      R->note_forward(1, nw, rl);
       RC(rank_cache_store_rows(m, slots ? t.s_ad.data() : nullptr, t.s_nh.data(), t.s_slot.data(), t.s_tab.data()));   // (no host wait)
       ++R->forwards[1]; ++R->forwards_full[0];
       if (keep) {
-        RC(R->keep_rows("store", bd, nw, S));
+        RC(R->keep_rows("store", bd, nw, S, rl, std::vector<int>(nw, 0)));
         for (int r = 0; r < nw; ++r) {
           const int32_t rec[4] = {t.sd[r].user, r, t.sd[r].ncopy, (int32_t)(w0 / RM)};   // user, slot, events, wave
           R->put("store.rows", rec, 4);

@@ -265,6 +265,40 @@ class RecommenderModel:
         check(lib().rsys_batch_upload(self._h, C.byref(b)))
         self._keep = keep
 
+    def upload_trimmed(self, d, row_len):
+        """rsys_batch_upload_trimmed: `d` as `upload` takes it (rows of max_sequence_length columns) for inference rows whose live events
+        are a prefix; only columns [0, row_len) of every row are checked and copied, and the forwards that follow run over rows of
+        2 * row_len tokens.  row_len % 4 == 0, 4 <= row_len <= S; every column from row_len on must be padding (userid 0).  Targets and
+        masks are not read.  A trimmed batch is inference-only; `row_len == S` is `upload`."""
+        b, keep = self._c_batch(d)
+        check(lib().rsys_batch_upload_trimmed(self._h, C.byref(b), int(row_len)))
+        self._keep = keep
+
+    def _upload_rows(self, d, row_len):
+        if row_len is None:
+            self.upload(d)
+        else:
+            self.upload_trimmed(d, row_len)
+
+    @property
+    def batch_row_length(self):
+        """interactions per row of the resident batch: S after an ordinary upload, row_len after `upload_trimmed`, 0 without a batch"""
+        n = C.c_int32()
+        check(lib().rsys_batch_row_length(self._h, C.byref(n)))
+        return n.value
+
+    @property
+    def serving_trim(self):
+        """rsys_serving_trim_set: every forward of `render_request` / `render_request_full` runs at the length of its longest live row
+        (whole 64-token tiles) instead of max_sequence_length.  Default off."""
+        on = C.c_int32()
+        check(lib().rsys_serving_trim_get(self._h, C.byref(on)))
+        return bool(on.value)
+
+    @serving_trim.setter
+    def serving_trim(self, on):
+        check(lib().rsys_serving_trim_set(self._h, 1 if on else 0))
+
     @property
     def can_prefetch(self):
         """rsys_batch_prefetch / rsys_batch_swap: the next batch staged and copied beside the running step (replicated table)"""
@@ -343,11 +377,12 @@ class RecommenderModel:
             return out
         raise AssertionError(task)
 
-    def inference_select(self, d, task, token_index, adapters=None):
+    def inference_select(self, d, task, token_index, adapters=None, row_len=None):
         """The inference forward reporting only the tokens a server reads (embed.py:147-161): `token_index` = flat token indices
         in [0, rows * 2S).  "retrieval" -> (n, D) trunk outputs, "ranking" -> (n,) rating-head values (computed on those rows only).
-        `adapters`: one adapter-bank slot per batch row (-1 = the base model) or one slot for every row; None = the model as it is."""
-        self.upload(d)
+        `adapters`: one adapter-bank slot per batch row (-1 = the base model) or one slot for every row; None = the model as it is.
+        `row_len`: run the rows trimmed to that many interactions (`upload_trimmed`); `token_index` keeps the geometry row * 2S + token."""
+        self._upload_rows(d, row_len)
         idx = np.ascontiguousarray(np.asarray(token_index).reshape(-1), np.int32)
         D = self.config["embed_dim"]
         t = {"retrieval": 0, "ranking": 1}[task]
@@ -378,20 +413,22 @@ class RecommenderModel:
         check(lib().rsys_rank_cache_reserve(self._h, int(n_slots)))
         self.rank_cache_slots = int(n_slots)
 
-    def rank_cache_store(self, d, n_hist, slots, adapters=None):
+    def rank_cache_store(self, d, n_hist, slots, adapters=None, row_len=None):
         """The trunk forward of the history-only rows `d` (row r: n_hist[r] events, token_mask_ids 0, rope_input_pos 0 .. n_hist[r] - 1);
-        every layer's K / V of row r's history tokens goes to cache slot slots[r].  `adapters` as in `inference_select`."""
-        self.upload(d)
+        every layer's K / V of row r's history tokens goes to cache slot slots[r].  `adapters` and `row_len` (>= every n_hist) as in
+        `inference_select`; a slot stored from a trimmed row is the slot the full row stores."""
+        self._upload_rows(d, row_len)
         rows, ad = self._row_slots(d, adapters)
         nh = np.ascontiguousarray(np.asarray(n_hist).reshape(-1), np.int32); sl = np.ascontiguousarray(np.asarray(slots).reshape(-1), np.int32)
         if nh.size != rows or sl.size != rows:
             raise ValueError(f"rank_cache_store: {nh.size} history lengths and {sl.size} slots for {rows} batch rows")
         check(lib().rsys_rank_cache_store(self._h, None if ad is None else ad.ctypes.data, nh.ctypes.data, sl.ctypes.data))
 
-    def rank_cache_candidates(self, d, slots, n_cand, adapters=None):
+    def rank_cache_candidates(self, d, slots, n_cand, adapters=None, row_len=None):
         """The trunk forward of the candidate rows `d` (row r: n_cand[r] candidates at events 0 .. n_cand[r] - 1) against the histories
-        cached in slots[r]; returns the rating head at the candidates' action tokens, (sum n_cand,) float32 in row order."""
-        self.upload(d)
+        cached in slots[r]; returns the rating head at the candidates' action tokens, (sum n_cand,) float32 in row order.  `row_len`
+        (>= every n_cand): the rows run trimmed, against slots stored from rows of any length."""
+        self._upload_rows(d, row_len)
         rows, ad = self._row_slots(d, adapters)
         sl = np.ascontiguousarray(np.asarray(slots).reshape(-1), np.int32); nc = np.ascontiguousarray(np.asarray(n_cand).reshape(-1), np.int32)
         if nc.size != rows or sl.size != rows:
@@ -935,9 +972,11 @@ class RecommenderModel:
 
     def debug_get(self, key, rows):
         """Bit-exact read-back of an index-path array of the last forward (rsys_debug_get; parity tests)."""
-        S = self.config["max_sequence_length"]; D = self.config["embed_dim"]; n = rows * S
+        S = self.batch_row_length or self.config["max_sequence_length"]; D = self.config["embed_dim"]; n = rows * S   # (a trimmed batch: its own row length)
         V = self.config["vocab_sizes"]["0_matchedid"] + self.config["vocab_sizes"]["1_matchedid"]
-        if key == "npos":
+        if key == "forward.tokens":
+            out = np.empty(1, np.int64)
+        elif key == "npos":
             out = np.empty(4, np.int32)
         elif key in ("top.n", "top.cap"):
             out = np.empty(1, np.int32)
@@ -980,6 +1019,11 @@ class RecommenderModel:
             out = np.empty(n, np.float32 if is_f32 else np.int32)
         check(lib().rsys_debug_get(self._h, key.encode(), out.ctypes.data, out.nbytes))
         return out
+
+    @property
+    def forward_tokens(self):
+        """tokens the last trunk forward ran over (rsys_debug_get "forward.tokens"): rows * 2 * the resident batch's row length"""
+        return int(self.debug_get("forward.tokens", 0)[0])
 
     def param_checksum(self):
         """[fp64 sum, fp64 sum of squares, low / high 32 bits of a position-weighted integer sum of the bit patterns] of this rank's flat

@@ -124,10 +124,30 @@ def _selected_tokens(users, task, S, max_user_len):
     return index, counts
 
 
-def predict(model, users, task, medium, max_user_len=None, max_ranking_items=None):
+def trim_length(live, S):
+    """The row length a forward whose longest row has `live` live columns runs at under `trim=True`: whole 64-token attention tiles
+    (32 interactions), clamped to the model's S."""
+    return min(int(S), 32 * max(1, -(-int(live) // 32)))
+
+
+def live_columns(d):
+    """columns of the longest live prefix of the rows `build_batch` / `_fill_row` filled (live events carry userid != 0, the rest is padding)"""
+    uid = np.asarray(d["userid"])
+    uid = uid.reshape(-1, uid.shape[-1])
+    cols = np.flatnonzero((uid != 0).any(axis=0))
+    return int(cols[-1]) + 1 if cols.size else 0
+
+
+def _row_len(d, S, trim):
+    return trim_length(live_columns(d), S) if trim else None
+
+
+def predict(model, users, task, medium, max_user_len=None, max_ranking_items=None, trim=False):
     """embed.py:74-161 on the HIP model (`model.config["forward"]` semantics = inference): sequence length of the request =
     the model's `max_sequence_length` (retrieval: all of it is history + query; ranking: split between history and candidates).
-    A model built by `get_models` (it has an `adapter_slots` map) runs every row with the adapter of "{medium}.{task}"."""
+    A model built by `get_models` (it has an `adapter_slots` map) runs every row with the adapter of "{medium}.{task}".
+    `trim=True`: the forward runs at `trim_length` of the batch's longest live row instead of S (the padding behind it is dropped, which
+    is exact: no live token attends it)."""
     S = model.config["max_sequence_length"]
     max_user_len, max_ranking_items = _request_lengths(model, task, max_user_len, max_ranking_items)
     d = build_batch(users, task, medium, model.config["vocab_sizes"]["0_matchedid"], max_user_len, max_ranking_items)
@@ -140,10 +160,11 @@ def predict(model, users, task, medium, max_user_len=None, max_ranking_items=Non
     if not index:
         return [{key: []} for _ in users]
     slots = getattr(model, "adapter_slots", None)
+    kw = dict(row_len=_row_len(d, S, trim)) if trim else {}
     if slots:
-        vals = model.inference_select(d, task, index, adapters=[slots[key]] * len(users))
+        vals = model.inference_select(d, task, index, adapters=[slots[key]] * len(users), **kw)
     else:
-        vals = model.inference_select(d, task, index)
+        vals = model.inference_select(d, task, index, **kw)
     out, at = [], 0
     for c in counts:
         out.append({key: (vals[at].tolist() if task == "retrieval" else vals[at:at + c].tolist())}); at += c
@@ -165,13 +186,14 @@ def rank_cache_plan(n_hist, n_cand, S, max_rows):
     return waves
 
 
-def predict_ranking_full(model, users, medium):
+def predict_ranking_full(model, users, medium, trim=False):
     """`predict(model, users, "ranking", medium)` on the reference's row (embed.py:74-161 with max_user_len = S): every user is ranked
     on its newest S - 1 history events, whatever the number of candidates, instead of the newest S // 2 - 1 that share a row with the
     candidates.  Each history is tokenised and projected once and runs once (one `rank_cache_store` per wave of `max_rows` users);
     the candidates run against the cached K / V in rows of up to S (a user's candidates may span rows, several users' rows share a
     forward).  Users with an empty history go through `predict`, one row per chunk of S - S // 2 candidates as `render` cuts them, so
-    their values are what `render` gives today.  Returns what `predict` returns, for any number of candidates."""
+    their values are what `render` gives today.  Returns what `predict` returns, for any number of candidates.  `trim=True`: every
+    store and candidate forward runs at `trim_length` of its longest row; slots, waves and chunks are unchanged."""
     S = model.config["max_sequence_length"]
     n0 = model.config["vocab_sizes"]["0_matchedid"]
     key = f"{medium}.ranking"
@@ -183,7 +205,7 @@ def predict_ranking_full(model, users, medium):
         # (with an empty history they depend on where the chunks are cut: candidate 0 of a row carries mask id 0)
         items, vals = users[i]["ranking_items"], []
         for c0 in range(0, len(items), chunk):
-            vals += predict(model, [dict(users[i], ranking_items=items[c0:c0 + chunk])], "ranking", medium)[0][key]
+            vals += predict(model, [dict(users[i], ranking_items=items[c0:c0 + chunk])], "ranking", medium, trim=trim)[0][key]
         out[i] = {key: vals}
     full = [i for i, h in enumerate(hists) if h]
     for i in full:
@@ -202,7 +224,8 @@ def predict_ranking_full(model, users, medium):
         d = _empty_rows(len(store), S)
         for row, (k, _, nh) in enumerate(store):
             _fill_row(d, row, hists[full[k]], nh, users[full[k]]["user"], n0, False)
-        model.rank_cache_store(d, [s[2] for s in store], [s[1] for s in store], adapters=adapter)
+        kw = dict(row_len=_row_len(d, S, True)) if trim else {}
+        model.rank_cache_store(d, [s[2] for s in store], [s[1] for s in store], adapters=adapter, **kw)
         vals = {k: [] for k, _, _ in store}
         for rows in batches:
             d = _empty_rows(len(rows), S)
@@ -212,7 +235,8 @@ def predict_ranking_full(model, users, medium):
                 _fill_row(d, row, seq, 0, u["user"], n0, False)
                 d["rope_input_pos"][row, :] = nh     # (the reference's value for every candidate; the call sets the positions itself from the
                                                      #  slot, so this only keeps the uploaded row equal to the reference's candidate events)
-            v = model.rank_cache_candidates(d, [r[1] for r in rows], [r[3] for r in rows], adapters=adapter)
+            kw = dict(row_len=_row_len(d, S, True)) if trim else {}
+            v = model.rank_cache_candidates(d, [r[1] for r in rows], [r[3] for r in rows], adapters=adapter, **kw)
             at = 0
             for k, _, _, n, _ in rows:
                 vals[k] += v[at:at + n].tolist(); at += n
@@ -221,7 +245,7 @@ def predict_ranking_full(model, users, medium):
     return out
 
 
-def predict_mixed(model, requests, task, max_user_len=None, max_ranking_items=None):
+def predict_mixed(model, requests, task, max_user_len=None, max_ranking_items=None, trim=False):
     """`predict` for users of both media in ONE forward: `requests` = [(user, medium), ...]; row i of the batch is the row
     `build_batch([user_i], task, medium_i, ...)` builds and runs with the adapter slot `model.adapter_slots[f"{medium_i}.{task}"]`
     (embed.jl:5-84 keeps one queue per (medium, task) on one GPU; single-user inference is launch-bound, so sharing a forward
@@ -241,7 +265,8 @@ def predict_mixed(model, requests, task, max_user_len=None, max_ranking_items=No
     keys = [f"{int(m)}.{task}" for _, m in requests]
     if not index:
         return [{k: []} for k in keys]
-    vals = model.inference_select(d, task, index, adapters=[slots[k] for k in keys])
+    kw = dict(row_len=_row_len(d, S, True)) if trim else {}
+    vals = model.inference_select(d, task, index, adapters=[slots[k] for k in keys], **kw)
     out, at = [], 0
     for k, c in zip(keys, counts):
         out.append({k: (vals[at].tolist() if task == "retrieval" else vals[at:at + c].tolist())}); at += c
@@ -650,7 +675,7 @@ def render_items(model, states, pagination):
     return [(pages[g], int(totals[g])) for g in range(len(states))]
 
 
-def render(model, states, pagination, registry=None, max_ranking_items=None, full_history=False, exact=False):
+def render(model, states, pagination, registry=None, max_ranking_items=None, full_history=False, exact=False, trim=False):
     """render.jl `render(state, pagination)` (lines 437-474) without the card rendering, for a list of states: `retrieval`, the page's
     slice of at most 1024 candidates, the ranking forward (`predict(..., "ranking")` in chunks of at most `max_ranking_items` candidates,
     default the model's S - S // 2; candidates are masked from each other, so chunking does not change the result of a user with a
@@ -662,7 +687,8 @@ def render(model, states, pagination, registry=None, max_ranking_items=None, ful
     clamped to the retrieved list (render.jl throws a BoundsError).  By default total = min(admissible items, 8192), the retrieval cap, a
     page past rank 8192 is empty and every state needs a user; both are closed by `exact=True` / `render_items`: the page's candidates
     then come from `retrieval_window`, so total is the number of admissible items and every offset below it has a page (ranking and
-    reranking unchanged), and states without users go through `render_items` -- every state render.jl renders."""
+    reranking unchanged), and states without users go through `render_items` -- every state render.jl renders.  `trim=True`: the
+    ranking forwards run trimmed (`predict(..., trim=True)` / `predict_ranking_full(..., trim=True)`)."""
     pags = [pagination] * len(states) if isinstance(pagination, dict) else list(pagination)
     if exact:
         for pg in pags:
@@ -675,13 +701,13 @@ def render(model, states, pagination, registry=None, max_ranking_items=None, ful
         rest = [j for j, st in enumerate(states) if st["users"]]
         if rest:
             for j, res in zip(rest, _render_states(model, [states[j] for j in rest], [pags[j] for j in rest], registry, max_ranking_items,
-                                                  full_history, True)):
+                                                  full_history, True, trim)):
                 out[j] = res
         return out
-    return _render_states(model, states, pags, registry, max_ranking_items, full_history, False)
+    return _render_states(model, states, pags, registry, max_ranking_items, full_history, False, trim)
 
 
-def _render_states(model, states, pags, registry, max_ranking_items, full_history, exact):
+def _render_states(model, states, pags, registry, max_ranking_items, full_history, exact, trim=False):
     """`render` for states with users; exact: the page's candidates are the window of `retrieval_window` instead of a slice of the top 8192"""
     S = model.config["max_sequence_length"]
     max_user_len = S // 2
@@ -716,14 +742,14 @@ def _render_states(model, states, pags, registry, max_ranking_items, full_histor
             cand = w[1]
             if full_history:
                 reqs = [dict(u["user"], ranking_items=[int(x) for x in cand]) for u in st["users"]]
-                for u, r in zip(st["users"], predict_ranking_full(model, reqs, m)):
+                for u, r in zip(st["users"], predict_ranking_full(model, reqs, m, trim=trim)):
                     u.setdefault("embeds", {})[f"{m}.ranking"] = np.asarray(r[f"{m}.ranking"], np.float32)
                 continue
             for u in st["users"]:
                 vals = []
                 for c0 in range(0, cand.size, chunk):
                     req = dict(u["user"], ranking_items=[int(x) for x in cand[c0:c0 + chunk]])
-                    vals += predict(model, [req], "ranking", m, max_user_len, S - max_user_len)[0][f"{m}.ranking"]
+                    vals += predict(model, [req], "ranking", m, max_user_len, S - max_user_len, trim=trim)[0][f"{m}.ranking"]
                 u.setdefault("embeds", {})[f"{m}.ranking"] = np.asarray(vals, np.float32)
         cand = [w[1] for w in items]
         q, group, rm, hist, pen = rank_arrays(sub, cand)
@@ -857,17 +883,26 @@ def render_full_forwards(n_hist, n_cand, S, max_rows):
     return len(waves), sum(len(b) for _, b in waves), -(-len(empty) // max_rows)
 
 
-def render_users(model, states, pagination, registry=None, full_history=False):
+def render_users(model, states, pagination, registry=None, full_history=False, trim=False):
     """`render` from raw histories in ONE device call (rsys_render_request): the same states, but users need no "embeds" -- the
     retrieval forward, `retrieval`, the page window, the ranking forward (every chunk row of every user, both media, in waves of the
     model's max_rows) and `ranking` + `reranking` run back to back on the device; only the pages and the totals come back.  A model built
     by `get_models` runs every row with the adapter of its "{medium}.{task}"; a plain model runs the base.  Returns one (ids of the
     page, total) pair per state, as `render`.  `full_history=True` (rsys_render_request_full): the ranking forward of
     `render(..., full_history=True)` inside the same call -- every user ranked on its newest S - 1 events through the per-user K/V cache,
-    whose store rows the device cuts from the retrieval rows it already holds; no ranking prefix is built or uploaded."""
+    whose store rows the device cuts from the retrieval rows it already holds; no ranking prefix is built or uploaded.
+    `trim=True` (rsys_serving_trim_set for the length of the call): every forward of the pipeline runs at the length of its longest live
+    row in whole 64-token tiles; waves, chunks, slots and outputs are unchanged."""
     if not states:
         return []
     args = render_pack(states, pagination, model.config["max_sequence_length"], model.config["vocab_sizes"]["0_matchedid"], registry,
                        getattr(model, "adapter_slots", None), full_history)
-    pages, totals = (model.render_request_full if full_history else model.render_request)(**args)
+    before = model.serving_trim if trim else False
+    if trim:
+        model.serving_trim = True
+    try:
+        pages, totals = (model.render_request_full if full_history else model.render_request)(**args)
+    finally:
+        if trim:
+            model.serving_trim = before
     return [(pages[g], int(totals[g])) for g in range(len(states))]

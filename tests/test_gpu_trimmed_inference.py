@@ -1,0 +1,417 @@
+"""GPU: inference on trimmed rows (rsys_batch_upload_trimmed, rsys_serving_trim_set, serve.* trim=True).  Every case runs
+the same rows trimmed and untrimmed on one model, checks through "forward.tokens" that the trimmed forward really ran over
+rows * 2 * row_len tokens, and compares the values.  The cases, lengths and bounds are the ones DESIGN.md 4za records with their measured
+differences."""
+import ctypes as C
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, HERE)
+import _trim_util as tu  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+S = tu.S_TEST
+ARG, STATE = -1, -3
+TASK_W = [0.05, 0.2, 0.3, 0.25]
+_MODELS = {}
+
+
+def relerr(a, b):
+    a = np.asarray(a, np.float64); b = np.asarray(b, np.float64)
+    return float(np.abs(a - b).max() / max(np.abs(b).max(), 1e-30))
+
+
+@pytest.fixture(scope="module")
+def models():
+    """one model per (kind, dtype) for the whole module; closed at the end"""
+    def get(kind, dtype):
+        if (kind, dtype) not in _MODELS:
+            cfg, V = tu.config()
+            _MODELS[(kind, dtype)] = (cfg, V) + tu.make_model(cfg, kind, dtype)
+        return _MODELS[(kind, dtype)]
+    yield get
+    for v in _MODELS.values():
+        v[2].close()
+    _MODELS.clear()
+
+
+def _same(trimmed, full, ref, dtype, what):
+    """`equals untrimmed`: measured 0.0 at these sizes in both dtypes, so equality is asserted; the errors against the
+    fp64 oracle are printed beside it and hold the project's bounds (fp32 < 1e-4; bf16: trimmed <= 1.5 x untrimmed)"""
+    trimmed, full = np.asarray(trimmed, np.float32), np.asarray(full, np.float32)
+    diff = float(np.abs(trimmed - full).max()) if full.size else 0.0
+    line = f"{what} [{dtype}] max |trimmed - untrimmed| {diff:.3e}"
+    if ref is not None:
+        e_t, e_f = relerr(trimmed, ref), relerr(full, ref)
+        line += f"  oracle error: trimmed {e_t:.3e} untrimmed {e_f:.3e}"
+    print(line)
+    if ref is not None:
+        if dtype == "fp32":
+            assert e_t < 1e-4, (what, e_t)
+        else:
+            assert e_t <= 1.5 * e_f, (what, e_t, e_f)
+    assert np.array_equal(trimmed, full), (what, diff)
+
+
+def _retrieval_users(rng, lives, V):
+    return [tu.user_with_history(rng, live - 1, []) for live in lives]
+
+
+# ---------------------------------------------------------------- 1. retrieval embedding and the full tensor
+@pytest.mark.parametrize("dtype", ["fp32", "bf16"])
+@pytest.mark.parametrize("kind", ["base", "bank"])
+def test_retrieval_rows_alone_and_mixed(models, kind, dtype):
+    from recommendersystem_amd import serve
+    cfg, V, model, P, adapters = models(kind, dtype)
+    rng = np.random.default_rng(11)
+    medium = 1
+    key = f"{medium}.retrieval"
+    for lives in [(4,), (32,), (33,), (91,), (128,), (4, 91)]:
+        users = _retrieval_users(rng, lives, V)
+        rl = serve.trim_length(max(lives), S)
+        assert rl == tu.LIVE_TO_ROW_LEN[max(lives)]
+        full = [r[key] for r in serve.predict(model, users, "retrieval", medium)]
+        tok_full = model.forward_tokens
+        got = [r[key] for r in serve.predict(model, users, "retrieval", medium, trim=True)]
+        assert model.forward_tokens == len(users) * 2 * rl and tok_full == len(users) * 2 * S
+        assert model.batch_row_length == rl
+        ref = tu.oracle_predict(cfg, P, adapters, kind, users, "retrieval", medium)
+        _same(got, full, ref, dtype, f"retrieval {kind} live {lives}")
+    model.upload(serve.build_batch(users, "retrieval", medium, V[0], S, 0))      # (leave the shared model on full rows)
+
+
+@pytest.mark.parametrize("dtype", ["fp32", "bf16"])
+def test_full_tensor_and_row_len_36(models, dtype):
+    """rsys_infer on a trimmed batch returns [rows][2 row_len][D] = the leading tokens of the untrimmed tensor, at the live tokens; the
+    C-level row_len 36 for 33 live columns gives T = 72: a ragged last attention tile, no multiple of 32"""
+    from recommendersystem_amd import _lib, serve
+    cfg, V, model, P, adapters = models("base", dtype)
+    D = cfg["embed_dim"]
+    rng = np.random.default_rng(12)
+    users = _retrieval_users(rng, (33, 4), V)
+    d = serve.build_batch(users, "retrieval", 0, V[0], S, 0)
+    whole = model.inference_forward(d, "retrieval")
+    for rl in (36, 64):
+        model.upload_trimmed(d, rl)
+        out = np.full((2, 2 * rl, D), 7.0, np.float32)
+        assert _lib.lib().rsys_infer(model._h, 0, out.ctypes.data, out.size) == 0
+        assert model.forward_tokens == 2 * 2 * rl
+        for r, live in enumerate((33, 4)):
+            _same(out[r, :2 * live], whole[r, :2 * live], None, dtype, f"rsys_infer row_len {rl} row {r}")
+        bad = np.empty((2, 2 * S, D), np.float32)
+        assert _lib.lib().rsys_infer(model._h, 0, bad.ctypes.data, bad.size) == ARG        # n is checked against the trimmed rows
+        # rsys_infer_select keeps the caller's geometry r * 2S + t
+        idx = np.array([2 * 32, 2 * S + 2 * 3], np.int32)
+        sel = model.inference_select(d, "retrieval", idx, row_len=rl)
+        _same(sel, whole.reshape(-1, D)[idx], None, dtype, f"rsys_infer_select row_len {rl}")
+        act = model.debug_get("tokens.userid", 2)                                          # a key sized by rows * S follows the row length
+        assert act.size == 2 * 2 * rl
+    model.upload(d)
+
+
+# ---------------------------------------------------------------- 2. ranking rows
+@pytest.mark.parametrize("dtype", ["fp32", "bf16"])
+@pytest.mark.parametrize("kind", ["base", "bank"])
+def test_ranking_rows(models, kind, dtype):
+    from recommendersystem_amd import serve
+    cfg, V, model, P, adapters = models(kind, dtype)
+    rng = np.random.default_rng(13)
+    medium = 0
+    key = f"{medium}.ranking"
+    for nh, nc, rl in [(5, 3, 32), (31, 33, 64)]:
+        user = tu.user_with_history(rng, nh, [int(x) for x in rng.choice(np.arange(1, V[medium]), nc, replace=False)])
+        full = serve.predict(model, [user], "ranking", medium)[0][key]
+        got = serve.predict(model, [user], "ranking", medium, trim=True)[0][key]
+        assert model.forward_tokens == 2 * rl and len(got) == nc
+        ref = tu.oracle_predict(cfg, P, adapters, kind, [user], "ranking", medium)[0]
+        _same(got, full, ref, dtype, f"ranking {kind} nh {nh} nc {nc}")
+    model.upload(serve.build_batch([user], "ranking", medium, V[0], S // 2, S - S // 2))
+
+
+# ---------------------------------------------------------------- 3. rows with different adapter slots in one trimmed batch
+@pytest.mark.parametrize("dtype", ["fp32", "bf16"])
+def test_bank_rows_with_their_own_slots(models, dtype):
+    from recommendersystem_amd import serve
+    cfg, V, model, P, adapters = models("bank", dtype)
+    rng = np.random.default_rng(14)
+    users = _retrieval_users(rng, (20, 33, 7), V)
+    d = serve.build_batch(users, "retrieval", 1, V[0], S, 0)
+    index, _ = serve._selected_tokens(users, "retrieval", S, S)
+    slots = [model.adapter_slots["1.retrieval"], model.adapter_slots["0.retrieval"], -1]
+    full = model.inference_select(d, "retrieval", index, adapters=slots)
+    got = model.inference_select(d, "retrieval", index, adapters=slots, row_len=64)
+    assert model.forward_tokens == 3 * 2 * 64
+    _same(got, full, None, dtype, "bank rows, slots (1.retrieval, 0.retrieval, base)")
+    base = model.inference_select(d, "retrieval", index, adapters=[-1, -1, -1], row_len=64)
+    assert not np.array_equal(base[0], got[0]) and np.array_equal(base[2], got[2])         # the slots were applied, row by row
+    mixed = serve.predict_mixed(model, [(users[0], 1), (users[1], 0)], "retrieval", trim=True)
+    plain = serve.predict_mixed(model, [(users[0], 1), (users[1], 0)], "retrieval")
+    _same([mixed[0]["1.retrieval"], mixed[1]["0.retrieval"]], [plain[0]["1.retrieval"], plain[1]["0.retrieval"]], None, dtype, "predict_mixed")
+    model.upload(d)
+
+
+# ---------------------------------------------------------------- 4. the ranking K/V cache
+def _hist_rows(users):
+    from recommendersystem_amd import serve
+    cfg, V = tu.config()
+    d = serve._empty_rows(len(users), S)
+    hs = [serve._history(u, S) for u in users]
+    for row, (u, h) in enumerate(zip(users, hs)):
+        serve._fill_row(d, row, h, len(h), u["user"], V[0], False)
+    return d, [len(h) for h in hs]
+
+
+def _cand_rows(user, medium, n):
+    from recommendersystem_amd import serve
+    cfg, V = tu.config()
+    d = serve._empty_rows(1, S)
+    serve._fill_row(d, 0, [serve.make_item(user["timestamp"], medium, c) for c in user["ranking_items"][:n]], 0, user["user"], V[0], False)
+    return d
+
+
+@pytest.mark.parametrize("dtype", ["fp32", "bf16"])
+@pytest.mark.parametrize("kind", ["base", "bank"])
+def test_rank_cache(models, kind, dtype):
+    from recommendersystem_amd import serve
+    cfg, V, model, P, adapters = models(kind, dtype)
+    rng = np.random.default_rng(15)
+    medium = 1
+    key = f"{medium}.ranking"
+    cands = lambda n: [int(x) for x in rng.choice(np.arange(1, V[medium]), n, replace=False)]
+    users = [tu.user_with_history(rng, 5, cands(3)), tu.user_with_history(rng, 0, cands(4)), tu.user_with_history(rng, 40, cands(70)),
+             tu.user_with_history(rng, 31, cands(33))]
+    full = serve.predict_ranking_full(model, users, medium)
+    got = serve.predict_ranking_full(model, users, medium, trim=True)
+    for i, u in enumerate(users):
+        _same(got[i][key], full[i][key], None, dtype, f"predict_ranking_full {kind} user {i} (nh {len(serve._history(u, S))})")
+    # a slot stored from a trimmed row holds what the full row stores; trimmed and untrimmed calls mix freely on one slot
+    ad = model.adapter_slots[key] if kind == "bank" else None
+    u = users[2]
+    dh, nh = _hist_rows([u])
+    dc = _cand_rows(u, medium, 33)
+    model.rank_cache_store(dh, nh, [0], adapters=ad)
+    kv_full = [model.rank_cache_get(l, 0, nh[0]) for l in range(cfg["num_layers"])]
+    vals_ff = model.rank_cache_candidates(dc, [0], [33], adapters=ad)
+    vals_ft = model.rank_cache_candidates(dc, [0], [33], adapters=ad, row_len=64)          # stored full, candidates trimmed
+    assert model.forward_tokens == 2 * 64
+    model.rank_cache_store(dh, nh, [1], adapters=ad, row_len=64)                            # 40 events in a row of 64
+    assert model.forward_tokens == 2 * 64
+    for l in range(cfg["num_layers"]):
+        assert np.array_equal(kv_full[l], model.rank_cache_get(l, 1, nh[0])), l
+    vals_tf = model.rank_cache_candidates(dc, [1], [33], adapters=ad)                       # stored trimmed, candidates full
+    vals_tt = model.rank_cache_candidates(dc, [1], [33], adapters=ad, row_len=64)
+    for name, v in (("full/trimmed", vals_ft), ("trimmed/full", vals_tf), ("trimmed/trimmed", vals_tt)):
+        _same(v, vals_ff, None, dtype, f"rank cache {kind} store/candidates {name}")
+    # a history longer than the trimmed candidate row: 40 events, 3 candidates, alone -> candidate rows of 32 columns whose every column
+    # sits at rope_input_pos 40 (a position is not a column: its bound is the RoPE table's, as in the ordinary upload)
+    short = dict(users[2], ranking_items=users[2]["ranking_items"][:3])
+    one_full = serve.predict_ranking_full(model, [short], medium)[0][key]
+    one_trim = serve.predict_ranking_full(model, [short], medium, trim=True)[0][key]
+    assert model.forward_tokens == 2 * 32
+    _same(one_trim, one_full, None, dtype, f"predict_ranking_full {kind}, 40 events and 3 candidates alone")
+    _same(one_full, full[2][key][:3], None, dtype, f"predict_ranking_full {kind}, the same candidates in the four-user call")
+    dc3 = _cand_rows(short, medium, 3)
+    dc3["rope_input_pos"][0, :] = nh[0]                                                      # the reference's candidate row: position = n_hist
+    v3_full = model.rank_cache_candidates(dc3, [0], [3], adapters=ad)
+    v3_trim = model.rank_cache_candidates(dc3, [0], [3], adapters=ad, row_len=32)
+    assert model.forward_tokens == 2 * 32 and nh[0] == 40
+    _same(v3_trim, v3_full, None, dtype, f"rank cache {kind} candidates at position n_hist 40 in a row of 32")
+    _same(v3_full, vals_ff[:3], None, dtype, f"rank cache {kind} 3 of the 33 candidates")
+    # the counts are checked against the trimmed rows
+    from recommendersystem_amd import _lib
+    i32 = lambda *x: np.array(x, np.int32)
+    out = np.zeros(2 * S, np.float32)
+    model.upload_trimmed(dh, 64)
+    assert _lib.lib().rsys_rank_cache_store(model._h, None, i32(65).ctypes.data, i32(0).ctypes.data) == ARG
+    model.upload_trimmed(dc, 64)
+    assert _lib.lib().rsys_rank_cache_candidates(model._h, None, i32(1).ctypes.data, i32(65).ctypes.data, out.ctypes.data) == ARG
+    assert _lib.lib().rsys_rank_cache_candidates(model._h, None, i32(1).ctypes.data, i32(64).ctypes.data, out.ctypes.data) == 0
+    model.upload(dh)
+
+
+# ---------------------------------------------------------------- 5. the map-width edge, max_sequence_length 2048
+@pytest.mark.parametrize("dtype", ["fp32", "bf16"])
+def test_map_width_edge_at_2048(tmp_path, dtype):
+    """A model created with S = 2048 (64-bit tile-map words, arrays sized for them): 1000 events run at row_len 1024 = 32 tiles, the
+    narrow maps on the wide arrays; 1030 events at row_len 1056 = 33 tiles, the wide maps.  Each alone, against untrimmed, in a child
+    process as tests/_sequence_2048_worker.py runs."""
+    out = str(tmp_path / "edge.npz")
+    root = os.path.dirname(HERE)
+    r = subprocess.run([sys.executable, os.path.join(HERE, "_trim_2048_worker.py"), out, dtype, root], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    z = np.load(out)
+    for n, rl in ((1000, 1024), (1030, 1056)):
+        assert int(z[f"tokens_{n}"]) == 2 * rl and int(z[f"tokens_full_{n}"]) == 2 * 2048
+        _same(z[f"trim_{n}"], z[f"full_{n}"], None, dtype, f"S 2048, {n} events, row_len {rl}")
+
+
+# ---------------------------------------------------------------- 6. the render pipelines
+_COLS = ("time", "userid", "token_mask_ids", "gender", "source", "matchedid", "status", "rating", "progress", "rope_input_pos")
+KEPT_ARRAYS = {False: tuple(f"batch.{c}" for c in _COLS),
+               True: tuple(f"{b}.{c}" for b in ("batch", "store", "cand") for c in _COLS) + ("cand.token_index",)}
+
+
+@pytest.mark.parametrize("dtype", ["fp32", "bf16"])
+@pytest.mark.parametrize("full_history", [False, True])
+def test_render_pipelines(full_history, dtype):
+    """render_users(trim=True) against trim=False on the states of tests/test_gpu_render_request.py (both media, several users in a state,
+    a user with an empty history, one with a history longer than a ranking row keeps): pages, totals, "forwards" and "queries" equal;
+    "forward_rows" shows the rule of rsys_serving_trim_set for every forward, and row_len < S somewhere."""
+    import test_gpu_render_request as rq
+    from recommendersystem_amd import serve
+    cfg, model, V = rq._model("bank", dtype)
+    Sm = cfg["max_sequence_length"]
+    rq._tables(model, V)
+    states, pags, registry = rq._request()
+    states[0]["users"][0]["user"]["items"] = []                        # a user with an empty history
+    model.render_keep(True)
+    res, kept = {}, {}
+    for trim in (False, True):
+        res[trim] = serve.render_users(model, states, pags, registry, full_history=full_history, trim=trim)
+        kept[trim] = {k: model.render_kept(k).copy() for k in ("forwards", "queries", "forward_rows", "r_masked", "token_index") + KEPT_ARRAYS[full_history]}
+        assert model.serving_trim is False
+    kept_rows = model.render_kept("rows").copy()
+    kept_store = model.render_kept("store.rows").copy() if full_history else None
+    for (pa, ta), (pb, tb) in zip(res[False], res[True]):
+        assert np.array_equal(pa, pb) and ta == tb
+    assert np.array_equal(kept[False]["forwards"], kept[True]["forwards"])
+    _same(kept[True]["queries"], kept[False]["queries"], None, dtype, f"render queries full_history={full_history}")
+    _same(kept[True]["r_masked"], kept[False]["r_masked"], None, dtype, f"render r_masked full_history={full_history}")
+    for k in ("token_index",) + KEPT_ARRAYS[full_history]:              # the kept batches are the switch-off call's: shapes, geometry and values
+        assert np.array_equal(kept[False][k], kept[True][k]), k
+    fr_off, fr_on = kept[False]["forward_rows"].reshape(-1, 3), kept[True]["forward_rows"].reshape(-1, 3)
+    assert len(fr_on) == len(fr_off) == int(kept[True]["forwards"].sum())
+    assert np.array_equal(fr_off[:, :2], fr_on[:, :2]) and (fr_off[:, 2] == Sm).all()
+    assert (fr_on[:, 2] % 32 == 0).all() and (fr_on[:, 2] <= Sm).all() and (fr_on[:, 2] < Sm).any()
+    # the rule, forward by forward, for the retrieval waves: min(S, 32 ceil(longest live row / 32)) over the wave's users
+    args = serve.render_pack(states, pags, Sm, V[0], registry, model.adapter_slots, full_history)
+    live = args["retrieval_token"] // 2 + 1
+    waves = [fr for fr in fr_on if fr[0] == 0]
+    for w, fr in enumerate(waves):
+        rows = live[w * model.max_rows:(w + 1) * model.max_rows]
+        assert fr[1] == len(rows) and fr[2] == serve.trim_length(int(rows.max()), Sm), (w, fr)
+    # ... and for the ranking forwards, from the kept row records: a row's live columns are its history columns + its candidates
+    desc = np.asarray(args["user_desc"]).reshape(-1, 4)
+    recs = kept_rows.reshape(-1, 7 if full_history else 6)
+    by_stage = {st: [int(fr[2]) for fr in fr_on if fr[0] == st] for st in (1, 2, 3)}
+    if full_history:
+        store = kept_store.reshape(-1, 4)                               # user, slot, events, wave
+        want1 = [serve.trim_length(int(store[store[:, 3] == w][:, 2].max()), Sm) for w in sorted(set(store[:, 3].tolist()))]
+        cached, empty = recs[recs[:, 6] == 0], recs[recs[:, 6] == 1]  # candidate rows against the cache; rows of users with an empty history
+        want2 = [serve.trim_length(int(cached[cached[:, 5] == w][:, 3].max()), Sm) for w in sorted(set(cached[:, 5].tolist()))]
+        want3 = [serve.trim_length(int(empty[empty[:, 5] == w][:, 3].max()), Sm) for w in sorted(set(empty[:, 5].tolist()))]
+        assert by_stage == {1: want1, 2: want2, 3: want3}, (by_stage, want1, want2, want3)
+    else:
+        live3 = desc[recs[:, 0], 0] + recs[:, 3]
+        want3 = [serve.trim_length(int(live3[recs[:, 5] == w].max()), Sm) for w in sorted(set(recs[:, 5].tolist()))]
+        assert by_stage == {1: [], 2: [], 3: want3}, (by_stage, want3)
+    print(f"render full_history={full_history} [{dtype}] forward_rows (stage, rows, row_len): {fr_on.tolist()}")
+    model.close()
+
+
+# ---------------------------------------------------------------- 7. errors and side effects
+def test_errors_leave_the_resident_batch(models):
+    import recommendersystem_amd as ra
+    from oracle import synth
+    from recommendersystem_amd import _lib, serve
+    Lb = _lib.lib()
+    cfg, V, model, P, adapters = models("base", "fp32")
+    rng = np.random.default_rng(16)
+    users = _retrieval_users(rng, (33, 4), V)
+    d = serve.build_batch(users, "retrieval", 0, V[0], S, 0)
+    model.upload_trimmed(d, 64)
+    rows, rl = C.c_int32(), C.c_int32()
+
+    def state():
+        assert Lb.rsys_batch_rows(model._h, C.byref(rows)) == 0 and Lb.rsys_batch_row_length(model._h, C.byref(rl)) == 0
+        return rows.value, rl.value
+
+    assert state() == (2, 64)
+    b, keep = model._c_batch(d)
+    assert Lb.rsys_batch_upload_trimmed(model._h, C.byref(b), 32) == ARG and state() == (2, 64)     # a live event at column 32
+    assert "userid" in _lib.last_error()
+    for bad in (0, 6, S + 4, -4):
+        assert Lb.rsys_batch_upload_trimmed(model._h, C.byref(b), bad) == ARG and state() == (2, 64)
+    idx = np.array([2 * 64], np.int32)                                                               # a token behind 2 row_len
+    out = np.full(cfg["embed_dim"], 5.0, np.float32)
+    assert Lb.rsys_infer_select(model._h, 0, idx.ctypes.data, 1, out.ctypes.data, out.size) == ARG and (out == 5.0).all()
+    assert Lb.rsys_batch_upload_trimmed(model._h, C.byref(b), S) == 0 and state() == (2, S)          # row_len == S: the ordinary upload
+    one = C.c_int32(7)
+    assert Lb.rsys_serving_trim_get(model._h, C.byref(one)) == 0 and one.value == 0                  # default off
+    for kind in ("fp8", "sharded"):
+        if kind == "fp8":
+            c8 = synth.make_config("f8t", mask_rate=0.2, mask_topk=16)
+            m8 = ra.RecommenderModel(c8, dtype="fp8", max_rows=2)
+        else:
+            c8 = synth.make_config("tiny", mask_rate=0.2, mask_topk=4)
+            c8["table_shard"] = (0, 1)
+            m8 = ra.RecommenderModel(c8, dtype="fp32", max_rows=2)
+        S8 = c8["max_sequence_length"]
+        d8 = serve._empty_rows(1, S8)
+        d8["userid"][0, :2] = 1
+        b8, keep8 = m8._c_batch(d8)
+        assert Lb.rsys_batch_upload_trimmed(m8._h, C.byref(b8), S8 // 2) == ARG, kind
+        assert ("fp8" if kind == "fp8" else "replicated table") in _lib.last_error(), (kind, _lib.last_error())       # the check that fired
+        m8.close()
+    # training through the adapter bank refuses a trimmed batch too, before anything is enqueued
+    cfgb, Vb, bank, Pb, adb = models("bank", "fp32")
+    bank.enable_adapter_training(0.0)
+    bank.upload_trimmed(d, 64)
+    names = [n for n, _ in bank.adapter_names()][:2]
+    before = [bank.adapter_grad(0, n).copy() for n in names]
+    rs, rt = np.array([0, 1], np.int32), np.array([0, 1], np.int32)
+    assert Lb.rsys_adapter_forward_backward(bank._h, 0, rs.ctypes.data, rt.ctypes.data, 1.0, 1, 1) == STATE
+    assert "inference-only" in _lib.last_error()
+    assert all(np.array_equal(x, bank.adapter_grad(0, n)) for x, n in zip(before, names))
+    bank.upload(d)
+
+
+@pytest.mark.parametrize("dtype", ["fp32", "bf16"])
+def test_trimmed_batch_is_inference_only_and_training_is_untouched(dtype):
+    """rsys_forward_backward on a trimmed batch: RSYS_ERR_STATE, parameters and gradients untouched.  Deterministic mode: step ->
+    trimmed predict -> step gives the step -> step results bit for bit."""
+    import recommendersystem_amd as ra
+    from oracle import synth
+    from recommendersystem_amd import _lib, serve
+    cfg = synth.make_config("hd64", mask_rate=0.2, deterministic=True)
+    V = (cfg["vocab_sizes"]["0_matchedid"], cfg["vocab_sizes"]["1_matchedid"])
+    Sm = cfg["max_sequence_length"]
+    P = synth.make_params(cfg, 3, "test")
+    rows = 4
+    batches = [synth.make_batch(cfg, rows, 40 + i) for i in range(2)]
+    masks = [synth.make_masks(cfg, rows, 50 + i) for i in range(2)]
+    names = synth.trainable_names(cfg)
+    rng = np.random.default_rng(2)
+    users = [tu.user_with_history(rng, 5, []), tu.user_with_history(rng, 20, [])]
+
+    def run(with_trim):
+        model = ra.RecommenderModel(cfg, dtype=dtype, max_rows=rows)
+        model.load_state_dict(P)
+        opt = ra.create_optimizer(model, dict(cfg, learning_rate=1e-2))
+        model.set_loss_weights(TASK_W, 1)
+        out = []
+        for i, (d, mk) in enumerate(zip(batches, masks)):
+            if i == 1 and with_trim:
+                vals = serve.predict(model, users, "retrieval", 0, trim=True)
+                assert model.forward_tokens == 2 * 2 * 32 and np.isfinite(vals[0]["0.retrieval"]).all()
+                before = [model.get_parameter(n).copy() for n in names] + [model.grad(n).copy() for n in names]
+                tw = (C.c_float * 4)(*TASK_W)
+                assert _lib.lib().rsys_forward_backward(model._h, 0, tw, 1.0, 1, 1) == STATE
+                assert "inference-only" in _lib.last_error()
+                after = [model.get_parameter(n).copy() for n in names] + [model.grad(n).copy() for n in names]
+                assert all(np.array_equal(x, y) for x, y in zip(before, after))
+            out.append(np.array(model(d, False, masks=mk), np.float32))
+            out += [model.grad(n).copy() for n in names]
+            opt.step(clip_max_norm=1.0)
+        out += [model.get_parameter(n).copy() for n in names]
+        model.close()
+        return out
+
+    a, b = run(False), run(True)
+    assert Sm == 64 and len(a) == len(b) and all(np.array_equal(x, y) for x, y in zip(a, b))
