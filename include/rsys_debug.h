@@ -237,6 +237,42 @@ int32_t rsys_op_sumsq(const float* g, int64_t n, float* out);
 int32_t rsys_op_clip_adamw(int32_t dtype, float* p, float* g, float* m, float* v, void* shadow, int64_t n_decay, int64_t n_total,
                            float lr, float b1, float b2, float eps, float wd, int32_t step, float max_norm, float grad_div,
                            int32_t zero_grad, int64_t sh_skip_lo, int64_t sh_skip_hi, int32_t fused, float* sumsq);
+/* the adapter bank's kernels (csrc/adapter_bank.hip), unit-test access on caller-provided device buffers: each call fills the arguments of
+ * the launch routines the model path calls, runs the selected launches on the null stream and synchronises.  dtype RSYS_DTYPE_FP32 / BF16 =
+ * the compute type T.  Nq = H hd, Nk = Nv = KV hd, ld = Nq + Nk + Nv.
+ * rsys_op_adapter_bank: `stages` is a mask, run in this (the production) order: 1 stage A (train != 0: the training form, with the
+ *   dropout mask of (p, seed, stream); stream in [0, 2^32) is the model's step * 64 + layer), 2 stage B, 4 dLa, 8 the dB partials, 16 the
+ *   dA partials, 32 dx, 64 both row reductions.  A stage reads its inputs from the buffers below, so one bit runs that kernel alone on
+ *   given intermediates.  Buffers (T-typed unless fp32 is said):
+ *     row_slot int32 [rows] (device), values in [-1, RSYS_ADAPTER_SLOTS); a row with -1 is neither read nor written by any stage
+ *     bankA [slots][L][16][D] ([A_q; A_v]), bankB [slots][L][Nq + Nv][8] (B_q rows, then B_v rows), slots >= 1 + the largest slot named
+ *     xn [rows*Ttok][D]                read by 1, 16
+ *     La [rows*Ttok][16]               written by 1, read by 2, 8
+ *     qkv [rows*Ttok][ld]              q and v columns updated in place by 2 (k columns untouched)
+ *     dqkv [rows*Ttok][ld]             read by 4, 8 (gradients w.r.t. the un-rotated q and v)
+ *     dLa [rows*Ttok][16]              written by 4, read by 16, 32
+ *     dxn [rows*Ttok][D]               added to by 32
+ *     partA fp32 [rows][16][D]         written by 16, read by 64
+ *     partB fp32 [rows][Nq + Nv][8]    written by 8 (without the factor 2), read by 64
+ *     gA fp32 [slots][L][16][D], gB fp32 [slots][L][Nq + Nv][8]: layer `layer` of every slot with a row is added to by 64
+ *     rope_cos / rope_sin fp32 [rope_rows][hd / 2]; rope_pos int32 [rows*Ttok] (device) or null: token t of a row has position t
+ *   Buffers of stages that are not selected may be null.  RSYS_ERR_ARG before anything is launched unless Ttok % 8 == 0, D % 16 == 0,
+ *   D == H hd, hd in {16, 32, 64, 128}, H % KV == 0, 0 <= layer < L, 0 <= p < 1, every row_slot value in range and (stage B) every
+ *   rope_pos value in [0, rope_rows), resp. rope_rows >= Ttok without rope_pos (row_slot and rope_pos are copied back once for this).
+ * rsys_op_adapter_bank_adamw: the per-slot clip + AdamW kernel, one workgroup per slot, all RSYS_ADAPTER_SLOTS slots.  fp32 masters A32 /
+ *   B32, gradients gA / gB and moments mA, vA / mB, vB: [RSYS_ADAPTER_SLOTS][nA] resp. [..][nB]; A / B: the T-typed copies of the masters
+ *   (bf16; null in fp32); per_slot (host) float [RSYS_ADAPTER_SLOTS][4] = (active, lr, max_norm, step) with step >= 1 the count the bias
+ *   corrections are taken at (computed by the host code of rsys_adapter_adamw_step); norms (device) fp32 [RSYS_ADAPTER_SLOTS]: the slot's
+ *   gradient norm, 0 for an inactive slot, of which nothing else is read or written.
+ * rsys_op_dropout: the finetune model's dropout launch on src / dst T-typed [n]: dst = (accumulate ? dst : 0) + (kept ? src / (1 - p) : 0),
+ *   element e kept iff u01(Philox(seed)(e >> 2, stream)[e & 3]) >= p. */
+int32_t rsys_op_adapter_bank(int32_t dtype, int32_t stages, int32_t train, int32_t rows, int32_t Ttok, int32_t D, int32_t H, int32_t KV, int32_t hd,
+                             int32_t L, int32_t layer, float p, uint64_t seed, int64_t stream, const int32_t* row_slot, const void* bankA,
+                             const void* bankB, const void* xn, void* La, void* qkv, const void* dqkv, void* dLa, void* dxn, float* partA, float* partB,
+                             float* gA, float* gB, const float* rope_cos, const float* rope_sin, const int32_t* rope_pos, int32_t rope_rows);
+int32_t rsys_op_adapter_bank_adamw(int32_t dtype, float* A32, float* B32, float* gA, float* gB, float* mA, float* vA, float* mB, float* vB, void* A,
+                                   void* B, int64_t nA, int64_t nB, const float* per_slot, float b1, float b2, float eps, float wd, float* norms);
+int32_t rsys_op_dropout(int32_t dtype, const void* src, void* dst, int64_t n, float p, uint64_t seed, int64_t stream, int32_t accumulate);
 
 #ifdef __cplusplus
 }

@@ -226,6 +226,9 @@ _SIGS = [
     ("rsys_op_sumsq", C.c_int32, [_P, C.c_int64, _P]),
     ("rsys_op_clip_adamw", C.c_int32, [C.c_int32] + [_P] * 5 + [C.c_int64, C.c_int64] + [C.c_float] * 5
                                        + [C.c_int32, C.c_float, C.c_float, C.c_int32, C.c_int64, C.c_int64, C.c_int32, _P]),
+    ("rsys_op_adapter_bank", C.c_int32, [C.c_int32] * 11 + [C.c_float, C.c_uint64, C.c_int64] + [_P] * 16 + [C.c_int32]),
+    ("rsys_op_adapter_bank_adamw", C.c_int32, [C.c_int32] + [_P] * 10 + [C.c_int64, C.c_int64, _P] + [C.c_float] * 4 + [_P]),
+    ("rsys_op_dropout", C.c_int32, [C.c_int32, _P, _P, C.c_int64, C.c_float, C.c_uint64, C.c_int64, C.c_int32]),
     ("rsys_step_mark", C.c_int32, [_P]),
     ("rsys_step_marks_get", C.c_int32, [_P, _P, C.c_int32, C.POINTER(C.c_int32)]),
     ("rsys_op_timing", C.c_int32, [_P, C.c_int32]),

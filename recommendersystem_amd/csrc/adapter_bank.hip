@@ -32,6 +32,14 @@ struct AdapterBank {
   float* d_norms = nullptr;               // [RSYS_ADAPTER_SLOTS] the optimizer step's per-slot gradient norms
 };
 
+struct BankLaunch {                       // the plain arguments of one layer's bank launches
+  int rows, Ttok, D, H, KV, hd, L, layer;
+  const int* row_slot;                    // [rows] device
+  const void *bankA, *bankB;              // compute type: [slots][L][16][D], [slots][L][Nq + Nv][8]
+  float p; unsigned long long seed; unsigned int stream;   // dropout key (a_train, da, dx)
+  hipStream_t s;
+};
+
 static inline int64_t bank_a_floats(const Model* m) { return (int64_t)16 * m->D; }
 static inline int64_t bank_b_floats(const Model* m) { return (int64_t)(m->H + m->KV) * m->hd * 8; }
 template <typename T> static inline T* bank_la(const Model* m, int l) { return (T*)m->bank->La_l + (int64_t)l * m->rows_max * m->Ta * 16; }   // layer l's La of a training pass
@@ -591,18 +599,72 @@ int adapter_bind_rows(Model* m, const int32_t* row_adapter) {
 }
 void adapter_unbind_rows(Model* m) { m->bank_rows = nullptr; }
 
+// One layer's launches on plain arguments: what the model-side callers below fill from Model and the test hooks (rsys_op_adapter_bank,
+// rsys_debug.h) fill from the caller's buffers.  bankA / bankB: the compute-type copies; (p, seed, stream): the dropout key of BankDrop.
+template <typename T>
+int bank_launch_a(const BankLaunch& a, const T* xn, T* La, bool train) {
+  const dim3 grid((a.Ttok + BANK_A_TOK - 1) / BANK_A_TOK, a.rows);
+  if (train)   // the LoRA input under the dropout mask
+    hipLaunchKernelGGL((adapter_bank_a_train_kernel<T>), grid, dim3(256), 0, a.s, xn, (const T*)a.bankA, a.row_slot, a.layer, a.L, a.D, a.Ttok, La, a.p,
+                       a.seed, a.stream);
+  else
+    hipLaunchKernelGGL((adapter_bank_a_kernel<T>), grid, dim3(256), 0, a.s, xn, (const T*)a.bankA, a.row_slot, a.layer, a.L, a.D, a.Ttok, La);
+  HIP_CHECK(hipGetLastError());
+  return RSYS_OK;
+}
+template <typename T>
+int bank_launch_b(const BankLaunch& a, const T* La, T* qkv, const float* rope_cos, const float* rope_sin, const int* rope_pos) {
+  const int Nq = a.H * a.hd, Nk = a.KV * a.hd;
+  hipLaunchKernelGGL((adapter_bank_b_kernel<T>), dim3((a.Ttok + BANK_B_TOK - 1) / BANK_B_TOK, a.rows), dim3(256), 0, a.s, La, (const T*)a.bankB, a.row_slot,
+                     a.layer, a.L, Nq, Nk, Nk, a.Ttok, a.hd, rope_cos, rope_sin, rope_pos, qkv);
+  HIP_CHECK(hipGetLastError());
+  return RSYS_OK;
+}
+// the backward's launches in the order adapter_bank_backward issues them; `stages` as rsys_op_adapter_bank's mask (4 dLa, 8 dB partials,
+// 16 dA partials, 32 dx, 64 both row reductions)
+template <typename T>
+int bank_launch_backward(const BankLaunch& a, int stages, const T* xn, const T* dqkv, const T* La, T* dLa, T* dxn, float* partA, float* partB,
+                         float* gA, float* gB) {
+  const int rows = a.rows, Nq = a.H * a.hd, Nk = a.KV * a.hd, Nv = Nk, Ttok = a.Ttok, D = a.D;
+  hipStream_t s = a.s;
+  if (stages & 4)
+    hipLaunchKernelGGL((adapter_bank_dla_kernel<T>), dim3((Ttok + BANK_A_TOK - 1) / BANK_A_TOK, rows), dim3(256), 0, s, dqkv, (const T*)a.bankB, a.row_slot,
+                       a.layer, a.L, Nq, Nk, Nv, Ttok, dLa);
+  if (stages & 8)
+    hipLaunchKernelGGL((adapter_bank_db_kernel<T>), dim3((Nq + Nv + 63) / 64, rows), dim3(256), 0, s, dqkv, La, a.row_slot, Nq, Nk, Nv, Ttok, partB);
+  if (stages & 16)
+    hipLaunchKernelGGL((adapter_bank_da_kernel<T>), dim3((D + 63) / 64, rows), dim3(256), 0, s, (const T*)dLa, xn, a.row_slot, D, Ttok, partA, a.p, a.seed,
+                       a.stream);
+  if (stages & 32)
+    hipLaunchKernelGGL((adapter_bank_dx_kernel<T>), dim3((Ttok + BANK_B_TOK - 1) / BANK_B_TOK, rows), dim3(256), 0, s, (const T*)dLa, (const T*)a.bankA,
+                       a.row_slot, a.layer, a.L, D, Ttok, dxn, a.p, a.seed, a.stream);
+  if (stages & 64) {
+    const long long na = (long long)16 * D, nb = (long long)(Nq + Nv) * 8;
+    hipLaunchKernelGGL(adapter_bank_rows_reduce_kernel, dim3((unsigned)((na + 255) / 256)), dim3(256), 0, s, partA, a.row_slot, rows, na, 1.f,
+                       gA + (long long)a.layer * na, (long long)a.L * na);
+    hipLaunchKernelGGL(adapter_bank_rows_reduce_kernel, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, s, partB, a.row_slot, rows, nb, 2.f,
+                       gB + (long long)a.layer * nb, (long long)a.L * nb);
+  }
+  HIP_CHECK(hipGetLastError());
+  return RSYS_OK;
+}
+
+static BankLaunch bank_launch_of(const Model* m, int l) {
+  const AdapterBank* b = m->bank;
+  BankLaunch a{};
+  a.rows = m->cur_rows; a.Ttok = m->T; a.D = m->D; a.H = m->H; a.KV = m->KV; a.hd = m->hd; a.L = m->L; a.layer = l;
+  a.row_slot = m->bank_rows; a.bankA = b->A; a.bankB = b->B;
+  a.p = b->drop_now ? b->dropout : 0.f; a.seed = m->drop_seed; a.stream = (unsigned int)(m->drop_step * 64 + l);
+  a.s = m->stream;
+  return a;
+}
+
 template <typename T>
 int adapter_bank_stage_a(Model* m, int l, const T* xn) {
   const AdapterBank* b = m->bank;
-  const int rows = m->cur_rows;
-  tic(m, "hbm_adapter_bank_a", (double)sizeof(T) * rows * m->T * (m->D + 16.0));
-  if (m->bank_train)   // the layer's own La (the backward reads it), the LoRA input under this pass's dropout mask
-    hipLaunchKernelGGL((adapter_bank_a_train_kernel<T>), dim3((m->T + BANK_A_TOK - 1) / BANK_A_TOK, rows), dim3(256), 0, m->stream, xn, (const T*)b->A,
-                       m->bank_rows, l, m->L, m->D, m->T, bank_la<T>(m, l), b->drop_now ? b->dropout : 0.f, m->drop_seed, (unsigned int)(m->drop_step * 64 + l));
-  else
-  hipLaunchKernelGGL((adapter_bank_a_kernel<T>), dim3((m->T + BANK_A_TOK - 1) / BANK_A_TOK, rows), dim3(256), 0, m->stream, xn, (const T*)b->A,
-                     m->bank_rows, l, m->L, m->D, m->T, (T*)b->La);
-  HIP_CHECK(hipGetLastError());
+  tic(m, "hbm_adapter_bank_a", (double)sizeof(T) * m->cur_rows * m->T * (m->D + 16.0));
+  // a training pass writes the layer's own La (the backward reads it)
+  RC(bank_launch_a<T>(bank_launch_of(m, l), xn, m->bank_train ? bank_la<T>(m, l) : (T*)b->La, m->bank_train));
   toc(m);
   return RSYS_OK;
 }
@@ -611,10 +673,7 @@ int adapter_bank_stage_b(Model* m, int l, T* qkv, const int* rope_pos) {
   const AdapterBank* b = m->bank;
   const int rows = m->cur_rows, Nq = m->H * m->hd, Nk = m->KV * m->hd;
   tic(m, "hbm_adapter_bank_b", (double)sizeof(T) * rows * m->T * (2.0 * (Nq + Nk) + 16.0));
-  hipLaunchKernelGGL((adapter_bank_b_kernel<T>), dim3((m->T + BANK_B_TOK - 1) / BANK_B_TOK, rows), dim3(256), 0, m->stream,
-                     m->bank_train ? (const T*)bank_la<T>(m, l) : (const T*)b->La,
-                     (const T*)b->B, m->bank_rows, l, m->L, Nq, Nk, Nk, m->T, m->hd, m->rope_cos, m->rope_sin, rope_pos, qkv);
-  HIP_CHECK(hipGetLastError());
+  RC(bank_launch_b<T>(bank_launch_of(m, l), m->bank_train ? (const T*)bank_la<T>(m, l) : (const T*)b->La, qkv, m->rope_cos, m->rope_sin, rope_pos));
   toc(m);
   return RSYS_OK;
 }
@@ -700,31 +759,72 @@ template <typename T>
 int adapter_bank_backward(Model* m, int l, const T* xn, const T* dqkv, T* dxn) {
   if (!m->bank_rows) return RSYS_OK;   // every row runs the base model: nothing to differentiate
   AdapterBank* b = m->bank;
-  const int rows = m->cur_rows, Nq = m->H * m->hd, Nk = m->KV * m->hd, Nv = Nk, Ttok = m->T, D = m->D;
-  const float p = b->drop_now ? b->dropout : 0.f;
-  const unsigned int stream = (unsigned int)(m->drop_step * 64 + l);
-  hipStream_t s = m->stream;
-  T* dLa = (T*)b->dLa;
-  const T* La = bank_la<T>(m, l);
   tic(m, "adapter_bank_bwd");
-  hipLaunchKernelGGL((adapter_bank_dla_kernel<T>), dim3((Ttok + BANK_A_TOK - 1) / BANK_A_TOK, rows), dim3(256), 0, s, dqkv, (const T*)b->B, m->bank_rows, l,
-                     m->L, Nq, Nk, Nv, Ttok, dLa);
-  hipLaunchKernelGGL((adapter_bank_db_kernel<T>), dim3((Nq + Nv + 63) / 64, rows), dim3(256), 0, s, dqkv, La, m->bank_rows, Nq, Nk, Nv, Ttok, b->partB);
-  hipLaunchKernelGGL((adapter_bank_da_kernel<T>), dim3((D + 63) / 64, rows), dim3(256), 0, s, (const T*)dLa, xn, m->bank_rows, D, Ttok, b->partA, p,
-                     m->drop_seed, stream);
-  hipLaunchKernelGGL((adapter_bank_dx_kernel<T>), dim3((Ttok + BANK_B_TOK - 1) / BANK_B_TOK, rows), dim3(256), 0, s, (const T*)dLa, (const T*)b->A, m->bank_rows,
-                     l, m->L, D, Ttok, dxn, p, m->drop_seed, stream);
-  const long long na = bank_a_floats(m), nb = bank_b_floats(m);
-  hipLaunchKernelGGL(adapter_bank_rows_reduce_kernel, dim3((unsigned)((na + 255) / 256)), dim3(256), 0, s, b->partA, m->bank_rows, rows, na, 1.f,
-                     b->gA + (long long)l * na, (long long)m->L * na);
-  hipLaunchKernelGGL(adapter_bank_rows_reduce_kernel, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, s, b->partB, m->bank_rows, rows, nb, 2.f,
-                     b->gB + (long long)l * nb, (long long)m->L * nb);
-  HIP_CHECK(hipGetLastError());
+  RC(bank_launch_backward<T>(bank_launch_of(m, l), 4 | 8 | 16 | 32 | 64, xn, dqkv, (const T*)bank_la<T>(m, l), (T*)b->dLa, dxn, b->partA, b->partB, b->gA,
+                             b->gB));
   toc(m);
   return RSYS_OK;
 }
 template int adapter_bank_backward<float>(Model*, int, const float*, const float*, float*);
 template int adapter_bank_backward<bf16>(Model*, int, const bf16*, const bf16*, bf16*);
+
+// rsys_op_adapter_bank (rsys_debug.h): the launches above on the caller's device buffers, in production order, then a device synchronise.
+// Every refusal comes before the first launch.
+template <typename T>
+static int bank_op_run(const BankLaunch& a, int stages, int train, const void* xn, void* La, void* qkv, const void* dqkv, void* dLa, void* dxn,
+                       float* partA, float* partB, float* gA, float* gB, const float* rope_cos, const float* rope_sin, const int* rope_pos) {
+  if (stages & 1) RC(bank_launch_a<T>(a, (const T*)xn, (T*)La, train != 0));
+  if (stages & 2) RC(bank_launch_b<T>(a, (const T*)La, (T*)qkv, rope_cos, rope_sin, rope_pos));
+  if (stages & 124) RC(bank_launch_backward<T>(a, stages, (const T*)xn, (const T*)dqkv, (const T*)La, (T*)dLa, (T*)dxn, partA, partB, gA, gB));
+  return RSYS_OK;
+}
+int adapter_bank_op(int dtype, int stages, int train, int rows, int Ttok, int D, int H, int KV, int hd, int L, int layer, float p, uint64_t seed,
+                    int64_t stream, const int32_t* row_slot, const void* bankA, const void* bankB, const void* xn, void* La, void* qkv, const void* dqkv,
+                    void* dLa, void* dxn, float* partA, float* partB, float* gA, float* gB, const float* rope_cos, const float* rope_sin,
+                    const int32_t* rope_pos, int rope_rows) {
+  ARG_CHECK(dtype == RSYS_DTYPE_BF16 || dtype == RSYS_DTYPE_FP32, "rsys_op_adapter_bank: dtype fp32 or bf16");
+  ARG_CHECK(stages >= 1 && stages <= 127, "rsys_op_adapter_bank: stages is a mask of bits 1 .. 64");
+  ARG_CHECK(rows >= 1 && rows <= 65535 && Ttok >= 8 && L >= 1 && layer >= 0 && layer < L && H >= 1 && KV >= 1, "rsys_op_adapter_bank: empty shape or layer outside [0, L)");
+  ARG_CHECK(Ttok % 8 == 0, "rsys_op_adapter_bank: Ttok % 8 must be 0");
+  ARG_CHECK(D >= 16 && D % 16 == 0, "rsys_op_adapter_bank: D % 16 must be 0");
+  ARG_CHECK(hd == 16 || hd == 32 || hd == 64 || hd == 128, "rsys_op_adapter_bank: hd must be 16, 32, 64 or 128");
+  ARG_CHECK(D == H * hd, "rsys_op_adapter_bank: D must be H * hd");
+  ARG_CHECK(H % KV == 0, "rsys_op_adapter_bank: H % KV must be 0");
+  ARG_CHECK(p >= 0.f && p < 1.f, "rsys_op_adapter_bank: dropout p must be in [0, 1)");
+  ARG_CHECK(stream >= 0 && stream <= 0xFFFFFFFFLL, "rsys_op_adapter_bank: stream is a 32-bit counter word");
+  ARG_CHECK(row_slot != nullptr, "rsys_op_adapter_bank: row_slot is null");
+  ARG_CHECK(!(stages & (1 | 32)) || bankA, "rsys_op_adapter_bank: stage A and dx read bankA");
+  ARG_CHECK(!(stages & (2 | 4)) || bankB, "rsys_op_adapter_bank: stage B and dLa read bankB");
+  ARG_CHECK(!(stages & (1 | 16)) || xn, "rsys_op_adapter_bank: stage A and dA read xn");
+  ARG_CHECK(!(stages & (1 | 2 | 8)) || La, "rsys_op_adapter_bank: stage A, stage B and dB use La");
+  ARG_CHECK(!(stages & 2) || (qkv && rope_cos && rope_sin), "rsys_op_adapter_bank: stage B needs qkv and the rope tables");
+  ARG_CHECK(!(stages & (4 | 8)) || dqkv, "rsys_op_adapter_bank: dLa and dB read dqkv");
+  ARG_CHECK(!(stages & (4 | 16 | 32)) || dLa, "rsys_op_adapter_bank: dLa, dA and dx use dLa");
+  ARG_CHECK(!(stages & 32) || dxn, "rsys_op_adapter_bank: dx needs dxn");
+  ARG_CHECK(!(stages & (16 | 64)) || partA, "rsys_op_adapter_bank: dA and the reductions use partA");
+  ARG_CHECK(!(stages & (8 | 64)) || partB, "rsys_op_adapter_bank: dB and the reductions use partB");
+  ARG_CHECK(!(stages & 64) || (gA && gB), "rsys_op_adapter_bank: the reductions need gA and gB");
+  std::vector<int32_t> host((size_t)rows);
+  HIP_CHECK(hipMemcpy(host.data(), row_slot, host.size() * 4, hipMemcpyDeviceToHost));
+  for (int32_t v : host) ARG_CHECK(v >= -1 && v < RSYS_ADAPTER_SLOTS, "rsys_op_adapter_bank: row_slot entries must be in [-1, RSYS_ADAPTER_SLOTS)");
+  if ((stages & 2) && rope_pos) {   // every explicit position inside the tables (one copy back)
+    host.resize((size_t)rows * Ttok);
+    HIP_CHECK(hipMemcpy(host.data(), rope_pos, host.size() * 4, hipMemcpyDeviceToHost));
+    for (int32_t v : host) ARG_CHECK(v >= 0 && v < rope_rows, "rsys_op_adapter_bank: rope_pos outside the tables");
+  } else if (stages & 2) {
+    ARG_CHECK(rope_rows >= Ttok, "rsys_op_adapter_bank: rope tables shorter than Ttok");
+  }
+  BankLaunch a{};
+  a.rows = rows; a.Ttok = Ttok; a.D = D; a.H = H; a.KV = KV; a.hd = hd; a.L = L; a.layer = layer;
+  a.row_slot = row_slot; a.bankA = bankA; a.bankB = bankB; a.p = p; a.seed = seed; a.stream = (unsigned int)stream; a.s = nullptr;
+  int rc = dtype == RSYS_DTYPE_BF16
+               ? bank_op_run<bf16>(a, stages, train, xn, La, qkv, dqkv, dLa, dxn, partA, partB, gA, gB, rope_cos, rope_sin, rope_pos)
+               : bank_op_run<float>(a, stages, train, xn, La, qkv, dqkv, dLa, dxn, partA, partB, gA, gB, rope_cos, rope_sin, rope_pos);
+  hipError_t e = hipDeviceSynchronize();
+  if (rc) return rc;
+  HIP_CHECK(e);
+  return RSYS_OK;
+}
 
 // a slot's tensor in one of the training buffers (which: 0 gradient, 1 exp_avg, 2 exp_avg_sq)
 static int bank_train_locate(Model* m, int slot, const char* name, int64_t n, float** g, float** mo, float** va) {
@@ -761,6 +861,30 @@ int adapter_zero_grad(Model* m) {
   return RSYS_OK;
 }
 
+// one slot's record of the optimizer launch: the bias corrections of step `t` (1-based) in the host arithmetic every caller shares
+static BankStepRec bank_step_rec(bool active, float lr, float max_norm, int t, float b1, float b2) {
+  BankStepRec r{};
+  r.active = active ? 1 : 0;
+  if (!active) return r;
+  const float tf = (float)t;
+  r.lr = lr; r.max_norm = max_norm;
+  r.bc1 = 1.f - powf(b1, tf); r.bc2_sqrt = sqrtf(1.f - powf(b2, tf));
+  return r;
+}
+// the optimizer launch on plain arguments (A / B: the compute-type copies, used in bf16 mode only)
+static int bank_launch_adamw(bool bf16_mode, int n_slots, float* A32, float* B32, float* gA, float* gB, float* mA, float* vA, float* mB, float* vB, void* A,
+                             void* B, long long na, long long nb, const BankStepArgs& a, float b1, float b2, float eps, float wd, float* norms,
+                             hipStream_t s) {
+  if (bf16_mode)
+    hipLaunchKernelGGL((adapter_bank_adamw_kernel<bf16>), dim3(n_slots), dim3(1024), 0, s, A32, B32, gA, gB, mA, vA, mB, vB, (bf16*)A, (bf16*)B, na, nb, a, b1,
+                       b2, eps, wd, norms);
+  else
+    hipLaunchKernelGGL((adapter_bank_adamw_kernel<float>), dim3(n_slots), dim3(1024), 0, s, A32, B32, gA, gB, mA, vA, mB, vB, (float*)nullptr,
+                       (float*)nullptr, na, nb, a, b1, b2, eps, wd, norms);
+  HIP_CHECK(hipGetLastError());
+  return RSYS_OK;
+}
+
 int adapter_adamw_step(Model* m, float lr0, float b1, float b2, float eps, float wd, const float* per_slot, int n_slots, float* norms_out) {
   RC(bank_train_check_model(m));
   ARG_CHECK(m->bank != nullptr && m->bank->train, "adapter bank training is not enabled (rsys_adapter_train_enable)");
@@ -770,27 +894,37 @@ int adapter_adamw_step(Model* m, float lr0, float b1, float b2, float eps, float
     if (per_slot[3 * s] != 0.f) ARG_CHECK(bank_complete(m, s), "an active slot is not complete (4 tensors per layer since its last clear)");
   AdapterBank* b = m->bank;
   BankStepArgs a{};
-  for (int s = 0; s < n_slots; ++s) {
-    BankStepRec& r = a.rec[s];
-    r.active = per_slot[3 * s] != 0.f ? 1 : 0;
-    if (!r.active) continue;
-    const float t = (float)(b->step[s] + 1);   // (the count itself moves once the kernel is enqueued)
-    r.lr = lr0 * per_slot[3 * s + 1]; r.max_norm = per_slot[3 * s + 2];
-    r.bc1 = 1.f - powf(b1, t); r.bc2_sqrt = sqrtf(1.f - powf(b2, t));
-  }
+  for (int s = 0; s < n_slots; ++s)   // (the count itself moves once the kernel is enqueued)
+    a.rec[s] = bank_step_rec(per_slot[3 * s] != 0.f, lr0 * per_slot[3 * s + 1], per_slot[3 * s + 2], b->step[s] + 1, b1, b2);
   HIP_CHECK(hipSetDevice(m->device));
   const long long na = (long long)m->L * bank_a_floats(m), nb = (long long)m->L * bank_b_floats(m);
-  if (m->bf16_mode)
-    hipLaunchKernelGGL((adapter_bank_adamw_kernel<bf16>), dim3(n_slots), dim3(1024), 0, m->stream, b->A32, b->B32, b->gA, b->gB, b->mA, b->vA, b->mB, b->vB,
-                       (bf16*)b->A, (bf16*)b->B, na, nb, a, b1, b2, eps, wd, b->d_norms);
-  else
-    hipLaunchKernelGGL((adapter_bank_adamw_kernel<float>), dim3(n_slots), dim3(1024), 0, m->stream, b->A32, b->B32, b->gA, b->gB, b->mA, b->vA, b->mB, b->vB,
-                       (float*)nullptr, (float*)nullptr, na, nb, a, b1, b2, eps, wd, b->d_norms);
-  HIP_CHECK(hipGetLastError());
+  RC(bank_launch_adamw(m->bf16_mode, n_slots, b->A32, b->B32, b->gA, b->gB, b->mA, b->vA, b->mB, b->vB, b->A, b->B, na, nb, a, b1, b2, eps, wd, b->d_norms,
+                       m->stream));
   for (int s = 0; s < n_slots; ++s) b->step[s] += a.rec[s].active;
   HIP_CHECK(hipMemcpyAsync(norms_out, b->d_norms, (size_t)n_slots * 4, hipMemcpyDeviceToHost, m->stream));
   HIP_CHECK(hipStreamSynchronize(m->stream));
   return RSYS_OK;   // (no parameter of the trunk changed: table_dirty / wt_dirty stay as they are)
+}
+
+// rsys_op_adapter_bank_adamw (rsys_debug.h): per_slot [RSYS_ADAPTER_SLOTS][4] = (active, lr, max_norm, step), step = the 1-based count the
+// bias corrections are taken at
+int adapter_bank_adamw_op(int dtype, float* A32, float* B32, float* gA, float* gB, float* mA, float* vA, float* mB, float* vB, void* A, void* B,
+                          int64_t nA, int64_t nB, const float* per_slot, float b1, float b2, float eps, float wd, float* norms) {
+  ARG_CHECK(dtype == RSYS_DTYPE_BF16 || dtype == RSYS_DTYPE_FP32, "rsys_op_adapter_bank_adamw: dtype fp32 or bf16");
+  ARG_CHECK(A32 && B32 && gA && gB && mA && vA && mB && vB && per_slot && norms && nA >= 1 && nB >= 1, "rsys_op_adapter_bank_adamw: null or empty");
+  const bool bf = dtype == RSYS_DTYPE_BF16;
+  ARG_CHECK(!bf || (A && B), "rsys_op_adapter_bank_adamw: bf16 needs the compute-type copies");
+  BankStepArgs a{};
+  for (int s = 0; s < RSYS_ADAPTER_SLOTS; ++s) {
+    const float* q = per_slot + 4 * s;
+    ARG_CHECK(q[0] == 0.f || q[3] >= 1.f, "rsys_op_adapter_bank_adamw: an active slot's step must be >= 1");
+    a.rec[s] = bank_step_rec(q[0] != 0.f, q[1], q[2], (int)q[3], b1, b2);
+  }
+  int rc = bank_launch_adamw(bf, RSYS_ADAPTER_SLOTS, A32, B32, gA, gB, mA, vA, mB, vB, A, B, nA, nB, a, b1, b2, eps, wd, norms, nullptr);
+  hipError_t e = hipDeviceSynchronize();
+  if (rc) return rc;
+  HIP_CHECK(e);
+  return RSYS_OK;
 }
 
 int adapter_adamw_state_io(Model* m, int slot, const char* name, float* m_out, float* v_out, const float* m_in, const float* v_in, int64_t n,

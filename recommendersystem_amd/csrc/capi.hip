@@ -1229,6 +1229,33 @@ int32_t rsys_op_clip_adamw(int32_t dtype, float* p, float* g, float* m, float* v
   return RSYS_OK;
 }
 
+// the adapter bank's kernels on caller-provided buffers (adapter_bank.hip: the launch routines the model path calls)
+int32_t rsys_op_adapter_bank(int32_t dtype, int32_t stages, int32_t train, int32_t rows, int32_t Ttok, int32_t D, int32_t H, int32_t KV, int32_t hd,
+                             int32_t L, int32_t layer, float p, uint64_t seed, int64_t stream, const int32_t* row_slot, const void* bankA,
+                             const void* bankB, const void* xn, void* La, void* qkv, const void* dqkv, void* dLa, void* dxn, float* partA, float* partB,
+                             float* gA, float* gB, const float* rope_cos, const float* rope_sin, const int32_t* rope_pos, int32_t rope_rows) {
+  switches_parse();
+  return adapter_bank_op(dtype, stages, train, rows, Ttok, D, H, KV, hd, L, layer, p, seed, stream, row_slot, bankA, bankB, xn, La, qkv, dqkv, dLa, dxn,
+                         partA, partB, gA, gB, rope_cos, rope_sin, rope_pos, rope_rows);
+}
+
+int32_t rsys_op_adapter_bank_adamw(int32_t dtype, float* A32, float* B32, float* gA, float* gB, float* mA, float* vA, float* mB, float* vB, void* A,
+                                   void* B, int64_t nA, int64_t nB, const float* per_slot, float b1, float b2, float eps, float wd, float* norms) {
+  switches_parse();
+  return adapter_bank_adamw_op(dtype, A32, B32, gA, gB, mA, vA, mB, vB, A, B, nA, nB, per_slot, b1, b2, eps, wd, norms);
+}
+
+int32_t rsys_op_dropout(int32_t dtype, const void* src, void* dst, int64_t n, float p, uint64_t seed, int64_t stream, int32_t accumulate) {
+  switches_parse();
+  ARG_CHECK(dtype == RSYS_DTYPE_BF16 || dtype == RSYS_DTYPE_FP32, "rsys_op_dropout: dtype fp32 or bf16");
+  ARG_CHECK(src && dst && n >= 1 && p >= 0.f && p < 1.f && stream >= 0 && stream <= 0xFFFFFFFFLL, "rsys_op_dropout: arguments");
+  int rc = dtype == RSYS_DTYPE_BF16 ? launch_dropout<bf16>((const bf16*)src, (bf16*)dst, n, p, seed, (unsigned int)stream, accumulate, nullptr)
+                                    : launch_dropout<float>((const float*)src, (float*)dst, n, p, seed, (unsigned int)stream, accumulate, nullptr);
+  if (rc) return rc;
+  HIP_CHECK(hipDeviceSynchronize());
+  return RSYS_OK;
+}
+
 // step boundaries on the model's stream: rsys_step_mark records an event, rsys_step_marks_get returns the elapsed time
 // between consecutive marks (ms) and clears them -- the per-step time distribution without a host sync per step
 int32_t rsys_step_mark(rsys_model* h) {

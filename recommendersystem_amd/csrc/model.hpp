@@ -351,6 +351,13 @@ int adapter_adamw_step(Model* m, float lr0, float b1, float b2, float eps, float
 int adapter_adamw_state_io(Model* m, int slot, const char* name, float* m_out, float* v_out, const float* m_in, const float* v_in, int64_t n, int32_t* step_out, int32_t step_in);
 // per layer of the backward, after the attention backward: dxn (dhn, this layer's token order) += drop'(dLa . [A_q; A_v][slot]) and the slots' dA / dB
 template <typename T> int adapter_bank_backward(Model* m, int l, const T* xn, const T* dqkv, T* dxn);
+// the bank's launches on caller-provided device buffers (rsys_op_adapter_bank / rsys_op_adapter_bank_adamw, rsys_debug.h)
+int adapter_bank_op(int dtype, int stages, int train, int rows, int Ttok, int D, int H, int KV, int hd, int L, int layer, float p, uint64_t seed,
+                    int64_t stream, const int32_t* row_slot, const void* bankA, const void* bankB, const void* xn, void* La, void* qkv, const void* dqkv,
+                    void* dLa, void* dxn, float* partA, float* partB, float* gA, float* gB, const float* rope_cos, const float* rope_sin,
+                    const int32_t* rope_pos, int rope_rows);
+int adapter_bank_adamw_op(int dtype, float* A32, float* B32, float* gA, float* gB, float* mA, float* vA, float* mB, float* vB, void* A, void* B,
+                          int64_t nA, int64_t nB, const float* per_slot, float b1, float b2, float eps, float wd, float* norms);
 // the joint pass's body (model.hip): masks per row task (d_row_task: device, [rows]), forward, heads with every task at grad_scale, backward
 int model_forward_backward_rows(Model* m, int evaluate, const int* d_row_task, float grad_scale, uint64_t seed, uint64_t step);
 int model_infer_adapters(Model* m, int task, const int32_t* row_adapter, const int32_t* token_index, int64_t n_tokens, float* out, int64_t n);

@@ -18,7 +18,12 @@ import _adapter_bank_util as ab  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-CONFIGS = {"tiny": (dict(mask_rate=0.25, mask_topk=6), 26), "hd64": (dict(mask_rate=0.2, mask_topk=16), 21)}
+CONFIGS = {"tiny": (dict(mask_rate=0.25, mask_topk=6), 26), "hd64": (dict(mask_rate=0.2, mask_topk=16), 21),
+           # 2S = 40, D = 80, hd = 16 (base: the shape make_config starts from): the bank's ragged branches inside the whole model -- a half
+           # token tile (40 % 16 == 8), a partial token-K step in dA / dB (40 % 32), a partial bf16 K step over the columns (80 % 32 == 16)
+           "s20d80": (dict(base="tiny", max_sequence_length=20, embed_dim=80, num_heads=5, num_kv_heads=1, intermediate_dim=224, mask_rate=0.25,
+                           mask_topk=6), 20)}
+REGULAR = ["tiny", "hd64"]           # the shapes of the tests that need per-shape constants
 ROWS = 6
 SLOTS = [0, 1, 2, 3, -1, 2]          # slot s runs task s; two rows for slot 2 (accumulation across rows), one base-model row
 TASKS = [0, 1, 2, 3, -1, 2]
@@ -66,7 +71,8 @@ def _setup(name, seed_shift=0):
     if key not in _SETUPS:
         from oracle import synth
         over, seed = CONFIGS[name]
-        cfg = synth.make_config(name, **over)
+        over = dict(over)
+        cfg = synth.make_config(over.pop("base", name), **over)
         S, K = cfg["max_sequence_length"], cfg["mask_topk"]
         P = synth.make_params(cfg, seed, "test")
         d = _thin(cfg, synth.make_batch(cfg, ROWS, seed + 1 + seed_shift), ROWS)
@@ -192,7 +198,7 @@ def _grads(bank):
 
 
 @pytest.mark.parametrize("dtype", ["fp32", "bf16"])
-@pytest.mark.parametrize("name", list(CONFIGS))
+@pytest.mark.parametrize("name", REGULAR)
 def test_exact_properties(name, dtype):
     from recommendersystem_amd.optim import AdapterAdamW
     cfg, P, d, adapters = _setup(name)
@@ -246,7 +252,7 @@ OPT_LR = {"tiny": 1e-3, "hd64": 1e-4}
 
 
 @pytest.mark.parametrize("dtype,tol", [("fp32", 3e-4), ("bf16", 8e-2)])
-@pytest.mark.parametrize("name", list(CONFIGS))
+@pytest.mark.parametrize("name", REGULAR)
 def test_three_joint_optimizer_steps(name, dtype, tol):
     """Three joint steps (forward / backward, per-slot clip at 1.0, AdamW) against oracle.train_np's clip_grad_norm and AdamW run per
     adapter on that adapter's rows.  Norms: the bounds of test_clip_adamw_three_steps_vs_golden, the project's three-step optimizer
@@ -359,6 +365,56 @@ def test_dropout():
     for (p_drop, key), v in mism.items():
         if p_drop > 0:
             assert v <= 3 * mism[(0.0, key)], (key, v, mism[(0.0, key)])
+    bank.close()
+
+
+@pytest.fixture
+def dense_top(monkeypatch):
+    """RSYS_SPARSE_TOP=0 for the models the test creates; the environment and the parsed switches are restored afterwards"""
+    from recommendersystem_amd._lib import lib
+    monkeypatch.setenv("RSYS_SPARSE_TOP", "0")
+    lib().rsys_switches_reload()
+    yield
+    monkeypatch.undo()
+    lib().rsys_switches_reload()
+
+
+def test_dropout_matches_the_finetune_model(dense_top):
+    """The bank's dropout IS the finetune = 1 model's: both key the mask on (seed ^ 0xD409, step * 64 + layer, element of the layer's
+    [tokens][D] LoRA input), the model in a pass of its own (launch_dropout), the bank inside stage A, dA and dx.  A joint pass in which
+    every row names slot s at bank dropout 0.5 against the finetune = 1 model of task s with lora_dropout = 0.5 on the same batch, seed and
+    step, fp32: the loss and every LoRA gradient within FP32_TOL (gradients relative to each tensor's maximum).
+    With the last layer dense (RSYS_SPARSE_TOP=0).  Under the compact top that layer runs in selected-first token order, so ITS element
+    index is a token's place in that order, and the order follows the positions the pass selected: the joint pass and the finetune = 1
+    model select different sets (other tasks' targets), draw the same mask array and lay it over different tokens of the last layer --
+    two equally valid masks, not comparable value for value."""
+    import recommendersystem_amd as ra
+    name = "tiny"
+    cfg, P, d, adapters = _setup(name)
+    bank = _bank(name, "fp32", dropout=0.5)
+    bank.upload(d)
+    for s in range(4):
+        bank.zero_adapter_grads()
+        plain = bank.forward_backward_adapters(None, [s] * ROWS, [s] * ROWS, evaluate=True, step=5)[s]
+        plain = plain[0] if isinstance(plain, list) else plain                    # (a rating task's evaluation: [mse, ...])
+        bank.zero_adapter_grads()
+        loss = bank.forward_backward_adapters(None, [s] * ROWS, [s] * ROWS, step=5)[s]
+        grads = bank.adapter_grad(s)
+        assert abs(loss - plain) > 1e-3 * abs(plain), (s, loss, plain)            # the mask acts
+        ft = ra.RecommenderModel(dict(_task_cfg(cfg, s), lora_dropout=0.5), dtype="fp32", max_rows=ROWS)
+        ft.load_state_dict(dict(P, **adapters[s]))
+        ft.set_loss_weights([1.0 if i == s else 0.0 for i in range(4)], 1)
+        ft.zero_grad()
+        ft.upload(d)
+        ft.forward_resident(False, step=5)
+        ref_loss = ft.losses()[s]
+        ref = {k: ft.grad(k) for k in adapters[s]}
+        ft.close()
+        e_loss = abs(loss - ref_loss) / abs(ref_loss)
+        e_grad = max(relerr(grads[k], ref[k]) for k in ref)
+        print(f"adapter dropout 0.5, all rows on slot {s}: loss {loss:.6f} finetune = 1 model {ref_loss:.6f} (rel {e_loss:.2e}), "
+              f"worst gradient error {e_grad:.2e}")
+        assert e_loss < FP32_TOL and e_grad < FP32_TOL, (s, e_loss, e_grad)
     bank.close()
 
 

@@ -156,6 +156,28 @@ def test_bank_rows_with_their_own_slots(models, dtype):
     model.upload(d)
 
 
+@pytest.mark.parametrize("dtype", ["fp32", "bf16"])
+def test_bank_rows_with_their_own_slots_row_len_36(models, dtype):
+    """the same rows at the C-level row_len 36 (33 live columns; T = 72 = 64 + 8): the bank's stage A runs a half token tile behind four
+    full ones, the case a serving call with adapters reaches whenever the longest history of a batch rounds to 4 but not to 8"""
+    from recommendersystem_amd import serve
+    cfg, V, model, P, adapters = models("bank", dtype)
+    rng = np.random.default_rng(14)
+    users = _retrieval_users(rng, (20, 33, 7), V)
+    d = serve.build_batch(users, "retrieval", 1, V[0], S, 0)
+    index, _ = serve._selected_tokens(users, "retrieval", S, S)
+    slots = [model.adapter_slots["1.retrieval"], model.adapter_slots["0.retrieval"], -1]
+    full = model.inference_select(d, "retrieval", index, adapters=slots)
+    got = model.inference_select(d, "retrieval", index, adapters=slots, row_len=36)
+    assert model.forward_tokens == 3 * 2 * 36 and model.batch_row_length == 36
+    _same(got, full, None, dtype, "bank rows at row_len 36, slots (1.retrieval, 0.retrieval, base)")
+    base = model.inference_select(d, "retrieval", index, adapters=[-1, -1, -1], row_len=36)
+    assert not np.array_equal(base[0], got[0]) and not np.array_equal(base[1], got[1]) and np.array_equal(base[2], got[2])
+    other = model.inference_select(d, "retrieval", index, adapters=[slots[1], slots[0], -1], row_len=36)
+    assert not np.array_equal(other[0], got[0]) and not np.array_equal(other[1], got[1])    # which slot a row names matters
+    model.upload(d)
+
+
 # ---------------------------------------------------------------- 4. the ranking K/V cache
 def _hist_rows(users):
     from recommendersystem_amd import serve
@@ -232,6 +254,37 @@ def test_rank_cache(models, kind, dtype):
     model.upload_trimmed(dc, 64)
     assert _lib.lib().rsys_rank_cache_candidates(model._h, None, i32(1).ctypes.data, i32(65).ctypes.data, out.ctypes.data) == ARG
     assert _lib.lib().rsys_rank_cache_candidates(model._h, None, i32(1).ctypes.data, i32(64).ctypes.data, out.ctypes.data) == 0
+    model.upload(dh)
+
+
+@pytest.mark.parametrize("dtype", ["fp32", "bf16"])
+def test_rank_cache_bank_row_len_36(models, dtype):
+    """the ranking cache with an adapter at row_len 36: a history of 31 events stored from a row of 36, 33 candidates in rows of 36 (T = 72,
+    the bank's half token tile; the candidates' explicit RoPE positions go through stage B), each against the untrimmed call"""
+    cfg, V, model, P, adapters = models("bank", dtype)
+    rng = np.random.default_rng(16)
+    medium = 1
+    u = tu.user_with_history(rng, 31, [int(x) for x in rng.choice(np.arange(1, V[medium]), 33, replace=False)])
+    ad = model.adapter_slots[f"{medium}.ranking"]
+    dh, nh = _hist_rows([u])
+    dc = _cand_rows(u, medium, 33)
+    dc["rope_input_pos"][0, :] = nh[0]
+    assert nh[0] == 31
+    model.rank_cache_store(dh, nh, [0], adapters=ad)
+    kv_full = [model.rank_cache_get(l, 0, nh[0]) for l in range(cfg["num_layers"])]
+    vals_ff = model.rank_cache_candidates(dc, [0], [33], adapters=ad)
+    vals_ft = model.rank_cache_candidates(dc, [0], [33], adapters=ad, row_len=36)
+    assert model.forward_tokens == 2 * 36
+    model.rank_cache_store(dh, nh, [1], adapters=ad, row_len=36)
+    assert model.forward_tokens == 2 * 36
+    for l in range(cfg["num_layers"]):
+        assert np.array_equal(kv_full[l], model.rank_cache_get(l, 1, nh[0])), l
+    vals_tf = model.rank_cache_candidates(dc, [1], [33], adapters=ad)
+    vals_tt = model.rank_cache_candidates(dc, [1], [33], adapters=ad, row_len=36)
+    for name, v in (("full/trimmed", vals_ft), ("trimmed/full", vals_tf), ("trimmed/trimmed", vals_tt)):
+        _same(v, vals_ff, None, dtype, f"rank cache bank row_len 36 store/candidates {name}")
+    base = model.rank_cache_candidates(dc, [1], [33], adapters=None, row_len=36)
+    assert not np.array_equal(base, vals_tt)                                               # the adapter was applied
     model.upload(dh)
 
 
