@@ -113,7 +113,9 @@ __device__ __forceinline__ bf16x8 frag_tr(const bf16* tile, int ld, int tok0, in
   return __builtin_shufflevector(t0, t1, 0, 1, 2, 3, 4, 5, 6, 7);
 }
 // The same fragments from an UNPADDED bf16 tile of 64 columns whose 16-byte chunks are XOR-swizzled (chunk c of row r in slot c ^ (r & 7)):
-// free of bank conflicts for both kinds of read, and what one LDS-DMA instruction can fill (attn_*_dma_kernel below).
+// free of bank conflicts for both kinds of read, and what one LDS-DMA instruction can fill (1 KB = 8 consecutive rows, the swizzle
+// applied on the SOURCE side: the lane that fills slot s of row r loads chunk s ^ (r & 7)); the DMA forms of attn_fwd_kernel and
+// attn_bwd_q_kernel below.
 __device__ __forceinline__ bf16x8 frag_rows_sw(const bf16* tile, int row0, int k0, int l) {
   const int row = row0 + (l & 15), ch = (k0 >> 3) + (l >> 4);
   return *(const bf16x8*)(tile + row * 64 + ((ch ^ (row & 7)) << 3));
@@ -467,9 +469,9 @@ __global__ __launch_bounds__(256) void attn_order_kernel(AttnParams p, int R, in
   constexpr int NTM = 1 << LG, OS = NTM + 2;
   const W *qmap = map_ptr<LG>(p.qmap), *kmap = map_ptr<LG>(p.kmap);
   extern __shared__ int ocnt[];   // [chunks of 64 slots + 1][OS]: slots per (chunk, key), then their exclusive prefixes; last row: totals / bases
-  const int side = blockIdx.y, nt = (p.T + 63) / 64, n_groups = p.B * p.KV;   // side 2: the forward kernel's (head, q tile PAIR) slots
-  const int n_inner = side == 0 ? (p.H / p.KV / R) * nt : side == 2 ? (p.H / p.KV) * ((nt + 1) / 2) : (kv_pairs ? (nt + 1) / 2 : nt);
-  int* out = side == 0 ? p.order_q : side == 2 ? p.order_q2 : p.order_k;
+  const int side = blockIdx.y, nt = (p.T + 63) / 64, n_groups = p.B * p.KV;
+  const int n_inner = side == 0 ? (p.H / p.KV / R) * nt : (kv_pairs ? (nt + 1) / 2 : nt);
+  int* out = side == 0 ? p.order_q : p.order_k;
   if (out == nullptr) return;
   const bool lists = (n_groups & 7) == 0;
   const int ns = lists ? (n_groups >> 3) * n_inner : n_groups * n_inner, xcd = blockIdx.x;
@@ -482,10 +484,6 @@ __global__ __launch_bounds__(256) void attn_order_kernel(AttnParams p, int R, in
     const int group = lists ? (sl / n_inner) * 8 + xcd : sl / n_inner, tile = (sl % n_inner) % nt, b = group / p.KV;
     const int qa = p.q_active != nullptr ? p.q_active[b] : NTM;
     if (side == 0) return tile < qa ? map_popc(qmap[b * nt + tile]) : 0;
-    if (side == 2) {
-      const int t0 = 2 * ((sl % n_inner) % ((nt + 1) / 2)), lim = min(nt, qa);
-      return map_popc((t0 < lim ? qmap[b * nt + t0] : (W)0) | (t0 + 1 < lim ? qmap[b * nt + t0 + 1] : (W)0));
-    }
     if (kv_pairs) {
       const int t0 = 2 * (sl % n_inner);
       const W u = kmap[b * nt + t0] | (t0 + 1 < nt ? kmap[b * nt + t0 + 1] : (W)0);
@@ -541,12 +539,12 @@ int launch_attn_tilemap(const AttnParams& p, hipStream_t s) {
   }
   if (wide) hipLaunchKernelGGL(attn_tilemap_kernel<6>, dim3((p.T + 63) / 64, p.B), dim3(256), 0, s, p);
   else hipLaunchKernelGGL(attn_tilemap_kernel<5>, dim3((p.T + 63) / 64, p.B), dim3(256), 0, s, p);
-  if (p.order_q != nullptr || p.order_k != nullptr || p.order_q2 != nullptr) {
+  if (p.order_q != nullptr || p.order_k != nullptr) {
     const int R = attn_heads_per_wg(p), nt = (p.T + 63) / 64, n_groups = p.B * p.KV;
     const int ns_max = ((n_groups & 7) == 0 ? (n_groups >> 3) : n_groups) * (p.H / p.KV) * nt;
     // (a list beyond one workgroup's LDS: keep the plain order -- the kernels read an identity permutation)
     const int cap = attn_order_chunk_cap(wide ? 6 : 5), nch = (ns_max + 63) / 64;
-    const dim3 og((n_groups & 7) == 0 ? 8 : 1, p.order_q2 != nullptr ? 3 : 2);
+    const dim3 og((n_groups & 7) == 0 ? 8 : 1, 2);
     if (wide) hipLaunchKernelGGL(attn_order_kernel<6>, og, dim3(256), (size_t)(std::min(nch, cap) + 1) * 66 * 4, s, p, R, nch > cap ? 1 : 0, attn_kv_pairs(p) ? 1 : 0);
     else hipLaunchKernelGGL(attn_order_kernel<5>, og, dim3(256), (size_t)(std::min(nch, cap) + 1) * 34 * 4, s, p, R, nch > cap ? 1 : 0, attn_kv_pairs(p) ? 1 : 0);
   }
@@ -668,43 +666,7 @@ __device__ __forceinline__ void dma16(at_i32x4 rsrc, unsigned char* lds, int vof
   if constexpr (ASM) dma16_asm(rsrc, (unsigned int)__builtin_amdgcn_readfirstlane((int)(unsigned int)(unsigned long long)(LDS_AS unsigned char*)lds), voffset, soffset);
   else rsys_at_buffer_load_lds(rsrc, (LDS_AS unsigned int*)lds, 16, voffset, soffset, 0, 0);
 }
-// store_grad_tile / copy_out_tile on one such 8 KB tile (the epilogue stages through a tile buffer it no longer needs)
-__device__ __forceinline__ void store_grad_tile_sw(f32x4 (&acc)[4], bool rotate, const float* rope_cos, const float* rope_sin, int pos, bf16* Os, int w, int l) {
-  const int g = l >> 4, fr = l & 15, row = w * 16 + fr;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    float o[4] = {acc[j][0], acc[j][1], acc[j][2], acc[j][3]};
-    if (rotate) {
-      const int d2 = (16 * j + 4 * g) >> 1;
-      const float2 cc = *(const float2*)(rope_cos + pos * 32 + d2);
-      const float2 ss = *(const float2*)(rope_sin + pos * 32 + d2);
-      const float a0 = o[0] * cc.x + o[1] * ss.x, a1 = -o[0] * ss.x + o[1] * cc.x;
-      const float b0 = o[2] * cc.y + o[3] * ss.y, b1 = -o[2] * ss.y + o[3] * cc.y;
-      o[0] = a0; o[1] = a1; o[2] = b0; o[3] = b1;
-    }
-    const int col = 16 * j + 4 * g;
-    bf16* dst = Os + row * 64 + (((col >> 3) ^ (row & 7)) << 3) + (col & 4);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) dst[r] = (bf16)o[r];
-  }
-}
-__device__ __forceinline__ void copy_out_tile_sw(const bf16* Os, bf16* dst, long long ld, int tile_tok0, int T_len, int t, float* amax = nullptr) {
-  float am = 0.f;
-#pragma unroll
-  for (int c = t; c < 512; c += 256) {
-    const int row = c >> 3, ch = c & 7;
-    if (tile_tok0 + row < T_len) {
-      const uint4 v = *(const uint4*)(Os + row * 64 + ((ch ^ (row & 7)) << 3));
-      *(uint4*)(dst + (long long)row * ld + ch * 8) = v;
-      if (amax != nullptr) am = fmaxf(am, chunk_amax<bf16>(v));
-    }
-  }
-  if (amax != nullptr) {
-    am = wave_max(am);
-    if ((t & 63) == 0) f8_amax_add(amax, am);
-  }
-}
-// 32 x 32 x 16 products (the 32-token-per-wave kernels: attn_fwd32_kernel, attn_bwd_kv32_kernel; LDS image and fragment maps: see the dK/dV kernel)
+// 32 x 32 x 16 products (the 32-token-per-wave kernel attn_bwd_kv32_kernel; LDS image and fragment maps: see there)
 typedef __attribute__((ext_vector_type(16))) float f32x16;
 __device__ __forceinline__ int sw32(int r) { return (((r >> 1) & 1) << 2) | (((r >> 2) & 1) << 1) | ((r >> 3) & 1); }
 __device__ __forceinline__ f32x16 mfma32(bf16x8 a, bf16x8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
@@ -718,7 +680,7 @@ __device__ __forceinline__ bf16x8 pack8f(const f32x16& v, int o) {
 // R = query heads per workgroup: the R heads of one kv head's group at the SAME 64 tokens (R = 1: one head).  They share the
 // staged K / V tile, every K and V^T fragment read, the tile maps and -- the mask depends on the tokens only -- the mask
 // predicates; soft-max statistics and the output accumulators are per head.
-// DMA (bf16, head_dim 64): the K / V tiles arrive by LDS-DMA in unpadded XOR-swizzled tiles (frag_rows_sw), as in attn_bwd_kv_dma_kernel.
+// DMA (bf16, head_dim 64): the K / V tiles arrive by LDS-DMA in unpadded XOR-swizzled tiles (frag_rows_sw).
 template <typename T, int HD, int R, bool DMA = false, int LG = 5>
 __global__ __launch_bounds__(256, (is_bf16<T>::value && HD <= 64) ? (R == 1 ? 3 : (DMA ? 3 : 2)) : 1) void attn_fwd_kernel(AttnParams p) {
   using C = ACfg<T, HD>;
@@ -880,223 +842,6 @@ __global__ __launch_bounds__(256, (is_bf16<T>::value && HD <= 64) ? (R == 1 ? 3 
 }
 
 
-// ------------------------------------------------------------------------ forward on v_mfma_f32_32x32x16_bf16 (bf16, head_dim 64; round 6)
-// The dK/dV recipe of round 5 (attn_bwd_kv32_kernel) for the forward pass: a wave owns 32 QUERIES (the lanes' l & 31), four waves = 128
-// queries = two q tiles of ONE head per workgroup; every staged K / V tile feeds all of them -- the staging per FLOP of the two-head 64-query
-// kernel above, half its MFMA instructions and fragment reads per FLOP, and one head's accumulators per wave (O 32 + S 32 + Q 16 registers):
-// compiled for FOUR waves per SIMD.
-//   S^T[kv][q] = sum_d K[kv][d] Q[q][d]:  A = K rows from LDS (ds_read_b128: row kv0 + (l & 31), d = 16 s + 8 (l >> 5) ..+7), B = Q from registers
-//   O^T[d][q] += V^T[d][kv] P[kv][q]:     the S accumulator registers 8 s .. 8 s + 7 ARE the B operand of k-step s (keys 16 s + 8 (j >> 2) +
-//   4 (l >> 5) + (j & 3)); A = V^T read transposed from the row-major tile (two ds_read_b64_tr_b16), exactly the dO^T operand of dV in the dK/dV kernel
-// Soft-max: a query's 64 scores of a tile sit in the 32 registers of lanes l and l ^ 32: row maximum and sum are lane-local plus ONE
-// v_permlane32_swap; the accumulators are rescaled only when some query's running maximum moved (wave-uniform test).
-#ifndef ATTN_FWD32_WPS
-#define ATTN_FWD32_WPS 4
-#endif
-__device__ __forceinline__ float pair_rows_max(float v) {   // over lanes l, l ^ 32
-  const unsigned int u = __builtin_bit_cast(unsigned int, v);
-  auto b = __builtin_amdgcn_permlane32_swap(u, u, false, false);
-  return fmaxf(__builtin_bit_cast(float, (unsigned int)b[0]), __builtin_bit_cast(float, (unsigned int)b[1]));
-}
-__device__ __forceinline__ float pair_rows_sum(float v) {
-  const unsigned int u = __builtin_bit_cast(unsigned int, v);
-  auto b = __builtin_amdgcn_permlane32_swap(u, u, false, false);
-  return __builtin_bit_cast(float, (unsigned int)b[0]) + __builtin_bit_cast(float, (unsigned int)b[1]);
-}
-template <int LG>
-__global__ __launch_bounds__(256, ATTN_FWD32_WPS) void attn_fwd32_kernel(AttnParams p) {
-  constexpr int HD = 64, TB = 64 * 64;   // elements of an unpadded tile
-  using T = bf16;
-  using W = typename AMap<LG>::W;
-  const W *qmap = map_ptr<LG>(p.qmap), *qmap_full = map_ptr<LG>(p.qmap_full), *qmap16 = map_ptr<LG>(p.qmap16);
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-  unsigned char* const Kb = smem_raw;                 // [2][64 kv][128 B] swizzled (sw32)
-  unsigned char* const Vb = smem_raw + 2 * TB * 2;    // [2][64 kv][128 B]
-  const int rep = p.H / p.KV, nt = (p.T + 63) / 64, npair = (nt + 1) / 2;
-  int grp, inner;
-  attn_work(p.B * p.KV, rep * npair, p.order_q2, grp, inner);
-  const int b = grp / p.KV, kvh = grp % p.KV, hh = kvh * rep + inner / npair, pr = inner % npair;
-  const int qa = p.q_active != nullptr ? min(p.q_active[b], nt) : nt;   // q tiles >= qa: nobody reads their output
-  if (2 * pr >= qa) return;                                            // (uniform: whole workgroup)
-  const int t = threadIdx.x, l = t & 63, r32 = l & 31, h = l >> 5;
-  const int w = __builtin_amdgcn_readfirstlane(t >> 6);
-  const int qt = 2 * pr + (w >> 1);                   // this wave's q tile (may be inactive: the wave then only stages)
-  const bool tile_ok = qt < qa;
-  const long long tok0 = (long long)b * p.T;
-  const float c2 = rsqrtf((float)HD) * LOG2E;        // scores are handled in log2 units
-  const int q = qt * 64 + 32 * (w & 1) + r32;        // this lane's query
-  const bool qv = tile_ok && q < p.T;
-  bf16x8 qf[4];
-  {
-    const T* qrow = (const T*)p.q + (tok0 + min(q, p.T - 1)) * p.ld + hh * HD;
-#pragma unroll
-    for (int s = 0; s < 4; ++s) qf[s] = *(const bf16x8*)(qrow + 16 * s + 8 * h);
-  }
-  f32x16 O[2];
-#pragma unroll
-  for (int i = 0; i < 16; ++i) { O[0][i] = 0.f; O[1][i] = 0.f; }
-  float m_run = -1e30f, l_run = 0.f;
-  const int t0i = b * nt + 2 * pr, t1i = b * nt + min(2 * pr + 1, nt - 1), qti = b * nt + min(qt, nt - 1);
-  const W bits = map_uniform((W)(qmap[t0i] | (2 * pr + 1 < qa ? qmap[t1i] : (W)0)));   // kv tiles the workgroup stages
-  const W fullbits = tile_ok ? map_uniform(qmap_full[qti]) : (W)0;
-  const W wbits = tile_ok ? map_uniform((W)(qmap16[qti * 4 + 2 * (w & 1)] | qmap16[qti * 4 + 2 * (w & 1) + 1])) : (W)0;
-  const at_i32x4 k_rs = at_rsrc((const T*)p.k + tok0 * p.ld + kvh * HD, ((long long)(p.T - 1) * p.ld + HD) * sizeof(T));
-  const at_i32x4 v_rs = at_rsrc((const T*)p.v + tok0 * p.ld + kvh * HD, ((long long)(p.T - 1) * p.ld + HD) * sizeof(T));
-  // the pair bits of this wave's q tile against every kv tile: [nt][64 queries] words (an inactive tile: an empty window, all zero)
-  const at_i32x4 qb_rs = at_rsrc(p.qbits + (long long)qti * nt * 64, tile_ok ? (long long)nt * 64 * 8 : 0);
-  // wave w fills rows 16 w .. 16 w + 15 of each tile with two DMA instructions (8 rows = 1 KB each): per-lane source offsets, fixed
-  int dv_[2];
-#pragma unroll
-  for (int k = 0; k < 2; ++k) {
-    const int row = 16 * w + 8 * k + (l >> 3), ch = (l & 7) ^ sw32(row);
-    dv_[k] = (int)((row * p.ld + ch * 8) * sizeof(T));
-  }
-  // fragment addresses inside a tile (bytes; lane constants), as in attn_bwd_kv32_kernel:
-  //   row reads: row kv0 + r32, chunk 2 s + h -> slot (2 s) ^ G, G = h ^ sw32(r32)
-  //   transposed reads: row kv0 + 16 s2 + 8 u + 4 h + (i >> 2), columns 32 db + 16 g16 + 4 (i & 3) -> slot L ^ (4 db) ^ u
-  const int G = h ^ sw32(r32);
-  const int i16 = l & 15, g16 = (l >> 4) & 1;
-  const int Lc = (2 * g16 + ((i16 & 3) >> 1)) ^ ((((i16 >> 2) >> 1) & 1) << 2 | (h << 1));
-  int a_row[4], a_tr[4];
-#pragma unroll
-  for (int s = 0; s < 4; ++s) a_row[s] = r32 * 128 + (((2 * s) ^ G) << 4);
-#pragma unroll
-  for (int v = 0; v < 4; ++v) a_tr[v] = (4 * h + (i16 >> 2)) * 128 + ((Lc ^ ((v >> 1) << 2) ^ (v & 1)) << 4) + ((i16 & 1) << 3);   // v = 2 db + u
-  const unsigned int lds0 = (unsigned int)__builtin_amdgcn_readfirstlane((int)(unsigned int)(unsigned long long)(LDS_AS unsigned char*)smem_raw);
-  unsigned long long sqb = 0ull;   // this lane's pair-bit word of the next tile on its way
-  auto stage = [&](int kt, int buf) {
-    const int so = (int)(kt * 64 * p.ld * sizeof(T));
-    const unsigned int kd = lds0 + buf * (TB * 2) + (16 * w) * 128, vd = kd + 2 * TB * 2;
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-      dma16_asm(k_rs, kd + k * 1024, dv_[k], so);
-      dma16_asm(v_rs, vd + k * 1024, dv_[k], so);
-    }
-    sqb = __builtin_bit_cast(unsigned long long, rsys_at_buffer_load_b64(qb_rs, 8 * (32 * (w & 1) + r32), kt * 512, 0));   // this query's keys of tile kt
-  };
-  int kt = next_bit(bits, 0), cur = 0;
-  unsigned long long wq = 0ull;
-  if (kt < nt) { stage(kt, 0); asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); wq = sqb; }
-  // the Q fragments' loads are retired here in the compiler's bookkeeping (see dma16 / attn_bwd_kv32_kernel)
-#pragma unroll
-  for (int s = 0; s < 4; ++s) asm volatile("" : "+v"(qf[s]));
-  asm volatile("" : "+v"(wq));
-  __syncthreads();
-  while (kt < nt) {
-    const int nxt = next_bit(bits, kt + 1);
-    if (nxt < nt) stage(nxt, cur ^ 1);   // (the other buffer: every wave left it before the barrier that ended the previous tile)
-    if ((wbits >> kt) & 1u) {            // (a wave whose 32 queries have no allowed key in this tile leaves its state untouched)
-      const unsigned char* Kc = Kb + cur * (TB * 2);
-      const unsigned char* Vc = Vb + cur * (TB * 2);
-      const bool fullt = (fullbits >> kt) & 1u;
-      f32x16 S[2];
-#pragma unroll
-      for (int kb = 0; kb < 2; ++kb) {   // 32 keys at a time: accumulator register r = key 32 kb + 8 (r >> 2) + 4 h + (r & 3)
-        const unsigned int w32 = (unsigned int)(kb ? (wq >> 32) : wq);
-        // the mask enters the score chain as its starting value (0 / -1e30); a 32 x 32 block of which every pair is allowed needs none
-        if (!fullt && __builtin_amdgcn_ballot_w64(w32 != 0xFFFFFFFFu) != 0ull) {
-          const int src = (int)(w32 >> (4 * h));
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            const int m = __builtin_amdgcn_sbfe(src, 8 * (r >> 2) + (r & 3), 1);
-            S[kb][r] = __builtin_bit_cast(float, __builtin_bit_cast(int, -1e30f) & ~m);
-          }
-        } else {
-#pragma unroll
-          for (int r = 0; r < 16; ++r) S[kb][r] = 0.f;
-        }
-#pragma unroll
-        for (int s = 0; s < 4; ++s) S[kb] = mfma32(*(const bf16x8*)(Kc + kb * 4096 + a_row[s]), qf[s], S[kb]);   // S^T[kv][q]
-      }
-      float tmax = -1e30f;
-#ifndef ATTN_FWD32_TIMING_NOMAX   // (timing-only builds, tools/: what the row maximum, the exponential and the row sum cost)
-#pragma unroll
-      for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) tmax = fmaxf(tmax, S[kb][r]);
-      tmax = pair_rows_max(tmax);
-#else
-      tmax = 0.25f;
-#endif
-      const float m_new = fmaxf(m_run, tmax * c2);
-      const float mu_old = fmaxf(m_run, -1e20f), mu_new = fmaxf(m_new, -1e20f);
-      const float alpha = fexp2(mu_old - mu_new);
-      float psum = 0.f;
-#pragma unroll
-      for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-#ifdef ATTN_FWD32_TIMING_NOEXP
-          const float pv = fmaf(S[kb][r], c2, -mu_new);
-#else
-          const float pv = fexp2(fmaf(S[kb][r], c2, -mu_new));   // masked entries: exp2(-1.8e29) = 0
-#endif
-          S[kb][r] = pv;
-#ifndef ATTN_FWD32_TIMING_NOSUM
-          psum += pv;
-#endif
-        }
-      psum = pair_rows_sum(psum);
-      l_run = l_run * alpha + psum;
-      m_run = m_new;
-      if (__builtin_amdgcn_ballot_w64(alpha != 1.0f) != 0ull) {   // (some query's maximum moved: after the first tiles of a user it rarely does)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) { O[0][i] *= alpha; O[1][i] *= alpha; }
-      }
-#pragma unroll
-      for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-        for (int s2 = 0; s2 < 2; ++s2) {   // k-step = 16 keys: accumulator registers 8 s2 .. 8 s2 + 7
-          const bf16x8 pf = pack8f(S[kb], 8 * s2);
-#pragma unroll
-          for (int db = 0; db < 2; ++db) {
-            const int o = (32 * kb + 16 * s2) * 128;
-            const bf16x4 v0 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((LDS_AS bf16x4*)(Vc + o + a_tr[2 * db]));
-            const bf16x4 v1 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((LDS_AS bf16x4*)(Vc + o + 8 * 128 + a_tr[2 * db + 1]));
-            O[db] = mfma32(__builtin_shufflevector(v0, v1, 0, 1, 2, 3, 4, 5, 6, 7), pf, O[db]);   // O^T[d][q] += V^T[d][kv] P[kv][q]
-          }
-        }
-    }
-    if (nxt < nt) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's DMA of the next tile landed (the barrier publishes it)
-    __syncthreads();
-    wq = sqb;
-    cur ^= 1;
-    kt = nxt;
-  }
-  // epilogue: O as bf16 rows [query][64] through the two K buffers (128 queries x 128 bytes), then row stores.
-  // accumulator register r of block db: d = 32 db + 8 (r >> 2) + 4 h + (r & 3), query = r32 of this wave
-  const float inv = l_run > 0.f ? 1.f / l_run : 0.f;
-  if (h == 0 && qv) p.lse[((long long)b * p.H + hh) * p.T + q] = (m_run + log2f(l_run)) * (1.f / LOG2E);
-  const int orow = 32 * w + r32;
-#pragma unroll
-  for (int db = 0; db < 2; ++db)
-#pragma unroll
-    for (int g4 = 0; g4 < 4; ++g4) {
-      const int d = 32 * db + 8 * g4 + 4 * h;
-      bf16x4 oo; oo[0] = (bf16)(O[db][4 * g4] * inv); oo[1] = (bf16)(O[db][4 * g4 + 1] * inv); oo[2] = (bf16)(O[db][4 * g4 + 2] * inv); oo[3] = (bf16)(O[db][4 * g4 + 3] * inv);
-      // (chunk slot permuted by the row so that the 8-byte stores of a half-wave spread over the banks; the copy below undoes it)
-      *(bf16x4*)(Kb + orow * 128 + ((((d >> 3) ^ (orow & 7)) << 4) | ((d & 4) << 1))) = oo;
-    }
-  __syncthreads();
-  {
-    float am = 0.f;
-#pragma unroll
-    for (int c = t; c < 128 * 8; c += 256) {   // 16-byte chunks of the 128 rows
-      const int row = c >> 3, ch = c & 7;
-      const int tile = 2 * pr + (row >> 6), tok = tile * 64 + (row & 63);
-      if (tile < qa && tok < p.T) {
-        const uint4 v = *(const uint4*)(Kb + row * 128 + ((ch ^ (row & 7)) << 4));
-        *(uint4*)((T*)p.o + (tok0 + tok) * p.ldo + hh * HD + ch * 8) = v;
-        if (p.f8_amax != nullptr) am = fmaxf(am, chunk_amax<bf16>(v));
-      }
-    }
-    if (p.f8_amax != nullptr) {
-      am = wave_max(am);
-      if (l == 0) f8_amax_add(p.f8_amax, am);
-    }
-  }
-}
-
 // query heads per workgroup of the forward / dQ kernels: the whole group of a kv head when that is 2 (every configuration of
 // H / KV = 2), else 1.
 static bool attn_dma_on() { return sw().attn_dma != 0; }
@@ -1115,14 +860,6 @@ static int attn_fwd_hd(const AttnParams& p, hipStream_t s) {
     set = true;
   }
   if constexpr (is_bf16<T>::value && HD == 64) {
-    if (attn_dma_on() && sw().attn_fwd32 != 0) {   // RSYS_ATTN_FWD32=1 (opt-in): 128 queries of one head per workgroup on 32 x 32 x 16 products
-      static bool set32 = false;
-      if (!set32) { HIP_CHECK(hipFuncSetAttribute((const void*)attn_fwd32_kernel<LG>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 64 * 64 * 2)); set32 = true; }
-      const int nt = (p.T + 63) / 64;
-      hipLaunchKernelGGL(attn_fwd32_kernel<LG>, dim3(((nt + 1) / 2) * p.H * p.B), dim3(256), 4 * 64 * 64 * 2, s, p);
-      HIP_CHECK(hipGetLastError());
-      return RSYS_OK;
-    }
     if (attn_dma_on()) {   // LDS-DMA staging (RSYS_ATTN_DMA=0: the register-staged kernels)
       const size_t sm_dma = 4 * 64 * 64 * 2 + 384 * 4;
       if (attn_heads_per_wg(p) == 2) hipLaunchKernelGGL((attn_fwd_kernel<T, HD, 2, true, LG>), dim3(((p.T + 63) / 64) * (p.H / 2) * p.B), dim3(256), sm_dma, s, p);
@@ -1332,180 +1069,15 @@ __global__ __launch_bounds__(256, (is_bf16<T>::value && HD <= 64) ? 3 : 1) void 
 }
 
 
-// ------------------------------------------------------------------------ dK, dV with LDS-DMA staging (bf16, head_dim 64)
-// The same kernel with the Q / dO tiles brought in by `buffer_load ... lds` (no staging registers, no LDS stores) into UNPADDED tiles:
-// a 64-column bf16 row is 128 bytes = 8 chunks of 16, chunk c of row r sits in slot c ^ (r & 7).  By the guide's lane groups that
-// layout is free of bank conflicts for the natural ds_read_b128 fragments and for both ds_read_b64_tr_b16 reads (as the 160-byte rows
-// are), it is what a DMA instruction can fill (1 KB = 8 consecutive rows, the swizzle applied on the SOURCE side: the lane that fills
-// slot s of row r loads chunk s ^ (r & 7)), and it makes a tile 8 KB: 34 KB per workgroup and ~110 registers -- four workgroups per CU.
-// -DATTN_KV_TRACE (tools/trace_attn_kv.sh; never in the product build): wave 0 of every workgroup stamps the wall clock (10 ns) at entry,
-// after the first item is staged, after the item loop and at exit, and sums the item loop's phases -- issue of the next item's DMA and
-// scalar loads, arithmetic, publishing (waits for the DMA), barrier.  rsys_attn_trace_read copies the table out.
+// -DATTN_KV_TRACE (tools/trace_attn_kv.sh; never in the product build): wave 0 of every attn_bwd_kv32_kernel workgroup stamps the wall
+// clock (10 ns) at entry, after the first item is staged, after the item loop and at exit, and sums the item loop's phases -- issue of the
+// next item's DMA and scalar loads, arithmetic, publishing (waits for the DMA), barrier.  rsys_attn_trace_read copies the table out.
 #ifdef ATTN_KV_TRACE
 __device__ unsigned long long rsys_attn_trace[16 * 8192];
 #define KVT_NOW() ((unsigned long long)wall_clock64())
 #else
 #define KVT_NOW() 0ull
 #endif
-template <int LG>
-__global__ __launch_bounds__(256, 4) void attn_bwd_kv_dma_kernel(AttnParams p) {
-  [[maybe_unused]] unsigned long long tr_[12] = {KVT_NOW(), 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-  constexpr int HD = 64, TB = 64 * 64;   // elements of an unpadded tile
-  using T = bf16;
-  using C = ACfg<T, HD>;
-  using W = typename AMap<LG>::W;
-  constexpr int NTM = 1 << LG;   // item = head of the group * NTM + q tile
-  // (The compiler orders an LDS read behind a pending LDS-DMA unless it can tell the two apart, so each item starts with a wait for the
-  // next item's DMA it has just issued; the other three workgroups of the CU run meanwhile.  Telling them apart was tried -- one LDS
-  // object per buffer and the item loop unrolled by two: no wait, but 158 registers = three workgroups per CU and 209 against 198 us, or
-  // 30 spilled registers at four; profiles/r4_ab_attn_kv_dma.log.)
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-  T* Qs = (T*)smem_raw;                  // [2][64 q][64] swizzled
-  T* dOs = Qs + 2 * TB;                  // [2][64 q][64] swizzled
-  float* lse2 = (float*)(dOs + 2 * TB);  // [2][64]
-  float* dls = lse2 + 128;               // [2][64]
-  unsigned long long* kbs = (unsigned long long*)(dls + 128);   // [2][64]
-  const int rep = p.H / p.KV, nt = (p.T + 63) / 64;
-  int grp, kvt;
-  attn_work(p.B * p.KV, nt, p.order_k, grp, kvt);
-  const int b = grp / p.KV, kvh = grp % p.KV;
-  const int t = threadIdx.x, l = t & 63, w = t >> 6, g = l >> 4, fr = l & 15;
-  const long long tok0 = (long long)b * p.T;
-  const float scale = rsqrtf((float)HD), c2 = scale * LOG2E;
-  const int kv = kvt * 64 + w * 16 + fr;       // this lane's key/value token
-  bf16x8 kf[2], vf[2];
-  {
-    const T* krow = (const T*)p.k + (tok0 + min(kv, p.T - 1)) * p.ld + kvh * HD;
-    const T* vrow = (const T*)p.v + (tok0 + min(kv, p.T - 1)) * p.ld + kvh * HD;
-#pragma unroll
-    for (int s = 0; s < 2; ++s) { kf[s] = frag_global<T>(krow, s * 32, HD, l); vf[s] = frag_global<T>(vrow, s * 32, HD, l); }
-  }
-  f32x4 dK[1][4], dV[1][4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) { dK[0][j] = f32x4{0, 0, 0, 0}; dV[0][j] = f32x4{0, 0, 0, 0}; }
-  const int qa = p.q_active != nullptr ? p.q_active[b] : NTM;
-  const W act = map_below<LG>(qa);
-  const W bits = map_ptr<LG>(p.kmap)[b * nt + kvt] & act, fullbits = map_ptr<LG>(p.kmap_full)[b * nt + kvt];
-  const W wbits = map_uniform(map_ptr<LG>(p.kmap16)[(b * nt + kvt) * 4 + w]);
-  const at_i32x4 q_rs = at_rsrc((const T*)p.q + tok0 * p.ld + kvh * rep * HD, ((long long)(p.T - 1) * p.ld + rep * HD) * sizeof(T));
-  const at_i32x4 do_rs = at_rsrc((const T*)p.dO + tok0 * p.ldo + kvh * rep * HD, ((long long)(p.T - 1) * p.ldo + rep * HD) * sizeof(T));
-  const at_i32x4 lse_rs = at_rsrc(p.lse + ((long long)b * p.H + kvh * rep) * p.T, (long long)rep * p.T * 4);
-  const at_i32x4 dl_rs = at_rsrc(p.delta + ((long long)b * p.H + kvh * rep) * p.T, (long long)rep * p.T * 4);
-  const at_i32x4 kb_rs = at_rsrc(p.kbits + ((long long)b * nt + kvt) * nt * 64, (long long)nt * 64 * 8);
-  const bool w0 = __builtin_amdgcn_readfirstlane(w) == 0;
-  // wave w fills rows 16 w .. 16 w + 15 of each tile with two DMA instructions (8 rows = 1 KB each): per-lane source offsets, fixed
-  int qv_[2], dv_[2];
-#pragma unroll
-  for (int k = 0; k < 2; ++k) {
-    const int row = 16 * w + 8 * k + (l >> 3), ch = (l & 7) ^ (row & 7);
-    qv_[k] = (int)((row * p.ld + ch * 8) * sizeof(T));
-    dv_[k] = (int)((row * p.ldo + ch * 8) * sizeof(T));
-  }
-  int sx = 0, sy = 0; unsigned long long skb = 0ull;   // (wave 0) the next item's row scalars on their way to LDS
-  auto stage = [&](int it, int buf) {   // it = head-in-group * NTM + q tile
-    const int hh = it >> LG, qt = it & (NTM - 1);
-    const int qso = (int)((qt * 64 * p.ld + hh * HD) * sizeof(T)), dso = (int)((qt * 64 * p.ldo + hh * HD) * sizeof(T));
-    unsigned char* qd = (unsigned char*)(Qs + buf * TB) + (16 * w) * 128;
-    unsigned char* dd = (unsigned char*)(dOs + buf * TB) + (16 * w) * 128;
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-      dma16<true>(q_rs, qd + k * 1024, qv_[k], qso);
-      dma16<true>(do_rs, dd + k * 1024, dv_[k], dso);
-    }
-    if (w0) {
-      const int so = (hh * p.T + qt * 64) * 4;
-      sx = rsys_at_buffer_load_b32(lse_rs, 4 * l, so, 0);   // (raw: used, and therefore waited for, only when published)
-      sy = rsys_at_buffer_load_b32(dl_rs, 4 * l, so, 0);
-      skb = __builtin_bit_cast(unsigned long long, rsys_at_buffer_load_b64(kb_rs, 8 * l, qt * 512, 0));
-    }
-  };
-  auto publish = [&](int buf) {   // the scalars into LDS; every DMA of this wave landed
-    if (w0) { lse2[buf * 64 + l] = __builtin_bit_cast(float, sx) * LOG2E; ((int*)dls)[buf * 64 + l] = sy ^ 0x80000000; kbs[buf * 64 + l] = skb; }   // log2 units; -delta
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  };
-  auto next_item = [&](int from) {
-    int hh = from >> LG, qt = from & (NTM - 1);
-    while (hh < rep) {
-      const int n = next_bit(bits, qt);
-      if (n < nt) return hh * NTM + n;
-      ++hh; qt = 0;
-    }
-    return rep * NTM;
-  };
-  const int end = rep * NTM;
-  int it = next_item(0), cur = 0;
-  if (it < end) { stage(it, 0); publish(0); }
-  __syncthreads();
-  tr_[1] = KVT_NOW();
-  while (it < end) {
-    [[maybe_unused]] const unsigned long long ta = KVT_NOW();
-    const int nxt = next_item(it + 1);
-    if (nxt < end) stage(nxt, cur ^ 1);   // (the other buffer: every wave left it before the barrier that ended the previous item)
-    [[maybe_unused]] const unsigned long long tb = KVT_NOW();
-    const T* Qc = Qs + cur * TB;
-    const T* dOc = dOs + cur * TB;
-    if ((wbits >> (it & (NTM - 1))) & 1u) {
-      const bool fullt = (fullbits >> (it & (NTM - 1))) & 1u;
-      const unsigned long long wk = kbs[cur * 64 + w * 16 + fr] >> (4 * g);
-#pragma unroll
-      for (int t2 = 0; t2 < 2; ++t2) {
-        f32x4 P2[2], dS2[2];
-#pragma unroll
-        for (int ii = 0; ii < 2; ++ii) {
-          const int i = 2 * t2 + ii;
-          const float4 l4 = *(const float4*)(lse2 + cur * 64 + 16 * i + 4 * g);
-          const float4 d4 = *(const float4*)(dls + cur * 64 + 16 * i + 4 * g);
-          const float ll[4] = {l4.x, l4.y, l4.z, l4.w};
-          f32x4 S[1] = {f32x4{0, 0, 0, 0}}, dP = f32x4{d4.x, d4.y, d4.z, d4.w};
-#pragma unroll
-          for (int s2 = 0; s2 < 2; ++s2) {
-            S[0] = AMma<bf16>::mma(frag_rows_sw(Qc, 16 * i, 32 * s2, l), kf[s2], S[0]);       // S[q][kv]
-            dP = AMma<bf16>::mma(frag_rows_sw(dOc, 16 * i, 32 * s2, l), vf[s2], dP);          // dP[q][kv] - delta[q]
-          }
-          if (!fullt) mask_bits_block<1>(S, wk, i, -1e30f);
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const float pv = fexp2(fmaf(S[0][r], c2, -ll[r]));
-            P2[ii][r] = pv;
-            dS2[ii][r] = pv * dP[r];
-          }
-        }
-        const bf16x8 pf = pack8(P2[0], P2[1]), sf = pack8(dS2[0], dS2[1]);
-#pragma unroll
-        for (int jd = 0; jd < 4; ++jd) {
-          dV[0][jd] = AMma<bf16>::mma(frag_tr_sw(dOc, 32 * t2, 16 * jd, l), pf, dV[0][jd]);   // dV^T[d][kv] += dO^T[d][q] P[q][kv]
-          dK[0][jd] = AMma<bf16>::mma(frag_tr_sw(Qc, 32 * t2, 16 * jd, l), sf, dK[0][jd]);    // dK^T[d][kv] += Q^T[d][q] dS[q][kv]
-        }
-      }
-    }
-#ifdef ATTN_KV_TRACE
-    asm volatile("" ::"v"(dK[0][0]), "v"(dV[0][0]));
-    const unsigned long long tc = KVT_NOW();
-#endif
-    if (nxt < end) publish(cur ^ 1);
-    [[maybe_unused]] const unsigned long long td = KVT_NOW();
-    __syncthreads();
-#ifdef ATTN_KV_TRACE
-    const unsigned long long te = KVT_NOW();
-    tr_[4] += tb - ta; tr_[5] += tc - tb; tr_[6] += td - tc; tr_[7] += te - td; tr_[8] += 1; tr_[9] += (wbits >> (it & (NTM - 1))) & 1u;
-#endif
-    cur ^= 1;
-    it = nxt;
-  }
-  tr_[2] = KVT_NOW();
-  const int pos = p.rope_pos ? p.rope_pos[tok0 + min(kv, p.T - 1)] : min(kv, p.T - 1);
-#pragma unroll
-  for (int j = 0; j < 4; ++j) dK[0][j] *= scale;
-  store_grad_tile_sw(dK[0], true, p.rope_cos, p.rope_sin, pos, Qs, w, l);    // (dK through one Q buffer, dV through the other: one barrier fewer)
-  store_grad_tile_sw(dV[0], false, p.rope_cos, p.rope_sin, pos, Qs + TB, w, l);
-  __syncthreads();
-  copy_out_tile_sw(Qs, (T*)p.dk + (tok0 + kvt * 64) * p.ldg + kvh * HD, p.ldg, kvt * 64, p.T, t, p.f8_amax ? p.f8_amax + 1 : nullptr);
-  copy_out_tile_sw(Qs + TB, (T*)p.dv + (tok0 + kvt * 64) * p.ldg + kvh * HD, p.ldg, kvt * 64, p.T, t, p.f8_amax ? p.f8_amax + 2 : nullptr);
-#ifdef ATTN_KV_TRACE
-  tr_[3] = KVT_NOW();
-  if (threadIdx.x == 0 && blockIdx.x < 8192) for (int i = 0; i < 12; ++i) rsys_attn_trace[blockIdx.x * 16 + i] = tr_[i];
-#endif
-}
 
 // ------------------------------------------------------------------------ dK, dV on v_mfma_f32_32x32x16_bf16 (bf16, head_dim 64)
 // The item loops above are bound by instruction ISSUE (profiles/r4_pmc_attention_sq.txt: the waves' active cycles add up to the SIMDs'
@@ -1518,10 +1090,7 @@ __global__ __launch_bounds__(256, 4) void attn_bwd_kv_dma_kernel(AttnParams p) {
 // LDS image: unpadded 128-byte rows, 16-byte chunk c of row r in slot c ^ sw32(r), sw32(r) = (r1, r2, r3) as bits (2, 1, 0): with that
 // permutation the 32-row ds_read_b128 fragments (lane groups {0-3, 12-15, 20-27}, ...) and the 4-row x 4-chunk transposed reads of a
 // 32-lane half both touch every bank once (checked against the guide's lane groups; the 16-row kernels' c ^ (r & 7) is 2-way here).
-static bool attn_kv32_on() { return sw().attn_kv32 != 0; }   // 0 = the 16-key-per-wave kernel
-static bool attn_kv_pairs(const AttnParams& p) {   // (bf16 is the caller's business: the fp32 launches never read order_k's pair form)
-  return p.hd == 64 && p.is_bf16 && sw().attn_kv_dma != 0 && attn_dma_on() && attn_kv32_on();
-}
+static bool attn_kv_pairs(const AttnParams& p) { return p.hd == 64 && p.is_bf16 && attn_dma_on(); }
 #ifndef ATTN_KV32_WPS
 #define ATTN_KV32_WPS 3   // waves per SIMD the kernel is compiled for: 168 registers, 5 dwords spilled OUTSIDE the item loop; 2 (189 registers) is 9 % slower (profiles/r5_ab_attn_kv32.log)
 #endif
@@ -1955,15 +1524,9 @@ static int attn_bwd_hd(const AttnParams& p, hipStream_t s) {
   // (two adjacent kv tiles per workgroup -- Q / dO staging and every fragment read shared by 32 keys per wave -- measured 6 % slower:
   // 254 registers, two waves per SIMD; profiles/r4_ab_attn_dkv_two_key_tiles.log)
   if constexpr (is_bf16<T>::value && HD == 64) {
-    const bool dma = sw().attn_kv_dma != 0;   // A/B switch of this kernel alone
     if (attn_kv_pairs(p)) {   // 32 keys per wave on 32 x 32 x 16 products, two kv tiles per workgroup (order_k lists the pairs)
       const int npair = ((p.T + 63) / 64 + 1) / 2;
       hipLaunchKernelGGL(attn_bwd_kv32_kernel<LG>, dim3(npair * p.KV * p.B), dim3(256), 4 * 64 * 64 * 2 + 256 * 4, s, p);
-      HIP_CHECK(hipGetLastError());
-      return RSYS_OK;
-    }
-    if (dma && attn_dma_on()) {
-      hipLaunchKernelGGL(attn_bwd_kv_dma_kernel<LG>, dim3(((p.T + 63) / 64) * p.KV * p.B), dim3(256), 4 * 64 * 64 * 2 + 512 * 4, s, p);
       HIP_CHECK(hipGetLastError());
       return RSYS_OK;
     }

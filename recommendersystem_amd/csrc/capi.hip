@@ -1009,12 +1009,12 @@ int32_t rsys_op_attention_ex(int32_t dtype, int32_t B, int32_t T, int32_t H, int
   unsigned int* maps = nullptr; float* delta = nullptr;
   unsigned long long* pairbits = nullptr;
   const size_t mw = (size_t)attn_map_words(T) * B * nt;   // words of one [B][nt] map
-  HIP_CHECK(hipMalloc((void**)&maps, sizeof(unsigned int) * (12 * mw + (size_t)B * (2 * H + KV) * nt)));
+  HIP_CHECK(hipMalloc((void**)&maps, sizeof(unsigned int) * (12 * mw + (size_t)B * (H + KV) * nt)));
   HIP_CHECK(hipMalloc((void**)&pairbits, sizeof(unsigned long long) * 2 * (size_t)B * nt * nt * 64));
   HIP_CHECK(hipMalloc((void**)&delta, sizeof(float) * B * H * T));
   p.qmap = maps; p.kmap = maps + mw; p.qmap_full = maps + 2 * mw; p.kmap_full = maps + 3 * mw; p.delta = delta;
   p.qmap16 = maps + 4 * mw; p.kmap16 = maps + 8 * mw;
-  p.order_q = (int*)(maps + 12 * mw); p.order_k = p.order_q + (size_t)B * H * nt; p.order_q2 = p.order_k + (size_t)B * KV * nt;
+  p.order_q = (int*)(maps + 12 * mw); p.order_k = p.order_q + (size_t)B * H * nt;
   p.qbits = pairbits; p.kbits = pairbits + (size_t)B * nt * nt * 64;
   p.dO = dO; p.dq = dqkv; p.dk = (unsigned char*)dqkv + (size_t)H * hd * e;
   p.dv = (unsigned char*)dqkv + (size_t)(H + KV) * hd * e; p.ldg = p.ld;
@@ -1295,9 +1295,7 @@ int32_t rsys_op_timing(rsys_model* h, int32_t enable) {
   if (enable == 3) { m->timer.enabled = false; return RSYS_OK; }   // pause: stop recording, keep what was recorded, no host wait (read it later with rsys_timing_get)
   HIP_CHECK(hipSetDevice(m->device));
   HIP_CHECK(hipStreamSynchronize(m->stream));
-  m->timer.enabled = enable != 0;
-  m->timer.serialize = enable == 2;
-  HIP_CHECK(hipStreamSynchronize(m->side));
+  m->timer.enabled = enable != 0;   // (2 is accepted and means 1)
   m->timer.marks.clear(); m->timer.acc_ms.clear(); m->timer.used = 0; m->timer.open.clear();
   if (!enable) m->timer.filter.clear();
   return RSYS_OK;
@@ -1315,7 +1313,6 @@ int32_t rsys_timing_get(rsys_model* h, char* buf, size_t cap) {
   Model* m = h->m;
   HIP_CHECK(hipSetDevice(m->device));
   HIP_CHECK(hipStreamSynchronize(m->stream));
-  HIP_CHECK(hipStreamSynchronize(m->side));
   PhaseTimer& t = m->timer;
   std::map<std::string, std::pair<double, long>> agg;
   std::vector<size_t> stack;

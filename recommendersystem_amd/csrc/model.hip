@@ -149,11 +149,6 @@ int model_create(const rsys_config* cfg, int device, Model** out) {
   m->row_lo = (int)((int64_t)m->sh_rank * (m->V + 1) / m->sh_world);
   m->TR = (int)((int64_t)(m->sh_rank + 1) * (m->V + 1) / m->sh_world) - m->row_lo;
   HIP_CHECK(hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking));
-  HIP_CHECK(hipStreamCreateWithFlags(&m->side, hipStreamNonBlocking));
-  HIP_CHECK(hipEventCreateWithFlags(&m->ev_fork, hipEventDisableTiming));
-  HIP_CHECK(hipEventCreateWithFlags(&m->ev_join, hipEventDisableTiming));
-  for (int k = 0; k < 4; ++k) HIP_CHECK(hipEventCreateWithFlags(&m->ev_dw[k], hipEventDisableTiming));
-  HIP_CHECK(hipEventCreateWithFlags(&m->ev_sel, hipEventDisableTiming));
   build_layout(m);
   const int64_t D = m->D, N = (int64_t)m->rows_max * m->Sa, NT = 2 * N, KB = (int64_t)m->K * m->rows_max;
   const size_t e = m->esz;
@@ -221,7 +216,7 @@ int model_create(const rsys_config* cfg, int device, Model** out) {
     m->qmap = (unsigned int*)(base + 7 * mb); m->qmap16 = (unsigned int*)(base + 8 * mb);
     m->maps_zero_bytes = (size_t)(7 * mb);
     const int64_t nt = (m->Ta + 63) / 64;
-    DALLOC(m->attn_order_q, (int64_t)m->rows_max * m->H * nt * 4 * 2);   /* second half: the q-tile-pair list (AttnParams::order_q2) */ DALLOC(m->attn_order_k, (int64_t)m->rows_max * m->KV * nt * 4);
+    DALLOC(m->attn_order_q, (int64_t)m->rows_max * m->H * nt * 4); DALLOC(m->attn_order_k, (int64_t)m->rows_max * m->KV * nt * 4);
     DALLOC(m->attn_qbits, (int64_t)m->rows_max * nt * nt * 64 * 8); DALLOC(m->attn_kbits, (int64_t)m->rows_max * nt * nt * 64 * 8);
   }
   m->la.resize(m->L);
@@ -322,7 +317,7 @@ int model_create(const rsys_config* cfg, int device, Model** out) {
       m->kmap_p = (unsigned int*)base; m->kmap_full_p = (unsigned int*)(base + mb); m->qmap_full_p = (unsigned int*)(base + 2 * mb); m->kmap16_p = (unsigned int*)(base + 3 * mb);
       m->qmap_p = (unsigned int*)(base + 7 * mb); m->qmap16_p = (unsigned int*)(base + 8 * mb);
       const int64_t nt = (m->Ta + 63) / 64;
-      DALLOC(m->attn_order_q_p, (int64_t)m->rows_max * m->H * nt * 4 * 2); DALLOC(m->attn_order_k_p, (int64_t)m->rows_max * m->KV * nt * 4);
+      DALLOC(m->attn_order_q_p, (int64_t)m->rows_max * m->H * nt * 4); DALLOC(m->attn_order_k_p, (int64_t)m->rows_max * m->KV * nt * 4);
       DALLOC(m->attn_qbits_p, (int64_t)m->rows_max * nt * nt * 64 * 8); DALLOC(m->attn_kbits_p, (int64_t)m->rows_max * nt * nt * 64 * 8);
     }
   }
@@ -385,11 +380,10 @@ int model_create(const rsys_config* cfg, int device, Model** out) {
 }
 
 int model_destroy(Model* m) {
-  if (m->loss_ring) { hipFree(m->loss_ring); m->loss_ring = nullptr; }
   if (!m) return RSYS_OK;
+  if (m->loss_ring) { hipFree(m->loss_ring); m->loss_ring = nullptr; }
   hipSetDevice(m->device);
   hipStreamSynchronize(m->stream);
-  hipStreamSynchronize(m->side);
   for (void* p : m->allocs) hipFree(p);
   m->rws.release();
   retrieve_tables_free(m);
@@ -416,8 +410,6 @@ int model_destroy(Model* m) {
   if (m->tok_Uall) hipFree(m->tok_Uall);
   if (m->tok_Pall) hipFree(m->tok_Pall);
   if (m->rows_xchg) hipFree(m->rows_xchg);
-  hipEventDestroy(m->ev_fork); hipEventDestroy(m->ev_join); if (m->ev_sel) hipEventDestroy(m->ev_sel); hipStreamDestroy(m->side);
-  for (int k = 0; k < 4; ++k) if (m->ev_dw[k]) hipEventDestroy(m->ev_dw[k]);
   for (auto& kv : m->dw_plans) gemm8p_group_plan_destroy(kv.second);
   for (auto e : m->timer.pool) hipEventDestroy(e);
   for (auto e : m->step_marks) hipEventDestroy(e);
@@ -589,8 +581,7 @@ int model_param_io(Model* m, const char* name, float* out, const float* in, int6
   float* base = (which == 0 ? m->P : m->G) + t.off;
   const int64_t int_rows = (t.map == MAP_DIRECT) ? t.rows : 2 * m->Ip;
   std::vector<float> host((size_t)int_rows * t.ld);
-  HIP_CHECK(hipStreamSynchronize(m->stream));   // (the model's streams are non-blocking: a plain hipMemcpy does not wait for them)
-  HIP_CHECK(hipStreamSynchronize(m->side));
+  HIP_CHECK(hipStreamSynchronize(m->stream));   // (the model's stream is non-blocking: a plain hipMemcpy does not wait for it)
   HIP_CHECK(hipMemcpy(host.data(), base, host.size() * 4, hipMemcpyDeviceToHost));
   if (out) {
     for (int64_t r = 0; r < t.rows; ++r) memcpy(out + r * t.cols, host.data() + internal_row(t, r) * t.ld, t.cols * 4);

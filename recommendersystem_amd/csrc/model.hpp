@@ -34,7 +34,6 @@ struct LayerOff {  // offsets into the flat buffers
 
 struct PhaseTimer {
   bool enabled = false;
-  bool serialize = false;   // run the side-stream GEMMs in line (clean per-kernel attribution)
   std::vector<std::pair<std::string, hipEvent_t>> marks;
   std::map<std::string, double> acc_ms;
   std::vector<hipEvent_t> pool;
@@ -54,16 +53,6 @@ struct Model {
   rsys_config cfg;
   int device = 0;
   hipStream_t stream = nullptr;
-  // second stream for the weight-gradient GEMMs of the trunk backward: each runs beside the dx GEMM that shares its
-  // input (MFMA-bound beside output-bound), forked and joined with events around the pair
-  hipStream_t side = nullptr;
-  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-  bool side_pending = false;
-  hipEvent_t ev_sel = nullptr; bool sel_pending = false;   // position selection + token union of the pass, running on the side stream
-  // deferred joins (RSYS_SIDE_STREAM=2): one event per weight-gradient product of a layer (W2, W13, Wo, Wqkv), recorded on the
-  // side stream behind it; the main stream waits for a product only where the buffer it reads is overwritten next
-  hipEvent_t ev_dw[4] = {nullptr, nullptr, nullptr, nullptr};
-  bool dw_pending[4] = {false, false, false, false};
   // DDP-style early gradient reduction (train.py:678-682): when set, the trunk backward hands every finished bucket of
   // per-layer weight gradients [lo, hi) of the flat buffer to this hook (>= 25 MB each, reverse layer order); the hook
   // enqueues its all-reduce on the communicator's stream behind an event and records the range in `reduced`
@@ -103,7 +92,7 @@ struct Model {
   // dims
   int L, H, KV, D, I, Ip, S, T, V0, V1, V, M, Mp, K, hd, Nqkv, rows_max;
   // S / T above are the RESIDENT BATCH's row length (interactions / tokens): everything that walks the batch reads them.  Sa / Ta are the
-  // allocated geometry (cfg.max_sequence_length, twice that): buffer sizes, the RoPE tables, the offsets inside the launch-order arrays,
+  // allocated geometry (cfg.max_sequence_length, twice that): buffer sizes, the RoPE tables,
   // the ranking cache's slot stride, the render pipelines' chunking.  S == Sa except under rsys_batch_upload_trimmed and the trimmed
   // forwards of the render pipelines; every ordinary upload, swap and device-assembled batch sets S = Sa.
   int Sa = 0, Ta = 0;

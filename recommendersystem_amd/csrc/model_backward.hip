@@ -147,7 +147,7 @@ int backward_trunk(Model* m) {
   // deferred weight gradients: the dY operands of layer l live in m->dwb[l] until the grouped launch that consumes them
   // (deterministic mode: the grouped launch in its ordered form -- bf16 products only, and the fp8 weight gradients are off in that mode)
   const bool det_group = sw().det_dw_group != 0;   // A/B: 0 = the per-layer slab path
-  const bool defer = m->defer_dw && (!m->deterministic || (det_group && m->bf16_mode)) && side_mode() == 0 && !m->bank_train;   // (bank pass: no weight gradients at all)
+  const bool defer = m->defer_dw && (!m->deterministic || (det_group && m->bf16_mode)) && !m->bank_train;   // (bank pass: no weight gradients at all)
   const bool ctop = m->top_is_sparse;
   if (defer && !ctop) gxt = AT<T>(m->dwb[m->L - 1].gxt);
   RC(ensure_transposes(m));
@@ -166,7 +166,7 @@ int backward_trunk(Model* m) {
   AttnParams ap{};
   ap.B = rows; ap.T = m->T; ap.H = m->H; ap.KV = m->KV; ap.hd = hd; ap.is_bf16 = is_bf16<T>::value ? 1 : 0;
   ap.uid = m->uid_t; ap.tm = m->tm_t; ap.qmap = m->qmap; ap.kmap = m->kmap; ap.qmap_full = m->qmap_full; ap.kmap_full = m->kmap_full; ap.qmap16 = m->qmap16; ap.kmap16 = m->kmap16;
-  ap.order_q = m->attn_order_q; ap.order_q2 = m->attn_order_q + (int64_t)m->rows_max * m->H * ((m->Ta + 63) / 64); ap.order_k = m->attn_order_k; ap.qbits = m->attn_qbits; ap.kbits = m->attn_kbits;
+  ap.order_q = m->attn_order_q; ap.order_k = m->attn_order_k; ap.qbits = m->attn_qbits; ap.kbits = m->attn_kbits;
   ap.rope_cos = m->rope_cos; ap.rope_sin = m->rope_sin; ap.rope_pos = rpos;
   int bucket_top = m->L - 1;
   for (int l = m->L - 1; l >= 0; --l) {
@@ -184,24 +184,22 @@ int backward_trunk(Model* m) {
       GemmParams p{};  // dW2 += gx^T . g
       p.A = gxt; p.lda = D; p.B = a.g; p.ldb = Ip; p.C = m->G + m->lo[l].w2; p.ldc = Ip; p.c_f32 = 1;
       p.M = D; p.N = Ip; p.K = NT; p.epi = EPI_ATOMIC;
-      RC(gemm_side<T>(m, "gemm_w2_dw", p, false, true, true, DW_W2));
+      RC(gemm<T>(m, "gemm_w2_dw", p, false, true, true));
     }
     {
       GemmParams p{};  // dg = gx . W2, fused with the SwiGLU backward: writes [da|db] directly
       p.A = gxt; p.lda = D; p.B = W<T>(m, m->lo[l].w2); p.ldb = Ip; p.C = dab; p.ldc = 2 * Ip;
       if (wt) { p.B = WT<T>(m, m->lo[l].w2); p.ldb = D; }
       p.M = NT; p.N = Ip; p.K = D; p.epi = EPI_SWIGLU_BWD; p.C2 = a.ab; p.ldc2 = 2 * Ip;
-      RC(join_dw(m, DW_W13));   // the layer above's dW13 reads dab
       if (m->fp8) { p.f8_amax_out = f8_slot(m, l, F8S_DAB); RC(gemm_f8(m, l, F8P_W2_DX, "gemm_w2_dx", p, W8T(m, m->lo[l].w2), D, true)); }
       else RC(gemm<T>(m, "gemm_w2_dx", p, false, false, !wt));
       if (f8dw && !defer) RC(f8_dw_launch(m, l, 0, "gemm_w2_dw", NT));
-      RC(join_side(m));
     }
     if (!ft && !defer && !f8dw) {
       GemmParams p{};  // dW13 += dab^T . hn
       p.A = dab; p.lda = 2 * Ip; p.B = a.hn; p.ldb = D; p.C = m->G + m->lo[l].w13; p.ldc = D; p.c_f32 = 1;
       p.M = 2 * Ip; p.N = D; p.K = NT; p.epi = EPI_ATOMIC;
-      RC(gemm_side<T>(m, "gemm_w13_dw", p, false, true, true, DW_W13));
+      RC(gemm<T>(m, "gemm_w13_dw", p, false, true, true));
     }
     {
       GemmParams p{};  // dhn = dab . W13
@@ -212,9 +210,7 @@ int backward_trunk(Model* m) {
       else RC(gemm<T>(m, "gemm_w13_dx", p, false, false, !wt));
       if (f8dw && !defer) RC(f8_dw_launch(m, l, 1, "gemm_w13_dw", NT));
       if (!m->f8_keep.empty()) HIP_CHECK(hipMemcpyAsync(m->f8_keep[l * 3 + 0], m->dhn, (size_t)NT * D * 2, hipMemcpyDeviceToDevice, s));
-      RC(join_side(m));
     }
-    RC(join_dw(m, DW_O));       // the layer above's dWo reads dht
     tic(m, "hbm_rmsnorm_bwd", nb_bytes);
     RC(launch_rmsnorm_bwd<T>(AT<T>(m->dhn), a.h, m->P + m->lo[l].mlp, a.rstd2, gx, m->dh, cp ? dht : nullptr, small_grad(m, m->lo[l].mlp), NT, D, s, nullptr, nullptr, nullptr,
                              m->fp8 ? f8_slot(m, l, F8S_DH) : nullptr));
@@ -223,7 +219,7 @@ int backward_trunk(Model* m) {
       GemmParams p{};  // dWo += dh^T . O
       p.A = dht; p.lda = D; p.B = a.O; p.ldb = D; p.C = m->G + m->lo[l].wo; p.ldc = D; p.c_f32 = 1;
       p.M = D; p.N = D; p.K = NT; p.epi = EPI_ATOMIC;
-      RC(gemm_side<T>(m, "gemm_o_dw", p, false, true, true, DW_O));
+      RC(gemm<T>(m, "gemm_o_dw", p, false, true, true));
     }
     {
       GemmParams p{};  // dO = dh . Wo
@@ -234,21 +230,19 @@ int backward_trunk(Model* m) {
       else RC(gemm<T>(m, "gemm_o_dx", p, false, false, !wt));
       if (f8dw && !defer) RC(f8_dw_launch(m, l, 2, "gemm_o_dw", NT));
       if (!m->f8_keep.empty()) HIP_CHECK(hipMemcpyAsync(m->f8_keep[l * 3 + 1], m->dO, (size_t)NT * D * 2, hipMemcpyDeviceToDevice, s));
-      RC(join_side(m));
     }
     }   // !top
     ap.q = a.qkv; ap.k = AT<T>(a.qkv) + m->H * hd; ap.v = AT<T>(a.qkv) + (m->H + m->KV) * hd; ap.ld = m->Nqkv;
     ap.o = a.O; ap.ldo = D; ap.lse = a.lse;
     ap.dO = m->dO; ap.delta = m->delta;
     ap.dq = dqkv; ap.dk = AT<T>(dqkv) + m->H * hd; ap.dv = AT<T>(dqkv) + (m->H + m->KV) * hd; ap.ldg = m->Nqkv;
-    RC(join_dw(m, DW_QKV));     // the layer above's dWqkv reads dqkv
     ap.f8_amax = m->fp8 ? f8_slot(m, l, F8S_DQKV) : nullptr;
     tic(m, "attn_bwd");
     if (top) {   // selected-first token order of the last layer: its ids, tile maps, RoPE positions; dO is non-zero in the leading query tiles only
       AttnParams at = ap;
       at.uid = m->uid_p; at.tm = m->tm_p; at.rope_pos = m->pos_p; at.q_active = m->c_qact;
       at.qmap = m->qmap_p; at.kmap = m->kmap_p; at.qmap_full = m->qmap_full_p; at.kmap_full = m->kmap_full_p; at.qmap16 = m->qmap16_p; at.kmap16 = m->kmap16_p;
-      at.order_q = m->attn_order_q_p; at.order_q2 = m->attn_order_q_p + (int64_t)m->rows_max * m->H * ((m->Ta + 63) / 64); at.order_k = m->attn_order_k_p; at.qbits = m->attn_qbits_p; at.kbits = m->attn_kbits_p;
+      at.order_q = m->attn_order_q_p; at.order_k = m->attn_order_k_p; at.qbits = m->attn_qbits_p; at.kbits = m->attn_kbits_p;
       RC(launch_attn_bwd<T>(at, s));
     } else {
       RC(launch_attn_bwd<T>(ap, s));
@@ -258,7 +252,7 @@ int backward_trunk(Model* m) {
       GemmParams p{};  // dWqkv += dqkv^T . xn
       p.A = dqkv; p.lda = m->Nqkv; p.B = a.xn; p.ldb = D; p.C = m->G + m->lo[l].wqkv; p.ldc = D; p.c_f32 = 1;
       p.M = m->Nqkv; p.N = D; p.K = NT; p.epi = EPI_ATOMIC;
-      RC(gemm_side<T>(m, "gemm_qkv_dw", p, false, true, true, DW_QKV));
+      RC(gemm<T>(m, "gemm_qkv_dw", p, false, true, true));
     }
     {
       GemmParams p{};  // dxn = dqkv . Wqkv
@@ -269,7 +263,6 @@ int backward_trunk(Model* m) {
       else RC(gemm<T>(m, "gemm_qkv_dx", p, false, false, !wt));
       if (f8dw && !defer) RC(f8_dw_launch(m, l, 3, "gemm_qkv_dw", NT));
       if (!m->f8_keep.empty()) HIP_CHECK(hipMemcpyAsync(m->f8_keep[l * 3 + 2], m->dhn, (size_t)NT * D * 2, hipMemcpyDeviceToDevice, s));
-      RC(join_side(m));
     }
     if (m->bank_train) RC(adapter_bank_backward<T>(m, l, AT<T>(a.xn), AT<T>(dqkv), AT<T>(m->dhn)));
     if (own_lora) {
@@ -337,7 +330,6 @@ int backward_trunk(Model* m) {
       const bool boundary = defer ? (l == m->L / 2 && (hi - lo) * 4 >= (25ll << 20)) : (hi - lo) * 4 >= (25ll << 20);
       if (l == 0 || boundary) {
         if (defer) RC(grouped_weight_grads<T>(m, l, bucket_top));   // the bucket's products, then its all-reduce
-        RC(join_all(m));
         RC(m->grad_bucket_hook(lo, hi));
         bucket_top = l - 1;
         // From here on all-reduce kernels share the CUs with the backward.  A persistent grid (one workgroup pinned per
@@ -347,7 +339,6 @@ int backward_trunk(Model* m) {
       }
     }
   }
-  RC(join_all(m));   // every weight gradient is final (and the saved activations may be overwritten by the next forward)
   toc(m);
   if (trunk_frozen(m)) return RSYS_OK;   // embeddings are frozen (model.py:361-369)
   // gx = gradient w.r.t. the interleaved input embeddings (even rows: items, odd rows: actions)

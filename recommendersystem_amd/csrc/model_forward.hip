@@ -57,8 +57,6 @@ static int ensure_f8_weights(Model* m) {
   return RSYS_OK;
 }
 
-int select_join(Model* m);   // (position selection runs on the side stream: defined with select_positions_all below)
-
 // token-local tail of layer l (model.py:300-309): h = x + O Wo^T ; out = h + W2 (silu(W1 hn) * W3 hn), hn = RMSNorm(h)
 template <typename T>
 static int layer_tail_dense(Model* m, int l, const void* O_in = nullptr /* attention output in token order (default: the layer's own) */) {
@@ -101,7 +99,6 @@ static int top_tail_compact(Model* m) {
   hipStream_t s = m->stream;
   Model::LayerAct& a = m->la[l];
   const int* n = m->c_n;
-  RC(select_join(m));
   tic(m, "phase_top_compact_fwd");
   RC(launch_gather_rows_sel<T>(AT<T>(a.O), D, m->c_sel_p, n, cap, AT<T>(m->c_O), D, s));   // (the layer's attention ran in selected-first order)
   RC(launch_gather_rows_sel<float>(a.x, D, m->c_sel, n, cap, m->c_x, D, s));
@@ -173,19 +170,18 @@ int forward_trunk(Model* m) {
   ap.B = rows; ap.T = m->T; ap.H = m->H; ap.KV = m->KV; ap.hd = hd; ap.is_bf16 = is_bf16<T>::value ? 1 : 0;
   ap.uid = m->uid_t; ap.tm = m->tm_t; ap.qmap = m->qmap; ap.kmap = m->kmap; ap.qmap_full = m->qmap_full; ap.kmap_full = m->kmap_full; ap.qmap16 = m->qmap16; ap.kmap16 = m->kmap16;
   ap.maps_zero_base = m->kmap; ap.maps_zero_bytes = m->maps_zero_bytes;
-  ap.order_q = m->attn_order_q; ap.order_q2 = m->attn_order_q + (int64_t)m->rows_max * m->H * ((m->Ta + 63) / 64); ap.order_k = m->attn_order_k; ap.qbits = m->attn_qbits; ap.kbits = m->attn_kbits;
+  ap.order_q = m->attn_order_q; ap.order_k = m->attn_order_k; ap.qbits = m->attn_qbits; ap.kbits = m->attn_kbits;
   if (m->rc_mode != 2) RC(launch_attn_tilemap(ap, s));   // (rc_mode 2, rsys_rank_cache_candidates: candidate rows have no tile maps)
   toc(m);
   AttnParams ap_top = ap;   // the last layer under the compact top: selected-first token order, its own tile maps, leading query tiles only
   if (m->top_is_sparse) {
-    RC(select_join(m));
     RC(launch_selected_first(m->c_bits, m->c_pre, m->c_slot, m->c_sel, m->uid_t, m->tm_t, rpos, rows, m->T, m->c_perm, m->uid_p, m->tm_p, m->pos_p, m->c_slot_p,
                              m->c_sel_p, m->c_qact, s));
     ap_top.uid = m->uid_p; ap_top.tm = m->tm_p;
     ap_top.qmap = m->qmap_p; ap_top.kmap = m->kmap_p; ap_top.qmap_full = m->qmap_full_p; ap_top.kmap_full = m->kmap_full_p;
     ap_top.qmap16 = m->qmap16_p; ap_top.kmap16 = m->kmap16_p;
     ap_top.maps_zero_base = m->kmap_p;
-    ap_top.order_q = m->attn_order_q_p; ap_top.order_q2 = m->attn_order_q_p + (int64_t)m->rows_max * m->H * ((m->Ta + 63) / 64); ap_top.order_k = m->attn_order_k_p; ap_top.qbits = m->attn_qbits_p; ap_top.kbits = m->attn_kbits_p;
+    ap_top.order_q = m->attn_order_q_p; ap_top.order_k = m->attn_order_k_p; ap_top.qbits = m->attn_qbits_p; ap_top.kbits = m->attn_kbits_p;
     ap_top.q_active = m->c_qact;   // (the launch orders put the query tiles beyond it last)
     RC(launch_attn_tilemap(ap_top, s));
   }
@@ -266,7 +262,7 @@ static int materialise_output_t(Model* m) {
   AttnParams ap{};
   ap.B = m->cur_rows; ap.T = m->T; ap.H = m->H; ap.KV = m->KV; ap.hd = hd; ap.is_bf16 = is_bf16<T>::value ? 1 : 0;
   ap.uid = m->uid_p; ap.tm = m->tm_p; ap.qmap = m->qmap_p; ap.kmap = m->kmap_p; ap.qmap_full = m->qmap_full_p; ap.kmap_full = m->kmap_full_p;
-  ap.qmap16 = m->qmap16_p; ap.kmap16 = m->kmap16_p; ap.order_q = m->attn_order_q_p; ap.order_q2 = m->attn_order_q_p + (int64_t)m->rows_max * m->H * ((m->Ta + 63) / 64); ap.order_k = m->attn_order_k_p; ap.qbits = m->attn_qbits_p; ap.kbits = m->attn_kbits_p;
+  ap.qmap16 = m->qmap16_p; ap.kmap16 = m->kmap16_p; ap.order_q = m->attn_order_q_p; ap.order_k = m->attn_order_k_p; ap.qbits = m->attn_qbits_p; ap.kbits = m->attn_kbits_p;
   ap.q = a.qkv; ap.k = AT<T>(a.qkv) + m->H * hd; ap.v = AT<T>(a.qkv) + (m->H + m->KV) * hd; ap.ld = m->Nqkv;
   ap.o = a.O; ap.ldo = D; ap.lse = a.lse;
   RC(launch_attn_fwd<T>(ap, m->stream));
@@ -471,7 +467,6 @@ int heads(Model* m, int evaluate, const float tw[4]) {
   const bool train = !evaluate;
   tic(m, "phase_heads");
   const bool ctop = m->top_is_sparse;   // trunk output and its gradient live in the compact buffers (rows = selected tokens)
-  RC(select_join(m));
   if (train && ctop && m->loss_acc_with_c_gy) HIP_CHECK(hipMemsetAsync(m->loss_acc, 0, 256 + (size_t)m->ctop_cap * D * 4, s));   // (one allocation: model.hip)
   else {
     HIP_CHECK(hipMemsetAsync(m->loss_acc, 0, 16 * 4, s));
@@ -553,27 +548,17 @@ int heads(Model* m, int evaluate, const float tw[4]) {
 
 // position selection of the four (medium, metric) tasks in one launch (model.py:501,509): depends on the masked batch only, so it
 // runs before the trunk; with the compact top also the union of the live positions
-// Both are one-workgroup kernels (~40 us each) that nothing needs before the last layer's tail; running them on the side stream
-// beside the fused-table GEMM was measured and is NOT the default (see below; select_join is the matching wait).
+// Both are one-workgroup kernels (~40 us each) that nothing needs before the last layer's tail.  They stay in line: on a second stream
+// beside the fused-table GEMM a 1024-thread workgroup landing on a CU stalls that CU's share of the persistent GEMM's tiles.
 int select_positions_all(Model* m) {
   const int N = m->cur_rows * m->S, KB = m->K * m->cur_rows;
   const float* ws[4]; int* is[4]; float* sts[4]; int* nps[4];
   for (int ti = 0; ti < 4; ++ti) { ws[ti] = m->bd.m_weight[ti]; is[ti] = m->idx[ti]; sts[ti] = m->stats + 2 * ti; nps[ti] = m->npos + ti; }
-  // (RSYS_SELECT_ASIDE=1: measured on one box, alternating, 30 steps each: 24.27 / 24.41 / 24.36 ms in line against 24.44 / 24.61 / 24.38 ms
-  // aside -- a 1024-thread workgroup landing on a CU stalls that CU's share of the persistent GEMM's tiles: off by default)
-  const bool aside_on = sw().select_aside == 1;
-  const bool aside = aside_on && !m->sharded && !(m->timer.enabled && m->timer.serialize);   // (sharded: the early counts need them at once)
-  hipStream_t s = aside ? m->side : m->stream;
-  if (aside) { HIP_CHECK(hipEventRecord(m->ev_fork, m->stream)); HIP_CHECK(hipStreamWaitEvent(m->side, m->ev_fork, 0)); }
+  hipStream_t s = m->stream;
   const bool chunked_on = sw().select_chunked != 0;   // (A/B)
   if (chunked_on && N >= 4096) RC(launch_select_positions_chunked(4, ws, N, KB, is, sts, nps, m->sel_scratch, s));
   else RC(launch_select_positions_batch(4, ws, N, KB, is, sts, nps, s));
   if (m->top_is_sparse) RC(launch_token_union(is, nps, 4, 2 * N, m->c_bits, m->c_pre, m->c_n, s));
-  if (aside) { HIP_CHECK(hipEventRecord(m->ev_sel, m->side)); m->sel_pending = true; }
-  return RSYS_OK;
-}
-int select_join(Model* m) {
-  if (m->sel_pending) { HIP_CHECK(hipStreamWaitEvent(m->stream, m->ev_sel, 0)); m->sel_pending = false; }
   return RSYS_OK;
 }
 

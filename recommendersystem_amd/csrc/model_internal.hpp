@@ -1,6 +1,6 @@
 // Shared by the translation units of the training step (model.hip: set-up, batches, orchestration, inference; model_forward.hip;
-// model_backward.hip; model_optim.hip -- one file until round 5): the timing brackets, the GEMM wrappers that pick split counts and
-// streams, the fp8 product table, and the declarations of what one unit calls in another.  Everything defined here is `static`:
+// model_backward.hip; model_optim.hip -- one file until round 5): the timing brackets, the GEMM wrapper that picks split
+// counts, the fp8 product table, and the declarations of what one unit calls in another.  Everything defined here is `static`:
 // each unit gets its own copy, none of it owns state.
 #pragma once
 #include <math.h>
@@ -31,7 +31,7 @@ static int dalloc(Model* m, void** p, size_t bytes) {
 #define DALLOC(ptr, bytes) RC(dalloc(m, (void**)&(ptr), (size_t)(bytes)))
 
 // ------------------------------------------------------------------ timing
-static void tic(Model* m, const char* name, double flops = 0.0, hipStream_t st = nullptr) {
+static void tic(Model* m, const char* name, double flops = 0.0) {
   PhaseTimer& t = m->timer;
   if (!t.enabled) return;
   if (!t.filter.empty() && strstr(name, t.filter.c_str()) == nullptr) { t.open.push_back(0); return; }
@@ -49,7 +49,7 @@ static void tic(Model* m, const char* name, double flops = 0.0, hipStream_t st =
     }
   }
   hipEvent_t e = t.pool[t.used++];
-  if (hipEventRecord(e, st ? st : m->stream) != hipSuccess) {   // (seen at the production shape with every step instrumented: the record fails once
+  if (hipEventRecord(e, m->stream) != hipSuccess) {             // (seen at the production shape with every step instrumented: the record fails once
     (void)hipGetLastError();                                    //  thousands of events are pending; an unchecked failure surfaced at the next launch check)
     t.enabled = false;
     return;
@@ -57,12 +57,12 @@ static void tic(Model* m, const char* name, double flops = 0.0, hipStream_t st =
   t.marks.push_back({std::string(name), e});
   t.acc_ms[std::string("#flops:") + name] += flops;
 }
-static void toc(Model* m, hipStream_t st = nullptr) {
+static void toc(Model* m) {
   PhaseTimer& t = m->timer;
   if (!t.enabled) return;
   if (!t.open.empty()) { const char rec = t.open.back(); t.open.pop_back(); if (!rec) return; }
   hipEvent_t e = t.pool[t.used++];
-  if (hipEventRecord(e, st ? st : m->stream) != hipSuccess) {   // (the span that was open stays unpaired and is dropped by rsys_timing_get)
+  if (hipEventRecord(e, m->stream) != hipSuccess) {   // (the span that was open stays unpaired and is dropped by rsys_timing_get)
     (void)hipGetLastError();
     t.enabled = false;
     return;
@@ -98,7 +98,6 @@ static int det_slab_for(Model* m, long long need, GemmParams& p) {
   if (need > m->det_slab_floats) {
     ++m->host_stream_syncs;
     HIP_CHECK(hipStreamSynchronize(m->stream));
-    HIP_CHECK(hipStreamSynchronize(m->side));
     if (m->det_slab) HIP_CHECK(hipFree(m->det_slab));
     m->det_slab = nullptr; m->det_slab_floats = 0;
     HIP_CHECK(hipMalloc((void**)&m->det_slab, (size_t)need * 4));
@@ -125,54 +124,6 @@ static int gemm(Model* m, const char* tag, GemmParams p, bool a_f32, bool a_km, 
   int rc = launch_gemm<T>(p, a_f32, false, a_km, b_km, m->stream);
   toc(m);
   return rc;
-}
-
-// Weight-gradient GEMM, optionally on the side stream beside what the main stream launches next: the side stream first waits for
-// everything the main stream has enqueued so far (the operands).  RSYS_SIDE_STREAM=1: the main stream joins right behind the
-// paired dx GEMM (join_side).  RSYS_SIDE_STREAM=2: deferred joins -- the four products of a layer queue up on the side stream and
-// the main stream waits for product `slot` only where the buffer that product reads is about to be overwritten (join_dw), so the
-// MFMA-bound weight gradients run beside the HBM-bound RMSNorm backward and the VALU-bound attention backward.  rsys_op_timing(2)
-// (bench.py --detail) runs everything in line instead, so that every kernel's time is measured without a neighbour.
-enum { DW_W2 = 0, DW_W13 = 1, DW_O = 2, DW_QKV = 3 };
-static int side_mode() {
-  const int mode = sw().side_stream;
-  return mode;
-}
-template <typename T>
-static int gemm_side(Model* m, const char* tag, GemmParams p, bool a_f32, bool a_km, bool b_km, int slot) {
-  const int mode = side_mode();
-  if (mode == 0 || m->deterministic || (m->timer.enabled && m->timer.serialize)) return gemm<T>(m, tag, p, a_f32, a_km, b_km);   // (deterministic: one slab, one stream)
-  if (p.alpha == 0.f) p.alpha = 1.f;
-  if (p.epi == EPI_ATOMIC && p.splitk == 0) p.splitk = pick_splitk(p.M, p.N, p.K, is_bf16<T>::value ? 64 : 32);
-  if (p.splitk == 0) p.splitk = 1;
-  HIP_CHECK(hipEventRecord(m->ev_fork, m->stream));
-  HIP_CHECK(hipStreamWaitEvent(m->side, m->ev_fork, 0));
-  if (m->timer.enabled) tic(m, (std::string(tag) + "@" + gemm_kernel_name(p, is_bf16<T>::value, a_f32, false, a_km, b_km)).c_str(), 2.0 * p.M * p.N * (double)p.K, m->side);   // (events on the stream the kernel runs on)
-  RC(launch_gemm<T>(p, a_f32, false, a_km, b_km, m->side));
-  toc(m, m->side);
-  if (mode >= 2) {
-    HIP_CHECK(hipEventRecord(m->ev_dw[slot], m->side));
-    m->dw_pending[slot] = true;
-  } else {
-    HIP_CHECK(hipEventRecord(m->ev_join, m->side));
-    m->side_pending = true;
-  }
-  return RSYS_OK;
-}
-// mode 1: wait for the product launched last
-static int join_side(Model* m) {
-  if (m->side_pending) { HIP_CHECK(hipStreamWaitEvent(m->stream, m->ev_join, 0)); m->side_pending = false; }
-  return RSYS_OK;
-}
-// mode 2: the main stream is about to overwrite what product `slot` reads (the side stream runs in order: earlier products are done too)
-static int join_dw(Model* m, int slot) {
-  if (m->dw_pending[slot]) { HIP_CHECK(hipStreamWaitEvent(m->stream, m->ev_dw[slot], 0)); m->dw_pending[slot] = false; }
-  return RSYS_OK;
-}
-static int join_all(Model* m) {
-  RC(join_side(m));
-  for (int k = 3; k >= 0; --k) RC(join_dw(m, k));
-  return RSYS_OK;
 }
 
 template <typename T> static inline T* W(Model* m, int64_t off) { return (T*)m->Sh + off; }
@@ -308,7 +259,6 @@ template <typename T> int forward_trunk(Model* m);
 template <typename T> int heads(Model* m, int evaluate, const float tw[4]);
 template <typename T> int sharded_counts_early(Model* m, bool train, const float tw[4]);
 int select_positions_all(Model* m);
-int select_join(Model* m);   // (position selection may run on the side stream)
 // ---- defined in model_backward.hip
 template <typename T> int backward_trunk(Model* m);
 

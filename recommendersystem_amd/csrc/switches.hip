@@ -12,9 +12,6 @@ namespace {
 struct Entry { const char* name; int Switches::*field; int dflt; };
 const Entry kEntries[] = {
     {"RSYS_ATTN_DMA", &Switches::attn_dma, 1},
-    {"RSYS_ATTN_KV_DMA", &Switches::attn_kv_dma, 1},
-    {"RSYS_ATTN_KV32", &Switches::attn_kv32, 1},
-    {"RSYS_ATTN_FWD32", &Switches::attn_fwd32, 0},
     {"RSYS_GEMM_KERNEL", &Switches::gemm_kernel, -1},
     {"RSYS_GEMM_KERNEL_TN", &Switches::gemm_kernel_tn, -1},
     {"RSYS_GEMM_KERNEL_NT_SPLITK", &Switches::gemm_kernel_nt_splitk, -1},
@@ -30,9 +27,7 @@ const Entry kEntries[] = {
     {"RSYS_DET_DW_GROUP", &Switches::det_dw_group, 1},
     {"RSYS_SPARSE_TOP", &Switches::sparse_top, 1},
     {"RSYS_TOP_ORDER", &Switches::top_order, 1},
-    {"RSYS_SELECT_ASIDE", &Switches::select_aside, 0},
     {"RSYS_SELECT_CHUNKED", &Switches::select_chunked, 1},
-    {"RSYS_SIDE_STREAM", &Switches::side_stream, 0},
     {"RSYS_SCATTER_ATOMIC", &Switches::scatter_atomic, 0},
     {"RSYS_F8_DW", &Switches::f8_dw, 1},
     {"RSYS_F8_DW_ROUND_BF16", &Switches::f8_dw_round_bf16, 0},

@@ -10,9 +10,6 @@ namespace rsys {
 struct Switches {
   // ---- kernel choice: both arms live code (the other arm serves other shapes / dtypes, or is the reference side of a bitwise test)
   int attn_dma;               // RSYS_ATTN_DMA=0: bf16 / head_dim 64 on the register-staged attention kernels (every other head size's kernels)
-  int attn_kv_dma;            // RSYS_ATTN_KV_DMA=0: dK/dV alone on the register-staged kernel
-  int attn_fwd32;             // RSYS_ATTN_FWD32=1: forward on attn_fwd32_kernel (128 queries of one head per workgroup, 32x32x16 products; measured level with the default 64-query two-head kernel)
-  int attn_kv32;              // RSYS_ATTN_KV32=0: dK/dV on the 16-key-per-wave LDS-DMA kernel (the bitwise partner of the register-staged one)
   int gemm_kernel;            // RSYS_GEMM_KERNEL: -1 unset / 0 (shape rule); 1 = the 128x128 register-staged kernel everywhere, 2 = 256x256 LDS-DMA wherever eligible
   int gemm_kernel_tn;         // RSYS_GEMM_KERNEL_TN: -1 unset / 0 (shape rule); 1 = never the K-major LDS-DMA kernels, 2 = both their forms (split-K, store) wherever eligible
   int gemm_kernel_nt_splitk;  // RSYS_GEMM_KERNEL_NT_SPLITK: -1 unset (shape rule); 0 off; 2 force
@@ -28,9 +25,7 @@ struct Switches {
   int det_dw_group;           // RSYS_DET_DW_GROUP=0: deterministic mode on the per-layer slab path instead of the ordered grouped launch
   int sparse_top;             // RSYS_SPARSE_TOP=0: dense last layer and final norm
   int top_order;              // RSYS_TOP_ORDER=0: the last layer's attention keeps the token order (test hook: two summation orders of one arithmetic)
-  int select_aside;           // RSYS_SELECT_ASIDE=1: position selection on the side stream
   int select_chunked;         // RSYS_SELECT_CHUNKED=0: one-pass position selection
-  int side_stream;            // RSYS_SIDE_STREAM: 0 = off (default), 1 / 2 = the two side-stream placements of profiles/r4_ab_side_stream*
   int scatter_atomic;         // RSYS_SCATTER_ATOMIC=1: embedding-gradient scatter by float atomics (the A/B partner of the segmented sum)
   int f8_dw;                  // RSYS_F8_DW=0: fp8 trunk with bf16 weight gradients
   int f8_dw_round_bf16;       // RSYS_F8_DW_ROUND_BF16=1: fp8 weight-gradient operands rounded through bf16 first (parity test of the quantiser)

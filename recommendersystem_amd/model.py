@@ -1041,8 +1041,9 @@ class RecommenderModel:
 
     # ---- instrumentation
     def timing(self, enable, serialize=False):
-        """HIP-event timing of every kernel call site.  serialize=True additionally runs the side-stream GEMMs in
-        line, so that each kernel is measured without a concurrent neighbour (bench.py --detail)."""
+        """HIP-event timing of every kernel call site.  serialize no longer changes anything: it pulled the GEMMs of the
+        side stream in line, and that stream is gone -- every kernel of the step runs on one stream (the argument stays for
+        the callers that pass it)."""
         check(lib().rsys_op_timing(self._h, (2 if serialize else 1) if enable else 0))
 
     def timing_pause(self):

@@ -78,14 +78,14 @@ def attn_emul_bf16(q, k, v, uid, tm, dO, H, KV, hd, cos=None, sin=None, pos=None
     """attn_ref with a bf16 rounding wherever the bf16 kernels round (csrc/attention.hip), everything between in float64 -- it says how
     much error the storage format itself produces on these inputs, nothing about summation order or the hardware exponential:
       * q, k, v, dO are bf16 (the operands of every product);
-      * forward: the soft-max numerators exp(s - max) are packed to bf16 for P . V (pack8 in acc_second_stage_r, :205-208; pack8f in
-        attn_fwd32_kernel), the row sum l adds the unrounded fp32 values (:805-810) and divides the fp32 accumulator, O is rounded on
-        store (:831); the kernel rounds against its RUNNING maximum, this against the final one -- the same relative rounding;
-      * backward: delta = rowsum(dO * O) reads the stored bf16 O (:1756-1758); P = exp(s - lse) is packed to bf16 for P^T . dO (dV,
-        acc_second_stage_half_r :252-254 from :1258; pack8f in attn_bwd_kv32_kernel); dS = P (dP - delta), WITHOUT its 1 / sqrt(hd),
-        is packed to bf16 for dS . K (:1847-1850) and dS^T . Q (:1255-1259), the factor multiplies the fp32 accumulators (:1275, :1862,
-        :1673); dq, dk (after the fp32 un-rotation) and dv are rounded on store (store_grad_tile :1141, store_grad_tile_sw :648,
-        :1678-1679).
+      * forward (attn_fwd_kernel): the soft-max numerators exp(s - max) are packed to bf16 for P . V (pack8 in acc_second_stage_r), the
+        row sum l adds the unrounded fp32 values and divides the fp32 accumulator, O is rounded on store; the kernel rounds against
+        its RUNNING maximum, this against the final one -- the same relative rounding;
+      * backward: delta = rowsum(dO * O) reads the stored bf16 O (attn_bwd_q_kernel); P = exp(s - lse) is packed to bf16 for
+        P^T . dO (dV: pack8 in acc_second_stage_half_r from attn_bwd_kv_kernel, pack8f in attn_bwd_kv32_kernel); dS = P (dP - delta),
+        WITHOUT its 1 / sqrt(hd), is packed to bf16 for dS . K (attn_bwd_q_kernel) and dS^T . Q (the dK/dV kernels), the factor
+        multiplies the fp32 accumulators; dq, dk (after the fp32 un-rotation) and dv are rounded on store (store_grad_tile and the
+        epilogue of attn_bwd_kv32_kernel).
     lse has no bf16 point (fp32 scores of bf16 operands, fp32 store)."""
     return _attention(q, k, v, uid, tm, dO, H, KV, hd, cos, sin, pos, q_active, bf16_round)
 

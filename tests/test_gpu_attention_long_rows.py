@@ -7,7 +7,7 @@ Every test first ASSERTS what its inputs contain, counted per (q tile, kv tile) 
 empty pairs in each quadrant of the old word boundary (tile 32), bit 63 in use on both sides, a row of one user (every map word all
 ones), the first bit beyond the old word (33 tiles) and a ragged 34th tile.  Two heads per kv head (H = 2, KV = 1) throughout: head_dim 16
 and 128 run the register-staged kernels, head_dim 64 in bf16 the LDS-DMA forward / dQ kernels and attn_bwd_kv32_kernel; one test runs
-every kernel variant behind the RSYS_ATTN_* switches at 64 tiles.
+both kernel variants of the RSYS_ATTN_DMA switch at 64 tiles.
 
 The last test guards the rows of up to 32 tiles, which keep their 32-bit map words and their launch order: two launches give the same bits.
 
@@ -110,11 +110,11 @@ def test_compact_top_above_and_below_the_old_word(qa, dtype):
 
 
 def test_every_kernel_variant_on_rows_of_64_tiles(tmp_path):
-    """bf16 / head_dim 64 at T = 4096 behind the RSYS_ATTN_* switches, as test_every_kernel_variant_on_full_tiles_and_a_real_rotation does it
-    (the switches are read once per process: one fresh child per variant, one at a time, each under its own time limit; the first
-    abnormal exit ends the test): the 64-bit instantiations of the register-staged forward / dQ / dK/dV kernels, of the 16-key LDS-DMA
-    dK/dV kernel and of the 128-query forward kernel, each against the reference; the register-staged and the 16-key LDS-DMA kernels
-    run the same products in the same order and must agree bit for bit."""
+    """bf16 / head_dim 64 at T = 4096 behind the RSYS_ATTN_DMA switch, as test_every_kernel_variant_on_full_tiles_and_a_real_rotation does it
+    (the switch is read once per process: one fresh child per variant, one at a time, each under its own time limit; the first
+    abnormal exit ends the test): the 64-bit instantiations of the register-staged forward / dQ / dK/dV kernels and of the LDS-DMA
+    kernels, each against the reference; the register-staged and the LDS-DMA forward and dQ kernels run the same products in the same
+    order, so O, lse and dQ must agree bit for bit."""
     T, hd = 4096, 64
     key = _key(T, hd, "low", 1)
     _check_inputs(key, T, "low")
@@ -134,8 +134,9 @@ def test_every_kernel_variant_on_rows_of_64_tiles(tmp_path):
         outs.append(dict(np.load(out)))
     for (name, _), res in zip(ap.VARIANTS, outs):
         ap._compare(f"long-variant[{name}]", res, ref, emu, key, H, KV)
-    for n in ("raw_O", "raw_dqkv", "lse"):
+    for n in ("raw_O", "lse"):
         assert ap._same_bits(outs[0][n], outs[1][n]), n
+    assert ap._same_bits(outs[0]["raw_dqkv"][:, :H * hd], outs[1]["raw_dqkv"][:, :H * hd]), "dq"
 
 
 @pytest.mark.parametrize("dtype", [0, 1])

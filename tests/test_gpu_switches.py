@@ -19,11 +19,9 @@ ARMS = {"default": {}, "dense_top": {"RSYS_SPARSE_TOP": "0"}, "token_order": {"R
         # one batched in-order sum; round 4) and the per-layer slab path it replaced
         "det_grouped_dw": {"RSYS_TEST_DETERMINISTIC": "1"}, "det_per_layer_dw": {"RSYS_TEST_DETERMINISTIC": "1", "RSYS_DET_DW_GROUP": "0"},
         # round 5 (csrc/switches.hpp): every kernel-choice switch whose other arm is live code has an arm here or a test of its own
-        "select_one_pass": {"RSYS_SELECT_CHUNKED": "0"}, "select_aside": {"RSYS_SELECT_ASIDE": "1"},
-        "scatter_atomic": {"RSYS_SCATTER_ATOMIC": "1"}, "dkdv_register_staged": {"RSYS_ATTN_KV_DMA": "0"},
-        "side_stream_joined": {"RSYS_SIDE_STREAM": "1"}, "side_stream_deferred": {"RSYS_SIDE_STREAM": "2"},
-        # round 6: the opt-in 128-query forward attention kernel (also with the compact top's q_active limit) and gemm8c's half tiles forced
-        "fwd32": {"RSYS_ATTN_FWD32": "1"}, "gemm8c_half": {"RSYS_GEMM8C_HALF": "2", "RSYS_GEMM_KERNEL": "2"},
+        "select_one_pass": {"RSYS_SELECT_CHUNKED": "0"}, "scatter_atomic": {"RSYS_SCATTER_ATOMIC": "1"},
+        # round 6: gemm8c's half tiles forced
+        "gemm8c_half": {"RSYS_GEMM8C_HALF": "2", "RSYS_GEMM_KERNEL": "2"},
         # round 6, late: the four-wave register-named loops forced on (row-major plain stores, every eligible shape) / off (weight gradients back on the
         # eight-wave kernels), the mixed-layout dEw kernel forced, the reverse walk of the tile rows on every gemm8c launch
         "gemm4p_forced": {"RSYS_GEMM4P": "2", "RSYS_GEMM_KERNEL": "2"}, "gemm4k_off": {"RSYS_GEMM4K": "0", "RSYS_GEMM_KERNEL_TN": "2"},

@@ -530,7 +530,8 @@ def test_environment_is_read_in_one_place():
     for env, field, _ in names:
         assert re.search(r"\bint " + field + r";", header), field
         assert env in design, env
-    for gone in ("RSYS_ATTN_PAIR", "RSYS_ATTN_ORDER", "RSYS_DEBUG_KEEP_PERSISTENT"):
+    for gone in ("RSYS_ATTN_PAIR", "RSYS_ATTN_ORDER", "RSYS_DEBUG_KEEP_PERSISTENT",
+                 "RSYS_ATTN_FWD32", "RSYS_ATTN_KV32", "RSYS_ATTN_KV_DMA", "RSYS_SIDE_STREAM", "RSYS_SELECT_ASIDE"):
         assert gone not in open(os.path.join(csrc, "switches.hip")).read()
 
 

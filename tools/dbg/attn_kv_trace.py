@@ -1,4 +1,4 @@
-"""Where a dK/dV workgroup's time goes (attn_bwd_kv_dma_kernel built with -DATTN_KV_TRACE: tools/trace_attn_kv.sh): wall-clock stamps
+"""Where a dK/dV workgroup's time goes (attn_bwd_kv32_kernel built with -DATTN_KV_TRACE: tools/trace_attn_kv.sh): wall-clock stamps
 (10 ns) of wave 0 at entry, after the first item is staged, after the item loop, at exit, and the item loop's phases summed per workgroup.
 Each stamp is an s_memrealtime that drains the scalar queue, so the short phases are somewhat overstated."""
 import ctypes as C, os, sys
