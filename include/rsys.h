@@ -130,9 +130,18 @@ int32_t rsys_batch_swap(rsys_model* m);
  * rsys_batch_row_length: interactions per row of the resident batch: S after an ordinary upload, 0 without a batch.
  * rsys_serving_trim_set (default 0; read by rsys_render_request and rsys_render_request_full only): every forward of those pipelines
  *   runs at row_len = min(S, 32 ceil(longest live row of that forward / 32)) -- whole 64-token attention tiles.  Waves, chunks, slots
- *   and outputs are unchanged; with the switch off every launch is what it was. */
+ *   and outputs are unchanged; with the switch off every launch is what it was.
+ * rsys_serving_pack_set (default 0; read by rsys_render_request and rsys_render_request_full only): the retrieval stage of
+ *   those pipelines runs several users per row.  A user's live columns (through its query token) become a segment that starts at a
+ *   column that is a multiple of 32 and lies inside one row; users are placed first-fit in decreasing length, ties in user order, and
+ *   a forward is max_rows such rows at row_len = min(S, 32 ceil(its fullest row / 32)), whatever rsys_serving_trim_set says.  Each
+ *   segment runs with the adapter slot of its own medium (one slot per 64-token tile).  A retrieval row must hold one user (one userid
+ *   beside 0: RSYS_ERR_ARG otherwise).  Q and everything after it is in user order as before: pages, totals, ranking waves, store
+ *   rows, slots and chunks are unchanged; "forward_rows" reports the packed forwards as (0, rows, row_len). */
 int32_t rsys_batch_upload_trimmed(rsys_model* m, const rsys_batch* b, int32_t row_len);
 int32_t rsys_batch_row_length(rsys_model* m, int32_t* row_len_out);
+int32_t rsys_serving_pack_set(rsys_model* m, int32_t on);
+int32_t rsys_serving_pack_get(rsys_model* m, int32_t* on_out);
 int32_t rsys_serving_trim_set(rsys_model* m, int32_t on);
 int32_t rsys_serving_trim_get(rsys_model* m, int32_t* on_out);
 /* device-side synthetic batch (bench): fills the resident batch from a counter RNG */
@@ -540,6 +549,15 @@ int32_t rsys_adapter_slots(rsys_model* m, int32_t* mask_out);
  * rsys_infer_select.  RSYS_ERR_ARG (out untouched): row_adapter NULL, an entry out of range or naming an incomplete slot, no batch. */
 int32_t rsys_infer_select_adapters(rsys_model* m, int32_t task, const int32_t* row_adapter, const int32_t* token_index, int64_t n_tokens,
                                    float* out, int64_t n);
+/* rsys_infer_select_adapters on packed serving rows: several users share a batch row, each in a segment that starts at
+ * an interaction column that is a multiple of 32 (a multiple of 64 tokens), so no 64-token tile holds two users and a slot per tile is
+ * enough.  tile_adapter int32 [rows][ceil(S / 32)] in the caller's geometry (S = max_sequence_length): entry j of row r is the slot, or
+ * -1 = the base model, of interactions [32 j, 32 j + 32) of row r.  On a trimmed batch the entries behind row_len are range-checked and
+ * otherwise unused; token_index keeps r * 2S + t.  The per-token arithmetic is that of rsys_infer_select_adapters: a user's result does
+ * not depend on the slots of other tiles.  tile_adapter == NULL behaves as rsys_infer_select.  RSYS_ERR_ARG (out untouched): an entry
+ * outside [-1, RSYS_ADAPTER_SLOTS) or naming an incomplete slot, no batch, an fp8 or finetune = 1 model. */
+int32_t rsys_infer_select_tiles(rsys_model* m, int32_t task, const int32_t* tile_adapter, const int32_t* token_index, int64_t n_tokens,
+                                float* out, int64_t n);
 /* Training through the adapter bank: the reference's daily finetune -- four rank-8 adapters, one per medium and metric, as
  * four sequential jobs on the same frozen trunk (Finetune/run.jl:9-13; transformer.py:591-597, 259-276) -- as ONE pass over a batch whose
  * rows name their slot and task.

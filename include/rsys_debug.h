@@ -270,6 +270,12 @@ int32_t rsys_op_adapter_bank(int32_t dtype, int32_t stages, int32_t train, int32
                              int32_t L, int32_t layer, float p, uint64_t seed, int64_t stream, const int32_t* row_slot, const void* bankA,
                              const void* bankB, const void* xn, void* La, void* qkv, const void* dqkv, void* dLa, void* dxn, float* partA, float* partB,
                              float* gA, float* gB, const float* rope_cos, const float* rope_sin, const int32_t* rope_pos, int32_t rope_rows);
+/* rsys_op_adapter_bank restricted to the forward (stages a mask of 1 and 2, train == 0) in the per-tile form of packed serving rows:
+ * tile_slot int32 [rows][ceil(Ttok / 64)] (device) in place of row_slot, tokens [64 j, 64 j + 64) of row r run with slot
+ * tile_slot[r][j]; a tile with -1 is neither read nor written.  Same buffers and argument checks. */
+int32_t rsys_op_adapter_bank_tiles(int32_t dtype, int32_t stages, int32_t rows, int32_t Ttok, int32_t D, int32_t H, int32_t KV, int32_t hd, int32_t L,
+                                   int32_t layer, const int32_t* tile_slot, const void* bankA, const void* bankB, const void* xn, void* La, void* qkv,
+                                   const float* rope_cos, const float* rope_sin, const int32_t* rope_pos, int32_t rope_rows);
 int32_t rsys_op_adapter_bank_adamw(int32_t dtype, float* A32, float* B32, float* gA, float* gB, float* mA, float* vA, float* mB, float* vB, void* A,
                                    void* B, int64_t nA, int64_t nB, const float* per_slot, float b1, float b2, float eps, float wd, float* norms);
 int32_t rsys_op_dropout(int32_t dtype, const void* src, void* dst, int64_t n, float p, uint64_t seed, int64_t stream, int32_t accumulate);

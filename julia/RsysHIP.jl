@@ -128,6 +128,16 @@ function infer_select_adapters(m::Model, task::Integer, row_adapter::Vector{Int3
                                                     m.h, task, row_adapter, tokens, length(tokens), out, length(out)))
     out
 end
+# the same on packed rows (rsys.h: rsys_infer_select_tiles): tile_adapter (ceil(S / 32), rows) column-major = [rows][ceil(S / 32)], a slot or
+# -1 per 32 interactions of a row; `nothing` runs the base model
+function infer_select_tiles(m::Model, task::Integer, tile_adapter::Union{Matrix{Int32},Nothing}, tokens::Vector{Int32}, D::Integer)
+    out = task == 0 ? Matrix{Float32}(undef, D, length(tokens)) : Vector{Float32}(undef, length(tokens))
+    ta = tile_adapter === nothing ? Ptr{Int32}(C_NULL) : pointer(tile_adapter)
+    GC.@preserve tile_adapter tokens out check(ccall((:rsys_infer_select_tiles, LIB), Int32,
+                                                     (Ptr{Cvoid}, Int32, Ptr{Int32}, Ptr{Int32}, Int64, Ptr{Float32}, Int64),
+                                                     m.h, task, ta, tokens, length(tokens), out, length(out)))
+    out
+end
 
 # Training through the adapter bank (rsys.h: rsys_adapter_train_enable ...; Finetune/run.jl:9-13 as one pass): row r of the resident
 # batch runs with slot row_slot[r] on task row_task[r] = medium * 2 + metric (-1 / -1: base model, no loss)
@@ -145,6 +155,12 @@ function batch_row_length(m::Model)
     n = Ref{Int32}(0)
     check(ccall((:rsys_batch_row_length, LIB), Int32, (Ptr{Cvoid}, Ref{Int32}), m.h, n))
     Int(n[])
+end
+serving_pack!(m::Model, on::Bool) = check(ccall((:rsys_serving_pack_set, LIB), Int32, (Ptr{Cvoid}, Int32), m.h, on ? 1 : 0))
+function serving_pack(m::Model)   # the retrieval stage of the two render calls packs several users into a row
+    on = Ref{Int32}(0)
+    check(ccall((:rsys_serving_pack_get, LIB), Int32, (Ptr{Cvoid}, Ref{Int32}), m.h, on))
+    on[] != 0
 end
 serving_trim!(m::Model, on::Bool) = check(ccall((:rsys_serving_trim_set, LIB), Int32, (Ptr{Cvoid}, Int32), m.h, on ? 1 : 0))
 function serving_trim(m::Model)

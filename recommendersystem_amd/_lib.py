@@ -142,9 +142,12 @@ _SIGS = [
     ("rsys_adapter_clear", C.c_int32, [_P, C.c_int32]),
     ("rsys_adapter_slots", C.c_int32, [_P, C.POINTER(C.c_int32)]),
     ("rsys_infer_select_adapters", C.c_int32, [_P, C.c_int32, _P, _P, C.c_int64, _P, C.c_int64]),
+    ("rsys_infer_select_tiles", C.c_int32, [_P, C.c_int32, _P, _P, C.c_int64, _P, C.c_int64]),
     ("rsys_batch_rows", C.c_int32, [_P, C.POINTER(C.c_int32)]),
     ("rsys_batch_upload_trimmed", C.c_int32, [_P, C.POINTER(rsys_batch), C.c_int32]),
     ("rsys_batch_row_length", C.c_int32, [_P, C.POINTER(C.c_int32)]),
+    ("rsys_serving_pack_set", C.c_int32, [_P, C.c_int32]),
+    ("rsys_serving_pack_get", C.c_int32, [_P, C.POINTER(C.c_int32)]),
     ("rsys_serving_trim_set", C.c_int32, [_P, C.c_int32]),
     ("rsys_serving_trim_get", C.c_int32, [_P, C.POINTER(C.c_int32)]),
     ("rsys_adapter_train_enable", C.c_int32, [_P, C.c_float]),
@@ -227,6 +230,7 @@ _SIGS = [
     ("rsys_op_clip_adamw", C.c_int32, [C.c_int32] + [_P] * 5 + [C.c_int64, C.c_int64] + [C.c_float] * 5
                                        + [C.c_int32, C.c_float, C.c_float, C.c_int32, C.c_int64, C.c_int64, C.c_int32, _P]),
     ("rsys_op_adapter_bank", C.c_int32, [C.c_int32] * 11 + [C.c_float, C.c_uint64, C.c_int64] + [_P] * 16 + [C.c_int32]),
+    ("rsys_op_adapter_bank_tiles", C.c_int32, [C.c_int32] * 10 + [_P] * 9 + [C.c_int32]),
     ("rsys_op_adapter_bank_adamw", C.c_int32, [C.c_int32] + [_P] * 10 + [C.c_int64, C.c_int64, _P] + [C.c_float] * 4 + [_P]),
     ("rsys_op_dropout", C.c_int32, [C.c_int32, _P, _P, C.c_int64, C.c_float, C.c_uint64, C.c_int64, C.c_int32]),
     ("rsys_step_mark", C.c_int32, [_P]),

@@ -4,7 +4,8 @@
 //   stage A   La[t, 0:16]  = xn[t, :] . [A_q; A_v][slot(t)]^T                        (once per layer, reads xn once)
 //   stage B   q[t, :]     += rope(2 * La[t, 0:8] . B_q[slot(t)]^T),  v[t, :] += 2 * La[t, 8:16] . B_v[slot(t)]^T   (k is not touched)
 // A workgroup works on tokens of ONE batch row (a row is 2S consecutive tokens), so the slot is workgroup-uniform; rows with slot -1
-// return before their first load.  Rounding points are those of the finetune model's two LoRA GEMMs (model_forward.hip): operands
+// return before their first load.  Packed serving rows (several users per row, segments of whole 64-token tiles) name a slot
+// per TILE instead: the two forward kernels have a per-tile form on the same body.  Rounding points are those of the finetune model's two LoRA GEMMs (model_forward.hip): operands
 // and La in the compute type, fp32 accumulation, alpha = 2 on the fp32 sum, the q part rotated and added to the rotated projection.
 // No atomics: every sum has a fixed order.
 #include "model_internal.hpp"
@@ -18,6 +19,8 @@ struct AdapterBank {
   int* d_rows = nullptr;                  // [rows_max] slot per batch row of the current call
   std::vector<unsigned char> have[RSYS_ADAPTER_SLOTS];   // per slot: tensor (4 l + {qA, qB, vA, vB}) has been set since the last clear
   bool any_row = false;                   // the current call names at least one slot
+  int* d_tiles = nullptr;                 // [rows_max][ceil(Ta / 64)] slot per 64-token tile of the current call (packed rows)
+  std::vector<int32_t> h_tiles;           // its host image in the resident rows' geometry (the source of a stream-ordered copy)
   // ---- training through the bank (allocated by rsys_adapter_train_enable)
   bool train = false;
   float dropout = 0.f;                    // nn.Dropout(p) on the LoRA input, training passes only
@@ -35,6 +38,7 @@ struct AdapterBank {
 struct BankLaunch {                       // the plain arguments of one layer's bank launches
   int rows, Ttok, D, H, KV, hd, L, layer;
   const int* row_slot;                    // [rows] device
+  const int* tile_slot = nullptr;         // [rows][ceil(Ttok / 64)] device: the forward stages read it instead of row_slot when set
   const void *bankA, *bankB;              // compute type: [slots][L][16][D], [slots][L][Nq + Nv][8]
   float p; unsigned long long seed; unsigned int stream;   // dropout key (a_train, da, dx)
   hipStream_t s;
@@ -97,13 +101,12 @@ constexpr int BANK_B_TOK = 8;    // tokens per workgroup of stage B (2S is a mul
 
 // grid (ceil(2S / 16), rows), 256 threads: the four waves split K (wave w takes the K steps w, w + 4, ...), their partial tiles are
 // added in wave order through LDS.  Tokens past the row's end (2S % 16 == 8) load zeros and store nothing.
+// (the body both forward forms of stage A share: `slot` >= 0 is the workgroup's)
 template <typename T>
-__global__ __launch_bounds__(256) void adapter_bank_a_kernel(const T* __restrict__ xn, const T* __restrict__ bankA, const int* __restrict__ row_slot,
-                                                             int layer, int L, int D, int Ttok, T* __restrict__ La) {
+__device__ __forceinline__ void bank_a_body(const T* __restrict__ xn, const T* __restrict__ bankA, int row, int slot, int layer, int L, int D, int Ttok,
+                                            T* __restrict__ La) {
   using MM = BankMma<T>;
   __shared__ float red[4][4][64];
-  const int row = blockIdx.y, slot = row_slot[row];
-  if (slot < 0) return;
   const int t0 = blockIdx.x * BANK_A_TOK;
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int r = lane & 15, kq = lane >> 4;
@@ -126,16 +129,29 @@ __global__ __launch_bounds__(256) void adapter_bank_a_kernel(const T* __restrict
   const int tok = t0 + 4 * kq + w;
   if (tok < Ttok) La[((long long)row * Ttok + tok) * 16 + r] = from_f32<T>(sum);
 }
+template <typename T>
+__global__ __launch_bounds__(256) void adapter_bank_a_kernel(const T* __restrict__ xn, const T* __restrict__ bankA, const int* __restrict__ row_slot,
+                                                             int layer, int L, int D, int Ttok, T* __restrict__ La) {
+  const int row = blockIdx.y, slot = row_slot[row];
+  if (slot < 0) return;
+  bank_a_body<T>(xn, bankA, row, slot, layer, L, D, Ttok, La);
+}
+// Packed serving rows: one slot per 64-token attention tile, tile_slot[row][nt] with nt = ceil(Ttok / 64).  The workgroup's
+// 16 tokens lie inside one tile (16 | 64), so the slot is still workgroup-uniform and the sums are those of the row-slot form.
+template <typename T>
+__global__ __launch_bounds__(256) void adapter_bank_a_tiles_kernel(const T* __restrict__ xn, const T* __restrict__ bankA, const int* __restrict__ tile_slot,
+                                                                   int nt, int layer, int L, int D, int Ttok, T* __restrict__ La) {
+  const int row = blockIdx.y, slot = tile_slot[row * nt + ((blockIdx.x * BANK_A_TOK) >> 6)];
+  if (slot < 0) return;
+  bank_a_body<T>(xn, bankA, row, slot, layer, L, D, Ttok, La);
+}
 
 // grid (2S / 8, rows), 256 threads; a work item = 8 consecutive q or v columns of one token (one 16-byte access of bf16 qkv; 8 | hd, so
 // the item's RoPE pairs are its own).  The k columns are neither read nor written.
 template <typename T>
-__global__ __launch_bounds__(256) void adapter_bank_b_kernel(const T* __restrict__ La, const T* __restrict__ bankB, const int* __restrict__ row_slot,
-                                                             int layer, int L, int Nq, int Nk, int Nv, int Ttok, int hd,
-                                                             const float* __restrict__ rope_cos, const float* __restrict__ rope_sin,
-                                                             const int* __restrict__ rope_pos, T* __restrict__ qkv) {
-  const int row = blockIdx.y, slot = row_slot[row];
-  if (slot < 0) return;
+__device__ __forceinline__ void bank_b_body(const T* __restrict__ La, const T* __restrict__ bankB, int row, int slot, int layer, int L, int Nq, int Nk, int Nv,
+                                            int Ttok, int hd, const float* __restrict__ rope_cos, const float* __restrict__ rope_sin,
+                                            const int* __restrict__ rope_pos, T* __restrict__ qkv) {
   const int t0 = blockIdx.x * BANK_B_TOK;
   const int ntok = min(BANK_B_TOK, Ttok - t0);
   const int G = (Nq + Nv) >> 3, ld = Nq + Nk + Nv;
@@ -173,6 +189,25 @@ __global__ __launch_bounds__(256) void adapter_bank_b_kernel(const T* __restrict
     for (int k = 0; k < 8; ++k) u[k] += old[k];
     store8<T>(dst, u);
   }
+}
+template <typename T>
+__global__ __launch_bounds__(256) void adapter_bank_b_kernel(const T* __restrict__ La, const T* __restrict__ bankB, const int* __restrict__ row_slot,
+                                                             int layer, int L, int Nq, int Nk, int Nv, int Ttok, int hd,
+                                                             const float* __restrict__ rope_cos, const float* __restrict__ rope_sin,
+                                                             const int* __restrict__ rope_pos, T* __restrict__ qkv) {
+  const int row = blockIdx.y, slot = row_slot[row];
+  if (slot < 0) return;
+  bank_b_body<T>(La, bankB, row, slot, layer, L, Nq, Nk, Nv, Ttok, hd, rope_cos, rope_sin, rope_pos, qkv);
+}
+// the per-tile form (8 | 64: the workgroup's 8 tokens lie inside one tile)
+template <typename T>
+__global__ __launch_bounds__(256) void adapter_bank_b_tiles_kernel(const T* __restrict__ La, const T* __restrict__ bankB, const int* __restrict__ tile_slot,
+                                                                   int nt, int layer, int L, int Nq, int Nk, int Nv, int Ttok, int hd,
+                                                                   const float* __restrict__ rope_cos, const float* __restrict__ rope_sin,
+                                                                   const int* __restrict__ rope_pos, T* __restrict__ qkv) {
+  const int row = blockIdx.y, slot = tile_slot[row * nt + ((blockIdx.x * BANK_B_TOK) >> 6)];
+  if (slot < 0) return;
+  bank_b_body<T>(La, bankB, row, slot, layer, L, Nq, Nk, Nv, Ttok, hd, rope_cos, rope_sin, rope_pos, qkv);
 }
 
 
@@ -597,14 +632,46 @@ int adapter_bind_rows(Model* m, const int32_t* row_adapter) {
   m->bank_rows = b->d_rows;
   return RSYS_OK;
 }
-void adapter_unbind_rows(Model* m) { m->bank_rows = nullptr; }
+void adapter_unbind_rows(Model* m) { m->bank_rows = nullptr; m->bank_tiles = nullptr; }
+
+// Packed serving rows: tile_adapter [rows][ceil(Sa / 32)] in the caller's geometry, entry j of row r = the slot of
+// interactions [32 j, 32 j + 32) = tokens [64 j, 64 j + 64).  Every entry is checked; the ceil(S / 32) leading entries of each row -- the
+// tiles the resident (possibly trimmed) rows have -- become the tile map of the next forward_trunk (m->bank_tiles).
+int adapter_bind_tiles(Model* m, const int32_t* tile_adapter) {
+  RC(bank_check_model(m));
+  ARG_CHECK(tile_adapter != nullptr, "tile_adapter is null");
+  ARG_CHECK(m->cur_rows > 0, "no batch uploaded");
+  const int nta = (m->Sa + 31) / 32, nt = (m->S + 31) / 32;
+  bool any = false;
+  for (int i = 0; i < m->cur_rows * nta; ++i) {
+    const int s = tile_adapter[i];
+    ARG_CHECK(s >= -1 && s < RSYS_ADAPTER_SLOTS, "tile_adapter entries must be in [-1, RSYS_ADAPTER_SLOTS)");
+    if (s >= 0) ARG_CHECK(bank_complete(m, s), "tile_adapter names a slot that is not complete (4 tensors per layer since its last clear)");
+    if (s >= 0 && i % nta < nt) any = true;
+  }
+  m->bank_rows = nullptr; m->bank_tiles = nullptr;
+  if (!any) return RSYS_OK;   // every live tile runs the base model: the forward launches what rsys_infer_select launches
+  AdapterBank* b = m->bank;
+  HIP_CHECK(hipSetDevice(m->device));
+  if (!b->La) DALLOC(b->La, (int64_t)m->rows_max * m->Ta * 16 * m->esz);
+  if (!b->d_tiles) DALLOC(b->d_tiles, (int64_t)m->rows_max * nta * 4);
+  HIP_CHECK(hipStreamSynchronize(m->stream));   // (the previous call's copy has read h_tiles)
+  b->h_tiles.resize((size_t)m->cur_rows * nt);
+  for (int r = 0; r < m->cur_rows; ++r) std::copy(tile_adapter + (size_t)r * nta, tile_adapter + (size_t)r * nta + nt, b->h_tiles.begin() + (size_t)r * nt);
+  HIP_CHECK(hipMemcpyAsync(b->d_tiles, b->h_tiles.data(), b->h_tiles.size() * 4, hipMemcpyHostToDevice, m->stream));
+  m->bank_tiles = b->d_tiles;
+  return RSYS_OK;
+}
 
 // One layer's launches on plain arguments: what the model-side callers below fill from Model and the test hooks (rsys_op_adapter_bank,
 // rsys_debug.h) fill from the caller's buffers.  bankA / bankB: the compute-type copies; (p, seed, stream): the dropout key of BankDrop.
 template <typename T>
 int bank_launch_a(const BankLaunch& a, const T* xn, T* La, bool train) {
   const dim3 grid((a.Ttok + BANK_A_TOK - 1) / BANK_A_TOK, a.rows);
-  if (train)   // the LoRA input under the dropout mask
+  if (a.tile_slot)   // (forward only: adapter_bind_tiles and rsys_op_adapter_bank_tiles never come with train)
+    hipLaunchKernelGGL((adapter_bank_a_tiles_kernel<T>), grid, dim3(256), 0, a.s, xn, (const T*)a.bankA, a.tile_slot, (a.Ttok + 63) / 64, a.layer, a.L, a.D,
+                       a.Ttok, La);
+  else if (train)   // the LoRA input under the dropout mask
     hipLaunchKernelGGL((adapter_bank_a_train_kernel<T>), grid, dim3(256), 0, a.s, xn, (const T*)a.bankA, a.row_slot, a.layer, a.L, a.D, a.Ttok, La, a.p,
                        a.seed, a.stream);
   else
@@ -615,8 +682,13 @@ int bank_launch_a(const BankLaunch& a, const T* xn, T* La, bool train) {
 template <typename T>
 int bank_launch_b(const BankLaunch& a, const T* La, T* qkv, const float* rope_cos, const float* rope_sin, const int* rope_pos) {
   const int Nq = a.H * a.hd, Nk = a.KV * a.hd;
-  hipLaunchKernelGGL((adapter_bank_b_kernel<T>), dim3((a.Ttok + BANK_B_TOK - 1) / BANK_B_TOK, a.rows), dim3(256), 0, a.s, La, (const T*)a.bankB, a.row_slot,
-                     a.layer, a.L, Nq, Nk, Nk, a.Ttok, a.hd, rope_cos, rope_sin, rope_pos, qkv);
+  const dim3 grid((a.Ttok + BANK_B_TOK - 1) / BANK_B_TOK, a.rows);
+  if (a.tile_slot)
+    hipLaunchKernelGGL((adapter_bank_b_tiles_kernel<T>), grid, dim3(256), 0, a.s, La, (const T*)a.bankB, a.tile_slot, (a.Ttok + 63) / 64, a.layer, a.L, Nq, Nk,
+                       Nk, a.Ttok, a.hd, rope_cos, rope_sin, rope_pos, qkv);
+  else
+    hipLaunchKernelGGL((adapter_bank_b_kernel<T>), grid, dim3(256), 0, a.s, La, (const T*)a.bankB, a.row_slot, a.layer, a.L, Nq, Nk, Nk, a.Ttok, a.hd,
+                       rope_cos, rope_sin, rope_pos, qkv);
   HIP_CHECK(hipGetLastError());
   return RSYS_OK;
 }
@@ -653,7 +725,7 @@ static BankLaunch bank_launch_of(const Model* m, int l) {
   const AdapterBank* b = m->bank;
   BankLaunch a{};
   a.rows = m->cur_rows; a.Ttok = m->T; a.D = m->D; a.H = m->H; a.KV = m->KV; a.hd = m->hd; a.L = m->L; a.layer = l;
-  a.row_slot = m->bank_rows; a.bankA = b->A; a.bankB = b->B;
+  a.row_slot = m->bank_rows; a.tile_slot = m->bank_tiles; a.bankA = b->A; a.bankB = b->B;
   a.p = b->drop_now ? b->dropout : 0.f; a.seed = m->drop_seed; a.stream = (unsigned int)(m->drop_step * 64 + l);
   a.s = m->stream;
   return a;
@@ -781,7 +853,9 @@ static int bank_op_run(const BankLaunch& a, int stages, int train, const void* x
 int adapter_bank_op(int dtype, int stages, int train, int rows, int Ttok, int D, int H, int KV, int hd, int L, int layer, float p, uint64_t seed,
                     int64_t stream, const int32_t* row_slot, const void* bankA, const void* bankB, const void* xn, void* La, void* qkv, const void* dqkv,
                     void* dLa, void* dxn, float* partA, float* partB, float* gA, float* gB, const float* rope_cos, const float* rope_sin,
-                    const int32_t* rope_pos, int rope_rows) {
+                    const int32_t* rope_pos, int rope_rows, int tiles) {
+  // (tiles != 0, rsys_op_adapter_bank_tiles: row_slot is the tile map [rows][ceil(Ttok / 64)] and the two forward stages run in their per-tile form)
+  ARG_CHECK(!tiles || ((stages & ~3) == 0 && train == 0), "rsys_op_adapter_bank_tiles: stages 1 and 2 only (the forward, train = 0)");
   ARG_CHECK(dtype == RSYS_DTYPE_BF16 || dtype == RSYS_DTYPE_FP32, "rsys_op_adapter_bank: dtype fp32 or bf16");
   ARG_CHECK(stages >= 1 && stages <= 127, "rsys_op_adapter_bank: stages is a mask of bits 1 .. 64");
   ARG_CHECK(rows >= 1 && rows <= 65535 && Ttok >= 8 && L >= 1 && layer >= 0 && layer < L && H >= 1 && KV >= 1, "rsys_op_adapter_bank: empty shape or layer outside [0, L)");
@@ -804,7 +878,7 @@ int adapter_bank_op(int dtype, int stages, int train, int rows, int Ttok, int D,
   ARG_CHECK(!(stages & (16 | 64)) || partA, "rsys_op_adapter_bank: dA and the reductions use partA");
   ARG_CHECK(!(stages & (8 | 64)) || partB, "rsys_op_adapter_bank: dB and the reductions use partB");
   ARG_CHECK(!(stages & 64) || (gA && gB), "rsys_op_adapter_bank: the reductions need gA and gB");
-  std::vector<int32_t> host((size_t)rows);
+  std::vector<int32_t> host((size_t)rows * (tiles ? (Ttok + 63) / 64 : 1));
   HIP_CHECK(hipMemcpy(host.data(), row_slot, host.size() * 4, hipMemcpyDeviceToHost));
   for (int32_t v : host) ARG_CHECK(v >= -1 && v < RSYS_ADAPTER_SLOTS, "rsys_op_adapter_bank: row_slot entries must be in [-1, RSYS_ADAPTER_SLOTS)");
   if ((stages & 2) && rope_pos) {   // every explicit position inside the tables (one copy back)
@@ -816,7 +890,7 @@ int adapter_bank_op(int dtype, int stages, int train, int rows, int Ttok, int D,
   }
   BankLaunch a{};
   a.rows = rows; a.Ttok = Ttok; a.D = D; a.H = H; a.KV = KV; a.hd = hd; a.L = L; a.layer = layer;
-  a.row_slot = row_slot; a.bankA = bankA; a.bankB = bankB; a.p = p; a.seed = seed; a.stream = (unsigned int)stream; a.s = nullptr;
+  a.row_slot = tiles ? nullptr : row_slot; a.tile_slot = tiles ? row_slot : nullptr; a.bankA = bankA; a.bankB = bankB; a.p = p; a.seed = seed; a.stream = (unsigned int)stream; a.s = nullptr;
   int rc = dtype == RSYS_DTYPE_BF16
                ? bank_op_run<bf16>(a, stages, train, xn, La, qkv, dqkv, dLa, dxn, partA, partB, gA, gB, rope_cos, rope_sin, rope_pos)
                : bank_op_run<float>(a, stages, train, xn, La, qkv, dqkv, dLa, dxn, partA, partB, gA, gB, rope_cos, rope_sin, rope_pos);

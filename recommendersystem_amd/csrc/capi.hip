@@ -87,6 +87,8 @@ int32_t rsys_batch_row_length(rsys_model* h, int32_t* row_len_out) {
   *row_len_out = h->m->cur_rows > 0 ? h->m->S : 0;
   return RSYS_OK;
 }
+int32_t rsys_serving_pack_set(rsys_model* h, int32_t on) { CHECK_HANDLE(h); h->m->serving_pack = on != 0; return RSYS_OK; }
+int32_t rsys_serving_pack_get(rsys_model* h, int32_t* on_out) { CHECK_HANDLE(h); ARG_CHECK(on_out, "null"); *on_out = h->m->serving_pack ? 1 : 0; return RSYS_OK; }
 int32_t rsys_serving_trim_set(rsys_model* h, int32_t on) { CHECK_HANDLE(h); h->m->serving_trim = on != 0; return RSYS_OK; }
 int32_t rsys_serving_trim_get(rsys_model* h, int32_t* on_out) { CHECK_HANDLE(h); ARG_CHECK(on_out, "null"); *on_out = h->m->serving_trim ? 1 : 0; return RSYS_OK; }
 int32_t rsys_batch_prefetch(rsys_model* h, const rsys_batch* b) { CHECK_HANDLE(h); return model_batch_prefetch(h->m, b); }
@@ -323,6 +325,11 @@ int32_t rsys_infer_select_adapters(rsys_model* h, int32_t task, const int32_t* r
   CHECK_HANDLE(h); ARG_CHECK(out && token_index && n_tokens >= 1, "null or empty selection");
   ARG_CHECK(row_adapter, "row_adapter is null (rsys_infer_select runs the base model)");
   return model_infer_adapters(h->m, task, row_adapter, token_index, n_tokens, out, n);
+}
+int32_t rsys_infer_select_tiles(rsys_model* h, int32_t task, const int32_t* tile_adapter, const int32_t* token_index, int64_t n_tokens, float* out,
+                                int64_t n) {
+  CHECK_HANDLE(h); ARG_CHECK(out && token_index && n_tokens >= 1, "null or empty selection");
+  return model_infer_tiles(h->m, task, tile_adapter, token_index, n_tokens, out, n);
 }
 
 int32_t rsys_rank_cache_reserve(rsys_model* h, int32_t n_slots) { CHECK_HANDLE(h); return model_rank_cache_reserve(h->m, n_slots); }
@@ -1237,6 +1244,14 @@ int32_t rsys_op_adapter_bank(int32_t dtype, int32_t stages, int32_t train, int32
   switches_parse();
   return adapter_bank_op(dtype, stages, train, rows, Ttok, D, H, KV, hd, L, layer, p, seed, stream, row_slot, bankA, bankB, xn, La, qkv, dqkv, dLa, dxn,
                          partA, partB, gA, gB, rope_cos, rope_sin, rope_pos, rope_rows);
+}
+
+int32_t rsys_op_adapter_bank_tiles(int32_t dtype, int32_t stages, int32_t rows, int32_t Ttok, int32_t D, int32_t H, int32_t KV, int32_t hd, int32_t L,
+                                   int32_t layer, const int32_t* tile_slot, const void* bankA, const void* bankB, const void* xn, void* La, void* qkv,
+                                   const float* rope_cos, const float* rope_sin, const int32_t* rope_pos, int32_t rope_rows) {
+  switches_parse();
+  return adapter_bank_op(dtype, stages, 0, rows, Ttok, D, H, KV, hd, L, layer, 0.f, 0, 0, tile_slot, bankA, bankB, xn, La, qkv, nullptr, nullptr, nullptr,
+                         nullptr, nullptr, nullptr, nullptr, rope_cos, rope_sin, rope_pos, rope_rows, 1);
 }
 
 int32_t rsys_op_adapter_bank_adamw(int32_t dtype, float* A32, float* B32, float* gA, float* gB, float* mA, float* vA, float* mB, float* vB, void* A,

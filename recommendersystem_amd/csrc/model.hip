@@ -1082,13 +1082,14 @@ int infer_rows_device(Model* m, int task, const int* d_sel, int64_t ntok, float*
 template int infer_rows_device<float>(Model*, int, const int*, int64_t, float*, const float**);
 template int infer_rows_device<bf16>(Model*, int, const int*, int64_t, float*, const float**);
 
-int model_infer_device(Model* m, int task, const int32_t* row_adapter, const int* d_sel, int n_sel, float* d_out) {
+int model_infer_device(Model* m, int task, const int32_t* row_adapter, const int* d_sel, int n_sel, float* d_out, const int32_t* tile_adapter) {
   ARG_CHECK(m->cur_rows > 0, "no batch uploaded");
   ARG_CHECK(task == 0 || task == 1, "task: 0 retrieval, 1 ranking");
   ARG_CHECK(!m->fp8, "device-resident inference: fp32 and bf16 models only");
   ARG_CHECK(d_sel && d_out && n_sel >= 1 && n_sel <= 2 * m->cur_rows * m->S, "selection: 1 <= tokens <= the batch's");
   HIP_CHECK(hipSetDevice(m->device));
   if (row_adapter) RC(adapter_bind_rows(m, row_adapter));
+  if (tile_adapter) RC(adapter_bind_tiles(m, tile_adapter));
   const float* f = nullptr;
   const int rc = m->bf16_mode ? infer_rows_t<bf16>(m, task, d_sel, n_sel, d_out, &f) : infer_rows_t<float>(m, task, d_sel, n_sel, d_out, &f);
   adapter_unbind_rows(m);
@@ -1141,6 +1142,16 @@ int model_infer_adapters(Model* m, int task, const int32_t* row_adapter, const i
   ARG_CHECK(m->cur_rows > 0, "no batch uploaded");
   ARG_CHECK(task == 0 || task == 1, "task: 0 retrieval, 1 ranking");
   RC(adapter_bind_rows(m, row_adapter));
+  const int rc = m->bf16_mode ? infer_t<bf16>(m, task, token_index, n_tokens, out, n) : infer_t<float>(m, task, token_index, n_tokens, out, n);
+  adapter_unbind_rows(m);
+  return rc;
+}
+
+// the same forward on packed rows: a slot per 64-token tile; tile_adapter == nullptr: the base model
+int model_infer_tiles(Model* m, int task, const int32_t* tile_adapter, const int32_t* token_index, int64_t n_tokens, float* out, int64_t n) {
+  ARG_CHECK(m->cur_rows > 0, "no batch uploaded");
+  ARG_CHECK(task == 0 || task == 1, "task: 0 retrieval, 1 ranking");
+  if (tile_adapter) RC(adapter_bind_tiles(m, tile_adapter));
   const int rc = m->bf16_mode ? infer_t<bf16>(m, task, token_index, n_tokens, out, n) : infer_t<float>(m, task, token_index, n_tokens, out, n);
   adapter_unbind_rows(m);
   return rc;

@@ -96,6 +96,7 @@ struct Model {
   // the ranking cache's slot stride, the render pipelines' chunking.  S == Sa except under rsys_batch_upload_trimmed and the trimmed
   // forwards of the render pipelines; every ordinary upload, swap and device-assembled batch sets S = Sa.
   int Sa = 0, Ta = 0;
+  bool serving_pack = false;      // rsys_serving_pack_set: the retrieval stage of the two render entry points packs several users into a row
   bool serving_trim = false;      // rsys_serving_trim_set: the two render entry points run every forward at its longest live row
   int64_t fwd_tokens = 0;         // tokens the last forward_trunk ran over (rsys_debug_get "forward.tokens")
   int64_t n_decay = 0, n_total = 0;
@@ -272,6 +273,7 @@ struct Model {
   // every row's own update to q and v; every other pass leaves it null and launches what it always has
   AdapterBank* bank = nullptr;
   const int* bank_rows = nullptr;
+  const int* bank_tiles = nullptr;      // packed rows: one slot or -1 per 64-token tile, [rows][ceil(T / 64)]; non-null only inside rsys_infer_select_tiles
   // training through the bank: true only inside rsys_adapter_forward_backward.  The pass then treats the trunk as frozen
   // (the `ft` paths of the forward, heads and backward: dx chain only), keeps La per layer, draws the LoRA dropout inside the bank's
   // kernels and sends the few small gradients those paths still write (norm gains, rating-head biases) to bank_sink, never to G
@@ -323,7 +325,8 @@ int adapter_io(Model* m, int slot, const char* name, float* out, const float* in
 int adapter_clear(Model* m, int slot);
 int adapter_slots(Model* m, int32_t* mask_out);
 int adapter_bind_rows(Model* m, const int32_t* row_adapter);
-void adapter_unbind_rows(Model* m);
+int adapter_bind_tiles(Model* m, const int32_t* tile_adapter);   // [rows][ceil(Sa / 32)], the caller's geometry
+void adapter_unbind_rows(Model* m);                              // ends either binding
 void adapter_bank_free(Model* m);
 template <typename T> int adapter_bank_stage_a(Model* m, int l, const T* xn);                      // La = xn . [A_q; A_v][slot]^T
 template <typename T> int adapter_bank_stage_b(Model* m, int l, T* qkv, const int* rope_pos);      // q, v += 2 La . B[slot]^T (q rotated)
@@ -344,12 +347,13 @@ template <typename T> int adapter_bank_backward(Model* m, int l, const T* xn, co
 int adapter_bank_op(int dtype, int stages, int train, int rows, int Ttok, int D, int H, int KV, int hd, int L, int layer, float p, uint64_t seed,
                     int64_t stream, const int32_t* row_slot, const void* bankA, const void* bankB, const void* xn, void* La, void* qkv, const void* dqkv,
                     void* dLa, void* dxn, float* partA, float* partB, float* gA, float* gB, const float* rope_cos, const float* rope_sin,
-                    const int32_t* rope_pos, int rope_rows);
+                    const int32_t* rope_pos, int rope_rows, int tiles = 0 /* row_slot is a tile map: rsys_op_adapter_bank_tiles */);
 int adapter_bank_adamw_op(int dtype, float* A32, float* B32, float* gA, float* gB, float* mA, float* vA, float* mB, float* vB, void* A, void* B,
                           int64_t nA, int64_t nB, const float* per_slot, float b1, float b2, float eps, float wd, float* norms);
 // the joint pass's body (model.hip): masks per row task (d_row_task: device, [rows]), forward, heads with every task at grad_scale, backward
 int model_forward_backward_rows(Model* m, int evaluate, const int* d_row_task, float grad_scale, uint64_t seed, uint64_t step);
 int model_infer_adapters(Model* m, int task, const int32_t* row_adapter, const int32_t* token_index, int64_t n_tokens, float* out, int64_t n);
+int model_infer_tiles(Model* m, int task, const int32_t* tile_adapter, const int32_t* token_index, int64_t n_tokens, float* out, int64_t n);
 // A batch whose arrays a kernel fills on the device (render_request.hip): makes `rows` rows the resident batch without a host copy and
 // returns where its arrays live in the current slot's blob (target arrays stay as they are: an inference forward never reads them).
 // rope_pos holds the per-token positions (2 p, 2 p + 1 for interaction position p), as rsys_batch_upload derives them.
@@ -358,7 +362,8 @@ int model_batch_device_begin(Model* m, int rows, BatchDevRows* out, int row_len 
 // the forward of rsys_infer_select_adapters over the resident batch with the selection (n_sel flat token indices) and the result
 // (task 0: n_sel x D trunk rows, task 1: n_sel rating-head values, fp32) both on the device; row_adapter (host) may be null (base model);
 // stream-ordered, no host wait
-int model_infer_device(Model* m, int task, const int32_t* row_adapter, const int* d_sel, int n_sel, float* d_out);
+// tile_adapter (host, [rows][ceil(Sa / 32)], instead of row_adapter): packed rows, one slot per 64-token tile (adapter_bind_tiles)
+int model_infer_device(Model* m, int task, const int32_t* row_adapter, const int* d_sel, int n_sel, float* d_out, const int32_t* tile_adapter = nullptr);
 // rank_cache.hip: full-length ranking through a per-user K/V cache of the history (rsys_rank_cache_*)
 int model_rank_cache_reserve(Model* m, int n_slots);
 int model_rank_cache_store(Model* m, const int32_t* row_adapter, const int32_t* n_hist, const int32_t* slot);

@@ -206,7 +206,7 @@ int forward_trunk(Model* m) {
       p.M = NT; p.N = 16; p.K = D; p.epi = EPI_STORE;
       RC(gemm<T>(m, "gemm_lora_a_fwd", p, false, false, false));
     }
-    if (m->bank_rows) RC(adapter_bank_stage_a<T>(m, l, AT<T>(a.xn)));   // rsys_infer_select_adapters: every row's own adapter (or none)
+    if (m->bank_rows || m->bank_tiles) RC(adapter_bank_stage_a<T>(m, l, AT<T>(a.xn)));   // rsys_infer_select_adapters: every row's own adapter (or none)
     {
       GemmParams p{};
       p.A = a.xn; p.lda = D; p.B = W<T>(m, m->lo[l].wqkv); p.ldb = D; p.C = a.qkv; p.ldc = m->Nqkv;
@@ -226,7 +226,7 @@ int forward_trunk(Model* m) {
       p.n_q = m->H * hd; p.n_k = m->KV * hd;
       RC(gemm<T>(m, "gemm_lora_b_fwd", p, false, false, false));
     }
-    if (m->bank_rows) RC(adapter_bank_stage_b<T>(m, l, AT<T>(a.qkv), rpos_l));
+    if (m->bank_rows || m->bank_tiles) RC(adapter_bank_stage_b<T>(m, l, AT<T>(a.qkv), rpos_l));
     if (m->rc_mode == 1) RC(rank_cache_store_layer<T>(m, l, AT<T>(a.qkv)));   // rsys_rank_cache_store: the forward as it is + this layer's K | V of the history rows into their slots
     if (m->rc_mode == 2) {   // rsys_rank_cache_candidates: the rows' candidates against their slots' cached history
       RC(rank_cache_attention<T>(m, l, AT<T>(a.qkv), AT<T>(a.O)));

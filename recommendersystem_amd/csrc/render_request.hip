@@ -7,6 +7,7 @@
 //   render_carve          the call's device arrays inside RenderState::ws
 //   retrieval_forward     the users' rows in waves of <= max_rows (media mixed, one adapter slot per row); the trunk output at each
 //                         user's query token goes to the query buffer Q [n_users][D] fp32; full: the rows' history columns stay on the device
+//                         (rsys_serving_pack_set: retrieval_forward_packed instead -- several users per row, one adapter slot per tile)
 //   retrieve_and_window   per medium the body of rsys_retrieve_request on the medium's rows of Q (gathered in user order), then
 //                         render.jl:447-465 on the host from the counts; window_kernel copies each group's slice to the candidate list
 //   plan_ranking          the ranking rows of every group with a page, as row descriptors: split rows (user x chunk of <= S - S/2
@@ -104,6 +105,20 @@ __global__ void __launch_bounds__(RN_THREADS) rank_scatter_kernel(const RowDesc*
 __global__ void __launch_bounds__(RN_THREADS) window_kernel(const Win* w, const int32_t* ids, int32_t* cand) {
   const Win d = w[blockIdx.x];
   for (int i = threadIdx.x; i < d.n; i += RN_THREADS) cand[d.dst + i] = ids[d.src + i];
+}
+
+// Packed retrieval rows (rsys_serving_pack_set): user d.user's segment -- columns [col0, col0 + cols) of row d.row of the
+// resident batch (rows of S columns) -- to columns [0, cols) of its kept history row (stride h.stride), the eight arrays a store row reads.
+// userid: the caller's value, not the segment's number inside the forward.  One workgroup per user of the wave.
+struct SegDesc { int user, row, col0, cols, userid; };
+struct SegSrc { const double* time; const int *userid, *gender, *source, *matchedid, *status; const float *rating, *progress; };
+__global__ void __launch_bounds__(RN_THREADS) unpack_rows_kernel(const SegDesc* segs, SegSrc b, int S, HistSrc h) {
+  const SegDesc d = segs[blockIdx.x];
+  for (int j = threadIdx.x; j < d.cols; j += RN_THREADS) {
+    const long long i = (long long)d.row * S + d.col0 + j, q = (long long)d.user * h.stride + j;
+    h.time[q] = b.time[i]; h.userid[q] = b.userid[i] != 0 ? d.userid : 0; h.gender[q] = b.gender[i]; h.source[q] = b.source[i];
+    h.matchedid[q] = b.matchedid[i]; h.status[q] = b.status[i]; h.rating[q] = b.rating[i]; h.progress[q] = b.progress[i];
+  }
 }
 
 #define RN_LAUNCH_CHECK() HIP_CHECK(hipGetLastError())
@@ -263,7 +278,7 @@ struct Render : RenderArgs {
   hipStream_t s = nullptr;
   bool keep = false;
   // device (render_carve)
-  float *Q, *Qs, *pred, *rm; int *d_sel, *d_order; int32_t* cand; RowDesc *d_rows, *d_store; Win* d_win;
+  float *Q, *Qs, *pred, *rm; int *d_sel, *d_order; int32_t* cand; RowDesc *d_rows, *d_store; Win* d_win; SegDesc* d_segs;
   HistSrc hist;                                  // the ranking prefixes as uploaded; full: the history columns of the retrieval rows
   // host plan: users and groups by medium, the groups with a page, the r_masked layout, the ranking rows, the result
   std::vector<int> users_m[2], groups_m[2], gloc;
@@ -279,16 +294,18 @@ struct Render : RenderArgs {
   // host tables of a wave, read by stream-ordered copies: the retrieval waves' tokens, a wave's adapter slots and candidate counts, the
   // store forward's rows (s_*, sd) and the candidate rows of a cached wave with their cache slots
   struct WaveTabs {
-    std::vector<int32_t> tok, ra, nc, s_nh, s_slot, s_ad, crow_slot;
+    std::vector<int32_t> tok, ra, nc, s_nh, s_slot, s_ad, crow_slot, tiles, place;
+    std::vector<SegDesc> segs;
     std::vector<int> s_tab, c_tab;
     std::vector<RowDesc> sd, crows;
   } t;
 
-  Render(Model* model, const RenderArgs& a) : RenderArgs(a), m(model), S(m->Sa), D(m->D), chunk(S - S / 2), RM(m->rows_max), trim(m->serving_trim) {}
+  Render(Model* model, const RenderArgs& a) : RenderArgs(a), m(model), S(m->Sa), D(m->D), chunk(S - S / 2), RM(m->rows_max), trim(m->serving_trim), pack(m->serving_pack) {}
 
   // rsys_serving_trim_set: a forward whose longest row has `live` live columns runs at this row length -- whole 64-token attention tiles,
   // clamped to S (serve.trim_length); off: S.  Chunking, waves and slots are planned on S either way.
   const bool trim;
+  const bool pack;   // rsys_serving_pack_set: the retrieval stage runs several users per row (retrieval_forward_packed)
   int row_len_for(int live) const { return trim ? std::min(S, (std::max(live, 1) + 31) / 32 * 32) : S; }
 
   // ---- arguments.  Checked here, before anything is enqueued: the request's shape, pagination, groups, offsets' monotonicity, adapter
@@ -379,6 +396,7 @@ struct Render : RenderArgs {
       d_sel = c.take<int>(sel_cap); d_order = c.take<int>(nu);
       cand = c.take<int32_t>((size_t)ng * RN_MAX_RANK);
       d_rows = c.take<RowDesc>(RM); d_store = c.take<RowDesc>(full ? RM : 0); d_win = c.take<Win>(ng);
+      d_segs = c.take<SegDesc>(pack && full ? (size_t)RM * ((S + 31) / 32) : 0);
       hist.time = c.take<double>(n_hist);
       hist.userid = c.take<int>(n_hist); hist.gender = c.take<int>(n_hist); hist.source = c.take<int>(n_hist);
       hist.matchedid = c.take<int>(n_hist); hist.status = c.take<int>(n_hist);
@@ -433,6 +451,110 @@ struct Render : RenderArgs {
       HIP_CHECK(hipStreamSynchronize(s));   // (t.tok / t.ra are rewritten by the next wave)
       ++R->forwards[0];
     }
+    if (keep) {
+      std::vector<float> h((size_t)nu * D);
+      HIP_CHECK(hipMemcpy(h.data(), Q, h.size() * 4, hipMemcpyDeviceToHost));
+      R->put("queries", h.data(), h.size());
+    }
+    return RSYS_OK;
+  }
+
+  // ---- 1. (rsys_serving_pack_set) the same stage with several users per row, serve.pack_plan's layout: user u's live columns -- through
+  // its query token, its last column with a userid and (full) its n_hist columns -- become a segment that starts on a 32-column boundary
+  // of a row; first-fit decreasing over the users, ties in user order; forwards of <= max_rows rows at the trim length of their fullest
+  // row, whatever rsys_serving_trim_set says.  A segment's userid is 1 + its place in the forward, its adapter slot goes per tile, and the
+  // trunk output at every query token lands in Qs in forward order, from where one gather puts Q into user order.
+  int retrieval_forward_packed() {
+    const int NT = (S + 31) / 32;
+    std::vector<int> n_live((size_t)nu), uid((size_t)nu, 0), order((size_t)nu);
+    for (int64_t u = 0; u < nu; ++u) {
+      const int32_t* id = rb->userid + (size_t)u * S;
+      int live = retrieval_token[u] / 2 + 1;
+      if (full) live = std::max(live, user_desc[4 * u] + 1);
+      int j = S;
+      while (j > live && id[j - 1] == 0) --j;
+      n_live[u] = std::max(live, j);
+      for (int c = 0; c < n_live[u]; ++c) {
+        if (id[c] == 0) continue;
+        ARG_CHECK(uid[u] == 0 || uid[u] == id[c], "render_request: a packed retrieval row holds one user (one userid beside 0)");
+        uid[u] = id[c];
+      }
+      order[u] = (int)u;
+    }
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return n_live[a] > n_live[b]; });
+    struct Seg { int user, col0; };
+    struct Row { int taken = 0, end = 0; std::vector<Seg> segs; };
+    std::vector<Row> prow;
+    for (int u : order) {
+      size_t r = 0;
+      while (r < prow.size() && prow[r].taken + n_live[u] > S) ++r;
+      if (r == prow.size()) prow.emplace_back();
+      prow[r].segs.push_back({u, prow[r].taken});
+      prow[r].end = prow[r].taken + n_live[u];
+      prow[r].taken += (n_live[u] + 31) / 32 * 32;
+    }
+    // the packed rows of one forward, host side (everything a segment does not cover stays zero)
+    const size_t cap = (size_t)RM * S;
+    std::vector<double> p_time(cap);
+    std::vector<int32_t> p_int[7];
+    std::vector<float> p_rating(cap), p_progress(cap);
+    for (auto& v : p_int) v.resize(cap);
+    const int32_t* src_i[7] = {rb->userid, rb->token_mask_ids, rb->gender, rb->source, rb->matchedid, rb->status, rb->rope_input_pos};
+    const std::vector<float> zf(cap, 0.f);
+    const std::vector<int32_t> zi(cap, 0);
+    t.place.assign((size_t)nu, 0);
+    int at = 0;   // users forwarded so far: the first row of Qs the forward writes
+    for (size_t r0 = 0; r0 < prow.size(); r0 += RM) {
+      const int nr = (int)std::min<size_t>(RM, prow.size() - r0);
+      std::fill(p_time.begin(), p_time.end(), 0.0); std::fill(p_rating.begin(), p_rating.end(), 0.f); std::fill(p_progress.begin(), p_progress.end(), 0.f);
+      for (auto& v : p_int) std::fill(v.begin(), v.end(), 0);
+      int end = 1;
+      for (int r = 0; r < nr; ++r) end = std::max(end, prow[r0 + r].end);
+      const int rl = std::min(S, (end + 31) / 32 * 32);
+      t.tok.clear(); t.segs.clear(); t.tiles.assign((size_t)nr * NT, -1);
+      for (int r = 0; r < nr; ++r) {
+        for (const Seg& sg : prow[r0 + r].segs) {
+          const int u = sg.user, n = n_live[u];
+          const size_t so = (size_t)u * S, po = (size_t)r * S + sg.col0;
+          std::copy(rb->time + so, rb->time + so + n, p_time.begin() + po);
+          for (int k = 0; k < 7; ++k) std::copy(src_i[k] + so, src_i[k] + so + n, p_int[k].begin() + po);
+          std::copy(rb->rating + so, rb->rating + so + n, p_rating.begin() + po);
+          std::copy(rb->progress + so, rb->progress + so + n, p_progress.begin() + po);
+          const int k1 = (int)t.tok.size() + 1;
+          for (int c = 0; c < n; ++c) if (p_int[0][po + c] != 0) p_int[0][po + c] = k1;
+          t.place[u] = at + k1 - 1;
+          t.tok.push_back(r * 2 * rl + 2 * sg.col0 + retrieval_token[u]);
+          t.segs.push_back({u, r, sg.col0, n, uid[u]});
+          if (slots) std::fill(t.tiles.begin() + (size_t)r * NT + sg.col0 / 32, t.tiles.begin() + (size_t)r * NT + (sg.col0 + n + 31) / 32, slots[2 * group_medium[group[u]]]);
+        }
+      }
+      const int nseg = (int)t.tok.size();
+      rsys_batch b{};
+      b.rows = nr;
+      b.userid = p_int[0].data(); b.token_mask_ids = p_int[1].data(); b.gender = p_int[2].data(); b.source = p_int[3].data();
+      b.matchedid = p_int[4].data(); b.status = p_int[5].data(); b.rope_input_pos = p_int[6].data();
+      b.time = p_time.data(); b.rating = p_rating.data(); b.progress = p_progress.data();
+      for (int k = 0; k < 6; ++k) { b.label[k] = zf.data(); b.weight[k] = zf.data(); b.position[k] = zi.data(); }
+      RC(rl == S ? model_batch_upload(m, &b) : model_batch_upload_trimmed(m, &b, rl));
+      R->note_forward(0, nr, rl);
+      if (full) {   // the users' history columns back to one kept row each, [n_users][S]: what the store rows are cut from
+        HIP_CHECK(hipMemcpyAsync(d_segs, t.segs.data(), (size_t)nseg * sizeof(SegDesc), hipMemcpyHostToDevice, s));
+        const BatchDev& bd = m->bd;
+        const SegSrc br{bd.time, bd.userid, bd.gender, bd.source, bd.matchedid, bd.status, bd.rating, bd.progress};
+        tic(m, "render_unpack_rows");
+        unpack_rows_kernel<<<nseg, RN_THREADS, 0, s>>>(d_segs, br, rl, hist);
+        RN_LAUNCH_CHECK();
+        toc(m);
+      }
+      HIP_CHECK(hipMemcpyAsync(d_sel, t.tok.data(), (size_t)nseg * 4, hipMemcpyHostToDevice, s));
+      RC(model_infer_device(m, 0, nullptr, d_sel, nseg, Qs + (size_t)at * D, slots ? t.tiles.data() : nullptr));
+      HIP_CHECK(hipStreamSynchronize(s));   // (the host tables and the packed rows are rewritten by the next forward)
+      ++R->forwards[0];
+      at += nseg;
+    }
+    HIP_CHECK(hipMemcpyAsync(d_order, t.place.data(), (size_t)nu * 4, hipMemcpyHostToDevice, s));
+    RC(launch_gather_rows_plain<float>(Qs, D, d_order, 0, Q, (int)nu, D, s));   // Q[u] = Qs[place[u]]: user order, as every later stage reads it
+    HIP_CHECK(hipStreamSynchronize(s));   // (Qs and d_order are the scratch of the next stage)
     if (keep) {
       std::vector<float> h((size_t)nu * D);
       HIP_CHECK(hipMemcpy(h.data(), Q, h.size() * 4, hipMemcpyDeviceToHost));
@@ -703,7 +825,7 @@ struct Render : RenderArgs {
 
   int run_stages() {
     RC(render_carve());
-    RC(retrieval_forward());
+    RC(pack ? retrieval_forward_packed() : retrieval_forward());
     RC(retrieve_and_window());
     plan_ranking();
     RC(rank_cached_waves());

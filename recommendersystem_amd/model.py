@@ -300,6 +300,18 @@ class RecommenderModel:
         check(lib().rsys_serving_trim_set(self._h, 1 if on else 0))
 
     @property
+    def serving_pack(self):
+        """rsys_serving_pack_set: the retrieval stage of `render_request` / `render_request_full` runs several users per row (segments of
+        whole 64-token tiles, one adapter slot per tile), each forward at the length of its fullest row.  Default off."""
+        on = C.c_int32()
+        check(lib().rsys_serving_pack_get(self._h, C.byref(on)))
+        return bool(on.value)
+
+    @serving_pack.setter
+    def serving_pack(self, on):
+        check(lib().rsys_serving_pack_set(self._h, 1 if on else 0))
+
+    @property
     def can_prefetch(self):
         """rsys_batch_prefetch / rsys_batch_swap: the next batch staged and copied beside the running step (replicated table)"""
         return self.config.get("table_shard") is None and not getattr(self, "_no_prefetch", False)   # (_no_prefetch: A/B switch of the tests)
@@ -377,16 +389,28 @@ class RecommenderModel:
             return out
         raise AssertionError(task)
 
-    def inference_select(self, d, task, token_index, adapters=None, row_len=None):
+    def inference_select(self, d, task, token_index, adapters=None, row_len=None, tile_adapters=None):
         """The inference forward reporting only the tokens a server reads (embed.py:147-161): `token_index` = flat token indices
         in [0, rows * 2S).  "retrieval" -> (n, D) trunk outputs, "ranking" -> (n,) rating-head values (computed on those rows only).
         `adapters`: one adapter-bank slot per batch row (-1 = the base model) or one slot for every row; None = the model as it is.
-        `row_len`: run the rows trimmed to that many interactions (`upload_trimmed`); `token_index` keeps the geometry row * 2S + token."""
+        `row_len`: run the rows trimmed to that many interactions (`upload_trimmed`); `token_index` keeps the geometry row * 2S + token.
+        `tile_adapters` (packed rows, `serve.build_packed`): (rows, ceil(S / 32)) slots, entry j of a row for its interactions
+        [32 j, 32 j + 32), -1 = the base model; instead of `adapters`."""
+        if adapters is not None and tile_adapters is not None:
+            raise ValueError("inference_select: adapters (one slot per row) or tile_adapters (one per 32 interactions), not both")
         self._upload_rows(d, row_len)
         idx = np.ascontiguousarray(np.asarray(token_index).reshape(-1), np.int32)
         D = self.config["embed_dim"]
         t = {"retrieval": 0, "ranking": 1}[task]
         out = np.empty((idx.size, D) if t == 0 else (idx.size,), np.float32)
+        if tile_adapters is not None:
+            S = self.config["max_sequence_length"]
+            rows = int(np.asarray(d["userid"]).size) // S
+            tiles = np.ascontiguousarray(np.asarray(tile_adapters).reshape(-1), np.int32)
+            if tiles.size != rows * -(-S // 32):
+                raise ValueError(f"inference_select: {tiles.size} tile slots for {rows} batch rows of {-(-S // 32)} tiles")
+            check(lib().rsys_infer_select_tiles(self._h, t, tiles.ctypes.data, idx.ctypes.data, idx.size, out.ctypes.data, out.size))
+            return out
         if adapters is None:
             check(lib().rsys_infer_select(self._h, t, idx.ctypes.data, idx.size, out.ctypes.data, out.size))
             return out

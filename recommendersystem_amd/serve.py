@@ -142,12 +142,99 @@ def _row_len(d, S, trim):
     return trim_length(live_columns(d), S) if trim else None
 
 
-def predict(model, users, task, medium, max_user_len=None, max_ranking_items=None, trim=False):
+def pack_plan(n_live, S, max_rows):
+    """Several users per serving row, as data: user i has `n_live[i]` >= 1 live columns (history + query, or history +
+    candidates) and takes ceil(n_live / 32) attention tiles of 32 interactions.  First-fit decreasing over the users (ties in user
+    order) into rows where first_column + n_live <= S; a segment starts on a tile boundary and lies inside one row.  Rows keep the
+    order they were opened in and a forward is a group of `max_rows` of them.  Returns [(row_len, [(user, row, first_column)])] with
+    row = the row inside its forward, segments in (row, column) order and row_len = `trim_length` of the forward's fullest row."""
+    n_live = [int(n) for n in n_live]
+    if any(n < 1 or n > S for n in n_live):
+        raise ValueError(f"pack_plan: every user needs 1 <= live columns <= {S}")
+    rows = []                                   # [columns taken (whole tiles), live end, [(user, first_column)]]
+    for u in sorted(range(len(n_live)), key=lambda i: -n_live[i]):      # (sorted is stable: ties stay in user order)
+        n = n_live[u]
+        row = next((r for r in rows if r[0] + n <= S), None)
+        if row is None:
+            row = [0, 0, []]; rows.append(row)
+        row[2].append((u, row[0]))
+        row[1] = row[0] + n
+        row[0] += 32 * -(-n // 32)
+    plan = []
+    for r0 in range(0, len(rows), max_rows):
+        group = rows[r0:r0 + max_rows]
+        plan.append((trim_length(max(r[1] for r in group), S), [(u, k, c0) for k, r in enumerate(group) for u, c0 in r[2]]))
+    return plan
+
+
+def build_packed(users, media, task, plan_forward, num_items_0, max_user_len=1024, max_ranking_items=1024, adapter_slots=None, hists=None):
+    """One forward of `pack_plan` as arrays.  `users` / `media`: the request's users and each one's medium (one int: the same for all);
+    `plan_forward` = (row_len, [(user, row, first_column)]).  A user's segment is the live prefix of its own `build_batch` row --
+    `rope_input_pos` and the candidates' `token_mask_ids` stay relative to the segment -- except `userid`: 1 + the segment's place in
+    the forward, distinct within a row; the columns between segments are zero.  Returns (d, index, tiles): the ten (rows, S) arrays,
+    per segment the flat token indices row * 2S + token `extract` would read, and the (rows, ceil(S / 32)) int32 map of
+    `adapter_slots["{medium}.{task}"]` over each segment's tiles, -1 elsewhere (None without `adapter_slots`).  `hists`: the users'
+    `_history(user, max_user_len)` when the caller has them already (each history is tokenised once per request)."""
+    width = max_user_len + (max_ranking_items if task == "ranking" else 0)
+    _, placed = plan_forward
+    rows = 1 + max(r for _, r, _ in placed)
+    d = _empty_rows(rows, width)
+    tiles = np.full((rows, -(-width // 32)), -1, np.int32) if adapter_slots else None
+    index = []
+    for k, (u, row, c0) in enumerate(placed):
+        medium = int(media if np.ndim(media) == 0 else media[u])
+        user = users[u]
+        hist = _history(user, max_user_len) if hists is None else hists[u]
+        ranking = task == "ranking"
+        seq = hist + ([make_item(user["timestamp"], medium, c) for c in user["ranking_items"]] if ranking else [make_item(user["timestamp"])])
+        n, nh = len(seq), len(hist)
+        if c0 % 32 or c0 + n > width or (ranking and n - nh > max_ranking_items) or d["userid"][row, c0:c0 + n].any():
+            raise ValueError(f"build_packed: user {u} does not fit at column {c0} of row {row}")
+        _fill_row(d, row, seq, nh, user["user"], num_items_0, ranking, c0)         # (the row `build_batch` fills for this user alone)
+        d["userid"][row, c0:c0 + n] = k + 1
+        toks = [2 * nh] if not ranking else [2 * (nh + j) + 1 for j in range(n - nh)]      # (`_selected_tokens` of the user's own row)
+        index.append([row * 2 * width + 2 * c0 + t for t in toks])
+        if tiles is not None:
+            tiles[row, c0 // 32:-(-(c0 + n) // 32)] = adapter_slots[f"{medium}.{task}"]
+    return d, index, tiles
+
+
+def _predict_packed(model, requests, task, max_user_len, max_ranking_items):
+    """`predict` / `predict_mixed` with several users per row: the forwards of `pack_plan` over the users that have a token to read,
+    each at its own trimmed length with one adapter slot per tile; results in request order."""
+    S = model.config["max_sequence_length"]
+    max_user_len, max_ranking_items = _request_lengths(model, task, max_user_len, max_ranking_items)
+    n0 = model.config["vocab_sizes"]["0_matchedid"]
+    users = [u for u, _ in requests]
+    media = [int(m) for _, m in requests]
+    out = [{f"{m}.{task}": []} for m in media]
+    tail = [1 if task == "retrieval" else len(u["ranking_items"]) for u in users]
+    live = [i for i, t in enumerate(tail) if t]
+    hists = [_history(u, max_user_len) for u in users]               # once per user
+    n_live = [len(hists[i]) + tail[i] for i in live]
+    slots = getattr(model, "adapter_slots", None)
+    for forward in pack_plan(n_live, S, model.max_rows):
+        sub = (forward[0], [(live[u], r, c0) for u, r, c0 in forward[1]])
+        d, index, tiles = build_packed(users, media, task, sub, n0, max_user_len, max_ranking_items, slots or None, hists)
+        kw = dict(tile_adapters=tiles) if tiles is not None else {}
+        vals = model.inference_select(d, task, [t for ix in index for t in ix], row_len=forward[0], **kw)
+        at = 0
+        for (u, _, _), ix in zip(sub[1], index):
+            out[u] = {f"{media[u]}.{task}": (vals[at].tolist() if task == "retrieval" else vals[at:at + len(ix)].tolist())}
+            at += len(ix)
+    return out
+
+
+def predict(model, users, task, medium, max_user_len=None, max_ranking_items=None, trim=False, pack=False):
     """embed.py:74-161 on the HIP model (`model.config["forward"]` semantics = inference): sequence length of the request =
     the model's `max_sequence_length` (retrieval: all of it is history + query; ranking: split between history and candidates).
     A model built by `get_models` (it has an `adapter_slots` map) runs every row with the adapter of "{medium}.{task}".
     `trim=True`: the forward runs at `trim_length` of the batch's longest live row instead of S (the padding behind it is dropped, which
-    is exact: no live token attends it)."""
+    is exact: no live token attends it).
+    `pack=True` (implies trimming): several users share a row, each in a segment of whole 64-token attention tiles (`pack_plan`), and any
+    number of users is served in forwards of at most `max_rows` rows; results are in the users' order."""
+    if pack:
+        return _predict_packed(model, [(u, medium) for u in users], task, max_user_len, max_ranking_items)
     S = model.config["max_sequence_length"]
     max_user_len, max_ranking_items = _request_lengths(model, task, max_user_len, max_ranking_items)
     d = build_batch(users, task, medium, model.config["vocab_sizes"]["0_matchedid"], max_user_len, max_ranking_items)
@@ -245,16 +332,19 @@ def predict_ranking_full(model, users, medium, trim=False):
     return out
 
 
-def predict_mixed(model, requests, task, max_user_len=None, max_ranking_items=None, trim=False):
+def predict_mixed(model, requests, task, max_user_len=None, max_ranking_items=None, trim=False, pack=False):
     """`predict` for users of both media in ONE forward: `requests` = [(user, medium), ...]; row i of the batch is the row
     `build_batch([user_i], task, medium_i, ...)` builds and runs with the adapter slot `model.adapter_slots[f"{medium_i}.{task}"]`
     (embed.jl:5-84 keeps one queue per (medium, task) on one GPU; single-user inference is launch-bound, so sharing a forward
-    is what the shared trunk buys).  Result i is keyed "{medium_i}.{task}" like `predict`'s."""
+    is what the shared trunk buys).  Result i is keyed "{medium_i}.{task}" like `predict`'s.  `pack=True`: users of both media share
+    rows as well (`pack_plan`, one adapter slot per tile)."""
     slots = getattr(model, "adapter_slots", None)
     if not slots:
         raise ValueError("predict_mixed: the model has no adapter_slots map (build it with get_models)")
     if not requests:
         return []
+    if pack:
+        return _predict_packed(model, requests, task, max_user_len, max_ranking_items)
     S = model.config["max_sequence_length"]
     max_user_len, max_ranking_items = _request_lengths(model, task, max_user_len, max_ranking_items)
     n0 = model.config["vocab_sizes"]["0_matchedid"]
@@ -765,21 +855,23 @@ def _render_states(model, states, pags, registry, max_ranking_items, full_histor
 _ROW_COLS = _INT_COLS + ("time", "rating", "progress")
 
 
-def _fill_row(d, row, seq, nh, who, num_items_0, ranking):
+def _fill_row(d, row, seq, nh, who, num_items_0, ranking, c0=0):
     """row `row` of the ten arrays from the token sequence `seq` (nh history tokens first), exactly as `build_batch` fills the row of a
-    one-user request: userid 1, history positions 0..nh-1 and mask id 0, appended tokens at position nh with their own mask id"""
+    one-user request: userid 1, history positions 0..nh-1 and mask id 0, appended tokens at position nh with their own mask id.
+    `c0`: the column the sequence starts at (a segment of a packed row; positions and mask ids stay relative to it)"""
     L = len(seq)
-    d["userid"][row, :L] = 1
-    d["gender"][row, :L] = 0 if who["gender"] is None else who["gender"] + 1
-    d["source"][row, :L] = who["source"]
-    d["time"][row, :L] = [e["history_max_ts"] for e in seq]
-    d["rope_input_pos"][row, :L] = np.minimum(np.arange(L), nh)
+    at = slice(c0, c0 + L)
+    d["userid"][row, at] = 1
+    d["gender"][row, at] = 0 if who["gender"] is None else who["gender"] + 1
+    d["source"][row, at] = who["source"]
+    d["time"][row, at] = [e["history_max_ts"] for e in seq]
+    d["rope_input_pos"][row, at] = np.minimum(np.arange(L), nh)
     if ranking:
-        d["token_mask_ids"][row, nh:L] = np.arange(nh, L)
-    d["matchedid"][row, :L] = [e["matchedid"] + (num_items_0 if e["medium"] == 1 else 0) for e in seq]
-    d["status"][row, :L] = [e["status"] for e in seq]
-    d["rating"][row, :L] = [e["rating"] for e in seq]
-    d["progress"][row, :L] = [e["progress"] for e in seq]
+        d["token_mask_ids"][row, c0 + nh:c0 + L] = np.arange(nh, L)
+    d["matchedid"][row, at] = [e["matchedid"] + (num_items_0 if e["medium"] == 1 else 0) for e in seq]
+    d["status"][row, at] = [e["status"] for e in seq]
+    d["rating"][row, at] = [e["rating"] for e in seq]
+    d["progress"][row, at] = [e["progress"] for e in seq]
 
 
 def _empty_rows(n, width):
@@ -883,7 +975,7 @@ def render_full_forwards(n_hist, n_cand, S, max_rows):
     return len(waves), sum(len(b) for _, b in waves), -(-len(empty) // max_rows)
 
 
-def render_users(model, states, pagination, registry=None, full_history=False, trim=False):
+def render_users(model, states, pagination, registry=None, full_history=False, trim=False, pack=False):
     """`render` from raw histories in ONE device call (rsys_render_request): the same states, but users need no "embeds" -- the
     retrieval forward, `retrieval`, the page window, the ranking forward (every chunk row of every user, both media, in waves of the
     model's max_rows) and `ranking` + `reranking` run back to back on the device; only the pages and the totals come back.  A model built
@@ -892,17 +984,24 @@ def render_users(model, states, pagination, registry=None, full_history=False, t
     `render(..., full_history=True)` inside the same call -- every user ranked on its newest S - 1 events through the per-user K/V cache,
     whose store rows the device cuts from the retrieval rows it already holds; no ranking prefix is built or uploaded.
     `trim=True` (rsys_serving_trim_set for the length of the call): every forward of the pipeline runs at the length of its longest live
-    row in whole 64-token tiles; waves, chunks, slots and outputs are unchanged."""
+    row in whole 64-token tiles; waves, chunks, slots and outputs are unchanged.
+    `pack=True` (rsys_serving_pack_set and, as packing implies trimming, rsys_serving_trim_set for the length of the call): the
+    retrieval stage runs several users per row (`pack_plan`'s layout); the ranking stages are the trimmed ones."""
     if not states:
         return []
+    trim = trim or pack
     args = render_pack(states, pagination, model.config["max_sequence_length"], model.config["vocab_sizes"]["0_matchedid"], registry,
                        getattr(model, "adapter_slots", None), full_history)
     before = model.serving_trim if trim else False
     if trim:
         model.serving_trim = True
+    if pack:
+        model.serving_pack = True
     try:
         pages, totals = (model.render_request_full if full_history else model.render_request)(**args)
     finally:
         if trim:
             model.serving_trim = before
+        if pack:
+            model.serving_pack = False
     return [(pages[g], int(totals[g])) for g in range(len(states))]
