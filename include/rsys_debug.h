@@ -279,6 +279,82 @@ int32_t rsys_op_adapter_bank_tiles(int32_t dtype, int32_t stages, int32_t rows, 
 int32_t rsys_op_adapter_bank_adamw(int32_t dtype, float* A32, float* B32, float* gA, float* gB, float* mA, float* vA, float* mB, float* vB, void* A,
                                    void* B, int64_t nA, int64_t nB, const float* per_slot, float b1, float b2, float eps, float wd, float* norms);
 int32_t rsys_op_dropout(int32_t dtype, const void* src, void* dst, int64_t n, float p, uint64_t seed, int64_t stream, int32_t accumulate);
+/* the kernels of the row-sharded table (csrc/shard.hip), unit-test access on caller-provided device buffers: every stage calls the launch
+ * routine the model path calls, unchanged, on the null stream; the call synchronises.  There is NO collective and NO GEMM inside: the logits
+ * are an input, and what the model all-reduces between two stages (lmax -> gmax, sums, the target logit) the caller reduces on the host and
+ * writes back, so "W ranks" are W calls with each rank's (Vloc or len, col0, logits block, rank).  `stages` is a mask, run in ascending bit
+ * order (the production order); a stage reads its inputs from the buffers below, so one bit runs that launcher alone on given
+ * intermediates; buffers of stages that are not selected may be null.  dtype RSYS_DTYPE_FP32 / BF16 = the T of the launcher (rows, logits).
+ * deterministic != 0: the call runs with deterministic-mode scratch of its own and returns RSYS_ERR_STATE if a launcher that has an ordered
+ * form (vp finish, ss finish, ss target_grad) did not take it.  RSYS_ERR_ARG before anything is launched where an argument is out of range;
+ * index arrays that address a caller buffer are copied back once for that.
+ * A row's meta is 4 floats {target id inside the medium (int bits), label * weight, gradient coefficient, 0}.
+ * rsys_op_vp_ce, stages 1 meta, 2 compact, 4 stats, 8 rebase, 16 finish:
+ *     meta      own f32 [KBmax * 4 + 1]: row j < KB gets {position[i], label[i] weight[i], task_w label[i] weight[i] / max(stats[0], 1e-8), 0}
+ *               with i = idx[j] (idx int32 [KB]; label, weight, position indexed by it), rows [KB, KBmax) zeros, own[KBmax * 4] = *npos (int
+ *               bits).  0 <= KB <= KBmax.
+ *     compact   EwAll T [W][KBmax][D], metaAll f32 [W][KBmax * 4 + 4] (element KBmax * 4 of a block = its live count n_q <= KBmax, int bits):
+ *               EwC T [W * KBmax][D] and metaC f32 [W * KBmax][4] get rows (q, i < n_q) packed at pre[q] + i; *nlive = sum n_q, pre int32
+ *               [W + 1] the prefix.  metaC rows [nlive, min(round_up(nlive, 256), W * KBmax)) are zeroed, everything behind is untouched
+ *               (so are the EwC rows from nlive on).  D a multiple of 16 bytes of T, 1 <= W <= 47.
+ *     stats     logits T [>= rows][ldl], ldl % 8 == 0, Vloc <= ldl local columns, the first being class col0.  For row < rows (rows <= cap):
+ *               lmax[row] = the row's maximum, sums[row] = sum exp(x - lmax), sums[cap + row] = the target's logit where col0 <= target <
+ *               col0 + Vloc, else 0; rows >= *nlive and Vloc == 0 give (-3e38, 0, 0).  lmax f32 [cap], sums f32 [2 cap].  Columns
+ *               [Vloc, ldl) are not interpreted.
+ *     rebase    sums[row] *= exp(lmax[row] - gmax[row]) for row < rows.
+ *     finish    grid of rows_finish <= cap rows (the model's min(cap, round_up(nlive, 256))).  Live rows: lse = gmax + log(sums[row]); a row
+ *               in [pre[rank], pre[rank + 1]) with label weight != 0 adds (lse - sums[cap + row]) label weight to loss[0]; the row becomes
+ *               coef (exp(x - lse) - [column == target - col0]) on [0, Vloc) and zeros on [Vloc, ldl).  Rows [nlive, rows_finish) are
+ *               zeroed over [0, ldl); later rows are untouched.
+ * rsys_op_ss (sampled soft-max), stages 1 sample, 2 targets, 4 drop_hits, 8 gather_rows_plain, 16 target_logit, 32 stats, 64 max_with_target,
+ * 128 rebase, 256 finish, 512 add_rows_plain, 1024 target_grad:
+ *     sample    cols int32 [n_s]: one class per stratum [floor(j len / n_s), floor((j + 1) len / n_s)) from Philox(seed)(j, stream)[0];
+ *               1 <= n_s <= len, stream in [0, 2^32).
+ *     targets   bitmap int32 [ceil(len / 32)] (bit b of word w = class 32 w + b) is cleared, the classes target - col0 in [0, len) of metaC rows < *nlive (< cap_rows = the
+ *               grid) are marked; tlist gets them ascending, *tcount their number; tlist behind that is untouched.
+ *     drop_hits cols[j] = -1 where the bitmap holds cols[j] (values in [0, len)).
+ *     gather_rows_plain   gdst T [rn][D] row j = gsrc row (rbase + ridx[j]) (row stride rld), zeros where ridx[j] < 0.
+ *     add_rows_plain      adst f32 row (rbase + ridx[j]) (stride rld) += asrc f32 [rn][D] row j; ridx[j] < 0 skipped; the others distinct.
+ *               Both: 0 <= rbase + ridx[j] < rtable_rows.
+ *     target_logit   tl[row] = <EwC row, Floc row (target - col0)> where that lies in [0, len), else 0, for row < min(rows, *nlive); EwC T
+ *               [rows][D], Floc T [len][D].
+ *     stats     logits T [>= rows][ldl >= n_tot]: column c < n_s belongs to sampled class cols[c] (weight s_c = its stratum's size), column
+ *               n_s <= c < n_tot to an in-batch target cols[c] (weight 1).  lmax / lsum [rows] = maximum and sum-exp of x + log weight
+ *               over the columns with cols[c] >= 0 and cols[c] != target - col0; rows >= *nlive and n_tot == 0 give (-3e38, 0).
+ *     max_with_target   gmax[row] = max(lmax[row], tl[row]), row < rows (tl summed over the ranks by the caller).
+ *     rebase    lsum[row] *= exp(lmax[row] - gmax[row]) (0 stays 0), row < rows.
+ *     finish    grid of rows_finish rows.  lse = gmax + log(exp(tl - gmax) + lsum); dt[row] = coef (exp(tl - lse) - 1); the owner of the row
+ *               ([pre[rank], pre[rank + 1]), label weight != 0) adds (lse - tl) label weight to loss[0]; column c becomes coef weight_c
+ *               exp(x - lse), or 0 at a dropped entry, at the row's own target and on [n_tot, ldl).  Rows [nlive, rows_finish): zeros,
+ *               dt = 0.  A rank without classes calls it with n_s = n_tot = 0, ldl = 8.
+ *     target_grad    for row < min(rows, *nlive) with a local target t and dt[row] != 0: gE_loc f32 [len][D] row t += dt[row] EwC[row] and
+ *               dEwC f32 [rows][D] row += dt[row] Floc[t]: float atomics, or (deterministic) the first row of a class adds for all rows
+ *               that share it, in row order; D <= 2048 there.
+ * rsys_op_shard_rows, stages 1 plan_unique, 2 plan_offsets, and at most one of 4 gather_rows_by_id, 8 add_rows_by_id, 16
+ * add_rows_by_id_counted, then 32 gather_items_remote:
+ *     plan_unique    skey int32 [N] ascending in [0, V] (V = the mask row), sidx [N] a permutation: slot[p] = rank of skey[p] among the distinct
+ *               keys, uniq[slot] = key, tok2u[sidx[p]] = slot[p]; V gets a slot even when absent (uniq [N + 1]); plan = {U, uV}.
+ *     plan_offsets   off[o] = first slot of uniq[0, plan[0]) with id >= bound[o], o < nb, 2 <= nb <= 64.
+ *     gather    packed f32 [n][D] row j = table row (ids[j] - sub) (stride ld);  add: table row (ids[j] - sub) += packed row j (ids distinct);
+ *               counted: table row ids[j] += packed row j for j < min(*count, n) (n is the capacity).  Ids inside [sub, sub + table_rows).
+ *     gather_items_remote   x0 f32 [2 Ntok][D] row 2 t = Frem row (m_matchedid[t] == -1 ? plan[1] : tok2u[t]) (odd rows untouched), uid_t /
+ *               tm_t int32 [2 Ntok] = userid[t] / m_tmid[t] twice; Frem f32 [frem_rows][D]. */
+int32_t rsys_op_vp_ce(int32_t dtype, int32_t stages, int32_t deterministic, const int32_t* idx, const float* label, const float* weight,
+                      const int32_t* position, const float* stats, const int32_t* npos, float task_w, int32_t KB, int32_t KBmax, float* own,
+                      const void* EwAll, const float* metaAll, int32_t W, int32_t D, void* EwC, float* metaC, int32_t* nlive, int32_t* pre,
+                      void* logits, int64_t ldl, int32_t Vloc, int32_t col0, float* lmax, const float* gmax, float* sums, int32_t cap,
+                      int32_t rank, float* loss, int32_t rows, int32_t rows_finish);
+int32_t rsys_op_ss(int32_t dtype, int32_t stages, int32_t deterministic, int32_t len, int32_t n_s, int32_t n_tot, int32_t col0, uint64_t seed,
+                   int64_t stream, int32_t* cols, int32_t* bitmap, int32_t* tlist, int32_t* tcount, const float* metaC, const int32_t* nlive,
+                   const int32_t* pre, int32_t rank, int32_t cap_rows, int32_t rows, int32_t rows_finish, const void* EwC, const void* Floc,
+                   int32_t D, void* logits, int64_t ldl, float* lmax, float* lsum, float* tl, float* gmax, float* loss, float* dt,
+                   float* gE_loc, float* dEwC, const int32_t* ridx, int32_t rbase, int64_t rld, int32_t rn, int32_t rtable_rows,
+                   const void* gsrc, void* gdst, const float* asrc, float* adst);
+int32_t rsys_op_shard_rows(int32_t stages, const int32_t* skey, const int32_t* sidx, int32_t N, int32_t V, int32_t* slot, int32_t* uniq,
+                           int32_t* tok2u, int32_t* plan, const int32_t* bound, int32_t nb, int32_t* off, float* table, int64_t ld,
+                           int32_t table_rows, const int32_t* ids, int32_t sub, float* packed, int32_t n, int32_t D, const int32_t* count,
+                           const int32_t* m_matchedid, const int32_t* userid, const int32_t* m_tmid, int32_t Ntok, const float* Frem,
+                           int32_t frem_rows, float* x0, int32_t* uid_t, int32_t* tm_t);
 
 #ifdef __cplusplus
 }

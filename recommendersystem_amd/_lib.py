@@ -233,6 +233,12 @@ _SIGS = [
     ("rsys_op_adapter_bank_tiles", C.c_int32, [C.c_int32] * 10 + [_P] * 9 + [C.c_int32]),
     ("rsys_op_adapter_bank_adamw", C.c_int32, [C.c_int32] + [_P] * 10 + [C.c_int64, C.c_int64, _P] + [C.c_float] * 4 + [_P]),
     ("rsys_op_dropout", C.c_int32, [C.c_int32, _P, _P, C.c_int64, C.c_float, C.c_uint64, C.c_int64, C.c_int32]),
+    ("rsys_op_vp_ce", C.c_int32, [C.c_int32] * 3 + [_P] * 6 + [C.c_float, C.c_int32, C.c_int32, _P, _P, _P, C.c_int32, C.c_int32]
+                                  + [_P] * 5 + [C.c_int64, C.c_int32, C.c_int32, _P, _P, _P, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32]),
+    ("rsys_op_ss", C.c_int32, [C.c_int32] * 7 + [C.c_uint64, C.c_int64] + [_P] * 7 + [C.c_int32] * 4 + [_P, _P, C.c_int32, _P, C.c_int64]
+                               + [_P] * 9 + [C.c_int32, C.c_int64, C.c_int32, C.c_int32] + [_P] * 4),
+    ("rsys_op_shard_rows", C.c_int32, [C.c_int32, _P, _P, C.c_int32, C.c_int32] + [_P] * 5 + [C.c_int32, _P, _P, C.c_int64, C.c_int32, _P,
+                                       C.c_int32, _P, C.c_int32, C.c_int32] + [_P] * 4 + [C.c_int32, _P, C.c_int32, _P, _P, _P]),
     ("rsys_step_mark", C.c_int32, [_P]),
     ("rsys_step_marks_get", C.c_int32, [_P, _P, C.c_int32, C.POINTER(C.c_int32)]),
     ("rsys_op_timing", C.c_int32, [_P, C.c_int32]),

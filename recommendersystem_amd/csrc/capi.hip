@@ -1271,6 +1271,186 @@ int32_t rsys_op_dropout(int32_t dtype, const void* src, void* dst, int64_t n, fl
   return RSYS_OK;
 }
 
+// ---------------------------------------------------------------- the sharded-table kernels on caller-provided buffers (shard.hip)
+// Each stage calls the launch routine the model path calls, unchanged, on the null stream.  No collective and no GEMM: the caller stands
+// in for both.  Index arrays that address caller buffers are copied back once and checked before anything is launched.
+namespace {
+int hook_ints(const int32_t* dev, long long n, std::vector<int>& out) {
+  out.resize((size_t)std::max(n, 0LL));
+  if (n > 0) HIP_CHECK(hipMemcpy(out.data(), dev, (size_t)n * 4, hipMemcpyDeviceToHost));
+  return RSYS_OK;
+}
+// a launch of a launcher with an ordered branch: in deterministic mode it must have counted itself in g_det.part_used
+struct DetTook {
+  const HookDet& det; int before;
+  explicit DetTook(const HookDet& d) : det(d), before(g_det.part_used) {}
+  int check(const char* who) const {
+    if (!det.on || (g_det.part_used > before && g_det.part_short == 0)) return RSYS_OK;
+    set_error(std::string(who) + ": the ordered (deterministic) branch did not run");
+    return RSYS_ERR_STATE;
+  }
+};
+}  // namespace
+
+int32_t rsys_op_vp_ce(int32_t dtype, int32_t stages, int32_t deterministic, const int32_t* idx, const float* label, const float* weight,
+                      const int32_t* position, const float* stats, const int32_t* npos, float task_w, int32_t KB, int32_t KBmax, float* own,
+                      const void* EwAll, const float* metaAll, int32_t W, int32_t D, void* EwC, float* metaC, int32_t* nlive, int32_t* pre,
+                      void* logits, int64_t ldl, int32_t Vloc, int32_t col0, float* lmax, const float* gmax, float* sums, int32_t cap,
+                      int32_t rank, float* loss, int32_t rows, int32_t rows_finish) {
+  switches_parse();
+  ARG_CHECK(dtype == RSYS_DTYPE_BF16 || dtype == RSYS_DTYPE_FP32, "rsys_op_vp_ce: dtype fp32 or bf16");
+  ARG_CHECK(stages > 0 && stages < 32, "rsys_op_vp_ce: stages is a mask of 1, 2, 4, 8, 16");
+  const bool bf = dtype == RSYS_DTYPE_BF16;
+  const int E = bf ? 8 : 4;
+  if (stages & 1) ARG_CHECK(idx && label && weight && position && stats && npos && own && KB >= 0 && KB <= KBmax && KBmax >= 1, "rsys_op_vp_ce: meta arguments");
+  if (stages & 2) ARG_CHECK(EwAll && metaAll && EwC && metaC && nlive && pre && W >= 1 && W <= 47 && KBmax >= 1 && D >= E && D % E == 0, "rsys_op_vp_ce: compact arguments");
+  if (stages & (4 | 16)) ARG_CHECK(cap >= 1 && metaC && nlive && sums && Vloc >= 0 && ldl >= 0 && ldl % 8 == 0 && Vloc <= ldl, "rsys_op_vp_ce: cap >= 1, Vloc <= ldl, ldl a multiple of 8");
+  if (stages & 4) ARG_CHECK(lmax && rows >= 0 && rows <= cap && (Vloc == 0 || logits), "rsys_op_vp_ce: stats arguments (rows <= cap)");
+  if (stages & 8) ARG_CHECK(lmax && gmax && sums && rows >= 0, "rsys_op_vp_ce: rebase arguments");
+  if (stages & 16) ARG_CHECK(gmax && pre && loss && rank >= 0 && rank < 47 && rows_finish >= 0 && rows_finish <= cap && (ldl == 0 || logits), "rsys_op_vp_ce: finish arguments (rows_finish <= cap)");
+  HookDet det(deterministic != 0 && (stages & 16) && rows_finish > 0);
+  RC(det.alloc(rows_finish, ceil32(rows_finish)));
+  if (stages & 1) RC(launch_vp_meta(idx, label, weight, position, stats, npos, task_w, KB, KBmax, own, nullptr));
+  if (stages & 2) RC(bf ? launch_vp_compact<bf16>((const bf16*)EwAll, metaAll, W, KBmax, D, (bf16*)EwC, metaC, nlive, pre, nullptr)
+                        : launch_vp_compact<float>((const float*)EwAll, metaAll, W, KBmax, D, (float*)EwC, metaC, nlive, pre, nullptr));
+  if ((stages & 4) && rows > 0) RC(bf ? launch_vp_stats<bf16>((const bf16*)logits, ldl, Vloc, col0, metaC, nlive, lmax, sums, cap, rows, nullptr)
+                                      : launch_vp_stats<float>((const float*)logits, ldl, Vloc, col0, metaC, nlive, lmax, sums, cap, rows, nullptr));
+  if ((stages & 8) && rows > 0) RC(launch_vp_rebase(lmax, gmax, sums, rows, nullptr));
+  if ((stages & 16) && rows_finish > 0) {
+    DetTook took(det);
+    RC(bf ? launch_vp_finish<bf16>((bf16*)logits, ldl, Vloc, col0, metaC, gmax, sums, cap, nlive, pre, rank, loss, rows_finish, nullptr)
+          : launch_vp_finish<float>((float*)logits, ldl, Vloc, col0, metaC, gmax, sums, cap, nlive, pre, rank, loss, rows_finish, nullptr));
+    RC(took.check("rsys_op_vp_ce"));
+  }
+  HIP_CHECK(hipDeviceSynchronize());
+  return RSYS_OK;
+}
+
+int32_t rsys_op_ss(int32_t dtype, int32_t stages, int32_t deterministic, int32_t len, int32_t n_s, int32_t n_tot, int32_t col0, uint64_t seed,
+                   int64_t stream, int32_t* cols, int32_t* bitmap, int32_t* tlist, int32_t* tcount, const float* metaC, const int32_t* nlive,
+                   const int32_t* pre, int32_t rank, int32_t cap_rows, int32_t rows, int32_t rows_finish, const void* EwC, const void* Floc,
+                   int32_t D, void* logits, int64_t ldl, float* lmax, float* lsum, float* tl, float* gmax, float* loss, float* dt,
+                   float* gE_loc, float* dEwC, const int32_t* ridx, int32_t rbase, int64_t rld, int32_t rn, int32_t rtable_rows,
+                   const void* gsrc, void* gdst, const float* asrc, float* adst) {
+  switches_parse();
+  ARG_CHECK(dtype == RSYS_DTYPE_BF16 || dtype == RSYS_DTYPE_FP32, "rsys_op_ss: dtype fp32 or bf16");
+  ARG_CHECK(stages > 0 && stages < 2048, "rsys_op_ss: stages is a mask of 1 .. 1024");
+  const bool bf = dtype == RSYS_DTYPE_BF16;
+  const int E = bf ? 8 : 4;
+  ARG_CHECK(len >= 0 && n_s >= 0 && n_tot >= n_s, "rsys_op_ss: len >= 0, 0 <= n_s <= n_tot");
+  if (stages & 1) ARG_CHECK(cols && stream >= 0 && stream <= 0xFFFFFFFFLL, "rsys_op_ss: sample arguments");
+  if (stages & 2) ARG_CHECK(metaC && nlive && bitmap && tlist && tcount && cap_rows >= 1 && len >= 1, "rsys_op_ss: targets arguments");
+  if (stages & 4) ARG_CHECK(cols && bitmap && n_s >= 1, "rsys_op_ss: drop_hits arguments");
+  if (stages & (8 | 512)) ARG_CHECK(ridx && rn >= 1 && rtable_rows >= 1 && D >= 4 && rld >= D, "rsys_op_ss: plain row copy arguments");
+  if (stages & 8) ARG_CHECK(gsrc && gdst && D % E == 0 && rld % E == 0, "rsys_op_ss: gather_rows_plain arguments");
+  if (stages & 512) ARG_CHECK(asrc && adst && D % 4 == 0 && rld % 4 == 0, "rsys_op_ss: add_rows_plain arguments");
+  if (stages & (16 | 32 | 64 | 128 | 256 | 1024)) ARG_CHECK(rows >= 0, "rsys_op_ss: rows");
+  if (stages & (16 | 1024)) ARG_CHECK(EwC && Floc && metaC && nlive && D >= 1 && len >= 1, "rsys_op_ss: target row arguments");
+  if (stages & 16) ARG_CHECK(tl, "rsys_op_ss: target_logit arguments");
+  if (stages & (32 | 256)) ARG_CHECK(metaC && nlive && (n_tot == 0 || (logits && cols)) && ldl >= n_tot && len >= n_s, "rsys_op_ss: logits arguments (ldl >= n_tot)");
+  if (stages & 32) ARG_CHECK(lmax && lsum, "rsys_op_ss: stats arguments");
+  if (stages & 64) ARG_CHECK(lmax && tl && gmax, "rsys_op_ss: max_with_target arguments");
+  if (stages & 128) ARG_CHECK(lmax && gmax && lsum, "rsys_op_ss: rebase arguments");
+  if (stages & 256) ARG_CHECK(logits && ldl >= 1 && gmax && lsum && tl && pre && loss && dt && rank >= 0 && rank < 47 && rows_finish >= 0, "rsys_op_ss: finish arguments");
+  if (stages & 1024) ARG_CHECK(dt && gE_loc && dEwC, "rsys_op_ss: target_grad arguments");
+  std::vector<int> h;
+  if ((stages & 4) && !(stages & 1)) {   // drop_hits reads the bitmap at cols[j]
+    RC(hook_ints(cols, n_s, h));
+    for (int c : h) ARG_CHECK(c >= 0 && c < len, "rsys_op_ss: drop_hits takes columns in [0, len)");
+  }
+  if (stages & (8 | 512)) {
+    RC(hook_ints(ridx, rn, h));
+    for (int c : h) ARG_CHECK(c < 0 || ((long long)rbase + c >= 0 && (long long)rbase + c < rtable_rows), "rsys_op_ss: a row index outside the table");
+  }
+  const bool det_stage = ((stages & 256) && rows_finish > 0) || ((stages & 1024) && rows > 0);
+  HookDet det(deterministic != 0 && det_stage);
+  RC(det.alloc(rows_finish, ceil32(rows_finish)));
+  const unsigned int st = (unsigned int)stream;
+  if (stages & 1) RC(launch_ss_sample(len, n_s, seed, st, cols, nullptr));
+  if (stages & 2) RC(launch_ss_targets(metaC, nlive, cap_rows, len, col0, (unsigned int*)bitmap, tlist, tcount, nullptr));
+  if (stages & 4) RC(launch_ss_drop_hits(cols, n_s, (const unsigned int*)bitmap, nullptr));
+  if (stages & 8) RC(bf ? launch_gather_rows_plain<bf16>((const bf16*)gsrc, rld, ridx, rbase, (bf16*)gdst, rn, D, nullptr)
+                        : launch_gather_rows_plain<float>((const float*)gsrc, rld, ridx, rbase, (float*)gdst, rn, D, nullptr));
+  if ((stages & 16) && rows > 0) RC(bf ? launch_ss_target_logit<bf16>((const bf16*)EwC, (const bf16*)Floc, D, len, col0, metaC, nlive, tl, rows, nullptr)
+                                       : launch_ss_target_logit<float>((const float*)EwC, (const float*)Floc, D, len, col0, metaC, nlive, tl, rows, nullptr));
+  if ((stages & 32) && rows > 0) RC(bf ? launch_ss_stats<bf16>((const bf16*)logits, ldl, n_s, n_tot, len, col0, cols, metaC, nlive, lmax, lsum, rows, nullptr)
+                                       : launch_ss_stats<float>((const float*)logits, ldl, n_s, n_tot, len, col0, cols, metaC, nlive, lmax, lsum, rows, nullptr));
+  if ((stages & 64) && rows > 0) RC(launch_ss_max_with_target(lmax, tl, gmax, rows, nullptr));
+  if ((stages & 128) && rows > 0) RC(launch_ss_rebase(lmax, gmax, lsum, rows, nullptr));
+  if ((stages & 256) && rows_finish > 0) {
+    DetTook took(det);
+    RC(bf ? launch_ss_finish<bf16>((bf16*)logits, ldl, n_s, n_tot, len, col0, cols, metaC, gmax, lsum, tl, nlive, pre, rank, loss, dt, rows_finish, nullptr)
+          : launch_ss_finish<float>((float*)logits, ldl, n_s, n_tot, len, col0, cols, metaC, gmax, lsum, tl, nlive, pre, rank, loss, dt, rows_finish, nullptr));
+    RC(took.check("rsys_op_ss (finish)"));
+  }
+  if (stages & 512) RC(launch_add_rows_plain(asrc, ridx, rbase, adst, rld, rn, D, nullptr));
+  if ((stages & 1024) && rows > 0) {
+    DetTook took(det);
+    RC(bf ? launch_ss_target_grad<bf16>((const bf16*)EwC, (const bf16*)Floc, D, len, col0, metaC, dt, nlive, gE_loc, dEwC, rows, nullptr)
+          : launch_ss_target_grad<float>((const float*)EwC, (const float*)Floc, D, len, col0, metaC, dt, nlive, gE_loc, dEwC, rows, nullptr));
+    RC(took.check("rsys_op_ss (target_grad)"));
+  }
+  HIP_CHECK(hipDeviceSynchronize());
+  return RSYS_OK;
+}
+
+int32_t rsys_op_shard_rows(int32_t stages, const int32_t* skey, const int32_t* sidx, int32_t N, int32_t V, int32_t* slot, int32_t* uniq,
+                           int32_t* tok2u, int32_t* plan, const int32_t* bound, int32_t nb, int32_t* off, float* table, int64_t ld,
+                           int32_t table_rows, const int32_t* ids, int32_t sub, float* packed, int32_t n, int32_t D, const int32_t* count,
+                           const int32_t* m_matchedid, const int32_t* userid, const int32_t* m_tmid, int32_t Ntok, const float* Frem,
+                           int32_t frem_rows, float* x0, int32_t* uid_t, int32_t* tm_t) {
+  ARG_CHECK(stages > 0 && stages < 64, "rsys_op_shard_rows: stages is a mask of 1 .. 32");
+  const int row_stages = stages & (4 | 8 | 16);
+  ARG_CHECK((row_stages & (row_stages - 1)) == 0, "rsys_op_shard_rows: one of the three rows-by-id stages per call");
+  std::vector<int> h, h2;
+  if (stages & 1) {
+    ARG_CHECK(skey && sidx && slot && uniq && tok2u && plan && N >= 1 && N <= (1 << 20) && V >= 0, "rsys_op_shard_rows: plan_unique arguments");
+    RC(hook_ints(skey, N, h)); RC(hook_ints(sidx, N, h2));
+    for (int p = 0; p < N; ++p) {
+      ARG_CHECK(h[p] >= 0 && h[p] <= V && (p == 0 || h[p - 1] <= h[p]), "rsys_op_shard_rows: skey ascending in [0, V]");
+      ARG_CHECK(h2[p] >= 0 && h2[p] < N, "rsys_op_shard_rows: sidx in [0, N)");
+    }
+  }
+  if (stages & 2) {
+    ARG_CHECK(uniq && plan && bound && off && nb >= 2 && nb <= 64, "rsys_op_shard_rows: plan_offsets arguments");
+    if (!(stages & 1)) { RC(hook_ints(plan, 2, h)); ARG_CHECK(h[0] >= 0 && h[0] <= (1 << 20) + 1, "rsys_op_shard_rows: plan[0] = the number of unique slots"); }
+  }
+  if (row_stages) {
+    ARG_CHECK(table && ids && packed && n >= 0 && D >= 4 && D % 4 == 0 && ld >= D && ld % 4 == 0 && table_rows >= 1, "rsys_op_shard_rows: rows-by-id arguments");
+    long long live = n, lo = sub;
+    if (row_stages == 16) {
+      ARG_CHECK(count, "rsys_op_shard_rows: the counted form takes a device count");
+      RC(hook_ints(count, 1, h));
+      ARG_CHECK(h[0] >= 0, "rsys_op_shard_rows: *count >= 0");
+      live = std::min<long long>(n, h[0]); lo = 0;
+    }
+    RC(hook_ints(ids, live, h));
+    for (int id : h) ARG_CHECK(id >= lo && id - lo < table_rows, "rsys_op_shard_rows: an id outside the table");
+  }
+  if (stages & 32) {
+    ARG_CHECK(m_matchedid && userid && m_tmid && Frem && tok2u && plan && x0 && uid_t && tm_t && Ntok >= 1 && D >= 4 && D % 4 == 0 && frem_rows >= 1,
+              "rsys_op_shard_rows: gather_items_remote arguments");
+    if (!(stages & 1)) {
+      RC(hook_ints(tok2u, Ntok, h)); RC(hook_ints(plan, 2, h2));
+      for (int u : h) ARG_CHECK(u >= 0 && u < frem_rows, "rsys_op_shard_rows: tok2u outside the fetched rows");
+      ARG_CHECK(h2[1] >= 0 && h2[1] < frem_rows, "rsys_op_shard_rows: plan[1] outside the fetched rows");
+    } else
+      ARG_CHECK(Ntok == N && frem_rows >= N + 1, "rsys_op_shard_rows: with plan_unique, Ntok == N and frem_rows >= N + 1");
+  }
+  if (stages & 1) RC(launch_plan_unique(skey, sidx, N, V, slot, uniq, tok2u, plan, nullptr));
+  if (stages & 2) RC(launch_plan_offsets(uniq, plan, bound, nb, off, nullptr));
+  if (stages & 4) RC(launch_gather_rows_by_id(table, ld, ids, sub, packed, n, D, nullptr));
+  if (stages & 8) RC(launch_add_rows_by_id(packed, ids, sub, table, ld, n, D, nullptr));
+  if (stages & 16) RC(launch_add_rows_by_id_counted(packed, ids, count, table, ld, n, D, nullptr));
+  if (stages & 32) {
+    BatchDev b{};   // the kernel reads N, m_matchedid, userid and m_tmid
+    b.N = Ntok; b.m_matchedid = const_cast<int*>(m_matchedid); b.userid = userid; b.m_tmid = const_cast<int*>(m_tmid);
+    RC(launch_gather_items_remote(b, Frem, tok2u, plan, D, x0, uid_t, tm_t, nullptr));
+  }
+  HIP_CHECK(hipDeviceSynchronize());
+  return RSYS_OK;
+}
+
 // step boundaries on the model's stream: rsys_step_mark records an event, rsys_step_marks_get returns the elapsed time
 // between consecutive marks (ms) and clears them -- the per-step time distribution without a host sync per step
 int32_t rsys_step_mark(rsys_model* h) {

@@ -301,7 +301,7 @@ int launch_vp_finish(T* logits, long long ldl, int Vloc, int col0, const float* 
                      const int* nlive, const int* pre, int rank, float* loss_out, int grid_rows, hipStream_t s) {
   float* part = g_det.part != nullptr && (long long)grid_rows <= g_det.cap ? g_det.part : nullptr;   // deterministic mode (kernels.hpp DetScratch)
   if (g_det.part != nullptr && part == nullptr) { set_error("vocabulary-parallel CE: deterministic scratch too small"); return RSYS_ERR_STATE; }
-  if (part != nullptr) HIP_CHECK(hipMemsetAsync(part, 0, (size_t)grid_rows * 4, s));   // (rows without a term write nothing)
+  if (part != nullptr) { ++g_det.part_used; HIP_CHECK(hipMemsetAsync(part, 0, (size_t)grid_rows * 4, s)); }   // (rows without a term write nothing)
   hipLaunchKernelGGL((vp_finish_kernel<T>), dim3(grid_rows), dim3(256), 0, s, logits, ldl, Vloc, col0, metaC, gmax, sums, cap, nlive, pre, rank, loss_out, part);
   HIP_CHECK(hipGetLastError());
   if (part != nullptr) return launch_reduce_parts(part, grid_rows, 1, 1, loss_out, s);
@@ -583,7 +583,7 @@ int launch_ss_finish(T* logits, long long ldl, int n_s, int n_tot, int len, int 
                      float* dt, int grid_rows, hipStream_t s) {
   float* part = g_det.part != nullptr && (long long)grid_rows <= g_det.cap ? g_det.part : nullptr;   // deterministic mode (kernels.hpp DetScratch)
   if (g_det.part != nullptr && part == nullptr) { set_error("sampled soft-max: deterministic scratch too small"); return RSYS_ERR_STATE; }
-  if (part != nullptr) HIP_CHECK(hipMemsetAsync(part, 0, (size_t)grid_rows * 4, s));   // (rows without a term write nothing)
+  if (part != nullptr) { ++g_det.part_used; HIP_CHECK(hipMemsetAsync(part, 0, (size_t)grid_rows * 4, s)); }   // (rows without a term write nothing)
   hipLaunchKernelGGL((ss_finish_kernel<T>), dim3(grid_rows), dim3(256), 0, s, logits, ldl, n_s, n_tot, len, col0, cols, metaC, gmax, sneg, tl,
                      nlive, pre, rank, loss_out, dt, part);
   HIP_CHECK(hipGetLastError());
@@ -595,6 +595,7 @@ int launch_ss_target_grad(const T* EwC, const T* Floc, int D, int len, int col0,
                           float* gE_loc, float* dEwC, int grid_rows, hipStream_t s) {
   if (g_det.part != nullptr) {   // deterministic mode
     ARG_CHECK(D <= 64 * 32, "sampled soft-max, deterministic mode: embed_dim <= 2048");
+    ++g_det.part_used;
     if (D <= 64 * 8) hipLaunchKernelGGL((ss_target_grad_ordered_kernel<T, 8>), dim3(div_up(grid_rows, 4)), dim3(256), 0, s, EwC, Floc, D, len, col0, metaC, dt, nlive, gE_loc, dEwC);
     else hipLaunchKernelGGL((ss_target_grad_ordered_kernel<T, 32>), dim3(div_up(grid_rows, 4)), dim3(256), 0, s, EwC, Floc, D, len, col0, metaC, dt, nlive, gE_loc, dEwC);
   } else
