@@ -584,6 +584,20 @@ int32_t rsys_infer_select_tiles(rsys_model* m, int32_t task, const int32_t* tile
 int32_t rsys_adapter_train_enable(rsys_model* m, float dropout);
 int32_t rsys_adapter_forward_backward(rsys_model* m, int32_t evaluate, const int32_t* row_slot, const int32_t* row_task, float grad_scale,
                                       uint64_t seed, uint64_t step);
+/* rsys_adapter_forward_backward on packed rows: several users share a batch row, each in a SEGMENT -- the live prefix of
+ * its finetune row -- that starts at an interaction column that is a multiple of 32 (64 tokens) and lies inside one row, so no 64-token
+ * tile holds two users.  seg int32 [n_seg][5] = (row, first_column, columns, slot, task); slot and task as above, -1 / -1 = the base model,
+ * no loss.  Semantics are those of rsys_adapter_forward_backward with "row" read as "segment": the finetune mask rule uses the segment's
+ * metric, masked weights of every other task are zero, a task belongs to at most one slot.  A slot's gradient is alpha times the sum over
+ * its segments IN DESCRIPTOR ORDER of per-segment partials, each summed over the segment's tokens in ascending order: bitwise
+ * reproducible, independent of other slots' segments, and the unpacked call's order when descriptors follow the rows' order.  The last
+ * layer runs dense in this call (no compact top).  Dropout is keyed on the element index in the packed batch.  Rows are full-length rows
+ * (rsys_batch_upload); a trimmed batch is RSYS_ERR_STATE.  THE CALLER GUARANTEES THE RESIDENT COLUMNS: inside a segment one non-zero
+ * userid, distinct within its row, rope_input_pos relative to the segment; zeros in every column no segment covers.
+ * RSYS_ERR_ARG, nothing written or enqueued: everything rsys_adapter_forward_backward refuses; seg NULL; n_seg < 1 or > rows * ceil(S / 32);
+ * first_column % 32 != 0; a segment outside its row (columns < 1 or first_column + columns > S); two segments sharing a tile. */
+int32_t rsys_adapter_forward_backward_packed(rsys_model* m, int32_t evaluate, const int32_t* seg, int32_t n_seg, float grad_scale,
+                                             uint64_t seed, uint64_t step);
 int32_t rsys_adapter_grad_get(rsys_model* m, int32_t slot, const char* name, float* out, int64_t n);
 int32_t rsys_adapter_zero_grad(rsys_model* m);
 int32_t rsys_adapter_adamw_step(rsys_model* m, float lr0, float beta1, float beta2, float eps, float wd, const float* per_slot,

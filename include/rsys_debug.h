@@ -276,6 +276,18 @@ int32_t rsys_op_adapter_bank(int32_t dtype, int32_t stages, int32_t train, int32
 int32_t rsys_op_adapter_bank_tiles(int32_t dtype, int32_t stages, int32_t rows, int32_t Ttok, int32_t D, int32_t H, int32_t KV, int32_t hd, int32_t L,
                                    int32_t layer, const int32_t* tile_slot, const void* bankA, const void* bankB, const void* xn, void* La, void* qkv,
                                    const float* rope_cos, const float* rope_sin, const int32_t* rope_pos, int32_t rope_rows);
+/* rsys_op_adapter_bank in the forms of packed finetune rows: segs int32 [n_seg][5] (device) = (row, first interaction
+ * column, columns, slot, task) in place of row_slot, on rows of Ttok / 2 interactions.  Stages 1 (train != 0: under the dropout mask), 2, 4
+ * and 32 run per 64-token tile with the slot of the segment that owns the tile; 8 and 16 write one partial per segment over the segment's
+ * whole tiles, partA fp32 [n_seg][16][D], partB fp32 [n_seg][Nq + Nv][8]; 64 adds, per slot, its segments' partials in descriptor order.
+ * A tile no segment owns and a segment with slot -1 are neither read nor written.  The table is copied back once and checked as
+ * rsys_adapter_forward_backward_packed checks it (RSYS_ERR_ARG before anything is launched); otherwise buffers and checks of
+ * rsys_op_adapter_bank. */
+int32_t rsys_op_adapter_bank_segments(int32_t dtype, int32_t stages, int32_t train, int32_t rows, int32_t Ttok, int32_t D, int32_t H, int32_t KV, int32_t hd,
+                                      int32_t L, int32_t layer, float p, uint64_t seed, int64_t stream, const int32_t* segs, int32_t n_seg, const void* bankA,
+                                      const void* bankB, const void* xn, void* La, void* qkv, const void* dqkv, void* dLa, void* dxn, float* partA,
+                                      float* partB, float* gA, float* gB, const float* rope_cos, const float* rope_sin, const int32_t* rope_pos,
+                                      int32_t rope_rows);
 int32_t rsys_op_adapter_bank_adamw(int32_t dtype, float* A32, float* B32, float* gA, float* gB, float* mA, float* vA, float* mB, float* vB, void* A,
                                    void* B, int64_t nA, int64_t nB, const float* per_slot, float b1, float b2, float eps, float wd, float* norms);
 int32_t rsys_op_dropout(int32_t dtype, const void* src, void* dst, int64_t n, float p, uint64_t seed, int64_t stream, int32_t accumulate);

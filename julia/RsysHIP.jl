@@ -174,6 +174,14 @@ function adapter_forward_backward(m::Model, evaluate::Bool, row_slot::Vector{Int
                                                (Ptr{Cvoid}, Int32, Ptr{Int32}, Ptr{Int32}, Float32, UInt64, UInt64),
                                                m.h, evaluate ? 1 : 0, row_slot, row_task, grad_scale, seed, step))
 end
+# the same on packed rows (rsys.h: rsys_adapter_forward_backward_packed): segments (5, n_seg) column-major = [n_seg][5] =
+# (row, first_column, columns, slot, task), all 0-based as in the C ABI
+function adapter_forward_backward_packed(m::Model, evaluate::Bool, segments::Matrix{Int32}, grad_scale::Real, seed::Integer, step::Integer)
+    size(segments, 1) == 5 || throw(ArgumentError("segments is (5, n_seg)"))
+    GC.@preserve segments check(ccall((:rsys_adapter_forward_backward_packed, LIB), Int32,
+                                      (Ptr{Cvoid}, Int32, Ptr{Int32}, Int32, Float32, UInt64, UInt64),
+                                      m.h, evaluate ? 1 : 0, segments, size(segments, 2), grad_scale, seed, step))
+end
 function adapter_grad!(m::Model, slot::Integer, name::String, out::Array{Float32})
     GC.@preserve out check(ccall((:rsys_adapter_grad_get, LIB), Int32, (Ptr{Cvoid}, Int32, Cstring, Ptr{Float32}, Int64), m.h, slot, name, out, length(out)))
     out

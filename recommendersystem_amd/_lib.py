@@ -152,6 +152,7 @@ _SIGS = [
     ("rsys_serving_trim_get", C.c_int32, [_P, C.POINTER(C.c_int32)]),
     ("rsys_adapter_train_enable", C.c_int32, [_P, C.c_float]),
     ("rsys_adapter_forward_backward", C.c_int32, [_P, C.c_int32, _P, _P, C.c_float, C.c_uint64, C.c_uint64]),
+    ("rsys_adapter_forward_backward_packed", C.c_int32, [_P, C.c_int32, _P, C.c_int32, C.c_float, C.c_uint64, C.c_uint64]),
     ("rsys_adapter_grad_get", C.c_int32, [_P, C.c_int32, C.c_char_p, _P, C.c_int64]),
     ("rsys_adapter_zero_grad", C.c_int32, [_P]),
     ("rsys_adapter_adamw_step", C.c_int32, [_P, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, _P, C.c_int32, _P]),
@@ -231,6 +232,7 @@ _SIGS = [
                                        + [C.c_int32, C.c_float, C.c_float, C.c_int32, C.c_int64, C.c_int64, C.c_int32, _P]),
     ("rsys_op_adapter_bank", C.c_int32, [C.c_int32] * 11 + [C.c_float, C.c_uint64, C.c_int64] + [_P] * 16 + [C.c_int32]),
     ("rsys_op_adapter_bank_tiles", C.c_int32, [C.c_int32] * 10 + [_P] * 9 + [C.c_int32]),
+    ("rsys_op_adapter_bank_segments", C.c_int32, [C.c_int32] * 11 + [C.c_float, C.c_uint64, C.c_int64, _P, C.c_int32] + [_P] * 15 + [C.c_int32]),
     ("rsys_op_adapter_bank_adamw", C.c_int32, [C.c_int32] + [_P] * 10 + [C.c_int64, C.c_int64, _P] + [C.c_float] * 4 + [_P]),
     ("rsys_op_dropout", C.c_int32, [C.c_int32, _P, _P, C.c_int64, C.c_float, C.c_uint64, C.c_int64, C.c_int32]),
     ("rsys_op_vp_ce", C.c_int32, [C.c_int32] * 3 + [_P] * 6 + [C.c_float, C.c_int32, C.c_int32, _P, _P, _P, C.c_int32, C.c_int32]

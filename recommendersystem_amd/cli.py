@@ -123,7 +123,8 @@ def finetune_all(args):
     runs = rtrain.make_adapter_runs([(s, s) for s, _ in tasks], config)
     history = rtrain.train_adapters(model, optimizer, runs, loaders, config, os.path.join(args.datadir, "finetune_all"), num_epochs,
                                     global_batch // local_batch, log=log,
-                                    base_blob={k: v for k, v in blob.items() if k.startswith("model/") and "lora_" not in k})
+                                    base_blob={k: v for k, v in blob.items() if k.startswith("model/") and "lora_" not in k},
+                                    pack=bool(getattr(args, "finetune_pack", False)))
     model.close()
     return history
 
@@ -137,6 +138,9 @@ def main(argv=None):
     ap.add_argument("--finetune_all", action="store_true",
                     help="with --finetune CKPT: train the four (medium, metric) adapters in one run through the adapter bank of one base "
                          "model (Finetune/run.jl:9-13 as one job) and write base.npz + four {m}.{metric}.lora.npz (DESIGN 4y)")
+    ap.add_argument("--finetune_pack", action="store_true",
+                    help="with --finetune_all: several users per row in every joint pass, each in a segment of whole 64-token tiles "
+                         "(train.pack_adapter_rows, DESIGN 4zc); same files, counters and schedules")
     ap.add_argument("--mini", action="store_true")
     ap.add_argument("--prod", action="store_true")
     ap.add_argument("--model", default="prod", help="prod (transformer.py:536-558) or a workload.make_config name")

@@ -5,7 +5,8 @@
 //   stage B   q[t, :]     += rope(2 * La[t, 0:8] . B_q[slot(t)]^T),  v[t, :] += 2 * La[t, 8:16] . B_v[slot(t)]^T   (k is not touched)
 // A workgroup works on tokens of ONE batch row (a row is 2S consecutive tokens), so the slot is workgroup-uniform; rows with slot -1
 // return before their first load.  Packed serving rows (several users per row, segments of whole 64-token tiles) name a slot
-// per TILE instead: the two forward kernels have a per-tile form on the same body.  Rounding points are those of the finetune model's two LoRA GEMMs (model_forward.hip): operands
+// per TILE instead: the two forward kernels have a per-tile form on the same body; packed finetune rows add the per-tile
+// forms of the training stages and per-SEGMENT partial gradients, summed per slot in descriptor order.  Rounding points are those of the finetune model's two LoRA GEMMs (model_forward.hip): operands
 // and La in the compute type, fp32 accumulation, alpha = 2 on the fp32 sum, the q part rotated and added to the rotated projection.
 // No atomics: every sum has a fixed order.
 #include "model_internal.hpp"
@@ -33,12 +34,21 @@ struct AdapterBank {
   float *partA = nullptr, *partB = nullptr;   // per-row partial gradients of that layer: [rows_max][16][D], [rows_max][Nq + Nv][8]
   int* d_task = nullptr;                  // [rows_max] task per batch row of the current call
   float* d_norms = nullptr;               // [RSYS_ADAPTER_SLOTS] the optimizer step's per-slot gradient norms
+  // ---- training on packed rows (allocated by the first rsys_adapter_forward_backward_packed)
+  int* d_tile_task = nullptr;             // [rows_max][ceil(Ta / 64)] task per tile (the slot map is d_tiles)
+  int* d_segs = nullptr;                  // [rows_max * ceil(Ta / 64)][5] the call's segment table
+  int n_seg = 0;                          // its length in the current call
+  std::vector<int32_t> h_pack;            // host image of (tile slots | tile tasks | segments): rewritten once the stream has passed the last copy
+  float *segA = nullptr, *segB = nullptr; // per-segment partial gradients [seg_cap][16][D], [seg_cap][Nq + Nv][8]: grown to the call's segment count
+  int seg_cap = 0;
 };
 
 struct BankLaunch {                       // the plain arguments of one layer's bank launches
   int rows, Ttok, D, H, KV, hd, L, layer;
   const int* row_slot;                    // [rows] device
-  const int* tile_slot = nullptr;         // [rows][ceil(Ttok / 64)] device: the forward stages read it instead of row_slot when set
+  const int* tile_slot = nullptr;         // [rows][ceil(Ttok / 64)] device: the stages read it instead of row_slot when set
+  const int* segs = nullptr;              // [n_seg][5] device (row, first column, columns, slot, task): with tile_slot, the backward's partials and sums
+  int n_seg = 0;
   const void *bankA, *bankB;              // compute type: [slots][L][16][D], [slots][L][Nq + Nv][8]
   float p; unsigned long long seed; unsigned int stream;   // dropout key (a_train, da, dx)
   hipStream_t s;
@@ -256,14 +266,12 @@ __device__ __forceinline__ void bank_frag_mul(bf16x8& x, int k, float f) { x[k] 
 __device__ __forceinline__ void bank_frag_mul(float4& x, int k, float f) { ((float*)&x)[k] *= f; }
 
 // stage A of a training pass: adapter_bank_a_kernel with the LoRA input under the dropout mask (p == 0: the same sums) and the layer's own La
+// (the body the row-slot and the per-tile form share: `slot` >= 0 is the workgroup's)
 template <typename T>
-__global__ __launch_bounds__(256) void adapter_bank_a_train_kernel(const T* __restrict__ xn, const T* __restrict__ bankA, const int* __restrict__ row_slot,
-                                                                   int layer, int L, int D, int Ttok, T* __restrict__ La, float p,
-                                                                   unsigned long long seed, unsigned int stream) {
+__device__ __forceinline__ void bank_a_train_body(const T* __restrict__ xn, const T* __restrict__ bankA, int row, int slot, int layer, int L, int D, int Ttok,
+                                                  T* __restrict__ La, float p, unsigned long long seed, unsigned int stream) {
   using MM = BankMma<T>;
   __shared__ float red[4][4][64];
-  const int row = blockIdx.y, slot = row_slot[row];
-  if (slot < 0) return;
   const BankDrop dr(p, seed, stream);
   const int t0 = blockIdx.x * BANK_A_TOK;
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -288,18 +296,33 @@ __global__ __launch_bounds__(256) void adapter_bank_a_train_kernel(const T* __re
   const int tk = t0 + 4 * kq + w;
   if (tk < Ttok) La[((long long)row * Ttok + tk) * 16 + r] = from_f32<T>(sum);
 }
+template <typename T>
+__global__ __launch_bounds__(256) void adapter_bank_a_train_kernel(const T* __restrict__ xn, const T* __restrict__ bankA, const int* __restrict__ row_slot,
+                                                                   int layer, int L, int D, int Ttok, T* __restrict__ La, float p,
+                                                                   unsigned long long seed, unsigned int stream) {
+  const int row = blockIdx.y, slot = row_slot[row];
+  if (slot < 0) return;
+  bank_a_train_body<T>(xn, bankA, row, slot, layer, L, D, Ttok, La, p, seed, stream);
+}
+// Packed finetune rows: the slot of the workgroup's 64-token tile, as adapter_bank_a_tiles_kernel takes it
+template <typename T>
+__global__ __launch_bounds__(256) void adapter_bank_a_train_tiles_kernel(const T* __restrict__ xn, const T* __restrict__ bankA, const int* __restrict__ tile_slot,
+                                                                         int nt, int layer, int L, int D, int Ttok, T* __restrict__ La, float p,
+                                                                         unsigned long long seed, unsigned int stream) {
+  const int row = blockIdx.y, slot = tile_slot[row * nt + ((blockIdx.x * BANK_A_TOK) >> 6)];
+  if (slot < 0) return;
+  bank_a_train_body<T>(xn, bankA, row, slot, layer, L, D, Ttok, La, p, seed, stream);
+}
 
 // dLa[t, 0:8] = 2 dq_t . B_q[slot], dLa[t, 8:16] = 2 dv_t . B_v[slot] (the un-rotated dqkv the finetune model's gemm_lora_dla reads; rounded
 // to the compute type as that GEMM stores it).  grid (ceil(2S / 16), rows), 256 threads: stage A's tile -- tokens on the rows, the 16
 // LoRA columns on the columns -- with K = the q columns, then the v columns; B is [column][8], so its fragment is gathered 8 apart and
 // is zero on the half of the LoRA columns the segment does not feed.  The four waves split the K steps, partial tiles added in wave order.
 template <typename T>
-__global__ __launch_bounds__(256) void adapter_bank_dla_kernel(const T* __restrict__ dqkv, const T* __restrict__ bankB, const int* __restrict__ row_slot,
-                                                               int layer, int L, int Nq, int Nk, int Nv, int Ttok, T* __restrict__ dLa) {
+__device__ __forceinline__ void bank_dla_body(const T* __restrict__ dqkv, const T* __restrict__ bankB, int row, int slot, int layer, int L, int Nq, int Nk, int Nv,
+                                              int Ttok, T* __restrict__ dLa) {
   using MM = BankMma<T>;
   __shared__ float red[4][4][64];
-  const int row = blockIdx.y, slot = row_slot[row];
-  if (slot < 0) return;
   const int t0 = blockIdx.x * BANK_A_TOK;
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int r = lane & 15, kq = lane >> 4;
@@ -326,15 +349,28 @@ __global__ __launch_bounds__(256) void adapter_bank_dla_kernel(const T* __restri
   if (tk < Ttok) dLa[((long long)row * Ttok + tk) * 16 + r] = from_f32<T>(2.f * sum);   // lora_scaling = 2 on the fp32 sum
 }
 
+template <typename T>
+__global__ __launch_bounds__(256) void adapter_bank_dla_kernel(const T* __restrict__ dqkv, const T* __restrict__ bankB, const int* __restrict__ row_slot,
+                                                               int layer, int L, int Nq, int Nk, int Nv, int Ttok, T* __restrict__ dLa) {
+  const int row = blockIdx.y, slot = row_slot[row];
+  if (slot < 0) return;
+  bank_dla_body<T>(dqkv, bankB, row, slot, layer, L, Nq, Nk, Nv, Ttok, dLa);
+}
+// the per-tile form (16 | 64: the workgroup's 16 tokens lie inside one tile)
+template <typename T>
+__global__ __launch_bounds__(256) void adapter_bank_dla_tiles_kernel(const T* __restrict__ dqkv, const T* __restrict__ bankB, const int* __restrict__ tile_slot,
+                                                                     int nt, int layer, int L, int Nq, int Nk, int Nv, int Ttok, T* __restrict__ dLa) {
+  const int row = blockIdx.y, slot = tile_slot[row * nt + ((blockIdx.x * BANK_A_TOK) >> 6)];
+  if (slot < 0) return;
+  bank_dla_body<T>(dqkv, bankB, row, slot, layer, L, Nq, Nk, Nv, Ttok, dLa);
+}
+
 // dxn[t, :] += drop'(dLa[t, :] . [A_q; A_v][slot]) (K = 16: no MFMA).  grid (2S / 8, rows), 256 threads, an item = 8 columns of one
 // token.  Rounding as the finetune model's gemm_lora_dx: without dropout the fp32 sum is added to dxn; with it the sum is rounded to the
 // compute type first (that model stores it), masked and scaled, then added.
 template <typename T>
-__global__ __launch_bounds__(256) void adapter_bank_dx_kernel(const T* __restrict__ dLa, const T* __restrict__ bankA, const int* __restrict__ row_slot,
-                                                              int layer, int L, int D, int Ttok, T* __restrict__ dxn, float p,
-                                                              unsigned long long seed, unsigned int stream) {
-  const int row = blockIdx.y, slot = row_slot[row];
-  if (slot < 0) return;
+__device__ __forceinline__ void bank_dx_body(const T* __restrict__ dLa, const T* __restrict__ bankA, int row, int slot, int layer, int L, int D, int Ttok,
+                                             T* __restrict__ dxn, float p, unsigned long long seed, unsigned int stream) {
   const BankDrop dr(p, seed, stream);
   const int t0 = blockIdx.x * BANK_B_TOK;
   const int ntok = min(BANK_B_TOK, Ttok - t0);
@@ -370,17 +406,33 @@ __global__ __launch_bounds__(256) void adapter_bank_dx_kernel(const T* __restric
   }
 }
 
+template <typename T>
+__global__ __launch_bounds__(256) void adapter_bank_dx_kernel(const T* __restrict__ dLa, const T* __restrict__ bankA, const int* __restrict__ row_slot,
+                                                              int layer, int L, int D, int Ttok, T* __restrict__ dxn, float p,
+                                                              unsigned long long seed, unsigned int stream) {
+  const int row = blockIdx.y, slot = row_slot[row];
+  if (slot < 0) return;
+  bank_dx_body<T>(dLa, bankA, row, slot, layer, L, D, Ttok, dxn, p, seed, stream);
+}
+// the per-tile form (8 | 64: the workgroup's 8 tokens lie inside one tile)
+template <typename T>
+__global__ __launch_bounds__(256) void adapter_bank_dx_tiles_kernel(const T* __restrict__ dLa, const T* __restrict__ bankA, const int* __restrict__ tile_slot,
+                                                                    int nt, int layer, int L, int D, int Ttok, T* __restrict__ dxn, float p,
+                                                                    unsigned long long seed, unsigned int stream) {
+  const int row = blockIdx.y, slot = tile_slot[row * nt + ((blockIdx.x * BANK_B_TOK) >> 6)];
+  if (slot < 0) return;
+  bank_dx_body<T>(dLa, bankA, row, slot, layer, L, D, Ttok, dxn, p, seed, stream);
+}
+
 // Per-row partial of dA: partA[row][j][d] = sum over the row's tokens t, ascending, of dLa[t][j] drop(xn)[t][d].  grid (ceil(D / 64), rows),
 // 256 threads: every wave owns 16 columns d and the whole contraction (K = 2S tokens), so a partial has one fixed order and no
 // cross-wave sum.  MFMA tile: the 16 LoRA rows j on the rows, d on the columns; both operands have the token as their OUTER index, so
 // the fragments are gathered (16 resp. D apart).
+// (the body of the row and the segment form: the contraction runs over tokens [kb, ke) of `row`, kb a multiple of 64, into dst[16][D])
 template <typename T>
-__global__ __launch_bounds__(256) void adapter_bank_da_kernel(const T* __restrict__ dLa, const T* __restrict__ xn, const int* __restrict__ row_slot,
-                                                              int D, int Ttok, float* __restrict__ partA, float p, unsigned long long seed,
-                                                              unsigned int stream) {
+__device__ __forceinline__ void bank_da_body(const T* __restrict__ dLa, const T* __restrict__ xn, int row, int kb, int ke, int D, int Ttok,
+                                             float* __restrict__ dst, float p, unsigned long long seed, unsigned int stream) {
   using MM = BankMma<T>;
-  const int row = blockIdx.y;
-  if (row_slot[row] < 0) return;
   const BankDrop dr(p, seed, stream);
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int d0 = (blockIdx.x * 4 + w) * 16;
@@ -388,9 +440,9 @@ __global__ __launch_bounds__(256) void adapter_bank_da_kernel(const T* __restric
   const int r = lane & 15, kq = lane >> 4;
   const long long tb = (long long)row * Ttok;
   f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-  for (int k0 = 0; k0 < Ttok; k0 += MM::KS) {
+  for (int k0 = kb; k0 < ke; k0 += MM::KS) {
     const int k = k0 + kq * MM::E;
-    const bool k_ok = k < Ttok;   // (2S % 8 == 0: a fragment's tokens are inside the row or all past it)
+    const bool k_ok = k < ke;   // (2S % 8 == 0: a fragment's tokens are inside the range or all past it)
     typename MM::Frag ga = MM::zero(), xb = MM::zero();
     if (k_ok) {
       ga = bank_gather(dLa + (tb + k) * 16 + r, 16);
@@ -402,20 +454,43 @@ __global__ __launch_bounds__(256) void adapter_bank_da_kernel(const T* __restric
     }
     acc = MM::mma(ga, xb, acc);
   }
-  float* dst = partA + (long long)row * 16 * D;
 #pragma unroll
   for (int i = 0; i < 4; ++i) dst[(long long)(4 * kq + i) * D + d0 + r] = acc[i];
+}
+template <typename T>
+__global__ __launch_bounds__(256) void adapter_bank_da_kernel(const T* __restrict__ dLa, const T* __restrict__ xn, const int* __restrict__ row_slot,
+                                                              int D, int Ttok, float* __restrict__ partA, float p, unsigned long long seed,
+                                                              unsigned int stream) {
+  const int row = blockIdx.y;
+  if (row_slot[row] < 0) return;
+  bank_da_body<T>(dLa, xn, row, 0, Ttok, D, Ttok, partA + (long long)row * 16 * D, p, seed, stream);
+}
+// Packed finetune rows: one partial per SEGMENT.  segs [n_seg][5] = (row, first column, columns, slot, task); the contraction
+// runs over the segment's whole 64-token tiles, tokens [2 c0, min(2S, 2 c0 + 64 ceil(columns / 32))), which nobody else owns.  grid
+// (ceil(D / 64), n_seg); a segment with slot -1 writes nothing.
+__device__ __forceinline__ bool bank_seg_range(const int* __restrict__ segs, int Ttok, int* row, int* kb, int* ke) {
+  const int* sg = segs + (long long)blockIdx.y * 5;
+  if (sg[3] < 0) return false;
+  *row = sg[0]; *kb = 2 * sg[1];
+  *ke = min(Ttok, *kb + 64 * ((sg[2] + 31) >> 5));
+  return true;
+}
+template <typename T>
+__global__ __launch_bounds__(256) void adapter_bank_da_seg_kernel(const T* __restrict__ dLa, const T* __restrict__ xn, const int* __restrict__ segs,
+                                                                  int D, int Ttok, float* __restrict__ partA, float p, unsigned long long seed,
+                                                                  unsigned int stream) {
+  int row, kb, ke;
+  if (!bank_seg_range(segs, Ttok, &row, &kb, &ke)) return;
+  bank_da_body<T>(dLa, xn, row, kb, ke, D, Ttok, partA + (long long)blockIdx.y * 16 * D, p, seed, stream);
 }
 
 // Per-row partial of dB: partB[row][c][j] = sum over the row's tokens, ascending, of dqv[t][c] La[t][j (q columns) | 8 + j (v columns)]
 // (the factor 2 is applied when the rows are added).  grid (ceil((Nq + Nv) / 64), rows), 256 threads; a wave owns 16 columns c of
 // [dq | dv] and the whole contraction; the tile's 16 columns are La's, of which a q (v) row keeps the first (last) 8.
 template <typename T>
-__global__ __launch_bounds__(256) void adapter_bank_db_kernel(const T* __restrict__ dqkv, const T* __restrict__ La, const int* __restrict__ row_slot,
-                                                              int Nq, int Nk, int Nv, int Ttok, float* __restrict__ partB) {
+__device__ __forceinline__ void bank_db_body(const T* __restrict__ dqkv, const T* __restrict__ La, int row, int kb, int ke, int Nq, int Nk, int Nv, int Ttok,
+                                             float* __restrict__ dst) {
   using MM = BankMma<T>;
-  const int row = blockIdx.y;
-  if (row_slot[row] < 0) return;
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int c0 = (blockIdx.x * 4 + w) * 16;
   if (c0 >= Nq + Nv) return;
@@ -426,14 +501,13 @@ __global__ __launch_bounds__(256) void adapter_bank_db_kernel(const T* __restric
   const bool ca_ok = ca < Nq + Nv;
   const int col = ca < Nq ? ca : ca + Nk;            // its column of dqkv
   f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-  for (int k0 = 0; k0 < Ttok; k0 += MM::KS) {
+  for (int k0 = kb; k0 < ke; k0 += MM::KS) {
     const int k = k0 + kq * MM::E;
-    const bool k_ok = k < Ttok;
+    const bool k_ok = k < ke;
     const typename MM::Frag ga = (k_ok && ca_ok) ? bank_gather(dqkv + (tb + k) * ld + col, ld) : MM::zero();
     const typename MM::Frag lb = k_ok ? bank_gather(La + (tb + k) * 16 + r, 16) : MM::zero();
     acc = MM::mma(ga, lb, acc);
   }
-  float* dst = partB + (long long)row * (Nq + Nv) * 8;
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     const int c = c0 + 4 * kq + i;
@@ -441,6 +515,21 @@ __global__ __launch_bounds__(256) void adapter_bank_db_kernel(const T* __restric
     const bool isq = c < Nq;
     if (isq ? r < 8 : r >= 8) dst[(long long)c * 8 + (r & 7)] = acc[i];
   }
+}
+template <typename T>
+__global__ __launch_bounds__(256) void adapter_bank_db_kernel(const T* __restrict__ dqkv, const T* __restrict__ La, const int* __restrict__ row_slot,
+                                                              int Nq, int Nk, int Nv, int Ttok, float* __restrict__ partB) {
+  const int row = blockIdx.y;
+  if (row_slot[row] < 0) return;
+  bank_db_body<T>(dqkv, La, row, 0, Ttok, Nq, Nk, Nv, Ttok, partB + (long long)row * (Nq + Nv) * 8);
+}
+// the segment form, grid (ceil((Nq + Nv) / 64), n_seg): adapter_bank_da_seg_kernel's token range
+template <typename T>
+__global__ __launch_bounds__(256) void adapter_bank_db_seg_kernel(const T* __restrict__ dqkv, const T* __restrict__ La, const int* __restrict__ segs,
+                                                                  int Nq, int Nk, int Nv, int Ttok, float* __restrict__ partB) {
+  int row, kb, ke;
+  if (!bank_seg_range(segs, Ttok, &row, &kb, &ke)) return;
+  bank_db_body<T>(dqkv, La, row, kb, ke, Nq, Nk, Nv, Ttok, partB + (long long)blockIdx.y * (Nq + Nv) * 8);
 }
 
 // g[slot][layer][e] += alpha * (sum of part[row][e] over the rows of `slot`, in row order): one thread per element, the fixed order that
@@ -453,6 +542,19 @@ __global__ __launch_bounds__(256) void adapter_bank_rows_reduce_kernel(const flo
     float acc = 0.f; bool any = false;
     for (int r = 0; r < rows; ++r)
       if (row_slot[r] == a) { acc += part[(long long)r * n + e]; any = true; }
+    if (any) g[(long long)a * slot_stride + e] += alpha * acc;
+  }
+}
+
+// the same over per-SEGMENT partials: per slot the sum over that slot's segments in descriptor order (segs [n_seg][5], slot at [3])
+__global__ __launch_bounds__(256) void adapter_bank_segs_reduce_kernel(const float* __restrict__ part, const int* __restrict__ segs, int n_seg,
+                                                                       long long n, float alpha, float* __restrict__ g, long long slot_stride) {
+  const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (e >= n) return;
+  for (int a = 0; a < RSYS_ADAPTER_SLOTS; ++a) {
+    float acc = 0.f; bool any = false;
+    for (int i = 0; i < n_seg; ++i)
+      if (segs[i * 5 + 3] == a) { acc += part[(long long)i * n + e]; any = true; }
     if (any) g[(long long)a * slot_stride + e] += alpha * acc;
   }
 }
@@ -532,7 +634,10 @@ static int bank_ensure(Model* m) {
   return RSYS_OK;
 }
 
-void adapter_bank_free(Model* m) { delete m->bank; m->bank = nullptr; }
+void adapter_bank_free(Model* m) {
+  if (m->bank) { (void)hipFree(m->bank->segA); (void)hipFree(m->bank->segB); }   // (grown on demand, so not in m->allocs)
+  delete m->bank; m->bank = nullptr;
+}
 
 // "transformers.layers.{l}.attn.{q,v}_proj_lora_{A,B}.weight" -> layer, which (0 qA, 1 qB, 2 vA, 3 vB)
 static bool bank_parse_name(const Model* m, const char* name, int* layer, int* which) {
@@ -668,7 +773,10 @@ int adapter_bind_tiles(Model* m, const int32_t* tile_adapter) {
 template <typename T>
 int bank_launch_a(const BankLaunch& a, const T* xn, T* La, bool train) {
   const dim3 grid((a.Ttok + BANK_A_TOK - 1) / BANK_A_TOK, a.rows);
-  if (a.tile_slot)   // (forward only: adapter_bind_tiles and rsys_op_adapter_bank_tiles never come with train)
+  if (a.tile_slot && train)   // packed finetune rows
+    hipLaunchKernelGGL((adapter_bank_a_train_tiles_kernel<T>), grid, dim3(256), 0, a.s, xn, (const T*)a.bankA, a.tile_slot, (a.Ttok + 63) / 64, a.layer, a.L,
+                       a.D, a.Ttok, La, a.p, a.seed, a.stream);
+  else if (a.tile_slot)   // packed serving rows (adapter_bind_tiles, rsys_op_adapter_bank_tiles)
     hipLaunchKernelGGL((adapter_bank_a_tiles_kernel<T>), grid, dim3(256), 0, a.s, xn, (const T*)a.bankA, a.tile_slot, (a.Ttok + 63) / 64, a.layer, a.L, a.D,
                        a.Ttok, La);
   else if (train)   // the LoRA input under the dropout mask
@@ -699,6 +807,29 @@ int bank_launch_backward(const BankLaunch& a, int stages, const T* xn, const T* 
                          float* gA, float* gB) {
   const int rows = a.rows, Nq = a.H * a.hd, Nk = a.KV * a.hd, Nv = Nk, Ttok = a.Ttok, D = a.D;
   hipStream_t s = a.s;
+  if (a.tile_slot) {   // packed finetune rows: per-tile token stages, per-segment partials (partA / partB: [n_seg][..]), sums in descriptor order
+    const int nt = (Ttok + 63) / 64;
+    if (stages & 4)
+      hipLaunchKernelGGL((adapter_bank_dla_tiles_kernel<T>), dim3((Ttok + BANK_A_TOK - 1) / BANK_A_TOK, rows), dim3(256), 0, s, dqkv, (const T*)a.bankB,
+                         a.tile_slot, nt, a.layer, a.L, Nq, Nk, Nv, Ttok, dLa);
+    if (stages & 8)
+      hipLaunchKernelGGL((adapter_bank_db_seg_kernel<T>), dim3((Nq + Nv + 63) / 64, a.n_seg), dim3(256), 0, s, dqkv, La, a.segs, Nq, Nk, Nv, Ttok, partB);
+    if (stages & 16)
+      hipLaunchKernelGGL((adapter_bank_da_seg_kernel<T>), dim3((D + 63) / 64, a.n_seg), dim3(256), 0, s, (const T*)dLa, xn, a.segs, D, Ttok, partA, a.p, a.seed,
+                         a.stream);
+    if (stages & 32)
+      hipLaunchKernelGGL((adapter_bank_dx_tiles_kernel<T>), dim3((Ttok + BANK_B_TOK - 1) / BANK_B_TOK, rows), dim3(256), 0, s, (const T*)dLa, (const T*)a.bankA,
+                         a.tile_slot, nt, a.layer, a.L, D, Ttok, dxn, a.p, a.seed, a.stream);
+    if (stages & 64) {
+      const long long na = (long long)16 * D, nb = (long long)(Nq + Nv) * 8;
+      hipLaunchKernelGGL(adapter_bank_segs_reduce_kernel, dim3((unsigned)((na + 255) / 256)), dim3(256), 0, s, partA, a.segs, a.n_seg, na, 1.f,
+                         gA + (long long)a.layer * na, (long long)a.L * na);
+      hipLaunchKernelGGL(adapter_bank_segs_reduce_kernel, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, s, partB, a.segs, a.n_seg, nb, 2.f,
+                         gB + (long long)a.layer * nb, (long long)a.L * nb);
+    }
+    HIP_CHECK(hipGetLastError());
+    return RSYS_OK;
+  }
   if (stages & 4)
     hipLaunchKernelGGL((adapter_bank_dla_kernel<T>), dim3((Ttok + BANK_A_TOK - 1) / BANK_A_TOK, rows), dim3(256), 0, s, dqkv, (const T*)a.bankB, a.row_slot,
                        a.layer, a.L, Nq, Nk, Nv, Ttok, dLa);
@@ -726,6 +857,7 @@ static BankLaunch bank_launch_of(const Model* m, int l) {
   BankLaunch a{};
   a.rows = m->cur_rows; a.Ttok = m->T; a.D = m->D; a.H = m->H; a.KV = m->KV; a.hd = m->hd; a.L = m->L; a.layer = l;
   a.row_slot = m->bank_rows; a.tile_slot = m->bank_tiles; a.bankA = b->A; a.bankB = b->B;
+  if (m->bank_packed) { a.segs = b->d_segs; a.n_seg = b->n_seg; }
   a.p = b->drop_now ? b->dropout : 0.f; a.seed = m->drop_seed; a.stream = (unsigned int)(m->drop_step * 64 + l);
   a.s = m->stream;
   return a;
@@ -827,13 +959,101 @@ int adapter_forward_backward(Model* m, int evaluate, const int32_t* row_slot, co
   return rc;
 }
 
+// The segment table of a packed call, checked on the host (rsys_adapter_forward_backward_packed and rsys_op_adapter_bank_segments): seg
+// [n_seg][5] = (row, first column, columns, slot, task) on rows of S interactions.  Fills the [rows][ceil(S / 32)] tile maps of slot and task
+// (-1 where no segment, or a base-model segment, lies) and says whether any segment names a slot.
+static int bank_segs_check(const int32_t* seg, int n_seg, int rows, int S, std::vector<int32_t>* tile_slot, std::vector<int32_t>* tile_task, bool* any) {
+  const int nt = (S + 31) / 32;
+  ARG_CHECK(seg != nullptr, "segment table is null");
+  ARG_CHECK(n_seg >= 1 && (long long)n_seg <= (long long)rows * nt && n_seg <= 65535, "n_seg must be in [1, rows * ceil(S / 32)]");
+  tile_slot->assign((size_t)rows * nt, -1); tile_task->assign((size_t)rows * nt, -1);
+  std::vector<unsigned char> owned((size_t)rows * nt, 0);
+  int owner[4] = {-1, -1, -1, -1};
+  *any = false;
+  for (int i = 0; i < n_seg; ++i) {
+    const int32_t* g = seg + (size_t)i * 5;
+    const int row = g[0], c0 = g[1], cols = g[2], sl = g[3], t = g[4];
+    ARG_CHECK(row >= 0 && row < rows, "a segment's row is outside the resident batch");
+    ARG_CHECK(c0 >= 0 && c0 % 32 == 0, "a segment starts at an interaction column that is a multiple of 32");
+    ARG_CHECK(cols >= 1 && cols <= S - c0, "a segment lies inside its row");
+    ARG_CHECK(sl >= -1 && sl < RSYS_ADAPTER_SLOTS, "segment slots must be in [-1, RSYS_ADAPTER_SLOTS)");
+    ARG_CHECK(t >= -1 && t < 4, "segment tasks must be in [-1, 4)");
+    ARG_CHECK((sl < 0) == (t < 0), "a segment names a slot and a task, or neither (-1 / -1)");
+    for (int j = c0 / 32; j < (c0 + cols + 31) / 32; ++j) {
+      ARG_CHECK(!owned[(size_t)row * nt + j], "two segments share a 64-token tile");
+      owned[(size_t)row * nt + j] = 1;
+      (*tile_slot)[(size_t)row * nt + j] = sl; (*tile_task)[(size_t)row * nt + j] = t;
+    }
+    if (sl < 0) continue;
+    ARG_CHECK(owner[t] < 0 || owner[t] == sl, "one task is named by two slots in the same call");
+    owner[t] = sl;
+    *any = true;
+  }
+  return RSYS_OK;
+}
+
+// rsys_adapter_forward_backward on packed rows: several users per row, each in a segment of whole 64-token tiles that names
+// its slot and task.  The caller guarantees the resident columns (one non-zero userid per segment, distinct within a row, zeros elsewhere).
+int adapter_forward_backward_packed(Model* m, int evaluate, const int32_t* seg, int n_seg, float grad_scale, uint64_t seed, uint64_t step) {
+  RC(bank_train_check_model(m));
+  ARG_CHECK(m->bank != nullptr && m->bank->train, "adapter bank training is not enabled (rsys_adapter_train_enable)");
+  ARG_CHECK(m->cur_rows > 0, "no batch uploaded");
+  RC(check_not_trimmed(m));
+  std::vector<int32_t> ts, tt;
+  bool any = false;
+  RC(bank_segs_check(seg, n_seg, m->cur_rows, m->S, &ts, &tt, &any));
+  for (int i = 0; i < n_seg; ++i)
+    if (seg[(size_t)i * 5 + 3] >= 0)
+      ARG_CHECK(bank_complete(m, seg[(size_t)i * 5 + 3]), "a segment names a slot that is not complete (4 tensors per layer since its last clear)");
+  AdapterBank* b = m->bank;
+  HIP_CHECK(hipSetDevice(m->device));
+  const int nta = (m->Sa + 31) / 32, nt = (m->S + 31) / 32;   // (full rows: nt == nta)
+  if (!b->d_tiles) DALLOC(b->d_tiles, (int64_t)m->rows_max * nta * 4);
+  if (!b->d_tile_task) DALLOC(b->d_tile_task, (int64_t)m->rows_max * nta * 4);
+  if (!b->d_segs) DALLOC(b->d_segs, (int64_t)m->rows_max * nta * 5 * 4);
+  HIP_CHECK(hipStreamSynchronize(m->stream));   // (the previous call's copies have read h_pack, its kernels the partials)
+  if (n_seg > b->seg_cap) {
+    float *na = nullptr, *nb = nullptr;
+    HIP_CHECK(hipMalloc((void**)&na, (size_t)n_seg * bank_a_floats(m) * 4));
+    if (hipMalloc((void**)&nb, (size_t)n_seg * bank_b_floats(m) * 4) != hipSuccess) { (void)hipFree(na); set_error("adapter bank: out of device memory for the segment partials"); return RSYS_ERR_HIP; }
+    (void)hipFree(b->segA); (void)hipFree(b->segB);
+    b->segA = na; b->segB = nb; b->seg_cap = n_seg;
+  }
+  const size_t ntile = (size_t)m->cur_rows * nt;
+  b->h_pack.resize(2 * ntile + (size_t)n_seg * 5);
+  std::copy(ts.begin(), ts.end(), b->h_pack.begin());
+  std::copy(tt.begin(), tt.end(), b->h_pack.begin() + ntile);
+  std::copy(seg, seg + (size_t)n_seg * 5, b->h_pack.begin() + 2 * ntile);
+  HIP_CHECK(hipMemcpyAsync(b->d_tiles, b->h_pack.data(), ntile * 4, hipMemcpyHostToDevice, m->stream));
+  HIP_CHECK(hipMemcpyAsync(b->d_tile_task, b->h_pack.data() + ntile, ntile * 4, hipMemcpyHostToDevice, m->stream));
+  HIP_CHECK(hipMemcpyAsync(b->d_segs, b->h_pack.data() + 2 * ntile, (size_t)n_seg * 5 * 4, hipMemcpyHostToDevice, m->stream));
+  b->n_seg = n_seg;
+  const bool det = m->deterministic;
+  m->deterministic = true;
+  m->bank_rows = nullptr;
+  m->bank_tiles = any ? b->d_tiles : nullptr;
+  m->bank_train = true;
+  m->bank_packed = true;   // masks per tile; the last layer runs dense (its compact order would mix segments inside a work item)
+  b->drop_now = !evaluate && b->dropout > 0.f;
+  int rc;
+  {
+    DetScope scope(m);
+    rc = model_forward_backward_rows(m, evaluate, b->d_tile_task, grad_scale, seed, step);
+  }
+  m->bank_packed = false;
+  m->bank_train = false;
+  m->bank_tiles = nullptr;
+  m->deterministic = det;
+  return rc;
+}
+
 template <typename T>
 int adapter_bank_backward(Model* m, int l, const T* xn, const T* dqkv, T* dxn) {
-  if (!m->bank_rows) return RSYS_OK;   // every row runs the base model: nothing to differentiate
+  if (!m->bank_rows && !m->bank_tiles) return RSYS_OK;   // every row runs the base model: nothing to differentiate
   AdapterBank* b = m->bank;
   tic(m, "adapter_bank_bwd");
-  RC(bank_launch_backward<T>(bank_launch_of(m, l), 4 | 8 | 16 | 32 | 64, xn, dqkv, (const T*)bank_la<T>(m, l), (T*)b->dLa, dxn, b->partA, b->partB, b->gA,
-                             b->gB));
+  RC(bank_launch_backward<T>(bank_launch_of(m, l), 4 | 8 | 16 | 32 | 64, xn, dqkv, (const T*)bank_la<T>(m, l), (T*)b->dLa, dxn,
+                             m->bank_packed ? b->segA : b->partA, m->bank_packed ? b->segB : b->partB, b->gA, b->gB));
   toc(m);
   return RSYS_OK;
 }
@@ -853,9 +1073,10 @@ static int bank_op_run(const BankLaunch& a, int stages, int train, const void* x
 int adapter_bank_op(int dtype, int stages, int train, int rows, int Ttok, int D, int H, int KV, int hd, int L, int layer, float p, uint64_t seed,
                     int64_t stream, const int32_t* row_slot, const void* bankA, const void* bankB, const void* xn, void* La, void* qkv, const void* dqkv,
                     void* dLa, void* dxn, float* partA, float* partB, float* gA, float* gB, const float* rope_cos, const float* rope_sin,
-                    const int32_t* rope_pos, int rope_rows, int tiles) {
-  // (tiles != 0, rsys_op_adapter_bank_tiles: row_slot is the tile map [rows][ceil(Ttok / 64)] and the two forward stages run in their per-tile form)
-  ARG_CHECK(!tiles || ((stages & ~3) == 0 && train == 0), "rsys_op_adapter_bank_tiles: stages 1 and 2 only (the forward, train = 0)");
+                    const int32_t* rope_pos, int rope_rows, int tiles, int n_seg) {
+  // (tiles == 1, rsys_op_adapter_bank_tiles: row_slot is the tile map [rows][ceil(Ttok / 64)] and the two forward stages run in their per-tile form;
+  //  tiles == 2, rsys_op_adapter_bank_segments: row_slot is the segment table [n_seg][5], every stage runs in its per-tile / per-segment form)
+  ARG_CHECK(tiles != 1 || ((stages & ~3) == 0 && train == 0), "rsys_op_adapter_bank_tiles: stages 1 and 2 only (the forward, train = 0)");
   ARG_CHECK(dtype == RSYS_DTYPE_BF16 || dtype == RSYS_DTYPE_FP32, "rsys_op_adapter_bank: dtype fp32 or bf16");
   ARG_CHECK(stages >= 1 && stages <= 127, "rsys_op_adapter_bank: stages is a mask of bits 1 .. 64");
   ARG_CHECK(rows >= 1 && rows <= 65535 && Ttok >= 8 && L >= 1 && layer >= 0 && layer < L && H >= 1 && KV >= 1, "rsys_op_adapter_bank: empty shape or layer outside [0, L)");
@@ -878,9 +1099,17 @@ int adapter_bank_op(int dtype, int stages, int train, int rows, int Ttok, int D,
   ARG_CHECK(!(stages & (16 | 64)) || partA, "rsys_op_adapter_bank: dA and the reductions use partA");
   ARG_CHECK(!(stages & (8 | 64)) || partB, "rsys_op_adapter_bank: dB and the reductions use partB");
   ARG_CHECK(!(stages & 64) || (gA && gB), "rsys_op_adapter_bank: the reductions need gA and gB");
-  std::vector<int32_t> host((size_t)rows * (tiles ? (Ttok + 63) / 64 : 1));
-  HIP_CHECK(hipMemcpy(host.data(), row_slot, host.size() * 4, hipMemcpyDeviceToHost));
-  for (int32_t v : host) ARG_CHECK(v >= -1 && v < RSYS_ADAPTER_SLOTS, "rsys_op_adapter_bank: row_slot entries must be in [-1, RSYS_ADAPTER_SLOTS)");
+  std::vector<int32_t> host((size_t)rows * (tiles ? (Ttok + 63) / 64 : 1)), seg_tiles, seg_tasks;
+  if (tiles == 2) {   // the segment table, checked as rsys_adapter_forward_backward_packed checks it (rows of Ttok / 2 interactions)
+    ARG_CHECK(n_seg >= 1 && n_seg <= 65535, "rsys_op_adapter_bank_segments: n_seg must be in [1, rows * ceil(Ttok / 64)]");
+    host.resize((size_t)n_seg * 5);
+    HIP_CHECK(hipMemcpy(host.data(), row_slot, host.size() * 4, hipMemcpyDeviceToHost));
+    bool any = false;
+    RC(bank_segs_check(host.data(), n_seg, rows, Ttok / 2, &seg_tiles, &seg_tasks, &any));
+  } else {
+    HIP_CHECK(hipMemcpy(host.data(), row_slot, host.size() * 4, hipMemcpyDeviceToHost));
+    for (int32_t v : host) ARG_CHECK(v >= -1 && v < RSYS_ADAPTER_SLOTS, "rsys_op_adapter_bank: row_slot entries must be in [-1, RSYS_ADAPTER_SLOTS)");
+  }
   if ((stages & 2) && rope_pos) {   // every explicit position inside the tables (one copy back)
     host.resize((size_t)rows * Ttok);
     HIP_CHECK(hipMemcpy(host.data(), rope_pos, host.size() * 4, hipMemcpyDeviceToHost));
@@ -890,11 +1119,18 @@ int adapter_bank_op(int dtype, int stages, int train, int rows, int Ttok, int D,
   }
   BankLaunch a{};
   a.rows = rows; a.Ttok = Ttok; a.D = D; a.H = H; a.KV = KV; a.hd = hd; a.L = L; a.layer = layer;
-  a.row_slot = tiles ? nullptr : row_slot; a.tile_slot = tiles ? row_slot : nullptr; a.bankA = bankA; a.bankB = bankB; a.p = p; a.seed = seed; a.stream = (unsigned int)stream; a.s = nullptr;
+  int* d_seg_tiles = nullptr;
+  if (tiles == 2) {   // (partA / partB: [n_seg][16][D], [n_seg][Nq + Nv][8])
+    HIP_CHECK(hipMalloc((void**)&d_seg_tiles, seg_tiles.size() * 4));
+    if (hipMemcpy(d_seg_tiles, seg_tiles.data(), seg_tiles.size() * 4, hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(d_seg_tiles); set_error("rsys_op_adapter_bank_segments: tile map upload failed"); return RSYS_ERR_HIP; }
+    a.segs = row_slot; a.n_seg = n_seg;
+  }
+  a.row_slot = tiles ? nullptr : row_slot; a.tile_slot = tiles == 2 ? d_seg_tiles : tiles ? row_slot : nullptr; a.bankA = bankA; a.bankB = bankB; a.p = p; a.seed = seed; a.stream = (unsigned int)stream; a.s = nullptr;
   int rc = dtype == RSYS_DTYPE_BF16
                ? bank_op_run<bf16>(a, stages, train, xn, La, qkv, dqkv, dLa, dxn, partA, partB, gA, gB, rope_cos, rope_sin, rope_pos)
                : bank_op_run<float>(a, stages, train, xn, La, qkv, dqkv, dLa, dxn, partA, partB, gA, gB, rope_cos, rope_sin, rope_pos);
   hipError_t e = hipDeviceSynchronize();
+  if (d_seg_tiles) (void)hipFree(d_seg_tiles);
   if (rc) return rc;
   HIP_CHECK(e);
   return RSYS_OK;

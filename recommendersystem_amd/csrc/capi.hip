@@ -303,6 +303,11 @@ int32_t rsys_adapter_forward_backward(rsys_model* h, int32_t evaluate, const int
   CHECK_HANDLE(h);
   return adapter_forward_backward(h->m, evaluate, row_slot, row_task, grad_scale, seed, step);
 }
+int32_t rsys_adapter_forward_backward_packed(rsys_model* h, int32_t evaluate, const int32_t* seg, int32_t n_seg, float grad_scale, uint64_t seed,
+                                             uint64_t step) {   // the same on packed rows: slot and task per segment
+  CHECK_HANDLE(h);
+  return adapter_forward_backward_packed(h->m, evaluate, seg, n_seg, grad_scale, seed, step);
+}
 int32_t rsys_adapter_grad_get(rsys_model* h, int32_t slot, const char* name, float* out, int64_t n) { CHECK_HANDLE(h); return adapter_grad_get(h->m, slot, name, out, n); }
 int32_t rsys_adapter_zero_grad(rsys_model* h) { CHECK_HANDLE(h); return adapter_zero_grad(h->m); }   // train.py:275
 int32_t rsys_adapter_adamw_step(rsys_model* h, float lr0, float beta1, float beta2, float eps, float wd, const float* per_slot, int32_t n_slots,
@@ -1252,6 +1257,16 @@ int32_t rsys_op_adapter_bank_tiles(int32_t dtype, int32_t stages, int32_t rows, 
   switches_parse();
   return adapter_bank_op(dtype, stages, 0, rows, Ttok, D, H, KV, hd, L, layer, 0.f, 0, 0, tile_slot, bankA, bankB, xn, La, qkv, nullptr, nullptr, nullptr,
                          nullptr, nullptr, nullptr, nullptr, rope_cos, rope_sin, rope_pos, rope_rows, 1);
+}
+
+int32_t rsys_op_adapter_bank_segments(int32_t dtype, int32_t stages, int32_t train, int32_t rows, int32_t Ttok, int32_t D, int32_t H, int32_t KV, int32_t hd,
+                                      int32_t L, int32_t layer, float p, uint64_t seed, int64_t stream, const int32_t* segs, int32_t n_seg, const void* bankA,
+                                      const void* bankB, const void* xn, void* La, void* qkv, const void* dqkv, void* dLa, void* dxn, float* partA,
+                                      float* partB, float* gA, float* gB, const float* rope_cos, const float* rope_sin, const int32_t* rope_pos,
+                                      int32_t rope_rows) {
+  switches_parse();
+  return adapter_bank_op(dtype, stages, train, rows, Ttok, D, H, KV, hd, L, layer, p, seed, stream, segs, bankA, bankB, xn, La, qkv, dqkv, dLa, dxn, partA,
+                         partB, gA, gB, rope_cos, rope_sin, rope_pos, rope_rows, 2, n_seg);
 }
 
 int32_t rsys_op_adapter_bank_adamw(int32_t dtype, float* A32, float* B32, float* gA, float* gB, float* mA, float* vA, float* mB, float* vB, void* A,

@@ -99,10 +99,7 @@ int launch_mask_tokens(BatchDev b, int finetune, int finetune_metric, float mask
 // transformer.model.py:417-435 with the metric of the ROW's task (training through the adapter bank): the finetune branch of
 // the kernel above per row, then the masked weights of every task but the row's own are zero, so a task's loss and weight sum come
 // from the rows of its slot alone.  row_task[r] = -1: the row runs the base model as given and carries no weight.
-__global__ void mask_tokens_rows_kernel(BatchDev b, const int* __restrict__ row_task) {
-  int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= b.N) return;
-  const int task = row_task[i / b.S];
+__device__ __forceinline__ void mask_tokens_task(const BatchDev& b, int i, int task) {
   const int x = task & 1;
   bool wm = false, rm = false;
   if (task >= 0) {
@@ -127,9 +124,26 @@ __global__ void mask_tokens_rows_kernel(BatchDev b, const int* __restrict__ row_
     }
   }
 }
+__global__ void mask_tokens_rows_kernel(BatchDev b, const int* __restrict__ row_task) {
+  int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= b.N) return;
+  mask_tokens_task(b, i, row_task[i / b.S]);
+}
+// packed finetune rows: the task of the interaction's tile of 32 columns, tile_task [rows][ceil(S / 32)] (-1 between segments)
+__global__ void mask_tokens_tiles_kernel(BatchDev b, const int* __restrict__ tile_task, int nt) {
+  int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= b.N) return;
+  const int row = i / b.S, col = i - row * b.S;
+  mask_tokens_task(b, i, tile_task[row * nt + (col >> 5)]);
+}
 
 int launch_mask_tokens_rows(BatchDev b, const int* row_task, hipStream_t s) {
   hipLaunchKernelGGL(mask_tokens_rows_kernel, dim3(div_up(b.N, 256)), dim3(256), 0, s, b, row_task);
+  HIP_CHECK(hipGetLastError());
+  return RSYS_OK;
+}
+int launch_mask_tokens_tiles(BatchDev b, const int* tile_task, hipStream_t s) {
+  hipLaunchKernelGGL(mask_tokens_tiles_kernel, dim3(div_up(b.N, 256)), dim3(256), 0, s, b, tile_task, (b.S + 31) / 32);
   HIP_CHECK(hipGetLastError());
   return RSYS_OK;
 }

@@ -50,6 +50,8 @@ int launch_mask_tokens(BatchDev b, int finetune, int finetune_metric, float mask
 // the finetune rule per batch row: row r of task row_task[r] = medium * 2 + metric is masked as a finetune model of that
 // metric masks it, and its masked weights of every other task are zero; row_task[r] = -1: nothing masked, no weight
 int launch_mask_tokens_rows(BatchDev b, const int* row_task, hipStream_t s);
+// the same with the task per 32 interactions (packed finetune rows): tile_task [rows][ceil(S / 32)]
+int launch_mask_tokens_tiles(BatchDev b, const int* tile_task, hipStream_t s);
 
 template <typename T>
 int launch_action_features(const BatchDev& b, const SmallParams& sp, T* feat /*[N][32]*/, hipStream_t s);

@@ -936,11 +936,12 @@ static int forward_backward_t(Model* m, int evaluate, const float task_w[4], flo
   BatchDev b = m->bd; b.N = N; b.rows = rows; b.S = m->S;
   if (m->has_masks) { b.watch_mask = m->d_wm; b.rating_mask = m->d_rm; }
   m->cur_seed = seed; m->cur_step = step;
-  if (d_row_task) RC(launch_mask_tokens_rows(b, d_row_task, m->stream));
+  if (d_row_task && m->bank_packed) RC(launch_mask_tokens_tiles(b, d_row_task, m->stream));   // (packed rows: the vector is the [rows][ceil(S / 32)] tile map)
+  else if (d_row_task) RC(launch_mask_tokens_rows(b, d_row_task, m->stream));
   else RC(launch_mask_tokens(b, m->cfg.finetune, m->cfg.finetune_metric, m->cfg.mask_rate, seed, step, m->stream));
   m->drop_active = m->cfg.finetune && !evaluate && m->cfg.lora_dropout > 0.f;   // nn.Dropout is active in train() mode only
   m->drop_seed = seed ^ 0xD409ull; m->drop_step = step;
-  m->top_is_sparse = m->sparse_top && !evaluate;
+  m->top_is_sparse = m->sparse_top && !evaluate && !m->bank_packed;
   m->f8_tcopies = !evaluate;
   m->host_stream_syncs = 0; m->host_event_waits = 0;
   float tw[4];

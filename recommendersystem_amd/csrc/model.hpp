@@ -278,6 +278,10 @@ struct Model {
   // (the `ft` paths of the forward, heads and backward: dx chain only), keeps La per layer, draws the LoRA dropout inside the bank's
   // kernels and sends the few small gradients those paths still write (norm gains, rating-head biases) to bank_sink, never to G
   bool bank_train = false;
+  // training on packed rows: true only inside rsys_adapter_forward_backward_packed.  The pass's masks take their task per 64-token
+  // tile (the task vector handed to model_forward_backward_rows is the tile map), the bank's backward runs per tile / segment, and the last
+  // layer runs dense (top_is_sparse stays false: its selected-first order would put tokens of several segments into one work item)
+  bool bank_packed = false;
   float* bank_sink = nullptr;   // [max(D, 64)] floats nobody reads
   RenderState* render = nullptr;        // rsys_render_request's workspace, forward counters and kept intermediates (allocated on first use)
   // ranking cache (rank_cache.hip, rsys_rank_cache_*): the post-RoPE K | V of users' history tokens per layer, [L][rc_slots][T][2 KV hd] in
@@ -337,6 +341,7 @@ inline bool trunk_frozen(const Model* m) { return m->cfg.finetune != 0 || m->ban
 inline float* small_grad(Model* m, int64_t off) { return m->bank_train ? m->bank_sink : m->G + off; }   // where a frozen-trunk pass may drop a <= D-float gradient
 int adapter_train_enable(Model* m, float dropout);
 int adapter_forward_backward(Model* m, int evaluate, const int32_t* row_slot, const int32_t* row_task, float grad_scale, uint64_t seed, uint64_t step);
+int adapter_forward_backward_packed(Model* m, int evaluate, const int32_t* seg, int n_seg, float grad_scale, uint64_t seed, uint64_t step);   // packed rows
 int adapter_grad_get(Model* m, int slot, const char* name, float* out, int64_t n);
 int adapter_zero_grad(Model* m);
 int adapter_adamw_step(Model* m, float lr0, float b1, float b2, float eps, float wd, const float* per_slot, int n_slots, float* norms_out);
@@ -347,7 +352,8 @@ template <typename T> int adapter_bank_backward(Model* m, int l, const T* xn, co
 int adapter_bank_op(int dtype, int stages, int train, int rows, int Ttok, int D, int H, int KV, int hd, int L, int layer, float p, uint64_t seed,
                     int64_t stream, const int32_t* row_slot, const void* bankA, const void* bankB, const void* xn, void* La, void* qkv, const void* dqkv,
                     void* dLa, void* dxn, float* partA, float* partB, float* gA, float* gB, const float* rope_cos, const float* rope_sin,
-                    const int32_t* rope_pos, int rope_rows, int tiles = 0 /* row_slot is a tile map: rsys_op_adapter_bank_tiles */);
+                    const int32_t* rope_pos, int rope_rows, int tiles = 0 /* 1: row_slot is a tile map (rsys_op_adapter_bank_tiles); 2: a segment table */,
+                    int n_seg = 0 /* tiles == 2: its length (rsys_op_adapter_bank_segments) */);
 int adapter_bank_adamw_op(int dtype, float* A32, float* B32, float* gA, float* gB, float* mA, float* vA, float* mB, float* vB, void* A, void* B,
                           int64_t nA, int64_t nB, const float* per_slot, float b1, float b2, float eps, float wd, float* norms);
 // the joint pass's body (model.hip): masks per row task (d_row_task: device, [rows]), forward, heads with every task at grad_scale, backward

@@ -537,6 +537,22 @@ class RecommenderModel:
                                                   self.mask_seed, int(step)))
         return self.losses(bool(evaluate))
 
+    def forward_backward_adapters_packed(self, d, segments, evaluate=False, grad_scale=1.0, step=None):
+        """`forward_backward_adapters` on packed rows (`train.pack_adapter_rows`): `segments` (n, 5) int32 = (row,
+        first_column, columns, slot, task), one per user, each the live prefix of that user's finetune row starting on a multiple of 32
+        columns.  d None: the batch already resident.  A slot's gradient sums its segments in the order given."""
+        if d is not None:
+            self.upload(d)
+        sg = np.ascontiguousarray(np.asarray(segments), np.int32)
+        if sg.ndim != 2 or sg.shape[1] != 5:
+            raise ValueError(f"forward_backward_adapters_packed: segments has shape {sg.shape}, expected (n, 5)")
+        if step is None:
+            step = self._step
+            self._step += 1
+        check(lib().rsys_adapter_forward_backward_packed(self._h, 1 if evaluate else 0, sg.ctypes.data, sg.shape[0], float(grad_scale),
+                                                         self.mask_seed, int(step)))
+        return self.losses(bool(evaluate))
+
     def adapter_grad(self, slot, name=None):
         """the fp32 gradient of one LoRA tensor of `slot`, or {name: gradient} of all of them"""
         def one(n, shape):

@@ -4,6 +4,7 @@ alternating in one process, medians of --calls calls after a warm-up, taken twic
 (hipMemGetInfo before / after creation).
 
     python tools/bench_adapter_train.py [--config cfg3] [--calls 20] [--out profiles/adapter_train_bench.json]
+    python tools/bench_adapter_train.py --pack [--out profiles/adapter_pack_train_bench.json]     (packed rows, DESIGN 4zc: see pack_bench)
     rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python tools/bench_adapter_train.py --trace     (a few joint steps only)
 """
 import argparse
@@ -49,13 +50,92 @@ def median_ms(fn, calls, warmup=3):
     return statistics.median(ts), min(ts)
 
 
+def finetune_users(cfg, users, events, seed, task):
+    """`users` finetune rows of task (medium, metric): `events` live columns cut from the synthetic stream as ONE user each, zeros
+    behind, and one target -- the last event, an item of the task's medium -- as the reference's FinetuneDataset rows carry it"""
+    S = cfg["max_sequence_length"]
+    m, metric = task >> 1, METRICS[task & 1]
+    d = {k: np.array(np.asarray(v).reshape(users, S)) for k, v in workload.make_batch(cfg, users, seed).items()}
+    for k, v in d.items():
+        v[:, events:] = 0
+        if k.endswith(".weight"):
+            v[:] = 0
+    d["userid"][:, :events] = 1 + np.arange(users)[:, None]
+    last = events - 1
+    d["matchedid"][:, last] = 5 + (cfg["vocab_sizes"]["0_matchedid"] if m == 1 else 0)
+    d["token_mask_ids"][:, last] = 1
+    d[f"{m}.{metric}.weight"][:, last] = 1
+    d[f"{m}.{metric}.label"][:, last] = 1 if metric == "watch" else 7
+    d[f"{m}.{metric}.position"][:, last] = 5
+    return {k: v.reshape(-1) for k, v in d.items()}
+
+
+def pack_bench(a):
+    """Packed against unpacked joint steps at the cfg-3 size, bf16: four slots x 16 users of `events` live events each.
+    Arm (a): the unpacked joint step, one user per row (64 rows); arm (b): the packed step on the same users (train.pack_adapter_rows).
+    Both models live in this process, the arms alternate (a b a b), every figure is the median of --calls steps after a warm-up, and
+    every step ends in its loss read-back and the optimizer's norm copy (both synchronise).  events = S: 64 full-length users, the
+    same rows in both arms -- what is left is the packed pass's dense last layer."""
+    from recommendersystem_amd.train import pack_adapter_batch, pack_adapter_rows
+    lines = []
+    for S in (512, 1024):
+        cfg = workload.make_config(a.config, max_sequence_length=S)
+        cfg["forward"] = "train"
+        banks = []
+        for _ in range(2):
+            bank = ra.RecommenderModel(cfg, device=0, dtype="bf16", max_rows=4 * ROWS)
+            bank.init_weights(0x1217); bank.random_pretrained_embeddings(0x3E7A)
+            for s in range(4):
+                bank.load_adapter(s, adapter(bank, 100 + s))
+            bank.enable_adapter_training(0.1)
+            banks.append((bank, AdapterAdamW(bank, lr=2e-4, slots=range(4))))
+        (flat_bank, flat_opt), (pack_bank, pack_opt) = banks
+        for events in (30, 100, 300, S):
+            subs = [(s, s, finetune_users(cfg, ROWS, events, 11 + s, s)) for s in range(4)]
+            flat, row_slot, row_task = pack_adapter_batch(subs, S)
+            packed, segs = pack_adapter_rows(subs, S, 4 * ROWS, cfg["mask_topk"])
+            flat_bank.upload(flat); pack_bank.upload(packed)
+
+            def step_a():
+                flat_bank.forward_backward_adapters(None, row_slot, row_task)
+                flat_opt.step({s: 1.0 for s in range(4)}, clip_max_norm=1.0)
+
+            def step_b():
+                pack_bank.forward_backward_adapters_packed(None, segs)
+                pack_opt.step({s: 1.0 for s in range(4)}, clip_max_norm=1.0)
+
+            if a.trace:
+                for _ in range(5):
+                    step_b()
+                continue
+            ta, tb = median_ms(step_a, a.calls), median_ms(step_b, a.calls)
+            ta2, tb2 = median_ms(step_a, a.calls), median_ms(step_b, a.calls)
+            rows_b = packed["userid"].size // S
+            line = {"config": a.config, "dtype": "bf16", "S": S, "events": events, "users": 4 * ROWS, "calls": a.calls,
+                    "unpacked": {"rows": 4 * ROWS, "tokens": 4 * ROWS * 2 * S, "median_ms": [ta[0], ta2[0]], "min_ms": min(ta[1], ta2[1])},
+                    "packed": {"rows": rows_b, "tokens": rows_b * 2 * S, "median_ms": [tb[0], tb2[0]], "min_ms": min(tb[1], tb2[1])},
+                    "packed_over_unpacked_time": (tb[0] + tb2[0]) / (ta[0] + ta2[0]), "packed_over_unpacked_tokens": rows_b / (4.0 * ROWS),
+                    "packed_median_below_unpacked_min": max(tb[0], tb2[0]) < min(ta[1], ta2[1])}
+            lines.append(line)
+            print("pack", json.dumps(line), flush=True)
+        for bank, _ in banks:
+            bank.close()
+    if a.out and not a.trace:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(lines, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", default="cfg3")
     ap.add_argument("--calls", type=int, default=20)
     ap.add_argument("--out", default=None)
     ap.add_argument("--trace", action="store_true", help="a few joint steps only (run under rocprofv3 --kernel-trace --stats)")
+    ap.add_argument("--pack", action="store_true", help="packed against unpacked joint steps at S = 512 and 1024 (DESIGN 4zc)")
     a = ap.parse_args()
+    if a.pack:
+        return pack_bench(a)
     cfg = workload.make_config(a.config)
     cfg["forward"] = "train"
     S = cfg["max_sequence_length"]
