@@ -137,11 +137,21 @@ int32_t rsys_batch_swap(rsys_model* m);
  *   a forward is max_rows such rows at row_len = min(S, 32 ceil(its fullest row / 32)), whatever rsys_serving_trim_set says.  Each
  *   segment runs with the adapter slot of its own medium (one slot per 64-token tile).  A retrieval row must hold one user (one userid
  *   beside 0: RSYS_ERR_ARG otherwise).  Q and everything after it is in user order as before: pages, totals, ranking waves, store
- *   rows, slots and chunks are unchanged; "forward_rows" reports the packed forwards as (0, rows, row_len). */
+ *   rows, slots and chunks are unchanged; "forward_rows" reports the packed forwards as (0, rows, row_len).
+ * rsys_serving_pack_ranking_set (default 0; read by rsys_render_request_full only): the K/V-cache store rows of that pipeline
+ *   hold several users.  A store wave is up to rc_slots users with a history (the model's reserve, rsys_rank_cache_reserve; at least
+ *   max_rows), slot = the user's place in the wave.  Its histories become segments that start at a column that is a multiple of 32, placed
+ *   first-fit in decreasing length, ties in user order, rows in the order they were opened, forwards of max_rows rows at row_len =
+ *   min(S, 32 ceil(fullest row / 32)) -- if that takes fewer forwards than one history per row at that row's trim length, or as many
+ *   forwards and fewer tokens; otherwise one history per row, at column 0.  The rows are cut on the device from the kept history rows
+ *   and stored as rsys_rank_cache_store_packed stores them, without a host wait.  Candidate forwards, the empty-history rows, chunking,
+ *   pages and totals are unchanged; "forward_rows" reports the packed store forwards as (1, rows, row_len). */
 int32_t rsys_batch_upload_trimmed(rsys_model* m, const rsys_batch* b, int32_t row_len);
 int32_t rsys_batch_row_length(rsys_model* m, int32_t* row_len_out);
 int32_t rsys_serving_pack_set(rsys_model* m, int32_t on);
 int32_t rsys_serving_pack_get(rsys_model* m, int32_t* on_out);
+int32_t rsys_serving_pack_ranking_set(rsys_model* m, int32_t on);
+int32_t rsys_serving_pack_ranking_get(rsys_model* m, int32_t* on_out);
 int32_t rsys_serving_trim_set(rsys_model* m, int32_t on);
 int32_t rsys_serving_trim_get(rsys_model* m, int32_t* on_out);
 /* device-side synthetic batch (bench): fills the resident batch from a counter RNG */
@@ -632,6 +642,25 @@ int32_t rsys_adapter_adamw_state_set(rsys_model* m, int32_t slot, const char* na
 int32_t rsys_rank_cache_reserve(rsys_model* m, int32_t n_slots);
 int32_t rsys_rank_cache_store(rsys_model* m, const int32_t* row_adapter, const int32_t* n_hist, const int32_t* slot);
 int32_t rsys_rank_cache_candidates(rsys_model* m, const int32_t* row_adapter, const int32_t* slot, const int32_t* n_cand, float* out);
+/* The two cache calls on PACKED rows: several users per row of the resident batch (full or trimmed), each in a segment -- a run
+ * of whole 64-token attention tiles of one row that starts at an interaction column that is a multiple of 32; no tile holds two segments;
+ * the columns between segments are zero padding with userid 0.  seg_adapter[n_seg]: the adapter-bank slot of every segment or -1 (NULL:
+ * the base model), applied per tile as in rsys_infer_select_tiles.
+ * rsys_rank_cache_store_packed: seg[n_seg][4] = (row, first_column, n_hist, slot).  A store segment holds one user's n_hist history events
+ *   alone (token_mask_ids 0; userid distinct among the segments of the forward, so that no history sees another); the call runs event i of a
+ *   segment at RoPE position i itself, whatever the batch's rope_input_pos says.  K and V of the segment's tokens of every layer go to rows
+ *   [0, 2 n_hist) of its slot: the slot rsys_rank_cache_store fills from the same history in a row of its own.
+ * rsys_rank_cache_candidates_packed: seg[n_seg][4] = (row, first_column, n_cand, slot).  A candidate segment holds n_cand in [1, S] candidates
+ *   at columns first_column + j and reads its slot as a row of rsys_rank_cache_candidates does; every token of its tiles runs at RoPE
+ *   position n_hist of that slot.  A user's list may be cut into several segments, in one row or in several, and several segments may read
+ *   one slot.  out[sum n_cand]: the rating head at the candidates' action tokens, segment after segment in descriptor order.
+ * Both are synchronous.  RSYS_ERR_ARG (nothing is written, no slot is marked stored, out untouched): what the row calls refuse, n_seg outside
+ * [1, max_rows x ceil(S / 32)], a row outside the batch, a first column that is not a multiple of 32, a segment that crosses its row's end
+ * or shares a tile with another, n_hist outside [0, row length], n_cand outside [1, row length], duplicate slots in one store, a candidate
+ * slot never stored or holding more than S - 1 events, an incomplete adapter slot, an fp8, finetune = 1 or row-sharded model.  A store that
+ * fails while it runs invalidates the slots it names. */
+int32_t rsys_rank_cache_store_packed(rsys_model* m, const int32_t* seg_adapter, int32_t n_seg, const int32_t* seg);
+int32_t rsys_rank_cache_candidates_packed(rsys_model* m, const int32_t* seg_adapter, int32_t n_seg, const int32_t* seg, float* out);
 /* debug/parity: trunk output of the last forward (rows*2S*D floats).  A training pass computes it only at the positions the heads
  * select; this call then runs the dense tail of the last layer first (results as model.py:335-343 over every token). */
 int32_t rsys_trunk_output_get(rsys_model* m, float* out, int64_t n);

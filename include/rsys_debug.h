@@ -114,6 +114,17 @@ int32_t rsys_op_attention_ex(int32_t dtype, int32_t B, int32_t T, int32_t H, int
  * 64-token tile that holds a candidate and left as they were behind it */
 int32_t rsys_op_attention_cached(int32_t dtype, int32_t rows, int32_t T, int32_t H, int32_t KV, int32_t hd, const void* qkv, const void* cache,
                                  int32_t n_slots, const int32_t* slot, const int32_t* n_hist, const int32_t* n_cand, void* O);
+/* the candidate attention of rsys_rank_cache_candidates_packed alone (attn_cand_tiles_kernel), buffers as above: seg (HOST int32 [n_seg][5]) =
+ * (row, first_tile, n_cand, slot, n_hist): the segment's candidate j sits at tokens 64 first_tile + 2 j, + 1 of its row and reads the 2 n_hist
+ * cached tokens of slot; segments lie inside their rows and share no 64-token tile (RSYS_ERR_ARG otherwise); cache [n_slots][Tc][2*KV*hd]
+ * (Tc = 0: T).  O: a tile no segment covers is left as it was; rows of tokens behind a segment's candidates are zeros up to the end of its last tile */
+int32_t rsys_op_attention_cached_tiles(int32_t dtype, int32_t rows, int32_t T, int32_t H, int32_t KV, int32_t hd, const void* qkv, const void* cache,
+                                       int32_t n_slots, int32_t Tc, int32_t n_seg, const int32_t* seg, void* O);
+/* the copy of rsys_rank_cache_store_packed alone (rank_cache_copy_segments_kernel): seg (HOST int32 [n_seg][4]) = (row, first column c0, n_hist,
+ * slot); K | V of tokens [2 c0, 2 c0 + 2 n_hist) of the row of qkv [rows*T][(H+2KV)*hd] -> rows [0, 2 n_hist) of the slot of cache
+ * [n_slots][Tc][2*KV*hd] (Tc = 0: T); nothing else is written */
+int32_t rsys_op_rank_cache_copy_segments(int32_t dtype, int32_t rows, int32_t T, int32_t H, int32_t KV, int32_t hd, const void* qkv, void* cache,
+                                         int32_t n_slots, int32_t Tc, int32_t n_seg, const int32_t* seg);
 /* K | V rows a ranking-cache slot holds for one layer: out (host) [2 n_hist][2*KV*hd] in the compute dtype; bytes must be exact */
 int32_t rsys_rank_cache_get(rsys_model* m, int32_t layer, int32_t slot, void* out, int64_t bytes);
 /* the selection of rsys_retrieve_topk alone, on caller-provided device buffers: per row r of scores [rows][ld >= V] the min(k, admissible)

@@ -162,6 +162,12 @@ function serving_pack(m::Model)   # the retrieval stage of the two render calls 
     check(ccall((:rsys_serving_pack_get, LIB), Int32, (Ptr{Cvoid}, Ref{Int32}), m.h, on))
     on[] != 0
 end
+serving_pack_ranking!(m::Model, on::Bool) = check(ccall((:rsys_serving_pack_ranking_set, LIB), Int32, (Ptr{Cvoid}, Int32), m.h, on ? 1 : 0))
+function serving_pack_ranking(m::Model)   # render_request_full packs its K/V-cache store rows (several histories per row)
+    on = Ref{Int32}(0)
+    check(ccall((:rsys_serving_pack_ranking_get, LIB), Int32, (Ptr{Cvoid}, Ref{Int32}), m.h, on))
+    on[] != 0
+end
 serving_trim!(m::Model, on::Bool) = check(ccall((:rsys_serving_trim_set, LIB), Int32, (Ptr{Cvoid}, Int32), m.h, on ? 1 : 0))
 function serving_trim(m::Model)
     on = Ref{Int32}(0)
@@ -221,6 +227,20 @@ function rank_cache_candidates(m::Model, row_adapter::Union{Nothing, Vector{Int3
     ra = row_adapter === nothing ? Ptr{Int32}(C_NULL) : pointer(row_adapter)
     GC.@preserve row_adapter slot n_cand out check(ccall((:rsys_rank_cache_candidates, LIB), Int32,
                                                          (Ptr{Cvoid}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Float32}), m.h, ra, slot, n_cand, out))
+    out
+end
+# The same two passes on packed rows (rsys.h: several users per row, one segment of whole 64-token tiles each).  seg: 4 x n_seg Int32,
+# column i = (row, first_column, n_hist | n_cand, slot) of segment i, zero-based as in the C ABI; seg_adapter may be `nothing`.
+function rank_cache_store_packed(m::Model, seg_adapter::Union{Nothing, Vector{Int32}}, seg::Matrix{Int32})
+    sa = seg_adapter === nothing ? Ptr{Int32}(C_NULL) : pointer(seg_adapter)
+    GC.@preserve seg_adapter seg check(ccall((:rsys_rank_cache_store_packed, LIB), Int32, (Ptr{Cvoid}, Ptr{Int32}, Int32, Ptr{Int32}),
+                                             m.h, sa, size(seg, 2), seg))
+end
+function rank_cache_candidates_packed(m::Model, seg_adapter::Union{Nothing, Vector{Int32}}, seg::Matrix{Int32})
+    out = Vector{Float32}(undef, sum(seg[3, :]))
+    sa = seg_adapter === nothing ? Ptr{Int32}(C_NULL) : pointer(seg_adapter)
+    GC.@preserve seg_adapter seg out check(ccall((:rsys_rank_cache_candidates_packed, LIB), Int32,
+                                                 (Ptr{Cvoid}, Ptr{Int32}, Int32, Ptr{Int32}, Ptr{Float32}), m.h, sa, size(seg, 2), seg, out))
     out
 end
 

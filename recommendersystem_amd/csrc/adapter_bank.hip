@@ -732,7 +732,10 @@ int adapter_bind_rows(Model* m, const int32_t* row_adapter) {
   if (!any) return RSYS_OK;   // every row runs the base model: the forward launches what rsys_infer_select launches
   AdapterBank* b = m->bank;
   HIP_CHECK(hipSetDevice(m->device));
-  if (!b->La) DALLOC(b->La, (int64_t)m->rows_max * m->Ta * 16 * m->esz);
+  if (!b->La) {
+    DALLOC(b->La, (int64_t)m->rows_max * m->Ta * 16 * m->esz);
+    HIP_CHECK(hipDeviceSynchronize());   // (its zero fill runs on the null stream: done before the model's stream writes La)
+  }
   HIP_CHECK(hipMemcpyAsync(b->d_rows, row_adapter, (size_t)m->cur_rows * 4, hipMemcpyHostToDevice, m->stream));
   m->bank_rows = b->d_rows;
   return RSYS_OK;
@@ -758,8 +761,12 @@ int adapter_bind_tiles(Model* m, const int32_t* tile_adapter) {
   if (!any) return RSYS_OK;   // every live tile runs the base model: the forward launches what rsys_infer_select launches
   AdapterBank* b = m->bank;
   HIP_CHECK(hipSetDevice(m->device));
+  const bool fresh = !b->La || !b->d_tiles;
   if (!b->La) DALLOC(b->La, (int64_t)m->rows_max * m->Ta * 16 * m->esz);
   if (!b->d_tiles) DALLOC(b->d_tiles, (int64_t)m->rows_max * nta * 4);
+  // (dalloc's zero fill runs on the null stream and the model's stream does not wait for that one: without this the fill may land on the
+  // map copied below -- every tile then reads slot 0 in the first packed forward of a model)
+  if (fresh) HIP_CHECK(hipDeviceSynchronize());
   HIP_CHECK(hipStreamSynchronize(m->stream));   // (the previous call's copy has read h_tiles)
   b->h_tiles.resize((size_t)m->cur_rows * nt);
   for (int r = 0; r < m->cur_rows; ++r) std::copy(tile_adapter + (size_t)r * nta, tile_adapter + (size_t)r * nta + nt, b->h_tiles.begin() + (size_t)r * nt);

@@ -1564,20 +1564,18 @@ template int launch_attn_bwd<float>(const AttnParams&, hipStream_t);
 // through a descriptor that ends at the slot's last stored row: rows past it come back as zeros, never as what an earlier user left.
 // No atomics; query tiles past the row's candidates return at once and write nothing; inside the last live tile the rows of tokens
 // >= 2 n_cand are written as zeros.
+// The body both kernels below call: query tile qt of row b, heads h0 .. h0 + R - 1 of kv head kvh, against the nh2 cached tokens of `slot`
+// and the tile's own 64 tokens; the rows of tokens >= nq (a token index of the row) are written as zeros.  Everything it is handed is
+// workgroup-uniform.  Loads, the cached-tile walk, the self tile, the online soft-max, the zeroing and the stores live here, so the row
+// form and the per-tile form (packed rows) have the same per-token arithmetic in the same order.
 template <typename T, int HD, int R>
-__global__ __launch_bounds__(256, (is_bf16<T>::value && HD <= 64) ? (R == 1 ? 3 : 2) : 1) void attn_cand_kernel(CandAttnParams p) {
+__device__ __forceinline__ void attn_cand_body(const CandAttnParams& p, const int b, const int kvh, const int h0, const int qt, const int nq, const int nh2,
+                                               const int slot) {
   using C = ACfg<T, HD>;
   using M = AMma<T>;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   T* Ks = (T*)smem_raw;                       // [2][64][LDD]
   T* Vs = Ks + 2 * C::TILE;                   // [2][64][LDD]
-  const int nt = (p.T + 63) / 64, n_inner = (p.H / p.KV / R) * nt;
-  const int grp = blockIdx.x / n_inner, inner = blockIdx.x % n_inner;
-  const int b = grp / p.KV, kvh = grp % p.KV, h0 = kvh * (p.H / p.KV) + (inner / nt) * R, qt = inner % nt;
-  const int nq = 2 * min(max(p.n_cand[b], 0), p.T / 2);     // candidate tokens of the row
-  if (qt * 64 >= nq) return;                                 // (uniform: whole workgroup)
-  const int nh2 = 2 * min(max(p.n_hist[b], 0), p.Tc / 2);    // cached tokens of the row's slot
-  const int slot = min(max(p.slot[b], 0), p.n_slots - 1);
   const int nht = (nh2 + 63) / 64;
   const int t = threadIdx.x, l = t & 63, w = t >> 6, g = l >> 4, fr = l & 15;
   const long long tok0 = (long long)b * p.T;
@@ -1701,6 +1699,40 @@ __global__ __launch_bounds__(256, (is_bf16<T>::value && HD <= 64) ? (R == 1 ? 3 
     copy_out_tile<T, HD>(Ks + r * C::TILE, (T*)p.o + (tok0 + qt * 64) * p.ldo + (h0 + r) * HD, p.ldo, qt * 64, p.T, t);
 }
 
+template <typename T, int HD, int R>
+__global__ __launch_bounds__(256, (is_bf16<T>::value && HD <= 64) ? (R == 1 ? 3 : 2) : 1) void attn_cand_kernel(CandAttnParams p) {
+  const int nt = (p.T + 63) / 64, n_inner = (p.H / p.KV / R) * nt;
+  const int grp = blockIdx.x / n_inner, inner = blockIdx.x % n_inner;
+  const int b = grp / p.KV, kvh = grp % p.KV, h0 = kvh * (p.H / p.KV) + (inner / nt) * R, qt = inner % nt;
+  const int nq = 2 * min(max(p.n_cand[b], 0), p.T / 2);     // candidate tokens of the row
+  if (qt * 64 >= nq) return;                                 // (uniform: whole workgroup)
+  const int nh2 = 2 * min(max(p.n_hist[b], 0), p.Tc / 2);    // cached tokens of the row's slot
+  const int slot = min(max(p.slot[b], 0), p.n_slots - 1);
+  attn_cand_body<T, HD, R>(p, b, kvh, h0, qt, nq, nh2, slot);
+}
+
+// Packed candidate rows (rsys_rank_cache_candidates_packed): attn_cand_kernel with the row triple replaced by a per-tile
+// lookup.  tile_seg [rows][ceil(T / 64)] names the segment of every 64-token tile (-1: a dead tile, which returns before its first load and
+// writes nothing); seg [n_seg][4] = (slot, n_hist, first_tile, n_cand).  A segment is a run of whole tiles of one row, so the tile's
+// "self" tile is still its own 64 tokens and the segment's last tile ends at token 64 first_tile + 2 n_cand of the row.  The lookup
+// depends on blockIdx alone: the compiler keeps it in scalar registers.
+template <typename T, int HD, int R>
+__global__ __launch_bounds__(256, (is_bf16<T>::value && HD <= 64) ? (R == 1 ? 3 : 2) : 1) void attn_cand_tiles_kernel(CandAttnParams p) {
+  const int nt = (p.T + 63) / 64, n_inner = (p.H / p.KV / R) * nt;
+  const int grp = blockIdx.x / n_inner, inner = blockIdx.x % n_inner;
+  const int b = grp / p.KV, kvh = grp % p.KV, h0 = kvh * (p.H / p.KV) + (inner / nt) * R, qt = inner % nt;
+  const int sg = p.tile_seg[b * nt + qt];
+  if (sg < 0 || sg >= p.n_seg) return;                       // (uniform: whole workgroup)
+  const int* d = p.seg + 4 * sg;
+  const int ft = d[2];
+  if (ft < 0 || ft > qt) return;
+  const int nq = min(64 * ft + 2 * max(d[3], 0), p.T);       // first token of the row behind the segment's candidates
+  if (qt * 64 >= nq) return;
+  const int nh2 = 2 * min(max(d[1], 0), p.Tc / 2);           // cached tokens of the segment's slot
+  const int slot = min(max(d[0], 0), p.n_slots - 1);
+  attn_cand_body<T, HD, R>(p, b, kvh, h0, qt, nq, nh2, slot);
+}
+
 template <typename T, int HD>
 static int attn_cand_hd(const CandAttnParams& p, hipStream_t s) {
   using C = ACfg<T, HD>;
@@ -1712,6 +1744,20 @@ static int attn_cand_hd(const CandAttnParams& p, hipStream_t s) {
     set = true;
   }
   const int nt = (p.T + 63) / 64;
+  if (p.tile_seg) {   // packed rows: the same grid, the per-tile form
+    static bool set_t[64] = {};   // (the attribute belongs to the device: once per device of this process)
+    int dev = 0;
+    HIP_CHECK(hipGetDevice(&dev));
+    if (dev < 0 || dev >= 64 || !set_t[dev]) {
+      HIP_CHECK(hipFuncSetAttribute((const void*)attn_cand_tiles_kernel<T, HD, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm));
+      HIP_CHECK(hipFuncSetAttribute((const void*)attn_cand_tiles_kernel<T, HD, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm));
+      if (dev >= 0 && dev < 64) set_t[dev] = true;
+    }
+    if (p.H / p.KV == 2 && HD <= 64) hipLaunchKernelGGL((attn_cand_tiles_kernel<T, HD, 2>), dim3(nt * (p.H / 2) * p.rows), dim3(256), sm, s, p);
+    else hipLaunchKernelGGL((attn_cand_tiles_kernel<T, HD, 1>), dim3(nt * p.H * p.rows), dim3(256), sm, s, p);
+    HIP_CHECK(hipGetLastError());
+    return RSYS_OK;
+  }
   if (p.H / p.KV == 2 && HD <= 64) hipLaunchKernelGGL((attn_cand_kernel<T, HD, 2>), dim3(nt * (p.H / 2) * p.rows), dim3(256), sm, s, p);   // (heads per workgroup: as attn_heads_per_wg)
   else hipLaunchKernelGGL((attn_cand_kernel<T, HD, 1>), dim3(nt * p.H * p.rows), dim3(256), sm, s, p);
   HIP_CHECK(hipGetLastError());
@@ -1722,6 +1768,7 @@ int launch_attn_cand(const CandAttnParams& p_in, hipStream_t s) {
   CandAttnParams p = p_in;
   if (p.Tc == 0) p.Tc = p.T;
   ARG_CHECK(p.rows >= 1 && p.n_slots >= 1, "candidate attention: rows and slots");
+  ARG_CHECK(p.tile_seg ? (p.seg != nullptr && p.n_seg >= 1) : (p.slot && p.n_hist && p.n_cand), "candidate attention: row arrays, or a tile map with its segment table");
   ARG_CHECK(p.Tc >= p.T && p.Tc % 8 == 0 && p.Tc <= 4096, "candidate attention: the slot stride must be a multiple of 8, >= T and <= 4096");
   ARG_CHECK(p.T % 8 == 0 && p.T <= 4096, "candidate attention: T must be a multiple of 8 and <= 4096");
   ARG_CHECK(p.H % p.KV == 0, "candidate attention: H % KV");
@@ -1767,6 +1814,39 @@ int launch_rank_cache_copy(const T* qkv, long long ld, int kv_off, int kvw, int 
 }
 template int launch_rank_cache_copy<bf16>(const bf16*, long long, int, int, int, int, int, const int*, const int*, int, bf16*, hipStream_t);
 template int launch_rank_cache_copy<float>(const float*, long long, int, int, int, int, int, const int*, const int*, int, float*, hipStream_t);
+
+// Packed store rows (rsys_rank_cache_store_packed): per segment descriptor seg[i] = (row, first column c0, n_hist, slot), K | V of
+// tokens [2 c0, 2 c0 + 2 n_hist) of the row -> rows [0, 2 n_hist) of the slot, in 16-byte chunks; grid (chunks, segments).  A descriptor that
+// does not fit the rows or the cache copies nothing.
+template <typename T>
+__global__ __launch_bounds__(256) void rank_cache_copy_segments_kernel(const T* __restrict__ qkv, long long ld, int kv_off, int kvw, int T_len, int T_slot, int rows,
+                                                                       const int* __restrict__ seg, int n_slots, T* __restrict__ cache) {
+  const int* d = seg + 4 * blockIdx.y;
+  const int r = d[0], c0 = d[1], nh = d[2], sl = d[3];
+  if (r < 0 || r >= rows || sl < 0 || sl >= n_slots || c0 < 0 || nh <= 0) return;
+  if (2 * ((long long)c0 + nh) > T_len || 2 * (long long)nh > T_slot) return;
+  const int cpr = kvw * (int)sizeof(T) / 16;
+  const long long n = (long long)2 * nh * cpr;
+  for (long long c = (long long)blockIdx.x * 256 + threadIdx.x; c < n; c += (long long)gridDim.x * 256) {
+    const long long tok = c / cpr; const int ch = (int)(c % cpr);
+    const uint4 v = *(const uint4*)((const unsigned char*)(qkv + ((long long)r * T_len + 2 * c0 + tok) * ld + kv_off) + 16 * ch);
+    *(uint4*)((unsigned char*)(cache + ((long long)sl * T_slot + tok) * kvw) + 16 * ch) = v;
+  }
+}
+template <typename T>
+int launch_rank_cache_copy_segments(const T* qkv, long long ld, int kv_off, int kvw, int T_len, int T_slot, int rows, const int* seg, int n_seg, int n_slots, T* cache,
+                                    hipStream_t s) {
+  ARG_CHECK(T_slot >= T_len, "ranking cache: rows longer than a slot");
+  ARG_CHECK(rows >= 1 && n_seg >= 1 && n_seg <= 65535 && n_slots >= 1 && seg != nullptr, "ranking cache: rows, segments and slots");
+  ARG_CHECK((kvw * sizeof(T)) % 16 == 0 && (kv_off * sizeof(T)) % 16 == 0 && (ld * sizeof(T)) % 16 == 0, "ranking cache: 16-byte row alignment");
+  const int cpr = kvw * (int)sizeof(T) / 16;
+  const int gx = (int)std::min<long long>(((long long)T_len * cpr + 255) / 256, 64);
+  hipLaunchKernelGGL((rank_cache_copy_segments_kernel<T>), dim3(gx, n_seg), dim3(256), 0, s, qkv, ld, kv_off, kvw, T_len, T_slot, rows, seg, n_slots, cache);
+  HIP_CHECK(hipGetLastError());
+  return RSYS_OK;
+}
+template int launch_rank_cache_copy_segments<bf16>(const bf16*, long long, int, int, int, int, int, const int*, int, int, bf16*, hipStream_t);
+template int launch_rank_cache_copy_segments<float>(const float*, long long, int, int, int, int, int, const int*, int, int, float*, hipStream_t);
 
 }  // namespace rsys
 

@@ -89,6 +89,8 @@ int32_t rsys_batch_row_length(rsys_model* h, int32_t* row_len_out) {
 }
 int32_t rsys_serving_pack_set(rsys_model* h, int32_t on) { CHECK_HANDLE(h); h->m->serving_pack = on != 0; return RSYS_OK; }
 int32_t rsys_serving_pack_get(rsys_model* h, int32_t* on_out) { CHECK_HANDLE(h); ARG_CHECK(on_out, "null"); *on_out = h->m->serving_pack ? 1 : 0; return RSYS_OK; }
+int32_t rsys_serving_pack_ranking_set(rsys_model* h, int32_t on) { CHECK_HANDLE(h); h->m->serving_pack_ranking = on != 0; return RSYS_OK; }
+int32_t rsys_serving_pack_ranking_get(rsys_model* h, int32_t* on_out) { CHECK_HANDLE(h); ARG_CHECK(on_out, "null"); *on_out = h->m->serving_pack_ranking ? 1 : 0; return RSYS_OK; }
 int32_t rsys_serving_trim_set(rsys_model* h, int32_t on) { CHECK_HANDLE(h); h->m->serving_trim = on != 0; return RSYS_OK; }
 int32_t rsys_serving_trim_get(rsys_model* h, int32_t* on_out) { CHECK_HANDLE(h); ARG_CHECK(on_out, "null"); *on_out = h->m->serving_trim ? 1 : 0; return RSYS_OK; }
 int32_t rsys_batch_prefetch(rsys_model* h, const rsys_batch* b) { CHECK_HANDLE(h); return model_batch_prefetch(h->m, b); }
@@ -345,6 +347,14 @@ int32_t rsys_rank_cache_store(rsys_model* h, const int32_t* row_adapter, const i
 int32_t rsys_rank_cache_candidates(rsys_model* h, const int32_t* row_adapter, const int32_t* slot, const int32_t* n_cand, float* out) {
   CHECK_HANDLE(h);
   return model_rank_cache_candidates(h->m, row_adapter, slot, n_cand, out);
+}
+int32_t rsys_rank_cache_store_packed(rsys_model* h, const int32_t* seg_adapter, int32_t n_seg, const int32_t* seg) {
+  CHECK_HANDLE(h);
+  return model_rank_cache_store_packed(h->m, seg_adapter, n_seg, seg);
+}
+int32_t rsys_rank_cache_candidates_packed(rsys_model* h, const int32_t* seg_adapter, int32_t n_seg, const int32_t* seg, float* out) {
+  CHECK_HANDLE(h);
+  return model_rank_cache_candidates_packed(h->m, seg_adapter, n_seg, seg, out);
 }
 int32_t rsys_rank_cache_get(rsys_model* h, int32_t layer, int32_t slot, void* out, int64_t bytes) {
   CHECK_HANDLE(h);
@@ -1059,6 +1069,74 @@ int32_t rsys_op_attention_cached(int32_t dtype, int32_t rows, int32_t T, int32_t
   const int rc = dtype == RSYS_DTYPE_BF16 ? launch_attn_cand<bf16>(p, nullptr) : launch_attn_cand<float>(p, nullptr);
   if (rc) return rc;
   HIP_CHECK(hipDeviceSynchronize());
+  return RSYS_OK;
+}
+
+// attn_cand_tiles_kernel alone: the host's segments (row, first_tile, n_cand, slot, n_hist) are checked (inside their rows, no tile twice, slots
+// and counts in range) and become the kernel's two device tables for the length of the call
+int32_t rsys_op_attention_cached_tiles(int32_t dtype, int32_t rows, int32_t T, int32_t H, int32_t KV, int32_t hd, const void* qkv, const void* cache,
+                                       int32_t n_slots, int32_t Tc, int32_t n_seg, const int32_t* seg, void* O) {
+  switches_parse();
+  ARG_CHECK(dtype == RSYS_DTYPE_BF16 || dtype == RSYS_DTYPE_FP32, "dtype: fp32 or bf16");
+  ARG_CHECK(qkv && cache && seg && O && KV >= 1 && H >= 1 && rows >= 1 && T >= 8 && n_slots >= 1, "null or empty");
+  if (Tc == 0) Tc = T;
+  const int nt = (T + 63) / 64;
+  ARG_CHECK(n_seg >= 1 && n_seg <= rows * nt, "1 <= n_seg <= rows x ceil(T / 64)");
+  std::vector<int> tab((size_t)4 * n_seg + (size_t)rows * nt, -1);
+  for (int i = 0; i < n_seg; ++i) {
+    const int r = seg[5 * i], ft = seg[5 * i + 1], nc = seg[5 * i + 2], sl = seg[5 * i + 3], nh = seg[5 * i + 4];
+    ARG_CHECK(r >= 0 && r < rows && ft >= 0 && nc >= 1 && 64 * (long long)ft + 2 * (long long)nc <= T, "segment outside its row");
+    ARG_CHECK(sl >= 0 && sl < n_slots && nh >= 0 && 2 * nh <= Tc, "segment's slot or n_hist out of range");
+    for (int t = ft; t < ft + (2 * nc + 63) / 64; ++t) {
+      ARG_CHECK(tab[(size_t)4 * n_seg + (size_t)r * nt + t] < 0, "segments overlap");
+      tab[(size_t)4 * n_seg + (size_t)r * nt + t] = i;
+    }
+    tab[4 * i] = sl; tab[4 * i + 1] = nh; tab[4 * i + 2] = ft; tab[4 * i + 3] = nc;
+  }
+  int* d_tab = nullptr;
+  HIP_CHECK(hipMalloc((void**)&d_tab, tab.size() * 4));
+  hipError_t e = hipMemcpy(d_tab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice);
+  int rc = RSYS_OK;
+  if (e == hipSuccess) {
+    CandAttnParams p{};
+    p.rows = rows; p.T = T; p.Tc = Tc; p.H = H; p.KV = KV; p.hd = hd;
+    p.qkv = qkv; p.ld = (long long)(H + 2 * KV) * hd; p.cache = cache; p.n_slots = n_slots;
+    p.seg = d_tab; p.tile_seg = d_tab + 4 * n_seg; p.n_seg = n_seg; p.o = O; p.ldo = (long long)H * hd;
+    rc = dtype == RSYS_DTYPE_BF16 ? launch_attn_cand<bf16>(p, nullptr) : launch_attn_cand<float>(p, nullptr);
+    e = hipDeviceSynchronize();
+  }
+  (void)hipFree(d_tab);
+  if (rc) return rc;
+  HIP_CHECK(e);
+  return RSYS_OK;
+}
+
+// rank_cache_copy_segments_kernel alone: the host's descriptors (row, first column, n_hist, slot) are checked against the rows and the cache
+int32_t rsys_op_rank_cache_copy_segments(int32_t dtype, int32_t rows, int32_t T, int32_t H, int32_t KV, int32_t hd, const void* qkv, void* cache,
+                                         int32_t n_slots, int32_t Tc, int32_t n_seg, const int32_t* seg) {
+  switches_parse();
+  ARG_CHECK(dtype == RSYS_DTYPE_BF16 || dtype == RSYS_DTYPE_FP32, "dtype: fp32 or bf16");
+  ARG_CHECK(qkv && cache && seg && KV >= 1 && H >= 1 && hd >= 1 && rows >= 1 && T >= 2 && n_slots >= 1 && n_seg >= 1 && n_seg <= 65535, "null or empty");
+  if (Tc == 0) Tc = T;
+  for (int i = 0; i < n_seg; ++i) {
+    const int r = seg[4 * i], c0 = seg[4 * i + 1], nh = seg[4 * i + 2], sl = seg[4 * i + 3];
+    ARG_CHECK(r >= 0 && r < rows && c0 >= 0 && nh >= 0 && 2 * ((long long)c0 + nh) <= T && 2 * (long long)nh <= Tc, "segment outside its row or longer than a slot");
+    ARG_CHECK(sl >= 0 && sl < n_slots, "slot outside the cache");
+  }
+  int* d_seg = nullptr;
+  HIP_CHECK(hipMalloc((void**)&d_seg, (size_t)4 * n_seg * 4));
+  hipError_t e = hipMemcpy(d_seg, seg, (size_t)4 * n_seg * 4, hipMemcpyHostToDevice);
+  int rc = RSYS_OK;
+  if (e == hipSuccess) {
+    const long long ld = (long long)(H + 2 * KV) * hd;
+    rc = dtype == RSYS_DTYPE_BF16
+             ? launch_rank_cache_copy_segments<bf16>((const bf16*)qkv, ld, H * hd, 2 * KV * hd, T, Tc, rows, d_seg, n_seg, n_slots, (bf16*)cache, nullptr)
+             : launch_rank_cache_copy_segments<float>((const float*)qkv, ld, H * hd, 2 * KV * hd, T, Tc, rows, d_seg, n_seg, n_slots, (float*)cache, nullptr);
+    e = hipDeviceSynchronize();
+  }
+  (void)hipFree(d_seg);
+  if (rc) return rc;
+  HIP_CHECK(e);
   return RSYS_OK;
 }
 

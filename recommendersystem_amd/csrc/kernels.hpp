@@ -248,6 +248,10 @@ struct CandAttnParams {
   int Tc;                               // tokens per cache slot (the slot stride); 0: T.  T < Tc: rows shorter than the slots (a trimmed batch)
   const int *slot, *n_hist, *n_cand;    // [rows], device
   void* o; long long ldo;               // [rows * T][H * hd]
+  // packed rows (attn_cand_tiles_kernel), instead of the three row arrays: tile_seg [rows][ceil(T / 64)] = the segment of every
+  // 64-token tile or -1 (a dead tile: no work, O untouched), seg [n_seg][4] = (slot, n_hist, first_tile, n_cand), both on the device.  A
+  // segment is a run of whole tiles of one row; its candidate j sits at tokens 64 first_tile + 2 j, + 1.  nullptr: the row form.
+  const int *tile_seg, *seg; int n_seg;
 };
 template <typename T> int launch_attn_cand(const CandAttnParams& p, hipStream_t s);
 // K | V of tokens [0, 2 n_hist[r]) of row r of qkv -> cache slot slot[r] (one layer)
@@ -255,6 +259,10 @@ template <typename T> int launch_attn_cand(const CandAttnParams& p, hipStream_t 
 // (T_len: tokens per row of qkv; T_slot: tokens per cache slot, >= T_len)
 template <typename T> int launch_rank_cache_copy(const T* qkv, long long ld, int kv_off, int kvw, int T_len, int T_slot, int rows, const int* slot, const int* n_hist,
                                                  int n_slots, T* cache, hipStream_t s);
+// K | V of tokens [2 c0, 2 c0 + 2 n_hist) of row r of qkv -> rows [0, 2 n_hist) of cache slot s, per descriptor seg[i] = (r, c0, n_hist, s) (device,
+// [n_seg][4]; packed store rows).  Nothing else of the cache is written.
+template <typename T> int launch_rank_cache_copy_segments(const T* qkv, long long ld, int kv_off, int kvw, int T_len, int T_slot, int rows, const int* seg, int n_seg,
+                                                          int n_slots, T* cache, hipStream_t s);
 template <typename T> int launch_attn_fwd(const AttnParams& p, hipStream_t s);
 template <typename T> int launch_attn_bwd(const AttnParams& p, hipStream_t s);
 

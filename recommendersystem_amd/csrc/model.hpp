@@ -97,6 +97,7 @@ struct Model {
   // forwards of the render pipelines; every ordinary upload, swap and device-assembled batch sets S = Sa.
   int Sa = 0, Ta = 0;
   bool serving_pack = false;      // rsys_serving_pack_set: the retrieval stage of the two render entry points packs several users into a row
+  bool serving_pack_ranking = false;   // rsys_serving_pack_ranking_set: rsys_render_request_full packs its K/V-cache store rows
   bool serving_trim = false;      // rsys_serving_trim_set: the two render entry points run every forward at its longest live row
   int64_t fwd_tokens = 0;         // tokens the last forward_trunk ran over (rsys_debug_get "forward.tokens")
   int64_t n_decay = 0, n_total = 0;
@@ -273,7 +274,7 @@ struct Model {
   // every row's own update to q and v; every other pass leaves it null and launches what it always has
   AdapterBank* bank = nullptr;
   const int* bank_rows = nullptr;
-  const int* bank_tiles = nullptr;      // packed rows: one slot or -1 per 64-token tile, [rows][ceil(T / 64)]; non-null only inside rsys_infer_select_tiles
+  const int* bank_tiles = nullptr;      // packed rows: one slot or -1 per 64-token tile, [rows][ceil(T / 64)]; non-null only inside rsys_infer_select_tiles and the packed cache calls (4zd)
   // training through the bank: true only inside rsys_adapter_forward_backward.  The pass then treats the trunk as frozen
   // (the `ft` paths of the forward, heads and backward: dx chain only), keeps La per layer, draws the LoRA dropout inside the bank's
   // kernels and sends the few small gradients those paths still write (norm gains, rating-head biases) to bank_sink, never to G
@@ -292,6 +293,12 @@ struct Model {
   void* rcache = nullptr; int rc_slots = 0; std::vector<int> rc_nhist;
   int* rc_rows = nullptr;               // [3][rows_max]
   int rc_mode = 0;
+  // packed rows: rc_nseg is non-zero only inside rsys_rank_cache_store_packed / _candidates_packed, whose store copy then runs per
+  // segment descriptor and whose candidate attention per tile.  rc_seg (device, sized at reserve for max_rows x ceil(S / 32) segments): the
+  // segment table [max_seg][4] -- store: (row, first column, n_hist, slot); candidates: (slot, n_hist, first tile, n_cand) -- and behind it
+  // the candidate rows' tile -> segment map [rows][ceil(T / 64)] (-1: a dead tile)
+  int* rc_seg = nullptr;
+  int rc_nseg = 0;
 };
 
 struct Optimizer {
@@ -374,6 +381,8 @@ int model_infer_device(Model* m, int task, const int32_t* row_adapter, const int
 int model_rank_cache_reserve(Model* m, int n_slots);
 int model_rank_cache_store(Model* m, const int32_t* row_adapter, const int32_t* n_hist, const int32_t* slot);
 int model_rank_cache_candidates(Model* m, const int32_t* row_adapter, const int32_t* slot, const int32_t* n_cand, float* out);
+int model_rank_cache_store_packed(Model* m, const int32_t* seg_adapter, int n_seg, const int32_t* seg);                    // seg [n_seg][4] = (row, first column, n_hist, slot)
+int model_rank_cache_candidates_packed(Model* m, const int32_t* seg_adapter, int n_seg, const int32_t* seg, float* out);   // seg [n_seg][4] = (row, first column, n_cand, slot)
 int model_rank_cache_get(Model* m, int layer, int slot, void* out, int64_t bytes);   // a slot's K | V rows of one layer, [2 n_hist][2 KV hd], compute dtype
 void rank_cache_free(Model* m);
 // the two passes without a host wait, for a caller whose rows (and, for the candidates, RoPE positions d_pos [rows][2S], selection d_sel
@@ -382,6 +391,9 @@ void rank_cache_free(Model* m);
 int rank_cache_store_rows(Model* m, const int32_t* row_adapter, const int32_t* n_hist, const int32_t* slot, int* tab);
 int rank_cache_candidates_rows(Model* m, const int32_t* row_adapter, const int32_t* slot, const int32_t* n_cand, int* tab, int* d_pos,
                                const int* d_sel, int64_t ntok, float* d_out);
+// the packed store pass without a host wait: seg (host, [n_seg][4] = (row, first column, n_hist, slot)) and seg_adapter are read by
+// stream-ordered copies; d_pos [rows][2 row_len] (device) holds the tokens' RoPE positions, relative to their segments
+int rank_cache_store_packed_rows(Model* m, const int32_t* seg_adapter, int n_seg, const int32_t* seg, int* d_pos);
 template <typename T> int rank_cache_store_layer(Model* m, int l, const T* qkv);      // forward_trunk, rc_mode == 1
 template <typename T> int rank_cache_attention(Model* m, int l, const T* qkv, T* O);  // forward_trunk, rc_mode == 2
 // the inference forward over the resident batch with the tokens to report (n_sel flat indices) and the rating head's values on the device

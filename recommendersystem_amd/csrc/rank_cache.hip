@@ -18,10 +18,13 @@ static int rc_check_model(Model* m) {
 static inline size_t rc_kvw(const Model* m) { return (size_t)2 * m->KV * m->hd; }                    // values of a cached token: K | V
 static inline size_t rc_layer_elems(const Model* m) { return (size_t)m->rc_slots * m->Ta * rc_kvw(m); }   // (the slot stride is the allocated row: a slot serves rows of any length)
 
+static inline int rc_max_seg(const Model* m) { return m->rows_max * ((m->Sa + 31) / 32); }   // segments of one packed forward: one per 64-token tile at most
+
 void rank_cache_free(Model* m) {
   if (m->rcache) (void)hipFree(m->rcache);
   if (m->rc_rows) (void)hipFree(m->rc_rows);
-  m->rcache = nullptr; m->rc_rows = nullptr; m->rc_slots = 0; m->rc_nhist.clear(); m->rc_mode = 0;
+  if (m->rc_seg) (void)hipFree(m->rc_seg);
+  m->rcache = nullptr; m->rc_rows = nullptr; m->rc_seg = nullptr; m->rc_slots = 0; m->rc_nhist.clear(); m->rc_mode = 0; m->rc_nseg = 0;
 }
 
 int model_rank_cache_reserve(Model* m, int n_slots) {
@@ -53,7 +56,14 @@ int model_rank_cache_reserve(Model* m, int n_slots) {
     set_error("ranking cache: no memory for the row descriptors");
     return RSYS_ERR_STATE;
   }
-  m->rcache = p; m->rc_rows = rows; m->rc_slots = n_slots;
+  // packed rows: a segment table [max_seg][4] and the candidate rows' tile map [rows_max][ceil(Sa / 32)] behind it
+  int* segs = nullptr;
+  if (hipMalloc((void**)&segs, (size_t)5 * rc_max_seg(m) * 4) != hipSuccess) {
+    (void)hipGetLastError(); (void)hipFree(p); (void)hipFree(rows);
+    set_error("ranking cache: no memory for the segment tables");
+    return RSYS_ERR_STATE;
+  }
+  m->rcache = p; m->rc_rows = rows; m->rc_seg = segs; m->rc_slots = n_slots;
   m->rc_nhist.assign((size_t)n_slots, -1);
   return RSYS_OK;
 }
@@ -61,8 +71,11 @@ int model_rank_cache_reserve(Model* m, int n_slots) {
 template <typename T>
 int rank_cache_store_layer(Model* m, int l, const T* qkv) {
   tic(m, "hbm_rank_cache_store", 2.0 * sizeof(T) * m->cur_rows * m->T * (double)rc_kvw(m));
-  const int rc = launch_rank_cache_copy<T>(qkv, m->Nqkv, m->H * m->hd, (int)rc_kvw(m), m->T, m->Ta, m->cur_rows, m->rc_rows, m->rc_rows + m->rows_max, m->rc_slots,
-                                           (T*)m->rcache + (size_t)l * rc_layer_elems(m), m->stream);
+  T* const cache = (T*)m->rcache + (size_t)l * rc_layer_elems(m);
+  const int rc = m->rc_nseg   // (packed store rows: one copy per segment descriptor)
+                     ? launch_rank_cache_copy_segments<T>(qkv, m->Nqkv, m->H * m->hd, (int)rc_kvw(m), m->T, m->Ta, m->cur_rows, m->rc_seg, m->rc_nseg, m->rc_slots, cache, m->stream)
+                     : launch_rank_cache_copy<T>(qkv, m->Nqkv, m->H * m->hd, (int)rc_kvw(m), m->T, m->Ta, m->cur_rows, m->rc_rows, m->rc_rows + m->rows_max, m->rc_slots,
+                                                 cache, m->stream);
   toc(m);
   return rc;
 }
@@ -74,6 +87,7 @@ int rank_cache_attention(Model* m, int l, const T* qkv, T* O) {
   p.cache = (const T*)m->rcache + (size_t)l * rc_layer_elems(m); p.n_slots = m->rc_slots;
   p.slot = m->rc_rows; p.n_hist = m->rc_rows + m->rows_max; p.n_cand = m->rc_rows + 2 * m->rows_max;
   p.o = O; p.ldo = m->D;
+  if (m->rc_nseg) { p.seg = m->rc_seg; p.tile_seg = m->rc_seg + 4 * rc_max_seg(m); p.n_seg = m->rc_nseg; }   // packed candidate rows: slot per tile
   tic(m, "attn_cand");
   const int rc = launch_attn_cand<T>(p, m->stream);
   toc(m);
@@ -204,6 +218,161 @@ int model_rank_cache_candidates(Model* m, const int32_t* row_adapter, const int3
     return RSYS_OK;
   };
   const int rc = run();
+  if (rc != RSYS_OK) { (void)hipStreamSynchronize(s); return rc; }   // (the copies above read this call's host vectors)
+  HIP_CHECK(hipMemcpy(out, m->delta, (size_t)ntok * 4, hipMemcpyDeviceToHost));   // (out is written only by a call that succeeded)
+  return RSYS_OK;
+}
+
+// ------------------------------------------------------------------ packed rows
+// Several users per row, each in a segment of whole 64-token tiles.  The two calls below check the caller's descriptors on the host, write
+// the device tables (segments, tile map, RoPE positions, selection) and run the passes above with rc_nseg set: the trunk is the same, the
+// copy and the candidate attention take their per-segment / per-tile forms, the adapter bank its per-tile form (adapter_bind_tiles).
+static int rc_check_packed(Model* m, int n_seg, const int32_t* seg) {
+  RC(rc_check_model(m));
+  ARG_CHECK(m->cfg.finetune == 0, "ranking cache, packed rows: a base model (finetune = 0)");
+  ARG_CHECK(m->rcache != nullptr, "ranking cache: nothing reserved (rsys_rank_cache_reserve)");
+  ARG_CHECK(m->cur_rows > 0, "no batch uploaded");
+  ARG_CHECK(seg != nullptr && n_seg >= 1 && n_seg <= rc_max_seg(m), "ranking cache, packed rows: 1 <= n_seg <= max_rows x ceil(S / 32) descriptors");
+  return RSYS_OK;
+}
+// marks the tiles [c0 / 32, ceil((c0 + n) / 32)) of `row` in used ([rows][nt]); a descriptor off a tile boundary, across the row's end or on a
+// taken tile is refused
+static int rc_place_segment(Model* m, std::vector<int>& used, int nt, int row, int c0, int n, int id) {
+  ARG_CHECK(row >= 0 && row < m->cur_rows, "ranking cache, packed rows: row outside the resident batch");
+  ARG_CHECK(c0 >= 0 && c0 % 32 == 0, "ranking cache, packed rows: a segment starts at a column that is a multiple of 32");
+  ARG_CHECK((long long)c0 + n <= m->S, "ranking cache, packed rows: a segment must end inside its row");
+  for (int t = c0 / 32; t < (c0 + n + 31) / 32; ++t) {
+    ARG_CHECK(used[(size_t)row * nt + t] < 0, "ranking cache, packed rows: segments overlap");
+    used[(size_t)row * nt + t] = id;
+  }
+  return RSYS_OK;
+}
+// seg_adapter [n_seg] (or null) -> the per-tile binding, every slot on the tiles `used` gives its segment
+static int rc_bind_segments(Model* m, const int32_t* seg_adapter, int n_seg, const std::vector<int>& used, int nt) {
+  if (!seg_adapter) return RSYS_OK;
+  const int nta = (m->Sa + 31) / 32;
+  for (int i = 0; i < n_seg; ++i) ARG_CHECK(seg_adapter[i] >= -1 && seg_adapter[i] < RSYS_ADAPTER_SLOTS, "seg_adapter entries must be in [-1, RSYS_ADAPTER_SLOTS)");
+  std::vector<int32_t> tiles((size_t)m->cur_rows * nta, -1);
+  for (int r = 0; r < m->cur_rows; ++r)
+    for (int t = 0; t < nt; ++t)
+      if (used[(size_t)r * nt + t] >= 0) tiles[(size_t)r * nta + t] = seg_adapter[used[(size_t)r * nt + t]];
+  return adapter_bind_tiles(m, tiles.data());   // (range and completeness of every entry; copies the map before it returns)
+}
+
+// The packed store pass over the resident batch, whose rows were uploaded (rsys_rank_cache_store_packed) or assembled on the device
+// (rsys_render_request_full under rsys_serving_pack_ranking_set).  d_pos [rows][2 row_len] (device): the tokens' RoPE positions -- event i of
+// a segment at (2 i, 2 i + 1).  `seg` (host) is read by a stream-ordered copy, as the adapter map is: it stays as it is until the stream has
+// passed this call.  No host wait on success.
+int rank_cache_store_packed_rows(Model* m, const int32_t* seg_adapter, int n_seg, const int32_t* seg, int* d_pos) {
+  RC(rc_check_packed(m, n_seg, seg));
+  ARG_CHECK(d_pos != nullptr, "ranking cache, packed rows: null positions");
+  const int rows = m->cur_rows, nt = (m->S + 31) / 32;
+  std::vector<int> used((size_t)rows * nt, -1);
+  std::vector<char> seen((size_t)m->rc_slots, 0);
+  for (int i = 0; i < n_seg; ++i) {
+    const int row = seg[4 * i], c0 = seg[4 * i + 1], nh = seg[4 * i + 2], sl = seg[4 * i + 3];
+    ARG_CHECK(nh >= 0 && nh <= m->S, "ranking cache: n_hist must be in [0, the resident rows' length]");
+    RC(rc_place_segment(m, used, nt, row, c0, nh, i));
+    ARG_CHECK(sl >= 0 && sl < m->rc_slots, "ranking cache: slot outside the reserve");
+    ARG_CHECK(!seen[sl], "ranking cache: the slots of one store call must be distinct");
+    seen[sl] = 1;
+  }
+  HIP_CHECK(hipSetDevice(m->device));
+  RC(rc_bind_segments(m, seg_adapter, n_seg, used, nt));
+  int* const saved_pos = m->d_rope_pos; const bool saved_has = m->has_rope_pos;
+  auto run = [&]() -> int {
+    HIP_CHECK(hipMemcpyAsync(m->rc_seg, seg, (size_t)4 * n_seg * 4, hipMemcpyHostToDevice, m->stream));
+    m->d_rope_pos = d_pos; m->has_rope_pos = true;
+    m->rc_mode = 1; m->rc_nseg = n_seg;
+    RC(m->bf16_mode ? infer_trunk<bf16>(m) : infer_trunk<float>(m));
+    return RSYS_OK;
+  };
+  const int rc = run();
+  m->rc_mode = 0; m->rc_nseg = 0;
+  m->d_rope_pos = saved_pos; m->has_rope_pos = saved_has;
+  adapter_unbind_rows(m);
+  if (rc != RSYS_OK) (void)hipStreamSynchronize(m->stream);   // (the copy above reads the caller's host array)
+  // (a failed pass may have written some layers of the slots: they no longer hold a history)
+  for (int i = 0; i < n_seg; ++i) m->rc_nhist[seg[4 * i + 3]] = rc == RSYS_OK ? seg[4 * i + 2] : -1;
+  return rc;
+}
+
+int model_rank_cache_store_packed(Model* m, const int32_t* seg_adapter, int n_seg, const int32_t* seg) {
+  RC(rc_check_packed(m, n_seg, seg));
+  const int rows = m->cur_rows, T = m->T;
+  // a history token runs at its position inside the segment (model.py:470-476); padding keeps the column.  (Segments that do not fit
+  // their rows are refused by the body below, before the positions are read: they are only skipped here.)
+  std::vector<int> pos((size_t)rows * T);
+  for (int r = 0; r < rows; ++r)
+    for (int t = 0; t < T; ++t) pos[(size_t)r * T + t] = t;
+  for (int i = 0; i < n_seg; ++i) {
+    const int row = seg[4 * i], c0 = seg[4 * i + 1], nh = seg[4 * i + 2];
+    if (row < 0 || row >= rows || c0 < 0 || nh < 0 || (long long)c0 + nh > m->S) continue;
+    for (int j = 0; j < 2 * nh; ++j) pos[(size_t)row * T + 2 * c0 + j] = j;
+  }
+  HIP_CHECK(hipSetDevice(m->device));
+  int* const d_pos = m->rc_rows + 3 * m->rows_max;
+  HIP_CHECK(hipMemcpyAsync(d_pos, pos.data(), pos.size() * 4, hipMemcpyHostToDevice, m->stream));
+  const int rc = rank_cache_store_packed_rows(m, seg_adapter, n_seg, seg, d_pos);
+  const hipError_t e = hipStreamSynchronize(m->stream);   // (also on a refusal: the copy above reads this call's vector)
+  if (rc != RSYS_OK) return rc;
+  if (e != hipSuccess)
+    for (int i = 0; i < n_seg; ++i) m->rc_nhist[seg[4 * i + 3]] = -1;
+  HIP_CHECK(e);
+  return RSYS_OK;
+}
+
+int model_rank_cache_candidates_packed(Model* m, const int32_t* seg_adapter, int n_seg, const int32_t* seg, float* out) {
+  RC(rc_check_packed(m, n_seg, seg));
+  ARG_CHECK(out != nullptr, "ranking cache: null output");
+  const int rows = m->cur_rows, T = m->T, nt = (m->S + 31) / 32;
+  std::vector<int> used((size_t)rows * nt, -1);
+  int64_t ntok = 0;
+  for (int i = 0; i < n_seg; ++i) {
+    const int row = seg[4 * i], c0 = seg[4 * i + 1], nc = seg[4 * i + 2], sl = seg[4 * i + 3];
+    ARG_CHECK(sl >= 0 && sl < m->rc_slots, "ranking cache: slot outside the reserve");
+    ARG_CHECK(m->rc_nhist[sl] >= 0, "ranking cache: slot never stored");
+    ARG_CHECK(m->rc_nhist[sl] <= m->Sa - 1, "ranking cache: candidates run at position n_hist, which must stay below max_sequence_length");
+    ARG_CHECK(nc >= 1 && nc <= m->S, "ranking cache: n_cand must be in [1, the resident rows' length]");
+    RC(rc_place_segment(m, used, nt, row, c0, nc, i));
+    ntok += nc;
+  }
+  HIP_CHECK(hipSetDevice(m->device));
+  // device tables: (slot, n_hist, first_tile, n_cand) per segment, the tile map, the positions (every token of a segment's tiles at
+  // (2 n_hist, 2 n_hist + 1), as a candidate row's; padding keeps the column) and the candidates' action tokens in descriptor order
+  const int max_seg = rc_max_seg(m);
+  std::vector<int> tab((size_t)5 * max_seg, -1), pos((size_t)rows * T), sel((size_t)ntok);
+  for (int r = 0; r < rows; ++r)
+    for (int t = 0; t < T; ++t) pos[(size_t)r * T + t] = t;
+  int64_t k = 0;
+  for (int i = 0; i < n_seg; ++i) {
+    const int row = seg[4 * i], c0 = seg[4 * i + 1], nc = seg[4 * i + 2], sl = seg[4 * i + 3], nh = m->rc_nhist[sl];
+    tab[4 * i] = sl; tab[4 * i + 1] = nh; tab[4 * i + 2] = c0 / 32; tab[4 * i + 3] = nc;
+    for (int c = c0; c < std::min(m->S, 32 * ((c0 + nc + 31) / 32)); ++c) { pos[(size_t)row * T + 2 * c] = 2 * nh; pos[(size_t)row * T + 2 * c + 1] = 2 * nh + 1; }
+    for (int j = 0; j < nc; ++j) sel[k++] = row * T + 2 * (c0 + j) + 1;
+  }
+  for (int r = 0; r < rows; ++r)
+    for (int t = 0; t < nt; ++t) tab[(size_t)4 * max_seg + (size_t)r * nt + t] = used[(size_t)r * nt + t];
+  RC(rc_bind_segments(m, seg_adapter, n_seg, used, nt));
+  int* const d_pos = m->rc_rows + 3 * m->rows_max;
+  int* const d_sel = (int*)m->gf;   // (as rsys_infer_select: room for every token of the batch)
+  int* const saved_pos = m->d_rope_pos; const bool saved_has = m->has_rope_pos;
+  hipStream_t s = m->stream;
+  auto run = [&]() -> int {
+    HIP_CHECK(hipMemcpyAsync(m->rc_seg, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(d_pos, pos.data(), pos.size() * 4, hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(d_sel, sel.data(), sel.size() * 4, hipMemcpyHostToDevice, s));
+    m->d_rope_pos = d_pos; m->has_rope_pos = true;
+    m->rc_mode = 2; m->rc_nseg = n_seg;
+    const float* f = nullptr;
+    RC(m->bf16_mode ? infer_rows_device<bf16>(m, 1, d_sel, ntok, m->delta, &f) : infer_rows_device<float>(m, 1, d_sel, ntok, m->delta, &f));
+    HIP_CHECK(hipStreamSynchronize(s));
+    return RSYS_OK;
+  };
+  const int rc = run();
+  m->rc_mode = 0; m->rc_nseg = 0;
+  m->d_rope_pos = saved_pos; m->has_rope_pos = saved_has;
+  adapter_unbind_rows(m);
   if (rc != RSYS_OK) { (void)hipStreamSynchronize(s); return rc; }   // (the copies above read this call's host vectors)
   HIP_CHECK(hipMemcpy(out, m->delta, (size_t)ntok * 4, hipMemcpyDeviceToHost));   // (out is written only by a call that succeeded)
   return RSYS_OK;

@@ -121,6 +121,31 @@ __global__ void __launch_bounds__(RN_THREADS) unpack_rows_kernel(const SegDesc* 
   }
 }
 
+// Packed store rows (rsys_serving_pack_ranking_set): row blockIdx.x of the resident batch from the segments that lie in it --
+// columns [col0, col0 + cols) are columns [0, cols) of user d.user's kept history row, with mask id 0, RoPE position = the column inside
+// the segment and userid d.userid (1 + the segment's place in the forward); every other column is zero.  The inverse of unpack_rows_kernel.
+__global__ void __launch_bounds__(RN_THREADS) pack_store_rows_kernel(const SegDesc* segs, int n_seg, HistSrc h, int S, BatchDevRows out) {
+  const int r = blockIdx.x;
+  for (int j = threadIdx.x; j < S; j += RN_THREADS) {
+    const long long i = (long long)r * S + j;
+    double time = 0.0;
+    int userid = 0, gender = 0, source = 0, matchedid = 0, status = 0, p = 0;
+    float rating = 0.f, progress = 0.f;
+    for (int k = 0; k < n_seg; ++k) {
+      const SegDesc d = segs[k];
+      if (d.row != r || j < d.col0 || j >= d.col0 + d.cols) continue;
+      const long long q = (long long)d.user * h.stride + (j - d.col0);
+      time = h.time[q]; userid = d.userid; gender = h.gender[q]; source = h.source[q];
+      matchedid = h.matchedid[q]; status = h.status[q]; rating = h.rating[q]; progress = h.progress[q];
+      p = j - d.col0;
+      break;
+    }
+    out.time[i] = time; out.userid[i] = userid; out.tmid[i] = 0; out.gender[i] = gender; out.source[i] = source;
+    out.matchedid[i] = matchedid; out.status[i] = status; out.rating[i] = rating; out.progress[i] = progress;
+    ((int2*)out.rope_pos)[i] = make_int2(2 * p, 2 * p + 1);
+  }
+}
+
 #define RN_LAUNCH_CHECK() HIP_CHECK(hipGetLastError())
 
 // render.jl:447-465 for one group (serve.page_window, clamp included): false when the page starts past the list
@@ -300,12 +325,13 @@ struct Render : RenderArgs {
     std::vector<RowDesc> sd, crows;
   } t;
 
-  Render(Model* model, const RenderArgs& a) : RenderArgs(a), m(model), S(m->Sa), D(m->D), chunk(S - S / 2), RM(m->rows_max), trim(m->serving_trim), pack(m->serving_pack) {}
+  Render(Model* model, const RenderArgs& a) : RenderArgs(a), m(model), S(m->Sa), D(m->D), chunk(S - S / 2), RM(m->rows_max), trim(m->serving_trim), pack(m->serving_pack), pack_rank(m->serving_pack_ranking) {}
 
   // rsys_serving_trim_set: a forward whose longest row has `live` live columns runs at this row length -- whole 64-token attention tiles,
   // clamped to S (serve.trim_length); off: S.  Chunking, waves and slots are planned on S either way.
   const bool trim;
   const bool pack;   // rsys_serving_pack_set: the retrieval stage runs several users per row (retrieval_forward_packed)
+  const bool pack_rank;   // rsys_serving_pack_ranking_set (full only): the K/V-cache store rows hold several users (rank_cached_waves_packed)
   int row_len_for(int live) const { return trim ? std::min(S, (std::max(live, 1) + 31) / 32 * 32) : S; }
 
   // ---- arguments.  Checked here, before anything is enqueued: the request's shape, pagination, groups, offsets' monotonicity, adapter
@@ -396,7 +422,7 @@ struct Render : RenderArgs {
       d_sel = c.take<int>(sel_cap); d_order = c.take<int>(nu);
       cand = c.take<int32_t>((size_t)ng * RN_MAX_RANK);
       d_rows = c.take<RowDesc>(RM); d_store = c.take<RowDesc>(full ? RM : 0); d_win = c.take<Win>(ng);
-      d_segs = c.take<SegDesc>(pack && full ? (size_t)RM * ((S + 31) / 32) : 0);
+      d_segs = c.take<SegDesc>((pack || pack_rank) && full ? (size_t)RM * ((S + 31) / 32) : 0);
       hist.time = c.take<double>(n_hist);
       hist.userid = c.take<int>(n_hist); hist.gender = c.take<int>(n_hist); hist.source = c.take<int>(n_hist);
       hist.matchedid = c.take<int>(n_hist); hist.status = c.take<int>(n_hist);
@@ -707,6 +733,7 @@ struct Render : RenderArgs {
   // The host tables of a wave are read by stream-ordered copies: they stay as they are until the wave's last batch has been waited for.
   int rank_cached_waves() {
     if (cached.empty()) return RSYS_OK;
+    if (pack_rank) return rank_cached_waves_packed();
     t.sd.resize(RM); t.s_nh.resize(RM); t.s_slot.resize(RM); t.s_ad.resize(RM); t.s_tab.resize((size_t)3 * RM); t.c_tab.resize((size_t)3 * RM);
     int cand_forward = 0;
     for (size_t w0 = 0; w0 < cached.size(); w0 += RM) {
@@ -740,6 +767,103 @@ struct Render : RenderArgs {
       }
       for (size_t b0 = 0; b0 < t.crows.size(); b0 += RM)
         RC(rank_wave(WAVE_CACHED, t.crows.data() + b0, t.crow_slot.data() + b0, (int)std::min<size_t>(RM, t.crows.size() - b0), cand_forward++));
+    }
+    return RSYS_OK;
+  }
+
+  // ---- 4. + 5. (full, rsys_serving_pack_ranking_set) the same with packed store rows, serve.rank_cache_pack_plan's store stage: a wave
+  // holds up to rc_slots users (slot = the user's place in the wave); its histories become segments on 32-column boundaries, first-fit
+  // decreasing, ties in user order, rows in the order they were opened, forwards of <= max_rows rows at the trim length of their fullest
+  // row -- if that needs fewer forwards than one history per row at its trim length, or as many and fewer tokens; otherwise one history
+  // per row at column 0.  Either way the rows are cut from the kept history rows by pack_store_rows_kernel and stored through the packed
+  // store body, without a host wait.  The candidate rows, their forwards and rank_scatter_kernel are rank_cached_waves'.
+  // The host tables of a wave are read by stream-ordered copies: every forward has its own, kept until the wave's last batch has been waited for.
+  int rank_cached_waves_packed() {
+    struct Place { int k, row, col0; };                      // user k of the wave at column col0 of row `row` of its forward
+    struct Fwd { int rl = 0, rows = 0; std::vector<Place> at; };
+    struct Tabs { std::vector<SegDesc> desc; std::vector<int32_t> seg, ad; };
+    const int W = std::max(m->rc_slots, 1);
+    t.c_tab.resize((size_t)3 * RM);
+    auto tokens = [](const std::vector<Fwd>& f) { long long n = 0; for (const Fwd& x : f) n += (long long)x.rl * x.rows; return n; };
+    int cand_forward = 0, wave = 0;
+    for (size_t w0 = 0; w0 < cached.size(); w0 += W, ++wave) {
+      const int nw = (int)std::min<size_t>(W, cached.size() - w0);
+      t.crows.clear(); t.crow_slot.clear();
+      std::vector<int> n(nw), order(nw);
+      for (int k = 0; k < nw; ++k) {
+        const RowDesc& cu = cached[w0 + k];
+        n[k] = cu.cpos; order[k] = k;
+        for (int c0 = 0; c0 < cu.ncand; c0 += S) {   // the user's window in rows of <= S candidates
+          RowDesc q = cu;
+          q.cand0 += c0; q.rm0 += c0; q.ncand = std::min(S, cu.ncand - c0);
+          t.crows.push_back(q); t.crow_slot.push_back(k);
+        }
+      }
+      // the two layouts of the store stage
+      std::vector<Fwd> single, packed;
+      for (int k0 = 0; k0 < nw; k0 += RM) {
+        Fwd f; int live = 1;
+        for (int k = k0; k < std::min(nw, k0 + RM); ++k) { f.at.push_back({k, k - k0, 0}); live = std::max(live, n[k]); }
+        f.rows = (int)f.at.size(); f.rl = std::min(S, (live + 31) / 32 * 32);
+        single.push_back(f);
+      }
+      std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return n[a] > n[b]; });
+      struct Row { int taken = 0, end = 0; std::vector<Place> at; };
+      std::vector<Row> prow;
+      for (int k : order) {
+        size_t r = 0;
+        while (r < prow.size() && prow[r].taken + n[k] > S) ++r;
+        if (r == prow.size()) prow.emplace_back();
+        prow[r].at.push_back({k, 0, prow[r].taken});
+        prow[r].end = prow[r].taken + n[k];
+        prow[r].taken += (n[k] + 31) / 32 * 32;
+      }
+      for (size_t r0 = 0; r0 < prow.size(); r0 += RM) {
+        Fwd f; int end = 1;
+        f.rows = (int)std::min<size_t>(RM, prow.size() - r0);
+        for (int r = 0; r < f.rows; ++r) {
+          end = std::max(end, prow[r0 + r].end);
+          for (Place p : prow[r0 + r].at) { p.row = r; f.at.push_back(p); }
+        }
+        f.rl = std::min(S, (end + 31) / 32 * 32);
+        packed.push_back(f);
+      }
+      const bool take_packed = packed.size() < single.size() || (packed.size() == single.size() && tokens(packed) < tokens(single));
+      const std::vector<Fwd>& plan = take_packed ? packed : single;
+      std::vector<Tabs> tabs(plan.size());
+      for (size_t fi = 0; fi < plan.size(); ++fi) {
+        const Fwd& f = plan[fi];
+        Tabs& tb = tabs[fi];
+        for (const Place& p : f.at) {
+          const RowDesc& cu = cached[w0 + p.k];
+          tb.desc.push_back({cu.user, p.row, p.col0, n[p.k], (int)tb.desc.size() + 1});
+          const int32_t sg[4] = {p.row, p.col0, n[p.k], p.k};
+          tb.seg.insert(tb.seg.end(), sg, sg + 4);
+          tb.ad.push_back(slots ? slots[2 * cu.med + 1] : -1);
+        }
+        const int nseg = (int)tb.desc.size();
+        BatchDevRows bd;
+        RC(model_batch_device_begin(m, f.rows, &bd, f.rl));
+        HIP_CHECK(hipMemcpyAsync(d_segs, tb.desc.data(), (size_t)nseg * sizeof(SegDesc), hipMemcpyHostToDevice, s));
+        tic(m, "render_store_rows");
+        pack_store_rows_kernel<<<f.rows, RN_THREADS, 0, s>>>(d_segs, nseg, hist, f.rl, bd);
+        RN_LAUNCH_CHECK();
+        toc(m);
+        R->note_forward(1, f.rows, f.rl);
+        RC(rank_cache_store_packed_rows(m, slots ? tb.ad.data() : nullptr, nseg, tb.seg.data(), bd.rope_pos));   // (no host wait)
+        ++R->forwards[1]; ++R->forwards_full[0];
+        if (keep) {
+          HIP_CHECK(hipStreamSynchronize(s));
+          RC(R->keep_rows("store", bd, f.rows, S, f.rl, std::vector<int>(f.rows, 0)));
+          for (const Place& p : f.at) {
+            const int32_t rec[4] = {cached[w0 + p.k].user, p.k, n[p.k], wave};   // user, slot, events, wave
+            R->put("store.rows", rec, 4);
+          }
+        }
+      }
+      for (size_t b0 = 0; b0 < t.crows.size(); b0 += RM)
+        RC(rank_wave(WAVE_CACHED, t.crows.data() + b0, t.crow_slot.data() + b0, (int)std::min<size_t>(RM, t.crows.size() - b0), cand_forward++));
+      HIP_CHECK(hipStreamSynchronize(s));   // (the wave's host tables go out of scope)
     }
     return RSYS_OK;
   }

@@ -311,6 +311,16 @@ class RecommenderModel:
     def serving_pack(self, on):
         check(lib().rsys_serving_pack_set(self._h, 1 if on else 0))
 
+    def serving_pack_ranking(self, on=None):
+        """rsys_serving_pack_ranking_set: `render_request_full` packs its K/V-cache store rows -- waves of up to the reserved cache slots,
+        several histories per store row where that saves a forward or tokens (`serve.rank_cache_pack_plan`'s store stage).  Sets the
+        switch when `on` is given; returns its state.  Default off."""
+        if on is not None:
+            check(lib().rsys_serving_pack_ranking_set(self._h, 1 if on else 0))
+        state = C.c_int32()
+        check(lib().rsys_serving_pack_ranking_get(self._h, C.byref(state)))
+        return bool(state.value)
+
     @property
     def can_prefetch(self):
         """rsys_batch_prefetch / rsys_batch_swap: the next batch staged and copied beside the running step (replicated table)"""
@@ -459,6 +469,34 @@ class RecommenderModel:
             raise ValueError(f"rank_cache_candidates: {sl.size} slots and {nc.size} candidate counts for {rows} batch rows")
         out = np.empty(int(np.clip(nc, 0, None).sum()), np.float32)
         check(lib().rsys_rank_cache_candidates(self._h, None if ad is None else ad.ctypes.data, sl.ctypes.data, nc.ctypes.data, out.ctypes.data))
+        return out
+
+    def _segments(self, what, segments, adapters):
+        seg = np.ascontiguousarray(np.asarray(segments, np.int32).reshape(-1, 4))
+        if adapters is None:
+            return seg, None
+        ad = np.full(len(seg), int(adapters), np.int32) if np.ndim(adapters) == 0 else np.ascontiguousarray(np.asarray(adapters).reshape(-1), np.int32)
+        if ad.size != len(seg):
+            raise ValueError(f"{what}: {ad.size} adapter slots for {len(seg)} segments")
+        return seg, ad
+
+    def rank_cache_store_packed(self, d, segments, adapters=None, row_len=None):
+        """`rank_cache_store` on packed rows: `segments` = [(row, first_column, n_hist, slot)], each one user's history alone in a run of
+        whole 64-token tiles of row `row` of `d` (first_column a multiple of 32, userid distinct among the segments, token_mask_ids 0);
+        the call runs event i of a segment at position i.  `adapters`: one bank slot per segment (-1 = the base model), one for all, or
+        None.  Slot `slot` then holds what `rank_cache_store` stores from that history in a row of its own."""
+        self._upload_rows(d, row_len)
+        seg, ad = self._segments("rank_cache_store_packed", segments, adapters)
+        check(lib().rsys_rank_cache_store_packed(self._h, None if ad is None else ad.ctypes.data, len(seg), seg.ctypes.data))
+
+    def rank_cache_candidates_packed(self, d, segments, adapters=None, row_len=None):
+        """`rank_cache_candidates` on packed rows: `segments` = [(row, first_column, n_cand, slot)], n_cand candidates at columns
+        first_column + j of row `row` against the history cached in `slot`; several segments may read one slot.  Returns the rating head
+        at the candidates' action tokens, (sum n_cand,) float32, segment after segment."""
+        self._upload_rows(d, row_len)
+        seg, ad = self._segments("rank_cache_candidates_packed", segments, adapters)
+        out = np.empty(int(np.clip(seg[:, 2], 0, None).sum()), np.float32)
+        check(lib().rsys_rank_cache_candidates_packed(self._h, None if ad is None else ad.ctypes.data, len(seg), seg.ctypes.data, out.ctypes.data))
         return out
 
     def rank_cache_get(self, layer, slot, n_hist):

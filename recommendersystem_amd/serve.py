@@ -273,14 +273,89 @@ def rank_cache_plan(n_hist, n_cand, S, max_rows):
     return waves
 
 
-def predict_ranking_full(model, users, medium, trim=False):
+def _plan_segments(lengths, S, max_rows):
+    """One stage of `rank_cache_pack_plan`: segments of `lengths[i]` >= 1 columns into forwards [(row_len, [(segment, row, first_column)])].
+    The packed layout is `pack_plan`'s (first-fit decreasing, ties in order, rows in the order they were opened, forwards of `max_rows`
+    rows at `trim_length` of their fullest row); it is taken only if it needs fewer forwards than one segment per row at its trim
+    length, or as many forwards and fewer tokens.  Otherwise every segment gets a row of its own, at column 0, in segment order."""
+    packed = pack_plan(lengths, S, max_rows)
+    single = [(trim_length(max(lengths[r0:r0 + max_rows]), S), [(r0 + k, k, 0) for k in range(len(lengths[r0:r0 + max_rows]))])
+              for r0 in range(0, len(lengths), max_rows)]
+    tokens = lambda plan: sum(row_len * (1 + max(r for _, r, _ in placed)) for row_len, placed in plan)
+    if len(packed) < len(single) or (len(packed) == len(single) and tokens(packed) < tokens(single)):
+        return packed
+    return single
+
+
+def rank_cache_pack_plan(n_hist, n_cand, S, max_rows, slots):
+    """`rank_cache_plan` with several users per row, as data, for users with `n_hist[i]` in [1, S] history events and
+    `n_cand[i]` >= 0 candidates.  Waves hold at most `slots` users, in user order; slot = the user's place in its wave.  A wave is
+    (stores, candidates): `stores` = forwards (row_len, [(user, row, first_column, n_hist, slot)]) over the wave's histories, `candidates`
+    = forwards (row_len, [(user, row, first_column, first_candidate, n_cand <= S, slot)]) over its candidate lists cut into chunks of at
+    most S.  Segments start on a multiple of 32 columns, lie inside one row and share no 32-column tile; each stage is planned by
+    `_plan_segments`, so where packing saves neither a forward nor tokens the stage is one segment per row at column 0."""
+    n_hist = [int(n) for n in n_hist]; n_cand = [int(n) for n in n_cand]
+    if len(n_hist) != len(n_cand) or any(n < 1 or n > S for n in n_hist) or any(n < 0 for n in n_cand) or slots < 1 or max_rows < 1:
+        raise ValueError(f"rank_cache_pack_plan: 1 <= n_hist <= {S} and n_cand >= 0 per user, slots >= 1, max_rows >= 1")
+    waves = []
+    for u0 in range(0, len(n_hist), slots):
+        users = list(range(u0, min(u0 + slots, len(n_hist))))
+        stores = [(row_len, [(users[k], row, c0, n_hist[users[k]], k) for k, row, c0 in placed])
+                  for row_len, placed in _plan_segments([n_hist[u] for u in users], S, max_rows)]
+        chunks = [(u, u - u0, c, min(S, n_cand[u] - c)) for u in users for c in range(0, n_cand[u], S)]
+        cands = [(row_len, [(chunks[k][0], row, c0, chunks[k][2], chunks[k][3], chunks[k][1]) for k, row, c0 in placed])
+                 for row_len, placed in (_plan_segments([c[3] for c in chunks], S, max_rows) if chunks else [])]
+        waves.append((stores, cands))
+    return waves
+
+
+def _predict_ranking_packed(model, users, medium, full, hists, out, cache_slots):
+    """`predict_ranking_full`'s cached part over the plan of `rank_cache_pack_plan`: every forward at its own trimmed length"""
+    S = model.config["max_sequence_length"]
+    n0 = model.config["vocab_sizes"]["0_matchedid"]
+    key = f"{medium}.ranking"
+    slots = getattr(model, "adapter_slots", None)
+    adapter = slots[key] if slots else None
+    n_slots = min(sum(1 for h in hists if h), int(cache_slots) if cache_slots else 4 * model.max_rows)
+    if getattr(model, "rank_cache_slots", 0) < n_slots:
+        model.rank_cache_reserve(n_slots)
+    plan = rank_cache_pack_plan([len(hists[i]) for i in full], [len(users[i]["ranking_items"]) for i in full], S, model.max_rows, n_slots)
+    vals = {i: np.zeros(len(users[i]["ranking_items"]), np.float32) for i in full}
+    for stores, cands in plan:
+        for row_len, placed in stores:
+            d = _empty_rows(1 + max(p[1] for p in placed), S)
+            for k, (u, row, c0, nh, _) in enumerate(placed):
+                _fill_row(d, row, hists[full[u]], nh, users[full[u]]["user"], n0, False, c0)
+                d["userid"][row, c0:c0 + nh] = k + 1           # (distinct among the segments of the forward: no history sees another)
+            model.rank_cache_store_packed(d, [(row, c0, nh, slot) for _, row, c0, nh, slot in placed], adapters=adapter, row_len=row_len)
+        for row_len, placed in cands:
+            d = _empty_rows(1 + max(p[1] for p in placed), S)
+            for u, row, c0, first, n, _ in placed:
+                who = users[full[u]]
+                seq = [make_item(who["timestamp"], medium, c) for c in who["ranking_items"][first:first + n]]
+                _fill_row(d, row, seq, 0, who["user"], n0, False, c0)
+                d["rope_input_pos"][row, c0:c0 + n] = len(hists[full[u]])     # (as the candidate rows of the unpacked path; the call sets the positions itself)
+            v = model.rank_cache_candidates_packed(d, [(row, c0, n, slot) for _, row, c0, _, n, slot in placed], adapters=adapter, row_len=row_len)
+            at = 0
+            for u, _, _, first, n, _ in placed:
+                vals[full[u]][first:first + n] = v[at:at + n]; at += n
+    for i in full:
+        out[i] = {key: vals[i].tolist()}
+    return out
+
+
+def predict_ranking_full(model, users, medium, trim=False, pack=False, cache_slots=None):
     """`predict(model, users, "ranking", medium)` on the reference's row (embed.py:74-161 with max_user_len = S): every user is ranked
     on its newest S - 1 history events, whatever the number of candidates, instead of the newest S // 2 - 1 that share a row with the
     candidates.  Each history is tokenised and projected once and runs once (one `rank_cache_store` per wave of `max_rows` users);
     the candidates run against the cached K / V in rows of up to S (a user's candidates may span rows, several users' rows share a
     forward).  Users with an empty history go through `predict`, one row per chunk of S - S // 2 candidates as `render` cuts them, so
     their values are what `render` gives today.  Returns what `predict` returns, for any number of candidates.  `trim=True`: every
-    store and candidate forward runs at `trim_length` of its longest row; slots, waves and chunks are unchanged."""
+    store and candidate forward runs at `trim_length` of its longest row; slots, waves and chunks are unchanged.
+    `pack=True` (implies trimming): the users with a history run by `rank_cache_pack_plan` -- several histories per store row, several
+    users' candidate chunks per candidate row, waves of up to `cache_slots` (default 4 x max_rows) users; min(users with a history,
+    that many) cache slots are reserved when the model holds fewer -- which, as every `rank_cache_reserve` of a new size, drops what
+    a caller had stored.  Users with an empty history and users without candidates go the ways they go without it."""
     S = model.config["max_sequence_length"]
     n0 = model.config["vocab_sizes"]["0_matchedid"]
     key = f"{medium}.ranking"
@@ -301,6 +376,8 @@ def predict_ranking_full(model, users, medium, trim=False):
     full = [i for i in full if users[i]["ranking_items"]]
     if not full:
         return out
+    if pack:
+        return _predict_ranking_packed(model, users, medium, full, hists, out, cache_slots)
     slots = getattr(model, "adapter_slots", None)
     adapter = slots[key] if slots else None
     max_rows = model.max_rows
@@ -969,13 +1046,35 @@ def render_full_plan(n_hist, n_cand, S, max_rows):
     return waves, empty
 
 
-def render_full_forwards(n_hist, n_cand, S, max_rows):
-    """(store forwards, candidate forwards, empty-history chunk forwards) of `render_full_plan`: what the library reports as "forwards.full" """
-    waves, empty = render_full_plan(n_hist, n_cand, S, max_rows)
-    return len(waves), sum(len(b) for _, b in waves), -(-len(empty) // max_rows)
+def render_full_forwards(n_hist, n_cand, S, max_rows, pack_store=False, slots=None):
+    """(store forwards, candidate forwards, empty-history chunk forwards) of `render_full_plan`: what the library reports as "forwards.full".
+    `pack_store=True`: what it reports under rsys_serving_pack_ranking_set -- waves of `slots` users with a history (the model's reserved
+    cache slots; default `max_rows`), each wave's store stage planned as `rank_cache_pack_plan` plans it, its candidate rows (chunks of at
+    most S, one per row) in forwards of `max_rows` rows."""
+    if not pack_store:
+        waves, empty = render_full_plan(n_hist, n_cand, S, max_rows)
+        return len(waves), sum(len(b) for _, b in waves), -(-len(empty) // max_rows)
+    slots = max_rows if slots is None else int(slots)
+    hist = [i for i, h in enumerate(n_hist) if h >= 1]
+    empty = [c for i, h in enumerate(n_hist) if h < 1 for c in render_row_plan(n_cand[i], 0, S)]
+    store = cands = 0
+    for w0 in range(0, len(hist), slots):
+        wave = hist[w0:w0 + slots]
+        store += len(_plan_segments([int(n_hist[i]) for i in wave], S, max_rows))
+        cands += -(-sum(-(-int(n_cand[i]) // S) for i in wave) // max_rows)
+    return store, cands, -(-len(empty) // max_rows)
 
 
-def render_users(model, states, pagination, registry=None, full_history=False, trim=False, pack=False):
+def render_full_store_rows(n_hist, S, max_rows, slots=None):
+    """The packed store forwards of `render_full_forwards(pack_store=True)` as the library reports them in "forward_rows": [(rows, row_len)]
+    in run order, for the users with a history."""
+    slots = max_rows if slots is None else int(slots)
+    hist = [int(h) for h in n_hist if h >= 1]
+    return [(1 + max(r for _, r, _ in placed), row_len) for w0 in range(0, len(hist), slots)
+            for row_len, placed in _plan_segments(hist[w0:w0 + slots], S, max_rows)]
+
+
+def render_users(model, states, pagination, registry=None, full_history=False, trim=False, pack=False, pack_ranking=False):
     """`render` from raw histories in ONE device call (rsys_render_request): the same states, but users need no "embeds" -- the
     retrieval forward, `retrieval`, the page window, the ranking forward (every chunk row of every user, both media, in waves of the
     model's max_rows) and `ranking` + `reranking` run back to back on the device; only the pages and the totals come back.  A model built
@@ -986,9 +1085,14 @@ def render_users(model, states, pagination, registry=None, full_history=False, t
     `trim=True` (rsys_serving_trim_set for the length of the call): every forward of the pipeline runs at the length of its longest live
     row in whole 64-token tiles; waves, chunks, slots and outputs are unchanged.
     `pack=True` (rsys_serving_pack_set and, as packing implies trimming, rsys_serving_trim_set for the length of the call): the
-    retrieval stage runs several users per row (`pack_plan`'s layout); the ranking stages are the trimmed ones."""
+    retrieval stage runs several users per row (`pack_plan`'s layout); the ranking stages are the trimmed ones.
+    `pack_ranking=True` (rsys_serving_pack_ranking_set for the length of the call; `full_history=True` only): the K/V-cache store rows
+    hold several users, in waves of up to the model's reserved cache slots (`rank_cache_pack_plan`'s store stage); pages and totals are
+    unchanged."""
     if not states:
         return []
+    if pack_ranking and not full_history:
+        raise ValueError("render_users: pack_ranking packs the K/V-cache store rows, which only full_history=True runs")
     trim = trim or pack
     args = render_pack(states, pagination, model.config["max_sequence_length"], model.config["vocab_sizes"]["0_matchedid"], registry,
                        getattr(model, "adapter_slots", None), full_history)
@@ -997,6 +1101,8 @@ def render_users(model, states, pagination, registry=None, full_history=False, t
         model.serving_trim = True
     if pack:
         model.serving_pack = True
+    if pack_ranking:
+        model.serving_pack_ranking(True)
     try:
         pages, totals = (model.render_request_full if full_history else model.render_request)(**args)
     finally:
@@ -1004,4 +1110,6 @@ def render_users(model, states, pagination, registry=None, full_history=False, t
             model.serving_trim = before
         if pack:
             model.serving_pack = False
+        if pack_ranking:
+            model.serving_pack_ranking(False)
     return [(pages[g], int(totals[g])) for g in range(len(states))]
