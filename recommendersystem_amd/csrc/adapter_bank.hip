@@ -3,10 +3,11 @@
 // (Finetune/embed.py:180-255 serves four adapters on one trunk):
 //   stage A   La[t, 0:16]  = xn[t, :] . [A_q; A_v][slot(t)]^T                        (once per layer, reads xn once)
 //   stage B   q[t, :]     += rope(2 * La[t, 0:8] . B_q[slot(t)]^T),  v[t, :] += 2 * La[t, 8:16] . B_v[slot(t)]^T   (k is not touched)
-// A workgroup works on tokens of ONE batch row (a row is 2S consecutive tokens), so the slot is workgroup-uniform; rows with slot -1
-// return before their first load.  Packed serving rows (several users per row, segments of whole 64-token tiles) name a slot
-// per TILE instead: the two forward kernels have a per-tile form on the same body; packed finetune rows add the per-tile
-// forms of the training stages and per-SEGMENT partial gradients, summed per slot in descriptor order.  Rounding points are those of the finetune model's two LoRA GEMMs (model_forward.hip): operands
+// A workgroup works on tokens of ONE batch row (a row is 2S consecutive tokens) and, 16 | 64, of one 64-token tile of it, so the slot is
+// workgroup-uniform; a workgroup whose slot is -1 returns before its first load.  There is ONE kernel per stage.  Where its workgroup
+// finds the slot, or the tokens it sums over, is a by-value BankLookup: the slot of the row; or, on packed rows (DESIGN 4zb serving, 4zc
+// finetune: several users per row, segments of whole 64-token tiles), the slot of the TILE, with the partial gradients taken per SEGMENT
+// and summed per slot in descriptor order.  Rounding points are those of the finetune model's two LoRA GEMMs (model_forward.hip): operands
 // and La in the compute type, fp32 accumulation, alpha = 2 on the fp32 sum, the q part rotated and added to the rotated projection.
 // No atomics: every sum has a fixed order.
 #include "model_internal.hpp"
@@ -106,28 +107,98 @@ template <> struct BankMma<float> {
   }
 };
 
-constexpr int BANK_A_TOK = 16;   // tokens per workgroup of stage A (one MFMA tile row block)
-constexpr int BANK_B_TOK = 8;    // tokens per workgroup of stage B (2S is a multiple of 8)
+constexpr int BANK_A_TOK = 16;   // tokens per workgroup of stage A and dLa (one MFMA tile row block)
+constexpr int BANK_B_TOK = 8;    // tokens per workgroup of stage B and dx (2S is a multiple of 8)
 
-// grid (ceil(2S / 16), rows), 256 threads: the four waves split K (wave w takes the K steps w, w + 4, ...), their partial tiles are
-// added in wave order through LDS.  Tokens past the row's end (2S % 16 == 8) load zeros and store nothing.
-// (the body both forward forms of stage A share: `slot` >= 0 is the workgroup's)
-template <typename T>
-__device__ __forceinline__ void bank_a_body(const T* __restrict__ xn, const T* __restrict__ bankA, int row, int slot, int layer, int L, int D, int Ttok,
-                                            T* __restrict__ La) {
+// What a workgroup works for.  It reads blockIdx and kernel arguments alone, so it stays in scalar registers.
+//   token stages (a, b, dla, dx)   nt == 0: map [rows], the slot of the row;  nt > 0: map [rows][nt], nt = ceil(Ttok / 64), the slot of the
+//                                  64-token tile the workgroup's 16 or 8 tokens lie in (packed rows)
+//   partials (da, db), grid.y = the units:  segs == nullptr: unit = batch row, all its tokens, skipped when map[row] < 0;  otherwise unit
+//                                  = a segment of segs [n_seg][5] = (row, first column, columns, slot, task): its whole 64-token tiles, tokens
+//                                  [2 c0, min(Ttok, 2 c0 + 64 ceil(columns / 32))), which nobody else owns; skipped when its slot < 0
+struct BankLookup {
+  const int* map; int nt; const int* segs;
+  __device__ __forceinline__ int slot(int row, int t0) const { return map[nt ? row * nt + (t0 >> 6) : row]; }
+  __device__ __forceinline__ bool unit(int Ttok, int* row, int* kb, int* ke) const {
+    if (!segs) { *row = blockIdx.y; *kb = 0; *ke = Ttok; return map[blockIdx.y] >= 0; }
+    const int* sg = segs + (long long)blockIdx.y * 5;
+    *row = sg[0]; *kb = 2 * sg[1];
+    *ke = min(Ttok, *kb + 64 * ((sg[2] + 31) >> 5));
+    return sg[3] >= 0;
+  }
+};
+
+// ---- training through the bank
+// nn.Dropout of the LoRA input (model.py:238,265,269) drawn where it is used instead of in a pass of its own: element e of the layer's
+// [tokens][D] input is kept iff u01(Philox(seed)(e >> 2, stream)[e & 3]) >= p -- launch_dropout's mask, with stream = step * 64 + layer.
+// The forward (stage A) and the two backward kernels that need drop(xn) or drop' call the same function with the same key.
+struct BankDrop {
+  float p, keep; Philox ph; unsigned int stream;
+  __device__ BankDrop(float p_, unsigned long long seed, unsigned int stream_) : p(p_), keep(1.f / (1.f - p_)), ph(seed), stream(stream_) {}
+  // mask factors (keep or 0) of the 4 elements [4 q, 4 q + 4)
+  __device__ __forceinline__ void quad(long long q, float (&f)[4]) const {
+    uint32_t r[4];
+    ph.gen((unsigned long long)q, stream, r);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) f[k] = u01(r[k]) >= p ? keep : 0.f;
+  }
+  __device__ __forceinline__ float one(long long e) const {
+    uint32_t r[4];
+    ph.gen((unsigned long long)(e >> 2), stream, r);
+    return u01(r[e & 3]) >= p ? keep : 0.f;
+  }
+};
+struct BankNoDrop { __device__ BankNoDrop(float, unsigned long long, unsigned int) {} };   // (stage A of the inference forward: no key, no Philox)
+// drop(x) of one fragment of E consecutive elements starting at element e0 (a multiple of 4), rounded to T as launch_dropout stores it
+__device__ __forceinline__ bf16x8 bank_drop_frag(bf16x8 x, long long e0, const BankDrop& dr) {
+  float f0[4], f1[4];
+  dr.quad(e0 >> 2, f0); dr.quad((e0 >> 2) + 1, f1);
+#pragma unroll
+  for (int k = 0; k < 4; ++k) { x[k] = (bf16)((float)x[k] * f0[k]); x[4 + k] = (bf16)((float)x[4 + k] * f1[k]); }
+  return x;
+}
+__device__ __forceinline__ float4 bank_drop_frag(float4 x, long long e0, const BankDrop& dr) {
+  float f[4];
+  dr.quad(e0 >> 2, f);
+  return make_float4(x.x * f[0], x.y * f[1], x.z * f[2], x.w * f[3]);
+}
+// E elements `stride` apart as one fragment (operands whose contraction index is not the contiguous one)
+__device__ __forceinline__ bf16x8 bank_gather(const bf16* p, long long stride) {
+  bf16x8 x;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) x[k] = p[k * stride];
+  return x;
+}
+__device__ __forceinline__ float4 bank_gather(const float* p, long long stride) { return make_float4(p[0], p[stride], p[2 * stride], p[3 * stride]); }
+__device__ __forceinline__ void bank_frag_mul(bf16x8& x, int k, float f) { x[k] = (bf16)((float)x[k] * f); }
+__device__ __forceinline__ void bank_frag_mul(float4& x, int k, float f) { ((float*)&x)[k] *= f; }
+
+// Stage A.  grid (ceil(2S / 16), rows), 256 threads: the four waves split K (wave w takes the K steps w, w + 4, ...), their partial tiles
+// are added in wave order through LDS.  Tokens past the row's end (2S % 16 == 8) load zeros and store nothing.  DROP = false is the
+// inference forward; DROP = true a training pass: the LoRA input under the dropout mask of key (p, seed, stream) (p == 0: the same sums),
+// written to the layer's own La.
+template <typename T, bool DROP>
+__global__ __launch_bounds__(256) void adapter_bank_a_kernel(const T* __restrict__ xn, const T* __restrict__ bankA, BankLookup look, int layer, int L, int D,
+                                                             int Ttok, T* __restrict__ La, float p, unsigned long long seed, unsigned int stream) {
   using MM = BankMma<T>;
   __shared__ float red[4][4][64];
-  const int t0 = blockIdx.x * BANK_A_TOK;
+  const int row = blockIdx.y, t0 = blockIdx.x * BANK_A_TOK, slot = look.slot(row, t0);
+  if (slot < 0) return;
+  const typename std::conditional<DROP, BankDrop, BankNoDrop>::type dr(p, seed, stream);
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int r = lane & 15, kq = lane >> 4;
   const bool tok_ok = t0 + r < Ttok;
-  const T* xr = xn + ((long long)row * Ttok + (tok_ok ? t0 + r : 0)) * D;
+  const long long tok = (long long)row * Ttok + (tok_ok ? t0 + r : 0);
+  const T* xr = xn + tok * D;
   const T* ar = bankA + (((long long)slot * L + layer) * 16 + r) * D;
   f32x4 acc = {0.f, 0.f, 0.f, 0.f};
   for (int k0 = w * MM::KS; k0 < D; k0 += 4 * MM::KS) {
     const int k = k0 + kq * MM::E;
     const bool k_ok = k < D;   // (D % 16 == 0: a fragment is inside the row or entirely past it)
-    const typename MM::Frag xa = (tok_ok && k_ok) ? MM::load(xr + k) : MM::zero();
+    typename MM::Frag xa = (tok_ok && k_ok) ? MM::load(xr + k) : MM::zero();
+    if constexpr (DROP) {
+      if (p > 0.f && tok_ok && k_ok) xa = bank_drop_frag(xa, tok * D + k, dr);
+    }
     const typename MM::Frag ab = k_ok ? MM::load(ar + k) : MM::zero();
     acc = MM::mma(xa, ab, acc);
   }
@@ -136,33 +207,18 @@ __device__ __forceinline__ void bank_a_body(const T* __restrict__ xn, const T* _
   __syncthreads();
   // thread (i = wave, lane): element i of lane's accumulator = token 4 * (lane >> 4) + i, LoRA row lane & 15
   const float sum = ((red[0][w][lane] + red[1][w][lane]) + red[2][w][lane]) + red[3][w][lane];
-  const int tok = t0 + 4 * kq + w;
-  if (tok < Ttok) La[((long long)row * Ttok + tok) * 16 + r] = from_f32<T>(sum);
-}
-template <typename T>
-__global__ __launch_bounds__(256) void adapter_bank_a_kernel(const T* __restrict__ xn, const T* __restrict__ bankA, const int* __restrict__ row_slot,
-                                                             int layer, int L, int D, int Ttok, T* __restrict__ La) {
-  const int row = blockIdx.y, slot = row_slot[row];
-  if (slot < 0) return;
-  bank_a_body<T>(xn, bankA, row, slot, layer, L, D, Ttok, La);
-}
-// Packed serving rows: one slot per 64-token attention tile, tile_slot[row][nt] with nt = ceil(Ttok / 64).  The workgroup's
-// 16 tokens lie inside one tile (16 | 64), so the slot is still workgroup-uniform and the sums are those of the row-slot form.
-template <typename T>
-__global__ __launch_bounds__(256) void adapter_bank_a_tiles_kernel(const T* __restrict__ xn, const T* __restrict__ bankA, const int* __restrict__ tile_slot,
-                                                                   int nt, int layer, int L, int D, int Ttok, T* __restrict__ La) {
-  const int row = blockIdx.y, slot = tile_slot[row * nt + ((blockIdx.x * BANK_A_TOK) >> 6)];
-  if (slot < 0) return;
-  bank_a_body<T>(xn, bankA, row, slot, layer, L, D, Ttok, La);
+  const int tk = t0 + 4 * kq + w;
+  if (tk < Ttok) La[((long long)row * Ttok + tk) * 16 + r] = from_f32<T>(sum);
 }
 
-// grid (2S / 8, rows), 256 threads; a work item = 8 consecutive q or v columns of one token (one 16-byte access of bf16 qkv; 8 | hd, so
-// the item's RoPE pairs are its own).  The k columns are neither read nor written.
+// Stage B.  grid (2S / 8, rows), 256 threads; a work item = 8 consecutive q or v columns of one token (one 16-byte access of bf16 qkv;
+// 8 | hd, so the item's RoPE pairs are its own).  The k columns are neither read nor written.
 template <typename T>
-__device__ __forceinline__ void bank_b_body(const T* __restrict__ La, const T* __restrict__ bankB, int row, int slot, int layer, int L, int Nq, int Nk, int Nv,
-                                            int Ttok, int hd, const float* __restrict__ rope_cos, const float* __restrict__ rope_sin,
-                                            const int* __restrict__ rope_pos, T* __restrict__ qkv) {
-  const int t0 = blockIdx.x * BANK_B_TOK;
+__global__ __launch_bounds__(256) void adapter_bank_b_kernel(const T* __restrict__ La, const T* __restrict__ bankB, BankLookup look, int layer, int L, int Nq,
+                                                             int Nk, int Nv, int Ttok, int hd, const float* __restrict__ rope_cos,
+                                                             const float* __restrict__ rope_sin, const int* __restrict__ rope_pos, T* __restrict__ qkv) {
+  const int row = blockIdx.y, t0 = blockIdx.x * BANK_B_TOK, slot = look.slot(row, t0);
+  if (slot < 0) return;
   const int ntok = min(BANK_B_TOK, Ttok - t0);
   const int G = (Nq + Nv) >> 3, ld = Nq + Nk + Nv;
   const T* bb = bankB + ((long long)slot * L + layer) * (long long)(Nq + Nv) * 8;
@@ -200,130 +256,18 @@ __device__ __forceinline__ void bank_b_body(const T* __restrict__ La, const T* _
     store8<T>(dst, u);
   }
 }
-template <typename T>
-__global__ __launch_bounds__(256) void adapter_bank_b_kernel(const T* __restrict__ La, const T* __restrict__ bankB, const int* __restrict__ row_slot,
-                                                             int layer, int L, int Nq, int Nk, int Nv, int Ttok, int hd,
-                                                             const float* __restrict__ rope_cos, const float* __restrict__ rope_sin,
-                                                             const int* __restrict__ rope_pos, T* __restrict__ qkv) {
-  const int row = blockIdx.y, slot = row_slot[row];
-  if (slot < 0) return;
-  bank_b_body<T>(La, bankB, row, slot, layer, L, Nq, Nk, Nv, Ttok, hd, rope_cos, rope_sin, rope_pos, qkv);
-}
-// the per-tile form (8 | 64: the workgroup's 8 tokens lie inside one tile)
-template <typename T>
-__global__ __launch_bounds__(256) void adapter_bank_b_tiles_kernel(const T* __restrict__ La, const T* __restrict__ bankB, const int* __restrict__ tile_slot,
-                                                                   int nt, int layer, int L, int Nq, int Nk, int Nv, int Ttok, int hd,
-                                                                   const float* __restrict__ rope_cos, const float* __restrict__ rope_sin,
-                                                                   const int* __restrict__ rope_pos, T* __restrict__ qkv) {
-  const int row = blockIdx.y, slot = tile_slot[row * nt + ((blockIdx.x * BANK_B_TOK) >> 6)];
-  if (slot < 0) return;
-  bank_b_body<T>(La, bankB, row, slot, layer, L, Nq, Nk, Nv, Ttok, hd, rope_cos, rope_sin, rope_pos, qkv);
-}
-
-
-// ------------------------------------------------------------------ training through the bank
-// nn.Dropout of the LoRA input (model.py:238,265,269) drawn where it is used instead of in a pass of its own: element e of the layer's
-// [tokens][D] input is kept iff u01(Philox(seed)(e >> 2, stream)[e & 3]) >= p -- launch_dropout's mask, with stream = step * 64 + layer.
-// The forward (stage A) and the two backward kernels that need drop(xn) or drop' call the same function with the same key.
-struct BankDrop {
-  float p, keep; Philox ph; unsigned int stream;
-  __device__ BankDrop(float p_, unsigned long long seed, unsigned int stream_) : p(p_), keep(1.f / (1.f - p_)), ph(seed), stream(stream_) {}
-  // mask factors (keep or 0) of the 4 elements [4 q, 4 q + 4)
-  __device__ __forceinline__ void quad(long long q, float (&f)[4]) const {
-    uint32_t r[4];
-    ph.gen((unsigned long long)q, stream, r);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) f[k] = u01(r[k]) >= p ? keep : 0.f;
-  }
-  __device__ __forceinline__ float one(long long e) const {
-    uint32_t r[4];
-    ph.gen((unsigned long long)(e >> 2), stream, r);
-    return u01(r[e & 3]) >= p ? keep : 0.f;
-  }
-};
-// drop(x) of one fragment of E consecutive elements starting at element e0 (a multiple of 4), rounded to T as launch_dropout stores it
-__device__ __forceinline__ bf16x8 bank_drop_frag(bf16x8 x, long long e0, const BankDrop& dr) {
-  float f0[4], f1[4];
-  dr.quad(e0 >> 2, f0); dr.quad((e0 >> 2) + 1, f1);
-#pragma unroll
-  for (int k = 0; k < 4; ++k) { x[k] = (bf16)((float)x[k] * f0[k]); x[4 + k] = (bf16)((float)x[4 + k] * f1[k]); }
-  return x;
-}
-__device__ __forceinline__ float4 bank_drop_frag(float4 x, long long e0, const BankDrop& dr) {
-  float f[4];
-  dr.quad(e0 >> 2, f);
-  return make_float4(x.x * f[0], x.y * f[1], x.z * f[2], x.w * f[3]);
-}
-// E elements `stride` apart as one fragment (operands whose contraction index is not the contiguous one)
-__device__ __forceinline__ bf16x8 bank_gather(const bf16* p, long long stride) {
-  bf16x8 x;
-#pragma unroll
-  for (int k = 0; k < 8; ++k) x[k] = p[k * stride];
-  return x;
-}
-__device__ __forceinline__ float4 bank_gather(const float* p, long long stride) { return make_float4(p[0], p[stride], p[2 * stride], p[3 * stride]); }
-__device__ __forceinline__ void bank_frag_mul(bf16x8& x, int k, float f) { x[k] = (bf16)((float)x[k] * f); }
-__device__ __forceinline__ void bank_frag_mul(float4& x, int k, float f) { ((float*)&x)[k] *= f; }
-
-// stage A of a training pass: adapter_bank_a_kernel with the LoRA input under the dropout mask (p == 0: the same sums) and the layer's own La
-// (the body the row-slot and the per-tile form share: `slot` >= 0 is the workgroup's)
-template <typename T>
-__device__ __forceinline__ void bank_a_train_body(const T* __restrict__ xn, const T* __restrict__ bankA, int row, int slot, int layer, int L, int D, int Ttok,
-                                                  T* __restrict__ La, float p, unsigned long long seed, unsigned int stream) {
-  using MM = BankMma<T>;
-  __shared__ float red[4][4][64];
-  const BankDrop dr(p, seed, stream);
-  const int t0 = blockIdx.x * BANK_A_TOK;
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int r = lane & 15, kq = lane >> 4;
-  const bool tok_ok = t0 + r < Ttok;
-  const long long tok = (long long)row * Ttok + (tok_ok ? t0 + r : 0);
-  const T* xr = xn + tok * D;
-  const T* ar = bankA + (((long long)slot * L + layer) * 16 + r) * D;
-  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-  for (int k0 = w * MM::KS; k0 < D; k0 += 4 * MM::KS) {
-    const int k = k0 + kq * MM::E;
-    const bool k_ok = k < D;
-    typename MM::Frag xa = (tok_ok && k_ok) ? MM::load(xr + k) : MM::zero();
-    if (p > 0.f && tok_ok && k_ok) xa = bank_drop_frag(xa, tok * D + k, dr);
-    const typename MM::Frag ab = k_ok ? MM::load(ar + k) : MM::zero();
-    acc = MM::mma(xa, ab, acc);
-  }
-#pragma unroll
-  for (int i = 0; i < 4; ++i) red[w][i][lane] = acc[i];
-  __syncthreads();
-  const float sum = ((red[0][w][lane] + red[1][w][lane]) + red[2][w][lane]) + red[3][w][lane];
-  const int tk = t0 + 4 * kq + w;
-  if (tk < Ttok) La[((long long)row * Ttok + tk) * 16 + r] = from_f32<T>(sum);
-}
-template <typename T>
-__global__ __launch_bounds__(256) void adapter_bank_a_train_kernel(const T* __restrict__ xn, const T* __restrict__ bankA, const int* __restrict__ row_slot,
-                                                                   int layer, int L, int D, int Ttok, T* __restrict__ La, float p,
-                                                                   unsigned long long seed, unsigned int stream) {
-  const int row = blockIdx.y, slot = row_slot[row];
-  if (slot < 0) return;
-  bank_a_train_body<T>(xn, bankA, row, slot, layer, L, D, Ttok, La, p, seed, stream);
-}
-// Packed finetune rows: the slot of the workgroup's 64-token tile, as adapter_bank_a_tiles_kernel takes it
-template <typename T>
-__global__ __launch_bounds__(256) void adapter_bank_a_train_tiles_kernel(const T* __restrict__ xn, const T* __restrict__ bankA, const int* __restrict__ tile_slot,
-                                                                         int nt, int layer, int L, int D, int Ttok, T* __restrict__ La, float p,
-                                                                         unsigned long long seed, unsigned int stream) {
-  const int row = blockIdx.y, slot = tile_slot[row * nt + ((blockIdx.x * BANK_A_TOK) >> 6)];
-  if (slot < 0) return;
-  bank_a_train_body<T>(xn, bankA, row, slot, layer, L, D, Ttok, La, p, seed, stream);
-}
 
 // dLa[t, 0:8] = 2 dq_t . B_q[slot], dLa[t, 8:16] = 2 dv_t . B_v[slot] (the un-rotated dqkv the finetune model's gemm_lora_dla reads; rounded
 // to the compute type as that GEMM stores it).  grid (ceil(2S / 16), rows), 256 threads: stage A's tile -- tokens on the rows, the 16
 // LoRA columns on the columns -- with K = the q columns, then the v columns; B is [column][8], so its fragment is gathered 8 apart and
 // is zero on the half of the LoRA columns the segment does not feed.  The four waves split the K steps, partial tiles added in wave order.
 template <typename T>
-__device__ __forceinline__ void bank_dla_body(const T* __restrict__ dqkv, const T* __restrict__ bankB, int row, int slot, int layer, int L, int Nq, int Nk, int Nv,
-                                              int Ttok, T* __restrict__ dLa) {
+__global__ __launch_bounds__(256) void adapter_bank_dla_kernel(const T* __restrict__ dqkv, const T* __restrict__ bankB, BankLookup look, int layer, int L,
+                                                               int Nq, int Nk, int Nv, int Ttok, T* __restrict__ dLa) {
   using MM = BankMma<T>;
   __shared__ float red[4][4][64];
-  const int t0 = blockIdx.x * BANK_A_TOK;
+  const int row = blockIdx.y, t0 = blockIdx.x * BANK_A_TOK, slot = look.slot(row, t0);
+  if (slot < 0) return;
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int r = lane & 15, kq = lane >> 4;
   const bool tok_ok = t0 + r < Ttok;
@@ -349,30 +293,15 @@ __device__ __forceinline__ void bank_dla_body(const T* __restrict__ dqkv, const 
   if (tk < Ttok) dLa[((long long)row * Ttok + tk) * 16 + r] = from_f32<T>(2.f * sum);   // lora_scaling = 2 on the fp32 sum
 }
 
-template <typename T>
-__global__ __launch_bounds__(256) void adapter_bank_dla_kernel(const T* __restrict__ dqkv, const T* __restrict__ bankB, const int* __restrict__ row_slot,
-                                                               int layer, int L, int Nq, int Nk, int Nv, int Ttok, T* __restrict__ dLa) {
-  const int row = blockIdx.y, slot = row_slot[row];
-  if (slot < 0) return;
-  bank_dla_body<T>(dqkv, bankB, row, slot, layer, L, Nq, Nk, Nv, Ttok, dLa);
-}
-// the per-tile form (16 | 64: the workgroup's 16 tokens lie inside one tile)
-template <typename T>
-__global__ __launch_bounds__(256) void adapter_bank_dla_tiles_kernel(const T* __restrict__ dqkv, const T* __restrict__ bankB, const int* __restrict__ tile_slot,
-                                                                     int nt, int layer, int L, int Nq, int Nk, int Nv, int Ttok, T* __restrict__ dLa) {
-  const int row = blockIdx.y, slot = tile_slot[row * nt + ((blockIdx.x * BANK_A_TOK) >> 6)];
-  if (slot < 0) return;
-  bank_dla_body<T>(dqkv, bankB, row, slot, layer, L, Nq, Nk, Nv, Ttok, dLa);
-}
-
 // dxn[t, :] += drop'(dLa[t, :] . [A_q; A_v][slot]) (K = 16: no MFMA).  grid (2S / 8, rows), 256 threads, an item = 8 columns of one
 // token.  Rounding as the finetune model's gemm_lora_dx: without dropout the fp32 sum is added to dxn; with it the sum is rounded to the
 // compute type first (that model stores it), masked and scaled, then added.
 template <typename T>
-__device__ __forceinline__ void bank_dx_body(const T* __restrict__ dLa, const T* __restrict__ bankA, int row, int slot, int layer, int L, int D, int Ttok,
-                                             T* __restrict__ dxn, float p, unsigned long long seed, unsigned int stream) {
+__global__ __launch_bounds__(256) void adapter_bank_dx_kernel(const T* __restrict__ dLa, const T* __restrict__ bankA, BankLookup look, int layer, int L, int D,
+                                                              int Ttok, T* __restrict__ dxn, float p, unsigned long long seed, unsigned int stream) {
+  const int row = blockIdx.y, t0 = blockIdx.x * BANK_B_TOK, slot = look.slot(row, t0);
+  if (slot < 0) return;
   const BankDrop dr(p, seed, stream);
-  const int t0 = blockIdx.x * BANK_B_TOK;
   const int ntok = min(BANK_B_TOK, Ttok - t0);
   const int G = D >> 3;
   const T* aa = bankA + ((long long)slot * L + layer) * 16 * (long long)D;
@@ -406,33 +335,17 @@ __device__ __forceinline__ void bank_dx_body(const T* __restrict__ dLa, const T*
   }
 }
 
+// Partial of dA per unit (BankLookup: a batch row, or a segment): partA[unit][j][d] = sum over the unit's tokens t, ascending, of
+// dLa[t][j] drop(xn)[t][d].  grid (ceil(D / 64), units), 256 threads: every wave owns 16 columns d and the whole contraction (K = the
+// unit's tokens), so a partial has one fixed order and no cross-wave sum.  MFMA tile: the 16 LoRA rows j on the rows, d on the columns;
+// both operands have the token as their OUTER index, so the fragments are gathered (16 resp. D apart).
 template <typename T>
-__global__ __launch_bounds__(256) void adapter_bank_dx_kernel(const T* __restrict__ dLa, const T* __restrict__ bankA, const int* __restrict__ row_slot,
-                                                              int layer, int L, int D, int Ttok, T* __restrict__ dxn, float p,
-                                                              unsigned long long seed, unsigned int stream) {
-  const int row = blockIdx.y, slot = row_slot[row];
-  if (slot < 0) return;
-  bank_dx_body<T>(dLa, bankA, row, slot, layer, L, D, Ttok, dxn, p, seed, stream);
-}
-// the per-tile form (8 | 64: the workgroup's 8 tokens lie inside one tile)
-template <typename T>
-__global__ __launch_bounds__(256) void adapter_bank_dx_tiles_kernel(const T* __restrict__ dLa, const T* __restrict__ bankA, const int* __restrict__ tile_slot,
-                                                                    int nt, int layer, int L, int D, int Ttok, T* __restrict__ dxn, float p,
-                                                                    unsigned long long seed, unsigned int stream) {
-  const int row = blockIdx.y, slot = tile_slot[row * nt + ((blockIdx.x * BANK_B_TOK) >> 6)];
-  if (slot < 0) return;
-  bank_dx_body<T>(dLa, bankA, row, slot, layer, L, D, Ttok, dxn, p, seed, stream);
-}
-
-// Per-row partial of dA: partA[row][j][d] = sum over the row's tokens t, ascending, of dLa[t][j] drop(xn)[t][d].  grid (ceil(D / 64), rows),
-// 256 threads: every wave owns 16 columns d and the whole contraction (K = 2S tokens), so a partial has one fixed order and no
-// cross-wave sum.  MFMA tile: the 16 LoRA rows j on the rows, d on the columns; both operands have the token as their OUTER index, so
-// the fragments are gathered (16 resp. D apart).
-// (the body of the row and the segment form: the contraction runs over tokens [kb, ke) of `row`, kb a multiple of 64, into dst[16][D])
-template <typename T>
-__device__ __forceinline__ void bank_da_body(const T* __restrict__ dLa, const T* __restrict__ xn, int row, int kb, int ke, int D, int Ttok,
-                                             float* __restrict__ dst, float p, unsigned long long seed, unsigned int stream) {
+__global__ __launch_bounds__(256) void adapter_bank_da_kernel(const T* __restrict__ dLa, const T* __restrict__ xn, BankLookup look, int D, int Ttok,
+                                                              float* __restrict__ partA, float p, unsigned long long seed, unsigned int stream) {
   using MM = BankMma<T>;
+  int row, kb, ke;   // the contraction runs over tokens [kb, ke) of `row`, kb a multiple of 64
+  if (!look.unit(Ttok, &row, &kb, &ke)) return;
+  float* dst = partA + (long long)blockIdx.y * 16 * D;
   const BankDrop dr(p, seed, stream);
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int d0 = (blockIdx.x * 4 + w) * 16;
@@ -457,40 +370,17 @@ __device__ __forceinline__ void bank_da_body(const T* __restrict__ dLa, const T*
 #pragma unroll
   for (int i = 0; i < 4; ++i) dst[(long long)(4 * kq + i) * D + d0 + r] = acc[i];
 }
-template <typename T>
-__global__ __launch_bounds__(256) void adapter_bank_da_kernel(const T* __restrict__ dLa, const T* __restrict__ xn, const int* __restrict__ row_slot,
-                                                              int D, int Ttok, float* __restrict__ partA, float p, unsigned long long seed,
-                                                              unsigned int stream) {
-  const int row = blockIdx.y;
-  if (row_slot[row] < 0) return;
-  bank_da_body<T>(dLa, xn, row, 0, Ttok, D, Ttok, partA + (long long)row * 16 * D, p, seed, stream);
-}
-// Packed finetune rows: one partial per SEGMENT.  segs [n_seg][5] = (row, first column, columns, slot, task); the contraction
-// runs over the segment's whole 64-token tiles, tokens [2 c0, min(2S, 2 c0 + 64 ceil(columns / 32))), which nobody else owns.  grid
-// (ceil(D / 64), n_seg); a segment with slot -1 writes nothing.
-__device__ __forceinline__ bool bank_seg_range(const int* __restrict__ segs, int Ttok, int* row, int* kb, int* ke) {
-  const int* sg = segs + (long long)blockIdx.y * 5;
-  if (sg[3] < 0) return false;
-  *row = sg[0]; *kb = 2 * sg[1];
-  *ke = min(Ttok, *kb + 64 * ((sg[2] + 31) >> 5));
-  return true;
-}
-template <typename T>
-__global__ __launch_bounds__(256) void adapter_bank_da_seg_kernel(const T* __restrict__ dLa, const T* __restrict__ xn, const int* __restrict__ segs,
-                                                                  int D, int Ttok, float* __restrict__ partA, float p, unsigned long long seed,
-                                                                  unsigned int stream) {
-  int row, kb, ke;
-  if (!bank_seg_range(segs, Ttok, &row, &kb, &ke)) return;
-  bank_da_body<T>(dLa, xn, row, kb, ke, D, Ttok, partA + (long long)blockIdx.y * 16 * D, p, seed, stream);
-}
 
-// Per-row partial of dB: partB[row][c][j] = sum over the row's tokens, ascending, of dqv[t][c] La[t][j (q columns) | 8 + j (v columns)]
-// (the factor 2 is applied when the rows are added).  grid (ceil((Nq + Nv) / 64), rows), 256 threads; a wave owns 16 columns c of
+// Partial of dB per unit: partB[unit][c][j] = sum over the unit's tokens, ascending, of dqv[t][c] La[t][j (q columns) | 8 + j (v columns)]
+// (the factor 2 is applied when the units are added).  grid (ceil((Nq + Nv) / 64), units), 256 threads; a wave owns 16 columns c of
 // [dq | dv] and the whole contraction; the tile's 16 columns are La's, of which a q (v) row keeps the first (last) 8.
 template <typename T>
-__device__ __forceinline__ void bank_db_body(const T* __restrict__ dqkv, const T* __restrict__ La, int row, int kb, int ke, int Nq, int Nk, int Nv, int Ttok,
-                                             float* __restrict__ dst) {
+__global__ __launch_bounds__(256) void adapter_bank_db_kernel(const T* __restrict__ dqkv, const T* __restrict__ La, BankLookup look, int Nq, int Nk, int Nv,
+                                                              int Ttok, float* __restrict__ partB) {
   using MM = BankMma<T>;
+  int row, kb, ke;
+  if (!look.unit(Ttok, &row, &kb, &ke)) return;
+  float* dst = partB + (long long)blockIdx.y * (Nq + Nv) * 8;
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int c0 = (blockIdx.x * 4 + w) * 16;
   if (c0 >= Nq + Nv) return;
@@ -516,45 +406,21 @@ __device__ __forceinline__ void bank_db_body(const T* __restrict__ dqkv, const T
     if (isq ? r < 8 : r >= 8) dst[(long long)c * 8 + (r & 7)] = acc[i];
   }
 }
-template <typename T>
-__global__ __launch_bounds__(256) void adapter_bank_db_kernel(const T* __restrict__ dqkv, const T* __restrict__ La, const int* __restrict__ row_slot,
-                                                              int Nq, int Nk, int Nv, int Ttok, float* __restrict__ partB) {
-  const int row = blockIdx.y;
-  if (row_slot[row] < 0) return;
-  bank_db_body<T>(dqkv, La, row, 0, Ttok, Nq, Nk, Nv, Ttok, partB + (long long)row * (Nq + Nv) * 8);
-}
-// the segment form, grid (ceil((Nq + Nv) / 64), n_seg): adapter_bank_da_seg_kernel's token range
-template <typename T>
-__global__ __launch_bounds__(256) void adapter_bank_db_seg_kernel(const T* __restrict__ dqkv, const T* __restrict__ La, const int* __restrict__ segs,
-                                                                  int Nq, int Nk, int Nv, int Ttok, float* __restrict__ partB) {
-  int row, kb, ke;
-  if (!bank_seg_range(segs, Ttok, &row, &kb, &ke)) return;
-  bank_db_body<T>(dqkv, La, row, kb, ke, Nq, Nk, Nv, Ttok, partB + (long long)blockIdx.y * (Nq + Nv) * 8);
-}
 
-// g[slot][layer][e] += alpha * (sum of part[row][e] over the rows of `slot`, in row order): one thread per element, the fixed order that
-// makes a call reproducible and a slot's gradient independent of the other slots' rows.  A slot without a row is not touched.
-__global__ __launch_bounds__(256) void adapter_bank_rows_reduce_kernel(const float* __restrict__ part, const int* __restrict__ row_slot, int rows,
-                                                                       long long n, float alpha, float* __restrict__ g, long long slot_stride) {
+// g[slot][layer][e] += alpha * (sum of part[u][e] over the units u of `slot`, ascending): one thread per element, the fixed order that
+// makes a call reproducible and a slot's gradient independent of the other slots' units.  key[u * STRIDE] is unit u's slot: row_slot with
+// STRIDE 1, or the segment table from its slot field on with STRIDE 5 (descriptor order).  A slot without a unit is not touched.
+// (STRIDE is a template parameter, not an argument: with a run-time stride the compiler no longer unrolls the row form's key loop by 8,
+// and the unpacked joint step measured 0.09 ms of 18.8 slower, outside the parent's spread -- DESIGN 4zc.)
+template <int STRIDE>
+__global__ __launch_bounds__(256) void adapter_bank_reduce_kernel(const float* __restrict__ part, const int* __restrict__ key, int units, long long n,
+                                                                  float alpha, float* __restrict__ g, long long slot_stride) {
   const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
   if (e >= n) return;
   for (int a = 0; a < RSYS_ADAPTER_SLOTS; ++a) {
     float acc = 0.f; bool any = false;
-    for (int r = 0; r < rows; ++r)
-      if (row_slot[r] == a) { acc += part[(long long)r * n + e]; any = true; }
-    if (any) g[(long long)a * slot_stride + e] += alpha * acc;
-  }
-}
-
-// the same over per-SEGMENT partials: per slot the sum over that slot's segments in descriptor order (segs [n_seg][5], slot at [3])
-__global__ __launch_bounds__(256) void adapter_bank_segs_reduce_kernel(const float* __restrict__ part, const int* __restrict__ segs, int n_seg,
-                                                                       long long n, float alpha, float* __restrict__ g, long long slot_stride) {
-  const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (e >= n) return;
-  for (int a = 0; a < RSYS_ADAPTER_SLOTS; ++a) {
-    float acc = 0.f; bool any = false;
-    for (int i = 0; i < n_seg; ++i)
-      if (segs[i * 5 + 3] == a) { acc += part[(long long)i * n + e]; any = true; }
+    for (int u = 0; u < units; ++u)
+      if (key[u * STRIDE] == a) { acc += part[(long long)u * n + e]; any = true; }
     if (any) g[(long long)a * slot_stride + e] += alpha * acc;
   }
 }
@@ -716,7 +582,37 @@ int adapter_slots(Model* m, int32_t* mask_out) {
   return RSYS_OK;
 }
 
-// ------------------------------------------------------------------ the inference call's side
+// ------------------------------------------------------------------ the calls' side
+// one entry of a caller's slot list `what`: -1 (the base model), or a slot that is complete
+static int bank_entry_check(const Model* m, const char* what, int s) {
+  ARG_CHECK(s >= -1 && s < RSYS_ADAPTER_SLOTS, std::string(what) + " entries must be in [-1, RSYS_ADAPTER_SLOTS)");
+  if (s >= 0) ARG_CHECK(bank_complete(m, s), std::string(what) + " names a slot that is not complete (4 tensors per layer since its last clear)");
+  return RSYS_OK;
+}
+
+// The buffers the bank allocates at their first use: La of the serving forward, and the tables of the packed calls (the tile maps in
+// the caller's geometry, the segment table).  dalloc's zero fill runs on the null stream and the model's stream does not wait for that
+// one, so a fresh fill is waited for HERE, before the caller queues anything on the model's stream: without that the fill may land on a
+// table copied in behind it (every tile then reads slot 0 in the first packed call of a model), or on the first La.
+enum { BANK_BUF_LA = 1, BANK_BUF_TILES = 2, BANK_BUF_PACK = 4 };
+static int bank_first_use(Model* m, int which) {
+  AdapterBank* b = m->bank;
+  const int64_t tiles = (int64_t)m->rows_max * ((m->Sa + 31) / 32);
+  bool fresh = false;
+  auto once = [&](auto*& p, int64_t bytes) -> int {
+    if (p) return RSYS_OK;
+    fresh = true;
+    DALLOC(p, bytes);
+    return RSYS_OK;
+  };
+  HIP_CHECK(hipSetDevice(m->device));
+  if (which & BANK_BUF_LA) RC(once(b->La, (int64_t)m->rows_max * m->Ta * 16 * m->esz));
+  if (which & BANK_BUF_TILES) RC(once(b->d_tiles, tiles * 4));
+  if (which & BANK_BUF_PACK) { RC(once(b->d_tile_task, tiles * 4)); RC(once(b->d_segs, tiles * 5 * 4)); }
+  if (fresh) HIP_CHECK(hipDeviceSynchronize());
+  return RSYS_OK;
+}
+
 // checks row_adapter[0 .. rows) and makes it the slot vector of the next forward_trunk (m->bank_rows); adapter_unbind_rows ends that
 int adapter_bind_rows(Model* m, const int32_t* row_adapter) {
   RC(bank_check_model(m));
@@ -724,18 +620,13 @@ int adapter_bind_rows(Model* m, const int32_t* row_adapter) {
   ARG_CHECK(m->cur_rows > 0, "no batch uploaded");
   bool any = false;
   for (int r = 0; r < m->cur_rows; ++r) {
-    const int s = row_adapter[r];
-    ARG_CHECK(s >= -1 && s < RSYS_ADAPTER_SLOTS, "row_adapter entries must be in [-1, RSYS_ADAPTER_SLOTS)");
-    if (s >= 0) { ARG_CHECK(bank_complete(m, s), "row_adapter names a slot that is not complete (4 tensors per layer since its last clear)"); any = true; }
+    RC(bank_entry_check(m, "row_adapter", row_adapter[r]));
+    any |= row_adapter[r] >= 0;
   }
   m->bank_rows = nullptr;
   if (!any) return RSYS_OK;   // every row runs the base model: the forward launches what rsys_infer_select launches
   AdapterBank* b = m->bank;
-  HIP_CHECK(hipSetDevice(m->device));
-  if (!b->La) {
-    DALLOC(b->La, (int64_t)m->rows_max * m->Ta * 16 * m->esz);
-    HIP_CHECK(hipDeviceSynchronize());   // (its zero fill runs on the null stream: done before the model's stream writes La)
-  }
+  RC(bank_first_use(m, BANK_BUF_LA));
   HIP_CHECK(hipMemcpyAsync(b->d_rows, row_adapter, (size_t)m->cur_rows * 4, hipMemcpyHostToDevice, m->stream));
   m->bank_rows = b->d_rows;
   return RSYS_OK;
@@ -752,21 +643,13 @@ int adapter_bind_tiles(Model* m, const int32_t* tile_adapter) {
   const int nta = (m->Sa + 31) / 32, nt = (m->S + 31) / 32;
   bool any = false;
   for (int i = 0; i < m->cur_rows * nta; ++i) {
-    const int s = tile_adapter[i];
-    ARG_CHECK(s >= -1 && s < RSYS_ADAPTER_SLOTS, "tile_adapter entries must be in [-1, RSYS_ADAPTER_SLOTS)");
-    if (s >= 0) ARG_CHECK(bank_complete(m, s), "tile_adapter names a slot that is not complete (4 tensors per layer since its last clear)");
-    if (s >= 0 && i % nta < nt) any = true;
+    RC(bank_entry_check(m, "tile_adapter", tile_adapter[i]));
+    any |= tile_adapter[i] >= 0 && i % nta < nt;
   }
   m->bank_rows = nullptr; m->bank_tiles = nullptr;
   if (!any) return RSYS_OK;   // every live tile runs the base model: the forward launches what rsys_infer_select launches
   AdapterBank* b = m->bank;
-  HIP_CHECK(hipSetDevice(m->device));
-  const bool fresh = !b->La || !b->d_tiles;
-  if (!b->La) DALLOC(b->La, (int64_t)m->rows_max * m->Ta * 16 * m->esz);
-  if (!b->d_tiles) DALLOC(b->d_tiles, (int64_t)m->rows_max * nta * 4);
-  // (dalloc's zero fill runs on the null stream and the model's stream does not wait for that one: without this the fill may land on the
-  // map copied below -- every tile then reads slot 0 in the first packed forward of a model)
-  if (fresh) HIP_CHECK(hipDeviceSynchronize());
+  RC(bank_first_use(m, BANK_BUF_LA | BANK_BUF_TILES));
   HIP_CHECK(hipStreamSynchronize(m->stream));   // (the previous call's copy has read h_tiles)
   b->h_tiles.resize((size_t)m->cur_rows * nt);
   for (int r = 0; r < m->cur_rows; ++r) std::copy(tile_adapter + (size_t)r * nta, tile_adapter + (size_t)r * nta + nt, b->h_tiles.begin() + (size_t)r * nt);
@@ -777,20 +660,16 @@ int adapter_bind_tiles(Model* m, const int32_t* tile_adapter) {
 
 // One layer's launches on plain arguments: what the model-side callers below fill from Model and the test hooks (rsys_op_adapter_bank,
 // rsys_debug.h) fill from the caller's buffers.  bankA / bankB: the compute-type copies; (p, seed, stream): the dropout key of BankDrop.
+// The tile map, when set, takes the place of the row slots (packed rows: adapter_bind_tiles, rsys_adapter_forward_backward_packed, the
+// _tiles / _segments hooks); the segment table comes with it in a training pass.
+static BankLookup bank_lookup(const BankLaunch& a) {
+  return a.tile_slot ? BankLookup{a.tile_slot, (a.Ttok + 63) / 64, a.segs} : BankLookup{a.row_slot, 0, nullptr};
+}
 template <typename T>
 int bank_launch_a(const BankLaunch& a, const T* xn, T* La, bool train) {
   const dim3 grid((a.Ttok + BANK_A_TOK - 1) / BANK_A_TOK, a.rows);
-  if (a.tile_slot && train)   // packed finetune rows
-    hipLaunchKernelGGL((adapter_bank_a_train_tiles_kernel<T>), grid, dim3(256), 0, a.s, xn, (const T*)a.bankA, a.tile_slot, (a.Ttok + 63) / 64, a.layer, a.L,
-                       a.D, a.Ttok, La, a.p, a.seed, a.stream);
-  else if (a.tile_slot)   // packed serving rows (adapter_bind_tiles, rsys_op_adapter_bank_tiles)
-    hipLaunchKernelGGL((adapter_bank_a_tiles_kernel<T>), grid, dim3(256), 0, a.s, xn, (const T*)a.bankA, a.tile_slot, (a.Ttok + 63) / 64, a.layer, a.L, a.D,
-                       a.Ttok, La);
-  else if (train)   // the LoRA input under the dropout mask
-    hipLaunchKernelGGL((adapter_bank_a_train_kernel<T>), grid, dim3(256), 0, a.s, xn, (const T*)a.bankA, a.row_slot, a.layer, a.L, a.D, a.Ttok, La, a.p,
-                       a.seed, a.stream);
-  else
-    hipLaunchKernelGGL((adapter_bank_a_kernel<T>), grid, dim3(256), 0, a.s, xn, (const T*)a.bankA, a.row_slot, a.layer, a.L, a.D, a.Ttok, La);
+  auto* kernel = train ? adapter_bank_a_kernel<T, true> : adapter_bank_a_kernel<T, false>;   // (train: the LoRA input under the dropout mask)
+  hipLaunchKernelGGL(kernel, grid, dim3(256), 0, a.s, xn, (const T*)a.bankA, bank_lookup(a), a.layer, a.L, a.D, a.Ttok, La, a.p, a.seed, a.stream);
   HIP_CHECK(hipGetLastError());
   return RSYS_OK;
 }
@@ -798,62 +677,39 @@ template <typename T>
 int bank_launch_b(const BankLaunch& a, const T* La, T* qkv, const float* rope_cos, const float* rope_sin, const int* rope_pos) {
   const int Nq = a.H * a.hd, Nk = a.KV * a.hd;
   const dim3 grid((a.Ttok + BANK_B_TOK - 1) / BANK_B_TOK, a.rows);
-  if (a.tile_slot)
-    hipLaunchKernelGGL((adapter_bank_b_tiles_kernel<T>), grid, dim3(256), 0, a.s, La, (const T*)a.bankB, a.tile_slot, (a.Ttok + 63) / 64, a.layer, a.L, Nq, Nk,
-                       Nk, a.Ttok, a.hd, rope_cos, rope_sin, rope_pos, qkv);
-  else
-    hipLaunchKernelGGL((adapter_bank_b_kernel<T>), grid, dim3(256), 0, a.s, La, (const T*)a.bankB, a.row_slot, a.layer, a.L, Nq, Nk, Nk, a.Ttok, a.hd,
-                       rope_cos, rope_sin, rope_pos, qkv);
+  hipLaunchKernelGGL((adapter_bank_b_kernel<T>), grid, dim3(256), 0, a.s, La, (const T*)a.bankB, bank_lookup(a), a.layer, a.L, Nq, Nk, Nk, a.Ttok, a.hd,
+                     rope_cos, rope_sin, rope_pos, qkv);
   HIP_CHECK(hipGetLastError());
   return RSYS_OK;
 }
 // the backward's launches in the order adapter_bank_backward issues them; `stages` as rsys_op_adapter_bank's mask (4 dLa, 8 dB partials,
-// 16 dA partials, 32 dx, 64 both row reductions)
+// 16 dA partials, 32 dx, 64 both reductions).  partA / partB hold one partial per unit: [rows][..], or [n_seg][..] with a segment table.
 template <typename T>
 int bank_launch_backward(const BankLaunch& a, int stages, const T* xn, const T* dqkv, const T* La, T* dLa, T* dxn, float* partA, float* partB,
                          float* gA, float* gB) {
   const int rows = a.rows, Nq = a.H * a.hd, Nk = a.KV * a.hd, Nv = Nk, Ttok = a.Ttok, D = a.D;
+  const BankLookup look = bank_lookup(a);
+  const int units = look.segs ? a.n_seg : rows;
   hipStream_t s = a.s;
-  if (a.tile_slot) {   // packed finetune rows: per-tile token stages, per-segment partials (partA / partB: [n_seg][..]), sums in descriptor order
-    const int nt = (Ttok + 63) / 64;
-    if (stages & 4)
-      hipLaunchKernelGGL((adapter_bank_dla_tiles_kernel<T>), dim3((Ttok + BANK_A_TOK - 1) / BANK_A_TOK, rows), dim3(256), 0, s, dqkv, (const T*)a.bankB,
-                         a.tile_slot, nt, a.layer, a.L, Nq, Nk, Nv, Ttok, dLa);
-    if (stages & 8)
-      hipLaunchKernelGGL((adapter_bank_db_seg_kernel<T>), dim3((Nq + Nv + 63) / 64, a.n_seg), dim3(256), 0, s, dqkv, La, a.segs, Nq, Nk, Nv, Ttok, partB);
-    if (stages & 16)
-      hipLaunchKernelGGL((adapter_bank_da_seg_kernel<T>), dim3((D + 63) / 64, a.n_seg), dim3(256), 0, s, (const T*)dLa, xn, a.segs, D, Ttok, partA, a.p, a.seed,
-                         a.stream);
-    if (stages & 32)
-      hipLaunchKernelGGL((adapter_bank_dx_tiles_kernel<T>), dim3((Ttok + BANK_B_TOK - 1) / BANK_B_TOK, rows), dim3(256), 0, s, (const T*)dLa, (const T*)a.bankA,
-                         a.tile_slot, nt, a.layer, a.L, D, Ttok, dxn, a.p, a.seed, a.stream);
-    if (stages & 64) {
-      const long long na = (long long)16 * D, nb = (long long)(Nq + Nv) * 8;
-      hipLaunchKernelGGL(adapter_bank_segs_reduce_kernel, dim3((unsigned)((na + 255) / 256)), dim3(256), 0, s, partA, a.segs, a.n_seg, na, 1.f,
-                         gA + (long long)a.layer * na, (long long)a.L * na);
-      hipLaunchKernelGGL(adapter_bank_segs_reduce_kernel, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, s, partB, a.segs, a.n_seg, nb, 2.f,
-                         gB + (long long)a.layer * nb, (long long)a.L * nb);
-    }
-    HIP_CHECK(hipGetLastError());
-    return RSYS_OK;
-  }
   if (stages & 4)
-    hipLaunchKernelGGL((adapter_bank_dla_kernel<T>), dim3((Ttok + BANK_A_TOK - 1) / BANK_A_TOK, rows), dim3(256), 0, s, dqkv, (const T*)a.bankB, a.row_slot,
+    hipLaunchKernelGGL((adapter_bank_dla_kernel<T>), dim3((Ttok + BANK_A_TOK - 1) / BANK_A_TOK, rows), dim3(256), 0, s, dqkv, (const T*)a.bankB, look,
                        a.layer, a.L, Nq, Nk, Nv, Ttok, dLa);
   if (stages & 8)
-    hipLaunchKernelGGL((adapter_bank_db_kernel<T>), dim3((Nq + Nv + 63) / 64, rows), dim3(256), 0, s, dqkv, La, a.row_slot, Nq, Nk, Nv, Ttok, partB);
+    hipLaunchKernelGGL((adapter_bank_db_kernel<T>), dim3((Nq + Nv + 63) / 64, units), dim3(256), 0, s, dqkv, La, look, Nq, Nk, Nv, Ttok, partB);
   if (stages & 16)
-    hipLaunchKernelGGL((adapter_bank_da_kernel<T>), dim3((D + 63) / 64, rows), dim3(256), 0, s, (const T*)dLa, xn, a.row_slot, D, Ttok, partA, a.p, a.seed,
+    hipLaunchKernelGGL((adapter_bank_da_kernel<T>), dim3((D + 63) / 64, units), dim3(256), 0, s, (const T*)dLa, xn, look, D, Ttok, partA, a.p, a.seed,
                        a.stream);
   if (stages & 32)
     hipLaunchKernelGGL((adapter_bank_dx_kernel<T>), dim3((Ttok + BANK_B_TOK - 1) / BANK_B_TOK, rows), dim3(256), 0, s, (const T*)dLa, (const T*)a.bankA,
-                       a.row_slot, a.layer, a.L, D, Ttok, dxn, a.p, a.seed, a.stream);
+                       look, a.layer, a.L, D, Ttok, dxn, a.p, a.seed, a.stream);
   if (stages & 64) {
     const long long na = (long long)16 * D, nb = (long long)(Nq + Nv) * 8;
-    hipLaunchKernelGGL(adapter_bank_rows_reduce_kernel, dim3((unsigned)((na + 255) / 256)), dim3(256), 0, s, partA, a.row_slot, rows, na, 1.f,
-                       gA + (long long)a.layer * na, (long long)a.L * na);
-    hipLaunchKernelGGL(adapter_bank_rows_reduce_kernel, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, s, partB, a.row_slot, rows, nb, 2.f,
-                       gB + (long long)a.layer * nb, (long long)a.L * nb);
+    const int* key = look.segs ? look.segs + 3 : look.map;
+    auto* reduce = look.segs ? adapter_bank_reduce_kernel<5> : adapter_bank_reduce_kernel<1>;
+    hipLaunchKernelGGL(reduce, dim3((unsigned)((na + 255) / 256)), dim3(256), 0, s, partA, key, units, na, 1.f, gA + (long long)a.layer * na,
+                       (long long)a.L * na);
+    hipLaunchKernelGGL(reduce, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, s, partB, key, units, nb, 2.f, gB + (long long)a.layer * nb,
+                       (long long)a.L * nb);
   }
   HIP_CHECK(hipGetLastError());
   return RSYS_OK;
@@ -927,97 +783,100 @@ int adapter_train_enable(Model* m, float dropout) {
   return RSYS_OK;
 }
 
-int adapter_forward_backward(Model* m, int evaluate, const int32_t* row_slot, const int32_t* row_task, float grad_scale, uint64_t seed, uint64_t step) {
+// what both training calls require of the model and its resident batch
+static int bank_train_call_check(Model* m) {
   RC(bank_train_check_model(m));
   ARG_CHECK(m->bank != nullptr && m->bank->train, "adapter bank training is not enabled (rsys_adapter_train_enable)");
   ARG_CHECK(m->cur_rows > 0, "no batch uploaded");
-  RC(check_not_trimmed(m));
+  return check_not_trimmed(m);
+}
+
+// One unit of a training call -- `unit` = "row" or "segment" -- names a slot and a task, or neither; and one task has one slot per call
+// (owner[task], -1 while nobody named it).
+static int bank_pair_check(const char* unit, int s, int t, int (&owner)[4]) {
+  const std::string u(unit);
+  ARG_CHECK(s >= -1 && s < RSYS_ADAPTER_SLOTS, u + " slots must be in [-1, RSYS_ADAPTER_SLOTS)");
+  ARG_CHECK(t >= -1 && t < 4, u + " tasks must be in [-1, 4)");
+  ARG_CHECK((s < 0) == (t < 0), "a " + u + " names a slot and a task, or neither (-1 / -1)");
+  if (s < 0) return RSYS_OK;
+  ARG_CHECK(owner[t] < 0 || owner[t] == s, "one task is named by two slots in the same call");
+  owner[t] = s;
+  return RSYS_OK;
+}
+
+// One training pass over the resident batch with the tables the caller has queued on the model's stream: the slot per row or (packed)
+// per tile -- nullptr when every unit runs the base model -- and the task per row or tile.  The pass runs with every sum in a fixed
+// order whatever the model's own setting; what it sets is put back on every return path.
+static int bank_train_pass(Model* m, int evaluate, const int* rows, const int* tiles, bool packed, const int* d_task, float grad_scale, uint64_t seed,
+                           uint64_t step) {
+  AdapterBank* b = m->bank;
+  const bool det = m->deterministic;
+  m->deterministic = true;
+  m->bank_rows = rows; m->bank_tiles = tiles;
+  m->bank_train = true;
+  m->bank_packed = packed;   // masks per tile; the last layer runs dense (its compact order would mix segments inside a work item)
+  b->drop_now = !evaluate && b->dropout > 0.f;
+  int rc;
+  {
+    DetScope scope(m);
+    rc = model_forward_backward_rows(m, evaluate, d_task, grad_scale, seed, step);
+  }
+  m->bank_packed = false;
+  m->bank_train = false;
+  m->bank_rows = nullptr; m->bank_tiles = nullptr;
+  m->deterministic = det;
+  return rc;
+}
+
+int adapter_forward_backward(Model* m, int evaluate, const int32_t* row_slot, const int32_t* row_task, float grad_scale, uint64_t seed, uint64_t step) {
+  RC(bank_train_call_check(m));
   ARG_CHECK(row_slot != nullptr && row_task != nullptr, "row_slot / row_task is null");
   int owner[4] = {-1, -1, -1, -1};
   bool any = false;
   for (int r = 0; r < m->cur_rows; ++r) {
-    const int s = row_slot[r], t = row_task[r];
-    ARG_CHECK(s >= -1 && s < RSYS_ADAPTER_SLOTS, "row_slot entries must be in [-1, RSYS_ADAPTER_SLOTS)");
-    ARG_CHECK(t >= -1 && t < 4, "row_task entries must be in [-1, 4)");
-    ARG_CHECK((s < 0) == (t < 0), "a row names a slot and a task, or neither (-1 / -1)");
-    if (s < 0) continue;
-    ARG_CHECK(bank_complete(m, s), "row_slot names a slot that is not complete (4 tensors per layer since its last clear)");
-    ARG_CHECK(owner[t] < 0 || owner[t] == s, "one task is named by two slots in the same call");
-    owner[t] = s;
-    any = true;
+    RC(bank_pair_check("row", row_slot[r], row_task[r], owner));
+    RC(bank_entry_check(m, "row_slot", row_slot[r]));
+    any |= row_slot[r] >= 0;
   }
   AdapterBank* b = m->bank;
   HIP_CHECK(hipSetDevice(m->device));
   HIP_CHECK(hipMemcpyAsync(b->d_rows, row_slot, (size_t)m->cur_rows * 4, hipMemcpyHostToDevice, m->stream));
   HIP_CHECK(hipMemcpyAsync(b->d_task, row_task, (size_t)m->cur_rows * 4, hipMemcpyHostToDevice, m->stream));
-  const bool det = m->deterministic;
-  m->deterministic = true;
-  m->bank_rows = any ? b->d_rows : nullptr;
-  m->bank_train = true;
-  b->drop_now = !evaluate && b->dropout > 0.f;
-  int rc;
-  {
-    DetScope scope(m);
-    rc = model_forward_backward_rows(m, evaluate, b->d_task, grad_scale, seed, step);
-  }
-  m->bank_train = false;
-  m->bank_rows = nullptr;
-  m->deterministic = det;
-  return rc;
+  return bank_train_pass(m, evaluate, any ? b->d_rows : nullptr, nullptr, false, b->d_task, grad_scale, seed, step);
 }
 
 // The segment table of a packed call, checked on the host (rsys_adapter_forward_backward_packed and rsys_op_adapter_bank_segments): seg
 // [n_seg][5] = (row, first column, columns, slot, task) on rows of S interactions.  Fills the [rows][ceil(S / 32)] tile maps of slot and task
 // (-1 where no segment, or a base-model segment, lies) and says whether any segment names a slot.
 static int bank_segs_check(const int32_t* seg, int n_seg, int rows, int S, std::vector<int32_t>* tile_slot, std::vector<int32_t>* tile_task, bool* any) {
-  const int nt = (S + 31) / 32;
+  TileOwners tiles(rows, S);
   ARG_CHECK(seg != nullptr, "segment table is null");
-  ARG_CHECK(n_seg >= 1 && (long long)n_seg <= (long long)rows * nt && n_seg <= 65535, "n_seg must be in [1, rows * ceil(S / 32)]");
-  tile_slot->assign((size_t)rows * nt, -1); tile_task->assign((size_t)rows * nt, -1);
-  std::vector<unsigned char> owned((size_t)rows * nt, 0);
+  ARG_CHECK(n_seg >= 1 && (long long)n_seg <= (long long)rows * tiles.nt && n_seg <= 65535, "n_seg must be in [1, rows * ceil(S / 32)]");
   int owner[4] = {-1, -1, -1, -1};
   *any = false;
   for (int i = 0; i < n_seg; ++i) {
     const int32_t* g = seg + (size_t)i * 5;
-    const int row = g[0], c0 = g[1], cols = g[2], sl = g[3], t = g[4];
-    ARG_CHECK(row >= 0 && row < rows, "a segment's row is outside the resident batch");
-    ARG_CHECK(c0 >= 0 && c0 % 32 == 0, "a segment starts at an interaction column that is a multiple of 32");
-    ARG_CHECK(cols >= 1 && cols <= S - c0, "a segment lies inside its row");
-    ARG_CHECK(sl >= -1 && sl < RSYS_ADAPTER_SLOTS, "segment slots must be in [-1, RSYS_ADAPTER_SLOTS)");
-    ARG_CHECK(t >= -1 && t < 4, "segment tasks must be in [-1, 4)");
-    ARG_CHECK((sl < 0) == (t < 0), "a segment names a slot and a task, or neither (-1 / -1)");
-    for (int j = c0 / 32; j < (c0 + cols + 31) / 32; ++j) {
-      ARG_CHECK(!owned[(size_t)row * nt + j], "two segments share a 64-token tile");
-      owned[(size_t)row * nt + j] = 1;
-      (*tile_slot)[(size_t)row * nt + j] = sl; (*tile_task)[(size_t)row * nt + j] = t;
-    }
-    if (sl < 0) continue;
-    ARG_CHECK(owner[t] < 0 || owner[t] == sl, "one task is named by two slots in the same call");
-    owner[t] = sl;
-    *any = true;
+    ARG_CHECK(g[2] >= 1, "a segment lies inside its row, on at least one column");
+    RC(tiles.place("adapter bank", g[0], g[1], g[2], i));
+    RC(bank_pair_check("segment", g[3], g[4], owner));
+    *any |= g[3] >= 0;
   }
+  tile_slot->assign(tiles.owner.size(), -1); tile_task->assign(tiles.owner.size(), -1);
+  for (size_t k = 0; k < tiles.owner.size(); ++k)
+    if (tiles.owner[k] >= 0) { (*tile_slot)[k] = seg[(size_t)tiles.owner[k] * 5 + 3]; (*tile_task)[k] = seg[(size_t)tiles.owner[k] * 5 + 4]; }
   return RSYS_OK;
 }
 
 // rsys_adapter_forward_backward on packed rows: several users per row, each in a segment of whole 64-token tiles that names
 // its slot and task.  The caller guarantees the resident columns (one non-zero userid per segment, distinct within a row, zeros elsewhere).
 int adapter_forward_backward_packed(Model* m, int evaluate, const int32_t* seg, int n_seg, float grad_scale, uint64_t seed, uint64_t step) {
-  RC(bank_train_check_model(m));
-  ARG_CHECK(m->bank != nullptr && m->bank->train, "adapter bank training is not enabled (rsys_adapter_train_enable)");
-  ARG_CHECK(m->cur_rows > 0, "no batch uploaded");
-  RC(check_not_trimmed(m));
+  RC(bank_train_call_check(m));
   std::vector<int32_t> ts, tt;
   bool any = false;
   RC(bank_segs_check(seg, n_seg, m->cur_rows, m->S, &ts, &tt, &any));
-  for (int i = 0; i < n_seg; ++i)
-    if (seg[(size_t)i * 5 + 3] >= 0)
-      ARG_CHECK(bank_complete(m, seg[(size_t)i * 5 + 3]), "a segment names a slot that is not complete (4 tensors per layer since its last clear)");
+  for (int i = 0; i < n_seg; ++i) RC(bank_entry_check(m, "the segment table", seg[(size_t)i * 5 + 3]));
   AdapterBank* b = m->bank;
-  HIP_CHECK(hipSetDevice(m->device));
-  const int nta = (m->Sa + 31) / 32, nt = (m->S + 31) / 32;   // (full rows: nt == nta)
-  if (!b->d_tiles) DALLOC(b->d_tiles, (int64_t)m->rows_max * nta * 4);
-  if (!b->d_tile_task) DALLOC(b->d_tile_task, (int64_t)m->rows_max * nta * 4);
-  if (!b->d_segs) DALLOC(b->d_segs, (int64_t)m->rows_max * nta * 5 * 4);
+  RC(bank_first_use(m, BANK_BUF_TILES | BANK_BUF_PACK));   // (full rows: the caller's geometry is the resident one)
   HIP_CHECK(hipStreamSynchronize(m->stream));   // (the previous call's copies have read h_pack, its kernels the partials)
   if (n_seg > b->seg_cap) {
     float *na = nullptr, *nb = nullptr;
@@ -1026,7 +885,7 @@ int adapter_forward_backward_packed(Model* m, int evaluate, const int32_t* seg, 
     (void)hipFree(b->segA); (void)hipFree(b->segB);
     b->segA = na; b->segB = nb; b->seg_cap = n_seg;
   }
-  const size_t ntile = (size_t)m->cur_rows * nt;
+  const size_t ntile = ts.size();
   b->h_pack.resize(2 * ntile + (size_t)n_seg * 5);
   std::copy(ts.begin(), ts.end(), b->h_pack.begin());
   std::copy(tt.begin(), tt.end(), b->h_pack.begin() + ntile);
@@ -1035,23 +894,7 @@ int adapter_forward_backward_packed(Model* m, int evaluate, const int32_t* seg, 
   HIP_CHECK(hipMemcpyAsync(b->d_tile_task, b->h_pack.data() + ntile, ntile * 4, hipMemcpyHostToDevice, m->stream));
   HIP_CHECK(hipMemcpyAsync(b->d_segs, b->h_pack.data() + 2 * ntile, (size_t)n_seg * 5 * 4, hipMemcpyHostToDevice, m->stream));
   b->n_seg = n_seg;
-  const bool det = m->deterministic;
-  m->deterministic = true;
-  m->bank_rows = nullptr;
-  m->bank_tiles = any ? b->d_tiles : nullptr;
-  m->bank_train = true;
-  m->bank_packed = true;   // masks per tile; the last layer runs dense (its compact order would mix segments inside a work item)
-  b->drop_now = !evaluate && b->dropout > 0.f;
-  int rc;
-  {
-    DetScope scope(m);
-    rc = model_forward_backward_rows(m, evaluate, b->d_tile_task, grad_scale, seed, step);
-  }
-  m->bank_packed = false;
-  m->bank_train = false;
-  m->bank_tiles = nullptr;
-  m->deterministic = det;
-  return rc;
+  return bank_train_pass(m, evaluate, nullptr, any ? b->d_tiles : nullptr, true, b->d_tile_task, grad_scale, seed, step);
 }
 
 template <typename T>
@@ -1081,8 +924,8 @@ int adapter_bank_op(int dtype, int stages, int train, int rows, int Ttok, int D,
                     int64_t stream, const int32_t* row_slot, const void* bankA, const void* bankB, const void* xn, void* La, void* qkv, const void* dqkv,
                     void* dLa, void* dxn, float* partA, float* partB, float* gA, float* gB, const float* rope_cos, const float* rope_sin,
                     const int32_t* rope_pos, int rope_rows, int tiles, int n_seg) {
-  // (tiles == 1, rsys_op_adapter_bank_tiles: row_slot is the tile map [rows][ceil(Ttok / 64)] and the two forward stages run in their per-tile form;
-  //  tiles == 2, rsys_op_adapter_bank_segments: row_slot is the segment table [n_seg][5], every stage runs in its per-tile / per-segment form)
+  // (tiles == 1, rsys_op_adapter_bank_tiles: row_slot is the tile map [rows][ceil(Ttok / 64)] and the two forward stages take their slot per tile;
+  //  tiles == 2, rsys_op_adapter_bank_segments: row_slot is the segment table [n_seg][5], the token stages take their slot per tile, the partials and sums their range per segment)
   ARG_CHECK(tiles != 1 || ((stages & ~3) == 0 && train == 0), "rsys_op_adapter_bank_tiles: stages 1 and 2 only (the forward, train = 0)");
   ARG_CHECK(dtype == RSYS_DTYPE_BF16 || dtype == RSYS_DTYPE_FP32, "rsys_op_adapter_bank: dtype fp32 or bf16");
   ARG_CHECK(stages >= 1 && stages <= 127, "rsys_op_adapter_bank: stages is a mask of bits 1 .. 64");

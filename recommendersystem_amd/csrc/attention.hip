@@ -1737,22 +1737,18 @@ template <typename T, int HD>
 static int attn_cand_hd(const CandAttnParams& p, hipStream_t s) {
   using C = ACfg<T, HD>;
   const size_t sm = sizeof(T) * 4 * C::TILE;
-  static bool set = false;
-  if (!set) {
+  static bool set[64] = {};   // (the attribute belongs to the device: once per device of this process, all four instantiations)
+  int dev = 0;
+  HIP_CHECK(hipGetDevice(&dev));
+  if (dev < 0 || dev >= 64 || !set[dev]) {
     HIP_CHECK(hipFuncSetAttribute((const void*)attn_cand_kernel<T, HD, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm));
     HIP_CHECK(hipFuncSetAttribute((const void*)attn_cand_kernel<T, HD, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm));
-    set = true;
+    HIP_CHECK(hipFuncSetAttribute((const void*)attn_cand_tiles_kernel<T, HD, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm));
+    HIP_CHECK(hipFuncSetAttribute((const void*)attn_cand_tiles_kernel<T, HD, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm));
+    if (dev >= 0 && dev < 64) set[dev] = true;
   }
   const int nt = (p.T + 63) / 64;
   if (p.tile_seg) {   // packed rows: the same grid, the per-tile form
-    static bool set_t[64] = {};   // (the attribute belongs to the device: once per device of this process)
-    int dev = 0;
-    HIP_CHECK(hipGetDevice(&dev));
-    if (dev < 0 || dev >= 64 || !set_t[dev]) {
-      HIP_CHECK(hipFuncSetAttribute((const void*)attn_cand_tiles_kernel<T, HD, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm));
-      HIP_CHECK(hipFuncSetAttribute((const void*)attn_cand_tiles_kernel<T, HD, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm));
-      if (dev >= 0 && dev < 64) set_t[dev] = true;
-    }
     if (p.H / p.KV == 2 && HD <= 64) hipLaunchKernelGGL((attn_cand_tiles_kernel<T, HD, 2>), dim3(nt * (p.H / 2) * p.rows), dim3(256), sm, s, p);
     else hipLaunchKernelGGL((attn_cand_tiles_kernel<T, HD, 1>), dim3(nt * p.H * p.rows), dim3(256), sm, s, p);
     HIP_CHECK(hipGetLastError());

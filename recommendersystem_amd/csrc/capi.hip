@@ -9,11 +9,10 @@
 
 #include "comm.hpp"
 #include "encoder_handle.hpp"
-#include "model.hpp"
+#include "model_internal.hpp"
 
 namespace rsys {
 static thread_local std::string g_err;
-#define RC(expr) do { int _rc = (expr); if (_rc != RSYS_OK) return _rc; } while (0)
 void set_error(const std::string& msg) { g_err = msg; }
 }  // namespace rsys
 
@@ -1080,19 +1079,17 @@ int32_t rsys_op_attention_cached_tiles(int32_t dtype, int32_t rows, int32_t T, i
   ARG_CHECK(dtype == RSYS_DTYPE_BF16 || dtype == RSYS_DTYPE_FP32, "dtype: fp32 or bf16");
   ARG_CHECK(qkv && cache && seg && O && KV >= 1 && H >= 1 && rows >= 1 && T >= 8 && n_slots >= 1, "null or empty");
   if (Tc == 0) Tc = T;
-  const int nt = (T + 63) / 64;
-  ARG_CHECK(n_seg >= 1 && n_seg <= rows * nt, "1 <= n_seg <= rows x ceil(T / 64)");
-  std::vector<int> tab((size_t)4 * n_seg + (size_t)rows * nt, -1);
+  TileOwners tiles(rows, T / 2);   // (a row of T tokens holds T / 2 interaction columns; ceil(T / 64) tiles)
+  ARG_CHECK(n_seg >= 1 && n_seg <= rows * tiles.nt, "1 <= n_seg <= rows x ceil(T / 64)");
+  std::vector<int> tab((size_t)4 * n_seg, -1);
   for (int i = 0; i < n_seg; ++i) {
     const int r = seg[5 * i], ft = seg[5 * i + 1], nc = seg[5 * i + 2], sl = seg[5 * i + 3], nh = seg[5 * i + 4];
-    ARG_CHECK(r >= 0 && r < rows && ft >= 0 && nc >= 1 && 64 * (long long)ft + 2 * (long long)nc <= T, "segment outside its row");
+    ARG_CHECK(ft >= 0 && ft < tiles.nt && nc >= 1, "segment outside its row");
     ARG_CHECK(sl >= 0 && sl < n_slots && nh >= 0 && 2 * nh <= Tc, "segment's slot or n_hist out of range");
-    for (int t = ft; t < ft + (2 * nc + 63) / 64; ++t) {
-      ARG_CHECK(tab[(size_t)4 * n_seg + (size_t)r * nt + t] < 0, "segments overlap");
-      tab[(size_t)4 * n_seg + (size_t)r * nt + t] = i;
-    }
+    RC(tiles.place("rsys_op_attention_cached_tiles", r, 32 * ft, nc, i));
     tab[4 * i] = sl; tab[4 * i + 1] = nh; tab[4 * i + 2] = ft; tab[4 * i + 3] = nc;
   }
+  tab.insert(tab.end(), tiles.owner.begin(), tiles.owner.end());
   int* d_tab = nullptr;
   HIP_CHECK(hipMalloc((void**)&d_tab, tab.size() * 4));
   hipError_t e = hipMemcpy(d_tab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice);

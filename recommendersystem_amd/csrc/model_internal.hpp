@@ -253,6 +253,27 @@ static void shard_medium_range(const Model* m, int med, int* len, int* col0, int
   if (*len == 0) { *col0 = 0; *row = 0; }
 }
 
+// Packed rows: a segment owns whole 64-token tiles -- 32 interaction columns each -- of one row of S columns.
+// owner [rows][nt] names the segment of every tile, -1 while it is free.  place() gives the tiles of columns [c0, c0 + n) of `row` to
+// segment `id` and refuses a row outside the batch, a c0 that is negative or off a tile boundary, an end past the row and a tile that is
+// taken; n == 0 places nothing.  `who` starts the refusal's text.  Host only: callers check every segment before their first launch.
+struct TileOwners {
+  int rows, S, nt;
+  std::vector<int> owner;
+  TileOwners(int rows_, int S_) : rows(rows_), S(S_), nt((S_ + 31) / 32), owner((size_t)rows_ * ((S_ + 31) / 32), -1) {}
+  int place(const char* who, int row, int c0, int n, int id) {
+    const std::string w = std::string(who) + ": ";
+    ARG_CHECK(row >= 0 && row < rows, w + "a segment's row is outside the resident batch");
+    ARG_CHECK(c0 >= 0 && c0 % 32 == 0, w + "a segment starts at an interaction column that is a multiple of 32");
+    ARG_CHECK(n >= 0 && (long long)c0 + n <= S, w + "a segment lies inside its row");
+    for (int t = c0 / 32; t < (c0 + n + 31) / 32; ++t) {
+      ARG_CHECK(owner[(size_t)row * nt + t] < 0, w + "two segments share a 64-token tile");
+      owner[(size_t)row * nt + t] = id;
+    }
+    return RSYS_OK;
+  }
+};
+
 // ---- defined in model_forward.hip
 template <typename T> int table_forward(Model* m);
 template <typename T> int forward_trunk(Model* m);

@@ -226,7 +226,7 @@ int model_rank_cache_candidates(Model* m, const int32_t* row_adapter, const int3
 // ------------------------------------------------------------------ packed rows
 // Several users per row, each in a segment of whole 64-token tiles.  The two calls below check the caller's descriptors on the host, write
 // the device tables (segments, tile map, RoPE positions, selection) and run the passes above with rc_nseg set: the trunk is the same, the
-// copy and the candidate attention take their per-segment / per-tile forms, the adapter bank its per-tile form (adapter_bind_tiles).
+// copy and the candidate attention take their per-segment / per-tile forms, the adapter bank its slot per tile (adapter_bind_tiles).
 static int rc_check_packed(Model* m, int n_seg, const int32_t* seg) {
   RC(rc_check_model(m));
   ARG_CHECK(m->cfg.finetune == 0, "ranking cache, packed rows: a base model (finetune = 0)");
@@ -235,27 +235,15 @@ static int rc_check_packed(Model* m, int n_seg, const int32_t* seg) {
   ARG_CHECK(seg != nullptr && n_seg >= 1 && n_seg <= rc_max_seg(m), "ranking cache, packed rows: 1 <= n_seg <= max_rows x ceil(S / 32) descriptors");
   return RSYS_OK;
 }
-// marks the tiles [c0 / 32, ceil((c0 + n) / 32)) of `row` in used ([rows][nt]); a descriptor off a tile boundary, across the row's end or on a
-// taken tile is refused
-static int rc_place_segment(Model* m, std::vector<int>& used, int nt, int row, int c0, int n, int id) {
-  ARG_CHECK(row >= 0 && row < m->cur_rows, "ranking cache, packed rows: row outside the resident batch");
-  ARG_CHECK(c0 >= 0 && c0 % 32 == 0, "ranking cache, packed rows: a segment starts at a column that is a multiple of 32");
-  ARG_CHECK((long long)c0 + n <= m->S, "ranking cache, packed rows: a segment must end inside its row");
-  for (int t = c0 / 32; t < (c0 + n + 31) / 32; ++t) {
-    ARG_CHECK(used[(size_t)row * nt + t] < 0, "ranking cache, packed rows: segments overlap");
-    used[(size_t)row * nt + t] = id;
-  }
-  return RSYS_OK;
-}
 // seg_adapter [n_seg] (or null) -> the per-tile binding, every slot on the tiles `used` gives its segment
-static int rc_bind_segments(Model* m, const int32_t* seg_adapter, int n_seg, const std::vector<int>& used, int nt) {
+static int rc_bind_segments(Model* m, const int32_t* seg_adapter, int n_seg, const TileOwners& used) {
   if (!seg_adapter) return RSYS_OK;
   const int nta = (m->Sa + 31) / 32;
   for (int i = 0; i < n_seg; ++i) ARG_CHECK(seg_adapter[i] >= -1 && seg_adapter[i] < RSYS_ADAPTER_SLOTS, "seg_adapter entries must be in [-1, RSYS_ADAPTER_SLOTS)");
   std::vector<int32_t> tiles((size_t)m->cur_rows * nta, -1);
   for (int r = 0; r < m->cur_rows; ++r)
-    for (int t = 0; t < nt; ++t)
-      if (used[(size_t)r * nt + t] >= 0) tiles[(size_t)r * nta + t] = seg_adapter[used[(size_t)r * nt + t]];
+    for (int t = 0; t < used.nt; ++t)
+      if (used.owner[(size_t)r * used.nt + t] >= 0) tiles[(size_t)r * nta + t] = seg_adapter[used.owner[(size_t)r * used.nt + t]];
   return adapter_bind_tiles(m, tiles.data());   // (range and completeness of every entry; copies the map before it returns)
 }
 
@@ -266,19 +254,18 @@ static int rc_bind_segments(Model* m, const int32_t* seg_adapter, int n_seg, con
 int rank_cache_store_packed_rows(Model* m, const int32_t* seg_adapter, int n_seg, const int32_t* seg, int* d_pos) {
   RC(rc_check_packed(m, n_seg, seg));
   ARG_CHECK(d_pos != nullptr, "ranking cache, packed rows: null positions");
-  const int rows = m->cur_rows, nt = (m->S + 31) / 32;
-  std::vector<int> used((size_t)rows * nt, -1);
+  TileOwners used(m->cur_rows, m->S);
   std::vector<char> seen((size_t)m->rc_slots, 0);
   for (int i = 0; i < n_seg; ++i) {
     const int row = seg[4 * i], c0 = seg[4 * i + 1], nh = seg[4 * i + 2], sl = seg[4 * i + 3];
     ARG_CHECK(nh >= 0 && nh <= m->S, "ranking cache: n_hist must be in [0, the resident rows' length]");
-    RC(rc_place_segment(m, used, nt, row, c0, nh, i));
+    RC(used.place("ranking cache, packed rows", row, c0, nh, i));
     ARG_CHECK(sl >= 0 && sl < m->rc_slots, "ranking cache: slot outside the reserve");
     ARG_CHECK(!seen[sl], "ranking cache: the slots of one store call must be distinct");
     seen[sl] = 1;
   }
   HIP_CHECK(hipSetDevice(m->device));
-  RC(rc_bind_segments(m, seg_adapter, n_seg, used, nt));
+  RC(rc_bind_segments(m, seg_adapter, n_seg, used));
   int* const saved_pos = m->d_rope_pos; const bool saved_has = m->has_rope_pos;
   auto run = [&]() -> int {
     HIP_CHECK(hipMemcpyAsync(m->rc_seg, seg, (size_t)4 * n_seg * 4, hipMemcpyHostToDevice, m->stream));
@@ -325,8 +312,8 @@ int model_rank_cache_store_packed(Model* m, const int32_t* seg_adapter, int n_se
 int model_rank_cache_candidates_packed(Model* m, const int32_t* seg_adapter, int n_seg, const int32_t* seg, float* out) {
   RC(rc_check_packed(m, n_seg, seg));
   ARG_CHECK(out != nullptr, "ranking cache: null output");
-  const int rows = m->cur_rows, T = m->T, nt = (m->S + 31) / 32;
-  std::vector<int> used((size_t)rows * nt, -1);
+  const int rows = m->cur_rows, T = m->T;
+  TileOwners used(rows, m->S);
   int64_t ntok = 0;
   for (int i = 0; i < n_seg; ++i) {
     const int row = seg[4 * i], c0 = seg[4 * i + 1], nc = seg[4 * i + 2], sl = seg[4 * i + 3];
@@ -334,7 +321,7 @@ int model_rank_cache_candidates_packed(Model* m, const int32_t* seg_adapter, int
     ARG_CHECK(m->rc_nhist[sl] >= 0, "ranking cache: slot never stored");
     ARG_CHECK(m->rc_nhist[sl] <= m->Sa - 1, "ranking cache: candidates run at position n_hist, which must stay below max_sequence_length");
     ARG_CHECK(nc >= 1 && nc <= m->S, "ranking cache: n_cand must be in [1, the resident rows' length]");
-    RC(rc_place_segment(m, used, nt, row, c0, nc, i));
+    RC(used.place("ranking cache, packed rows", row, c0, nc, i));
     ntok += nc;
   }
   HIP_CHECK(hipSetDevice(m->device));
@@ -351,9 +338,8 @@ int model_rank_cache_candidates_packed(Model* m, const int32_t* seg_adapter, int
     for (int c = c0; c < std::min(m->S, 32 * ((c0 + nc + 31) / 32)); ++c) { pos[(size_t)row * T + 2 * c] = 2 * nh; pos[(size_t)row * T + 2 * c + 1] = 2 * nh + 1; }
     for (int j = 0; j < nc; ++j) sel[k++] = row * T + 2 * (c0 + j) + 1;
   }
-  for (int r = 0; r < rows; ++r)
-    for (int t = 0; t < nt; ++t) tab[(size_t)4 * max_seg + (size_t)r * nt + t] = used[(size_t)r * nt + t];
-  RC(rc_bind_segments(m, seg_adapter, n_seg, used, nt));
+  std::copy(used.owner.begin(), used.owner.end(), tab.begin() + (size_t)4 * max_seg);
+  RC(rc_bind_segments(m, seg_adapter, n_seg, used));
   int* const d_pos = m->rc_rows + 3 * m->rows_max;
   int* const d_sel = (int*)m->gf;   // (as rsys_infer_select: room for every token of the batch)
   int* const saved_pos = m->d_rope_pos; const bool saved_has = m->has_rope_pos;

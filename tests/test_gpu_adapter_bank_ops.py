@@ -266,7 +266,7 @@ def test_stages_alone(case, dt):
     act = ACTIVE
     qv, kc = qv_cols(case)
     what = f"case {case}"
-    # ---- stage A, inference form; the training form at p = 0 must give the same bits
+    # ---- stage A, the inference kernel (DROP = false); the training one (DROP = true) at p = 0 must give the same bits
     out = run(case, dt, c, A)
     untouched(case, out, A)
     check("a", dt, out["La"][act], o["La64"][act], (c_stage_a(D, dt) + 1) * U * o["La_mag"][act], True, what)

@@ -1,6 +1,8 @@
 """GPU: the adapter bank's kernels in the forms of packed finetune rows (csrc/adapter_bank.hip) through
-rsys_op_adapter_bank_segments (rsys_debug.h): the per-tile token stages (a_train_tiles, b_tiles, dla_tiles, dx_tiles), the per-segment
-partials (da_seg, db_seg) and the segment reduction, in fp32 and bf16, on sentinel-filled outputs with guard tails.
+rsys_op_adapter_bank_segments (rsys_debug.h): the token stages with the slot of the workgroup's tile (a with DROP, b, dla, dx; printed as
+a_train_tiles, b_tiles, dla_tiles, dx_tiles), the partials per segment (da, db; printed as da_seg, db_seg) and the reduction over the
+segment table (segs_reduce) -- the tile / segment path of each stage's one kernel -- in fp32 and bf16, on sentinel-filled outputs with
+guard tails.
 
   case  Ttok  D   H KV hd   rows  what it covers
   1      72  160  5 1  32    3    a ragged second tile (8 tokens); two one-tile segments in a row; a row whose second tile nobody owns

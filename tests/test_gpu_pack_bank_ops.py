@@ -1,5 +1,6 @@
-"""GPU: the per-tile forward forms of the adapter bank's two kernels (csrc/adapter_bank.hip: adapter_bank_a_tiles_kernel /
-adapter_bank_b_tiles_kernel) through rsys_op_adapter_bank_tiles, bit for bit against the row-slot kernels.
+"""GPU: the adapter bank's two forward kernels with a slot per 64-token tile (csrc/adapter_bank.hip: adapter_bank_a_kernel /
+adapter_bank_b_kernel with a tile map in their BankLookup) through rsys_op_adapter_bank_tiles, bit for bit against the same
+kernels with a slot per row: the two lookup paths of one kernel pinned against each other.
 
 The expected output needs no arithmetic of its own: for every slot s the tile map names, rsys_op_adapter_bank runs with row_slot = s on
 every row, and each 64-token tile is taken from the run of its slot.  La and the q and v columns of qkv must be equal bit for bit; tiles
