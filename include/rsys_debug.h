@@ -378,6 +378,61 @@ int32_t rsys_op_shard_rows(int32_t stages, const int32_t* skey, const int32_t* s
                            int32_t table_rows, const int32_t* ids, int32_t sub, float* packed, int32_t n, int32_t D, const int32_t* count,
                            const int32_t* m_matchedid, const int32_t* userid, const int32_t* m_tmid, int32_t Ntok, const float* Frem,
                            int32_t frem_rows, float* x0, int32_t* uid_t, int32_t* tm_t);
+/* the index and compaction kernels (csrc/compact.hip, the position selection, row movers and column sums of csrc/elementwise.hip, the batched
+ * transpose of csrc/optim.hip), unit-test access on caller-provided device buffers: every call runs the launcher the model path calls,
+ * unchanged, on the null stream and synchronises.  RSYS_ERR_ARG before anything is launched where an argument is out of range; index arrays
+ * that address a caller buffer are copied back once for that.  These kernels decide WHICH rows the products run on: their integer outputs
+ * and the rows they move are exact, whatever the launch shape.
+ * rsys_op_select_positions: per task t < ntask (1 .. 4) of w f32 [ntask][N]: idx [ntask][topk] = the positions with w > 0 in ascending
+ *   order, then the others ascending, CUT AT topk (slot topk and later do not exist and are not written); npos[t] = min(#(w > 0), topk);
+ *   stats [ntask][2] = (sum of w over the selected positions, sum over all).  form 0: launch_select_positions_batch (one workgroup per task),
+ *   form 1: launch_select_positions_chunked (32 chunks per task, scratch allocated by the call); neither is restricted by N here (the model
+ *   takes the chunked form from N >= 4096).  1 <= topk <= N <= 2^24 (the chunked form counts in fp32).
+ * rsys_op_token_union: idx int32 [ntask][cap], npos int32 [ntask] (device).  bits [ceil(NT / 32)] (int32 words read as bit patterns): bit (tok & 31) of word tok >> 5 is
+ *   set iff tok = 2 idx[t][r] + (t & 1) for some task t and r < npos[t]; pre [ceil(NT / 32)]: the number of set bits in the words before;
+ *   *nsel their total.  Bit t of null_mask passes task t with a null list (skipped; its npos is not read).  The call checks 0 <= npos[t] <= cap
+ *   and 0 <= 2 idx + 1 < NT for the live entries (both tokens of a position exist); 1 <= NT <= 2^19 is the launcher's own bound (the
+ *   bitmap lives in LDS).
+ * rsys_op_selected_first: bits / pre as above over the B T tokens of B rows (the call checks that pre is the exclusive prefix count of bits
+ *   over those words and that the total is <= sel_cap; B T <= 2^19, T <= 4096), uid / tm int32 [B T], rope_pos int32 [B T] or null.
+ *   slot [B T] = rank of the token among the selected (ascending token order) or -1; sel [sel_cap]: sel[slot[t]] = t, later entries untouched.
+ *   Placement rule: inside row b the selected tokens come first in their original order, then the others in theirs; perm [B T] = the
+ *   (global) token at each place, uid_p / tm_p = its ids, pos_p = its rope_pos (null: its index inside the row), slot_p = its slot,
+ *   sel_p [sel_cap]: sel_p[slot_p[p]] = p.  q_active [B] = ceil(selected tokens of the row / 64).  Under RSYS_TOP_ORDER=0 (read as parsed at
+ *   the call) the order is the identity (perm[p] = p) and q_active = ceil(T / 64); slot / sel are the same.
+ * rsys_op_rows: the row movers; T = dtype (fp32 / bf16; kinds 4 and 6 are fp32 only), D and every ld a multiple of 16 bytes of T, ld >= D.
+ *   A "token" is 2 idx[r] + parity, parity 0 / 1.  The launchers size their grid from n (kind 0: from cap): n >= 1, cap >= 1.
+ *   kind 0 gather_rows_sel: dst [cap = dst_rows][D] row r < *count = src [src_rows][ld] row map[r]; rows [*count, min(cap, round_up(*count,
+ *     256))) are zeros; later rows untouched.  0 <= *count <= min(cap, map_len), map values in [0, src_rows).
+ *   kind 1 scatter_rows_fill: n batch rows of Tseq places, dst [n Tseq = dst_rows][ld], map = slot_p [map_len = dst_rows], count = q_active
+ *     [n]: place p < min(Tseq, 64 q_active[b]) of row b = src [src_rows][D] row slot_p, or zeros where slot_p = -1; the places behind are
+ *     untouched, and so are columns [D, ld).
+ *   kind 2 scatter_rows_map: dst [dst_rows][ld] row map[r] = src [n][D] row r; map distinct, in [0, dst_rows); other rows untouched.
+ *   kind 3 gather_rows_slot: dst [n][D] row r = src [src_rows][D] row map[token] (map = slot [map_len]), zeros where that is -1.
+ *   kind 4 scatter_rows_add_slot: dst [dst_rows][D] row map[token] += src [n][D] row r for r < min(n, *count), skipped where -1.
+ *   kind 5 gather_rows: dst [n][D] row r = src [src_rows][ld] row token.
+ *   kind 6 scatter_rows_add: dst [dst_rows][ld] row token += src [n][D] row r for r < min(n, *count) (count null: r < n).
+ *   Kinds 4 and 6 take distinct destination rows among the live r (one task at a time in the model); tokens and slots inside their arrays.
+ * rsys_op_colsum: colsum [D] += column sums of src f32 [rows][ld] (1 <= rows <= 2^24).  kind 0 launch_colsum_add (D = cols, any ld >= D);
+ *   kind 1 launch_cast_colsum (ld == D, D / 4 divides 1024): also dst bf16 [rows][D] = src rounded to nearest even; kind 2
+ *   launch_cast_transpose_colsum (ld == D, D % 64 == 0, ldt % 8 == 0, ldt >= round_up(rows, 64)): also dst bf16 [D][ldt], dst[c][r] = src[r][c]
+ *   rounded, columns [rows, round_up(rows, 64)) zeros, columns behind untouched.  deterministic != 0: per-workgroup partials added in
+ *   workgroup order, scratch sized from the launcher's grid; RSYS_ERR_STATE if that branch did not run.
+ * rsys_op_transpose_bf16: one launch_transpose_bf16 of n_jobs (1 .. 64) jobs given as HOST arrays: dst[j] bf16 [cols][ld_dst] = the transpose of
+ *   src[j] bf16 [rows][ld_src] (device pointers, 16-byte aligned); ld_src >= cols, ld_dst >= rows, both multiples of 8 (16-byte row strides:
+ *   the kernel moves 8 elements per access); the padding columns of dst are untouched. */
+int32_t rsys_op_select_positions(int32_t form, int32_t ntask, const float* w, int32_t N, int32_t topk, int32_t* idx, float* stats, int32_t* npos);
+int32_t rsys_op_token_union(int32_t ntask, const int32_t* idx, int32_t cap, const int32_t* npos, int32_t null_mask, int32_t NT, int32_t* bits,
+                            int32_t* pre, int32_t* nsel);
+int32_t rsys_op_selected_first(const int32_t* bits, const int32_t* pre, int32_t B, int32_t T, const int32_t* uid, const int32_t* tm,
+                               const int32_t* rope_pos, int32_t* slot, int32_t* sel, int32_t sel_cap, int32_t* perm, int32_t* uid_p,
+                               int32_t* tm_p, int32_t* pos_p, int32_t* slot_p, int32_t* sel_p, int32_t* q_active);
+int32_t rsys_op_rows(int32_t kind, int32_t dtype, const void* src, int64_t src_rows, void* dst, int64_t dst_rows, int64_t ld, int32_t n, int32_t D,
+                     const int32_t* map, int64_t map_len, const int32_t* idx, int32_t parity, const int32_t* count, int32_t Tseq);
+int32_t rsys_op_colsum(int32_t kind, int32_t deterministic, const float* src, int64_t ld, int64_t rows, int32_t D, float* colsum, void* dst,
+                       int64_t ldt);
+int32_t rsys_op_transpose_bf16(int32_t n_jobs, const void* const* src, void* const* dst, const int32_t* rows, const int32_t* cols,
+                               const int64_t* ld_src, const int64_t* ld_dst);
 
 #ifdef __cplusplus
 }

@@ -247,6 +247,13 @@ _SIGS = [
                                + [_P] * 9 + [C.c_int32, C.c_int64, C.c_int32, C.c_int32] + [_P] * 4),
     ("rsys_op_shard_rows", C.c_int32, [C.c_int32, _P, _P, C.c_int32, C.c_int32] + [_P] * 5 + [C.c_int32, _P, _P, C.c_int64, C.c_int32, _P,
                                        C.c_int32, _P, C.c_int32, C.c_int32] + [_P] * 4 + [C.c_int32, _P, C.c_int32, _P, _P, _P]),
+    ("rsys_op_select_positions", C.c_int32, [C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, _P, _P, _P]),
+    ("rsys_op_token_union", C.c_int32, [C.c_int32, _P, C.c_int32, _P, C.c_int32, C.c_int32, _P, _P, _P]),
+    ("rsys_op_selected_first", C.c_int32, [_P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, C.c_int32] + [_P] * 7),
+    ("rsys_op_rows", C.c_int32, [C.c_int32, C.c_int32, _P, C.c_int64, _P, C.c_int64, C.c_int64, C.c_int32, C.c_int32, _P, C.c_int64, _P,
+                                 C.c_int32, _P, C.c_int32]),
+    ("rsys_op_colsum", C.c_int32, [C.c_int32, C.c_int32, _P, C.c_int64, C.c_int64, C.c_int32, _P, _P, C.c_int64]),
+    ("rsys_op_transpose_bf16", C.c_int32, [C.c_int32] + [_P] * 6),
     ("rsys_step_mark", C.c_int32, [_P]),
     ("rsys_step_marks_get", C.c_int32, [_P, _P, C.c_int32, C.POINTER(C.c_int32)]),
     ("rsys_op_timing", C.c_int32, [_P, C.c_int32]),

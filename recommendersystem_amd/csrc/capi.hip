@@ -1541,6 +1541,195 @@ int32_t rsys_op_shard_rows(int32_t stages, const int32_t* skey, const int32_t* s
   return RSYS_OK;
 }
 
+// ---------------------------------------------------------------- the index and compaction kernels on caller-provided buffers
+// (compact.hip, the position selection, row movers and column sums of elementwise.hip, the batched transpose of optim.hip).  Each call
+// runs the production launcher unchanged on the null stream and synchronises; index arrays that address a caller buffer are copied back
+// once and checked before anything is launched.
+namespace {
+struct HookScratch {   // device scratch of one hook call, freed on every return path
+  void* p = nullptr;
+  ~HookScratch() { if (p) hipFree(p); }
+};
+}  // namespace
+
+int32_t rsys_op_select_positions(int32_t form, int32_t ntask, const float* w, int32_t N, int32_t topk, int32_t* idx, float* stats,
+                                 int32_t* npos) {
+  switches_parse();
+  ARG_CHECK(form == 0 || form == 1, "rsys_op_select_positions: form 0 (one workgroup per task) or 1 (chunked)");
+  ARG_CHECK(w && idx && stats && npos && ntask >= 1 && ntask <= 4 && N >= 1 && N <= (1 << 24) && topk >= 1 && topk <= N,
+            "rsys_op_select_positions: 1..4 tasks, 1 <= topk <= N <= 2^24");
+  const float* ws[4]; int* is[4]; float* sts[4]; int* nps[4];
+  for (int i = 0; i < ntask; ++i) { ws[i] = w + (long long)i * N; is[i] = idx + (long long)i * topk; sts[i] = stats + 2 * i; nps[i] = npos + i; }
+  HookScratch scratch;
+  if (form == 1) {
+    HIP_CHECK(hipMalloc(&scratch.p, 3 * 4 * 32 * 4));   // 3 arrays of 4 tasks x 32 chunks (launch_select_positions_chunked)
+    RC(launch_select_positions_chunked(ntask, ws, N, topk, is, sts, nps, scratch.p, nullptr));
+  } else {
+    RC(launch_select_positions_batch(ntask, ws, N, topk, is, sts, nps, nullptr));
+  }
+  HIP_CHECK(hipDeviceSynchronize());
+  return RSYS_OK;
+}
+
+int32_t rsys_op_token_union(int32_t ntask, const int32_t* idx, int32_t cap, const int32_t* npos, int32_t null_mask, int32_t NT, int32_t* bits,
+                            int32_t* pre, int32_t* nsel) {
+  switches_parse();
+  ARG_CHECK(idx && npos && bits && pre && nsel && ntask >= 1 && ntask <= 4 && cap >= 1 && NT >= 1 && null_mask >= 0 && null_mask < 16,
+            "rsys_op_token_union: arguments");
+  std::vector<int> hn, hi;
+  RC(hook_ints(npos, ntask, hn));
+  const int* ips[4]; const int* nps[4];
+  for (int ti = 0; ti < ntask; ++ti) {
+    const bool null_task = (null_mask >> ti) & 1;
+    ips[ti] = null_task ? nullptr : idx + (long long)ti * cap; nps[ti] = npos + ti;
+    if (null_task) continue;
+    ARG_CHECK(hn[ti] >= 0 && hn[ti] <= cap, "rsys_op_token_union: 0 <= npos <= cap");
+    RC(hook_ints(idx + (long long)ti * cap, hn[ti], hi));
+    for (int i : hi) ARG_CHECK(i >= 0 && 2LL * i + 1 < NT, "rsys_op_token_union: a live position outside [0, NT / 2)");
+  }
+  RC(launch_token_union(ips, nps, ntask, NT, (unsigned int*)bits, pre, nsel, nullptr));
+  HIP_CHECK(hipDeviceSynchronize());
+  return RSYS_OK;
+}
+
+int32_t rsys_op_selected_first(const int32_t* bits, const int32_t* pre, int32_t B, int32_t T, const int32_t* uid, const int32_t* tm,
+                               const int32_t* rope_pos, int32_t* slot, int32_t* sel, int32_t sel_cap, int32_t* perm, int32_t* uid_p,
+                               int32_t* tm_p, int32_t* pos_p, int32_t* slot_p, int32_t* sel_p, int32_t* q_active) {
+  switches_parse();
+  ARG_CHECK(bits && pre && uid && tm && slot && sel && perm && uid_p && tm_p && pos_p && slot_p && sel_p && q_active && B >= 1 && T >= 1 &&
+                T <= 4096 && sel_cap >= 0 && (long long)B * T <= (1 << 19),
+            "rsys_op_selected_first: arguments (T <= 4096, B T <= 2^19)");
+  const long long nw = ((long long)B * T + 31) / 32;
+  std::vector<int> hb, hp;
+  RC(hook_ints(bits, nw, hb)); RC(hook_ints(pre, nw, hp));
+  long long run = 0;   // sel / sel_p are addressed by pre[w] + a count inside word w
+  for (long long w = 0; w < nw; ++w) {
+    ARG_CHECK(hp[(size_t)w] == run, "rsys_op_selected_first: pre is not the exclusive prefix count of bits");
+    run += __builtin_popcount((unsigned)hb[(size_t)w]);
+  }
+  ARG_CHECK(run <= sel_cap, "rsys_op_selected_first: more selected tokens than sel_cap");
+  RC(launch_selected_first((const unsigned int*)bits, pre, slot, sel, uid, tm, rope_pos, B, T, perm, uid_p, tm_p, pos_p, slot_p, sel_p, q_active, nullptr));
+  HIP_CHECK(hipDeviceSynchronize());
+  return RSYS_OK;
+}
+
+int32_t rsys_op_rows(int32_t kind, int32_t dtype, const void* src, int64_t src_rows, void* dst, int64_t dst_rows, int64_t ld, int32_t n, int32_t D,
+                     const int32_t* map, int64_t map_len, const int32_t* idx, int32_t parity, const int32_t* count, int32_t Tseq) {
+  switches_parse();
+  ARG_CHECK(kind >= 0 && kind <= 6, "rsys_op_rows: kind 0 .. 6");
+  ARG_CHECK(dtype == RSYS_DTYPE_BF16 || dtype == RSYS_DTYPE_FP32, "rsys_op_rows: dtype fp32 or bf16");
+  const bool bf = dtype == RSYS_DTYPE_BF16;
+  ARG_CHECK(!bf || (kind != 4 && kind != 6), "rsys_op_rows: the adding movers are fp32 only");
+  const int E = bf ? 8 : 4;
+  ARG_CHECK(src && dst && src_rows >= 1 && dst_rows >= 1 && dst_rows <= (1 << 24) && src_rows <= (1 << 24) && D >= E && D % E == 0,
+            "rsys_op_rows: buffers, at most 2^24 rows each, D a multiple of 16 bytes");
+  const bool strided = kind == 0 || kind == 1 || kind == 2 || kind == 5 || kind == 6;
+  if (strided) ARG_CHECK(ld >= D && ld % E == 0, "rsys_op_rows: ld >= D, a multiple of 16 bytes");
+  ARG_CHECK(parity == 0 || parity == 1, "rsys_op_rows: parity 0 or 1");
+  std::vector<int> hm, hi, hc;
+  long long live = n;
+  if (kind != 0) ARG_CHECK(n >= 1, "rsys_op_rows: n >= 1 (the launchers size their grid from it)");
+  if (kind == 0) {   // gather_rows_sel: cap = dst_rows
+    ARG_CHECK(map && count && map_len >= 0, "rsys_op_rows: gather_rows_sel takes sel and a device count");
+    RC(hook_ints(count, 1, hc));
+    ARG_CHECK(hc[0] >= 0 && hc[0] <= dst_rows && hc[0] <= map_len, "rsys_op_rows: 0 <= *count <= min(cap, map_len)");
+    RC(hook_ints(map, hc[0], hm));
+    for (int r : hm) ARG_CHECK(r >= 0 && r < src_rows, "rsys_op_rows: sel outside the source");
+  } else if (kind == 1) {   // scatter_rows_fill: n = B batch rows of Tseq places
+    ARG_CHECK(map && count && Tseq >= 1 && (long long)n * Tseq == dst_rows && map_len == dst_rows, "rsys_op_rows: scatter_rows_fill takes slot_p [n Tseq] and q_active [n]");
+    RC(hook_ints(count, n, hc)); RC(hook_ints(map, map_len, hm));
+    for (int b = 0; b < n; ++b) {
+      ARG_CHECK(hc[b] >= 0 && hc[b] <= (1 << 20), "rsys_op_rows: q_active >= 0");
+      for (long long p = 0; p < std::min<long long>(Tseq, 64LL * hc[b]); ++p) {
+        const int s = hm[(size_t)((long long)b * Tseq + p)];
+        ARG_CHECK(s >= -1 && s < src_rows, "rsys_op_rows: slot_p outside the compact rows");
+      }
+    }
+  } else if (kind == 2) {   // scatter_rows_map
+    ARG_CHECK(map && map_len >= n && src_rows >= n, "rsys_op_rows: scatter_rows_map takes map [n]");
+    RC(hook_ints(map, n, hm));
+    std::vector<char> seen((size_t)dst_rows, 0);
+    for (int r : hm) {
+      ARG_CHECK(r >= 0 && r < dst_rows && !seen[(size_t)r], "rsys_op_rows: map outside the destination or not distinct");
+      seen[(size_t)r] = 1;
+    }
+  } else {   // 3 .. 6: head rows, token 2 idx[r] + parity
+    ARG_CHECK(idx, "rsys_op_rows: idx");
+    const bool via_slot = kind == 3 || kind == 4, adds = kind == 4 || kind == 6;
+    if (via_slot) ARG_CHECK(map && map_len >= 1, "rsys_op_rows: the slot forms take slot [map_len]");
+    if (kind == 4) ARG_CHECK(count, "rsys_op_rows: scatter_rows_add_slot takes a device count");
+    if (adds && count) { RC(hook_ints(count, 1, hc)); ARG_CHECK(hc[0] >= 0, "rsys_op_rows: *count >= 0"); live = std::min<long long>(n, hc[0]); }
+    if (adds) ARG_CHECK(src_rows >= n, "rsys_op_rows: src holds n rows");
+    else ARG_CHECK(dst_rows >= n, "rsys_op_rows: dst holds n rows");
+    RC(hook_ints(idx, live, hi));
+    if (via_slot) RC(hook_ints(map, map_len, hm));
+    const long long tokens = via_slot ? map_len : (adds ? dst_rows : src_rows), table = adds ? dst_rows : src_rows;
+    std::vector<char> seen(adds ? (size_t)table : 0, 0);
+    for (int i : hi) {
+      const long long tok = 2LL * i + parity;
+      ARG_CHECK(i >= 0 && tok < tokens, "rsys_op_rows: a position outside the token range");
+      long long row = tok;
+      if (via_slot) { row = hm[(size_t)tok]; ARG_CHECK(row >= -1 && row < table, "rsys_op_rows: slot outside the compact rows"); }
+      if (adds && row >= 0) { ARG_CHECK(!seen[(size_t)row], "rsys_op_rows: two live rows add to one destination row"); seen[(size_t)row] = 1; }
+    }
+  }
+  const int cap = (int)dst_rows;
+  switch (kind) {
+    case 0: RC(bf ? launch_gather_rows_sel<bf16>((const bf16*)src, ld, map, count, cap, (bf16*)dst, D, nullptr)
+                  : launch_gather_rows_sel<float>((const float*)src, ld, map, count, cap, (float*)dst, D, nullptr)); break;
+    case 1: RC(bf ? launch_scatter_rows_fill<bf16>((const bf16*)src, map, count, n, Tseq, (bf16*)dst, ld, D, nullptr)
+                  : launch_scatter_rows_fill<float>((const float*)src, map, count, n, Tseq, (float*)dst, ld, D, nullptr)); break;
+    case 2: RC(bf ? launch_scatter_rows_map<bf16>((const bf16*)src, map, n, (bf16*)dst, ld, D, nullptr)
+                  : launch_scatter_rows_map<float>((const float*)src, map, n, (float*)dst, ld, D, nullptr)); break;
+    case 3: RC(bf ? launch_gather_rows_slot<bf16>((const bf16*)src, map, idx, parity, (bf16*)dst, n, D, nullptr)
+                  : launch_gather_rows_slot<float>((const float*)src, map, idx, parity, (float*)dst, n, D, nullptr)); break;
+    case 4: RC(launch_scatter_rows_add_slot((const float*)src, map, idx, parity, count, (float*)dst, n, D, nullptr)); break;
+    case 5: RC(bf ? launch_gather_rows<bf16>((const bf16*)src, ld, idx, parity, (bf16*)dst, n, D, nullptr)
+                  : launch_gather_rows<float>((const float*)src, ld, idx, parity, (float*)dst, n, D, nullptr)); break;
+    default: RC(launch_scatter_rows_add((const float*)src, idx, parity, (float*)dst, ld, n, D, nullptr, count)); break;
+  }
+  HIP_CHECK(hipDeviceSynchronize());
+  return RSYS_OK;
+}
+
+int32_t rsys_op_colsum(int32_t kind, int32_t deterministic, const float* src, int64_t ld, int64_t rows, int32_t D, float* colsum, void* dst,
+                       int64_t ldt) {
+  switches_parse();
+  ARG_CHECK(kind >= 0 && kind <= 2, "rsys_op_colsum: kind 0 colsum_add, 1 cast_colsum, 2 cast_transpose_colsum");
+  ARG_CHECK(src && colsum && rows >= 1 && rows <= (1LL << 24) && D >= 1, "rsys_op_colsum: 1 <= rows <= 2^24");
+  if (kind == 0) ARG_CHECK(ld >= D, "rsys_op_colsum: ld >= cols");
+  else ARG_CHECK(dst && ld == D, "rsys_op_colsum: the cast forms read a dense source (ld == D) and take dst");
+  long long parts;   // the launcher's own grid formula (elementwise.hip)
+  if (kind == 0) { const long long rpb = std::max<long long>(64, (rows + 511) / 512); parts = (rows + rpb - 1) / rpb; }
+  else if (kind == 1) { const long long rpb = std::max<long long>(32, (rows + 511) / 512); parts = (rows + rpb - 1) / rpb; }
+  else { const long long chunks = (rows + 63) / 64, cpb = std::max<long long>(1, (chunks + 2047) / 2048); parts = (chunks + cpb - 1) / cpb; }
+  HookDet det(deterministic != 0);
+  RC(det.alloc(parts * D, ceil32(parts) * D));
+  if (kind == 0) RC(launch_colsum_add(src, ld, rows, D, colsum, nullptr));
+  else if (kind == 1) RC(launch_cast_colsum(src, (bf16*)dst, rows, D, colsum, nullptr));
+  else RC(launch_cast_transpose_colsum(src, (bf16*)dst, rows, D, ldt, colsum, nullptr));
+  HIP_CHECK(hipDeviceSynchronize());
+  return det.check("rsys_op_colsum");
+}
+
+int32_t rsys_op_transpose_bf16(int32_t n_jobs, const void* const* src, void* const* dst, const int32_t* rows, const int32_t* cols,
+                               const int64_t* ld_src, const int64_t* ld_dst) {
+  switches_parse();
+  ARG_CHECK(src && dst && rows && cols && ld_src && ld_dst && n_jobs >= 1 && n_jobs <= 64, "rsys_op_transpose_bf16: 1 .. 64 jobs");
+  TransposeBatch b{};
+  for (int i = 0; i < n_jobs; ++i) {
+    ARG_CHECK(src[i] && dst[i] && ((uintptr_t)src[i] & 15) == 0 && ((uintptr_t)dst[i] & 15) == 0, "rsys_op_transpose_bf16: 16-byte aligned matrices");
+    ARG_CHECK(rows[i] >= 1 && cols[i] >= 1 && rows[i] <= (1 << 21) && cols[i] <= (1 << 21), "rsys_op_transpose_bf16: 1 <= rows, cols <= 2^21");
+    ARG_CHECK(ld_src[i] >= cols[i] && ld_dst[i] >= rows[i] && ld_src[i] % 8 == 0 && ld_dst[i] % 8 == 0,
+              "rsys_op_transpose_bf16: ld_src >= cols, ld_dst >= rows, both multiples of 8 (16-byte row strides)");
+    b.job[i] = TransposeJob{src[i], dst[i], rows[i], cols[i], ld_src[i], ld_dst[i]};
+  }
+  b.n = n_jobs;
+  RC(launch_transpose_bf16(b, nullptr));
+  HIP_CHECK(hipDeviceSynchronize());
+  return RSYS_OK;
+}
+
 // step boundaries on the model's stream: rsys_step_mark records an event, rsys_step_marks_get returns the elapsed time
 // between consecutive marks (ms) and clears them -- the per-step time distribution without a host sync per step
 int32_t rsys_step_mark(rsys_model* h) {

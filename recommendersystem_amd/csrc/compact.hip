@@ -122,17 +122,6 @@ __global__ void gather_rows_sel_kernel(const T* __restrict__ src, long long ld, 
   }
 }
 
-// dst rows sel[r] <- src rows r, r < n
-template <typename T>
-__global__ void scatter_rows_sel_kernel(const T* __restrict__ src, const int* __restrict__ sel, const int* __restrict__ n_dev, T* dst, long long ld, int D) {
-  const int row = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, l = threadIdx.x & 63;
-  if (row >= *n_dev) return;
-  constexpr int E = 16 / sizeof(T);
-  const uint4* s4 = (const uint4*)(src + (long long)row * D);
-  uint4* d4 = (uint4*)(dst + (long long)sel[row] * ld);
-  for (int c = l; c < D / E; c += 64) d4[c] = s4[c];
-}
-
 // The compact top's dO in selected-first order: place p of batch row b (p < 64 q_active[b]: the query tiles the last layer's attention backward visits)
 // <- compact row slot_p[b T + p], or zeros where that place holds no selected token (the ragged end of the last visited tile; every place when the
 // order is the identity).  Places beyond the visited tiles are never read and keep what they held.  One wave per place.
@@ -231,13 +220,6 @@ template int launch_gather_rows_sel<bf16>(const bf16*, long long, const int*, co
 template int launch_gather_rows_sel<float>(const float*, long long, const int*, const int*, int, float*, int, hipStream_t);
 
 template <typename T>
-int launch_scatter_rows_sel(const T* src, const int* sel, const int* n_dev, int cap, T* dst, long long ld, int D, hipStream_t s) {
-  ARG_CHECK((D * sizeof(T)) % 16 == 0 && (ld * sizeof(T)) % 16 == 0, "scatter_rows_sel: rows must be 16-byte multiples");
-  hipLaunchKernelGGL((scatter_rows_sel_kernel<T>), dim3((cap + 3) / 4), dim3(256), 0, s, src, sel, n_dev, dst, ld, D);
-  HIP_CHECK(hipGetLastError());
-  return RSYS_OK;
-}
-template <typename T>
 int launch_scatter_rows_fill(const T* src, const int* slot_p, const int* q_active, int B, int Tseq, T* dst, long long ld, int D, hipStream_t s) {
   ARG_CHECK((D * sizeof(T)) % 16 == 0 && (ld * sizeof(T)) % 16 == 0, "scatter_rows_fill: rows must be 16-byte multiples");
   const long long places = (long long)B * Tseq;
@@ -247,8 +229,6 @@ int launch_scatter_rows_fill(const T* src, const int* slot_p, const int* q_activ
 }
 template int launch_scatter_rows_fill<bf16>(const bf16*, const int*, const int*, int, int, bf16*, long long, int, hipStream_t);
 template int launch_scatter_rows_fill<float>(const float*, const int*, const int*, int, int, float*, long long, int, hipStream_t);
-template int launch_scatter_rows_sel<bf16>(const bf16*, const int*, const int*, int, bf16*, long long, int, hipStream_t);
-template int launch_scatter_rows_sel<float>(const float*, const int*, const int*, int, float*, long long, int, hipStream_t);
 
 template <typename T>
 int launch_scatter_rows_map(const T* src, const int* map, int n, T* dst, long long ld, int D, hipStream_t s) {
