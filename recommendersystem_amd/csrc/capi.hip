@@ -1628,7 +1628,7 @@ int32_t rsys_op_rows(int32_t kind, int32_t dtype, const void* src, int64_t src_r
   ARG_CHECK(parity == 0 || parity == 1, "rsys_op_rows: parity 0 or 1");
   std::vector<int> hm, hi, hc;
   long long live = n;
-  if (kind != 0) ARG_CHECK(n >= 1, "rsys_op_rows: n >= 1 (the launchers size their grid from it)");
+  if (kind != 0) ARG_CHECK(n >= 1, "rsys_op_rows: n >= 1");
   if (kind == 0) {   // gather_rows_sel: cap = dst_rows
     ARG_CHECK(map && count && map_len >= 0, "rsys_op_rows: gather_rows_sel takes sel and a device count");
     RC(hook_ints(count, 1, hc));

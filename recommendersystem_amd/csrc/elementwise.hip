@@ -47,8 +47,6 @@ static inline float* det_part(long long floats) {
   return g_det.part;
 }
 
-static inline int div_up(long long a, long long b) { return (int)((a + b - 1) / b); }
-
 // --------------------------------------------------------------------- mask_tokens
 // transformer.model.py:417-462
 __global__ void mask_tokens_kernel(BatchDev b, int finetune, int ft_metric, float rate,
@@ -609,44 +607,6 @@ int launch_select_positions_batch(int ntask, const float* const* w, int N, int t
   SelectBatch sb{};
   for (int i = 0; i < ntask; ++i) { sb.w[i] = w[i]; sb.idx[i] = idx[i]; sb.stats[i] = stats[i]; sb.npos[i] = npos_out[i]; }
   hipLaunchKernelGGL(select_positions_kernel, dim3(ntask), dim3(1024), 0, s, sb, N, topk);
-  HIP_CHECK(hipGetLastError());
-  return RSYS_OK;
-}
-
-// --------------------------------------------------------------------- row gather / scatter for the heads
-template <typename T>
-__global__ void gather_rows_kernel(const T* __restrict__ src, long long ld, const int* __restrict__ idx, int parity, T* dst, int n, int D) {
-  const int row = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, l = threadIdx.x & 63;
-  if (row >= n) return;
-  constexpr int E = 16 / sizeof(T);
-  const uint4* s4 = (const uint4*)(src + (2LL * idx[row] + parity) * ld);
-  uint4* d4 = (uint4*)(dst + (long long)row * D);
-  for (int c = l; c < D / E; c += 64) d4[c] = s4[c];
-}
-template <typename T>
-int launch_gather_rows(const T* src, long long ld, const int* idx, int parity, T* dst, int n, int D, hipStream_t s) {
-  ARG_CHECK((D * sizeof(T)) % 16 == 0 && (ld * sizeof(T)) % 16 == 0, "gather_rows: rows must be 16-byte multiples");
-  hipLaunchKernelGGL((gather_rows_kernel<T>), dim3(div_up(n, 4)), dim3(256), 0, s, src, ld, idx, parity, dst, n, D);
-  HIP_CHECK(hipGetLastError());
-  return RSYS_OK;
-}
-template int launch_gather_rows<bf16>(const bf16*, long long, const int*, int, bf16*, int, int, hipStream_t);
-template int launch_gather_rows<float>(const float*, long long, const int*, int, float*, int, int, hipStream_t);
-
-__global__ void scatter_rows_add_kernel(const float* __restrict__ src, const int* __restrict__ idx, int parity, float* dst, long long ld, int n, int D,
-                                        const int* __restrict__ npos) {
-  const int row = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, l = threadIdx.x & 63;
-  if (row >= n || (npos != nullptr && row >= *npos)) return;   // (rows from *npos on are zero-weight padding: their gradient is zero)
-  const float4* s4 = (const float4*)(src + (long long)row * D);
-  float4* d4 = (float4*)(dst + (2LL * idx[row] + parity) * ld);
-  for (int c = l; c < (D >> 2); c += 64) {
-    float4 a = d4[c], b = s4[c];
-    a.x += b.x; a.y += b.y; a.z += b.z; a.w += b.w;
-    d4[c] = a;
-  }
-}
-int launch_scatter_rows_add(const float* src, const int* idx, int parity, float* dst, long long ld, int n, int D, hipStream_t s, const int* npos) {
-  hipLaunchKernelGGL(scatter_rows_add_kernel, dim3(div_up(n, 4)), dim3(256), 0, s, src, idx, parity, dst, ld, n, D, npos);
   HIP_CHECK(hipGetLastError());
   return RSYS_OK;
 }

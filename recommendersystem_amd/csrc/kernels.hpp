@@ -6,6 +6,8 @@
 
 namespace rsys {
 
+static inline int div_up(long long a, long long b) { return (int)((a + b - 1) / b); }
+
 // Device-resident batch record: the 27 arrays of SURVEY 8(a) A1 plus the masked
 // copies mask_tokens produces (transformer.model.py:417-462).
 struct BatchDev {
@@ -141,7 +143,7 @@ int launch_selected_first(const unsigned int* bits, const int* pre, int* slot, i
                           int* perm, int* uid_p, int* tm_p, int* pos_p, int* slot_p, int* sel_p, int* q_active, hipStream_t s);
 // dst rows [0, n) <- src rows sel[r]; dst rows [n, n rounded up to 256) <- 0   (n = *n_dev <= cap)
 template <typename T> int launch_gather_rows_sel(const T* src, long long ld, const int* sel, const int* n_dev, int cap, T* dst, int D, hipStream_t s);
-// places [0, 64 q_active[b]) of every batch row <- compact row slot_p[place] or zeros; the other places untouched (compact.hip)
+// places [0, 64 q_active[b]) of every batch row <- compact row slot_p[place] or zeros; the other places untouched (rows.hip, as every launch_*_rows_* here and below)
 template <typename T> int launch_scatter_rows_fill(const T* src, const int* slot_p, const int* q_active, int B, int Tseq, T* dst, long long ld, int D, hipStream_t s);
 template <typename T> int launch_scatter_rows_map(const T* src, const int* map, int n, T* dst, long long ld, int D, hipStream_t s);   // dst[map[r]] = src[r]
 // heads: dst[r] = compact[slot[2 idx[r] + parity]] (zeros where -1), r < n; and compact[slot[..]] += src[r] for r < min(n, *npos)

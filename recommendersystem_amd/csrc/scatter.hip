@@ -18,8 +18,6 @@
 
 namespace rsys {
 
-static inline int div_up(long long a, long long b) { return (int)((a + b - 1) / b); }
-
 constexpr int SEG_TILE = 8;      // sorted positions per wave
 constexpr int MASK_CHUNK = 256;  // tokens per mask-row partial
 

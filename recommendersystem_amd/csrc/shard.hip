@@ -12,8 +12,6 @@
 
 namespace rsys {
 
-static inline int div_up(long long a, long long b) { return (int)((a + b - 1) / b); }
-
 // ------------------------------------------------------------------ exchange plan (once per uploaded batch)
 // skey sorted ascending (raw ids, -1 -> V).  slot[p] = rank of skey[p] among the distinct keys; uniq[slot] = key;
 // tok2u[token] = slot.  The mask row V always gets a slot (watch-masked tokens read it): plan = {U, uV}.
@@ -63,60 +61,6 @@ __global__ void plan_offsets_kernel(const int* __restrict__ uniq, const int* __r
 int launch_plan_offsets(const int* uniq, const int* plan, const int* bound_dev, int nb, int* off, hipStream_t s) {
   ARG_CHECK(nb >= 2 && nb <= 64, "exchange plan: ranks");
   hipLaunchKernelGGL(plan_offsets_kernel, dim3(1), dim3(64), 0, s, uniq, plan, bound_dev, nb, off);
-  HIP_CHECK(hipGetLastError());
-  return RSYS_OK;
-}
-
-// ------------------------------------------------------------------ rows by id
-// dst[j] = src[(ids[j] - sub) * ld ..+D)   (owner side: the rows its peers asked for)
-__global__ void gather_rows_by_id_kernel(const float* __restrict__ src, long long ld, const int* __restrict__ ids, int sub, float* dst, int n, int D) {
-  const int j = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, l = threadIdx.x & 63;
-  if (j >= n) return;
-  const float4* s4 = (const float4*)(src + (long long)(ids[j] - sub) * ld);
-  float4* d4 = (float4*)(dst + (long long)j * D);
-  for (int c = l; c < (D >> 2); c += 64) d4[c] = s4[c];
-}
-int launch_gather_rows_by_id(const float* src, long long ld, const int* ids, int sub, float* dst, int n, int D, hipStream_t s) {
-  if (n == 0) return RSYS_OK;
-  hipLaunchKernelGGL(gather_rows_by_id_kernel, dim3(div_up(n, 4)), dim3(256), 0, s, src, ld, ids, sub, dst, n, D);
-  HIP_CHECK(hipGetLastError());
-  return RSYS_OK;
-}
-// dst[(ids[j] - sub)] += src[j]; the ids of one call are distinct (one requester's list): plain read-modify-write
-__global__ void add_rows_by_id_kernel(const float* __restrict__ src, const int* __restrict__ ids, int sub, float* dst, long long ld, int n, int D) {
-  const int j = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, l = threadIdx.x & 63;
-  if (j >= n) return;
-  const float4* s4 = (const float4*)(src + (long long)j * D);
-  float4* d4 = (float4*)(dst + (long long)(ids[j] - sub) * ld);
-  for (int c = l; c < (D >> 2); c += 64) {
-    float4 a = d4[c]; const float4 b = s4[c];
-    a.x += b.x; a.y += b.y; a.z += b.z; a.w += b.w;
-    d4[c] = a;
-  }
-}
-int launch_add_rows_by_id(const float* src, const int* ids, int sub, float* dst, long long ld, int n, int D, hipStream_t s) {
-  if (n == 0) return RSYS_OK;
-  hipLaunchKernelGGL(add_rows_by_id_kernel, dim3(div_up(n, 4)), dim3(256), 0, s, src, ids, sub, dst, ld, n, D);
-  HIP_CHECK(hipGetLastError());
-  return RSYS_OK;
-}
-
-// the same with the row count on the device (split table reduce: a peer's list of distinct token rows, its length in plan[0])
-__global__ void add_rows_by_id_counted_kernel(const float* __restrict__ src, const int* __restrict__ ids, const int* __restrict__ count,
-                                              float* dst, long long ld, int cap, int D) {
-  const int j = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, l = threadIdx.x & 63;
-  if (j >= cap || j >= count[0]) return;
-  const float4* s4 = (const float4*)(src + (long long)j * D);
-  float4* d4 = (float4*)(dst + (long long)ids[j] * ld);
-  for (int c = l; c < (D >> 2); c += 64) {
-    float4 a = d4[c]; const float4 b = s4[c];
-    a.x += b.x; a.y += b.y; a.z += b.z; a.w += b.w;
-    d4[c] = a;
-  }
-}
-int launch_add_rows_by_id_counted(const float* src, const int* ids, const int* count_dev, float* dst, long long ld, int cap, int D, hipStream_t s) {
-  if (cap == 0) return RSYS_OK;
-  hipLaunchKernelGGL(add_rows_by_id_counted_kernel, dim3(div_up(cap, 4)), dim3(256), 0, s, src, ids, count_dev, dst, ld, cap, D);
   HIP_CHECK(hipGetLastError());
   return RSYS_OK;
 }
@@ -386,41 +330,6 @@ int launch_ss_drop_hits(int* cols, int n_s, const unsigned int* bitmap, hipStrea
   return RSYS_OK;
 }
 
-// dst[j] = src[(base + idx[j]) * ld ..+D)  (T rows, 16-byte copies); idx[j] < 0: zeros
-template <typename T>
-__global__ void gather_rows_plain_kernel(const T* __restrict__ src, long long ld, const int* __restrict__ idx, int base, T* dst, int n, int D) {
-  const int j = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, l = threadIdx.x & 63;
-  if (j >= n) return;
-  constexpr int E = 16 / sizeof(T);
-  uint4* d4 = (uint4*)(dst + (long long)j * D);
-  if (idx[j] < 0) { for (int c = l; c < D / E; c += 64) d4[c] = make_uint4(0, 0, 0, 0); return; }   // dropped entry: a zero row
-  const uint4* s4 = (const uint4*)(src + (long long)(base + idx[j]) * ld);
-  for (int c = l; c < D / E; c += 64) d4[c] = s4[c];
-}
-template <typename T>
-int launch_gather_rows_plain(const T* src, long long ld, const int* idx, int base, T* dst, int n, int D, hipStream_t s) {
-  hipLaunchKernelGGL((gather_rows_plain_kernel<T>), dim3(div_up(n, 4)), dim3(256), 0, s, src, ld, idx, base, dst, n, D);
-  HIP_CHECK(hipGetLastError());
-  return RSYS_OK;
-}
-// dst[(base + idx[j])] += src[j]  (f32 rows; the non-negative idx are distinct, negative ones are skipped)
-__global__ void add_rows_plain_kernel(const float* __restrict__ src, const int* __restrict__ idx, int base, float* dst, long long ld, int n, int D) {
-  const int j = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, l = threadIdx.x & 63;
-  if (j >= n || idx[j] < 0) return;
-  const float4* s4 = (const float4*)(src + (long long)j * D);
-  float4* d4 = (float4*)(dst + (long long)(base + idx[j]) * ld);
-  for (int c = l; c < (D >> 2); c += 64) {
-    float4 a = d4[c]; const float4 b = s4[c];
-    a.x += b.x; a.y += b.y; a.z += b.z; a.w += b.w;
-    d4[c] = a;
-  }
-}
-int launch_add_rows_plain(const float* src, const int* idx, int base, float* dst, long long ld, int n, int D, hipStream_t s) {
-  hipLaunchKernelGGL(add_rows_plain_kernel, dim3(div_up(n, 4)), dim3(256), 0, s, src, idx, base, dst, ld, n, D);
-  HIP_CHECK(hipGetLastError());
-  return RSYS_OK;
-}
-
 // tl[row] = <selected row, F[target]> where the target class is local (one owner per row), else 0; one wave per row
 template <typename T>
 __global__ void ss_target_logit_kernel(const T* __restrict__ EwC, const T* __restrict__ Floc, int D, int len, int col0,
@@ -611,7 +520,6 @@ INST(bf16)
 INST(float)
 #undef INST
 #define INST(T)                                                                                                          \
-  template int launch_gather_rows_plain<T>(const T*, long long, const int*, int, T*, int, int, hipStream_t);               \
   template int launch_ss_target_logit<T>(const T*, const T*, int, int, int, const float*, const int*, float*, int, hipStream_t); \
   template int launch_ss_stats<T>(const T*, long long, int, int, int, int, const int*, const float*, const int*, float*, float*, int, hipStream_t); \
   template int launch_ss_finish<T>(T*, long long, int, int, int, int, const int*, const float*, const float*, const float*, const float*, const int*, const int*, int, float*, float*, int, hipStream_t); \

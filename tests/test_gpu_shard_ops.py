@@ -392,6 +392,9 @@ def test_rows_plain_and_by_id(dev, D, n):
     _ok(rows_call(dev, 4, table=dev.put(tab), ld=ld, table_rows=trows, ids=dev.puti(ids), sub=sub, packed=dpk, n=n, D=D))
     got = dev.get(dpk, (n + 2, D))
     assert np.array_equal(got[:n], tab[ids - sub, :D]) and np.all(got[n:] == SENT)
+    dpk = dev.put(np.full((n + 2, D), SENT, np.float32))                         # no rows: no launch, no error, nothing written
+    _ok(rows_call(dev, 4, table=dev.put(tab), ld=ld, table_rows=trows, ids=dev.puti(ids), sub=sub, packed=dpk, n=0, D=D))
+    assert np.all(dev.get(dpk, (n + 2, D)) == SENT)
     dtab = dev.put(tab)
     _ok(rows_call(dev, 8, table=dtab, ld=ld, table_rows=trows, ids=dev.puti(ids), sub=sub, packed=dev.put(src), n=n, D=D))
     want = tab.copy(); want[ids - sub, :D] += src
