@@ -145,13 +145,25 @@ int32_t rsys_batch_swap(rsys_model* m);
  *   min(S, 32 ceil(fullest row / 32)) -- if that takes fewer forwards than one history per row at that row's trim length, or as many
  *   forwards and fewer tokens; otherwise one history per row, at column 0.  The rows are cut on the device from the kept history rows
  *   and stored as rsys_rank_cache_store_packed stores them, without a host wait.  Candidate forwards, the empty-history rows, chunking,
- *   pages and totals are unchanged; "forward_rows" reports the packed store forwards as (1, rows, row_len). */
+ *   pages and totals are unchanged; "forward_rows" reports the packed store forwards as (1, rows, row_len).
+ * rsys_serving_compact_top_set (default 0): inference passes run the last layer only where its outputs are read.  Read by
+ *   every inference pass over the resident batch: rsys_infer_select[_adapters | _tiles], the render pipelines' retrieval and ranking
+ *   forwards, and the four rsys_rank_cache_* passes.  A pass that reports n selected tokens with n <= the compact buffers' rows and
+ *   2 n <= the batch's tokens runs the last layer's output projection, MLP and the final norm on those n rows only (token order is kept);
+ *   when also n <= rows * ceil(2 row_len / 64) and the rows are not candidate rows, that layer's attention runs for the selected queries
+ *   only.  A store pass (rsys_rank_cache_store[_packed]) ends after its last K | V copy; the slots hold the same bits.  Needs the
+ *   compact buffers (an fp32 / bf16 model with a replicated table and at most 2^19 tokens per batch): otherwise, and for rsys_infer
+ *   without a selection, the pass runs dense as before.  Values agree with the dense pass to rounding (the order of two sums changes), not
+ *   bit for bit.  rsys_trunk_output_get after such a pass computes the dense output on demand.  With the switch off every launch is what
+ *   it was.  on = 2 / 3 are measurement values (tools/bench_compact_top.py): as 1, with the attention rule forced to "never" / "always". */
 int32_t rsys_batch_upload_trimmed(rsys_model* m, const rsys_batch* b, int32_t row_len);
 int32_t rsys_batch_row_length(rsys_model* m, int32_t* row_len_out);
 int32_t rsys_serving_pack_set(rsys_model* m, int32_t on);
 int32_t rsys_serving_pack_get(rsys_model* m, int32_t* on_out);
 int32_t rsys_serving_pack_ranking_set(rsys_model* m, int32_t on);
 int32_t rsys_serving_pack_ranking_get(rsys_model* m, int32_t* on_out);
+int32_t rsys_serving_compact_top_set(rsys_model* m, int32_t on);
+int32_t rsys_serving_compact_top_get(rsys_model* m, int32_t* on_out);
 int32_t rsys_serving_trim_set(rsys_model* m, int32_t on);
 int32_t rsys_serving_trim_get(rsys_model* m, int32_t* on_out);
 /* device-side synthetic batch (bench): fills the resident batch from a counter RNG */

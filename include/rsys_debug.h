@@ -108,6 +108,14 @@ int32_t rsys_op_attention_ex(int32_t dtype, int32_t B, int32_t T, int32_t H, int
                              const int32_t* uid, const int32_t* tm, void* O, float* lse, const void* dO, void* dqkv,
                              const float* rope_cos, const float* rope_sin, const int32_t* rope_pos, int32_t rope_rows,
                              const int32_t* q_active, float* amax_fwd, float* amax_bwd);
+/* the selected-query attention of the serving compact top alone (attn_sel_kernel), on caller-provided device buffers: qkv
+ * [B*T][(H+2KV)*hd] (T-typed, q and k already rotated), uid / tm int32 [B*T], sel int32 [n_sel] (device; flat token indices b * T + t, any
+ * order, duplicates allowed; copied back once and checked).  Query sel[i] attends to the keys of its row under the model's mask (key k
+ * allowed iff uid[k] == uid[q] and (tm[k] == 0 or tm[k] == tm[q])), one soft-max at scale 1/sqrt(hd); its H*hd outputs go to row i of O
+ * [>= n_sel][H*hd] (T-typed).  Rows of O from n_sel on are not written; there is no lse.  The tile maps are built here, as in
+ * rsys_op_attention_ex (T a multiple of 8, T <= 4096; rows of more than 2048 tokens use the 64-bit map words) */
+int32_t rsys_op_attention_selected(int32_t dtype, int32_t B, int32_t T, int32_t H, int32_t KV, int32_t hd, const void* qkv,
+                                   const int32_t* uid, const int32_t* tm, int32_t n_sel, const int32_t* sel, void* O);
 /* the candidate attention of rsys_rank_cache_candidates alone, on caller-provided device buffers (T-typed): qkv [rows*T][(H+2KV)*hd] the
  * candidate rows' post-RoPE q | k | v, cache [n_slots][T][2*KV*hd] (K | V per cached token), slot / n_hist / n_cand int32 [rows] (device;
  * 0 <= n_hist[r] <= T/2, 0 <= n_cand[r] <= T/2; T a multiple of 8, T <= 4096); O [rows*T][H*hd]: rows of tokens >= 2 n_cand[r] are zeros up to the end of the last

@@ -168,6 +168,12 @@ function serving_pack_ranking(m::Model)   # render_request_full packs its K/V-ca
     check(ccall((:rsys_serving_pack_ranking_get, LIB), Int32, (Ptr{Cvoid}, Ref{Int32}), m.h, on))
     on[] != 0
 end
+serving_compact_top!(m::Model, on::Bool) = check(ccall((:rsys_serving_compact_top_set, LIB), Int32, (Ptr{Cvoid}, Int32), m.h, on ? 1 : 0))
+function serving_compact_top(m::Model)   # inference passes run the last layer only where its outputs are read
+    on = Ref{Int32}(0)
+    check(ccall((:rsys_serving_compact_top_get, LIB), Int32, (Ptr{Cvoid}, Ref{Int32}), m.h, on))
+    on[] != 0
+end
 serving_trim!(m::Model, on::Bool) = check(ccall((:rsys_serving_trim_set, LIB), Int32, (Ptr{Cvoid}, Int32), m.h, on ? 1 : 0))
 function serving_trim(m::Model)
     on = Ref{Int32}(0)

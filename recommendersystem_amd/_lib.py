@@ -150,6 +150,8 @@ _SIGS = [
     ("rsys_serving_pack_get", C.c_int32, [_P, C.POINTER(C.c_int32)]),
     ("rsys_serving_pack_ranking_set", C.c_int32, [_P, C.c_int32]),
     ("rsys_serving_pack_ranking_get", C.c_int32, [_P, C.POINTER(C.c_int32)]),
+    ("rsys_serving_compact_top_set", C.c_int32, [_P, C.c_int32]),
+    ("rsys_serving_compact_top_get", C.c_int32, [_P, C.POINTER(C.c_int32)]),
     ("rsys_serving_trim_set", C.c_int32, [_P, C.c_int32]),
     ("rsys_serving_trim_get", C.c_int32, [_P, C.POINTER(C.c_int32)]),
     ("rsys_adapter_train_enable", C.c_int32, [_P, C.c_float]),
@@ -166,6 +168,7 @@ _SIGS = [
     ("rsys_rank_cache_store_packed", C.c_int32, [_P, _P, C.c_int32, _P]),
     ("rsys_rank_cache_candidates_packed", C.c_int32, [_P, _P, C.c_int32, _P, _P]),
     ("rsys_rank_cache_get", C.c_int32, [_P, C.c_int32, C.c_int32, _P, C.c_int64]),
+    ("rsys_op_attention_selected", C.c_int32, [C.c_int32] * 6 + [_P, _P, _P, C.c_int32, _P, _P]),
     ("rsys_op_attention_cached", C.c_int32, [C.c_int32] * 6 + [_P, _P, C.c_int32, _P, _P, _P, _P]),
     ("rsys_op_attention_cached_tiles", C.c_int32, [C.c_int32] * 6 + [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
     ("rsys_op_rank_cache_copy_segments", C.c_int32, [C.c_int32] * 6 + [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P]),

@@ -1554,6 +1554,164 @@ int launch_attn_bwd(const AttnParams& p, hipStream_t s) {
 template int launch_attn_bwd<bf16>(const AttnParams&, hipStream_t);
 template int launch_attn_bwd<float>(const AttnParams&, hipStream_t);
 
+// ------------------------------------------------------------------------ selected-query attention (the serving compact top)
+// Decode-shaped: query token sel[i] (a flat index of the [B][T] geometry; any order, duplicates allowed) against the keys of its own row in
+// token order, the model's mask from uid / tm, one soft-max, H * hd outputs into COMPACT row i of `co`.  No lse.  One workgroup per (selected
+// token, kv head, R query heads of it); with 1 .. 8 query rows an MFMA tile would be mostly empty, so the products are fp32 VALU dot products
+// and the kernel is bound by reading the row's K | V once.  A key is spread over G = hd / E lanes (E = the elements of one 16-byte load), a
+// wave takes 64 / G keys per step, and the four waves take the steps of every visited 64-key tile in turn -- tiles without an allowed pair
+// for the query's tile are skipped through the token-order qmap of launch_attn_tilemap (nullptr: every tile).  Every lane keeps its own
+// running (max, sum, acc[R][E]); the groups of a wave merge by lane exchanges, the waves through LDS.
+template <typename T, int E> struct SelVec;
+template <> struct SelVec<bf16, 8> { using V = bf16x8; };
+template <> struct SelVec<float, 4> { using V = f32x4; };
+template <typename T, int HD, int R>
+__global__ __launch_bounds__(256) void attn_sel_kernel(AttnParams p, const int* __restrict__ sel, T* __restrict__ co, long long ldc) {
+  constexpr int E = 16 / (int)sizeof(T), G = HD / E, KPW = 64 / G;
+  using V = typename SelVec<T, E>::V;
+  __shared__ float sm_m[4][R], sm_s[4][R];
+  __shared__ float sm_acc[4][R][HD];
+  const int i = blockIdx.x, g = blockIdx.y, h0 = g * (p.H / p.KV) + blockIdx.z * R;
+  const int t = threadIdx.x, l = t & 63, w = t >> 6, sub = l % G, kl = l / G;
+  const long long tok = sel[i];
+  T* const orow = co + (long long)i * ldc + (long long)h0 * HD;
+  if (tok < 0 || tok >= (long long)p.B * p.T) {   // (uniform; the callers check the list: a bad entry reads nothing and reports zeros)
+    for (int c = t; c < R * HD; c += 256) orow[c] = from_f32<T>(0.f);
+    return;
+  }
+  const int b = (int)(tok / p.T), tq = (int)(tok % p.T), nt = (p.T + 63) / 64;
+  const long long base = (long long)b * p.T;
+  const int uq = p.uid[tok], mq = p.tm[tok];
+  const float scale = LOG2E / sqrtf((float)HD);
+  float qf[R][E];
+  {
+    const T* qp = (const T*)p.q + tok * p.ld + (long long)h0 * HD + sub * E;
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      const V qv = *(const V*)(qp + r * HD);
+#pragma unroll
+      for (int e = 0; e < E; ++e) qf[r][e] = (float)qv[e] * scale;
+    }
+  }
+  float mx[R], sum[R], acc[R][E];
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    mx[r] = -1e30f; sum[r] = 0.f;
+#pragma unroll
+    for (int e = 0; e < E; ++e) acc[r][e] = 0.f;
+  }
+  unsigned long long tiles = nt >= 64 ? ~0ull : ((1ull << nt) - 1ull);
+  if (p.qmap != nullptr) {
+    const int ent = b * nt + (tq >> 6);
+    tiles &= nt > 32 /* 64-bit map words: attn_map_words */ ?((const unsigned long long*)p.qmap)[ent] : (unsigned long long)p.qmap[ent];
+  }
+  const T* const kb = (const T*)p.k + (long long)g * HD + sub * E;
+  const T* const vb = (const T*)p.v + (long long)g * HD + sub * E;
+  while (tiles) {   // (uniform)
+    const int j = __builtin_ctzll(tiles);
+    tiles &= tiles - 1ull;
+    for (int c = w; c < G; c += 4) {
+      const int key = j * 64 + c * KPW + kl;
+      const long long row = base + (key < p.T ? key : p.T - 1);   // (a key behind the row's end: a clamped load, masked below)
+      const int uk = p.uid[row], mk = p.tm[row];
+      const V kv = *(const V*)(kb + row * p.ld);
+      const V vv = *(const V*)(vb + row * p.ld);
+      const bool ok = key < p.T && uk == uq && (mk == 0 || mk == mq);
+      if (__ballot(ok) == 0ull) continue;   // (wave-uniform: none of this step's keys is allowed)
+      float kf[E], vf[E];
+#pragma unroll
+      for (int e = 0; e < E; ++e) { kf[e] = (float)kv[e]; vf[e] = (float)vv[e]; }
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        float d = 0.f;
+#pragma unroll
+        for (int e = 0; e < E; ++e) d = fmaf(qf[r][e], kf[e], d);
+#pragma unroll
+        for (int o = G / 2; o > 0; o >>= 1) d += __shfl_xor(d, o, 64);
+        const float sc = ok ? d : -1e30f;
+        const float mn = fmaxf(mx[r], sc);
+        const float a = fexp2(mx[r] - mn), pe = ok ? fexp2(sc - mn) : 0.f;
+        sum[r] = fmaf(sum[r], a, pe);
+#pragma unroll
+        for (int e = 0; e < E; ++e) acc[r][e] = fmaf(acc[r][e], a, pe * vf[e]);
+        mx[r] = mn;
+      }
+    }
+  }
+  // the key groups of a wave -> its lanes kl == 0 (lane exchanges), then the four waves through LDS
+#pragma unroll
+  for (int o = G; o < 64; o <<= 1) {
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      const float mo = __shfl_xor(mx[r], o, 64), so = __shfl_xor(sum[r], o, 64);
+      const float mn = fmaxf(mx[r], mo);
+      const float a = fexp2(mx[r] - mn), bo = fexp2(mo - mn);
+      sum[r] = sum[r] * a + so * bo;
+#pragma unroll
+      for (int e = 0; e < E; ++e) acc[r][e] = acc[r][e] * a + __shfl_xor(acc[r][e], o, 64) * bo;
+      mx[r] = mn;
+    }
+  }
+  if (kl == 0) {
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      if (sub == 0) { sm_m[w][r] = mx[r]; sm_s[w][r] = sum[r]; }
+#pragma unroll
+      for (int e = 0; e < E; ++e) sm_acc[w][r][sub * E + e] = acc[r][e];
+    }
+  }
+  __syncthreads();
+  for (int c = t; c < R * HD; c += 256) {
+    const int r = c / HD, d = c % HD;
+    float mn = sm_m[0][r];
+#pragma unroll
+    for (int ww = 1; ww < 4; ++ww) mn = fmaxf(mn, sm_m[ww][r]);
+    float s = 0.f, o = 0.f;
+#pragma unroll
+    for (int ww = 0; ww < 4; ++ww) {
+      const float a = fexp2(sm_m[ww][r] - mn);
+      s = fmaf(sm_s[ww][r], a, s);
+      o = fmaf(sm_acc[ww][r][d], a, o);
+    }
+    orow[c] = from_f32<T>(s > 0.f ? o / s : 0.f);   // (a query always sees itself: s > 0 whenever the maps are the row's)
+  }
+}
+
+template <typename T, int HD>
+static int attn_sel_hd(const AttnParams& p, const int* sel, int n_sel, T* co, long long ldc, hipStream_t s) {
+  const int rep = p.H / p.KV;
+  const int R = rep % 8 == 0 ? 8 : rep % 4 == 0 ? 4 : rep % 2 == 0 ? 2 : 1;   // query heads of the kv head per workgroup
+  const dim3 grid(n_sel, p.KV, rep / R);
+  switch (R) {
+    case 8: hipLaunchKernelGGL((attn_sel_kernel<T, HD, 8>), grid, dim3(256), 0, s, p, sel, co, ldc); break;
+    case 4: hipLaunchKernelGGL((attn_sel_kernel<T, HD, 4>), grid, dim3(256), 0, s, p, sel, co, ldc); break;
+    case 2: hipLaunchKernelGGL((attn_sel_kernel<T, HD, 2>), grid, dim3(256), 0, s, p, sel, co, ldc); break;
+    default: hipLaunchKernelGGL((attn_sel_kernel<T, HD, 1>), grid, dim3(256), 0, s, p, sel, co, ldc); break;
+  }
+  HIP_CHECK(hipGetLastError());
+  return RSYS_OK;
+}
+template <typename T>
+int launch_attn_sel(const AttnParams& p, const int* sel, int n_sel, void* c_O, long long ldc, hipStream_t s) {
+  ARG_CHECK(sel != nullptr && c_O != nullptr && n_sel >= 1, "selected-query attention: a selection and its output");
+  ARG_CHECK(p.B >= 1 && p.T >= 1 && (p.T + 63) / 64 <= 64, "selected-query attention: T <= 4096");
+  ARG_CHECK(p.KV >= 1 && p.KV <= 65535 && p.H % p.KV == 0 && p.H / p.KV <= 65535 * 8, "selected-query attention: H % KV");
+  ARG_CHECK(p.q && p.k && p.v && p.uid && p.tm, "selected-query attention: null operands");
+  ARG_CHECK((p.ld * sizeof(T)) % 16 == 0 && (p.hd * sizeof(T)) % 16 == 0 && ((size_t)p.q | (size_t)p.k | (size_t)p.v) % 16 == 0,
+            "selected-query attention: 16-byte row alignment");
+  ARG_CHECK(ldc >= (long long)p.H * p.hd, "selected-query attention: compact rows of at least H * hd values");
+  switch (p.hd) {
+    case 16: return attn_sel_hd<T, 16>(p, sel, n_sel, (T*)c_O, ldc, s);
+    case 32: return attn_sel_hd<T, 32>(p, sel, n_sel, (T*)c_O, ldc, s);
+    case 64: return attn_sel_hd<T, 64>(p, sel, n_sel, (T*)c_O, ldc, s);
+    case 128: return attn_sel_hd<T, 128>(p, sel, n_sel, (T*)c_O, ldc, s);
+  }
+  set_error("selected-query attention: head_dim must be 16, 32, 64 or 128");
+  return RSYS_ERR_ARG;
+}
+template int launch_attn_sel<bf16>(const AttnParams&, const int*, int, void*, long long, hipStream_t);
+template int launch_attn_sel<float>(const AttnParams&, const int*, int, void*, long long, hipStream_t);
+
 // ------------------------------------------------------------------------ candidate attention against a cached history
 // rsys_rank_cache_candidates (Finetune/embed.py:74-131 without the history half of the row).  A row holds candidates only: candidate j at
 // tokens 2 j, 2 j + 1.  The key set of a query token is dense -- the 2 n_hist cached tokens of the row's slot -- plus its own pair, so

@@ -90,6 +90,8 @@ int32_t rsys_serving_pack_set(rsys_model* h, int32_t on) { CHECK_HANDLE(h); h->m
 int32_t rsys_serving_pack_get(rsys_model* h, int32_t* on_out) { CHECK_HANDLE(h); ARG_CHECK(on_out, "null"); *on_out = h->m->serving_pack ? 1 : 0; return RSYS_OK; }
 int32_t rsys_serving_pack_ranking_set(rsys_model* h, int32_t on) { CHECK_HANDLE(h); h->m->serving_pack_ranking = on != 0; return RSYS_OK; }
 int32_t rsys_serving_pack_ranking_get(rsys_model* h, int32_t* on_out) { CHECK_HANDLE(h); ARG_CHECK(on_out, "null"); *on_out = h->m->serving_pack_ranking ? 1 : 0; return RSYS_OK; }
+int32_t rsys_serving_compact_top_set(rsys_model* h, int32_t on) { CHECK_HANDLE(h); h->m->serving_compact_top = on == 2 || on == 3 ? on : (on != 0 ? 1 : 0); return RSYS_OK; }   // (2 / 3: the measurement values of model.hpp)
+int32_t rsys_serving_compact_top_get(rsys_model* h, int32_t* on_out) { CHECK_HANDLE(h); ARG_CHECK(on_out, "null"); *on_out = h->m->serving_compact_top; return RSYS_OK; }
 int32_t rsys_serving_trim_set(rsys_model* h, int32_t on) { CHECK_HANDLE(h); h->m->serving_trim = on != 0; return RSYS_OK; }
 int32_t rsys_serving_trim_get(rsys_model* h, int32_t* on_out) { CHECK_HANDLE(h); ARG_CHECK(on_out, "null"); *on_out = h->m->serving_trim ? 1 : 0; return RSYS_OK; }
 int32_t rsys_batch_prefetch(rsys_model* h, const rsys_batch* b) { CHECK_HANDLE(h); return model_batch_prefetch(h->m, b); }
@@ -388,6 +390,8 @@ int32_t rsys_trunk_output_get(rsys_model* h, float* out, int64_t n) {
 //   "forward.tokens" int64 [1]: tokens the last trunk forward ran over = rows * 2 * row length of the resident batch (S here is that length)
 //   "top.n" int32 [1] | "top.sel" int32 [top.cap] | "top.slot" int32 [rows*2S] | "top.cap" int32 [1]: compact top of the last training
 //                  pass (model.hpp sparse_top): number of selected tokens, the sorted tokens, token -> compact row (-1: not selected)
+//   "infer.top" int32 [1] | "infer.top_rows" int32 [1]: what the last inference pass did under rsys_serving_compact_top_set -- 0 dense,
+//                  1 compact tail behind the dense attention, 2 compact tail behind attn_sel_kernel, 3 store stopped at K | V -- and the rows its tail ran on
 int32_t rsys_debug_get(rsys_model* h, const char* key, void* out, int64_t bytes) {
   CHECK_HANDLE(h);
   ARG_CHECK(key && out, "null");
@@ -443,6 +447,8 @@ int32_t rsys_debug_get(rsys_model* h, const char* key, void* out, int64_t bytes)
   else if (k == "f8.wamax" && m->fp8) { src = m->f8_wamax; n = (int64_t)m->L * 8 * 4; }
   else if (k == "f8.desc" && m->fp8) { src = m->f8_desc; n = (int64_t)m->L * 8 * 32 * 4; }
   else if (k == "top.cap") { ARG_CHECK(bytes == 4, "top.cap: one int32"); *(int32_t*)out = m->top_is_sparse ? m->ctop_cap : 0; return RSYS_OK; }
+  else if (k == "infer.top") { ARG_CHECK(bytes == 4, "infer.top: one int32"); *(int32_t*)out = m->infer_top; return RSYS_OK; }
+  else if (k == "infer.top_rows") { ARG_CHECK(bytes == 4, "infer.top_rows: one int32"); *(int32_t*)out = m->infer_top_rows; return RSYS_OK; }
   else if (k == "top.n" && m->top_is_sparse) { src = m->c_n; n = 4; }
   else if (k == "top.sel" && m->top_is_sparse) { src = m->c_sel; n = (int64_t)m->ctop_cap * 4; }
   else if (k == "top.slot" && m->top_is_sparse) { src = m->c_slot; n = 2 * N * 4; }
@@ -1051,6 +1057,40 @@ int32_t rsys_op_attention_ex(int32_t dtype, int32_t B, int32_t T, int32_t H, int
   }
   hipError_t e2 = hipDeviceSynchronize();
   hipFree(maps); hipFree(delta); hipFree(pairbits);
+  if (rc) return rc;
+  HIP_CHECK(e2);
+  return RSYS_OK;
+}
+
+// attn_sel_kernel alone: the tile maps are built here, as rsys_op_attention_ex builds them; sel is checked on the host
+int32_t rsys_op_attention_selected(int32_t dtype, int32_t B, int32_t T, int32_t H, int32_t KV, int32_t hd, const void* qkv, const int32_t* uid,
+                                   const int32_t* tm, int32_t n_sel, const int32_t* sel, void* O) {
+  switches_parse();
+  ARG_CHECK(dtype == RSYS_DTYPE_BF16 || dtype == RSYS_DTYPE_FP32, "rsys_op_attention_selected: dtype fp32 or bf16");
+  ARG_CHECK(B >= 1 && T >= 1 && H >= 1 && KV >= 1 && n_sel >= 1 && qkv && uid && tm && sel && O, "rsys_op_attention_selected: null or empty");
+  ARG_CHECK((long long)B * T < (1ll << 31), "rsys_op_attention_selected: B * T must stay below 2^31");
+  {
+    std::vector<int32_t> hs((size_t)n_sel);
+    HIP_CHECK(hipMemcpy(hs.data(), sel, hs.size() * 4, hipMemcpyDeviceToHost));
+    for (int32_t v : hs) ARG_CHECK(v >= 0 && v < B * T, "rsys_op_attention_selected: a selected token outside [0, B * T)");
+  }
+  const size_t e = dtype == RSYS_DTYPE_BF16 ? 2 : 4;
+  const int nt = (T + 63) / 64;
+  AttnParams p{};
+  p.B = B; p.T = T; p.H = H; p.KV = KV; p.hd = hd; p.is_bf16 = dtype == RSYS_DTYPE_BF16;
+  p.q = qkv; p.k = (const unsigned char*)qkv + (size_t)H * hd * e; p.v = (const unsigned char*)qkv + (size_t)(H + KV) * hd * e;
+  p.ld = (long long)(H + 2 * KV) * hd; p.uid = uid; p.tm = tm;
+  unsigned int* maps = nullptr; unsigned long long* pairbits = nullptr;
+  const size_t mw = (size_t)attn_map_words(T) * B * nt;   // words of one [B][nt] map
+  HIP_CHECK(hipMalloc((void**)&maps, sizeof(unsigned int) * 12 * mw));
+  if (hipMalloc((void**)&pairbits, sizeof(unsigned long long) * 2 * (size_t)B * nt * nt * 64) != hipSuccess) { (void)hipGetLastError(); hipFree(maps); set_error("rsys_op_attention_selected: no memory for the pair bits"); return RSYS_ERR_HIP; }
+  p.qmap = maps; p.kmap = maps + mw; p.qmap_full = maps + 2 * mw; p.kmap_full = maps + 3 * mw;
+  p.qmap16 = maps + 4 * mw; p.kmap16 = maps + 8 * mw;
+  p.qbits = pairbits; p.kbits = pairbits + (size_t)B * nt * nt * 64;
+  int rc = launch_attn_tilemap(p, nullptr);
+  if (!rc) rc = dtype == RSYS_DTYPE_BF16 ? launch_attn_sel<bf16>(p, sel, n_sel, O, (long long)H * hd, nullptr) : launch_attn_sel<float>(p, sel, n_sel, O, (long long)H * hd, nullptr);
+  hipError_t e2 = hipDeviceSynchronize();
+  hipFree(maps); hipFree(pairbits);
   if (rc) return rc;
   HIP_CHECK(e2);
   return RSYS_OK;

@@ -106,7 +106,16 @@ __global__ __launch_bounds__(1024) void selected_first_kernel(const unsigned int
   if (t == 0) q_active[b] = identity ? (T + 63) >> 6 : (n_sel + 63) >> 6;
 }
 
+__global__ void set_int_kernel(int* dst, int v) { *dst = v; }
+
 }  // namespace
+
+// *dst = v, stream-ordered, the value a kernel argument (the serving compact top's device row count: no host memory is read later)
+int launch_set_int(int* dst, int v, hipStream_t s) {
+  hipLaunchKernelGGL(set_int_kernel, dim3(1), dim3(1), 0, s, dst, v);
+  HIP_CHECK(hipGetLastError());
+  return RSYS_OK;
+}
 
 int launch_token_union(const int* const* idx, const int* const* npos, int ntask, int NT, unsigned int* bits, int* pre, int* nsel, hipStream_t s) {
   ARG_CHECK(ntask >= 1 && ntask <= 4 && NT >= 1 && NT <= (1 << 19), "token union: 1..4 tasks, at most 2^19 tokens (64 KB bitmap in LDS)");

@@ -138,6 +138,7 @@ int launch_embedding_scatter_segmented(const float* gx0, long long ldx, const in
 // union of the tasks' live positions (token 2 idx + (task & 1), rows r < *npos[task]) as a bitmap over the tokens + the number of
 // selected tokens before each bitmap word + their total; launch_selected_first turns it into sel[0 .. *nsel) ascending, slot[token] = rank or -1
 int launch_token_union(const int* const* idx, const int* const* npos, int ntask, int NT, unsigned int* bits, int* pre, int* nsel, hipStream_t s);
+int launch_set_int(int* dst, int v, hipStream_t s);   // *dst = v (the value travels as a kernel argument)
 // slot / sel from the bitmap of launch_token_union, and the selected-first token order of every batch row: see compact.hip
 int launch_selected_first(const unsigned int* bits, const int* pre, int* slot, int* sel, const int* uid, const int* tm, const int* rope_pos, int B, int T,
                           int* perm, int* uid_p, int* tm_p, int* pos_p, int* slot_p, int* sel_p, int* q_active, hipStream_t s);
@@ -266,6 +267,11 @@ template <typename T> int launch_rank_cache_copy_segments(const T* qkv, long lon
                                                           int n_slots, T* cache, hipStream_t s);
 template <typename T> int launch_attn_fwd(const AttnParams& p, hipStream_t s);
 template <typename T> int launch_attn_bwd(const AttnParams& p, hipStream_t s);
+// Selected-query attention (attn_sel_kernel; the serving compact top): query token sel[i] (device; flat indices of the [B][T]
+// geometry, any order, duplicates allowed) against its row's keys under the model's mask, H * hd outputs into compact row i of c_O
+// (T-typed, row stride ldc).  Reads p.q / k / v / ld, uid, tm and -- optional, for skipping 64-key tiles -- the token-order p.qmap of
+// launch_attn_tilemap.  Writes rows [0, n_sel) of c_O and nothing else (no lse).
+template <typename T> int launch_attn_sel(const AttnParams& p, const int* sel, int n_sel, void* c_O, long long ldc, hipStream_t s);
 
 // ---- optimizer (optim.hip)
 // *out += sum of g[i]^2 in a fixed order (bitwise the same on every rank for the same gradient); part: sumsq_parts() floats of device scratch,

@@ -942,6 +942,7 @@ static int forward_backward_t(Model* m, int evaluate, const float task_w[4], flo
   m->drop_active = m->cfg.finetune && !evaluate && m->cfg.lora_dropout > 0.f;   // nn.Dropout is active in train() mode only
   m->drop_seed = seed ^ 0xD409ull; m->drop_step = step;
   m->top_is_sparse = m->sparse_top && !evaluate && !m->bank_packed;
+  m->top_serving = false; m->out_pending = false; m->out_attn_pending = false;   // (the serving compact top is for inference passes)
   m->f8_tcopies = !evaluate;
   m->host_stream_syncs = 0; m->host_event_waits = 0;
   float tw[4];
@@ -1038,6 +1039,9 @@ int infer_trunk(Model* m) {
   HIP_CHECK(hipMemcpyAsync(b.m_progress, b.progress, N * 4, hipMemcpyDeviceToDevice, s));
   m->drop_active = false;
   m->top_is_sparse = false;
+  // the serving compact top: needs the compact buffers (so neither fp8 nor more than 2^19 tokens) and a replicated table
+  m->top_serving = m->serving_compact_top != 0 && m->sparse_top && !m->sharded;
+  m->out_pending = false; m->out_attn_pending = false;
   return forward_trunk<T>(m);
 }
 template int infer_trunk<float>(Model*);
@@ -1047,9 +1051,14 @@ static int infer_rows_t(Model* m, int task, const int* d_sel, int64_t ntok, floa
   const int D = m->D;
   hipStream_t s = m->stream;
   const int KB = m->K * m->rows_max;
-  RC(infer_trunk<T>(m));
+  m->top_sel = d_sel; m->top_nsel = d_sel != nullptr ? (int)ntok : 0;
+  const int rc_trunk = infer_trunk<T>(m);
+  m->top_sel = nullptr; m->top_nsel = 0;
+  RC(rc_trunk);
   const T* src = AT<T>(m->out);
-  if (d_sel != nullptr) {
+  if (m->infer_top == 1 || m->infer_top == 2) {
+    src = AT<T>(m->c_out);   // the compact tail wrote the selected rows in the order of the selection
+  } else if (d_sel != nullptr) {
     RC(launch_gather_rows_plain<T>(AT<T>(m->out), D, d_sel, 0, AT<T>(m->dhn), (int)ntok, D, s));
     src = AT<T>(m->dhn);
   }

@@ -299,6 +299,20 @@ struct Model {
   // the candidate rows' tile -> segment map [rows][ceil(T / 64)] (-1: a dead tile)
   int* rc_seg = nullptr;
   int rc_nseg = 0;
+  // Serving compact top (rsys_serving_compact_top_set; inference passes only, token order kept).  With the switch on, a pass
+  // with a selection runs the last layer's tail and the final norm on the selected rows (the compact buffers above, rows in the order of the
+  // selection: infer_rows_t reads c_out directly) and a store pass (rc_mode == 1) ends after its last K | V copy.  top_sel / top_nsel: the
+  // selection of the pass under way, set by infer_rows_t around infer_trunk (null: none).  infer_top: what the last inference pass did --
+  // 0 dense, 1 compact tail behind the dense attention, 2 compact tail behind attn_sel_kernel, 3 store stopped at K | V -- and
+  // infer_top_rows the rows its tail ran on.  out_pending: xL / out of the resident forward are NOT materialised (separate from
+  // top_is_sparse, the permuted training form); out_attn_pending: nor is la[L-1].O.  model_materialise_trunk_output runs the rest in
+  // token order; the next forward_backward or infer_trunk clears both.
+  int serving_compact_top = 0;   // 0 off, 1 on; 2 / 3 (measurement only): on, with c_O always gathered from the dense attention / always from attn_sel_kernel
+  bool top_serving = false;   // the pass under way is an inference pass of a model with the compact buffers, under the switch (infer_trunk)
+  const int* top_sel = nullptr; int top_nsel = 0;
+  int infer_top = 0, infer_top_rows = 0;
+  std::vector<int32_t>* top_log = nullptr;   // non-null inside a render call: every inference pass appends (infer_top, infer_top_rows)
+  bool out_pending = false, out_attn_pending = false;
 };
 
 struct Optimizer {

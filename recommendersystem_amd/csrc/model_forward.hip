@@ -93,15 +93,18 @@ static int layer_tail_dense(Model* m, int l, const void* O_in = nullptr /* atten
 
 // The same tail of the LAST layer plus the final norm on the compact set of selected tokens (Model::sparse_top, compact.hip):
 // every buffer has ctop_cap rows, the GEMMs stop at the device-side row count.
+// sel_x: the selected tokens' rows of the layer's input; sel_O: their rows of the attention output a.O, or nullptr when c_O holds them
+// already (the serving form behind attn_sel_kernel).  A training pass hands its sorted set and that set's selected-first places, an
+// inference pass its own selection twice: token order is kept there, and compact row i is the i-th entry of the selection.
 template <typename T>
-static int top_tail_compact(Model* m) {
+static int top_tail_compact(Model* m, const int* sel_x, const int* sel_O) {
   const int D = m->D, Ip = m->Ip, l = m->L - 1, cap = m->ctop_cap;
   hipStream_t s = m->stream;
   Model::LayerAct& a = m->la[l];
   const int* n = m->c_n;
   tic(m, "phase_top_compact_fwd");
-  RC(launch_gather_rows_sel<T>(AT<T>(a.O), D, m->c_sel_p, n, cap, AT<T>(m->c_O), D, s));   // (the layer's attention ran in selected-first order)
-  RC(launch_gather_rows_sel<float>(a.x, D, m->c_sel, n, cap, m->c_x, D, s));
+  if (sel_O) RC(launch_gather_rows_sel<T>(AT<T>(a.O), D, sel_O, n, cap, AT<T>(m->c_O), D, s));
+  RC(launch_gather_rows_sel<float>(a.x, D, sel_x, n, cap, m->c_x, D, s));
   {
     GemmParams p{};
     p.A = m->c_O; p.lda = D; p.B = W<T>(m, m->lo[l].wo); p.ldb = D; p.C = m->c_h; p.ldc = D; p.c_f32 = 1;
@@ -124,6 +127,20 @@ static int top_tail_compact(Model* m) {
   RC(launch_rmsnorm_fwd<T>(m->c_xL, m->P + m->o_norm, AT<T>(m->c_out), m->c_rstdf, cap, D, s, n));
   toc(m);
   return RSYS_OK;
+}
+
+// The serving compact top's two count rules (restated by serve.compact_top_mode): 0 dense; 3 a store pass, which ends at its
+// last K | V copy; else, with a selection of n tokens that fits the compact buffers and is at most half the batch's tokens, the compact
+// tail -- 2 behind attn_sel_kernel when there is at most one selected query per 64-token tile on average (it then reads no more K | V
+// bytes than the tile kernel would) and the rows are not candidate rows, 1 behind the layer's own attention and a row gather.
+static int serving_top_mode(const Model* m, int NT) {
+  if (!m->top_serving) return 0;
+  if (m->rc_mode == 1) return 3;
+  const int64_t n = m->top_nsel;
+  if (m->top_sel == nullptr || n < 1 || n > m->ctop_cap || 2 * n > NT) return 0;
+  // (switch values 2 / 3 are for measurement, tools/bench_compact_top.py: c_O always from the gather / always from attn_sel_kernel)
+  const bool few = m->serving_compact_top == 3 || (m->serving_compact_top != 2 && n <= (int64_t)m->cur_rows * ((m->T + 63) / 64));
+  return m->rc_mode == 0 && few ? 2 : 1;
 }
 
 // ------------------------------------------------------------------ forward trunk (model.py:464-491, 335-343)
@@ -185,6 +202,10 @@ int forward_trunk(Model* m) {
     ap_top.q_active = m->c_qact;   // (the launch orders put the query tiles beyond it last)
     RC(launch_attn_tilemap(ap_top, s));
   }
+  // the serving compact top: what the last layer of this inference pass does, by counts alone
+  const int stop = serving_top_mode(m, NT);
+  m->infer_top = stop; m->infer_top_rows = stop == 1 || stop == 2 ? m->top_nsel : 0;
+  if (m->top_log) { m->top_log->push_back(m->infer_top); m->top_log->push_back(m->infer_top_rows); }
   tic(m, "phase_trunk_fwd");
   for (int l = 0; l < m->L; ++l) {
     Model::LayerAct& a = m->la[l];
@@ -228,8 +249,11 @@ int forward_trunk(Model* m) {
     }
     if (m->bank_rows || m->bank_tiles) RC(adapter_bank_stage_b<T>(m, l, AT<T>(a.qkv), rpos_l));
     if (m->rc_mode == 1) RC(rank_cache_store_layer<T>(m, l, AT<T>(a.qkv)));   // rsys_rank_cache_store: the forward as it is + this layer's K | V of the history rows into their slots
+    const bool last = l == m->L - 1;
+    if (last && stop == 3) break;   // a store pass under the serving switch: nothing behind the last K | V copy is read
     if (m->rc_mode == 2) {   // rsys_rank_cache_candidates: the rows' candidates against their slots' cached history
       RC(rank_cache_attention<T>(m, l, AT<T>(a.qkv), AT<T>(a.O)));
+      if (last && stop) break;
       RC(layer_tail_dense<T>(m, l));
       continue;
     }
@@ -238,12 +262,25 @@ int forward_trunk(Model* m) {
     apl.o = a.O; apl.ldo = D; apl.lse = a.lse;
     apl.f8_amax = m->fp8 ? f8_slot(m, l, F8S_O) : nullptr;
     tic(m, "attn_fwd");
-    RC(launch_attn_fwd<T>(apl, s));
+    if (last && stop == 2) RC(launch_attn_sel<T>(apl, m->top_sel, m->top_nsel, m->c_O, D, s));   // the selected queries only, into compact rows
+    else RC(launch_attn_fwd<T>(apl, s));
     toc(m);
-    if (l == m->L - 1 && m->top_is_sparse) break;   // the tail of the last layer and the final norm run on the selected tokens
+    if (last && (m->top_is_sparse || stop)) break;   // the tail of the last layer and the final norm run on the selected tokens
     RC(layer_tail_dense<T>(m, l));
   }
-  if (m->top_is_sparse) { toc(m); return top_tail_compact<T>(m); }
+  if (m->top_is_sparse) { toc(m); return top_tail_compact<T>(m, m->c_sel, m->c_sel_p); }   // (the layer's attention ran in selected-first order)
+  if (stop) {
+    toc(m);
+    m->out_pending = true; m->out_attn_pending = stop != 1;
+    if (stop == 3) return RSYS_OK;
+    // the device row count (a kernel argument: nothing of the host is read after this call returns); rows [n, n up to 256) of c_O as the gather leaves them
+    RC(launch_set_int(m->c_n, m->top_nsel, s));
+    if (stop == 2) {
+      const int64_t pad = std::min<int64_t>(m->ctop_cap, ((int64_t)m->top_nsel + 255) / 256 * 256) - m->top_nsel;
+      if (pad > 0) HIP_CHECK(hipMemsetAsync(AT<T>(m->c_O) + (int64_t)m->top_nsel * D, 0, (size_t)pad * D * sizeof(T), s));
+    }
+    return top_tail_compact<T>(m, m->top_sel, stop == 1 ? m->top_sel : nullptr);
+  }
   tic(m, "hbm_rmsnorm_fwd", (4.0 + sizeof(T)) * D * NT);
   RC(launch_rmsnorm_fwd<T>(m->xL, m->P + m->o_norm, AT<T>(m->out), m->rstdf, NT, D, s));
   toc(m);
@@ -271,12 +308,36 @@ static int materialise_output_t(Model* m) {
   RC(launch_rmsnorm_fwd<T>(m->xL, m->P + m->o_norm, AT<T>(m->out), m->rstdf, NT, D, m->stream));
   return RSYS_OK;
 }
+// The same after an inference pass under the serving compact top: token order was kept, so the rest runs as the dense pass
+// would have -- the last layer's attention where it has not run (a stopped store, or attn_sel_kernel's selected queries only; the tile
+// maps are still those of the pass), its dense tail, the final norm.
+template <typename T>
+static int materialise_serving_t(Model* m) {
+  const int D = m->D, NT = 2 * m->cur_rows * m->S, l = m->L - 1, hd = m->hd;
+  Model::LayerAct& a = m->la[l];
+  if (m->out_attn_pending) {
+    AttnParams ap{};
+    ap.B = m->cur_rows; ap.T = m->T; ap.H = m->H; ap.KV = m->KV; ap.hd = hd; ap.is_bf16 = is_bf16<T>::value ? 1 : 0;
+    ap.uid = m->uid_t; ap.tm = m->tm_t; ap.qmap = m->qmap; ap.kmap = m->kmap; ap.qmap_full = m->qmap_full; ap.kmap_full = m->kmap_full;
+    ap.qmap16 = m->qmap16; ap.kmap16 = m->kmap16; ap.order_q = m->attn_order_q; ap.order_k = m->attn_order_k; ap.qbits = m->attn_qbits; ap.kbits = m->attn_kbits;
+    ap.q = a.qkv; ap.k = AT<T>(a.qkv) + m->H * hd; ap.v = AT<T>(a.qkv) + (m->H + m->KV) * hd; ap.ld = m->Nqkv;
+    ap.o = a.O; ap.ldo = D; ap.lse = a.lse;
+    RC(launch_attn_fwd<T>(ap, m->stream));
+    m->out_attn_pending = false;
+  }
+  RC(layer_tail_dense<T>(m, l));
+  RC(launch_rmsnorm_fwd<T>(m->xL, m->P + m->o_norm, AT<T>(m->out), m->rstdf, NT, D, m->stream));
+  m->out_pending = false;
+  return RSYS_OK;
+}
 int model_materialise_trunk_output(Model* m) {
-  if (!m->top_is_sparse) return RSYS_OK;
+  if (!m->top_is_sparse && !m->out_pending) return RSYS_OK;
   ARG_CHECK(m->cur_rows > 0, "no batch uploaded");
   HIP_CHECK(hipSetDevice(m->device));
   const bool tim = m->timer.enabled; m->timer.enabled = false;
-  const int rc = m->bf16_mode ? materialise_output_t<bf16>(m) : materialise_output_t<float>(m);
+  int rc;
+  if (m->top_is_sparse) rc = m->bf16_mode ? materialise_output_t<bf16>(m) : materialise_output_t<float>(m);
+  else rc = m->bf16_mode ? materialise_serving_t<bf16>(m) : materialise_serving_t<float>(m);
   m->timer.enabled = tim;
   return rc;
 }

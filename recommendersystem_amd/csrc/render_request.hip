@@ -181,11 +181,13 @@ struct RenderState {
   int forwards_full[3] = {0, 0, 0};                    // rsys_render_request_full's ranking forwards: store, candidates, empty-history chunks
   std::vector<int32_t> forward_rows;                   // (stage, rows, row_len) of every forward of the last call, run order: stage 0 retrieval, 1 store, 2 cached candidates, 3 assembled
   void note_forward(int stage, int rows, int row_len) { forward_rows.push_back(stage); forward_rows.push_back(rows); forward_rows.push_back(row_len); }
+  std::vector<int32_t> forward_top;                    // (infer.top, infer.top_rows) of every forward of the last call, in the order of forward_rows (Model::top_log)
   std::map<std::string, std::vector<unsigned char>> kept;
   void begin() {   // a call starts
     forwards[0] = forwards[1] = 0;
     forwards_full[0] = forwards_full[1] = forwards_full[2] = 0;
     forward_rows.clear();
+    forward_top.clear();
     kept.clear();
   }
   void put_bytes(const std::string& key, const void* p, size_t n) {
@@ -252,6 +254,11 @@ int render_debug_get(Model* m, const char* key, void* out, int64_t cap, int64_t*
   if (std::string(key) == "forward_rows") {
     *bytes = (int64_t)R->forward_rows.size() * 4;
     if (out && cap >= *bytes && *bytes) memcpy(out, R->forward_rows.data(), (size_t)*bytes);
+    return RSYS_OK;
+  }
+  if (std::string(key) == "forward_top") {
+    *bytes = (int64_t)R->forward_top.size() * 4;
+    if (out && cap >= *bytes && *bytes) memcpy(out, R->forward_top.data(), (size_t)*bytes);
     return RSYS_OK;
   }
   if (std::string(key) == "forwards.full") {
@@ -325,6 +332,7 @@ struct Render : RenderArgs {
     std::vector<RowDesc> sd, crows;
   } t;
 
+  ~Render() { m->top_log = nullptr; }
   Render(Model* model, const RenderArgs& a) : RenderArgs(a), m(model), S(m->Sa), D(m->D), chunk(S - S / 2), RM(m->rows_max), trim(m->serving_trim), pack(m->serving_pack), pack_rank(m->serving_pack_ranking) {}
 
   // rsys_serving_trim_set: a forward whose longest row has `live` live columns runs at this row length -- whole 64-token attention tiles,
@@ -407,6 +415,7 @@ struct Render : RenderArgs {
     }
     R = render_state(m);
     R->begin();
+    m->top_log = &R->forward_top;   // every trunk forward of this call notes what its last layer did (cleared by ~Render)
     keep = R->keep;
     return RSYS_OK;
   }

@@ -321,6 +321,16 @@ class RecommenderModel:
         check(lib().rsys_serving_pack_ranking_get(self._h, C.byref(state)))
         return bool(state.value)
 
+    def serving_compact_top(self, on=None):
+        """rsys_serving_compact_top_set: inference passes run the last layer only where its outputs are read -- the tail and the final norm
+        on the selected tokens, the attention for the selected queries where they are few, and a K/V-cache store pass ends at its last
+        copy (`serve.compact_top_mode` restates the rules).  Sets the switch when `on` is given; returns its state.  Default off."""
+        if on is not None:
+            check(lib().rsys_serving_compact_top_set(self._h, int(on)))      # (2 / 3: the measurement values of rsys.h)
+        state = C.c_int32()
+        check(lib().rsys_serving_compact_top_get(self._h, C.byref(state)))
+        return bool(state.value)
+
     @property
     def can_prefetch(self):
         """rsys_batch_prefetch / rsys_batch_swap: the next batch staged and copied beside the running step (replicated table)"""
@@ -1056,7 +1066,7 @@ class RecommenderModel:
             out = np.empty(1, np.int64)
         elif key == "npos":
             out = np.empty(4, np.int32)
-        elif key in ("top.n", "top.cap"):
+        elif key in ("top.n", "top.cap", "infer.top", "infer.top_rows"):
             out = np.empty(1, np.int32)
         elif key == "host_syncs":
             out = np.empty(2, np.int32)

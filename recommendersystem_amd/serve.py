@@ -9,6 +9,8 @@ event's identity and the last event's state, embed.py:39-60), `project` drops ev
 appends one token per candidate item, each with its own `token_mask_ids` value (candidates see the history but not each
 other), and returns the rating head at the candidates' action tokens.
 """
+import contextlib
+
 import numpy as np
 
 
@@ -225,14 +227,56 @@ def _predict_packed(model, requests, task, max_user_len, max_ranking_items):
     return out
 
 
-def predict(model, users, task, medium, max_user_len=None, max_ranking_items=None, trim=False, pack=False):
+def compact_top_rows(n_sel, n_tokens, cap):
+    """First count rule of the serving compact top (restates csrc/model_forward.hip serving_top_mode, as `_plan_segments`
+    restates the library's packing): a forward of `n_tokens` tokens that reports `n_sel` of them runs the last layer's tail and the
+    final norm on those rows only iff the selection fits the compact buffers (`cap` rows) and is at most half of the tokens."""
+    return 1 <= n_sel <= cap and 2 * n_sel <= n_tokens
+
+
+def compact_top_selected_attention(n_sel, rows, row_len):
+    """Second count rule: the last layer's attention runs for the selected queries only (attn_sel_kernel) iff there is at most one of
+    them per 64-token tile on average, `n_sel <= rows * ceil(2 row_len / 64)` -- it then reads no more K | V bytes than the tile kernel
+    would.  A count rule, not a measured threshold."""
+    return n_sel <= rows * -(-2 * row_len // 64)
+
+
+def compact_top_mode(n_sel, rows, row_len, cap, kind="select"):
+    """What the library reports as "infer.top" for an inference pass under rsys_serving_compact_top_set on a model that has the compact
+    buffers: kind "store" (a K/V-cache store pass) -> 3; "select" / "candidates" (a pass that reports `n_sel` tokens of `rows` rows of
+    2 `row_len` tokens) -> 0 dense, 1 compact tail behind the dense attention, 2 compact tail behind the selected-query attention
+    (never for candidate rows, whose keys live in the cache); n_sel = None (rsys_infer without a selection) -> 0."""
+    if kind == "store":
+        return 3
+    if n_sel is None or not compact_top_rows(n_sel, rows * 2 * row_len, cap):
+        return 0
+    return 2 if kind == "select" and compact_top_selected_attention(n_sel, rows, row_len) else 1
+
+
+@contextlib.contextmanager
+def _compact_top(model):
+    """rsys_serving_compact_top_set for the length of a call, restored on every exit path"""
+    before = model.serving_compact_top()
+    model.serving_compact_top(True)
+    try:
+        yield
+    finally:
+        model.serving_compact_top(before)
+
+
+def predict(model, users, task, medium, max_user_len=None, max_ranking_items=None, trim=False, pack=False, compact_top=False):
     """embed.py:74-161 on the HIP model (`model.config["forward"]` semantics = inference): sequence length of the request =
     the model's `max_sequence_length` (retrieval: all of it is history + query; ranking: split between history and candidates).
     A model built by `get_models` (it has an `adapter_slots` map) runs every row with the adapter of "{medium}.{task}".
     `trim=True`: the forward runs at `trim_length` of the batch's longest live row instead of S (the padding behind it is dropped, which
     is exact: no live token attends it).
     `pack=True` (implies trimming): several users share a row, each in a segment of whole 64-token attention tiles (`pack_plan`), and any
-    number of users is served in forwards of at most `max_rows` rows; results are in the users' order."""
+    number of users is served in forwards of at most `max_rows` rows; results are in the users' order.
+    `compact_top=True` (rsys_serving_compact_top_set for the length of the call): the last layer runs only where its outputs are read
+    (`compact_top_mode`); values agree with the dense pass to rounding."""
+    if compact_top:
+        with _compact_top(model):
+            return predict(model, users, task, medium, max_user_len, max_ranking_items, trim, pack)
     if pack:
         return _predict_packed(model, [(u, medium) for u in users], task, max_user_len, max_ranking_items)
     S = model.config["max_sequence_length"]
@@ -344,7 +388,7 @@ def _predict_ranking_packed(model, users, medium, full, hists, out, cache_slots)
     return out
 
 
-def predict_ranking_full(model, users, medium, trim=False, pack=False, cache_slots=None):
+def predict_ranking_full(model, users, medium, trim=False, pack=False, cache_slots=None, compact_top=False):
     """`predict(model, users, "ranking", medium)` on the reference's row (embed.py:74-161 with max_user_len = S): every user is ranked
     on its newest S - 1 history events, whatever the number of candidates, instead of the newest S // 2 - 1 that share a row with the
     candidates.  Each history is tokenised and projected once and runs once (one `rank_cache_store` per wave of `max_rows` users);
@@ -355,7 +399,12 @@ def predict_ranking_full(model, users, medium, trim=False, pack=False, cache_slo
     `pack=True` (implies trimming): the users with a history run by `rank_cache_pack_plan` -- several histories per store row, several
     users' candidate chunks per candidate row, waves of up to `cache_slots` (default 4 x max_rows) users; min(users with a history,
     that many) cache slots are reserved when the model holds fewer -- which, as every `rank_cache_reserve` of a new size, drops what
-    a caller had stored.  Users with an empty history and users without candidates go the ways they go without it."""
+    a caller had stored.  Users with an empty history and users without candidates go the ways they go without it.
+    `compact_top=True` (rsys_serving_compact_top_set for the length of the call): every store forward ends at its last K | V copy (the
+    slots hold the same bits) and the candidate forwards run the last layer's tail on the candidates' action tokens only."""
+    if compact_top:
+        with _compact_top(model):
+            return predict_ranking_full(model, users, medium, trim, pack, cache_slots)
     S = model.config["max_sequence_length"]
     n0 = model.config["vocab_sizes"]["0_matchedid"]
     key = f"{medium}.ranking"
@@ -409,12 +458,15 @@ def predict_ranking_full(model, users, medium, trim=False, pack=False, cache_slo
     return out
 
 
-def predict_mixed(model, requests, task, max_user_len=None, max_ranking_items=None, trim=False, pack=False):
+def predict_mixed(model, requests, task, max_user_len=None, max_ranking_items=None, trim=False, pack=False, compact_top=False):
     """`predict` for users of both media in ONE forward: `requests` = [(user, medium), ...]; row i of the batch is the row
     `build_batch([user_i], task, medium_i, ...)` builds and runs with the adapter slot `model.adapter_slots[f"{medium_i}.{task}"]`
     (embed.jl:5-84 keeps one queue per (medium, task) on one GPU; single-user inference is launch-bound, so sharing a forward
     is what the shared trunk buys).  Result i is keyed "{medium_i}.{task}" like `predict`'s.  `pack=True`: users of both media share
-    rows as well (`pack_plan`, one adapter slot per tile)."""
+    rows as well (`pack_plan`, one adapter slot per tile).  `compact_top=True`: as `predict`'s."""
+    if compact_top:
+        with _compact_top(model):
+            return predict_mixed(model, requests, task, max_user_len, max_ranking_items, trim, pack)
     slots = getattr(model, "adapter_slots", None)
     if not slots:
         raise ValueError("predict_mixed: the model has no adapter_slots map (build it with get_models)")
@@ -842,7 +894,7 @@ def render_items(model, states, pagination):
     return [(pages[g], int(totals[g])) for g in range(len(states))]
 
 
-def render(model, states, pagination, registry=None, max_ranking_items=None, full_history=False, exact=False, trim=False):
+def render(model, states, pagination, registry=None, max_ranking_items=None, full_history=False, exact=False, trim=False, compact_top=False):
     """render.jl `render(state, pagination)` (lines 437-474) without the card rendering, for a list of states: `retrieval`, the page's
     slice of at most 1024 candidates, the ranking forward (`predict(..., "ranking")` in chunks of at most `max_ranking_items` candidates,
     default the model's S - S // 2; candidates are masked from each other, so chunking does not change the result of a user with a
@@ -855,7 +907,11 @@ def render(model, states, pagination, registry=None, max_ranking_items=None, ful
     page past rank 8192 is empty and every state needs a user; both are closed by `exact=True` / `render_items`: the page's candidates
     then come from `retrieval_window`, so total is the number of admissible items and every offset below it has a page (ranking and
     reranking unchanged), and states without users go through `render_items` -- every state render.jl renders.  `trim=True`: the
-    ranking forwards run trimmed (`predict(..., trim=True)` / `predict_ranking_full(..., trim=True)`)."""
+    ranking forwards run trimmed (`predict(..., trim=True)` / `predict_ranking_full(..., trim=True)`).  `compact_top=True`: they run
+    under rsys_serving_compact_top_set (`predict(..., compact_top=True)` / `predict_ranking_full(..., compact_top=True)`)."""
+    if compact_top:
+        with _compact_top(model):
+            return render(model, states, pagination, registry, max_ranking_items, full_history, exact, trim)
     pags = [pagination] * len(states) if isinstance(pagination, dict) else list(pagination)
     if exact:
         for pg in pags:
@@ -1074,7 +1130,7 @@ def render_full_store_rows(n_hist, S, max_rows, slots=None):
             for row_len, placed in _plan_segments(hist[w0:w0 + slots], S, max_rows)]
 
 
-def render_users(model, states, pagination, registry=None, full_history=False, trim=False, pack=False, pack_ranking=False):
+def render_users(model, states, pagination, registry=None, full_history=False, trim=False, pack=False, pack_ranking=False, compact_top=False):
     """`render` from raw histories in ONE device call (rsys_render_request): the same states, but users need no "embeds" -- the
     retrieval forward, `retrieval`, the page window, the ranking forward (every chunk row of every user, both media, in waves of the
     model's max_rows) and `ranking` + `reranking` run back to back on the device; only the pages and the totals come back.  A model built
@@ -1088,7 +1144,12 @@ def render_users(model, states, pagination, registry=None, full_history=False, t
     retrieval stage runs several users per row (`pack_plan`'s layout); the ranking stages are the trimmed ones.
     `pack_ranking=True` (rsys_serving_pack_ranking_set for the length of the call; `full_history=True` only): the K/V-cache store rows
     hold several users, in waves of up to the model's reserved cache slots (`rank_cache_pack_plan`'s store stage); pages and totals are
-    unchanged."""
+    unchanged.
+    `compact_top=True` (rsys_serving_compact_top_set for the length of the call): every forward of the pipeline runs its last layer only
+    where its outputs are read; scores agree with the dense pipeline to rounding, so two items closer than that may swap places."""
+    if compact_top:
+        with _compact_top(model):
+            return render_users(model, states, pagination, registry, full_history, trim, pack, pack_ranking)
     if not states:
         return []
     if pack_ranking and not full_history:
