@@ -235,6 +235,32 @@ int32_t rsys_retrieve_relations_set(rsys_model* m, int32_t medium, int32_t kind,
 int32_t rsys_retrieve_similarity_set(rsys_model* m, int32_t medium, int64_t dim, const float* emb, const float* crossproject);
 /* released items of medium m: mask[V_m], nonzero = released (render.jl's `keys(get_media_info(m))`); NULL: every item released */
 int32_t rsys_retrieve_released_set(rsys_model* m, int32_t medium, const uint8_t* mask);
+/* Query weights of the NEXT request (the reference's roadmap: "inference: allow weighting different queries"): a finite f32
+ * weight per user and per selected item of the request's states, in the call's user order and in the order of sel_ids.  One call instead of
+ * a weighted twin of each of the six request entry points.  The arrays are copied on the host and held by the model until the next call of
+ * rsys_retrieve_request, rsys_retrieve_window, rsys_rank_request, rsys_render_request, rsys_render_request_full or rsys_render_items, which
+ * consumes them: they are cleared when that call returns, on success and on error alike.  No other entry point (rsys_retrieve_topk included)
+ * reads or clears them.  (NULL, 0) for a kind = unweighted for that kind; (NULL, 0, NULL, 0) clears both; a call replaces what was held.
+ * The consuming call checks the counts before anything else -- n_users against its n_queries / n_users, n_sel against
+ * sel_offsets[n_groups] (0 without sel_offsets) -- and a mismatch is RSYS_ERR_ARG with outputs untouched.  rsys_rank_request takes no
+ * selected-item weights and rsys_render_items no user weights (RSYS_ERR_ARG); rsys_rank_request with r_in reads no weights but consumes
+ * them.  A weight that is NaN or infinite: RSYS_ERR_ARG, and nothing is held.
+ * Semantics: weights scale score terms only, every operation rounded in fp32 on its own (no fused multiply-add), so a float32 restatement
+ * is bit-exact --
+ *   selected sum   s_g = s_g + w_a * x_a in list order (x_a = E_m[id] or crossproject.{am} E_am[id]); the prior E_m^T s_g as without weights
+ *   retrieval      score = score + w_q * (z_q[i] - lse_q) in query order
+ *   ranking        score = score + w_u * (lp_u + r_u) in user order, lp_u and r_u as rsys_rank_request forms them
+ * A weight of +0.0 or -0.0 skips the term: the running sum keeps its bits, so 0 * -inf never makes a NaN.  Negative weights are allowed
+ * ("less like B"; a thumbs-down).  With every weight 1.0 each result equals the unweighted call's bit for bit; without pending weights of a
+ * kind the unweighted kernels run.  Masks and flags ignore the weights: a user vetoes its watched items, adaptations, recaps, missing
+ * dependencies and sequels whatever its weight, a selected item of the request's medium is masked whatever its weight, the related flags
+ * read every user's list; totals change only where a score becomes NaN or -inf.  Inside rsys_render_request / _full the same weights reach
+ * the retrieval stage and the ranking stage of every wave (packed, trimmed and compact-topped alike: those change which forwards run, not
+ * the score kernels); no forward is skipped for a zero-weight user. */
+int32_t rsys_query_weights_set(rsys_model* m, const float* user_w, int64_t n_users,   /* [n_users], or NULL with 0 */
+                               const float* sel_w, int64_t n_sel);                    /* [n_sel], or NULL with 0 */
+/* out = (n_users, n_sel) of the weights the model holds for the next request, 0 = none of that kind */
+int32_t rsys_query_weights_pending(rsys_model* m, int64_t out[2]);
 /* A whole render.jl `retrieval(state)` per group of queries, on the tables above: score_g = p_g + the rsys_retrieve_topk score, where
  * p_g = E_m^T s_g, s_g = sum over the group's selected items in list order of E_m[id] (same medium) or crossproject.{am} E_am[id] (fp32
  * throughout; 0 without selected items).  Masked for group g (render.jl:255-331): item 0; the group's selected items of medium m; items

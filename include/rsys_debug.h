@@ -140,6 +140,22 @@ int32_t rsys_rank_cache_get(rsys_model* m, int32_t layer, int32_t slot, void* ou
  * counts [rows]; 1 <= k <= min(V, 8192) */
 int32_t rsys_op_topk(const float* scores, int64_t ld, int32_t rows, int32_t V, int32_t k,
                      int32_t* ids, float* vals, int32_t* counts);
+/* the three weighted accumulations of rsys_query_weights_set alone, one launch each on caller-provided DEVICE buffers (host: cand_offsets,
+ * retrieval_coef, rating_coefs); a section runs when its output is not NULL.  Shared by the first two: z [rows][ldz] and lse (indexed by
+ * query / user q, row q - q0 of z), members (the queries of every group, group by group), ranges int32 [n_groups][2] = the slice of
+ * members each group adds in this launch, user_w indexed as lse.
+ * dst != NULL (combine_w_kernel): dst[g][i] = src[g][i] + sum of w_q * (z_q[i] - lse_q), rows of V floats; last != 0 writes the
+ *   order-preserving uint32 key of the score instead (0 = NaN / -inf); last == 0 leaves the row of a group with an empty range unwritten.
+ * sc != NULL (rank_score_w_kernel): groups of cand_offsets[g + 1] - cand_offsets[g] <= 1024 candidates cand (column ids of z);
+ *   sc[c] = (first ? 0 : sc[c]) + sum of w_u * (lp_u + r_u), r_masked ragged with user u's values at rm_offsets[u] (int64, device).
+ * S != NULL (selected_sum_w_kernel): S[g][dim] = sum over a in [sel_offsets[g], sel_offsets[g + 1]) (int64, device) of sel_w[a] * x_a,
+ *   x_a = emb_m[sel_ids[a]] when sel_medium[a] == medium, else X[a] (rows of dim floats). */
+int32_t rsys_op_query_weights(const float* z, int64_t ldz, const float* lse, const int32_t* members, const int32_t* ranges, int32_t q0,
+                              const float* user_w, int32_t n_groups, const float* src, float* dst, int32_t V, int32_t last,
+                              const int64_t* cand_offsets, const int32_t* cand, const float* r_masked, const int64_t* rm_offsets,
+                              const float* retrieval_coef, const float* rating_coefs, float rating_mean, int32_t first, float* sc,
+                              const int64_t* sel_offsets, const int32_t* sel_medium, const int32_t* sel_ids, int32_t medium, const float* emb_m,
+                              const float* X, int32_t dim, const float* sel_w, float* S);
 /* the count of rsys_retrieve_target_rank alone, on caller-provided device buffers: per row r of scores [rows][ld >= V] (NaN or -inf marks
  * an inadmissible entry, -0.0 == +0.0) rank_out[r] = 1 + #{admissible i : s_i > s_t} + #{admissible i < t : s_i == s_t} with
  * t = targets[r] in [0, V), or 0 when s_t is NaN or -inf; 1 <= rows <= 65535 */

@@ -397,6 +397,23 @@ function retrieve_released_set(m::Model, medium::Integer, mask = nothing)
     x = mask === nothing ? Ptr{UInt8}(C_NULL) : Vector{UInt8}(mask)
     GC.@preserve x check(ccall((:rsys_retrieve_released_set, LIB), Int32, (Ptr{Cvoid}, Int32, Ptr{UInt8}), m.h, medium, x))
 end
+# query weights of the NEXT request call on the model (rsys_query_weights_set): one finite Float32 per user / per selected item in the
+# call's order, or nothing (unweighted for that kind; both nothing clears).  retrieve_request, retrieve_window, rank_request,
+# render_request, render_request_full and render_items consume them, on success and on error alike.
+function query_weights_set(m::Model, user_w = nothing, sel_w = nothing)
+    u = (user_w === nothing || isempty(user_w)) ? Ptr{Float32}(C_NULL) : Vector{Float32}(user_w)
+    s = (sel_w === nothing || isempty(sel_w)) ? Ptr{Float32}(C_NULL) : Vector{Float32}(sel_w)
+    nu = u isa Ptr ? 0 : length(u)
+    ns = s isa Ptr ? 0 : length(s)
+    GC.@preserve u s check(ccall((:rsys_query_weights_set, LIB), Int32, (Ptr{Cvoid}, Ptr{Float32}, Int64, Ptr{Float32}, Int64),
+        m.h, u, nu, s, ns))
+end
+# (n_users, n_sel) of the weights held for the next request, 0 = none of that kind
+function query_weights_pending(m::Model)
+    out = zeros(Int64, 2)
+    GC.@preserve out check(ccall((:rsys_query_weights_pending, LIB), Int32, (Ptr{Cvoid}, Ptr{Int64}), m.h, out))
+    (out[1], out[2])
+end
 # Q (D, n_queries); group 0-based per query or nothing; hist: one vector of (medium, matchedid, status) tuples per query in list order;
 # sel: one vector of (medium, matchedid) tuples per group.  Returns (ids, scores, counts) as retrieve_topk does.
 function retrieve_request(m::Model, medium::Integer, Q::Matrix{Float32}, k::Integer; group = nothing, n_groups::Integer = size(Q, 2),

@@ -79,6 +79,8 @@ _SIGS = [
     ("rsys_retrieve_similarity_set", C.c_int32, [_P, C.c_int32, C.c_int64, _P, _P]),
     ("rsys_retrieve_released_set", C.c_int32, [_P, C.c_int32, _P]),
     ("rsys_retrieve_request", C.c_int32, [_P, C.c_int32, _P, C.c_int64, _P, C.c_int32, _P, _P, _P, _P, _P, _P, _P, C.c_int32, _P, _P, _P]),
+    ("rsys_query_weights_set", C.c_int32, [_P, _P, C.c_int64, _P, C.c_int64]),
+    ("rsys_query_weights_pending", C.c_int32, [_P, _P]),
     ("rsys_retrieve_window", C.c_int32, [_P, C.c_int32, _P, C.c_int64, _P, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     ("rsys_render_items", C.c_int32, [_P, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int64, _P, _P]),
     ("rsys_rank_related_set", C.c_int32, [_P, C.c_int32, C.c_int64, _P, _P, _P]),
@@ -225,6 +227,9 @@ _SIGS = [
                                           + [C.c_char_p, C.c_int32, C.POINTER(C.c_int32)]),
     ("rsys_op_attention", C.c_int32, [C.c_int32] + [C.c_int32] * 5 + [_P] * 9),
     ("rsys_op_attention_ex", C.c_int32, [C.c_int32] + [C.c_int32] * 5 + [_P] * 10 + [C.c_int32, _P, _P, _P]),
+    ("rsys_op_query_weights", C.c_int32, [_P, C.c_int64, _P, _P, _P, C.c_int32, _P, C.c_int32, _P, _P, C.c_int32, C.c_int32,
+                                          _P, _P, _P, _P, _P, _P, C.c_float, C.c_int32, _P,
+                                          _P, _P, _P, C.c_int32, _P, _P, C.c_int32, _P, _P]),
     ("rsys_op_topk", C.c_int32, [_P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P]),
     ("rsys_op_target_rank", C.c_int32, [_P, C.c_int64, C.c_int32, C.c_int32, _P, _P]),
     ("rsys_op_pair_ranks", C.c_int32, [_P, C.c_int64, C.c_int32, C.c_int32, _P, _P, _P, _P]),

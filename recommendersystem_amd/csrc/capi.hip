@@ -23,6 +23,37 @@ struct rsys_optimizer { Optimizer o; };
 
 #define CHECK_HANDLE(h) do { if ((h) == nullptr) { set_error("null handle"); return RSYS_ERR_ARG; } } while (0)
 
+namespace {
+// The pending query weights of a model (rsys_query_weights_set) in the hands of the request entry point that consumes them: moved out
+// of the model on entry, so the model holds none again on every return path, success and error alike.
+struct TakenWeights {
+  std::vector<float> user, sel;
+  bool have_user, have_sel;
+  explicit TakenWeights(Model* m) : user(std::move(m->qw_user)), sel(std::move(m->qw_sel)), have_user(m->qw_have_user), have_sel(m->qw_have_sel) {
+    m->qw_user.clear(); m->qw_sel.clear();
+    m->qw_have_user = m->qw_have_sel = false;
+  }
+  // the counts against the call's: n_users (-1: the call accepts no user weights) and sel_off[n_groups] (accept_sel == false: the
+  // call accepts no selected-item weights).  A group count the call itself will refuse is left to it: no weights are handed on.
+  int check(const char* who, int64_t n_users, bool accept_sel, const int64_t* sel_off, int64_t ng, QueryWeights* out) const {
+    *out = QueryWeights{};
+    if (have_user) {
+      ARG_CHECK(n_users >= 0, std::string(who) + ": the pending query weights hold user weights, which this call does not take");
+      ARG_CHECK((int64_t)user.size() == n_users, std::string(who) + ": the pending user weights do not match the call's users (rsys_query_weights_set n_users)");
+      out->user = user.data();
+    }
+    if (have_sel) {
+      ARG_CHECK(accept_sel, std::string(who) + ": the pending query weights hold selected-item weights, which this call does not take");
+      if (ng < 1 || ng > 4096) { *out = QueryWeights{}; return RSYS_OK; }
+      const int64_t nsel = sel_off ? sel_off[ng] : 0;
+      ARG_CHECK((int64_t)sel.size() == nsel, std::string(who) + ": the pending selected-item weights do not match sel_offsets[n_groups] (rsys_query_weights_set n_sel)");
+      out->sel = sel.data();
+    }
+    return RSYS_OK;
+  }
+};
+}  // namespace
+
 extern "C" {
 
 const char* rsys_version(void) { return "recommendersystem_amd 0.1 (gfx950)"; }
@@ -202,29 +233,58 @@ int32_t rsys_retrieve_released_set(rsys_model* h, int32_t medium, const uint8_t*
   CHECK_HANDLE(h);
   return model_retrieve_released_set(h->m, medium, mask);
 }
+int32_t rsys_query_weights_set(rsys_model* h, const float* user_w, int64_t n_users, const float* sel_w, int64_t n_sel) {
+  CHECK_HANDLE(h);
+  Model* m = h->m;
+  m->qw_user.clear(); m->qw_sel.clear();
+  m->qw_have_user = m->qw_have_sel = false;   // (a refused call holds nothing)
+  ARG_CHECK(n_users >= 0 && n_sel >= 0, "query_weights_set: counts must be >= 0");
+  ARG_CHECK((user_w != nullptr) == (n_users > 0) && (sel_w != nullptr) == (n_sel > 0), "query_weights_set: an array and its count go together ((NULL, 0) = unweighted)");
+  for (int64_t i = 0; i < n_users; ++i) ARG_CHECK(std::isfinite(user_w[i]), "query_weights_set: weights must be finite");
+  for (int64_t i = 0; i < n_sel; ++i) ARG_CHECK(std::isfinite(sel_w[i]), "query_weights_set: weights must be finite");
+  if (n_users) { m->qw_user.assign(user_w, user_w + n_users); m->qw_have_user = true; }
+  if (n_sel) { m->qw_sel.assign(sel_w, sel_w + n_sel); m->qw_have_sel = true; }
+  return RSYS_OK;
+}
+int32_t rsys_query_weights_pending(rsys_model* h, int64_t out[2]) {
+  CHECK_HANDLE(h);
+  ARG_CHECK(out, "query_weights_pending: null output");
+  out[0] = h->m->qw_have_user ? (int64_t)h->m->qw_user.size() : 0;
+  out[1] = h->m->qw_have_sel ? (int64_t)h->m->qw_sel.size() : 0;
+  return RSYS_OK;
+}
 int32_t rsys_retrieve_request(rsys_model* h, int32_t medium, const float* queries, int64_t n_queries, const int32_t* group, int32_t n_groups,
                               const int64_t* hist_offsets, const int32_t* hist_medium, const int32_t* hist_ids, const int32_t* hist_status,
                               const int64_t* sel_offsets, const int32_t* sel_medium, const int32_t* sel_ids, int32_t k, int32_t* ids_out,
                               float* scores_out, int32_t* counts_out) {
   CHECK_HANDLE(h);
+  const TakenWeights tw(h->m);
+  QueryWeights qw;
+  RC(tw.check("retrieve_request", n_queries, true, sel_offsets, n_groups, &qw));
   return model_retrieve_request(h->m, medium, queries, n_queries, group, n_groups, hist_offsets, hist_medium, hist_ids, hist_status,
-                                sel_offsets, sel_medium, sel_ids, k, ids_out, scores_out, counts_out);
+                                sel_offsets, sel_medium, sel_ids, k, ids_out, scores_out, counts_out, qw);
 }
 int32_t rsys_retrieve_window(rsys_model* h, int32_t medium, const float* queries, int64_t n_queries, const int32_t* group, int32_t n_groups,
                              const int64_t* hist_offsets, const int32_t* hist_medium, const int32_t* hist_ids, const int32_t* hist_status,
                              const int64_t* sel_offsets, const int32_t* sel_medium, const int32_t* sel_ids, const int64_t* win_start,
                              const int32_t* win_len, int32_t* ids_out, float* scores_out, int32_t* counts_out, int32_t* total_out) {
   CHECK_HANDLE(h);
+  const TakenWeights tw(h->m);
+  QueryWeights qw;
+  RC(tw.check("retrieve_window", n_queries, true, sel_offsets, n_groups, &qw));
   const RetrieveWin win{win_start, win_len, total_out};
   return model_retrieve_window(h->m, medium, queries, n_queries, group, n_groups, hist_offsets, hist_medium, hist_ids, hist_status,
-                               sel_offsets, sel_medium, sel_ids, &win, nullptr, ids_out, scores_out, counts_out);
+                               sel_offsets, sel_medium, sel_ids, &win, nullptr, ids_out, scores_out, counts_out, qw);
 }
 int32_t rsys_render_items(rsys_model* h, int32_t n_groups, const int32_t* group_medium, const int64_t* offset, const int32_t* limit,
                           const float* penalties, const int64_t* sel_offsets, const int32_t* sel_medium, const int32_t* sel_ids,
                           int32_t* ids_out, int64_t ids_cap, int64_t* ids_offsets, int32_t* total_out) {
   CHECK_HANDLE(h);
+  const TakenWeights tw(h->m);
+  QueryWeights qw;
+  RC(tw.check("render_items", -1, true, sel_offsets, n_groups, &qw));
   return model_render_items(h->m, n_groups, group_medium, offset, limit, penalties, sel_offsets, sel_medium, sel_ids, ids_out, ids_cap,
-                            ids_offsets, total_out);
+                            ids_offsets, total_out, qw.sel);
 }
 int32_t rsys_rank_related_set(rsys_model* h, int32_t medium, int64_t n, const int64_t* colptr, const int32_t* rowval, const float* nzval) {
   CHECK_HANDLE(h);
@@ -236,8 +296,12 @@ int32_t rsys_rank_request(rsys_model* h, int32_t medium, int32_t n_groups, const
                           const int32_t* hist_ids, const int32_t* hist_status, const float* retrieval_coef, const float* rating_coefs,
                           float rating_mean, const float* r_in, int32_t* ids_out, float* r_out) {
   CHECK_HANDLE(h);
+  const TakenWeights tw(h->m);
+  QueryWeights qw;
+  RC(tw.check("rank_request", n_users, false, nullptr, n_groups, &qw));
   return model_rank_request(h->m, medium, n_groups, cand_offsets, cand_ids, partialk, penalties, queries, n_users, group, r_masked, n_r_masked,
-                            hist_offsets, hist_medium, hist_ids, hist_status, retrieval_coef, rating_coefs, rating_mean, r_in, ids_out, r_out);
+                            hist_offsets, hist_medium, hist_ids, hist_status, retrieval_coef, rating_coefs, rating_mean, r_in, ids_out, r_out,
+                            qw.user);
 }
 int32_t rsys_render_request(rsys_model* h, int32_t n_groups, const int32_t* group_medium, const int64_t* offset, const int32_t* limit,
                             const float* penalties, int64_t n_users, const int32_t* group, const rsys_batch* retrieval_rows,
@@ -247,7 +311,9 @@ int32_t rsys_render_request(rsys_model* h, int32_t n_groups, const int32_t* grou
                             const int32_t* sel_ids, const int32_t* coef_have, const float* coefs, int32_t* ids_out, int64_t ids_cap,
                             int64_t* ids_offsets, int32_t* total_out) {
   CHECK_HANDLE(h);
+  const TakenWeights tw(h->m);
   RenderArgs a{};
+  RC(tw.check("render_request", n_users, true, sel_offsets, n_groups, &a.qw));
   a.full = false; a.ng = n_groups; a.group_medium = group_medium; a.offset = offset; a.limit = limit; a.penalties = penalties;
   a.nu = n_users; a.group = group; a.rb = retrieval_rows; a.retrieval_token = retrieval_token; a.pb = ranking_prefix; a.P = prefix_stride;
   a.user_desc = user_desc; a.user_ts = user_ts; a.slots = adapter_slots;
@@ -263,7 +329,9 @@ int32_t rsys_render_request_full(rsys_model* h, int32_t n_groups, const int32_t*
                                  const int64_t* sel_offsets, const int32_t* sel_medium, const int32_t* sel_ids, const int32_t* coef_have,
                                  const float* coefs, int32_t* ids_out, int64_t ids_cap, int64_t* ids_offsets, int32_t* total_out) {
   CHECK_HANDLE(h);
+  const TakenWeights tw(h->m);
   RenderArgs a{};
+  RC(tw.check("render_request", n_users, true, sel_offsets, n_groups, &a.qw));
   a.full = true; a.ng = n_groups; a.group_medium = group_medium; a.offset = offset; a.limit = limit; a.penalties = penalties;
   a.nu = n_users; a.group = group; a.rb = retrieval_rows; a.retrieval_token = retrieval_token; a.pb = nullptr; a.P = 0;
   a.user_desc = user_desc; a.user_ts = user_ts; a.slots = adapter_slots;
@@ -1183,6 +1251,20 @@ int32_t rsys_op_rank_cache_copy_segments(int32_t dtype, int32_t rows, int32_t T,
 int32_t rsys_op_topk(const float* scores, int64_t ld, int32_t rows, int32_t V, int32_t k, int32_t* ids, float* vals, int32_t* counts) {
   switches_parse();
   return op_topk(scores, ld, rows, V, k, ids, vals, counts);
+}
+int32_t rsys_op_query_weights(const float* z, int64_t ldz, const float* lse, const int32_t* members, const int32_t* ranges, int32_t q0,
+                              const float* user_w, int32_t n_groups, const float* src, float* dst, int32_t V, int32_t last,
+                              const int64_t* cand_offsets, const int32_t* cand, const float* r_masked, const int64_t* rm_offsets,
+                              const float* retrieval_coef, const float* rating_coefs, float rating_mean, int32_t first, float* sc,
+                              const int64_t* sel_offsets, const int32_t* sel_medium, const int32_t* sel_ids, int32_t medium, const float* emb_m,
+                              const float* X, int32_t dim, const float* sel_w, float* S) {
+  switches_parse();
+  ARG_CHECK(dst || sc || S, "rsys_op_query_weights: no section asked for (dst, sc and S are all NULL)");
+  if (dst) RC(op_combine_weighted(src, dst, n_groups, V, last, z, ldz, lse, members, ranges, q0, user_w));
+  if (sc) RC(op_rank_score_weighted(n_groups, cand_offsets, cand, z, ldz, lse, members, ranges, q0, r_masked, rm_offsets, retrieval_coef,
+                                    rating_coefs, rating_mean, first, user_w, sc));
+  if (S) RC(op_selected_sum_weighted(n_groups, sel_offsets, sel_medium, sel_ids, medium, emb_m, X, dim, sel_w, S));
+  return RSYS_OK;
 }
 int32_t rsys_op_target_rank(const float* scores, int64_t ld, int32_t rows, int32_t V, const int32_t* targets, int32_t* rank_out) {
   switches_parse();

@@ -71,7 +71,17 @@ __device__ __forceinline__ unsigned score_key(float s) {
   return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 
-// total-order key of a float under Julia's `isless` (similarity_metrics.hip; the order rsys_rank_request documents for its argmax):
+// s + w * x of a weighted query term (rsys_query_weights_set; retrieve.hip, retrieve_request.hip, rank_request.hip): the product and the
+// sum each rounded to fp32 on their own -- never one fused multiply-add -- so a float32 restatement on the host gives the same bits.  A
+// weight of +-0.0 drops the term: s keeps its bits, whatever x holds (0 * -inf would be NaN).
+__device__ __forceinline__ float weighted_add(float s, float w, float x) {
+#pragma clang fp contract(off)
+  if (w == 0.f) return s;
+  const float p = w * x;
+  return s + p;
+}
+
+// total-order key of a float under Julia's `isless` (similarity_metrics.hip;the order rsys_rank_request documents for its argmax):
 // -inf < ... < -0.0 < +0.0 < ... < +inf < NaN, every NaN (either sign, any payload) the same largest key.  Unlike score_key nothing is
 // merged or dropped: the two zeros differ, -inf and NaN are ordinary values.  The smallest key, -inf's, is 0x007fffff, so 0 is free.
 __device__ __forceinline__ unsigned isless_key(float s) {

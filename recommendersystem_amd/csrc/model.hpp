@@ -268,6 +268,9 @@ struct Model {
   DevScratch rws;                       // rsys_retrieve_topk's workspace; a RetrieveDev result lives in it until the next retrieval call
   RetrievalTables* rtab = nullptr;      // rsys_retrieve_request's serving tables and workspace (not part of checkpoints)
   RankTables* rank = nullptr;           // rsys_rank_request's "{m}.related" tables and workspace (not part of checkpoints)
+  // rsys_query_weights_set: the weights the next request entry point consumes (host copies; have_*: that kind was given)
+  std::vector<float> qw_user, qw_sel;
+  bool qw_have_user = false, qw_have_sel = false;
   DevScratch ews;                       // rsys_retrieve_target_rank's workspace
   // adapter bank of a base model (adapter_bank.hip, allocated by the first rsys_adapter_set): LoRA adapter sets in slots beside the frozen
   // trunk.  bank_rows (device, one slot or -1 per batch row) is non-null only inside rsys_infer_select_adapters: forward_trunk then adds
@@ -439,7 +442,11 @@ struct RetrieveDev;
 struct RetrieveWin { const int64_t* start; const int32_t* len; int32_t* total_out; };
 int model_retrieve_run(Model* m, int medium, const float* queries, int64_t nq, const int32_t* group, int32_t ng, const RetrieveInit& init,
                        int32_t k, int32_t* ids_out, float* scores_out, int32_t* counts_out, RetrieveDev* dev = nullptr,
-                       const RetrieveWin* win = nullptr);
+                       const RetrieveWin* win = nullptr, const float* user_w = nullptr);
+// Query weights of one request (rsys_query_weights_set), host arrays: user [n_queries / n_users] and sel
+// [sel_off[n_groups]], each null when that kind is unweighted -- the request then launches the unweighted kernels.  The C entry points
+// take them from the model's pending pair (query_weights_take) and have checked the counts; inner calls pass their slices.
+struct QueryWeights { const float* user = nullptr; const float* sel = nullptr; };
 // z = Q F_m^T and lse of one chunk of <= RETRIEVE_CHUNK query rows (part: nc * RETRIEVE_LSE_SPLIT float2), as rsys_retrieve_topk scores
 constexpr int RETRIEVE_CHUNK = 256, RETRIEVE_LSE_SPLIT = 64;
 template <typename T>
@@ -452,7 +459,7 @@ int model_retrieve_released_set(Model* m, int medium, const uint8_t* mask);
 int model_retrieve_request(Model* m, int medium, const float* queries, int64_t nq, const int32_t* group, int32_t ng, const int64_t* hist_off,
                            const int32_t* hist_medium, const int32_t* hist_ids, const int32_t* hist_status, const int64_t* sel_off,
                            const int32_t* sel_medium, const int32_t* sel_ids, int32_t k, int32_t* ids_out, float* scores_out,
-                           int32_t* counts_out);
+                           int32_t* counts_out, QueryWeights qw = {});
 void retrieve_tables_free(Model* m);
 // the same request with its queries read from, and its result left in, device memory (rsys_render_request): d_queries [nq][D] fp32;
 // after the call *d_ids / *d_vals point at the [ng][k] result rows in the retrieval workspace (valid until the next retrieval call on the
@@ -460,13 +467,13 @@ void retrieve_tables_free(Model* m);
 struct RetrieveDev { const float* d_queries = nullptr; int32_t* d_ids = nullptr; float* d_vals = nullptr; };
 int model_retrieve_request_dev(Model* m, int medium, RetrieveDev* dev, int64_t nq, const int32_t* group, int32_t ng, const int64_t* hist_off,
                                const int32_t* hist_medium, const int32_t* hist_ids, const int32_t* hist_status, const int64_t* sel_off,
-                               const int32_t* sel_medium, const int32_t* sel_ids, int32_t k, int32_t* counts_out);
+                               const int32_t* sel_medium, const int32_t* sel_ids, int32_t k, int32_t* counts_out, QueryWeights qw = {});
 // rsys_retrieve_window: the request above with a window of each group's ordering instead of its top k (RetrieveWin); dev == nullptr: the
 // rows [ng][1024] go to ids_out / scores_out (host), else they stay on the device as after model_retrieve_request_dev
 int model_retrieve_window(Model* m, int medium, const float* queries, int64_t nq, const int32_t* group, int32_t ng, const int64_t* hist_off,
                           const int32_t* hist_medium, const int32_t* hist_ids, const int32_t* hist_status, const int64_t* sel_off,
                           const int32_t* sel_medium, const int32_t* sel_ids, const RetrieveWin* win, RetrieveDev* dev, int32_t* ids_out,
-                          float* scores_out, int32_t* counts_out);
+                          float* scores_out, int32_t* counts_out, QueryWeights qw = {});
 const float* retrieve_similarity_table(Model* m, int medium, int64_t* dim);   // "embeddings.{m}" [V_m][dim] on the device, or null
 // rank_request.hip: ranking and diversity reranking of retrieved candidates (rsys_rank_related_set, rsys_rank_request, test hooks)
 int model_rank_related_set(Model* m, int medium, int64_t n, const int64_t* colptr, const int32_t* rowval, const float* nzval);
@@ -474,7 +481,7 @@ int model_rank_request(Model* m, int medium, int32_t ng, const int64_t* cand_off
                        const float* penalties, const float* queries, int64_t nu, const int32_t* group, const float* r_masked, int64_t n_rm,
                        const int64_t* hist_off, const int32_t* hist_medium, const int32_t* hist_ids, const int32_t* hist_status,
                        const float* retrieval_coef, const float* rating_coefs, float rating_mean, const float* r_in, int32_t* ids_out,
-                       float* r_out);
+                       float* r_out, const float* user_w = nullptr);
 int model_rank_gram(Model* m, int medium, int32_t ng, const int64_t* cand_off, const int32_t* cand_ids, float* out, int64_t n_out);
 // the same request with candidates, queries and r_masked read from device memory (rsys_render_request): d_cand [n_total] distinct ids in
 // [0, V_m) per group (a retrieval result), d_queries [nu][D], d_rm ragged over users.  Group g's page = picks [page_lo[g], page_hi[g]) of
@@ -485,7 +492,7 @@ struct RankDev { const int32_t* d_cand; const float* d_queries; const float* d_r
 int model_rank_request_dev(Model* m, int medium, int32_t ng, const int64_t* cand_off, const RankDev* dev, const int32_t* partialk,
                            const float* penalties, int64_t nu, const int32_t* group, int64_t n_rm, const int64_t* hist_off,
                            const int32_t* hist_medium, const int32_t* hist_ids, const int32_t* hist_status, const float* retrieval_coef,
-                           const float* rating_coefs, float rating_mean);
+                           const float* rating_coefs, float rating_mean, const float* user_w = nullptr);
 // reranking alone on device candidates (rsys_render_items: a state without users): r = +0.0 for every candidate, no related flags
 int model_rank_items_dev(Model* m, int medium, int32_t ng, const int64_t* cand_off, const RankDev* dev, const int32_t* partialk,
                          const float* penalties);
@@ -503,18 +510,28 @@ struct RenderArgs {
   const int64_t* sel_off; const int32_t *sel_medium, *sel_ids;
   const int32_t* coef_have; const float* coefs;
   int32_t* ids_out; int64_t ids_cap; int64_t* ids_offsets; int32_t* total_out;
+  QueryWeights qw;   // not a C argument: the pending weights the entry point took (user order / selected-item order of the call)
 };
 int model_render(Model* m, const RenderArgs& a);
 // rsys_render_items: a page per user-less state (windowed retrieval on the prior, reranking) in one device pipeline
 int model_render_items(Model* m, int32_t ng, const int32_t* group_medium, const int64_t* offset, const int32_t* limit, const float* penalties,
                        const int64_t* sel_off, const int32_t* sel_medium, const int32_t* sel_ids, int32_t* ids_out, int64_t ids_cap,
-                       int64_t* ids_offsets, int32_t* total_out);
+                       int64_t* ids_offsets, int32_t* total_out, const float* sel_w = nullptr);
 int render_debug_keep(Model* m, int on);
 int render_debug_get(Model* m, const char* key, void* out, int64_t cap, int64_t* bytes);
 void render_free(Model* m);
 int op_rerank(int32_t n, int32_t partialk, const float* pen, const float* r, const float* gram, const int32_t* ss_bits,
               const int32_t* related_bits, int32_t* picks);
 int op_topk(const float* scores, int64_t ld, int32_t rows, int32_t V, int32_t k, int32_t* ids, float* vals, int32_t* counts);
+// rsys_op_query_weights: the three weighted accumulations alone, on device arrays (one section each; include/rsys_debug.h)
+int op_combine_weighted(const float* src, float* dst, int32_t ng, int32_t V, int32_t last, const float* z, int64_t ldz, const float* lse,
+                        const int32_t* members, const int32_t* ranges, int32_t q0, const float* user_w);
+int op_rank_score_weighted(int32_t ng, const int64_t* cand_off, const int32_t* cand, const float* z, int64_t ldz, const float* lse,
+                           const int32_t* members, const int32_t* ranges, int32_t q0, const float* rm, const int64_t* rm_off,
+                           const float* retrieval_coef, const float* rating_coefs, float rating_mean, int32_t first, const float* user_w,
+                           float* sc);
+int op_selected_sum_weighted(int32_t ng, const int64_t* sel_off, const int32_t* sel_med, const int32_t* sel_ids, int32_t medium,
+                             const float* emb_m, const float* X, int32_t dim, const float* sel_w, float* S);
 // the selection of rsys_op_topk on device scores [rows][ld], stream-ordered, in a caller's device workspace of topk_rows_ws_bytes bytes
 // (1 <= k <= min(V, 8192)); ids / vals / counts are device arrays
 size_t topk_rows_ws_bytes(int rows, int V, int k);

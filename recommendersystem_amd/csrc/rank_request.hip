@@ -79,11 +79,13 @@ __device__ __forceinline__ int find_sorted(const int32_t* sorted, int n, int id)
 }
 
 // sc[c0 + i] = (first ? 0 : sc[c0 + i]) + sum over the group's users of this chunk (members[range.x .. range.y), ascending user index)
-// of (lp_u[i] + r_u[i]), one rounding per operation
-__global__ void __launch_bounds__(RK_THREADS) rank_score_kernel(const RankGroup* grp, const int32_t* cand, const float* z, long long ldz,
-                                                                const float* lse, const int* members, const int2* ranges, int q0,
-                                                                const float* rm, const int64_t* rm_off, float coef, float logc,
-                                                                int have_rc, float c0m, float c1, int first, float* sc) {
+// of (lp_u[i] + r_u[i]), one rounding per operation.  W (rank_score_w_kernel; rsys_query_weights_set): the term is w[u] * (lp_u[i] +
+// r_u[i]), product and sum rounded on their own, a user whose weight is +-0.0 skipped; W == false (rank_score_kernel) never reads `w`.
+template <bool W>
+__device__ __forceinline__ void rank_score_body(const RankGroup* grp, const int32_t* cand, const float* z, long long ldz, const float* lse,
+                                                const int* members, const int2* ranges, int q0, const float* rm, const int64_t* rm_off,
+                                                float coef, float logc, int have_rc, float c0m, float c1, int first, float* sc,
+                                                const float* w) {
   const RankGroup gd = grp[blockIdx.y];
   const int i = blockIdx.x * RK_THREADS + threadIdx.x;
   if (i >= gd.n) return;
@@ -97,9 +99,23 @@ __global__ void __launch_bounds__(RK_THREADS) rank_score_kernel(const RankGroup*
     const float lp = p == 0.f ? -INFINITY : __fadd_rn(d, logc);
     const float x = rm[rm_off[u] + i];
     const float ru = have_rc ? __fadd_rn(c0m, __fmul_rn(c1, x)) : x;
-    s = __fadd_rn(s, __fadd_rn(lp, ru));
+    if constexpr (W) s = weighted_add(s, w[u], __fadd_rn(lp, ru));
+    else s = __fadd_rn(s, __fadd_rn(lp, ru));
   }
   sc[gd.c0 + i] = s;
+}
+__global__ void __launch_bounds__(RK_THREADS) rank_score_kernel(const RankGroup* grp, const int32_t* cand, const float* z, long long ldz,
+                                                                const float* lse, const int* members, const int2* ranges, int q0,
+                                                                const float* rm, const int64_t* rm_off, float coef, float logc,
+                                                                int have_rc, float c0m, float c1, int first, float* sc) {
+  rank_score_body<false>(grp, cand, z, ldz, lse, members, ranges, q0, rm, rm_off, coef, logc, have_rc, c0m, c1, first, sc, nullptr);
+}
+// the weighted form: w[u] per user, indexed as lse is
+__global__ void __launch_bounds__(RK_THREADS) rank_score_w_kernel(const RankGroup* grp, const int32_t* cand, const float* z, long long ldz,
+                                                                  const float* lse, const int* members, const int2* ranges, int q0,
+                                                                  const float* rm, const int64_t* rm_off, float coef, float logc,
+                                                                  int have_rc, float c0m, float c1, int first, const float* w, float* sc) {
+  rank_score_body<true>(grp, cand, z, ldz, lse, members, ranges, q0, rm, rm_off, coef, logc, have_rc, c0m, c1, first, sc, w);
 }
 
 // G_g[i][j] = sum over columns c in ascending order of E[id_i][c] * E[id_j][c] (one fmaf chain) for the 64 x 64 tile (blockIdx.y,
@@ -366,7 +382,7 @@ static int rank_t(Model* m, int medium, int ng, const Groups& gs, const int32_t*
                   const std::vector<int32_t>& ugroup, const float* r_masked, int64_t n_rm, const std::vector<int64_t>& rm_off,
                   const std::vector<int32_t>& ent_g, const std::vector<int32_t>& ent_id, const float* retrieval_coef,
                   const float* rating_coefs, float rating_mean, const float* r_in, const float* E, int dim, int32_t* ids_out, float* r_out,
-                  const RankDev* dev = nullptr) {
+                  const RankDev* dev, const float* user_w) {
   const int Vm = medium == 0 ? m->V0 : m->V1;
   hipStream_t s = m->stream;
   const bool score = r_in == nullptr, rerank = ids_out != nullptr || dev != nullptr;
@@ -379,12 +395,13 @@ static int rank_t(Model* m, int medium, int ng, const Groups& gs, const int32_t*
   const int nchunks = gp.nchunks;
   const int64_t nent = (int64_t)ent_g.size();
   ScoreBufs<T> b(m);
-  float *d_rm, *sc, *G; int *d_members, *picks; int2* d_ranges; int64_t* d_rmoff; RankGroup* d_grp;
+  float *d_rm, *sc, *G, *d_uw; int *d_members, *picks; int2* d_ranges; int64_t* d_rmoff; RankGroup* d_grp;
   int32_t *d_cand, *d_sid, *d_spos, *d_eg, *d_eid, *d_plo, *d_phi, *d_page; int64_t* d_poff; unsigned *bits, *flags;
   RC(carve_into(rank_tables(m)->ws, s, [&](Carve& c) {
     b.take(c, score ? nu : 0);
     d_members = c.take<int>(nu);
     d_ranges = c.take<int2>((size_t)std::max(nchunks, 1) * ng);
+    d_uw = c.take<float>(score && user_w ? nu : 0);
     d_rm = c.take<float>(score ? n_rm : 0);
     d_rmoff = c.take<int64_t>(nu);
     d_grp = c.take<RankGroup>(ng);
@@ -414,6 +431,7 @@ static int rank_t(Model* m, int medium, int ng, const Groups& gs, const int32_t*
     RC(score_upload_queries(b, queries, nu, in_kind, s));
     HIP_CHECK(hipMemcpyAsync(d_members, gp.members.data(), gp.members.size() * 4, hipMemcpyHostToDevice, s));
     HIP_CHECK(hipMemcpyAsync(d_ranges, gp.ranges.data(), gp.ranges.size() * sizeof(int2), hipMemcpyHostToDevice, s));
+    if (user_w) HIP_CHECK(hipMemcpyAsync(d_uw, user_w, (size_t)nu * 4, hipMemcpyHostToDevice, s));
     HIP_CHECK(hipMemcpyAsync(d_rm, r_masked, (size_t)n_rm * 4, in_kind, s));
     HIP_CHECK(hipMemcpyAsync(d_rmoff, rm_off.data(), (size_t)nu * 8, hipMemcpyHostToDevice, s));
   } else {
@@ -450,8 +468,14 @@ static int rank_t(Model* m, int medium, int ng, const Groups& gs, const int32_t*
       const int q0 = ch * RETRIEVE_CHUNK, nc = (int)std::min<int64_t>(RETRIEVE_CHUNK, nu - q0);
       RC(retrieve_chunk_scores<T>(m, b.qt + (size_t)q0 * b.D, nc, q0, Fm, Vm, b.z, b.ldz, b.part, b.lse));
       tic(m, "rank_score");
-      rank_score_kernel<<<dim3(RK_MAXN / RK_THREADS, ng), RK_THREADS, 0, s>>>(d_grp, d_cand, b.z, b.ldz, b.lse, d_members, d_ranges + (size_t)ch * ng,
-                                                                             q0, d_rm, d_rmoff, coef, logc, have_rc, c0m, c1, ch == 0, sc);
+      const dim3 grid(RK_MAXN / RK_THREADS, ng);
+      const int2* rg = d_ranges + (size_t)ch * ng;
+      if (user_w)
+        rank_score_w_kernel<<<grid, RK_THREADS, 0, s>>>(d_grp, d_cand, b.z, b.ldz, b.lse, d_members, rg, q0, d_rm, d_rmoff, coef, logc, have_rc,
+                                                        c0m, c1, ch == 0, d_uw, sc);
+      else
+        rank_score_kernel<<<grid, RK_THREADS, 0, s>>>(d_grp, d_cand, b.z, b.ldz, b.lse, d_members, rg, q0, d_rm, d_rmoff, coef, logc, have_rc,
+                                                      c0m, c1, ch == 0, sc);
       RK_LAUNCH_CHECK();
       toc(m);
     }
@@ -497,7 +521,7 @@ static int rank_request_body(Model* m, int medium, int32_t ng, const int64_t* ca
                              const float* penalties, const float* queries, int64_t nu, const int32_t* group, const float* r_masked, int64_t n_rm,
                              const int64_t* hist_off, const int32_t* hist_medium, const int32_t* hist_ids, const int32_t* hist_status,
                              const float* retrieval_coef, const float* rating_coefs, float rating_mean, const float* r_in, int32_t* ids_out,
-                             float* r_out, const RankDev* dev) {
+                             float* r_out, const RankDev* dev, const float* user_w) {
   ARG_CHECK(medium == 0 || medium == 1, "rank_request: medium must be 0 or 1");
   ARG_CHECK(ids_out || r_out || dev, "rank_request: no output (ids_out and r_out are both NULL)");
   ARG_CHECK(nu >= 1 && nu <= RK_MAXQ, "rank_request: 1 <= n_users <= 4096");
@@ -551,27 +575,27 @@ static int rank_request_body(Model* m, int medium, int32_t ng, const int64_t* ca
   }
   HIP_CHECK(hipSetDevice(m->device));
   return m->bf16_mode ? rank_t<bf16>(m, medium, ng, gs, cand_ids, queries, nu, ugroup, r_masked, n_rm, rm_off, ent_g, ent_id, retrieval_coef,
-                                     rating_coefs, rating_mean, r_in, E, (int)dim, ids_out, r_out, dev)
+                                     rating_coefs, rating_mean, r_in, E, (int)dim, ids_out, r_out, dev, user_w)
                       : rank_t<float>(m, medium, ng, gs, cand_ids, queries, nu, ugroup, r_masked, n_rm, rm_off, ent_g, ent_id, retrieval_coef,
-                                      rating_coefs, rating_mean, r_in, E, (int)dim, ids_out, r_out, dev);
+                                      rating_coefs, rating_mean, r_in, E, (int)dim, ids_out, r_out, dev, user_w);
 }
 
 int model_rank_request(Model* m, int medium, int32_t ng, const int64_t* cand_off, const int32_t* cand_ids, const int32_t* partialk,
                        const float* penalties, const float* queries, int64_t nu, const int32_t* group, const float* r_masked, int64_t n_rm,
                        const int64_t* hist_off, const int32_t* hist_medium, const int32_t* hist_ids, const int32_t* hist_status,
                        const float* retrieval_coef, const float* rating_coefs, float rating_mean, const float* r_in, int32_t* ids_out,
-                       float* r_out) {
+                       float* r_out, const float* user_w) {
   return rank_request_body(m, medium, ng, cand_off, cand_ids, partialk, penalties, queries, nu, group, r_masked, n_rm, hist_off, hist_medium,
-                           hist_ids, hist_status, retrieval_coef, rating_coefs, rating_mean, r_in, ids_out, r_out, nullptr);
+                           hist_ids, hist_status, retrieval_coef, rating_coefs, rating_mean, r_in, ids_out, r_out, nullptr, user_w);
 }
 
 int model_rank_request_dev(Model* m, int medium, int32_t ng, const int64_t* cand_off, const RankDev* dev, const int32_t* partialk,
                            const float* penalties, int64_t nu, const int32_t* group, int64_t n_rm, const int64_t* hist_off,
                            const int32_t* hist_medium, const int32_t* hist_ids, const int32_t* hist_status, const float* retrieval_coef,
-                           const float* rating_coefs, float rating_mean) {
+                           const float* rating_coefs, float rating_mean, const float* user_w) {
   ARG_CHECK(dev && dev->d_cand && dev->page_lo && dev->page_hi && dev->page_off && dev->page_out, "rank_request: null device buffers");
   return rank_request_body(m, medium, ng, cand_off, nullptr, partialk, penalties, nullptr, nu, group, nullptr, n_rm, hist_off, hist_medium,
-                           hist_ids, hist_status, retrieval_coef, rating_coefs, rating_mean, nullptr, nullptr, nullptr, dev);
+                           hist_ids, hist_status, retrieval_coef, rating_coefs, rating_mean, nullptr, nullptr, nullptr, dev, user_w);
 }
 
 int model_rank_items_dev(Model* m, int medium, int32_t ng, const int64_t* cand_off, const RankDev* dev, const int32_t* partialk,
@@ -581,7 +605,7 @@ int model_rank_items_dev(Model* m, int medium, int32_t ng, const int64_t* cand_o
   // render.jl:354 ranks a state without users as zeros; one user without a list per group stands in for its (absent) users
   const std::vector<float> zeros((size_t)std::max<int64_t>(cand_off[ng], 1), 0.f);
   return rank_request_body(m, medium, ng, cand_off, nullptr, partialk, penalties, nullptr, ng, nullptr, nullptr, 0, nullptr, nullptr, nullptr,
-                           nullptr, nullptr, nullptr, 0.f, zeros.data(), nullptr, nullptr, dev);
+                           nullptr, nullptr, nullptr, 0.f, zeros.data(), nullptr, nullptr, dev, nullptr);
 }
 
 int model_rank_gram(Model* m, int medium, int32_t ng, const int64_t* cand_off, const int32_t* cand_ids, float* out, int64_t n_out) {
@@ -628,6 +652,34 @@ int op_rerank(int32_t n, int32_t partialk, const float* pen, const float* r, con
   const hipError_t e = hipDeviceSynchronize();
   hipFree(d_grp);
   if (rc == RSYS_OK && e != hipSuccess) { set_error(std::string("rsys_op_rerank: ") + hipGetErrorString(e)); rc = RSYS_ERR_HIP; }
+  return rc;
+}
+
+// rsys_op_query_weights, the ranking section: one launch of rank_score_w_kernel over device arrays; the groups' descriptors are built
+// from the host offsets as rsys_rank_request builds them
+int op_rank_score_weighted(int32_t ng, const int64_t* cand_off, const int32_t* cand, const float* z, int64_t ldz, const float* lse,
+                           const int32_t* members, const int32_t* ranges, int32_t q0, const float* rm, const int64_t* rm_off,
+                           const float* retrieval_coef, const float* rating_coefs, float rating_mean, int32_t first, const float* user_w,
+                           float* sc) {
+  ARG_CHECK(cand && z && lse && members && ranges && rm && rm_off && user_w && sc, "rsys_op_query_weights: null buffer (rank score)");
+  ARG_CHECK(ng >= 1 && ng <= 65535 && q0 >= 0, "rsys_op_query_weights: 1 <= n_groups <= 65535, q0 >= 0");
+  Groups gs;
+  RC(make_groups("rsys_op_query_weights", ng, cand_off, nullptr, nullptr, nullptr, 0, gs, true));
+  RankGroup* d_grp = nullptr;
+  HIP_CHECK(hipMalloc(&d_grp, (size_t)ng * sizeof(RankGroup)));
+  int rc = RSYS_OK;
+  if (hipMemcpy(d_grp, gs.g.data(), (size_t)ng * sizeof(RankGroup), hipMemcpyHostToDevice) != hipSuccess) rc = RSYS_ERR_HIP;
+  if (rc == RSYS_OK) {
+    const float coef = retrieval_coef ? *retrieval_coef : 1.f;
+    const int have_rc = rating_coefs != nullptr;
+    const float c0m = have_rc ? rating_coefs[0] * rating_mean : 0.f, c1 = have_rc ? rating_coefs[1] : 0.f;
+    rank_score_w_kernel<<<dim3(RK_MAXN / RK_THREADS, (unsigned)ng), RK_THREADS>>>(d_grp, cand, z, ldz, lse, members, (const int2*)ranges, q0, rm,
+                                                                                 rm_off, coef, logf(coef), have_rc, c0m, c1, first, user_w, sc);
+    if (hipGetLastError() != hipSuccess) { set_error("rsys_op_query_weights: launch failed (rank score)"); rc = RSYS_ERR_HIP; }
+  }
+  const hipError_t e = hipDeviceSynchronize();
+  hipFree(d_grp);
+  if (rc == RSYS_OK && e != hipSuccess) { set_error(std::string("rsys_op_query_weights: ") + hipGetErrorString(e)); rc = RSYS_ERR_HIP; }
   return rc;
 }
 

@@ -292,6 +292,22 @@ void sub_csr(const std::vector<int>& rows, const int64_t* off, const int32_t* a,
   if (out.a.empty()) { out.a.push_back(0); out.b.push_back(0); out.c.push_back(0); }   // (non-null pointers for empty lists)
   if (c == nullptr) out.c.assign(1, 0);
 }
+// the query weights (rsys_query_weights_set) of a subset of a request, in subset order: per user, and per selected item of a subset of
+// groups.  w == nullptr: unweighted, `out` stays empty and the slice is null.
+const float* sub_weights(const std::vector<int>& users, const float* w, std::vector<float>& out) {
+  if (!w) return nullptr;
+  out.clear();
+  out.reserve(users.size() + 1);   // (a non-null pointer for an empty subset too)
+  for (int u : users) out.push_back(w[u]);
+  return out.data();
+}
+const float* sub_sel_weights(const std::vector<int>& groups, const int64_t* off, const float* w, std::vector<float>& out) {
+  if (!w || !off) return nullptr;
+  out.clear();
+  out.reserve(1);
+  for (int g : groups) out.insert(out.end(), w + off[g], w + off[g + 1]);
+  return out.data();
+}
 
 // a group with a page: its slice [c0, c0 + n) of the candidate list, the page = picks [sidx - 1, eidx) of it
 struct Active { int g, c0, n, sidx, eidx; };
@@ -619,10 +635,12 @@ struct Render : RenderArgs {
       if (hist_off) sub_csr(us, hist_off, hist_medium, hist_ids, hist_status, h);
       if (sel_off) sub_csr(gs, sel_off, sel_medium, sel_ids, nullptr, sl);
       std::vector<int32_t> counts(ngm);
+      std::vector<float> wu, ws;
+      const QueryWeights qm{sub_weights(us, qw.user, wu), sub_sel_weights(gs, sel_off, qw.sel, ws)};
       RetrieveDev rd; rd.d_queries = Qs;
       RC(model_retrieve_request_dev(m, mm, &rd, nq, lg.data(), ngm, hist_off ? h.off.data() : nullptr, hist_off ? h.a.data() : nullptr,
                                     hist_off ? h.b.data() : nullptr, hist_off ? h.c.data() : nullptr, sel_off ? sl.off.data() : nullptr,
-                                    sel_off ? sl.a.data() : nullptr, sel_off ? sl.b.data() : nullptr, k, counts.data()));
+                                    sel_off ? sl.a.data() : nullptr, sel_off ? sl.b.data() : nullptr, k, counts.data(), qm));
       std::vector<Win> wins;
       for (int j = 0; j < ngm; ++j) {
         const int g = gs[j];
@@ -921,9 +939,11 @@ struct Render : RenderArgs {
                  keep ? kp.data() : nullptr};
       const int have = coef_have ? coef_have[mm] : 0;
       const float* cf = coefs ? coefs + 4 * mm : nullptr;
+      std::vector<float> wu;
       RC(model_rank_request_dev(m, mm, na, coff.data(), &rd, pk.data(), pen.data(), nq, lg.data(), rm_n[mm], hist_off ? h.off.data() : nullptr,
                                 hist_off ? h.a.data() : nullptr, hist_off ? h.b.data() : nullptr, hist_off ? h.c.data() : nullptr,
-                                (have & 1) ? cf : nullptr, (have & 2) ? cf + 1 : nullptr, (have & 2) ? cf[3] : 0.f));
+                                (have & 1) ? cf : nullptr, (have & 2) ? cf + 1 : nullptr, (have & 2) ? cf[3] : 0.f,
+                                sub_weights(us, qw.user, wu)));
       for (int a = 0; a < na; ++a) pages[act[a].g].assign(page.begin() + poff[a], page.begin() + poff[a] + (phi[a] - plo[a]));
       if (keep) {
         std::vector<float> hrm((size_t)rm_n[mm]);
@@ -988,7 +1008,7 @@ int model_render(Model* m, const RenderArgs& a) {
 // one candidate list, the reranking of rsys_rank_request on zeros.  Outputs are written once both media have succeeded.
 int model_render_items(Model* m, int32_t ng, const int32_t* group_medium, const int64_t* offset, const int32_t* limit, const float* penalties,
                        const int64_t* sel_off, const int32_t* sel_medium, const int32_t* sel_ids, int32_t* ids_out, int64_t ids_cap,
-                       int64_t* ids_offsets, int32_t* total_out) {
+                       int64_t* ids_offsets, int32_t* total_out, const float* sel_w) {
   ARG_CHECK(ng >= 1 && ng <= RN_MAXQ, "render_items: 1 <= n_groups <= 4096");
   ARG_CHECK(group_medium && offset && limit && penalties && ids_out && ids_offsets && total_out, "render_items: null argument");
   RC(check_ragged("render_items", LIST_SELECTED, sel_off, ng, {sel_medium, sel_ids}));
@@ -1031,9 +1051,11 @@ int model_render_items(Model* m, int32_t ng, const int32_t* group_medium, const 
     SubCsr sl;
     if (sel_off) sub_csr(gs, sel_off, sel_medium, sel_ids, nullptr, sl);
     const RetrieveWin win{wstart.data(), wlen.data(), totals.data()};
+    std::vector<float> ws;
+    const QueryWeights qm{nullptr, sub_sel_weights(gs, sel_off, sel_w, ws)};
     RetrieveDev rd;
     RC(model_retrieve_window(m, mm, nullptr, 0, nullptr, ngm, nullptr, nullptr, nullptr, nullptr, sel_off ? sl.off.data() : nullptr,
-                             sel_off ? sl.a.data() : nullptr, sel_off ? sl.b.data() : nullptr, &win, &rd, nullptr, nullptr, counts.data()));
+                             sel_off ? sl.a.data() : nullptr, sel_off ? sl.b.data() : nullptr, &win, &rd, nullptr, nullptr, counts.data(), qm));
     std::vector<Win> wins;
     std::vector<int> act;
     std::vector<int64_t> coff(1, 0), poff;

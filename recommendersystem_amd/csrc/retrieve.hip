@@ -105,10 +105,13 @@ __global__ void scatter_nan_kernel(float* sc, const long long* pos, long long n)
 // score_g[i] = src_g[i] + sum over the group's queries of this chunk (members[range.x .. range.y), ascending query index) of
 // (z_q[i] - lse_q).  LAST: write the key instead of the score and count the keys' first digit (bits 31..24) into hist[g][256].
 // ranges == nullptr: no queries (the op hook: keys of given scores).
-template <bool LAST>
-__global__ void __launch_bounds__(RT_THREADS) combine_kernel(const float* src, long long lds, float* dst, long long ldd, const float* z,
-                                                             long long ldz, const float* lse, const int* members, const int2* ranges,
-                                                             int q0, int V, unsigned* hist) {
+// W (combine_w_kernel; rsys_query_weights_set): the term of query q is w[q] * (z_q[i] - lse_q), the product and
+// the sum rounded on their own; a query whose weight is +-0.0 is skipped, so the running sum keeps its bits whatever the term holds.
+// W == false (combine_kernel) never reads `w`.
+template <bool LAST, bool W>
+__device__ __forceinline__ void combine_body(const float* src, long long lds, float* dst, long long ldd, const float* z, long long ldz,
+                                             const float* lse, const int* members, const int2* ranges, int q0, int V, unsigned* hist,
+                                             const float* w) {
   const int g = blockIdx.y;
   const int2 r = ranges ? ranges[g] : make_int2(0, 0);
   if (!LAST && r.x == r.y) return;   // (in place, nothing to add)
@@ -124,7 +127,11 @@ __global__ void __launch_bounds__(RT_THREADS) combine_kernel(const float* src, l
     if (valid)
       for (int t = r.x; t < r.y; ++t) {
         const int q = members[t];
-        s += z[(long long)(q - q0) * ldz + i] - lse[q];
+        if constexpr (W) {
+          s = weighted_add(s, w[q], __fsub_rn(z[(long long)(q - q0) * ldz + i], lse[q]));
+        } else {
+          s += z[(long long)(q - q0) * ldz + i] - lse[q];
+        }
       }
     if (!LAST) {
       if (valid) dg[i] = s;
@@ -138,6 +145,19 @@ __global__ void __launch_bounds__(RT_THREADS) combine_kernel(const float* src, l
     __syncthreads();
     if (h[threadIdx.x]) atomicAdd(&hist[g * 256 + threadIdx.x], h[threadIdx.x]);
   }
+}
+template <bool LAST>
+__global__ void __launch_bounds__(RT_THREADS) combine_kernel(const float* src, long long lds, float* dst, long long ldd, const float* z,
+                                                             long long ldz, const float* lse, const int* members, const int2* ranges,
+                                                             int q0, int V, unsigned* hist) {
+  combine_body<LAST, false>(src, lds, dst, ldd, z, ldz, lse, members, ranges, q0, V, hist, nullptr);
+}
+// the weighted form: w[q] per query, indexed as lse is
+template <bool LAST>
+__global__ void __launch_bounds__(RT_THREADS) combine_w_kernel(const float* src, long long lds, float* dst, long long ldd, const float* z,
+                                                               long long ldz, const float* lse, const int* members, const int2* ranges,
+                                                               int q0, int V, unsigned* hist, const float* w) {
+  combine_body<LAST, true>(src, lds, dst, ldd, z, ldz, lse, members, ranges, q0, V, hist, w);
 }
 
 // digit pass `pass` (digit = bits [24 - 8 pass, 32 - 8 pass)) of every group still open: pick the bin that holds the need-th largest
@@ -682,7 +702,8 @@ int csc_nonzero_pattern(const char* who, const char* rows, int64_t n_rows, int64
 template <typename T>
 static int retrieve_t(Model* m, int medium, const float* queries, int64_t nq, const int32_t* group, int ng, const float* prior,
                       const int64_t* excl_off, const int32_t* excl_ids, const RetrieveInit* init, int k, int32_t* ids_out, float* scores_out,
-                      int32_t* counts_out, RetrieveDev* dev = nullptr, const RetrieveWin* win = nullptr) {
+                      int32_t* counts_out, RetrieveDev* dev = nullptr, const RetrieveWin* win = nullptr, const float* user_w = nullptr) {
+  // user_w (host, [nq], or null): a weight per query (rsys_query_weights_set); null runs the unweighted kernels
   // win: the window [start, start + len) of each group's ordering instead of its top k (rsys_retrieve_window): rows of RT_WIN ranks, a
   // group may have no queries (its score row is what `init` wrote), nq may be 0 (nothing is scored, the item table is not read)
   const int Vm = medium == 0 ? m->V0 : m->V1;
@@ -707,7 +728,7 @@ static int retrieve_t(Model* m, int medium, const float* queries, int64_t nq, co
   const size_t zrows = win ? (size_t)std::min<int64_t>(nq, RT_CHUNK) : (size_t)RT_CHUNK;
   const size_t slab = std::max<size_t>(zrows * (size_t)b.ldz * 4, (size_t)ng * (size_t)k * 8);
   const size_t nbound = win ? 2 : 1;   // (a window selects two rank bounds per group and counts int4 per workgroup)
-  float *sc, *d_vals; SelBufs sb; int *d_ids, *d_counts, *d_members, *d_totals, *d_wlen; int2* d_ranges; long long *d_xpos, *d_wstart;
+  float *sc, *d_vals, *d_uw; SelBufs sb; int *d_ids, *d_counts, *d_members, *d_totals, *d_wlen; int2* d_ranges; long long *d_xpos, *d_wstart;
   RC(carve_into(m->rws, s, [&](Carve& c) {
     b.take(c, nq, slab);
     sc = c.take<float>((size_t)ng * Vm);
@@ -719,6 +740,7 @@ static int retrieve_t(Model* m, int medium, const float* queries, int64_t nq, co
     d_counts = c.take<int>(ng);
     d_members = c.take<int>(nq);
     d_ranges = c.take<int2>(gp.ranges.size());
+    d_uw = c.take<float>(user_w ? (size_t)nq : 0);
     d_xpos = c.take<long long>(xpos.size());
     d_totals = c.take<int>(win ? ng : 0);
     d_wstart = c.take<long long>(win ? ng : 0);
@@ -732,6 +754,7 @@ static int retrieve_t(Model* m, int medium, const float* queries, int64_t nq, co
     RC(score_upload_queries(b, dev ? dev->d_queries : queries, nq, dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
     HIP_CHECK(hipMemcpyAsync(d_members, gp.members.data(), gp.members.size() * 4, hipMemcpyHostToDevice, s));
     HIP_CHECK(hipMemcpyAsync(d_ranges, gp.ranges.data(), gp.ranges.size() * sizeof(int2), hipMemcpyHostToDevice, s));
+    if (user_w) HIP_CHECK(hipMemcpyAsync(d_uw, user_w, (size_t)nq * 4, hipMemcpyHostToDevice, s));
   }
   if (win) {
     static_assert(sizeof(long long) == sizeof(int64_t), "window starts are copied as they are");
@@ -756,10 +779,15 @@ static int retrieve_t(Model* m, int medium, const float* queries, int64_t nq, co
     RC(retrieve_chunk_scores<T>(m, b.qt + (size_t)q0 * b.D, nc, q0, Fm, Vm, b.z, b.ldz, b.part, b.lse));
     tic(m, "retrieve_combine");
     const dim3 grid(nb, ng);
-    if (ch + 1 < gp.nchunks)
-      combine_kernel<false><<<grid, RT_THREADS, 0, s>>>(sc, Vm, sc, Vm, b.z, b.ldz, b.lse, d_members, d_ranges + (size_t)ch * ng, q0, Vm, sb.hist);
-    else
-      combine_kernel<true><<<grid, RT_THREADS, 0, s>>>(sc, Vm, sc, Vm, b.z, b.ldz, b.lse, d_members, d_ranges + (size_t)ch * ng, q0, Vm, sb.hist);
+    const bool last = ch + 1 == gp.nchunks;
+    const int2* rg = d_ranges + (size_t)ch * ng;
+    if (user_w) {
+      if (!last) combine_w_kernel<false><<<grid, RT_THREADS, 0, s>>>(sc, Vm, sc, Vm, b.z, b.ldz, b.lse, d_members, rg, q0, Vm, sb.hist, d_uw);
+      else combine_w_kernel<true><<<grid, RT_THREADS, 0, s>>>(sc, Vm, sc, Vm, b.z, b.ldz, b.lse, d_members, rg, q0, Vm, sb.hist, d_uw);
+    } else {
+      if (!last) combine_kernel<false><<<grid, RT_THREADS, 0, s>>>(sc, Vm, sc, Vm, b.z, b.ldz, b.lse, d_members, rg, q0, Vm, sb.hist);
+      else combine_kernel<true><<<grid, RT_THREADS, 0, s>>>(sc, Vm, sc, Vm, b.z, b.ldz, b.lse, d_members, rg, q0, Vm, sb.hist);
+    }
     RT_LAUNCH_CHECK();
     toc(m);
   }
@@ -797,9 +825,10 @@ int model_retrieve_topk(Model* m, int medium, const float* queries, int64_t nq, 
 // stream after the workspace is in place): the prior and the NaN masks of rsys_retrieve_request.  The caller has checked the arguments
 // model_retrieve_topk checks.
 int model_retrieve_run(Model* m, int medium, const float* queries, int64_t nq, const int32_t* group, int32_t ng, const RetrieveInit& init,
-                       int32_t k, int32_t* ids_out, float* scores_out, int32_t* counts_out, RetrieveDev* dev, const RetrieveWin* win) {
-  return m->bf16_mode ? retrieve_t<bf16>(m, medium, queries, nq, group, ng, nullptr, nullptr, nullptr, &init, k, ids_out, scores_out, counts_out, dev, win)
-                      : retrieve_t<float>(m, medium, queries, nq, group, ng, nullptr, nullptr, nullptr, &init, k, ids_out, scores_out, counts_out, dev, win);
+                       int32_t k, int32_t* ids_out, float* scores_out, int32_t* counts_out, RetrieveDev* dev, const RetrieveWin* win,
+                       const float* user_w) {
+  return m->bf16_mode ? retrieve_t<bf16>(m, medium, queries, nq, group, ng, nullptr, nullptr, nullptr, &init, k, ids_out, scores_out, counts_out, dev, win, user_w)
+                      : retrieve_t<float>(m, medium, queries, nq, group, ng, nullptr, nullptr, nullptr, &init, k, ids_out, scores_out, counts_out, dev, win, user_w);
 }
 
 static void topk_rows_layout(Carve& c, int rows, int V, int k, unsigned** keys, SelBufs* sb) {
@@ -840,6 +869,28 @@ int op_topk(const float* scores, int64_t ld, int32_t rows, int32_t V, int32_t k,
   const hipError_t e = hipDeviceSynchronize();
   hipFree(buf);
   if (rc == RSYS_OK && e != hipSuccess) { set_error(std::string("rsys_op_topk: ") + hipGetErrorString(e)); rc = RSYS_ERR_HIP; }
+  return rc;
+}
+
+// rsys_op_query_weights, the combine section: one launch of combine_w_kernel over device arrays; the first-digit histogram of `last`
+// goes to a scratch of its own
+int op_combine_weighted(const float* src, float* dst, int32_t ng, int32_t V, int32_t last, const float* z, int64_t ldz, const float* lse,
+                        const int32_t* members, const int32_t* ranges, int32_t q0, const float* user_w) {
+  ARG_CHECK(src && dst && z && lse && members && ranges && user_w, "rsys_op_query_weights: null buffer (combine)");
+  ARG_CHECK(ng >= 1 && ng <= 65535 && V >= 1 && ldz >= V && q0 >= 0, "rsys_op_query_weights: 1 <= n_groups <= 65535, V >= 1, ldz >= V, q0 >= 0");
+  unsigned* hist = nullptr;
+  HIP_CHECK(hipMalloc(&hist, (size_t)ng * 256 * 4));
+  int rc = RSYS_OK;
+  if (hipMemset(hist, 0, (size_t)ng * 256 * 4) != hipSuccess) rc = RSYS_ERR_HIP;
+  if (rc == RSYS_OK) {
+    const dim3 grid((unsigned)((V + RT_ITEMS - 1) / RT_ITEMS), (unsigned)ng);
+    if (last) combine_w_kernel<true><<<grid, RT_THREADS>>>(src, V, dst, V, z, ldz, lse, members, (const int2*)ranges, q0, V, hist, user_w);
+    else combine_w_kernel<false><<<grid, RT_THREADS>>>(src, V, dst, V, z, ldz, lse, members, (const int2*)ranges, q0, V, hist, user_w);
+    if (hipGetLastError() != hipSuccess) { set_error("rsys_op_query_weights: launch failed (combine)"); rc = RSYS_ERR_HIP; }
+  }
+  const hipError_t e = hipDeviceSynchronize();
+  hipFree(hist);
+  if (rc == RSYS_OK && e != hipSuccess) { set_error(std::string("rsys_op_query_weights: ") + hipGetErrorString(e)); rc = RSYS_ERR_HIP; }
   return rc;
 }
 

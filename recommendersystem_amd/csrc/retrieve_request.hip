@@ -83,6 +83,18 @@ __global__ void __launch_bounds__(RR_THREADS) selected_sum_kernel(const int64_t*
     s += sel_med[a] == m ? emb_m[(long long)sel_ids[a] * dim + r] : X[a * dim + r];
   S[(long long)g * dim + r] = s;
 }
+// the weighted form (rsys_query_weights_set): s_g = sum of w[a] * x_a, w indexed by selected-item position as sel_ids is; the product
+// and the sum rounded on their own, a weight of +-0.0 skips the item
+__global__ void __launch_bounds__(RR_THREADS) selected_sum_w_kernel(const int64_t* sel_off, const int32_t* sel_med, const int32_t* sel_ids,
+                                                                    int m, const float* emb_m, const float* X, int dim, const float* w,
+                                                                    float* S) {
+  const int g = blockIdx.y, r = blockIdx.x * RR_THREADS + threadIdx.x;
+  if (r >= dim) return;
+  float s = 0.f;
+  for (long long a = sel_off[g]; a < sel_off[g + 1]; ++a)
+    s = weighted_add(s, w[a], sel_med[a] == m ? emb_m[(long long)sel_ids[a] * dim + r] : X[a * dim + r]);
+  S[(long long)g * dim + r] = s;
+}
 
 // sc[g][i] = s_g . E[i] for the GT groups g0 + [0, GT) of this workgroup's tile and RR_ROWS items per wave step.  blockIdx.x = group
 // tile, blockIdx.y = item block: the tiles of one item block run side by side and read its rows of E from HBM once.  Lane l sums columns
@@ -300,7 +312,7 @@ int model_retrieve_released_set(Model* m, int medium, const uint8_t* mask) {
 static int retrieve_request_body(Model* m, int medium, const float* queries, RetrieveDev* dev, int64_t nq, const int32_t* group, int32_t ng,
                                  const int64_t* hist_off, const int32_t* hist_medium, const int32_t* hist_ids, const int32_t* hist_status,
                                  const int64_t* sel_off, const int32_t* sel_medium, const int32_t* sel_ids, int32_t k, int32_t* ids_out,
-                                 float* scores_out, int32_t* counts_out, const RetrieveWin* win = nullptr) {
+                                 float* scores_out, int32_t* counts_out, const RetrieveWin* win, QueryWeights qw) {
   const char* who = win ? "retrieve_window" : "retrieve_request";
   auto msg = [who](const char* text) { return std::string(who) + ": " + text; };
   // the limits of rsys_retrieve_topk (model_retrieve_topk)
@@ -397,13 +409,14 @@ static int retrieve_request_body(Model* m, int medium, const float* queries, Ret
 
   HIP_CHECK(hipSetDevice(m->device));
   hipStream_t s = m->stream;
-  float *S, *X; int64_t* d_soff; int32_t *d_smed, *d_sids, *d_eq, *d_eid, *d_ef, *d_qg; unsigned* planes;
+  float *S, *X, *d_sw; int64_t* d_soff; int32_t *d_smed, *d_sids, *d_eq, *d_eid, *d_ef, *d_qg; unsigned* planes;
   RC(carve_into(R->ws, s, [&](Carve& c) {
     S = c.take<float>(nsel ? (size_t)ng * dim : 0);
     X = c.take<float>(nsel ? (size_t)nsel * dim : 0);
     d_soff = c.take<int64_t>((size_t)ng + 1);
     d_smed = c.take<int32_t>(nsel);
     d_sids = c.take<int32_t>(nsel);
+    d_sw = c.take<float>(qw.sel ? nsel : 0);
     d_eq = c.take<int32_t>(nent);
     d_eid = c.take<int32_t>(nent);
     d_ef = c.take<int32_t>(nent);
@@ -417,6 +430,7 @@ static int retrieve_request_body(Model* m, int medium, const float* queries, Ret
   if (nsel) {
     HIP_CHECK(hipMemcpyAsync(d_smed, sel_medium, (size_t)nsel * 4, hipMemcpyHostToDevice, s));
     HIP_CHECK(hipMemcpyAsync(d_sids, sel_ids, (size_t)nsel * 4, hipMemcpyHostToDevice, s));
+    if (qw.sel) HIP_CHECK(hipMemcpyAsync(d_sw, qw.sel, (size_t)nsel * 4, hipMemcpyHostToDevice, s));
   }
   if (nent) {
     HIP_CHECK(hipMemcpyAsync(d_eq, ent_q.data(), (size_t)nent * 4, hipMemcpyHostToDevice, s));
@@ -434,8 +448,9 @@ static int retrieve_request_body(Model* m, int medium, const float* queries, Ret
       cross_kernel<<<dim3((unsigned)((dim + 63) / 64), (unsigned)nsel), 1024, 0, st>>>(d_smed, d_sids, medium, T0.emb, T1.emb, T0.cross,
                                                                                       T1.cross, dim, X);
       RR_LAUNCH_CHECK();
-      selected_sum_kernel<<<dim3((unsigned)((dim + RR_THREADS - 1) / RR_THREADS), ng), RR_THREADS, 0, st>>>(d_soff, d_smed, d_sids, medium,
-                                                                                                        T.emb, X, dim, S);
+      const dim3 sgrid((unsigned)((dim + RR_THREADS - 1) / RR_THREADS), ng);
+      if (qw.sel) selected_sum_w_kernel<<<sgrid, RR_THREADS, 0, st>>>(d_soff, d_smed, d_sids, medium, T.emb, X, dim, d_sw, S);
+      else selected_sum_kernel<<<sgrid, RR_THREADS, 0, st>>>(d_soff, d_smed, d_sids, medium, T.emb, X, dim, S);
       RR_LAUNCH_CHECK();
       const int gt = ng == 1 ? 1 : (ng <= 4 ? 4 : RR_GT);
       const int rows_per_block = 64;
@@ -472,32 +487,44 @@ static int retrieve_request_body(Model* m, int medium, const float* queries, Ret
     toc(m);
     return RSYS_OK;
   };
-  return model_retrieve_run(m, medium, queries, nq, group, ng, init, k, ids_out, scores_out, counts_out, dev, win);
+  return model_retrieve_run(m, medium, queries, nq, group, ng, init, k, ids_out, scores_out, counts_out, dev, win, qw.user);
 }
 
 int model_retrieve_request(Model* m, int medium, const float* queries, int64_t nq, const int32_t* group, int32_t ng, const int64_t* hist_off,
                            const int32_t* hist_medium, const int32_t* hist_ids, const int32_t* hist_status, const int64_t* sel_off,
                            const int32_t* sel_medium, const int32_t* sel_ids, int32_t k, int32_t* ids_out, float* scores_out,
-                           int32_t* counts_out) {
+                           int32_t* counts_out, QueryWeights qw) {
   return retrieve_request_body(m, medium, queries, nullptr, nq, group, ng, hist_off, hist_medium, hist_ids, hist_status, sel_off, sel_medium,
-                               sel_ids, k, ids_out, scores_out, counts_out);
+                               sel_ids, k, ids_out, scores_out, counts_out, nullptr, qw);
 }
 
 int model_retrieve_request_dev(Model* m, int medium, RetrieveDev* dev, int64_t nq, const int32_t* group, int32_t ng, const int64_t* hist_off,
                                const int32_t* hist_medium, const int32_t* hist_ids, const int32_t* hist_status, const int64_t* sel_off,
-                               const int32_t* sel_medium, const int32_t* sel_ids, int32_t k, int32_t* counts_out) {
+                               const int32_t* sel_medium, const int32_t* sel_ids, int32_t k, int32_t* counts_out, QueryWeights qw) {
   ARG_CHECK(dev != nullptr, "retrieve_request: null device buffers");
   return retrieve_request_body(m, medium, nullptr, dev, nq, group, ng, hist_off, hist_medium, hist_ids, hist_status, sel_off, sel_medium,
-                               sel_ids, k, nullptr, nullptr, counts_out);
+                               sel_ids, k, nullptr, nullptr, counts_out, nullptr, qw);
 }
 
 int model_retrieve_window(Model* m, int medium, const float* queries, int64_t nq, const int32_t* group, int32_t ng, const int64_t* hist_off,
                           const int32_t* hist_medium, const int32_t* hist_ids, const int32_t* hist_status, const int64_t* sel_off,
                           const int32_t* sel_medium, const int32_t* sel_ids, const RetrieveWin* win, RetrieveDev* dev, int32_t* ids_out,
-                          float* scores_out, int32_t* counts_out) {
+                          float* scores_out, int32_t* counts_out, QueryWeights qw) {
   ARG_CHECK(win != nullptr, "retrieve_window: null window");
   return retrieve_request_body(m, medium, queries, dev, nq, group, ng, hist_off, hist_medium, hist_ids, hist_status, sel_off, sel_medium,
-                               sel_ids, 0, ids_out, scores_out, counts_out, win);
+                               sel_ids, 0, ids_out, scores_out, counts_out, win, qw);
+}
+
+// rsys_op_query_weights, the selected-sum section: one launch of selected_sum_w_kernel over device arrays
+int op_selected_sum_weighted(int32_t ng, const int64_t* sel_off, const int32_t* sel_med, const int32_t* sel_ids, int32_t medium,
+                             const float* emb_m, const float* X, int32_t dim, const float* sel_w, float* S) {
+  ARG_CHECK(sel_off && sel_med && sel_ids && emb_m && X && sel_w && S, "rsys_op_query_weights: null buffer (selected sum)");
+  ARG_CHECK(ng >= 1 && ng <= 65535 && dim >= 1 && (medium == 0 || medium == 1), "rsys_op_query_weights: 1 <= n_groups <= 65535, dim >= 1, medium 0 or 1");
+  selected_sum_w_kernel<<<dim3((unsigned)((dim + RR_THREADS - 1) / RR_THREADS), (unsigned)ng), RR_THREADS>>>(sel_off, sel_med, sel_ids, medium,
+                                                                                                            emb_m, X, dim, sel_w, S);
+  RR_LAUNCH_CHECK();
+  HIP_CHECK(hipDeviceSynchronize());
+  return RSYS_OK;
 }
 
 }  // namespace rsys

@@ -750,12 +750,36 @@ class RecommenderModel:
             mask[ids] = 1
         check(lib().rsys_retrieve_released_set(self._h, int(medium), np.ascontiguousarray(mask).ctypes.data))
 
-    def retrieve_request(self, queries, medium, k, group=None, histories=None, selected=None):
+    def set_query_weights(self, user_weights=None, selected_weights=None):
+        """rsys_query_weights_set: a finite float32 weight per user and per selected item (flat, in the order of the request's users and
+        of its selected items) for the NEXT request call on this model, which consumes them.  None = unweighted for that
+        kind; both None clears what is held.  The request methods call this themselves from `user_weights=` / `selected_weights=`, and
+        not at all when both are None -- the unweighted path."""
+        uw = None if user_weights is None else query_weights_array(user_weights)
+        sw = None if selected_weights is None else query_weights_array(selected_weights)
+        uw = None if uw is None or uw.size == 0 else uw
+        sw = None if sw is None or sw.size == 0 else sw
+        ptr = lambda a: None if a is None else a.ctypes.data
+        check(lib().rsys_query_weights_set(self._h, ptr(uw), 0 if uw is None else uw.size, ptr(sw), 0 if sw is None else sw.size))
+
+    def query_weights_pending(self):
+        """rsys_query_weights_pending: (n_users, n_sel) of the weights held for the next request, 0 = none of that kind"""
+        out = np.zeros(2, np.int64)
+        check(lib().rsys_query_weights_pending(self._h, out.ctypes.data))
+        return int(out[0]), int(out[1])
+
+    def _weights_before(self, user_weights, selected_weights):
+        if user_weights is not None or selected_weights is not None:
+            self.set_query_weights(user_weights, selected_weights)
+
+    def retrieve_request(self, queries, medium, k, group=None, histories=None, selected=None, user_weights=None, selected_weights=None):
         """A whole render.jl `retrieval(state)` per group on the device (rsys_retrieve_request): the scores of `retrieve_topk` plus the
         item-similarity prior of the group's selected items, with the relation masks, item 0, the selected items and unreleased items
         masked, from the tables loaded by set_retrieval_relations / set_item_similarity / set_released.  `histories`: one list per query
         of (medium, id, status) list items in list order (None: no lists); `selected`: one list per group of (medium, id) items in
-        the request's order (None: none).  Returns (ids (n_groups, k) int32, scores (n_groups, k) float32, counts (n_groups,) int32)."""
+        the request's order (None: none).  `user_weights` (one per query) / `selected_weights` (flat, one per selected item): the query
+        weights of `set_query_weights`, set immediately before the request (None: unweighted, the setter is not called).
+        Returns (ids (n_groups, k) int32, scores (n_groups, k) float32, counts (n_groups,) int32)."""
         q = np.ascontiguousarray(queries, np.float32)
         if q.ndim == 1:
             q = q[None, :]
@@ -780,17 +804,19 @@ class RecommenderModel:
         ptr = lambda a: None if a is None else a.ctypes.data
         hp = (None,) * 4 if h is None else tuple(ptr(a) for a in h)
         sp = (None,) * 3 if sl is None else tuple(ptr(a) for a in sl)
+        self._weights_before(user_weights, selected_weights)
         check(lib().rsys_retrieve_request(self._h, int(medium), q.ctypes.data, n, ptr(gp), ng, *hp, *sp, int(k), ids.ctypes.data,
                                           scores.ctypes.data, counts.ctypes.data))
         return ids, scores, counts
 
     WINDOW_ROWS = 1024                # ranks per window row of rsys_retrieve_window
 
-    def retrieve_window(self, queries, medium, starts, lengths, group=None, n_groups=None, histories=None, selected=None):
+    def retrieve_window(self, queries, medium, starts, lengths, group=None, n_groups=None, histories=None, selected=None,
+                        user_weights=None, selected_weights=None):
         """`retrieve_request` for any rank range (rsys_retrieve_window): per group the items of ranks [starts[g], starts[g] + lengths[g])
         of its ordering (0-based, 1 <= length <= 1024) and its exact number of admissible items.  A group may have no queries (a state
         without users: scored by the prior of its selected items alone, no relation masks); `queries` may be None or empty, `group` then
-        too.  `n_groups` defaults to len(starts).  Returns (ids (n_groups, 1024) int32, scores (n_groups, 1024) float32, counts, totals
+        too.  `n_groups` defaults to len(starts).  `user_weights` / `selected_weights` as `retrieve_request`.  Returns (ids (n_groups, 1024) int32, scores (n_groups, 1024) float32, counts, totals
         (n_groups,) int32 each); slots past counts[g] = clamp(totals[g] - starts[g], 0, lengths[g]) hold -1 / -inf."""
         q = None if queries is None else np.ascontiguousarray(queries, np.float32)
         if q is not None and q.ndim == 1:
@@ -825,14 +851,16 @@ class RecommenderModel:
         ptr = lambda a: None if a is None else a.ctypes.data
         hp = (None,) * 4 if h is None else tuple(ptr(a) for a in h)
         sp = (None,) * 3 if sl is None else tuple(ptr(a) for a in sl)
+        self._weights_before(user_weights, selected_weights)
         check(lib().rsys_retrieve_window(self._h, int(medium), ptr(q), n, ptr(gp), ng, *hp, *sp, ptr(ws), ptr(wl), ids.ctypes.data,
                                          scores.ctypes.data, counts.ctypes.data, totals.ctypes.data))
         return ids, scores, counts[:ng], totals[:ng]
 
-    def render_items(self, group_medium, offsets, limits, penalties, selected=None):
+    def render_items(self, group_medium, offsets, limits, penalties, selected=None, selected_weights=None):
         """rsys_render_items: a page per state WITHOUT users (compute.jl `/add_item`) in one device call -- per group (medium, offset,
         limit, penalties (4)) and its selected items [(medium, id), ...]: the windowed retrieval on the item-similarity prior, then the
-        reranking on zero ranking scores.  Returns (one int32 page array per group, exact totals (n_groups,) int32)."""
+        reranking on zero ranking scores.  `selected_weights` as `retrieve_request`.  Returns (one int32 page array per group, exact
+        totals (n_groups,) int32)."""
         gm = np.ascontiguousarray(group_medium, np.int32).reshape(-1)
         ng = gm.size
         off = np.ascontiguousarray(offsets, np.int64).reshape(-1)
@@ -851,6 +879,7 @@ class RecommenderModel:
         total = np.empty(max(ng, 1), np.int32)
         ptr = lambda a: None if a is None else a.ctypes.data
         sp = (None,) * 3 if sel is None else tuple(ptr(a) for a in sel)
+        self._weights_before(None, selected_weights)
         check(lib().rsys_render_items(self._h, ng, ptr(gm), ptr(off), ptr(lim), ptr(pen), *sp, ptr(ids), cap, ptr(ioff), ptr(total)))
         return [ids[ioff[g]:ioff[g + 1]].copy() for g in range(ng)], total[:ng].copy()
 
@@ -867,14 +896,14 @@ class RecommenderModel:
         check(lib().rsys_rank_related_set(self._h, int(medium), int(shape[1]), indptr.ctypes.data, indices.ctypes.data, data.ctypes.data))
 
     def rank_request(self, queries, medium, candidates, group=None, r_masked=None, partialk=None, penalties=None, histories=None,
-                     retrieval_coef=None, rating_coefs=None, rating_mean=0.0, scores=None, rerank=True):
+                     retrieval_coef=None, rating_coefs=None, rating_mean=0.0, scores=None, rerank=True, user_weights=None):
         """render.jl `ranking` + `reranking!` per group on the device (rsys_rank_request).  `candidates`: one array of distinct medium-local
         ids per group (1..1024 each); `queries` (n_users, D) the users' "{m}.retrieval" embeddings; `group` (n_users,) group ids or None
         (one group per user); `r_masked`: one array per user of its group's candidates' rating-head values; `partialk`: rounds per group;
         `penalties`: per group (decay, mmr_penalty, same_series_penalty, related_penalty); `histories`: per user (medium, id, status) list
         items or None; `retrieval_coef`, `rating_coefs` (c0, c1), `rating_mean`: the registry's (None: p = softmax, r = r_masked);
         `scores`: one given ranking-score array per group instead of computing them (queries and r_masked are then not needed);
-        rerank=False: ranking only.  Returns (ids per group in pick order, min(partialk, n) each, or None; ranking scores per group)."""
+        rerank=False: ranking only; `user_weights` (one per user) as `retrieve_request`.  Returns (ids per group in pick order, min(partialk, n) each, or None; ranking scores per group)."""
         ng = len(candidates)
         cand = [np.asarray(c, np.int64).reshape(-1) for c in candidates]
         off = np.zeros(ng + 1, np.int64)
@@ -918,6 +947,7 @@ class RecommenderModel:
         rout = np.empty(max(N, 1), np.float32)
         ptr = lambda a: None if a is None else a.ctypes.data
         hp = (None,) * 4 if h is None else tuple(ptr(a) for a in h)
+        self._weights_before(user_weights, None)
         check(lib().rsys_rank_request(self._h, int(medium), ng, off.ctypes.data, ids_in.ctypes.data, ptr(pk), ptr(pen), ptr(q), nu, ptr(gp),
                                       ptr(rm), 0 if rm is None else rm.size, *hp, ptr(rc), ptr(kc), float(rating_mean), ptr(rin), ptr(ids),
                                       rout.ctypes.data))
@@ -949,31 +979,35 @@ class RecommenderModel:
         return b, keep
 
     def render_request(self, group_medium, offsets, limits, penalties, group, retrieval_rows, retrieval_token, ranking_prefix, prefix_stride,
-                       user_desc, user_ts, adapter_slots=None, histories=None, selected=None, coef_have=None, coefs=None):
+                       user_desc, user_ts, adapter_slots=None, histories=None, selected=None, coef_have=None, coefs=None,
+                       user_weights=None, selected_weights=None):
         """rsys_render_request: per group (medium, offset, limit, penalties (4)); per user its group, its row of `retrieval_rows` (the
         dict `serve.build_batch(..., "retrieval")` builds, n_users rows) with its query token `retrieval_token`, its row of
         `ranking_prefix` (the same ten arrays, `prefix_stride` columns per row), `user_desc` (nh, userid, gender, source) and `user_ts`;
         `adapter_slots` the bank slots of (0.retrieval, 0.ranking, 1.retrieval, 1.ranking) or None (base model); `histories` per user
-        and `selected` per group as `retrieve_request` takes them; `coef_have` (2,) / `coefs` (2, 4) the registry's coefficients.
+        and `selected` per group as `retrieve_request` takes them; `coef_have` (2,) / `coefs` (2, 4) the registry's coefficients;
+        `user_weights` / `selected_weights` as `retrieve_request` (they reach the retrieval and the ranking stage).
         Returns (one int32 page array per group, totals (n_groups,) int32)."""
         return self._render_call(False, group_medium, offsets, limits, penalties, group, retrieval_rows, retrieval_token, ranking_prefix,
-                                 prefix_stride, user_desc, user_ts, adapter_slots, histories, selected, coef_have, coefs)
+                                 prefix_stride, user_desc, user_ts, adapter_slots, histories, selected, coef_have, coefs, user_weights,
+                                 selected_weights)
 
     def render_request_full(self, group_medium, offsets, limits, penalties, group, retrieval_rows, retrieval_token, user_desc, user_ts,
-                            adapter_slots=None, histories=None, selected=None, coef_have=None, coefs=None):
+                            adapter_slots=None, histories=None, selected=None, coef_have=None, coefs=None, user_weights=None,
+                            selected_weights=None):
         """rsys_render_request_full: `render_request` with the ranking forward on full-length histories through the per-user K/V cache
         (DESIGN.md 4w).  The same arguments without `ranking_prefix` / `prefix_stride`; `user_desc` = (n_hist, userid, gender, source)
         with n_hist in [0, S - 1] = the history columns of the user's retrieval row (`serve.render_pack(..., full_history=True)`).  The
         library reserves max_rows cache slots when the model's reserve is smaller than a wave's users."""
         out = self._render_call(True, group_medium, offsets, limits, penalties, group, retrieval_rows, retrieval_token, None, 0, user_desc,
-                                user_ts, adapter_slots, histories, selected, coef_have, coefs)
+                                user_ts, adapter_slots, histories, selected, coef_have, coefs, user_weights, selected_weights)
         with_hist = int((np.asarray(user_desc, np.int32).reshape(-1, 4)[:, 0] >= 1).sum())
         if getattr(self, "rank_cache_slots", 0) < min(self.max_rows, with_hist):       # (the library reserved max_rows slots)
             self.rank_cache_slots = self.max_rows
         return out
 
     def _render_call(self, full, group_medium, offsets, limits, penalties, group, retrieval_rows, retrieval_token, ranking_prefix, prefix_stride,
-                     user_desc, user_ts, adapter_slots, histories, selected, coef_have, coefs):
+                     user_desc, user_ts, adapter_slots, histories, selected, coef_have, coefs, user_weights=None, selected_weights=None):
         gm = np.ascontiguousarray(group_medium, np.int32).reshape(-1)
         ng = gm.size
         off = np.ascontiguousarray(offsets, np.int64).reshape(-1)
@@ -1018,6 +1052,7 @@ class RecommenderModel:
         sp = (None,) * 3 if sel is None else tuple(ptr(a) for a in sel)
         prefix = () if full else (C.byref(pb), int(prefix_stride))
         fn = lib().rsys_render_request_full if full else lib().rsys_render_request
+        self._weights_before(user_weights, selected_weights)
         check(fn(self._h, ng, ptr(gm), ptr(off), ptr(lim), ptr(pen), nu, ptr(gp), C.byref(rb), ptr(tok), *prefix, ptr(desc), ptr(ts), ptr(sl),
                  *hp, *sp, ptr(ch), ptr(cf), ptr(ids), cap, ptr(ioff), ptr(total)))
         return [ids[ioff[g]:ioff[g + 1]].copy() for g in range(ng)], total[:ng].copy()
@@ -1160,6 +1195,14 @@ class RecommenderModel:
             name, ms, cnt, fl = line.split()
             rep[name] = {"ms": float(ms), "count": int(cnt), "flops": float(fl)}
         return rep
+
+
+def query_weights_array(weights):
+    """flat contiguous float32 copy of query weights; a NaN or infinite weight raises (the library refuses it too)"""
+    w = np.ascontiguousarray(np.asarray(weights, np.float32).reshape(-1))
+    if not np.isfinite(w).all():
+        raise ValueError("query weights must be finite")
+    return w
 
 
 def exclusion_csr(exclude, n_groups):

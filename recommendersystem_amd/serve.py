@@ -668,10 +668,29 @@ def load_retrieval_tables(model, relations, item_similarity, released=None):
             model.set_released(m, released[m])
 
 
-def request_arrays(states, medium):
+def state_weights(states):
+    """The query weights of request states: `state["users"][i]["weight"]` per user in user order and
+    `state["items"][i]["weight"]` per selected item in item order, float32, an absent key = 1.0.  Returns (user_weights,
+    selected_weights); a kind for which no user / no item of any state carries the key is None -- unweighted, the library's setter is
+    then not called for it.  A NaN or infinite weight raises."""
+    users = [u for st in states for u in st["users"]]
+    items = [a for st in states for a in st.get("items", ())]      # (`ranking` takes states without selected items)
+    out = []
+    for entries in (users, items):
+        if not any("weight" in e for e in entries):
+            out.append(None)
+            continue
+        w = np.asarray([float(e.get("weight", 1.0)) for e in entries], np.float32)
+        if not np.isfinite(w).all():
+            raise ValueError("query weights must be finite")
+        out.append(w)
+    return out[0], out[1]
+
+
+def request_arrays(states, medium, weights=False):
     """The arguments of `RecommenderModel.retrieve_request` for render.jl request states of one medium, one group per state: the
     users' "{medium}.retrieval" embeddings (n, D), their group ids, each user's list items as (medium, matchedid, status) in list
-    order, and each state's selected items as (medium, matchedid) in order."""
+    order, and each state's selected items as (medium, matchedid) in order.  weights=True: then the two arrays of `state_weights`."""
     key = f"{medium}.retrieval"
     q, group, hist, sel = [], [], [], []
     for g, st in enumerate(states):
@@ -682,14 +701,15 @@ def request_arrays(states, medium):
             group.append(g)
             hist.append([(int(x["medium"]), int(x["matchedid"]), int(x["status"])) for x in u["user"]["items"]])
         sel.append([(int(a["medium"]), int(a["matchedid"])) for a in st["items"]])
-    return np.stack(q), np.asarray(group, np.int32), hist, sel
+    return (np.stack(q), np.asarray(group, np.int32), hist, sel) + (state_weights(states) if weights else ())
 
 
 def retrieval(model, states, k=1024, coefs=None):
     """render.jl `retrieval(state)` on the device for a list of request states (`medium`, `items`, `users[*].embeds`,
     `users[*].user.items`), one group per state, on the tables of `load_retrieval_tables`: prior of the selected items, summed log
     soft-max of the users, relation / watched / selected / item-0 / unreleased masks, best first.  `coefs`: the registry's retrieval
-    coefficient (adds n_users * log(coef), the order does not change).  Returns one (ids, scores) pair per state, ids 0-based
+    coefficient (adds n_users * log(coef), the order does not change; with user weights, sum of w_u * log(coef)).  Users and selected
+    items may carry a "weight" (`state_weights`).  Returns one (ids, scores) pair per state, ids 0-based
     medium-local, at most min(k, V_m, 8192) of them."""
     out = [None] * len(states)
     by_medium = {}
@@ -699,11 +719,12 @@ def retrieval(model, states, k=1024, coefs=None):
             raise ValueError("retrieval: medium must be 0 or 1")
         by_medium.setdefault(m, []).append(j)
     for m, idx in sorted(by_medium.items()):
-        q, group, hist, sel = request_arrays([states[j] for j in idx], m)
+        q, group, hist, sel, uw, sw = request_arrays([states[j] for j in idx], m, weights=True)
         Vm = model.config["vocab_sizes"][f"{m}_matchedid"]
         kk = min(int(k), Vm, 8192)
-        ids, scores, counts = model.retrieve_request(q, m, kk, group=group, histories=hist, selected=sel)
-        members = np.bincount(group, minlength=len(idx))
+        ids, scores, counts = model.retrieve_request(q, m, kk, group=group, histories=hist, selected=sel, user_weights=uw, selected_weights=sw)
+        members = np.bincount(group, minlength=len(idx)) if uw is None else \
+            np.bincount(group, weights=uw.astype(np.float64), minlength=len(idx))
         for g, j in enumerate(idx):
             n = int(counts[g])
             s = scores[g, :n]
@@ -713,7 +734,7 @@ def retrieval(model, states, k=1024, coefs=None):
     return out
 
 
-def _window_arrays(states, medium):
+def _window_arrays(states, medium, weights=False):
     """`request_arrays` for states that may have no users: (queries or None, group ids, list items per user, selected items per state)"""
     key = f"{medium}.retrieval"
     q, group, hist, sel = [], [], [], []
@@ -723,7 +744,7 @@ def _window_arrays(states, medium):
             group.append(g)
             hist.append([(int(x["medium"]), int(x["matchedid"]), int(x["status"])) for x in u["user"]["items"]])
         sel.append([(int(a["medium"]), int(a["matchedid"])) for a in st["items"]])
-    return (np.stack(q) if q else None), np.asarray(group, np.int32), hist, sel
+    return ((np.stack(q) if q else None), np.asarray(group, np.int32), hist, sel) + (state_weights(states) if weights else ())
 
 
 def retrieval_window(model, states, windows):
@@ -741,9 +762,10 @@ def retrieval_window(model, states, windows):
             raise ValueError("retrieval_window: start >= 0 and 1 <= length <= 1024")
     out = [None] * len(states)
     for m, idx in _by_medium(states):
-        q, group, hist, sel = _window_arrays([states[j] for j in idx], m)
+        q, group, hist, sel, uw, sw = _window_arrays([states[j] for j in idx], m, weights=True)
         ids, scores, counts, totals = model.retrieve_window(q, m, [int(wins[j][0]) for j in idx], [int(wins[j][1]) for j in idx], group=group,
-                                                            n_groups=len(idx), histories=hist, selected=sel)
+                                                            n_groups=len(idx), histories=hist, selected=sel, user_weights=uw,
+                                                            selected_weights=sw)
         for g, j in enumerate(idx):
             n = int(counts[g])
             out[j] = (ids[g, :n].copy(), scores[g, :n].copy(), int(totals[g]))
@@ -776,11 +798,12 @@ def _registry_coefs(registry, m):
     return rc, kc, mean
 
 
-def rank_arrays(states, idxs, with_embeds=True):
+def rank_arrays(states, idxs, with_embeds=True, weights=False):
     """The per-user arguments of `RecommenderModel.rank_request` for render.jl states of one medium (one group per state, `idxs[g]` its
     candidates): queries (n, D) or None, group ids, r_masked (one row per user: its "{m}.ranking" values), list items (medium,
     matchedid, status) in list order -- every entry, duplicates and all statuses included -- and per group the penalties
-    (decay, mmr_penalty, same_series_penalty, related_penalty) of `state["penalties"]`."""
+    (decay, mmr_penalty, same_series_penalty, related_penalty) of `state["penalties"]`.  weights=True: then the two arrays of
+    `state_weights` (the ranking reads the users' only)."""
     q, group, rm, hist, pen = [], [], [], [], []
     for g, st in enumerate(states):
         m = int(st["medium"])
@@ -797,8 +820,8 @@ def rank_arrays(states, idxs, with_embeds=True):
                 if r.size != len(idxs[g]):
                     raise ValueError(f"ranking: a user has {r.size} \"{m}.ranking\" values for {len(idxs[g])} candidates")
                 rm.append(r)
-    return (np.stack(q) if with_embeds else None), np.asarray(group, np.int32), (rm if with_embeds else None), hist, \
-        np.asarray(pen, np.float32).reshape(-1, 4)
+    return ((np.stack(q) if with_embeds else None), np.asarray(group, np.int32), (rm if with_embeds else None), hist,
+            np.asarray(pen, np.float32).reshape(-1, 4)) + (state_weights(states) if weights else ())
 
 
 def _by_medium(states):
@@ -820,9 +843,10 @@ def ranking(model, states, idxs, registry=None):
     out = [None] * len(states)
     for m, js in _by_medium(states):
         sub, cand = [states[j] for j in js], [np.asarray(idxs[j]) for j in js]
-        q, group, rm, hist, _ = rank_arrays(sub, cand)
+        q, group, rm, hist, _, uw, _ = rank_arrays(sub, cand, weights=True)
         rc, kc, mean = _registry_coefs(registry, m)
-        _, r = model.rank_request(q, m, cand, group=group, r_masked=rm, retrieval_coef=rc, rating_coefs=kc, rating_mean=mean, rerank=False)
+        _, r = model.rank_request(q, m, cand, group=group, r_masked=rm, retrieval_coef=rc, rating_coefs=kc, rating_mean=mean, rerank=False,
+                                  user_weights=uw)
         for g, j in enumerate(js):
             out[j] = r[g]
     return out
@@ -890,7 +914,7 @@ def render_items(model, states, pagination):
         sel.append([(int(a["medium"]), int(a["matchedid"])) for a in st["items"]])
     if not states:
         return []
-    pages, totals = model.render_items(gm, off, lim, np.asarray(pen, np.float32).reshape(-1, 4), sel)
+    pages, totals = model.render_items(gm, off, lim, np.asarray(pen, np.float32).reshape(-1, 4), sel, selected_weights=state_weights(states)[1])
     return [(pages[g], int(totals[g])) for g in range(len(states))]
 
 
@@ -975,10 +999,10 @@ def _render_states(model, states, pags, registry, max_ranking_items, full_histor
                     vals += predict(model, [req], "ranking", m, max_user_len, S - max_user_len, trim=trim)[0][f"{m}.ranking"]
                 u.setdefault("embeds", {})[f"{m}.ranking"] = np.asarray(vals, np.float32)
         cand = [w[1] for w in items]
-        q, group, rm, hist, pen = rank_arrays(sub, cand)
+        q, group, rm, hist, pen, uw, _ = rank_arrays(sub, cand, weights=True)
         rc, kc, mean = _registry_coefs(registry, m)
         ids, _ = model.rank_request(q, m, cand, group=group, r_masked=rm, partialk=[w[3] for w in items], penalties=pen, histories=hist,
-                                    retrieval_coef=rc, rating_coefs=kc, rating_mean=mean)
+                                    retrieval_coef=rc, rating_coefs=kc, rating_mean=mean, user_weights=uw)
         for g, w in enumerate(items):
             out[w[0]] = (ids[g][w[2] - 1:w[3]], w[4])
     return out
@@ -1031,7 +1055,8 @@ def render_pack(states, pagination, S, num_items_0, registry=None, adapter_slots
     "ranking")`: the newest S // 2 - 1 tokens) with the descriptor (nh, userid, gender, source) and timestamp the device completes them
     from, its list items, and per state the selected items, penalties, pagination and medium.  `full_history=True`: the arguments of
     `RecommenderModel.render_request_full` instead -- no prefix arrays, and the descriptor's first entry is n_hist = len(hr), the history
-    columns of the retrieval row (the device cuts the cache's store rows from them)."""
+    columns of the retrieval row (the device cuts the cache's store rows from them).  When a user or a selected item carries a
+    "weight", the dict also holds `user_weights` / `selected_weights` (`state_weights`); without any it has no such keys."""
     pags = [pagination] * len(states) if isinstance(pagination, dict) else list(pagination)
     if len(pags) != len(states):
         raise ValueError(f"render_users: {len(pags)} paginations for {len(states)} states")
@@ -1085,6 +1110,9 @@ def render_pack(states, pagination, S, num_items_0, registry=None, adapter_slots
                adapter_slots=slots, histories=hist, selected=sel, coef_have=have, coefs=coefs)
     if full_history:
         del out["ranking_prefix"], out["prefix_stride"]
+    uw, sw = state_weights(states)
+    if uw is not None or sw is not None:
+        out.update(user_weights=uw, selected_weights=sw)
     return out
 
 

@@ -24,6 +24,13 @@ with 1000 events.  Forwards of (i) are counted at the wrapper (inference_select,
 by the library and compared with serve.render_full_forwards.  "bytes up" of (ii) is (iii)'s accounting minus the prefix arrays.
 
     python tools/bench_render.py --full-history --out profiles/render_full_bench.json
+
+--weights: serve.render_users alone on the same set-up and cases, two arms in alternating blocks -- the states as they
+are (no "weight" key: rsys_query_weights_set is never called, the unweighted kernels run) and the same states with a non-trivial weight
+on every user and, in case (c), on two selected items of the state's medium per state (the weighted kernels).  One JSON line per case.  On a tree without
+query weights only the unweighted arm runs, so the same command measures the commit before for an A/B across builds.
+
+    python tools/bench_render.py --weights --out profiles/query_weights_bench.json
 """
 import argparse
 import json
@@ -93,6 +100,7 @@ def main():
     ap.add_argument("--reps", type=int, default=15)
     ap.add_argument("--out", default=None)
     ap.add_argument("--full-history", action="store_true", help="time the staged full-history path, render_users(full_history=True) and render_users()")
+    ap.add_argument("--weights", action="store_true", help="time render_users without and with query weights (no staged path)")
     a = ap.parse_args()
     import recommendersystem_amd as ra
     from recommendersystem_amd import serve, workload
@@ -159,6 +167,9 @@ def main():
     if a.full_history:
         results = full_history_cases(a, model, V, registry, pag, rng)
         cases = {}
+    if a.weights:
+        results = weights_cases(a, model, V, registry, pag, cases, rng)
+        cases = {}
     for name, states in cases.items():
         n_users = sum(len(st["users"]) for st in states)
         model.inference_select, model.retrieve_request, model.rank_request = count_select, count_ret, count_rank
@@ -195,6 +206,41 @@ def main():
     if a.out:
         with open(a.out, "w") as f:
             json.dump(results, f, indent=1)
+
+
+def weights_cases(a, model, V, registry, pag, cases, rng):
+    """render_users on the states as they are against the same states with a weight on every user (and on the selected items that
+    case (c) gets here: the other cases keep none, as their states have none)"""
+    import copy
+    from recommendersystem_amd import serve
+    have = hasattr(serve, "state_weights")
+    results = []
+    for name, states in cases.items():
+        if name == "c_8_states":
+            for st in states:
+                st["items"] = [dict(medium=int(st["medium"]), matchedid=int(rng.integers(1, V[int(st["medium"])]))) for _ in range(2)]
+        weighted = copy.deepcopy(states)
+        pool = [0.5, 2.25, -1.0, 3e-3, 1.5]
+        for i, e in enumerate([u for st in weighted for u in st["users"]] + [x for st in weighted for x in st["items"]]):
+            e["weight"] = pool[i % len(pool)]
+        arms = {"unweighted": states}
+        if have:
+            arms["weighted"] = weighted
+        t = {k: [] for k in arms}
+        got = {k: serve.render_users(model, v, pag, registry) for k, v in arms.items()}
+        blocks = 5
+        for b in range(blocks):
+            for k, v in arms.items():
+                t[k] += timed(lambda: serve.render_users(model, v, pag, registry), a.warmup if b == 0 else 1, max(a.reps // blocks, 1))
+        res = dict(case=name, shape=a.shape, S=a.seq, states=len(states), users=sum(len(st["users"]) for st in states),
+                   selected=sum(len(st["items"]) for st in states), totals=[int(x) for _, x in got["unweighted"]],
+                   **{k: stats(v) for k, v in t.items()})
+        if have:
+            res["pages_differ"] = bool(any(not np.array_equal(x[0], y[0]) for x, y in zip(got["unweighted"], got["weighted"])))
+            res["weighted_over_unweighted"] = round(float(np.median(t["weighted"]) / np.median(t["unweighted"])), 4)
+        results.append(res)
+        print(json.dumps(res), flush=True)
+    return results
 
 
 def full_history_cases(a, model, V, registry, pag, rng):
