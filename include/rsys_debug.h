@@ -202,10 +202,14 @@ int32_t rsys_render_debug_keep(rsys_model* m, int32_t on);
 int32_t rsys_render_debug_get(rsys_model* m, const char* key, void* out, int64_t cap, int64_t* bytes);
 /* the last rsys_sim_forward_backward / rsys_sim_ndcg call of an item-similarity handle (host arrays): "ranks" int32 [n_q][n] (1-based
  * order of each slot), "scores" f32 [n_q][n] (x), "dldx" f32 [n_q][n] (d batch loss / dx), "dropout_mask" uint8 [rows][F] (1 = kept, the
- * mask of every gathered row: rows = 2 n_q n in training, [source copies | targets], slot-major; all ones without dropout) */
+ * mask of every gathered row: rows = 2 n_q n in training, [source copies | targets], slot-major; all ones without dropout), "splits"
+ * int32 [1] (the K-split count the last call's dW product ran with, as routed: the requested count rounded by the GEMM route; 0 when the
+ * call ran no backward) */
 int32_t rsys_sim_debug_get(void* h, const char* name, void* out, int64_t n);
 /* the last rsys_search_forward_backward / rsys_search_topk call of a search handle (host arrays, f32): "lse" [B] (the per-row logsumexp of
- * the logits), "dP" [B][D] (d loss / d (x Wenc) in fp32, before the bf16 mode rounds it for dWenc; training calls only) */
+ * the logits), "dP" [B][D] (d loss / d (x Wenc) in fp32, before the bf16 mode rounds it for dWenc; training calls only), "splits" [2] (the
+ * column splits the row statistics of the last call ran with, and the K-split count its dP product ran with as routed, 0 when the call
+ * ran no backward) */
 int32_t rsys_search_debug_get(void* h, const char* name, float* out, int64_t n);
 /* embedding-gradient scatter of the backward (nn.Embedding backward, model.py:21) on caller-provided device buffers:
  * gE[id'] += sum over tokens n of gx0[n*ldx .. +D) with id' = m_matchedid[n] (-1 -> row V); matchedid = the raw ids the

@@ -158,14 +158,15 @@ int enc_features_from_device(EncoderCore* h, const float* rows, int64_t V, int64
 }
 
 template <typename T>
-int enc_ordered_gemm(EncoderCore* h, GemmParams p, bool a_km, bool b_km) {
+int enc_ordered_gemm(EncoderCore* h, GemmParams p, bool a_km, bool b_km, int* splits_out) {
   ENC_RC(h->slab.reserve(256 * 4, h->stream));
   p.slab = (float*)h->slab.p; p.slab_floats = (long long)(h->slab.bytes / 4);
   ENC_RC(h->slab.reserve((size_t)std::max<long long>(256, gemm_slab_need<T>(p, false, false, a_km, b_km)) * 4, h->stream));
   p.slab = (float*)h->slab.p; p.slab_floats = (long long)(h->slab.bytes / 4);
+  if (splits_out) *splits_out = gemm_route<T>(p, false, false, a_km, b_km, cu_count()).splitk;
   return launch_gemm<T>(p, false, false, a_km, b_km, h->stream);
 }
-template int enc_ordered_gemm<bf16>(EncoderCore*, GemmParams, bool, bool);
-template int enc_ordered_gemm<float>(EncoderCore*, GemmParams, bool, bool);
+template int enc_ordered_gemm<bf16>(EncoderCore*, GemmParams, bool, bool, int*);
+template int enc_ordered_gemm<float>(EncoderCore*, GemmParams, bool, bool, int*);
 
 }  // namespace rsys

@@ -71,8 +71,8 @@ int enc_features_from_device(EncoderCore* h, const float* rows, int64_t V, int64
 // A product whose sum must have a fixed order (EPI_ATOMIC into fp32 C): with a slab in its parameters launch_gemm stays off the
 // split-K forms that add partial tiles with float atomics (gemm8p's mixed-layout form, gemm4k), and every K split stores its partial
 // tile into the slab, summed in split order afterwards.  The slab is present when the need is asked, as it is at the launch, so
-// the size is the routed kernel's.
+// the size is the routed kernel's.  splits_out (may be null): the K splits the launch runs with, from the route launch_gemm reads.
 template <typename T>
-int enc_ordered_gemm(EncoderCore* h, GemmParams p, bool a_km, bool b_km);
+int enc_ordered_gemm(EncoderCore* h, GemmParams p, bool a_km, bool b_km, int* splits_out = nullptr);
 
 }  // namespace rsys

@@ -35,6 +35,15 @@ constexpr int SEARCH_TOPK_MAXK = 8192;     // topk_rows' limit
 
 struct RowStat { float m, s, t; };   // running maximum, sum exp(v - m), sum exp(v - m) v
 
+// The logit of a raw score: one rounded product, the same value in every kernel.  Written as z * sc the compiler contracts it into the
+// subtraction that follows (fma(z, sc, -lse)), which keeps the product's unrounded bits there but not in the maximum lse is built from:
+// lse - logit[y] is then the product's rounding error instead of 0 where one item holds all the mass, and the loss can be negative.
+// (HIP's __fmul_rn is a plain product, so the pragma.)
+__device__ __forceinline__ float search_logit(float z, float sc) {
+#pragma clang fp contract(off)
+  return z * sc;
+}
+
 __device__ __forceinline__ RowStat stat_merge(RowStat a, RowStat b) {
   RowStat r;
   r.m = fmaxf(a.m, b.m);
@@ -58,10 +67,10 @@ __global__ void __launch_bounds__(256) search_stats_kernel(const float* __restri
     float v[4];
     if (c + 3 < c1) {
       const float4 q = *(const float4*)(zr + c);
-      v[0] = q.x * sc; v[1] = q.y * sc; v[2] = q.z * sc; v[3] = q.w * sc;
+      v[0] = search_logit(q.x, sc); v[1] = search_logit(q.y, sc); v[2] = search_logit(q.z, sc); v[3] = search_logit(q.w, sc);
     } else {
 #pragma unroll
-      for (int k = 0; k < 4; ++k) v[k] = c + k < c1 ? zr[c + k] * sc : -INFINITY;
+      for (int k = 0; k < 4; ++k) v[k] = c + k < c1 ? search_logit(zr[c + k], sc) : -INFINITY;
     }
     const float mx = fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3]));
     if (mx > a.m) {
@@ -111,7 +120,7 @@ __global__ void __launch_bounds__(1024) search_finish_kernel(const float4* __res
     const float l = r.m + logf(r.s);
     lse[row] = l;
     if (labels) {
-      const float zy = z[(long long)row * ldz + labels[row]] * sc, w = wn[row];
+      const float zy = search_logit(z[(long long)row * ldz + labels[row]], sc), w = wn[row];
       al += (double)(w * (l - zy));
       ad += (double)(w * (r.t / r.s - zy));
     }
@@ -152,7 +161,7 @@ __global__ void __launch_bounds__(256) search_grad_kernel(const float* __restric
       const float zz[4] = {q.x, q.y, q.z, q.w};
 #pragma unroll
       for (int k = 0; k < 4; ++k)
-        if (c + k < V) v[k] = w * (expf(zz[k] * sc - l) - (c + k == y ? 1.f : 0.f));
+        if (c + k < V) v[k] = w * (expf(search_logit(zz[k], sc) - l) - (c + k == y ? 1.f : 0.f));
     }
     search_store4(gr + c, v);
   }
@@ -176,7 +185,7 @@ __global__ void __launch_bounds__(256) search_logp_kernel(float* __restrict__ z,
   const int row = blockIdx.y, c = blockIdx.x * 256 + threadIdx.x;
   if (c >= V) return;
   float* p = z + (long long)row * ldz + c;
-  *p = *p * expf(*ls) - lse[row];
+  *p = search_logit(*p, expf(*ls)) - lse[row];
 }
 
 }  // namespace
@@ -195,6 +204,7 @@ struct SearchModel : EncoderCore {
   float* exp32 = nullptr;                           // export [V][Q], allocated by the first export
   DevScratch tws;                                   // top-k workspace
   int last_B = 0; bool last_grads = false;
+  int last_nsplit = 0, last_ksplits = 0;            // of the last call: statistics splits; K splits of dP as routed, 0 without a backward
   int g_rows = 0;                                   // rows of Gs an earlier call wrote (the rest is zero)
   std::vector<float> h_wn;                          // host source of a call's upload, alive until its closing wait
   void free_own() override {
@@ -280,6 +290,7 @@ static int search_scores(SearchModel* h, int B, int Bpad, bool with_loss, bool g
   search_finish_kernel<<<1, 1024, 0, s>>>(h->part, nsplit, B, h->z, h->Vpad, with_loss ? h->labels : nullptr, h->wn, h->ls(), h->lse, h->loss,
                                           h->G + h->nw(), grads ? 1 : 0);
   HIP_CHECK(hipGetLastError());
+  h->last_nsplit = nsplit; h->last_ksplits = 0;
   if (nsplit_out) *nsplit_out = nsplit;
   return RSYS_OK;
 }
@@ -305,7 +316,7 @@ static int search_backward(SearchModel* h, int B, int Bpad) {
     const long long tiles = (long long)((Bpad + 127) / 128) * ((h->D + 127) / 128);
     const long long sk = std::min<long long>(64, std::min<long long>(h->Vpad / 2048, std::max<long long>(1, 2048 / tiles)));
     p.splitk = sk >= 8 ? (int)(sk / 8 * 8) : 1;
-    ENC_RC(enc_ordered_gemm<T>(h, p, false, true));
+    ENC_RC(enc_ordered_gemm<T>(h, p, false, true, &h->last_ksplits));
   }
   search_scale_kernel<T><<<grid_for((long long)Bpad * h->D / 4), 256, 0, s>>>(h->dP, bf ? (T*)h->dPt : (T*)nullptr, (long long)Bpad * h->D / 4,
                                                                                 h->ls());
@@ -420,13 +431,18 @@ static int search_debug_get(SearchModel* h, const char* name, float* out, int64_
     HIP_CHECK(hipMemcpy(out, h->lse, (size_t)n * 4, hipMemcpyDeviceToHost));
     return RSYS_OK;
   }
+  if (strcmp(name, "splits") == 0) {
+    ARG_CHECK(n == 2, "rsys_search_debug_get: splits takes 2 floats");
+    out[0] = (float)h->last_nsplit; out[1] = (float)h->last_ksplits;
+    return RSYS_OK;
+  }
   if (strcmp(name, "dP") == 0) {
     ARG_CHECK(h->last_grads, "rsys_search_debug_get: the last call ran no backward");
     ARG_CHECK(n == (long long)h->last_B * h->D, "rsys_search_debug_get: dP takes B * D floats of the last call");
     HIP_CHECK(hipMemcpy(out, h->dP, (size_t)n * 4, hipMemcpyDeviceToHost));
     return RSYS_OK;
   }
-  set_error(std::string("rsys_search_debug_get: unknown name '") + name + "' (lse, dP)");
+  set_error(std::string("rsys_search_debug_get: unknown name '") + name + "' (lse, dP, splits)");
   return RSYS_ERR_ARG;
 }
 

@@ -341,6 +341,7 @@ struct SimModel : EncoderCore {
   DevScratch pws;                                   // catalogue-rank workspace (similarity_metrics.hip)
   int last_nq = 0, last_n = 0, last_drop = 0; long long last_rows = 0;
   uint64_t last_seed = 0, last_step = 0;
+  int last_ksplits = 0;                             // K splits of the last call's dW product as routed, 0: it ran none
   std::vector<int> h_rowid; std::vector<float> h_wscale;   // host sources of a call's uploads, alive until its closing wait
   void free_own() override {
     hws.release(); pws.release();
@@ -403,7 +404,7 @@ static int sim_weight_grad(SimModel* h, long long Rpad) {
   p.C = h->G; p.ldc = h->F; p.c_f32 = 1;
   p.M = h->E; p.N = h->F; p.K = (int)Rpad; p.epi = EPI_ATOMIC; p.alpha = 1.f;
   p.splitk = (int)std::max<long long>(1, std::min<long long>(64, Rpad / 4096));
-  return enc_ordered_gemm<T>(h, p, true, true);
+  return enc_ordered_gemm<T>(h, p, true, true, &h->last_ksplits);
 }
 
 static int sim_check_lists(SimModel* h, int nq, int n, const int32_t* src, const int32_t* tgt, const float* rel, const float* w) {
@@ -464,7 +465,7 @@ static int sim_run(SimModel* h, int nq, int n, const int32_t* src, const int32_t
   sim_rank_kernel<<<nq, 1024, 0, s>>>(h->x, n, h->order, h->perm);
   HIP_CHECK(hipGetLastError());
   h->last_nq = nq; h->last_n = n; h->last_drop = drop; h->last_rows = R;
-  h->last_seed = seed; h->last_step = step;
+  h->last_seed = seed; h->last_step = step; h->last_ksplits = 0;
   if (!with_loss) return RSYS_OK;
   const int nb = (n + SIM_LT - 1) / SIM_LT;
   sim_lambda_kernel<<<dim3(nb, nq), SIM_LT, 0, s>>>(h->x, h->rel, h->order, n, h->wscale, h->dldx, h->lpart);
@@ -665,6 +666,11 @@ static int sim_debug_get(SimModel* h, const char* name, void* out, int64_t n) {
   HIP_CHECK(hipSetDevice(h->device));
   HIP_CHECK(hipStreamSynchronize(h->stream));
   const long long P2 = (long long)h->last_nq * h->last_n;
+  if (strcmp(name, "splits") == 0) {
+    ARG_CHECK(n == 1, "rsys_sim_debug_get: splits takes 1 int");
+    *(int32_t*)out = h->last_ksplits;
+    return RSYS_OK;
+  }
   const bool ranks = strcmp(name, "ranks") == 0, scores = strcmp(name, "scores") == 0;
   if (ranks || scores || strcmp(name, "dldx") == 0) {
     ARG_CHECK(n == P2, "rsys_sim_debug_get: n must be n_q * n of the last call");
@@ -691,7 +697,7 @@ static int sim_debug_get(SimModel* h, const char* name, void* out, int64_t n) {
     if (e != hipSuccess) { set_error(std::string("rsys_sim_debug_get: ") + hipGetErrorString(e)); return RSYS_ERR_HIP; }
     return RSYS_OK;
   }
-  set_error(std::string("rsys_sim_debug_get: unknown name '") + name + "' (ranks, scores, dldx, dropout_mask)");
+  set_error(std::string("rsys_sim_debug_get: unknown name '") + name + "' (ranks, scores, dldx, dropout_mask, splits)");
   return RSYS_ERR_ARG;
 }
 

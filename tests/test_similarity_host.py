@@ -1,15 +1,114 @@
 """CPU: the host side of the item-similarity model (recommendersystem_amd/similarity.py) against tests/_similarity_np.py: query grouping
 and the stable target sort, the positive caps, list assembly, the -inf fill rule of the hard negatives, EarlyStopper and the CSV rows, the
-cross-medium map and the layout of the item_similarity tables."""
+cross-medium map and the layout of the item_similarity tables; and the restatement's own hand-derived gradients (what the GPU tests compare
+the device with) against torch autograd in fp64, at ragged list lengths and on the clamp branch of the normalisation."""
+import math
 import os
 import sys
 
 import numpy as np
+import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import _similarity_np as sn  # noqa: E402
 
 from recommendersystem_amd import similarity as sim  # noqa: E402
+
+
+# ---- the oracle's hand-derived gradients against autograd (the formulas of csrc/similarity.hip's header, restated in torch fp64)
+def _ltr_problem(nq, n, seed=0, v=400, f=24, e=16):
+    """targets drawn without replacement, at least two distinct relevances per list (where n > 1), ties among the relevances"""
+    rng = np.random.default_rng(seed)
+    feat = rng.standard_normal((v, f))
+    W = rng.standard_normal((e, f)) / np.sqrt(f)
+    src = rng.integers(0, v, nq)
+    tgt = np.stack([rng.permutation(v)[:n] for _ in range(nq)])
+    rel = np.where(rng.random((nq, n)) < 0.4, rng.integers(1, 6, (nq, n)).astype(np.float64), 0.0)
+    if n > 1:
+        rel[:, 0], rel[:, 1] = 3.0, 0.0
+    w = np.sqrt(rng.integers(1, 100, nq).astype(np.float64))
+    return feat, W, math.log(1.0 / 0.07), src, tgt, rel, w
+
+
+def _ltr_autograd(feat, W, ls, src, tgt, rel, w):
+    """(loss, x, dL/dx, dW, dls): encoder f[id] @ W.T, F.normalize, dot product * exp(logit_scale), LambdaRank with the ranks a constant"""
+    torch = pytest.importorskip("torch")
+    nq, n = tgt.shape
+    tW = torch.tensor(W, dtype=torch.float64, requires_grad=True)
+    tls = torch.tensor(ls, dtype=torch.float64, requires_grad=True)
+    tf = torch.tensor(feat, dtype=torch.float64)
+    ys = tf[torch.tensor(np.repeat(src, n))] @ tW.T
+    yt = tf[torch.tensor(tgt.reshape(-1))] @ tW.T
+    a, b = torch.nn.functional.normalize(ys, dim=-1), torch.nn.functional.normalize(yt, dim=-1)
+    x = ((a * b).sum(-1) * tls.exp()).reshape(nq, n)
+    x.retain_grad()
+    pos = torch.argsort(x.detach(), dim=1, descending=True, stable=True)
+    order = torch.empty_like(pos)
+    order.scatter_(1, pos, torch.arange(1, n + 1).repeat(nq, 1))
+    disc = 1.0 / torch.log2(1.0 + order.to(torch.float64))
+    y = torch.tensor(rel, dtype=torch.float64)
+    dy = y[:, :, None] - y[:, None, :]
+    c = ((disc[:, :, None] - disc[:, None, :]) * dy).abs() * (dy > 0)
+    lq = (c * -torch.nn.functional.logsigmoid(x[:, :, None] - x[:, None, :])).sum(dim=(1, 2))   # (softplus goes linear beyond 20)
+    tw = torch.tensor(w, dtype=torch.float64)
+    loss = (lq * tw).sum() / tw.sum()
+    loss.backward()
+    return float(loss.detach()), x.detach().numpy(), x.grad.numpy(), tW.grad.numpy(), float(tls.grad)
+
+
+def _rel(a, b):
+    return float(np.linalg.norm(np.asarray(a, np.float64) - np.asarray(b, np.float64)) / max(np.linalg.norm(b), 1e-300))
+
+
+_LTR_SHAPES = [(1, 1), (3, 2), (5, 3), (7, 65), (2, 257)]
+
+
+@pytest.mark.parametrize("nq,n", _LTR_SHAPES)
+def test_oracle_gradients_against_autograd(nq, n):
+    p = _ltr_problem(nq, n, seed=nq * 1000 + n)
+    ref = _ltr_autograd(*p)
+    got = sn.forward_backward(*p)
+    by_id = sn.forward_backward_by_id(*p, sn.ranks(got[1]))
+    if n == 1:   # no pair: everything is exactly 0
+        for r in (ref, got, by_id):
+            assert r[0] == 0.0 and r[4] == 0.0 and not np.any(r[2]) and not np.any(r[3])
+        assert _rel(got[1], ref[1]) <= 1e-12 and _rel(by_id[1], got[1]) <= 1e-12
+        return
+    assert all(len(set(r)) >= 2 for r in p[5])   # every list has a pair
+    for cand, base, tag in ((got, ref, "oracle vs autograd"), (by_id, got, "by_id vs oracle")):
+        errs = {"loss": abs(cand[0] - base[0]) / abs(base[0]), "x": _rel(cand[1], base[1]), "dldx": _rel(cand[2], base[2]),
+                "dW": _rel(cand[3], base[3]), "dls": abs(cand[4] - base[4]) / abs(base[4])}
+        print(tag, (nq, n), {k: f"{e:.1e}" for k, e in errs.items()})
+        for k, e in errs.items():
+            assert e <= 1e-12, (tag, k, e)
+
+
+def test_oracle_clamp_branch_against_autograd():
+    """a target whose encoder output is exactly zero (feature row e_0, column 0 of W zero) while its feature row is not: F.normalize
+    divides by the constant 1e-12 there, and dW's column 0 carries that row's dY / 1e-12"""
+    nq, n = 3, 5
+    feat, W, ls, src, tgt, rel, w = _ltr_problem(nq, n, seed=77)
+    zid = int(np.setdiff1d(np.arange(feat.shape[0]), np.concatenate([src, tgt.reshape(-1)]))[0])
+    tgt[1, 2] = zid
+    feat[zid] = 0.0
+    feat[zid, 0] = 1.0
+    W[:, 0] = 0.0
+    rel[1] = [0.0, 2.0, 4.0, 0.0, 1.0]
+    p = (feat, W, ls, src, tgt, rel, w)
+    ref = _ltr_autograd(*p)
+    got = sn.forward_backward(*p)
+    by_id = sn.forward_backward_by_id(*p, sn.ranks(got[1]))
+    where = np.argwhere(tgt == zid)
+    for r in (ref, got, by_id):
+        assert all(r[1][q, j] == 0.0 for q, j in where)
+    g = max(abs(ref[2][q, j]) for q, j in where)
+    assert g > 0 and np.abs(ref[3][:, 0]).max() > 1e10 * g     # column 0 is ~ 1e12 dL/dx
+    for cand, base, tag in ((got, ref, "oracle vs autograd"), (by_id, got, "by_id vs oracle")):
+        errs = {"loss": abs(cand[0] - base[0]) / abs(base[0]), "dldx": _rel(cand[2], base[2]), "dW col 0": _rel(cand[3][:, 0], base[3][:, 0]),
+                "dW rest": _rel(cand[3][:, 1:], base[3][:, 1:]), "dls": abs(cand[4] - base[4]) / abs(base[4])}
+        print(tag, {k: f"{e:.1e}" for k, e in errs.items()})
+        for k, e in errs.items():
+            assert e <= 1e-12, (tag, k, e)
 
 
 def _pairs(seed=0, v=50, rows=400):
