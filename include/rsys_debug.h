@@ -137,9 +137,21 @@ int32_t rsys_op_rank_cache_copy_segments(int32_t dtype, int32_t rows, int32_t T,
 int32_t rsys_rank_cache_get(rsys_model* m, int32_t layer, int32_t slot, void* out, int64_t bytes);
 /* the selection of rsys_retrieve_topk alone, on caller-provided device buffers: per row r of scores [rows][ld >= V] the min(k, admissible)
  * best columns by descending value, ties by ascending column, -inf / NaN excluded, -0.0 == +0.0; ids / vals [rows][k] (padding -1 / -inf),
- * counts [rows]; 1 <= k <= min(V, 8192) */
+ * counts [rows]; 1 <= k <= min(V, 8192), 1 <= rows <= 65535 */
 int32_t rsys_op_topk(const float* scores, int64_t ld, int32_t rows, int32_t V, int32_t k,
                      int32_t* ids, float* vals, int32_t* counts);
+/* the windowed selection of rsys_retrieve_window alone (win_*_kernel), on caller-provided device buffers: per row r of scores
+ * [rows][ld >= V] the ranks [start[r], start[r] + len[r]) of rsys_op_topk's ordering; start (int64) and len are HOST arrays, 1 <= len <= 1024,
+ * start >= 0, 1 <= rows <= 65535.  ids / vals [rows][1024] (padding -1 / -inf), counts [rows] = clip(total - start, 0, len), totals [rows] =
+ * the admissible count.  bounds (device, may be NULL) [rows][2][2] = (threshold key T as its uint32 bits, need) of the window's end bound
+ * and of its start bound after the select: the top-c set of a bound is every key above T plus the first `need` keys equal to T by
+ * ascending id; need == 0 with T != 0 and T != 0xffffffff is the "between two keys" form (T = a bin's smallest key - 1) */
+int32_t rsys_op_topk_window(const float* scores, int64_t ld, int32_t rows, int32_t V, const int64_t* start, const int32_t* len,
+                            int32_t* ids, float* vals, int32_t* counts, int32_t* totals, int32_t* bounds);
+/* the log-sum-exp of rsys_retrieve_topk's scoring alone (lse_partial_kernel, lse_final_kernel: 64 slices per row, online max, a fixed
+ * fold order), on device buffers: lse[r] = log sum_i exp(z[r][i]) over i < V of z [rows][ldz >= V]; 1 <= rows <= 65535.  -inf entries add
+ * nothing; a row that is all -inf gives -inf (every item of such a query is then NaN or -inf downstream and excluded); rows are expected to hold no NaN */
+int32_t rsys_op_lse(const float* z, int64_t ldz, int32_t rows, int32_t V, float* lse);
 /* the three weighted accumulations of rsys_query_weights_set alone, one launch each on caller-provided DEVICE buffers (host: cand_offsets,
  * retrieval_coef, rating_coefs); a section runs when its output is not NULL.  Shared by the first two: z [rows][ldz] and lse (indexed by
  * query / user q, row q - q0 of z), members (the queries of every group, group by group), ranges int32 [n_groups][2] = the slice of

@@ -231,6 +231,8 @@ _SIGS = [
                                           _P, _P, _P, _P, _P, _P, C.c_float, C.c_int32, _P,
                                           _P, _P, _P, C.c_int32, _P, _P, C.c_int32, _P, _P]),
     ("rsys_op_topk", C.c_int32, [_P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P]),
+    ("rsys_op_topk_window", C.c_int32, [_P, C.c_int64, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, _P]),
+    ("rsys_op_lse", C.c_int32, [_P, C.c_int64, C.c_int32, C.c_int32, _P]),
     ("rsys_op_target_rank", C.c_int32, [_P, C.c_int64, C.c_int32, C.c_int32, _P, _P]),
     ("rsys_op_pair_ranks", C.c_int32, [_P, C.c_int64, C.c_int32, C.c_int32, _P, _P, _P, _P]),
     ("rsys_rank_gram_get", C.c_int32, [_P, C.c_int32, C.c_int32, _P, _P, _P, C.c_int64]),

@@ -1252,6 +1252,15 @@ int32_t rsys_op_topk(const float* scores, int64_t ld, int32_t rows, int32_t V, i
   switches_parse();
   return op_topk(scores, ld, rows, V, k, ids, vals, counts);
 }
+int32_t rsys_op_topk_window(const float* scores, int64_t ld, int32_t rows, int32_t V, const int64_t* start, const int32_t* len,
+                            int32_t* ids, float* vals, int32_t* counts, int32_t* totals, int32_t* bounds) {
+  switches_parse();
+  return op_topk_window(scores, ld, rows, V, start, len, ids, vals, counts, totals, bounds);
+}
+int32_t rsys_op_lse(const float* z, int64_t ldz, int32_t rows, int32_t V, float* lse) {
+  switches_parse();
+  return op_lse(z, ldz, rows, V, lse);
+}
 int32_t rsys_op_query_weights(const float* z, int64_t ldz, const float* lse, const int32_t* members, const int32_t* ranges, int32_t q0,
                               const float* user_w, int32_t n_groups, const float* src, float* dst, int32_t V, int32_t last,
                               const int64_t* cand_offsets, const int32_t* cand, const float* r_masked, const int64_t* rm_offsets,

@@ -523,6 +523,10 @@ void render_free(Model* m);
 int op_rerank(int32_t n, int32_t partialk, const float* pen, const float* r, const float* gram, const int32_t* ss_bits,
               const int32_t* related_bits, int32_t* picks);
 int op_topk(const float* scores, int64_t ld, int32_t rows, int32_t V, int32_t k, int32_t* ids, float* vals, int32_t* counts);
+// rsys_op_topk_window / rsys_op_lse: the windowed selection and the log-sum-exp launches alone, on device arrays (include/rsys_debug.h)
+int op_topk_window(const float* scores, int64_t ld, int32_t rows, int32_t V, const int64_t* start, const int32_t* len, int32_t* ids,
+                   float* vals, int32_t* counts, int32_t* totals, int32_t* bounds);
+int op_lse(const float* z, int64_t ldz, int32_t rows, int32_t V, float* lse);
 // rsys_op_query_weights: the three weighted accumulations alone, on device arrays (one section each; include/rsys_debug.h)
 int op_combine_weighted(const float* src, float* dst, int32_t ng, int32_t V, int32_t last, const float* z, int64_t ldz, const float* lse,
                         const int32_t* members, const int32_t* ranges, int32_t q0, const float* user_w);

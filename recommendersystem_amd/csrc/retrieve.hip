@@ -861,7 +861,7 @@ int topk_rows(const float* scores, long long ld, int rows, int V, int k, void* w
 
 int op_topk(const float* scores, int64_t ld, int32_t rows, int32_t V, int32_t k, int32_t* ids, float* vals, int32_t* counts) {
   ARG_CHECK(scores && ids && vals && counts, "rsys_op_topk: null buffer");
-  ARG_CHECK(rows >= 1 && V >= 1 && ld >= V, "rsys_op_topk: rows >= 1, V >= 1, ld >= V");
+  ARG_CHECK(rows >= 1 && rows <= 65535 && V >= 1 && ld >= V, "rsys_op_topk: 1 <= rows <= 65535 (grid.y), V >= 1, ld >= V");
   ARG_CHECK(k >= 1 && k <= std::min(V, RT_MAXK), "rsys_op_topk: 1 <= k <= min(V, 8192)");
   void* buf = nullptr;
   HIP_CHECK(hipMalloc(&buf, topk_rows_ws_bytes(rows, V, k)));
@@ -869,6 +869,85 @@ int op_topk(const float* scores, int64_t ld, int32_t rows, int32_t V, int32_t k,
   const hipError_t e = hipDeviceSynchronize();
   hipFree(buf);
   if (rc == RSYS_OK && e != hipSuccess) { set_error(std::string("rsys_op_topk: ") + hipGetErrorString(e)); rc = RSYS_ERR_HIP; }
+  return rc;
+}
+
+// workspace of rsys_op_topk_window: the keys, the selection buffers of a window (two bounds per row, int4 counts) and the windows
+struct WinOpBufs { unsigned* keys; SelBufs sb; long long* wstart; int* wlen; };
+static void topk_window_layout(Carve& c, int rows, int V, WinOpBufs* w) {
+  const int nb = (V + RT_ITEMS - 1) / RT_ITEMS;
+  w->keys = c.take<unsigned>((size_t)rows * V);
+  w->sb.hist = c.take<unsigned>((size_t)2 * rows * 256);
+  w->sb.st = c.take<SelState>((size_t)2 * rows);
+  w->sb.cnt = c.take<int2>((size_t)2 * rows * nb);
+  w->sb.cand = c.take<unsigned long long>((size_t)rows * RT_WIN);
+  w->sb.ldc = RT_WIN;
+  w->wstart = c.take<long long>(rows);
+  w->wlen = c.take<int>(rows);
+}
+
+// rsys_op_topk_window: the keys of given scores (combine_kernel<true> without queries, as topk_rows) and window_select, on a workspace of
+// its own; bounds (device, or null) [rows][2][2] = (T, need) of the end bound and of the start bound as the select left them
+int op_topk_window(const float* scores, int64_t ld, int32_t rows, int32_t V, const int64_t* start, const int32_t* len, int32_t* ids,
+                   float* vals, int32_t* counts, int32_t* totals, int32_t* bounds) {
+  ARG_CHECK(scores && start && len && ids && vals && counts && totals, "rsys_op_topk_window: null buffer");
+  ARG_CHECK(rows >= 1 && rows <= 65535 && V >= 1 && ld >= V, "rsys_op_topk_window: 1 <= rows <= 65535 (grid.y), V >= 1, ld >= V");
+  for (int r = 0; r < rows; ++r) {
+    ARG_CHECK(len[r] >= 1 && len[r] <= RT_WIN, "rsys_op_topk_window: 1 <= len <= 1024");
+    ARG_CHECK(start[r] >= 0, "rsys_op_topk_window: start >= 0");
+  }
+  static_assert(sizeof(long long) == sizeof(int64_t), "window starts are copied as they are");
+  Carve probe{nullptr};
+  WinOpBufs w;
+  topk_window_layout(probe, rows, V, &w);
+  void* buf = nullptr;
+  HIP_CHECK(hipMalloc(&buf, probe.off));
+  Carve c{(char*)buf};
+  topk_window_layout(c, rows, V, &w);
+  const int nb = (V + RT_ITEMS - 1) / RT_ITEMS;
+  std::vector<SelState> st(bounds ? (size_t)2 * rows : 0);
+  auto run = [&]() -> int {
+    HIP_CHECK(hipMemcpy(w.wstart, start, (size_t)rows * 8, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(w.wlen, len, (size_t)rows * 4, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemsetAsync(w.sb.hist, 0, (size_t)2 * rows * 256 * 4, nullptr));
+    combine_kernel<true><<<dim3(nb, rows), RT_THREADS>>>(scores, ld, (float*)w.keys, V, nullptr, 0, nullptr, nullptr, nullptr, 0, V, w.sb.hist);
+    RT_LAUNCH_CHECK();
+    RC(window_select(w.keys, V, rows, V, w.wstart, w.wlen, w.sb, ids, vals, counts, totals, nullptr));
+    if (bounds) {
+      HIP_CHECK(hipMemcpy(st.data(), w.sb.st, st.size() * sizeof(SelState), hipMemcpyDeviceToHost));
+      std::vector<int32_t> hb((size_t)rows * 4);
+      for (int r = 0; r < rows; ++r)
+        for (int b = 0; b < 2; ++b) {
+          hb[(size_t)r * 4 + 2 * b] = (int32_t)st[(size_t)b * rows + r].prefix;
+          hb[(size_t)r * 4 + 2 * b + 1] = st[(size_t)b * rows + r].need;
+        }
+      HIP_CHECK(hipMemcpy(bounds, hb.data(), hb.size() * 4, hipMemcpyHostToDevice));
+    }
+    return RSYS_OK;
+  };
+  int rc = run();
+  const hipError_t e = hipDeviceSynchronize();
+  hipFree(buf);
+  if (rc == RSYS_OK && e != hipSuccess) { set_error(std::string("rsys_op_topk_window: ") + hipGetErrorString(e)); rc = RSYS_ERR_HIP; }
+  return rc;
+}
+
+// rsys_op_lse: the two log-sum-exp launches of retrieve_chunk_scores on device rows
+int op_lse(const float* z, int64_t ldz, int32_t rows, int32_t V, float* lse) {
+  ARG_CHECK(z && lse, "rsys_op_lse: null buffer");
+  ARG_CHECK(rows >= 1 && rows <= 65535 && V >= 1 && ldz >= V, "rsys_op_lse: 1 <= rows <= 65535 (grid.y), V >= 1, ldz >= V");
+  float2* part = nullptr;
+  HIP_CHECK(hipMalloc(&part, (size_t)rows * RT_LSE_SPLIT * sizeof(float2)));
+  int rc = RSYS_OK;
+  lse_partial_kernel<<<dim3(RT_LSE_SPLIT, rows), RT_THREADS>>>(z, ldz, V, part);
+  if (hipGetLastError() != hipSuccess) { set_error("rsys_op_lse: launch failed (partial)"); rc = RSYS_ERR_HIP; }
+  if (rc == RSYS_OK) {
+    lse_final_kernel<<<(rows + 255) / 256, 256>>>(part, RT_LSE_SPLIT, rows, 0, lse);
+    if (hipGetLastError() != hipSuccess) { set_error("rsys_op_lse: launch failed (final)"); rc = RSYS_ERR_HIP; }
+  }
+  const hipError_t e = hipDeviceSynchronize();
+  hipFree(part);
+  if (rc == RSYS_OK && e != hipSuccess) { set_error(std::string("rsys_op_lse: ") + hipGetErrorString(e)); rc = RSYS_ERR_HIP; }
   return rc;
 }
 

@@ -3,9 +3,13 @@ Inference/render.jl:240-333).  The selection is checked bit for bit against a st
 restatement on the same operands (the model's fused item table and its inference_select queries, rounded to bf16 in bf16 mode)."""
 import ctypes as C
 import os
+import sys
 
 import numpy as np
 import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from _retrieve_np import _expect_topk, _rows  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -13,15 +17,6 @@ TASK_W = [0.05, 0.2, 0.3, 0.25]
 
 
 # ---------------------------------------------------------------- rsys_op_topk against np.lexsort
-def _expect_topk(row, k):
-    ids = np.arange(row.size)
-    ok = ~np.isnan(row) & (row > -np.inf)
-    order = np.lexsort((ids[ok], -row[ok].astype(np.float64)))
-    sel = ids[ok][order][:k]
-    vals = row[sel] + np.float32(0.0)            # -0.0 comes back as +0.0
-    return sel.astype(np.int32), vals.astype(np.float32)
-
-
 def _op_topk(scores, k, ld=None):
     from recommendersystem_amd._lib import check, lib
     rows, V = scores.shape
@@ -56,29 +51,6 @@ def _check_op(scores, k, ld=None):
         assert np.array_equal(ids[r, :n], e_ids), r
         assert np.array_equal(vals[r, :n].view(np.uint32), e_vals.view(np.uint32)), r
         assert (ids[r, n:] == -1).all() and np.isneginf(vals[r, n:]).all(), r
-
-
-def _rows(kind, rows, V, rng):
-    if kind == "random":
-        return rng.standard_normal((rows, V)).astype(np.float32) * 4 - 10
-    if kind == "equal":
-        return np.full((rows, V), -3.25, np.float32)
-    if kind == "ulp":      # a handful of neighbouring floats: every digit pass runs, long runs of ties
-        base = np.float32(-7.5).view(np.int32)
-        return (base + rng.integers(0, 5, (rows, V))).astype(np.int32).view(np.float32)
-    if kind == "zeros":    # +-0.0 mixed with a few values around them
-        x = np.where(rng.random((rows, V)) < 0.5, np.float32(-0.0), np.float32(0.0)).astype(np.float32)
-        x[rng.random((rows, V)) < 0.05] = 1e-30
-        x[rng.random((rows, V)) < 0.05] = -1e-30
-        return x
-    if kind == "special":  # -inf and NaN sprinkled in; the last row all -inf
-        x = rng.standard_normal((rows, V)).astype(np.float32)
-        x[rng.random((rows, V)) < 0.3] = -np.inf
-        x[rng.random((rows, V)) < 0.1] = np.nan
-        x[rng.random((rows, V)) < 0.01] = np.inf
-        x[-1] = -np.inf
-        return x
-    raise AssertionError(kind)
 
 
 @pytest.mark.parametrize("kind", ["random", "equal", "ulp", "zeros", "special"])

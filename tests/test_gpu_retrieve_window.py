@@ -1,7 +1,9 @@
 """GPU: windowed retrieval (rsys_retrieve_window): the ranks [start, start + len) of rsys_retrieve_request's ordering and the
 exact admissible count, for groups with any number of queries including none.  Windows are checked byte for byte against slices of
 rsys_retrieve_request where that call reaches (k = V_m <= 8192), as a strictly ordered permutation of the admissible set past its cap,
-and exactly against an int64 oracle on integer-valued tables for groups without queries (tests/_render_items_np.py)."""
+and exactly against an int64 oracle on integer-valued tables for groups without queries (tests/_render_items_np.py).  These are the
+windows of whole requests; the windowed selection kernels alone (win_*_kernel through rsys_op_topk_window) are checked exactly, branch
+by branch, on score populations built for them in tests/test_gpu_retrieve_select.py."""
 import os
 import sys
 
