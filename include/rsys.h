@@ -261,6 +261,35 @@ int32_t rsys_query_weights_set(rsys_model* m, const float* user_w, int64_t n_use
                                const float* sel_w, int64_t n_sel);                    /* [n_sel], or NULL with 0 */
 /* out = (n_users, n_sel) of the weights the model holds for the next request, 0 = none of that kind */
 int32_t rsys_query_weights_pending(rsys_model* m, int64_t out[2]);
+/* Text queries of the NEXT request (the reference's roadmap: "Natural language queries" beside "Multiquery recs"): n_texts
+ * query embeddings x [n_texts][Q] (host f32) of the search handle `search` (rsys_search_*, features set, on the model's device, its V_m the
+ * model's for `medium`), each for one group of the consuming call and with a finite weight (w == NULL: 1.0 each).  The call scores them on
+ * the search handle's stream, with one wait -- P = x Wenc as rsys_search_topk forms it, then one streaming pass over E_m per tile of up
+ * to 8 texts (text_scores_kernel; 4 texts above D = 2048, 2 above 4096: the tile's fp32 rows stay within 64 KiB of LDS), z_t[i] = (P_t . E_m[i]) * exp(logit_scale) for i < V_m in fp32, and lse_t = log sum_i exp(z_t[i]) by
+ * the launches of rsys_op_lse -- into a buffer the model owns, and the model holds rows, lse, groups and weights of that medium until the
+ * next call of rsys_retrieve_request, rsys_retrieve_window, rsys_rank_request, rsys_render_request, rsys_render_request_full or
+ * rsys_render_items, which consumes the sets of BOTH media: they are gone when that call returns, on success and on error alike.  No other
+ * entry point (rsys_retrieve_topk and rsys_search_* included) reads or clears them.  One set per medium; a call replaces that medium's
+ * set, n_texts == 0 clears it (the other arguments are then not read); 1 <= n_texts <= min(64, the handle's max_batch).
+ * RSYS_ERR_ARG, with nothing held for that medium afterwards: a null handle, a handle on another device, a V_m that is not the model's,
+ * features never set, null x or group, a non-finite x or w; a medium that is not 0 or 1 (nothing changes).
+ * The consuming call checks, before anything else, every text's group against its n_groups, and in the page pipelines against
+ * group_medium (a text of medium m belongs to a group of medium m); a call on one medium refuses a set of the other.  Each is RSYS_ERR_ARG
+ * with outputs untouched.
+ * Semantics, every operation rounded in fp32 on its own (weighted_add: no fused multiply-add), a weight of +-0.0 skips its term --
+ *   retrieval   after the prior and before the masks: score_g[i] = score_g[i] + w_t * (z_t[i] - lse_t) over the group's texts in text
+ *               order, then the users' terms exactly as without texts.  A group without users (rsys_retrieve_window, rsys_render_items)
+ *               is scored by prior + texts.  Texts carry no masks and no flags.
+ *   ranking     r[c] = +0.0, then r[c] = r[c] + w_t * (z_t[id_c] - lse_t) in text order (rank_text_kernel), then the users' terms onto it;
+ *               no coefficient and no rating term apply to a text.  With r_in the texts are consumed and not read.  rsys_render_items
+ *               keeps r = +0.0: its retrieval order already carries the texts.
+ * The page pipelines hand each medium's set to that medium's retrieval and ranking stages, groups renumbered as the stages number them. */
+int32_t rsys_query_texts_set(rsys_model* m, void* search, int32_t medium,
+                             const float* x, int64_t n_texts,      /* [n_texts][Q] f32, host */
+                             const int32_t* group,                 /* [n_texts], group of the consuming call */
+                             const float* w);                      /* [n_texts] or NULL = 1.0 */
+/* out[m] = the texts the model holds for medium m for the next request, 0 = none */
+int32_t rsys_query_texts_pending(rsys_model* m, int64_t out[2]);
 /* A whole render.jl `retrieval(state)` per group of queries, on the tables above: score_g = p_g + the rsys_retrieve_topk score, where
  * p_g = E_m^T s_g, s_g = sum over the group's selected items in list order of E_m[id] (same medium) or crossproject.{am} E_am[id] (fp32
  * throughout; 0 without selected items).  Masked for group g (render.jl:255-331): item 0; the group's selected items of medium m; items

@@ -152,6 +152,10 @@ int32_t rsys_op_topk_window(const float* scores, int64_t ld, int32_t rows, int32
  * fold order), on device buffers: lse[r] = log sum_i exp(z[r][i]) over i < V of z [rows][ldz >= V]; 1 <= rows <= 65535.  -inf entries add
  * nothing; a row that is all -inf gives -inf (every item of such a query is then NaN or -inf downstream and excluded); rows are expected to hold no NaN */
 int32_t rsys_op_lse(const float* z, int64_t ldz, int32_t rows, int32_t V, float* lse);
+/* the scoring of rsys_query_texts_set alone, to HOST outputs: z_out [n][V_m] = the logits of n texts x [n][Q] (host) over the search
+ * handle's items and lse_out [n] = their log-sum-exp, the same bits the setter computes; 1 <= n <= min(64, the handle's max_batch).
+ * Like the setter it rewrites the handle's query and projection buffers, so rsys_search_debug_get has no forward to report until the next one */
+int32_t rsys_op_text_rows(void* search, const float* x, int32_t n, float* z_out, float* lse_out);
 /* the three weighted accumulations of rsys_query_weights_set alone, one launch each on caller-provided DEVICE buffers (host: cand_offsets,
  * retrieval_coef, rating_coefs); a section runs when its output is not NULL.  Shared by the first two: z [rows][ldz] and lse (indexed by
  * query / user q, row q - q0 of z), members (the queries of every group, group by group), ranges int32 [n_groups][2] = the slice of

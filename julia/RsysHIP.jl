@@ -783,6 +783,22 @@ function search_topk(s::SearchModel, queries::Matrix{Float32}, k::Integer)
         s.h, queries, n, k, ids, lp))
     ids, lp
 end
+# text queries of the NEXT request call on the model (rsys_query_texts_set): x is Q x n_texts (embeddings of the search handle `s`, whose
+# features are medium `medium`'s item table), group 0-based per text, w one finite Float32 per text or nothing (1.0 each).  An empty x
+# clears the medium's set.  The six request calls that consume query weights consume both media's sets, on success and on error alike.
+function query_texts_set(m::Model, s::SearchModel, medium::Integer, x::Matrix{Float32}, group, w = nothing)
+    n = size(x, 2)
+    g = Vector{Int32}(group)
+    ww = w === nothing ? Ptr{Float32}(C_NULL) : Vector{Float32}(w)
+    GC.@preserve x g ww check(ccall((:rsys_query_texts_set, LIB), Int32,
+        (Ptr{Cvoid}, Ptr{Cvoid}, Int32, Ptr{Float32}, Int64, Ptr{Int32}, Ptr{Float32}), m.h, s.h, medium, x, n, g, ww))
+end
+# the texts held per medium for the next request, 0 = none
+function query_texts_pending(m::Model)
+    out = zeros(Int64, 2)
+    GC.@preserve out check(ccall((:rsys_query_texts_pending, LIB), Int32, (Ptr{Cvoid}, Ptr{Int64}), m.h, out))
+    (out[1], out[2])
+end
 
 # Watch-order counts (Training/media_relations.jl get_watch_order; DESIGN.md §4q): its own handle over the row band [row0, row1) of W.
 # Ids are 0-based; W[a][b] = users who watched a before b.

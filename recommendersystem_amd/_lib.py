@@ -81,6 +81,8 @@ _SIGS = [
     ("rsys_retrieve_request", C.c_int32, [_P, C.c_int32, _P, C.c_int64, _P, C.c_int32, _P, _P, _P, _P, _P, _P, _P, C.c_int32, _P, _P, _P]),
     ("rsys_query_weights_set", C.c_int32, [_P, _P, C.c_int64, _P, C.c_int64]),
     ("rsys_query_weights_pending", C.c_int32, [_P, _P]),
+    ("rsys_query_texts_set", C.c_int32, [_P, _P, C.c_int32, _P, C.c_int64, _P, _P]),
+    ("rsys_query_texts_pending", C.c_int32, [_P, _P]),
     ("rsys_retrieve_window", C.c_int32, [_P, C.c_int32, _P, C.c_int64, _P, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     ("rsys_render_items", C.c_int32, [_P, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int64, _P, _P]),
     ("rsys_rank_related_set", C.c_int32, [_P, C.c_int32, C.c_int64, _P, _P, _P]),
@@ -233,6 +235,7 @@ _SIGS = [
     ("rsys_op_topk", C.c_int32, [_P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P]),
     ("rsys_op_topk_window", C.c_int32, [_P, C.c_int64, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, _P]),
     ("rsys_op_lse", C.c_int32, [_P, C.c_int64, C.c_int32, C.c_int32, _P]),
+    ("rsys_op_text_rows", C.c_int32, [_P, _P, C.c_int32, _P, _P]),
     ("rsys_op_target_rank", C.c_int32, [_P, C.c_int64, C.c_int32, C.c_int32, _P, _P]),
     ("rsys_op_pair_ranks", C.c_int32, [_P, C.c_int64, C.c_int32, C.c_int32, _P, _P, _P, _P]),
     ("rsys_rank_gram_get", C.c_int32, [_P, C.c_int32, C.c_int32, _P, _P, _P, C.c_int64]),

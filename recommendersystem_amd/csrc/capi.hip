@@ -52,6 +52,49 @@ struct TakenWeights {
     return RSYS_OK;
   }
 };
+// The pending text queries of a model (rsys_query_texts_set), both media, in the hands of the request entry point that consumes them:
+// moved out on entry as the weights are, so the model holds none again on every return path.  The rows stay in the model's buffers,
+// which only the next rsys_query_texts_set rewrites.
+struct TakenTexts {
+  struct Set { QueryTexts q; std::vector<int32_t> group, row; } t[2];
+  explicit TakenTexts(Model* m) {
+    for (int mm = 0; mm < 2; ++mm) {
+      TextSet& ts = m->qtexts[mm];
+      Set& o = t[mm];
+      o.group = std::move(ts.group);
+      o.group.resize((size_t)ts.n);
+      o.row.resize((size_t)ts.n);
+      for (int i = 0; i < ts.n; ++i) o.row[i] = i;
+      o.q.n = ts.n; o.q.z = ts.z; o.q.lse = ts.lse; o.q.d_w = ts.d_w; o.q.ldz = ts.ldz;
+      o.q.row = o.row.data(); o.q.group = o.group.data();
+      ts.n = 0; ts.group.clear();
+    }
+  }
+  // a call on one medium: a set of the other medium is refused, every group must be one of the call's.  A medium or a group count the
+  // call itself will refuse is left to it: no texts are handed on.
+  int check(const char* who, int medium, int64_t ng, QueryTexts* out) const {
+    *out = QueryTexts{};
+    if (t[0].q.n == 0 && t[1].q.n == 0) return RSYS_OK;
+    if ((medium != 0 && medium != 1) || ng < 1 || ng > 4096) return RSYS_OK;
+    ARG_CHECK(t[1 - medium].q.n == 0, std::string(who) + ": text queries are pending for a medium this call does not serve (rsys_query_texts_set)");
+    for (int32_t g : t[medium].group) ARG_CHECK(g >= 0 && g < ng, std::string(who) + ": the group of a pending text query must be in [0, n_groups)");
+    *out = t[medium].q;
+    return RSYS_OK;
+  }
+  // a page pipeline: every text's group must be one of the call's and of the set's medium
+  int check_media(const char* who, const int32_t* group_medium, int64_t ng, QueryTexts out[2]) const {
+    out[0] = out[1] = QueryTexts{};
+    if (t[0].q.n == 0 && t[1].q.n == 0) return RSYS_OK;
+    if (group_medium == nullptr || ng < 1 || ng > 4096) return RSYS_OK;
+    for (int mm = 0; mm < 2; ++mm)
+      for (int32_t g : t[mm].group) {
+        ARG_CHECK(g >= 0 && g < ng, std::string(who) + ": the group of a pending text query must be in [0, n_groups)");
+        ARG_CHECK(group_medium[g] == mm, std::string(who) + ": a pending text query belongs to a group of another medium (rsys_query_texts_set)");
+      }
+    out[0] = t[0].q; out[1] = t[1].q;
+    return RSYS_OK;
+  }
+};
 }  // namespace
 
 extern "C" {
@@ -253,16 +296,30 @@ int32_t rsys_query_weights_pending(rsys_model* h, int64_t out[2]) {
   out[1] = h->m->qw_have_sel ? (int64_t)h->m->qw_sel.size() : 0;
   return RSYS_OK;
 }
+int32_t rsys_query_texts_set(rsys_model* h, void* search, int32_t medium, const float* x, int64_t n_texts, const int32_t* group,
+                             const float* w) {
+  CHECK_HANDLE(h);
+  return model_query_texts_set(h->m, search, medium, x, n_texts, group, w);
+}
+int32_t rsys_query_texts_pending(rsys_model* h, int64_t out[2]) {
+  CHECK_HANDLE(h);
+  ARG_CHECK(out, "query_texts_pending: null output");
+  out[0] = h->m->qtexts[0].n; out[1] = h->m->qtexts[1].n;
+  return RSYS_OK;
+}
 int32_t rsys_retrieve_request(rsys_model* h, int32_t medium, const float* queries, int64_t n_queries, const int32_t* group, int32_t n_groups,
                               const int64_t* hist_offsets, const int32_t* hist_medium, const int32_t* hist_ids, const int32_t* hist_status,
                               const int64_t* sel_offsets, const int32_t* sel_medium, const int32_t* sel_ids, int32_t k, int32_t* ids_out,
                               float* scores_out, int32_t* counts_out) {
   CHECK_HANDLE(h);
   const TakenWeights tw(h->m);
+  const TakenTexts tt(h->m);
   QueryWeights qw;
+  QueryTexts qt;
+  RC(tt.check("retrieve_request", medium, n_groups, &qt));
   RC(tw.check("retrieve_request", n_queries, true, sel_offsets, n_groups, &qw));
   return model_retrieve_request(h->m, medium, queries, n_queries, group, n_groups, hist_offsets, hist_medium, hist_ids, hist_status,
-                                sel_offsets, sel_medium, sel_ids, k, ids_out, scores_out, counts_out, qw);
+                                sel_offsets, sel_medium, sel_ids, k, ids_out, scores_out, counts_out, qw, qt);
 }
 int32_t rsys_retrieve_window(rsys_model* h, int32_t medium, const float* queries, int64_t n_queries, const int32_t* group, int32_t n_groups,
                              const int64_t* hist_offsets, const int32_t* hist_medium, const int32_t* hist_ids, const int32_t* hist_status,
@@ -270,21 +327,27 @@ int32_t rsys_retrieve_window(rsys_model* h, int32_t medium, const float* queries
                              const int32_t* win_len, int32_t* ids_out, float* scores_out, int32_t* counts_out, int32_t* total_out) {
   CHECK_HANDLE(h);
   const TakenWeights tw(h->m);
+  const TakenTexts tt(h->m);
   QueryWeights qw;
+  QueryTexts qt;
+  RC(tt.check("retrieve_window", medium, n_groups, &qt));
   RC(tw.check("retrieve_window", n_queries, true, sel_offsets, n_groups, &qw));
   const RetrieveWin win{win_start, win_len, total_out};
   return model_retrieve_window(h->m, medium, queries, n_queries, group, n_groups, hist_offsets, hist_medium, hist_ids, hist_status,
-                               sel_offsets, sel_medium, sel_ids, &win, nullptr, ids_out, scores_out, counts_out, qw);
+                               sel_offsets, sel_medium, sel_ids, &win, nullptr, ids_out, scores_out, counts_out, qw, qt);
 }
 int32_t rsys_render_items(rsys_model* h, int32_t n_groups, const int32_t* group_medium, const int64_t* offset, const int32_t* limit,
                           const float* penalties, const int64_t* sel_offsets, const int32_t* sel_medium, const int32_t* sel_ids,
                           int32_t* ids_out, int64_t ids_cap, int64_t* ids_offsets, int32_t* total_out) {
   CHECK_HANDLE(h);
   const TakenWeights tw(h->m);
+  const TakenTexts tt(h->m);
   QueryWeights qw;
+  QueryTexts qt[2];
+  RC(tt.check_media("render_items", group_medium, n_groups, qt));
   RC(tw.check("render_items", -1, true, sel_offsets, n_groups, &qw));
   return model_render_items(h->m, n_groups, group_medium, offset, limit, penalties, sel_offsets, sel_medium, sel_ids, ids_out, ids_cap,
-                            ids_offsets, total_out, qw.sel);
+                            ids_offsets, total_out, qw.sel, qt);
 }
 int32_t rsys_rank_related_set(rsys_model* h, int32_t medium, int64_t n, const int64_t* colptr, const int32_t* rowval, const float* nzval) {
   CHECK_HANDLE(h);
@@ -297,11 +360,14 @@ int32_t rsys_rank_request(rsys_model* h, int32_t medium, int32_t n_groups, const
                           float rating_mean, const float* r_in, int32_t* ids_out, float* r_out) {
   CHECK_HANDLE(h);
   const TakenWeights tw(h->m);
+  const TakenTexts tt(h->m);
   QueryWeights qw;
+  QueryTexts qt;
+  RC(tt.check("rank_request", medium, n_groups, &qt));
   RC(tw.check("rank_request", n_users, false, nullptr, n_groups, &qw));
   return model_rank_request(h->m, medium, n_groups, cand_offsets, cand_ids, partialk, penalties, queries, n_users, group, r_masked, n_r_masked,
                             hist_offsets, hist_medium, hist_ids, hist_status, retrieval_coef, rating_coefs, rating_mean, r_in, ids_out, r_out,
-                            qw.user);
+                            qw.user, qt);
 }
 int32_t rsys_render_request(rsys_model* h, int32_t n_groups, const int32_t* group_medium, const int64_t* offset, const int32_t* limit,
                             const float* penalties, int64_t n_users, const int32_t* group, const rsys_batch* retrieval_rows,
@@ -312,7 +378,9 @@ int32_t rsys_render_request(rsys_model* h, int32_t n_groups, const int32_t* grou
                             int64_t* ids_offsets, int32_t* total_out) {
   CHECK_HANDLE(h);
   const TakenWeights tw(h->m);
+  const TakenTexts tt(h->m);
   RenderArgs a{};
+  RC(tt.check_media("render_request", group_medium, n_groups, a.qt));
   RC(tw.check("render_request", n_users, true, sel_offsets, n_groups, &a.qw));
   a.full = false; a.ng = n_groups; a.group_medium = group_medium; a.offset = offset; a.limit = limit; a.penalties = penalties;
   a.nu = n_users; a.group = group; a.rb = retrieval_rows; a.retrieval_token = retrieval_token; a.pb = ranking_prefix; a.P = prefix_stride;
@@ -330,7 +398,9 @@ int32_t rsys_render_request_full(rsys_model* h, int32_t n_groups, const int32_t*
                                  const float* coefs, int32_t* ids_out, int64_t ids_cap, int64_t* ids_offsets, int32_t* total_out) {
   CHECK_HANDLE(h);
   const TakenWeights tw(h->m);
+  const TakenTexts tt(h->m);
   RenderArgs a{};
+  RC(tt.check_media("render_request", group_medium, n_groups, a.qt));
   RC(tw.check("render_request", n_users, true, sel_offsets, n_groups, &a.qw));
   a.full = true; a.ng = n_groups; a.group_medium = group_medium; a.offset = offset; a.limit = limit; a.penalties = penalties;
   a.nu = n_users; a.group = group; a.rb = retrieval_rows; a.retrieval_token = retrieval_token; a.pb = nullptr; a.P = 0;

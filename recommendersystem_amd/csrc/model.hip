@@ -389,6 +389,7 @@ int model_destroy(Model* m) {
   retrieve_tables_free(m);
   rank_free(m);
   m->ews.release();
+  for (TextSet& t : m->qtexts) t.buf.release();
   adapter_bank_free(m);
   render_free(m);
   rank_cache_free(m);

@@ -44,6 +44,32 @@ struct PhaseTimer {
   std::vector<char> open;   // per open tic: 1 = recorded, 0 = filtered out (its toc records nothing)
 };
 
+// The text queries held for one medium (rsys_query_texts_set): per text the logits z [n][ldz] over the medium's
+// items, their log-sum-exp and the weight on the device (one grow-on-demand buffer), the group on the host.
+struct TextSet {
+  DevScratch buf;
+  int n = 0; long long ldz = 0;
+  float *z = nullptr, *lse = nullptr, *d_w = nullptr;
+  std::vector<int32_t> group;
+};
+// The texts of one request or of one inner call of a pipeline: rows `row[i]` of a TextSet's device arrays, in text order, with the group
+// of the call each belongs to (host arrays; the C entry points have checked the groups against the call's, capi.hip TakenTexts, and
+// the pipelines renumber them).  n == 0: none, and the call launches what it always has.
+struct QueryTexts {
+  int n = 0;
+  const float *z = nullptr, *lse = nullptr, *d_w = nullptr; long long ldz = 0;
+  const int32_t *row = nullptr, *group = nullptr;
+};
+// per group of a call the texts' rows in text order (members) and their range in it (ranges: 2 ints per group), as GroupPlan lays users out
+inline void text_plan(const QueryTexts& qt, int ng, std::vector<int32_t>& members, std::vector<int32_t>& ranges) {
+  members.clear(); ranges.assign((size_t)2 * ng, 0);
+  for (int g = 0; g < ng; ++g) {
+    ranges[2 * g] = (int32_t)members.size();
+    for (int i = 0; i < qt.n; ++i) if (qt.group[i] == g) members.push_back(qt.row[i]);
+    ranges[2 * g + 1] = (int32_t)members.size();
+  }
+}
+
 struct RetrievalTables;  // retrieve_request.hip
 struct RankTables;       // rank_request.hip
 struct AdapterBank;      // adapter_bank.hip
@@ -271,6 +297,7 @@ struct Model {
   // rsys_query_weights_set: the weights the next request entry point consumes (host copies; have_*: that kind was given)
   std::vector<float> qw_user, qw_sel;
   bool qw_have_user = false, qw_have_sel = false;
+  TextSet qtexts[2];                    // rsys_query_texts_set: the text queries the next request entry point consumes, per medium
   DevScratch ews;                       // rsys_retrieve_target_rank's workspace
   // adapter bank of a base model (adapter_bank.hip, allocated by the first rsys_adapter_set): LoRA adapter sets in slots beside the frozen
   // trunk.  bank_rows (device, one slot or -1 per batch row) is non-null only inside rsys_infer_select_adapters: forward_trunk then adds
@@ -459,7 +486,7 @@ int model_retrieve_released_set(Model* m, int medium, const uint8_t* mask);
 int model_retrieve_request(Model* m, int medium, const float* queries, int64_t nq, const int32_t* group, int32_t ng, const int64_t* hist_off,
                            const int32_t* hist_medium, const int32_t* hist_ids, const int32_t* hist_status, const int64_t* sel_off,
                            const int32_t* sel_medium, const int32_t* sel_ids, int32_t k, int32_t* ids_out, float* scores_out,
-                           int32_t* counts_out, QueryWeights qw = {});
+                           int32_t* counts_out, QueryWeights qw = {}, QueryTexts qt = {});
 void retrieve_tables_free(Model* m);
 // the same request with its queries read from, and its result left in, device memory (rsys_render_request): d_queries [nq][D] fp32;
 // after the call *d_ids / *d_vals point at the [ng][k] result rows in the retrieval workspace (valid until the next retrieval call on the
@@ -467,13 +494,13 @@ void retrieve_tables_free(Model* m);
 struct RetrieveDev { const float* d_queries = nullptr; int32_t* d_ids = nullptr; float* d_vals = nullptr; };
 int model_retrieve_request_dev(Model* m, int medium, RetrieveDev* dev, int64_t nq, const int32_t* group, int32_t ng, const int64_t* hist_off,
                                const int32_t* hist_medium, const int32_t* hist_ids, const int32_t* hist_status, const int64_t* sel_off,
-                               const int32_t* sel_medium, const int32_t* sel_ids, int32_t k, int32_t* counts_out, QueryWeights qw = {});
+                               const int32_t* sel_medium, const int32_t* sel_ids, int32_t k, int32_t* counts_out, QueryWeights qw = {}, QueryTexts qt = {});
 // rsys_retrieve_window: the request above with a window of each group's ordering instead of its top k (RetrieveWin); dev == nullptr: the
 // rows [ng][1024] go to ids_out / scores_out (host), else they stay on the device as after model_retrieve_request_dev
 int model_retrieve_window(Model* m, int medium, const float* queries, int64_t nq, const int32_t* group, int32_t ng, const int64_t* hist_off,
                           const int32_t* hist_medium, const int32_t* hist_ids, const int32_t* hist_status, const int64_t* sel_off,
                           const int32_t* sel_medium, const int32_t* sel_ids, const RetrieveWin* win, RetrieveDev* dev, int32_t* ids_out,
-                          float* scores_out, int32_t* counts_out, QueryWeights qw = {});
+                          float* scores_out, int32_t* counts_out, QueryWeights qw = {}, QueryTexts qt = {});
 const float* retrieve_similarity_table(Model* m, int medium, int64_t* dim);   // "embeddings.{m}" [V_m][dim] on the device, or null
 // rank_request.hip: ranking and diversity reranking of retrieved candidates (rsys_rank_related_set, rsys_rank_request, test hooks)
 int model_rank_related_set(Model* m, int medium, int64_t n, const int64_t* colptr, const int32_t* rowval, const float* nzval);
@@ -481,7 +508,7 @@ int model_rank_request(Model* m, int medium, int32_t ng, const int64_t* cand_off
                        const float* penalties, const float* queries, int64_t nu, const int32_t* group, const float* r_masked, int64_t n_rm,
                        const int64_t* hist_off, const int32_t* hist_medium, const int32_t* hist_ids, const int32_t* hist_status,
                        const float* retrieval_coef, const float* rating_coefs, float rating_mean, const float* r_in, int32_t* ids_out,
-                       float* r_out, const float* user_w = nullptr);
+                       float* r_out, const float* user_w = nullptr, QueryTexts qt = {});
 int model_rank_gram(Model* m, int medium, int32_t ng, const int64_t* cand_off, const int32_t* cand_ids, float* out, int64_t n_out);
 // the same request with candidates, queries and r_masked read from device memory (rsys_render_request): d_cand [n_total] distinct ids in
 // [0, V_m) per group (a retrieval result), d_queries [nu][D], d_rm ragged over users.  Group g's page = picks [page_lo[g], page_hi[g]) of
@@ -492,7 +519,7 @@ struct RankDev { const int32_t* d_cand; const float* d_queries; const float* d_r
 int model_rank_request_dev(Model* m, int medium, int32_t ng, const int64_t* cand_off, const RankDev* dev, const int32_t* partialk,
                            const float* penalties, int64_t nu, const int32_t* group, int64_t n_rm, const int64_t* hist_off,
                            const int32_t* hist_medium, const int32_t* hist_ids, const int32_t* hist_status, const float* retrieval_coef,
-                           const float* rating_coefs, float rating_mean, const float* user_w = nullptr);
+                           const float* rating_coefs, float rating_mean, const float* user_w = nullptr, QueryTexts qt = {});
 // reranking alone on device candidates (rsys_render_items: a state without users): r = +0.0 for every candidate, no related flags
 int model_rank_items_dev(Model* m, int medium, int32_t ng, const int64_t* cand_off, const RankDev* dev, const int32_t* partialk,
                          const float* penalties);
@@ -511,12 +538,13 @@ struct RenderArgs {
   const int32_t* coef_have; const float* coefs;
   int32_t* ids_out; int64_t ids_cap; int64_t* ids_offsets; int32_t* total_out;
   QueryWeights qw;   // not a C argument: the pending weights the entry point took (user order / selected-item order of the call)
+  QueryTexts qt[2];  // not C arguments: the pending text queries the entry point took, per medium (groups of the call)
 };
 int model_render(Model* m, const RenderArgs& a);
 // rsys_render_items: a page per user-less state (windowed retrieval on the prior, reranking) in one device pipeline
 int model_render_items(Model* m, int32_t ng, const int32_t* group_medium, const int64_t* offset, const int32_t* limit, const float* penalties,
                        const int64_t* sel_off, const int32_t* sel_medium, const int32_t* sel_ids, int32_t* ids_out, int64_t ids_cap,
-                       int64_t* ids_offsets, int32_t* total_out, const float* sel_w = nullptr);
+                       int64_t* ids_offsets, int32_t* total_out, const float* sel_w = nullptr, const QueryTexts* qt = nullptr /* [2], per medium */);
 int render_debug_keep(Model* m, int on);
 int render_debug_get(Model* m, const char* key, void* out, int64_t cap, int64_t* bytes);
 void render_free(Model* m);
@@ -527,6 +555,12 @@ int op_topk(const float* scores, int64_t ld, int32_t rows, int32_t V, int32_t k,
 int op_topk_window(const float* scores, int64_t ld, int32_t rows, int32_t V, const int64_t* start, const int32_t* len, int32_t* ids,
                    float* vals, int32_t* counts, int32_t* totals, int32_t* bounds);
 int op_lse(const float* z, int64_t ldz, int32_t rows, int32_t V, float* lse);
+// the launches behind rsys_op_lse on stream s: lse[row] of z [rows][ldz] over V columns; part: rows * RETRIEVE_LSE_SPLIT float2 of scratch
+int lse_rows(const float* z, long long ldz, int rows, int V, float2* part, float* lse, hipStream_t s);
+// text queries.  search.hip: the setter behind rsys_query_texts_set.  retrieve.hip: sc[g][i] = weighted_add(sc[g][i],
+// w_t, z_t[i] - lse_t) over group g's texts in text order, one in-place launch of combine_w_kernel<false> (members / ranges: device, text_plan)
+int model_query_texts_set(Model* m, void* search, int medium, const float* x, int64_t n, const int32_t* group, const float* w);
+int retrieve_text_terms(float* sc, int ng, int V, const QueryTexts& qt, const int32_t* d_members, const int32_t* d_ranges, hipStream_t s);
 // rsys_op_query_weights: the three weighted accumulations alone, on device arrays (one section each; include/rsys_debug.h)
 int op_combine_weighted(const float* src, float* dst, int32_t ng, int32_t V, int32_t last, const float* z, int64_t ldz, const float* lse,
                         const int32_t* members, const int32_t* ranges, int32_t q0, const float* user_w);

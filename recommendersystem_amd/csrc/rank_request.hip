@@ -118,6 +118,25 @@ __global__ void __launch_bounds__(RK_THREADS) rank_score_w_kernel(const RankGrou
   rank_score_body<true>(grp, cand, z, ldz, lse, members, ranges, q0, rm, rm_off, coef, logc, have_rc, c0m, c1, first, sc, w);
 }
 
+// the text queries of a request (rsys_query_texts_set), before the users' chunks: sc[c0 + i] = +0.0, then per text of the group in text
+// order (members[range.x .. range.y): rows of z / lse / w) weighted_add(s, w_t, z_t[id] - lse_t).  No coefficient and no rating term
+// apply to a text; a group without texts gets +0.0, which is what chunk 0 starts from with first = 1.
+__global__ void __launch_bounds__(RK_THREADS) rank_text_kernel(const RankGroup* grp, const int32_t* cand, const float* z, long long ldz,
+                                                               const float* lse, const int* members, const int2* ranges, const float* w,
+                                                               float* sc) {
+  const RankGroup gd = grp[blockIdx.y];
+  const int i = blockIdx.x * RK_THREADS + threadIdx.x;
+  if (i >= gd.n) return;
+  const int2 r = ranges[blockIdx.y];
+  const int id = cand[gd.c0 + i];
+  float s = 0.f;
+  for (int t = r.x; t < r.y; ++t) {
+    const int q = members[t];
+    s = weighted_add(s, w[q], __fsub_rn(z[(long long)q * ldz + id], lse[q]));
+  }
+  sc[gd.c0 + i] = s;
+}
+
 // G_g[i][j] = sum over columns c in ascending order of E[id_i][c] * E[id_j][c] (one fmaf chain) for the 64 x 64 tile (blockIdx.y,
 // blockIdx.x) of group blockIdx.z.  Both operand tiles are gathered into LDS column-major; thread (ty, tx) owns rows 4 ty.., cols 4 tx..
 __global__ void __launch_bounds__(RK_THREADS) gram_kernel(const RankGroup* grp, const int32_t* cand, const float* E, int dim, float* G) {
@@ -382,10 +401,13 @@ static int rank_t(Model* m, int medium, int ng, const Groups& gs, const int32_t*
                   const std::vector<int32_t>& ugroup, const float* r_masked, int64_t n_rm, const std::vector<int64_t>& rm_off,
                   const std::vector<int32_t>& ent_g, const std::vector<int32_t>& ent_id, const float* retrieval_coef,
                   const float* rating_coefs, float rating_mean, const float* r_in, const float* E, int dim, int32_t* ids_out, float* r_out,
-                  const RankDev* dev, const float* user_w) {
+                  const RankDev* dev, const float* user_w, const QueryTexts& qt) {
   const int Vm = medium == 0 ? m->V0 : m->V1;
   hipStream_t s = m->stream;
   const bool score = r_in == nullptr, rerank = ids_out != nullptr || dev != nullptr;
+  const bool texts = score && qt.n > 0;   // (with r_in the texts are consumed and not read)
+  std::vector<int32_t> tmem, trng;
+  if (texts) text_plan(qt, ng, tmem, trng);
   int64_t npage = 0;
   if (dev) for (int g = 0; g < ng; ++g) npage = std::max<int64_t>(npage, dev->page_off[g] + dev->page_hi[g] - dev->page_lo[g]);
   // users of each group in user order; per chunk of RETRIEVE_CHUNK users the range of them it holds.  Only scoring reads the plan;
@@ -396,12 +418,14 @@ static int rank_t(Model* m, int medium, int ng, const Groups& gs, const int32_t*
   const int64_t nent = (int64_t)ent_g.size();
   ScoreBufs<T> b(m);
   float *d_rm, *sc, *G, *d_uw; int *d_members, *picks; int2* d_ranges; int64_t* d_rmoff; RankGroup* d_grp;
-  int32_t *d_cand, *d_sid, *d_spos, *d_eg, *d_eid, *d_plo, *d_phi, *d_page; int64_t* d_poff; unsigned *bits, *flags;
+  int32_t *d_cand, *d_sid, *d_spos, *d_eg, *d_eid, *d_plo, *d_phi, *d_page, *d_tmem, *d_trng; int64_t* d_poff; unsigned *bits, *flags;
   RC(carve_into(rank_tables(m)->ws, s, [&](Carve& c) {
     b.take(c, score ? nu : 0);
     d_members = c.take<int>(nu);
     d_ranges = c.take<int2>((size_t)std::max(nchunks, 1) * ng);
     d_uw = c.take<float>(score && user_w ? nu : 0);
+    d_tmem = c.take<int32_t>(tmem.size());
+    d_trng = c.take<int32_t>(trng.size());
     d_rm = c.take<float>(score ? n_rm : 0);
     d_rmoff = c.take<int64_t>(nu);
     d_grp = c.take<RankGroup>(ng);
@@ -434,6 +458,10 @@ static int rank_t(Model* m, int medium, int ng, const Groups& gs, const int32_t*
     if (user_w) HIP_CHECK(hipMemcpyAsync(d_uw, user_w, (size_t)nu * 4, hipMemcpyHostToDevice, s));
     HIP_CHECK(hipMemcpyAsync(d_rm, r_masked, (size_t)n_rm * 4, in_kind, s));
     HIP_CHECK(hipMemcpyAsync(d_rmoff, rm_off.data(), (size_t)nu * 8, hipMemcpyHostToDevice, s));
+    if (texts) {
+      HIP_CHECK(hipMemcpyAsync(d_tmem, tmem.data(), tmem.size() * 4, hipMemcpyHostToDevice, s));
+      HIP_CHECK(hipMemcpyAsync(d_trng, trng.data(), trng.size() * 4, hipMemcpyHostToDevice, s));
+    }
   } else {
     HIP_CHECK(hipMemcpyAsync(sc, r_in, (size_t)gs.N * 4, hipMemcpyHostToDevice, s));
   }
@@ -464,18 +492,26 @@ static int rank_t(Model* m, int medium, int ng, const Groups& gs, const int32_t*
     const float logc = logf(coef);
     const int have_rc = rating_coefs != nullptr;
     const float c0m = have_rc ? rating_coefs[0] * rating_mean : 0.f, c1 = have_rc ? rating_coefs[1] : 0.f;
+    if (texts) {   // the users' first chunk then adds to the texts' sums
+      tic(m, "rank_texts");
+      rank_text_kernel<<<dim3(RK_MAXN / RK_THREADS, ng), RK_THREADS, 0, s>>>(d_grp, d_cand, qt.z, qt.ldz, qt.lse, d_tmem, (const int2*)d_trng,
+                                                                            qt.d_w, sc);
+      RK_LAUNCH_CHECK();
+      toc(m);
+    }
     for (int ch = 0; ch < nchunks; ++ch) {
       const int q0 = ch * RETRIEVE_CHUNK, nc = (int)std::min<int64_t>(RETRIEVE_CHUNK, nu - q0);
       RC(retrieve_chunk_scores<T>(m, b.qt + (size_t)q0 * b.D, nc, q0, Fm, Vm, b.z, b.ldz, b.part, b.lse));
       tic(m, "rank_score");
       const dim3 grid(RK_MAXN / RK_THREADS, ng);
       const int2* rg = d_ranges + (size_t)ch * ng;
+      const int first = ch == 0 && !texts;
       if (user_w)
         rank_score_w_kernel<<<grid, RK_THREADS, 0, s>>>(d_grp, d_cand, b.z, b.ldz, b.lse, d_members, rg, q0, d_rm, d_rmoff, coef, logc, have_rc,
-                                                        c0m, c1, ch == 0, d_uw, sc);
+                                                        c0m, c1, first, d_uw, sc);
       else
         rank_score_kernel<<<grid, RK_THREADS, 0, s>>>(d_grp, d_cand, b.z, b.ldz, b.lse, d_members, rg, q0, d_rm, d_rmoff, coef, logc, have_rc,
-                                                      c0m, c1, ch == 0, sc);
+                                                      c0m, c1, first, sc);
       RK_LAUNCH_CHECK();
       toc(m);
     }
@@ -521,7 +557,7 @@ static int rank_request_body(Model* m, int medium, int32_t ng, const int64_t* ca
                              const float* penalties, const float* queries, int64_t nu, const int32_t* group, const float* r_masked, int64_t n_rm,
                              const int64_t* hist_off, const int32_t* hist_medium, const int32_t* hist_ids, const int32_t* hist_status,
                              const float* retrieval_coef, const float* rating_coefs, float rating_mean, const float* r_in, int32_t* ids_out,
-                             float* r_out, const RankDev* dev, const float* user_w) {
+                             float* r_out, const RankDev* dev, const float* user_w, const QueryTexts& qt = {}) {
   ARG_CHECK(medium == 0 || medium == 1, "rank_request: medium must be 0 or 1");
   ARG_CHECK(ids_out || r_out || dev, "rank_request: no output (ids_out and r_out are both NULL)");
   ARG_CHECK(nu >= 1 && nu <= RK_MAXQ, "rank_request: 1 <= n_users <= 4096");
@@ -575,27 +611,27 @@ static int rank_request_body(Model* m, int medium, int32_t ng, const int64_t* ca
   }
   HIP_CHECK(hipSetDevice(m->device));
   return m->bf16_mode ? rank_t<bf16>(m, medium, ng, gs, cand_ids, queries, nu, ugroup, r_masked, n_rm, rm_off, ent_g, ent_id, retrieval_coef,
-                                     rating_coefs, rating_mean, r_in, E, (int)dim, ids_out, r_out, dev, user_w)
+                                     rating_coefs, rating_mean, r_in, E, (int)dim, ids_out, r_out, dev, user_w, qt)
                       : rank_t<float>(m, medium, ng, gs, cand_ids, queries, nu, ugroup, r_masked, n_rm, rm_off, ent_g, ent_id, retrieval_coef,
-                                      rating_coefs, rating_mean, r_in, E, (int)dim, ids_out, r_out, dev, user_w);
+                                      rating_coefs, rating_mean, r_in, E, (int)dim, ids_out, r_out, dev, user_w, qt);
 }
 
 int model_rank_request(Model* m, int medium, int32_t ng, const int64_t* cand_off, const int32_t* cand_ids, const int32_t* partialk,
                        const float* penalties, const float* queries, int64_t nu, const int32_t* group, const float* r_masked, int64_t n_rm,
                        const int64_t* hist_off, const int32_t* hist_medium, const int32_t* hist_ids, const int32_t* hist_status,
                        const float* retrieval_coef, const float* rating_coefs, float rating_mean, const float* r_in, int32_t* ids_out,
-                       float* r_out, const float* user_w) {
+                       float* r_out, const float* user_w, QueryTexts qt) {
   return rank_request_body(m, medium, ng, cand_off, cand_ids, partialk, penalties, queries, nu, group, r_masked, n_rm, hist_off, hist_medium,
-                           hist_ids, hist_status, retrieval_coef, rating_coefs, rating_mean, r_in, ids_out, r_out, nullptr, user_w);
+                           hist_ids, hist_status, retrieval_coef, rating_coefs, rating_mean, r_in, ids_out, r_out, nullptr, user_w, qt);
 }
 
 int model_rank_request_dev(Model* m, int medium, int32_t ng, const int64_t* cand_off, const RankDev* dev, const int32_t* partialk,
                            const float* penalties, int64_t nu, const int32_t* group, int64_t n_rm, const int64_t* hist_off,
                            const int32_t* hist_medium, const int32_t* hist_ids, const int32_t* hist_status, const float* retrieval_coef,
-                           const float* rating_coefs, float rating_mean, const float* user_w) {
+                           const float* rating_coefs, float rating_mean, const float* user_w, QueryTexts qt) {
   ARG_CHECK(dev && dev->d_cand && dev->page_lo && dev->page_hi && dev->page_off && dev->page_out, "rank_request: null device buffers");
   return rank_request_body(m, medium, ng, cand_off, nullptr, partialk, penalties, nullptr, nu, group, nullptr, n_rm, hist_off, hist_medium,
-                           hist_ids, hist_status, retrieval_coef, rating_coefs, rating_mean, nullptr, nullptr, nullptr, dev, user_w);
+                           hist_ids, hist_status, retrieval_coef, rating_coefs, rating_mean, nullptr, nullptr, nullptr, dev, user_w, qt);
 }
 
 int model_rank_items_dev(Model* m, int medium, int32_t ng, const int64_t* cand_off, const RankDev* dev, const int32_t* partialk,

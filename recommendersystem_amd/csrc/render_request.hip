@@ -309,6 +309,21 @@ const float* sub_sel_weights(const std::vector<int>& groups, const int64_t* off,
   return out.data();
 }
 
+// the text queries (rsys_query_texts_set) of a subset of a request's groups, in text order: local[g] = the group's index in the inner call,
+// or -1 for a group the call does not hold.  No text left: n == 0, and the inner call launches what it always has.
+struct SubTexts { std::vector<int32_t> row, group; };
+QueryTexts sub_texts(const QueryTexts& qt, const std::vector<int>& local, SubTexts& out) {
+  out.row.clear(); out.group.clear();
+  for (int i = 0; i < qt.n; ++i) {
+    const int l = local[qt.group[i]];
+    if (l < 0) continue;
+    out.row.push_back(qt.row[i]); out.group.push_back(l);
+  }
+  QueryTexts r = qt;
+  r.n = (int)out.row.size(); r.row = out.row.data(); r.group = out.group.data();
+  return r;
+}
+
 // a group with a page: its slice [c0, c0 + n) of the candidate list, the page = picks [sidx - 1, eidx) of it
 struct Active { int g, c0, n, sidx, eidx; };
 
@@ -637,10 +652,14 @@ struct Render : RenderArgs {
       std::vector<int32_t> counts(ngm);
       std::vector<float> wu, ws;
       const QueryWeights qm{sub_weights(us, qw.user, wu), sub_sel_weights(gs, sel_off, qw.sel, ws)};
+      std::vector<int> tloc(ng, -1);
+      for (int j = 0; j < ngm; ++j) tloc[gs[j]] = j;
+      SubTexts st;
+      const QueryTexts tm = sub_texts(qt[mm], tloc, st);
       RetrieveDev rd; rd.d_queries = Qs;
       RC(model_retrieve_request_dev(m, mm, &rd, nq, lg.data(), ngm, hist_off ? h.off.data() : nullptr, hist_off ? h.a.data() : nullptr,
                                     hist_off ? h.b.data() : nullptr, hist_off ? h.c.data() : nullptr, sel_off ? sl.off.data() : nullptr,
-                                    sel_off ? sl.a.data() : nullptr, sel_off ? sl.b.data() : nullptr, k, counts.data(), qm));
+                                    sel_off ? sl.a.data() : nullptr, sel_off ? sl.b.data() : nullptr, k, counts.data(), qm, tm));
       std::vector<Win> wins;
       for (int j = 0; j < ngm; ++j) {
         const int g = gs[j];
@@ -940,10 +959,12 @@ struct Render : RenderArgs {
       const int have = coef_have ? coef_have[mm] : 0;
       const float* cf = coefs ? coefs + 4 * mm : nullptr;
       std::vector<float> wu;
+      SubTexts st;
+      const QueryTexts tm = sub_texts(qt[mm], gact, st);   // (a text of medium mm belongs to a group of medium mm)
       RC(model_rank_request_dev(m, mm, na, coff.data(), &rd, pk.data(), pen.data(), nq, lg.data(), rm_n[mm], hist_off ? h.off.data() : nullptr,
                                 hist_off ? h.a.data() : nullptr, hist_off ? h.b.data() : nullptr, hist_off ? h.c.data() : nullptr,
                                 (have & 1) ? cf : nullptr, (have & 2) ? cf + 1 : nullptr, (have & 2) ? cf[3] : 0.f,
-                                sub_weights(us, qw.user, wu)));
+                                sub_weights(us, qw.user, wu), tm));
       for (int a = 0; a < na; ++a) pages[act[a].g].assign(page.begin() + poff[a], page.begin() + poff[a] + (phi[a] - plo[a]));
       if (keep) {
         std::vector<float> hrm((size_t)rm_n[mm]);
@@ -1008,7 +1029,7 @@ int model_render(Model* m, const RenderArgs& a) {
 // one candidate list, the reranking of rsys_rank_request on zeros.  Outputs are written once both media have succeeded.
 int model_render_items(Model* m, int32_t ng, const int32_t* group_medium, const int64_t* offset, const int32_t* limit, const float* penalties,
                        const int64_t* sel_off, const int32_t* sel_medium, const int32_t* sel_ids, int32_t* ids_out, int64_t ids_cap,
-                       int64_t* ids_offsets, int32_t* total_out, const float* sel_w) {
+                       int64_t* ids_offsets, int32_t* total_out, const float* sel_w, const QueryTexts* qt) {
   ARG_CHECK(ng >= 1 && ng <= RN_MAXQ, "render_items: 1 <= n_groups <= 4096");
   ARG_CHECK(group_medium && offset && limit && penalties && ids_out && ids_offsets && total_out, "render_items: null argument");
   RC(check_ragged("render_items", LIST_SELECTED, sel_off, ng, {sel_medium, sel_ids}));
@@ -1053,9 +1074,13 @@ int model_render_items(Model* m, int32_t ng, const int32_t* group_medium, const 
     const RetrieveWin win{wstart.data(), wlen.data(), totals.data()};
     std::vector<float> ws;
     const QueryWeights qm{nullptr, sub_sel_weights(gs, sel_off, sel_w, ws)};
+    std::vector<int> tloc(ng, -1);
+    for (int j = 0; j < ngm; ++j) tloc[gs[j]] = j;
+    SubTexts st;
+    const QueryTexts tm = qt ? sub_texts(qt[mm], tloc, st) : QueryTexts{};
     RetrieveDev rd;
     RC(model_retrieve_window(m, mm, nullptr, 0, nullptr, ngm, nullptr, nullptr, nullptr, nullptr, sel_off ? sl.off.data() : nullptr,
-                             sel_off ? sl.a.data() : nullptr, sel_off ? sl.b.data() : nullptr, &win, &rd, nullptr, nullptr, counts.data(), qm));
+                             sel_off ? sl.a.data() : nullptr, sel_off ? sl.b.data() : nullptr, &win, &rd, nullptr, nullptr, counts.data(), qm, tm));
     std::vector<Win> wins;
     std::vector<int> act;
     std::vector<int64_t> coff(1, 0), poff;

@@ -932,23 +932,35 @@ int op_topk_window(const float* scores, int64_t ld, int32_t rows, int32_t V, con
   return rc;
 }
 
-// rsys_op_lse: the two log-sum-exp launches of retrieve_chunk_scores on device rows
+// the two log-sum-exp launches of retrieve_chunk_scores on device rows, stream-ordered (rsys_op_lse; the text rows of search.hip)
+int lse_rows(const float* z, long long ldz, int rows, int V, float2* part, float* lse, hipStream_t s) {
+  lse_partial_kernel<<<dim3(RT_LSE_SPLIT, rows), RT_THREADS, 0, s>>>(z, ldz, V, part);
+  if (hipGetLastError() != hipSuccess) { set_error("lse_rows: launch failed (partial)"); return RSYS_ERR_HIP; }
+  lse_final_kernel<<<(rows + 255) / 256, 256, 0, s>>>(part, RT_LSE_SPLIT, rows, 0, lse);
+  if (hipGetLastError() != hipSuccess) { set_error("lse_rows: launch failed (final)"); return RSYS_ERR_HIP; }
+  return RSYS_OK;
+}
+
+// rsys_op_lse: lse_rows on device rows
 int op_lse(const float* z, int64_t ldz, int32_t rows, int32_t V, float* lse) {
   ARG_CHECK(z && lse, "rsys_op_lse: null buffer");
   ARG_CHECK(rows >= 1 && rows <= 65535 && V >= 1 && ldz >= V, "rsys_op_lse: 1 <= rows <= 65535 (grid.y), V >= 1, ldz >= V");
   float2* part = nullptr;
   HIP_CHECK(hipMalloc(&part, (size_t)rows * RT_LSE_SPLIT * sizeof(float2)));
-  int rc = RSYS_OK;
-  lse_partial_kernel<<<dim3(RT_LSE_SPLIT, rows), RT_THREADS>>>(z, ldz, V, part);
-  if (hipGetLastError() != hipSuccess) { set_error("rsys_op_lse: launch failed (partial)"); rc = RSYS_ERR_HIP; }
-  if (rc == RSYS_OK) {
-    lse_final_kernel<<<(rows + 255) / 256, 256>>>(part, RT_LSE_SPLIT, rows, 0, lse);
-    if (hipGetLastError() != hipSuccess) { set_error("rsys_op_lse: launch failed (final)"); rc = RSYS_ERR_HIP; }
-  }
+  int rc = lse_rows(z, ldz, rows, V, part, lse, nullptr);
   const hipError_t e = hipDeviceSynchronize();
   hipFree(part);
   if (rc == RSYS_OK && e != hipSuccess) { set_error(std::string("rsys_op_lse: ") + hipGetErrorString(e)); rc = RSYS_ERR_HIP; }
   return rc;
+}
+
+// the text terms of a request (rsys_query_texts_set) onto the group score rows, in place: combine_w_kernel<false> with the texts' rows as
+// its queries (q0 = 0: z, lse and the weights are indexed by row)
+int retrieve_text_terms(float* sc, int ng, int V, const QueryTexts& qt, const int32_t* d_members, const int32_t* d_ranges, hipStream_t s) {
+  const dim3 grid((unsigned)((V + RT_ITEMS - 1) / RT_ITEMS), (unsigned)ng);
+  combine_w_kernel<false><<<grid, RT_THREADS, 0, s>>>(sc, V, sc, V, qt.z, qt.ldz, qt.lse, d_members, (const int2*)d_ranges, 0, V, nullptr, qt.d_w);
+  RT_LAUNCH_CHECK();
+  return RSYS_OK;
 }
 
 // rsys_op_query_weights, the combine section: one launch of combine_w_kernel over device arrays; the first-digit histogram of `last`

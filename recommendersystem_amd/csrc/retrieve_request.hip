@@ -312,7 +312,7 @@ int model_retrieve_released_set(Model* m, int medium, const uint8_t* mask) {
 static int retrieve_request_body(Model* m, int medium, const float* queries, RetrieveDev* dev, int64_t nq, const int32_t* group, int32_t ng,
                                  const int64_t* hist_off, const int32_t* hist_medium, const int32_t* hist_ids, const int32_t* hist_status,
                                  const int64_t* sel_off, const int32_t* sel_medium, const int32_t* sel_ids, int32_t k, int32_t* ids_out,
-                                 float* scores_out, int32_t* counts_out, const RetrieveWin* win, QueryWeights qw) {
+                                 float* scores_out, int32_t* counts_out, const RetrieveWin* win, QueryWeights qw, QueryTexts qt) {
   const char* who = win ? "retrieve_window" : "retrieve_request";
   auto msg = [who](const char* text) { return std::string(who) + ": " + text; };
   // the limits of rsys_retrieve_topk (model_retrieve_topk)
@@ -342,6 +342,9 @@ static int retrieve_request_body(Model* m, int medium, const float* queries, Ret
     qgroup[q] = group ? group[q] : (int32_t)q;
     ARG_CHECK(qgroup[q] >= 0 && qgroup[q] < ng, msg("group ids must be in [0, n_groups)"));
   }
+  // text queries (rsys_query_texts_set): their rows per group in text order
+  std::vector<int32_t> tmem, trng;
+  if (qt.n) text_plan(qt, ng, tmem, trng);
   RetrievalTables* R = tables(m);
   const MediumTables& T = R->t[medium];
   for (int kind = 0; kind < 3 && nq > 0; ++kind)
@@ -409,7 +412,7 @@ static int retrieve_request_body(Model* m, int medium, const float* queries, Ret
 
   HIP_CHECK(hipSetDevice(m->device));
   hipStream_t s = m->stream;
-  float *S, *X, *d_sw; int64_t* d_soff; int32_t *d_smed, *d_sids, *d_eq, *d_eid, *d_ef, *d_qg; unsigned* planes;
+  float *S, *X, *d_sw; int64_t* d_soff; int32_t *d_smed, *d_sids, *d_eq, *d_eid, *d_ef, *d_qg, *d_tmem, *d_trng; unsigned* planes;
   RC(carve_into(R->ws, s, [&](Carve& c) {
     S = c.take<float>(nsel ? (size_t)ng * dim : 0);
     X = c.take<float>(nsel ? (size_t)nsel * dim : 0);
@@ -421,6 +424,8 @@ static int retrieve_request_body(Model* m, int medium, const float* queries, Ret
     d_eid = c.take<int32_t>(nent);
     d_ef = c.take<int32_t>(nent);
     d_qg = c.take<int32_t>((size_t)nq);
+    d_tmem = c.take<int32_t>(tmem.size());
+    d_trng = c.take<int32_t>(trng.size());
     planes = c.take<unsigned>((size_t)slice * RR_PLANES * W);
   }));
   std::vector<int64_t> soff(sel_off ? sel_off : nullptr, sel_off ? sel_off + ng + 1 : nullptr);
@@ -438,6 +443,10 @@ static int retrieve_request_body(Model* m, int medium, const float* queries, Ret
     HIP_CHECK(hipMemcpyAsync(d_ef, ent_f.data(), (size_t)nent * 4, hipMemcpyHostToDevice, s));
   }
   if (nq) HIP_CHECK(hipMemcpyAsync(d_qg, qgroup.data(), (size_t)nq * 4, hipMemcpyHostToDevice, s));
+  if (qt.n) {
+    HIP_CHECK(hipMemcpyAsync(d_tmem, tmem.data(), tmem.size() * 4, hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(d_trng, trng.data(), trng.size() * 4, hipMemcpyHostToDevice, s));
+  }
 
   const MediumTables& T0 = R->t[0];
   const MediumTables& T1 = R->t[1];
@@ -464,6 +473,11 @@ static int retrieve_request_body(Model* m, int medium, const float* queries, Ret
       HIP_CHECK(hipMemsetAsync(sc, 0, (size_t)ng * Vm * 4, st));
     }
     toc(m);
+    if (qt.n) {   // the text terms join the prior, before the masks
+      tic(m, "retrieve_request_texts");
+      RC(retrieve_text_terms(sc, ng, Vm, qt, d_tmem, d_trng, st));
+      toc(m);
+    }
     tic(m, "retrieve_request_masks");
     static_mask_kernel<<<dim3(nbv, ng), RR_THREADS, 0, st>>>(sc, Vm, T.released);
     RR_LAUNCH_CHECK();
@@ -493,26 +507,27 @@ static int retrieve_request_body(Model* m, int medium, const float* queries, Ret
 int model_retrieve_request(Model* m, int medium, const float* queries, int64_t nq, const int32_t* group, int32_t ng, const int64_t* hist_off,
                            const int32_t* hist_medium, const int32_t* hist_ids, const int32_t* hist_status, const int64_t* sel_off,
                            const int32_t* sel_medium, const int32_t* sel_ids, int32_t k, int32_t* ids_out, float* scores_out,
-                           int32_t* counts_out, QueryWeights qw) {
+                           int32_t* counts_out, QueryWeights qw, QueryTexts qt) {
   return retrieve_request_body(m, medium, queries, nullptr, nq, group, ng, hist_off, hist_medium, hist_ids, hist_status, sel_off, sel_medium,
-                               sel_ids, k, ids_out, scores_out, counts_out, nullptr, qw);
+                               sel_ids, k, ids_out, scores_out, counts_out, nullptr, qw, qt);
 }
 
 int model_retrieve_request_dev(Model* m, int medium, RetrieveDev* dev, int64_t nq, const int32_t* group, int32_t ng, const int64_t* hist_off,
                                const int32_t* hist_medium, const int32_t* hist_ids, const int32_t* hist_status, const int64_t* sel_off,
-                               const int32_t* sel_medium, const int32_t* sel_ids, int32_t k, int32_t* counts_out, QueryWeights qw) {
+                               const int32_t* sel_medium, const int32_t* sel_ids, int32_t k, int32_t* counts_out, QueryWeights qw,
+                               QueryTexts qt) {
   ARG_CHECK(dev != nullptr, "retrieve_request: null device buffers");
   return retrieve_request_body(m, medium, nullptr, dev, nq, group, ng, hist_off, hist_medium, hist_ids, hist_status, sel_off, sel_medium,
-                               sel_ids, k, nullptr, nullptr, counts_out, nullptr, qw);
+                               sel_ids, k, nullptr, nullptr, counts_out, nullptr, qw, qt);
 }
 
 int model_retrieve_window(Model* m, int medium, const float* queries, int64_t nq, const int32_t* group, int32_t ng, const int64_t* hist_off,
                           const int32_t* hist_medium, const int32_t* hist_ids, const int32_t* hist_status, const int64_t* sel_off,
                           const int32_t* sel_medium, const int32_t* sel_ids, const RetrieveWin* win, RetrieveDev* dev, int32_t* ids_out,
-                          float* scores_out, int32_t* counts_out, QueryWeights qw) {
+                          float* scores_out, int32_t* counts_out, QueryWeights qw, QueryTexts qt) {
   ARG_CHECK(win != nullptr, "retrieve_window: null window");
   return retrieve_request_body(m, medium, queries, dev, nq, group, ng, hist_off, hist_medium, hist_ids, hist_status, sel_off, sel_medium,
-                               sel_ids, 0, ids_out, scores_out, counts_out, win, qw);
+                               sel_ids, 0, ids_out, scores_out, counts_out, win, qw, qt);
 }
 
 // rsys_op_query_weights, the selected-sum section: one launch of selected_sum_w_kernel over device arrays

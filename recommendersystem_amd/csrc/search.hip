@@ -12,6 +12,8 @@
 //   dWenc     += x^T dP through launch_gemm (K-major operands)
 //   export     E_m Wenc^T in fp32, chunks of rows, one wait at the end
 //   topk       log_softmax of the factored scores of query rows, then the selection of retrieve.hip (topk_rows)
+//   texts      the logits and lse of the 1-64 text queries of a request (rsys_query_texts_set): the projection above, then
+//              one streaming pass over E_m per tile of up to 8 texts (text_scores_kernel) instead of the 256-row GEMM and its slab
 // Every reduction runs in a fixed order: a call is bitwise reproducible.
 #include <math.h>
 #include <string.h>
@@ -188,6 +190,99 @@ __global__ void __launch_bounds__(256) search_logp_kernel(float* __restrict__ z,
   *p = search_logit(*p, expf(*ls)) - lse[row];
 }
 
+// ---- the rows of a request's text queries (rsys_query_texts_set): one to a few dozen queries, a decode shape
+constexpr int TX_THREADS = 256;
+constexpr int TX_ROWS = 4;            // items a wave scores at once (reuses each LDS read of a text four times)
+constexpr int TX_MAXTQ = 8;           // texts per workgroup (largest tile)
+constexpr int TX_LDS = 65536;         // the tile's P rows in fp32: 8 rows at D <= 2048, 4 up to 4096, 2 up to 8192 (powers of two only)
+constexpr int TX_MAXN = 64;           // texts per call
+
+// one 16-byte load of a table row as fp32 values: 4 floats, or 8 bf16 (a bf16 is the upper half of its float)
+template <typename T> struct TextVec;
+template <> struct TextVec<float> {
+  static constexpr int N = 4;
+  static __device__ __forceinline__ void load(const float* p, float (&e)[4]) {
+    const float4 q = *(const float4*)p;
+    e[0] = q.x; e[1] = q.y; e[2] = q.z; e[3] = q.w;
+  }
+};
+template <> struct TextVec<bf16> {
+  static constexpr int N = 8;
+  static __device__ __forceinline__ void load(const bf16* p, float (&e)[8]) {
+    const uint4 q = *(const uint4*)p;
+    const unsigned u[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) { e[2 * k] = __uint_as_float(u[k] << 16); e[2 * k + 1] = __uint_as_float(u[k] & 0xffff0000u); }
+  }
+};
+
+// z[t][i] = search_logit(P_t . E[i], exp(*ls)) for the TQ texts t0 + [0, TQ) of this workgroup's tile and TX_ROWS items per wave step,
+// i < V only (the padding rows of the table are never stored).  blockIdx.x = text tile, blockIdx.y = item block: the tiles of one item
+// block run side by side and read its rows of E from HBM once.  The tile's rows of P are staged in LDS as fp32; lane l sums the 16-byte
+// vectors l + 64 j (j ascending) of each product in column order, then a butterfly over the 64 lanes adds the partials: a fixed order,
+// no atomics, the same bits whatever TQ.  D % 64 == 0.
+template <typename T, int TQ>
+__global__ void __launch_bounds__(TX_THREADS) text_scores_kernel(const T* __restrict__ P, int n, const T* __restrict__ E, int V, int D,
+                                                                 int rows_per_block, const float* __restrict__ ls, float* __restrict__ z,
+                                                                 long long ldz) {
+  extern __shared__ float4 p4[];   // [TQ][D / 4]
+  constexpr int N = TextVec<T>::N, H = N / 4;
+  const int t0 = blockIdx.x * TQ, d4 = D >> 2, nv = D / N;
+  for (int t = threadIdx.x; t < TQ * nv; t += TX_THREADS) {
+    const int gg = t / nv, c = t - gg * nv;
+    float e[N];
+#pragma unroll
+    for (int k = 0; k < N; ++k) e[k] = 0.f;
+    if (t0 + gg < n) TextVec<T>::load(P + (long long)(t0 + gg) * D + (long long)c * N, e);
+#pragma unroll
+    for (int h = 0; h < H; ++h) p4[gg * d4 + c * H + h] = make_float4(e[4 * h], e[4 * h + 1], e[4 * h + 2], e[4 * h + 3]);
+  }
+  __syncthreads();
+  const float sc = expf(*ls);
+  const int w = threadIdx.x >> 6, lane = lane_id();
+  const long long rb = (long long)blockIdx.y * rows_per_block;
+  const long long rend = rb + rows_per_block < V ? rb + rows_per_block : V;
+  for (long long r0 = rb + w * TX_ROWS; r0 < rend; r0 += (TX_THREADS / 64) * TX_ROWS) {
+    float acc[TX_ROWS][TQ];
+#pragma unroll
+    for (int r = 0; r < TX_ROWS; ++r)
+#pragma unroll
+      for (int gg = 0; gg < TQ; ++gg) acc[r][gg] = 0.f;
+    const T* er[TX_ROWS];
+#pragma unroll
+    for (int r = 0; r < TX_ROWS; ++r) er[r] = E + (r0 + r < V ? r0 + r : V - 1) * D;
+    for (int c = lane; c < nv; c += 64) {
+      float e[TX_ROWS][N];
+#pragma unroll
+      for (int r = 0; r < TX_ROWS; ++r) TextVec<T>::load(er[r] + (long long)c * N, e[r]);
+#pragma unroll
+      for (int gg = 0; gg < TQ; ++gg)
+#pragma unroll
+        for (int h = 0; h < H; ++h) {
+          const float4 s = p4[gg * d4 + c * H + h];
+#pragma unroll
+          for (int r = 0; r < TX_ROWS; ++r) {
+            float a = acc[r][gg];
+            a = fmaf(e[r][4 * h], s.x, a); a = fmaf(e[r][4 * h + 1], s.y, a); a = fmaf(e[r][4 * h + 2], s.z, a); a = fmaf(e[r][4 * h + 3], s.w, a);
+            acc[r][gg] = a;
+          }
+        }
+    }
+    float out = 0.f;
+#pragma unroll
+    for (int r = 0; r < TX_ROWS; ++r)
+#pragma unroll
+      for (int gg = 0; gg < TQ; ++gg) {
+        float v = acc[r][gg];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+        if (lane == r * TQ + gg) out = v;
+      }
+    const int r = lane / TQ, gg = lane - r * TQ;
+    if (r < TX_ROWS && r0 + r < rend && t0 + gg < n) z[(long long)(t0 + gg) * ldz + r0 + r] = search_logit(out, sc);
+  }
+}
+
 }  // namespace
 
 // ------------------------------------------------------------------ the handle
@@ -260,19 +355,24 @@ static int search_upload_x(SearchModel* h, const float* x, int B, int Bpad) {
   return RSYS_OK;
 }
 
+// P = x Wenc over Bpad rows, in the operand dtype
+template <typename T>
+static int search_project(SearchModel* h, int Bpad) {
+  const bool bf = h->bf16_mode();
+  GemmParams p{};   // P[m][n] = sum_k x[m][k] Wenc[k][n]: Wenc is the K-major operand
+  p.A = h->Xt; p.lda = h->Q;
+  p.B = bf ? (const void*)h->Wsh : (const void*)h->P; p.ldb = h->D;
+  p.C = h->Pt; p.ldc = h->D; p.c_f32 = bf ? 0 : 1;
+  p.M = Bpad; p.N = h->D; p.K = h->Q; p.epi = EPI_STORE; p.alpha = 1.f; p.splitk = 1;
+  return launch_gemm<T>(p, false, false, false, true, h->stream);
+}
+
 // P = x Wenc and z = P E_m^T over Bpad rows, then the row statistics and lse of rows [0, B); with labels also the loss
 template <typename T>
 static int search_scores(SearchModel* h, int B, int Bpad, bool with_loss, bool grads, int* nsplit_out) {
   hipStream_t s = h->stream;
   const bool bf = h->bf16_mode();
-  {
-    GemmParams p{};   // P[m][n] = sum_k x[m][k] Wenc[k][n]: Wenc is the K-major operand
-    p.A = h->Xt; p.lda = h->Q;
-    p.B = bf ? (const void*)h->Wsh : (const void*)h->P; p.ldb = h->D;
-    p.C = h->Pt; p.ldc = h->D; p.c_f32 = bf ? 0 : 1;
-    p.M = Bpad; p.N = h->D; p.K = h->Q; p.epi = EPI_STORE; p.alpha = 1.f; p.splitk = 1;
-    ENC_RC(launch_gemm<T>(p, false, false, false, true, s));
-  }
+  ENC_RC(search_project<T>(h, Bpad));
   {
     GemmParams p{};   // z[m][n] = sum_k P[m][k] E[n][k]
     p.A = h->Pt; p.lda = h->D;
@@ -421,6 +521,111 @@ static int search_topk(SearchModel* h, const float* x, int nq, int k, int32_t* i
   return RSYS_OK;
 }
 
+// ---- text queries of a request
+template <typename T, int TQ>
+static int launch_text_tile(SearchModel* h, int n, const T* E, float* z) {
+  int rpb = 64;   // items per workgroup; more only where the grid's y range needs it
+  while (((long long)h->V + rpb - 1) / rpb > 65535) rpb *= 2;
+  const dim3 grid((unsigned)((n + TQ - 1) / TQ), (unsigned)((h->V + rpb - 1) / rpb));
+  text_scores_kernel<T, TQ><<<grid, TX_THREADS, (size_t)TQ * h->D * 4, h->stream>>>((const T*)h->Pt, n, E, h->V, h->D, rpb, h->ls(), z, h->V);
+  HIP_CHECK(hipGetLastError());
+  return RSYS_OK;
+}
+
+// z [n][V_m] (logits, fp32) and lse [n] of n texts x [n][Q] (host) into device memory, on the handle's stream, no wait: the upload and
+// the projection of rsys_search_topk, text_scores_kernel in tiles of TQ texts, the log-sum-exp launches of rsys_op_lse (part: n *
+// RETRIEVE_LSE_SPLIT float2).  The caller has checked x and 1 <= n <= min(64, max_batch).
+template <typename T>
+static int search_text_rows_t(SearchModel* h, const float* x, int n, float* z, float2* part, float* lse) {
+  const int Bpad = (n + 255) / 256 * 256;
+  h->last_B = 0;   // (the handle's query and projection buffers are rewritten: rsys_search_debug_get has no forward to report)
+  ENC_RC(search_upload_x<T>(h, x, n, Bpad));
+  ENC_RC(search_project<T>(h, Bpad));
+  const T* E = h->bf16_mode() ? (const T*)h->feat16 : (const T*)h->feat;
+  // the largest power of two of texts that the call can use and whose fp32 rows fit the LDS tile (D <= 8192: at least two); the same
+  // bits at every tile size
+  const int fit = std::min({TX_MAXTQ, TX_LDS / (h->D * 4), n});
+  int tq = 1;
+  while (tq * 2 <= fit) tq *= 2;
+  if (tq == 1) ENC_RC((launch_text_tile<T, 1>(h, n, E, z)));
+  else if (tq == 2) ENC_RC((launch_text_tile<T, 2>(h, n, E, z)));
+  else if (tq == 4) ENC_RC((launch_text_tile<T, 4>(h, n, E, z)));
+  else ENC_RC((launch_text_tile<T, TX_MAXTQ>(h, n, E, z)));
+  return lse_rows(z, h->V, n, h->V, part, lse, h->stream);
+}
+
+static int search_text_check(SearchModel* h, const char* who, const float* x, int64_t n) {
+  const std::string w = std::string(who) + ": ";
+  ARG_CHECK(h->has_features, w + "the search handle's features are not set (rsys_search_features_set)");
+  ARG_CHECK(x != nullptr, w + "null embeddings");
+  ARG_CHECK(n >= 1 && n <= std::min(TX_MAXN, h->maxb), w + "1 <= n_texts <= min(64, the handle's max_batch)");
+  for (long long i = 0; i < (long long)n * h->Q; ++i) ARG_CHECK(std::isfinite(x[i]), w + "the text embeddings must be finite");
+  return RSYS_OK;
+}
+
+static int search_text_rows(SearchModel* h, const float* x, int n, float* z, float2* part, float* lse) {
+  return h->bf16_mode() ? search_text_rows_t<bf16>(h, x, n, z, part, lse) : search_text_rows_t<float>(h, x, n, z, part, lse);
+}
+
+// rsys_op_text_rows: the rows alone, to the host
+static int op_text_rows(SearchModel* h, const float* x, int n, float* z_out, float* lse_out) {
+  ARG_CHECK(z_out && lse_out, "rsys_op_text_rows: null output");
+  ENC_RC(search_text_check(h, "rsys_op_text_rows", x, n));
+  HIP_CHECK(hipSetDevice(h->device));
+  DevScratch ws;
+  float *z, *lse; float2* part;
+  int rc = carve_into(ws, h->stream, [&](Carve& c) {
+    z = c.take<float>((size_t)n * h->V);
+    lse = c.take<float>(n);
+    part = c.take<float2>((size_t)n * RETRIEVE_LSE_SPLIT);
+  });
+  if (rc == RSYS_OK) rc = search_text_rows(h, x, n, z, part, lse);
+  if (rc == RSYS_OK && hipMemcpyAsync(z_out, z, (size_t)n * h->V * 4, hipMemcpyDeviceToHost, h->stream) != hipSuccess) rc = RSYS_ERR_HIP;
+  if (rc == RSYS_OK && hipMemcpyAsync(lse_out, lse, (size_t)n * 4, hipMemcpyDeviceToHost, h->stream) != hipSuccess) rc = RSYS_ERR_HIP;
+  const hipError_t e = hipStreamSynchronize(h->stream);
+  ws.release();
+  if (rc == RSYS_OK && e != hipSuccess) { set_error(std::string("rsys_op_text_rows: ") + hipGetErrorString(e)); rc = RSYS_ERR_HIP; }
+  return rc;
+}
+
+// rsys_query_texts_set: the rows of n texts into the model's buffer of `medium`, held with their groups and weights until the next
+// request entry point takes them (capi.hip: TakenTexts).  A refused call holds nothing for the medium.
+int model_query_texts_set(Model* m, void* search, int medium, const float* x, int64_t n, const int32_t* group, const float* w) {
+  ARG_CHECK(medium == 0 || medium == 1, "query_texts_set: medium must be 0 or 1");
+  TextSet& ts = m->qtexts[medium];
+  ts.n = 0; ts.group.clear();
+  if (n == 0) return RSYS_OK;
+  SearchModel* h = static_cast<SearchModel*>((EncoderCore*)search);
+  ARG_CHECK(h != nullptr, "query_texts_set: null search handle");
+  ARG_CHECK(h->device == m->device, "query_texts_set: the search handle is on another device than the model");
+  ARG_CHECK(h->V == (medium == 0 ? m->V0 : m->V1), "query_texts_set: the search handle's V_m is not the model's for this medium");
+  ENC_RC(search_text_check(h, "query_texts_set", x, n));
+  ARG_CHECK(group != nullptr, "query_texts_set: null groups");
+  std::vector<float> wv((size_t)n, 1.f);
+  if (w)
+    for (int64_t i = 0; i < n; ++i) {
+      ARG_CHECK(std::isfinite(w[i]), "query_texts_set: weights must be finite");
+      wv[i] = w[i];
+    }
+  HIP_CHECK(hipSetDevice(m->device));
+  float2* part;
+  ENC_RC(carve_into(ts.buf, m->stream, [&](Carve& c) {
+    ts.z = c.take<float>((size_t)n * h->V);
+    ts.lse = c.take<float>(n);
+    ts.d_w = c.take<float>(n);
+    part = c.take<float2>((size_t)n * RETRIEVE_LSE_SPLIT);
+  }));
+  int rc = search_text_rows(h, x, (int)n, ts.z, part, ts.lse);
+  if (rc == RSYS_OK && hipMemcpyAsync(ts.d_w, wv.data(), (size_t)n * 4, hipMemcpyHostToDevice, h->stream) != hipSuccess) {
+    set_error("query_texts_set: the copy of the weights failed"); rc = RSYS_ERR_HIP;
+  }
+  const hipError_t e = hipStreamSynchronize(h->stream);   // the one wait: the model's stream reads the rows from here on
+  if (rc == RSYS_OK && e != hipSuccess) { set_error(std::string("query_texts_set: ") + hipGetErrorString(e)); rc = RSYS_ERR_HIP; }
+  if (rc != RSYS_OK) return rc;
+  ts.n = (int)n; ts.ldz = h->V; ts.group.assign(group, group + n);
+  return RSYS_OK;
+}
+
 static int search_debug_get(SearchModel* h, const char* name, float* out, int64_t n) {
   ARG_CHECK(name && out, "rsys_search_debug_get: null argument");
   ARG_CHECK(h->last_B > 0, "rsys_search_debug_get: no forward yet");
@@ -508,6 +713,10 @@ int32_t rsys_search_export(void* hv, float* out) { ENC_HANDLE(SearchModel, hv); 
 int32_t rsys_search_topk(void* hv, const float* x, int32_t n_queries, int32_t k, int32_t* ids_out, float* logp_out) {
   ENC_HANDLE(SearchModel, hv);
   return search_topk(h, x, n_queries, k, ids_out, logp_out);
+}
+int32_t rsys_op_text_rows(void* hv, const float* x, int32_t n, float* z_out, float* lse_out) {
+  ENC_HANDLE(SearchModel, hv);
+  return op_text_rows(h, x, n, z_out, lse_out);
 }
 int32_t rsys_search_debug_get(void* hv, const char* name, float* out, int64_t n) { ENC_HANDLE(SearchModel, hv); return search_debug_get(h, name, out, n); }
 

@@ -768,6 +768,31 @@ class RecommenderModel:
         check(lib().rsys_query_weights_pending(self._h, out.ctypes.data))
         return int(out[0]), int(out[1])
 
+    def query_texts_set(self, search_model, medium, x, group, weights=None):
+        """rsys_query_texts_set: text queries for the NEXT request call on this model.  `x` (n, Q) float32 embeddings of
+        `search_model` (a SearchModel whose features are medium `medium`'s item table, on this model's device), `group` the group of the
+        consuming call per text, `weights` one finite float32 per text (None: 1.0 each).  The call scores the texts against the medium's
+        items on the device and the model holds the rows until the next request call, which consumes both media's sets.  n == 0 clears
+        the medium's set."""
+        x = np.ascontiguousarray(x, np.float32)
+        if x.ndim == 1:
+            x = x[None, :]
+        n = x.shape[0]
+        g = np.ascontiguousarray(group, np.int32).reshape(-1)
+        if g.size != n:
+            raise ValueError(f"group has {g.size} entries for {n} texts")
+        w = None if weights is None else query_weights_array(weights)
+        if w is not None and w.size != n:
+            raise ValueError(f"weights has {w.size} entries for {n} texts")
+        check(lib().rsys_query_texts_set(self._h, None if search_model is None else search_model.h, int(medium), x.ctypes.data, n,
+                                         g.ctypes.data, None if w is None else w.ctypes.data))
+
+    def query_texts_pending(self):
+        """rsys_query_texts_pending: the texts held per medium for the next request, 0 = none"""
+        out = np.zeros(2, np.int64)
+        check(lib().rsys_query_texts_pending(self._h, out.ctypes.data))
+        return int(out[0]), int(out[1])
+
     def _weights_before(self, user_weights, selected_weights):
         if user_weights is not None or selected_weights is not None:
             self.set_query_weights(user_weights, selected_weights)

@@ -193,6 +193,18 @@ class SearchModel(EncoderHandle):
         check(lib().rsys_search_topk(self.h, _ptr(x), x.shape[0], k, _ptr(ids), _ptr(lp)))
         return ids, lp
 
+    def text_rows(self, queries):
+        """rsys_op_text_rows: what rsys_query_texts_set computes for a request's text queries, to the host -- the logits
+        z (n, V_m) float32 of n <= min(64, max_batch) query embeddings over the medium's items and their log-sum-exp (n,); z - lse[:, None]
+        is `topk`'s log-probability per id, scored by the streaming kernel instead of the 256-row GEMM"""
+        x = np.ascontiguousarray(queries, np.float32)
+        if x.ndim != 2 or x.shape[1] != self.Q:
+            raise ValueError(f"SearchModel: queries must be [n][{self.Q}]")
+        z = np.zeros((x.shape[0], self.V), np.float32)
+        lse = np.zeros(x.shape[0], np.float32)
+        check(lib().rsys_op_text_rows(self.h, _ptr(x), x.shape[0], _ptr(z), _ptr(lse)))
+        return z, lse
+
     def debug(self, name, shape):
         out = np.zeros(shape, np.float32)
         check(lib().rsys_search_debug_get(self.h, name.encode(), _ptr(out), out.size))

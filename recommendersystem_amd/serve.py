@@ -687,6 +687,73 @@ def state_weights(states):
     return out[0], out[1]
 
 
+def state_texts(states, medium=None):
+    """The text queries of request states: `state["texts"] = [{"embedding": array[Q], "weight": w}, ...]`, optional, in
+    state order and text order.  Returns None when no state (of `medium`, if given) holds a text -- the library's setter is then not
+    called -- else (embeddings (n, Q) float32, group (n,) int32 = the state's index in `states`, weights (n,) float32 or None).  As in
+    `state_weights` an absent "weight" is 1.0, weights is None when no text carries the key, and a NaN or infinite weight or embedding
+    value raises."""
+    x, group, entries = [], [], []
+    for g, st in enumerate(states):
+        if medium is not None and int(st["medium"]) != medium:
+            continue
+        for t in st.get("texts", ()):
+            x.append(np.asarray(t["embedding"], np.float32).reshape(-1))
+            group.append(g)
+            entries.append(t)
+    if not x:
+        return None
+    if len({v.size for v in x}) != 1:
+        raise ValueError("text queries: the embeddings of one request must have one width")
+    x = np.stack(x)
+    if not np.isfinite(x).all():
+        raise ValueError("text queries: embeddings must be finite")
+    w = None
+    if any("weight" in e for e in entries):
+        w = np.asarray([float(e.get("weight", 1.0)) for e in entries], np.float32)
+        if not np.isfinite(w).all():
+            raise ValueError("query weights must be finite")
+    return x, np.asarray(group, np.int32), w
+
+
+def _texts_before(model, states, search, media=None):
+    """`RecommenderModel.query_texts_set` for the texts of `states`: one call per medium that has texts, with `search[medium]` (a
+    SearchModel on the medium's item table).  `media`: the media to look at (default: those of the states); groups are indices into
+    `states`.  Every medium with texts is checked against `search` before the first call, so a missing entry raises with nothing set;
+    if a later call fails, the sets of the earlier ones are cleared.  States without a "texts" entry call nothing.  Returns the media set."""
+    sets = [(m, state_texts(states, m)) for m in sorted({int(st["medium"]) for st in states} if media is None else media)]
+    sets = [(m, t) for m, t in sets if t is not None]
+    for m, _ in sets:
+        if not search or m not in search:
+            raise ValueError(f"a state of medium {m} holds text queries but `search` has no SearchModel for it")
+    done = []
+    try:
+        for m, t in sets:
+            model.query_texts_set(search[m], m, *t)
+            done.append(m)
+    except BaseException:
+        _texts_clear(model, done)
+        raise
+    return done
+
+
+def _texts_clear(model, media):
+    for m in media:
+        model.query_texts_set(None, m, np.zeros((0, 1), np.float32), np.zeros(0, np.int32))
+
+
+@contextlib.contextmanager
+def _texts(model, states, search, media=None):
+    """the texts of `states` set for the request that runs in the body, immediately before it; if the body raises before the library has
+    consumed them (a check of the Python wrapper), they are cleared, so that no later request finds them"""
+    done = _texts_before(model, states, search, media)
+    try:
+        yield
+    except BaseException:
+        _texts_clear(model, done)
+        raise
+
+
 def request_arrays(states, medium, weights=False):
     """The arguments of `RecommenderModel.retrieve_request` for render.jl request states of one medium, one group per state: the
     users' "{medium}.retrieval" embeddings (n, D), their group ids, each user's list items as (medium, matchedid, status) in list
@@ -704,13 +771,14 @@ def request_arrays(states, medium, weights=False):
     return (np.stack(q), np.asarray(group, np.int32), hist, sel) + (state_weights(states) if weights else ())
 
 
-def retrieval(model, states, k=1024, coefs=None):
+def retrieval(model, states, k=1024, coefs=None, search=None):
     """render.jl `retrieval(state)` on the device for a list of request states (`medium`, `items`, `users[*].embeds`,
     `users[*].user.items`), one group per state, on the tables of `load_retrieval_tables`: prior of the selected items, summed log
     soft-max of the users, relation / watched / selected / item-0 / unreleased masks, best first.  `coefs`: the registry's retrieval
     coefficient (adds n_users * log(coef), the order does not change; with user weights, sum of w_u * log(coef)).  Users and selected
-    items may carry a "weight" (`state_weights`).  Returns one (ids, scores) pair per state, ids 0-based
-    medium-local, at most min(k, V_m, 8192) of them."""
+    items may carry a "weight" (`state_weights`); a state may carry "texts" (`state_texts`), scored through `search` = {medium:
+    SearchModel} and added to its prior.  Returns one (ids, scores) pair per state, ids 0-based medium-local, at most min(k, V_m, 8192)
+    of them."""
     out = [None] * len(states)
     by_medium = {}
     for j, st in enumerate(states):
@@ -722,7 +790,9 @@ def retrieval(model, states, k=1024, coefs=None):
         q, group, hist, sel, uw, sw = request_arrays([states[j] for j in idx], m, weights=True)
         Vm = model.config["vocab_sizes"][f"{m}_matchedid"]
         kk = min(int(k), Vm, 8192)
-        ids, scores, counts = model.retrieve_request(q, m, kk, group=group, histories=hist, selected=sel, user_weights=uw, selected_weights=sw)
+        with _texts(model, [states[j] for j in idx], search):
+            ids, scores, counts = model.retrieve_request(q, m, kk, group=group, histories=hist, selected=sel, user_weights=uw,
+                                                         selected_weights=sw)
         members = np.bincount(group, minlength=len(idx)) if uw is None else \
             np.bincount(group, weights=uw.astype(np.float64), minlength=len(idx))
         for g, j in enumerate(idx):
@@ -747,13 +817,13 @@ def _window_arrays(states, medium, weights=False):
     return ((np.stack(q) if q else None), np.asarray(group, np.int32), hist, sel) + (state_weights(states) if weights else ())
 
 
-def retrieval_window(model, states, windows):
+def retrieval_window(model, states, windows, search=None):
     """Ranks [start, start + length) of render.jl `retrieval(state)` and its exact length (rsys_retrieve_window), for a list of request
     states with or without users: `retrieval`'s ordering without its cap of 8192 -- any start, at most 1024 ranks per call.  A state
     without users (compute.jl `/add_item`) is ordered by the item-similarity prior of its selected items alone.  `windows`: one
     (start, length) pair, or one per state.  Returns one (ids, scores, total) triple per state: the window's ids (0-based
     medium-local) and scores, best first -- fewer than `length` when the list ends inside the window, none when it starts past the end
-    -- and the number of admissible items."""
+    -- and the number of admissible items.  `search`: as in `retrieval`; a state without users is then ordered by prior + texts."""
     wins = [windows] * len(states) if np.ndim(windows) == 1 else list(windows)
     if len(wins) != len(states):
         raise ValueError(f"retrieval_window: {len(wins)} windows for {len(states)} states")
@@ -763,9 +833,10 @@ def retrieval_window(model, states, windows):
     out = [None] * len(states)
     for m, idx in _by_medium(states):
         q, group, hist, sel, uw, sw = _window_arrays([states[j] for j in idx], m, weights=True)
-        ids, scores, counts, totals = model.retrieve_window(q, m, [int(wins[j][0]) for j in idx], [int(wins[j][1]) for j in idx], group=group,
-                                                            n_groups=len(idx), histories=hist, selected=sel, user_weights=uw,
-                                                            selected_weights=sw)
+        with _texts(model, [states[j] for j in idx], search):
+            ids, scores, counts, totals = model.retrieve_window(q, m, [int(wins[j][0]) for j in idx], [int(wins[j][1]) for j in idx],
+                                                                group=group, n_groups=len(idx), histories=hist, selected=sel,
+                                                                user_weights=uw, selected_weights=sw)
         for g, j in enumerate(idx):
             n = int(counts[g])
             out[j] = (ids[g, :n].copy(), scores[g, :n].copy(), int(totals[g]))
@@ -834,19 +905,21 @@ def _by_medium(states):
     return sorted(out.items())
 
 
-def ranking(model, states, idxs, registry=None):
+def ranking(model, states, idxs, registry=None, search=None):
     """render.jl `ranking(state, idxs)` on the device for a list of states (one candidate array `idxs[j]` of 0-based medium-local ids
     per state): score = sum over the state's users, in order, of log(p_u[idxs]) + r_u, with p_u = coef * softmax(table_m . u) and
     r_u = c0 * rating_mean + c1 * "{m}.ranking" (compute_retrieval / compute_ranking; without registry coefficients p_u = softmax and
     r_u = "{m}.ranking").  Every user needs "{m}.retrieval" and "{m}.ranking" (the rating head at the candidates, `predict(...,
-    "ranking")`) in its embeds.  Returns one float32 score array per state."""
+    "ranking")`) in its embeds.  A state's "texts" (`state_texts`, scored through `search` = {medium: SearchModel}) come first: w_t *
+    log_softmax of the text at the candidates, no coefficient and no rating term.  Returns one float32 score array per state."""
     out = [None] * len(states)
     for m, js in _by_medium(states):
         sub, cand = [states[j] for j in js], [np.asarray(idxs[j]) for j in js]
         q, group, rm, hist, _, uw, _ = rank_arrays(sub, cand, weights=True)
         rc, kc, mean = _registry_coefs(registry, m)
-        _, r = model.rank_request(q, m, cand, group=group, r_masked=rm, retrieval_coef=rc, rating_coefs=kc, rating_mean=mean, rerank=False,
-                                  user_weights=uw)
+        with _texts(model, sub, search):
+            _, r = model.rank_request(q, m, cand, group=group, r_masked=rm, retrieval_coef=rc, rating_coefs=kc, rating_mean=mean,
+                                      rerank=False, user_weights=uw)
         for g, j in enumerate(js):
             out[j] = r[g]
     return out
@@ -891,12 +964,13 @@ def _penalties(st):
     return [float(p.get(k, 0.0)) for k in ("decay", "mmr_penalty", "same_series_penalty", "related_penalty")]
 
 
-def render_items(model, states, pagination):
+def render_items(model, states, pagination, search=None):
     """render.jl `render(state, pagination)` for states WITHOUT users (compute.jl:490-514 `/add_item`: pick a title, see similar
     titles) in one device call (rsys_render_items): `retrieval` is the item-similarity prior of the selected items with item 0, the
     selected and the unreleased items masked, `ranking` is zeros, `reranking!` runs on them under `state["penalties"]`.  `pagination`:
     {"offset", "limit"} or one per state.  Returns one (ids of the page, total) pair per state; total is the exact number of admissible
-    items and every offset below it has a page."""
+    items and every offset below it has a page.  A state's "texts" (`state_texts`, through `search` = {medium: SearchModel}) join the
+    prior: "search for a phrase, get a reranked page" is a state with a text and no selected item."""
     pags = [pagination] * len(states) if isinstance(pagination, dict) else list(pagination)
     if len(pags) != len(states):
         raise ValueError(f"render_items: {len(pags)} paginations for {len(states)} states")
@@ -914,11 +988,14 @@ def render_items(model, states, pagination):
         sel.append([(int(a["medium"]), int(a["matchedid"])) for a in st["items"]])
     if not states:
         return []
-    pages, totals = model.render_items(gm, off, lim, np.asarray(pen, np.float32).reshape(-1, 4), sel, selected_weights=state_weights(states)[1])
+    with _texts(model, states, search):
+        pages, totals = model.render_items(gm, off, lim, np.asarray(pen, np.float32).reshape(-1, 4), sel,
+                                           selected_weights=state_weights(states)[1])
     return [(pages[g], int(totals[g])) for g in range(len(states))]
 
 
-def render(model, states, pagination, registry=None, max_ranking_items=None, full_history=False, exact=False, trim=False, compact_top=False):
+def render(model, states, pagination, registry=None, max_ranking_items=None, full_history=False, exact=False, trim=False, compact_top=False,
+           search=None):
     """render.jl `render(state, pagination)` (lines 437-474) without the card rendering, for a list of states: `retrieval`, the page's
     slice of at most 1024 candidates, the ranking forward (`predict(..., "ranking")` in chunks of at most `max_ranking_items` candidates,
     default the model's S - S // 2; candidates are masked from each other, so chunking does not change the result of a user with a
@@ -932,10 +1009,11 @@ def render(model, states, pagination, registry=None, max_ranking_items=None, ful
     then come from `retrieval_window`, so total is the number of admissible items and every offset below it has a page (ranking and
     reranking unchanged), and states without users go through `render_items` -- every state render.jl renders.  `trim=True`: the
     ranking forwards run trimmed (`predict(..., trim=True)` / `predict_ranking_full(..., trim=True)`).  `compact_top=True`: they run
-    under rsys_serving_compact_top_set (`predict(..., compact_top=True)` / `predict_ranking_full(..., compact_top=True)`)."""
+    under rsys_serving_compact_top_set (`predict(..., compact_top=True)` / `predict_ranking_full(..., compact_top=True)`).  `search` =
+    {medium: SearchModel}: the states' "texts" (`state_texts`) reach `retrieval` / `retrieval_window` and `ranking`."""
     if compact_top:
         with _compact_top(model):
-            return render(model, states, pagination, registry, max_ranking_items, full_history, exact, trim)
+            return render(model, states, pagination, registry, max_ranking_items, full_history, exact, trim, search=search)
     pags = [pagination] * len(states) if isinstance(pagination, dict) else list(pagination)
     if exact:
         for pg in pags:
@@ -943,18 +1021,18 @@ def render(model, states, pagination, registry=None, max_ranking_items=None, ful
                 raise ValueError("pagination: 1 <= limit <= 1024 and offset >= 0")
         out = [None] * len(states)
         bare = [j for j, st in enumerate(states) if not st["users"]]
-        for j, res in zip(bare, render_items(model, [states[j] for j in bare], [pags[j] for j in bare])):
+        for j, res in zip(bare, render_items(model, [states[j] for j in bare], [pags[j] for j in bare], search)):
             out[j] = res
         rest = [j for j, st in enumerate(states) if st["users"]]
         if rest:
             for j, res in zip(rest, _render_states(model, [states[j] for j in rest], [pags[j] for j in rest], registry, max_ranking_items,
-                                                  full_history, True, trim)):
+                                                  full_history, True, trim, search)):
                 out[j] = res
         return out
-    return _render_states(model, states, pags, registry, max_ranking_items, full_history, False, trim)
+    return _render_states(model, states, pags, registry, max_ranking_items, full_history, False, trim, search)
 
 
-def _render_states(model, states, pags, registry, max_ranking_items, full_history, exact, trim=False):
+def _render_states(model, states, pags, registry, max_ranking_items, full_history, exact, trim=False, search=None):
     """`render` for states with users; exact: the page's candidates are the window of `retrieval_window` instead of a slice of the top 8192"""
     S = model.config["max_sequence_length"]
     max_user_len = S // 2
@@ -965,9 +1043,9 @@ def _render_states(model, states, pags, registry, max_ranking_items, full_histor
     work = []
     if exact:   # the ranked slice starts at a multiple of max_items_to_rank that the offset alone fixes: ask for exactly it
         mitr = [MAX_ITEMS_TO_RANK - MAX_ITEMS_TO_RANK % int(pg["limit"]) for pg in pags]
-        windows = retrieval_window(model, states, [(int(pg["offset"]) // k * k, k) for pg, k in zip(pags, mitr)])
+        windows = retrieval_window(model, states, [(int(pg["offset"]) // k * k, k) for pg, k in zip(pags, mitr)], search)
     else:
-        retrieved = retrieval(model, states, k=RETRIEVAL_CAP, coefs=None)
+        retrieved = retrieval(model, states, k=RETRIEVAL_CAP, coefs=None, search=search)
     for j, st in enumerate(states):
         if exact:
             ids, _, total = windows[j]
@@ -1001,8 +1079,9 @@ def _render_states(model, states, pags, registry, max_ranking_items, full_histor
         cand = [w[1] for w in items]
         q, group, rm, hist, pen, uw, _ = rank_arrays(sub, cand, weights=True)
         rc, kc, mean = _registry_coefs(registry, m)
-        ids, _ = model.rank_request(q, m, cand, group=group, r_masked=rm, partialk=[w[3] for w in items], penalties=pen, histories=hist,
-                                    retrieval_coef=rc, rating_coefs=kc, rating_mean=mean, user_weights=uw)
+        with _texts(model, sub, search):
+            ids, _ = model.rank_request(q, m, cand, group=group, r_masked=rm, partialk=[w[3] for w in items], penalties=pen, histories=hist,
+                                        retrieval_coef=rc, rating_coefs=kc, rating_mean=mean, user_weights=uw)
         for g, w in enumerate(items):
             out[w[0]] = (ids[g][w[2] - 1:w[3]], w[4])
     return out
@@ -1158,7 +1237,8 @@ def render_full_store_rows(n_hist, S, max_rows, slots=None):
             for row_len, placed in _plan_segments(hist[w0:w0 + slots], S, max_rows)]
 
 
-def render_users(model, states, pagination, registry=None, full_history=False, trim=False, pack=False, pack_ranking=False, compact_top=False):
+def render_users(model, states, pagination, registry=None, full_history=False, trim=False, pack=False, pack_ranking=False, compact_top=False,
+                 search=None):
     """`render` from raw histories in ONE device call (rsys_render_request): the same states, but users need no "embeds" -- the
     retrieval forward, `retrieval`, the page window, the ranking forward (every chunk row of every user, both media, in waves of the
     model's max_rows) and `ranking` + `reranking` run back to back on the device; only the pages and the totals come back.  A model built
@@ -1174,10 +1254,11 @@ def render_users(model, states, pagination, registry=None, full_history=False, t
     hold several users, in waves of up to the model's reserved cache slots (`rank_cache_pack_plan`'s store stage); pages and totals are
     unchanged.
     `compact_top=True` (rsys_serving_compact_top_set for the length of the call): every forward of the pipeline runs its last layer only
-    where its outputs are read; scores agree with the dense pipeline to rounding, so two items closer than that may swap places."""
+    where its outputs are read; scores agree with the dense pipeline to rounding, so two items closer than that may swap places.
+    `search` = {medium: SearchModel}: the states' "texts" (`state_texts`) reach the retrieval and the ranking stage of their medium."""
     if compact_top:
         with _compact_top(model):
-            return render_users(model, states, pagination, registry, full_history, trim, pack, pack_ranking)
+            return render_users(model, states, pagination, registry, full_history, trim, pack, pack_ranking, search=search)
     if not states:
         return []
     if pack_ranking and not full_history:
@@ -1193,7 +1274,8 @@ def render_users(model, states, pagination, registry=None, full_history=False, t
     if pack_ranking:
         model.serving_pack_ranking(True)
     try:
-        pages, totals = (model.render_request_full if full_history else model.render_request)(**args)
+        with _texts(model, states, search):
+            pages, totals = (model.render_request_full if full_history else model.render_request)(**args)
     finally:
         if trim:
             model.serving_trim = before

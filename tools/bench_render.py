@@ -31,6 +31,13 @@ on every user and, in case (c), on two selected items of the state's medium per 
 query weights only the unweighted arm runs, so the same command measures the commit before for an A/B across builds.
 
     python tools/bench_render.py --weights --out profiles/query_weights_bench.json
+
+--texts: serve.render_users alone on the same set-up and cases, arms in alternating blocks -- the states as they are
+(no "texts" key: rsys_query_texts_set is never called), and the same states with 1 and with 4 text queries per state, scored through a
+search handle per medium on the model's item tables (Q = 3072; the setter's scoring is inside the timed call, as a server pays it).  On a
+tree without text queries only the first arm runs, so the same command measures the commit before for an A/B across builds.
+
+    python tools/bench_render.py --texts --out profiles/query_texts_bench.json
 """
 import argparse
 import json
@@ -101,6 +108,7 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--full-history", action="store_true", help="time the staged full-history path, render_users(full_history=True) and render_users()")
     ap.add_argument("--weights", action="store_true", help="time render_users without and with query weights (no staged path)")
+    ap.add_argument("--texts", action="store_true", help="time render_users without text queries and with 1 and 4 per state (no staged path)")
     a = ap.parse_args()
     import recommendersystem_amd as ra
     from recommendersystem_amd import serve, workload
@@ -169,6 +177,9 @@ def main():
         cases = {}
     if a.weights:
         results = weights_cases(a, model, V, registry, pag, cases, rng)
+        cases = {}
+    if a.texts:
+        results = texts_cases(a, model, cfg, V, registry, pag, cases, rng)
         cases = {}
     for name, states in cases.items():
         n_users = sum(len(st["users"]) for st in states)
@@ -240,6 +251,46 @@ def weights_cases(a, model, V, registry, pag, cases, rng):
             res["weighted_over_unweighted"] = round(float(np.median(t["weighted"]) / np.median(t["unweighted"])), 4)
         results.append(res)
         print(json.dumps(res), flush=True)
+    return results
+
+
+def texts_cases(a, model, cfg, V, registry, pag, cases, rng):
+    """render_users on the states as they are against the same states with 1 and with 4 text queries each"""
+    import copy
+    from recommendersystem_amd import search, serve
+    have = hasattr(serve, "state_texts")
+    S, Q = {}, 3072
+    if have:
+        W = (rng.standard_normal((Q, cfg["embed_dim"]), dtype=np.float32) * 1.5 / np.sqrt(Q)).astype(np.float32)
+        for m in (0, 1):
+            S[m] = search.SearchModel(search.training_config({m: V[m]}, batch_size=64, embed_dim=cfg["embed_dim"], query_dim=Q), m, model,
+                                      dtype="bf16", max_batch=64)
+            S[m].param_set("encoder.weight", W)
+            S[m].param_set("logit_scale", 1.0)
+    results = []
+    for name, states in cases.items():
+        arms = {"no_texts": states}
+        for n in (1, 4) if have else ():
+            arms[f"texts_{n}"] = copy.deepcopy(states)
+            for st in arms[f"texts_{n}"]:
+                st["texts"] = [{"embedding": rng.standard_normal(Q, dtype=np.float32), "weight": [1.0, 0.5, -1.0, 2.0][i]} for i in range(n)]
+        kw = dict(search=S) if have else {}
+        t = {k: [] for k in arms}
+        got = {k: serve.render_users(model, v, pag, registry, **kw) for k, v in arms.items()}
+        blocks = 5
+        for b in range(blocks):
+            for k, v in arms.items():
+                t[k] += timed(lambda: serve.render_users(model, v, pag, registry, **kw), a.warmup if b == 0 else 1, max(a.reps // blocks, 1))
+        res = dict(case=name, shape=a.shape, S=a.seq, states=len(states), users=sum(len(st["users"]) for st in states),
+                   totals=[int(x) for _, x in got["no_texts"]], **{k: stats(v) for k, v in t.items()})
+        for k in arms:
+            if k != "no_texts":
+                res[f"{k}_pages_differ"] = bool(any(not np.array_equal(x[0], y[0]) for x, y in zip(got["no_texts"], got[k])))
+                res[f"{k}_over_no_texts"] = round(float(np.median(t[k]) / np.median(t["no_texts"])), 4)
+        results.append(res)
+        print(json.dumps(res), flush=True)
+    for s in S.values():
+        s.close()
     return results
 
 
