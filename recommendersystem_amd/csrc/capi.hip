@@ -24,18 +24,60 @@ struct rsys_optimizer { Optimizer o; };
 #define CHECK_HANDLE(h) do { if ((h) == nullptr) { set_error("null handle"); return RSYS_ERR_ARG; } } while (0)
 
 namespace {
-// The pending query weights of a model (rsys_query_weights_set) in the hands of the request entry point that consumes them: moved out
-// of the model on entry, so the model holds none again on every return path, success and error alike.
-struct TakenWeights {
+// The pending query weights (rsys_query_weights_set) and text queries (rsys_query_texts_set, both media) of a model in the hands of the
+// request entry point that consumes them: moved out of the model on entry, so the model holds none again on every return path, success
+// and error alike.  The texts' rows stay in the model's buffers, which only the next rsys_query_texts_set rewrites.  for_medium /
+// for_page check them against the call -- texts first, then weights -- and hand the call its QueryWeights / QueryTexts.
+struct PendingQueries {
   std::vector<float> user, sel;
   bool have_user, have_sel;
-  explicit TakenWeights(Model* m) : user(std::move(m->qw_user)), sel(std::move(m->qw_sel)), have_user(m->qw_have_user), have_sel(m->qw_have_sel) {
+  struct Set { QueryTexts q; std::vector<int32_t> group, row; } t[2];
+  explicit PendingQueries(Model* m) : user(std::move(m->qw_user)), sel(std::move(m->qw_sel)), have_user(m->qw_have_user), have_sel(m->qw_have_sel) {
     m->qw_user.clear(); m->qw_sel.clear();
     m->qw_have_user = m->qw_have_sel = false;
+    for (int mm = 0; mm < 2; ++mm) {
+      TextSet& ts = m->qtexts[mm];
+      Set& o = t[mm];
+      o.group = std::move(ts.group);
+      o.group.resize((size_t)ts.n);
+      o.row.resize((size_t)ts.n);
+      for (int i = 0; i < ts.n; ++i) o.row[i] = i;
+      o.q.n = ts.n; o.q.z = ts.z; o.q.lse = ts.lse; o.q.d_w = ts.d_w; o.q.ldz = ts.ldz;
+      o.q.row = o.row.data(); o.q.group = o.group.data();
+      ts.n = 0; ts.group.clear();
+    }
   }
+  // a call on one medium: a text set of the other medium is refused, every text's group must be one of the call's.  A medium or a
+  // group count the call itself will refuse is left to it: no texts are handed on.
+  int for_medium(const char* who, int medium, int64_t n_users, bool accept_sel, const int64_t* sel_off, int64_t ng, QueryWeights* qw,
+                 QueryTexts* qt) const {
+    *qt = QueryTexts{};
+    if ((t[0].q.n || t[1].q.n) && (medium == 0 || medium == 1) && ng >= 1 && ng <= 4096) {
+      ARG_CHECK(t[1 - medium].q.n == 0, std::string(who) + ": text queries are pending for a medium this call does not serve (rsys_query_texts_set)");
+      for (int32_t g : t[medium].group) ARG_CHECK(g >= 0 && g < ng, std::string(who) + ": the group of a pending text query must be in [0, n_groups)");
+      *qt = t[medium].q;
+    }
+    return check_weights(who, n_users, accept_sel, sel_off, ng, qw);
+  }
+  // a page pipeline: every text's group must be one of the call's and of the set's medium
+  int for_page(const char* who, const int32_t* group_medium, int64_t n_users, const int64_t* sel_off, int64_t ng, QueryWeights* qw,
+               QueryTexts qt[2]) const {
+    qt[0] = qt[1] = QueryTexts{};
+    if ((t[0].q.n || t[1].q.n) && group_medium != nullptr && ng >= 1 && ng <= 4096) {
+      for (int mm = 0; mm < 2; ++mm)
+        for (int32_t g : t[mm].group) {
+          ARG_CHECK(g >= 0 && g < ng, std::string(who) + ": the group of a pending text query must be in [0, n_groups)");
+          ARG_CHECK(group_medium[g] == mm, std::string(who) + ": a pending text query belongs to a group of another medium (rsys_query_texts_set)");
+        }
+      qt[0] = t[0].q; qt[1] = t[1].q;
+    }
+    return check_weights(who, n_users, true, sel_off, ng, qw);
+  }
+
+ private:
   // the counts against the call's: n_users (-1: the call accepts no user weights) and sel_off[n_groups] (accept_sel == false: the
   // call accepts no selected-item weights).  A group count the call itself will refuse is left to it: no weights are handed on.
-  int check(const char* who, int64_t n_users, bool accept_sel, const int64_t* sel_off, int64_t ng, QueryWeights* out) const {
+  int check_weights(const char* who, int64_t n_users, bool accept_sel, const int64_t* sel_off, int64_t ng, QueryWeights* out) const {
     *out = QueryWeights{};
     if (have_user) {
       ARG_CHECK(n_users >= 0, std::string(who) + ": the pending query weights hold user weights, which this call does not take");
@@ -49,49 +91,6 @@ struct TakenWeights {
       ARG_CHECK((int64_t)sel.size() == nsel, std::string(who) + ": the pending selected-item weights do not match sel_offsets[n_groups] (rsys_query_weights_set n_sel)");
       out->sel = sel.data();
     }
-    return RSYS_OK;
-  }
-};
-// The pending text queries of a model (rsys_query_texts_set), both media, in the hands of the request entry point that consumes them:
-// moved out on entry as the weights are, so the model holds none again on every return path.  The rows stay in the model's buffers,
-// which only the next rsys_query_texts_set rewrites.
-struct TakenTexts {
-  struct Set { QueryTexts q; std::vector<int32_t> group, row; } t[2];
-  explicit TakenTexts(Model* m) {
-    for (int mm = 0; mm < 2; ++mm) {
-      TextSet& ts = m->qtexts[mm];
-      Set& o = t[mm];
-      o.group = std::move(ts.group);
-      o.group.resize((size_t)ts.n);
-      o.row.resize((size_t)ts.n);
-      for (int i = 0; i < ts.n; ++i) o.row[i] = i;
-      o.q.n = ts.n; o.q.z = ts.z; o.q.lse = ts.lse; o.q.d_w = ts.d_w; o.q.ldz = ts.ldz;
-      o.q.row = o.row.data(); o.q.group = o.group.data();
-      ts.n = 0; ts.group.clear();
-    }
-  }
-  // a call on one medium: a set of the other medium is refused, every group must be one of the call's.  A medium or a group count the
-  // call itself will refuse is left to it: no texts are handed on.
-  int check(const char* who, int medium, int64_t ng, QueryTexts* out) const {
-    *out = QueryTexts{};
-    if (t[0].q.n == 0 && t[1].q.n == 0) return RSYS_OK;
-    if ((medium != 0 && medium != 1) || ng < 1 || ng > 4096) return RSYS_OK;
-    ARG_CHECK(t[1 - medium].q.n == 0, std::string(who) + ": text queries are pending for a medium this call does not serve (rsys_query_texts_set)");
-    for (int32_t g : t[medium].group) ARG_CHECK(g >= 0 && g < ng, std::string(who) + ": the group of a pending text query must be in [0, n_groups)");
-    *out = t[medium].q;
-    return RSYS_OK;
-  }
-  // a page pipeline: every text's group must be one of the call's and of the set's medium
-  int check_media(const char* who, const int32_t* group_medium, int64_t ng, QueryTexts out[2]) const {
-    out[0] = out[1] = QueryTexts{};
-    if (t[0].q.n == 0 && t[1].q.n == 0) return RSYS_OK;
-    if (group_medium == nullptr || ng < 1 || ng > 4096) return RSYS_OK;
-    for (int mm = 0; mm < 2; ++mm)
-      for (int32_t g : t[mm].group) {
-        ARG_CHECK(g >= 0 && g < ng, std::string(who) + ": the group of a pending text query must be in [0, n_groups)");
-        ARG_CHECK(group_medium[g] == mm, std::string(who) + ": a pending text query belongs to a group of another medium (rsys_query_texts_set)");
-      }
-    out[0] = t[0].q; out[1] = t[1].q;
     return RSYS_OK;
   }
 };
@@ -312,41 +311,31 @@ int32_t rsys_retrieve_request(rsys_model* h, int32_t medium, const float* querie
                               const int64_t* sel_offsets, const int32_t* sel_medium, const int32_t* sel_ids, int32_t k, int32_t* ids_out,
                               float* scores_out, int32_t* counts_out) {
   CHECK_HANDLE(h);
-  const TakenWeights tw(h->m);
-  const TakenTexts tt(h->m);
-  QueryWeights qw;
-  QueryTexts qt;
-  RC(tt.check("retrieve_request", medium, n_groups, &qt));
-  RC(tw.check("retrieve_request", n_queries, true, sel_offsets, n_groups, &qw));
-  return model_retrieve_request(h->m, medium, queries, n_queries, group, n_groups, hist_offsets, hist_medium, hist_ids, hist_status,
-                                sel_offsets, sel_medium, sel_ids, k, ids_out, scores_out, counts_out, qw, qt);
+  const PendingQueries pq(h->m);
+  Request rq{queries, n_queries, group, n_groups, {hist_offsets, hist_medium, hist_ids, hist_status}, {sel_offsets, sel_medium, sel_ids}};
+  RC(pq.for_medium("retrieve_request", medium, n_queries, true, sel_offsets, n_groups, &rq.qw, &rq.qt));
+  return model_retrieve_request(h->m, medium, rq, k, nullptr, nullptr, ids_out, scores_out, counts_out);
 }
 int32_t rsys_retrieve_window(rsys_model* h, int32_t medium, const float* queries, int64_t n_queries, const int32_t* group, int32_t n_groups,
                              const int64_t* hist_offsets, const int32_t* hist_medium, const int32_t* hist_ids, const int32_t* hist_status,
                              const int64_t* sel_offsets, const int32_t* sel_medium, const int32_t* sel_ids, const int64_t* win_start,
                              const int32_t* win_len, int32_t* ids_out, float* scores_out, int32_t* counts_out, int32_t* total_out) {
   CHECK_HANDLE(h);
-  const TakenWeights tw(h->m);
-  const TakenTexts tt(h->m);
-  QueryWeights qw;
-  QueryTexts qt;
-  RC(tt.check("retrieve_window", medium, n_groups, &qt));
-  RC(tw.check("retrieve_window", n_queries, true, sel_offsets, n_groups, &qw));
+  const PendingQueries pq(h->m);
+  Request rq{queries, n_queries, group, n_groups, {hist_offsets, hist_medium, hist_ids, hist_status}, {sel_offsets, sel_medium, sel_ids}};
+  RC(pq.for_medium("retrieve_window", medium, n_queries, true, sel_offsets, n_groups, &rq.qw, &rq.qt));
   const RetrieveWin win{win_start, win_len, total_out};
-  return model_retrieve_window(h->m, medium, queries, n_queries, group, n_groups, hist_offsets, hist_medium, hist_ids, hist_status,
-                               sel_offsets, sel_medium, sel_ids, &win, nullptr, ids_out, scores_out, counts_out, qw, qt);
+  return model_retrieve_request(h->m, medium, rq, 0, &win, nullptr, ids_out, scores_out, counts_out);
 }
 int32_t rsys_render_items(rsys_model* h, int32_t n_groups, const int32_t* group_medium, const int64_t* offset, const int32_t* limit,
                           const float* penalties, const int64_t* sel_offsets, const int32_t* sel_medium, const int32_t* sel_ids,
                           int32_t* ids_out, int64_t ids_cap, int64_t* ids_offsets, int32_t* total_out) {
   CHECK_HANDLE(h);
-  const TakenWeights tw(h->m);
-  const TakenTexts tt(h->m);
+  const PendingQueries pq(h->m);
   QueryWeights qw;
   QueryTexts qt[2];
-  RC(tt.check_media("render_items", group_medium, n_groups, qt));
-  RC(tw.check("render_items", -1, true, sel_offsets, n_groups, &qw));
-  return model_render_items(h->m, n_groups, group_medium, offset, limit, penalties, sel_offsets, sel_medium, sel_ids, ids_out, ids_cap,
+  RC(pq.for_page("render_items", group_medium, -1, sel_offsets, n_groups, &qw, qt));
+  return model_render_items(h->m, n_groups, group_medium, offset, limit, penalties, {sel_offsets, sel_medium, sel_ids}, ids_out, ids_cap,
                             ids_offsets, total_out, qw.sel, qt);
 }
 int32_t rsys_rank_related_set(rsys_model* h, int32_t medium, int64_t n, const int64_t* colptr, const int32_t* rowval, const float* nzval) {
@@ -359,15 +348,30 @@ int32_t rsys_rank_request(rsys_model* h, int32_t medium, int32_t n_groups, const
                           const int32_t* hist_ids, const int32_t* hist_status, const float* retrieval_coef, const float* rating_coefs,
                           float rating_mean, const float* r_in, int32_t* ids_out, float* r_out) {
   CHECK_HANDLE(h);
-  const TakenWeights tw(h->m);
-  const TakenTexts tt(h->m);
-  QueryWeights qw;
-  QueryTexts qt;
-  RC(tt.check("rank_request", medium, n_groups, &qt));
-  RC(tw.check("rank_request", n_users, false, nullptr, n_groups, &qw));
-  return model_rank_request(h->m, medium, n_groups, cand_offsets, cand_ids, partialk, penalties, queries, n_users, group, r_masked, n_r_masked,
-                            hist_offsets, hist_medium, hist_ids, hist_status, retrieval_coef, rating_coefs, rating_mean, r_in, ids_out, r_out,
-                            qw.user, qt);
+  const PendingQueries pq(h->m);
+  Request rq{queries, n_users, group, n_groups, {hist_offsets, hist_medium, hist_ids, hist_status}, {}};
+  RC(pq.for_medium("rank_request", medium, n_users, false, nullptr, n_groups, &rq.qw, &rq.qt));
+  const RankCands rc{cand_offsets, cand_ids, partialk, penalties, r_masked, n_r_masked, retrieval_coef, rating_coefs, rating_mean, r_in};
+  return model_rank_request(h->m, medium, rq, rc, ids_out, r_out);
+}
+// The one body of rsys_render_request (full == false) and rsys_render_request_full (full == true; no ranking prefixes): the C
+// arguments, in their order, become a RenderArgs, and the pending weights and texts join it.
+static int32_t render_page(rsys_model* h, bool full, int32_t n_groups, const int32_t* group_medium, const int64_t* offset, const int32_t* limit,
+                           const float* penalties, int64_t n_users, const int32_t* group, const rsys_batch* retrieval_rows,
+                           const int32_t* retrieval_token, const rsys_batch* ranking_prefix, int32_t prefix_stride, const int32_t* user_desc,
+                           const double* user_ts, const int32_t* adapter_slots, const HistoryList& hist, const SelectedList& sel,
+                           const int32_t* coef_have, const float* coefs, int32_t* ids_out, int64_t ids_cap, int64_t* ids_offsets,
+                           int32_t* total_out) {
+  CHECK_HANDLE(h);
+  const PendingQueries pq(h->m);
+  RenderArgs a{};
+  RC(pq.for_page("render_request", group_medium, n_users, sel.off, n_groups, &a.qw, a.qt));
+  a.full = full; a.ng = n_groups; a.group_medium = group_medium; a.offset = offset; a.limit = limit; a.penalties = penalties;
+  a.nu = n_users; a.group = group; a.rb = retrieval_rows; a.retrieval_token = retrieval_token; a.pb = ranking_prefix; a.P = prefix_stride;
+  a.user_desc = user_desc; a.user_ts = user_ts; a.slots = adapter_slots;
+  a.hist_list = hist; a.sel_list = sel; a.coef_have = coef_have; a.coefs = coefs;
+  a.ids_out = ids_out; a.ids_cap = ids_cap; a.ids_offsets = ids_offsets; a.total_out = total_out;
+  return model_render(h->m, a);
 }
 int32_t rsys_render_request(rsys_model* h, int32_t n_groups, const int32_t* group_medium, const int64_t* offset, const int32_t* limit,
                             const float* penalties, int64_t n_users, const int32_t* group, const rsys_batch* retrieval_rows,
@@ -376,19 +380,9 @@ int32_t rsys_render_request(rsys_model* h, int32_t n_groups, const int32_t* grou
                             const int32_t* hist_ids, const int32_t* hist_status, const int64_t* sel_offsets, const int32_t* sel_medium,
                             const int32_t* sel_ids, const int32_t* coef_have, const float* coefs, int32_t* ids_out, int64_t ids_cap,
                             int64_t* ids_offsets, int32_t* total_out) {
-  CHECK_HANDLE(h);
-  const TakenWeights tw(h->m);
-  const TakenTexts tt(h->m);
-  RenderArgs a{};
-  RC(tt.check_media("render_request", group_medium, n_groups, a.qt));
-  RC(tw.check("render_request", n_users, true, sel_offsets, n_groups, &a.qw));
-  a.full = false; a.ng = n_groups; a.group_medium = group_medium; a.offset = offset; a.limit = limit; a.penalties = penalties;
-  a.nu = n_users; a.group = group; a.rb = retrieval_rows; a.retrieval_token = retrieval_token; a.pb = ranking_prefix; a.P = prefix_stride;
-  a.user_desc = user_desc; a.user_ts = user_ts; a.slots = adapter_slots;
-  a.hist_off = hist_offsets; a.hist_medium = hist_medium; a.hist_ids = hist_ids; a.hist_status = hist_status;
-  a.sel_off = sel_offsets; a.sel_medium = sel_medium; a.sel_ids = sel_ids; a.coef_have = coef_have; a.coefs = coefs;
-  a.ids_out = ids_out; a.ids_cap = ids_cap; a.ids_offsets = ids_offsets; a.total_out = total_out;
-  return model_render(h->m, a);
+  return render_page(h, false, n_groups, group_medium, offset, limit, penalties, n_users, group, retrieval_rows, retrieval_token, ranking_prefix,
+                     prefix_stride, user_desc, user_ts, adapter_slots, {hist_offsets, hist_medium, hist_ids, hist_status},
+                     {sel_offsets, sel_medium, sel_ids}, coef_have, coefs, ids_out, ids_cap, ids_offsets, total_out);
 }
 int32_t rsys_render_request_full(rsys_model* h, int32_t n_groups, const int32_t* group_medium, const int64_t* offset, const int32_t* limit,
                                  const float* penalties, int64_t n_users, const int32_t* group, const rsys_batch* retrieval_rows,
@@ -396,19 +390,9 @@ int32_t rsys_render_request_full(rsys_model* h, int32_t n_groups, const int32_t*
                                  const int64_t* hist_offsets, const int32_t* hist_medium, const int32_t* hist_ids, const int32_t* hist_status,
                                  const int64_t* sel_offsets, const int32_t* sel_medium, const int32_t* sel_ids, const int32_t* coef_have,
                                  const float* coefs, int32_t* ids_out, int64_t ids_cap, int64_t* ids_offsets, int32_t* total_out) {
-  CHECK_HANDLE(h);
-  const TakenWeights tw(h->m);
-  const TakenTexts tt(h->m);
-  RenderArgs a{};
-  RC(tt.check_media("render_request", group_medium, n_groups, a.qt));
-  RC(tw.check("render_request", n_users, true, sel_offsets, n_groups, &a.qw));
-  a.full = true; a.ng = n_groups; a.group_medium = group_medium; a.offset = offset; a.limit = limit; a.penalties = penalties;
-  a.nu = n_users; a.group = group; a.rb = retrieval_rows; a.retrieval_token = retrieval_token; a.pb = nullptr; a.P = 0;
-  a.user_desc = user_desc; a.user_ts = user_ts; a.slots = adapter_slots;
-  a.hist_off = hist_offsets; a.hist_medium = hist_medium; a.hist_ids = hist_ids; a.hist_status = hist_status;
-  a.sel_off = sel_offsets; a.sel_medium = sel_medium; a.sel_ids = sel_ids; a.coef_have = coef_have; a.coefs = coefs;
-  a.ids_out = ids_out; a.ids_cap = ids_cap; a.ids_offsets = ids_offsets; a.total_out = total_out;
-  return model_render(h->m, a);
+  return render_page(h, true, n_groups, group_medium, offset, limit, penalties, n_users, group, retrieval_rows, retrieval_token, nullptr, 0,
+                     user_desc, user_ts, adapter_slots, {hist_offsets, hist_medium, hist_ids, hist_status}, {sel_offsets, sel_medium, sel_ids},
+                     coef_have, coefs, ids_out, ids_cap, ids_offsets, total_out);
 }
 int32_t rsys_render_debug_keep(rsys_model* h, int32_t on) { CHECK_HANDLE(h); return render_debug_keep(h->m, on); }
 int32_t rsys_render_debug_get(rsys_model* h, const char* key, void* out, int64_t cap, int64_t* bytes) {

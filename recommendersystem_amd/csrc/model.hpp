@@ -53,12 +53,28 @@ struct TextSet {
   std::vector<int32_t> group;
 };
 // The texts of one request or of one inner call of a pipeline: rows `row[i]` of a TextSet's device arrays, in text order, with the group
-// of the call each belongs to (host arrays; the C entry points have checked the groups against the call's, capi.hip TakenTexts, and
+// of the call each belongs to (host arrays; the C entry points have checked the groups against the call's, capi.hip PendingQueries, and
 // the pipelines renumber them).  n == 0: none, and the call launches what it always has.
 struct QueryTexts {
   int n = 0;
   const float *z = nullptr, *lse = nullptr, *d_w = nullptr; long long ldz = 0;
   const int32_t *row = nullptr, *group = nullptr;
+};
+// Query weights of one request (rsys_query_weights_set, DESIGN.md section 4zf), host arrays: user [n_queries / n_users] and sel
+// [sel.off[n_groups]], each null when that kind is unweighted -- the request then launches the unweighted kernels.  The C entry points
+// take them from the model's pending pair (capi.hip PendingQueries) and have checked the counts; inner calls pass their slices.
+struct QueryWeights { const float* user = nullptr; const float* sel = nullptr; };
+// The ragged lists of a request, host arrays with offsets [rows + 1]: the list items of every user and the selected items of every
+// group.  All null: the request has no such list.
+struct HistoryList { const int64_t* off = nullptr; const int32_t *medium = nullptr, *ids = nullptr, *status = nullptr; };
+struct SelectedList { const int64_t* off = nullptr; const int32_t *medium = nullptr, *ids = nullptr; };
+// What a serving request is handed, the same value on every path (retrieval, ranking, the stages of a page): nq users -- their queries
+// [nq][D] on the host, or null where the call reads them from the device (RetrieveDev, RankDev) or scores none --, the group of each
+// (null: user u is group u) out of ng, the two lists, the weights and the text queries.
+struct Request {
+  const float* queries = nullptr; int64_t nq = 0; const int32_t* group = nullptr; int32_t ng = 0;
+  HistoryList hist; SelectedList sel;
+  QueryWeights qw; QueryTexts qt;
 };
 // per group of a call the texts' rows in text order (members) and their range in it (ranges: 2 ints per group), as GroupPlan lays users out
 inline void text_plan(const QueryTexts& qt, int ng, std::vector<int32_t>& members, std::vector<int32_t>& ranges) {
@@ -470,10 +486,6 @@ struct RetrieveWin { const int64_t* start; const int32_t* len; int32_t* total_ou
 int model_retrieve_run(Model* m, int medium, const float* queries, int64_t nq, const int32_t* group, int32_t ng, const RetrieveInit& init,
                        int32_t k, int32_t* ids_out, float* scores_out, int32_t* counts_out, RetrieveDev* dev = nullptr,
                        const RetrieveWin* win = nullptr, const float* user_w = nullptr);
-// Query weights of one request (rsys_query_weights_set, DESIGN.md section 4zf), host arrays: user [n_queries / n_users] and sel
-// [sel_off[n_groups]], each null when that kind is unweighted -- the request then launches the unweighted kernels.  The C entry points
-// take them from the model's pending pair (query_weights_take) and have checked the counts; inner calls pass their slices.
-struct QueryWeights { const float* user = nullptr; const float* sel = nullptr; };
 // z = Q F_m^T and lse of one chunk of <= RETRIEVE_CHUNK query rows (part: nc * RETRIEVE_LSE_SPLIT float2), as rsys_retrieve_topk scores
 constexpr int RETRIEVE_CHUNK = 256, RETRIEVE_LSE_SPLIT = 64;
 template <typename T>
@@ -483,32 +495,30 @@ int model_retrieve_relations_set(Model* m, int medium, int kind, int64_t n_rows,
                                  const float* nzval);
 int model_retrieve_similarity_set(Model* m, int medium, int64_t dim, const float* emb, const float* crossproject);
 int model_retrieve_released_set(Model* m, int medium, const uint8_t* mask);
-int model_retrieve_request(Model* m, int medium, const float* queries, int64_t nq, const int32_t* group, int32_t ng, const int64_t* hist_off,
-                           const int32_t* hist_medium, const int32_t* hist_ids, const int32_t* hist_status, const int64_t* sel_off,
-                           const int32_t* sel_medium, const int32_t* sel_ids, int32_t k, int32_t* ids_out, float* scores_out,
-                           int32_t* counts_out, QueryWeights qw = {}, QueryTexts qt = {});
+// The one retrieval request: rsys_retrieve_request, rsys_retrieve_window and the retrieval stages of the page pipelines.
+// win == nullptr: the top k of every group; else a window of each group's ordering (RetrieveWin; k is not read, rows of 1024).
+// dev == nullptr: the queries are rq.queries and the rows [ng][k] go to ids_out / scores_out (host); else the queries are read from, and
+// the result is left in, device memory (RetrieveDev; ids_out / scores_out are not read) and only counts_out crosses to the host.
+int model_retrieve_request(Model* m, int medium, const Request& rq, int32_t k, const RetrieveWin* win, RetrieveDev* dev, int32_t* ids_out,
+                           float* scores_out, int32_t* counts_out);
 void retrieve_tables_free(Model* m);
-// the same request with its queries read from, and its result left in, device memory (rsys_render_request): d_queries [nq][D] fp32;
-// after the call *d_ids / *d_vals point at the [ng][k] result rows in the retrieval workspace (valid until the next retrieval call on the
-// model) and only counts_out has crossed to the host
+// d_queries [nq][D] fp32; after the call *d_ids / *d_vals point at the [ng][k] result rows in the retrieval workspace (valid until the
+// next retrieval call on the model)
 struct RetrieveDev { const float* d_queries = nullptr; int32_t* d_ids = nullptr; float* d_vals = nullptr; };
-int model_retrieve_request_dev(Model* m, int medium, RetrieveDev* dev, int64_t nq, const int32_t* group, int32_t ng, const int64_t* hist_off,
-                               const int32_t* hist_medium, const int32_t* hist_ids, const int32_t* hist_status, const int64_t* sel_off,
-                               const int32_t* sel_medium, const int32_t* sel_ids, int32_t k, int32_t* counts_out, QueryWeights qw = {}, QueryTexts qt = {});
-// rsys_retrieve_window: the request above with a window of each group's ordering instead of its top k (RetrieveWin); dev == nullptr: the
-// rows [ng][1024] go to ids_out / scores_out (host), else they stay on the device as after model_retrieve_request_dev
-int model_retrieve_window(Model* m, int medium, const float* queries, int64_t nq, const int32_t* group, int32_t ng, const int64_t* hist_off,
-                          const int32_t* hist_medium, const int32_t* hist_ids, const int32_t* hist_status, const int64_t* sel_off,
-                          const int32_t* sel_medium, const int32_t* sel_ids, const RetrieveWin* win, RetrieveDev* dev, int32_t* ids_out,
-                          float* scores_out, int32_t* counts_out, QueryWeights qw = {}, QueryTexts qt = {});
 const float* retrieve_similarity_table(Model* m, int medium, int64_t* dim);   // "embeddings.{m}" [V_m][dim] on the device, or null
 // rank_request.hip: ranking and diversity reranking of retrieved candidates (rsys_rank_related_set, rsys_rank_request, test hooks)
 int model_rank_related_set(Model* m, int medium, int64_t n, const int64_t* colptr, const int32_t* rowval, const float* nzval);
-int model_rank_request(Model* m, int medium, int32_t ng, const int64_t* cand_off, const int32_t* cand_ids, const int32_t* partialk,
-                       const float* penalties, const float* queries, int64_t nu, const int32_t* group, const float* r_masked, int64_t n_rm,
-                       const int64_t* hist_off, const int32_t* hist_medium, const int32_t* hist_ids, const int32_t* hist_status,
-                       const float* retrieval_coef, const float* rating_coefs, float rating_mean, const float* r_in, int32_t* ids_out,
-                       float* r_out, const float* user_w = nullptr, QueryTexts qt = {});
+// The candidates of a ranking request and how they are scored, host arrays: group g's candidates cand_ids[cand_off[g] .. cand_off[g + 1])
+// (null where they are on the device, RankDev), its partialk and four penalties, the users' r_masked values (n_rm of them, ragged over
+// users; null with RankDev or r_in), the coefficients (null: not given) and r_in (given: the scores themselves, nothing is scored).
+struct RankCands {
+  const int64_t* cand_off = nullptr; const int32_t* cand_ids = nullptr; const int32_t* partialk = nullptr; const float* penalties = nullptr;
+  const float* r_masked = nullptr; int64_t n_rm = 0;
+  const float* retrieval_coef = nullptr; const float* rating_coefs = nullptr; float rating_mean = 0.f;
+  const float* r_in = nullptr;
+};
+// rq: the users (rq.nq of them, rq.queries), their groups and list items; rq.sel is not read, of rq.qw only the user weights
+int model_rank_request(Model* m, int medium, const Request& rq, const RankCands& rc, int32_t* ids_out, float* r_out);
 int model_rank_gram(Model* m, int medium, int32_t ng, const int64_t* cand_off, const int32_t* cand_ids, float* out, int64_t n_out);
 // the same request with candidates, queries and r_masked read from device memory (rsys_render_request): d_cand [n_total] distinct ids in
 // [0, V_m) per group (a retrieval result), d_queries [nu][D], d_rm ragged over users.  Group g's page = picks [page_lo[g], page_hi[g]) of
@@ -516,10 +526,7 @@ int model_rank_gram(Model* m, int medium, int32_t ng, const int64_t* cand_off, c
 // scores and the picked positions.  Only those cross to the host.
 struct RankDev { const int32_t* d_cand; const float* d_queries; const float* d_rm; const int32_t *page_lo, *page_hi; const int64_t* page_off;
                  int32_t* page_out; float* keep_r; int32_t* keep_picks; };
-int model_rank_request_dev(Model* m, int medium, int32_t ng, const int64_t* cand_off, const RankDev* dev, const int32_t* partialk,
-                           const float* penalties, int64_t nu, const int32_t* group, int64_t n_rm, const int64_t* hist_off,
-                           const int32_t* hist_medium, const int32_t* hist_ids, const int32_t* hist_status, const float* retrieval_coef,
-                           const float* rating_coefs, float rating_mean, const float* user_w = nullptr, QueryTexts qt = {});
+int model_rank_request_dev(Model* m, int medium, const Request& rq, const RankCands& rc, const RankDev* dev);
 // reranking alone on device candidates (rsys_render_items: a state without users): r = +0.0 for every candidate, no related flags
 int model_rank_items_dev(Model* m, int medium, int32_t ng, const int64_t* cand_off, const RankDev* dev, const int32_t* partialk,
                          const float* penalties);
@@ -533,8 +540,7 @@ struct RenderArgs {
   int32_t ng; const int32_t* group_medium; const int64_t* offset; const int32_t* limit; const float* penalties;
   int64_t nu; const int32_t* group; const rsys_batch* rb; const int32_t* retrieval_token; const rsys_batch* pb; int32_t P;
   const int32_t* user_desc; const double* user_ts; const int32_t* slots;
-  const int64_t* hist_off; const int32_t *hist_medium, *hist_ids, *hist_status;
-  const int64_t* sel_off; const int32_t *sel_medium, *sel_ids;
+  HistoryList hist_list; SelectedList sel_list;   // (hist_offsets .. hist_status, sel_offsets .. sel_ids)
   const int32_t* coef_have; const float* coefs;
   int32_t* ids_out; int64_t ids_cap; int64_t* ids_offsets; int32_t* total_out;
   QueryWeights qw;   // not a C argument: the pending weights the entry point took (user order / selected-item order of the call)
@@ -543,8 +549,8 @@ struct RenderArgs {
 int model_render(Model* m, const RenderArgs& a);
 // rsys_render_items: a page per user-less state (windowed retrieval on the prior, reranking) in one device pipeline
 int model_render_items(Model* m, int32_t ng, const int32_t* group_medium, const int64_t* offset, const int32_t* limit, const float* penalties,
-                       const int64_t* sel_off, const int32_t* sel_medium, const int32_t* sel_ids, int32_t* ids_out, int64_t ids_cap,
-                       int64_t* ids_offsets, int32_t* total_out, const float* sel_w = nullptr, const QueryTexts* qt = nullptr /* [2], per medium */);
+                       const SelectedList& sel, int32_t* ids_out, int64_t ids_cap, int64_t* ids_offsets, int32_t* total_out,
+                       const float* sel_w = nullptr, const QueryTexts* qt = nullptr /* [2], per medium */);
 int render_debug_keep(Model* m, int on);
 int render_debug_get(Model* m, const char* key, void* out, int64_t cap, int64_t* bytes);
 void render_free(Model* m);

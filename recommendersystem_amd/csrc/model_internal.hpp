@@ -324,6 +324,17 @@ int check_ragged(const char* who, const ListKind& what, const int64_t* off, int6
 // every item's medium in {0, 1} and id in [0, V[medium]); medium == nullptr: ids in [0, V[0]).  off == nullptr: nothing to check
 int check_list_items(const char* who, const ListKind& what, const int64_t* off, int64_t n, const int32_t* medium, const int32_t* ids,
                      const int V[2]);
+// the two checks on a request's list value over n rows (users / groups), in the words of its kind
+inline int check_ragged(const char* who, const HistoryList& l, int64_t n) {
+  return check_ragged(who, LIST_HISTORY, l.off, n, {l.medium, l.ids, l.status});
+}
+inline int check_ragged(const char* who, const SelectedList& l, int64_t n) { return check_ragged(who, LIST_SELECTED, l.off, n, {l.medium, l.ids}); }
+inline int check_list_items(const char* who, const HistoryList& l, int64_t n, const int V[2]) {
+  return check_list_items(who, LIST_HISTORY, l.off, n, l.medium, l.ids, V);
+}
+inline int check_list_items(const char* who, const SelectedList& l, int64_t n, const int V[2]) {
+  return check_list_items(who, LIST_SELECTED, l.off, n, l.medium, l.ids, V);
+}
 // A host CSC matrix checked (colptr, row indices in [0, n_rows) -- `rows` is that range in the caller's words --, values finite and >= 0)
 // and reduced to the pattern of its non-zero entries: cp [n_cols + 1], rv
 int csc_nonzero_pattern(const char* who, const char* rows, int64_t n_rows, int64_t n_cols, const int64_t* colptr, const int32_t* rowval,

@@ -396,16 +396,31 @@ static int launch_gram(Model* m, const Groups& gs, const RankGroup* d_grp, const
   return RSYS_OK;
 }
 
+// the host plan of a checked request, as rank_request_body hands it to rank_t: the groups, every user's group and first r_masked value,
+// the distinct (group, id) list entries behind the related flags, the similarity table of the reranking
+struct RankPlan {
+  Groups gs;
+  std::vector<int32_t> ugroup, ent_g, ent_id;
+  std::vector<int64_t> rm_off;
+  const float* E = nullptr; int dim = 0;
+};
+
 template <typename T>
-static int rank_t(Model* m, int medium, int ng, const Groups& gs, const int32_t* cand_ids, const float* queries, int64_t nu,
-                  const std::vector<int32_t>& ugroup, const float* r_masked, int64_t n_rm, const std::vector<int64_t>& rm_off,
-                  const std::vector<int32_t>& ent_g, const std::vector<int32_t>& ent_id, const float* retrieval_coef,
-                  const float* rating_coefs, float rating_mean, const float* r_in, const float* E, int dim, int32_t* ids_out, float* r_out,
-                  const RankDev* dev, const float* user_w, const QueryTexts& qt) {
+static int rank_t(Model* m, int medium, const Request& rq, const RankCands& rc, const RankPlan& pl, int32_t* ids_out, float* r_out,
+                  const RankDev* dev) {
+  const int ng = rq.ng;
+  const int64_t nu = rq.nq, n_rm = rc.n_rm;
+  const Groups& gs = pl.gs;
+  const std::vector<int32_t>& ent_g = pl.ent_g;
+  const std::vector<int32_t>& ent_id = pl.ent_id;
+  const QueryTexts& qt = rq.qt;
+  const int32_t* cand_ids = rc.cand_ids;   // (the three inputs that a RankDev replaces, below)
+  const float* queries = rq.queries;
+  const float* r_masked = rc.r_masked;
   const int Vm = medium == 0 ? m->V0 : m->V1;
   hipStream_t s = m->stream;
-  const bool score = r_in == nullptr, rerank = ids_out != nullptr || dev != nullptr;
-  const bool texts = score && qt.n > 0;   // (with r_in the texts are consumed and not read)
+  const bool score = rc.r_in == nullptr, rerank = ids_out != nullptr || dev != nullptr;
+  const bool texts = score && qt.n > 0;   // (with rc.r_in the texts are consumed and not read)
   std::vector<int32_t> tmem, trng;
   if (texts) text_plan(qt, ng, tmem, trng);
   int64_t npage = 0;
@@ -413,7 +428,7 @@ static int rank_t(Model* m, int medium, int ng, const Groups& gs, const int32_t*
   // users of each group in user order; per chunk of RETRIEVE_CHUNK users the range of them it holds.  Only scoring reads the plan;
   // rank_request_body has checked the group ids and that no group is empty, in its own words, so group_plan's two checks cannot fail here.
   GroupPlan gp;
-  if (score) RC(group_plan("rank_request", ugroup.data(), nu, ng, RETRIEVE_CHUNK, gp));
+  if (score) RC(group_plan("rank_request", pl.ugroup.data(), nu, ng, RETRIEVE_CHUNK, gp));
   const int nchunks = gp.nchunks;
   const int64_t nent = (int64_t)ent_g.size();
   ScoreBufs<T> b(m);
@@ -423,7 +438,7 @@ static int rank_t(Model* m, int medium, int ng, const Groups& gs, const int32_t*
     b.take(c, score ? nu : 0);
     d_members = c.take<int>(nu);
     d_ranges = c.take<int2>((size_t)std::max(nchunks, 1) * ng);
-    d_uw = c.take<float>(score && user_w ? nu : 0);
+    d_uw = c.take<float>(score && rq.qw.user ? nu : 0);
     d_tmem = c.take<int32_t>(tmem.size());
     d_trng = c.take<int32_t>(trng.size());
     d_rm = c.take<float>(score ? n_rm : 0);
@@ -455,15 +470,15 @@ static int rank_t(Model* m, int medium, int ng, const Groups& gs, const int32_t*
     RC(score_upload_queries(b, queries, nu, in_kind, s));
     HIP_CHECK(hipMemcpyAsync(d_members, gp.members.data(), gp.members.size() * 4, hipMemcpyHostToDevice, s));
     HIP_CHECK(hipMemcpyAsync(d_ranges, gp.ranges.data(), gp.ranges.size() * sizeof(int2), hipMemcpyHostToDevice, s));
-    if (user_w) HIP_CHECK(hipMemcpyAsync(d_uw, user_w, (size_t)nu * 4, hipMemcpyHostToDevice, s));
+    if (rq.qw.user) HIP_CHECK(hipMemcpyAsync(d_uw, rq.qw.user, (size_t)nu * 4, hipMemcpyHostToDevice, s));
     HIP_CHECK(hipMemcpyAsync(d_rm, r_masked, (size_t)n_rm * 4, in_kind, s));
-    HIP_CHECK(hipMemcpyAsync(d_rmoff, rm_off.data(), (size_t)nu * 8, hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(d_rmoff, pl.rm_off.data(), (size_t)nu * 8, hipMemcpyHostToDevice, s));
     if (texts) {
       HIP_CHECK(hipMemcpyAsync(d_tmem, tmem.data(), tmem.size() * 4, hipMemcpyHostToDevice, s));
       HIP_CHECK(hipMemcpyAsync(d_trng, trng.data(), trng.size() * 4, hipMemcpyHostToDevice, s));
     }
   } else {
-    HIP_CHECK(hipMemcpyAsync(sc, r_in, (size_t)gs.N * 4, hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(sc, rc.r_in, (size_t)gs.N * 4, hipMemcpyHostToDevice, s));
   }
   if (rerank) {
     if (dev) {
@@ -488,10 +503,10 @@ static int rank_t(Model* m, int medium, int ng, const Groups& gs, const int32_t*
   if (score) {
     const T* Fm;
     RC(score_table_ready<T>(m, medium, &Fm));
-    const float coef = retrieval_coef ? *retrieval_coef : 1.f;
+    const float coef = rc.retrieval_coef ? *rc.retrieval_coef : 1.f;
     const float logc = logf(coef);
-    const int have_rc = rating_coefs != nullptr;
-    const float c0m = have_rc ? rating_coefs[0] * rating_mean : 0.f, c1 = have_rc ? rating_coefs[1] : 0.f;
+    const int have_rc = rc.rating_coefs != nullptr;
+    const float c0m = have_rc ? rc.rating_coefs[0] * rc.rating_mean : 0.f, c1 = have_rc ? rc.rating_coefs[1] : 0.f;
     if (texts) {   // the users' first chunk then adds to the texts' sums
       tic(m, "rank_texts");
       rank_text_kernel<<<dim3(RK_MAXN / RK_THREADS, ng), RK_THREADS, 0, s>>>(d_grp, d_cand, qt.z, qt.ldz, qt.lse, d_tmem, (const int2*)d_trng,
@@ -506,7 +521,7 @@ static int rank_t(Model* m, int medium, int ng, const Groups& gs, const int32_t*
       const dim3 grid(RK_MAXN / RK_THREADS, ng);
       const int2* rg = d_ranges + (size_t)ch * ng;
       const int first = ch == 0 && !texts;
-      if (user_w)
+      if (rq.qw.user)
         rank_score_w_kernel<<<grid, RK_THREADS, 0, s>>>(d_grp, d_cand, b.z, b.ldz, b.lse, d_members, rg, q0, d_rm, d_rmoff, coef, logc, have_rc,
                                                         c0m, c1, first, d_uw, sc);
       else
@@ -518,7 +533,7 @@ static int rank_t(Model* m, int medium, int ng, const Groups& gs, const int32_t*
   }
   if (rerank) {
     const RelCsc& rel = m->rank->related[medium];
-    RC(launch_gram(m, gs, d_grp, d_cand, E, dim, G));
+    RC(launch_gram(m, gs, d_grp, d_cand, pl.E, pl.dim, G));
     tic(m, "rank_pairs");
     pair_rows_kernel<<<dim3(RK_MAXN / RK_THREADS, ng), RK_THREADS, 0, s>>>(d_grp, d_cand, d_sid, d_spos, rel.colptr, rel.rowval, bits);
     RK_LAUNCH_CHECK();
@@ -553,85 +568,73 @@ static int rank_t(Model* m, int medium, int ng, const Groups& gs, const int32_t*
 }
 
 // the one body of rsys_rank_request and of rsys_render_request's last stage (dev != nullptr: candidates, queries and r_masked on the device)
-static int rank_request_body(Model* m, int medium, int32_t ng, const int64_t* cand_off, const int32_t* cand_ids, const int32_t* partialk,
-                             const float* penalties, const float* queries, int64_t nu, const int32_t* group, const float* r_masked, int64_t n_rm,
-                             const int64_t* hist_off, const int32_t* hist_medium, const int32_t* hist_ids, const int32_t* hist_status,
-                             const float* retrieval_coef, const float* rating_coefs, float rating_mean, const float* r_in, int32_t* ids_out,
-                             float* r_out, const RankDev* dev, const float* user_w, const QueryTexts& qt = {}) {
+static int rank_request_body(Model* m, int medium, const Request& rq, const RankCands& rc, int32_t* ids_out, float* r_out, const RankDev* dev) {
+  const int32_t ng = rq.ng;
+  const int64_t nu = rq.nq;
+  const HistoryList& hist = rq.hist;
   ARG_CHECK(medium == 0 || medium == 1, "rank_request: medium must be 0 or 1");
   ARG_CHECK(ids_out || r_out || dev, "rank_request: no output (ids_out and r_out are both NULL)");
   ARG_CHECK(nu >= 1 && nu <= RK_MAXQ, "rank_request: 1 <= n_users <= 4096");
   ARG_CHECK(ng >= 1 && ng <= nu, "rank_request: 1 <= n_groups <= n_users (every group needs a user)");
-  ARG_CHECK(group != nullptr || ng == nu, "rank_request: without `group`, n_groups must equal n_users");
-  const bool score = r_in == nullptr;
+  ARG_CHECK(rq.group != nullptr || ng == nu, "rank_request: without `group`, n_groups must equal n_users");
+  const bool score = rc.r_in == nullptr;
   if (score) {
     ARG_CHECK(!m->sharded, "rank_request: the row-sharded item table is not supported (replicated table only)");
-    ARG_CHECK(dev ? (dev->d_queries && dev->d_rm) : (queries && r_masked), "rank_request: queries and r_masked are required unless r_in is given");
+    ARG_CHECK(dev ? (dev->d_queries && dev->d_rm) : (rq.queries && rc.r_masked), "rank_request: queries and r_masked are required unless r_in is given");
   }
   const bool rerank = ids_out != nullptr || dev != nullptr;
-  if (rerank) ARG_CHECK(partialk && penalties, "rank_request: partialk and penalties are required with ids_out");
+  if (rerank) ARG_CHECK(rc.partialk && rc.penalties, "rank_request: partialk and penalties are required with ids_out");
   const int V[2] = {m->V0, m->V1};
   const int Vm = V[medium];
-  Groups gs;
-  RC(make_groups("rank_request", ng, cand_off, cand_ids, rerank ? partialk : nullptr, rerank ? penalties : nullptr, Vm, gs, dev != nullptr));
-  std::vector<int32_t> ugroup((size_t)nu);
+  RankPlan pl;
+  Groups& gs = pl.gs;
+  RC(make_groups("rank_request", ng, rc.cand_off, rc.cand_ids, rerank ? rc.partialk : nullptr, rerank ? rc.penalties : nullptr, Vm, gs, dev != nullptr));
+  std::vector<int32_t>& ugroup = pl.ugroup;
+  ugroup.resize((size_t)nu);
   std::vector<int> members(ng, 0);
-  std::vector<int64_t> rm_off((size_t)nu);
+  pl.rm_off.resize((size_t)nu);
   int64_t need = 0;
   for (int64_t u = 0; u < nu; ++u) {
-    ugroup[u] = group ? group[u] : (int32_t)u;
+    ugroup[u] = rq.group ? rq.group[u] : (int32_t)u;
     ARG_CHECK(ugroup[u] >= 0 && ugroup[u] < ng, "rank_request: group ids must be in [0, n_groups)");
     ++members[ugroup[u]];
-    rm_off[u] = need;
+    pl.rm_off[u] = need;
     need += gs.g[ugroup[u]].n;
   }
   for (int g = 0; g < ng; ++g) ARG_CHECK(members[g] > 0, "rank_request: every group needs at least one user");
-  if (score) ARG_CHECK(n_rm == need, "rank_request: r_masked must hold n_g values per user of group g (n_r_masked = their sum)");
-  RC(check_ragged("rank_request", LIST_HISTORY, hist_off, nu, {hist_medium, hist_ids, hist_status}));
-  RC(check_list_items("rank_request", LIST_HISTORY, hist_off, nu, hist_medium, hist_ids, V));
+  if (score) ARG_CHECK(rc.n_rm == need, "rank_request: r_masked must hold n_g values per user of group g (n_r_masked = their sum)");
+  RC(check_ragged("rank_request", hist, nu));
+  RC(check_list_items("rank_request", hist, nu, V));
   // related flags: every list entry of medium m whose status is not deleted / planned (render.jl:395-408 walks the whole list, not the
   // last status per item), one entry per distinct (group, id)
-  std::vector<int32_t> ent_g, ent_id;
-  if (hist_off) {
+  if (hist.off) {
     std::vector<std::pair<int32_t, int32_t>> ent;
     for (int64_t u = 0; u < nu; ++u)
-      for (int64_t j = hist_off[u]; j < hist_off[u + 1]; ++j)
-        if (hist_medium[j] == medium && hist_status[j] != ST_DELETED && hist_status[j] != ST_PLANNED) ent.emplace_back(ugroup[u], hist_ids[j]);
+      for (int64_t j = hist.off[u]; j < hist.off[u + 1]; ++j)
+        if (hist.medium[j] == medium && hist.status[j] != ST_DELETED && hist.status[j] != ST_PLANNED) ent.emplace_back(ugroup[u], hist.ids[j]);
     std::sort(ent.begin(), ent.end());
     ent.erase(std::unique(ent.begin(), ent.end()), ent.end());
-    for (const auto& e : ent) { ent_g.push_back(e.first); ent_id.push_back(e.second); }
+    for (const auto& e : ent) { pl.ent_g.push_back(e.first); pl.ent_id.push_back(e.second); }
   }
-  const float* E = nullptr;
-  int64_t dim = 0;
   if (rerank) {
-    E = retrieve_similarity_table(m, medium, &dim);
-    ARG_CHECK(E != nullptr, "rank_request: the item-similarity embeddings of the medium are not loaded (rsys_retrieve_similarity_set)");
+    int64_t dim = 0;
+    pl.E = retrieve_similarity_table(m, medium, &dim);
+    pl.dim = (int)dim;
+    ARG_CHECK(pl.E != nullptr, "rank_request: the item-similarity embeddings of the medium are not loaded (rsys_retrieve_similarity_set)");
     const RankTables* R = rank_tables(m);
     ARG_CHECK(R->related[medium].colptr != nullptr, "rank_request: the related table of the medium is not loaded (rsys_rank_related_set)");
   }
   HIP_CHECK(hipSetDevice(m->device));
-  return m->bf16_mode ? rank_t<bf16>(m, medium, ng, gs, cand_ids, queries, nu, ugroup, r_masked, n_rm, rm_off, ent_g, ent_id, retrieval_coef,
-                                     rating_coefs, rating_mean, r_in, E, (int)dim, ids_out, r_out, dev, user_w, qt)
-                      : rank_t<float>(m, medium, ng, gs, cand_ids, queries, nu, ugroup, r_masked, n_rm, rm_off, ent_g, ent_id, retrieval_coef,
-                                      rating_coefs, rating_mean, r_in, E, (int)dim, ids_out, r_out, dev, user_w, qt);
+  return m->bf16_mode ? rank_t<bf16>(m, medium, rq, rc, pl, ids_out, r_out, dev) : rank_t<float>(m, medium, rq, rc, pl, ids_out, r_out, dev);
 }
 
-int model_rank_request(Model* m, int medium, int32_t ng, const int64_t* cand_off, const int32_t* cand_ids, const int32_t* partialk,
-                       const float* penalties, const float* queries, int64_t nu, const int32_t* group, const float* r_masked, int64_t n_rm,
-                       const int64_t* hist_off, const int32_t* hist_medium, const int32_t* hist_ids, const int32_t* hist_status,
-                       const float* retrieval_coef, const float* rating_coefs, float rating_mean, const float* r_in, int32_t* ids_out,
-                       float* r_out, const float* user_w, QueryTexts qt) {
-  return rank_request_body(m, medium, ng, cand_off, cand_ids, partialk, penalties, queries, nu, group, r_masked, n_rm, hist_off, hist_medium,
-                           hist_ids, hist_status, retrieval_coef, rating_coefs, rating_mean, r_in, ids_out, r_out, nullptr, user_w, qt);
+int model_rank_request(Model* m, int medium, const Request& rq, const RankCands& rc, int32_t* ids_out, float* r_out) {
+  return rank_request_body(m, medium, rq, rc, ids_out, r_out, nullptr);
 }
 
-int model_rank_request_dev(Model* m, int medium, int32_t ng, const int64_t* cand_off, const RankDev* dev, const int32_t* partialk,
-                           const float* penalties, int64_t nu, const int32_t* group, int64_t n_rm, const int64_t* hist_off,
-                           const int32_t* hist_medium, const int32_t* hist_ids, const int32_t* hist_status, const float* retrieval_coef,
-                           const float* rating_coefs, float rating_mean, const float* user_w, QueryTexts qt) {
+int model_rank_request_dev(Model* m, int medium, const Request& rq, const RankCands& rc, const RankDev* dev) {
   ARG_CHECK(dev && dev->d_cand && dev->page_lo && dev->page_hi && dev->page_off && dev->page_out, "rank_request: null device buffers");
-  return rank_request_body(m, medium, ng, cand_off, nullptr, partialk, penalties, nullptr, nu, group, nullptr, n_rm, hist_off, hist_medium,
-                           hist_ids, hist_status, retrieval_coef, rating_coefs, rating_mean, nullptr, nullptr, nullptr, dev, user_w, qt);
+  return rank_request_body(m, medium, rq, rc, nullptr, nullptr, dev);
 }
 
 int model_rank_items_dev(Model* m, int medium, int32_t ng, const int64_t* cand_off, const RankDev* dev, const int32_t* partialk,
@@ -640,8 +643,11 @@ int model_rank_items_dev(Model* m, int medium, int32_t ng, const int64_t* cand_o
   ARG_CHECK(ng >= 1 && ng <= RK_MAXQ, "render_items: 1 <= n_groups <= 4096");
   // render.jl:354 ranks a state without users as zeros; one user without a list per group stands in for its (absent) users
   const std::vector<float> zeros((size_t)std::max<int64_t>(cand_off[ng], 1), 0.f);
-  return rank_request_body(m, medium, ng, cand_off, nullptr, partialk, penalties, nullptr, ng, nullptr, nullptr, 0, nullptr, nullptr, nullptr,
-                           nullptr, nullptr, nullptr, 0.f, zeros.data(), nullptr, nullptr, dev, nullptr);
+  Request rq;
+  rq.nq = ng; rq.ng = ng;
+  RankCands rc;
+  rc.cand_off = cand_off; rc.partialk = partialk; rc.penalties = penalties; rc.r_in = zeros.data();
+  return rank_request_body(m, medium, rq, rc, nullptr, nullptr, dev);
 }
 
 int model_rank_gram(Model* m, int medium, int32_t ng, const int64_t* cand_off, const int32_t* cand_ids, float* out, int64_t n_out) {

@@ -275,23 +275,30 @@ int render_debug_get(Model* m, const char* key, void* out, int64_t cap, int64_t*
 
 namespace {
 
-// list items / selected items of a subset of rows of a CSR, in subset order
+// The list items / selected items of a subset of a request's users / groups, in subset order: the list value an inner call is handed.
+// The vectors own its arrays, so a SubCsr outlives the inner call's stream-ordered copies.  An absent outer list gives an absent
+// subset (all null); a given one gives non-null pointers even when the subset holds no item (one padding element per array).
 struct SubCsr {
+  const bool given;
   std::vector<int64_t> off;
-  std::vector<int32_t> a, b, c;
-};
-void sub_csr(const std::vector<int>& rows, const int64_t* off, const int32_t* a, const int32_t* b, const int32_t* c, SubCsr& out) {
-  out.off.assign(1, 0);
-  for (int r : rows) {
-    for (int64_t j = off[r]; j < off[r + 1]; ++j) {
-      out.a.push_back(a[j]); out.b.push_back(b[j]);
-      if (c) out.c.push_back(c[j]);
+  std::vector<int32_t> medium, ids, status;
+  SubCsr(const std::vector<int>& rows, const SelectedList& l) : SubCsr(rows, HistoryList{l.off, l.medium, l.ids, nullptr}) {}
+  SubCsr(const std::vector<int>& rows, const HistoryList& l) : given(l.off != nullptr) {
+    if (!given) return;
+    off.assign(1, 0);
+    for (int r : rows) {
+      for (int64_t j = l.off[r]; j < l.off[r + 1]; ++j) {
+        medium.push_back(l.medium[j]); ids.push_back(l.ids[j]);
+        if (l.status) status.push_back(l.status[j]);
+      }
+      off.push_back((int64_t)medium.size());
     }
-    out.off.push_back((int64_t)out.a.size());
+    if (medium.empty()) { medium.push_back(0); ids.push_back(0); }
+    if (status.empty()) status.push_back(0);
   }
-  if (out.a.empty()) { out.a.push_back(0); out.b.push_back(0); out.c.push_back(0); }   // (non-null pointers for empty lists)
-  if (c == nullptr) out.c.assign(1, 0);
-}
+  HistoryList history() const { return given ? HistoryList{off.data(), medium.data(), ids.data(), status.data()} : HistoryList{}; }
+  SelectedList selected() const { return given ? SelectedList{off.data(), medium.data(), ids.data()} : SelectedList{}; }
+};
 // the query weights (rsys_query_weights_set) of a subset of a request, in subset order: per user, and per selected item of a subset of
 // groups.  w == nullptr: unweighted, `out` stays empty and the slice is null.
 const float* sub_weights(const std::vector<int>& users, const float* w, std::vector<float>& out) {
@@ -386,8 +393,8 @@ struct Render : RenderArgs {
     ARG_CHECK(group_medium && offset && limit && penalties && group && rb && retrieval_token && (pb || full) && user_desc && user_ts && ids_out &&
                   ids_offsets && total_out,
               "render_request: null argument");
-    RC(check_ragged("render_request", LIST_HISTORY, hist_off, nu, {hist_medium, hist_ids, hist_status}));
-    RC(check_ragged("render_request", LIST_SELECTED, sel_off, ng, {sel_medium, sel_ids}));
+    RC(check_ragged("render_request", hist_list, nu));
+    RC(check_ragged("render_request", sel_list, ng));
     ARG_CHECK(coef_have == nullptr || coefs != nullptr, "render_request: coef_have needs coefs");
     int64_t need_ids = 0;
     for (int g = 0; g < ng; ++g) {
@@ -646,20 +653,18 @@ struct Render : RenderArgs {
       RC(launch_gather_rows_plain<float>(Q, D, d_order, 0, Qs, nq, D, s));
       std::vector<int32_t> lg(nq);
       for (int i = 0; i < nq; ++i) lg[i] = gloc[group[us[i]]];
-      SubCsr h, sl;
-      if (hist_off) sub_csr(us, hist_off, hist_medium, hist_ids, hist_status, h);
-      if (sel_off) sub_csr(gs, sel_off, sel_medium, sel_ids, nullptr, sl);
+      const SubCsr h(us, hist_list), sl(gs, sel_list);
       std::vector<int32_t> counts(ngm);
       std::vector<float> wu, ws;
-      const QueryWeights qm{sub_weights(us, qw.user, wu), sub_sel_weights(gs, sel_off, qw.sel, ws)};
       std::vector<int> tloc(ng, -1);
       for (int j = 0; j < ngm; ++j) tloc[gs[j]] = j;
       SubTexts st;
-      const QueryTexts tm = sub_texts(qt[mm], tloc, st);
+      Request rq;
+      rq.nq = nq; rq.group = lg.data(); rq.ng = ngm; rq.hist = h.history(); rq.sel = sl.selected();
+      rq.qw = {sub_weights(us, qw.user, wu), sub_sel_weights(gs, sel_list.off, qw.sel, ws)};
+      rq.qt = sub_texts(qt[mm], tloc, st);
       RetrieveDev rd; rd.d_queries = Qs;
-      RC(model_retrieve_request_dev(m, mm, &rd, nq, lg.data(), ngm, hist_off ? h.off.data() : nullptr, hist_off ? h.a.data() : nullptr,
-                                    hist_off ? h.b.data() : nullptr, hist_off ? h.c.data() : nullptr, sel_off ? sl.off.data() : nullptr,
-                                    sel_off ? sl.a.data() : nullptr, sel_off ? sl.b.data() : nullptr, k, counts.data(), qm, tm));
+      RC(model_retrieve_request(m, mm, rq, k, nullptr, &rd, nullptr, nullptr, counts.data()));
       std::vector<Win> wins;
       for (int j = 0; j < ngm; ++j) {
         const int g = gs[j];
@@ -950,8 +955,7 @@ struct Render : RenderArgs {
         memcpy(&pen[4 * (size_t)a], penalties + 4 * (size_t)act[a].g, 16);
       }
       for (int i = 0; i < nq; ++i) lg[i] = gact[group[us[i]]];
-      SubCsr h;
-      if (hist_off) sub_csr(us, hist_off, hist_medium, hist_ids, hist_status, h);
+      const SubCsr h(us, hist_list);
       std::vector<int32_t> page(std::max<int64_t>(np, 1)), kp(keep ? coff[na] : 0);
       std::vector<float> kr(keep ? coff[na] : 0);
       RankDev rd{cand + act[0].c0, Qs, rm + rm_base[mm], plo.data(), phi.data(), poff.data(), page.data(), keep ? kr.data() : nullptr,
@@ -960,11 +964,15 @@ struct Render : RenderArgs {
       const float* cf = coefs ? coefs + 4 * mm : nullptr;
       std::vector<float> wu;
       SubTexts st;
-      const QueryTexts tm = sub_texts(qt[mm], gact, st);   // (a text of medium mm belongs to a group of medium mm)
-      RC(model_rank_request_dev(m, mm, na, coff.data(), &rd, pk.data(), pen.data(), nq, lg.data(), rm_n[mm], hist_off ? h.off.data() : nullptr,
-                                hist_off ? h.a.data() : nullptr, hist_off ? h.b.data() : nullptr, hist_off ? h.c.data() : nullptr,
-                                (have & 1) ? cf : nullptr, (have & 2) ? cf + 1 : nullptr, (have & 2) ? cf[3] : 0.f,
-                                sub_weights(us, qw.user, wu), tm));
+      Request rq;
+      rq.nq = nq; rq.group = lg.data(); rq.ng = na; rq.hist = h.history();
+      rq.qw.user = sub_weights(us, qw.user, wu);
+      rq.qt = sub_texts(qt[mm], gact, st);   // (a text of medium mm belongs to a group of medium mm)
+      RankCands rc;
+      rc.cand_off = coff.data(); rc.partialk = pk.data(); rc.penalties = pen.data(); rc.n_rm = rm_n[mm];
+      if (have & 1) rc.retrieval_coef = cf;
+      if (have & 2) { rc.rating_coefs = cf + 1; rc.rating_mean = cf[3]; }
+      RC(model_rank_request_dev(m, mm, rq, rc, &rd));
       for (int a = 0; a < na; ++a) pages[act[a].g].assign(page.begin() + poff[a], page.begin() + poff[a] + (phi[a] - plo[a]));
       if (keep) {
         std::vector<float> hrm((size_t)rm_n[mm]);
@@ -1028,11 +1036,11 @@ int model_render(Model* m, const RenderArgs& a) {
 // the total is known: the window's first rank does not depend on it), rsys_retrieve_window without queries, the windows gathered into
 // one candidate list, the reranking of rsys_rank_request on zeros.  Outputs are written once both media have succeeded.
 int model_render_items(Model* m, int32_t ng, const int32_t* group_medium, const int64_t* offset, const int32_t* limit, const float* penalties,
-                       const int64_t* sel_off, const int32_t* sel_medium, const int32_t* sel_ids, int32_t* ids_out, int64_t ids_cap,
-                       int64_t* ids_offsets, int32_t* total_out, const float* sel_w, const QueryTexts* qt) {
+                       const SelectedList& sel, int32_t* ids_out, int64_t ids_cap, int64_t* ids_offsets, int32_t* total_out,
+                       const float* sel_w, const QueryTexts* qt) {
   ARG_CHECK(ng >= 1 && ng <= RN_MAXQ, "render_items: 1 <= n_groups <= 4096");
   ARG_CHECK(group_medium && offset && limit && penalties && ids_out && ids_offsets && total_out, "render_items: null argument");
-  RC(check_ragged("render_items", LIST_SELECTED, sel_off, ng, {sel_medium, sel_ids}));
+  RC(check_ragged("render_items", sel, ng));
   int64_t need_ids = 0;
   std::vector<int> groups_m[2];
   for (int g = 0; g < ng; ++g) {
@@ -1069,18 +1077,18 @@ int model_render_items(Model* m, int32_t ng, const int32_t* group_medium, const 
       wstart[j] = offset[gs[j]] / mitr * mitr;
       wlen[j] = mitr;
     }
-    SubCsr sl;
-    if (sel_off) sub_csr(gs, sel_off, sel_medium, sel_ids, nullptr, sl);
+    const SubCsr sl(gs, sel);
     const RetrieveWin win{wstart.data(), wlen.data(), totals.data()};
     std::vector<float> ws;
-    const QueryWeights qm{nullptr, sub_sel_weights(gs, sel_off, sel_w, ws)};
     std::vector<int> tloc(ng, -1);
     for (int j = 0; j < ngm; ++j) tloc[gs[j]] = j;
     SubTexts st;
-    const QueryTexts tm = qt ? sub_texts(qt[mm], tloc, st) : QueryTexts{};
+    Request rq;   // (no users: every group is scored by its prior and its texts)
+    rq.ng = ngm; rq.sel = sl.selected();
+    rq.qw.sel = sub_sel_weights(gs, sel.off, sel_w, ws);
+    if (qt) rq.qt = sub_texts(qt[mm], tloc, st);
     RetrieveDev rd;
-    RC(model_retrieve_window(m, mm, nullptr, 0, nullptr, ngm, nullptr, nullptr, nullptr, nullptr, sel_off ? sl.off.data() : nullptr,
-                             sel_off ? sl.a.data() : nullptr, sel_off ? sl.b.data() : nullptr, &win, &rd, nullptr, nullptr, counts.data(), qm, tm));
+    RC(model_retrieve_request(m, mm, rq, 0, &win, &rd, nullptr, nullptr, counts.data()));
     std::vector<Win> wins;
     std::vector<int> act;
     std::vector<int64_t> coff(1, 0), poff;

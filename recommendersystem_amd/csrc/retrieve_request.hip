@@ -305,20 +305,25 @@ int model_retrieve_released_set(Model* m, int medium, const uint8_t* mask) {
   return upload((void**)&t.released, b.data(), b.size() * 4);
 }
 
-// the one body of rsys_retrieve_request, rsys_retrieve_window and the retrieval stages of rsys_render_request / rsys_render_items:
+// rsys_retrieve_request, rsys_retrieve_window and the retrieval stages of rsys_render_request / rsys_render_items (model.hpp):
 // dev == nullptr takes the queries from, and returns the result to, the host; else both stay on the device (RetrieveDev) and only the
 // counts come back.  win != nullptr: a window of each group's ordering instead of its top k (RetrieveWin); groups may then have no
 // queries -- such a group is scored by its prior alone and has no relation masks -- and nq may be 0, which needs no relation table.
-static int retrieve_request_body(Model* m, int medium, const float* queries, RetrieveDev* dev, int64_t nq, const int32_t* group, int32_t ng,
-                                 const int64_t* hist_off, const int32_t* hist_medium, const int32_t* hist_ids, const int32_t* hist_status,
-                                 const int64_t* sel_off, const int32_t* sel_medium, const int32_t* sel_ids, int32_t k, int32_t* ids_out,
-                                 float* scores_out, int32_t* counts_out, const RetrieveWin* win, QueryWeights qw, QueryTexts qt) {
+int model_retrieve_request(Model* m, int medium, const Request& rq, int32_t k, const RetrieveWin* win, RetrieveDev* dev, int32_t* ids_out,
+                           float* scores_out, int32_t* counts_out) {
+  const int64_t nq = rq.nq;
+  const int32_t ng = rq.ng;
+  const int32_t* group = rq.group;
+  const HistoryList& hist = rq.hist;
+  const SelectedList& sel = rq.sel;
+  const QueryWeights& qw = rq.qw;
+  const QueryTexts& qt = rq.qt;
   const char* who = win ? "retrieve_window" : "retrieve_request";
   auto msg = [who](const char* text) { return std::string(who) + ": " + text; };
   // the limits of rsys_retrieve_topk (model_retrieve_topk)
   ARG_CHECK(medium == 0 || medium == 1, msg("medium must be 0 or 1"));
   ARG_CHECK(!m->sharded, msg("the row-sharded item table is not supported (replicated table only)"));
-  ARG_CHECK((nq == 0 || (dev ? dev->d_queries != nullptr : queries != nullptr)) && counts_out && (dev || (ids_out && scores_out)), msg("null buffer"));
+  ARG_CHECK((nq == 0 || (dev ? dev->d_queries != nullptr : rq.queries != nullptr)) && counts_out && (dev || (ids_out && scores_out)), msg("null buffer"));
   const int Vm = medium == 0 ? m->V0 : m->V1;
   const int V[2] = {m->V0, m->V1};
   if (win) {
@@ -349,16 +354,16 @@ static int retrieve_request_body(Model* m, int medium, const float* queries, Ret
   const MediumTables& T = R->t[medium];
   for (int kind = 0; kind < 3 && nq > 0; ++kind)
     ARG_CHECK(T.rel[kind].colptr != nullptr, msg("the dependencies, recaps and adaptations of the medium must be loaded"));
-  RC(check_ragged(who, LIST_HISTORY, hist_off, nq, {hist_medium, hist_ids, hist_status}));
-  RC(check_ragged(who, LIST_SELECTED, sel_off, ng, {sel_medium, sel_ids}));
+  RC(check_ragged(who, hist, nq));
+  RC(check_ragged(who, sel, ng));
   // selected items: ranges, ids, the similarity tables they need
   int64_t nsel = 0;
-  if (sel_off) {
-    nsel = sel_off[ng];
+  if (sel.off) {
+    nsel = sel.off[ng];
     ARG_CHECK(nsel <= 65535, msg("at most 65535 selected items per call"));
-    RC(check_list_items(who, LIST_SELECTED, sel_off, ng, sel_medium, sel_ids, V));
+    RC(check_list_items(who, sel, ng, V));
     for (int64_t a = 0; a < nsel; ++a) {
-      const int am = sel_medium[a];
+      const int am = sel.medium[a];
       ARG_CHECK(R->t[am].emb != nullptr, msg("the item-similarity embeddings of a selected item's medium are not loaded"));
       if (am != medium)
         ARG_CHECK(R->t[am].cross != nullptr, msg("the crossproject of a selected item's medium is not loaded"));
@@ -366,32 +371,32 @@ static int retrieve_request_body(Model* m, int medium, const float* queries, Ret
     if (nsel) {
       ARG_CHECK(T.emb != nullptr, msg("the item-similarity embeddings of the request medium are not loaded"));
       for (int64_t a = 0; a < nsel; ++a)
-        ARG_CHECK(R->t[sel_medium[a]].dim == T.dim, msg("the item-similarity tables of the two media differ in width"));
+        ARG_CHECK(R->t[sel.medium[a]].dim == T.dim, msg("the item-similarity tables of the two media differ in width"));
     }
   }
   // list items: the last status of each (medium, id) per user (render.jl's `statuses` dict), turned into the sets it is in
   std::vector<int32_t> ent_q, ent_id, ent_f;
   std::vector<int64_t> ent_off((size_t)nq + 1, 0);
-  if (hist_off) {
-    RC(check_list_items(who, LIST_HISTORY, hist_off, nq, hist_medium, hist_ids, V));
+  if (hist.off) {
+    RC(check_list_items(who, hist, nq, V));
     const size_t nkeys = (size_t)m->V0 + m->V1;
     if (R->mark.size() != nkeys || R->tick > 0xfffffff0u) { R->mark.assign(nkeys, 0u); R->status.assign(nkeys, 0); R->tick = 0; }
     for (int64_t q = 0; q < nq; ++q) {
       const uint32_t seen = R->tick + 1, emitted = R->tick + 2;
       R->tick += 2;
-      for (int64_t j = hist_off[q]; j < hist_off[q + 1]; ++j) {
-        const size_t key = (size_t)(hist_medium[j] ? m->V0 : 0) + hist_ids[j];
+      for (int64_t j = hist.off[q]; j < hist.off[q + 1]; ++j) {
+        const size_t key = (size_t)(hist.medium[j] ? m->V0 : 0) + hist.ids[j];
         R->mark[key] = seen;
-        R->status[key] = hist_status[j];
+        R->status[key] = hist.status[j];
       }
-      for (int64_t j = hist_off[q]; j < hist_off[q + 1]; ++j) {
-        const size_t key = (size_t)(hist_medium[j] ? m->V0 : 0) + hist_ids[j];
+      for (int64_t j = hist.off[q]; j < hist.off[q + 1]; ++j) {
+        const size_t key = (size_t)(hist.medium[j] ? m->V0 : 0) + hist.ids[j];
         if (R->mark[key] != seen) continue;
         R->mark[key] = emitted;
         const int s = R->status[key];
         const bool watched = s != ST_DELETED && s != ST_PLANNED;
         int f = 0;
-        if (hist_medium[j] == medium) {
+        if (hist.medium[j] == medium) {
           if (watched) f |= F_WM;
           if (s >= ST_COMPLETED) f |= F_CM;
           if (s == ST_WATCHING || s == ST_DROPPED || s == ST_WONT_WATCH) f |= F_KM;
@@ -399,7 +404,7 @@ static int retrieve_request_body(Model* m, int medium, const float* queries, Ret
           f |= F_WO;
         }
         if (!f) continue;
-        ent_q.push_back((int32_t)q); ent_id.push_back(hist_ids[j]); ent_f.push_back(f);
+        ent_q.push_back((int32_t)q); ent_id.push_back(hist.ids[j]); ent_f.push_back(f);
       }
       ent_off[(size_t)q + 1] = (int64_t)ent_q.size();
     }
@@ -428,13 +433,13 @@ static int retrieve_request_body(Model* m, int medium, const float* queries, Ret
     d_trng = c.take<int32_t>(trng.size());
     planes = c.take<unsigned>((size_t)slice * RR_PLANES * W);
   }));
-  std::vector<int64_t> soff(sel_off ? sel_off : nullptr, sel_off ? sel_off + ng + 1 : nullptr);
-  if (!sel_off) soff.assign((size_t)ng + 1, 0);
+  std::vector<int64_t> soff(sel.off ? sel.off : nullptr, sel.off ? sel.off + ng + 1 : nullptr);
+  if (!sel.off) soff.assign((size_t)ng + 1, 0);
   // (synchronous copies from pageable memory: the host vectors above outlive them)
   HIP_CHECK(hipMemcpyAsync(d_soff, soff.data(), soff.size() * 8, hipMemcpyHostToDevice, s));
   if (nsel) {
-    HIP_CHECK(hipMemcpyAsync(d_smed, sel_medium, (size_t)nsel * 4, hipMemcpyHostToDevice, s));
-    HIP_CHECK(hipMemcpyAsync(d_sids, sel_ids, (size_t)nsel * 4, hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(d_smed, sel.medium, (size_t)nsel * 4, hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(d_sids, sel.ids, (size_t)nsel * 4, hipMemcpyHostToDevice, s));
     if (qw.sel) HIP_CHECK(hipMemcpyAsync(d_sw, qw.sel, (size_t)nsel * 4, hipMemcpyHostToDevice, s));
   }
   if (nent) {
@@ -501,33 +506,7 @@ static int retrieve_request_body(Model* m, int medium, const float* queries, Ret
     toc(m);
     return RSYS_OK;
   };
-  return model_retrieve_run(m, medium, queries, nq, group, ng, init, k, ids_out, scores_out, counts_out, dev, win, qw.user);
-}
-
-int model_retrieve_request(Model* m, int medium, const float* queries, int64_t nq, const int32_t* group, int32_t ng, const int64_t* hist_off,
-                           const int32_t* hist_medium, const int32_t* hist_ids, const int32_t* hist_status, const int64_t* sel_off,
-                           const int32_t* sel_medium, const int32_t* sel_ids, int32_t k, int32_t* ids_out, float* scores_out,
-                           int32_t* counts_out, QueryWeights qw, QueryTexts qt) {
-  return retrieve_request_body(m, medium, queries, nullptr, nq, group, ng, hist_off, hist_medium, hist_ids, hist_status, sel_off, sel_medium,
-                               sel_ids, k, ids_out, scores_out, counts_out, nullptr, qw, qt);
-}
-
-int model_retrieve_request_dev(Model* m, int medium, RetrieveDev* dev, int64_t nq, const int32_t* group, int32_t ng, const int64_t* hist_off,
-                               const int32_t* hist_medium, const int32_t* hist_ids, const int32_t* hist_status, const int64_t* sel_off,
-                               const int32_t* sel_medium, const int32_t* sel_ids, int32_t k, int32_t* counts_out, QueryWeights qw,
-                               QueryTexts qt) {
-  ARG_CHECK(dev != nullptr, "retrieve_request: null device buffers");
-  return retrieve_request_body(m, medium, nullptr, dev, nq, group, ng, hist_off, hist_medium, hist_ids, hist_status, sel_off, sel_medium,
-                               sel_ids, k, nullptr, nullptr, counts_out, nullptr, qw, qt);
-}
-
-int model_retrieve_window(Model* m, int medium, const float* queries, int64_t nq, const int32_t* group, int32_t ng, const int64_t* hist_off,
-                          const int32_t* hist_medium, const int32_t* hist_ids, const int32_t* hist_status, const int64_t* sel_off,
-                          const int32_t* sel_medium, const int32_t* sel_ids, const RetrieveWin* win, RetrieveDev* dev, int32_t* ids_out,
-                          float* scores_out, int32_t* counts_out, QueryWeights qw, QueryTexts qt) {
-  ARG_CHECK(win != nullptr, "retrieve_window: null window");
-  return retrieve_request_body(m, medium, queries, dev, nq, group, ng, hist_off, hist_medium, hist_ids, hist_status, sel_off, sel_medium,
-                               sel_ids, 0, ids_out, scores_out, counts_out, win, qw, qt);
+  return model_retrieve_run(m, medium, rq.queries, nq, group, ng, init, k, ids_out, scores_out, counts_out, dev, win, qw.user);
 }
 
 // rsys_op_query_weights, the selected-sum section: one launch of selected_sum_w_kernel over device arrays

@@ -589,7 +589,7 @@ static int op_text_rows(SearchModel* h, const float* x, int n, float* z_out, flo
 }
 
 // rsys_query_texts_set: the rows of n texts into the model's buffer of `medium`, held with their groups and weights until the next
-// request entry point takes them (capi.hip: TakenTexts).  A refused call holds nothing for the medium.
+// request entry point takes them (capi.hip: PendingQueries).  A refused call holds nothing for the medium.
 int model_query_texts_set(Model* m, void* search, int medium, const float* x, int64_t n, const int32_t* group, const float* w) {
   ARG_CHECK(medium == 0 || medium == 1, "query_texts_set: medium must be 0 or 1");
   TextSet& ts = m->qtexts[medium];

@@ -754,21 +754,34 @@ def _texts(model, states, search, media=None):
         raise
 
 
+def _users_and_selected(states, who=None, selected=True):
+    """What every request path reads off its states, one group per state: the users' dicts in state and user order, their group ids,
+    each user's list items as (medium, matchedid, status) in list order -- every entry, duplicates and all statuses included -- and
+    (selected=True) each state's selected items as (medium, matchedid) in order.  `who`: a state without users raises in its name."""
+    users, group, hist, sel = [], [], [], []
+    for g, st in enumerate(states):
+        if who and not st["users"]:
+            raise ValueError(f"{who}: every state needs at least one user")
+        for u in st["users"]:
+            users.append(u)
+            group.append(g)
+            hist.append([(int(x["medium"]), int(x["matchedid"]), int(x["status"])) for x in u["user"]["items"]])
+        if selected:
+            sel.append([(int(a["medium"]), int(a["matchedid"])) for a in st["items"]])
+    return users, np.asarray(group, np.int32), hist, sel
+
+
+def _embeds(users, key):
+    """the users' `key` embeddings as rows (n, D), or None without users"""
+    return np.stack([np.asarray(u["embeds"][key], np.float32).reshape(-1) for u in users]) if users else None
+
+
 def request_arrays(states, medium, weights=False):
     """The arguments of `RecommenderModel.retrieve_request` for render.jl request states of one medium, one group per state: the
     users' "{medium}.retrieval" embeddings (n, D), their group ids, each user's list items as (medium, matchedid, status) in list
     order, and each state's selected items as (medium, matchedid) in order.  weights=True: then the two arrays of `state_weights`."""
-    key = f"{medium}.retrieval"
-    q, group, hist, sel = [], [], [], []
-    for g, st in enumerate(states):
-        if not st["users"]:
-            raise ValueError("retrieval: every state needs at least one user")
-        for u in st["users"]:
-            q.append(np.asarray(u["embeds"][key], np.float32).reshape(-1))
-            group.append(g)
-            hist.append([(int(x["medium"]), int(x["matchedid"]), int(x["status"])) for x in u["user"]["items"]])
-        sel.append([(int(a["medium"]), int(a["matchedid"])) for a in st["items"]])
-    return (np.stack(q), np.asarray(group, np.int32), hist, sel) + (state_weights(states) if weights else ())
+    users, group, hist, sel = _users_and_selected(states, "retrieval")
+    return (_embeds(users, f"{medium}.retrieval"), group, hist, sel) + (state_weights(states) if weights else ())
 
 
 def retrieval(model, states, k=1024, coefs=None, search=None):
@@ -780,13 +793,7 @@ def retrieval(model, states, k=1024, coefs=None, search=None):
     SearchModel} and added to its prior.  Returns one (ids, scores) pair per state, ids 0-based medium-local, at most min(k, V_m, 8192)
     of them."""
     out = [None] * len(states)
-    by_medium = {}
-    for j, st in enumerate(states):
-        m = int(st["medium"])
-        if m not in (0, 1):
-            raise ValueError("retrieval: medium must be 0 or 1")
-        by_medium.setdefault(m, []).append(j)
-    for m, idx in sorted(by_medium.items()):
+    for m, idx in _by_medium(states, "retrieval: "):
         q, group, hist, sel, uw, sw = request_arrays([states[j] for j in idx], m, weights=True)
         Vm = model.config["vocab_sizes"][f"{m}_matchedid"]
         kk = min(int(k), Vm, 8192)
@@ -806,15 +813,8 @@ def retrieval(model, states, k=1024, coefs=None, search=None):
 
 def _window_arrays(states, medium, weights=False):
     """`request_arrays` for states that may have no users: (queries or None, group ids, list items per user, selected items per state)"""
-    key = f"{medium}.retrieval"
-    q, group, hist, sel = [], [], [], []
-    for g, st in enumerate(states):
-        for u in st["users"]:
-            q.append(np.asarray(u["embeds"][key], np.float32).reshape(-1))
-            group.append(g)
-            hist.append([(int(x["medium"]), int(x["matchedid"]), int(x["status"])) for x in u["user"]["items"]])
-        sel.append([(int(a["medium"]), int(a["matchedid"])) for a in st["items"]])
-    return ((np.stack(q) if q else None), np.asarray(group, np.int32), hist, sel) + (state_weights(states) if weights else ())
+    users, group, hist, sel = _users_and_selected(states)
+    return (_embeds(users, f"{medium}.retrieval"), group, hist, sel) + (state_weights(states) if weights else ())
 
 
 def retrieval_window(model, states, windows, search=None):
@@ -875,32 +875,29 @@ def rank_arrays(states, idxs, with_embeds=True, weights=False):
     matchedid, status) in list order -- every entry, duplicates and all statuses included -- and per group the penalties
     (decay, mmr_penalty, same_series_penalty, related_penalty) of `state["penalties"]`.  weights=True: then the two arrays of
     `state_weights` (the ranking reads the users' only)."""
-    q, group, rm, hist, pen = [], [], [], [], []
-    for g, st in enumerate(states):
-        m = int(st["medium"])
-        if not st["users"]:
-            raise ValueError("ranking: every state needs at least one user")
-        p = st.get("penalties", {})
-        pen.append([float(p.get(k, 0.0)) for k in ("decay", "mmr_penalty", "same_series_penalty", "related_penalty")])
-        for u in st["users"]:
-            group.append(g)
-            hist.append([(int(x["medium"]), int(x["matchedid"]), int(x["status"])) for x in u["user"]["items"]])
-            if with_embeds:
-                q.append(np.asarray(u["embeds"][f"{m}.retrieval"], np.float32).reshape(-1))
-                r = np.asarray(u["embeds"][f"{m}.ranking"], np.float32).reshape(-1)
-                if r.size != len(idxs[g]):
-                    raise ValueError(f"ranking: a user has {r.size} \"{m}.ranking\" values for {len(idxs[g])} candidates")
-                rm.append(r)
-    return ((np.stack(q) if with_embeds else None), np.asarray(group, np.int32), (rm if with_embeds else None), hist,
-            np.asarray(pen, np.float32).reshape(-1, 4)) + (state_weights(states) if weights else ())
+    users, group, hist, _ = _users_and_selected(states, "ranking", selected=False)
+    pen = [[float(st.get("penalties", {}).get(k, 0.0)) for k in ("decay", "mmr_penalty", "same_series_penalty", "related_penalty")]
+           for st in states]
+    q = rm = None
+    if with_embeds:
+        q, rm = [], []
+        for u, g in zip(users, group):
+            m = int(states[g]["medium"])
+            q.append(np.asarray(u["embeds"][f"{m}.retrieval"], np.float32).reshape(-1))
+            rm.append(np.asarray(u["embeds"][f"{m}.ranking"], np.float32).reshape(-1))
+            if rm[-1].size != len(idxs[g]):
+                raise ValueError(f"ranking: a user has {rm[-1].size} \"{m}.ranking\" values for {len(idxs[g])} candidates")
+        q = np.stack(q)
+    return (q, group, rm, hist, np.asarray(pen, np.float32).reshape(-1, 4)) + (state_weights(states) if weights else ())
 
 
-def _by_medium(states):
+def _by_medium(states, who=""):
+    """[(medium, indices of its states)], media ascending; `who` starts the refusal's text"""
     out = {}
     for j, st in enumerate(states):
         m = int(st["medium"])
         if m not in (0, 1):
-            raise ValueError("medium must be 0 or 1")
+            raise ValueError(f"{who}medium must be 0 or 1")
         out.setdefault(m, []).append(j)
     return sorted(out.items())
 
