@@ -528,15 +528,8 @@ int launch_attn_tilemap(const AttnParams& p, hipStream_t s) {
   ARG_CHECK(p.T % 8 == 0 && (p.T + 63) / 64 <= 64, "attention: T must be a multiple of 8 and <= 4096");
   ARG_CHECK(p.qbits != nullptr && p.kbits != nullptr, "attention: the pair-bit buffers (AttnParams::qbits / kbits) are required");
   const bool wide = (p.T + 63) / 64 > 32;   // 64-bit map words (AMap<6>)
-  const size_t bytes = sizeof(unsigned int) * attn_map_words(p.T) * p.B * ((p.T + 63) / 64);
-  if (p.maps_zero_base != nullptr) {
-    HIP_CHECK(hipMemsetAsync(p.maps_zero_base, 0, p.maps_zero_bytes, s));
-  } else {
-    HIP_CHECK(hipMemsetAsync(p.kmap, 0, bytes, s));
-    HIP_CHECK(hipMemsetAsync(p.kmap_full, 0, bytes, s));
-    HIP_CHECK(hipMemsetAsync(p.qmap_full, 0, bytes, s));
-    HIP_CHECK(hipMemsetAsync(p.kmap16, 0, bytes * 4, s));
-  }
+  ARG_CHECK(p.maps_zero_base != nullptr, "attention: the tile maps come from attn_maps_alloc (AttnParams::maps_zero_base)");
+  HIP_CHECK(hipMemsetAsync(p.maps_zero_base, 0, p.maps_zero_bytes, s));
   if (wide) hipLaunchKernelGGL(attn_tilemap_kernel<6>, dim3((p.T + 63) / 64, p.B), dim3(256), 0, s, p);
   else hipLaunchKernelGGL(attn_tilemap_kernel<5>, dim3((p.T + 63) / 64, p.B), dim3(256), 0, s, p);
   if (p.order_q != nullptr || p.order_k != nullptr) {

@@ -217,8 +217,8 @@ struct AttnParams {
   // ordered selected-first).  Forward and dQ skip the other query tiles (their outputs are never read; dQ writes zeros), dK/dV
   // leaves them out of its sums (their dO is identically zero).
   const int* q_active;
-  // optional: kmap, kmap_full, qmap_full and kmap16 (the maps the tile-map kernel ORs into) live back to back in one allocation
-  // starting here: one zero-fill instead of four
+  // kmap, kmap_full, qmap_full and kmap16 (the maps the tile-map kernel ORs into) live back to back in one allocation starting
+  // here (AttnMaps): launch_attn_tilemap zero-fills it
   void* maps_zero_base; size_t maps_zero_bytes;
   // backward
   const void* dO; float* delta;   // delta [B][H][T] = rowsum(dO * O): written by the dQ kernel, read by the dK/dV kernel
@@ -237,6 +237,35 @@ struct AttnParams {
   unsigned long long *qbits, *kbits;
 };
 inline int attn_map_words(int T) { return (T + 63) / 64 > 32 ? 2 : 1; }   // 32-bit words per tile-map entry
+// The tile-map set of one token order, on the host: the ten map pointers of AttnParams and the region launch_attn_tilemap zero-fills.
+struct AttnMaps {
+  unsigned int *qmap = nullptr, *kmap = nullptr, *qmap_full = nullptr, *kmap_full = nullptr, *qmap16 = nullptr, *kmap16 = nullptr;
+  int *order_q = nullptr, *order_k = nullptr;
+  unsigned long long *qbits = nullptr, *kbits = nullptr;
+  void* zero_base = nullptr; size_t zero_bytes = 0;
+  void apply(AttnParams& p) const {
+    p.qmap = qmap; p.kmap = kmap; p.qmap_full = qmap_full; p.kmap_full = kmap_full; p.qmap16 = qmap16; p.kmap16 = kmap16;
+    p.order_q = order_q; p.order_k = order_k; p.qbits = qbits; p.kbits = kbits;
+    p.maps_zero_base = zero_base; p.maps_zero_bytes = zero_bytes;
+  }
+};
+// The set for `rows` rows of up to T tokens, in five buffers that alloc(void** p, size_t bytes) -> RSYS_OK / error hands out.  The maps: mb =
+// one [rows][ceil(T/64)] map padded to 256 bytes; kmap | kmap_full | qmap_full | kmap16 (4 entries) back to back are the zero-filled
+// 7 mb, then qmap and qmap16 (4 entries), 12 mb in all.  Then the two order lists and the two pair-bit arrays.
+template <typename Alloc>
+int attn_maps_alloc(AttnMaps& a, long long rows, int T, int H, int KV, Alloc&& alloc) {
+  const long long nt = (T + 63) / 64;
+  const long long mb = (rows * nt * 4 * attn_map_words(T) + 255) / 256 * 256;   // (64-bit map words above 32 tiles per row)
+  unsigned char* base = nullptr;
+  if (int rc = alloc((void**)&base, (size_t)(mb * 12))) return rc;
+  a.kmap = (unsigned int*)base; a.kmap_full = (unsigned int*)(base + mb); a.qmap_full = (unsigned int*)(base + 2 * mb); a.kmap16 = (unsigned int*)(base + 3 * mb);
+  a.qmap = (unsigned int*)(base + 7 * mb); a.qmap16 = (unsigned int*)(base + 8 * mb);
+  a.zero_base = base; a.zero_bytes = (size_t)(7 * mb);
+  if (int rc = alloc((void**)&a.order_q, (size_t)(rows * H * nt * 4))) return rc;
+  if (int rc = alloc((void**)&a.order_k, (size_t)(rows * KV * nt * 4))) return rc;
+  if (int rc = alloc((void**)&a.qbits, (size_t)(rows * nt * nt * 64 * 8))) return rc;
+  return alloc((void**)&a.kbits, (size_t)(rows * nt * nt * 64 * 8));
+}
 int launch_attn_tilemap(const AttnParams& p, hipStream_t s);
 // Candidate attention against a cached history (rank_cache.hip; Finetune/embed.py:74-131's ranking row without its history half).  Row r of
 // qkv [rows * T][ld] holds n_cand[r] candidates, candidate j at tokens 2 j (item) and 2 j + 1 (action).  A query token of candidate j

@@ -208,17 +208,8 @@ int model_create(const rsys_config* cfg, int device, Model** out) {
   }
   DALLOC(m->feat, N * 32 * e); DALLOC(m->x0, NT * D * 4);
   DALLOC(m->uid_t, NT * 4); DALLOC(m->tm_t, NT * 4);
-  {   // attention tile maps: the four the tile-map kernel ORs into sit back to back (one zero-fill per step), then the two it stores
-    const int64_t mb = ((int64_t)m->rows_max * ((m->Ta + 63) / 64) * 4 * attn_map_words(m->Ta) + 255) / 256 * 256;   // (64-bit map words above 32 tiles per row)
-    unsigned char* base = nullptr;
-    DALLOC(base, mb * 7 + mb * 5);
-    m->kmap = (unsigned int*)base; m->kmap_full = (unsigned int*)(base + mb); m->qmap_full = (unsigned int*)(base + 2 * mb); m->kmap16 = (unsigned int*)(base + 3 * mb);
-    m->qmap = (unsigned int*)(base + 7 * mb); m->qmap16 = (unsigned int*)(base + 8 * mb);
-    m->maps_zero_bytes = (size_t)(7 * mb);
-    const int64_t nt = (m->Ta + 63) / 64;
-    DALLOC(m->attn_order_q, (int64_t)m->rows_max * m->H * nt * 4); DALLOC(m->attn_order_k, (int64_t)m->rows_max * m->KV * nt * 4);
-    DALLOC(m->attn_qbits, (int64_t)m->rows_max * nt * nt * 64 * 8); DALLOC(m->attn_kbits, (int64_t)m->rows_max * nt * nt * 64 * 8);
-  }
+  const auto maps_alloc = [m](void** p, size_t bytes) { return dalloc(m, p, bytes); };
+  RC(attn_maps_alloc(m->maps, m->rows_max, m->Ta, m->H, m->KV, maps_alloc));   // attention tile maps (one zero-fill per step)
   m->la.resize(m->L);
   for (int l = 0; l < m->L; ++l) {
     Model::LayerAct& a = m->la[l];
@@ -311,14 +302,7 @@ int model_create(const rsys_config* cfg, int device, Model** out) {
       if (m->bf16_mode) { DALLOC(m->c_gx_t, cap * D * 2); DALLOC(m->c_dh_t, cap * D * 2); } else { m->c_gx_t = m->c_gx; m->c_dh_t = m->c_dh; }
       DALLOC(m->c_perm, NT * 4); DALLOC(m->uid_p, NT * 4); DALLOC(m->tm_p, NT * 4); DALLOC(m->pos_p, NT * 4); DALLOC(m->c_slot_p, NT * 4);
       DALLOC(m->c_sel_p, cap * 4); DALLOC(m->c_qact, (int64_t)m->rows_max * 4 + 64);
-      const int64_t mb = ((int64_t)m->rows_max * ((m->Ta + 63) / 64) * 4 * attn_map_words(m->Ta) + 255) / 256 * 256;   // (64-bit map words above 32 tiles per row)
-      unsigned char* base = nullptr;
-      DALLOC(base, mb * 12);
-      m->kmap_p = (unsigned int*)base; m->kmap_full_p = (unsigned int*)(base + mb); m->qmap_full_p = (unsigned int*)(base + 2 * mb); m->kmap16_p = (unsigned int*)(base + 3 * mb);
-      m->qmap_p = (unsigned int*)(base + 7 * mb); m->qmap16_p = (unsigned int*)(base + 8 * mb);
-      const int64_t nt = (m->Ta + 63) / 64;
-      DALLOC(m->attn_order_q_p, (int64_t)m->rows_max * m->H * nt * 4); DALLOC(m->attn_order_k_p, (int64_t)m->rows_max * m->KV * nt * 4);
-      DALLOC(m->attn_qbits_p, (int64_t)m->rows_max * nt * nt * 64 * 8); DALLOC(m->attn_kbits_p, (int64_t)m->rows_max * nt * nt * 64 * 8);
+      RC(attn_maps_alloc(m->maps_p, m->rows_max, m->Ta, m->H, m->KV, maps_alloc));
     }
   }
   if (m->fp8) {

@@ -254,8 +254,8 @@ struct Model {
   unsigned char *d_wm = nullptr, *d_rm = nullptr;
   int* d_rope_pos = nullptr;
   // activations (void* = T-typed)
-  size_t maps_zero_bytes = 0;   // kmap | kmap_full | qmap_full | kmap16 are one allocation: bytes of the region the tile-map kernel needs zeroed
-  void* feat; float* x0; int *uid_t, *tm_t; unsigned int *qmap, *kmap, *qmap_full, *kmap_full, *qmap16, *kmap16;
+  void* feat; float* x0; int *uid_t, *tm_t;
+  AttnMaps maps, maps_p;   // the attention tile maps of the token order and of the selected-first order (below)
   struct LayerAct { float* x; void* xn; void* xnd; void* La; void* qkv; void* O; float* lse; float* rstd1; float* h; void* hn; float* rstd2; void* ab; void* g; };
   std::vector<LayerAct> la;
   float* xL; float* rstdf; void* out;
@@ -294,11 +294,8 @@ struct Model {
   // ... and the last layer runs on a SELECTED-FIRST token order (inside every batch row the selected tokens, then the others; attention
   // is indifferent to token order): its attention kernels then visit only the leading query tiles c_qact[b] of a row.  c_perm: original
   // token of a permuted place; uid_p / tm_p / pos_p: ids and RoPE position per permuted place; c_slot_p / c_sel_p: the compact maps in
-  // permuted places; *_p maps: the attention tile maps of that order.  la[L-1].{xn, rstd1, qkv, O, lse} are stored in permuted order.
+  // permuted places; maps_p: the attention tile maps of that order.  la[L-1].{xn, rstd1, qkv, O, lse} are stored in permuted order.
   int *c_perm = nullptr, *uid_p = nullptr, *tm_p = nullptr, *pos_p = nullptr, *c_slot_p = nullptr, *c_sel_p = nullptr, *c_qact = nullptr;
-  unsigned int *qmap_p = nullptr, *kmap_p = nullptr, *qmap_full_p = nullptr, *kmap_full_p = nullptr, *qmap16_p = nullptr, *kmap16_p = nullptr;
-  unsigned long long *attn_qbits = nullptr, *attn_kbits = nullptr, *attn_qbits_p = nullptr, *attn_kbits_p = nullptr;   // pair bits of the two map sets (AttnParams::qbits / kbits)
-  int *attn_order_q = nullptr, *attn_order_k = nullptr, *attn_order_q_p = nullptr, *attn_order_k_p = nullptr;   // heaviest-first launch orders of the two map sets (AttnParams::order_q / order_k)
   bool table_grads_pending = false;
   // the item-table gradient rows of medium m are known to be zero (just zeroed by zero_grad / AdamW and not written since):
   // the first head GEMM of a step then stores dF instead of reading 245 MB of zeros to add to
