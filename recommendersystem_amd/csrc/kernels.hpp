@@ -197,7 +197,7 @@ int launch_action_small_bwd(const float* gf /*[N][32]*/, const BatchDev& b, cons
                             float* g_per_cos, float* g_per_sin, float* g_status, float* g_gender, float* g_source,
                             hipStream_t s);
 
-// ---- attention (attention.hip)
+// ---- attention (attention_maps.hip, attention.hip, attention_serve.hip; shared helpers: attention_common.hpp)
 struct AttnParams {
   int B, T, H, KV, hd;
   int is_bf16;                 // the launches that follow are the bf16 ones (launch_attn_tilemap needs to know: order_k lists kv tile PAIRS for attn_bwd_kv32_kernel)

@@ -68,6 +68,68 @@ int model_rank_cache_reserve(Model* m, int n_slots) {
   return RSYS_OK;
 }
 
+// K | V of the leading 2 n_hist[r] tokens of every row -> the row's cache slot, in 16-byte chunks (rsys_rank_cache_store, once per layer)
+template <typename T>
+__global__ __launch_bounds__(256) void rank_cache_copy_kernel(const T* __restrict__ qkv, long long ld, int kv_off, int kvw, int T_len, int T_slot, const int* __restrict__ slot,
+                                                              const int* __restrict__ n_hist, int n_slots, T* __restrict__ cache) {
+  const int r = blockIdx.y, sl = slot[r];
+  if (sl < 0 || sl >= n_slots) return;
+  const int ntok = 2 * min(max(n_hist[r], 0), T_len / 2);
+  const int cpr = kvw * (int)sizeof(T) / 16;
+  const long long n = (long long)ntok * cpr;
+  for (long long c = (long long)blockIdx.x * 256 + threadIdx.x; c < n; c += (long long)gridDim.x * 256) {
+    const long long tok = c / cpr; const int ch = (int)(c % cpr);
+    const uint4 v = *(const uint4*)((const unsigned char*)(qkv + ((long long)r * T_len + tok) * ld + kv_off) + 16 * ch);
+    *(uint4*)((unsigned char*)(cache + ((long long)sl * T_slot + tok) * kvw) + 16 * ch) = v;
+  }
+}
+template <typename T>
+int launch_rank_cache_copy(const T* qkv, long long ld, int kv_off, int kvw, int T_len, int T_slot, int rows, const int* slot, const int* n_hist, int n_slots, T* cache,
+                           hipStream_t s) {
+  ARG_CHECK(T_slot >= T_len, "ranking cache: rows longer than a slot");
+  ARG_CHECK((kvw * sizeof(T)) % 16 == 0 && (kv_off * sizeof(T)) % 16 == 0 && (ld * sizeof(T)) % 16 == 0, "ranking cache: 16-byte row alignment");
+  const int cpr = kvw * (int)sizeof(T) / 16;
+  const int gx = (int)std::min<long long>(((long long)T_len * cpr + 255) / 256, 64);
+  hipLaunchKernelGGL((rank_cache_copy_kernel<T>), dim3(gx, rows), dim3(256), 0, s, qkv, ld, kv_off, kvw, T_len, T_slot, slot, n_hist, n_slots, cache);
+  HIP_CHECK(hipGetLastError());
+  return RSYS_OK;
+}
+template int launch_rank_cache_copy<bf16>(const bf16*, long long, int, int, int, int, int, const int*, const int*, int, bf16*, hipStream_t);
+template int launch_rank_cache_copy<float>(const float*, long long, int, int, int, int, int, const int*, const int*, int, float*, hipStream_t);
+
+// Packed store rows (rsys_rank_cache_store_packed): per segment descriptor seg[i] = (row, first column c0, n_hist, slot), K | V of
+// tokens [2 c0, 2 c0 + 2 n_hist) of the row -> rows [0, 2 n_hist) of the slot, in 16-byte chunks; grid (chunks, segments).  A descriptor that
+// does not fit the rows or the cache copies nothing.
+template <typename T>
+__global__ __launch_bounds__(256) void rank_cache_copy_segments_kernel(const T* __restrict__ qkv, long long ld, int kv_off, int kvw, int T_len, int T_slot, int rows,
+                                                                       const int* __restrict__ seg, int n_slots, T* __restrict__ cache) {
+  const int* d = seg + 4 * blockIdx.y;
+  const int r = d[0], c0 = d[1], nh = d[2], sl = d[3];
+  if (r < 0 || r >= rows || sl < 0 || sl >= n_slots || c0 < 0 || nh <= 0) return;
+  if (2 * ((long long)c0 + nh) > T_len || 2 * (long long)nh > T_slot) return;
+  const int cpr = kvw * (int)sizeof(T) / 16;
+  const long long n = (long long)2 * nh * cpr;
+  for (long long c = (long long)blockIdx.x * 256 + threadIdx.x; c < n; c += (long long)gridDim.x * 256) {
+    const long long tok = c / cpr; const int ch = (int)(c % cpr);
+    const uint4 v = *(const uint4*)((const unsigned char*)(qkv + ((long long)r * T_len + 2 * c0 + tok) * ld + kv_off) + 16 * ch);
+    *(uint4*)((unsigned char*)(cache + ((long long)sl * T_slot + tok) * kvw) + 16 * ch) = v;
+  }
+}
+template <typename T>
+int launch_rank_cache_copy_segments(const T* qkv, long long ld, int kv_off, int kvw, int T_len, int T_slot, int rows, const int* seg, int n_seg, int n_slots, T* cache,
+                                    hipStream_t s) {
+  ARG_CHECK(T_slot >= T_len, "ranking cache: rows longer than a slot");
+  ARG_CHECK(rows >= 1 && n_seg >= 1 && n_seg <= 65535 && n_slots >= 1 && seg != nullptr, "ranking cache: rows, segments and slots");
+  ARG_CHECK((kvw * sizeof(T)) % 16 == 0 && (kv_off * sizeof(T)) % 16 == 0 && (ld * sizeof(T)) % 16 == 0, "ranking cache: 16-byte row alignment");
+  const int cpr = kvw * (int)sizeof(T) / 16;
+  const int gx = (int)std::min<long long>(((long long)T_len * cpr + 255) / 256, 64);
+  hipLaunchKernelGGL((rank_cache_copy_segments_kernel<T>), dim3(gx, n_seg), dim3(256), 0, s, qkv, ld, kv_off, kvw, T_len, T_slot, rows, seg, n_slots, cache);
+  HIP_CHECK(hipGetLastError());
+  return RSYS_OK;
+}
+template int launch_rank_cache_copy_segments<bf16>(const bf16*, long long, int, int, int, int, int, const int*, int, int, bf16*, hipStream_t);
+template int launch_rank_cache_copy_segments<float>(const float*, long long, int, int, int, int, int, const int*, int, int, float*, hipStream_t);
+
 template <typename T>
 int rank_cache_store_layer(Model* m, int l, const T* qkv) {
   tic(m, "hbm_rank_cache_store", 2.0 * sizeof(T) * m->cur_rows * m->T * (double)rc_kvw(m));

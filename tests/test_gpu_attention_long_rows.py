@@ -1,5 +1,5 @@
 """GPU: the attention kernels on rows of 33 .. 64 tiles (2048 < T <= 4096 tokens, max_sequence_length up to 2048), where a tile-map
-entry is a 64-bit word (csrc/attention.hip, AMap<6>): forward and backward through rsys_op_attention_ex against the float64 reference of
+entry is a 64-bit word (csrc/attention_common.hpp, AMap<6>): forward and backward through rsys_op_attention_ex against the float64 reference of
 tests/_attention_np.py, with the helpers, the error measure and the bounds of tests/test_gpu_attention_parity.py (its docstring):
 fp32 row error <= 1e-4, whole tensor 2e-5, lse 1e-4; bf16 e <= 2 E against attn_emul_bf16 on the same inputs and whole tensor 3e-2.
 

@@ -1,4 +1,4 @@
-"""GPU: the selected-query attention of the serving compact top (attn_sel_kernel, csrc/attention.hip) through
+"""GPU: the selected-query attention of the serving compact top (attn_sel_kernel, csrc/attention_serve.hip) through
 rsys_op_attention_selected against the float64 reference of tests/_attention_np.py.  The kernel attends query token sel[i] to the keys of
 its own row under the model's mask and writes compact row i; the reference computes every row of O and the test reads rows sel.
 

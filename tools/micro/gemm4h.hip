@@ -30,7 +30,7 @@ constexpr int H4_BM = 256, H4_BN = 128, H4_BK = 32, H4_ST = 3;
 constexpr int H4_A_BYTES = H4_BM * 64, H4_B_BYTES = H4_BN * 64, H4_STAGE = H4_A_BYTES + H4_B_BYTES;   // 16 KB + 8 KB
 
 // The DMA behind an asm statement: the compiler's wait-count pass would order every LDS read it cannot tell apart from a pending LDS-DMA
-// behind it (attention.hip, dma16_asm); the kernel keeps its own counted waits.  lds: wave-uniform LDS byte address.
+// behind it (attention_common.hpp, dma16_asm); the kernel keeps its own counted waits.  lds: wave-uniform LDS byte address.
 __device__ __forceinline__ void h4_dma(h4_i32x4 rsrc, unsigned int lds, int voffset, int soffset) {
   asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds" ::"s"(lds), "v"(voffset), "s"(rsrc), "s"(soffset) : "memory");
 }
