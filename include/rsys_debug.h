@@ -116,6 +116,21 @@ int32_t rsys_op_attention_ex(int32_t dtype, int32_t B, int32_t T, int32_t H, int
  * rsys_op_attention_ex (T a multiple of 8, T <= 4096; rows of more than 2048 tokens use the 64-bit map words) */
 int32_t rsys_op_attention_selected(int32_t dtype, int32_t B, int32_t T, int32_t H, int32_t KV, int32_t hd, const void* qkv,
                                    const int32_t* uid, const int32_t* tm, int32_t n_sel, const int32_t* sel, void* O);
+/* the tile maps, pair bits and launch orders of an attention launch alone (launch_attn_tilemap, csrc/attention_maps.hip), built as
+ * rsys_op_attention_ex and rsys_op_attention_selected build them before their first attention kernel; no attention kernel runs.  dtype,
+ * KV and hd only decide the query heads per workgroup and whether order_k lists kv tile pairs.  uid / tm (device int32 [B*T]) are copied
+ * back and checked: 0 <= uid < 2^19, 0 <= tm < 4096; q_active (device int32 [B], or null): 0 <= q_active[b] <= nt = ceil(T / 64); T a
+ * multiple of 8, T <= 4096, H a multiple of KV; RSYS_ERR_ARG otherwise, with nothing launched.  Every byte of the map set holds 0xA5
+ * before the first launch.  uid_prev / tm_prev (device, both or neither): launch_attn_tilemap runs on them first, into the same set.
+ * Outputs, HOST buffers, W = 32-bit words for nt <= 32, else 64-bit: qmap / kmap / qmap_full / kmap_full W [B][nt]; qmap16 / kmap16
+ * W [B][nt][4]; qbits uint64 [B][nt q][nt kv][64 queries], kbits uint64 [B][nt kv][nt q][64 keys]; order_q int32 [B*H*nt] and order_k
+ * int32 [B*KV*nt], the whole buffers (the lists sit back to back at their start, 0xA5 behind them); info int32 [8] = 32-bit words per
+ * map entry, query heads per workgroup, kv tile pairs (0 / 1), eight XCD lists (1) or one list (0), slots per (row, kv head) on the
+ * q side, on the k side, identity fallback taken (0 / 1), nt */
+int32_t rsys_op_attention_maps(int32_t dtype, int32_t B, int32_t T, int32_t H, int32_t KV, int32_t hd, const int32_t* uid, const int32_t* tm,
+                               const int32_t* q_active, const int32_t* uid_prev, const int32_t* tm_prev, void* qmap, void* kmap,
+                               void* qmap_full, void* kmap_full, void* qmap16, void* kmap16, uint64_t* qbits, uint64_t* kbits,
+                               int32_t* order_q, int32_t* order_k, int32_t* info);
 /* the candidate attention of rsys_rank_cache_candidates alone, on caller-provided device buffers (T-typed): qkv [rows*T][(H+2KV)*hd] the
  * candidate rows' post-RoPE q | k | v, cache [n_slots][T][2*KV*hd] (K | V per cached token), slot / n_hist / n_cand int32 [rows] (device;
  * 0 <= n_hist[r] <= T/2, 0 <= n_cand[r] <= T/2; T a multiple of 8, T <= 4096); O [rows*T][H*hd]: rows of tokens >= 2 n_cand[r] are zeros up to the end of the last

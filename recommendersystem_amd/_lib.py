@@ -173,6 +173,7 @@ _SIGS = [
     ("rsys_rank_cache_candidates_packed", C.c_int32, [_P, _P, C.c_int32, _P, _P]),
     ("rsys_rank_cache_get", C.c_int32, [_P, C.c_int32, C.c_int32, _P, C.c_int64]),
     ("rsys_op_attention_selected", C.c_int32, [C.c_int32] * 6 + [_P, _P, _P, C.c_int32, _P, _P]),
+    ("rsys_op_attention_maps", C.c_int32, [C.c_int32] * 6 + [_P] * 16),
     ("rsys_op_attention_cached", C.c_int32, [C.c_int32] * 6 + [_P, _P, C.c_int32, _P, _P, _P, _P]),
     ("rsys_op_attention_cached_tiles", C.c_int32, [C.c_int32] * 6 + [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
     ("rsys_op_rank_cache_copy_segments", C.c_int32, [C.c_int32] * 6 + [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P]),

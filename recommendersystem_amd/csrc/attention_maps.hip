@@ -169,6 +169,19 @@ __global__ __launch_bounds__(256) void attn_order_kernel(AttnParams p, int R, in
   }
 }
 
+AttnOrderPlan attn_order_plan(const AttnParams& p) {
+  AttnOrderPlan o{};
+  const int nt = (p.T + 63) / 64, n_groups = p.B * p.KV;
+  o.R = attn_heads_per_wg(p); o.kv_pairs = attn_kv_pairs(p) ? 1 : 0;
+  o.lists = (n_groups & 7) == 0 ? 8 : 1;
+  o.n_inner_q = (p.H / p.KV / o.R) * nt; o.n_inner_k = o.kv_pairs ? (nt + 1) / 2 : nt;
+  // (a list beyond one workgroup's LDS: keep the plain order -- the kernels read an identity permutation)
+  const int ns_max = (n_groups / o.lists) * (p.H / p.KV) * nt;
+  o.chunk_cap = attn_order_chunk_cap(nt > 32 ? 6 : 5); o.chunks = (ns_max + 63) / 64;
+  o.identity = o.chunks > o.chunk_cap ? 1 : 0;
+  return o;
+}
+
 int launch_attn_tilemap(const AttnParams& p, hipStream_t s) {
   ARG_CHECK(p.T % 8 == 0 && (p.T + 63) / 64 <= 64, "attention: T must be a multiple of 8 and <= 4096");
   ARG_CHECK(p.qbits != nullptr && p.kbits != nullptr, "attention: the pair-bit buffers (AttnParams::qbits / kbits) are required");
@@ -178,13 +191,11 @@ int launch_attn_tilemap(const AttnParams& p, hipStream_t s) {
   if (wide) hipLaunchKernelGGL(attn_tilemap_kernel<6>, dim3((p.T + 63) / 64, p.B), dim3(256), 0, s, p);
   else hipLaunchKernelGGL(attn_tilemap_kernel<5>, dim3((p.T + 63) / 64, p.B), dim3(256), 0, s, p);
   if (p.order_q != nullptr || p.order_k != nullptr) {
-    const int R = attn_heads_per_wg(p), nt = (p.T + 63) / 64, n_groups = p.B * p.KV;
-    const int ns_max = ((n_groups & 7) == 0 ? (n_groups >> 3) : n_groups) * (p.H / p.KV) * nt;
-    // (a list beyond one workgroup's LDS: keep the plain order -- the kernels read an identity permutation)
-    const int cap = attn_order_chunk_cap(wide ? 6 : 5), nch = (ns_max + 63) / 64;
-    const dim3 og((n_groups & 7) == 0 ? 8 : 1, 2);
-    if (wide) hipLaunchKernelGGL(attn_order_kernel<6>, og, dim3(256), (size_t)(std::min(nch, cap) + 1) * 66 * 4, s, p, R, nch > cap ? 1 : 0, attn_kv_pairs(p) ? 1 : 0);
-    else hipLaunchKernelGGL(attn_order_kernel<5>, og, dim3(256), (size_t)(std::min(nch, cap) + 1) * 34 * 4, s, p, R, nch > cap ? 1 : 0, attn_kv_pairs(p) ? 1 : 0);
+    const AttnOrderPlan o = attn_order_plan(p);
+    const dim3 og(o.lists, 2);
+    const size_t rows = (size_t)(std::min(o.chunks, o.chunk_cap) + 1);
+    if (wide) hipLaunchKernelGGL(attn_order_kernel<6>, og, dim3(256), rows * 66 * 4, s, p, o.R, o.identity, o.kv_pairs);
+    else hipLaunchKernelGGL(attn_order_kernel<5>, og, dim3(256), rows * 34 * 4, s, p, o.R, o.identity, o.kv_pairs);
   }
   HIP_CHECK(hipGetLastError());
   return RSYS_OK;

@@ -78,6 +78,29 @@ int hook_ints(const int32_t* dev, long long n, std::vector<int>& out) {
   if (n > 0) HIP_CHECK(hipMemcpy(out.data(), dev, (size_t)n * 4, hipMemcpyDeviceToHost));
   return RSYS_OK;
 }
+// The tile maps of one attention hook call, as every one of them builds them before its first attention launch: a map set from the
+// call's scratch, applied to p, one launch_attn_tilemap on the null stream.  rsys_op_attention_maps alone passes the rest: fill = every
+// byte of the set holds 0xA5 before the first launch (an entry the kernels leave unwritten then shows), uid_prev / tm_prev = an
+// earlier launch on those tokens into the same set (a model reuses one set step after step).
+int hook_attn_maps(HookScratch& scratch, AttnParams& p, AttnMaps& maps, bool fill = false, const int32_t* uid_prev = nullptr,
+                   const int32_t* tm_prev = nullptr) {
+  RC(attn_maps_alloc(maps, p.B, p.T, p.H, p.KV, [&](void** b, size_t bytes) { return scratch.alloc(b, bytes); }));
+  maps.apply(p);
+  if (fill) {
+    const size_t nt = (size_t)(p.T + 63) / 64;
+    HIP_CHECK(hipMemsetAsync(maps.zero_base, 0xA5, 12 * maps.map_bytes, nullptr));
+    HIP_CHECK(hipMemsetAsync(maps.order_q, 0xA5, (size_t)p.B * p.H * nt * 4, nullptr));
+    HIP_CHECK(hipMemsetAsync(maps.order_k, 0xA5, (size_t)p.B * p.KV * nt * 4, nullptr));
+    HIP_CHECK(hipMemsetAsync(maps.qbits, 0xA5, (size_t)p.B * nt * nt * 64 * 8, nullptr));
+    HIP_CHECK(hipMemsetAsync(maps.kbits, 0xA5, (size_t)p.B * nt * nt * 64 * 8, nullptr));
+  }
+  if (uid_prev != nullptr) {
+    AttnParams prev = p;
+    prev.uid = uid_prev; prev.tm = tm_prev;
+    RC(launch_attn_tilemap(prev, nullptr));
+  }
+  return launch_attn_tilemap(p, nullptr);
+}
 // expr, which names the element type Elt, with Elt = bf16 for RSYS_DTYPE_BF16 and Elt = float for any other dtype (a hook that takes
 // only the two checks its dtype first)
 #define BY_DTYPE(dtype, ...) \
@@ -254,15 +277,14 @@ int32_t rsys_op_attention_ex(int32_t dtype, int32_t B, int32_t T, int32_t H, int
   p.o = O; p.ldo = (long long)H * hd; p.lse = lse; p.uid = uid; p.tm = tm;
   HookScratch scratch("rsys_op_attention");
   AttnMaps maps; float* delta = nullptr;
-  RC(attn_maps_alloc(maps, B, T, H, KV, [&](void** b, size_t bytes) { return scratch.alloc(b, bytes); }));
   RC(scratch.get(&delta, (size_t)B * H * T));
-  maps.apply(p); p.delta = delta;
+  p.delta = delta;
   p.dO = dO; p.dq = dqkv; p.dk = (unsigned char*)dqkv + (size_t)H * hd * e;
   p.dv = (unsigned char*)dqkv + (size_t)(H + KV) * hd * e; p.ldg = p.ld;
   p.rope_cos = rope_cos; p.rope_sin = rope_sin; p.rope_pos = rope_pos; p.q_active = q_active;
   // (delta of the query tiles beyond q_active is never written: NaN there, so that a dK/dV kernel that reads it shows)
   if (q_active) HIP_CHECK(hipMemsetAsync(delta, 0xFF, sizeof(float) * B * H * T, nullptr));
-  int rc = launch_attn_tilemap(p, nullptr);
+  int rc = hook_attn_maps(scratch, p, maps);
   p.f8_amax = amax_fwd;
   if (!rc) rc = BY_DTYPE(dtype, launch_attn_fwd<Elt>(p, nullptr));
   p.f8_amax = amax_bwd;
@@ -289,11 +311,63 @@ int32_t rsys_op_attention_selected(int32_t dtype, int32_t B, int32_t T, int32_t 
   p.ld = (long long)(H + 2 * KV) * hd; p.uid = uid; p.tm = tm;
   HookScratch scratch("rsys_op_attention_selected");
   AttnMaps maps;
-  RC(attn_maps_alloc(maps, B, T, H, KV, [&](void** b, size_t bytes) { return scratch.alloc(b, bytes); }));
-  maps.apply(p);
-  int rc = launch_attn_tilemap(p, nullptr);
+  int rc = hook_attn_maps(scratch, p, maps);
   if (!rc) rc = BY_DTYPE(dtype, launch_attn_sel<Elt>(p, sel, n_sel, O, (long long)H * hd, nullptr));
   return hook_finish(rc);
+}
+
+// launch_attn_tilemap alone, through hook_attn_maps as the two hooks above reach it; no attention kernel runs
+int32_t rsys_op_attention_maps(int32_t dtype, int32_t B, int32_t T, int32_t H, int32_t KV, int32_t hd, const int32_t* uid, const int32_t* tm,
+                               const int32_t* q_active, const int32_t* uid_prev, const int32_t* tm_prev, void* qmap, void* kmap,
+                               void* qmap_full, void* kmap_full, void* qmap16, void* kmap16, uint64_t* qbits, uint64_t* kbits,
+                               int32_t* order_q, int32_t* order_k, int32_t* info) {
+  switches_parse();
+  ARG_CHECK(dtype == RSYS_DTYPE_BF16 || dtype == RSYS_DTYPE_FP32, "rsys_op_attention_maps: dtype fp32 or bf16");
+  ARG_CHECK(B >= 1 && T >= 1 && H >= 1 && KV >= 1 && hd >= 1 && uid && tm, "rsys_op_attention_maps: null or empty");
+  ARG_CHECK(H % KV == 0, "rsys_op_attention_maps: H must be a multiple of KV");
+  ARG_CHECK(T % 8 == 0 && T <= 4096, "rsys_op_attention_maps: T must be a multiple of 8 and <= 4096");
+  ARG_CHECK((uid_prev == nullptr) == (tm_prev == nullptr), "rsys_op_attention_maps: uid_prev and tm_prev come together");
+  ARG_CHECK(qmap && kmap && qmap_full && kmap_full && qmap16 && kmap16 && qbits && kbits && order_q && order_k && info,
+            "rsys_op_attention_maps: null output");
+  const size_t nt = (size_t)(T + 63) / 64, n_tok = (size_t)B * T;
+  {   // the token keys' ranges (attn_tilemap_kernel takes them on trust) and q_active, one copy back each
+    std::vector<int> h;
+    for (const int32_t* ids : {uid, uid_prev}) {
+      if (ids == nullptr) continue;
+      RC(hook_ints(ids, (long long)n_tok, h));
+      for (int v : h) ARG_CHECK(v >= 0 && v < (1 << 19), "rsys_op_attention_maps: a uid outside [0, 2^19)");
+    }
+    for (const int32_t* ids : {tm, tm_prev}) {
+      if (ids == nullptr) continue;
+      RC(hook_ints(ids, (long long)n_tok, h));
+      for (int v : h) ARG_CHECK(v >= 0 && v < 4096, "rsys_op_attention_maps: a tm outside [0, 4096)");
+    }
+    if (q_active != nullptr) {
+      RC(hook_ints(q_active, B, h));
+      for (int v : h) ARG_CHECK(v >= 0 && v <= (int)nt, "rsys_op_attention_maps: q_active outside [0, ceil(T / 64)]");
+    }
+  }
+  AttnParams p{};
+  p.B = B; p.T = T; p.H = H; p.KV = KV; p.hd = hd; p.is_bf16 = dtype == RSYS_DTYPE_BF16;
+  p.uid = uid; p.tm = tm; p.q_active = q_active;
+  HookScratch scratch("rsys_op_attention_maps");
+  AttnMaps maps;
+  RC(hook_finish(hook_attn_maps(scratch, p, maps, true, uid_prev, tm_prev)));
+  const size_t mapb = (size_t)B * nt * 4 * attn_map_words(T), bitb = (size_t)B * nt * nt * 64 * 8;
+  HIP_CHECK(hipMemcpy(qmap, maps.qmap, mapb, hipMemcpyDeviceToHost));
+  HIP_CHECK(hipMemcpy(kmap, maps.kmap, mapb, hipMemcpyDeviceToHost));
+  HIP_CHECK(hipMemcpy(qmap_full, maps.qmap_full, mapb, hipMemcpyDeviceToHost));
+  HIP_CHECK(hipMemcpy(kmap_full, maps.kmap_full, mapb, hipMemcpyDeviceToHost));
+  HIP_CHECK(hipMemcpy(qmap16, maps.qmap16, 4 * mapb, hipMemcpyDeviceToHost));
+  HIP_CHECK(hipMemcpy(kmap16, maps.kmap16, 4 * mapb, hipMemcpyDeviceToHost));
+  HIP_CHECK(hipMemcpy(qbits, maps.qbits, bitb, hipMemcpyDeviceToHost));
+  HIP_CHECK(hipMemcpy(kbits, maps.kbits, bitb, hipMemcpyDeviceToHost));
+  HIP_CHECK(hipMemcpy(order_q, maps.order_q, (size_t)B * H * nt * 4, hipMemcpyDeviceToHost));
+  HIP_CHECK(hipMemcpy(order_k, maps.order_k, (size_t)B * KV * nt * 4, hipMemcpyDeviceToHost));
+  const AttnOrderPlan o = attn_order_plan(p);
+  const int32_t facts[8] = {attn_map_words(T), o.R, o.kv_pairs, o.lists == 8 ? 1 : 0, o.n_inner_q, o.n_inner_k, o.identity, (int32_t)nt};
+  memcpy(info, facts, sizeof(facts));
+  return RSYS_OK;
 }
 
 int32_t rsys_op_attention_cached(int32_t dtype, int32_t rows, int32_t T, int32_t H, int32_t KV, int32_t hd, const void* qkv, const void* cache,

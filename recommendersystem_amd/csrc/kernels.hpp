@@ -243,6 +243,7 @@ struct AttnMaps {
   int *order_q = nullptr, *order_k = nullptr;
   unsigned long long *qbits = nullptr, *kbits = nullptr;
   void* zero_base = nullptr; size_t zero_bytes = 0;
+  size_t map_bytes = 0;   // one padded map (mb below): the twelve of them start at zero_base
   void apply(AttnParams& p) const {
     p.qmap = qmap; p.kmap = kmap; p.qmap_full = qmap_full; p.kmap_full = kmap_full; p.qmap16 = qmap16; p.kmap16 = kmap16;
     p.order_q = order_q; p.order_k = order_k; p.qbits = qbits; p.kbits = kbits;
@@ -260,12 +261,19 @@ int attn_maps_alloc(AttnMaps& a, long long rows, int T, int H, int KV, Alloc&& a
   if (int rc = alloc((void**)&base, (size_t)(mb * 12))) return rc;
   a.kmap = (unsigned int*)base; a.kmap_full = (unsigned int*)(base + mb); a.qmap_full = (unsigned int*)(base + 2 * mb); a.kmap16 = (unsigned int*)(base + 3 * mb);
   a.qmap = (unsigned int*)(base + 7 * mb); a.qmap16 = (unsigned int*)(base + 8 * mb);
-  a.zero_base = base; a.zero_bytes = (size_t)(7 * mb);
+  a.zero_base = base; a.zero_bytes = (size_t)(7 * mb); a.map_bytes = (size_t)mb;
   if (int rc = alloc((void**)&a.order_q, (size_t)(rows * H * nt * 4))) return rc;
   if (int rc = alloc((void**)&a.order_k, (size_t)(rows * KV * nt * 4))) return rc;
   if (int rc = alloc((void**)&a.qbits, (size_t)(rows * nt * nt * 64 * 8))) return rc;
   return alloc((void**)&a.kbits, (size_t)(rows * nt * nt * 64 * 8));
 }
+// What launch_attn_tilemap decides about the launch orders of a shape, on the host (the launch and rsys_op_attention_maps read it here):
+// R = query heads per workgroup, kv_pairs = order_k lists kv tile PAIRS, lists = 8 (one per XCD: B * KV a multiple of 8) or 1, n_inner_q /
+// n_inner_k = slots per (row, kv head) group on either side -- a list holds (B * KV / lists) * n_inner slots, order_q / order_k hold the
+// lists back to back --, identity = the longest possible list is beyond one workgroup's LDS (chunk_cap chunks of 64 slots): both orders
+// are then the identity permutation.
+struct AttnOrderPlan { int R, kv_pairs, lists, n_inner_q, n_inner_k, identity, chunk_cap, chunks; };
+AttnOrderPlan attn_order_plan(const AttnParams& p);
 int launch_attn_tilemap(const AttnParams& p, hipStream_t s);
 // Candidate attention against a cached history (rank_cache.hip; Finetune/embed.py:74-131's ranking row without its history half).  Row r of
 // qkv [rows * T][ld] holds n_cand[r] candidates, candidate j at tokens 2 j (item) and 2 j + 1 (action).  A query token of candidate j

@@ -1,6 +1,7 @@
 """Plain-numpy side of the attention op tests (tests/test_gpu_attention_parity.py, tests/test_gpu_ops.py): the float64 reference of the
 block-sparse masked attention forward + backward, the same computation with bf16 rounding at the kernels' rounding points, the tile-pair
-classes a launch contains, an input generator that produces every class, and the per-row error measure.  No GPU, no library."""
+classes a launch contains, the tile maps, pair bits and launch orders of a launch entry by entry (tests/test_gpu_attention_maps.py), an
+input generator that produces every class, and the per-row error measure.  No GPU, no library."""
 import numpy as np
 
 TILE = 64
@@ -95,7 +96,8 @@ def tile_classes(uid, tm):
     full when all 64 x 64 token pairs are allowed: the tokens past T of a ragged last tile are allowed nothing):
     empty / partial / full pair counts; idle_q16 / idle_k16 = groups of 16 queries (keys) without an allowed pair inside a non-empty
     pair (a wave of the forward / dQ (dK/dV) kernels that skips the tile); *_hi = the same counts over the pairs whose query or key tile
-    index is >= 16; q_tiles / k_tiles = the tile indices that occur in a non-empty pair as the query (key) side."""
+    index is >= 16; q_tiles / k_tiles = the tile indices that occur in a non-empty pair as the query (key) side.
+    tile_maps below is the entry-by-entry form of the same classification: the words the device must hold, not only their counts."""
     B, T = uid.shape
     nt = (T + TILE - 1) // TILE
     a = np.zeros((B, nt * TILE, nt * TILE), bool)
@@ -117,6 +119,99 @@ def tile_classes(uid, tm):
     out["q_tiles"] = sorted(set(np.nonzero(some.any((0, 2)))[0].tolist()))
     out["k_tiles"] = sorted(set(np.nonzero(some.any((0, 1)))[0].tolist()))
     return out
+
+
+def allowed_rows(uid, tm, b, q0, q1):
+    """rows q0 .. q1 - 1 of allowed_pairs(uid, tm)[b], without the [T][T] matrix"""
+    return (uid[b, q0:q1, None] == uid[b, None, :]) & ((tm[b, None, :] == 0) | (tm[b, q0:q1, None] == tm[b, None, :]))
+
+
+def popcount(x):
+    x = np.ascontiguousarray(x)
+    return np.unpackbits(x.view(np.uint8).reshape(x.shape + (x.dtype.itemsize,)), axis=-1).sum(-1).astype(np.int64)
+
+
+def _bits(flags, W):
+    """flags [..., n] bool -> [...] words of type W, bit j = flags[..., j]"""
+    n = flags.shape[-1]
+    return np.bitwise_or.reduce(flags.astype(W) << np.arange(n, dtype=W), axis=-1) if n else np.zeros(flags.shape[:-1], W)
+
+
+def tile_maps(uid, tm):
+    """Every word launch_attn_tilemap must write for these rows (csrc/kernels.hpp, AttnParams), from a[b, q, k] = allowed_pairs padded
+    with False beyond T to nt * 64, one query tile at a time.  W = uint32 for nt <= 32 tiles, else uint64:
+      qmap [B][nt] W: bit j = some pair allowed in (q tile, kv tile j); kmap [B][nt]: bit j = some pair in (q tile j, kv tile);
+      qmap_full / kmap_full: the same with "all 4096 pairs" (a ragged last tile is never full);
+      qmap16 [B][nt][4]: bit j = queries 16 g .. 16 g + 15 of the q tile have a pair in kv tile j;
+      kmap16 [B][nt][4]: bit j = keys 16 g .. 16 g + 15 of the kv tile are seen from q tile j;
+      qbits [B][qt][kt][64] uint64: bit k of word q = a[b, 64 qt + q, 64 kt + k]; kbits [B][kt][qt][64]: bit q of word k = the same pair."""
+    uid = np.asarray(uid); tm = np.asarray(tm)
+    B, T = uid.shape
+    nt = (T + TILE - 1) // TILE
+    W = np.uint32 if nt <= 32 else np.uint64
+    m = {k: np.zeros((B, nt), W) for k in ("qmap", "kmap", "qmap_full", "kmap_full")}
+    m["qmap16"] = np.zeros((B, nt, 4), W); m["kmap16"] = np.zeros((B, nt, 4), W)
+    m["qbits"] = np.zeros((B, nt, nt, TILE), np.uint64); m["kbits"] = np.zeros((B, nt, nt, TILE), np.uint64)
+    for b in range(B):
+        for qt in range(nt):
+            q0, q1 = qt * TILE, min(qt * TILE + TILE, T)
+            a = np.zeros((TILE, nt * TILE), bool)
+            a[:q1 - q0, :T] = allowed_rows(uid, tm, b, q0, q1)
+            a = a.reshape(TILE, nt, TILE)                                      # [q][kt][k]
+            cnt = a.sum((0, 2))
+            bit = W(1) << W(qt)
+            m["qmap"][b, qt] = _bits(cnt > 0, W)
+            m["qmap_full"][b, qt] = _bits(cnt == TILE * TILE, W)
+            m["kmap"][b] |= np.where(cnt > 0, bit, W(0))
+            m["kmap_full"][b] |= np.where(cnt == TILE * TILE, bit, W(0))
+            m["qmap16"][b, qt] = _bits(a.reshape(4, 16, nt, TILE).any((1, 3)), W)
+            m["kmap16"][b] |= np.where(a.reshape(TILE, nt, 4, 16).any((0, 3)), bit, W(0))
+            m["qbits"][b, qt] = np.ascontiguousarray(np.packbits(a.transpose(1, 0, 2), axis=-1, bitorder="little")).view("<u8")[..., 0]   # [kt][q]
+            m["kbits"][b, :, qt] = np.ascontiguousarray(np.packbits(a.transpose(1, 2, 0), axis=-1, bitorder="little")).view("<u8")[..., 0]  # [kt][k]
+    return m
+
+
+def order_keys(qmap, kmap, B, T, H, KV, R, kv_pairs, q_active=None):
+    """The work of every slot of the launch-order lists (csrc/kernels.hpp, AttnOrderPlan; attention_maps.hip, attn_order_kernel):
+    (keys_q [lists][ns_q], keys_k [lists][ns_k]).  8 lists when B * KV is a multiple of 8, slot sl of list x being group (sl // n_inner) * 8 + x
+    with group = b * KV + kv head; otherwise one list of all groups.  q side: n_inner = (H // KV // R) * nt, key = kv tiles the slot's q tile
+    (sl % n_inner) % nt visits, 0 for a tile >= q_active[b].  k side: n_inner = nt slots of one kv tile, or (nt + 1) // 2 slots of a
+    PAIR of kv tiles (kv_pairs; the second is absent when nt is odd), key = active q tiles the slot's tile(s) are visited by."""
+    nt = (T + TILE - 1) // TILE
+    W = qmap.dtype.type
+    groups = B * KV
+    lists = 8 if groups % 8 == 0 else 1
+    qa = np.full(B, nt, np.int64) if q_active is None else np.asarray(q_active, np.int64)
+    below = np.array([(1 << int(n)) - 1 for n in qa], dtype=W)                 # bits 0 .. q_active[b] - 1
+    work_q = np.where(np.arange(nt)[None, :] < qa[:, None], popcount(qmap), 0)          # [B][nt]
+    if kv_pairs:
+        pad = np.concatenate([kmap, np.zeros((B, nt % 2), W)], 1).reshape(B, (nt + 1) // 2, 2)
+        work_k = popcount((pad[:, :, 0] | pad[:, :, 1]) & below[:, None])
+    else:
+        work_k = popcount(kmap & below[:, None])
+    out = []
+    for work, n_inner in ((work_q, (H // KV // R) * nt), (work_k, work_k.shape[1])):
+        ns = groups // lists * n_inner
+        keys = np.zeros((lists, ns), np.int64)
+        for x in range(lists):
+            sl = np.arange(ns)
+            group = (sl // n_inner) * 8 + x if lists == 8 else sl // n_inner
+            keys[x] = work[group // KV, (sl % n_inner) % work.shape[1]]
+        out.append(keys)
+    return out[0], out[1]
+
+
+def launch_orders(qmap, kmap, B, T, H, KV, R, kv_pairs, q_active=None, identity=False):
+    """order_q [lists][ns_q], order_k [lists][ns_k] int32: per list the stable sort of its slots by descending work (order_keys) --
+    heaviest first, equal work in slot order --, or the identity permutation where the launch takes its fallback (a list too long for
+    one workgroup's table).  qmap / kmap: tile_maps' own, never the device's."""
+    out = []
+    for keys in order_keys(qmap, kmap, B, T, H, KV, R, kv_pairs, q_active):
+        if identity:
+            out.append(np.broadcast_to(np.arange(keys.shape[1], dtype=np.int32), keys.shape).copy())
+        else:
+            out.append(np.stack([np.argsort(-k, kind="stable") for k in keys]).astype(np.int32))
+    return out[0], out[1]
 
 
 def make_users(B, T, seed, long_at="low", long_len=None):
