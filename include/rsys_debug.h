@@ -267,6 +267,28 @@ int32_t rsys_op_f8_weights(const float* src, int64_t ld, int32_t rows, int32_t c
 int32_t rsys_op_gemm_f8(const void* A8, const void* B8, void* C, int32_t M, int32_t N, int32_t K, int64_t lda, int64_t ldb, int64_t ldc,
                         int32_t a_fmt, int32_t c_f32, const float* desc_dev, int32_t seg_cols, int32_t alt, int32_t kb0, int32_t kb1,
                         int32_t kb2);
+/* The grouped weight-gradient launch (csrc/gemm8p.hip: gemm8p_group_plan_create + launch_gemm8p_group), one plan of n products
+ * C_i[M_i][ldc_i] += A_i^T B_i with fp32 atomics, built as the training step builds them (c_f32, EPI_ATOMIC, alpha 1).  Host arrays of
+ * n entries each; A / B / C / f8_desc hold device pointers.
+ *   bf16 products (f8[i] == 0, desc / rseg / rowmode 0): K-major operands A [K][lda >= M], B [K][ldb >= N], M, N, lda, ldb % 8 == 0.
+ *   fp8 products (f8[i] == 2): A e5m2 [M][lda >= K], B e4m3 [N][ldb >= K], K % 128 == 0, K >= 256, lda, ldb % 16 == 0, N % 8 == 0;
+ *     f8_desc[i] = 32 device floats, output row r scaled by desc[r / f8_rseg] (f8_rseg 0: desc[0]; at most 16 segments);
+ *     f8_rowmode 1 (M % 32 == 0): row r is added to row (j >> 4) * 32 + is_b * 16 + (j & 15), j = r - is_b * M / 2 (GemmParams::f8_*).
+ *   One form per plan.  ordered != 0 (bf16 only, N % 4 == 0 and ldc % 4 == 0, C 16-byte aligned): the deterministic form, per-product
+ *     slabs cleared per launch and summed in split order.
+ *   launches >= 1: the one plan is launched that many times (C accumulates), then the call synchronises and destroys the plan.
+ * Reads the switches as the call parses them (RSYS_GEMM4K, RSYS_DEBUG_8G_SPLITK).  *splitk_out = the plan's K-split count, *kernel_out
+ * = the kernel launch_gemm8p_group ran (RSYS_GROUP_KERNEL_*).  What the plan refuses is RSYS_ERR_ARG with nothing launched.
+ * rsys_op_gemm_f8_splitk: one fp8 product of that form through launch_gemm8p_f8_splitk (its own K-split count), `launches` times. */
+#define RSYS_GROUP_KERNEL_8G 0  /* gemm8p_group_kernel (bf16, eight waves; also the ordered form) */
+#define RSYS_GROUP_KERNEL_4KG 1 /* gemm4k_group_kernel (bf16, the default where every product is eligible) */
+#define RSYS_GROUP_KERNEL_8GF 2 /* gemm8p_group_f8_kernel */
+int32_t rsys_op_gemm_group(int32_t n, const void* const* A, const void* const* B, void* const* C, const int32_t* M, const int32_t* N,
+                           const int32_t* K, const int64_t* lda, const int64_t* ldb, const int64_t* ldc, const int32_t* f8,
+                           const float* const* f8_desc, const int32_t* f8_rseg, const int32_t* f8_rowmode, int32_t ordered,
+                           int32_t launches, int32_t* splitk_out, int32_t* kernel_out);
+int32_t rsys_op_gemm_f8_splitk(const void* A8, const void* B8, void* C, int32_t M, int32_t N, int32_t K, int64_t lda, int64_t ldb,
+                               int64_t ldc, const float* desc_dev, int32_t rseg, int32_t rowmode, int32_t launches);
 /* row kernels between the products and the optimiser (csrc/elementwise.hip, csrc/optim.hip), unit-test access on caller-provided
  * device buffers; each calls the training step's launcher unchanged and synchronises.  dtype RSYS_DTYPE_FP32 / BF16 = the T of the
  * launcher (the storage type of y, g, dx_t, logits, z, hact; the shadow copy of AdamW).  deterministic != 0: the call runs with

@@ -220,6 +220,9 @@ _SIGS = [
     ("rsys_op_f8_weights", C.c_int32, [_P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, C.c_int64]),
     ("rsys_op_gemm_f8", C.c_int32, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32, _P,
                                       C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    ("rsys_op_gemm_group", C.c_int32, [C.c_int32] + [_P] * 13 + [C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    ("rsys_op_gemm_f8_splitk", C.c_int32, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64, _P,
+                                             C.c_int32, C.c_int32, C.c_int32]),
     ("rsys_op_gemm_rows", C.c_int32, [C.c_int32, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64,
                                       C.c_int32, C.c_int32, _P]),
     ("rsys_op_gemm_klimit", C.c_int32, [C.c_int32, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int32, _P]),

@@ -101,6 +101,15 @@ int hook_attn_maps(HookScratch& scratch, AttnParams& p, AttnMaps& maps, bool fil
   }
   return launch_attn_tilemap(p, nullptr);
 }
+// one product of the split-K weight-gradient forms as grouped_weight_grads / f8_dw_params build it
+GemmParams hook_dw_params(const void* A, const void* B, void* C, int32_t M, int32_t N, int32_t K, int64_t lda, int64_t ldb, int64_t ldc,
+                          int32_t f8, const float* f8_desc, int32_t f8_rseg, int32_t f8_rowmode) {
+  GemmParams p{};
+  p.A = A; p.B = B; p.C = C; p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldb = ldb; p.ldc = ldc;
+  p.c_f32 = 1; p.epi = EPI_ATOMIC; p.alpha = 1.f; p.splitk = 1;
+  p.f8 = f8; p.f8_desc = f8_desc; p.f8_rseg = f8_rseg; p.f8_rowmode = f8_rowmode;
+  return p;
+}
 // expr, which names the element type Elt, with Elt = bf16 for RSYS_DTYPE_BF16 and Elt = float for any other dtype (a hook that takes
 // only the two checks its dtype first)
 #define BY_DTYPE(dtype, ...) \
@@ -246,6 +255,41 @@ int32_t rsys_op_gemm_f8(const void* A8, const void* B8, void* C, int32_t M, int3
   p.c_f32 = c_f32; p.splitk = 1; p.alpha = 1.f; p.epi = EPI_STORE;
   p.f8 = a_fmt == F8_E5M2 ? 2 : 1; p.f8_desc = desc_dev; p.f8_seg_cols = seg_cols; p.f8_alt = alt; p.f8_kb[0] = kb0; p.f8_kb[1] = kb1; p.f8_kb[2] = kb2;
   return hook_finish(launch_gemm8p_f8(p, nullptr));
+}
+
+int32_t rsys_op_gemm_group(int32_t n, const void* const* A, const void* const* B, void* const* C, const int32_t* M, const int32_t* N,
+                           const int32_t* K, const int64_t* lda, const int64_t* ldb, const int64_t* ldc, const int32_t* f8,
+                           const float* const* f8_desc, const int32_t* f8_rseg, const int32_t* f8_rowmode, int32_t ordered,
+                           int32_t launches, int32_t* splitk_out, int32_t* kernel_out) {
+  switches_parse();
+  ARG_CHECK(n >= 0 && n <= 4096, "rsys_op_gemm_group: n outside 0..4096 (the plan takes 1..128 and says so)");
+  ARG_CHECK(n == 0 || (A && B && C && M && N && K && lda && ldb && ldc && f8 && f8_desc && f8_rseg && f8_rowmode), "rsys_op_gemm_group: null array");
+  ARG_CHECK(launches >= 1 && splitk_out != nullptr && kernel_out != nullptr, "rsys_op_gemm_group: launches >= 1, outputs not null");
+  std::vector<GemmParams> ps((size_t)n);
+  for (int i = 0; i < n; ++i) {
+    ARG_CHECK(A[i] != nullptr && B[i] != nullptr && C[i] != nullptr, "rsys_op_gemm_group: null operand");
+    ps[i] = hook_dw_params(A[i], B[i], C[i], M[i], N[i], K[i], lda[i], ldb[i], ldc[i], f8[i], f8_desc[i], f8_rseg[i], f8_rowmode[i]);
+  }
+  GemmGroupPlan* pl = nullptr;
+  RC(gemm8p_group_plan_create(ps.data(), n, &pl, ordered != 0));
+  *splitk_out = gemm8p_group_splitk(pl);
+  *kernel_out = ps[0].f8 != 0 ? RSYS_GROUP_KERNEL_8GF : (gemm8p_group_on_4k(pl) ? RSYS_GROUP_KERNEL_4KG : RSYS_GROUP_KERNEL_8G);
+  int rc = RSYS_OK;
+  for (int i = 0; i < launches && rc == RSYS_OK; ++i) rc = launch_gemm8p_group(pl, nullptr);
+  rc = hook_finish(rc);
+  gemm8p_group_plan_destroy(pl);   // (behind the synchronise: the plan owns the work lists and the slabs)
+  return rc;
+}
+
+int32_t rsys_op_gemm_f8_splitk(const void* A8, const void* B8, void* C, int32_t M, int32_t N, int32_t K, int64_t lda, int64_t ldb, int64_t ldc,
+                               const float* desc_dev, int32_t rseg, int32_t rowmode, int32_t launches) {
+  switches_parse();
+  ARG_CHECK(A8 != nullptr && B8 != nullptr && C != nullptr, "rsys_op_gemm_f8_splitk: null operand");
+  ARG_CHECK(launches >= 1, "rsys_op_gemm_f8_splitk: launches >= 1");
+  const GemmParams p = hook_dw_params(A8, B8, C, M, N, K, lda, ldb, ldc, 2, desc_dev, rseg, rowmode);
+  int rc = RSYS_OK;
+  for (int i = 0; i < launches && rc == RSYS_OK; ++i) rc = launch_gemm8p_f8_splitk(p, nullptr);
+  return hook_finish(rc);
 }
 
 int32_t rsys_op_attention(int32_t dtype, int32_t B, int32_t T, int32_t H, int32_t KV, int32_t hd, const void* qkv,

@@ -17,7 +17,8 @@ Which (epilogue x family) combinations exist -- `eligible` below restates the ro
   gemm8c, RoPE with rope_pos or c_f32     gemm8c_eligible: `case EPI_QKV_ROPE: return p.rope_pos == nullptr && !p.c_f32`
   gemm8c HALF, accumulate and table       c8_half_class (gemm8c.hip): the `default: return false` of its switch
   gemm8c HALF, store with c_f32           c8_half_class: `case EPI_STORE: return !p.c_f32`
-(EPI_ATOMIC, the split-K, K-major-A and grouped kernels and the fp8 fields belong to test_gpu_ops.py and test_gpu_fp8_*.py.)
+(EPI_ATOMIC, the split-K and K-major-A kernels belong to test_gpu_ops.py, the fp8 fields to test_gpu_fp8_*.py, the grouped kernels and
+the fp8 split-K form to test_gpu_gemm_group.py.)
 
 Exactness first.  Small-integer operands make the accumulators exact integers, and every epilogue operand (bias, residual, E, prior C,
 alpha in {1, 2, 0.5}) is a small dyadic number: store, accumulate, bias, residual and table results are then exact in fp32 and must be
