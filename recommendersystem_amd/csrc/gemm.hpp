@@ -30,7 +30,8 @@ enum GemmFlag : int {
   GEMM_BAND_SHIFT = 3,                // bits 3-6: gemm8c / gemm4p walk the tiles in bands of that many tile rows (set by their launchers)
   GEMM_BAND_MASK = 15 << GEMM_BAND_SHIFT,
   GEMM_SPLITK_256 = 1 << 7,           // EPI_ATOMIC row-major product on the 256x256 split-K kernel whatever its tile count
-  GEMM_REVERSE_ROWS = 1 << 8          // gemm8c walks its tile rows from the last to the first (the caller's A was written just before, front to back)
+  GEMM_REVERSE_ROWS = 1 << 8          // gemm8c walks its tile rows from the last to the first (the caller's A was written just before, front to back).
+                                      // Set by the call site; the bit is ignored on the gemm4p path, which runs its persistent grid in its own order.
 };
 
 struct GemmParams {

@@ -1063,10 +1063,9 @@ static int infer_rows_t(Model* m, int task, const int* d_sel, int64_t ntok, floa
   }
   for (int64_t r0 = 0; r0 < ntok; r0 += KB) {
     const int nr = (int)std::min<int64_t>(KB, ntok - r0);
-    GemmParams p{};
-    p.A = (const unsigned char*)src + (size_t)r0 * D * m->esz; p.lda = D; p.B = W<T>(m, m->o_r0w); p.ldb = D; p.C = m->z; p.ldc = D;
-    p.M = nr; p.N = D; p.K = D; p.epi = EPI_GELU; p.bias = m->P + m->o_r0b; p.C2 = m->hact; p.ldc2 = D;
-    RC(gemm<T>(m, "gemm_rating_fwd", p, false, false, false));
+    StepGemm p = gemm_xwt((const unsigned char*)src + (size_t)r0 * D * m->esz, D, W<T>(m, m->o_r0w), D, m->z, D, nr, D, D);
+    p.epi = EPI_GELU; p.bias = m->P + m->o_r0b; p.C2 = m->hact; p.ldc2 = D;
+    RC(gemm<T>(m, "gemm_rating_fwd", p));
     RC(launch_rowdot<T>(AT<T>(m->hact), m->P + m->o_r2w, m->P + m->o_r2b, dst + r0, nr, D, s));
   }
   return RSYS_OK;

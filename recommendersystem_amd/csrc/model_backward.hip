@@ -26,64 +26,97 @@ static int ensure_transposes(Model* m) {
   return RSYS_OK;
 }
 
-// Backward of top_tail_compact for the last layer: W2 / SwiGLU / W13 / RMSNorm / Wo on the compact rows (gradients of all other
-// tokens are identically zero there), then d(attention output) scattered into the zeroed dense buffer the attention backward reads.
-// The weight gradients reduce over the compact rows (k_dev); each has one operand whose rows [n, n rounded up to 256) are zero.
+// dX = dY . W for a trunk weight W [n_out][n_in] at offset `off`: bf16 mode reads the row-major transposed copy (ensure_transposes),
+// the fp32 parity mode W itself, K-major
 template <typename T>
-static int top_tail_compact_bwd(Model* m, bool wt) {
-  const int D = m->D, Ip = m->Ip, l = m->L - 1, cap = m->ctop_cap, NT = 2 * m->cur_rows * m->S;
+static StepGemm gemm_dx(Model* m, const void* dY, int64_t off, int n_out, int n_in, void* dX, long long ldx, int M) {
+  if (m->bf16_mode) return gemm_xwt(dY, n_out, WT<T>(m, off), n_out, dX, ldx, M, n_in, n_out);
+  return gemm_dyw(dY, n_out, W<T>(m, off), n_in, dX, ldx, M, n_in, n_out);
+}
+
+// The rows the backward of a token-local tail runs on (model_forward.hip TailRows): what the forward kept of them, the gradient of the
+// layer's output as fp32 residual (gx) and as GEMM operand (gxt), and where the gradients of the chain go.
+struct TailGrads {
+  int l, M;                         // layer; rows (compact: the buffers' capacity)
+  const int* n_dev; int k_expect;   // compact: the device-side row count and the host's estimate of it; nullptr / 0: all M rows
+  void *O, *hn, *ab, *g; float *h, *rstd2;
+  void* gxt; float* gx;
+  void *dab, *dhn; float* dh; void *dht, *dO;
+  const char *tag_w2_dw, *tag_w2_dx, *tag_w13_dw, *tag_w13_dx, *tag_norm, *tag_o_dw, *tag_o_dx;   // (tag_norm == nullptr: not timed on its own)
+  bool dense;                       // the dense rows' extras: the fp8 products, their weight gradients and f8_keep copies, reversed tile rows of W13's dx
+};
+static TailGrads tail_grads_dense(Model* m, int l, float* gx, void* gxt, void* dab, void* dht) {
+  Model::LayerAct& a = m->la[l];
+  return {l, 2 * m->cur_rows * m->S, nullptr, 0, a.O, a.hn, a.ab, a.g, a.h, a.rstd2, gxt, gx, dab, m->dhn, m->dh, dht, m->dO,
+          "gemm_w2_dw", "gemm_w2_dx", "gemm_w13_dw", "gemm_w13_dx", "hbm_rmsnorm_bwd", "gemm_o_dw", "gemm_o_dx", true};
+}
+static TailGrads tail_grads_compact(Model* m) {
+  return {m->L - 1, m->ctop_cap, m->c_n, expected_selected(m), m->c_O, m->c_hn, m->c_ab, m->c_g, m->c_h, m->c_rstd2, m->c_gx_t, m->c_gx,
+          m->c_dab, m->c_dhn, m->c_dh, m->c_dh_t, m->c_dO,
+          "gemm_top_w2_dw", "gemm_top_w2_dx", "gemm_top_w13_dw", "gemm_top_w13_dx", nullptr, "gemm_top_o_dw", "gemm_top_o_dx", false};
+}
+
+// Backward of layer_tail: W2 / SwiGLU / W13 / RMSNorm / Wo.  The weight gradients run in line here unless the base weights are frozen
+// (finetune / adapter bank: only the dx chain runs, the LoRA tensors sit before the attention) or the dense rows' products are deferred
+// to the grouped launch or run on the fp8 copies (behind the cast of their gradient operand, inside the dx product).  On compact rows they
+// reduce over the device-side row count; each has one operand whose rows [n, n rounded up to 256) are zero.
+template <typename T>
+static int layer_tail_bwd(Model* m, const TailGrads& r, bool defer) {
+  const int D = m->D, Ip = m->Ip, l = r.l;
   hipStream_t s = m->stream;
-  const int* n = m->c_n;
-  const bool cp = m->bf16_mode;
-  const bool ft = trunk_frozen(m);   // finetune / adapter bank: the base weights are frozen, only the dx chain runs here (the LoRA tensors sit before the attention)
+  const bool cp = m->bf16_mode;   // fp32 mode: the operand IS the fp32 buffer, no copy
+  const bool f8 = r.dense && m->fp8, f8dw = r.dense && use_f8_dw(m);
+  const bool dw = !trunk_frozen(m) && (!r.dense || (!defer && !f8dw));
+  auto weight_grad = [&](const char* tag, const void* dY, long long ldy, const void* X, long long ldx, int64_t off, int M, int N) -> int {
+    StepGemm p = gemm_dytx(dY, ldy, X, ldx, m->G + off, N, M, N, r.M);
+    p.k_dev = r.n_dev; p.k_expect = r.k_expect;
+    return gemm<T>(m, tag, p);
+  };
+  if (dw) RC(weight_grad(r.tag_w2_dw, r.gxt, D, r.g, Ip, m->lo[l].w2, D, Ip));   // dW2 += gx^T . g
+  {
+    StepGemm p = gemm_dx<T>(m, r.gxt, m->lo[l].w2, D, Ip, r.dab, 2 * Ip, r.M);   // dg = gx . W2, fused with the SwiGLU backward: writes [da|db] directly
+    p.epi = EPI_SWIGLU_BWD; p.C2 = r.ab; p.ldc2 = 2 * Ip; p.m_dev = r.n_dev;
+    if (f8) { p.f8_amax_out = f8_slot(m, l, F8S_DAB); RC(gemm_f8(m, l, F8P_W2_DX, r.tag_w2_dx, p, W8T(m, m->lo[l].w2), D, true)); }
+    else RC(gemm<T>(m, r.tag_w2_dx, p));
+    if (f8dw && !defer) RC(f8_dw_launch(m, l, 0, r.tag_w2_dw, r.M));
+  }
+  if (dw) RC(weight_grad(r.tag_w13_dw, r.dab, 2 * Ip, r.hn, D, m->lo[l].w13, 2 * Ip, D));   // dW13 += dab^T . hn
+  {
+    StepGemm p = gemm_dx<T>(m, r.dab, m->lo[l].w13, 2 * Ip, D, r.dhn, D, r.M);   // dhn = dab . W13
+    p.m_dev = r.n_dev;
+    // Tile rows from the LAST to the first, as the forward's W2 product (model_forward.hip layer_tail): this one reads dab behind w2_dx
+    // (profiles/r6_ab_reverse_tile_rows.log: -2.4 % at this call site, nothing at the compact rows).
+    if (r.dense && !f8) p.flags = GEMM_REVERSE_ROWS;
+    if (f8) RC(gemm_f8(m, l, F8P_W13_DX, r.tag_w13_dx, p, W8T(m, m->lo[l].w13), 2 * Ip, true));   // (amax |da|, |db| came with the SwiGLU-backward epilogue)
+    else RC(gemm<T>(m, r.tag_w13_dx, p));
+    if (f8dw && !defer) RC(f8_dw_launch(m, l, 1, r.tag_w13_dw, r.M));
+    if (r.dense && !m->f8_keep.empty()) HIP_CHECK(hipMemcpyAsync(m->f8_keep[l * 3 + 0], r.dhn, (size_t)r.M * D * 2, hipMemcpyDeviceToDevice, s));
+  }
+  if (r.tag_norm) tic(m, r.tag_norm, (sizeof(T) + 4.0 + 4.0 + 4.0 + (cp ? 2.0 : 0.0)) * D * r.M);   // g, x, residual gradient in; dx (+ its bf16 operand copy) out
+  RC(launch_rmsnorm_bwd<T>(AT<T>(r.dhn), r.h, m->P + m->lo[l].mlp, r.rstd2, r.gx, r.dh, cp ? AT<T>(r.dht) : nullptr, small_grad(m, m->lo[l].mlp), r.M, D, s,
+                           r.n_dev, nullptr, nullptr, f8 ? f8_slot(m, l, F8S_DH) : nullptr));
+  if (r.tag_norm) toc(m);
+  if (dw) RC(weight_grad(r.tag_o_dw, r.dht, D, r.O, D, m->lo[l].wo, D, D));   // dWo += dh^T . O
+  {
+    StepGemm p = gemm_dx<T>(m, r.dht, m->lo[l].wo, D, D, r.dO, D, r.M);   // dO = dh . Wo
+    p.m_dev = r.n_dev;
+    if (f8) RC(gemm_f8(m, l, F8P_O_DX, r.tag_o_dx, p, W8T(m, m->lo[l].wo), D, true));
+    else RC(gemm<T>(m, r.tag_o_dx, p));
+    if (f8dw && !defer) RC(f8_dw_launch(m, l, 2, r.tag_o_dw, r.M));
+    if (r.dense && !m->f8_keep.empty()) HIP_CHECK(hipMemcpyAsync(m->f8_keep[l * 3 + 1], r.dO, (size_t)r.M * D * 2, hipMemcpyDeviceToDevice, s));
+  }
+  return RSYS_OK;
+}
+
+// That backward for the last layer's compact rows (gradients of all other tokens are identically zero there), then d(attention output)
+// scattered into the dense buffer the attention backward reads.
+template <typename T>
+static int top_tail_compact_bwd(Model* m) {
   tic(m, "phase_top_compact_bwd");
-  if (!ft) {
-    GemmParams p{};  // dW2 += gx^T . g
-    p.A = m->c_gx_t; p.lda = D; p.B = m->c_g; p.ldb = Ip; p.C = m->G + m->lo[l].w2; p.ldc = Ip; p.c_f32 = 1;
-    p.M = D; p.N = Ip; p.K = cap; p.epi = EPI_ATOMIC; p.k_dev = n;
-    p.k_expect = expected_selected(m);
-    RC(gemm<T>(m, "gemm_top_w2_dw", p, false, true, true));
-  }
-  {
-    GemmParams p{};  // dg = gx . W2, fused with the SwiGLU backward
-    p.A = m->c_gx_t; p.lda = D; p.B = W<T>(m, m->lo[l].w2); p.ldb = Ip; p.C = m->c_dab; p.ldc = 2 * Ip;
-    if (wt) { p.B = WT<T>(m, m->lo[l].w2); p.ldb = D; }
-    p.M = cap; p.N = Ip; p.K = D; p.epi = EPI_SWIGLU_BWD; p.C2 = m->c_ab; p.ldc2 = 2 * Ip; p.m_dev = n;
-    RC(gemm<T>(m, "gemm_top_w2_dx", p, false, false, !wt));
-  }
-  if (!ft) {
-    GemmParams p{};  // dW13 += dab^T . hn
-    p.A = m->c_dab; p.lda = 2 * Ip; p.B = m->c_hn; p.ldb = D; p.C = m->G + m->lo[l].w13; p.ldc = D; p.c_f32 = 1;
-    p.M = 2 * Ip; p.N = D; p.K = cap; p.epi = EPI_ATOMIC; p.k_dev = n;
-    p.k_expect = expected_selected(m);
-    RC(gemm<T>(m, "gemm_top_w13_dw", p, false, true, true));
-  }
-  {
-    GemmParams p{};  // dhn = dab . W13
-    p.A = m->c_dab; p.lda = 2 * Ip; p.B = W<T>(m, m->lo[l].w13); p.ldb = D; p.C = m->c_dhn; p.ldc = D;
-    if (wt) { p.B = WT<T>(m, m->lo[l].w13); p.ldb = 2 * Ip; }
-    p.M = cap; p.N = D; p.K = 2 * Ip; p.epi = EPI_STORE; p.m_dev = n;
-    RC(gemm<T>(m, "gemm_top_w13_dx", p, false, false, !wt));
-  }
-  RC(launch_rmsnorm_bwd<T>(AT<T>(m->c_dhn), m->c_h, m->P + m->lo[l].mlp, m->c_rstd2, m->c_gx, m->c_dh, cp ? AT<T>(m->c_dh_t) : nullptr,
-                           small_grad(m, m->lo[l].mlp), cap, D, s, n));
-  if (!ft) {
-    GemmParams p{};  // dWo += dh^T . O
-    p.A = m->c_dh_t; p.lda = D; p.B = m->c_O; p.ldb = D; p.C = m->G + m->lo[l].wo; p.ldc = D; p.c_f32 = 1;
-    p.M = D; p.N = D; p.K = cap; p.epi = EPI_ATOMIC; p.k_dev = n;
-    p.k_expect = expected_selected(m);
-    RC(gemm<T>(m, "gemm_top_o_dw", p, false, true, true));
-  }
-  {
-    GemmParams p{};  // dO = dh . Wo
-    p.A = m->c_dh_t; p.lda = D; p.B = W<T>(m, m->lo[l].wo); p.ldb = D; p.C = m->c_dO; p.ldc = D;
-    if (wt) p.B = WT<T>(m, m->lo[l].wo);
-    p.M = cap; p.N = D; p.K = D; p.epi = EPI_STORE; p.m_dev = n;
-    RC(gemm<T>(m, "gemm_top_o_dx", p, false, false, !wt));
-  }
+  RC(layer_tail_bwd<T>(m, tail_grads_compact(m), false));
   // dO in selected-first order, as the attention backward reads it: the selected places from the compact rows, zeros up to the end of the last
   // query tile the kernels visit (c_qact); nothing is read beyond (round 6: was a 2 NT D-byte zero fill + a scatter)
-  RC(launch_scatter_rows_fill<T>(AT<T>(m->c_dO), m->c_slot_p, m->c_qact, m->cur_rows, m->T, AT<T>(m->dO), D, D, s));
+  RC(launch_scatter_rows_fill<T>(AT<T>(m->c_dO), m->c_slot_p, m->c_qact, m->cur_rows, m->T, AT<T>(m->dO), m->D, m->D, m->stream));
   toc(m);
   return RSYS_OK;
 }
@@ -103,8 +136,8 @@ static int grouped_weight_grads(Model* m, int l_lo, int l_hi) {
       const Model::LayerAct& a = m->la[l];
       const Model::DwOperands& o = m->dwb[l];
       auto add = [&](const void* A, long long lda, const void* B, long long ldb, float* C, long long ldc, int M, int N) {
-        GemmParams p{};
-        p.A = A; p.lda = lda; p.B = B; p.ldb = ldb; p.C = C; p.ldc = ldc; p.c_f32 = 1; p.M = M; p.N = N; p.K = NT; p.epi = EPI_ATOMIC; p.alpha = 1.f;
+        GemmParams p = gemm_dytx(A, lda, B, ldb, C, ldc, M, N, NT);
+        p.alpha = 1.f;
         ps.push_back(p);
       };
       const bool full = !(top_compact && l == m->L - 1);
@@ -151,7 +184,6 @@ int backward_trunk(Model* m) {
   const bool ctop = m->top_is_sparse;
   if (defer && !ctop) gxt = AT<T>(m->dwb[m->L - 1].gxt);
   RC(ensure_transposes(m));
-  const bool wt = m->bf16_mode;   // dx GEMMs: row-major W^T (bf16 mode) or the K-major read of W itself (fp32 parity mode)
   tic(m, "phase_trunk_bwd");
   const double nb_bytes = (sizeof(T) + 4.0 + 4.0 + 4.0 + (cp ? 2.0 : 0.0)) * D * NT;   // g, x, residual gradient in; dx (+ its bf16 operand copy) out
   if (ctop) {   // final norm on the compact rows: c_gx = d(last layer's output) at the selected tokens, zero everywhere else
@@ -163,11 +195,6 @@ int backward_trunk(Model* m) {
                                  m->fp8 ? f8_slot(m, m->L - 1, F8S_DY2) : nullptr));   // (fp8: the top layer's W2 takes this gradient as its dy)
     toc(m);
   }
-  AttnParams ap{};
-  ap.B = rows; ap.T = m->T; ap.H = m->H; ap.KV = m->KV; ap.hd = hd; ap.is_bf16 = is_bf16<T>::value ? 1 : 0;
-  ap.uid = m->uid_t; ap.tm = m->tm_t;
-  m->maps.apply(ap);
-  ap.rope_cos = m->rope_cos; ap.rope_sin = m->rope_sin; ap.rope_pos = rpos;
   int bucket_top = m->L - 1;
   for (int l = m->L - 1; l >= 0; --l) {
     Model::LayerAct& a = m->la[l];
@@ -178,88 +205,24 @@ int backward_trunk(Model* m) {
     void* const dab = (defer && !top) ? m->dwb[l].dab : m->dab;
     void* const dqkv = defer ? m->dwb[l].dqkv : m->dqkv;
     if (defer) { if (!top) dht = AT<T>(m->dwb[l].dht); gxt_other = l > 0 ? AT<T>(m->dwb[l - 1].gxt) : AT<T>(m->gxa_t); }
-    if (top) RC(top_tail_compact_bwd<T>(m, wt));
-    if (!top) {
-    if (!ft && !defer && !f8dw) {
-      GemmParams p{};  // dW2 += gx^T . g
-      p.A = gxt; p.lda = D; p.B = a.g; p.ldb = Ip; p.C = m->G + m->lo[l].w2; p.ldc = Ip; p.c_f32 = 1;
-      p.M = D; p.N = Ip; p.K = NT; p.epi = EPI_ATOMIC;
-      RC(gemm<T>(m, "gemm_w2_dw", p, false, true, true));
-    }
-    {
-      GemmParams p{};  // dg = gx . W2, fused with the SwiGLU backward: writes [da|db] directly
-      p.A = gxt; p.lda = D; p.B = W<T>(m, m->lo[l].w2); p.ldb = Ip; p.C = dab; p.ldc = 2 * Ip;
-      if (wt) { p.B = WT<T>(m, m->lo[l].w2); p.ldb = D; }
-      p.M = NT; p.N = Ip; p.K = D; p.epi = EPI_SWIGLU_BWD; p.C2 = a.ab; p.ldc2 = 2 * Ip;
-      if (m->fp8) { p.f8_amax_out = f8_slot(m, l, F8S_DAB); RC(gemm_f8(m, l, F8P_W2_DX, "gemm_w2_dx", p, W8T(m, m->lo[l].w2), D, true)); }
-      else RC(gemm<T>(m, "gemm_w2_dx", p, false, false, !wt));
-      if (f8dw && !defer) RC(f8_dw_launch(m, l, 0, "gemm_w2_dw", NT));
-    }
-    if (!ft && !defer && !f8dw) {
-      GemmParams p{};  // dW13 += dab^T . hn
-      p.A = dab; p.lda = 2 * Ip; p.B = a.hn; p.ldb = D; p.C = m->G + m->lo[l].w13; p.ldc = D; p.c_f32 = 1;
-      p.M = 2 * Ip; p.N = D; p.K = NT; p.epi = EPI_ATOMIC;
-      RC(gemm<T>(m, "gemm_w13_dw", p, false, true, true));
-    }
-    {
-      GemmParams p{};  // dhn = dab . W13
-      p.A = dab; p.lda = 2 * Ip; p.B = W<T>(m, m->lo[l].w13); p.ldb = D; p.C = m->dhn; p.ldc = D;
-      if (wt) { p.B = WT<T>(m, m->lo[l].w13); p.ldb = 2 * Ip; }
-      p.M = NT; p.N = D; p.K = 2 * Ip; p.epi = EPI_STORE;
-      if (m->fp8) RC(gemm_f8(m, l, F8P_W13_DX, "gemm_w13_dx", p, W8T(m, m->lo[l].w13), 2 * Ip, true));   // (amax |da|, |db| came with the SwiGLU-backward epilogue)
-      else RC(gemm<T>(m, "gemm_w13_dx", p, false, false, !wt));
-      if (f8dw && !defer) RC(f8_dw_launch(m, l, 1, "gemm_w13_dw", NT));
-      if (!m->f8_keep.empty()) HIP_CHECK(hipMemcpyAsync(m->f8_keep[l * 3 + 0], m->dhn, (size_t)NT * D * 2, hipMemcpyDeviceToDevice, s));
-    }
-    tic(m, "hbm_rmsnorm_bwd", nb_bytes);
-    RC(launch_rmsnorm_bwd<T>(AT<T>(m->dhn), a.h, m->P + m->lo[l].mlp, a.rstd2, gx, m->dh, cp ? dht : nullptr, small_grad(m, m->lo[l].mlp), NT, D, s, nullptr, nullptr, nullptr,
-                             m->fp8 ? f8_slot(m, l, F8S_DH) : nullptr));
-    toc(m);
-    if (!ft && !defer && !f8dw) {
-      GemmParams p{};  // dWo += dh^T . O
-      p.A = dht; p.lda = D; p.B = a.O; p.ldb = D; p.C = m->G + m->lo[l].wo; p.ldc = D; p.c_f32 = 1;
-      p.M = D; p.N = D; p.K = NT; p.epi = EPI_ATOMIC;
-      RC(gemm<T>(m, "gemm_o_dw", p, false, true, true));
-    }
-    {
-      GemmParams p{};  // dO = dh . Wo
-      p.A = dht; p.lda = D; p.B = W<T>(m, m->lo[l].wo); p.ldb = D; p.C = m->dO; p.ldc = D;
-      if (wt) p.B = WT<T>(m, m->lo[l].wo);
-      p.M = NT; p.N = D; p.K = D; p.epi = EPI_STORE;
-      if (m->fp8) RC(gemm_f8(m, l, F8P_O_DX, "gemm_o_dx", p, W8T(m, m->lo[l].wo), D, true));
-      else RC(gemm<T>(m, "gemm_o_dx", p, false, false, !wt));
-      if (f8dw && !defer) RC(f8_dw_launch(m, l, 2, "gemm_o_dw", NT));
-      if (!m->f8_keep.empty()) HIP_CHECK(hipMemcpyAsync(m->f8_keep[l * 3 + 1], m->dO, (size_t)NT * D * 2, hipMemcpyDeviceToDevice, s));
-    }
-    }   // !top
-    ap.q = a.qkv; ap.k = AT<T>(a.qkv) + m->H * hd; ap.v = AT<T>(a.qkv) + (m->H + m->KV) * hd; ap.ld = m->Nqkv;
-    ap.o = a.O; ap.ldo = D; ap.lse = a.lse;
+    if (top) RC(top_tail_compact_bwd<T>(m));
+    else RC(layer_tail_bwd<T>(m, tail_grads_dense(m, l, gx, gxt, dab, dht), defer));
+    // the last layer under the compact top: selected-first token order -- its ids, tile maps, RoPE positions; dO is non-zero in the leading query tiles only
+    AttnParams ap = layer_attn<T>(m, l, top ? TOKENS_SELECTED_FIRST : TOKENS_BATCH);
+    ap.rope_cos = m->rope_cos; ap.rope_sin = m->rope_sin; ap.rope_pos = top ? m->pos_p : rpos;
+    if (top) ap.q_active = m->c_qact;
     ap.dO = m->dO; ap.delta = m->delta;
     ap.dq = dqkv; ap.dk = AT<T>(dqkv) + m->H * hd; ap.dv = AT<T>(dqkv) + (m->H + m->KV) * hd; ap.ldg = m->Nqkv;
     ap.f8_amax = m->fp8 ? f8_slot(m, l, F8S_DQKV) : nullptr;
     tic(m, "attn_bwd");
-    if (top) {   // selected-first token order of the last layer: its ids, tile maps, RoPE positions; dO is non-zero in the leading query tiles only
-      AttnParams at = ap;
-      at.uid = m->uid_p; at.tm = m->tm_p; at.rope_pos = m->pos_p; at.q_active = m->c_qact;
-      m->maps_p.apply(at);
-      RC(launch_attn_bwd<T>(at, s));
-    } else {
-      RC(launch_attn_bwd<T>(ap, s));
-    }
+    RC(launch_attn_bwd<T>(ap, s));
     toc(m);
-    if (!ft && !defer && !f8dw) {
-      GemmParams p{};  // dWqkv += dqkv^T . xn
-      p.A = dqkv; p.lda = m->Nqkv; p.B = a.xn; p.ldb = D; p.C = m->G + m->lo[l].wqkv; p.ldc = D; p.c_f32 = 1;
-      p.M = m->Nqkv; p.N = D; p.K = NT; p.epi = EPI_ATOMIC;
-      RC(gemm<T>(m, "gemm_qkv_dw", p, false, true, true));
-    }
+    if (!ft && !defer && !f8dw)   // dWqkv += dqkv^T . xn
+      RC(gemm<T>(m, "gemm_qkv_dw", gemm_dytx(dqkv, m->Nqkv, a.xn, D, m->G + m->lo[l].wqkv, D, m->Nqkv, D, NT)));
     {
-      GemmParams p{};  // dxn = dqkv . Wqkv
-      p.A = dqkv; p.lda = m->Nqkv; p.B = W<T>(m, m->lo[l].wqkv); p.ldb = D; p.C = m->dhn; p.ldc = D;
-      if (wt) { p.B = WT<T>(m, m->lo[l].wqkv); p.ldb = m->Nqkv; }
-      p.M = NT; p.N = D; p.K = m->Nqkv; p.epi = EPI_STORE;
+      StepGemm p = gemm_dx<T>(m, dqkv, m->lo[l].wqkv, m->Nqkv, D, m->dhn, D, NT);   // dxn = dqkv . Wqkv
       if (m->fp8) RC(gemm_f8(m, l, F8P_QKV_DX, "gemm_qkv_dx", p, W8T(m, m->lo[l].wqkv), m->Nqkv, true));
-      else RC(gemm<T>(m, "gemm_qkv_dx", p, false, false, !wt));
+      else RC(gemm<T>(m, "gemm_qkv_dx", p));
       if (f8dw && !defer) RC(f8_dw_launch(m, l, 3, "gemm_qkv_dw", NT));
       if (!m->f8_keep.empty()) HIP_CHECK(hipMemcpyAsync(m->f8_keep[l * 3 + 2], m->dhn, (size_t)NT * D * 2, hipMemcpyDeviceToDevice, s));
     }
@@ -268,43 +231,29 @@ int backward_trunk(Model* m) {
       T* xnd = m->drop_active ? AT<T>(a.xnd) : AT<T>(a.xn);
       const int nq = m->H * hd, nv0 = (m->H + m->KV) * hd, nkv = m->KV * hd;
       {
-        GemmParams p{};  // dLa = 2 * dqkv . Bcat    (the unused blocks of Bcat are zero)
-        p.A = dqkv; p.lda = m->Nqkv; p.B = W<T>(m, m->lo[l].lb); p.ldb = 16; p.C = m->dLa; p.ldc = 16;
-        p.M = NT; p.N = 16; p.K = m->Nqkv; p.epi = EPI_STORE; p.alpha = 2.f;
-        RC(gemm<T>(m, "gemm_lora_dla", p, false, false, true));
+        StepGemm p = gemm_dyw(dqkv, m->Nqkv, W<T>(m, m->lo[l].lb), 16, m->dLa, 16, NT, 16, m->Nqkv);   // dLa = 2 * dqkv . Bcat    (the unused blocks of Bcat are zero)
+        p.alpha = 2.f;
+        RC(gemm<T>(m, "gemm_lora_dla", p));
       }
       {
-        GemmParams p{};  // dBq += 2 * dq^T . La[:, :8]
-        p.A = dqkv; p.lda = m->Nqkv; p.B = a.La; p.ldb = 16; p.C = m->G + m->lo[l].lb; p.ldc = 16; p.c_f32 = 1;
-        p.M = nq; p.N = 8; p.K = NT; p.epi = EPI_ATOMIC; p.alpha = 2.f;
-        RC(gemm<T>(m, "gemm_lora_db", p, false, true, true));
+        StepGemm p = gemm_dytx(dqkv, m->Nqkv, a.La, 16, m->G + m->lo[l].lb, 16, nq, 8, NT);   // dBq += 2 * dq^T . La[:, :8]
+        p.alpha = 2.f;
+        RC(gemm<T>(m, "gemm_lora_db", p));
       }
       {
-        GemmParams p{};  // dBv += 2 * dv^T . La[:, 8:]
-        p.A = AT<T>(dqkv) + nv0; p.lda = m->Nqkv; p.B = AT<T>(a.La) + 8; p.ldb = 16;
-        p.C = m->G + m->lo[l].lb + (int64_t)nv0 * 16 + 8; p.ldc = 16; p.c_f32 = 1;
-        p.M = nkv; p.N = 8; p.K = NT; p.epi = EPI_ATOMIC; p.alpha = 2.f;
-        RC(gemm<T>(m, "gemm_lora_db", p, false, true, true));
+        StepGemm p = gemm_dytx(AT<T>(dqkv) + nv0, m->Nqkv, AT<T>(a.La) + 8, 16, m->G + m->lo[l].lb + (int64_t)nv0 * 16 + 8, 16, nkv, 8, NT);   // dBv += 2 * dv^T . La[:, 8:]
+        p.alpha = 2.f;
+        RC(gemm<T>(m, "gemm_lora_db", p));
       }
+      RC(gemm<T>(m, "gemm_lora_da", gemm_dytx(m->dLa, 16, xnd, D, m->G + m->lo[l].la, D, 16, D, NT)));   // d[Aq; Av] += dLa^T . drop(xn)
       {
-        GemmParams p{};  // d[Aq; Av] += dLa^T . drop(xn)
-        p.A = m->dLa; p.lda = 16; p.B = xnd; p.ldb = D; p.C = m->G + m->lo[l].la; p.ldc = D; p.c_f32 = 1;
-        p.M = 16; p.N = D; p.K = NT; p.epi = EPI_ATOMIC;
-        RC(gemm<T>(m, "gemm_lora_da", p, false, true, true));
-      }
-      {
-        GemmParams p{};  // dxn += dropout'(dLa . [Aq; Av])
-        p.A = m->dLa; p.lda = 16; p.B = W<T>(m, m->lo[l].la); p.ldb = D; p.ldc = D;
-        p.M = NT; p.N = D; p.K = 16; p.epi = EPI_STORE;
-        if (m->drop_active) {
-          p.C = m->dxl;
-          RC(gemm<T>(m, "gemm_lora_dx", p, false, false, true));
+        // dxn += dropout'(dLa . [Aq; Av])
+        StepGemm p = gemm_dyw(m->dLa, 16, W<T>(m, m->lo[l].la), D, m->drop_active ? m->dxl : m->dhn, D, NT, D, 16);
+        p.accum = m->drop_active ? 0 : 1;
+        RC(gemm<T>(m, "gemm_lora_dx", p));
+        if (m->drop_active)
           RC(launch_dropout<T>(AT<T>(m->dxl), AT<T>(m->dhn), (long long)NT * D, m->cfg.lora_dropout, m->drop_seed,
                                (unsigned int)(m->drop_step * 64 + l), 1, s));
-        } else {
-          p.C = m->dhn; p.accum = 1;
-          RC(gemm<T>(m, "gemm_lora_dx", p, false, false, true));
-        }
       }
     }
     tic(m, "hbm_rmsnorm_bwd", nb_bytes);
@@ -387,18 +336,12 @@ int backward_trunk(Model* m) {
   toc(m);
   m->table_grads_pending = true;
   m->gE_clean[0] = m->gE_clean[1] = false;   // the rows now hold token gradients: a later head GEMM must add, not store
-  {
-    GemmParams p{};  // dWlin += g_act^T . feat
-    p.A = gxt + D; p.lda = 2 * D; p.B = m->feat; p.ldb = 32; p.C = m->G + m->o_lin_w; p.ldc = 32; p.c_f32 = 1;
-    p.M = D; p.N = 32; p.K = N; p.epi = EPI_ATOMIC;
-    RC(gemm<T>(m, "gemm_action_dw", p, false, true, true));
-  }
+  RC(gemm<T>(m, "gemm_action_dw", gemm_dytx(gxt + D, 2 * D, m->feat, 32, m->G + m->o_lin_w, 32, D, 32, N)));   // dWlin += g_act^T . feat
   RC(launch_colsum_add(gx + D, 2 * D, N, D, m->G + m->o_lin_b, s));
   {
-    GemmParams p{};  // gf = g_act . Wlin
-    p.A = gxt + D; p.lda = 2 * D; p.B = W<T>(m, m->o_lin_w); p.ldb = 32; p.C = m->gf; p.ldc = 32; p.c_f32 = 1;
-    p.M = N; p.N = 32; p.K = D; p.epi = EPI_STORE;
-    RC(gemm<T>(m, "gemm_action_dx", p, false, false, true));
+    StepGemm p = gemm_dyw(gxt + D, 2 * D, W<T>(m, m->o_lin_w), 32, m->gf, 32, N, 32, D);   // gf = g_act . Wlin
+    p.c_f32 = 1;
+    RC(gemm<T>(m, "gemm_action_dx", p));
   }
   SmallParams sp = small_params(m);
   RC(launch_action_small_bwd(m->gf, b, sp, m->G + m->o_pcos, m->G + m->o_psin, m->G + m->o_status, m->G + m->o_gender,
@@ -433,14 +376,13 @@ static int finalize_grads_t(Model* m, int stage) {
     }
   }
   if (stage != 1) {
-    GemmParams p{};
-    p.C = m->G + m->o_Wp; p.ldc = m->Mp; p.c_f32 = 1; p.M = m->D; p.N = m->Mp; p.epi = EPI_ATOMIC;
+    float* dWp = m->G + m->o_Wp;
     if (m->bf16_mode) {   // dWp[d][c] += sum_v dFT[d][v] MetaT[c][v]  (both operands K-contiguous, padding columns are zero)
-      p.A = m->dFT; p.lda = m->Vp; p.B = m->MetaT; p.ldb = m->Vp; p.K = (int)m->Vp;
-      RC(gemm<T>(m, "gemm_table_dw", p, false, false, false));
+      StepGemm p = gemm_xwt(m->dFT, m->Vp, m->MetaT, m->Vp, dWp, m->Mp, m->D, m->Mp, (int)m->Vp);
+      p.c_f32 = 1; p.epi = EPI_ATOMIC;
+      RC(gemm<T>(m, "gemm_table_dw", p));
     } else {
-      p.A = m->G + m->o_E; p.lda = m->D; p.B = m->Meta; p.ldb = m->Mp; p.K = m->TR;
-      RC(gemm<T>(m, "gemm_table_dw", p, false, true, true));
+      RC(gemm<T>(m, "gemm_table_dw", gemm_dytx(m->G + m->o_E, m->D, m->Meta, m->Mp, dWp, m->Mp, m->D, m->Mp, m->TR)));
     }
   }
   toc(m);

@@ -13,10 +13,6 @@ namespace rsys {
 // fp32 keep the single launch (the atomics' order is free).
 template <typename T>
 int table_forward(Model* m) {
-  GemmParams p{};
-  p.A = m->Meta; p.lda = m->Mp; p.B = W<T>(m, m->o_Wp); p.ldb = m->Mp; p.C = m->F32; p.ldc = m->D; p.c_f32 = 1;
-  p.M = m->TR; p.N = m->D; p.K = m->Mp; p.epi = EPI_TABLE; p.E = m->P + m->o_E; p.bias = m->P + m->o_bp;
-  p.C2 = m->FT; p.ldc2 = m->D;
   int rows_main = m->TR;
   if constexpr (is_bf16<T>::value) {
     const int cus = cu_count();
@@ -26,18 +22,18 @@ int table_forward(Model* m) {
         m->Mp % 64 == 0 && m->Mp >= 1024)
       rows_main = (rounds * cus / tiles_n) * 256;
   }
-  p.M = rows_main;
-  RC(gemm<T>(m, "gemm_table_fwd", p, false, false, false));
+  StepGemm p = gemm_xwt(m->Meta, m->Mp, W<T>(m, m->o_Wp), m->Mp, m->F32, m->D, rows_main, m->D, m->Mp);
+  p.c_f32 = 1; p.epi = EPI_TABLE; p.E = m->P + m->o_E; p.bias = m->P + m->o_bp; p.C2 = m->FT; p.ldc2 = m->D;
+  RC(gemm<T>(m, "gemm_table_fwd", p));
   if (rows_main < m->TR) {
     const int64_t r0 = rows_main, nr = m->TR - rows_main;
     float* Ft = (float*)m->F32 + r0 * m->D;
     tic(m, "table_tail_rows");
     RC(launch_add_bias_rows(m->P + m->o_E + r0 * m->D, m->P + m->o_bp, Ft, nr, (int)m->D, m->stream));
     toc(m);
-    GemmParams q{};
-    q.A = (const T*)m->Meta + r0 * m->Mp; q.lda = m->Mp; q.B = W<T>(m, m->o_Wp); q.ldb = m->Mp; q.C = Ft; q.ldc = m->D; q.c_f32 = 1;
-    q.M = (int)nr; q.N = m->D; q.K = m->Mp; q.epi = EPI_ATOMIC; q.flags = GEMM_SPLITK_256;
-    RC(gemm<T>(m, "gemm_table_fwd_tail", q, false, false, false));
+    StepGemm q = gemm_xwt((const T*)m->Meta + r0 * m->Mp, m->Mp, W<T>(m, m->o_Wp), m->Mp, Ft, m->D, (int)nr, m->D, m->Mp);
+    q.c_f32 = 1; q.epi = EPI_ATOMIC; q.flags = GEMM_SPLITK_256;
+    RC(gemm<T>(m, "gemm_table_fwd_tail", q));
     tic(m, "table_tail_rows");
     RC(launch_cast<T>(Ft, (T*)m->FT + r0 * m->D, nr * m->D, m->stream));
     toc(m);
@@ -58,73 +54,73 @@ static int ensure_f8_weights(Model* m) {
 }
 
 // token-local tail of layer l (model.py:300-309): h = x + O Wo^T ; out = h + W2 (silu(W1 hn) * W3 hn), hn = RMSNorm(h)
-template <typename T>
-static int layer_tail_dense(Model* m, int l, const void* O_in = nullptr /* attention output in token order (default: the layer's own) */) {
-  const int D = m->D, Ip = m->Ip, NT = 2 * m->cur_rows * m->S;
-  hipStream_t s = m->stream;
+// The rows a tail runs on: every token of the batch in layer l's own buffers, or the compact rows of the last layer's selected tokens
+// (Model::sparse_top, compact.hip: every buffer has ctop_cap rows, the GEMMs and the norm stop at the device-side row count).
+struct TailRows {
+  int l, M;                                   // layer; rows (compact: the buffers' capacity)
+  const int* n_dev;                           // compact: the device-side row count; nullptr: all M rows
+  const void* O; const float* x;              // the rows' attention output and layer input
+  float* h; void* hn; float* rstd2; void* ab; void* g; float* out;
+  const char *tag_o, *tag_norm, *tag_w13, *tag_w2;   // (tag_norm == nullptr: the norm is not timed on its own)
+  bool dense;                                 // the dense rows' extras: the fp8 products and their amax slots, reversed tile rows of W2
+};
+static TailRows tail_rows_dense(Model* m, int l, const void* O_in = nullptr /* attention output in token order (default: the layer's own) */) {
   Model::LayerAct& a = m->la[l];
-  float* xnext = (l + 1 < m->L) ? m->la[l + 1].x : m->xL;
+  return {l, 2 * m->cur_rows * m->S, nullptr, O_in ? O_in : a.O, a.x, a.h, a.hn, a.rstd2, a.ab, a.g, (l + 1 < m->L) ? m->la[l + 1].x : m->xL,
+          "gemm_o_fwd", "hbm_rmsnorm_fwd", "gemm_w13_fwd", "gemm_w2_fwd", true};
+}
+static TailRows tail_rows_compact(Model* m) {
+  return {m->L - 1, m->ctop_cap, m->c_n, m->c_O, m->c_x, m->c_h, m->c_hn, m->c_rstd2, m->c_ab, m->c_g, m->c_xL,
+          "gemm_top_o_fwd", nullptr, "gemm_top_w13_fwd", "gemm_top_w2_fwd", false};
+}
+
+template <typename T>
+static int layer_tail(Model* m, const TailRows& r) {
+  const int D = m->D, Ip = m->Ip, l = r.l;
+  const bool f8 = r.dense && m->fp8;   // (the compact top is off under fp8, model.hip)
   {
-    GemmParams p{};
-    p.A = O_in ? O_in : a.O; p.lda = D; p.B = W<T>(m, m->lo[l].wo); p.ldb = D; p.C = a.h; p.ldc = D; p.c_f32 = 1;
-    p.M = NT; p.N = D; p.K = D; p.epi = EPI_RESIDUAL; p.resid = a.x; p.ldr = D;
-    if (m->fp8) RC(gemm_f8(m, l, F8P_O, "gemm_o_fwd", p, W8(m, m->lo[l].wo), D, true));   // (amax |O| came with the attention kernel)
-    else RC(gemm<T>(m, "gemm_o_fwd", p, false, false, false));
+    StepGemm p = gemm_xwt(r.O, D, W<T>(m, m->lo[l].wo), D, r.h, D, r.M, D, D);
+    p.c_f32 = 1; p.epi = EPI_RESIDUAL; p.resid = r.x; p.ldr = D; p.m_dev = r.n_dev;
+    if (f8) RC(gemm_f8(m, l, F8P_O, r.tag_o, p, W8(m, m->lo[l].wo), D, true));   // (amax |O| came with the attention kernel)
+    else RC(gemm<T>(m, r.tag_o, p));
   }
-  tic(m, "hbm_rmsnorm_fwd", (4.0 + sizeof(T)) * D * NT);
-  RC(launch_rmsnorm_fwd<T>(a.h, m->P + m->lo[l].mlp, AT<T>(a.hn), a.rstd2, NT, D, s, nullptr, nullptr, m->fp8 ? f8_slot(m, l, F8S_HN) : nullptr));
-  toc(m);
+  if (r.tag_norm) tic(m, r.tag_norm, (4.0 + sizeof(T)) * D * r.M);
+  RC(launch_rmsnorm_fwd<T>(r.h, m->P + m->lo[l].mlp, AT<T>(r.hn), r.rstd2, r.M, D, m->stream, r.n_dev, nullptr, f8 ? f8_slot(m, l, F8S_HN) : nullptr));
+  if (r.tag_norm) toc(m);
   {
-    GemmParams p{};
-    p.A = a.hn; p.lda = D; p.B = W<T>(m, m->lo[l].w13); p.ldb = D; p.C = a.ab; p.ldc = 2 * Ip;
-    p.M = NT; p.N = 2 * Ip; p.K = D; p.epi = EPI_SWIGLU; p.C2 = a.g; p.ldc2 = Ip;
-    if (m->fp8) { p.f8_amax_out = f8_slot(m, l, F8S_G); RC(gemm_f8(m, l, F8P_W13, "gemm_w13_fwd", p, W8(m, m->lo[l].w13), D, true)); }
-    else RC(gemm<T>(m, "gemm_w13_fwd", p, false, false, false));
+    StepGemm p = gemm_xwt(r.hn, D, W<T>(m, m->lo[l].w13), D, r.ab, 2 * Ip, r.M, 2 * Ip, D);
+    p.epi = EPI_SWIGLU; p.C2 = r.g; p.ldc2 = Ip; p.m_dev = r.n_dev;
+    if (f8) { p.f8_amax_out = f8_slot(m, l, F8S_G); RC(gemm_f8(m, l, F8P_W13, r.tag_w13, p, W8(m, m->lo[l].w13), D, true)); }
+    else RC(gemm<T>(m, r.tag_w13, p));
   }
   {
-    GemmParams p{};
-    p.A = a.g; p.lda = Ip; p.B = W<T>(m, m->lo[l].w2); p.ldb = Ip; p.C = xnext; p.ldc = D; p.c_f32 = 1;
-    p.M = NT; p.N = D; p.K = Ip; p.epi = EPI_RESIDUAL; p.resid = a.h; p.ldr = D;
-    if (m->fp8) RC(gemm_f8(m, l, F8P_W2, "gemm_w2_fwd", p, W8(m, m->lo[l].w2), Ip, true));   // (amax |g| came with the SwiGLU epilogue)
-    else RC(gemm<T>(m, "gemm_w2_fwd", p, false, false, false));
+    StepGemm p = gemm_xwt(r.g, Ip, W<T>(m, m->lo[l].w2), Ip, r.out, D, r.M, D, Ip);
+    p.c_f32 = 1; p.epi = EPI_RESIDUAL; p.resid = r.h; p.ldr = D; p.m_dev = r.n_dev;
+    // A consumer that reads a large activation the previous kernel has just written walks its tile rows from the LAST to the first: the rows
+    // written last are still in the Infinity Cache, a forward walk meets only the evicted ones (this product reads g behind w13_fwd's 553 MB of
+    // output; measured per call site, profiles/r6_ab_reverse_tile_rows.log: -1.7 %, and nothing at the compact rows).  launch_gemm8c honours the
+    // bit by RSYS_GEMM_REVERSE.
+    if (r.dense && !f8) p.flags = GEMM_REVERSE_ROWS;
+    if (f8) RC(gemm_f8(m, l, F8P_W2, r.tag_w2, p, W8(m, m->lo[l].w2), Ip, true));   // (amax |g| came with the SwiGLU epilogue)
+    else RC(gemm<T>(m, r.tag_w2, p));
   }
   return RSYS_OK;
 }
 
-// The same tail of the LAST layer plus the final norm on the compact set of selected tokens (Model::sparse_top, compact.hip):
-// every buffer has ctop_cap rows, the GEMMs stop at the device-side row count.
+// That tail of the LAST layer plus the final norm on the compact set of selected tokens.
 // sel_x: the selected tokens' rows of the layer's input; sel_O: their rows of the attention output a.O, or nullptr when c_O holds them
 // already (the serving form behind attn_sel_kernel).  A training pass hands its sorted set and that set's selected-first places, an
 // inference pass its own selection twice: token order is kept there, and compact row i is the i-th entry of the selection.
 template <typename T>
 static int top_tail_compact(Model* m, const int* sel_x, const int* sel_O) {
-  const int D = m->D, Ip = m->Ip, l = m->L - 1, cap = m->ctop_cap;
+  const int D = m->D, cap = m->ctop_cap;
   hipStream_t s = m->stream;
-  Model::LayerAct& a = m->la[l];
-  const int* n = m->c_n;
+  Model::LayerAct& a = m->la[m->L - 1];
   tic(m, "phase_top_compact_fwd");
-  if (sel_O) RC(launch_gather_rows_sel<T>(AT<T>(a.O), D, sel_O, n, cap, AT<T>(m->c_O), D, s));
-  RC(launch_gather_rows_sel<float>(a.x, D, sel_x, n, cap, m->c_x, D, s));
-  {
-    GemmParams p{};
-    p.A = m->c_O; p.lda = D; p.B = W<T>(m, m->lo[l].wo); p.ldb = D; p.C = m->c_h; p.ldc = D; p.c_f32 = 1;
-    p.M = cap; p.N = D; p.K = D; p.epi = EPI_RESIDUAL; p.resid = m->c_x; p.ldr = D; p.m_dev = n;
-    RC(gemm<T>(m, "gemm_top_o_fwd", p, false, false, false));
-  }
-  RC(launch_rmsnorm_fwd<T>(m->c_h, m->P + m->lo[l].mlp, AT<T>(m->c_hn), m->c_rstd2, cap, D, s, n));
-  {
-    GemmParams p{};
-    p.A = m->c_hn; p.lda = D; p.B = W<T>(m, m->lo[l].w13); p.ldb = D; p.C = m->c_ab; p.ldc = 2 * Ip;
-    p.M = cap; p.N = 2 * Ip; p.K = D; p.epi = EPI_SWIGLU; p.C2 = m->c_g; p.ldc2 = Ip; p.m_dev = n;
-    RC(gemm<T>(m, "gemm_top_w13_fwd", p, false, false, false));
-  }
-  {
-    GemmParams p{};
-    p.A = m->c_g; p.lda = Ip; p.B = W<T>(m, m->lo[l].w2); p.ldb = Ip; p.C = m->c_xL; p.ldc = D; p.c_f32 = 1;
-    p.M = cap; p.N = D; p.K = Ip; p.epi = EPI_RESIDUAL; p.resid = m->c_h; p.ldr = D; p.m_dev = n;
-    RC(gemm<T>(m, "gemm_top_w2_fwd", p, false, false, false));
-  }
-  RC(launch_rmsnorm_fwd<T>(m->c_xL, m->P + m->o_norm, AT<T>(m->c_out), m->c_rstdf, cap, D, s, n));
+  if (sel_O) RC(launch_gather_rows_sel<T>(AT<T>(a.O), D, sel_O, m->c_n, cap, AT<T>(m->c_O), D, s));
+  RC(launch_gather_rows_sel<float>(a.x, D, sel_x, m->c_n, cap, m->c_x, D, s));
+  RC(layer_tail<T>(m, tail_rows_compact(m)));
+  RC(launch_rmsnorm_fwd<T>(m->c_xL, m->P + m->o_norm, AT<T>(m->c_out), m->c_rstdf, cap, D, s, m->c_n));
   toc(m);
   return RSYS_OK;
 }
@@ -146,7 +142,7 @@ static int serving_top_mode(const Model* m, int NT) {
 // ------------------------------------------------------------------ forward trunk (model.py:464-491, 335-343)
 template <typename T>
 int forward_trunk(Model* m) {
-  const int D = m->D, Ip = m->Ip, hd = m->hd, rows = m->cur_rows;
+  const int D = m->D, rows = m->cur_rows;
   const int N = rows * m->S, NT = 2 * N;   // (S, T: the resident batch's row length, model.hpp)
   m->fwd_tokens = NT;
   hipStream_t s = m->stream;
@@ -163,10 +159,9 @@ int forward_trunk(Model* m) {
   SmallParams sp = small_params(m);
   RC(launch_action_features<T>(b, sp, AT<T>(m->feat), s));
   {
-    GemmParams p{};
-    p.A = m->feat; p.lda = 32; p.B = W<T>(m, m->o_lin_w); p.ldb = 32; p.C = m->x0 + D; p.ldc = 2 * D; p.c_f32 = 1;
-    p.M = N; p.N = D; p.K = 32; p.epi = EPI_BIAS; p.bias = m->P + m->o_lin_b;
-    RC(gemm<T>(m, "gemm_action_fwd", p, false, false, false));
+    StepGemm p = gemm_xwt(m->feat, 32, W<T>(m, m->o_lin_w), 32, m->x0 + D, 2 * D, N, D, 32);
+    p.c_f32 = 1; p.epi = EPI_BIAS; p.bias = m->P + m->o_lin_b;
+    RC(gemm<T>(m, "gemm_action_fwd", p));
   }
   if (m->sharded) {
     // sparse row exchange: every owner sends the rows of F its peers' batches read (plan of the resident batch), then the
@@ -183,18 +178,13 @@ int forward_trunk(Model* m) {
     RC(launch_gather_items(b, m->F32, m->V, D, m->x0, m->uid_t, m->tm_t, s));
     toc(m);
   }
-  AttnParams ap{};
-  ap.B = rows; ap.T = m->T; ap.H = m->H; ap.KV = m->KV; ap.hd = hd; ap.is_bf16 = is_bf16<T>::value ? 1 : 0;
-  ap.uid = m->uid_t; ap.tm = m->tm_t;
-  m->maps.apply(ap);
-  if (m->rc_mode != 2) RC(launch_attn_tilemap(ap, s));   // (rc_mode 2, rsys_rank_cache_candidates: candidate rows have no tile maps)
+  // the tile maps of a token order depend on ids alone: built once, from any layer's AttnParams
+  if (m->rc_mode != 2) RC(launch_attn_tilemap(layer_attn<T>(m, 0, TOKENS_BATCH), s));   // (rc_mode 2, rsys_rank_cache_candidates: candidate rows have no tile maps)
   toc(m);
-  AttnParams ap_top = ap;   // the last layer under the compact top: selected-first token order, its own tile maps, leading query tiles only
-  if (m->top_is_sparse) {
+  if (m->top_is_sparse) {   // the last layer under the compact top: selected-first token order, its own tile maps, leading query tiles only
     RC(launch_selected_first(m->c_bits, m->c_pre, m->c_slot, m->c_sel, m->uid_t, m->tm_t, rpos, rows, m->T, m->c_perm, m->uid_p, m->tm_p, m->pos_p, m->c_slot_p,
                              m->c_sel_p, m->c_qact, s));
-    ap_top.uid = m->uid_p; ap_top.tm = m->tm_p;
-    m->maps_p.apply(ap_top);
+    AttnParams ap_top = layer_attn<T>(m, m->L - 1, TOKENS_SELECTED_FIRST);
     ap_top.q_active = m->c_qact;   // (the launch orders put the query tiles beyond it last)
     RC(launch_attn_tilemap(ap_top, s));
   }
@@ -218,30 +208,23 @@ int forward_trunk(Model* m) {
                              (unsigned int)(m->drop_step * 64 + l), 0, s));
         xnd = AT<T>(a.xnd);
       }
-      GemmParams p{};  // La = drop(xn) . [Aq; Av]^T   (NT x 16)
-      p.A = xnd; p.lda = D; p.B = W<T>(m, m->lo[l].la); p.ldb = D; p.C = a.La; p.ldc = 16;
-      p.M = NT; p.N = 16; p.K = D; p.epi = EPI_STORE;
-      RC(gemm<T>(m, "gemm_lora_a_fwd", p, false, false, false));
+      // La = drop(xn) . [Aq; Av]^T   (NT x 16)
+      RC(gemm<T>(m, "gemm_lora_a_fwd", gemm_xwt(xnd, D, W<T>(m, m->lo[l].la), D, a.La, 16, NT, 16, D)));
     }
     if (m->bank_rows || m->bank_tiles) RC(adapter_bank_stage_a<T>(m, l, AT<T>(a.xn)));   // rsys_infer_select_adapters: every row's own adapter (or none)
     {
-      GemmParams p{};
-      p.A = a.xn; p.lda = D; p.B = W<T>(m, m->lo[l].wqkv); p.ldb = D; p.C = a.qkv; p.ldc = m->Nqkv;
-      p.M = NT; p.N = m->Nqkv; p.K = D; p.epi = EPI_QKV_ROPE;
-      p.rope_cos = m->rope_cos; p.rope_sin = m->rope_sin; p.rope_cs = m->rope_cs; p.rope_pos = rpos_l; p.T = m->T; p.hd = hd;
-      p.n_q = m->H * hd; p.n_k = m->KV * hd;
+      StepGemm p = gemm_xwt(a.xn, D, W<T>(m, m->lo[l].wqkv), D, a.qkv, m->Nqkv, NT, m->Nqkv, D);
+      gemm_qkv_rope(p, m, rpos_l);
       if (m->fp8) RC(gemm_f8(m, l, F8P_QKV, "gemm_qkv_fwd", p, W8(m, m->lo[l].wqkv), D, true));
-      else RC(gemm<T>(m, "gemm_qkv_fwd", p, false, false, false));
+      else RC(gemm<T>(m, "gemm_qkv_fwd", p));
     }
     if (ft) {
       // q += 2 * La[:, :8] Bq^T, v += 2 * La[:, 8:] Bv^T (lora_scaling = 16/8, model.py:236-237,264-271).  RoPE is linear,
       // so the rotated update is accumulated onto the rotated projection.
-      GemmParams p{};
-      p.A = a.La; p.lda = 16; p.B = W<T>(m, m->lo[l].lb); p.ldb = 16; p.C = a.qkv; p.ldc = m->Nqkv;
-      p.M = NT; p.N = m->Nqkv; p.K = 16; p.epi = EPI_QKV_ROPE; p.alpha = 2.f; p.accum = 1;
-      p.rope_cos = m->rope_cos; p.rope_sin = m->rope_sin; p.rope_cs = m->rope_cs; p.rope_pos = rpos_l; p.T = m->T; p.hd = hd;
-      p.n_q = m->H * hd; p.n_k = m->KV * hd;
-      RC(gemm<T>(m, "gemm_lora_b_fwd", p, false, false, false));
+      StepGemm p = gemm_xwt(a.La, 16, W<T>(m, m->lo[l].lb), 16, a.qkv, m->Nqkv, NT, m->Nqkv, 16);
+      gemm_qkv_rope(p, m, rpos_l);
+      p.alpha = 2.f; p.accum = 1;
+      RC(gemm<T>(m, "gemm_lora_b_fwd", p));
     }
     if (m->bank_rows || m->bank_tiles) RC(adapter_bank_stage_b<T>(m, l, AT<T>(a.qkv), rpos_l));
     if (m->rc_mode == 1) RC(rank_cache_store_layer<T>(m, l, AT<T>(a.qkv)));   // rsys_rank_cache_store: the forward as it is + this layer's K | V of the history rows into their slots
@@ -250,19 +233,18 @@ int forward_trunk(Model* m) {
     if (m->rc_mode == 2) {   // rsys_rank_cache_candidates: the rows' candidates against their slots' cached history
       RC(rank_cache_attention<T>(m, l, AT<T>(a.qkv), AT<T>(a.O)));
       if (last && stop) break;
-      RC(layer_tail_dense<T>(m, l));
+      RC(layer_tail<T>(m, tail_rows_dense(m, l)));
       continue;
     }
-    AttnParams& apl = top ? ap_top : ap;
-    apl.q = a.qkv; apl.k = AT<T>(a.qkv) + m->H * hd; apl.v = AT<T>(a.qkv) + (m->H + m->KV) * hd; apl.ld = m->Nqkv;
-    apl.o = a.O; apl.ldo = D; apl.lse = a.lse;
+    AttnParams apl = layer_attn<T>(m, l, top ? TOKENS_SELECTED_FIRST : TOKENS_BATCH);
+    if (top) apl.q_active = m->c_qact;
     apl.f8_amax = m->fp8 ? f8_slot(m, l, F8S_O) : nullptr;
     tic(m, "attn_fwd");
     if (last && stop == 2) RC(launch_attn_sel<T>(apl, m->top_sel, m->top_nsel, m->c_O, D, s));   // the selected queries only, into compact rows
     else RC(launch_attn_fwd<T>(apl, s));
     toc(m);
     if (last && (m->top_is_sparse || stop)) break;   // the tail of the last layer and the final norm run on the selected tokens
-    RC(layer_tail_dense<T>(m, l));
+    RC(layer_tail<T>(m, tail_rows_dense(m, l)));
   }
   if (m->top_is_sparse) { toc(m); return top_tail_compact<T>(m, m->c_sel, m->c_sel_p); }   // (the layer's attention ran in selected-first order)
   if (stop) {
@@ -288,19 +270,12 @@ int forward_trunk(Model* m) {
 // computed it; the dense tail of the last layer and the final norm run now, from the saved attention output.
 template <typename T>
 static int materialise_output_t(Model* m) {
-  const int D = m->D, NT = 2 * m->cur_rows * m->S, l = m->L - 1, hd = m->hd;
+  const int D = m->D, NT = 2 * m->cur_rows * m->S, l = m->L - 1;
   // the last layer's attention ran in selected-first order over the leading query tiles only: run all of them, then bring the
   // attention output back to token order (into the free dO buffer of the backward) for the dense tail
-  Model::LayerAct& a = m->la[l];
-  AttnParams ap{};
-  ap.B = m->cur_rows; ap.T = m->T; ap.H = m->H; ap.KV = m->KV; ap.hd = hd; ap.is_bf16 = is_bf16<T>::value ? 1 : 0;
-  ap.uid = m->uid_p; ap.tm = m->tm_p;
-  m->maps_p.apply(ap);
-  ap.q = a.qkv; ap.k = AT<T>(a.qkv) + m->H * hd; ap.v = AT<T>(a.qkv) + (m->H + m->KV) * hd; ap.ld = m->Nqkv;
-  ap.o = a.O; ap.ldo = D; ap.lse = a.lse;
-  RC(launch_attn_fwd<T>(ap, m->stream));
-  RC(launch_scatter_rows_map<T>(AT<T>(a.O), m->c_perm, NT, AT<T>(m->dO), D, D, m->stream));
-  RC(layer_tail_dense<T>(m, l, m->dO));
+  RC(launch_attn_fwd<T>(layer_attn<T>(m, l, TOKENS_SELECTED_FIRST), m->stream));
+  RC(launch_scatter_rows_map<T>(AT<T>(m->la[l].O), m->c_perm, NT, AT<T>(m->dO), D, D, m->stream));
+  RC(layer_tail<T>(m, tail_rows_dense(m, l, m->dO)));
   RC(launch_rmsnorm_fwd<T>(m->xL, m->P + m->o_norm, AT<T>(m->out), m->rstdf, NT, D, m->stream));
   return RSYS_OK;
 }
@@ -309,19 +284,12 @@ static int materialise_output_t(Model* m) {
 // maps are still those of the pass), its dense tail, the final norm.
 template <typename T>
 static int materialise_serving_t(Model* m) {
-  const int D = m->D, NT = 2 * m->cur_rows * m->S, l = m->L - 1, hd = m->hd;
-  Model::LayerAct& a = m->la[l];
+  const int D = m->D, NT = 2 * m->cur_rows * m->S, l = m->L - 1;
   if (m->out_attn_pending) {
-    AttnParams ap{};
-    ap.B = m->cur_rows; ap.T = m->T; ap.H = m->H; ap.KV = m->KV; ap.hd = hd; ap.is_bf16 = is_bf16<T>::value ? 1 : 0;
-    ap.uid = m->uid_t; ap.tm = m->tm_t;
-    m->maps.apply(ap);
-    ap.q = a.qkv; ap.k = AT<T>(a.qkv) + m->H * hd; ap.v = AT<T>(a.qkv) + (m->H + m->KV) * hd; ap.ld = m->Nqkv;
-    ap.o = a.O; ap.ldo = D; ap.lse = a.lse;
-    RC(launch_attn_fwd<T>(ap, m->stream));
+    RC(launch_attn_fwd<T>(layer_attn<T>(m, l, TOKENS_BATCH), m->stream));
     m->out_attn_pending = false;
   }
-  RC(layer_tail_dense<T>(m, l));
+  RC(layer_tail<T>(m, tail_rows_dense(m, l)));
   RC(launch_rmsnorm_fwd<T>(m->xL, m->P + m->o_norm, AT<T>(m->out), m->rstdf, NT, D, m->stream));
   m->out_pending = false;
   return RSYS_OK;
@@ -362,10 +330,9 @@ static int watch_head_sampled(Model* m, int ti, int medium, bool bwd, int nlive,
     RC(launch_ss_sample(len, n_s, m->cur_seed ^ (0x5A3Dull + 977ull * (unsigned long long)m->sh_rank), (unsigned int)(m->cur_step * 2 + medium), m->ss_cols, s));
     if (n_t > 0) RC(launch_ss_drop_hits(m->ss_cols, n_s, m->ss_bitmap, s));
     RC(launch_gather_rows_plain<T>(Floc, D, m->ss_cols, 0, AT<T>(m->ss_F), n_tot, D, s));
-    GemmParams p{};
-    p.A = m->EwC; p.lda = D; p.B = m->ss_F; p.ldb = D; p.C = m->logits; p.ldc = lds;
-    p.M = cap; p.N = n_tot; p.K = D; p.epi = EPI_STORE; p.m_dev = m->vp_nlive;
-    RC(gemm<T>(m, "gemm_logits", p, false, false, false));
+    StepGemm p = gemm_xwt(m->EwC, D, m->ss_F, D, m->logits, lds, cap, n_tot, D);
+    p.m_dev = m->vp_nlive;
+    RC(gemm<T>(m, "gemm_logits", p));
     RC(launch_ss_target_logit<T>(AT<T>(m->EwC), Floc, D, len, col0, m->metaC, m->vp_nlive, m->ss_tl, nlive, s));
   }
   tic(m, "ce");
@@ -386,16 +353,14 @@ static int watch_head_sampled(Model* m, int ti, int medium, bool bwd, int nlive,
   HIP_CHECK(hipMemsetAsync(m->dEwC, 0, (size_t)nlive * D * 4, s));
   if (n_s > 0) {
     {
-      GemmParams p{};  // d(selected rows) = dlogits . F[sampled rows]
-      p.A = m->logits; p.lda = lds; p.B = m->ss_F; p.ldb = D; p.C = m->dEwC; p.ldc = D; p.c_f32 = 1;
-      p.M = cap; p.N = D; p.K = n_tot; p.epi = EPI_ATOMIC; p.m_dev = m->vp_nlive;
-      RC(gemm<T>(m, "gemm_head_dx", p, false, false, true));
+      StepGemm p = gemm_dyw(m->logits, lds, m->ss_F, D, m->dEwC, D, cap, D, n_tot);   // d(selected rows) = dlogits . F[sampled rows]
+      p.c_f32 = 1; p.epi = EPI_ATOMIC; p.m_dev = m->vp_nlive;
+      RC(gemm<T>(m, "gemm_head_dx", p));
     }
     {
-      GemmParams p{};  // dF[sampled rows] = dlogits^T . (selected rows of all ranks), then added to the table gradient rows
-      p.A = m->logits; p.lda = lds; p.B = m->EwC; p.ldb = D; p.C = m->ss_dF; p.ldc = D; p.c_f32 = 1;
-      p.M = n_tot; p.N = D; p.K = cap; p.epi = EPI_STORE; p.k_dev = m->vp_nlive;
-      RC(gemm<T>(m, "gemm_head_dw", p, false, true, true));
+      StepGemm p = gemm_dytx(m->logits, lds, m->EwC, D, m->ss_dF, D, n_tot, D, cap);   // dF[sampled rows] = dlogits^T . (selected rows of all ranks), then added to the table gradient rows
+      p.epi = EPI_STORE; p.k_dev = m->vp_nlive;
+      RC(gemm<T>(m, "gemm_head_dw", p));
       RC(launch_add_rows_plain(m->ss_dF, m->ss_cols, lrow, m->G + m->o_E, D, n_tot, D, s));
     }
     RC(launch_ss_target_grad<T>(AT<T>(m->EwC), Floc, D, len, col0, m->metaC, m->ss_dt, m->vp_nlive, m->G + m->o_E + (int64_t)lrow * D, m->dEwC, nlive, s));
@@ -480,10 +445,9 @@ static int watch_head_sharded(Model* m, int ti, int medium, bool train, bool bwd
   if (sampled)
     return watch_head_sampled<T>(m, ti, medium, bwd, nlive, npad, own0, nown, len, col0, lrow, n_t);
   if (len > 0) {
-    GemmParams p{};
-    p.A = m->EwC; p.lda = D; p.B = Fm; p.ldb = D; p.C = m->logits; p.ldc = m->ldl_loc;
-    p.M = cap; p.N = len; p.K = D; p.epi = EPI_STORE; p.m_dev = m->vp_nlive;
-    RC(gemm<T>(m, "gemm_logits", p, false, false, false));
+    StepGemm p = gemm_xwt(m->EwC, D, Fm, D, m->logits, m->ldl_loc, cap, len, D);
+    p.m_dev = m->vp_nlive;
+    RC(gemm<T>(m, "gemm_logits", p));
   }
   tic(m, "ce");
   RC(launch_vp_stats<T>(AT<T>(m->logits), m->ldl_loc, len, col0, m->metaC, m->vp_nlive, m->vp_lmax, m->vp_sums, cap, nlive, s));
@@ -498,19 +462,18 @@ static int watch_head_sharded(Model* m, int ti, int medium, bool train, bool bwd
   if (!bwd) return RSYS_OK;   // (the task weights are the same on every rank: all ranks leave here together)
   HIP_CHECK(hipMemsetAsync(m->dEwC, 0, (size_t)nlive * D * 4, s));
   if (len > 0) {
-    GemmParams p{};  // d(selected rows) = dlogits . F[local rows]   (partial over the vocabulary)
-    p.A = m->logits; p.lda = m->ldl_loc; p.B = Fm; p.ldb = D; p.C = m->dEwC; p.ldc = D; p.c_f32 = 1;
-    p.M = cap; p.N = D; p.K = len; p.epi = EPI_ATOMIC; p.m_dev = m->vp_nlive;
-    RC(gemm<T>(m, "gemm_head_dx", p, false, false, true));
+    StepGemm p = gemm_dyw(m->logits, m->ldl_loc, Fm, D, m->dEwC, D, cap, D, len);   // d(selected rows) = dlogits . F[local rows]   (partial over the vocabulary)
+    p.c_f32 = 1; p.epi = EPI_ATOMIC; p.m_dev = m->vp_nlive;
+    RC(gemm<T>(m, "gemm_head_dx", p));
   }
   RC(comm_all_reduce_f32(c, m->dEwC, (size_t)nlive * D, COMM_SUM, s));
   if (nown > 0) RC(head_add_rows(m, m->dEwC + (size_t)own0 * D, ti, 0, nown));
   if (len > 0) {
-    GemmParams p{};  // dF[local rows of the medium] (+)= dlogits^T . (selected rows of all ranks): complete, no all-reduce
-    p.A = m->logits; p.lda = m->ldl_loc; p.B = m->EwC; p.ldb = D; p.C = m->G + m->o_E + (int64_t)lrow * D; p.ldc = D; p.c_f32 = 1;
-    p.M = len; p.N = D; p.K = cap; p.epi = m->gE_clean[medium] ? EPI_STORE : EPI_ACCUM; p.k_dev = m->vp_nlive;
+    // dF[local rows of the medium] (+)= dlogits^T . (selected rows of all ranks): complete, no all-reduce
+    StepGemm p = gemm_dytx(m->logits, m->ldl_loc, m->EwC, D, m->G + m->o_E + (int64_t)lrow * D, D, len, D, cap);
+    p.epi = m->gE_clean[medium] ? EPI_STORE : EPI_ACCUM; p.k_dev = m->vp_nlive;
     m->gE_clean[medium] = false;
-    RC(gemm<T>(m, "gemm_head_dw", p, false, true, true));
+    RC(gemm<T>(m, "gemm_head_dw", p));
   }
   m->table_grads_pending = true;
   return RSYS_OK;
@@ -544,10 +507,9 @@ int heads(Model* m, int evaluate, const float tw[4]) {
       const int vs = medium == 0 ? 0 : m->V0, Vm = medium == 0 ? m->V0 : m->V1;
       T* Fm = AT<T>(m->FT) + (int64_t)vs * D;
       {
-        GemmParams p{};
-        p.A = m->Ew; p.lda = D; p.B = Fm; p.ldb = D; p.C = m->logits; p.ldc = m->ldl;
-        p.M = KB; p.N = Vm; p.K = D; p.epi = EPI_STORE; p.m_dev = np;
-        RC(gemm<T>(m, "gemm_logits", p, false, false, false));
+        StepGemm p = gemm_xwt(m->Ew, D, Fm, D, m->logits, m->ldl, KB, Vm, D);
+        p.m_dev = np;
+        RC(gemm<T>(m, "gemm_logits", p));
       }
       tic(m, "ce");
       RC(launch_ce_fwd_bwd<T>(AT<T>(m->logits), m->ldl, KB, Vm, m->idx[ti], m->bd.m_label[ti], m->bd.m_weight[ti],
@@ -555,45 +517,40 @@ int heads(Model* m, int evaluate, const float tw[4]) {
       toc(m);
       if (bwd) {
         {
-          GemmParams p{};  // dEw = dlogits . F   (few output tiles, K = V_m: split-K over the vocabulary)
           HIP_CHECK(hipMemsetAsync(m->dE, 0, (size_t)KB * D * 4, s));
-          p.A = m->logits; p.lda = m->ldl; p.B = Fm; p.ldb = D; p.C = m->dE; p.ldc = D; p.c_f32 = 1;
-          p.M = KB; p.N = D; p.K = Vm; p.epi = EPI_ATOMIC; p.m_dev = np;
-          RC(gemm<T>(m, "gemm_head_dx", p, false, false, true));
+          StepGemm p = gemm_dyw(m->logits, m->ldl, Fm, D, m->dE, D, KB, D, Vm);   // dEw = dlogits . F   (few output tiles, K = V_m: split-K over the vocabulary)
+          p.c_f32 = 1; p.epi = EPI_ATOMIC; p.m_dev = np;
+          RC(gemm<T>(m, "gemm_head_dx", p));
         }
         RC(add_rows(m->dE, ti, 0));
         if (!trunk_frozen(m)) {
-          GemmParams p{};  // dF[s:e] += dlogits^T . Ew
-          p.A = m->logits; p.lda = m->ldl; p.B = m->Ew; p.ldb = D; p.C = m->G + m->o_E + (int64_t)vs * D; p.ldc = D; p.c_f32 = 1;
-          p.M = Vm; p.N = D; p.K = KB; p.epi = m->gE_clean[medium] ? EPI_STORE : EPI_ACCUM; p.k_dev = np;
+          StepGemm p = gemm_dytx(m->logits, m->ldl, m->Ew, D, m->G + m->o_E + (int64_t)vs * D, D, Vm, D, KB);   // dF[s:e] += dlogits^T . Ew
+          p.epi = m->gE_clean[medium] ? EPI_STORE : EPI_ACCUM; p.k_dev = np;
           m->gE_clean[medium] = false;
-          RC(gemm<T>(m, "gemm_head_dw", p, false, true, true));
+          RC(gemm<T>(m, "gemm_head_dw", p));
         }
         if (!trunk_frozen(m)) m->table_grads_pending = true;
       }
     } else {
       {
-        GemmParams p{};
-        p.A = m->Ew; p.lda = D; p.B = W<T>(m, m->o_r0w); p.ldb = D; p.C = m->z; p.ldc = D;
-        p.M = KB; p.N = D; p.K = D; p.epi = EPI_GELU; p.bias = m->P + m->o_r0b; p.C2 = m->hact; p.ldc2 = D;
+        StepGemm p = gemm_xwt(m->Ew, D, W<T>(m, m->o_r0w), D, m->z, D, KB, D, D);
+        p.epi = EPI_GELU; p.bias = m->P + m->o_r0b; p.C2 = m->hact; p.ldc2 = D;
         p.m_dev = np;   // (the rating head too stops at the positive-weight rows: zero-weight padding adds nothing to loss or gradients)
-        RC(gemm<T>(m, "gemm_rating_fwd", p, false, false, false));
+        RC(gemm<T>(m, "gemm_rating_fwd", p));
       }
       RC(launch_rating_tail<T>(AT<T>(m->z), AT<T>(m->hact), KB, D, m->P + m->o_r2w, m->P + m->o_r2b, m->idx[ti],
                                m->bd.m_label[ti], m->bd.m_weight[ti], st, m->cfg.rating_mean, bwd ? tw[ti] : 0.f,
                                bwd ? 0 : 1, m->loss_acc + 3 * ti, small_grad(m, m->o_r2w), small_grad(m, m->o_r2b), small_grad(m, m->o_r0b), s, np));
       if (bwd) {
         if (!trunk_frozen(m)) {
-          GemmParams p{};  // dW0 += dz^T . Er
-          p.A = m->z; p.lda = D; p.B = m->Ew; p.ldb = D; p.C = m->G + m->o_r0w; p.ldc = D; p.c_f32 = 1;
-          p.M = D; p.N = D; p.K = KB; p.epi = EPI_ATOMIC; p.k_dev = np;   // (dz of the padding rows up to the next tile is zero: rating_tail)
-          RC(gemm<T>(m, "gemm_rating_dw", p, false, true, true));
+          StepGemm p = gemm_dytx(m->z, D, m->Ew, D, m->G + m->o_r0w, D, D, D, KB);   // dW0 += dz^T . Er
+          p.k_dev = np;   // (dz of the padding rows up to the next tile is zero: rating_tail)
+          RC(gemm<T>(m, "gemm_rating_dw", p));
         }
         {
-          GemmParams p{};  // dEr = dz . W0
-          p.A = m->z; p.lda = D; p.B = W<T>(m, m->o_r0w); p.ldb = D; p.C = m->dE; p.ldc = D; p.c_f32 = 1;
-          p.M = KB; p.N = D; p.K = D; p.epi = EPI_STORE; p.m_dev = np;
-          RC(gemm<T>(m, "gemm_rating_dx", p, false, false, true));
+          StepGemm p = gemm_dyw(m->z, D, W<T>(m, m->o_r0w), D, m->dE, D, KB, D, D);   // dEr = dz . W0
+          p.c_f32 = 1; p.m_dev = np;
+          RC(gemm<T>(m, "gemm_rating_dx", p));
         }
         RC(add_rows(m->dE, ti, 1));
       }

@@ -1,7 +1,8 @@
 // Shared by the translation units of the training step (model.hip: set-up, batches, orchestration, inference; model_forward.hip;
-// model_backward.hip; model_optim.hip -- one file until round 5): the timing brackets, the GEMM wrapper that picks split
-// counts, the fp8 product table, and the declarations of what one unit calls in another.  Everything defined here is `static`:
-// each unit gets its own copy, none of it owns state.
+// model_backward.hip; model_optim.hip -- one file until round 5) and of the request paths behind them: the timing brackets, the GEMM
+// builders and the wrapper that picks split counts, a layer's AttnParams, the fp8 product table, the tile owners of packed rows, and
+// the declarations of what one unit calls in another (the step's passes; the score buffers, group plans and list checks of the
+// requests).  What is defined here is `static` or inline: each unit gets its own copy, none of it owns state.
 #pragma once
 #include <math.h>
 #include <string.h>
@@ -107,21 +108,47 @@ static int det_slab_for(Model* m, long long need, GemmParams& p) {
   return RSYS_OK;
 }
 
+// The three operand forms of the step's products, C [M][N] = sum_k A(m, k) B(n, k): the builder's name says how A and B lie in memory,
+// the caller sets the epilogue's own fields on the value it gets back.
+struct StepGemm : GemmParams { bool a_km = false, b_km = false; };   // (K-major: the reduction index is the slow one)
+static inline StepGemm gemm_operands(const void* A, long long lda, const void* B, long long ldb, void* C, long long ldc, int M, int N, int K) {
+  StepGemm p{};
+  p.A = A; p.lda = lda; p.B = B; p.ldb = ldb; p.C = C; p.ldc = ldc; p.M = M; p.N = N; p.K = K;
+  return p;
+}
+// y = x . W^T: x [M][K] and W [N][K], both row-major
+static inline StepGemm gemm_xwt(const void* A, long long lda, const void* B, long long ldb, void* C, long long ldc, int M, int N, int K) {
+  return gemm_operands(A, lda, B, ldb, C, ldc, M, N, K);
+}
+// dx = dy . W: dy [M][K] row-major, W [K][N] as it is stored (read K-major)
+static inline StepGemm gemm_dyw(const void* A, long long lda, const void* B, long long ldb, void* C, long long ldc, int M, int N, int K) {
+  StepGemm p = gemm_operands(A, lda, B, ldb, C, ldc, M, N, K);
+  p.b_km = true;
+  return p;
+}
+// dW += dY^T . X: dY [K][M] and X [K][N], both K-major; fp32 C, the K splits add with float atomics
+static inline StepGemm gemm_dytx(const void* A, long long lda, const void* B, long long ldb, float* C, long long ldc, int M, int N, int K) {
+  StepGemm p = gemm_operands(A, lda, B, ldb, C, ldc, M, N, K);
+  p.a_km = p.b_km = true; p.c_f32 = 1; p.epi = EPI_ATOMIC;
+  return p;
+}
+// the q | k | v projection's epilogue: q and k columns rotated at the rows' positions (pos == nullptr: row % T)
+static inline void gemm_qkv_rope(GemmParams& p, const Model* m, const int* pos) {
+  p.epi = EPI_QKV_ROPE;
+  p.rope_cos = m->rope_cos; p.rope_sin = m->rope_sin; p.rope_cs = m->rope_cs; p.rope_pos = pos; p.T = m->T; p.hd = m->hd;
+  p.n_q = m->H * m->hd; p.n_k = m->KV * m->hd;
+}
+
 template <typename T>
-static int gemm(Model* m, const char* tag, GemmParams p, bool a_f32, bool a_km, bool b_km) {
+static int gemm(Model* m, const char* tag, StepGemm p) {
   if (p.alpha == 0.f) p.alpha = 1.f;
   if (p.epi == EPI_ATOMIC && p.splitk == 0)
     p.splitk = pick_splitk(p.M, p.N, (p.k_dev != nullptr && p.k_expect > 0) ? std::min(p.K, p.k_expect) : p.K, is_bf16<T>::value ? 64 : 32);
   if (p.splitk == 0) p.splitk = 1;
   p.flags |= m->gemm_flags;
-  // A consumer that reads a large activation the previous kernel has just written walks its tile rows from the LAST to the first: the rows written
-  // last are still in the Infinity Cache, a forward walk meets only the evicted ones (w2_fwd reads h behind w13_fwd's 553 MB of output, w13_dx reads
-  // dab behind w2_dx; measured per call site, profiles/r6_ab_reverse_tile_rows.log: -1.7 % and -2.4 %, nothing at the other sites).  launch_gemm8c
-  // honours the bit by RSYS_GEMM_REVERSE.
-  if (strcmp(tag, "gemm_w2_fwd") == 0 || strcmp(tag, "gemm_w13_dx") == 0) p.flags |= GEMM_REVERSE_ROWS;
-  if (m->deterministic && p.epi == EPI_ATOMIC) RC(det_slab_for(m, gemm_slab_need<T>(p, a_f32, false, a_km, b_km), p));
-  if (m->timer.enabled) tic(m, (std::string(tag) + "@" + gemm_kernel_name(p, is_bf16<T>::value, a_f32, false, a_km, b_km)).c_str(), 2.0 * p.M * p.N * (double)p.K);
-  int rc = launch_gemm<T>(p, a_f32, false, a_km, b_km, m->stream);
+  if (m->deterministic && p.epi == EPI_ATOMIC) RC(det_slab_for(m, gemm_slab_need<T>(p, false, false, p.a_km, p.b_km), p));
+  if (m->timer.enabled) tic(m, (std::string(tag) + "@" + gemm_kernel_name(p, is_bf16<T>::value, false, false, p.a_km, p.b_km)).c_str(), 2.0 * p.M * p.N * (double)p.K);
+  int rc = launch_gemm<T>(p, false, false, p.a_km, p.b_km, m->stream);
   toc(m);
   return rc;
 }
@@ -129,6 +156,23 @@ static int gemm(Model* m, const char* tag, GemmParams p, bool a_f32, bool a_km, 
 template <typename T> static inline T* W(Model* m, int64_t off) { return (T*)m->Sh + off; }
 template <typename T> static inline T* AT(void* p) { return (T*)p; }
 template <typename T> static inline T* WT(Model* m, int64_t off) { return (T*)m->ShT + off; }
+
+// AttnParams of layer l over the resident batch: shape, ids and tile maps of the token order -- the batch's own, or the selected-first
+// order of the last layer under the compact top --, and the layer's q | k | v, O and log-sum-exp.  Callers add what is theirs alone:
+// q_active, the fp8 amax slot, the backward's gradient and RoPE fields.
+enum TokenOrder { TOKENS_BATCH, TOKENS_SELECTED_FIRST };
+template <typename T>
+static AttnParams layer_attn(Model* m, int l, TokenOrder order) {
+  const Model::LayerAct& a = m->la[l];
+  const bool sel = order == TOKENS_SELECTED_FIRST;
+  AttnParams ap{};
+  ap.B = m->cur_rows; ap.T = m->T; ap.H = m->H; ap.KV = m->KV; ap.hd = m->hd; ap.is_bf16 = is_bf16<T>::value ? 1 : 0;
+  ap.uid = sel ? m->uid_p : m->uid_t; ap.tm = sel ? m->tm_p : m->tm_t;
+  (sel ? m->maps_p : m->maps).apply(ap);
+  ap.q = a.qkv; ap.k = AT<T>(a.qkv) + m->H * m->hd; ap.v = AT<T>(a.qkv) + (m->H + m->KV) * m->hd; ap.ld = m->Nqkv;
+  ap.o = a.O; ap.ldo = m->D; ap.lse = a.lse;
+  return ap;
+}
 
 // the eight fp8 products of a layer: amax slot(s) of the A operand (Model::f8_aamax), its column layout and format, the weight
 // scale slot(s) (Model::f8_wamax: q k v o w1 w3 w2) and how the descales combine

@@ -603,10 +603,9 @@ static_assert(RT_CHUNK == RETRIEVE_CHUNK && RT_LSE_SPLIT == RETRIEVE_LSE_SPLIT, 
 template <typename T>
 int retrieve_chunk_scores(Model* m, const T* qt, int nc, int q0, const T* Fm, int Vm, float* z, long long ldz, float2* part, float* lse) {
   hipStream_t s = m->stream;
-  GemmParams p{};
-  p.A = qt; p.lda = m->D; p.B = Fm; p.ldb = m->D; p.C = z; p.ldc = ldz; p.c_f32 = 1;
-  p.M = nc; p.N = Vm; p.K = m->D; p.epi = EPI_STORE;
-  RC(gemm<T>(m, "gemm_retrieve", p, false, false, false));
+  StepGemm p = gemm_xwt(qt, m->D, Fm, m->D, z, ldz, nc, Vm, m->D);
+  p.c_f32 = 1;
+  RC(gemm<T>(m, "gemm_retrieve", p));
   tic(m, "retrieve_lse");
   lse_partial_kernel<<<dim3(RT_LSE_SPLIT, nc), RT_THREADS, 0, s>>>(z, ldz, Vm, part);
   RT_LAUNCH_CHECK();
