@@ -89,6 +89,17 @@ int32_t rsys_op_gemm_epi(int32_t dtype, const void* A, const void* B, void* C, i
 int32_t rsys_debug_gemm_route(int32_t dtype, int32_t M, int32_t N, int32_t K, int64_t lda, int64_t ldb, int64_t ldc, int32_t a_km,
                               int32_t b_km, int32_t a_f32, int32_t c_f32, int32_t epi, int32_t splitk, int32_t flags, float alpha,
                               int32_t accum, int32_t set, int32_t m_expect, int32_t cus, char* tag, int32_t tag_bytes, int32_t* splits);
+/* the host side of rsys_batch_upload (row_len == max_sequence_length) and rsys_batch_upload_trimmed (a shorter row_len) alone, on the
+ * host only: the check of batch `b` and the packing of columns [0, row_len) of its rows into the caller's buffer `stage` of
+ * stage_bytes bytes, exactly as an upload fills its staging buffer -- no model, no device, no HIP call.  limits = {max_rows,
+ * max_sequence_length, RoPE table positions (2 max_sequence_length in a model), V = vocab_0 + vocab_1, vocab_0, vocab_1, vocab_status,
+ * vocab_gender, vocab_source}.  offsets [30]: where each array starts in `stage`, in the order the layout places them -- time,
+ * userid, token_mask_ids, gender, source, matchedid, status, rating, progress, then label / weight / position of target 0 .. 5, then
+ * watch_mask, rating_mask and the token positions (2 p, 2 p + 1 per rope_input_pos p); an array the batch or the form does not have
+ * keeps its place and stays unwritten.  *total_bytes: the end of the last array; *distinct_ids: the distinct matchedid values >= 0 of
+ * the packed columns + 1.  A rejected batch (RSYS_ERR_ARG) writes nothing; a buffer below *total_bytes is RSYS_ERR_STATE. */
+int32_t rsys_debug_batch_pack(const rsys_batch* b, const int32_t limits[9], int32_t row_len, void* stage, int64_t stage_bytes,
+                              int64_t offsets[30], int64_t* total_bytes, int32_t* distinct_ids);
 /* attention fwd+bwd on caller-provided device buffers (T-typed): qkv [B*T][(H+2KV)*hd] post-RoPE, dO [B*T][H*hd],
  * uid/tm [B*T] int32 with 0 <= uid < 2^19 and 0 <= tm < 4096, rope tables [T][hd/2] f32; outputs O [B*T][H*hd], lse [B][H][T] f32,
  * dqkv [B*T][(H+2KV)*hd] (gradients w.r.t. the un-rotated q, k and v).  T a multiple of 8, T <= 4096 (64 tiles of 64 tokens: rows of

@@ -231,6 +231,8 @@ _SIGS = [
                                      C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, C.c_char_p, C.c_int32, C.POINTER(C.c_int32)]),
     ("rsys_debug_gemm_route", C.c_int32, [C.c_int32] * 4 + [C.c_int64] * 3 + [C.c_int32] * 7 + [C.c_float] + [C.c_int32] * 4
                                           + [C.c_char_p, C.c_int32, C.POINTER(C.c_int32)]),
+    ("rsys_debug_batch_pack", C.c_int32, [C.POINTER(rsys_batch), _P, C.c_int32, _P, C.c_int64, _P, C.POINTER(C.c_int64),
+                                          C.POINTER(C.c_int32)]),
     ("rsys_op_attention", C.c_int32, [C.c_int32] + [C.c_int32] * 5 + [_P] * 9),
     ("rsys_op_attention_ex", C.c_int32, [C.c_int32] + [C.c_int32] * 5 + [_P] * 10 + [C.c_int32, _P, _P, _P]),
     ("rsys_op_query_weights", C.c_int32, [_P, C.c_int64, _P, _P, _P, C.c_int32, _P, C.c_int32, _P, _P, C.c_int32, C.c_int32,

@@ -524,7 +524,7 @@ int32_t rsys_debug_get(rsys_model* h, const char* key, void* out, int64_t bytes)
   const int64_t N = (int64_t)m->cur_rows * m->S;
   const std::string k(key);
   const void* src = nullptr; int64_t n = 0;   // n: bytes
-  const BatchDev& b = m->bd;
+  const BatchDev& b = m->resident.bd;
   if (k == "masked.token_mask_ids") { src = b.m_tmid; n = N * 4; }
   else if (k == "masked.matchedid") { src = b.m_matchedid; n = N * 4; }
   else if (k == "masked.status") { src = b.m_status; n = N * 4; }

@@ -211,6 +211,25 @@ int32_t rsys_debug_gemm_route(int32_t dtype, int32_t M, int32_t N, int32_t K, in
   return RSYS_OK;
 }
 
+// the check and the packer of an upload (model_batch.hip), on the host only: the caller's limits and buffer in place of a model's
+int32_t rsys_debug_batch_pack(const rsys_batch* b, const int32_t limits[9], int32_t row_len, void* stage, int64_t stage_bytes,
+                              int64_t offsets[30], int64_t* total_bytes, int32_t* distinct_ids) {
+  ARG_CHECK(limits && stage && offsets && total_bytes && distinct_ids, "rsys_debug_batch_pack: null argument");
+  const BatchLimits lim{limits[0], limits[1], limits[2], limits[3], limits[4], limits[5], limits[6], limits[7], limits[8]};
+  std::vector<unsigned long long> id_seen;
+  int distinct = 0;
+  RC(batch_check(lim, b, row_len, &id_seen, &distinct));
+  const BlobLayout L = blob_layout((size_t)b->rows * row_len);
+  if ((int64_t)L.bytes > stage_bytes) { set_error("rsys_debug_batch_pack: staging buffer too small"); return RSYS_ERR_STATE; }
+  batch_pack(lim, b, row_len, L, (unsigned char*)stage);
+  int n = 0;
+  for (size_t at : {L.time, L.userid, L.tmid, L.gender, L.source, L.matchedid, L.status, L.rating, L.progress}) offsets[n++] = (int64_t)at;
+  for (int k = 0; k < 6; ++k) { offsets[n++] = (int64_t)L.label[k]; offsets[n++] = (int64_t)L.weight[k]; offsets[n++] = (int64_t)L.position[k]; }
+  offsets[n++] = (int64_t)L.wm; offsets[n++] = (int64_t)L.rm; offsets[n++] = (int64_t)L.rope;
+  *total_bytes = (int64_t)L.bytes; *distinct_ids = distinct;
+  return RSYS_OK;
+}
+
 int32_t rsys_op_f8_quantize(const void* src, int64_t ld_src, int32_t rows, int32_t cols, int32_t fmt, int32_t layout, int32_t seg_cols,
                             int32_t seg_rep, void* dst, int64_t ld_dst, float* amax_dev, float* desc_dev, const float* wamax_dev,
                             int32_t n_w, int32_t w_rep, int32_t desc_mode) {

@@ -7,8 +7,8 @@
 //    16-row interleaved in the flat parameter buffer) with RoPE and SwiGLU epilogues;
 //  * residual stream fp32, GEMM operands T (bf16 or fp32), fp32 accumulation;
 //  * every kernel of a step is enqueued on one HIP stream, no host sync inside a step.
-// This file: model set-up, parameter I/O, batch upload, the step's orchestration and inference.  The forward pass is in
-// model_forward.hip, the backward pass in model_backward.hip, clipping and AdamW in model_optim.hip (split in round 5, no behaviour change).
+// This file: model set-up, parameter I/O, the step's orchestration and inference.  Which batch is resident is in model_batch.hip, the
+// forward pass in model_forward.hip, the backward pass in model_backward.hip, clipping and AdamW in model_optim.hip.
 #include "model_internal.hpp"
 
 namespace rsys {
@@ -101,6 +101,7 @@ static inline int64_t internal_row(const TensorInfo& t, int64_t r) {
   return r;
 }
 
+static int model_build(Model* m, const rsys_config* cfg, int device);
 
 int model_create(const rsys_config* cfg, int device, Model** out) {
   ARG_CHECK(cfg != nullptr && out != nullptr, "null argument");
@@ -129,6 +130,14 @@ int model_create(const rsys_config* cfg, int device, Model** out) {
   ARG_CHECK(device >= 0 && device < ndev, "device index");
   HIP_CHECK(hipSetDevice(device));
   Model* m = new Model();
+  const int rc = model_build(m, cfg, device);
+  if (rc == RSYS_OK) *out = m; else model_destroy(m);   // (a failure frees the stream, every allocation so far and the pinned buffers)
+  return rc;
+}
+
+// The body of model_create on a fresh Model.  Any return but RSYS_OK leaves a partly built model for model_destroy.
+static int model_build(Model* m, const rsys_config* cfg, int device) {
+  const int hd = cfg->embed_dim / cfg->num_heads;
   m->cfg = *cfg; m->device = device;
   m->bf16_mode = cfg->dtype == RSYS_DTYPE_BF16 || cfg->dtype == RSYS_DTYPE_FP8;
   m->fp8 = cfg->dtype == RSYS_DTYPE_FP8;
@@ -142,7 +151,6 @@ int model_create(const rsys_config* cfg, int device, Model** out) {
   m->sharded = cfg->table_shard_world >= 1;
   m->sh_world = m->sharded ? cfg->table_shard_world : 1; m->sh_rank = m->sharded ? cfg->table_shard_rank : 0;
   if (m->sh_world > 16 || m->sh_rank < 0 || m->sh_rank >= m->sh_world || (m->sharded && cfg->finetune)) {
-    delete m;
     set_error("table_shard: rank must be in [0, world), world <= 16, and finetuning keeps the table replicated (it is frozen)");
     return RSYS_ERR_ARG;
   }
@@ -177,32 +185,24 @@ int model_create(const rsys_config* cfg, int device, Model** out) {
     HIP_CHECK(hipMemcpy(m->rope_cs, cs.data(), cs.size() * 4, hipMemcpyHostToDevice));
     m->rope_npos = m->Ta;
   }
-  // batch blob: 27 raw arrays + masked copies
+  // batch: the masked copies mask_tokens writes (the model's own), and two (blob, pinned staging) slots for the raw arrays of a batch of
+  // every row at full length (model_batch.hip points the resident batch's input arrays into the current slot's blob)
   {
-    size_t per_i = 4 * 6 + 8 + 4 * 2 + 18 * 4 /*raw*/ + 4 * 3 + 4 * 2 + 12 * 4 /*masked*/;
-    DALLOC(m->batch_blob, (size_t)N * per_i + 4096);
+    DALLOC(m->batch_blob, (size_t)N * (4 * 3 + 4 * 2 + 12 * 4) + 4096);
     unsigned char* p = (unsigned char*)m->batch_blob;
     auto carve = [&](size_t bytes) { void* r = p; p += (bytes + 15) / 16 * 16; return r; };
-    BatchDev& b = m->bd;
-    b.time = (const double*)carve(N * 8);
-    b.userid = (const int*)carve(N * 4); b.tmid = (const int*)carve(N * 4); b.gender = (const int*)carve(N * 4);
-    b.source = (const int*)carve(N * 4); b.matchedid = (const int*)carve(N * 4); b.status = (const int*)carve(N * 4);
-    b.rating = (const float*)carve(N * 4); b.progress = (const float*)carve(N * 4);
-    for (int k = 0; k < 6; ++k) { b.label[k] = (const float*)carve(N * 4); b.weight[k] = (const float*)carve(N * 4); b.position[k] = (const int*)carve(N * 4); }
+    BatchDev& b = m->resident.bd;
     b.m_tmid = (int*)carve(N * 4); b.m_matchedid = (int*)carve(N * 4); b.m_status = (int*)carve(N * 4);
     b.m_rating = (float*)carve(N * 4); b.m_progress = (float*)carve(N * 4);
     for (int k = 0; k < 4; ++k) { b.m_label[k] = (float*)carve(N * 4); b.m_weight[k] = (float*)carve(N * 4); b.m_position[k] = (int*)carve(N * 4); }
-    b.watch_mask = nullptr; b.rating_mask = nullptr; b.rope_pos = nullptr;
-    m->raw_bytes = (size_t)N * (4 * 6 + 8 + 4 * 2 + 18 * 4 + 2 + 8) + 64 * 32;   // raw arrays + the two masks + 2N positions + padding
-    DALLOC(m->raw_blob, m->raw_bytes);
-    HIP_CHECK(hipHostMalloc((void**)&m->h_stage, m->raw_bytes, hipHostMallocDefault));
-    m->slot_blob[0] = m->raw_blob; m->slot_stage[0] = m->h_stage;
-    DALLOC(m->slot_blob[1], m->raw_bytes);
-    HIP_CHECK(hipHostMalloc((void**)&m->slot_stage[1], m->raw_bytes, hipHostMallocDefault));
+    m->raw_bytes = blob_layout((size_t)N).bytes;
+    for (int i = 0; i < 2; ++i) {
+      DALLOC(m->slot_blob[i], m->raw_bytes);
+      HIP_CHECK(hipHostMalloc((void**)&m->slot_stage[i], m->raw_bytes, hipHostMallocDefault));
+    }
     HIP_CHECK(hipStreamCreateWithFlags(&m->copy_stream, hipStreamNonBlocking));
     HIP_CHECK(hipEventCreateWithFlags(&m->ev_copy_done, hipEventDisableTiming));
     for (int i = 0; i < 2; ++i) HIP_CHECK(hipEventCreateWithFlags(&m->ev_blob_free[i], hipEventDisableTiming));
-    m->d_wm = nullptr; m->d_rm = nullptr; m->d_rope_pos = nullptr;   // (placed in raw_blob per upload)
     DALLOC(m->tok_keys, (size_t)token_index_capacity((int)N) * 8); DALLOC(m->tok_skey, N * 4); DALLOC(m->tok_sidx, N * 4);
     DALLOC(m->scatter_slab, seg_scatter_slab_floats((int)N, m->D) * 4);
   }
@@ -359,15 +359,15 @@ int model_create(const rsys_config* cfg, int device, Model** out) {
     HIP_CHECK(hipMemcpy(m->f8_tile_job, tile_job.data(), tile_job.size() * 4, hipMemcpyHostToDevice));
     HIP_CHECK(hipMemcpy(m->f8_tile_first, tile_first.data(), tile_first.size() * 4, hipMemcpyHostToDevice));
   }
-  *out = m;
   return RSYS_OK;
 }
 
+// (also the end of a model_create that failed half-way: whatever was not built yet is null or empty)
 int model_destroy(Model* m) {
   if (!m) return RSYS_OK;
   if (m->loss_ring) { hipFree(m->loss_ring); m->loss_ring = nullptr; }
   hipSetDevice(m->device);
-  hipStreamSynchronize(m->stream);
+  if (m->stream) hipStreamSynchronize(m->stream);
   for (void* p : m->allocs) hipFree(p);
   m->rws.release();
   retrieve_tables_free(m);
@@ -378,27 +378,19 @@ int model_destroy(Model* m) {
   render_free(m);
   rank_cache_free(m);
   if (m->copy_stream) { hipStreamSynchronize(m->copy_stream); hipStreamDestroy(m->copy_stream); }
-  if (m->h_stage) hipHostFree(m->h_stage);
-  if (m->slot_stage[1]) hipHostFree(m->slot_stage[1]);
+  for (int i = 0; i < 2; ++i) if (m->slot_stage[i]) hipHostFree(m->slot_stage[i]);
   if (m->ev_copy_done) hipEventDestroy(m->ev_copy_done);
   for (int i = 0; i < 2; ++i) if (m->ev_blob_free[i]) hipEventDestroy(m->ev_blob_free[i]);
   if (m->h_counts) hipHostFree(m->h_counts);
   if (m->ev_counts) hipEventDestroy(m->ev_counts);
-  if (m->det_slab) hipFree(m->det_slab);
-  if (m->det_part) hipFree(m->det_part);
-  if (m->det_tmp) hipFree(m->det_tmp);
-  if (m->req_ids) hipFree(m->req_ids);
-  if (m->tok_Tall) hipFree(m->tok_Tall);
+  for (void* p : std::initializer_list<void*>{m->det_slab, m->det_part, m->det_tmp, m->req_ids, m->tok_Tall, m->d_umax, m->tok_Uall, m->tok_Pall, m->rows_xchg})
+    if (p) hipFree(p);
   if (m->h_umax) hipHostFree(m->h_umax);
-  if (m->d_umax) hipFree(m->d_umax);
   if (m->ev_umax) hipEventDestroy(m->ev_umax);
-  if (m->tok_Uall) hipFree(m->tok_Uall);
-  if (m->tok_Pall) hipFree(m->tok_Pall);
-  if (m->rows_xchg) hipFree(m->rows_xchg);
   for (auto& kv : m->dw_plans) gemm8p_group_plan_destroy(kv.second);
   for (auto e : m->timer.pool) hipEventDestroy(e);
   for (auto e : m->step_marks) hipEventDestroy(e);
-  hipStreamDestroy(m->stream);
+  if (m->stream) hipStreamDestroy(m->stream);
   delete m;
   return RSYS_OK;
 }
@@ -581,320 +573,6 @@ int model_param_io(Model* m, const char* name, float* out, const float* in, int6
   return RSYS_OK;
 }
 
-// Row-sharded table: which rows of which rank this batch reads.  Depends on the batch only (a watch-masked token reads
-// the mask row V instead of its item's row, and V is always part of the plan), so it is built once per upload:
-// distinct ids (sorted) -> contiguous runs per owner -> counts all-gathered -> id lists exchanged.  Every rank calls this
-// at the same point (it contains collectives).
-static int build_exchange_plan(Model* m, int N) {
-  const int W = m->sh_world;
-  hipStream_t s = m->stream;
-  ARG_CHECK(W == 1 || m->shard_comm != nullptr, "row-sharded table: call rsys_model_set_shard_comm before the first batch");
-  RC(launch_plan_unique(m->tok_skey, m->tok_sidx, N, m->V, m->u_slot, m->u_ids, m->u_tok, m->u_plan, s));
-  int* d_off = m->u_off; int* d_cnt = m->u_off + (W + 1); int* d_all = d_cnt + W;
-  RC(launch_plan_offsets(m->u_ids, m->u_plan, m->u_bound, W + 1, d_off, s));
-  int plan[2]; std::vector<int> off(W + 1), cnt(W), all((size_t)W * W);
-  HIP_CHECK(hipMemcpyAsync(plan, m->u_plan, 8, hipMemcpyDeviceToHost, s));
-  HIP_CHECK(hipMemcpyAsync(off.data(), d_off, (W + 1) * 4, hipMemcpyDeviceToHost, s));
-  HIP_CHECK(hipStreamSynchronize(s));
-  m->U = plan[0]; m->uV = plan[1];
-  ARG_CHECK(off[W] == m->U && m->U >= 1 && m->U <= N + 1, "exchange plan: inconsistent unique-id list");
-  for (int q = 0; q <= W; ++q) { m->need_off[q] = off[q]; m->need_offD[q] = (long long)off[q] * m->D; }
-  for (int q = 0; q < W; ++q) cnt[q] = off[q + 1] - off[q];
-  HIP_CHECK(hipMemcpyAsync(d_cnt, cnt.data(), W * 4, hipMemcpyHostToDevice, s));
-  RC(comm_all_gather(m->shard_comm, d_cnt, d_all, (size_t)W * 4, s));
-  HIP_CHECK(hipMemcpyAsync(all.data(), d_all, (size_t)W * W * 4, hipMemcpyDeviceToHost, s));
-  HIP_CHECK(hipStreamSynchronize(s));
-  long long acc = 0;
-  for (int q = 0; q < W; ++q) { m->serve_off[q] = acc; m->serve_offD[q] = acc * m->D; acc += all[(size_t)q * W + m->sh_rank]; }
-  m->serve_off[W] = acc; m->serve_offD[W] = acc * m->D; m->R = acc;
-  if (acc > m->req_cap) {
-    if (m->req_ids) HIP_CHECK(hipFree(m->req_ids));
-    if (m->rows_xchg) HIP_CHECK(hipFree(m->rows_xchg));
-    m->req_cap = acc + acc / 4 + 1024;
-    HIP_CHECK(hipMalloc((void**)&m->req_ids, (size_t)m->req_cap * 4));
-    HIP_CHECK(hipMalloc((void**)&m->rows_xchg, (size_t)m->req_cap * m->D * 4));
-  }
-  RC(comm_exchange(m->shard_comm, m->u_ids, m->need_off.data(), m->req_ids, m->serve_off.data(), 4, s));
-  HIP_CHECK(hipStreamSynchronize(s));
-  return RSYS_OK;
-}
-
-// Where the arrays of a batch of N interactions sit in a slot's blob, back to back at 64-byte steps: the one layout of uploaded
-// (batch_stage) and device-assembled (model_batch_device_begin) batches.
-struct BlobLayout {
-  size_t time, userid, tmid, gender, source, matchedid, status, rating, progress, label[6], weight[6], position[6], wm, rm, rope, bytes;
-};
-static BlobLayout blob_layout(size_t N) {
-  BlobLayout L{};
-  size_t off = 0;
-  auto place = [&](size_t bytes) { const size_t at = off; off += (bytes + 63) / 64 * 64; return at; };
-  L.time = place(N * 8);
-  L.userid = place(N * 4); L.tmid = place(N * 4); L.gender = place(N * 4); L.source = place(N * 4);
-  L.matchedid = place(N * 4); L.status = place(N * 4); L.rating = place(N * 4); L.progress = place(N * 4);
-  for (int k = 0; k < 6; ++k) { L.label[k] = place(N * 4); L.weight[k] = place(N * 4); L.position[k] = place(N * 4); }
-  L.wm = place(N); L.rm = place(N);
-  L.rope = place(2 * N * 4);
-  L.bytes = off;
-  return L;
-}
-// the device addresses of a layout's arrays in `blob` (the mask_tokens outputs and the sizes stay the model's own)
-static void blob_point(Model* m, unsigned char* blob, const BlobLayout& L, BatchDev& d, unsigned char** wm, unsigned char** rm, int** rope) {
-  d.time = (const double*)(blob + L.time);
-  d.userid = (const int*)(blob + L.userid); d.tmid = (const int*)(blob + L.tmid);
-  d.gender = (const int*)(blob + L.gender); d.source = (const int*)(blob + L.source);
-  d.matchedid = (const int*)(blob + L.matchedid); d.status = (const int*)(blob + L.status);
-  d.rating = (const float*)(blob + L.rating); d.progress = (const float*)(blob + L.progress);
-  for (int k = 0; k < 6; ++k) {
-    d.label[k] = (const float*)(blob + L.label[k]); d.weight[k] = (const float*)(blob + L.weight[k]); d.position[k] = (const int*)(blob + L.position[k]);
-  }
-  *wm = blob + L.wm; *rm = blob + L.rm; *rope = (int*)(blob + L.rope);
-}
-
-// Checks a host batch and packs it into staging buffer `slot` (pinned); `d` and the flag outputs receive the device addresses the
-// arrays will have in that slot's blob.  Index paths are checked on the host BEFORE anything is written.
-struct StagedBatch { BatchDev bd; bool has_masks = false, has_rope_pos = false; unsigned char *d_wm = nullptr, *d_rm = nullptr; int* d_rope_pos = nullptr; size_t bytes = 0;
-                     int distinct_ids = 0; };   // split table reduce: distinct matchedid values of the batch + 1 (the mask row): an upper bound of its token-row list
-static int batch_stage(Model* m, const rsys_batch* b, int slot, StagedBatch& out) {
-  ARG_CHECK(b != nullptr, "null batch");
-  ARG_CHECK(b->rows >= 1 && b->rows <= m->rows_max, "batch rows must be in [1, max_rows]");
-  const size_t N = (size_t)b->rows * m->Sa;
-  ARG_CHECK(b->userid && b->token_mask_ids && b->gender && b->source && b->matchedid && b->status && b->time && b->rating && b->progress,
-            "batch arrays must not be null");
-  for (int k = 0; k < 6; ++k) {
-    if (k % 3 == 2 && b->label[k] == nullptr) continue;  // status targets are never used by the losses (model.py:448-449)
-    ARG_CHECK(b->label[k] && b->weight[k] && b->position[k], "target arrays must not be null");
-  }
-  ARG_CHECK(b->watch_mask == nullptr || b->rating_mask != nullptr, "watch_mask and rating_mask come together");
-  // index paths are checked on the host BEFORE anything is copied: a rejected batch leaves the resident one untouched
-  for (size_t i = 0; i < N; ++i) {
-    int id = b->matchedid[i];
-    ARG_CHECK(id >= -1 && id < m->V, "matchedid out of range");
-    // the attention kernels compare tokens through the key userid << 12 | token_mask_ids (attention_maps.hip: token_key)
-    ARG_CHECK(b->userid[i] >= 0 && b->userid[i] < (1 << 19), "userid must be in [0, 2^19)");
-    ARG_CHECK(b->token_mask_ids[i] >= 0 && b->token_mask_ids[i] < 4096, "token_mask_ids must be in [0, 4096)");
-    ARG_CHECK(b->status[i] >= -1 && b->status[i] <= m->cfg.vocab_status, "status out of range");
-    ARG_CHECK(b->gender[i] >= -1 && b->gender[i] <= m->cfg.vocab_gender, "gender out of range");
-    ARG_CHECK(b->source[i] >= -1 && b->source[i] <= m->cfg.vocab_source, "source out of range");
-    ARG_CHECK(b->position[0][i] >= 0 && b->position[0][i] < m->V0 && b->position[1][i] >= 0 && b->position[1][i] < m->V0,
-              "manga target position out of range");
-    ARG_CHECK(b->position[3][i] >= 0 && b->position[3][i] < m->V1 && b->position[4][i] >= 0 && b->position[4][i] < m->V1,
-              "anime target position out of range");
-  }
-  if (m->split_table) {   // (one pass over the ids with a bitmap of the table's rows: ~30 us for 32 K ids, on the thread that packs the batch anyway)
-    m->id_seen.assign(((size_t)m->V + 64) / 64, 0ull);
-    int distinct = 1;       // the mask row V: mask_tokens sends the masked events there (model.py:451)
-    for (size_t i = 0; i < N; ++i) {
-      const int id = b->matchedid[i] < 0 ? m->V : b->matchedid[i];
-      unsigned long long& wd = m->id_seen[(size_t)id >> 6];
-      const unsigned long long bit = 1ull << (id & 63);
-      if (!(wd & bit)) { wd |= bit; if (id != m->V) ++distinct; }
-    }
-    out.distinct_ids = distinct;
-  }
-  std::vector<int> pos;
-  if (b->rope_input_pos != nullptr) {
-    // model.py:470-476: token positions 2p, 2p+1
-    pos.resize(2 * N);
-    for (size_t i = 0; i < N; ++i) { pos[2 * i] = 2 * b->rope_input_pos[i]; pos[2 * i + 1] = 2 * b->rope_input_pos[i] + 1; }
-    for (size_t i = 0; i < 2 * N; ++i) ARG_CHECK(pos[i] >= 0 && pos[i] < m->Ta, "rope_input_pos out of range");
-  }
-  // pack (pinned staging) -> one H2D -> the device arrays sit back to back in the slot's blob
-  unsigned char* blob = m->slot_blob[slot]; unsigned char* stage = m->slot_stage[slot];
-  const BlobLayout L = blob_layout(N);
-  if (L.bytes > m->raw_bytes) { set_error("batch upload: staging buffer too small"); return RSYS_ERR_STATE; }
-  auto put = [&](size_t at, const void* src, size_t bytes) { if (src != nullptr) memcpy(stage + at, src, bytes); };
-  put(L.time, b->time, N * 8);
-  put(L.userid, b->userid, N * 4); put(L.tmid, b->token_mask_ids, N * 4); put(L.gender, b->gender, N * 4); put(L.source, b->source, N * 4);
-  put(L.matchedid, b->matchedid, N * 4); put(L.status, b->status, N * 4); put(L.rating, b->rating, N * 4); put(L.progress, b->progress, N * 4);
-  for (int k = 0; k < 6; ++k) {   // (status targets may be absent: their slots stay unwritten, nothing reads them)
-    put(L.label[k], b->label[k], N * 4); put(L.weight[k], b->weight[k], N * 4); put(L.position[k], b->position[k], N * 4);
-  }
-  put(L.wm, b->watch_mask, N); put(L.rm, b->rating_mask, N);
-  out.has_masks = b->watch_mask != nullptr;
-  out.has_rope_pos = b->rope_input_pos != nullptr;
-  put(L.rope, out.has_rope_pos ? pos.data() : nullptr, 2 * N * 4);
-  BatchDev d = m->bd;    // (the mask_tokens outputs and the sizes are the model's own; only the input arrays move)
-  blob_point(m, blob, L, d, &out.d_wm, &out.d_rm, &out.d_rope_pos);
-  const size_t off = L.bytes;
-  out.bd = d; out.bytes = off;
-  return RSYS_OK;
-}
-
-int model_batch_upload(Model* m, const rsys_batch* b) {
-  HIP_CHECK(hipSetDevice(m->device));
-  hipStream_t s = m->stream;
-  // an explicit upload supersedes a prefetched batch.  Its copy may still be reading the OTHER slot's staging buffer on the copy stream:
-  // wait for it here, so that the next prefetch (which skips its own wait when nothing is pending) never re-packs a buffer under a copy
-  if (m->pending.valid) HIP_CHECK(hipEventSynchronize(m->ev_copy_done));
-  m->pending.valid = false;
-  // No wait before packing: the previous upload synchronised after ITS copy, so the staging buffer is free, and the copy below is
-  // ordered on the stream behind the kernels that still read the old batch -- the host packs while the GPU finishes the previous
-  // step's optimizer pass.  (A prefetch into this slot's staging is complete too: model_batch_swap waited for its copy.)
-  StagedBatch st;
-  RC(batch_stage(m, b, m->cur_slot, st));
-  const size_t N = (size_t)b->rows * m->Sa;
-  set_row_len(m, m->Sa);
-  m->cur_rows = 0;   // (a failing copy below must not leave a half-written batch marked as resident)
-  m->bd = st.bd;
-  BatchDev& d = m->bd;
-  m->has_masks = st.has_masks; m->d_wm = st.d_wm; m->d_rm = st.d_rm;
-  m->has_rope_pos = st.has_rope_pos; m->d_rope_pos = st.d_rope_pos;
-  m->u_bound_host = st.distinct_ids;
-  HIP_CHECK(hipMemcpyAsync(m->slot_blob[m->cur_slot], m->slot_stage[m->cur_slot], st.bytes, hipMemcpyHostToDevice, s));
-  // inverted index "table row -> its tokens" for the backward's segmented scatter: depends on the batch only; built here for
-  // the row-sharded table (its exchange plan needs it now), else by the first backward over this batch (an inference or
-  // evaluation pass never needs it)
-  m->tok_index_valid = false;
-  m->split_plan_valid = false;
-  if (m->sharded) { RC(launch_token_index_build(d.matchedid, (int)N, m->V, m->tok_keys, m->tok_skey, m->tok_sidx, s)); m->tok_index_valid = true; }
-  HIP_CHECK(hipStreamSynchronize(s));
-  if (m->sharded) RC(build_exchange_plan(m, (int)N));
-  m->cur_rows = b->rows;
-  return RSYS_OK;
-}
-
-// A trimmed batch holds no targets and no masks: every pass that reads them refuses it and touches nothing.
-int check_not_trimmed(const Model* m) {
-  if (!batch_trimmed(m)) return RSYS_OK;
-  set_error("a trimmed batch is inference-only (rsys_batch_upload_trimmed): upload the full rows for this call");
-  return RSYS_ERR_STATE;
-}
-
-// rsys_batch_upload_trimmed.  The caller's arrays keep the row stride Sa; columns [0, row_len) of every row are checked,
-// packed at stride row_len and copied, and the resident batch then has rows of row_len interactions: every kernel of the inference
-// forward is launched over rows * 2 row_len tokens.  Exact because the dropped columns are padding (userid 0), which no live token
-// attends (the mask's first predicate is the user id) and every other operator of the trunk is token-local.  Targets and masks are not
-// read; their blob places stay unwritten and nothing of an inference forward reads them.
-int model_batch_upload_trimmed(Model* m, const rsys_batch* b, int row_len) {
-  ARG_CHECK(b != nullptr, "null batch");
-  ARG_CHECK(row_len >= 4 && row_len <= m->Sa && row_len % 4 == 0, "trimmed upload: row_len % 4 == 0 and 4 <= row_len <= max_sequence_length");
-  ARG_CHECK(!m->fp8, "trimmed upload: fp32 and bf16 models only (the fp8 trunk's tensor-wise amax sees every token)");
-  ARG_CHECK(!m->sharded, "trimmed upload: a model with a replicated table");
-  if (row_len == m->Sa) return model_batch_upload(m, b);
-  ARG_CHECK(b->rows >= 1 && b->rows <= m->rows_max, "batch rows must be in [1, max_rows]");
-  ARG_CHECK(b->userid && b->token_mask_ids && b->gender && b->source && b->matchedid && b->status && b->time && b->rating && b->progress,
-            "batch arrays must not be null");
-  const int rows = b->rows, Sa = m->Sa;
-  // index paths and the dead suffix are checked on the host BEFORE anything is written: a rejected batch leaves the resident one untouched
-  for (int r = 0; r < rows; ++r) {
-    const size_t r0 = (size_t)r * Sa;
-    for (int j = 0; j < row_len; ++j) {
-      const size_t i = r0 + j;
-      ARG_CHECK(b->matchedid[i] >= -1 && b->matchedid[i] < m->V, "matchedid out of range");
-      ARG_CHECK(b->userid[i] >= 0 && b->userid[i] < (1 << 19), "userid must be in [0, 2^19)");
-      ARG_CHECK(b->token_mask_ids[i] >= 0 && b->token_mask_ids[i] < 4096, "token_mask_ids must be in [0, 4096)");
-      ARG_CHECK(b->status[i] >= -1 && b->status[i] <= m->cfg.vocab_status, "status out of range");
-      ARG_CHECK(b->gender[i] >= -1 && b->gender[i] <= m->cfg.vocab_gender, "gender out of range");
-      ARG_CHECK(b->source[i] >= -1 && b->source[i] <= m->cfg.vocab_source, "source out of range");
-      if (b->rope_input_pos) ARG_CHECK(b->rope_input_pos[i] >= 0 && 2 * b->rope_input_pos[i] + 1 < m->Ta, "rope_input_pos out of range");   // (a position, not a column: the table's bound, as rsys_batch_upload)
-    }
-    for (int j = row_len; j < Sa; ++j) ARG_CHECK(b->userid[r0 + j] == 0, "trimmed upload: a live event (userid != 0) at or behind column row_len");
-  }
-  HIP_CHECK(hipSetDevice(m->device));
-  hipStream_t s = m->stream;
-  if (m->pending.valid) HIP_CHECK(hipEventSynchronize(m->ev_copy_done));   // (as model_batch_upload: an explicit upload supersedes a prefetched batch)
-  m->pending.valid = false;
-  const size_t N = (size_t)rows * row_len;
-  unsigned char* blob = m->slot_blob[m->cur_slot]; unsigned char* stage = m->slot_stage[m->cur_slot];
-  const BlobLayout L = blob_layout(N);
-  if (L.bytes > m->raw_bytes) { set_error("batch upload: staging buffer too small"); return RSYS_ERR_STATE; }
-  auto put = [&](size_t at, const void* src, size_t esz) {   // columns [0, row_len) of every row, stride Sa -> row_len
-    for (int r = 0; r < rows; ++r) memcpy(stage + at + (size_t)r * row_len * esz, (const unsigned char*)src + (size_t)r * Sa * esz, (size_t)row_len * esz);
-  };
-  put(L.time, b->time, 8);
-  put(L.userid, b->userid, 4); put(L.tmid, b->token_mask_ids, 4); put(L.gender, b->gender, 4); put(L.source, b->source, 4);
-  put(L.matchedid, b->matchedid, 4); put(L.status, b->status, 4); put(L.rating, b->rating, 4); put(L.progress, b->progress, 4);
-  if (b->rope_input_pos) {   // model.py:470-476: token positions 2p, 2p+1
-    int* pos = (int*)(stage + L.rope);
-    for (int r = 0; r < rows; ++r)
-      for (int j = 0; j < row_len; ++j) {
-        const int p = b->rope_input_pos[(size_t)r * Sa + j];
-        pos[2 * ((size_t)r * row_len + j)] = 2 * p; pos[2 * ((size_t)r * row_len + j) + 1] = 2 * p + 1;
-      }
-  }
-  m->cur_rows = 0;   // (a failing copy below must not leave a half-written batch marked as resident)
-  BatchDev d = m->bd;
-  blob_point(m, blob, L, d, &m->d_wm, &m->d_rm, &m->d_rope_pos);
-  m->bd = d;
-  m->has_masks = false; m->has_rope_pos = b->rope_input_pos != nullptr;
-  m->u_bound_host = 0; m->tok_index_valid = false; m->split_plan_valid = false;
-  HIP_CHECK(hipMemcpyAsync(blob, stage, L.bytes, hipMemcpyHostToDevice, s));
-  HIP_CHECK(hipStreamSynchronize(s));
-  set_row_len(m, row_len);
-  m->cur_rows = rows;
-  return RSYS_OK;
-}
-
-// The resident batch as device arrays for a kernel to fill (rsys_render_request's ranking rows): the layout of batch_stage for `rows`
-// rows in the current slot's blob, nothing copied.  Everything enqueued so far that reads the blob runs before the kernel that fills it
-// (same stream); the slot's staging buffer is not touched.
-int model_batch_device_begin(Model* m, int rows, BatchDevRows* out, int row_len) {
-  ARG_CHECK(rows >= 1 && rows <= m->rows_max, "batch rows must be in [1, max_rows]");
-  if (row_len == 0) row_len = m->Sa;
-  ARG_CHECK(row_len >= 4 && row_len <= m->Sa && row_len % 4 == 0, "device-assembled batch: row_len % 4 == 0 and 4 <= row_len <= max_sequence_length");
-  ARG_CHECK(!m->sharded, "device-assembled batch: replicated table only");
-  HIP_CHECK(hipSetDevice(m->device));
-  if (m->pending.valid) HIP_CHECK(hipEventSynchronize(m->ev_copy_done));
-  m->pending.valid = false;
-  const BlobLayout L = blob_layout((size_t)rows * row_len);
-  if (L.bytes > m->raw_bytes) { set_error("device-assembled batch: blob too small"); return RSYS_ERR_STATE; }
-  set_row_len(m, row_len);
-  BatchDev d = m->bd;
-  blob_point(m, m->slot_blob[m->cur_slot], L, d, &m->d_wm, &m->d_rm, &out->rope_pos);
-  out->time = (double*)d.time; out->userid = (int*)d.userid; out->tmid = (int*)d.tmid; out->gender = (int*)d.gender;
-  out->source = (int*)d.source; out->matchedid = (int*)d.matchedid; out->status = (int*)d.status; out->rating = (float*)d.rating;
-  out->progress = (float*)d.progress;
-  m->bd = d;
-  m->has_masks = false; m->has_rope_pos = true; m->d_rope_pos = out->rope_pos;
-  m->tok_index_valid = false; m->split_plan_valid = false; m->u_bound_host = 0;
-  m->cur_rows = rows;
-  return RSYS_OK;
-}
-
-// The NEXT batch beside the running step: checked and packed into the other slot's staging buffer by the calling thread while the GPU
-// works, copied on a stream of its own.  Nothing of the resident batch changes until model_batch_swap.
-int model_batch_prefetch(Model* m, const rsys_batch* b) {
-  ARG_CHECK(!m->sharded, "batch prefetch: the row-sharded table builds its exchange plan at upload (use rsys_batch_upload)");
-  HIP_CHECK(hipSetDevice(m->device));
-  const int slot = m->cur_slot ^ 1;
-  if (m->pending.valid) HIP_CHECK(hipEventSynchronize(m->ev_copy_done));   // (a prefetch that was never swapped in: its copy still reads the staging buffer)
-  m->pending.valid = false;
-  StagedBatch st;
-  RC(batch_stage(m, b, slot, st));
-  // the slot's blob was the resident batch two swaps ago: the kernels that read it were enqueued before ev_blob_free[slot]
-  if (m->blob_free_valid[slot]) HIP_CHECK(hipStreamWaitEvent(m->copy_stream, m->ev_blob_free[slot], 0));
-  HIP_CHECK(hipMemcpyAsync(m->slot_blob[slot], m->slot_stage[slot], st.bytes, hipMemcpyHostToDevice, m->copy_stream));
-  HIP_CHECK(hipEventRecord(m->ev_copy_done, m->copy_stream));
-  m->pending.valid = true; m->pending.bd = st.bd; m->pending.rows = b->rows;
-  m->pending.has_masks = st.has_masks; m->pending.has_rope_pos = st.has_rope_pos;
-  m->pending.d_wm = st.d_wm; m->pending.d_rm = st.d_rm; m->pending.d_rope_pos = st.d_rope_pos;
-  m->pending.distinct_ids = st.distinct_ids;
-  return RSYS_OK;
-}
-
-int model_batch_swap(Model* m) {
-  ARG_CHECK(m->pending.valid, "batch swap: no prefetched batch (rsys_batch_prefetch first)");
-  HIP_CHECK(hipSetDevice(m->device));
-  // everything enqueued so far may still read the resident batch's blob: the next prefetch into it waits for this point
-  HIP_CHECK(hipEventRecord(m->ev_blob_free[m->cur_slot], m->stream));
-  m->blob_free_valid[m->cur_slot] = true;
-  // The copy is waited for on the HOST as well as on the stream: the next prefetch re-packs this slot's staging buffer without a wait
-  // (as uploads always have), and by now -- a whole step after the copy was issued -- the wait returns at once.
-  HIP_CHECK(hipStreamWaitEvent(m->stream, m->ev_copy_done, 0));
-  HIP_CHECK(hipEventSynchronize(m->ev_copy_done));
-  m->cur_slot ^= 1;
-  m->bd = m->pending.bd;
-  m->has_masks = m->pending.has_masks; m->d_wm = m->pending.d_wm; m->d_rm = m->pending.d_rm;
-  m->has_rope_pos = m->pending.has_rope_pos; m->d_rope_pos = m->pending.d_rope_pos;
-  m->cur_rows = m->pending.rows;
-  set_row_len(m, m->Sa);
-  m->u_bound_host = m->pending.distinct_ids;
-  m->tok_index_valid = false;
-  m->split_plan_valid = false;
-  m->pending.valid = false;
-  return RSYS_OK;
-}
-
 // the partial-sum scratch of the fixed-order reductions (DetScope hands it to the kernels' launchers), allocated once
 int model_ensure_det_scratch(Model* m) {
   HIP_CHECK(hipSetDevice(m->device));
@@ -918,8 +596,7 @@ template <typename T>
 static int forward_backward_t(Model* m, int evaluate, const float task_w[4], float grad_scale, uint64_t seed, uint64_t step,
                               const int* d_row_task = nullptr /* rsys_adapter_forward_backward: one task per batch row */) {
   const int rows = m->cur_rows, N = rows * m->S;
-  BatchDev b = m->bd; b.N = N; b.rows = rows; b.S = m->S;
-  if (m->has_masks) { b.watch_mask = m->d_wm; b.rating_mask = m->d_rm; }
+  BatchDev b = m->resident.bd; b.N = N; b.rows = rows; b.S = m->S;
   m->cur_seed = seed; m->cur_step = step;
   if (d_row_task && m->bank_packed) RC(launch_mask_tokens_tiles(b, d_row_task, m->stream));   // (packed rows: the vector is the [rows][ceil(S / 32)] tile map)
   else if (d_row_task) RC(launch_mask_tokens_rows(b, d_row_task, m->stream));
@@ -1015,7 +692,7 @@ template <typename T>
 int infer_trunk(Model* m) {
   const int N = m->cur_rows * m->S;
   hipStream_t s = m->stream;
-  BatchDev b = m->bd;
+  BatchDev b = m->resident.bd;
   m->f8_tcopies = false;
   HIP_CHECK(hipMemcpyAsync(b.m_tmid, b.tmid, N * 4, hipMemcpyDeviceToDevice, s));
   HIP_CHECK(hipMemcpyAsync(b.m_matchedid, b.matchedid, N * 4, hipMemcpyDeviceToDevice, s));

@@ -91,6 +91,23 @@ struct RankTables;       // rank_request.hip
 struct AdapterBank;      // adapter_bank.hip
 struct RenderState;      // render_request.hip
 
+// A batch as the device holds it, the only description of one outside the kernels (model_batch.hip): bd's input arrays point into a
+// slot's blob; bd.watch_mask / rating_mask / rope_pos are set when the batch has them and null when not; the mask_tokens outputs are the
+// model's own.  rows of row_len interactions (row_len < max_sequence_length: a trimmed, inference-only batch); distinct_ids: the
+// distinct matchedid values + 1 (the mask row), an upper bound of the split table reduce's token-row list (0: not counted).
+struct ResidentBatch { BatchDev bd{}; int rows = 0, row_len = 0, distinct_ids = 0; };
+struct BatchLimits { int rows_max, Sa, Ta, V, V0, V1, vocab_status, vocab_gender, vocab_source; };   // what a host batch is checked against
+// Where the arrays of a batch of N interactions sit in a slot's blob and staging buffer, back to back at 64-byte steps: the one layout
+// of uploaded and device-assembled (model_batch_device_begin) batches.
+struct BlobLayout { size_t time, userid, tmid, gender, source, matchedid, status, rating, progress, label[6], weight[6], position[6], wm, rm, rope, bytes; };
+BlobLayout blob_layout(size_t N);
+// Host only, no Model and no HIP call.  batch_check: columns [0, row_len) of every row of b (row stride lim.Sa) against the limits;
+// row_len == lim.Sa is the ordinary upload (targets and masks too), a shorter one the trimmed form (neither, and userid 0 from column
+// row_len on).  id_seen (null: not counted): scratch bitmap of the table's rows for *distinct_ids; nothing else is written.
+// batch_pack: those columns of a checked batch into `stage` at layout L = blob_layout(rows * row_len).
+int batch_check(const BatchLimits& lim, const rsys_batch* b, int row_len, std::vector<unsigned long long>* id_seen, int* distinct_ids);
+void batch_pack(const BatchLimits& lim, const rsys_batch* b, int row_len, const BlobLayout& L, unsigned char* stage);
+
 struct Model {
   rsys_config cfg;
   int device = 0;
@@ -113,11 +130,11 @@ struct Model {
   int *tok_Uall = nullptr, *tok_Pall = nullptr;
   int64_t tok_cap = 0;               // rows of tok_T and ids of u_ids: rows_max * S + 1
   // The tail gathers max_r U_r rows per rank instead of tok_cap (round 6).  A rank knows an upper bound of its own U on the HOST as soon
-  // as the batch is staged (distinct matchedid values + the mask row: u_bound_host, counted by batch_stage); when the reduce is armed
+  // as the batch is staged (distinct matchedid values + the mask row: u_bound_host, counted by batch_check); when the reduce is armed
   // (rsys_set_grad_sync) the bounds' maximum over the ranks is formed by a one-float all-reduce at the head of the communicator's stream
   // and copied to pinned memory (h_umax[1], event ev_umax): by the time the tail is enqueued it has been there for a whole backward.
   int u_bound_host = 0;
-  std::vector<unsigned long long> id_seen;   // batch_stage's bitmap of table rows
+  std::vector<unsigned long long> id_seen;   // batch_check's bitmap of table rows
   float* h_umax = nullptr; float* d_umax = nullptr; hipEvent_t ev_umax = nullptr; bool umax_pending = false;
   int64_t tok_all_rows = 0;          // rows per rank tok_Tall / tok_Uall are sized for
   int tok_all_world = 0;             // ranks tok_Tall / tok_Uall / tok_Pall are sized for
@@ -222,37 +239,30 @@ struct Model {
   float *rope_cos = nullptr, *rope_sin = nullptr;
   int rope_npos = 0;
   std::vector<void*> allocs;
-  // batch
-  BatchDev bd;
-  void* batch_blob = nullptr;
-  // one upload = one copy: the batch's arrays are packed back to back (for the rows it has) in a pinned staging buffer and
-  // land in `raw_blob` with a single H2D; the BatchDev pointers are re-pointed into it per upload
-  unsigned char* raw_blob = nullptr; unsigned char* h_stage = nullptr; size_t raw_bytes = 0;
-  // A second (staging, blob) pair for rsys_batch_prefetch: the NEXT batch is checked, packed and copied on its own stream while the
-  // current step still runs (the reference's DataLoader + non_blocking to_device overlap, train.py:162-165,178-184); rsys_batch_swap
-  // makes it the resident batch.  slot_blob[0] / slot_stage[0] are raw_blob / h_stage.
-  unsigned char* slot_blob[2] = {nullptr, nullptr}; unsigned char* slot_stage[2] = {nullptr, nullptr};
+  // batch (model_batch.hip).  One upload = one copy: the batch's arrays are packed back to back (for the rows it has) in a slot's
+  // pinned staging buffer and land in the slot's blob with a single H2D; the ResidentBatch describes where.  Two (staging, blob) slots:
+  // rsys_batch_prefetch checks, packs and copies the NEXT batch into the other slot on its own stream while the current step still runs
+  // (the reference's DataLoader + non_blocking to_device overlap, train.py:162-165,178-184); rsys_batch_swap makes it the resident batch.
+  ResidentBatch resident, pending;   // resident: written by batch_install only; pending: the prefetched batch while pending_valid
+  bool pending_valid = false;
+  int cur_rows = 0;                  // resident.rows once the batch's copy has landed, 0 without a resident batch
+  unsigned char* slot_blob[2] = {nullptr, nullptr}; unsigned char* slot_stage[2] = {nullptr, nullptr}; size_t raw_bytes = 0;   // raw_bytes: of each
   int cur_slot = 0;
   hipStream_t copy_stream = nullptr;
   hipEvent_t ev_copy_done = nullptr;     // the pending batch's H2D copy (copy_stream)
   hipEvent_t ev_blob_free[2] = {nullptr, nullptr};   // recorded on `stream` when slot i stops being the resident batch: its kernels are all enqueued before
   bool blob_free_valid[2] = {false, false};
-  struct PendingBatch { bool valid = false; BatchDev bd; int rows = 0; bool has_masks = false, has_rope_pos = false; int distinct_ids = 0;
-                        unsigned char *d_wm = nullptr, *d_rm = nullptr; int* d_rope_pos = nullptr; } pending;
-  bool tok_index_valid = false;
+  void* batch_blob = nullptr;        // the mask_tokens outputs (resident.bd.m_*), the model's own whatever batch is resident
+  bool tok_index_valid = false;      // the token index of the resident batch (scatter / exchange plan) has been built
   // deterministic mode (rsys_model_set_deterministic): every float sum of the step has a fixed order -- split-K partial tiles go
   // to det_slab and are added in split order, the reduction kernels write per-workgroup partials to det_part (kernels.hpp
   // DetScratch) -- so a step is bitwise reproducible (replicated or row-sharded table, full or sampled soft-max)
   bool deterministic = false;
   float* det_slab = nullptr; long long det_slab_floats = 0;
   float* det_part = nullptr; long long det_part_floats = 0;
-  float* det_tmp = nullptr; long long det_tmp_floats = 0;   // the token index of the resident batch (scatter / exchange plan) has been built
-  bool has_masks = false, has_rope_pos = false;
-  int cur_rows = 0;
+  float* det_tmp = nullptr; long long det_tmp_floats = 0;
   // token index of the resident batch (scatter.hip): sorted (item id, token) pairs + the partial-sum slab of the scatter
   unsigned long long* tok_keys = nullptr; int *tok_skey = nullptr, *tok_sidx = nullptr; float* scatter_slab = nullptr;
-  unsigned char *d_wm = nullptr, *d_rm = nullptr;
-  int* d_rope_pos = nullptr;
   // activations (void* = T-typed)
   void* feat; float* x0; int *uid_t, *tm_t;
   AttnMaps maps, maps_p;   // the attention tile maps of the token order and of the selected-first order (below)

@@ -170,7 +170,7 @@ int backward_trunk(Model* m) {
   const int D = m->D, Ip = m->Ip, hd = m->hd, rows = m->cur_rows;
   const int N = rows * m->S, NT = 2 * N;
   hipStream_t s = m->stream;
-  const int* rpos = m->has_rope_pos ? m->d_rope_pos : nullptr;
+  const int* rpos = m->resident.bd.rope_pos;
   float* gx = m->gxa;   // gradient w.r.t. the current layer's output (fp32 residual stream)
   float* gx_other = m->gxb;
   T* gxt = AT<T>(m->gxa_t);      // the same gradient as a GEMM operand (T)
@@ -291,7 +291,7 @@ int backward_trunk(Model* m) {
   if (trunk_frozen(m)) return RSYS_OK;   // embeddings are frozen (model.py:361-369)
   // gx = gradient w.r.t. the interleaved input embeddings (even rows: items, odd rows: actions)
   tic(m, "phase_embed_bwd");
-  BatchDev b = m->bd; b.N = N; b.rows = rows; b.S = m->S;
+  BatchDev b = m->resident.bd; b.N = N; b.rows = rows; b.S = m->S;
   tic(m, "hbm_scatter", 12.0 * D * N);   // bytes: one gradient row read + one table-gradient row read-modify-written per interaction
   {
     const bool atomic_ab = sw().scatter_atomic != 0;   // A/B measurement against the float-atomic form only

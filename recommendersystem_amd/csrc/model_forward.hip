@@ -146,8 +146,7 @@ int forward_trunk(Model* m) {
   const int N = rows * m->S, NT = 2 * N;   // (S, T: the resident batch's row length, model.hpp)
   m->fwd_tokens = NT;
   hipStream_t s = m->stream;
-  BatchDev b = m->bd; b.N = N; b.rows = rows; b.S = m->S;
-  b.rope_pos = m->has_rope_pos ? m->d_rope_pos : nullptr;
+  BatchDev b = m->resident.bd; b.N = N; b.rows = rows; b.S = m->S;
   const int* rpos = b.rope_pos;
   // fused item table F = E + Meta Wp^T + bp
   tic(m, "phase_embed");
@@ -386,7 +385,7 @@ int sharded_counts_early(Model* m, bool train, const float tw[4]) {
     const int ti = 2 * t2, medium = t2;
     int len, col0, lrow;
     shard_medium_range(m, medium, &len, &col0, &lrow);
-    RC(launch_vp_meta(m->idx[ti], m->bd.m_label[ti], m->bd.m_weight[ti], m->bd.m_position[ti], m->stats + 2 * ti, m->npos + ti,
+    RC(launch_vp_meta(m->idx[ti], m->resident.bd.m_label[ti], m->resident.bd.m_weight[ti], m->resident.bd.m_position[ti], m->stats + 2 * ti, m->npos + ti,
                       train ? tw[ti] : 0.f, KB, KBmax, m->metaOwn, s));
     RC(comm_all_gather(m->shard_comm, m->metaOwn, m->metaAllT[t2], ((size_t)KBmax * 4 + 4) * 4, s));
     // (the row payload EwAll is not there yet: this pass is for the counts and the packed meta only)
@@ -512,8 +511,8 @@ int heads(Model* m, int evaluate, const float tw[4]) {
         RC(gemm<T>(m, "gemm_logits", p));
       }
       tic(m, "ce");
-      RC(launch_ce_fwd_bwd<T>(AT<T>(m->logits), m->ldl, KB, Vm, m->idx[ti], m->bd.m_label[ti], m->bd.m_weight[ti],
-                              m->bd.m_position[ti], st, np, train ? tw[ti] : 0.f, m->loss_acc + 3 * ti, s));
+      RC(launch_ce_fwd_bwd<T>(AT<T>(m->logits), m->ldl, KB, Vm, m->idx[ti], m->resident.bd.m_label[ti], m->resident.bd.m_weight[ti],
+                              m->resident.bd.m_position[ti], st, np, train ? tw[ti] : 0.f, m->loss_acc + 3 * ti, s));
       toc(m);
       if (bwd) {
         {
@@ -539,7 +538,7 @@ int heads(Model* m, int evaluate, const float tw[4]) {
         RC(gemm<T>(m, "gemm_rating_fwd", p));
       }
       RC(launch_rating_tail<T>(AT<T>(m->z), AT<T>(m->hact), KB, D, m->P + m->o_r2w, m->P + m->o_r2b, m->idx[ti],
-                               m->bd.m_label[ti], m->bd.m_weight[ti], st, m->cfg.rating_mean, bwd ? tw[ti] : 0.f,
+                               m->resident.bd.m_label[ti], m->resident.bd.m_weight[ti], st, m->cfg.rating_mean, bwd ? tw[ti] : 0.f,
                                bwd ? 0 : 1, m->loss_acc + 3 * ti, small_grad(m, m->o_r2w), small_grad(m, m->o_r2b), small_grad(m, m->o_r0b), s, np));
       if (bwd) {
         if (!trunk_frozen(m)) {
@@ -567,7 +566,7 @@ int heads(Model* m, int evaluate, const float tw[4]) {
 int select_positions_all(Model* m) {
   const int N = m->cur_rows * m->S, KB = m->K * m->cur_rows;
   const float* ws[4]; int* is[4]; float* sts[4]; int* nps[4];
-  for (int ti = 0; ti < 4; ++ti) { ws[ti] = m->bd.m_weight[ti]; is[ti] = m->idx[ti]; sts[ti] = m->stats + 2 * ti; nps[ti] = m->npos + ti; }
+  for (int ti = 0; ti < 4; ++ti) { ws[ti] = m->resident.bd.m_weight[ti]; is[ti] = m->idx[ti]; sts[ti] = m->stats + 2 * ti; nps[ti] = m->npos + ti; }
   hipStream_t s = m->stream;
   const bool chunked_on = sw().select_chunked != 0;   // (A/B)
   if (chunked_on && N >= 4096) RC(launch_select_positions_chunked(4, ws, N, KB, is, sts, nps, m->sel_scratch, s));

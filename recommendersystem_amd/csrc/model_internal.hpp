@@ -1,4 +1,4 @@
-// Shared by the translation units of the training step (model.hip: set-up, batches, orchestration, inference; model_forward.hip;
+// Shared by the translation units of the training step (model.hip: set-up, orchestration, inference; model_batch.hip; model_forward.hip;
 // model_backward.hip; model_optim.hip -- one file until round 5) and of the request paths behind them: the timing brackets, the GEMM
 // builders and the wrapper that picks split counts, a layer's AttnParams, the fp8 product table, the tile owners of packed rows, and
 // the declarations of what one unit calls in another (the step's passes; the score buffers, group plans and list checks of the
@@ -25,8 +25,8 @@ static inline int64_t pad8(int64_t n) { return (n + 7) / 8 * 8; }
 static int dalloc(Model* m, void** p, size_t bytes) {
   bytes = (bytes + 255) / 256 * 256;
   HIP_CHECK(hipMalloc(p, bytes));
-  HIP_CHECK(hipMemset(*p, 0, bytes));
   m->allocs.push_back(*p);
+  HIP_CHECK(hipMemset(*p, 0, bytes));
   return RSYS_OK;
 }
 #define DALLOC(ptr, bytes) RC(dalloc(m, (void**)&(ptr), (size_t)(bytes)))

@@ -168,6 +168,15 @@ static int rc_check_call(Model* m, const int32_t* a, const int32_t* b) {
   return RSYS_OK;
 }
 
+// The rows' RoPE positions are the caller's for the length of a cache call: the resident batch runs at d_pos while the scope lives and
+// has its own rope_input_pos (or none) back on every way out.  Nothing else of the call is undone here.
+struct RopePosScope {
+  Model* m; const int* saved;
+  RopePosScope(Model* m_, const int* d_pos) : m(m_), saved(m_->resident.bd.rope_pos) { m->resident.bd.rope_pos = d_pos; }
+  ~RopePosScope() { m->resident.bd.rope_pos = saved; }
+  RopePosScope(const RopePosScope&) = delete;
+};
+
 // The store pass over the resident batch, whose rows were uploaded (rsys_rank_cache_store) or assembled on the device
 // (rsys_render_request_full).  `tab` (host, [3 max_rows]) receives the rows' {slot | n_hist | 0} table and is read by a stream-ordered
 // copy, as row_adapter is: both stay as they are until the stream has passed this call.  No host wait on success.
@@ -237,11 +246,9 @@ int rank_cache_candidates_rows(Model* m, const int32_t* row_adapter, const int32
   if (row_adapter) RC(adapter_bind_rows(m, row_adapter));
   std::fill(tab, tab + (size_t)3 * m->rows_max, 0);
   for (int r = 0; r < rows; ++r) { tab[r] = slot[r]; tab[m->rows_max + r] = m->rc_nhist[slot[r]]; tab[2 * m->rows_max + r] = n_cand[r]; }
-  // the rows' positions are the caller's for the length of this call: the resident batch's rope_input_pos stays what it is
-  int* const saved_pos = m->d_rope_pos; const bool saved_has = m->has_rope_pos;
+  RopePosScope pos(m, d_pos);   // (the resident batch's rope_input_pos stays what it is)
   auto run = [&]() -> int {
     HIP_CHECK(hipMemcpyAsync(m->rc_rows, tab, (size_t)3 * m->rows_max * 4, hipMemcpyHostToDevice, m->stream));
-    m->d_rope_pos = d_pos; m->has_rope_pos = true;
     m->rc_mode = 2;
     const float* f = nullptr;
     RC(m->bf16_mode ? infer_rows_device<bf16>(m, 1, d_sel, ntok, d_out, &f) : infer_rows_device<float>(m, 1, d_sel, ntok, d_out, &f));
@@ -249,7 +256,6 @@ int rank_cache_candidates_rows(Model* m, const int32_t* row_adapter, const int32
   };
   const int rc = run();
   m->rc_mode = 0;
-  m->d_rope_pos = saved_pos; m->has_rope_pos = saved_has;
   adapter_unbind_rows(m);
   if (rc != RSYS_OK) (void)hipStreamSynchronize(m->stream);
   return rc;
@@ -328,17 +334,15 @@ int rank_cache_store_packed_rows(Model* m, const int32_t* seg_adapter, int n_seg
   }
   HIP_CHECK(hipSetDevice(m->device));
   RC(rc_bind_segments(m, seg_adapter, n_seg, used));
-  int* const saved_pos = m->d_rope_pos; const bool saved_has = m->has_rope_pos;
+  RopePosScope pos(m, d_pos);
   auto run = [&]() -> int {
     HIP_CHECK(hipMemcpyAsync(m->rc_seg, seg, (size_t)4 * n_seg * 4, hipMemcpyHostToDevice, m->stream));
-    m->d_rope_pos = d_pos; m->has_rope_pos = true;
     m->rc_mode = 1; m->rc_nseg = n_seg;
     RC(m->bf16_mode ? infer_trunk<bf16>(m) : infer_trunk<float>(m));
     return RSYS_OK;
   };
   const int rc = run();
   m->rc_mode = 0; m->rc_nseg = 0;
-  m->d_rope_pos = saved_pos; m->has_rope_pos = saved_has;
   adapter_unbind_rows(m);
   if (rc != RSYS_OK) (void)hipStreamSynchronize(m->stream);   // (the copy above reads the caller's host array)
   // (a failed pass may have written some layers of the slots: they no longer hold a history)
@@ -404,13 +408,12 @@ int model_rank_cache_candidates_packed(Model* m, const int32_t* seg_adapter, int
   RC(rc_bind_segments(m, seg_adapter, n_seg, used));
   int* const d_pos = m->rc_rows + 3 * m->rows_max;
   int* const d_sel = (int*)m->gf;   // (as rsys_infer_select: room for every token of the batch)
-  int* const saved_pos = m->d_rope_pos; const bool saved_has = m->has_rope_pos;
+  RopePosScope rows_pos(m, d_pos);
   hipStream_t s = m->stream;
   auto run = [&]() -> int {
     HIP_CHECK(hipMemcpyAsync(m->rc_seg, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, s));
     HIP_CHECK(hipMemcpyAsync(d_pos, pos.data(), pos.size() * 4, hipMemcpyHostToDevice, s));
     HIP_CHECK(hipMemcpyAsync(d_sel, sel.data(), sel.size() * 4, hipMemcpyHostToDevice, s));
-    m->d_rope_pos = d_pos; m->has_rope_pos = true;
     m->rc_mode = 2; m->rc_nseg = n_seg;
     const float* f = nullptr;
     RC(m->bf16_mode ? infer_rows_device<bf16>(m, 1, d_sel, ntok, m->delta, &f) : infer_rows_device<float>(m, 1, d_sel, ntok, m->delta, &f));
@@ -419,7 +422,6 @@ int model_rank_cache_candidates_packed(Model* m, const int32_t* seg_adapter, int
   };
   const int rc = run();
   m->rc_mode = 0; m->rc_nseg = 0;
-  m->d_rope_pos = saved_pos; m->has_rope_pos = saved_has;
   adapter_unbind_rows(m);
   if (rc != RSYS_OK) { (void)hipStreamSynchronize(s); return rc; }   // (the copies above read this call's host vectors)
   HIP_CHECK(hipMemcpy(out, m->delta, (size_t)ntok * 4, hipMemcpyDeviceToHost));   // (out is written only by a call that succeeded)

@@ -503,7 +503,7 @@ struct Render : RenderArgs {
       RC(rl == S ? model_batch_upload(m, &b) : model_batch_upload_trimmed(m, &b, rl));
       R->note_forward(0, nr, rl);
       if (full) {   // the rows' history columns stay on the device: the store rows are cut from them, nothing of a history is uploaded twice
-        const BatchDev& bd = m->bd;   // (rows of rl columns; the kept rows keep the stride S, their columns behind rl are never read: n_hist < rl by the choice of rl above)
+        const BatchDev& bd = m->resident.bd;   // (rows of rl columns; the kept rows keep the stride S, their columns behind rl are never read: n_hist < rl by the choice of rl above)
         auto keep_cols = [&](void* dst, const void* src, size_t esz) {
           if (rl == S) return hipMemcpyAsync(dst, src, (size_t)nr * S * esz, hipMemcpyDeviceToDevice, s);   // (full rows: one contiguous copy)
           return hipMemcpy2DAsync(dst, (size_t)S * esz, src, (size_t)rl * esz, (size_t)rl * esz, (size_t)nr, hipMemcpyDeviceToDevice, s);
@@ -612,7 +612,7 @@ struct Render : RenderArgs {
       R->note_forward(0, nr, rl);
       if (full) {   // the users' history columns back to one kept row each, [n_users][S]: what the store rows are cut from
         HIP_CHECK(hipMemcpyAsync(d_segs, t.segs.data(), (size_t)nseg * sizeof(SegDesc), hipMemcpyHostToDevice, s));
-        const BatchDev& bd = m->bd;
+        const BatchDev& bd = m->resident.bd;
         const SegSrc br{bd.time, bd.userid, bd.gender, bd.source, bd.matchedid, bd.status, bd.rating, bd.progress};
         tic(m, "render_unpack_rows");
         unpack_rows_kernel<<<nseg, RN_THREADS, 0, s>>>(d_segs, br, rl, hist);
